@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- processor-step throughput of the MI355X-native MeshGraphNets engine.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by torch.distributed.run, one rank per GPU (RCCL), RANK/LOCAL_RANK/WORLD_SIZE from env.
   One "step" = one pass of the hot path over the mesh = `mps` (15) message-passing steps of the processor
   (mgn_processor_steps_dev; at N > 1 the staged edge/node kernels + RCCL halo all-to-all-v between them).
   W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + device synchronise on both
-  sides; time = MAX over ranks; rank 0 prints ONE JSON line.
+  sides; time = MAX over ranks; rank 0 prints ONE JSON line (`ms_per_step` = time / K).
+  A plain run does nothing else.  --dump-outputs DIR writes what the last timed step left (node and edge latents, a
+  fixed seeded sample of rows) as DIR/<name>.npy.  --full adds everything that is not the headline: the median of
+  individually bracketed passes, per-kernel times and the roofline, the finiteness check, the secondary workloads
+  and the CPU baseline (--no-secondary / --no-cpu-baseline leave those out again).
 
 Metric (BASELINE.json): processor-step edges/s (+ nodes/s) = E * mps * K / time  -- whole job, all GPUs.
 Workload at N = 1: M-1M, the 1000x1000 jittered-grid triangulation (N = 1 000 000 nodes, E = 5 992 002
 directed edges, L = 128, 15 steps, fp32) -- BASELINE.json configs[3], the config the multi-GPU metric is
-quoted on; it fits one GPU (5 GB).  configs[1] (cylinder_flow-sized M-cyl) is timed too and reported in the
-same line under "secondary" (it is latency-bound: ~12k edges).  At N > 1 the SAME mesh is edge-cut over
+quoted on; it fits one GPU (5 GB).  Under --full, configs[1] (cylinder_flow-sized M-cyl) is timed too and reported
+in the same line under "secondary" (it is latency-bound: ~12k edges).  At N > 1 the SAME mesh is edge-cut over
 the N GPUs ("scaling": "strong").  Latents are N(0,1) generated on device, weights Glorot-uniform
 (random init: no datasets/checkpoints exist offline) -- "data": "synthetic".
 """
@@ -25,10 +29,11 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_F32_MFMA_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: dense f32-input MFMA peak
+PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X microarchitecture guide: dense f32-input MFMA peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # same guide: dense bf16 MFMA peak (the headline figures with 2:1 sparsity are not used)
 PEAK_HBM_GBPS = 8000.0         # same guide: HBM3E ~8 TB/s
 L, MPS, FN, FE, O = 128, 15, 9, 3, 2
+DUMP_ROWS = 32768              # --dump-outputs: rows sampled per array (2 arrays x 32768 x 128 x 4 B = 32 MB at most)
 
 
 def glorot_params(seed=1234, Fn=None, Fe=None, O_=None, Fe2=None):
@@ -242,6 +247,32 @@ def time_single(eng, steps, warmup, sync):
     return dt, kernel_split(eng, max(1, min(steps, 3)), sync)
 
 
+def dump_rows(n, seed):
+    """the rows --dump-outputs writes of an array of n rows: all of them up to DUMP_ROWS, else a fixed seeded sample (ascending)"""
+    import numpy as np
+    if n <= DUMP_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(eng, out_dir, rank, staged):
+    """What the timed path leaves its caller after the last timed step: the node latents [N][L] and edge latents [E][L]
+    (mgn_latents_export: rows in the input's node ids and edge-list positions, fp32 also in bf16 storage), a fixed seeded sample
+    of rows of each (dump_rows).  At N > 1 every rank exports the rows it owns (zeros elsewhere) and a sum over the ranks
+    completes the sample (each row is owned once: the sum is exact); rank 0 writes DIR/node_latents.npy, DIR/edge_latents.npy."""
+    import numpy as np
+    v, e = eng.latents_export()
+    vs, es = v[dump_rows(v.shape[0], 1)], e[dump_rows(e.shape[0], 2)]
+    del v, e
+    if staged:
+        vs = eng.comm_allreduce(vs.ravel(), "sum").astype(np.float32).reshape(vs.shape)
+        es = eng.comm_allreduce(es.ravel(), "sum").astype(np.float32).reshape(es.shape)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "node_latents.npy"), np.ascontiguousarray(vs, np.float32))
+        np.save(os.path.join(out_dir, "edge_latents.npy"), np.ascontiguousarray(es, np.float32))
+
+
 def rccl_loadable():
     """can this process bind an RCCL library (the engine binds librccl at run time, MGN_RCCL_LIB or the loader's search path)"""
     import ctypes
@@ -338,8 +369,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)   # >= 20 timed runs after >= 5 warm-ups
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--nx", type=int, default=1000, help="M-1M grid side (default 1000 -> 1M nodes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (node / edge latents, a fixed seeded row sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: median pass, per-kernel times and roofline, finiteness, "
+                         "secondary workloads, CPU baseline")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32 = the reference's precision (headline); bf16 = BASELINE.json configs[2] precision")
     ap.add_argument("--force-staged", action="store_true",
@@ -395,46 +431,26 @@ def main():
     dt = time_clean(eng, args.steps, args.warmup, barrier_sync)
     if staged:
         dt = float(eng.comm_allreduce([dt], "max")[0])      # MAX over ranks
-    t_med, t_min = time_each(eng, max(args.steps, 3), barrier_sync)
-    if staged:
-        t_med = float(eng.comm_allreduce([t_med], "max")[0])
-        setup_all = eng.comm_allreduce([t_setup if q == rank else 0.0 for q in range(world)], "sum")
-    prof = kernel_split(eng, max(1, min(args.steps, 5)), barrier_sync)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, staged)  # (before any further pass changes the latents)
+    if args.full:
+        t_med, t_min = time_each(eng, max(args.steps, 3), barrier_sync)
+        if staged:
+            t_med = float(eng.comm_allreduce([t_med], "max")[0])
+            setup_all = eng.comm_allreduce([t_setup if q == rank else 0.0 for q in range(world)], "sum")
+        prof = kernel_split(eng, max(1, min(args.steps, 5)), barrier_sync)
 
-    chk = eng.latents_checksum()
-    finite = all(np.isfinite(v) for v in chk.values())
-    if staged:
-        finite = bool(eng.comm_allreduce([0.0 if finite else 1.0], "max")[0] == 0.0)
+        chk = eng.latents_checksum()
+        finite = all(np.isfinite(v) for v in chk.values())
+        if staged:
+            finite = bool(eng.comm_allreduce([0.0 if finite else 1.0], "max")[0] == 0.0)
 
     if rank == 0:
         bf = args.dtype == "bf16"
-        # a split edge step (N > 1: interior tiles while the halo is in flight, boundary tiles after) is two launches
-        t_edge = (prof["edge_step"]["avg_ms"] + (prof["edge_boundary"]["avg_ms"] if prof["edge_boundary"]["count"] else 0.0)) * 1e-3
-        t_node = prof["node_step"]["avg_ms"] * 1e-3
         e_loc, n_loc = eng.e_local, eng.n_own
         t_step = dt / (args.steps * MPS)
-        # MFMA flops the kernels EXECUTE per pass (layer 1 of the edge MLP is factored into per-node P / Q): edge kernel 3 chunks
-        # per edge; node side 4 chunks per node per step + 2 for every projection (15 per pass: 14 next-step + the initial one)
-        exec_flops_pass = MPS * flops_edge_kernel(E) + (MPS * 4 + MPS * 2) * 2.0 * L * L * N
-        node_flops_pass = (MPS * 4 + MPS * 2) * 2.0 * L * L * n_loc
-        node_launches = max(prof["node_step"]["count"], 1) / max(1, min(args.steps, 5))
-        edge_kernel = "k_edge_bf16" if bf else "k_edge_step<4,2>"
-        if bf:
-            # bf16 storage: the step is HBM-bound.  Algorithmic bytes of the edge kernel: e latents R + W,
-            # two index streams, one pass over the P, Q rows it gathers and the AGG rows it writes
-            edge_bytes = 2.0 * L * 2 * e_loc + 8.0 * e_loc + 3.0 * 2.0 * L * n_loc
-            ach = edge_bytes / t_edge / 1e9 if t_edge > 0 else 0.0
-            traffic, tsrc = committed_traffic(["k_edge_bf16"], "bf16") if (world == 1 and args.nx == 1000) else (None, None)
-            roof = {"bound": "hbm", "kernel": "k_edge_bf16 (fused gather + edge MLP + LayerNorm + residual + segmented scatter, bf16 storage)",
-                    "achieved": ach, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBPS,
-                    "bytes_per_launch": edge_bytes, "bytes_kind": "algorithmic: 2 L (2 E) latents R+W + 8 E indices + 3 x 2 L N (P, Q rows read once, AGG rows written)",
-                    "avg_launch_ms": t_edge * 1e3, "launches": prof["edge_step"]["count"], "traffic": traffic, "traffic_source": tsrc}
-            bytes_step = 2.0 * L * (2 * E + 2 * N) + 8.0 * E
-            roof["processor_step"] = {"bound": "hbm", "algorithmic_bytes_per_step": bytes_step, "achieved": bytes_step / t_step / 1e9,
-                                      "peak": PEAK_HBM_GBPS * world, "unit": "GB/s", "frac": bytes_step / t_step / 1e9 / (PEAK_HBM_GBPS * world),
-                                      "note": "SURVEY.md 8(d) compulsory bytes at 2-byte storage / wall time per step",
-                                      "mfma_TFLOPs_executed": exec_flops_pass / MPS / t_step / 1e12, "mfma_peak_bf16_dense": 2500.0}
-        else:
+        split_mode = products = 0
+        if not bf:
             import ctypes
             lib = mgn_amd.load()
             lib.mgn_debug_fp32_split.restype = ctypes.c_int
@@ -454,84 +470,110 @@ def main():
             # piece products per fp32 product of the family that ran: 6 (three bf16 pieces), 3 (two fp16 pieces), 0 = fp32 MFMA
             products = {7: 6, 8: 6, 12: 6, 13: 3, 14: 3, 15: 3, 16: 3, 17: 3}.get(fam, 0)
             split_mode = split_mode if products else 0
-            comp = (1024.0 + 8.0) * e_loc + 3.0 * 512.0 * n_loc
-            alg_bytes = (1024.0 + 8.0 + 85.0) * e_loc
-            common = {"avg_launch_ms": t_edge * 1e3, "launches": prof["edge_step"]["count"],
-                      "traffic_unit": "bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE); algorithmic = 1117 B/edge",
-                      "algorithmic_bytes_per_launch": alg_bytes,
-                      # what THIS kernel has to move at least, given the factored design: e latents R + W, index streams, and one
-                      # pass over the P, Q rows it gathers and the AGG rows it writes (3 x N x 512 B); gather re-reads come on top
-                      "kernel_compulsory_bytes_per_launch": comp}
-            if products:
-                # fp32 storage, every L x L product as `products` exact 16-bit piece products, fp32 accumulation (csrc/split.hip).  Two
-                # roofs: the dense 16-bit MFMA peak with the flops the kernel EXECUTES, and HBM with SURVEY 8(d)'s algorithmic bytes;
-                # the line's `bound` is whichever floor is the longer time for this kernel.
-                kname = FAMILY[fam].split("<")[0].split(" ")[0]
-                fl = products * flops_edge_kernel(e_loc)
-                ach = fl / t_edge / 1e12 if t_edge > 0 else 0.0
-                ach_b = alg_bytes / t_edge / 1e9 if t_edge > 0 else 0.0
-                traffic, tsrc = committed_traffic([kname + "<"]) if (world == 1 and args.nx == 1000) else (None, None)
-                pieces = ("two fp16 pieces after a power-of-two scaling per weight chunk and per activation row, three piece products"
-                          if products == 3 else "three bf16 pieces, six piece products")
-                mfma_roof = {"achieved": ach, "peak": PEAK_BF16_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_MFMA_TFLOPS,
-                             "flops_per_launch": fl, "floor_ms": fl / (PEAK_BF16_MFMA_TFLOPS * 1e12) * 1e3,
-                             "flops_kind": f"16-bit MFMA flops executed by this kernel: {products} x 98 304 per edge (layer 1 is factored: the "
-                                           "v_s / v_r blocks run per node); against the dense bf16 / fp16 peak"}
-                hbm_roof = {"achieved": ach_b, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": ach_b / PEAK_HBM_GBPS,
-                            "bytes_per_launch": alg_bytes, "floor_ms": alg_bytes / (PEAK_HBM_GBPS * 1e9) * 1e3,
-                            "bytes_kind": "SURVEY.md 8(d) algorithmic bytes of the edge step: 1 024 B of e latents R + W + 8 B of indices + "
-                                          "512 N / E B of aggregates per edge"}
-                hbm_binds = hbm_roof["floor_ms"] > mfma_roof["floor_ms"]
-                bind, other = (hbm_roof, mfma_roof) if hbm_binds else (mfma_roof, hbm_roof)
-                roof = {"bound": "hbm" if hbm_binds else "mfma",
-                        "kernel": kname + f" (fused gather + edge MLP + LayerNorm + residual + segmented scatter; fp32 operands as {pieces}, "
-                        "fp32 accumulate)",
-                        **{k: bind[k] for k in ("achieved", "peak", "unit", "frac")},
-                        "binding_roof": bind, ("mfma_roof" if hbm_binds else "hbm_roof"): other,
-                        "bound_note": "the roof whose floor is the longer time for this kernel (both are given): with three piece products the "
-                                      "matrix floor (0.71 ms on M-1M) falls below the HBM floor (0.84 ms)" if hbm_binds else
-                                      "matrix floor above the HBM floor",
-                        "fp32_equivalent_TFLOPs": flops_edge_kernel(e_loc) / t_edge / 1e12 if t_edge > 0 else 0.0,
-                        "fp32_equivalent_note": "the same launch counted as the fp32 products it replaces (98 304 flop per edge): what an fp32-MFMA "
-                                                "kernel would have to sustain (its peak: 157.3)",
-                        "traffic": traffic, "traffic_source": tsrc, **common}
-                ex = products * exec_flops_pass / MPS
-                bytes_step = 4.0 * L * (2 * E + 2 * N) + 8.0 * E
-                step_m = {"executed_flops_per_step": ex, "achieved": ex / t_step / 1e12, "peak": PEAK_BF16_MFMA_TFLOPS * world,
-                          "unit": "TFLOP/s", "frac": ex / t_step / 1e12 / (PEAK_BF16_MFMA_TFLOPS * world)}
-                step_h = {"algorithmic_bytes_per_step": bytes_step, "achieved": bytes_step / t_step / 1e9, "peak": PEAK_HBM_GBPS * world,
-                          "unit": "GB/s", "frac": bytes_step / t_step / 1e9 / (PEAK_HBM_GBPS * world)}
-                sb, so_ = (step_h, step_m) if hbm_binds else (step_m, step_h)
-                roof["processor_step"] = {
-                    "bound": "hbm" if hbm_binds else "mfma", **sb, ("mfma_roof" if hbm_binds else "hbm_roof"): so_,
-                    "note": f"whole step: 16-bit MFMA flops executed ({products} x (98 304 E + 196 608 N)) and SURVEY.md 8(d) bytes "
-                            "(1 024 (E + N) + 8 E) over the wall time per step",
-                    "fp32_equivalent_TFLOPs": exec_flops_pass / MPS / t_step / 1e12,
-                    "algorithmic_equivalent_TFLOPs": flops_algorithmic(E, N) / t_step / 1e12,
-                    "algorithmic_equivalent_note": "SURVEY.md 8(d) flops of the UN-factored fp32 algorithm (163 840 E + 131 072 N) over the same "
-                                                   "time: a speed-up of the design, not a fraction of any peak"}
+        if args.full:
+            # a split edge step (N > 1: interior tiles while the halo is in flight, boundary tiles after) is two launches
+            t_edge = (prof["edge_step"]["avg_ms"] + (prof["edge_boundary"]["avg_ms"] if prof["edge_boundary"]["count"] else 0.0)) * 1e-3
+            t_node = prof["node_step"]["avg_ms"] * 1e-3
+            # MFMA flops the kernels EXECUTE per pass (layer 1 of the edge MLP is factored into per-node P / Q): edge kernel 3 chunks
+            # per edge; node side 4 chunks per node per step + 2 for every projection (15 per pass: 14 next-step + the initial one)
+            exec_flops_pass = MPS * flops_edge_kernel(E) + (MPS * 4 + MPS * 2) * 2.0 * L * L * N
+            node_flops_pass = (MPS * 4 + MPS * 2) * 2.0 * L * L * n_loc
+            node_launches = max(prof["node_step"]["count"], 1) / max(1, min(args.steps, 5))
+            edge_kernel = "k_edge_bf16" if bf else "k_edge_step<4,2>"
+            if bf:
+                # bf16 storage: the step is HBM-bound.  Algorithmic bytes of the edge kernel: e latents R + W,
+                # two index streams, one pass over the P, Q rows it gathers and the AGG rows it writes
+                edge_bytes = 2.0 * L * 2 * e_loc + 8.0 * e_loc + 3.0 * 2.0 * L * n_loc
+                ach = edge_bytes / t_edge / 1e9 if t_edge > 0 else 0.0
+                traffic, tsrc = committed_traffic(["k_edge_bf16"], "bf16") if (world == 1 and args.nx == 1000) else (None, None)
+                roof = {"bound": "hbm", "kernel": "k_edge_bf16 (fused gather + edge MLP + LayerNorm + residual + segmented scatter, bf16 storage)",
+                        "achieved": ach, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBPS,
+                        "bytes_per_launch": edge_bytes, "bytes_kind": "algorithmic: 2 L (2 E) latents R+W + 8 E indices + 3 x 2 L N (P, Q rows read once, AGG rows written)",
+                        "avg_launch_ms": t_edge * 1e3, "launches": prof["edge_step"]["count"], "traffic": traffic, "traffic_source": tsrc}
+                bytes_step = 2.0 * L * (2 * E + 2 * N) + 8.0 * E
+                roof["processor_step"] = {"bound": "hbm", "algorithmic_bytes_per_step": bytes_step, "achieved": bytes_step / t_step / 1e9,
+                                          "peak": PEAK_HBM_GBPS * world, "unit": "GB/s", "frac": bytes_step / t_step / 1e9 / (PEAK_HBM_GBPS * world),
+                                          "note": "SURVEY.md 8(d) compulsory bytes at 2-byte storage / wall time per step",
+                                          "mfma_TFLOPs_executed": exec_flops_pass / MPS / t_step / 1e12, "mfma_peak_bf16_dense": 2500.0}
             else:
-                ach = flops_edge_kernel(e_loc) / t_edge / 1e12 if t_edge > 0 else 0.0
-                traffic, tsrc = committed_traffic(["k_edge_step<4, 2"]) if (world == 1 and args.nx == 1000) else (None, None)
-                roof = {"bound": "mfma", "kernel": FAMILY.get(fam, "k_edge_step<4,2>") + " (fused gather + edge MLP + LayerNorm + residual + segmented scatter; "
-                        "fp32 MFMA)",
-                        "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_F32_MFMA_TFLOPS,
-                        "flops_per_launch": flops_edge_kernel(e_loc), "flops_kind": "MFMA flops executed by this kernel (98 304 per edge; "
-                        "layer 1 is factored so the v_s/v_r blocks run per node in k_node_step)",
-                        "traffic": traffic, "traffic_source": tsrc, **common}
-                roof["processor_step"] = {
-                    "bound": "mfma", "executed_flops_per_step": exec_flops_pass / MPS, "achieved": exec_flops_pass / MPS / t_step / 1e12,
-                    "peak": PEAK_F32_MFMA_TFLOPS * world, "unit": "TFLOP/s", "frac": exec_flops_pass / MPS / t_step / 1e12 / (PEAK_F32_MFMA_TFLOPS * world),
-                    "note": "MFMA flops the kernels execute (edge 98 304 E; node side 196 608 N incl. the P / Q projection) / wall time per step",
-                    "algorithmic_equivalent_TFLOPs": flops_algorithmic(E, N) / t_step / 1e12,
-                    "algorithmic_equivalent_note": "SURVEY.md 8(d) flops of the UN-factored algorithm (163 840 E + 131 072 N) over the same time: "
-                                                   "a speed-up of the factored design, not a fraction of any peak"}
-        roof["kernel_timing"] = "separate pass after the timed region: HIP event pairs per launch on the launch stream (mgn_profile_enable)"
-        roof["node_side"] = {"avg_launch_ms": t_node * 1e3, "launches": prof["node_step"]["count"],
-                             "achieved_TFLOPs_fp32_equivalent": node_flops_pass / max(node_launches, 1) / t_node / 1e12 if t_node > 0 else 0.0,
-                             "note": "node MLP + P / Q projection per event group; flops counted as fp32 products (x 6 executed on the split path)"}
-        if prof["halo"]["count"]:
-            roof["halo_pack_ms"] = prof["halo"]["avg_ms"]
+                comp = (1024.0 + 8.0) * e_loc + 3.0 * 512.0 * n_loc
+                alg_bytes = (1024.0 + 8.0 + 85.0) * e_loc
+                common = {"avg_launch_ms": t_edge * 1e3, "launches": prof["edge_step"]["count"],
+                          "traffic_unit": "bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE); algorithmic = 1117 B/edge",
+                          "algorithmic_bytes_per_launch": alg_bytes,
+                          # what THIS kernel has to move at least, given the factored design: e latents R + W, index streams, and one
+                          # pass over the P, Q rows it gathers and the AGG rows it writes (3 x N x 512 B); gather re-reads come on top
+                          "kernel_compulsory_bytes_per_launch": comp}
+                if products:
+                    # fp32 storage, every L x L product as `products` exact 16-bit piece products, fp32 accumulation (csrc/split.hip).  Two
+                    # roofs: the dense 16-bit MFMA peak with the flops the kernel EXECUTES, and HBM with SURVEY 8(d)'s algorithmic bytes;
+                    # the line's `bound` is whichever floor is the longer time for this kernel.
+                    kname = FAMILY[fam].split("<")[0].split(" ")[0]
+                    fl = products * flops_edge_kernel(e_loc)
+                    ach = fl / t_edge / 1e12 if t_edge > 0 else 0.0
+                    ach_b = alg_bytes / t_edge / 1e9 if t_edge > 0 else 0.0
+                    traffic, tsrc = committed_traffic([kname + "<"]) if (world == 1 and args.nx == 1000) else (None, None)
+                    pieces = ("two fp16 pieces after a power-of-two scaling per weight chunk and per activation row, three piece products"
+                              if products == 3 else "three bf16 pieces, six piece products")
+                    mfma_roof = {"achieved": ach, "peak": PEAK_BF16_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_MFMA_TFLOPS,
+                                 "flops_per_launch": fl, "floor_ms": fl / (PEAK_BF16_MFMA_TFLOPS * 1e12) * 1e3,
+                                 "flops_kind": f"16-bit MFMA flops executed by this kernel: {products} x 98 304 per edge (layer 1 is factored: the "
+                                               "v_s / v_r blocks run per node); against the dense bf16 / fp16 peak"}
+                    hbm_roof = {"achieved": ach_b, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": ach_b / PEAK_HBM_GBPS,
+                                "bytes_per_launch": alg_bytes, "floor_ms": alg_bytes / (PEAK_HBM_GBPS * 1e9) * 1e3,
+                                "bytes_kind": "SURVEY.md 8(d) algorithmic bytes of the edge step: 1 024 B of e latents R + W + 8 B of indices + "
+                                              "512 N / E B of aggregates per edge"}
+                    hbm_binds = hbm_roof["floor_ms"] > mfma_roof["floor_ms"]
+                    bind, other = (hbm_roof, mfma_roof) if hbm_binds else (mfma_roof, hbm_roof)
+                    roof = {"bound": "hbm" if hbm_binds else "mfma",
+                            "kernel": kname + f" (fused gather + edge MLP + LayerNorm + residual + segmented scatter; fp32 operands as {pieces}, "
+                            "fp32 accumulate)",
+                            **{k: bind[k] for k in ("achieved", "peak", "unit", "frac")},
+                            "binding_roof": bind, ("mfma_roof" if hbm_binds else "hbm_roof"): other,
+                            "bound_note": "the roof whose floor is the longer time for this kernel (both are given): with three piece products the "
+                                          "matrix floor (0.71 ms on M-1M) falls below the HBM floor (0.84 ms)" if hbm_binds else
+                                          "matrix floor above the HBM floor",
+                            "fp32_equivalent_TFLOPs": flops_edge_kernel(e_loc) / t_edge / 1e12 if t_edge > 0 else 0.0,
+                            "fp32_equivalent_note": "the same launch counted as the fp32 products it replaces (98 304 flop per edge): what an fp32-MFMA "
+                                                    "kernel would have to sustain (its peak: 157.3)",
+                            "traffic": traffic, "traffic_source": tsrc, **common}
+                    ex = products * exec_flops_pass / MPS
+                    bytes_step = 4.0 * L * (2 * E + 2 * N) + 8.0 * E
+                    step_m = {"executed_flops_per_step": ex, "achieved": ex / t_step / 1e12, "peak": PEAK_BF16_MFMA_TFLOPS * world,
+                              "unit": "TFLOP/s", "frac": ex / t_step / 1e12 / (PEAK_BF16_MFMA_TFLOPS * world)}
+                    step_h = {"algorithmic_bytes_per_step": bytes_step, "achieved": bytes_step / t_step / 1e9, "peak": PEAK_HBM_GBPS * world,
+                              "unit": "GB/s", "frac": bytes_step / t_step / 1e9 / (PEAK_HBM_GBPS * world)}
+                    sb, so_ = (step_h, step_m) if hbm_binds else (step_m, step_h)
+                    roof["processor_step"] = {
+                        "bound": "hbm" if hbm_binds else "mfma", **sb, ("mfma_roof" if hbm_binds else "hbm_roof"): so_,
+                        "note": f"whole step: 16-bit MFMA flops executed ({products} x (98 304 E + 196 608 N)) and SURVEY.md 8(d) bytes "
+                                "(1 024 (E + N) + 8 E) over the wall time per step",
+                        "fp32_equivalent_TFLOPs": exec_flops_pass / MPS / t_step / 1e12,
+                        "algorithmic_equivalent_TFLOPs": flops_algorithmic(E, N) / t_step / 1e12,
+                        "algorithmic_equivalent_note": "SURVEY.md 8(d) flops of the UN-factored fp32 algorithm (163 840 E + 131 072 N) over the same "
+                                                       "time: a speed-up of the design, not a fraction of any peak"}
+                else:
+                    ach = flops_edge_kernel(e_loc) / t_edge / 1e12 if t_edge > 0 else 0.0
+                    traffic, tsrc = committed_traffic(["k_edge_step<4, 2"]) if (world == 1 and args.nx == 1000) else (None, None)
+                    roof = {"bound": "mfma", "kernel": FAMILY.get(fam, "k_edge_step<4,2>") + " (fused gather + edge MLP + LayerNorm + residual + segmented scatter; "
+                            "fp32 MFMA)",
+                            "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_F32_MFMA_TFLOPS,
+                            "flops_per_launch": flops_edge_kernel(e_loc), "flops_kind": "MFMA flops executed by this kernel (98 304 per edge; "
+                            "layer 1 is factored so the v_s/v_r blocks run per node in k_node_step)",
+                            "traffic": traffic, "traffic_source": tsrc, **common}
+                    roof["processor_step"] = {
+                        "bound": "mfma", "executed_flops_per_step": exec_flops_pass / MPS, "achieved": exec_flops_pass / MPS / t_step / 1e12,
+                        "peak": PEAK_F32_MFMA_TFLOPS * world, "unit": "TFLOP/s", "frac": exec_flops_pass / MPS / t_step / 1e12 / (PEAK_F32_MFMA_TFLOPS * world),
+                        "note": "MFMA flops the kernels execute (edge 98 304 E; node side 196 608 N incl. the P / Q projection) / wall time per step",
+                        "algorithmic_equivalent_TFLOPs": flops_algorithmic(E, N) / t_step / 1e12,
+                        "algorithmic_equivalent_note": "SURVEY.md 8(d) flops of the UN-factored algorithm (163 840 E + 131 072 N) over the same time: "
+                                                       "a speed-up of the factored design, not a fraction of any peak"}
+            roof["kernel_timing"] = "separate pass after the timed region: HIP event pairs per launch on the launch stream (mgn_profile_enable)"
+            roof["node_side"] = {"avg_launch_ms": t_node * 1e3, "launches": prof["node_step"]["count"],
+                                 "achieved_TFLOPs_fp32_equivalent": node_flops_pass / max(node_launches, 1) / t_node / 1e12 if t_node > 0 else 0.0,
+                                 "note": "node MLP + P / Q projection per event group; flops counted as fp32 products (x 6 executed on the split path)"}
+            if prof["halo"]["count"]:
+                roof["halo_pack_ms"] = prof["halo"]["avg_ms"]
         if bf:
             precision = "bf16 storage + bf16 MFMA"
         elif split_mode and products == 3:
@@ -555,9 +597,9 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
             "ms_per_processor_step": t_step * 1e3,
-            "median": {"ms_per_step": t_med * 1e3, "value": E * MPS / t_med, "min_ms_per_step": t_min * 1e3,
-                       "note": f"SURVEY.md 8(d): median of {max(args.steps, 3)} individually bracketed passes (a separate pass; `value` is the "
-                               "driver contract's single bracket around all timed steps)"},
+            **({"median": {"ms_per_step": t_med * 1e3, "value": E * MPS / t_med, "min_ms_per_step": t_min * 1e3,
+                           "note": f"SURVEY.md 8(d): median of {max(args.steps, 3)} individually bracketed passes (a separate pass; `value` is "
+                                   "the driver contract's single bracket around all timed steps)"}} if args.full else {}),
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -569,16 +611,16 @@ def main():
                        "partition": (f"edge-cut RCB over {world} GPU(s), halo exchange inside mgn_processor_steps_dev, transport {transport}"
                                      if world > 1 else "single partition"),
                        "edge_order": "engine re-sorts by receiver once per trajectory (mgn_set_graph)"},
-            "roofline": roof,
-            "latents_finite": bool(finite),
+            **({"roofline": roof, "latents_finite": bool(finite)} if args.full else {}),
             "graph_setup_s": t_setup,   # once per trajectory (mgn_set_graph: sort by receiver, CSR, partition, upload), not in `value`
         }
         if world > 1:
             out["transport"] = transport
+        if world > 1 and args.full:
             out["per_rank"] = {"n_own": n_loc, "e_local": e_loc, "n_halo": eng.n_halo,
                                "graph_setup_s": [float(x) for x in setup_all],
                                "graph_setup_note": "every rank ingests the global edge lists in mgn_set_graph and keeps its partition"}
-        if world == 1 and not args.no_secondary and args.dtype == "f32" and split_mode:
+        if args.full and world == 1 and not args.no_secondary and args.dtype == "f32" and split_mode:
             # the same workload on the fp32-MFMA kernels (v_mfma_f32_32x32x2_f32), for the record beside the split-path headline
             lib.mgn_debug_fp32_split(0)
             try:
@@ -599,7 +641,7 @@ def main():
                 engs.close()
             finally:
                 lib.mgn_debug_fp32_split(split_mode)
-        if world == 1 and not args.no_secondary and args.dtype == "f32" and split_mode and products == 3:
+        if args.full and world == 1 and not args.no_secondary and args.dtype == "f32" and split_mode and products == 3:
             # ... and on the three-piece bf16 split (six products): round 3 / 4's headline path
             lib.mgn_debug_split_f16.restype = ctypes.c_int
             lib.mgn_debug_split_f16.argtypes = [ctypes.c_int]
@@ -623,7 +665,7 @@ def main():
                 engs.close()
             finally:
                 lib.mgn_debug_split_f16(oldh)
-        if world == 1 and not args.no_secondary and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_secondary and args.dtype == "f32":
             engb = mgn_amd.Engine(FN, FE, O, L, 2, MPS, device=local_rank, dtype="bf16")
             engb.set_params(ps)
             engb.set_graph(s, r, N)
@@ -644,7 +686,7 @@ def main():
                                        "bytes_per_launch": eb_b, "traffic": trb, "traffic_source": srcb,
                                        "processor_step_frac": bytes_b / tb / 1e9 / PEAK_HBM_GBPS}
             engb.close()
-        if world == 1 and not args.no_secondary and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_secondary and args.dtype == "f32":
             # The same mesh under arbitrary node labels (DeepMind's trajectories; create_base_graph passes them through, reference
             # src/graph.jl:30-36): mgn_set_graph re-numbers it breadth-first inside the engine (csrc/graph_host.cpp) -- against the
             # coherent labels above, and against the scattered labels kept as they are (MGN_RENUMBER=0)
@@ -675,7 +717,7 @@ def main():
             scat["vs_coherent_f32"] = scat["renumbered_f32"]["ms_per_processor_step"] / (t_step * 1e3)
             scat["vs_coherent_bf16"] = scat["renumbered_bf16"]["ms_per_processor_step"] / out["bf16"]["ms_per_processor_step"]
             out["scattered_labels"] = scat
-        if world == 1 and not args.no_secondary and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_secondary and args.dtype == "f32":
             pos2, cells2, _, _ = mgn_amd.synth.mesh_cyl(1234, 2000)
             s2, r2 = mgn_amd.synth.cells_to_edges(cells2)
             eng2 = mgn_amd.Engine(FN, FE, O, L, 2, MPS, device=local_rank)
@@ -1011,7 +1053,7 @@ def main():
                                            "identical_count": bool(n_w == swh.size)},
                 "set_graph_s": t_setup}
             engp.close()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(ps)
         print(json.dumps(out), flush=True)
 

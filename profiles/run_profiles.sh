@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/prof_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $ROOT
-CMD=(python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary "$@")
+CMD=(python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary "$@")
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- "${CMD[@]}" > $OUT/trace.log 2>&1
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 --output-format csv -d $OUT/pmc_sq -- "${CMD[@]}" > $OUT/pmc_sq.log 2>&1
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS --output-format csv -d $OUT/pmc_sq2 -- "${CMD[@]}" > $OUT/pmc_sq2.log 2>&1

@@ -253,7 +253,7 @@ def test_bench_staged_path_with_rccl_world1():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--nx", "200", "--force-staged", "--no-cpu-baseline", "--no-secondary"],
+                          "--nx", "200", "--force-staged", "--full", "--no-cpu-baseline", "--no-secondary"],
                          env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert lines, out.stdout[-2000:] + out.stderr[-2000:]

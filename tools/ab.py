@@ -22,7 +22,7 @@ for r in range(rounds):
         if lib != "default":
             env["MGN_LIB_PATH"] = os.path.join(ROOT, "meshgraphnets.jl_amd", "lib", "variants", lib + ".so")
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--nx", str(nx),
-                              "--no-cpu-baseline", "--no-secondary", "--dtype", dtype], env=env, capture_output=True, text=True)
+                              "--full", "--no-cpu-baseline", "--no-secondary", "--dtype", dtype], env=env, capture_output=True, text=True)
         err, out = out.stderr, out.stdout
         line = [l for l in out.splitlines() if l.startswith("{")]
         if not line:

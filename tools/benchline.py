@@ -1,4 +1,4 @@
-"""Pretty-print a bench.py JSON line: python tools/benchline.py FILE   (never reads stdin: a forgotten pipe must not hang a GPU box)"""
+"""Pretty-print a `bench.py --full` JSON line: python tools/benchline.py FILE   (never reads stdin: a forgotten pipe must not hang a GPU box)"""
 import json, sys
 if len(sys.argv) < 2:
     raise SystemExit("usage: benchline.py FILE")
