@@ -277,6 +277,24 @@ typedef struct mgn_rollout_desc {
 typedef enum mgn_inflow_rule { MGN_INFLOW_REFERENCE = 0, MGN_INFLOW_TOLERANT = 1 } mgn_inflow_rule;
 int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d);
 
+/* ---- solver-based training: the loss and d loss / d ps of one fixed-step Euler solve of ode_func_train (reference src/solve.jl:101-117,
+ * strategies.jl:175-196) -- what train_step(::SolverTraining) (strategies.jl:257-292) and one window of train_step(::MultipleShooting)
+ * (:312-383) differentiate, with no host work per step and one synchronisation at the end.
+ * d is read as mgn_rollout reads it (same fields, time type, inflow_rule, Euler time loop and save rule), with two differences: only
+ * solver 0 (Euler; Tsit5 answers MGN_E_UNSUPPORTED), and the inflow overwrite takes ode_func_train's form -- the rows go into a COPY the
+ * right-hand side is evaluated on, the state itself is never overwritten.  Every save point must be reached (else MGN_E_ARG).
+ *   loss = mean over (save s, node n, component o) of (loss_scale[o] (gt[s][n][o] - x_s[n][o]))^2 vm[n]  +  cont_weight sum |x_end - cont_target|
+ * with the mean over n_saves * N * O, vm = d->val_mask (NULL: 1), loss_scale [O] (NULL: 1; the scale of the field normaliser, whose shift
+ * cancels), cont_target [N][O] (NULL: no continuity term; MultipleShooting's, strategies.jl:376-378, subgradient 0 at 0).
+ * gt [n_saves][N][O].  grads [n_grads = mgn_param_count] receives the EXACT gradient of that loss of the computed Euler solution (the
+ * discrete adjoint, what ReverseDiffAdjoint / ZygoteAdjoint give -- not InterpolatingAdjoint's continuous approximation); d->out, if not
+ * NULL, the predicted saves; d->n_accept, d->n_rhs are filled.  gt, cont_target and grads may be host or device pointers (hipMemcpyDefault);
+ * the others follow mgn_rollout.  fp32, one partition, one edge set, hidden_layers 1 .. 4, both ln_mode and ln_dims values.  Memory: the
+ * (K + 1) N O floats of the states before every step (4.8 GB for 1 M nodes over 600 steps); MGN_E_OOM when they do not fit.
+ * Bitwise repeatable (reductions in a fixed order).                                                                                  */
+int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt /* [n_saves][N][O] */, const float* loss_scale /* [O] or NULL */,
+                    const float* cont_target /* [N][O] or NULL */, float cont_weight, float* grads, size_t n_grads, float* loss);
+
 /* ---- training step -------------------------------------------------------
  * GraphNetCore.step!(mgn, graph, target, mask, mse_reduce) as called at reference src/strategies.jl:418-422 and
  * consumed at src/MeshGraphNets.jl:370-378:  out = model(graph);  loss = mean(mse_reduce(target, out)[mask]) with

@@ -29,7 +29,7 @@ export NormaliserOffline, NormaliserOfflineMinMax, NormaliserOfflineMeanStd, Nor
 export FeatureGraph, GraphNetwork, step!, load, save!
 # engine extras (optional fast paths; none is needed for the drop-in)
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
-       native_rollout, ode_vjp, forward_vjp, feature_stats
+       native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, native_solver_train_step
 export comm_unique_id, comm_init!, comm_init_file!, comm_barrier, processor_steps_dev!
 
 const LIB = get(ENV, "MGN_HIP_LIB", joinpath(@__DIR__, "..", "meshgraphnets.jl_amd", "lib", "libmgn_hip.so"))
@@ -588,6 +588,85 @@ function native_rollout(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_typ
     GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out check(mgn.handle,
         ccall((:mgn_rollout, LIB), Cint, (Ptr{Cvoid}, Ref{MgnRolloutDesc}), mgn.handle, d))
     return [out[:, :, i] for i in 1:ns], collect(saves)
+end
+
+"""
+    solver_grad(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, start, stop, dt, saves;
+                loss_scale = nothing, cont_target = nothing, cont_weight = 0f0) -> (gs, loss, pred::Array{Float32, 3})
+
+Loss and gradient of ONE fixed-step Euler solve of `ode_func_train` (src/solve.jl:101-117) on the device (mgn_solver_grad): the time
+grid, inflow frames and save rule of `native_rollout` with `dt` given, the inflow rows written into a copy the right-hand side sees,
+`loss = mean(((gt - pred) .* loss_scale) .^ 2 .* val_mask) + cont_weight * sum(abs, pred[:, :, end] - cont_target)`, gt (O x N x saves).
+`gs` is the discrete adjoint -- the exact gradient of that loss of the computed Euler solution, what ReverseDiffAdjoint / ZygoteAdjoint
+give -- not InterpolatingAdjoint's continuous approximation.  One upload of the statics, no host work per step, one synchronisation.
+"""
+function solver_grad(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
+        val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
+        inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, start, stop, dt, saves;
+        loss_scale::Union{Nothing, Vector{Float32}} = nothing, cont_target::Union{Nothing, Matrix{Float32}} = nothing, cont_weight = 0.0f0,
+        tolerant_inflow = false)
+    ps = mgn.ps::Vector{Float32}
+    sync_params!(mgn, ps)
+    O, N = size(x0)
+    ns = length(saves)
+    size(gt, 3) >= ns || throw(DimensionMismatch("gt has $(size(gt, 3)) frames, the solve saves $ns"))
+    g = Array{Float32, 3}(gt[:, :, 1:ns])
+    out = Array{Float32, 3}(undef, O, N, ns)
+    gs = Vector{Float32}(undef, length(ps))
+    loss = Ref{Float32}(0)
+    sdt = ns > 1 ? saves[2] - saves[1] : one(eltype(saves))
+    f64 = eltype(saves) == Float64
+    d = MgnRolloutDesc(0, start, stop, dt, sdt, ns, 0, 0,
+        pointer(x0), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
+        inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
+        inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
+        start, stop, dt, sdt)
+    GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out g loss_scale cont_target gs check(mgn.handle,
+        ccall((:mgn_solver_grad, LIB), Cint,
+            (Ptr{Cvoid}, Ref{MgnRolloutDesc}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Float32, Ptr{Float32}, Csize_t, Ref{Float32}),
+            mgn.handle, d, g, opt_ptr(loss_scale), opt_ptr(cont_target), Float32(cont_weight), gs, length(gs), loss))
+    return gs, loss[], out
+end
+
+"""
+    native_solver_train_step(strategy, mgn, gt, node_type_onehot, edge_features, val_mask_row, inflow_mask_row;
+                             n_scale = nothing, inflow_data = gt) -> (gs, loss)
+
+`train_step(::SolverTraining)` / `train_step(::MultipleShooting)` (src/strategies.jl:175-196, 257-292, 312-383) for a strategy with
+`Euler()` as its solver, through `solver_grad`: SolverTraining is one solve from `gt[:, :, 1]` over `tstart:dt:tstop` with the field
+normaliser's scale `n_scale` in the loss; MultipleShooting one solve per window of the reference's own
+`[i:min(T, i + interval_size - 1) for i in 1:(interval_size - 1):(T - 1)]` from `gt[:, :, first(rg)]`, no normaliser, and the continuity
+term of window i attached to window i - 1.  The Euler step is `solargs.dt` when given, else `strategy.dt` (the example's
+`tstops = tstart:dt:tstop`).  It returns the DISCRETE adjoint (exact gradient of the computed Euler solution), not
+InterpolatingAdjoint's continuous approximation the reference defaults to.  Opt-in for `train_network`:
+`gs, loss = native_solver_train_step(strategy, mgn, gt, ...)` in place of `train_step(strategy, t)`.
+(Julia is not available where this shim is tested: its ccalls are checked against the header by tests/test_julia_shim.py.)
+"""
+function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
+        edge_features::Matrix{Float32}, val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}};
+        n_scale::Union{Nothing, Vector{Float32}} = nothing, inflow_data::Union{Nothing, Array{Float32, 3}} = gt)
+    nameof(typeof(strategy.solver)) == :Euler || throw(ArgumentError("native_solver_train_step drives Euler(); got $(strategy.solver)"))
+    tsteps = (strategy.tstart):(strategy.dt):(strategy.tstop)
+    sargs = hasproperty(strategy, :solargs) ? strategy.solargs : (;)
+    dt = haskey(sargs, :dt) ? sargs[:dt] : strategy.dt
+    im = inflow_mask_row === nothing ? nothing : inflow_data
+    if !hasproperty(strategy, :interval_size)      # SolverTraining
+        gs, loss, _ = solver_grad(mgn, gt[:, :, 1], node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, gt,
+            strategy.tstart, strategy.tstop, dt, tsteps; loss_scale = n_scale)
+        return (gs,), loss
+    end
+    T = length(tsteps)
+    ranges = [i:min(T, i + strategy.interval_size - 1) for i in 1:(strategy.interval_size - 1):(T - 1)]
+    gs_sum = zeros(Float64, length(mgn.ps)); loss_sum = 0.0
+    for (i, rg) in enumerate(ranges)
+        last_window = i == length(ranges)
+        ct = last_window ? nothing : gt[:, :, first(ranges[i + 1])]
+        gs, loss, _ = solver_grad(mgn, gt[:, :, first(rg)], node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im,
+            gt[:, :, rg], tsteps[first(rg)], tsteps[last(rg)], dt, tsteps[rg];
+            cont_target = ct, cont_weight = last_window ? 0.0f0 : Float32(strategy.continuity_term))
+        gs_sum .+= gs; loss_sum += loss
+    end
+    return (Float32.(gs_sum),), Float32(loss_sum)
 end
 
 # ---- multi-GPU: one Julia process per GPU (e.g. under MPI.jl or Distributed), one handle each; the halo exchange (RCCL grouped

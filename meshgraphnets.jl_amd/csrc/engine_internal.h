@@ -208,6 +208,26 @@ int lnall_forward(mgn_engine* h, const float* nf, const float* ef, float* out);
 int lnall_processor_steps(mgn_engine* h, float* v, float* e, int32_t nsteps);
 int lnall_rhs_prepare(mgn_engine* h);                                              // binds the arena (may allocate / copy: outside of any capture)
 int lnall_rhs_dev(mgn_engine* h, const float* srcA, float* out, bool reuse_edges);  // the right-hand side on resident inputs; launches only
+// mgn_solver_grad: the training-side checks and arena (train_prepare), and the reverse sweep over the states the forward stored (mgn_train.cpp).
+// Device arrays in the engine's order unless noted; the user's pointers are read with hipMemcpyDefault.
+struct SolverSweep {
+    int64_t K;                           // Euler steps
+    const float* states;                 // [K + 1][N][O]: the array the RHS of step k saw (P_k x_k), then x_K
+    const float* saves;                  // [n_saves][N][O]: the solution at the save points
+    const int64_t* save_step;            // [n_saves] (host): the step whose state each save is, non-decreasing
+    int32_t n_saves;
+    const float* gt;                     // [n_saves][N][O]
+    const float* loss_scale;             // [O] or null
+    const uint8_t* inflow;               // [N] or null
+    const float* cont_target;            // [N][O] or null (continuity term on x_K)
+    float cont_weight;
+    float dt;
+    const float* onehot; const float* ef_raw; const float* val_mask;   // the caller's, in the caller's order
+    float* a; double* gacc; double* part;   // scratch: [N][O], [n_params], [n_saves + 1][2][solver_adjoint_blocks]
+    float* grads; float* loss;              // results (grads: host or device)
+};
+int solver_prepare(mgn_engine* h, size_t n_grads);
+int solver_sweep(mgn_engine* h, const SolverSweep& S);
 
 #define HIPCHK(h, expr)                                                                              \
     do {                                                                                             \

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2101,6 +2102,197 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     d->n_rhs = R.n_rhs;
+    return MGN_OK;
+} MGN_CATCH(h)
+
+// ---- solver-based training (SolverTraining / MultipleShooting with Euler()): loss and gradient of one solved window ---------------
+// Forward: the Euler loop of mgn_rollout on the resident right-hand side (the same launches, the same hipGraph replay), in the training
+// form of the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the array every
+// step's RHS saw.  Backward: solver_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
+int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
+                    float* grads, size_t n_grads, float* loss) try {
+    if (!h) return MGN_E_ARG;
+    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
+    const mgn_config& c = h->cfg;
+    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", "mgn_solver_grad");
+    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", "mgn_solver_grad");
+    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", "mgn_solver_grad");
+    const bool lnall = c.ln_dims == MGN_LN_ALL;
+    if (int rc = need(h, true, true, !lnall, true)) return rc;
+    if (!d || !gt || !grads || !loss || !d->x0 || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot))
+        return fail(h, MGN_E_ARG, "mgn_solver_grad: null argument");
+    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "mgn_solver_grad: Fn < O");
+    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is not supported");
+    if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
+    const bool f64 = d->time_f64 != 0;
+    const double T0 = f64 ? d->t0_f64 : (double)d->t0, T1 = f64 ? d->t1_f64 : (double)d->t1, DT = f64 ? d->dt_f64 : (double)d->dt,
+                 SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
+    if (d->n_saves < 1 || !(SDT > 0.0) || !(T1 >= T0)) return fail(h, MGN_E_ARG, "mgn_solver_grad: bad time grid");
+    if (!(DT > 0.0)) return fail(h, MGN_E_ARG, "mgn_solver_grad: Euler needs dt > 0");
+    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "mgn_solver_grad: unknown inflow_rule");
+    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "mgn_solver_grad: inflow mask and data go together");
+    if (d->inflow_data && d->n_frames < 1) return fail(h, MGN_E_ARG, "mgn_solver_grad: inflow_data needs n_frames >= 1");
+    if (!std::isfinite(cont_weight)) return fail(h, MGN_E_ARG, "mgn_solver_grad: cont_weight must be finite");
+    const double steps = (T1 - T0) / DT;
+    if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "mgn_solver_grad: %.3g Euler steps", steps);
+    const int64_t K = (int64_t)std::llround(steps);
+
+    // the time grid of the Euler loop of mgn_rollout, walked once on the host: which step each save is (every one must be reached)
+    Rollout R;
+    R.h = h;
+    R.d = d;
+    R.f64 = f64;
+    R.sdt = SDT;
+    auto tt = [&](double v) { return R.tt(v); };
+    auto stop_time = [&](int i) { return tt(T0 + (double)i * SDT); };
+    auto next_t = [&](int64_t i, double t) { return (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT); };
+    std::vector<int64_t> save_step(1, 0);
+    {
+        double t = T0;
+        for (int64_t i = 0; i < K && (int)save_step.size() < d->n_saves; ++i) {
+            t = next_t(i, t);
+            while ((int)save_step.size() < d->n_saves && stop_time((int)save_step.size()) <= t + 0.25 * DT) save_step.push_back(i + 1);
+        }
+        if ((int)save_step.size() < d->n_saves)
+            return fail(h, MGN_E_ARG, "mgn_solver_grad: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached",
+                        (int)save_step.size(), stop_time((int)save_step.size()), T1);
+    }
+    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
+    const LocalGraph& g = h->g;
+    invalidate_static(h);
+    const int32_t N = g.N;
+    const int O = c.O;
+    const bool loc = g.renumbered;
+    R.n = (int64_t)N * O;
+    R.n_global = R.n;
+    R.nrows = N;
+    const size_t nb = (size_t)R.n * 4;
+    const size_t P = h->params.size();
+    const int ablk = solver_adjoint_blocks(N, O);
+    if ((size_t)(K + 1) > (SIZE_MAX / 2) / (nb > 0 ? nb : 1))
+        return fail(h, MGN_E_OOM, "mgn_solver_grad: %lld stored states of %zu bytes overflow the address space", (long long)(K + 1), nb);
+    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
+    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    const size_t o_u = take(nb), o_ut = take(nb), o_k = take(nb), o_fr = take(fb), o_sv = take(sb), o_mask = take((size_t)N);
+    R.elat0_off = take(eb);
+    const size_t o_gt = take(sb), o_ct = take(cont_target ? nb : 0), o_ls = take((size_t)O * 4), o_a = take(nb), o_tmp = take(nb),
+                 o_gacc = take(P * sizeof(double)), o_part = take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
+    const size_t o_st = take((size_t)(K + 1) * nb);
+    if (hipError_t e = h->ode.ensure(off)) {
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "mgn_solver_grad: %.3f GB for the %lld stored states of the solve and the call's buffers: %s",
+                    (double)off * 1e-9, (long long)(K + 1), hipGetErrorString(e));
+    }
+    char* base = h->ode.as<char>();
+    R.u = (float*)(base + o_u); R.utmp = (float*)(base + o_ut); R.unew = nullptr;
+    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k);      // (Euler takes k[0] only)
+    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
+    R.saves = (float*)(base + o_sv);
+    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
+    R.partial = nullptr;
+    float* states = (float*)(base + o_st);
+
+    // entry: x0, frames and the inflow mask into the engine's order (as mgn_rollout), then the static inputs
+    if (!loc) {
+        HIPCHK(h, hipMemcpyAsync(R.u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
+        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
+        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, d->inflow_mask, (size_t)N, hipMemcpyHostToDevice, h->stream));
+    } else {
+        std::vector<float> lx((size_t)N * O * (1 + (d->inflow_data ? d->n_frames : 0)));
+        std::vector<uint8_t> lm(d->inflow_mask ? (size_t)N : 0);
+        for (int32_t i = 0; i < N; ++i) {
+            const size_t gi = (size_t)g.own_gid[i];
+            memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
+            for (int f = 0; d->inflow_data && f < d->n_frames; ++f)
+                memcpy(lx.data() + ((size_t)(1 + f) * N + i) * O, d->inflow_data + ((size_t)f * N + gi) * O, (size_t)O * 4);
+            if (d->inflow_mask) lm[i] = d->inflow_mask[gi];
+        }
+        HIPCHK(h, hipMemcpyAsync(R.u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
+        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, lx.data() + (size_t)N * O, fb, hipMemcpyHostToDevice, h->stream));
+        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, lm.data(), (size_t)N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (int rc = upload_inputs(h, d->x0, O, d->node_type_onehot, c.Fn - O, d->ef_raw, true)) return rc;
+    h->have_mask = d->val_mask != nullptr;
+    if (d->val_mask) {
+        HIPCHK(h, h->d_mask.ensure((size_t)N * 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (lnall) {
+        if (int rc = lnall_rhs_prepare(h)) return rc;
+    } else {
+        if (int rc = encode_impl(h, true, false, true)) return rc;
+        HIPCHK(h, hipMemcpyAsync(base + R.elat0_off, h->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, h->stream));
+    }
+
+    // forward: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k kept for the sweep
+    d->n_accept = d->n_reject = 0;
+    int saved = 0;
+    auto save = [&]() { return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream); };
+    HIPCHK(h, save());
+    double t = T0;
+    for (int64_t i = 0; i < K; ++i) {
+        float* xin = R.u;
+        if (R.mask) {      // ode_func_train: the inflow rows go into a copy, the state itself is not overwritten
+            HIPCHK(h, hipMemcpyAsync(R.utmp, R.u, nb, hipMemcpyDeviceToDevice, h->stream));
+            xin = R.utmp;
+        }
+        if (int rc = R.rhs(xin, t, R.k[0])) return rc;
+        HIPCHK(h, hipMemcpyAsync(states + (size_t)i * R.n, xin, nb, hipMemcpyDeviceToDevice, h->stream));
+        LinComb lc{1, {1.f}, {R.k[0]}};
+        HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)DT, R.n, h->stream));
+        t = next_t(i, t);
+        ++d->n_accept;
+        while (saved < d->n_saves && stop_time(saved) <= t + 0.25 * DT) HIPCHK(h, save());
+    }
+    HIPCHK(h, hipMemcpyAsync(states + (size_t)K * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream));
+    d->n_rhs = R.n_rhs;
+
+    // gt and cont_target (host or device, the caller's order) into the engine's order; loss_scale as given
+    float* gtl = (float*)(base + o_gt);
+    float* tmp = (float*)(base + o_tmp);
+    const int32_t* ngid = h->d_own_gid.as<int32_t>();
+    for (int s = 0; s < d->n_saves; ++s) {
+        if (!loc) {
+            HIPCHK(h, hipMemcpyAsync(gtl + (size_t)s * R.n, gt + (size_t)s * R.n, nb, hipMemcpyDefault, h->stream));
+        } else {
+            HIPCHK(h, hipMemcpyAsync(tmp, gt + (size_t)s * R.n, nb, hipMemcpyDefault, h->stream));
+            HIPCHK(h, launch_permute_rows(gtl + (size_t)s * R.n, tmp, ngid, N, O, false, h->stream));
+        }
+    }
+    float* ctl = cont_target ? (float*)(base + o_ct) : nullptr;
+    if (ctl) {
+        HIPCHK(h, hipMemcpyAsync(loc ? tmp : ctl, cont_target, nb, hipMemcpyDefault, h->stream));
+        if (loc) HIPCHK(h, launch_permute_rows(ctl, tmp, ngid, N, O, false, h->stream));
+    }
+    float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
+    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)O * 4, hipMemcpyDefault, h->stream));
+
+    SolverSweep S{};
+    S.K = K; S.states = states; S.saves = R.saves; S.save_step = save_step.data(); S.n_saves = d->n_saves;
+    S.gt = gtl; S.loss_scale = lsd; S.inflow = R.mask; S.cont_target = ctl; S.cont_weight = ctl ? cont_weight : 0.f; S.dt = (float)DT;
+    S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
+    S.a = (float*)(base + o_a); S.gacc = (double*)(base + o_gacc); S.part = (double*)(base + o_part);
+    S.grads = grads; S.loss = loss;
+    if (int rc = solver_sweep(h, S)) return rc;
+
+    // exit: the predicted saves in the caller's order
+    if (d->out) {
+        if (loc) {
+            std::vector<float> sv((size_t)d->n_saves * R.n);
+            HIPCHK(h, hipMemcpyAsync(sv.data(), R.saves, sb, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (int i = 0; i < d->n_saves; ++i)
+                for (int32_t j = 0; j < N; ++j)
+                    memcpy(d->out + ((size_t)i * N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * N + j) * O, (size_t)O * 4);
+        } else {
+            HIPCHK(h, hipMemcpyAsync(d->out, R.saves, sb, hipMemcpyDeviceToHost, h->stream));
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return MGN_OK;
 } MGN_CATCH(h)
 

@@ -457,6 +457,10 @@ struct TrainJob {
     // vjp of the model itself (mgn_forward_vjp): nf / ef as in step!, cotangent `lambda` of the output, gradient of all of nf out
     bool fvjp = false;
     float* nfbar = nullptr; float* out = nullptr;
+    // one step of the reverse sweep of mgn_solver_grad (with vjp): x is a device slot in the engine's order, lambda is already in its io slot
+    // and the statics in theirs (solver_sweep staged them); xbar stays in io, the gradient is added to gacc (first: gacc = it), no synchronisation
+    bool sweep = false, first = false;
+    double* gacc = nullptr;
 };
 
 int train_prepare(mgn_handle* h, const char* who, size_t n_grads) {
@@ -578,6 +582,11 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                 }
             }
         }
+    } else if (J.sweep) {
+        // the state this step's RHS saw; one-hot node types, val_mask and the normalised edge features were staged once for the sweep
+        float* io = A + T.io;
+        HIPCHK(h, launch_affine_pad(J.x, O, io + (size_t)2 * N * O, c.Fn - O, h->have_nnorm ? nrm : nullptr, h->have_nnorm ? nrm + c.Fn : nullptr,
+                                    A + T.nf_pad, L, N, st));
     } else {
         // RHS inputs exactly as mgn_ode_step takes them: nf = [n_norm(x); n_norm(onehot)], ef = e_norm(ef_raw)
         float* io = A + T.io;                  // x [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N]
@@ -1047,6 +1056,11 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     if (int rc = graphed(J.vjp ? 2 : 1, backward_launches)) return rc;
 
     // ---- results
+    if (J.sweep) {     // xbar (engine order) into io for the adjoint kernel; the step's gradient into the double accumulator
+        HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, A + T.io, N, st));
+        HIPCHK(h, launch_grad_accum(G, J.gacc, (int64_t)h->params.size(), J.first, st));
+        return MGN_OK;
+    }
     std::vector<double> lp((size_t)nlb);
     HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
     if (!J.vjp) {
@@ -1113,6 +1127,100 @@ extern "C" int mgn_ode_vjp(mgn_handle* h, const float* x, const float* node_type
     J.dxdt = dxdt; J.xbar = xbar; J.grads = grads;
     return train_run(h, J);
 } MGN_CATCH(h)
+
+namespace mgn {
+
+int solver_prepare(mgn_engine* h, size_t n_grads) { return train_prepare(h, "mgn_solver_grad", n_grads); }
+
+// Reverse sweep of mgn_solver_grad: k = K-1 .. 0 through train_run's VJP path, seeded and chained by k_solver_adjoint (train.hip).
+int solver_sweep(mgn_engine* h, const SolverSweep& S) {
+    const mgn_config& c = h->cfg;
+    TrainState& T = *h->train;
+    const LocalGraph& g = h->g;
+    const int64_t N = g.n_own, n = N * c.O, E = g.set[0].e_local, P = (int64_t)h->params.size();
+    const int O = c.O, W1 = c.Fn - c.O;
+    hipStream_t st = h->stream;
+    float* A = T.arena.as<float>();
+    float* io = A + T.io;                      // xbar [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N], as train_run lays them out
+    const float* nrm = h->norms.as<float>();
+    const int32_t* ngid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+    auto to_local = [&](float* buf, int width) -> hipError_t {
+        if (!ngid || width <= 0) return hipSuccess;
+        if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, false, st)) return e;
+        return hipMemcpyAsync(buf, A + T.ptmp, (size_t)N * width * 4, hipMemcpyDeviceToDevice, st);
+    };
+    // the statics, once per call
+    if (W1 > 0) {
+        HIPCHK(h, hipMemcpyAsync(io + 2 * n, S.onehot, (size_t)N * W1 * 4, hipMemcpyDefault, st));
+        HIPCHK(h, to_local(io + 2 * n, W1));
+    }
+    float* vm = S.val_mask ? io + (size_t)N * (O + c.Fn) : nullptr;
+    if (vm) {
+        HIPCHK(h, hipMemcpyAsync(vm, S.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
+        HIPCHK(h, to_local(vm, 1));
+    }
+    if (E > 0) {
+        HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], S.ef_raw, (size_t)E * c.Fe * 4, hipMemcpyDefault, st));
+        HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
+                                    h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, A + T.ef_pad[0], c.L, E, st));
+    }
+    HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, st));
+
+    const int nb = solver_adjoint_blocks(N, O);
+    const float gscale = (float)(2.0 / ((double)S.n_saves * (double)n));
+    int64_t sidx = S.n_saves - 1;              // saves are visited last to first; save_step is non-decreasing
+    int slot = 0;
+    // every loss term of step k (one launch per save that ends there; the continuity seed rides on the first), xbar folded in by the first
+    // launch, the seed of step k - 1 written by the last
+    auto adjoint_step = [&](int64_t k, bool with_xbar) -> int {
+        for (bool first = true;; first = false) {
+            SolverAdjArgs p{};
+            p.a = S.a;
+            p.xbar = (first && with_xbar) ? io : nullptr;
+            p.inflow = S.inflow;
+            const bool has_save = sidx >= 0 && S.save_step[sidx] == k;
+            if (has_save) {
+                p.xs = S.saves + (size_t)sidx * n; p.gt = S.gt + (size_t)sidx * n; p.ls = S.loss_scale; p.vm = vm; p.gscale = gscale;
+                --sidx;
+            }
+            if (first && k == S.K && S.cont_target) { p.xend = S.states + (size_t)S.K * n; p.ct = S.cont_target; p.cw = S.cont_weight; }
+            const bool more = sidx >= 0 && S.save_step[sidx] == k;
+            p.lam = (!more && k > 0) ? io + n : nullptr;
+            p.dt = S.dt; p.N = N; p.O = O;
+            if (p.gt || p.ct) p.part = S.part + (size_t)slot++ * 2 * nb;
+            HIPCHK(h, launch_solver_adjoint(p, st));
+            if (!more) return MGN_OK;
+        }
+    };
+    if (int rc = adjoint_step(S.K, false)) return rc;
+    for (int64_t k = S.K - 1; k >= 0; --k) {
+        TrainJob J;
+        J.vjp = J.sweep = true;
+        J.first = k == S.K - 1;
+        J.x = S.states + (size_t)k * n;
+        J.val_mask = vm;
+        J.gacc = S.gacc;
+        if (int rc = train_run(h, J)) return rc;
+        if (int rc = adjoint_step(k, true)) return rc;
+    }
+    float* G = T.grads.as<float>();
+    if (S.K > 0) HIPCHK(h, launch_grad_finish(S.gacc, G, P, st));
+    else HIPCHK(h, hipMemsetAsync(G, 0, (size_t)P * 4, st));
+    HIPCHK(h, hipMemcpyAsync(S.grads, G, (size_t)P * 4, hipMemcpyDefault, st));
+    std::vector<double> lp((size_t)slot * 2 * nb);
+    if (!lp.empty()) HIPCHK(h, hipMemcpyAsync(lp.data(), S.part, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    double se = 0.0, sa = 0.0;
+    for (int i = 0; i < slot; ++i)
+        for (int b = 0; b < nb; ++b) {
+            se += lp[(size_t)i * 2 * nb + b];
+            sa += lp[(size_t)i * 2 * nb + nb + b];
+        }
+    *S.loss = (float)(se / ((double)S.n_saves * (double)n) + (double)S.cont_weight * sa);
+    return MGN_OK;
+}
+
+}  // namespace mgn
 
 // =====================================================================================================================================
 // mgn_config.ln_dims = MGN_LN_ALL: LayerNorm statistics over the whole (rows x L) output of an MLP -- what Lux 0.5's LayerNorm(shape)

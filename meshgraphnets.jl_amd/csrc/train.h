@@ -163,4 +163,20 @@ int loss_blocks(int64_t nmask);
 hipError_t launch_loss(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int32_t index_base,
                        float* G, double* loss_partial, hipStream_t s);
 
+// solver-based training (mgn_solver_grad), one step k of the reverse sweep of a fixed-step Euler solve, per element of the [N][O] state:
+//   a <- a + (xbar ? (inflow[n] ? 0 : xbar) : 0) + (gt ? -gscale ls[o]^2 (gt - xs) vm[n] : 0) + (ct ? cw sign(xend - ct) : 0);  lam <- dt a
+// part (may be null): [2][solver_adjoint_blocks] doubles -- per block the sum of (ls (gt - xs))^2 vm, then of |xend - ct|
+struct SolverAdjArgs {
+    float* a; float* lam; const float* xbar; const uint8_t* inflow;
+    const float* xs; const float* gt; const float* ls; const float* vm; float gscale;
+    const float* xend; const float* ct; float cw;
+    float dt; int64_t N; int32_t O;
+    double* part;
+};
+int solver_adjoint_blocks(int64_t N, int O);
+hipError_t launch_solver_adjoint(const SolverAdjArgs& p, hipStream_t s);
+// acc[i] = (first ? 0 : acc[i]) + g[i] in double; out[i] = (float)acc[i]
+hipError_t launch_grad_accum(const float* g, double* acc, int64_t n, bool first, hipStream_t s);
+hipError_t launch_grad_finish(const double* acc, float* out, int64_t n, hipStream_t s);
+
 }  // namespace mgn

@@ -1998,4 +1998,81 @@ hipError_t launch_loss(const float* Y, int L, const float* target, int O, const 
     return hipGetLastError();
 }
 
+// ---- solver-based training (mgn_solver_grad): the discrete adjoint of a fixed-step Euler solve ------------------------------------
+// One element per thread.  a_k = a_{k+1} + (1 - inflow) .* xbar + dL/dx_k, the next seed dt * a_k goes straight into the VJP's lambda
+// slot, and the loss terms of this step leave one double per block (mse | L1): the host adds the blocks in order.
+__global__ __launch_bounds__(256) void k_solver_adjoint(SolverAdjArgs p) {
+    __shared__ double sh[2][4];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double e2 = 0.0, e1 = 0.0;
+    if (i < p.N * p.O) {
+        const int64_t n = i / p.O;
+        const int o = (int)(i - n * p.O);
+        float av = p.a[i];
+        if (p.xbar && !(p.inflow && p.inflow[n])) av += p.xbar[i];     // overwritten rows are constants of the RHS
+        if (p.gt) {      // (ls (gt - x))^2 vm / D  ->  d/dx = -2 ls^2 (gt - x) vm / D
+            const float sc = p.ls ? p.ls[o] : 1.f, m = p.vm ? p.vm[n] : 1.f;
+            const float d = p.gt[i] - p.xs[i];
+            const double ed = (double)sc * ((double)p.gt[i] - (double)p.xs[i]);
+            e2 = ed * ed * (double)m;
+            av -= p.gscale * sc * sc * d * m;
+        }
+        if (p.ct) {      // cw |x_end - ct|: subgradient 0 at 0
+            const float r = p.xend[i] - p.ct[i];
+            e1 = fabs((double)p.xend[i] - (double)p.ct[i]);
+            av += r > 0.f ? p.cw : (r < 0.f ? -p.cw : 0.f);
+        }
+        p.a[i] = av;
+        if (p.lam) p.lam[i] = p.dt * av;
+    }
+    if (!p.part) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        e2 += __shfl_xor(e2, off, 64);
+        e1 += __shfl_xor(e1, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = e2; sh[1][threadIdx.x >> 6] = e1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p.part[blockIdx.x] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
+        p.part[gridDim.x + blockIdx.x] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+    }
+}
+
+// acc[i] = (first ? 0 : acc[i]) + g[i]  (double accumulator of the per-step parameter gradients)
+__global__ __launch_bounds__(256) void k_grad_accum(const float* __restrict__ g, double* __restrict__ acc, int64_t n, int first) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        acc[i] = (first ? 0.0 : acc[i]) + (double)g[i];
+}
+
+__global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ acc, float* __restrict__ out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = (float)acc[i];
+}
+
+int solver_adjoint_blocks(int64_t N, int O) { return N * O > 0 ? (int)((N * O + 255) / 256) : 0; }
+
+hipError_t launch_solver_adjoint(const SolverAdjArgs& p, hipStream_t s) {
+    const int nb = solver_adjoint_blocks(p.N, p.O);
+    if (nb == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_solver_adjoint, dim3(nb), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+static unsigned grad_blocks(int64_t n) {
+    const int64_t b = (n + 255) / 256;
+    return (unsigned)(b < 4096 ? b : 4096);
+}
+
+hipError_t launch_grad_accum(const float* g, double* acc, int64_t n, bool first, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_grad_accum, dim3(grad_blocks(n)), dim3(256), 0, s, g, acc, n, first ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_finish(const double* acc, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_grad_finish, dim3(grad_blocks(n)), dim3(256), 0, s, acc, out, n);
+    return hipGetLastError();
+}
+
 }  // namespace mgn

@@ -346,6 +346,55 @@ class Engine:
         self._chk(self.lib.mgn_rollout(self.h, C.byref(d)))
         return out, dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)
 
+    def solver_grad(self, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask=None, inflow_mask=None,
+                    inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0, inflow_rule="reference", time_type=np.float32,
+                    want_pred=False, out=None, solver="Euler"):
+        """Loss and gradient of one fixed-step Euler solve of ode_func_train on the device (mgn_solver_grad; reference
+        src/solve.jl:101-117, strategies.jl:175-196, 257-292): the time grid, inflow frames and save rule of rollout("Euler", ...), with
+        the inflow rows written into a copy the right-hand side sees (the state is not overwritten).
+            loss = mean(((gt - x_saves) .* loss_scale) .^ 2 .* val_mask) + cont_weight * sum(abs.(x_end - cont_target))
+        gt [n_saves][N][O] and cont_target [N][O]: NumPy arrays or contiguous fp32 device tensors; `out`: NumPy array or device tensor
+        of param_count floats for the gradient.  The gradient is the discrete adjoint of the computed solution.
+        solver: "Euler" (the only one with a discrete adjoint here; "Tsit5" is answered with MGN_E_UNSUPPORTED).
+        Returns (grads, loss) or, with want_pred, (grads, loss, pred [n_saves][N][O])."""
+        O, Fn = self.cfg.O, self.cfg.Fn
+        if int(n_saves) < 1:
+            raise ValueError("n_saves must be >= 1")
+        d = _capi.MgnRolloutDesc()
+        d.solver = {"Euler": 0, "Tsit5": 1}[solver]
+        d.t0, d.t1, d.dt, d.saves_dt, d.n_saves = t0, t1, dt, saves_dt, n_saves
+        if inflow_rule not in ("reference", "tolerant"):
+            raise ValueError(f"inflow_rule must be 'reference' or 'tolerant', got {inflow_rule!r}")
+        d.inflow_rule = {"reference": 0, "tolerant": 1}[inflow_rule]
+        d.time_f64 = 1 if np.dtype(time_type) == np.float64 else 0
+        d.t0_f64, d.t1_f64, d.dt_f64, d.saves_dt_f64 = t0, t1, dt, saves_dt
+        x0 = _c32(x0, (self.N, O))
+        oh = _c32(node_type_onehot, (self.N, Fn - O)) if Fn > O else None
+        ef = _c32(ef_raw, (self.E, self.cfg.Fe))
+        vm = _c32(val_mask, (self.N,)) if val_mask is not None else None
+        if (inflow_mask is None) != (inflow_data is None):
+            raise ValueError("inflow_mask and inflow_data go together")
+        im = np.ascontiguousarray(inflow_mask, dtype=np.uint8).reshape(self.N) if inflow_mask is not None else None
+        idata = _c32(inflow_data) if inflow_data is not None else None
+        if idata is not None and (idata.ndim != 3 or idata.shape[1:] != (self.N, O)):
+            raise ValueError("DimensionMismatch: inflow_data must be [frames][N][O]")
+        gt, p_gt = _host_or_device(gt, (n_saves, self.N, O))
+        ls = _c32(loss_scale, (O,)) if loss_scale is not None else None
+        ct, p_ct = _host_or_device(cont_target, (self.N, O)) if cont_target is not None else (None, None)
+        if out is None:
+            out = np.zeros(self.param_count, np.float32)
+        gs, p_gs = _host_or_device(out, (self.param_count,), writable=True)
+        pred = np.zeros((n_saves, self.N, O), np.float32) if want_pred else None
+        d.x0, d.node_type_onehot, d.ef_raw, d.val_mask = f32(x0), f32(oh), f32(ef), f32(vm)
+        d.inflow_mask = im.ctypes.data_as(C.POINTER(C.c_uint8)) if im is not None else None
+        d.inflow_data = f32(idata)
+        d.n_frames = idata.shape[0] if idata is not None else 0
+        d.out = f32(pred)
+        loss = C.c_float()
+        self._chk(self.lib.mgn_solver_grad(self.h, C.byref(d), p_gt, f32(ls), p_ct, float(cont_weight), p_gs, self.param_count,
+                                           C.byref(loss)))
+        return (gs, loss.value, pred) if want_pred else (gs, loss.value)
+
     def step(self, nf, ef, target, mask, mask_index_base=0, out=None):
         """step!(mgn, graph, target, mask, mse_reduce) (reference src/strategies.jl:418-422): returns (gs, loss) with gs
         in the packed order of set_params.  nf / ef / target may be NumPy arrays or contiguous fp32 torch tensors on

@@ -9,6 +9,7 @@ functions are written here in NumPy float32 to drive the engine exactly the way 
     ode_func_eval          reference src/solve.jl:147-158
     ode_step               reference src/solve.jl:188-219
     rollout (Euler branch) reference src/solve.jl:42-68  (`solve(prob, solver; adaptive=false, dt, saveat)`)
+    train_step (solver strategies with Euler())  reference src/strategies.jl:175-196, 238-383 (Engine.solver_grad per solved window)
     GraphNetCore surface   one_hot, triangles_to_edges, parse_edges, mse_reduce, NormaliserOfflineMinMax,
                            NormaliserOfflineMeanStd, NormaliserOnline, inverse_data (docs/src/graph_net_core.md)
 
@@ -417,3 +418,61 @@ def solver_training_euler(rhs, vjp, x0, gt, dt, val_mask, n_scale):
         gs = np.asarray(g, np.float64) if gs is None else gs + g
         a = dl_dx(k) + a + np.asarray(xbar, np.float64)
     return gs, loss, xs
+
+
+def _range_length(tstart, dt, tstop):
+    """length(tstart:dt:tstop)."""
+    return int(np.floor((float(tstop) - float(tstart)) / float(dt) + 1e-4)) + 1
+
+
+def _range_at(tstart, dt, i, time_type):
+    """(tstart:dt:tstop)[i + 1] in the range's element type."""
+    return float(np.dtype(time_type).type(float(tstart) + i * float(dt)))
+
+
+def multiple_shooting_ranges(T, interval_size):
+    """The windows of train_loss(::MultipleShooting) (reference src/strategies.jl:336-337),
+    `ranges = [i:min(T, i + interval_size - 1) for i in 1:(interval_size - 1):(T - 1)]`, as 0-based inclusive (first, last) pairs:
+    consecutive windows share their end point."""
+    if interval_size < 2:
+        raise ValueError("interval_size must be >= 2")
+    return [(i - 1, min(T, i + interval_size - 1) - 1) for i in range(1, T, interval_size - 1)]
+
+
+def train_step_solver_training(eng, gt, node_type_onehot, ef_raw, tstart, dt, tstop, val_mask=None, inflow_mask=None, inflow_data=None,
+                               n_scale=None, solver_dt=None, time_type=F32, inflow_rule="reference", out=None):
+    """train_step(::SolverTraining) with a fixed-step Euler solver (reference src/strategies.jl:175-196, 257-292) in one native call:
+    u0 = gt[1], saveat = tstart:dt:tstop, loss = mean(((n_norm(gt) - n_norm(pred)) .^ 2) .* val_mask).  gt [T][N][O] (the trajectory's
+    target fields, T >= the number of save points); n_scale [O]: scale of the field normaliser (its shift cancels); inflow_mask [N]:
+    rows overwritten inside the right-hand side from inflow_data [frames][N][O] (default: gt itself, data[field] of ode_func_train,
+    src/solve.jl:101-117); solver_dt: the Euler step (default dt, the example's tstops = saveat).  Returns (gs, loss): the discrete
+    adjoint of the computed Euler solution."""
+    n_saves = _range_length(tstart, dt, tstop)
+    if inflow_mask is not None and inflow_data is None:
+        inflow_data = gt
+    return eng.solver_grad(np.asarray(gt[0]), node_type_onehot, ef_raw, gt[:n_saves], tstart, tstop, solver_dt or dt, dt, n_saves,
+                           val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=inflow_data, loss_scale=n_scale, inflow_rule=inflow_rule,
+                           time_type=time_type, out=out)
+
+
+def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, tstop, interval_size, continuity_term, val_mask=None,
+                                 inflow_mask=None, inflow_data=None, solver_dt=None, time_type=F32, inflow_rule="reference"):
+    """train_step(::MultipleShooting) with a fixed-step Euler solver (reference src/strategies.jl:312-383): one Engine.solver_grad per
+    window rg of multiple_shooting_ranges, u0 = gt[first(rg)], saveat = tsteps[rg], loss = mean((gt[rg] - pred) .^ 2 .* val_mask) (no
+    normaliser); the continuity term continuity_term * sum(abs, pred_{i-1}[end] - gt[first(rg_i)]) goes with window i - 1.  Returns the
+    summed (gs, loss)."""
+    T = _range_length(tstart, dt, tstop)
+    ranges = multiple_shooting_ranges(T, interval_size)
+    if inflow_mask is not None and inflow_data is None:
+        inflow_data = gt
+    gs_sum, loss_sum = None, 0.0
+    for i, (a, b) in enumerate(ranges):
+        nxt = ranges[i + 1][0] if i + 1 < len(ranges) else None
+        gs, loss = eng.solver_grad(np.asarray(gt[a]), node_type_onehot, ef_raw, gt[a:b + 1], _range_at(tstart, dt, a, time_type),
+                                   _range_at(tstart, dt, b, time_type), solver_dt or dt, dt, b - a + 1, val_mask=val_mask,
+                                   inflow_mask=inflow_mask, inflow_data=inflow_data, cont_target=None if nxt is None else gt[nxt],
+                                   cont_weight=float(continuity_term) if nxt is not None else 0.0, inflow_rule=inflow_rule,
+                                   time_type=time_type)
+        gs_sum = np.asarray(gs, np.float64) if gs_sum is None else gs_sum + gs
+        loss_sum += float(loss)
+    return gs_sum, loss_sum
