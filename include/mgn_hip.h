@@ -281,7 +281,7 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d);
  * strategies.jl:175-196) -- what train_step(::SolverTraining) (strategies.jl:257-292) and one window of train_step(::MultipleShooting)
  * (:312-383) differentiate, with no host work per step and one synchronisation at the end.
  * d is read as mgn_rollout reads it (same fields, time type, inflow_rule, Euler time loop and save rule), with two differences: only
- * solver 0 (Euler; Tsit5 answers MGN_E_UNSUPPORTED), and the inflow overwrite takes ode_func_train's form -- the rows go into a COPY the
+ * solver 0 (Euler; Tsit5 answers MGN_E_UNSUPPORTED: it is mgn_solver_grad_tsit5), and the inflow overwrite takes ode_func_train's form -- the rows go into a COPY the
  * right-hand side is evaluated on, the state itself is never overwritten.  Every save point must be reached (else MGN_E_ARG).
  *   loss = mean over (save s, node n, component o) of (loss_scale[o] (gt[s][n][o] - x_s[n][o]))^2 vm[n]  +  cont_weight sum |x_end - cont_target|
  * with the mean over n_saves * N * O, vm = d->val_mask (NULL: 1), loss_scale [O] (NULL: 1; the scale of the field normaliser, whose shift
@@ -294,6 +294,42 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d);
  * Bitwise repeatable (reductions in a fixed order).                                                                                  */
 int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt /* [n_saves][N][O] */, const float* loss_scale /* [O] or NULL */,
                     const float* cont_target /* [N][O] or NULL */, float cont_weight, float* grads, size_t n_grads, float* loss);
+
+/* ---- solver-based training with Tsit5 (the package's default solver, src/MeshGraphNets.jl:53): mgn_solver_grad's loss (same gt,
+ * loss_scale, cont_target, cont_weight, grads, loss; same host-or-device rules and refusals) of one window of ode_func_train solved by
+ * the Tsitouras 5(4) pair, and its gradient.  d is read as mgn_solver_grad reads it, with d->solver = 1 (else MGN_E_ARG); d->out receives
+ * the predicted saves, d->n_accept / n_reject / n_rhs are filled.  For accepted step n from t_n with size h_n, i = 1 .. 6 (A[i][j] 1-based,
+ * b = A[7]):
+ *   y_{n,i} = x_n + h_n sum_{j<i} A[i][j] k_{n,j};   z_{n,i} = y_{n,i} with the inflow rows of frame(t_n + c_i h_n) (a COPY);
+ *   k_{n,i} = f(z_{n,i});   x_{n+1} = x_n + h_n sum_i A[7][i] k_{n,i}   (k_7 = f(z_{n+1,1}), FSAL, feeds the error estimate only)
+ * The gradient is the DISCRETE ADJOINT OF THE COMPUTED SOLUTION WITH THE ACCEPTED STEP SEQUENCE HELD FIXED: step sizes and accept / reject
+ * decisions are constants (the error norm carries no derivative), rejected trials contribute nothing -- the usual convention for
+ * differentiating through an adaptive integrator; it is not InterpolatingAdjoint's continuous adjoint.  Reverse, from lam = dL/dx_{n+1}:
+ *   for i = 6 .. 1:  kbar_i = h_n (A[7][i] lam + sum_{j>i} A[j][i] ybar_j);  zbar_i, g_i = VJP of f at z_{n,i};  ybar_i = zbar_i with
+ *   the inflow rows zeroed;  gs += g_i.        dL/dx_n = lam + sum_i ybar_i + the save / continuity terms at x_n.
+ * Step modes (o->adaptive):
+ *   1: solve(prob, Tsit5(); saveat = saves, tstops = saves) -- mgn_rollout's Tsit5 unchanged: first step d->dt (0: Hairer-Wanner), PI
+ *      controller, d->abstol / d->reltol, stops, stage times.  The error norm is taken on the states, which are not overwritten: with an
+ *      inflow mask the steps can differ from mgn_rollout's, which overwrites in place.  The stage-7 input is z_{n+1,1} and sees t_{n+1}.
+ *      More than 100 000 accepted steps (OrdinaryDiffEq's maxiters) or a NaN error estimate: MGN_E_STATE.
+ *   0: solve(...; adaptive = false, dt): steps of d->dt on mgn_solver_grad's Euler time grid and save rule (last step snapped onto t1;
+ *      every save must be reached, else MGN_E_ARG).  Its loss is a smooth function of the parameters.
+ * Every save is stepped onto (tstops = saves); a MultipleShooting window solved without tstops interpolates its saves in the reference.
+ * Memory: the six stage inputs z_{n,1..6} of every accepted step, 6 N O floats per step, in chunks kept on the handle and grown as steps
+ * are accepted; allocation failure or more than o->max_store_bytes (0: no limit) is MGN_E_OOM, and the handle stays usable.
+ * Bitwise repeatable.                                                                                                               */
+typedef struct mgn_solver_grad_opts {
+    int32_t adaptive;          /* 1: PI-controlled steps with tstops = saves (mgn_rollout's Tsit5); 0: fixed steps of d->dt         */
+    int32_t step_cap;          /* capacity of step_t / step_h (0: no record)                                                       */
+    double* step_t;            /* out [step_cap] or NULL: start time of every accepted step, in the solver's time type               */
+    double* step_h;            /* out [step_cap] or NULL: the h the stage combinations of that step used                             */
+    size_t max_store_bytes;    /* 0: bounded by device memory only; else the stored stage inputs may not exceed it (MGN_E_OOM)       */
+    int32_t n_steps;           /* out: accepted steps (only the first step_cap are recorded)                                         */
+    size_t stored_bytes;       /* out: bytes the stored stage inputs took                                                            */
+} mgn_solver_grad_opts;
+int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt /* [n_saves][N][O] */,
+                          const float* loss_scale /* [O] or NULL */, const float* cont_target /* [N][O] or NULL */, float cont_weight,
+                          float* grads, size_t n_grads, float* loss);
 
 /* ---- training step -------------------------------------------------------
  * GraphNetCore.step!(mgn, graph, target, mask, mse_reduce) as called at reference src/strategies.jl:418-422 and

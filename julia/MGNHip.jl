@@ -29,7 +29,7 @@ export NormaliserOffline, NormaliserOfflineMinMax, NormaliserOfflineMeanStd, Nor
 export FeatureGraph, GraphNetwork, step!, load, save!
 # engine extras (optional fast paths; none is needed for the drop-in)
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
-       native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, native_solver_train_step
+       native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
 export comm_unique_id, comm_init!, comm_init_file!, comm_barrier, processor_steps_dev!
 
 const LIB = get(ENV, "MGN_HIP_LIB", joinpath(@__DIR__, "..", "meshgraphnets.jl_amd", "lib", "libmgn_hip.so"))
@@ -78,6 +78,16 @@ mutable struct MgnRolloutDesc   # mirrors `mgn_rollout_desc` (include/mgn_hip.h)
     t1_f64::Float64
     dt_f64::Float64
     saves_dt_f64::Float64
+end
+
+mutable struct MgnSolverGradOpts   # mirrors `mgn_solver_grad_opts` (include/mgn_hip.h), field for field
+    adaptive::Int32
+    step_cap::Int32
+    step_t::Ptr{Float64}
+    step_h::Ptr{Float64}
+    max_store_bytes::Csize_t
+    n_steps::Int32
+    stored_bytes::Csize_t
 end
 
 function check(h::Ptr{Cvoid}, rc::Cint)
@@ -629,11 +639,60 @@ function solver_grad(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::M
 end
 
 """
+    solver_grad_tsit5(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, start, stop, saves;
+                      dt = 0, adaptive = true, abstol = 1f-6, reltol = 1f-3, loss_scale = nothing, cont_target = nothing,
+                      cont_weight = 0f0) -> (gs, loss, pred::Array{Float32, 3}, step_t::Vector{Float64}, step_h::Vector{Float64})
+
+`solver_grad` for Tsit5 (mgn_solver_grad_tsit5): `adaptive = true` is `solve(prob, Tsit5(); saveat = saves, tstops = saves)` with
+native_rollout's controller (first step `dt`, 0: Hairer-Wanner); `adaptive = false` is fixed steps of `dt` on solver_grad's time grid.
+`gs` is the discrete adjoint of the computed solution with the accepted step sequence (returned) held fixed -- not
+InterpolatingAdjoint's continuous adjoint.
+"""
+function solver_grad_tsit5(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
+        val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
+        inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, start, stop, saves;
+        dt = zero(eltype(saves)), adaptive = true, abstol = 1.0f-6, reltol = 1.0f-3,
+        loss_scale::Union{Nothing, Vector{Float32}} = nothing, cont_target::Union{Nothing, Matrix{Float32}} = nothing, cont_weight = 0.0f0,
+        tolerant_inflow = false)
+    ps = mgn.ps::Vector{Float32}
+    sync_params!(mgn, ps)
+    O, N = size(x0)
+    ns = length(saves)
+    size(gt, 3) >= ns || throw(DimensionMismatch("gt has $(size(gt, 3)) frames, the solve saves $ns"))
+    g = Array{Float32, 3}(gt[:, :, 1:ns])
+    out = Array{Float32, 3}(undef, O, N, ns)
+    gs = Vector{Float32}(undef, length(ps))
+    loss = Ref{Float32}(0)
+    sdt = ns > 1 ? saves[2] - saves[1] : one(eltype(saves))
+    f64 = eltype(saves) == Float64
+    cap = adaptive ? 4096 : round(Int, (stop - start) / dt) + 2
+    while true
+        st = Vector{Float64}(undef, cap); sh = Vector{Float64}(undef, cap)
+        d = MgnRolloutDesc(1, start, stop, dt, sdt, ns, abstol, reltol,
+            pointer(x0), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
+            inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
+            inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
+            start, stop, dt, sdt)
+        o = MgnSolverGradOpts(adaptive ? 1 : 0, cap, pointer(st), pointer(sh), 0, 0, 0)
+        # (@ccall: tests/test_solver_train_tsit5_host.py checks this call against the header)
+        rc = GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out g loss_scale cont_target gs st sh @ccall LIB.mgn_solver_grad_tsit5(
+            mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, o::Ref{MgnSolverGradOpts}, g::Ptr{Float32}, opt_ptr(loss_scale)::Ptr{Float32},
+            opt_ptr(cont_target)::Ptr{Float32}, Float32(cont_weight)::Float32, gs::Ptr{Float32}, length(gs)::Csize_t, loss::Ref{Float32})::Cint
+        check(mgn.handle, rc)
+        if o.n_steps <= cap
+            return gs, loss[], out, st[1:o.n_steps], sh[1:o.n_steps]
+        end
+        cap = o.n_steps          # the record was cut: again with room for every step (the call is bitwise repeatable)
+    end
+end
+
+"""
     native_solver_train_step(strategy, mgn, gt, node_type_onehot, edge_features, val_mask_row, inflow_mask_row;
                              n_scale = nothing, inflow_data = gt) -> (gs, loss)
 
 `train_step(::SolverTraining)` / `train_step(::MultipleShooting)` (src/strategies.jl:175-196, 257-292, 312-383) for a strategy with
-`Euler()` as its solver, through `solver_grad`: SolverTraining is one solve from `gt[:, :, 1]` over `tstart:dt:tstop` with the field
+`Euler()` or `Tsit5()` as its solver, through `solver_grad` / `solver_grad_tsit5` (Tsit5: adaptive unless `solargs.adaptive == false`,
+`abstol` / `reltol` from `solargs`, default 1e-6 / 1e-3; every window steps onto its saves): SolverTraining is one solve from `gt[:, :, 1]` over `tstart:dt:tstop` with the field
 normaliser's scale `n_scale` in the loss; MultipleShooting one solve per window of the reference's own
 `[i:min(T, i + interval_size - 1) for i in 1:(interval_size - 1):(T - 1)]` from `gt[:, :, first(rg)]`, no normaliser, and the continuity
 term of window i attached to window i - 1.  The Euler step is `solargs.dt` when given, else `strategy.dt` (the example's
@@ -645,14 +704,22 @@ InterpolatingAdjoint's continuous approximation the reference defaults to.  Opt-
 function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
         edge_features::Matrix{Float32}, val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}};
         n_scale::Union{Nothing, Vector{Float32}} = nothing, inflow_data::Union{Nothing, Array{Float32, 3}} = gt)
-    nameof(typeof(strategy.solver)) == :Euler || throw(ArgumentError("native_solver_train_step drives Euler(); got $(strategy.solver)"))
+    sname = nameof(typeof(strategy.solver))
+    sname in (:Euler, :Tsit5) || throw(ArgumentError("native_solver_train_step drives Euler() and Tsit5(); got $(strategy.solver)"))
     tsteps = (strategy.tstart):(strategy.dt):(strategy.tstop)
     sargs = hasproperty(strategy, :solargs) ? strategy.solargs : (;)
-    dt = haskey(sargs, :dt) ? sargs[:dt] : strategy.dt
+    adaptive = sname == :Tsit5 && get(sargs, :adaptive, true) != false
+    dt = haskey(sargs, :dt) ? sargs[:dt] : (adaptive ? zero(strategy.dt) : strategy.dt)
+    abstol = Float32(get(sargs, :abstol, 1e-6)); reltol = Float32(get(sargs, :reltol, 1e-3))
     im = inflow_mask_row === nothing ? nothing : inflow_data
+    function window(x0, g, t0, t1, saves; kw...)
+        sname == :Euler && return solver_grad(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, dt, saves; kw...)
+        gs, loss, pred, _, _ = solver_grad_tsit5(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, saves;
+            dt = dt, adaptive = adaptive, abstol = abstol, reltol = reltol, kw...)
+        return gs, loss, pred
+    end
     if !hasproperty(strategy, :interval_size)      # SolverTraining
-        gs, loss, _ = solver_grad(mgn, gt[:, :, 1], node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, gt,
-            strategy.tstart, strategy.tstop, dt, tsteps; loss_scale = n_scale)
+        gs, loss, _ = window(gt[:, :, 1], gt, strategy.tstart, strategy.tstop, tsteps; loss_scale = n_scale)
         return (gs,), loss
     end
     T = length(tsteps)
@@ -661,8 +728,7 @@ function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32
     for (i, rg) in enumerate(ranges)
         last_window = i == length(ranges)
         ct = last_window ? nothing : gt[:, :, first(ranges[i + 1])]
-        gs, loss, _ = solver_grad(mgn, gt[:, :, first(rg)], node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im,
-            gt[:, :, rg], tsteps[first(rg)], tsteps[last(rg)], dt, tsteps[rg];
+        gs, loss, _ = window(gt[:, :, first(rg)], gt[:, :, rg], tsteps[first(rg)], tsteps[last(rg)], tsteps[rg];
             cont_target = ct, cont_weight = last_window ? 0.0f0 : Float32(strategy.continuity_term))
         gs_sum .+= gs; loss_sum += loss
     end

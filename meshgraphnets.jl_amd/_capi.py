@@ -36,6 +36,11 @@ class MgnRolloutDesc(C.Structure):
                 ("t0_f64", C.c_double), ("t1_f64", C.c_double), ("dt_f64", C.c_double), ("saves_dt_f64", C.c_double)]
 
 
+class MgnSolverGradOpts(C.Structure):
+    _fields_ = [("adaptive", C.c_int32), ("step_cap", C.c_int32), ("step_t", C.POINTER(C.c_double)), ("step_h", C.POINTER(C.c_double)),
+                ("max_store_bytes", C.c_size_t), ("n_steps", C.c_int32), ("stored_bytes", C.c_size_t)]
+
+
 ABI_VERSION = 4      # MGN_ABI_VERSION of include/mgn_hip.h these mirrors were written against (tests/test_julia_shim.py compares)
 
 _f32p = C.POINTER(C.c_float)
@@ -85,6 +90,8 @@ PROTOTYPES = {
     "mgn_edge_set_export": (C.c_int, [_H, C.c_int32, _i32p, _i32p]),
     "mgn_rollout": (C.c_int, [_H, C.POINTER(MgnRolloutDesc)]),
     "mgn_solver_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f32p, _f32p, _f32p, C.c_float, _f32p, C.c_size_t, _f32p]),
+    "mgn_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float, _f32p,
+                                        C.c_size_t, _f32p]),
     "mgn_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
     "mgn_ode_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
     "mgn_forward_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),

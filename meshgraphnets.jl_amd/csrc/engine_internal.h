@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <exception>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -147,6 +148,7 @@ struct mgn_engine {
     DevBuf gwork, gout, gpos, gtype;   // device-side graph prologue (csrc/graph_dev.hip): scratch, outputs, positions, node types
     DevBuf d_stamps;  // diagnostic builds only
     DevBuf ode;       // native rollout: state, stages, frames, saves, Elat0
+    std::vector<std::unique_ptr<DevBuf>> tsit5_store;   // mgn_solver_grad_tsit5: chunks of stored stage inputs, grown as steps are accepted, kept across calls
     const float* srcA_override = nullptr;  // rollout: encoder reads the node state from here instead of d_nfA
     const float* elat_src_override = nullptr;   // right-hand sides on small meshes: step 0's edge kernel reads the trajectory's encoded edge latents from here (EdgeArgs::ElatSrc) instead of a restore copy into Elat
     float* out_override = nullptr;         // rollout: decoder writes dx/dt here instead of d_out
@@ -228,6 +230,15 @@ struct SolverSweep {
 };
 int solver_prepare(mgn_engine* h, size_t n_grads);
 int solver_sweep(mgn_engine* h, const SolverSweep& S);
+// mgn_solver_grad_tsit5: S as for Euler with K = the accepted Tsit5 steps, save_step counting them, states / dt unused, a = dL/dx (lam)
+struct Tsit5Sweep {
+    const float* const* steps;           // [K] (host): step n's stored stage inputs z_{n,1 .. 6}, [6][N][O] each
+    const double* h;                     // [K] (host): the step sizes
+    const float* xend;                   // [N][O]: x_K (continuity term)
+    float* ybar;                         // scratch [5][N][O]: ybar_2 .. ybar_6 of the step being swept
+};
+int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5);
+double tsit5_a(int i, int j);          // the Tsit5 tableau (mgn_api.cpp), 1-based: A[i][j], b = A[7][j]
 
 #define HIPCHK(h, expr)                                                                              \
     do {                                                                                             \

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <ctime>
 #include <string>
 #include <sys/stat.h>
@@ -1783,6 +1784,12 @@ const double TS_A[7][6] = {
 const double TS_BT[7] = {-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629,
                          0.5823571654525552, -0.45808210592918697, 0.015151515151515152};
 
+}  // namespace
+
+extern "C++" double mgn::tsit5_a(int i, int j) { return TS_A[i - 1][j - 1]; }   // (this region is extern "C")
+
+namespace {
+
 struct Rollout {
     mgn_engine* h;
     mgn_rollout_desc* d;
@@ -1906,6 +1913,86 @@ struct Rollout {
         *out = std::sqrt(s / (double)(ng > 0 ? ng : 1));
         return MGN_OK;
     }
+
+    // ---- Tsit5, shared by mgn_rollout and mgn_solver_grad_tsit5 ----
+    // Training form (mgn_solver_grad_tsit5, ode_func_train): the right-hand side of a stage sees a COPY of the stage's combination with
+    // the inflow rows written -- za for stage 1 (z_{n,1}), zs for stages 2 .. 6, z7 for stage 7 (z_{n+1,1}) -- and the state is never
+    // overwritten.  mgn_rollout (train = false), or no inflow mask: the combination itself (mgn_rollout overwrites it in place).
+    bool train = false;
+    float *za = nullptr, *zs = nullptr, *z7 = nullptr;
+    std::function<int(int, const float*)> keep;     // training form: after stage i (1 .. 5, 0-based) of a trial, the array its RHS saw
+
+    int eval(float* y, float* z, double t, float* kout) {
+        if (train && mask) {
+            HIPCHK(h, hipMemcpyAsync(z, y, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+            y = z;
+        }
+        return rhs(y, t, kout);
+    }
+    // k1 = f(u) at t (FSAL afterwards)
+    int tsit5_first(double t) { return eval(u, za, t, k[0]); }
+    // Hairer-Wanner starting step from (u, k1)
+    int tsit5_h0(double t, double* dt) {
+        double d0, d1, d2;
+        LinComb l1{1, {1.f}, {k[0]}};
+        // d0 = ||u||, d1 = ||f0|| in the scaled norm: errnorm(dt = 1) of u and k1 themselves
+        LinComb lu{1, {1.f}, {u}};
+        if (int rc = norm(u, u, lu, 1.f, &d0)) return rc;
+        if (int rc = norm(u, u, l1, 1.f, &d1)) return rc;
+        const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+        HIPCHK(h, launch_lincomb(utmp, u, l1, (float)h0, n, h->stream));
+        if (int rc = eval(utmp, zs, tt(t + h0), k[1])) return rc;
+        LinComb ld{2, {1.f, -1.f}, {k[1], k[0]}};
+        if (int rc = norm(u, u, ld, (float)(1.0 / h0), &d2)) return rc;
+        const double mx = d1 > d2 ? d1 : d2;
+        const double h1 = mx <= 1e-15 ? (h0 * 1e-3 > 1e-6 ? h0 * 1e-3 : 1e-6) : std::pow(0.01 / mx, 1.0 / 5);
+        *dt = 100 * h0 < h1 ? 100 * h0 : h1;
+        return MGN_OK;
+    }
+    // one trial step from (u, k1) over hstep: stages 2 .. 6 at tt(t + tt(c_i hstep)), unew = u + hstep sum_j A[7][j] k_j, and k7 = f(unew)
+    // at t7 (FSAL); EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H
+    int tsit5_trial(double t, double hstep, double t7, double* EEst) {
+        for (int sidx = 1; sidx < 7; ++sidx) {     // stages 2..7; stage 7 is evaluated on unew (FSAL)
+            LinComb lc{sidx, {}, {}};
+            for (int j = 0; j < sidx; ++j) { lc.c[j] = (float)TS_A[sidx][j]; lc.k[j] = k[j]; }
+            float* dst = (sidx == 6) ? unew : utmp;
+            HIPCHK(h, launch_lincomb(dst, u, lc, (float)hstep, n, h->stream));
+            float* z = (sidx == 6) ? z7 : zs;
+            if (int rc = eval(dst, z, sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep)), k[sidx])) return rc;
+            if (sidx < 6 && keep)
+                if (int rc = keep(sidx, (train && mask) ? z : dst)) return rc;
+        }
+        if (!EEst) return MGN_OK;
+        LinComb le{7, {}, {}};
+        for (int j = 0; j < 7; ++j) { le.c[j] = (float)TS_BT[j]; le.k[j] = k[j]; }
+        return norm(u, unew, le, (float)hstep, EEst);
+    }
+    // the accepted trial becomes the state: unew -> u, k7 -> k1 (FSAL), z_{n+1,1} -> za
+    void tsit5_advance() {
+        std::swap(u, unew);
+        std::swap(k[0], k[6]);
+        std::swap(za, z7);
+    }
+};
+
+// mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
+// of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
+struct Tsit5Control {
+    static constexpr double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
+    double qold = 1e-4;
+    bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
+        const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
+        if (EEst <= 1.0) {
+            double q = q11 / std::pow(qold, beta2);
+            q = std::max(1.0 / qmax, std::min(1.0 / qmin, q / gamma));
+            qold = std::max(EEst, 1e-4);
+            if (!hit_stop || hstep >= dt * (1 - 1e-9)) dt = hstep / q;
+            else dt = std::max(dt, hstep / q);
+            return true;
+        }
+        dt = hstep / std::min(1.0 / qmin, q11 / gamma);
+        return false;
+    }
 };
 
 }  // namespace
@@ -2022,29 +2109,12 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
             while (saved < d->n_saves && stop_time(saved) <= t + 0.25 * dt) HIPCHK(h, save());
         }
     } else {
-        // adaptive Tsit5, PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10), tstops = saves
-        const double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
-        double qold = 1e-4;
-        if (int rc = R.rhs(R.u, t, R.k[0])) return rc;     // k1 (FSAL afterwards)
+        // adaptive Tsit5, PI controller, tstops = saves
+        Tsit5Control ctl;
+        if (int rc = R.tsit5_first(t)) return rc;     // k1 (FSAL afterwards)
         double dt = DT;
-        if (dt <= 0) {   // Hairer-Wanner starting step
-            LinComb z{0, {}, {}};
-            double d0, d1, d2;
-            LinComb l1{1, {1.f}, {R.k[0]}};
-            // d0 = ||u||, d1 = ||f0|| in the scaled norm: errnorm(dt = 1) of u and k1 themselves
-            LinComb lu{1, {1.f}, {R.u}};
-            if (int rc = R.norm(R.u, R.u, lu, 1.f, &d0)) return rc;
-            if (int rc = R.norm(R.u, R.u, l1, 1.f, &d1)) return rc;
-            const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-            HIPCHK(h, launch_lincomb(R.utmp, R.u, l1, (float)h0, R.n, h->stream));
-            if (int rc = R.rhs(R.utmp, tt(t + h0), R.k[1])) return rc;
-            LinComb ld{2, {1.f, -1.f}, {R.k[1], R.k[0]}};
-            if (int rc = R.norm(R.u, R.u, ld, (float)(1.0 / h0), &d2)) return rc;
-            const double mx = d1 > d2 ? d1 : d2;
-            const double h1 = mx <= 1e-15 ? (h0 * 1e-3 > 1e-6 ? h0 * 1e-3 : 1e-6) : std::pow(0.01 / mx, 1.0 / 5);
-            dt = 100 * h0 < h1 ? 100 * h0 : h1;
-            (void)z;
-        }
+        if (dt <= 0)   // Hairer-Wanner starting step
+            if (int rc = R.tsit5_h0(t, &dt)) return rc;
         const double tend = T1;
         int guard = 0;
         // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save
@@ -2055,34 +2125,17 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
             bool hit_stop = false;
             double hstep = dt;
             if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
-            for (int sidx = 1; sidx < 7; ++sidx) {     // stages 2..7; stage 7 is evaluated on unew (FSAL)
-                LinComb lc{sidx, {}, {}};
-                for (int j = 0; j < sidx; ++j) { lc.c[j] = (float)TS_A[sidx][j]; lc.k[j] = R.k[j]; }
-                float* dst = (sidx == 6) ? R.unew : R.utmp;
-                HIPCHK(h, launch_lincomb(dst, R.u, lc, (float)hstep, R.n, h->stream));
-                // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
-                if (int rc = R.rhs(dst, (sidx == 6 && hit_stop) ? tstop : tt(t + tt(TS_C[sidx] * hstep)), R.k[sidx])) return rc;
-            }
-            LinComb le{7, {}, {}};
-            for (int j = 0; j < 7; ++j) { le.c[j] = (float)TS_BT[j]; le.k[j] = R.k[j]; }
+            // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
             double EEst;
-            if (int rc = R.norm(R.u, R.unew, le, (float)hstep, &EEst)) return rc;
+            if (int rc = R.tsit5_trial(t, hstep, hit_stop ? tstop : tt(t + tt(TS_C[6] * hstep)), &EEst)) return rc;
             if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "mgn_rollout: NaN in the error estimate at t = %g", t);
-            const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
-            if (EEst <= 1.0) {
-                double q = q11 / std::pow(qold, beta2);
-                q = std::max(1.0 / qmax, std::min(1.0 / qmin, q / gamma));
-                qold = std::max(EEst, 1e-4);
-                std::swap(R.u, R.unew);
-                std::swap(R.k[0], R.k[6]);            // FSAL: k1 of the next step = f(unew)
+            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
+                R.tsit5_advance();
                 t = hit_stop ? tstop : tt(t + hstep);
                 ++d->n_accept;
-                if (!hit_stop || hstep >= dt * (1 - 1e-9)) dt = hstep / q;   // a step cut by a stop does not shrink dt
-                else dt = std::max(dt, hstep / q);
                 if (hit_stop && saved < d->n_saves && std::fabs(stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12) HIPCHK(h, save());
             } else {
                 ++d->n_reject;
-                dt = hstep / std::min(1.0 / qmin, q11 / gamma);
             }
         }
     }
@@ -2105,39 +2158,152 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     return MGN_OK;
 } MGN_CATCH(h)
 
-// ---- solver-based training (SolverTraining / MultipleShooting with Euler()): loss and gradient of one solved window ---------------
-// Forward: the Euler loop of mgn_rollout on the resident right-hand side (the same launches, the same hipGraph replay), in the training
-// form of the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the array every
-// step's RHS saw.  Backward: solver_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
+// ---- solver-based training (SolverTraining / MultipleShooting): loss and gradient of one solved window ------------------------------
+// Forward: mgn_rollout's time loop on the resident right-hand side (the same launches, the same hipGraph replay), in the training form of
+// the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the arrays the RHS saw.
+// Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
+namespace {
+
+// the checks mgn_solver_grad and mgn_solver_grad_tsit5 share (everything but the solver)
+int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss) {
+    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
+    const mgn_config& c = h->cfg;
+    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
+    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
+    if (int rc = need(h, true, true, c.ln_dims != MGN_LN_ALL, true)) return rc;
+    if (!d || !gt || !grads || !loss || !d->x0 || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
+    return MGN_OK;
+}
+
+int solver_checks2(mgn_handle* h, mgn_rollout_desc* d, const char* who, float cont_weight) {
+    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "%s: unknown inflow_rule", who);
+    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "%s: inflow mask and data go together", who);
+    if (d->inflow_data && d->n_frames < 1) return fail(h, MGN_E_ARG, "%s: inflow_data needs n_frames >= 1", who);
+    if (!std::isfinite(cont_weight)) return fail(h, MGN_E_ARG, "%s: cont_weight must be finite", who);
+    return MGN_OK;
+}
+
+// the fixed-step time grid of mgn_rollout's Euler loop (t <- t + dt in the time type, the last step snapped onto t1), walked once on the
+// host: the step whose state each save is (every one must be reached)
+int fixed_grid(mgn_handle* h, mgn_rollout_desc* d, const char* who, const Rollout& R, double T0, double T1, double DT, double SDT, int64_t K,
+               std::vector<int64_t>& save_step) {
+    auto stop_time = [&](int i) { return R.tt(T0 + (double)i * SDT); };
+    save_step.assign(1, 0);
+    double t = T0;
+    for (int64_t i = 0; i < K && (int)save_step.size() < d->n_saves; ++i) {
+        t = (i + 1 == K && std::fabs(R.tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : R.tt(t + DT);
+        while ((int)save_step.size() < d->n_saves && stop_time((int)save_step.size()) <= t + 0.25 * DT) save_step.push_back(i + 1);
+    }
+    if ((int)save_step.size() < d->n_saves)
+        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
+                    (int)save_step.size(), stop_time((int)save_step.size()), T1);
+    return MGN_OK;
+}
+
+// entry: x0, frames and the inflow mask into the engine's order (as mgn_rollout), then the static inputs and the encoded edges
+int solver_upload(mgn_handle* h, mgn_rollout_desc* d, Rollout& R, char* base, size_t eb) {
+    const mgn_config& c = h->cfg;
+    const LocalGraph& g = h->g;
+    const int32_t N = g.N;
+    const int O = c.O;
+    const size_t nb = (size_t)R.n * 4, fb = d->inflow_data ? (size_t)d->n_frames * nb : 0;
+    if (!g.renumbered) {
+        HIPCHK(h, hipMemcpyAsync(R.u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
+        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
+        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, d->inflow_mask, (size_t)N, hipMemcpyHostToDevice, h->stream));
+    } else {
+        std::vector<float> lx((size_t)N * O * (1 + (d->inflow_data ? d->n_frames : 0)));
+        std::vector<uint8_t> lm(d->inflow_mask ? (size_t)N : 0);
+        for (int32_t i = 0; i < N; ++i) {
+            const size_t gi = (size_t)g.own_gid[i];
+            memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
+            for (int f = 0; d->inflow_data && f < d->n_frames; ++f)
+                memcpy(lx.data() + ((size_t)(1 + f) * N + i) * O, d->inflow_data + ((size_t)f * N + gi) * O, (size_t)O * 4);
+            if (d->inflow_mask) lm[i] = d->inflow_mask[gi];
+        }
+        HIPCHK(h, hipMemcpyAsync(R.u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
+        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, lx.data() + (size_t)N * O, fb, hipMemcpyHostToDevice, h->stream));
+        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, lm.data(), (size_t)N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (int rc = upload_inputs(h, d->x0, O, d->node_type_onehot, c.Fn - O, d->ef_raw, true)) return rc;
+    h->have_mask = d->val_mask != nullptr;
+    if (d->val_mask) {
+        HIPCHK(h, h->d_mask.ensure((size_t)N * 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
+    if (int rc = encode_impl(h, true, false, true)) return rc;
+    HIPCHK(h, hipMemcpyAsync(base + R.elat0_off, h->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, h->stream));
+    return MGN_OK;
+}
+
+// gt and cont_target (host or device, the caller's order) into the engine's order (gtl, ctl); loss_scale as given (lsd); tmp: [N][O] scratch
+int solver_targets(mgn_handle* h, mgn_rollout_desc* d, int64_t n, const float* gt, const float* cont_target, const float* loss_scale,
+                   float* gtl, float* ctl, float* lsd, float* tmp) {
+    const bool loc = h->g.renumbered;
+    const int32_t N = h->g.N;
+    const int O = h->cfg.O;
+    const size_t nb = (size_t)n * 4;
+    const int32_t* ngid = h->d_own_gid.as<int32_t>();
+    for (int s = 0; s < d->n_saves; ++s) {
+        if (!loc) {
+            HIPCHK(h, hipMemcpyAsync(gtl + (size_t)s * n, gt + (size_t)s * n, nb, hipMemcpyDefault, h->stream));
+        } else {
+            HIPCHK(h, hipMemcpyAsync(tmp, gt + (size_t)s * n, nb, hipMemcpyDefault, h->stream));
+            HIPCHK(h, launch_permute_rows(gtl + (size_t)s * n, tmp, ngid, N, O, false, h->stream));
+        }
+    }
+    if (ctl) {
+        HIPCHK(h, hipMemcpyAsync(loc ? tmp : ctl, cont_target, nb, hipMemcpyDefault, h->stream));
+        if (loc) HIPCHK(h, launch_permute_rows(ctl, tmp, ngid, N, O, false, h->stream));
+    }
+    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)O * 4, hipMemcpyDefault, h->stream));
+    return MGN_OK;
+}
+
+// exit: the predicted saves in the caller's order, and the final synchronisation
+int solver_out(mgn_handle* h, mgn_rollout_desc* d, const Rollout& R) {
+    const LocalGraph& g = h->g;
+    const int O = h->cfg.O;
+    const size_t sb = (size_t)d->n_saves * R.n * 4;
+    if (d->out) {
+        if (g.renumbered) {
+            std::vector<float> sv((size_t)d->n_saves * R.n);
+            HIPCHK(h, hipMemcpyAsync(sv.data(), R.saves, sb, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (int i = 0; i < d->n_saves; ++i)
+                for (int32_t j = 0; j < g.N; ++j)
+                    memcpy(d->out + ((size_t)i * g.N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * g.N + j) * O, (size_t)O * 4);
+        } else {
+            HIPCHK(h, hipMemcpyAsync(d->out, R.saves, sb, hipMemcpyDeviceToHost, h->stream));
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+}
+
+}  // namespace
+
 int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
                     float* grads, size_t n_grads, float* loss) try {
     if (!h) return MGN_E_ARG;
-    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
+    if (int rc = solver_checks(h, d, "mgn_solver_grad", gt, grads, loss)) return rc;
     const mgn_config& c = h->cfg;
-    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", "mgn_solver_grad");
-    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", "mgn_solver_grad");
-    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", "mgn_solver_grad");
-    const bool lnall = c.ln_dims == MGN_LN_ALL;
-    if (int rc = need(h, true, true, !lnall, true)) return rc;
-    if (!d || !gt || !grads || !loss || !d->x0 || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot))
-        return fail(h, MGN_E_ARG, "mgn_solver_grad: null argument");
-    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "mgn_solver_grad: Fn < O");
-    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is not supported");
+    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
     if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
     const bool f64 = d->time_f64 != 0;
     const double T0 = f64 ? d->t0_f64 : (double)d->t0, T1 = f64 ? d->t1_f64 : (double)d->t1, DT = f64 ? d->dt_f64 : (double)d->dt,
                  SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
     if (d->n_saves < 1 || !(SDT > 0.0) || !(T1 >= T0)) return fail(h, MGN_E_ARG, "mgn_solver_grad: bad time grid");
     if (!(DT > 0.0)) return fail(h, MGN_E_ARG, "mgn_solver_grad: Euler needs dt > 0");
-    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "mgn_solver_grad: unknown inflow_rule");
-    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "mgn_solver_grad: inflow mask and data go together");
-    if (d->inflow_data && d->n_frames < 1) return fail(h, MGN_E_ARG, "mgn_solver_grad: inflow_data needs n_frames >= 1");
-    if (!std::isfinite(cont_weight)) return fail(h, MGN_E_ARG, "mgn_solver_grad: cont_weight must be finite");
+    if (int rc = solver_checks2(h, d, "mgn_solver_grad", cont_weight)) return rc;
     const double steps = (T1 - T0) / DT;
     if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "mgn_solver_grad: %.3g Euler steps", steps);
     const int64_t K = (int64_t)std::llround(steps);
 
-    // the time grid of the Euler loop of mgn_rollout, walked once on the host: which step each save is (every one must be reached)
     Rollout R;
     R.h = h;
     R.d = d;
@@ -2146,23 +2312,13 @@ int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const f
     auto tt = [&](double v) { return R.tt(v); };
     auto stop_time = [&](int i) { return tt(T0 + (double)i * SDT); };
     auto next_t = [&](int64_t i, double t) { return (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT); };
-    std::vector<int64_t> save_step(1, 0);
-    {
-        double t = T0;
-        for (int64_t i = 0; i < K && (int)save_step.size() < d->n_saves; ++i) {
-            t = next_t(i, t);
-            while ((int)save_step.size() < d->n_saves && stop_time((int)save_step.size()) <= t + 0.25 * DT) save_step.push_back(i + 1);
-        }
-        if ((int)save_step.size() < d->n_saves)
-            return fail(h, MGN_E_ARG, "mgn_solver_grad: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached",
-                        (int)save_step.size(), stop_time((int)save_step.size()), T1);
-    }
+    std::vector<int64_t> save_step;
+    if (int rc = fixed_grid(h, d, "mgn_solver_grad", R, T0, T1, DT, SDT, K, save_step)) return rc;
     if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
     const LocalGraph& g = h->g;
     invalidate_static(h);
     const int32_t N = g.N;
     const int O = c.O;
-    const bool loc = g.renumbered;
     R.n = (int64_t)N * O;
     R.n_global = R.n;
     R.nrows = N;
@@ -2194,39 +2350,7 @@ int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const f
     R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
     R.partial = nullptr;
     float* states = (float*)(base + o_st);
-
-    // entry: x0, frames and the inflow mask into the engine's order (as mgn_rollout), then the static inputs
-    if (!loc) {
-        HIPCHK(h, hipMemcpyAsync(R.u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
-        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
-        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, d->inflow_mask, (size_t)N, hipMemcpyHostToDevice, h->stream));
-    } else {
-        std::vector<float> lx((size_t)N * O * (1 + (d->inflow_data ? d->n_frames : 0)));
-        std::vector<uint8_t> lm(d->inflow_mask ? (size_t)N : 0);
-        for (int32_t i = 0; i < N; ++i) {
-            const size_t gi = (size_t)g.own_gid[i];
-            memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
-            for (int f = 0; d->inflow_data && f < d->n_frames; ++f)
-                memcpy(lx.data() + ((size_t)(1 + f) * N + i) * O, d->inflow_data + ((size_t)f * N + gi) * O, (size_t)O * 4);
-            if (d->inflow_mask) lm[i] = d->inflow_mask[gi];
-        }
-        HIPCHK(h, hipMemcpyAsync(R.u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
-        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, lx.data() + (size_t)N * O, fb, hipMemcpyHostToDevice, h->stream));
-        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, lm.data(), (size_t)N, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    if (int rc = upload_inputs(h, d->x0, O, d->node_type_onehot, c.Fn - O, d->ef_raw, true)) return rc;
-    h->have_mask = d->val_mask != nullptr;
-    if (d->val_mask) {
-        HIPCHK(h, h->d_mask.ensure((size_t)N * 4));
-        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (lnall) {
-        if (int rc = lnall_rhs_prepare(h)) return rc;
-    } else {
-        if (int rc = encode_impl(h, true, false, true)) return rc;
-        HIPCHK(h, hipMemcpyAsync(base + R.elat0_off, h->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, h->stream));
-    }
+    if (int rc = solver_upload(h, d, R, base, eb)) return rc;
 
     // forward: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k kept for the sweep
     d->n_accept = d->n_reject = 0;
@@ -2251,25 +2375,10 @@ int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const f
     HIPCHK(h, hipMemcpyAsync(states + (size_t)K * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream));
     d->n_rhs = R.n_rhs;
 
-    // gt and cont_target (host or device, the caller's order) into the engine's order; loss_scale as given
     float* gtl = (float*)(base + o_gt);
-    float* tmp = (float*)(base + o_tmp);
-    const int32_t* ngid = h->d_own_gid.as<int32_t>();
-    for (int s = 0; s < d->n_saves; ++s) {
-        if (!loc) {
-            HIPCHK(h, hipMemcpyAsync(gtl + (size_t)s * R.n, gt + (size_t)s * R.n, nb, hipMemcpyDefault, h->stream));
-        } else {
-            HIPCHK(h, hipMemcpyAsync(tmp, gt + (size_t)s * R.n, nb, hipMemcpyDefault, h->stream));
-            HIPCHK(h, launch_permute_rows(gtl + (size_t)s * R.n, tmp, ngid, N, O, false, h->stream));
-        }
-    }
     float* ctl = cont_target ? (float*)(base + o_ct) : nullptr;
-    if (ctl) {
-        HIPCHK(h, hipMemcpyAsync(loc ? tmp : ctl, cont_target, nb, hipMemcpyDefault, h->stream));
-        if (loc) HIPCHK(h, launch_permute_rows(ctl, tmp, ngid, N, O, false, h->stream));
-    }
     float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
-    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)O * 4, hipMemcpyDefault, h->stream));
+    if (int rc = solver_targets(h, d, R.n, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
 
     SolverSweep S{};
     S.K = K; S.states = states; S.saves = R.saves; S.save_step = save_step.data(); S.n_saves = d->n_saves;
@@ -2278,22 +2387,218 @@ int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const f
     S.a = (float*)(base + o_a); S.gacc = (double*)(base + o_gacc); S.part = (double*)(base + o_part);
     S.grads = grads; S.loss = loss;
     if (int rc = solver_sweep(h, S)) return rc;
+    return solver_out(h, d, R);
+} MGN_CATCH(h)
 
-    // exit: the predicted saves in the caller's order
-    if (d->out) {
-        if (loc) {
-            std::vector<float> sv((size_t)d->n_saves * R.n);
-            HIPCHK(h, hipMemcpyAsync(sv.data(), R.saves, sb, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            for (int i = 0; i < d->n_saves; ++i)
-                for (int32_t j = 0; j < N; ++j)
-                    memcpy(d->out + ((size_t)i * N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * N + j) * O, (size_t)O * 4);
-        } else {
-            HIPCHK(h, hipMemcpyAsync(d->out, R.saves, sb, hipMemcpyDeviceToHost, h->stream));
-        }
+// Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_*, Tsit5Control) or fixed steps on the Euler grid, in the training form (za / zs /
+// z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
+int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
+                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
+    static const char* who = "mgn_solver_grad_tsit5";
+    if (!h) return MGN_E_ARG;
+    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
+    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
+    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
+    const mgn_config& c = h->cfg;
+    const bool adaptive = o->adaptive != 0;
+    const bool f64 = d->time_f64 != 0;
+    const double T0 = f64 ? d->t0_f64 : (double)d->t0, T1 = f64 ? d->t1_f64 : (double)d->t1, DT = f64 ? d->dt_f64 : (double)d->dt,
+                 SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
+    if (d->n_saves < 1 || !(SDT > 0.0) || !(T1 >= T0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (!adaptive && !(DT > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
+    if (adaptive && !(DT >= 0.0)) return fail(h, MGN_E_ARG, "%s: dt must be >= 0 (0: the Hairer-Wanner start)", who);
+    if (adaptive && !(d->abstol > 0.f && d->reltol > 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+    if (int rc = solver_checks2(h, d, who, cont_weight)) return rc;
+    o->n_steps = 0;
+    o->stored_bytes = 0;
+
+    Rollout R;
+    R.h = h;
+    R.d = d;
+    R.f64 = f64;
+    R.sdt = SDT;
+    R.train = true;
+    auto tt = [&](double v) { return R.tt(v); };
+    auto stop_time = [&](int i) { return tt(T0 + (double)i * SDT); };
+    int64_t K = 0;                       // fixed steps: the step count; adaptive: grows
+    std::vector<int64_t> save_step;
+    if (!adaptive) {
+        const double steps = (T1 - T0) / DT;
+        if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: %.3g steps", who, steps);
+        K = (int64_t)std::llround(steps);
+        if (int rc = fixed_grid(h, d, who, R, T0, T1, DT, SDT, K, save_step)) return rc;
+    } else if (stop_time(d->n_saves - 1) > T1 + 1e-5 * SDT) {
+        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
+                    d->n_saves - 1, stop_time(d->n_saves - 1), T1);
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MGN_OK;
+    if (int rc = solver_prepare(h, n_grads)) return rc;
+    const LocalGraph& g = h->g;
+    invalidate_static(h);
+    const int32_t N = g.N;
+    const int O = c.O;
+    R.n = (int64_t)N * O;
+    R.n_global = R.n;
+    R.nrows = N;
+    const size_t nb = (size_t)R.n * 4;
+    const size_t P = h->params.size();
+    const int ablk = solver_adjoint_blocks(N, O);
+    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
+    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
+    const size_t o_u = take(nb), o_un = take(nb), o_ut = take(nb);
+    size_t o_k[7];
+    for (auto& x : o_k) x = take(nb);
+    const bool zc = d->inflow_mask != nullptr;       // training-form copies
+    const size_t o_za = take(zc ? nb : 0), o_zs = take(zc ? nb : 0), o_z7 = take(zc ? nb : 0);
+    const size_t o_fr = take(fb), o_sv = take(sb), o_mask = take((size_t)N), o_pe = take(errnorm_partials() * sizeof(double));
+    R.elat0_off = take(eb);
+    const size_t o_gt = take(sb), o_ct = take(cont_target ? nb : 0), o_ls = take((size_t)O * 4), o_a = take(nb), o_tmp = take(nb),
+                 o_yb = take(5 * nb), o_gacc = take(P * sizeof(double)), o_part = take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
+    if (hipError_t e = h->ode.ensure(off)) {
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %.3f GB for the call's buffers: %s", who, (double)off * 1e-9,
+                    hipGetErrorString(e));
+    }
+    char* base = h->ode.as<char>();
+    R.u = (float*)(base + o_u); R.unew = (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
+    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[j]);
+    if (zc) { R.za = (float*)(base + o_za); R.zs = (float*)(base + o_zs); R.z7 = (float*)(base + o_z7); }
+    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
+    R.saves = (float*)(base + o_sv);
+    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
+    R.partial = (double*)(base + o_pe);
+    if (int rc = solver_upload(h, d, R, base, eb)) return rc;
+
+    // the stored stage inputs: step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown geometrically
+    // (never reallocated: a stored step does not move)
+    const size_t stepb = 6 * nb;
+    const int64_t max_steps = 100000;
+    std::vector<float*> steps;
+    std::vector<double> step_t, step_h;
+    size_t chunk = 0, used_in_chunk = 0;
+    auto slot = [&](int64_t n) -> int {          // steps[n] exists afterwards
+        while ((int64_t)steps.size() <= n) {
+            if ((int64_t)steps.size() >= max_steps)
+                return fail(h, MGN_E_STATE, "%s: more than %lld accepted steps (maxiters)", who, (long long)max_steps);
+            if (o->max_store_bytes && (size_t)(steps.size() + 1) * stepb > o->max_store_bytes)
+                return fail(h, MGN_E_OOM, "%s: step %lld needs %zu bytes of stored stage inputs, beyond max_store_bytes = %zu", who,
+                            (long long)steps.size(), (size_t)(steps.size() + 1) * stepb, o->max_store_bytes);
+            DevBuf* cb = chunk < h->tsit5_store.size() ? h->tsit5_store[chunk].get() : nullptr;
+            if (cb && used_in_chunk + stepb <= cb->bytes) {
+                steps.push_back(reinterpret_cast<float*>(cb->as<char>() + used_in_chunk));
+                used_in_chunk += stepb;
+                continue;
+            }
+            if (cb && used_in_chunk > 0) { ++chunk; used_in_chunk = 0; continue; }
+            // a new chunk (or an earlier call's that holds no step of this size, regrown in place): as many steps as are stored so far (at
+            // least 8; a fixed-step solve: all it has left), within max_store_bytes
+            size_t want = (size_t)std::max<int64_t>(adaptive ? std::max<int64_t>((int64_t)steps.size(), 8) : K - (int64_t)steps.size(), 1);
+            if (o->max_store_bytes) want = std::min(want, o->max_store_bytes / stepb - steps.size());
+            if (want > (SIZE_MAX / 2) / stepb) return fail(h, MGN_E_OOM, "%s: %zu stored steps overflow the address space", who, want);
+            if (!cb) {
+                h->tsit5_store.push_back(std::make_unique<DevBuf>());
+                cb = h->tsit5_store.back().get();
+            }
+            if (hipError_t e = cb->ensure(want * stepb)) {
+                (void)hipGetLastError();
+                return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: step %lld: %.3f GB more for the stored stage inputs (%.3f GB stored): %s",
+                            who, (long long)steps.size(), (double)(want * stepb) * 1e-9, (double)(steps.size() * stepb) * 1e-9, hipGetErrorString(e));
+            }
+            used_in_chunk = 0;
+        }
+        return MGN_OK;
+    };
+    int64_t nacc = 0;
+    R.keep = [&](int sidx, const float* x) -> int {
+        HIPCHK(h, hipMemcpyAsync(steps[nacc] + (size_t)sidx * R.n, x, nb, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    };
+    // before every trial: step nacc's slot, and its z_{n,1} (za, or u itself without an inflow mask) into it
+    auto begin_trial = [&]() -> int {
+        if (int rc = slot(nacc)) return rc;
+        HIPCHK(h, hipMemcpyAsync(steps[nacc], zc ? R.za : R.u, nb, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    };
+
+    d->n_accept = d->n_reject = 0;
+    int saved = 0;
+    auto save = [&]() -> hipError_t {
+        save_step.resize(std::max<size_t>(save_step.size(), (size_t)saved + 1));
+        save_step[saved] = nacc;
+        return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream);
+    };
+    double t = T0;
+    HIPCHK(h, save());
+    if (int rc = R.tsit5_first(t)) return rc;
+    if (!adaptive) {
+        for (int64_t i = 0; i < K; ++i) {
+            const double tn = (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT);
+            if (int rc = begin_trial()) return rc;
+            if (int rc = R.tsit5_trial(t, DT, tn, nullptr)) return rc;
+            R.tsit5_advance();
+            step_t.push_back(t); step_h.push_back(DT);
+            t = tn;
+            ++nacc;
+            ++d->n_accept;
+            while (saved < d->n_saves && stop_time(saved) <= t + 0.25 * DT) HIPCHK(h, save());
+        }
+    } else {
+        Tsit5Control ctl;
+        double dt = DT;
+        if (dt <= 0)
+            if (int rc = R.tsit5_h0(t, &dt)) return rc;
+        int64_t guard = 0;
+        while (t < T1 - 1e-5 * SDT) {
+            if (++guard >= 10000000) return fail(h, MGN_E_STATE, "%s: %lld trial steps without reaching t1", who, (long long)guard);
+            double tstop = saved < d->n_saves ? stop_time(saved) : T1;
+            if (tstop > T1) tstop = T1;
+            bool hit_stop = false;
+            double hstep = dt;
+            if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
+            const double tn = hit_stop ? tstop : tt(t + hstep);      // stage 7 is z_{n+1,1}: it sees t_{n+1}
+            if (int rc = begin_trial()) return rc;
+            double EEst;
+            if (int rc = R.tsit5_trial(t, hstep, tn, &EEst)) return rc;
+            if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
+            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
+                R.tsit5_advance();
+                step_t.push_back(t); step_h.push_back(hstep);
+                t = tn;
+                ++nacc;
+                ++d->n_accept;
+                if (hit_stop && saved < d->n_saves && std::fabs(stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12) HIPCHK(h, save());
+            } else {
+                ++d->n_reject;
+            }
+        }
+        while (saved < d->n_saves) HIPCHK(h, save());      // (t1 an ulp short of the last stop: the final state)
+    }
+    d->n_rhs = R.n_rhs;
+    K = nacc;
+    o->n_steps = (int32_t)K;
+    o->stored_bytes = (size_t)K * stepb;
+    for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
+        if (o->step_t) o->step_t[i] = step_t[i];
+        if (o->step_h) o->step_h[i] = step_h[i];
+    }
+
+    float* gtl = (float*)(base + o_gt);
+    float* ctl = cont_target ? (float*)(base + o_ct) : nullptr;
+    float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
+    if (int rc = solver_targets(h, d, R.n, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
+
+    SolverSweep S{};
+    S.K = K; S.states = nullptr; S.saves = R.saves; S.save_step = save_step.data(); S.n_saves = d->n_saves;
+    S.gt = gtl; S.loss_scale = lsd; S.inflow = R.mask; S.cont_target = ctl; S.cont_weight = ctl ? cont_weight : 0.f; S.dt = 0.f;
+    S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
+    S.a = (float*)(base + o_a); S.gacc = (double*)(base + o_gacc); S.part = (double*)(base + o_part);
+    S.grads = grads; S.loss = loss;
+    Tsit5Sweep T5{steps.data(), step_h.data(), R.u, (float*)(base + o_yb)};
+    if (int rc = tsit5_sweep(h, S, T5)) return rc;
+    return solver_out(h, d, R);
 } MGN_CATCH(h)
 
 // ---- latents -------------------------------------------------------------------------------------

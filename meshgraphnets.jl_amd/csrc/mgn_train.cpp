@@ -1132,47 +1132,69 @@ namespace mgn {
 
 int solver_prepare(mgn_engine* h, size_t n_grads) { return train_prepare(h, "mgn_solver_grad", n_grads); }
 
-// Reverse sweep of mgn_solver_grad: k = K-1 .. 0 through train_run's VJP path, seeded and chained by k_solver_adjoint (train.hip).
-int solver_sweep(mgn_engine* h, const SolverSweep& S) {
-    const mgn_config& c = h->cfg;
-    TrainState& T = *h->train;
-    const LocalGraph& g = h->g;
-    const int64_t N = g.n_own, n = N * c.O, E = g.set[0].e_local, P = (int64_t)h->params.size();
-    const int O = c.O, W1 = c.Fn - c.O;
-    hipStream_t st = h->stream;
-    float* A = T.arena.as<float>();
-    float* io = A + T.io;                      // xbar [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N], as train_run lays them out
-    const float* nrm = h->norms.as<float>();
-    const int32_t* ngid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
-    auto to_local = [&](float* buf, int width) -> hipError_t {
-        if (!ngid || width <= 0) return hipSuccess;
-        if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, false, st)) return e;
-        return hipMemcpyAsync(buf, A + T.ptmp, (size_t)N * width * 4, hipMemcpyDeviceToDevice, st);
-    };
-    // the statics, once per call
-    if (W1 > 0) {
-        HIPCHK(h, hipMemcpyAsync(io + 2 * n, S.onehot, (size_t)N * W1 * 4, hipMemcpyDefault, st));
-        HIPCHK(h, to_local(io + 2 * n, W1));
-    }
-    float* vm = S.val_mask ? io + (size_t)N * (O + c.Fn) : nullptr;
-    if (vm) {
-        HIPCHK(h, hipMemcpyAsync(vm, S.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
-        HIPCHK(h, to_local(vm, 1));
-    }
-    if (E > 0) {
-        HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], S.ef_raw, (size_t)E * c.Fe * 4, hipMemcpyDefault, st));
-        HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
-                                    h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, A + T.ef_pad[0], c.L, E, st));
-    }
-    HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, st));
+namespace {
 
-    const int nb = solver_adjoint_blocks(N, O);
-    const float gscale = (float)(2.0 / ((double)S.n_saves * (double)n));
-    int64_t sidx = S.n_saves - 1;              // saves are visited last to first; save_step is non-decreasing
+// What the Euler and the Tsit5 sweeps share: the statics staged once per call, the adjoint launches of a state (k_solver_adjoint: every
+// loss term of state k, xbar folded in, the seed of the step before written), one VJP of the right-hand side through train_run, and the
+// results at the end.
+struct Sweep {
+    mgn_engine* h;
+    const SolverSweep& S;
+    const float* xend;                         // x_K (continuity term)
+    int64_t N = 0, n = 0;
+    int O = 0, nb = 0;
+    float* io = nullptr;                       // xbar [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N], as train_run lays them out
+    float* vm = nullptr;
+    float gscale = 0.f;
+    int64_t sidx = 0;                          // saves are visited last to first; save_step is non-decreasing
     int slot = 0;
-    // every loss term of step k (one launch per save that ends there; the continuity seed rides on the first), xbar folded in by the first
-    // launch, the seed of step k - 1 written by the last
-    auto adjoint_step = [&](int64_t k, bool with_xbar) -> int {
+
+    Sweep(mgn_engine* h_, const SolverSweep& S_, const float* xend_) : h(h_), S(S_), xend(xend_) {}
+
+    int begin() {
+        const mgn_config& c = h->cfg;
+        TrainState& T = *h->train;
+        const LocalGraph& g = h->g;
+        N = g.n_own;
+        n = N * c.O;
+        O = c.O;
+        const int64_t E = g.set[0].e_local;
+        const int W1 = c.Fn - c.O;
+        hipStream_t st = h->stream;
+        float* A = T.arena.as<float>();
+        io = A + T.io;
+        const float* nrm = h->norms.as<float>();
+        const int32_t* ngid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+        auto to_local = [&](float* buf, int width) -> hipError_t {
+            if (!ngid || width <= 0) return hipSuccess;
+            if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, false, st)) return e;
+            return hipMemcpyAsync(buf, A + T.ptmp, (size_t)N * width * 4, hipMemcpyDeviceToDevice, st);
+        };
+        // the statics, once per call
+        if (W1 > 0) {
+            HIPCHK(h, hipMemcpyAsync(io + 2 * n, S.onehot, (size_t)N * W1 * 4, hipMemcpyDefault, st));
+            HIPCHK(h, to_local(io + 2 * n, W1));
+        }
+        vm = S.val_mask ? io + (size_t)N * (O + c.Fn) : nullptr;
+        if (vm) {
+            HIPCHK(h, hipMemcpyAsync(vm, S.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
+            HIPCHK(h, to_local(vm, 1));
+        }
+        if (E > 0) {
+            HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], S.ef_raw, (size_t)E * c.Fe * 4, hipMemcpyDefault, st));
+            HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
+                                        h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, A + T.ef_pad[0], c.L, E, st));
+        }
+        HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, st));
+        nb = solver_adjoint_blocks(N, O);
+        gscale = (float)(2.0 / ((double)S.n_saves * (double)n));
+        sidx = S.n_saves - 1;
+        return MGN_OK;
+    }
+
+    // every loss term of state k (one launch per save that ends there; the continuity seed rides on the first), xbar folded in by the
+    // first launch, the seed `seed * a` of the step before written into the VJP's lambda slot by the last
+    int adjoint(int64_t k, bool with_xbar, float seed) {
         for (bool first = true;; first = false) {
             SolverAdjArgs p{};
             p.a = S.a;
@@ -1183,41 +1205,93 @@ int solver_sweep(mgn_engine* h, const SolverSweep& S) {
                 p.xs = S.saves + (size_t)sidx * n; p.gt = S.gt + (size_t)sidx * n; p.ls = S.loss_scale; p.vm = vm; p.gscale = gscale;
                 --sidx;
             }
-            if (first && k == S.K && S.cont_target) { p.xend = S.states + (size_t)S.K * n; p.ct = S.cont_target; p.cw = S.cont_weight; }
+            if (first && k == S.K && S.cont_target) { p.xend = xend; p.ct = S.cont_target; p.cw = S.cont_weight; }
             const bool more = sidx >= 0 && S.save_step[sidx] == k;
             p.lam = (!more && k > 0) ? io + n : nullptr;
-            p.dt = S.dt; p.N = N; p.O = O;
+            p.dt = seed; p.N = N; p.O = O;
             if (p.gt || p.ct) p.part = S.part + (size_t)slot++ * 2 * nb;
-            HIPCHK(h, launch_solver_adjoint(p, st));
+            HIPCHK(h, launch_solver_adjoint(p, h->stream));
             if (!more) return MGN_OK;
         }
-    };
-    if (int rc = adjoint_step(S.K, false)) return rc;
-    for (int64_t k = S.K - 1; k >= 0; --k) {
+    }
+
+    // one VJP of the right-hand side at x (device, engine order) with the seed already in io's lambda slot: xbar into io, the parameter
+    // gradient into the double accumulator (first: assigned)
+    int vjp(const float* x, bool first) {
         TrainJob J;
         J.vjp = J.sweep = true;
-        J.first = k == S.K - 1;
-        J.x = S.states + (size_t)k * n;
+        J.first = first;
+        J.x = x;
         J.val_mask = vm;
         J.gacc = S.gacc;
-        if (int rc = train_run(h, J)) return rc;
-        if (int rc = adjoint_step(k, true)) return rc;
+        return train_run(h, J);
     }
-    float* G = T.grads.as<float>();
-    if (S.K > 0) HIPCHK(h, launch_grad_finish(S.gacc, G, P, st));
-    else HIPCHK(h, hipMemsetAsync(G, 0, (size_t)P * 4, st));
-    HIPCHK(h, hipMemcpyAsync(S.grads, G, (size_t)P * 4, hipMemcpyDefault, st));
-    std::vector<double> lp((size_t)slot * 2 * nb);
-    if (!lp.empty()) HIPCHK(h, hipMemcpyAsync(lp.data(), S.part, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    double se = 0.0, sa = 0.0;
-    for (int i = 0; i < slot; ++i)
-        for (int b = 0; b < nb; ++b) {
-            se += lp[(size_t)i * 2 * nb + b];
-            sa += lp[(size_t)i * 2 * nb + nb + b];
+
+    int finish() {
+        hipStream_t st = h->stream;
+        const int64_t P = (int64_t)h->params.size();
+        float* G = h->train->grads.as<float>();
+        if (S.K > 0) HIPCHK(h, launch_grad_finish(S.gacc, G, P, st));
+        else HIPCHK(h, hipMemsetAsync(G, 0, (size_t)P * 4, st));
+        HIPCHK(h, hipMemcpyAsync(S.grads, G, (size_t)P * 4, hipMemcpyDefault, st));
+        std::vector<double> lp((size_t)slot * 2 * nb);
+        if (!lp.empty()) HIPCHK(h, hipMemcpyAsync(lp.data(), S.part, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        double se = 0.0, sa = 0.0;
+        for (int i = 0; i < slot; ++i)
+            for (int b = 0; b < nb; ++b) {
+                se += lp[(size_t)i * 2 * nb + b];
+                sa += lp[(size_t)i * 2 * nb + nb + b];
+            }
+        *S.loss = (float)(se / ((double)S.n_saves * (double)n) + (double)S.cont_weight * sa);
+        return MGN_OK;
+    }
+};
+
+}  // namespace
+
+// Reverse sweep of mgn_solver_grad: k = K-1 .. 0 through train_run's VJP path, seeded and chained by k_solver_adjoint (train.hip).
+int solver_sweep(mgn_engine* h, const SolverSweep& S) {
+    Sweep W(h, S, S.states + (size_t)S.K * h->g.n_own * h->cfg.O);
+    if (int rc = W.begin()) return rc;
+    if (int rc = W.adjoint(S.K, false, S.dt)) return rc;
+    for (int64_t k = S.K - 1; k >= 0; --k) {
+        if (int rc = W.vjp(S.states + (size_t)k * W.n, k == S.K - 1)) return rc;
+        if (int rc = W.adjoint(k, true, S.dt)) return rc;
+    }
+    return W.finish();
+}
+
+// Reverse sweep of mgn_solver_grad_tsit5: steps n = K-1 .. 0, stages i = 6 .. 1, one VJP per stage on its stored input z_{n,i}.  The seed
+// of stage 6 is written by the adjoint launch of state n + 1 (h_n A[7][6] lam); k_tsit5_stage_seed masks zbar_{i+1} into ybar_{i+1} and
+// writes kbar_i = h_n (A[7][i] lam + sum_{j>i} A[j][i] ybar_j) for i = 5 .. 1, and before stage 1's VJP adds sum_{j>=2} ybar_j to lam;
+// the adjoint launch of state n folds in ybar_1 and the loss terms of x_n.  No host synchronisation until the end.
+int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
+    Sweep W(h, S, T5.xend);
+    if (int rc = W.begin()) return rc;
+    auto seed6 = [&](int64_t k) { return k > 0 ? (float)(T5.h[k - 1] * tsit5_a(7, 6)) : 0.f; };
+    if (int rc = W.adjoint(S.K, false, seed6(S.K))) return rc;
+    for (int64_t k = S.K - 1; k >= 0; --k) {
+        for (int i = 6; i >= 1; --i) {
+            if (i < 6) {
+                Tsit5SeedArgs p{};
+                p.xbar = W.io;
+                p.inflow = S.inflow;
+                p.ybar = T5.ybar;
+                p.a = S.a;
+                p.kbar = W.io + W.n;
+                p.cb = (float)(T5.h[k] * tsit5_a(7, i));
+                for (int j = i + 1; j <= 6; ++j) p.ca[j - 1] = (float)(T5.h[k] * tsit5_a(j, i));
+                p.i = i;
+                p.N = W.N;
+                p.O = W.O;
+                HIPCHK(h, launch_tsit5_stage_seed(p, h->stream));
+            }
+            if (int rc = W.vjp(T5.steps[k] + (size_t)(i - 1) * W.n, k == S.K - 1 && i == 6)) return rc;
         }
-    *S.loss = (float)(se / ((double)S.n_saves * (double)n) + (double)S.cont_weight * sa);
-    return MGN_OK;
+        if (int rc = W.adjoint(k, true, seed6(k))) return rc;
+    }
+    return W.finish();
 }
 
 }  // namespace mgn

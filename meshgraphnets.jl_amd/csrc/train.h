@@ -175,6 +175,16 @@ struct SolverAdjArgs {
 };
 int solver_adjoint_blocks(int64_t N, int O);
 hipError_t launch_solver_adjoint(const SolverAdjArgs& p, hipStream_t s);
+// solver-based training with Tsit5 (mgn_solver_grad_tsit5), stage i (1 .. 5) of the reverse pass of one step, per element of the [N][O]
+// state, before the VJP of stage i:
+//   ybar_{i+1} <- inflow[n] ? 0 : xbar  (the VJP of stage i + 1 just finished);   kbar <- cb lam + sum_{j>i} ca[j - 1] ybar_j
+//   (cb = h A[7][i], ca[j - 1] = h A[j][i]);   i = 1: lam <- lam + sum_{j=2..6} ybar_j as well.   ybar: [5][N][O], ybar_j at j - 2.
+struct Tsit5SeedArgs {
+    const float* xbar; const uint8_t* inflow; float* ybar; float* a; float* kbar;
+    float cb; float ca[6];
+    int32_t i; int64_t N; int32_t O;
+};
+hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s);
 // acc[i] = (first ? 0 : acc[i]) + g[i] in double; out[i] = (float)acc[i]
 hipError_t launch_grad_accum(const float* g, double* acc, int64_t n, bool first, hipStream_t s);
 hipError_t launch_grad_finish(const double* acc, float* out, int64_t n, hipStream_t s);

@@ -2039,6 +2039,81 @@ __global__ __launch_bounds__(256) void k_solver_adjoint(SolverAdjArgs p) {
     }
 }
 
+// ---- solver-based training with Tsit5 (mgn_solver_grad_tsit5): one stage of the reverse pass of a step -----------------------------
+// V consecutive elements per thread (V = 4: dwordx4 loads and stores where N * O and the pointers allow).  The stage index is a kernel
+// argument; the j loop is unrolled over 2 .. 6 with a predicate, so the coefficients stay in scalar registers (no indexed array, no scratch).
+template <int V>
+__device__ inline void ldv(float (&r)[V], const float* p) {
+    if constexpr (V == 4) {
+        const float4 v = *reinterpret_cast<const float4*>(p);
+        r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < V; ++q) r[q] = p[q];
+    }
+}
+template <int V>
+__device__ inline void stv(float* p, const float (&r)[V]) {
+    if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < V; ++q) p[q] = r[q];
+    }
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_tsit5_stage_seed(Tsit5SeedArgs p) {
+    const int64_t n = p.N * p.O;
+    const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (e >= n) return;                     // n is a multiple of V
+    float y1[V], lam[V], kb[V], ys[V];
+    if (p.xbar) {                           // ybar_{i+1}: the VJP of stage i + 1, overwritten rows zeroed
+        ldv<V>(y1, p.xbar + e);
+        if (p.inflow) {
+#pragma unroll
+            for (int q = 0; q < V; ++q)
+                if (p.inflow[(e + q) / p.O]) y1[q] = 0.f;
+        }
+        stv<V>(p.ybar + (int64_t)(p.i - 1) * n + e, y1);
+    }
+    ldv<V>(lam, p.a + e);
+#pragma unroll
+    for (int q = 0; q < V; ++q) { kb[q] = p.cb * lam[q]; ys[q] = 0.f; }
+#pragma unroll
+    for (int j = 2; j <= 6; ++j) {
+        if (j <= p.i) continue;
+        float y[V];
+        if (j == p.i + 1 && p.xbar) {
+#pragma unroll
+            for (int q = 0; q < V; ++q) y[q] = y1[q];
+        } else {
+            ldv<V>(y, p.ybar + (int64_t)(j - 2) * n + e);
+        }
+        const float cj = p.ca[j - 1];
+#pragma unroll
+        for (int q = 0; q < V; ++q) { kb[q] = fmaf(cj, y[q], kb[q]); ys[q] += y[q]; }
+    }
+    stv<V>(p.kbar + e, kb);
+    if (p.i == 1) {
+#pragma unroll
+        for (int q = 0; q < V; ++q) lam[q] += ys[q];
+        stv<V>(p.a + e, lam);
+    }
+}
+
+hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s) {
+    const int64_t n = p.N * p.O;
+    if (n <= 0) return hipSuccess;
+    auto al16 = [](const void* q) { return q == nullptr || ((uintptr_t)q & 15) == 0; };
+    if (n % 4 == 0 && al16(p.xbar) && al16(p.ybar) && al16(p.a) && al16(p.kbar)) {
+        hipLaunchKernelGGL(k_tsit5_stage_seed<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, p);
+    } else {
+        hipLaunchKernelGGL(k_tsit5_stage_seed<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+    }
+    return hipGetLastError();
+}
+
 // acc[i] = (first ? 0 : acc[i]) + g[i]  (double accumulator of the per-step parameter gradients)
 __global__ __launch_bounds__(256) void k_grad_accum(const float* __restrict__ g, double* __restrict__ acc, int64_t n, int first) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

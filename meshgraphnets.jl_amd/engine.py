@@ -346,23 +346,15 @@ class Engine:
         self._chk(self.lib.mgn_rollout(self.h, C.byref(d)))
         return out, dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)
 
-    def solver_grad(self, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask=None, inflow_mask=None,
-                    inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0, inflow_rule="reference", time_type=np.float32,
-                    want_pred=False, out=None, solver="Euler"):
-        """Loss and gradient of one fixed-step Euler solve of ode_func_train on the device (mgn_solver_grad; reference
-        src/solve.jl:101-117, strategies.jl:175-196, 257-292): the time grid, inflow frames and save rule of rollout("Euler", ...), with
-        the inflow rows written into a copy the right-hand side sees (the state is not overwritten).
-            loss = mean(((gt - x_saves) .* loss_scale) .^ 2 .* val_mask) + cont_weight * sum(abs.(x_end - cont_target))
-        gt [n_saves][N][O] and cont_target [N][O]: NumPy arrays or contiguous fp32 device tensors; `out`: NumPy array or device tensor
-        of param_count floats for the gradient.  The gradient is the discrete adjoint of the computed solution.
-        solver: "Euler" (the only one with a discrete adjoint here; "Tsit5" is answered with MGN_E_UNSUPPORTED).
-        Returns (grads, loss) or, with want_pred, (grads, loss, pred [n_saves][N][O])."""
+    def _solver_desc(self, solver, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask, inflow_mask, inflow_data,
+                     loss_scale, cont_target, inflow_rule, time_type, want_pred, out, abstol=0.0, reltol=0.0):
+        """The descriptor and arrays of a solver_grad* call; returns (d, keep, p_gt, ls, p_ct, gs, p_gs, pred)."""
         O, Fn = self.cfg.O, self.cfg.Fn
         if int(n_saves) < 1:
             raise ValueError("n_saves must be >= 1")
         d = _capi.MgnRolloutDesc()
         d.solver = {"Euler": 0, "Tsit5": 1}[solver]
-        d.t0, d.t1, d.dt, d.saves_dt, d.n_saves = t0, t1, dt, saves_dt, n_saves
+        d.t0, d.t1, d.dt, d.saves_dt, d.n_saves, d.abstol, d.reltol = t0, t1, dt, saves_dt, n_saves, abstol, reltol
         if inflow_rule not in ("reference", "tolerant"):
             raise ValueError(f"inflow_rule must be 'reference' or 'tolerant', got {inflow_rule!r}")
         d.inflow_rule = {"reference": 0, "tolerant": 1}[inflow_rule]
@@ -390,10 +382,66 @@ class Engine:
         d.inflow_data = f32(idata)
         d.n_frames = idata.shape[0] if idata is not None else 0
         d.out = f32(pred)
+        return d, (x0, oh, ef, vm, im, idata, gt, ct), p_gt, ls, p_ct, gs, p_gs, pred
+
+    def solver_grad(self, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask=None, inflow_mask=None,
+                    inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0, inflow_rule="reference", time_type=np.float32,
+                    want_pred=False, out=None, solver="Euler"):
+        """Loss and gradient of one fixed-step Euler solve of ode_func_train on the device (mgn_solver_grad; reference
+        src/solve.jl:101-117, strategies.jl:175-196, 257-292): the time grid, inflow frames and save rule of rollout("Euler", ...), with
+        the inflow rows written into a copy the right-hand side sees (the state is not overwritten).
+            loss = mean(((gt - x_saves) .* loss_scale) .^ 2 .* val_mask) + cont_weight * sum(abs.(x_end - cont_target))
+        gt [n_saves][N][O] and cont_target [N][O]: NumPy arrays or contiguous fp32 device tensors; `out`: NumPy array or device tensor
+        of param_count floats for the gradient.  The gradient is the discrete adjoint of the computed solution.
+        solver: "Euler" (the only one this entry point differentiates; "Tsit5" is answered with MGN_E_UNSUPPORTED -- see
+        solver_grad_tsit5).  Returns (grads, loss) or, with want_pred, (grads, loss, pred [n_saves][N][O])."""
+        d, keep, p_gt, ls, p_ct, gs, p_gs, pred = self._solver_desc(solver, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves,
+                                                                   val_mask, inflow_mask, inflow_data, loss_scale, cont_target, inflow_rule,
+                                                                   time_type, want_pred, out)
         loss = C.c_float()
         self._chk(self.lib.mgn_solver_grad(self.h, C.byref(d), p_gt, f32(ls), p_ct, float(cont_weight), p_gs, self.param_count,
                                            C.byref(loss)))
+        del keep
         return (gs, loss.value, pred) if want_pred else (gs, loss.value)
+
+    def solver_grad_tsit5(self, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, adaptive=True, abstol=1e-6, reltol=1e-3,
+                          val_mask=None, inflow_mask=None, inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0,
+                          inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0):
+        """Loss and gradient of one Tsit5 solve of ode_func_train on the device (mgn_solver_grad_tsit5): solver_grad's loss, arguments
+        and array rules, with
+          adaptive=True:  rollout("Tsit5", ...)'s PI-controlled steps (first step dt, 0: the Hairer-Wanner start; abstol / reltol;
+                          tstops = the saves), the error norm on the states (not overwritten);
+          adaptive=False: fixed steps of dt on solver_grad's Euler time grid and save rule.
+        The gradient is the discrete adjoint of the computed solution with the accepted step sequence held fixed (step sizes and
+        accept / reject decisions are constants); not InterpolatingAdjoint's continuous adjoint.
+        Returns (grads, loss, stats): stats has n_accept, n_reject, n_rhs, step_t, step_h (the accepted steps' start times and sizes,
+        at most step_cap of them; None: all), stored_bytes, n_steps, and pred [n_saves][N][O] with want_pred."""
+        d, keep, p_gt, ls, p_ct, gs, p_gs, pred = self._solver_desc("Tsit5", x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves,
+                                                                   val_mask, inflow_mask, inflow_data, loss_scale, cont_target, inflow_rule,
+                                                                   time_type, want_pred, out, abstol, reltol)
+        o = _capi.MgnSolverGradOpts()
+        o.adaptive = 1 if adaptive else 0
+        o.max_store_bytes = int(max_store_bytes)
+        cap = step_cap
+        if cap is None:                      # enough for every step a fixed-step solve takes, or a generous start for an adaptive one
+            cap = int(round((float(t1) - float(t0)) / float(dt))) + 2 if (not adaptive and dt > 0) else 4096
+        st, sh = np.zeros(max(int(cap), 1), np.float64), np.zeros(max(int(cap), 1), np.float64)
+        o.step_cap = int(cap)
+        o.step_t, o.step_h = st.ctypes.data_as(C.POINTER(C.c_double)), sh.ctypes.data_as(C.POINTER(C.c_double))
+        loss = C.c_float()
+        self._chk(self.lib.mgn_solver_grad_tsit5(self.h, C.byref(d), C.byref(o), p_gt, f32(ls), p_ct, float(cont_weight), p_gs,
+                                                 self.param_count, C.byref(loss)))
+        if step_cap is None and o.n_steps > cap:     # the record was cut: the call again with room for every step (bitwise repeatable)
+            return self.solver_grad_tsit5(x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, adaptive, abstol, reltol, val_mask,
+                                          inflow_mask, inflow_data, loss_scale, cont_target, cont_weight, inflow_rule, time_type, want_pred,
+                                          out, o.n_steps, max_store_bytes)
+        del keep
+        nrec = min(int(o.n_steps), int(cap))
+        stats = dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs, n_steps=int(o.n_steps), step_t=st[:nrec].copy(),
+                     step_h=sh[:nrec].copy(), stored_bytes=int(o.stored_bytes))
+        if want_pred:
+            stats["pred"] = pred
+        return gs, loss.value, stats
 
     def step(self, nf, ef, target, mask, mask_index_base=0, out=None):
         """step!(mgn, graph, target, mask, mse_reduce) (reference src/strategies.jl:418-422): returns (gs, loss) with gs

@@ -9,7 +9,8 @@ functions are written here in NumPy float32 to drive the engine exactly the way 
     ode_func_eval          reference src/solve.jl:147-158
     ode_step               reference src/solve.jl:188-219
     rollout (Euler branch) reference src/solve.jl:42-68  (`solve(prob, solver; adaptive=false, dt, saveat)`)
-    train_step (solver strategies with Euler())  reference src/strategies.jl:175-196, 238-383 (Engine.solver_grad per solved window)
+    train_step (solver strategies with Euler() / Tsit5())  reference src/strategies.jl:175-196, 238-383 (Engine.solver_grad /
+                           Engine.solver_grad_tsit5 per solved window)
     GraphNetCore surface   one_hot, triangles_to_edges, parse_edges, mse_reduce, NormaliserOfflineMinMax,
                            NormaliserOfflineMeanStd, NormaliserOnline, inverse_data (docs/src/graph_net_core.md)
 
@@ -420,6 +421,74 @@ def solver_training_euler(rhs, vjp, x0, gt, dt, val_mask, n_scale):
     return gs, loss, xs
 
 
+# Tsitouras 5(4) (the method OrdinaryDiffEq.jl calls Tsit5): TSIT5_A[i][j] is A[i + 1][j + 1] of the 1-based tableau, row 6 is b
+TSIT5_C = (0.0, 0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0)
+TSIT5_A = ((0, 0, 0, 0, 0, 0),
+           (0.161, 0, 0, 0, 0, 0),
+           (-0.008480655492356989, 0.335480655492357, 0, 0, 0, 0),
+           (2.8971530571054935, -6.359448489975075, 4.3622954328695815, 0, 0, 0),
+           (5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525, 0, 0),
+           (5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383, 0),
+           (0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774))
+
+
+def solver_training_tsit5(rhs, vjp, x0, gt, step_t, step_h, val_mask=None, n_scale=None, save_step=None, cont_target=None,
+                          cont_weight=0.0):
+    """The twin of solver_training_euler for Tsit5 over a GIVEN accepted step sequence (step_t, step_h: e.g. what
+    Engine.solver_grad_tsit5 recorded), written as the discrete adjoint with the steps held fixed, through VJPs of the right-hand side:
+        z_{n,i} = x_n + h_n sum_{j<i} A[i][j] k_{n,j},  k_{n,i} = f(z_{n,i}),  x_{n+1} = x_n + h_n sum_i b_i k_{n,i}
+        lam_K = dL/dx_K;  for i = 6 .. 1: kbar_i = h_n (b_i lam + sum_{j>i} A[j][i] zbar_j), (zbar_i, g_i) = vjp(z_{n,i}, kbar_i),
+        gs += g_i;  lam_n = lam_{n+1} + sum_i zbar_i + dL/dx_n
+    loss = sum_s ((n_scale (gt_s - x_{save_step[s]}))^2 val_mask) / (n_saves N O) + cont_weight sum |x_K - cont_target|.
+    rhs(x) -> f(x) [N][O];  vjp(x, lam) -> (lam^T df/dx, lam^T df/dps) (Engine.ode_step / Engine.ode_vjp with the statics bound, no
+    inflow);  save_step: the state each save is (default 0 .. K: a save after every step).  The right-hand side has no time here, so
+    step_t only has to match step_h in length.  Returns (gs, loss, xs)."""
+    A = np.asarray(TSIT5_A, np.float64)
+    K = len(step_h)
+    if len(step_t) != K:
+        raise ValueError("step_t and step_h differ in length")
+    gt = np.asarray(gt, np.float64)
+    N, O = gt.shape[1], gt.shape[2]
+    vm = np.ones((N, 1)) if val_mask is None else np.asarray(val_mask, np.float64).reshape(N, 1)
+    sc = np.ones((1, O)) if n_scale is None else np.asarray(n_scale, np.float64).reshape(1, O)
+    save_step = list(range(K + 1)) if save_step is None else list(save_step)
+    xs, zs = [np.asarray(x0, np.float64)], []
+    for n in range(K):
+        h, x, k, z = float(step_h[n]), xs[-1], [], []
+        for i in range(6):
+            zi = x + h * sum(A[i][j] * k[j] for j in range(i)) if i else x.copy()
+            z.append(zi)
+            k.append(np.asarray(rhs(zi.astype(F32)), np.float64))
+        zs.append(z)
+        xs.append(x + h * sum(A[6][j] * k[j] for j in range(6)))
+    count = float(len(save_step) * N * O)
+    loss = float(sum((((gt[s] - xs[k]) * sc) ** 2 * vm).sum() for s, k in enumerate(save_step)) / count)
+    ct = None if cont_target is None else np.asarray(cont_target, np.float64)
+    if ct is not None:
+        loss += float(cont_weight) * float(np.abs(xs[K] - ct).sum())
+
+    def dl_dx(k):
+        g = np.zeros((N, O))
+        for s, ks in enumerate(save_step):
+            if ks == k:
+                g += -2.0 * sc * sc * (gt[s] - xs[k]) * vm / count
+        if k == K and ct is not None:
+            g += float(cont_weight) * np.sign(xs[K] - ct)
+        return g
+
+    lam = dl_dx(K)
+    gs = None
+    for n in range(K - 1, -1, -1):
+        h, zbar = float(step_h[n]), [None] * 6
+        for i in range(5, -1, -1):
+            kbar = h * (A[6][i] * lam + sum(A[j][i] * zbar[j] for j in range(i + 1, 6)))
+            xb, g = vjp(zs[n][i].astype(F32), kbar.astype(F32))
+            zbar[i] = np.asarray(xb, np.float64)
+            gs = np.asarray(g, np.float64).copy() if gs is None else gs + g
+        lam = lam + sum(zbar) + dl_dx(n)
+    return gs, loss, xs
+
+
 def _range_length(tstart, dt, tstop):
     """length(tstart:dt:tstop)."""
     return int(np.floor((float(tstop) - float(tstart)) / float(dt) + 1e-4)) + 1
@@ -439,28 +508,45 @@ def multiple_shooting_ranges(T, interval_size):
     return [(i - 1, min(T, i + interval_size - 1) - 1) for i in range(1, T, interval_size - 1)]
 
 
+def _solver_window(eng, solver, adaptive, abstol, reltol, x0, node_type_onehot, ef_raw, gt, t0, t1, solver_dt, saves_dt, n_saves, **kw):
+    """One solved window through Engine.solver_grad (Euler) or Engine.solver_grad_tsit5 (Tsit5): (gs, loss)."""
+    if solver == "Euler":
+        return eng.solver_grad(x0, node_type_onehot, ef_raw, gt, t0, t1, solver_dt, saves_dt, n_saves, **kw)
+    if solver != "Tsit5":
+        raise ValueError(f"solver must be 'Euler' or 'Tsit5', got {solver!r}")
+    gs, loss, _ = eng.solver_grad_tsit5(x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=solver_dt or 0.0, adaptive=adaptive,
+                                        abstol=abstol, reltol=reltol, **kw)
+    return gs, loss
+
+
 def train_step_solver_training(eng, gt, node_type_onehot, ef_raw, tstart, dt, tstop, val_mask=None, inflow_mask=None, inflow_data=None,
-                               n_scale=None, solver_dt=None, time_type=F32, inflow_rule="reference", out=None):
+                               n_scale=None, solver_dt=None, time_type=F32, inflow_rule="reference", out=None, solver="Euler",
+                               adaptive=True, abstol=1e-6, reltol=1e-3):
     """train_step(::SolverTraining) with a fixed-step Euler solver (reference src/strategies.jl:175-196, 257-292) in one native call:
     u0 = gt[1], saveat = tstart:dt:tstop, loss = mean(((n_norm(gt) - n_norm(pred)) .^ 2) .* val_mask).  gt [T][N][O] (the trajectory's
     target fields, T >= the number of save points); n_scale [O]: scale of the field normaliser (its shift cancels); inflow_mask [N]:
     rows overwritten inside the right-hand side from inflow_data [frames][N][O] (default: gt itself, data[field] of ode_func_train,
-    src/solve.jl:101-117); solver_dt: the Euler step (default dt, the example's tstops = saveat).  Returns (gs, loss): the discrete
-    adjoint of the computed Euler solution."""
+    src/solve.jl:101-117); solver_dt: the Euler step (default dt, the example's tstops = saveat).  solver="Tsit5":
+    Engine.solver_grad_tsit5, adaptive (first step solver_dt, default 0: the Hairer-Wanner start; abstol / reltol) or, with
+    adaptive=False, fixed steps of solver_dt (default dt).  Returns (gs, loss): the discrete adjoint of the computed solution (Tsit5: with
+    the accepted steps held fixed)."""
     n_saves = _range_length(tstart, dt, tstop)
     if inflow_mask is not None and inflow_data is None:
         inflow_data = gt
-    return eng.solver_grad(np.asarray(gt[0]), node_type_onehot, ef_raw, gt[:n_saves], tstart, tstop, solver_dt or dt, dt, n_saves,
-                           val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=inflow_data, loss_scale=n_scale, inflow_rule=inflow_rule,
-                           time_type=time_type, out=out)
+    sdt = solver_dt if (solver == "Tsit5" and adaptive) else (solver_dt or dt)
+    return _solver_window(eng, solver, adaptive, abstol, reltol, np.asarray(gt[0]), node_type_onehot, ef_raw, gt[:n_saves], tstart, tstop,
+                          sdt, dt, n_saves, val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=inflow_data, loss_scale=n_scale,
+                          inflow_rule=inflow_rule, time_type=time_type, out=out)
 
 
 def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, tstop, interval_size, continuity_term, val_mask=None,
-                                 inflow_mask=None, inflow_data=None, solver_dt=None, time_type=F32, inflow_rule="reference"):
+                                 inflow_mask=None, inflow_data=None, solver_dt=None, time_type=F32, inflow_rule="reference", solver="Euler",
+                                 adaptive=True, abstol=1e-6, reltol=1e-3):
     """train_step(::MultipleShooting) with a fixed-step Euler solver (reference src/strategies.jl:312-383): one Engine.solver_grad per
     window rg of multiple_shooting_ranges, u0 = gt[first(rg)], saveat = tsteps[rg], loss = mean((gt[rg] - pred) .^ 2 .* val_mask) (no
-    normaliser); the continuity term continuity_term * sum(abs, pred_{i-1}[end] - gt[first(rg_i)]) goes with window i - 1.  Returns the
-    summed (gs, loss)."""
+    normaliser); the continuity term continuity_term * sum(abs, pred_{i-1}[end] - gt[first(rg_i)]) goes with window i - 1.  solver,
+    adaptive, abstol, reltol as for train_step_solver_training (every window steps onto its saves: tstops = saveat, where the reference
+    interpolates a window solved without tstops).  Returns the summed (gs, loss)."""
     T = _range_length(tstart, dt, tstop)
     ranges = multiple_shooting_ranges(T, interval_size)
     if inflow_mask is not None and inflow_data is None:
@@ -468,11 +554,12 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
     gs_sum, loss_sum = None, 0.0
     for i, (a, b) in enumerate(ranges):
         nxt = ranges[i + 1][0] if i + 1 < len(ranges) else None
-        gs, loss = eng.solver_grad(np.asarray(gt[a]), node_type_onehot, ef_raw, gt[a:b + 1], _range_at(tstart, dt, a, time_type),
-                                   _range_at(tstart, dt, b, time_type), solver_dt or dt, dt, b - a + 1, val_mask=val_mask,
-                                   inflow_mask=inflow_mask, inflow_data=inflow_data, cont_target=None if nxt is None else gt[nxt],
-                                   cont_weight=float(continuity_term) if nxt is not None else 0.0, inflow_rule=inflow_rule,
-                                   time_type=time_type)
+        sdt = solver_dt if (solver == "Tsit5" and adaptive) else (solver_dt or dt)
+        gs, loss = _solver_window(eng, solver, adaptive, abstol, reltol, np.asarray(gt[a]), node_type_onehot, ef_raw, gt[a:b + 1],
+                                  _range_at(tstart, dt, a, time_type), _range_at(tstart, dt, b, time_type), sdt, dt, b - a + 1,
+                                  val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=inflow_data,
+                                  cont_target=None if nxt is None else gt[nxt], cont_weight=float(continuity_term) if nxt is not None else 0.0,
+                                  inflow_rule=inflow_rule, time_type=time_type)
         gs_sum = np.asarray(gs, np.float64) if gs_sum is None else gs_sum + gs
         loss_sum += float(loss)
     return gs_sum, loss_sum

@@ -4,7 +4,12 @@ mgn_ode_vjp (upload of the statics, synchronise, gradient copy-out) plus a float
 cylinder mesh (L = 128, mps = 15, K Euler steps); then the native call alone on a ~125 k-node grid at a small K.  Device-synchronised
 wall times (median of the repeats after one warm-up call).
 
-    python3 tools/solver_train_timing.py [K_cyl=100] [K_125k=10] [repeats=3]"""
+With --tsit5: one SolverTraining step with Tsit5() instead -- the native mgn_solver_grad_tsit5 (adaptive, tstops = saves) against the
+host composition reference_api.solver_training_tsit5(ode_step, ode_vjp) fed the step sequence the native call recorded, on the
+cylinder mesh over K save intervals of 0.01; ms per accepted step and the bytes of the stored stage inputs.
+
+    python3 tools/solver_train_timing.py [K_cyl=100] [K_125k=10] [repeats=3]
+    python3 tools/solver_train_timing.py --tsit5 [K_cyl=20] [repeats=3]"""
 import os
 import sys
 import time
@@ -16,9 +21,11 @@ import mgn_amd
 from mgn_amd import reference_api as ra
 import bench
 
-K_CYL = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-K_BIG = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-REPS = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+TSIT5 = "--tsit5" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--tsit5"]
+K_CYL = int(ARGS[0]) if ARGS else (20 if TSIT5 else 100)
+K_BIG = 0 if TSIT5 else (int(ARGS[1]) if len(ARGS) > 1 else 10)
+REPS = int(ARGS[1 if TSIT5 else 2]) if len(ARGS) > (1 if TSIT5 else 2) else 3
 DT = 0.01
 
 
@@ -54,6 +61,33 @@ def native(eng, onehot, ef, gt, vm, K):
     ns = np.full(2, 2.5, np.float32)
     return lambda: eng.solver_grad(gt[0], onehot, ef, gt, 0.0, K * DT, DT, DT, K + 1, val_mask=vm, loss_scale=ns)
 
+
+def tsit5_mode():
+    pos, cells, ntype, vel = mgn_amd.synth.mesh_cyl(1234, 2000)
+    eng, onehot, ef, gt, vm, N, E = setup(pos, cells, ntype, vel, K_CYL)
+    ns = np.full(2, 2.5, np.float32)
+    t1 = float(np.float32(K_CYL * DT))
+    t_nat, (gs, loss, st) = timed(lambda: eng.solver_grad_tsit5(gt[0], onehot, ef, gt, 0.0, t1, DT, K_CYL + 1, val_mask=vm, loss_scale=ns))
+    K = st["n_accept"]
+    # the save each state is: the solve stops on every save point
+    times = list(st["step_t"]) + [t1]
+    save_step = [next((n for n, t in enumerate(times) if abs(float(np.float32(s * np.float32(DT))) - t) <= 1e-9 * abs(t) + 1e-12), K)
+                 for s in range(K_CYL + 1)]
+    host = lambda: ra.solver_training_tsit5(lambda x: eng.ode_step(x, onehot, ef, vm),
+                                            lambda x, lam: eng.ode_vjp(x, onehot, ef, lam, val_mask=vm)[:2], gt[0], gt, st["step_t"],
+                                            st["step_h"], val_mask=vm, n_scale=ns, save_step=save_step)
+    t_host, (gs_h, loss_h, _) = timed(host)
+    rel = float(np.linalg.norm(gs - gs_h) / np.linalg.norm(gs_h))
+    print(f"Tsit5 cylinder N={N} E={E} L=128 mps=15, {K_CYL} save intervals: {K} accepted steps, {st['n_reject']} rejected, "
+          f"{st['n_rhs']} RHS; native {t_nat * 1e3:.1f} ms ({t_nat / K * 1e3:.2f} ms/step), host composition {t_host * 1e3:.1f} ms "
+          f"({t_host / K * 1e3:.2f} ms/step), x{t_host / t_nat:.2f}; stored {st['stored_bytes']} bytes "
+          f"({st['stored_bytes'] / K / 1e3:.1f} KB/step); loss {loss:.6e} vs {loss_h:.6e}, gradient rel L2 {rel:.2e}")
+    eng.close()
+
+
+if TSIT5:
+    tsit5_mode()
+    sys.exit(0)
 
 pos, cells, ntype, vel = mgn_amd.synth.mesh_cyl(1234, 2000)
 eng, onehot, ef, gt, vm, N, E = setup(pos, cells, ntype, vel, K_CYL)
