@@ -331,6 +331,35 @@ int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_op
                           const float* loss_scale /* [O] or NULL */, const float* cont_target /* [N][O] or NULL */, float cont_weight,
                           float* grads, size_t n_grads, float* loss);
 
+/* ---- MultipleShooting as one batch: the summed loss and gradient of the W windows of train_step(::MultipleShooting) (reference
+ * src/strategies.jl:312-383).  The result is the sum of the W single-window calls train_step_multiple_shooting makes one by one: window w
+ * is mgn_solver_grad (d->solver 0) or mgn_solver_grad_tsit5 with adaptive = 0 (d->solver 1) with x0 = gt[first[w]], t0 = t0[w], t1 = t1[w],
+ * n_saves = last[w] - first[w] + 1, gt = gt[first[w] .. last[w]], cont_target = gt[first[w + 1]] and cont_weight for w < W - 1 (no
+ * continuity term for the last window), everything else (dt, saves_dt, time_f64, inflow_rule, node_type_onehot, ef_raw, val_mask,
+ * inflow_mask, inflow_data / n_frames) from d and loss_scale as given.  Inflow frames are chosen by absolute time, so each window reads its
+ * own.  d->x0, d->t0, d->t1 and d->n_saves are ignored.  *loss: the summed loss; grads: the summed discrete-adjoint gradient; d->out, if not
+ * NULL, the predicted saves [sum_w n_saves_w][N][O] in window order; d->n_accept / d->n_rhs: the totals.
+ * Windows are independent (each starts from ground truth; the continuity term couples window w only to gt), so windows whose step plans
+ * are identical (same step count, save steps and step size) are solved together as one block-diagonal graph of B copies of the mesh, on a
+ * companion engine the handle keeps (released by mgn_set_graph / mgn_set_graph_local / mgn_destroy).  A pass of one window runs on the
+ * handle itself.  With ln_dims = MGN_LN_ALL the statistics of a LayerNorm would couple the copies: every pass holds one window there.
+ * Restrictions, pointer kinds (gt and grads: host or device) and refusals as mgn_solver_grad; Tsit5 with adaptive != 0 is MGN_E_UNSUPPORTED,
+ * W < 1 or a window outside gt MGN_E_ARG.  Bitwise repeatable; one synchronisation at the end.                                         */
+typedef struct mgn_shooting_desc {
+    int32_t n_windows;            /* W >= 1                                                                                          */
+    const int32_t* first;         /* [W] 0-based index into gt of window w's first save: u0 = gt[first[w]]                           */
+    const int32_t* last;          /* [W] inclusive; last[w] > first[w]; n_saves_w = last[w] - first[w] + 1                           */
+    const double* t0;             /* [W] the window's tspan in the solver's time type (Julia: tsteps[first(rg)])                     */
+    const double* t1;             /* [W]                                                                                             */
+    int32_t n_gt;                 /* frames in gt                                                                                    */
+    int32_t adaptive;             /* solver 1 (Tsit5): must be 0 (fixed steps of d->dt); adaptive is refused                         */
+    int32_t max_windows_per_pass; /* 0: no cap other than max_batch_nodes                                                            */
+    int64_t max_batch_nodes;      /* 0: 1 << 20; a pass holds at most max(1, floor(this / N)) windows                                */
+    int32_t n_groups, n_passes;   /* out                                                                                             */
+} mgn_shooting_desc;
+int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, const float* gt /* [n_gt][N][O] */,
+                      const float* loss_scale /* [O] or NULL */, float cont_weight, float* grads, size_t n_grads, float* loss);
+
 /* ---- training step -------------------------------------------------------
  * GraphNetCore.step!(mgn, graph, target, mask, mse_reduce) as called at reference src/strategies.jl:418-422 and
  * consumed at src/MeshGraphNets.jl:370-378:  out = model(graph);  loss = mean(mse_reduce(target, out)[mask]) with

@@ -26,7 +26,7 @@ import ChainRulesCore: NoTangent, ZeroTangent, Tangent
 export one_hot, triangles_to_edges, parse_edges, mse_reduce, inverse_data
 export NormaliserOffline, NormaliserOfflineMinMax, NormaliserOfflineMeanStd, NormaliserOnline
 # the replaced surface
-export FeatureGraph, GraphNetwork, step!, load, save!
+export FeatureGraph, GraphNetwork, step!, load, save!, shooting_grad
 # engine extras (optional fast paths; none is needed for the drop-in)
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
        native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
@@ -88,6 +88,20 @@ mutable struct MgnSolverGradOpts   # mirrors `mgn_solver_grad_opts` (include/mgn
     max_store_bytes::Csize_t
     n_steps::Int32
     stored_bytes::Csize_t
+end
+
+mutable struct MgnShootingDesc   # mirrors `mgn_shooting_desc` (include/mgn_hip.h), field for field
+    n_windows::Int32
+    first::Ptr{Int32}
+    last::Ptr{Int32}
+    t0::Ptr{Float64}
+    t1::Ptr{Float64}
+    n_gt::Int32
+    adaptive::Int32
+    max_windows_per_pass::Int32
+    max_batch_nodes::Int64
+    n_groups::Int32
+    n_passes::Int32
 end
 
 function check(h::Ptr{Cvoid}, rc::Cint)
@@ -687,6 +701,43 @@ function solver_grad_tsit5(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_one
 end
 
 """
+    shooting_grad(mgn, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, ranges, tsteps, dt;
+                  solver = :Euler, cont_weight = 0f0, max_windows_per_pass = 0) -> (gs, loss, pred::Array{Float32, 3})
+
+The summed loss and gradient of the MultipleShooting windows `ranges` (1-based ranges into `gt` and `tsteps`) in one call
+(mgn_shooting_grad): window i is `solver_grad` (`solver = :Euler`) or `solver_grad_tsit5(...; adaptive = false)` (`:Tsit5`) from
+`gt[:, :, first(rg)]` over `tsteps[rg]`, with the continuity term against `gt[:, :, first(ranges[i + 1])]` for every window but the
+last.  Windows with the same step plan run as one batch of graph copies.  `pred` holds every window's saves, in window order.
+"""
+function shooting_grad(mgn::GraphNetwork, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
+        val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
+        inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, ranges, tsteps, dt;
+        solver = :Euler, cont_weight = 0.0f0, max_windows_per_pass = 0, tolerant_inflow = false)
+    ps = mgn.ps::Vector{Float32}
+    sync_params!(mgn, ps)
+    O, N, n_gt = size(gt)
+    first_ = Int32[first(rg) - 1 for rg in ranges]; last_ = Int32[last(rg) - 1 for rg in ranges]
+    t0 = Float64[tsteps[first(rg)] for rg in ranges]; t1 = Float64[tsteps[last(rg)] for rg in ranges]
+    out = Array{Float32, 3}(undef, O, N, sum(length, ranges))
+    gs = Vector{Float32}(undef, length(ps))
+    loss = Ref{Float32}(0)
+    sdt = tsteps[2] - tsteps[1]
+    f64 = eltype(tsteps) == Float64
+    d = MgnRolloutDesc(solver == :Euler ? 0 : 1, 0, 0, dt, sdt, 0, 0, 0,
+        Ptr{Float32}(C_NULL), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
+        inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
+        inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
+        0, 0, dt, sdt)
+    s = MgnShootingDesc(length(ranges), pointer(first_), pointer(last_), pointer(t0), pointer(t1), n_gt, 0, max_windows_per_pass, 0, 0, 0)
+    # (@ccall: tests/test_shooting_batched_host.py checks this call against the header)
+    rc = GC.@preserve node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out gt gs first_ last_ t0 t1 @ccall LIB.mgn_shooting_grad(
+        mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, s::Ref{MgnShootingDesc}, gt::Ptr{Float32}, C_NULL::Ptr{Float32},
+        Float32(cont_weight)::Float32, gs::Ptr{Float32}, length(gs)::Csize_t, loss::Ref{Float32})::Cint
+    check(mgn.handle, rc)
+    return gs, loss[], out
+end
+
+"""
     native_solver_train_step(strategy, mgn, gt, node_type_onehot, edge_features, val_mask_row, inflow_mask_row;
                              n_scale = nothing, inflow_data = gt) -> (gs, loss)
 
@@ -698,12 +749,14 @@ normaliser's scale `n_scale` in the loss; MultipleShooting one solve per window 
 term of window i attached to window i - 1.  The Euler step is `solargs.dt` when given, else `strategy.dt` (the example's
 `tstops = tstart:dt:tstop`).  It returns the DISCRETE adjoint (exact gradient of the computed Euler solution), not
 InterpolatingAdjoint's continuous approximation the reference defaults to.  Opt-in for `train_network`:
-`gs, loss = native_solver_train_step(strategy, mgn, gt, ...)` in place of `train_step(strategy, t)`.
+`gs, loss = native_solver_train_step(strategy, mgn, gt, ...)` in place of `train_step(strategy, t)`.  `batched = true` routes a
+MultipleShooting strategy with Euler or fixed-step Tsit5 through `shooting_grad` (all windows in one call; the same sum); adaptive
+Tsit5 keeps the per-window loop.
 (Julia is not available where this shim is tested: its ccalls are checked against the header by tests/test_julia_shim.py.)
 """
 function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
         edge_features::Matrix{Float32}, val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}};
-        n_scale::Union{Nothing, Vector{Float32}} = nothing, inflow_data::Union{Nothing, Array{Float32, 3}} = gt)
+        n_scale::Union{Nothing, Vector{Float32}} = nothing, inflow_data::Union{Nothing, Array{Float32, 3}} = gt, batched = false)
     sname = nameof(typeof(strategy.solver))
     sname in (:Euler, :Tsit5) || throw(ArgumentError("native_solver_train_step drives Euler() and Tsit5(); got $(strategy.solver)"))
     tsteps = (strategy.tstart):(strategy.dt):(strategy.tstop)
@@ -724,6 +777,11 @@ function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32
     end
     T = length(tsteps)
     ranges = [i:min(T, i + strategy.interval_size - 1) for i in 1:(strategy.interval_size - 1):(T - 1)]
+    if batched && !adaptive
+        gs, loss, _ = shooting_grad(mgn, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, gt, ranges, tsteps,
+            sname == :Euler ? dt : (dt == 0 ? strategy.dt : dt); solver = sname, cont_weight = Float32(strategy.continuity_term))
+        return (gs,), loss
+    end
     gs_sum = zeros(Float64, length(mgn.ps)); loss_sum = 0.0
     for (i, rg) in enumerate(ranges)
         last_window = i == length(ranges)

@@ -41,6 +41,12 @@ class MgnSolverGradOpts(C.Structure):
                 ("max_store_bytes", C.c_size_t), ("n_steps", C.c_int32), ("stored_bytes", C.c_size_t)]
 
 
+class MgnShootingDesc(C.Structure):
+    _fields_ = [("n_windows", C.c_int32), ("first", C.POINTER(C.c_int32)), ("last", C.POINTER(C.c_int32)), ("t0", C.POINTER(C.c_double)),
+                ("t1", C.POINTER(C.c_double)), ("n_gt", C.c_int32), ("adaptive", C.c_int32), ("max_windows_per_pass", C.c_int32),
+                ("max_batch_nodes", C.c_int64), ("n_groups", C.c_int32), ("n_passes", C.c_int32)]
+
+
 ABI_VERSION = 4      # MGN_ABI_VERSION of include/mgn_hip.h these mirrors were written against (tests/test_julia_shim.py compares)
 
 _f32p = C.POINTER(C.c_float)
@@ -92,6 +98,8 @@ PROTOTYPES = {
     "mgn_solver_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f32p, _f32p, _f32p, C.c_float, _f32p, C.c_size_t, _f32p]),
     "mgn_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float, _f32p,
                                         C.c_size_t, _f32p]),
+    "mgn_shooting_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnShootingDesc), _f32p, _f32p, C.c_float, _f32p, C.c_size_t,
+                                    _f32p]),
     "mgn_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
     "mgn_ode_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
     "mgn_forward_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),

@@ -184,6 +184,14 @@ struct mgn_engine {
     // training step (mgn_step): weights in training order, kept activations, scratch -- created on first use
     mgn::TrainState* train = nullptr;
 
+    // mgn_shooting_grad: the companion engine solving B windows at once on B copies of this handle's graph (engine order, node offset
+    // w N), one per pass size B, kept until the graph changes, with the generation of the parameters it holds; the call's staging
+    uint64_t params_gen = 0;               // bumped by every mgn_set_params that changes the parameters
+    struct ShootKid { int32_t b = 0; mgn_engine* e = nullptr; uint64_t params_gen = 0; bool params_set = false; };
+    std::vector<ShootKid> shoot_kids;      // at most two pass sizes (a group's full passes and its remainder)
+    DevBuf shoot;
+    bool companion = false;                // this is a companion: its training arena never sizes itself from the device's free memory
+
     // profiling
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -227,6 +235,11 @@ struct SolverSweep {
     const float* onehot; const float* ef_raw; const float* val_mask;   // the caller's, in the caller's order
     float* a; double* gacc; double* part;   // scratch: [N][O], [n_params], [n_saves + 1][2][solver_adjoint_blocks]
     float* grads; float* loss;              // results (grads: host or device)
+    // mgn_shooting_grad (unset otherwise): the state holds windows of win_rows rows; the continuity weight per window (cw_win, device) replaces
+    // cont_weight, the loss terms are added into lacc ([2][lacc_ld] doubles, launch_shoot_adjoint), every VJP adds to gacc (the caller zeroed
+    // it), and nothing is finalised: the caller does that once for all passes
+    const float* cw_win = nullptr; int64_t win_rows = 0;
+    double* lacc = nullptr; int32_t lacc_ld = 0; double lscale = 0.0;
 };
 int solver_prepare(mgn_engine* h, size_t n_grads);
 int solver_sweep(mgn_engine* h, const SolverSweep& S);

@@ -626,6 +626,8 @@ inline bool is_bf16(const mgn_engine* h) { return h->cfg.dtype == MGN_BF16; }
 // =================================================================================================
 extern "C" {
 
+static void shoot_release(mgn_handle* h);   // mgn_shooting_grad's companions (below)
+
 int mgn_abi_version(void) { return MGN_ABI_VERSION; }
 
 int mgn_create(const mgn_config* cfg, mgn_handle** out) try {
@@ -675,6 +677,7 @@ void mgn_destroy(mgn_handle* h) {
     if (!h) return;
     if (h->host_only) { delete h->comm; delete h; return; }
     (void)hipStreamSynchronize(h->stream);
+    shoot_release(h);
     drop_graph(h);
     for (auto& r : h->recs) {
         (void)hipEventDestroy(r.a);
@@ -721,6 +724,7 @@ int mgn_set_params(mgn_handle* h, const float* packed, size_t n) try {
     // comparison of 9 MB): nothing is invalidated, captured graphs and packed layouts stay
     if (h->have_params && h->params.size() == n && memcmp(h->params.data(), packed, n * sizeof(float)) == 0) return MGN_OK;
     h->params.assign(packed, packed + n);
+    ++h->params_gen;
     train_invalidate(h, 1);
     // The kernels' own weight layouts (three fp32 fragment orders, the bf16 pieces of the split path in two, the bf16 copies) take
     // ~30 ms of host time for the 15-step model; a training loop sets new parameters before EVERY step! and its kernels pack their own
@@ -1085,7 +1089,8 @@ static int g_renumber = [] { const char* e = getenv("MGN_RENUMBER"); return e ? 
 
 // (re)build the local graph from the kept global edge lists and upload it.  keep_owner: node partition unchanged
 static int rebuild_graph(mgn_handle* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner,
-                         const char* who, const int32_t* owner_in = nullptr) {
+                         const char* who, const int32_t* owner_in = nullptr, int renumber = -1) {
+    shoot_release(h);                     // the companion of mgn_shooting_grad replicates the old graph
     h->have_graph = false;
     h->hx_ready = false;
     h->all_gid.clear();
@@ -1094,7 +1099,7 @@ static int rebuild_graph(mgn_handle* h, int32_t N, const EdgeList* sets, const f
     if (!h->host_only) { (void)hipStreamSynchronize(h->stream); drop_graph(h); }
     const std::string why = build_local_graph(N, h->nsets, sets, mesh_pos, pos_dim, owner_in ? owner_in : (keep_owner ? h->g.owner.data() : nullptr),
                                               h->cfg.rank, h->cfg.nranks, h->g,
-                                              g_renumber);   // (the numbering follows set 0 alone: a later mgn_set_edge_set / mgn_world_edges_dev keeps it)
+                                              renumber >= 0 ? renumber : g_renumber);   // (the numbering follows set 0 alone: a later mgn_set_edge_set / mgn_world_edges_dev keeps it)
     if (!why.empty()) return fail(h, MGN_E_ARG, "%s: %s", who, why.c_str());
     const LocalGraph& g = h->g;
     for (int q = 0; q < h->nsets; ++q) h->es[q].ntiles_e = (int32_t)((g.set[q].e_local + TILE - 1) / TILE);
@@ -1842,24 +1847,38 @@ struct Rollout {
         return rc;
     }
 
+    // data[field][:, :, floor(Int, t / saves_dt) + 1] (reference src/solve.jl:151): the quotient in the solver's own time type,
+    // no tolerance -- a t that sits an ulp below a frame boundary re-uses the previous frame there too -- and an index outside
+    // the data is the reference's BoundsError.  MGN_INFLOW_TOLERANT: nearest-below with a guard of 1e-3 frames (a Float32 time drifts by ~1e-4 frames), clamped.
+    int frame_index(double t, int64_t* out) const {
+        int64_t fr;
+        if (d->inflow_rule == MGN_INFLOW_TOLERANT) {
+            fr = (int64_t)std::floor(t / sdt + 1e-3);
+            if (fr < 0) fr = 0;
+            if (fr >= d->n_frames) fr = d->n_frames - 1;
+        } else {
+            fr = (int64_t)std::floor(tt(t / sdt));
+            if (fr < 0 || fr >= d->n_frames)
+                return fail(h, MGN_E_ARG, "mgn_rollout: inflow frame %lld at t = %.9g is outside the %d frames given (reference: BoundsError)",
+                            (long long)fr, t, d->n_frames);
+        }
+        *out = fr;
+        return MGN_OK;
+    }
+
+    // mgn_shooting_grad: the state holds windows of win_rows rows whose frames were chosen on the host, RHS evaluation e of the solve
+    // reading ftab[e * ftab_ld + window] (frames [n_frames][win_rows][O], mask [win_rows])
+    const int32_t* ftab = nullptr;
+    int64_t ftab_ld = 0, win_rows = 0;
+
     // f(x, t): in-place inflow overwrite of x, then dx/dt -> kout    (ode_func_eval, reference src/solve.jl:147-158)
     int rhs(float* x, double t, float* kout) {
         const mgn_config& c = h->cfg;
-        if (mask && frames) {
-            // data[field][:, :, floor(Int, t / saves_dt) + 1] (reference src/solve.jl:151): the quotient in the solver's own time type,
-            // no tolerance -- a t that sits an ulp below a frame boundary re-uses the previous frame there too -- and an index outside
-            // the data is the reference's BoundsError.  MGN_INFLOW_TOLERANT: nearest-below with a guard of 1e-3 frames (a Float32 time drifts by ~1e-4 frames), clamped.
+        if (mask && frames && ftab) {
+            HIPCHK(h, launch_shoot_overwrite(x, frames, mask, ftab + (size_t)n_rhs * ftab_ld, win_rows, c.O, nrows, h->stream));
+        } else if (mask && frames) {
             int64_t fr;
-            if (d->inflow_rule == MGN_INFLOW_TOLERANT) {
-                fr = (int64_t)std::floor(t / sdt + 1e-3);
-                if (fr < 0) fr = 0;
-                if (fr >= d->n_frames) fr = d->n_frames - 1;
-            } else {
-                fr = (int64_t)std::floor(tt(t / sdt));
-                if (fr < 0 || fr >= d->n_frames)
-                    return fail(h, MGN_E_ARG, "mgn_rollout: inflow frame %lld at t = %.9g is outside the %d frames given (reference: BoundsError)",
-                                (long long)fr, t, d->n_frames);
-            }
+            if (int rc = frame_index(t, &fr)) return rc;
             HIPCHK(h, launch_overwrite(x, frames + (size_t)fr * n, mask, nrows, c.O, h->stream));
         }
         ++n_rhs;
@@ -2202,6 +2221,24 @@ int fixed_grid(mgn_handle* h, mgn_rollout_desc* d, const char* who, const Rollou
     return MGN_OK;
 }
 
+// the static inputs (x0 only fills the encoder's unused state slot: every right-hand side reads its state through srcA_override) and the
+// edges encoded once into elat0
+int solver_statics(mgn_handle* h, mgn_rollout_desc* d, const float* x0, char* elat0, size_t eb) {
+    const mgn_config& c = h->cfg;
+    const int32_t N = h->g.N;
+    const int O = c.O;
+    if (int rc = upload_inputs(h, x0, O, d->node_type_onehot, c.Fn - O, d->ef_raw, true)) return rc;
+    h->have_mask = d->val_mask != nullptr;
+    if (d->val_mask) {
+        HIPCHK(h, h->d_mask.ensure((size_t)N * 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
+    if (int rc = encode_impl(h, true, false, true)) return rc;
+    HIPCHK(h, hipMemcpyAsync(elat0, h->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, h->stream));
+    return MGN_OK;
+}
+
 // entry: x0, frames and the inflow mask into the engine's order (as mgn_rollout), then the static inputs and the encoded edges
 int solver_upload(mgn_handle* h, mgn_rollout_desc* d, Rollout& R, char* base, size_t eb) {
     const mgn_config& c = h->cfg;
@@ -2228,16 +2265,7 @@ int solver_upload(mgn_handle* h, mgn_rollout_desc* d, Rollout& R, char* base, si
         if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, lm.data(), (size_t)N, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (int rc = upload_inputs(h, d->x0, O, d->node_type_onehot, c.Fn - O, d->ef_raw, true)) return rc;
-    h->have_mask = d->val_mask != nullptr;
-    if (d->val_mask) {
-        HIPCHK(h, h->d_mask.ensure((size_t)N * 4));
-        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
-    if (int rc = encode_impl(h, true, false, true)) return rc;
-    HIPCHK(h, hipMemcpyAsync(base + R.elat0_off, h->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, h->stream));
-    return MGN_OK;
+    return solver_statics(h, d, d->x0, base + R.elat0_off, eb);
 }
 
 // gt and cont_target (host or device, the caller's order) into the engine's order (gtl, ctl); loss_scale as given (lsd); tmp: [N][O] scratch
@@ -2599,6 +2627,502 @@ int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_op
     Tsit5Sweep T5{steps.data(), step_h.data(), R.u, (float*)(base + o_yb)};
     if (int rc = tsit5_sweep(h, S, T5)) return rc;
     return solver_out(h, d, R);
+} MGN_CATCH(h)
+
+// ---- MultipleShooting as one batch (mgn_shooting_grad) ----------------------------------------------------------------------------------
+// The windows of one MultipleShooting loss are independent (each starts from gt; the continuity term couples a window to gt only), so
+// windows with the same step plan are solved together on a companion engine holding B copies of the graph: one solve of a block-diagonal
+// graph per pass instead of B launch-bound solves.  Per window the arithmetic is that of mgn_solver_grad / mgn_solver_grad_tsit5 (fixed
+// steps); the loss partials and the gradient accumulate over all passes and are finalised once.
+static void shoot_release(mgn_handle* h) {
+    if (!h) return;
+    for (auto& k : h->shoot_kids) mgn_destroy(k.e);
+    h->shoot_kids.clear();
+    h->shoot.release();
+}
+
+namespace {
+
+struct ShootGroup {
+    int64_t K = 0;
+    std::vector<int64_t> save_step;          // n_saves entries, the same for every window of the group
+    std::vector<int32_t> win;                // its windows, ascending
+    std::vector<std::vector<int32_t>> fr;    // per window: the inflow frame of every right-hand side evaluation (no inflow mask: empty)
+    size_t ftab_off = 0;                     // [n_evals][win.size()] in the int table
+};
+
+// the companion for passes of B windows: B copies of h's graph in h's engine order (row w N + i = window w's engine row i), not renumbered;
+// parameters and normalisers brought up to date
+int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
+    static const char* who = "mgn_shooting_grad";
+    mgn_engine::ShootKid* kid = nullptr;
+    for (auto& k : h->shoot_kids)
+        if (k.b == B) kid = &k;
+    if (!kid) {
+        if (h->shoot_kids.size() >= 2) {     // the oldest size goes
+            mgn_destroy(h->shoot_kids.front().e);
+            h->shoot_kids.erase(h->shoot_kids.begin());
+        }
+        const LocalGraph& g = h->g;
+        const int32_t N = g.N;
+        const EdgeTopo& t = g.set[0];
+        const int64_t E = t.e_local;
+        if ((int64_t)B * N > INT32_MAX || (int64_t)B * E > INT32_MAX) return fail(h, MGN_E_ARG, "%s: %d windows of %d nodes overflow int32 node ids", who, B, N);
+        mgn_engine* c = nullptr;
+        mgn_config cfg = h->cfg;
+        if (mgn_create(&cfg, &c) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion engine: %s", who, mgn_last_error(nullptr));
+        c->companion = true;
+        std::vector<int32_t> snd((size_t)B * E), rcv((size_t)B * E);
+        for (int32_t w = 0; w < B; ++w)
+            for (int64_t j = 0; j < E; ++j) {
+                snd[(size_t)w * E + j] = w * N + t.snd[j];
+                rcv[(size_t)w * E + j] = w * N + t.rcv[j];
+            }
+        EdgeList sets[MAX_EDGE_SETS];
+        sets[0] = {(int64_t)B * E, snd.data(), rcv.data(), 0};
+        int rc = rebuild_graph(c, B * N, sets, nullptr, 0, false, who, nullptr, 0);
+        if (!rc) rc = alloc_latents(c);
+        if (rc) {
+            rc = fail(h, rc, "%s: companion graph: %s", who, c->err.c_str());
+            mgn_destroy(c);
+            return rc;
+        }
+        c->have_graph = true;
+        h->shoot_kids.push_back({B, c, 0, false});
+        kid = &h->shoot_kids.back();
+        // the copies keep h's engine order: no renumbering, edges in the replicated (receiver-sorted, stable) order
+        const LocalGraph& cg = c->g;
+        bool same = !cg.renumbered && cg.n_own == B * N && cg.set[0].e_local == (int64_t)B * E;
+        for (int32_t i = 0; same && i < cg.n_own; ++i) same = cg.own_gid[i] == i;
+        for (int64_t j = 0; same && j < cg.set[0].e_local; ++j) same = cg.set[0].edge_gid[j] == j;
+        if (!same) return fail(h, MGN_E_STATE, "%s: the companion graph does not keep the replicated order", who);
+    }
+    mgn_engine* c = kid->e;
+    if (c->stream != h->stream)
+        if (mgn_set_stream(c, (void*)h->stream) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion stream: %s", who, c->err.c_str());
+    if (!kid->params_set || kid->params_gen != h->params_gen) {      // parameters only when they changed
+        if (mgn_set_params(c, h->params.data(), h->params.size()) != MGN_OK) return fail(h, MGN_E_STATE, "%s: companion parameters: %s", who, c->err.c_str());
+        kid->params_set = true;
+        kid->params_gen = h->params_gen;
+    }
+    if (c->norms_host != h->norms_host || c->have_nnorm != h->have_nnorm || c->have_enorm != h->have_enorm || c->have_onorm != h->have_onorm) {
+        const mgn_config& k = h->cfg;
+        const float* v = h->norms_host.data();
+        const float* ne = v + 2 * k.Fn;
+        const float* no = ne + 2 * k.Fe;
+        if (mgn_set_norms(c, h->have_nnorm ? v : nullptr, h->have_nnorm ? v + k.Fn : nullptr, h->have_enorm ? ne : nullptr,
+                          h->have_enorm ? ne + k.Fe : nullptr, h->have_onorm ? no : nullptr, h->have_onorm ? no + k.O : nullptr) != MGN_OK)
+            return fail(h, MGN_E_STATE, "%s: companion normalisers: %s", who, c->err.c_str());
+        c->norms_host = h->norms_host;
+    }
+    if (int rc = need(c, true, true, true, true)) return fail(h, rc, "%s: companion: %s", who, c->err.c_str());
+    *out = c;
+    return MGN_OK;
+}
+
+// the static inputs of a companion pass: h's engine-order arrays replicated B times on the device, the edges encoded once into elat0
+int shoot_statics(mgn_engine* c, int32_t B, int32_t N, const float* oh, const float* vm, const float* ef, char* elat0, size_t eb) {
+    const mgn_config& k = c->cfg;
+    const int W1 = k.Fn - k.O, Fe = k.Fe;
+    const int64_t E = c->g.set[0].e_local / B, rows = (int64_t)B * N;
+    c->in_wa = k.O;
+    c->in_wb = W1;
+    c->in_local = true;                      // (the state slot d_nfA is never read: every right-hand side reads srcA_override)
+    HIPCHK(c, c->d_nfA.ensure(16));
+    HIPCHK(c, c->d_nfB.ensure((size_t)rows * (W1 > 0 ? W1 : 1) * 4));
+    if (W1 > 0) HIPCHK(c, launch_shoot_gather(c->d_nfB.as<float>(), oh, rows * W1, (int64_t)N * W1, 1, nullptr, nullptr, 0, c->stream));
+    c->have_mask = vm != nullptr;
+    if (vm) {
+        HIPCHK(c, c->d_mask.ensure((size_t)rows * 4));
+        HIPCHK(c, launch_shoot_gather(c->d_mask.as<float>(), vm, rows, N, 1, nullptr, nullptr, 0, c->stream));
+    }
+    HIPCHK(c, c->es[0].d_ef.ensure((size_t)B * E * Fe * 4 + 16));
+    if (E > 0) HIPCHK(c, launch_shoot_gather(c->es[0].d_ef.as<float>(), ef, (int64_t)B * E * Fe, E * Fe, 1, nullptr, nullptr, 0, c->stream));
+    if (int rc = encode_impl(c, true, false, true)) return rc;
+    HIPCHK(c, hipMemcpyAsync(elat0, c->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, c->stream));
+    return MGN_OK;
+}
+
+}  // namespace
+
+int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, const float* gt, const float* loss_scale, float cont_weight,
+                      float* grads, size_t n_grads, float* loss) try {
+    static const char* who = "mgn_shooting_grad";
+    if (!h) return MGN_E_ARG;
+    // the arguments first (a host-only handle answers them too)
+    if (!d || !s || !gt || !grads || !loss) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
+    if (d->solver == 1 && s->adaptive != 0)
+        return fail(h, MGN_E_UNSUPPORTED, "%s: adaptive Tsit5 windows need a step controller each: call mgn_solver_grad_tsit5 per window", who);
+    const int32_t W = s->n_windows;
+    if (W < 1 || !s->first || !s->last || !s->t0 || !s->t1) return fail(h, MGN_E_ARG, "%s: needs n_windows >= 1 and first / last / t0 / t1", who);
+    if (s->max_windows_per_pass < 0 || s->max_batch_nodes < 0) return fail(h, MGN_E_ARG, "%s: max_windows_per_pass and max_batch_nodes must be >= 0", who);
+    for (int32_t w = 0; w < W; ++w)
+        if (s->first[w] < 0 || s->last[w] <= s->first[w] || s->last[w] >= s->n_gt)
+            return fail(h, MGN_E_ARG, "%s: window %d = (%d, %d) must satisfy 0 <= first < last < n_gt = %d", who, w, s->first[w], s->last[w], s->n_gt);
+    s->n_groups = s->n_passes = 0;
+    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
+    const mgn_config& c = h->cfg;
+    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
+    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
+    if (int rc = need(h, true, true, c.ln_dims != MGN_LN_ALL, true)) return rc;
+    if (!d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
+    const bool f64 = d->time_f64 != 0;
+    const double DT = f64 ? d->dt_f64 : (double)d->dt, SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
+    if (!(SDT > 0.0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (!(DT > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
+    if (int rc = solver_checks2(h, d, who, cont_weight)) return rc;
+    const bool euler = d->solver == 0, inflow = d->inflow_mask != nullptr;
+
+    // ---- plans on the host: every window walks the single-window grid; identical plans form a group
+    Rollout P;                               // (its time type and frame rule only)
+    P.h = h;
+    P.d = d;
+    P.f64 = f64;
+    P.sdt = SDT;
+    auto tt = [&](double v) { return P.tt(v); };
+    std::vector<ShootGroup> groups;
+    std::vector<int32_t> grp_of(W);
+    mgn_rollout_desc dw = *d;
+    for (int32_t w = 0; w < W; ++w) {
+        const double T0 = tt(s->t0[w]), T1 = tt(s->t1[w]);
+        if (!(T1 >= T0)) return fail(h, MGN_E_ARG, "%s: window %d: t1 < t0", who, w);
+        dw.n_saves = s->last[w] - s->first[w] + 1;
+        const double steps = (T1 - T0) / DT;
+        if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: window %d: %.3g steps", who, w, steps);
+        const int64_t K = (int64_t)std::llround(steps);
+        std::vector<int64_t> ss;
+        if (int rc = fixed_grid(h, &dw, who, P, T0, T1, DT, SDT, K, ss)) return rc;
+        std::vector<int32_t> fr;
+        if (inflow) {      // the frame of every right-hand side evaluation, in the order the solve makes them
+            auto next_t = [&](int64_t i, double t) { return (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT); };
+            auto push = [&](double t) -> int {
+                int64_t f;
+                if (int rc = P.frame_index(t, &f)) return rc;
+                fr.push_back((int32_t)f);
+                return MGN_OK;
+            };
+            double t = T0;
+            if (!euler)
+                if (int rc = push(t)) return rc;                 // k1
+            for (int64_t i = 0; i < K; ++i) {
+                const double tn = next_t(i, t);
+                if (euler) {
+                    if (int rc = push(t)) return rc;
+                } else {
+                    for (int sidx = 1; sidx < 6; ++sidx)
+                        if (int rc = push(tt(t + tt(TS_C[sidx] * DT)))) return rc;
+                    if (int rc = push(tn)) return rc;            // stage 7 = z_{n+1,1} sees t_{n+1}
+                }
+                t = tn;
+            }
+        }
+        int32_t gi = -1;
+        for (size_t q = 0; q < groups.size() && gi < 0; ++q)
+            if (groups[q].K == K && groups[q].save_step == ss) gi = (int32_t)q;
+        if (gi < 0) {
+            gi = (int32_t)groups.size();
+            groups.emplace_back();
+            groups.back().K = K;
+            groups.back().save_step = ss;
+        }
+        groups[gi].win.push_back(w);
+        groups[gi].fr.push_back(std::move(fr));
+        grp_of[w] = gi;
+    }
+    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the handle's training state
+
+    // ---- passes: a group's windows in chunks of at most `cap` (sizes as even as the cap allows)
+    const LocalGraph& g = h->g;
+    const int32_t N = g.N;
+    const int O = c.O, W1 = c.Fn - c.O, Fe = c.Fe;
+    const int64_t E = g.set[0].e_local;
+    const int64_t nN = (int64_t)N * O;
+    int64_t cap = std::max<int64_t>(1, (s->max_batch_nodes > 0 ? s->max_batch_nodes : ((int64_t)1 << 20)) / std::max<int32_t>(N, 1));
+    if (s->max_windows_per_pass > 0) cap = std::min<int64_t>(cap, s->max_windows_per_pass);
+    if (c.ln_dims == MGN_LN_ALL) cap = 1;   // a whole-array LayerNorm would couple the copies
+    struct Pass { int32_t grp, j0, B; size_t idx_off, cw_off; };
+    std::vector<Pass> passes;
+    std::vector<int32_t> itab;               // int32 tables: per group the frame table, per pass x0 [B] | save targets [n_saves][B] | continuity [B]
+    std::vector<float> cwtab;
+    std::vector<int64_t> out_row(W + 1, 0);  // the first output save of every window
+    for (int32_t w = 0; w < W; ++w) out_row[w + 1] = out_row[w] + (s->last[w] - s->first[w] + 1);
+    int32_t Bmax = 1;
+    for (size_t q = 0; q < groups.size(); ++q) {
+        ShootGroup& G = groups[q];
+        const int32_t nw = (int32_t)G.win.size();
+        if (inflow) {
+            G.ftab_off = itab.size();
+            const size_t ne = G.fr[0].size();
+            for (size_t e = 0; e < ne; ++e)
+                for (int32_t j = 0; j < nw; ++j) itab.push_back(G.fr[j][e]);
+        }
+        const int32_t np = (int32_t)((nw + cap - 1) / cap);
+        for (int32_t p = 0, j0 = 0; p < np; ++p) {
+            const int32_t B = nw / np + (p < nw % np ? 1 : 0);
+            Pass ps{(int32_t)q, j0, B, itab.size(), cwtab.size()};
+            const int ns = (int)G.save_step.size();
+            for (int32_t j = 0; j < B; ++j) itab.push_back(s->first[G.win[j0 + j]]);
+            for (int sv = 0; sv < ns; ++sv)
+                for (int32_t j = 0; j < B; ++j) itab.push_back(s->first[G.win[j0 + j]] + sv);
+            for (int32_t j = 0; j < B; ++j) {
+                const int32_t w = G.win[j0 + j];
+                itab.push_back(w + 1 < W ? s->first[w + 1] : s->first[w]);
+                cwtab.push_back(w + 1 < W ? cont_weight : 0.f);
+            }
+            passes.push_back(ps);
+            Bmax = std::max(Bmax, B);
+            j0 += B;
+        }
+    }
+    s->n_groups = (int32_t)groups.size();
+    s->n_passes = (int32_t)passes.size();
+
+    // ---- the call's staging on the handle: gt (engine order), frames, masks, statics, tables, accumulators
+    const size_t P_ = h->params.size();
+    const int ld = solver_adjoint_blocks((int64_t)Bmax * N, O);
+    const bool any_batch = Bmax > 1;
+    const size_t gtb = (size_t)s->n_gt * nN * 4;
+    const size_t fb = inflow ? (size_t)d->n_frames * nN * 4 : 0;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
+    const size_t o_gt = take(gtb), o_gtc = take(g.renumbered ? gtb : 0), o_fr = take(fb), o_mk = take(inflow ? (size_t)N : 0),
+                 o_oh = take(any_batch ? (size_t)N * W1 * 4 : 0), o_vm = take(any_batch && d->val_mask ? (size_t)N * 4 : 0),
+                 o_ef = take(any_batch ? (size_t)E * Fe * 4 : 0), o_out = take(d->out ? (size_t)out_row[W] * nN * 4 : 0),
+                 o_gacc = take(P_ * 8), o_lacc = take((size_t)2 * ld * 8), o_gf = take(P_ * 4), o_ls = take((size_t)O * 4),
+                 o_it = take(itab.size() * 4), o_cw = take(cwtab.size() * 4);
+    if (hipError_t e = h->shoot.ensure(off)) {
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %.3f GB for the call's staging: %s", who, (double)off * 1e-9, hipGetErrorString(e));
+    }
+    hipStream_t st = h->stream;
+    char* sbase = h->shoot.as<char>();
+    float* gtl = (float*)(sbase + o_gt);
+    float* frl = inflow ? (float*)(sbase + o_fr) : nullptr;
+    uint8_t* mkl = inflow ? (uint8_t*)(sbase + o_mk) : nullptr;
+    double* gacc = (double*)(sbase + o_gacc);
+    double* lacc = (double*)(sbase + o_lacc);
+    float* lsd = loss_scale ? (float*)(sbase + o_ls) : nullptr;
+    const int32_t* itd = (const int32_t*)(sbase + o_it);
+    const float* cwd = (const float*)(sbase + o_cw);
+    const int32_t* ngid = h->d_own_gid.as<int32_t>();
+    if (!g.renumbered) {
+        HIPCHK(h, hipMemcpyAsync(gtl, gt, gtb, hipMemcpyDefault, st));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(sbase + o_gtc, gt, gtb, hipMemcpyDefault, st));
+        HIPCHK(h, launch_shoot_gather(gtl, (const float*)(sbase + o_gtc), (int64_t)s->n_gt * nN, nN, s->n_gt, nullptr, ngid, O, st));
+    }
+    // host arrays (as mgn_rollout takes them) into the engine's order on the host: frames, inflow mask, and the statics of companion passes
+    auto gi = [&](int32_t i) { return (size_t)(g.renumbered ? g.own_gid[i] : i); };
+    std::vector<float> hf;
+    std::vector<uint8_t> hm;
+    if (inflow) {
+        hf.resize((size_t)d->n_frames * nN);
+        hm.resize((size_t)N);
+        for (int f = 0; f < d->n_frames; ++f)
+            for (int32_t i = 0; i < N; ++i) memcpy(hf.data() + ((size_t)f * N + i) * O, d->inflow_data + ((size_t)f * N + gi(i)) * O, (size_t)O * 4);
+        for (int32_t i = 0; i < N; ++i) hm[i] = d->inflow_mask[gi(i)];
+        HIPCHK(h, hipMemcpyAsync(frl, hf.data(), fb, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(mkl, hm.data(), (size_t)N, hipMemcpyHostToDevice, st));
+    }
+    std::vector<float> hs;
+    if (any_batch) {
+        hs.resize((size_t)N * W1 + (d->val_mask ? (size_t)N : 0) + (size_t)E * Fe);
+        float* ho = hs.data();
+        float* hv = ho + (size_t)N * W1;
+        float* he = hv + (d->val_mask ? (size_t)N : 0);
+        for (int32_t i = 0; i < N; ++i) {
+            if (W1 > 0) memcpy(ho + (size_t)i * W1, d->node_type_onehot + gi(i) * W1, (size_t)W1 * 4);
+            if (d->val_mask) hv[i] = d->val_mask[gi(i)];
+        }
+        for (int64_t j = 0; j < E; ++j) memcpy(he + (size_t)j * Fe, d->ef_raw + (size_t)g.set[0].edge_gid[j] * Fe, (size_t)Fe * 4);
+        if (W1 > 0) HIPCHK(h, hipMemcpyAsync(sbase + o_oh, ho, (size_t)N * W1 * 4, hipMemcpyHostToDevice, st));
+        if (d->val_mask) HIPCHK(h, hipMemcpyAsync(sbase + o_vm, hv, (size_t)N * 4, hipMemcpyHostToDevice, st));
+        if (E > 0) HIPCHK(h, hipMemcpyAsync(sbase + o_ef, he, (size_t)E * Fe * 4, hipMemcpyHostToDevice, st));
+    }
+    if (!itab.empty()) HIPCHK(h, hipMemcpyAsync(sbase + o_it, itab.data(), itab.size() * 4, hipMemcpyHostToDevice, st));
+    if (!cwtab.empty()) HIPCHK(h, hipMemcpyAsync(sbase + o_cw, cwtab.data(), cwtab.size() * 4, hipMemcpyHostToDevice, st));
+    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)O * 4, hipMemcpyDefault, st));
+    HIPCHK(h, hipMemsetAsync(gacc, 0, P_ * 8, st));
+    HIPCHK(h, hipMemsetAsync(lacc, 0, (size_t)2 * ld * 8, st));
+    const std::vector<float> zero_x0((size_t)nN, 0.f);       // (the encoder's unused state slot of a one-window pass)
+
+    // ---- the passes
+    std::vector<std::unique_ptr<Rollout>> keep_alive;          // their captured right-hand sides live until the final synchronisation
+    d->n_accept = d->n_reject = d->n_rhs = 0;
+    for (const Pass& ps : passes) {
+        const ShootGroup& G = groups[ps.grp];
+        const int32_t B = ps.B;
+        const int64_t K = G.K;
+        const int ns = (int)G.save_step.size();
+        mgn_engine* e = h;
+        if (B > 1) {
+            if (int rc = shoot_companion(h, B, &e)) return rc;
+            if (int rc = solver_prepare(e, n_grads)) return fail(h, rc, "%s: companion: %s", who, e->err.c_str());
+        }
+        auto efail = [&](int rc) { return e == h ? rc : fail(h, rc, "%s: companion: %s", who, e->err.c_str()); };
+        invalidate_static(e);
+        keep_alive.push_back(std::make_unique<Rollout>());
+        Rollout& R = *keep_alive.back();
+        dw.n_saves = ns;
+        R.h = e;
+        R.d = &dw;
+        R.f64 = f64;
+        R.sdt = SDT;
+        R.train = !euler;
+        R.n = (int64_t)B * nN;
+        R.n_global = R.n;
+        R.nrows = B * N;
+        const size_t nb = (size_t)R.n * 4;
+        const size_t eb = tile_floats(e->es[0].ntiles_e, c.L) * 4;
+        const bool zc = !euler && inflow;
+        size_t eo = 0;
+        auto etake = [&](size_t bytes) { const size_t o_ = eo; eo += al(bytes); return o_; };
+        const size_t o_u = etake(nb), o_un = etake(euler ? 0 : nb), o_ut = etake(nb);
+        size_t o_k[7];
+        for (int j = 0; j < 7; ++j) o_k[j] = etake(euler && j > 0 ? 0 : nb);
+        const size_t o_za = etake(zc ? nb : 0), o_zs = etake(zc ? nb : 0), o_z7 = etake(zc ? nb : 0);
+        const size_t o_sv = etake((size_t)ns * nb), o_el = etake(eb), o_tg = etake((size_t)ns * nb), o_ct = etake(nb), o_a = etake(nb),
+                     o_yb = etake(euler ? 0 : 5 * nb), o_mr = etake(inflow && B > 1 ? (size_t)B * N : 0);
+        if ((size_t)(K + 1) > (SIZE_MAX / 8) / (nb > 0 ? nb : 1)) return fail(h, MGN_E_OOM, "%s: %lld stored steps overflow the address space", who, (long long)K);
+        const size_t o_st = etake((size_t)(euler ? K + 1 : 6 * K) * nb);
+        if (hipError_t er = e->ode.ensure(eo)) {
+            (void)hipGetLastError();
+            return fail(h, er == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %.3f GB for a pass of %d windows (stored states and buffers): %s",
+                        who, (double)eo * 1e-9, B, hipGetErrorString(er));
+        }
+        char* base = e->ode.as<char>();
+        R.u = (float*)(base + o_u); R.unew = euler ? nullptr : (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
+        for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + (euler ? o_k[0] : o_k[j]));
+        if (zc) { R.za = (float*)(base + o_za); R.zs = (float*)(base + o_zs); R.z7 = (float*)(base + o_z7); }
+        R.frames = frl;
+        R.mask = mkl;
+        R.ftab = inflow ? itd + G.ftab_off + ps.j0 : nullptr;
+        R.ftab_ld = (int64_t)G.win.size();
+        R.win_rows = N;
+        R.saves = (float*)(base + o_sv);
+        R.partial = nullptr;
+        R.elat0_off = o_el;
+        uint8_t* mrep = inflow ? (B > 1 ? (uint8_t*)(base + o_mr) : mkl) : nullptr;
+        float* store = (float*)(base + o_st);
+        if (e == h) {
+            if (int rc = solver_statics(h, d, zero_x0.data(), base + o_el, eb)) return rc;
+        } else {
+            if (int rc = shoot_statics(e, B, N, (const float*)(sbase + o_oh), d->val_mask ? (const float*)(sbase + o_vm) : nullptr,
+                                       (const float*)(sbase + o_ef), base + o_el, eb)) return efail(rc);
+            if (inflow) HIPCHK(h, launch_shoot_gather_u8(mrep, mkl, (int64_t)B * N, N, st));
+        }
+        const int32_t* ix = itd + ps.idx_off;
+        HIPCHK(h, launch_shoot_gather(R.u, gtl, R.n, nN, 0, ix, nullptr, 0, st));     // x0 = gt[first[w]]
+
+        // forward: the single-window loops, save points from the group's plan
+        int saved = 0;
+        auto save = [&]() { return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, st); };
+        auto saves_after = [&](int64_t steps_done) -> hipError_t {
+            while (saved < ns && G.save_step[saved] == steps_done)
+                if (hipError_t er = save()) return er;
+            return hipSuccess;
+        };
+        HIPCHK(h, saves_after(0));
+        std::vector<float*> steps;
+        std::vector<double> step_h;
+        if (euler) {
+            for (int64_t i = 0; i < K; ++i) {
+                float* xin = R.u;
+                if (R.mask) {
+                    HIPCHK(h, hipMemcpyAsync(R.utmp, R.u, nb, hipMemcpyDeviceToDevice, st));
+                    xin = R.utmp;
+                }
+                if (int rc = R.rhs(xin, 0.0, R.k[0])) return efail(rc);
+                HIPCHK(h, hipMemcpyAsync(store + (size_t)i * R.n, xin, nb, hipMemcpyDeviceToDevice, st));
+                LinComb lc{1, {1.f}, {R.k[0]}};
+                HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)DT, R.n, st));
+                HIPCHK(h, saves_after(i + 1));
+            }
+            HIPCHK(h, hipMemcpyAsync(store + (size_t)K * R.n, R.u, nb, hipMemcpyDeviceToDevice, st));
+        } else {
+            int64_t nacc = 0;
+            for (int64_t i = 0; i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
+            step_h.assign((size_t)K, DT);
+            R.keep = [&](int sidx, const float* x) -> int {
+                HIPCHK(h, hipMemcpyAsync(steps[nacc] + (size_t)sidx * R.n, x, nb, hipMemcpyDeviceToDevice, st));
+                return MGN_OK;
+            };
+            if (int rc = R.tsit5_first(0.0)) return efail(rc);
+            for (int64_t i = 0; i < K; ++i) {
+                HIPCHK(h, hipMemcpyAsync(steps[i], zc ? R.za : R.u, nb, hipMemcpyDeviceToDevice, st));
+                if (int rc = R.tsit5_trial(0.0, DT, 0.0, nullptr)) return efail(rc);
+                R.tsit5_advance();
+                ++nacc;
+                HIPCHK(h, saves_after(i + 1));
+            }
+            R.keep = nullptr;
+        }
+        if (saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", who, saved, ns);
+        d->n_accept += (int32_t)(K * B);
+        d->n_rhs += R.n_rhs * B;
+
+        // targets of the pass, gathered out of gt on the device
+        float* tg = (float*)(base + o_tg);
+        float* ctt = (float*)(base + o_ct);
+        bool has_ct = false;
+        for (int32_t j = 0; j < B; ++j) has_ct = has_ct || G.win[ps.j0 + j] + 1 < W;
+        HIPCHK(h, launch_shoot_gather(tg, gtl, (int64_t)ns * R.n, nN, 0, ix + B, nullptr, 0, st));
+        if (has_ct) HIPCHK(h, launch_shoot_gather(ctt, gtl, R.n, nN, 0, ix + B + (size_t)ns * B, nullptr, 0, st));
+
+        SolverSweep S{};
+        S.K = K; S.states = euler ? store : nullptr; S.saves = R.saves; S.save_step = G.save_step.data(); S.n_saves = ns;
+        S.gt = tg; S.loss_scale = lsd; S.inflow = mrep; S.cont_target = has_ct ? ctt : nullptr; S.cont_weight = 0.f; S.dt = euler ? (float)DT : 0.f;
+        if (e == h) {
+            S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
+        } else {
+            S.onehot = W1 > 0 ? e->d_nfB.as<float>() : nullptr; S.ef_raw = e->es[0].d_ef.as<float>(); S.val_mask = d->val_mask ? e->d_mask.as<float>() : nullptr;
+        }
+        S.a = (float*)(base + o_a); S.gacc = gacc; S.part = nullptr; S.grads = nullptr; S.loss = nullptr;
+        S.cw_win = cwd + ps.cw_off; S.win_rows = N; S.lacc = lacc; S.lacc_ld = ld; S.lscale = 1.0 / ((double)ns * (double)nN);
+        if (euler) {
+            if (int rc = solver_sweep(e, S)) return efail(rc);
+        } else {
+            Tsit5Sweep T5{steps.data(), step_h.data(), R.u, (float*)(base + o_yb)};
+            if (int rc = tsit5_sweep(e, S, T5)) return efail(rc);
+        }
+        if (d->out) {       // the predicted saves in window order
+            float* oall = (float*)(sbase + o_out);
+            for (int sv = 0; sv < ns; ++sv)
+                for (int32_t j = 0; j < B; ++j)
+                    HIPCHK(h, hipMemcpyAsync(oall + (size_t)(out_row[G.win[ps.j0 + j]] + sv) * nN, R.saves + (size_t)sv * R.n + (size_t)j * nN,
+                                             (size_t)nN * 4, hipMemcpyDeviceToDevice, st));
+        }
+    }
+
+    // ---- results: the gradient finalised once, the loss partials added in a fixed order, one synchronisation
+    float* gf = (float*)(sbase + o_gf);
+    HIPCHK(h, launch_grad_finish(gacc, gf, (int64_t)P_, st));
+    HIPCHK(h, hipMemcpyAsync(grads, gf, P_ * 4, hipMemcpyDefault, st));
+    std::vector<double> lp((size_t)2 * ld);
+    HIPCHK(h, hipMemcpyAsync(lp.data(), lacc, lp.size() * 8, hipMemcpyDeviceToHost, st));
+    std::vector<float> ov;
+    if (d->out) {
+        const size_t ob = (size_t)out_row[W] * nN * 4;
+        if (g.renumbered) {
+            ov.resize((size_t)out_row[W] * nN);
+            HIPCHK(h, hipMemcpyAsync(ov.data(), sbase + o_out, ob, hipMemcpyDeviceToHost, st));
+        } else {
+            HIPCHK(h, hipMemcpyAsync(d->out, sbase + o_out, ob, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (!ov.empty())
+        for (int64_t r = 0; r < out_row[W]; ++r)
+            for (int32_t j = 0; j < N; ++j)
+                memcpy(d->out + ((size_t)r * N + (size_t)g.own_gid[j]) * O, ov.data() + ((size_t)r * N + j) * O, (size_t)O * 4);
+    double se = 0.0, sa = 0.0;
+    for (int b = 0; b < ld; ++b) { se += lp[b]; sa += lp[(size_t)ld + b]; }
+    *loss = (float)(se + sa);
+    return MGN_OK;
 } MGN_CATCH(h)
 
 // ---- latents -------------------------------------------------------------------------------------

@@ -403,7 +403,8 @@ int prepare_graph(mgn_engine* h) {
             keep0 = 0;
             T.arena.release();                             // (an earlier graph's arena must not count as taken)
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            // a companion (mgn_shooting_grad) recomputes: the free memory belongs to its parent's own training arena
+            if (!h->companion && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
                 double reserve = 16e9;
                 if (const char* e = getenv("MGN_TRAIN_RESERVE_GB")) reserve = atof(e) * 1e9;
                 const double base = (double)layout(0) * 4.0;          // the arena with every step recomputed: a dry run of the layout below
@@ -1187,7 +1188,7 @@ struct Sweep {
         }
         HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, st));
         nb = solver_adjoint_blocks(N, O);
-        gscale = (float)(2.0 / ((double)S.n_saves * (double)n));
+        gscale = (float)(2.0 / ((double)S.n_saves * (double)(S.win_rows > 0 ? S.win_rows * O : n)));
         sidx = S.n_saves - 1;
         return MGN_OK;
     }
@@ -1209,6 +1210,13 @@ struct Sweep {
             const bool more = sidx >= 0 && S.save_step[sidx] == k;
             p.lam = (!more && k > 0) ? io + n : nullptr;
             p.dt = seed; p.N = N; p.O = O;
+            if (S.lacc) {          // mgn_shooting_grad: per-window continuity weights, partials added across the call
+                ShootAdjArgs q{p.a, p.lam, p.xbar, p.inflow, p.xs, p.gt, p.ls, p.vm, p.gscale, p.xend, p.ct, S.cw_win, S.win_rows,
+                               p.dt, N, O, (p.gt || p.ct) ? S.lacc : nullptr, S.lacc_ld, S.lscale};
+                HIPCHK(h, launch_shoot_adjoint(q, h->stream));
+                if (!more) return MGN_OK;
+                continue;
+            }
             if (p.gt || p.ct) p.part = S.part + (size_t)slot++ * 2 * nb;
             HIPCHK(h, launch_solver_adjoint(p, h->stream));
             if (!more) return MGN_OK;
@@ -1220,7 +1228,7 @@ struct Sweep {
     int vjp(const float* x, bool first) {
         TrainJob J;
         J.vjp = J.sweep = true;
-        J.first = first;
+        J.first = first && !S.lacc;       // (mgn_shooting_grad: every pass adds to the zeroed accumulator)
         J.x = x;
         J.val_mask = vm;
         J.gacc = S.gacc;
@@ -1228,6 +1236,7 @@ struct Sweep {
     }
 
     int finish() {
+        if (S.lacc) return MGN_OK;        // mgn_shooting_grad finalises once for all its passes
         hipStream_t st = h->stream;
         const int64_t P = (int64_t)h->params.size();
         float* G = h->train->grads.as<float>();

@@ -185,6 +185,27 @@ struct Tsit5SeedArgs {
     int32_t i; int64_t N; int32_t O;
 };
 hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s);
+// mgn_shooting_grad: the state holds B windows of N rows each (row r is window r / N's row r mod N).
+// The windowed adjoint step: k_solver_adjoint per element with the continuity weight of the row's window (cw_win[n / win_rows]: 0 for a
+// window with no successor), and its loss terms ADDED to running per-block partials acc[0][b] (mse times lscale = 1 / (n_saves N O) of the
+// group) and acc[ld + b] (cw_w |xend - ct|): the same block slot in every launch of a call, so the sums stay in a fixed order.
+struct ShootAdjArgs {
+    float* a; float* lam; const float* xbar; const uint8_t* inflow;
+    const float* xs; const float* gt; const float* ls; const float* vm; float gscale;
+    const float* xend; const float* ct; const float* cw_win; int64_t win_rows;
+    float dt; int64_t N; int32_t O;
+    double* acc; int32_t ld; double lscale;
+};
+hipError_t launch_shoot_adjoint(const ShootAdjArgs& p, hipStream_t s);
+// the batched inflow overwrite: x[r][:] = frames[ftab[r / N]][r mod N][:] where mask[r mod N]   (rows = B N; frames [n_frames][N][O])
+hipError_t launch_shoot_overwrite(float* x, const float* frames, const uint8_t* mask, const int32_t* ftab, int64_t N, int32_t O, int64_t rows,
+                                  hipStream_t s);
+// gathers of blocks of blk floats: dst[e] = src[sb * blk + (gid ? gid[(e mod blk) / width] * width + e mod width : e mod blk)], e < n, with
+// sb = idx ? idx[e / blk] : (e / blk) mod src_blocks -- per-window rows out of a trajectory (idx: the frame of every block), a static array
+// replicated (src_blocks = 1), a trajectory into the engine's node order (gid)
+hipError_t launch_shoot_gather(float* dst, const float* src, int64_t n, int64_t blk, int64_t src_blocks, const int32_t* idx, const int32_t* gid,
+                               int32_t width, hipStream_t s);
+hipError_t launch_shoot_gather_u8(uint8_t* dst, const uint8_t* src, int64_t n, int64_t blk, hipStream_t s);   // dst[e] = src[e mod blk]
 // acc[i] = (first ? 0 : acc[i]) + g[i] in double; out[i] = (float)acc[i]
 hipError_t launch_grad_accum(const float* g, double* acc, int64_t n, bool first, hipStream_t s);
 hipError_t launch_grad_finish(const double* acc, float* out, int64_t n, hipStream_t s);

@@ -2114,6 +2114,136 @@ hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- mgn_shooting_grad: MultipleShooting windows as one block-diagonal batch --------------------------------------------------------
+// Streaming kernels, one pass over their arrays each.  Bytes per launch (B windows of N nodes, O components, W1 one-hot columns, E edges):
+//   k_shoot_adjoint   ~ (4 + 2 (save) + 1 (continuity)) * 4 B N O read + 2 * 4 B N O written (+ B N mask bytes) -- k_solver_adjoint's
+//   k_shoot_overwrite 4 B N O read + written where the mask is set, frame rows read once per window, the mask read modulo N
+//   k_shoot_gather    4 n read + 4 n written (x0: B N O; targets: n_saves B N O; statics: B N W1, B N, B E Fe once per pass)
+__global__ __launch_bounds__(256) void k_shoot_adjoint(ShootAdjArgs p) {
+    __shared__ double sh[2][4];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double e2 = 0.0, e1 = 0.0;
+    if (i < p.N * p.O) {
+        const int64_t n = i / p.O;
+        const int o = (int)(i - n * p.O);
+        float av = p.a[i];
+        if (p.xbar && !(p.inflow && p.inflow[n])) av += p.xbar[i];
+        if (p.gt) {
+            const float sc = p.ls ? p.ls[o] : 1.f, m = p.vm ? p.vm[n] : 1.f;
+            const float d = p.gt[i] - p.xs[i];
+            const double ed = (double)sc * ((double)p.gt[i] - (double)p.xs[i]);
+            e2 = ed * ed * (double)m;
+            av -= p.gscale * sc * sc * d * m;
+        }
+        if (p.ct) {
+            const float cw = p.cw_win[n / p.win_rows];
+            const float r = p.xend[i] - p.ct[i];
+            e1 = (double)cw * fabs((double)p.xend[i] - (double)p.ct[i]);
+            av += r > 0.f ? cw : (r < 0.f ? -cw : 0.f);
+        }
+        p.a[i] = av;
+        if (p.lam) p.lam[i] = p.dt * av;
+    }
+    if (!p.acc) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        e2 += __shfl_xor(e2, off, 64);
+        e1 += __shfl_xor(e1, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = e2; sh[1][threadIdx.x >> 6] = e1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p.acc[blockIdx.x] += (sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3]) * p.lscale;
+        p.acc[p.ld + blockIdx.x] += sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+    }
+}
+
+hipError_t launch_shoot_adjoint(const ShootAdjArgs& p, hipStream_t s) {
+    const int nb = solver_adjoint_blocks(p.N, p.O);
+    if (nb == 0) return hipSuccess;
+    if (p.acc && nb > p.ld) return hipErrorInvalidValue;
+    if (p.ct && (!p.cw_win || p.win_rows <= 0)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_shoot_adjoint, dim3(nb), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_shoot_overwrite(float* __restrict__ x, const float* __restrict__ frames, const uint8_t* __restrict__ mask,
+                                                         const int32_t* __restrict__ ftab, int64_t N, int32_t O, int64_t n) {
+    const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (e >= n) return;                     // n is a multiple of V
+    float v[V];
+    ldv<V>(v, x + e);
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+        const int64_t r = (e + q) / O;
+        const int64_t w = r / N, i = r - w * N;
+        if (mask[i]) {
+            v[q] = frames[((int64_t)ftab[w] * N + i) * O + (e + q - r * O)];
+            any = true;
+        }
+    }
+    if (any) stv<V>(x + e, v);
+}
+
+hipError_t launch_shoot_overwrite(float* x, const float* frames, const uint8_t* mask, const int32_t* ftab, int64_t N, int32_t O, int64_t rows,
+                                  hipStream_t s) {
+    const int64_t n = rows * O;
+    if (n <= 0) return hipSuccess;
+    if (N <= 0 || rows % N) return hipErrorInvalidValue;
+    if (n % 4 == 0 && ((uintptr_t)x & 15) == 0)
+        hipLaunchKernelGGL(k_shoot_overwrite<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, frames, mask, ftab, N, O, n);
+    else
+        hipLaunchKernelGGL(k_shoot_overwrite<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, frames, mask, ftab, N, O, n);
+    return hipGetLastError();
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_shoot_gather(float* __restrict__ dst, const float* __restrict__ src, int64_t n, int64_t blk,
+                                                      int64_t src_blocks, const int32_t* __restrict__ idx, const int32_t* __restrict__ gid,
+                                                      int32_t width) {
+    const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (e >= n) return;                     // blk is a multiple of V: a vector never straddles two blocks
+    const int64_t b = e / blk, rem = e - b * blk;
+    const float* sb = src + (idx ? (int64_t)idx[b] : b % src_blocks) * blk;
+    float v[V];
+    if (gid) {
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            const int64_t row = (rem + q) / width;
+            v[q] = sb[(int64_t)gid[row] * width + (rem + q - row * width)];
+        }
+    } else {
+        ldv<V>(v, sb + rem);
+    }
+    stv<V>(dst + e, v);
+}
+
+hipError_t launch_shoot_gather(float* dst, const float* src, int64_t n, int64_t blk, int64_t src_blocks, const int32_t* idx, const int32_t* gid,
+                               int32_t width, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (blk <= 0 || n % blk || (!idx && src_blocks <= 0) || (gid && (width <= 0 || blk % width))) return hipErrorInvalidValue;
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    if (!gid && blk % 4 == 0 && al16(dst) && al16(src))
+        hipLaunchKernelGGL(k_shoot_gather<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, dst, src, n, blk, src_blocks, idx, gid, width);
+    else
+        hipLaunchKernelGGL(k_shoot_gather<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, src, n, blk, src_blocks, idx, gid, width);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void k_shoot_gather_u8(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t n, int64_t blk) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) dst[e] = src[e % blk];
+}
+
+hipError_t launch_shoot_gather_u8(uint8_t* dst, const uint8_t* src, int64_t n, int64_t blk, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (blk <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_shoot_gather_u8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, src, n, blk);
+    return hipGetLastError();
+}
+
 // acc[i] = (first ? 0 : acc[i]) + g[i]  (double accumulator of the per-step parameter gradients)
 __global__ __launch_bounds__(256) void k_grad_accum(const float* __restrict__ g, double* __restrict__ acc, int64_t n, int first) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

@@ -404,6 +404,43 @@ class Engine:
         del keep
         return (gs, loss.value, pred) if want_pred else (gs, loss.value)
 
+    def shooting_grad(self, node_type_onehot, ef_raw, gt, windows, t0s, t1s, dt, saves_dt, val_mask=None, inflow_mask=None, inflow_data=None,
+                      loss_scale=None, cont_weight=0.0, inflow_rule="reference", time_type=np.float32, solver="Euler", adaptive=False,
+                      max_windows_per_pass=0, max_batch_nodes=0, want_pred=False, out=None):
+        """The summed loss and gradient of the MultipleShooting windows `windows` [(first, last), ...] (0-based, inclusive indices into
+        gt [n_gt][N][O]) in one native call (mgn_shooting_grad): window w is solver_grad (solver "Euler") or solver_grad_tsit5 with
+        adaptive=False ("Tsit5") from x0 = gt[first] over (t0s[w], t1s[w]) with saves gt[first .. last], and the continuity term
+        cont_weight * sum(abs.(x_end - gt[first of window w + 1])) for every window but the last.  Windows with the same step plan run
+        together as one batch of graph copies, at most max_windows_per_pass (0: no cap) and max_batch_nodes nodes (0: 2^20) per pass.
+        gt and `out` may be device tensors.  adaptive=True (Tsit5) is refused (MGN_E_UNSUPPORTED).  Returns (grads, loss) or, with
+        want_pred, (grads, loss, pred [sum of the windows' saves][N][O]); self.last_shooting holds n_groups, n_passes, n_accept, n_rhs."""
+        O = self.cfg.O
+        n_gt = int(gt.shape[0])
+        windows = [(int(a), int(b)) for a, b in windows]
+        d, keep, p_gt, ls, _, gs, p_gs, _ = self._solver_desc(solver, np.zeros((self.N, O), np.float32), node_type_onehot, ef_raw, gt, 0.0,
+                                                             0.0, dt, saves_dt, n_gt, val_mask, inflow_mask, inflow_data, loss_scale, None,
+                                                             inflow_rule, time_type, False, out)
+        W = len(windows)
+        first = np.ascontiguousarray([a for a, _ in windows], np.int32)
+        last = np.ascontiguousarray([b for _, b in windows], np.int32)
+        t0 = np.ascontiguousarray(t0s, np.float64).reshape(W)
+        t1 = np.ascontiguousarray(t1s, np.float64).reshape(W)
+        s = _capi.MgnShootingDesc()
+        s.n_windows, s.n_gt, s.adaptive = W, n_gt, 1 if adaptive else 0
+        s.first = first.ctypes.data_as(C.POINTER(C.c_int32))
+        s.last = last.ctypes.data_as(C.POINTER(C.c_int32))
+        s.t0 = t0.ctypes.data_as(C.POINTER(C.c_double))
+        s.t1 = t1.ctypes.data_as(C.POINTER(C.c_double))
+        s.max_windows_per_pass, s.max_batch_nodes = int(max_windows_per_pass), int(max_batch_nodes)
+        pred = np.zeros((int(sum(b - a + 1 for a, b in windows)), self.N, O), np.float32) if want_pred else None
+        d.out = f32(pred)
+        loss = C.c_float()
+        self._chk(self.lib.mgn_shooting_grad(self.h, C.byref(d), C.byref(s), p_gt, f32(ls), float(cont_weight), p_gs, self.param_count,
+                                             C.byref(loss)))
+        del keep
+        self.last_shooting = {"n_groups": s.n_groups, "n_passes": s.n_passes, "n_accept": d.n_accept, "n_rhs": d.n_rhs}
+        return (gs, loss.value, pred) if want_pred else (gs, loss.value)
+
     def solver_grad_tsit5(self, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, adaptive=True, abstol=1e-6, reltol=1e-3,
                           val_mask=None, inflow_mask=None, inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0,
                           inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0):

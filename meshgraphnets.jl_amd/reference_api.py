@@ -541,16 +541,25 @@ def train_step_solver_training(eng, gt, node_type_onehot, ef_raw, tstart, dt, ts
 
 def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, tstop, interval_size, continuity_term, val_mask=None,
                                  inflow_mask=None, inflow_data=None, solver_dt=None, time_type=F32, inflow_rule="reference", solver="Euler",
-                                 adaptive=True, abstol=1e-6, reltol=1e-3):
+                                 adaptive=True, abstol=1e-6, reltol=1e-3, batched=False, max_windows_per_pass=0):
     """train_step(::MultipleShooting) with a fixed-step Euler solver (reference src/strategies.jl:312-383): one Engine.solver_grad per
     window rg of multiple_shooting_ranges, u0 = gt[first(rg)], saveat = tsteps[rg], loss = mean((gt[rg] - pred) .^ 2 .* val_mask) (no
     normaliser); the continuity term continuity_term * sum(abs, pred_{i-1}[end] - gt[first(rg_i)]) goes with window i - 1.  solver,
     adaptive, abstol, reltol as for train_step_solver_training (every window steps onto its saves: tstops = saveat, where the reference
-    interpolates a window solved without tstops).  Returns the summed (gs, loss)."""
+    interpolates a window solved without tstops).  Returns the summed (gs, loss).
+    batched=True: Euler and fixed-step Tsit5 (adaptive=False) solve all windows in one Engine.shooting_grad call (windows with the same
+    step plan as one batch of graph copies, at most max_windows_per_pass per pass, 0: no cap) -- the same sum.  Adaptive Tsit5 keeps the
+    per-window loop (each window would need its own step controller)."""
     T = _range_length(tstart, dt, tstop)
     ranges = multiple_shooting_ranges(T, interval_size)
     if inflow_mask is not None and inflow_data is None:
         inflow_data = gt
+    if batched and not (solver == "Tsit5" and adaptive):
+        gs, loss = eng.shooting_grad(node_type_onehot, ef_raw, gt, ranges, [_range_at(tstart, dt, a, time_type) for a, _ in ranges],
+                                     [_range_at(tstart, dt, b, time_type) for _, b in ranges], solver_dt or dt, dt, val_mask=val_mask,
+                                     inflow_mask=inflow_mask, inflow_data=inflow_data, cont_weight=float(continuity_term),
+                                     inflow_rule=inflow_rule, time_type=time_type, solver=solver, max_windows_per_pass=max_windows_per_pass)
+        return np.asarray(gs, np.float64), float(loss)
     gs_sum, loss_sum = None, 0.0
     for i, (a, b) in enumerate(ranges):
         nxt = ranges[i + 1][0] if i + 1 < len(ranges) else None
