@@ -1795,9 +1795,52 @@ extern "C++" double mgn::tsit5_a(int i, int j) { return TS_A[i - 1][j - 1]; }   
 
 namespace {
 
+// mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
+// of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
+struct Tsit5Control {
+    static constexpr double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
+    double qold = 1e-4;
+    bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
+        const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
+        if (EEst <= 1.0) {
+            double q = q11 / std::pow(qold, beta2);
+            q = std::max(1.0 / qmax, std::min(1.0 / qmin, q / gamma));
+            qold = std::max(EEst, 1e-4);
+            if (!hit_stop || hstep >= dt * (1 - 1e-9)) dt = hstep / q;
+            else dt = std::max(dt, hstep / q);
+            return true;
+        }
+        dt = hstep / std::min(1.0 / qmin, q11 / gamma);
+        return false;
+    }
+};
+
+// The time grid of a solve.  The solver's time type (mgn_rollout_desc.time_f64): Float32 times are held in doubles and rounded after
+// every operation (a double operation on two floats, rounded to float, IS the float operation).
+struct TimeGrid {
+    bool f64 = false;
+    double t0 = 0.0, t1 = 0.0, dt = 0.0, sdt = 0.0;     // sdt: saves_dt
+    explicit TimeGrid(const mgn_rollout_desc* d)
+        : f64(d->time_f64 != 0), t0(f64 ? d->t0_f64 : (double)d->t0), t1(f64 ? d->t1_f64 : (double)d->t1),
+          dt(f64 ? d->dt_f64 : (double)d->dt), sdt(f64 ? d->saves_dt_f64 : (double)d->saves_dt) {}
+    double tt(double v) const { return f64 ? v : (double)(float)v; }
+    // the time of save point i
+    double stop_time(int i) const { return tt(t0 + (double)i * sdt); }
+    // the fixed-step grid: the time after step i of K is the integrator's own t <- t + dt in its time type, step after step (a fixed-step
+    // solve has no stops to snap to but the end of the interval); t0 + (i + 1) dt would floor differently at frame boundaries
+    double next(int64_t i, int64_t K, double t) const { return (i + 1 == K && std::fabs(tt(t + dt) - t1) <= 1e-5 * sdt) ? t1 : tt(t + dt); }
+};
+
+// one call's buffers carved out of one DevBuf: 256-byte aligned offsets, then one ensure of `off` bytes
+struct Arena {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+};
+
 struct Rollout {
     mgn_engine* h;
     mgn_rollout_desc* d;
+    TimeGrid tg;
     int64_t n;                 // rows * O of the state this handle integrates (all N rows, or the owned rows of a partition)
     int64_t n_global = 0;      // N * O
     int32_t nrows = 0;
@@ -1805,11 +1848,8 @@ struct Rollout {
     uint8_t* mask;
     double* partial;
     int n_rhs = 0;
-    // the solver's time type (mgn_rollout_desc.time_f64): Float32 times are held in doubles and rounded after every operation
-    // (a double operation on two floats, rounded to float, IS the float operation)
-    bool f64 = false;
-    double sdt = 0.0;          // saves_dt in that type
-    double tt(double v) const { return f64 ? v : (double)(float)v; }
+    Rollout(mgn_engine* h_, mgn_rollout_desc* d_, const TimeGrid& g) : h(h_), d(d_), tg(g) {}
+    double tt(double v) const { return tg.tt(v); }
 
     // One right-hand side is ~35 launches; on a small mesh they are latency-bound, so each distinct (x, kout) pair of the
     // solver (1 for Euler, 7 for Tsit5) gets its launch sequence captured once and replayed (hipGraph).
@@ -1853,11 +1893,11 @@ struct Rollout {
     int frame_index(double t, int64_t* out) const {
         int64_t fr;
         if (d->inflow_rule == MGN_INFLOW_TOLERANT) {
-            fr = (int64_t)std::floor(t / sdt + 1e-3);
+            fr = (int64_t)std::floor(t / tg.sdt + 1e-3);
             if (fr < 0) fr = 0;
             if (fr >= d->n_frames) fr = d->n_frames - 1;
         } else {
-            fr = (int64_t)std::floor(tt(t / sdt));
+            fr = (int64_t)std::floor(tt(t / tg.sdt));
             if (fr < 0 || fr >= d->n_frames)
                 return fail(h, MGN_E_ARG, "mgn_rollout: inflow frame %lld at t = %.9g is outside the %d frames given (reference: BoundsError)",
                             (long long)fr, t, d->n_frames);
@@ -1933,21 +1973,56 @@ struct Rollout {
         return MGN_OK;
     }
 
-    // ---- Tsit5, shared by mgn_rollout and mgn_solver_grad_tsit5 ----
-    // Training form (mgn_solver_grad_tsit5, ode_func_train): the right-hand side of a stage sees a COPY of the stage's combination with
-    // the inflow rows written -- za for stage 1 (z_{n,1}), zs for stages 2 .. 6, z7 for stage 7 (z_{n+1,1}) -- and the state is never
-    // overwritten.  mgn_rollout (train = false), or no inflow mask: the combination itself (mgn_rollout overwrites it in place).
+    // ---- saves ----
+    int saved = 0;                         // saves taken
+    std::vector<int64_t> save_step;        // the accepted steps before each save taken
+    // saves[saved] <- u, the state after steps_done accepted steps
+    int save(int64_t steps_done) {
+        save_step.push_back(steps_done);
+        HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved++ * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    }
+    // the saves a fixed-step plan (the accepted steps before every save, fixed_grid) takes after steps_done steps
+    int saves_after(const std::vector<int64_t>& plan, int64_t steps_done) {
+        while (saved < (int)plan.size() && plan[saved] == steps_done)
+            if (int rc = save(steps_done)) return rc;
+        return MGN_OK;
+    }
+
+    // Training form (solver-based training, ode_func_train): the right-hand side sees a COPY of its input with the inflow rows written --
+    // utmp for Euler; za for Tsit5 stage 1 (z_{n,1}), zs for stages 2 .. 6, z7 for stage 7 (z_{n+1,1}) -- and the state is never
+    // overwritten.  mgn_rollout (train = false), or no inflow mask: the input itself (mgn_rollout overwrites it in place).
     bool train = false;
     float *za = nullptr, *zs = nullptr, *z7 = nullptr;
-    std::function<int(int, const float*)> keep;     // training form: after stage i (1 .. 5, 0-based) of a trial, the array its RHS saw
+    float* kept = nullptr;     // training form: the current Tsit5 trial's six stage inputs [6][n] (z_{n,1}, stages 2 .. 6), or null
 
+    // the array the right-hand side of input y sees (z: its training-form copy)
+    float* rhs_input(float* y, float* z) const { return (train && mask) ? z : y; }
     int eval(float* y, float* z, double t, float* kout) {
-        if (train && mask) {
-            HIPCHK(h, hipMemcpyAsync(z, y, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-            y = z;
-        }
-        return rhs(y, t, kout);
+        float* x = rhs_input(y, z);
+        if (x != y) HIPCHK(h, hipMemcpyAsync(x, y, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return rhs(x, t, kout);
     }
+
+    // ---- fixed-step Euler, training form: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k -> store[k] and x_K -> store[K]; saves from the plan ----
+    int euler_train(int64_t K, const std::vector<int64_t>& plan, float* store) {
+        double t = tg.t0;
+        if (int rc = saves_after(plan, 0)) return rc;
+        for (int64_t i = 0; i < K; ++i) {
+            float* xin = rhs_input(u, utmp);
+            if (int rc = eval(u, utmp, t, k[0])) return rc;
+            HIPCHK(h, hipMemcpyAsync(store + (size_t)i * n, xin, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+            LinComb lc{1, {1.f}, {k[0]}};
+            HIPCHK(h, launch_lincomb(u, u, lc, (float)tg.dt, n, h->stream));
+            t = tg.next(i, K, t);
+            ++d->n_accept;
+            if (int rc = saves_after(plan, i + 1)) return rc;
+        }
+        HIPCHK(h, hipMemcpyAsync(store + (size_t)K * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    }
+
+    // ---- Tsit5, shared by mgn_rollout, mgn_solver_grad_tsit5 and mgn_shooting_grad ----
     // k1 = f(u) at t (FSAL afterwards)
     int tsit5_first(double t) { return eval(u, za, t, k[0]); }
     // Hairer-Wanner starting step from (u, k1)
@@ -1978,8 +2053,8 @@ struct Rollout {
             HIPCHK(h, launch_lincomb(dst, u, lc, (float)hstep, n, h->stream));
             float* z = (sidx == 6) ? z7 : zs;
             if (int rc = eval(dst, z, sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep)), k[sidx])) return rc;
-            if (sidx < 6 && keep)
-                if (int rc = keep(sidx, (train && mask) ? z : dst)) return rc;
+            if (sidx < 6 && kept)
+                HIPCHK(h, hipMemcpyAsync(kept + (size_t)sidx * n, rhs_input(dst, z), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         }
         if (!EEst) return MGN_OK;
         LinComb le{7, {}, {}};
@@ -1992,27 +2067,165 @@ struct Rollout {
         std::swap(k[0], k[6]);
         std::swap(za, z7);
     }
-};
 
-// mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
-// of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
-struct Tsit5Control {
-    static constexpr double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
-    double qold = 1e-4;
-    bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
-        const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
-        if (EEst <= 1.0) {
-            double q = q11 / std::pow(qold, beta2);
-            q = std::max(1.0 / qmax, std::min(1.0 / qmin, q / gamma));
-            qold = std::max(EEst, 1e-4);
-            if (!hit_stop || hstep >= dt * (1 - 1e-9)) dt = hstep / q;
-            else dt = std::max(dt, hstep / q);
-            return true;
+    // training form: slot(n, &p) gives accepted step n's storage for its six stage inputs
+    using Slot = std::function<int(int64_t, float**)>;
+    std::vector<double> step_t, step_h;    // training form: every accepted step's t and h
+    // before a trial of step n: its storage, and z_{n,1} (what k1's right-hand side saw) into it
+    int begin_trial(const Slot& slot, int64_t n_) {
+        if (int rc = slot(n_, &kept)) return rc;
+        HIPCHK(h, hipMemcpyAsync(kept, rhs_input(u, za), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    }
+
+    // fixed-step Tsit5 in the training form: K steps of dt on the fixed grid, stage 7 at t_{n+1}; saves from the plan
+    int tsit5_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot& slot) {
+        double t = tg.t0;
+        if (int rc = saves_after(plan, 0)) return rc;
+        if (int rc = tsit5_first(t)) return rc;
+        for (int64_t i = 0; i < K; ++i) {
+            const double tn = tg.next(i, K, t);
+            if (int rc = begin_trial(slot, i)) return rc;
+            if (int rc = tsit5_trial(t, tg.dt, tn, nullptr)) return rc;
+            tsit5_advance();
+            step_t.push_back(t); step_h.push_back(tg.dt);
+            t = tn;
+            ++d->n_accept;
+            if (int rc = saves_after(plan, i + 1)) return rc;
         }
-        dt = hstep / std::min(1.0 / qmin, q11 / gamma);
-        return false;
+        kept = nullptr;
+        return MGN_OK;
+    }
+
+    // adaptive Tsit5 from t0 to t1: mgn_rollout's PI controller (Tsit5Control), tstops = saves, a save on every stop it hits, missing saves
+    // (t1 short of the last stop) padded with the final state.  mgn_rollout (no slot): stage 7 at c7 h, and the iteration guard stops
+    // silently.  Training form (slot): every trial's stage inputs kept in slot(n), stage 7 is z_{n+1,1} and sees t_{n+1}, the accepted
+    // steps recorded, and the guard fails the call.
+    int tsit5_adaptive(const char* who, const Slot* slot) {
+        const int ns = d->n_saves;
+        double t = tg.t0;
+        if (int rc = save(0)) return rc;
+        if (int rc = tsit5_first(t)) return rc;     // k1 (FSAL afterwards)
+        double dt = tg.dt;
+        if (dt <= 0)   // Hairer-Wanner starting step
+            if (int rc = tsit5_h0(t, &dt)) return rc;
+        Tsit5Control ctl;
+        int64_t guard = 0, nacc = 0;
+        // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save periods is not worth a step
+        while (t < tg.t1 - 1e-5 * tg.sdt) {
+            if (++guard >= 10000000) {
+                if (!slot) break;
+                return fail(h, MGN_E_STATE, "%s: %lld trial steps without reaching t1", who, (long long)guard);
+            }
+            double tstop = saved < ns ? tg.stop_time(saved) : tg.t1;
+            if (tstop > tg.t1) tstop = tg.t1;
+            bool hit_stop = false;
+            double hstep = dt;
+            if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
+            const double tn = hit_stop ? tstop : tt(t + hstep);
+            // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
+            const double t7 = (slot || hit_stop) ? tn : tt(t + tt(TS_C[6] * hstep));
+            if (slot)
+                if (int rc = begin_trial(*slot, nacc)) return rc;
+            double EEst;
+            if (int rc = tsit5_trial(t, hstep, t7, &EEst)) return rc;
+            if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
+            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
+                tsit5_advance();
+                if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
+                t = tn;
+                ++nacc;
+                ++d->n_accept;
+                if (hit_stop && saved < ns && std::fabs(tg.stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12)
+                    if (int rc = save(nacc)) return rc;
+            } else {
+                ++d->n_reject;
+            }
+        }
+        kept = nullptr;
+        while (saved < ns)
+            if (int rc = save(nacc)) return rc;
+        return MGN_OK;
     }
 };
+// b.ensure(bytes), or MGN_E_OOM (MGN_E_HIP for any other error) with the message "<what>: <the HIP error>"
+__attribute__((format(printf, 4, 5))) int ensure_or_fail(mgn_handle* h, DevBuf& b, size_t bytes, const char* what, ...) {
+    const hipError_t e = b.ensure(bytes);
+    if (e == hipSuccess) return MGN_OK;
+    (void)hipGetLastError();
+    char msg[400];
+    va_list ap;
+    va_start(ap, what);
+    vsnprintf(msg, sizeof msg, what, ap);
+    va_end(ap);
+    return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %s", msg, hipGetErrorString(e));
+}
+
+// x0 (u null: not wanted), the inflow frames and the inflow mask (null: none) of the caller's order into the engine's order on the device:
+// the rows this handle owns (all N, or a partition's), renumbered or not.  A reordered copy is staged on the host and synchronised.
+int upload_engine_order(mgn_handle* h, const mgn_rollout_desc* d, float* u, float* frames, uint8_t* mask) {
+    const LocalGraph& g = h->g;
+    const int O = h->cfg.O;
+    const bool part = h->cfg.nranks != 1;
+    const int32_t nloc = part ? g.n_own : g.N;
+    const int nf = frames ? d->n_frames : 0;
+    const size_t nb = (size_t)nloc * O * 4, fb = (size_t)nf * nb;
+    if (!part && !g.renumbered) {
+        if (u) HIPCHK(h, hipMemcpyAsync(u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
+        if (frames) HIPCHK(h, hipMemcpyAsync(frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
+        if (mask) HIPCHK(h, hipMemcpyAsync(mask, d->inflow_mask, (size_t)nloc, hipMemcpyHostToDevice, h->stream));
+        return MGN_OK;
+    }
+    std::vector<float> lx((size_t)nloc * O * (1 + nf));
+    std::vector<uint8_t> lm(mask ? (size_t)nloc : 0);
+    for (int32_t i = 0; i < nloc; ++i) {
+        const size_t gi = (size_t)g.own_gid[i];
+        if (u) memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
+        for (int f = 0; f < nf; ++f)
+            memcpy(lx.data() + ((size_t)(1 + f) * nloc + i) * O, d->inflow_data + ((size_t)f * g.N + gi) * O, (size_t)O * 4);
+        if (mask) lm[i] = d->inflow_mask[gi];
+    }
+    if (u) HIPCHK(h, hipMemcpyAsync(u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
+    if (frames) HIPCHK(h, hipMemcpyAsync(frames, lx.data() + (size_t)nloc * O, fb, hipMemcpyHostToDevice, h->stream));
+    if (mask) HIPCHK(h, hipMemcpyAsync(mask, lm.data(), (size_t)nloc, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+}
+
+// count [N][O] arrays in the engine's order on the device (one partition) into the caller's order on the host; the caller synchronises
+int saves_to_caller(mgn_handle* h, const float* src, int64_t count, float* out) {
+    const LocalGraph& g = h->g;
+    const int O = h->cfg.O;
+    const size_t bytes = (size_t)count * g.N * O * 4;
+    if (!g.renumbered) {
+        HIPCHK(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream));
+        return MGN_OK;
+    }
+    std::vector<float> sv((size_t)count * g.N * O);
+    HIPCHK(h, hipMemcpyAsync(sv.data(), src, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < count; ++i)
+        for (int32_t j = 0; j < g.N; ++j)
+            memcpy(out + ((size_t)i * g.N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * g.N + j) * O, (size_t)O * 4);
+    return MGN_OK;
+}
+
+// the static inputs of a solve (one-hot node types, raw edge features, val_mask; x0 only fills the encoder's state slot: every right-hand
+// side reads its state through srcA_override), and the edges encoded ONCE per trajectory into elat0 (eb: its fp32 bytes)
+int upload_statics(mgn_handle* h, const mgn_rollout_desc* d, const float* x0, char* elat0, size_t eb) {
+    const mgn_config& c = h->cfg;
+    if (int rc = upload_inputs(h, x0, c.O, d->node_type_onehot, c.Fn - c.O, d->ef_raw, true)) return rc;
+    h->have_mask = d->val_mask != nullptr;
+    if (d->val_mask) {
+        HIPCHK(h, h->d_mask.ensure((size_t)h->g.N * 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)h->g.N * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
+    if (int rc = encode_impl(h, true, false, true)) return rc;
+    const bool bf = is_bf16(h);
+    HIPCHK(h, hipMemcpyAsync(elat0, bf ? h->es[0].bElat.p : h->es[0].Elat.p, bf ? eb / 2 : eb, hipMemcpyDeviceToDevice, h->stream));
+    return MGN_OK;
+}
 
 }  // namespace
 
@@ -2025,24 +2238,16 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", "mgn_rollout");
     if (!d || !d->x0 || !d->out || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "mgn_rollout: null argument");
     if (c.Fn < c.O) return fail(h, MGN_E_ARG, "mgn_rollout: Fn < O");
-    const bool f64 = d->time_f64 != 0;
-    const double T0 = f64 ? d->t0_f64 : (double)d->t0, T1 = f64 ? d->t1_f64 : (double)d->t1, DT = f64 ? d->dt_f64 : (double)d->dt,
-                 SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
-    if (d->n_saves < 1 || !(SDT > 0.0) || T1 < T0) return fail(h, MGN_E_ARG, "mgn_rollout: bad time grid");
-    if (d->solver == 0 && !(DT > 0.0)) return fail(h, MGN_E_ARG, "mgn_rollout: Euler needs dt > 0");
+    const TimeGrid T(d);
+    if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "mgn_rollout: bad time grid");
+    if (d->solver == 0 && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "mgn_rollout: Euler needs dt > 0");
     if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "mgn_rollout: unknown inflow_rule");
     if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "mgn_rollout: solver must be 0 (Euler) or 1 (Tsit5)");
     if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "mgn_rollout: inflow mask and data go together");
     if (d->solver == 1 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "mgn_rollout: tolerances must be > 0");
     const LocalGraph& g = h->g;
     invalidate_static(h);
-    Rollout R;
-    R.h = h;
-    R.d = d;
-    R.f64 = f64;
-    R.sdt = SDT;
-    auto tt = [&](double v) { return R.tt(v); };
-    const bool loc = part || g.renumbered;            // the state lives in the engine's node order (owned rows): gathered in, scattered out
+    Rollout R(h, d, T);
     const int32_t nloc = part ? g.n_own : g.N;        // rows of the state this handle integrates
     R.n = (int64_t)nloc * c.O;
     R.n_global = (int64_t)g.N * c.O;
@@ -2050,15 +2255,13 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     const size_t nb = (size_t)R.n * 4;
     const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
     const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t o_u = take(nb), o_un = take(nb), o_ut = take(nb);
+    Arena a;
+    const size_t o_u = a.take(nb), o_un = a.take(nb), o_ut = a.take(nb);
     size_t o_k[7];
-    for (auto& o : o_k) o = take(nb);
-    const size_t o_fr = take(fb), o_sv = take(sb), o_mask = take((size_t)nloc), o_part = take(errnorm_partials() * sizeof(double));
-    R.elat0_off = take(eb);
-    HIPCHK(h, h->ode.ensure(off));
+    for (auto& o : o_k) o = a.take(nb);
+    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)nloc), o_part = a.take(errnorm_partials() * sizeof(double));
+    R.elat0_off = a.take(eb);
+    HIPCHK(h, h->ode.ensure(a.off));
     char* base = h->ode.as<char>();
     R.u = (float*)(base + o_u); R.unew = (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
     for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[j]);
@@ -2066,111 +2269,36 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     R.saves = (float*)(base + o_sv);
     R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
     R.partial = (double*)(base + o_part);
-
-    if (!loc) {
-        HIPCHK(h, hipMemcpyAsync(R.u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
-        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
-        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, d->inflow_mask, (size_t)g.N, hipMemcpyHostToDevice, h->stream));
-    } else {        // the owned rows of the state, of every inflow frame and of the inflow mask
-        const int O = c.O;
-        std::vector<float> loc((size_t)nloc * O * (1 + (d->inflow_data ? d->n_frames : 0)));
-        std::vector<uint8_t> lm(d->inflow_mask ? (size_t)nloc : 0);
-        for (int32_t i = 0; i < nloc; ++i) {
-            const size_t gi = (size_t)g.own_gid[i];
-            memcpy(loc.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
-            for (int f = 0; d->inflow_data && f < d->n_frames; ++f)
-                memcpy(loc.data() + ((size_t)(1 + f) * nloc + i) * O, d->inflow_data + ((size_t)f * g.N + gi) * O, (size_t)O * 4);
-            if (d->inflow_mask) lm[i] = d->inflow_mask[gi];
-        }
-        HIPCHK(h, hipMemcpyAsync(R.u, loc.data(), nb, hipMemcpyHostToDevice, h->stream));
-        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, loc.data() + (size_t)nloc * O, fb, hipMemcpyHostToDevice, h->stream));
-        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, lm.data(), (size_t)nloc, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    // static inputs: one-hot node types, raw edge features, val_mask; the edge encoder runs ONCE per trajectory
-    if (int rc = upload_inputs(h, d->x0, c.O, d->node_type_onehot, c.Fn - c.O, d->ef_raw, true)) return rc;
-    h->have_mask = d->val_mask != nullptr;
-    if (d->val_mask) {
-        HIPCHK(h, h->d_mask.ensure((size_t)g.N * 4));
-        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)g.N * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (lnall) {
-        if (int rc = lnall_rhs_prepare(h)) return rc;
-    } else {
-        if (int rc = encode_impl(h, true, false, true)) return rc;
-        HIPCHK(h, hipMemcpyAsync(base + R.elat0_off, is_bf16(h) ? h->es[0].bElat.p : h->es[0].Elat.p, is_bf16(h) ? eb / 2 : eb, hipMemcpyDeviceToDevice, h->stream));
-    }
+    if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
+    if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
 
     d->n_accept = d->n_reject = 0;
-    int saved = 0;
-    auto save = [&]() -> hipError_t {
-        if (saved >= d->n_saves) return hipSuccess;
-        return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream);
-    };
-    auto stop_time = [&](int i) { return tt(T0 + (double)i * SDT); };
-    double t = T0;
-    HIPCHK(h, save());   // solution at t0
-
     if (d->solver == 0) {
-        const double dt = DT;
-        const int64_t nsteps = (int64_t)std::llround((T1 - T0) / dt);
+        if (int rc = R.save(0)) return rc;   // solution at t0
+        double t = T.t0;
+        const int64_t nsteps = (int64_t)std::llround((T.t1 - T.t0) / T.dt);
         for (int64_t i = 0; i < nsteps; ++i) {
             if (int rc = R.rhs(R.u, t, R.k[0])) return rc;
             LinComb lc{1, {1.f}, {R.k[0]}};
-            HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)dt, R.n, h->stream));
-            // the time the right-hand side sees is the integrator's own: t <- t + dt in its time type, step after step (a fixed-step
-            // solve has no stops to snap to but the end of the interval); t0 + (i + 1) dt would floor differently at frame boundaries
-            t = (i + 1 == nsteps && std::fabs(tt(t + dt) - T1) <= 1e-5 * SDT) ? T1 : tt(t + dt);
+            HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)T.dt, R.n, h->stream));
+            t = T.next(i, nsteps, t);
             ++d->n_accept;
             // saveat: the state of the step that ends at the save point.  In its own time type the integrator's t drifts off the
             // save grid by a few ulps per step (Float32: ~1e-6 s after 600 steps of 0.01 s); the reference interpolates there, which
             // moves the saved state by (drift / dt) of one step's change -- far below the rollout tolerance -- so: the nearest step.
-            while (saved < d->n_saves && stop_time(saved) <= t + 0.25 * dt) HIPCHK(h, save());
+            while (R.saved < d->n_saves && T.stop_time(R.saved) <= t + 0.25 * T.dt)
+                if (int rc = R.save(i + 1)) return rc;
         }
+        while (R.saved < d->n_saves)      // (t1 short of the last stop: repeat the final state)
+            if (int rc = R.save(nsteps)) return rc;
     } else {
-        // adaptive Tsit5, PI controller, tstops = saves
-        Tsit5Control ctl;
-        if (int rc = R.tsit5_first(t)) return rc;     // k1 (FSAL afterwards)
-        double dt = DT;
-        if (dt <= 0)   // Hairer-Wanner starting step
-            if (int rc = R.tsit5_h0(t, &dt)) return rc;
-        const double tend = T1;
-        int guard = 0;
-        // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save
-        // periods is not worth a step
-        while (t < tend - 1e-5 * SDT && ++guard < 10000000) {
-            double tstop = saved < d->n_saves ? stop_time(saved) : tend;
-            if (tstop > tend) tstop = tend;
-            bool hit_stop = false;
-            double hstep = dt;
-            if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
-            // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
-            double EEst;
-            if (int rc = R.tsit5_trial(t, hstep, hit_stop ? tstop : tt(t + tt(TS_C[6] * hstep)), &EEst)) return rc;
-            if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "mgn_rollout: NaN in the error estimate at t = %g", t);
-            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
-                R.tsit5_advance();
-                t = hit_stop ? tstop : tt(t + hstep);
-                ++d->n_accept;
-                if (hit_stop && saved < d->n_saves && std::fabs(stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12) HIPCHK(h, save());
-            } else {
-                ++d->n_reject;
-            }
-        }
+        if (int rc = R.tsit5_adaptive("mgn_rollout", nullptr)) return rc;
     }
-    while (saved < d->n_saves) HIPCHK(h, save());      // (t1 short of the last stop: repeat the final state)
     if (part) {     // every rank returns the complete solution
         for (int i = 0; i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
-    } else if (loc) {   // one partition in the engine's own node order: back to the caller's
-        std::vector<float> sv((size_t)d->n_saves * R.n);
-        HIPCHK(h, hipMemcpyAsync(sv.data(), R.saves, sb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int i = 0; i < d->n_saves; ++i)
-            for (int32_t j = 0; j < g.n_own; ++j)
-                memcpy(d->out + ((size_t)i * g.N + (size_t)g.own_gid[j]) * c.O, sv.data() + ((size_t)i * g.n_own + j) * c.O, (size_t)c.O * 4);
-    } else {
-        HIPCHK(h, hipMemcpyAsync(d->out, R.saves, sb, hipMemcpyDeviceToHost, h->stream));
+    } else if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) {
+        return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     d->n_rhs = R.n_rhs;
@@ -2183,20 +2311,26 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
 // Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
 namespace {
 
-// the checks mgn_solver_grad and mgn_solver_grad_tsit5 share (everything but the solver)
-int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss) {
+// the handle's state that solver-based training needs: a device handle, one partition, fp32, one edge set, parameters and a graph
+int solver_state_checks(mgn_handle* h, const char* who) {
     if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
     const mgn_config& c = h->cfg;
     if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
     if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
     if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
-    if (int rc = need(h, true, true, c.ln_dims != MGN_LN_ALL, true)) return rc;
-    if (!d || !gt || !grads || !loss || !d->x0 || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    return need(h, true, true, c.ln_dims != MGN_LN_ALL, true);
+}
+
+// the static inputs of the right-hand side
+int solver_static_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who) {
+    const mgn_config& c = h->cfg;
+    if (!d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
     if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
     return MGN_OK;
 }
 
-int solver_checks2(mgn_handle* h, mgn_rollout_desc* d, const char* who, float cont_weight) {
+// the inflow and the continuity weight
+int solver_inflow_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who, float cont_weight) {
     if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "%s: unknown inflow_rule", who);
     if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "%s: inflow mask and data go together", who);
     if (d->inflow_data && d->n_frames < 1) return fail(h, MGN_E_ARG, "%s: inflow_data needs n_frames >= 1", who);
@@ -2204,68 +2338,22 @@ int solver_checks2(mgn_handle* h, mgn_rollout_desc* d, const char* who, float co
     return MGN_OK;
 }
 
-// the fixed-step time grid of mgn_rollout's Euler loop (t <- t + dt in the time type, the last step snapped onto t1), walked once on the
-// host: the step whose state each save is (every one must be reached)
-int fixed_grid(mgn_handle* h, mgn_rollout_desc* d, const char* who, const Rollout& R, double T0, double T1, double DT, double SDT, int64_t K,
-               std::vector<int64_t>& save_step) {
-    auto stop_time = [&](int i) { return R.tt(T0 + (double)i * SDT); };
+// the fixed-step grid (TimeGrid::next) walked once on the host: K = round((t1 - t0) / dt) steps, and the step whose state each of the
+// n_saves saves is (every one must be reached)
+int fixed_grid(mgn_handle* h, const char* who, const TimeGrid& T, int n_saves, int64_t* K, std::vector<int64_t>& save_step) {
+    const double steps = (T.t1 - T.t0) / T.dt;
+    if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: %.3g steps", who, steps);
+    *K = (int64_t)std::llround(steps);
     save_step.assign(1, 0);
-    double t = T0;
-    for (int64_t i = 0; i < K && (int)save_step.size() < d->n_saves; ++i) {
-        t = (i + 1 == K && std::fabs(R.tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : R.tt(t + DT);
-        while ((int)save_step.size() < d->n_saves && stop_time((int)save_step.size()) <= t + 0.25 * DT) save_step.push_back(i + 1);
+    double t = T.t0;
+    for (int64_t i = 0; i < *K && (int)save_step.size() < n_saves; ++i) {
+        t = T.next(i, *K, t);
+        while ((int)save_step.size() < n_saves && T.stop_time((int)save_step.size()) <= t + 0.25 * T.dt) save_step.push_back(i + 1);
     }
-    if ((int)save_step.size() < d->n_saves)
+    if ((int)save_step.size() < n_saves)
         return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
-                    (int)save_step.size(), stop_time((int)save_step.size()), T1);
+                    (int)save_step.size(), T.stop_time((int)save_step.size()), T.t1);
     return MGN_OK;
-}
-
-// the static inputs (x0 only fills the encoder's unused state slot: every right-hand side reads its state through srcA_override) and the
-// edges encoded once into elat0
-int solver_statics(mgn_handle* h, mgn_rollout_desc* d, const float* x0, char* elat0, size_t eb) {
-    const mgn_config& c = h->cfg;
-    const int32_t N = h->g.N;
-    const int O = c.O;
-    if (int rc = upload_inputs(h, x0, O, d->node_type_onehot, c.Fn - O, d->ef_raw, true)) return rc;
-    h->have_mask = d->val_mask != nullptr;
-    if (d->val_mask) {
-        HIPCHK(h, h->d_mask.ensure((size_t)N * 4));
-        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
-    if (int rc = encode_impl(h, true, false, true)) return rc;
-    HIPCHK(h, hipMemcpyAsync(elat0, h->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, h->stream));
-    return MGN_OK;
-}
-
-// entry: x0, frames and the inflow mask into the engine's order (as mgn_rollout), then the static inputs and the encoded edges
-int solver_upload(mgn_handle* h, mgn_rollout_desc* d, Rollout& R, char* base, size_t eb) {
-    const mgn_config& c = h->cfg;
-    const LocalGraph& g = h->g;
-    const int32_t N = g.N;
-    const int O = c.O;
-    const size_t nb = (size_t)R.n * 4, fb = d->inflow_data ? (size_t)d->n_frames * nb : 0;
-    if (!g.renumbered) {
-        HIPCHK(h, hipMemcpyAsync(R.u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
-        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
-        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, d->inflow_mask, (size_t)N, hipMemcpyHostToDevice, h->stream));
-    } else {
-        std::vector<float> lx((size_t)N * O * (1 + (d->inflow_data ? d->n_frames : 0)));
-        std::vector<uint8_t> lm(d->inflow_mask ? (size_t)N : 0);
-        for (int32_t i = 0; i < N; ++i) {
-            const size_t gi = (size_t)g.own_gid[i];
-            memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
-            for (int f = 0; d->inflow_data && f < d->n_frames; ++f)
-                memcpy(lx.data() + ((size_t)(1 + f) * N + i) * O, d->inflow_data + ((size_t)f * N + gi) * O, (size_t)O * 4);
-            if (d->inflow_mask) lm[i] = d->inflow_mask[gi];
-        }
-        HIPCHK(h, hipMemcpyAsync(R.u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
-        if (R.frames) HIPCHK(h, hipMemcpyAsync(R.frames, lx.data() + (size_t)N * O, fb, hipMemcpyHostToDevice, h->stream));
-        if (R.mask) HIPCHK(h, hipMemcpyAsync(R.mask, lm.data(), (size_t)N, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return solver_statics(h, d, d->x0, base + R.elat0_off, eb);
 }
 
 // gt and cont_target (host or device, the caller's order) into the engine's order (gtl, ctl); loss_scale as given (lsd); tmp: [N][O] scratch
@@ -2292,222 +2380,80 @@ int solver_targets(mgn_handle* h, mgn_rollout_desc* d, int64_t n, const float* g
     return MGN_OK;
 }
 
-// exit: the predicted saves in the caller's order, and the final synchronisation
-int solver_out(mgn_handle* h, mgn_rollout_desc* d, const Rollout& R) {
-    const LocalGraph& g = h->g;
-    const int O = h->cfg.O;
-    const size_t sb = (size_t)d->n_saves * R.n * 4;
-    if (d->out) {
-        if (g.renumbered) {
-            std::vector<float> sv((size_t)d->n_saves * R.n);
-            HIPCHK(h, hipMemcpyAsync(sv.data(), R.saves, sb, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            for (int i = 0; i < d->n_saves; ++i)
-                for (int32_t j = 0; j < g.N; ++j)
-                    memcpy(d->out + ((size_t)i * g.N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * g.N + j) * O, (size_t)O * 4);
-        } else {
-            HIPCHK(h, hipMemcpyAsync(d->out, R.saves, sb, hipMemcpyDeviceToHost, h->stream));
-        }
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MGN_OK;
-}
-
-}  // namespace
-
-int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
-                    float* grads, size_t n_grads, float* loss) try {
-    if (!h) return MGN_E_ARG;
-    if (int rc = solver_checks(h, d, "mgn_solver_grad", gt, grads, loss)) return rc;
-    const mgn_config& c = h->cfg;
-    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
-    if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
-    const bool f64 = d->time_f64 != 0;
-    const double T0 = f64 ? d->t0_f64 : (double)d->t0, T1 = f64 ? d->t1_f64 : (double)d->t1, DT = f64 ? d->dt_f64 : (double)d->dt,
-                 SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
-    if (d->n_saves < 1 || !(SDT > 0.0) || !(T1 >= T0)) return fail(h, MGN_E_ARG, "mgn_solver_grad: bad time grid");
-    if (!(DT > 0.0)) return fail(h, MGN_E_ARG, "mgn_solver_grad: Euler needs dt > 0");
-    if (int rc = solver_checks2(h, d, "mgn_solver_grad", cont_weight)) return rc;
-    const double steps = (T1 - T0) / DT;
-    if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "mgn_solver_grad: %.3g Euler steps", steps);
-    const int64_t K = (int64_t)std::llround(steps);
-
-    Rollout R;
-    R.h = h;
-    R.d = d;
-    R.f64 = f64;
-    R.sdt = SDT;
-    auto tt = [&](double v) { return R.tt(v); };
-    auto stop_time = [&](int i) { return tt(T0 + (double)i * SDT); };
-    auto next_t = [&](int64_t i, double t) { return (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT); };
-    std::vector<int64_t> save_step;
-    if (int rc = fixed_grid(h, d, "mgn_solver_grad", R, T0, T1, DT, SDT, K, save_step)) return rc;
-    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
-    const LocalGraph& g = h->g;
-    invalidate_static(h);
-    const int32_t N = g.N;
-    const int O = c.O;
-    R.n = (int64_t)N * O;
-    R.n_global = R.n;
-    R.nrows = N;
-    const size_t nb = (size_t)R.n * 4;
-    const size_t P = h->params.size();
-    const int ablk = solver_adjoint_blocks(N, O);
-    if ((size_t)(K + 1) > (SIZE_MAX / 2) / (nb > 0 ? nb : 1))
-        return fail(h, MGN_E_OOM, "mgn_solver_grad: %lld stored states of %zu bytes overflow the address space", (long long)(K + 1), nb);
-    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
-    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t o_u = take(nb), o_ut = take(nb), o_k = take(nb), o_fr = take(fb), o_sv = take(sb), o_mask = take((size_t)N);
-    R.elat0_off = take(eb);
-    const size_t o_gt = take(sb), o_ct = take(cont_target ? nb : 0), o_ls = take((size_t)O * 4), o_a = take(nb), o_tmp = take(nb),
-                 o_gacc = take(P * sizeof(double)), o_part = take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
-    const size_t o_st = take((size_t)(K + 1) * nb);
-    if (hipError_t e = h->ode.ensure(off)) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "mgn_solver_grad: %.3f GB for the %lld stored states of the solve and the call's buffers: %s",
-                    (double)off * 1e-9, (long long)(K + 1), hipGetErrorString(e));
-    }
-    char* base = h->ode.as<char>();
-    R.u = (float*)(base + o_u); R.utmp = (float*)(base + o_ut); R.unew = nullptr;
-    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k);      // (Euler takes k[0] only)
-    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
-    R.saves = (float*)(base + o_sv);
-    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
-    R.partial = nullptr;
-    float* states = (float*)(base + o_st);
-    if (int rc = solver_upload(h, d, R, base, eb)) return rc;
-
-    // forward: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k kept for the sweep
-    d->n_accept = d->n_reject = 0;
-    int saved = 0;
-    auto save = [&]() { return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream); };
-    HIPCHK(h, save());
-    double t = T0;
-    for (int64_t i = 0; i < K; ++i) {
-        float* xin = R.u;
-        if (R.mask) {      // ode_func_train: the inflow rows go into a copy, the state itself is not overwritten
-            HIPCHK(h, hipMemcpyAsync(R.utmp, R.u, nb, hipMemcpyDeviceToDevice, h->stream));
-            xin = R.utmp;
-        }
-        if (int rc = R.rhs(xin, t, R.k[0])) return rc;
-        HIPCHK(h, hipMemcpyAsync(states + (size_t)i * R.n, xin, nb, hipMemcpyDeviceToDevice, h->stream));
-        LinComb lc{1, {1.f}, {R.k[0]}};
-        HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)DT, R.n, h->stream));
-        t = next_t(i, t);
-        ++d->n_accept;
-        while (saved < d->n_saves && stop_time(saved) <= t + 0.25 * DT) HIPCHK(h, save());
-    }
-    HIPCHK(h, hipMemcpyAsync(states + (size_t)K * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream));
-    d->n_rhs = R.n_rhs;
-
-    float* gtl = (float*)(base + o_gt);
-    float* ctl = cont_target ? (float*)(base + o_ct) : nullptr;
-    float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
-    if (int rc = solver_targets(h, d, R.n, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
-
-    SolverSweep S{};
-    S.K = K; S.states = states; S.saves = R.saves; S.save_step = save_step.data(); S.n_saves = d->n_saves;
-    S.gt = gtl; S.loss_scale = lsd; S.inflow = R.mask; S.cont_target = ctl; S.cont_weight = ctl ? cont_weight : 0.f; S.dt = (float)DT;
-    S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
-    S.a = (float*)(base + o_a); S.gacc = (double*)(base + o_gacc); S.part = (double*)(base + o_part);
-    S.grads = grads; S.loss = loss;
-    if (int rc = solver_sweep(h, S)) return rc;
-    return solver_out(h, d, R);
-} MGN_CATCH(h)
-
-// Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_*, Tsit5Control) or fixed steps on the Euler grid, in the training form (za / zs /
-// z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
-int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
-                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
-    static const char* who = "mgn_solver_grad_tsit5";
-    if (!h) return MGN_E_ARG;
-    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
-    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
-    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
-    const mgn_config& c = h->cfg;
-    const bool adaptive = o->adaptive != 0;
-    const bool f64 = d->time_f64 != 0;
-    const double T0 = f64 ? d->t0_f64 : (double)d->t0, T1 = f64 ? d->t1_f64 : (double)d->t1, DT = f64 ? d->dt_f64 : (double)d->dt,
-                 SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
-    if (d->n_saves < 1 || !(SDT > 0.0) || !(T1 >= T0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (!adaptive && !(DT > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
-    if (adaptive && !(DT >= 0.0)) return fail(h, MGN_E_ARG, "%s: dt must be >= 0 (0: the Hairer-Wanner start)", who);
+// mgn_solver_grad (o null: fixed-step Euler) and mgn_solver_grad_tsit5 (o: fixed steps, or adaptive), after their own checks: the time grid,
+// the forward loop keeping what the sweep needs (Euler: every step's RHS input; Tsit5: every accepted step's six stage inputs, in chunks on
+// the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves
+int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
+                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) {
+    const bool euler = !o, adaptive = o && o->adaptive != 0;
+    const TimeGrid T(d);
+    if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (!adaptive && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, euler ? "%s: Euler needs dt > 0" : "%s: fixed steps need dt > 0", who);
+    if (adaptive && !(T.dt >= 0.0)) return fail(h, MGN_E_ARG, "%s: dt must be >= 0 (0: the Hairer-Wanner start)", who);
     if (adaptive && !(d->abstol > 0.f && d->reltol > 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
-    if (int rc = solver_checks2(h, d, who, cont_weight)) return rc;
-    o->n_steps = 0;
-    o->stored_bytes = 0;
-
-    Rollout R;
-    R.h = h;
-    R.d = d;
-    R.f64 = f64;
-    R.sdt = SDT;
-    R.train = true;
-    auto tt = [&](double v) { return R.tt(v); };
-    auto stop_time = [&](int i) { return tt(T0 + (double)i * SDT); };
-    int64_t K = 0;                       // fixed steps: the step count; adaptive: grows
-    std::vector<int64_t> save_step;
-    if (!adaptive) {
-        const double steps = (T1 - T0) / DT;
-        if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: %.3g steps", who, steps);
-        K = (int64_t)std::llround(steps);
-        if (int rc = fixed_grid(h, d, who, R, T0, T1, DT, SDT, K, save_step)) return rc;
-    } else if (stop_time(d->n_saves - 1) > T1 + 1e-5 * SDT) {
-        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
-                    d->n_saves - 1, stop_time(d->n_saves - 1), T1);
+    if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
+    if (o) {
+        o->n_steps = 0;
+        o->stored_bytes = 0;
     }
-    if (int rc = solver_prepare(h, n_grads)) return rc;
-    const LocalGraph& g = h->g;
-    invalidate_static(h);
-    const int32_t N = g.N;
+    int64_t K = 0;                       // fixed steps: the step count; adaptive: the accepted steps, after the solve
+    std::vector<int64_t> plan;
+    if (!adaptive) {
+        if (int rc = fixed_grid(h, who, T, d->n_saves, &K, plan)) return rc;
+    } else if (T.stop_time(d->n_saves - 1) > T.t1 + 1e-5 * T.sdt) {
+        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
+                    d->n_saves - 1, T.stop_time(d->n_saves - 1), T.t1);
+    }
+    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
+    const mgn_config& c = h->cfg;
+    const int32_t N = h->g.N;
     const int O = c.O;
+    invalidate_static(h);
+    Rollout R(h, d, T);
+    R.train = true;
     R.n = (int64_t)N * O;
     R.n_global = R.n;
     R.nrows = N;
     const size_t nb = (size_t)R.n * 4;
     const size_t P = h->params.size();
     const int ablk = solver_adjoint_blocks(N, O);
+    if (euler && (size_t)(K + 1) > (SIZE_MAX / 2) / (nb > 0 ? nb : 1))
+        return fail(h, MGN_E_OOM, "%s: %lld stored states of %zu bytes overflow the address space", who, (long long)(K + 1), nb);
     const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
     const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
-    const size_t o_u = take(nb), o_un = take(nb), o_ut = take(nb);
+    const bool zc = !euler && d->inflow_mask != nullptr;       // Tsit5's training-form copies
+    Arena a;
+    const size_t o_u = a.take(nb), o_un = a.take(euler ? 0 : nb), o_ut = a.take(nb);
     size_t o_k[7];
-    for (auto& x : o_k) x = take(nb);
-    const bool zc = d->inflow_mask != nullptr;       // training-form copies
-    const size_t o_za = take(zc ? nb : 0), o_zs = take(zc ? nb : 0), o_z7 = take(zc ? nb : 0);
-    const size_t o_fr = take(fb), o_sv = take(sb), o_mask = take((size_t)N), o_pe = take(errnorm_partials() * sizeof(double));
-    R.elat0_off = take(eb);
-    const size_t o_gt = take(sb), o_ct = take(cont_target ? nb : 0), o_ls = take((size_t)O * 4), o_a = take(nb), o_tmp = take(nb),
-                 o_yb = take(5 * nb), o_gacc = take(P * sizeof(double)), o_part = take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
-    if (hipError_t e = h->ode.ensure(off)) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %.3f GB for the call's buffers: %s", who, (double)off * 1e-9,
-                    hipGetErrorString(e));
-    }
+    for (int j = 0; j < 7; ++j) o_k[j] = a.take(euler && j > 0 ? 0 : nb);     // (Euler takes k[0] only)
+    const size_t o_za = a.take(zc ? nb : 0), o_zs = a.take(zc ? nb : 0), o_z7 = a.take(zc ? nb : 0);
+    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)N), o_pe = a.take(euler ? 0 : errnorm_partials() * sizeof(double));
+    R.elat0_off = a.take(eb);
+    const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb), o_tmp = a.take(nb),
+                 o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
+    const size_t o_st = a.take(euler ? (size_t)(K + 1) * nb : 0);
+    if (int rc = euler ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the %lld stored states of the solve and the call's buffers", who,
+                                        (double)a.off * 1e-9, (long long)(K + 1))
+                       : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
+        return rc;
     char* base = h->ode.as<char>();
-    R.u = (float*)(base + o_u); R.unew = (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
-    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[j]);
+    R.u = (float*)(base + o_u); R.unew = euler ? nullptr : (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
+    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[euler ? 0 : j]);
     if (zc) { R.za = (float*)(base + o_za); R.zs = (float*)(base + o_zs); R.z7 = (float*)(base + o_z7); }
     R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
     R.saves = (float*)(base + o_sv);
     R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
-    R.partial = (double*)(base + o_pe);
-    if (int rc = solver_upload(h, d, R, base, eb)) return rc;
+    R.partial = euler ? nullptr : (double*)(base + o_pe);
+    if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
+    if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
 
-    // the stored stage inputs: step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown geometrically
-    // (never reallocated: a stored step does not move)
+    // Tsit5: the stored stage inputs, step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown
+    // geometrically (never reallocated: a stored step does not move)
     const size_t stepb = 6 * nb;
     const int64_t max_steps = 100000;
     std::vector<float*> steps;
-    std::vector<double> step_t, step_h;
     size_t chunk = 0, used_in_chunk = 0;
-    auto slot = [&](int64_t n) -> int {          // steps[n] exists afterwards
+    const Rollout::Slot slot = [&](int64_t n, float** out) -> int {
         while ((int64_t)steps.size() <= n) {
             if ((int64_t)steps.size() >= max_steps)
                 return fail(h, MGN_E_STATE, "%s: more than %lld accepted steps (maxiters)", who, (long long)max_steps);
@@ -2530,87 +2476,27 @@ int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_op
                 h->tsit5_store.push_back(std::make_unique<DevBuf>());
                 cb = h->tsit5_store.back().get();
             }
-            if (hipError_t e = cb->ensure(want * stepb)) {
-                (void)hipGetLastError();
-                return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: step %lld: %.3f GB more for the stored stage inputs (%.3f GB stored): %s",
-                            who, (long long)steps.size(), (double)(want * stepb) * 1e-9, (double)(steps.size() * stepb) * 1e-9, hipGetErrorString(e));
-            }
+            if (int rc = ensure_or_fail(h, *cb, want * stepb, "%s: step %lld: %.3f GB more for the stored stage inputs (%.3f GB stored)", who,
+                                        (long long)steps.size(), (double)(want * stepb) * 1e-9, (double)(steps.size() * stepb) * 1e-9))
+                return rc;
             used_in_chunk = 0;
         }
-        return MGN_OK;
-    };
-    int64_t nacc = 0;
-    R.keep = [&](int sidx, const float* x) -> int {
-        HIPCHK(h, hipMemcpyAsync(steps[nacc] + (size_t)sidx * R.n, x, nb, hipMemcpyDeviceToDevice, h->stream));
-        return MGN_OK;
-    };
-    // before every trial: step nacc's slot, and its z_{n,1} (za, or u itself without an inflow mask) into it
-    auto begin_trial = [&]() -> int {
-        if (int rc = slot(nacc)) return rc;
-        HIPCHK(h, hipMemcpyAsync(steps[nacc], zc ? R.za : R.u, nb, hipMemcpyDeviceToDevice, h->stream));
+        *out = steps[n];
         return MGN_OK;
     };
 
     d->n_accept = d->n_reject = 0;
-    int saved = 0;
-    auto save = [&]() -> hipError_t {
-        save_step.resize(std::max<size_t>(save_step.size(), (size_t)saved + 1));
-        save_step[saved] = nacc;
-        return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, h->stream);
-    };
-    double t = T0;
-    HIPCHK(h, save());
-    if (int rc = R.tsit5_first(t)) return rc;
-    if (!adaptive) {
-        for (int64_t i = 0; i < K; ++i) {
-            const double tn = (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT);
-            if (int rc = begin_trial()) return rc;
-            if (int rc = R.tsit5_trial(t, DT, tn, nullptr)) return rc;
-            R.tsit5_advance();
-            step_t.push_back(t); step_h.push_back(DT);
-            t = tn;
-            ++nacc;
-            ++d->n_accept;
-            while (saved < d->n_saves && stop_time(saved) <= t + 0.25 * DT) HIPCHK(h, save());
-        }
-    } else {
-        Tsit5Control ctl;
-        double dt = DT;
-        if (dt <= 0)
-            if (int rc = R.tsit5_h0(t, &dt)) return rc;
-        int64_t guard = 0;
-        while (t < T1 - 1e-5 * SDT) {
-            if (++guard >= 10000000) return fail(h, MGN_E_STATE, "%s: %lld trial steps without reaching t1", who, (long long)guard);
-            double tstop = saved < d->n_saves ? stop_time(saved) : T1;
-            if (tstop > T1) tstop = T1;
-            bool hit_stop = false;
-            double hstep = dt;
-            if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
-            const double tn = hit_stop ? tstop : tt(t + hstep);      // stage 7 is z_{n+1,1}: it sees t_{n+1}
-            if (int rc = begin_trial()) return rc;
-            double EEst;
-            if (int rc = R.tsit5_trial(t, hstep, tn, &EEst)) return rc;
-            if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
-            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
-                R.tsit5_advance();
-                step_t.push_back(t); step_h.push_back(hstep);
-                t = tn;
-                ++nacc;
-                ++d->n_accept;
-                if (hit_stop && saved < d->n_saves && std::fabs(stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12) HIPCHK(h, save());
-            } else {
-                ++d->n_reject;
-            }
-        }
-        while (saved < d->n_saves) HIPCHK(h, save());      // (t1 an ulp short of the last stop: the final state)
-    }
+    float* states = (float*)(base + o_st);
+    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : R.tsit5_fixed(K, plan, slot)) return rc;
     d->n_rhs = R.n_rhs;
-    K = nacc;
-    o->n_steps = (int32_t)K;
-    o->stored_bytes = (size_t)K * stepb;
-    for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
-        if (o->step_t) o->step_t[i] = step_t[i];
-        if (o->step_h) o->step_h[i] = step_h[i];
+    if (!euler) {
+        K = (int64_t)R.step_h.size();
+        o->n_steps = (int32_t)K;
+        o->stored_bytes = (size_t)K * stepb;
+        for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
+            if (o->step_t) o->step_t[i] = R.step_t[i];
+            if (o->step_h) o->step_h[i] = R.step_h[i];
+        }
     }
 
     float* gtl = (float*)(base + o_gt);
@@ -2619,14 +2505,53 @@ int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_op
     if (int rc = solver_targets(h, d, R.n, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
 
     SolverSweep S{};
-    S.K = K; S.states = nullptr; S.saves = R.saves; S.save_step = save_step.data(); S.n_saves = d->n_saves;
-    S.gt = gtl; S.loss_scale = lsd; S.inflow = R.mask; S.cont_target = ctl; S.cont_weight = ctl ? cont_weight : 0.f; S.dt = 0.f;
+    S.K = K; S.states = euler ? states : nullptr; S.saves = R.saves; S.save_step = R.save_step.data(); S.n_saves = d->n_saves;
+    S.gt = gtl; S.loss_scale = lsd; S.inflow = R.mask; S.cont_target = ctl; S.cont_weight = ctl ? cont_weight : 0.f; S.dt = euler ? (float)T.dt : 0.f;
     S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
     S.a = (float*)(base + o_a); S.gacc = (double*)(base + o_gacc); S.part = (double*)(base + o_part);
     S.grads = grads; S.loss = loss;
-    Tsit5Sweep T5{steps.data(), step_h.data(), R.u, (float*)(base + o_yb)};
-    if (int rc = tsit5_sweep(h, S, T5)) return rc;
-    return solver_out(h, d, R);
+    if (euler) {
+        if (int rc = solver_sweep(h, S)) return rc;
+    } else {
+        Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, (float*)(base + o_yb)};
+        if (int rc = tsit5_sweep(h, S, T5)) return rc;
+    }
+    if (d->out)      // the predicted saves in the caller's order
+        if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+}
+
+// the checks mgn_solver_grad and mgn_solver_grad_tsit5 share before their solver's
+int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss) {
+    if (int rc = solver_state_checks(h, who)) return rc;
+    if (!d || !gt || !grads || !loss || !d->x0) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    return solver_static_checks(h, d, who);
+}
+
+}  // namespace
+
+int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
+                    float* grads, size_t n_grads, float* loss) try {
+    static const char* who = "mgn_solver_grad";
+    if (!h) return MGN_E_ARG;
+    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
+    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
+    if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
+    return solver_grad(h, d, nullptr, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+} MGN_CATCH(h)
+
+// Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_adaptive, Tsit5Control) or fixed steps on the Euler grid (Rollout::tsit5_fixed), in
+// the training form (za / zs / z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
+int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
+                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
+    static const char* who = "mgn_solver_grad_tsit5";
+    if (!h) return MGN_E_ARG;
+    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
+    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
+    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
+    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
 } MGN_CATCH(h)
 
 // ---- MultipleShooting as one batch (mgn_shooting_grad) ----------------------------------------------------------------------------------
@@ -2649,6 +2574,7 @@ struct ShootGroup {
     std::vector<int32_t> win;                // its windows, ascending
     std::vector<std::vector<int32_t>> fr;    // per window: the inflow frame of every right-hand side evaluation (no inflow mask: empty)
     size_t ftab_off = 0;                     // [n_evals][win.size()] in the int table
+    TimeGrid tg;                             // its first window's
 };
 
 // the companion for passes of B windows: B copies of h's graph in h's engine order (row w N + i = window w's engine row i), not renumbered;
@@ -2761,59 +2687,48 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         if (s->first[w] < 0 || s->last[w] <= s->first[w] || s->last[w] >= s->n_gt)
             return fail(h, MGN_E_ARG, "%s: window %d = (%d, %d) must satisfy 0 <= first < last < n_gt = %d", who, w, s->first[w], s->last[w], s->n_gt);
     s->n_groups = s->n_passes = 0;
-    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
+    if (int rc = solver_state_checks(h, who)) return rc;
+    if (int rc = solver_static_checks(h, d, who)) return rc;
     const mgn_config& c = h->cfg;
-    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
-    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
-    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
-    if (int rc = need(h, true, true, c.ln_dims != MGN_LN_ALL, true)) return rc;
-    if (!d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
-    const bool f64 = d->time_f64 != 0;
-    const double DT = f64 ? d->dt_f64 : (double)d->dt, SDT = f64 ? d->saves_dt_f64 : (double)d->saves_dt;
-    if (!(SDT > 0.0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (!(DT > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
-    if (int rc = solver_checks2(h, d, who, cont_weight)) return rc;
+    const TimeGrid DG(d);                    // (its time type, dt and saves_dt; every window has its own t0 and t1)
+    if (!(DG.sdt > 0.0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (!(DG.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
+    if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
     const bool euler = d->solver == 0, inflow = d->inflow_mask != nullptr;
 
     // ---- plans on the host: every window walks the single-window grid; identical plans form a group
-    Rollout P;                               // (its time type and frame rule only)
-    P.h = h;
-    P.d = d;
-    P.f64 = f64;
-    P.sdt = SDT;
-    auto tt = [&](double v) { return P.tt(v); };
     std::vector<ShootGroup> groups;
     std::vector<int32_t> grp_of(W);
     mgn_rollout_desc dw = *d;
     for (int32_t w = 0; w < W; ++w) {
-        const double T0 = tt(s->t0[w]), T1 = tt(s->t1[w]);
-        if (!(T1 >= T0)) return fail(h, MGN_E_ARG, "%s: window %d: t1 < t0", who, w);
-        dw.n_saves = s->last[w] - s->first[w] + 1;
-        const double steps = (T1 - T0) / DT;
-        if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: window %d: %.3g steps", who, w, steps);
-        const int64_t K = (int64_t)std::llround(steps);
+        TimeGrid T = DG;
+        T.t0 = T.tt(s->t0[w]);
+        T.t1 = T.tt(s->t1[w]);
+        if (!(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: window %d: t1 < t0", who, w);
+        char ww[64];
+        snprintf(ww, sizeof ww, "%s: window %d", who, w);
+        int64_t K;
         std::vector<int64_t> ss;
-        if (int rc = fixed_grid(h, &dw, who, P, T0, T1, DT, SDT, K, ss)) return rc;
+        if (int rc = fixed_grid(h, ww, T, s->last[w] - s->first[w] + 1, &K, ss)) return rc;
         std::vector<int32_t> fr;
         if (inflow) {      // the frame of every right-hand side evaluation, in the order the solve makes them
-            auto next_t = [&](int64_t i, double t) { return (i + 1 == K && std::fabs(tt(t + DT) - T1) <= 1e-5 * SDT) ? T1 : tt(t + DT); };
+            const Rollout P(h, d, T);        // (its frame rule only)
             auto push = [&](double t) -> int {
                 int64_t f;
                 if (int rc = P.frame_index(t, &f)) return rc;
                 fr.push_back((int32_t)f);
                 return MGN_OK;
             };
-            double t = T0;
+            double t = T.t0;
             if (!euler)
                 if (int rc = push(t)) return rc;                 // k1
             for (int64_t i = 0; i < K; ++i) {
-                const double tn = next_t(i, t);
+                const double tn = T.next(i, K, t);
                 if (euler) {
                     if (int rc = push(t)) return rc;
                 } else {
                     for (int sidx = 1; sidx < 6; ++sidx)
-                        if (int rc = push(tt(t + tt(TS_C[sidx] * DT)))) return rc;
+                        if (int rc = push(T.tt(t + T.tt(TS_C[sidx] * T.dt)))) return rc;
                     if (int rc = push(tn)) return rc;            // stage 7 = z_{n+1,1} sees t_{n+1}
                 }
                 t = tn;
@@ -2824,9 +2739,7 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
             if (groups[q].K == K && groups[q].save_step == ss) gi = (int32_t)q;
         if (gi < 0) {
             gi = (int32_t)groups.size();
-            groups.emplace_back();
-            groups.back().K = K;
-            groups.back().save_step = ss;
+            groups.push_back({K, ss, {}, {}, 0, T});
         }
         groups[gi].win.push_back(w);
         groups[gi].fr.push_back(std::move(fr));
@@ -2886,18 +2799,13 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
     const bool any_batch = Bmax > 1;
     const size_t gtb = (size_t)s->n_gt * nN * 4;
     const size_t fb = inflow ? (size_t)d->n_frames * nN * 4 : 0;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
-    const size_t o_gt = take(gtb), o_gtc = take(g.renumbered ? gtb : 0), o_fr = take(fb), o_mk = take(inflow ? (size_t)N : 0),
-                 o_oh = take(any_batch ? (size_t)N * W1 * 4 : 0), o_vm = take(any_batch && d->val_mask ? (size_t)N * 4 : 0),
-                 o_ef = take(any_batch ? (size_t)E * Fe * 4 : 0), o_out = take(d->out ? (size_t)out_row[W] * nN * 4 : 0),
-                 o_gacc = take(P_ * 8), o_lacc = take((size_t)2 * ld * 8), o_gf = take(P_ * 4), o_ls = take((size_t)O * 4),
-                 o_it = take(itab.size() * 4), o_cw = take(cwtab.size() * 4);
-    if (hipError_t e = h->shoot.ensure(off)) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %.3f GB for the call's staging: %s", who, (double)off * 1e-9, hipGetErrorString(e));
-    }
+    Arena a;
+    const size_t o_gt = a.take(gtb), o_gtc = a.take(g.renumbered ? gtb : 0), o_fr = a.take(fb), o_mk = a.take(inflow ? (size_t)N : 0),
+                 o_oh = a.take(any_batch ? (size_t)N * W1 * 4 : 0), o_vm = a.take(any_batch && d->val_mask ? (size_t)N * 4 : 0),
+                 o_ef = a.take(any_batch ? (size_t)E * Fe * 4 : 0), o_out = a.take(d->out ? (size_t)out_row[W] * nN * 4 : 0),
+                 o_gacc = a.take(P_ * 8), o_lacc = a.take((size_t)2 * ld * 8), o_gf = a.take(P_ * 4), o_ls = a.take((size_t)O * 4),
+                 o_it = a.take(itab.size() * 4), o_cw = a.take(cwtab.size() * 4);
+    if (int rc = ensure_or_fail(h, h->shoot, a.off, "%s: %.3f GB for the call's staging", who, (double)a.off * 1e-9)) return rc;
     hipStream_t st = h->stream;
     char* sbase = h->shoot.as<char>();
     float* gtl = (float*)(sbase + o_gt);
@@ -2915,19 +2823,9 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         HIPCHK(h, hipMemcpyAsync(sbase + o_gtc, gt, gtb, hipMemcpyDefault, st));
         HIPCHK(h, launch_shoot_gather(gtl, (const float*)(sbase + o_gtc), (int64_t)s->n_gt * nN, nN, s->n_gt, nullptr, ngid, O, st));
     }
-    // host arrays (as mgn_rollout takes them) into the engine's order on the host: frames, inflow mask, and the statics of companion passes
-    auto gi = [&](int32_t i) { return (size_t)(g.renumbered ? g.own_gid[i] : i); };
-    std::vector<float> hf;
-    std::vector<uint8_t> hm;
-    if (inflow) {
-        hf.resize((size_t)d->n_frames * nN);
-        hm.resize((size_t)N);
-        for (int f = 0; f < d->n_frames; ++f)
-            for (int32_t i = 0; i < N; ++i) memcpy(hf.data() + ((size_t)f * N + i) * O, d->inflow_data + ((size_t)f * N + gi(i)) * O, (size_t)O * 4);
-        for (int32_t i = 0; i < N; ++i) hm[i] = d->inflow_mask[gi(i)];
-        HIPCHK(h, hipMemcpyAsync(frl, hf.data(), fb, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(mkl, hm.data(), (size_t)N, hipMemcpyHostToDevice, st));
-    }
+    // host arrays (as mgn_rollout takes them) into the engine's order: frames, inflow mask, and the statics of companion passes (the node
+    // order of one partition: own_gid)
+    if (int rc = upload_engine_order(h, d, nullptr, frl, mkl)) return rc;
     std::vector<float> hs;
     if (any_batch) {
         hs.resize((size_t)N * W1 + (d->val_mask ? (size_t)N : 0) + (size_t)E * Fe);
@@ -2935,8 +2833,9 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         float* hv = ho + (size_t)N * W1;
         float* he = hv + (d->val_mask ? (size_t)N : 0);
         for (int32_t i = 0; i < N; ++i) {
-            if (W1 > 0) memcpy(ho + (size_t)i * W1, d->node_type_onehot + gi(i) * W1, (size_t)W1 * 4);
-            if (d->val_mask) hv[i] = d->val_mask[gi(i)];
+            const size_t gi = (size_t)g.own_gid[i];
+            if (W1 > 0) memcpy(ho + (size_t)i * W1, d->node_type_onehot + gi * W1, (size_t)W1 * 4);
+            if (d->val_mask) hv[i] = d->val_mask[gi];
         }
         for (int64_t j = 0; j < E; ++j) memcpy(he + (size_t)j * Fe, d->ef_raw + (size_t)g.set[0].edge_gid[j] * Fe, (size_t)Fe * 4);
         if (W1 > 0) HIPCHK(h, hipMemcpyAsync(sbase + o_oh, ho, (size_t)N * W1 * 4, hipMemcpyHostToDevice, st));
@@ -2965,35 +2864,27 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         }
         auto efail = [&](int rc) { return e == h ? rc : fail(h, rc, "%s: companion: %s", who, e->err.c_str()); };
         invalidate_static(e);
-        keep_alive.push_back(std::make_unique<Rollout>());
-        Rollout& R = *keep_alive.back();
         dw.n_saves = ns;
-        R.h = e;
-        R.d = &dw;
-        R.f64 = f64;
-        R.sdt = SDT;
-        R.train = !euler;
+        keep_alive.push_back(std::make_unique<Rollout>(e, &dw, G.tg));
+        Rollout& R = *keep_alive.back();
+        R.train = true;
         R.n = (int64_t)B * nN;
         R.n_global = R.n;
         R.nrows = B * N;
         const size_t nb = (size_t)R.n * 4;
         const size_t eb = tile_floats(e->es[0].ntiles_e, c.L) * 4;
         const bool zc = !euler && inflow;
-        size_t eo = 0;
-        auto etake = [&](size_t bytes) { const size_t o_ = eo; eo += al(bytes); return o_; };
-        const size_t o_u = etake(nb), o_un = etake(euler ? 0 : nb), o_ut = etake(nb);
+        Arena ea;
+        const size_t o_u = ea.take(nb), o_un = ea.take(euler ? 0 : nb), o_ut = ea.take(nb);
         size_t o_k[7];
-        for (int j = 0; j < 7; ++j) o_k[j] = etake(euler && j > 0 ? 0 : nb);
-        const size_t o_za = etake(zc ? nb : 0), o_zs = etake(zc ? nb : 0), o_z7 = etake(zc ? nb : 0);
-        const size_t o_sv = etake((size_t)ns * nb), o_el = etake(eb), o_tg = etake((size_t)ns * nb), o_ct = etake(nb), o_a = etake(nb),
-                     o_yb = etake(euler ? 0 : 5 * nb), o_mr = etake(inflow && B > 1 ? (size_t)B * N : 0);
+        for (int j = 0; j < 7; ++j) o_k[j] = ea.take(euler && j > 0 ? 0 : nb);
+        const size_t o_za = ea.take(zc ? nb : 0), o_zs = ea.take(zc ? nb : 0), o_z7 = ea.take(zc ? nb : 0);
+        const size_t o_sv = ea.take((size_t)ns * nb), o_el = ea.take(eb), o_tg = ea.take((size_t)ns * nb), o_ct = ea.take(nb), o_a = ea.take(nb),
+                     o_yb = ea.take(euler ? 0 : 5 * nb), o_mr = ea.take(inflow && B > 1 ? (size_t)B * N : 0);
         if ((size_t)(K + 1) > (SIZE_MAX / 8) / (nb > 0 ? nb : 1)) return fail(h, MGN_E_OOM, "%s: %lld stored steps overflow the address space", who, (long long)K);
-        const size_t o_st = etake((size_t)(euler ? K + 1 : 6 * K) * nb);
-        if (hipError_t er = e->ode.ensure(eo)) {
-            (void)hipGetLastError();
-            return fail(h, er == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %.3f GB for a pass of %d windows (stored states and buffers): %s",
-                        who, (double)eo * 1e-9, B, hipGetErrorString(er));
-        }
+        const size_t o_st = ea.take((size_t)(euler ? K + 1 : 6 * K) * nb);
+        if (int rc = ensure_or_fail(h, e->ode, ea.off, "%s: %.3f GB for a pass of %d windows (stored states and buffers)", who, (double)ea.off * 1e-9, B))
+            return rc;
         char* base = e->ode.as<char>();
         R.u = (float*)(base + o_u); R.unew = euler ? nullptr : (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
         for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + (euler ? o_k[0] : o_k[j]));
@@ -3009,7 +2900,7 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         uint8_t* mrep = inflow ? (B > 1 ? (uint8_t*)(base + o_mr) : mkl) : nullptr;
         float* store = (float*)(base + o_st);
         if (e == h) {
-            if (int rc = solver_statics(h, d, zero_x0.data(), base + o_el, eb)) return rc;
+            if (int rc = upload_statics(h, d, zero_x0.data(), base + o_el, eb)) return rc;
         } else {
             if (int rc = shoot_statics(e, B, N, (const float*)(sbase + o_oh), d->val_mask ? (const float*)(sbase + o_vm) : nullptr,
                                        (const float*)(sbase + o_ef), base + o_el, eb)) return efail(rc);
@@ -3018,50 +2909,12 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         const int32_t* ix = itd + ps.idx_off;
         HIPCHK(h, launch_shoot_gather(R.u, gtl, R.n, nN, 0, ix, nullptr, 0, st));     // x0 = gt[first[w]]
 
-        // forward: the single-window loops, save points from the group's plan
-        int saved = 0;
-        auto save = [&]() { return hipMemcpyAsync(R.saves + (size_t)saved++ * R.n, R.u, nb, hipMemcpyDeviceToDevice, st); };
-        auto saves_after = [&](int64_t steps_done) -> hipError_t {
-            while (saved < ns && G.save_step[saved] == steps_done)
-                if (hipError_t er = save()) return er;
-            return hipSuccess;
-        };
-        HIPCHK(h, saves_after(0));
+        // forward: the single-window loops, save points from the group's plan; Tsit5 keeps step i's stage inputs contiguously at steps[i]
         std::vector<float*> steps;
-        std::vector<double> step_h;
-        if (euler) {
-            for (int64_t i = 0; i < K; ++i) {
-                float* xin = R.u;
-                if (R.mask) {
-                    HIPCHK(h, hipMemcpyAsync(R.utmp, R.u, nb, hipMemcpyDeviceToDevice, st));
-                    xin = R.utmp;
-                }
-                if (int rc = R.rhs(xin, 0.0, R.k[0])) return efail(rc);
-                HIPCHK(h, hipMemcpyAsync(store + (size_t)i * R.n, xin, nb, hipMemcpyDeviceToDevice, st));
-                LinComb lc{1, {1.f}, {R.k[0]}};
-                HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)DT, R.n, st));
-                HIPCHK(h, saves_after(i + 1));
-            }
-            HIPCHK(h, hipMemcpyAsync(store + (size_t)K * R.n, R.u, nb, hipMemcpyDeviceToDevice, st));
-        } else {
-            int64_t nacc = 0;
-            for (int64_t i = 0; i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
-            step_h.assign((size_t)K, DT);
-            R.keep = [&](int sidx, const float* x) -> int {
-                HIPCHK(h, hipMemcpyAsync(steps[nacc] + (size_t)sidx * R.n, x, nb, hipMemcpyDeviceToDevice, st));
-                return MGN_OK;
-            };
-            if (int rc = R.tsit5_first(0.0)) return efail(rc);
-            for (int64_t i = 0; i < K; ++i) {
-                HIPCHK(h, hipMemcpyAsync(steps[i], zc ? R.za : R.u, nb, hipMemcpyDeviceToDevice, st));
-                if (int rc = R.tsit5_trial(0.0, DT, 0.0, nullptr)) return efail(rc);
-                R.tsit5_advance();
-                ++nacc;
-                HIPCHK(h, saves_after(i + 1));
-            }
-            R.keep = nullptr;
-        }
-        if (saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", who, saved, ns);
+        for (int64_t i = 0; !euler && i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
+        const Rollout::Slot slot = [&](int64_t i, float** out) { *out = steps[i]; return MGN_OK; };
+        if (int rc = euler ? R.euler_train(K, G.save_step, store) : R.tsit5_fixed(K, G.save_step, slot)) return efail(rc);
+        if (R.saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", who, R.saved, ns);
         d->n_accept += (int32_t)(K * B);
         d->n_rhs += R.n_rhs * B;
 
@@ -3075,7 +2928,7 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
 
         SolverSweep S{};
         S.K = K; S.states = euler ? store : nullptr; S.saves = R.saves; S.save_step = G.save_step.data(); S.n_saves = ns;
-        S.gt = tg; S.loss_scale = lsd; S.inflow = mrep; S.cont_target = has_ct ? ctt : nullptr; S.cont_weight = 0.f; S.dt = euler ? (float)DT : 0.f;
+        S.gt = tg; S.loss_scale = lsd; S.inflow = mrep; S.cont_target = has_ct ? ctt : nullptr; S.cont_weight = 0.f; S.dt = euler ? (float)DG.dt : 0.f;
         if (e == h) {
             S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
         } else {
@@ -3086,7 +2939,7 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
         if (euler) {
             if (int rc = solver_sweep(e, S)) return efail(rc);
         } else {
-            Tsit5Sweep T5{steps.data(), step_h.data(), R.u, (float*)(base + o_yb)};
+            Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, (float*)(base + o_yb)};
             if (int rc = tsit5_sweep(e, S, T5)) return efail(rc);
         }
         if (d->out) {       // the predicted saves in window order
@@ -3104,21 +2957,9 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
     HIPCHK(h, hipMemcpyAsync(grads, gf, P_ * 4, hipMemcpyDefault, st));
     std::vector<double> lp((size_t)2 * ld);
     HIPCHK(h, hipMemcpyAsync(lp.data(), lacc, lp.size() * 8, hipMemcpyDeviceToHost, st));
-    std::vector<float> ov;
-    if (d->out) {
-        const size_t ob = (size_t)out_row[W] * nN * 4;
-        if (g.renumbered) {
-            ov.resize((size_t)out_row[W] * nN);
-            HIPCHK(h, hipMemcpyAsync(ov.data(), sbase + o_out, ob, hipMemcpyDeviceToHost, st));
-        } else {
-            HIPCHK(h, hipMemcpyAsync(d->out, sbase + o_out, ob, hipMemcpyDeviceToHost, st));
-        }
-    }
+    if (d->out)
+        if (int rc = saves_to_caller(h, (const float*)(sbase + o_out), out_row[W], d->out)) return rc;
     HIPCHK(h, hipStreamSynchronize(st));
-    if (!ov.empty())
-        for (int64_t r = 0; r < out_row[W]; ++r)
-            for (int32_t j = 0; j < N; ++j)
-                memcpy(d->out + ((size_t)r * N + (size_t)g.own_gid[j]) * O, ov.data() + ((size_t)r * N + j) * O, (size_t)O * 4);
     double se = 0.0, sa = 0.0;
     for (int b = 0; b < ld; ++b) { se += lp[b]; sa += lp[(size_t)ld + b]; }
     *loss = (float)(se + sa);
