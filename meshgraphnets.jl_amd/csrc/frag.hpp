@@ -20,9 +20,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // The two waves that share a SIMD arbitrate instruction issue by priority, then age: without help the older
 // wave's MFMA chain starves the younger wave's gather/LayerNorm/scan phase (measured 2-3x longer).  Every
 // wave therefore raises its priority while it is OUTSIDE its MFMA chains (-6 % kernel time, same-box A/B).
-#ifndef MGN_PRIO
 #define MGN_PRIO 1
-#endif
 // Re-derive the lane id through an opaque asm once per tile: every address and table read that depends
 // on it then stays INSIDE the persistent tile loop.  Without this hipcc hoists ~250 loop-invariant LDS
 // table reads and 64-bit weight addresses out of the loop and spills them all to scratch.
@@ -149,11 +147,7 @@ DEVINL void zero_frag(f32x16 (&x)[NT]) {
 
 // ASM = false: plain fmaxf (two instructions per element, but nothing the scheduler cannot see: k_node_step, which keeps the builtin
 // MFMAs, is 7 % slower with the asm form and its wait states)
-#ifdef MGN_RELU_FMAXF
-constexpr bool RELU_ASM_DEFAULT = false;
-#else
 constexpr bool RELU_ASM_DEFAULT = true;
-#endif
 template <int NT, bool ASM = RELU_ASM_DEFAULT>
 DEVINL void relu_frag(f32x16 (&x)[NT]) {
     if constexpr (!ASM) {
@@ -163,32 +157,24 @@ DEVINL void relu_frag(f32x16 (&x)[NT]) {
             for (int k = 0; k < 16; ++k) x[t][k] = fmaxf(x[t][k], 0.f);
         return;
     }
-#ifndef MGN_RELU_FMAXF
     // x usually comes straight out of an MFMA chain, and hipcc's hazard recogniser does not cover an inline-asm reader of an MFMA
     // result (16 passes: 18 wait states before a VALU read): the wait states, tied to the registers
     if constexpr (NT == 4) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
     else if constexpr (NT == 2) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(x[0]), "+v"(x[1]));
     else asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(x[0]));
-#endif
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-#ifdef MGN_RELU_FMAXF
-            x[t][k] = fmaxf(x[t][k], 0.f);          // two instructions: hipcc canonicalises the operand first
-#else
             float r;                                // one v_max_f32 (maxNum: NaN -> 0, like fmaxf); non-volatile: free to be scheduled
             asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x[t][k]));
             x[t][k] = r;
-#endif
         }
-#ifndef MGN_RELU_FMAXF
     // ... and the other way round: an inline-asm VALU write followed by a compiler-issued MFMA that reads the register gets no
     // wait states either (k_node_step, builtin MFMAs: wrong results in the streaming and L = 64 / 32 instantiations)
     if constexpr (NT == 4) asm volatile("s_nop 3" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
     else if constexpr (NT == 2) asm volatile("s_nop 3" : "+v"(x[0]), "+v"(x[1]));
     else asm volatile("s_nop 3" : "+v"(x[0]));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -208,10 +194,7 @@ template <> DEVINL float aget<1>(const float& a, int) { return a; }
 // (`s_nop 3`) behind each they reach 156.  MGN_MFMA_NOP = N appends `s_nop N` to every MFMA of the chunk chains (non-volatile
 // inline asm: hipcc may still move the LDS / global weight reads across it).  The assembler-level MFMA is invisible to hipcc's
 // hazard recogniser: MFMA_CHAIN_BEGIN / _END supply the wait states around a chain.
-#ifndef MGN_MFMA_NOP
-#define MGN_MFMA_NOP 3          // -1: the compiler builtin, no padding (A/B)
-#endif
-#if MGN_MFMA_NOP >= 0
+#define MGN_MFMA_NOP 3
 template <bool PAD>
 DEVINL f32x16 mfma32(float a, float b, f32x16 c) {
     if constexpr (PAD) {
@@ -247,11 +230,6 @@ DEVINL void mfma_chain_end(f32x16 (&acc)[NT]) {
 }
 #define MFMA_CHAIN_BEGIN(ACC, IN) do { if constexpr (PAD) mfma_chain_begin(ACC, IN); } while (0)
 #define MFMA_CHAIN_END(ACC, NT_) do { if constexpr (PAD) mfma_chain_end(ACC); } while (0)
-#else
-template <bool PAD> DEVINL f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-#define MFMA_CHAIN_BEGIN(ACC, IN) do {} while (0)
-#define MFMA_CHAIN_END(ACC, NT_) do {} while (0)
-#endif
 
 // PAD = false: the compiler builtin (k_node_step is 6 % slower with the padded form; k_edge_step and k_project are faster)
 template <int NT, bool RES, bool PAD = true>
@@ -269,29 +247,18 @@ DEVINL void mfma_chunk(f32x16 (&acc)[NT], const f32x16 (&in)[NT], const float* w
                 acc[t] = mfma32<PAD>(aget<NT>(a, t), in[j >> 4][j & 15], acc[t]);
         }
     } else {
-#ifndef MGN_CHUNK_PF
 #define MGN_CHUNK_PF 4
-#endif
         constexpr int PF = MGN_CHUNK_PF;  // k-steps in flight: PF x (NT MFMA x 64 cyc) of cover for an L2 hit
         AV ring[PF];
 #pragma unroll
         for (int p = 0; p < PF; ++p) ring[p] = wv[p * 64];
-#ifdef MGN_CHUNK_FENCE
-        __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             const AV a = ring[j % PF];
             if (j + PF < J) ring[j % PF] = wv[(j + PF) * 64];
-#ifdef MGN_CHUNK_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 acc[t] = mfma32<PAD>(aget<NT>(a, t), in[j >> 4][j & 15], acc[t]);
-#ifdef MGN_CHUNK_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     }
     MFMA_CHAIN_END(acc, NT);
@@ -303,9 +270,7 @@ template <int NT, int JR, bool PAD = true>
 DEVINL void mfma_chunk_split(f32x16 (&acc)[NT], const f32x16 (&in)[NT], const float* w_lds, const float* w_glb, int lane) {
     typedef typename AVec<NT>::T AV;
     constexpr int J = 16 * NT;
-#ifndef MGN_PF
 #define MGN_PF 4
-#endif
     constexpr int PF = (J - JR) < MGN_PF ? (J - JR) : MGN_PF;
     const AV* wl = reinterpret_cast<const AV*>(w_lds) + lane;
     const AV* wg = reinterpret_cast<const AV*>(w_glb) + lane;
@@ -313,9 +278,6 @@ DEVINL void mfma_chunk_split(f32x16 (&acc)[NT], const f32x16 (&in)[NT], const fl
     MFMA_CHAIN_BEGIN(acc, in);
 #pragma unroll
     for (int p = 0; p < PF; ++p) ring[p] = wg[(JR + p) * 64];
-#ifdef MGN_SPLIT_FENCE
-    __builtin_amdgcn_sched_barrier(0);      // the requests go out HERE, not where hipcc would sink them (just before their use)
-#endif
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         AV a;
@@ -324,16 +286,10 @@ DEVINL void mfma_chunk_split(f32x16 (&acc)[NT], const f32x16 (&in)[NT], const fl
         } else {
             a = ring[(j - JR) % PF];
             if (j + PF < J) ring[(j - JR) % PF] = wg[(j + PF) * 64];
-#ifdef MGN_SPLIT_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
 #pragma unroll
         for (int t = 0; t < NT; ++t)
             acc[t] = mfma32<PAD>(aget<NT>(a, t), in[j >> 4][j & 15], acc[t]);
-#ifdef MGN_SPLIT_FENCE
-        if (j >= JR) __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     MFMA_CHAIN_END(acc, NT);
 }
@@ -429,9 +385,7 @@ DEVINL void copy_to_lds_sel(float* dst, const float* __restrict__ src, int nfloa
 // Cooperative 4-wave tiles (L = 128): wave t owns feature block t of every layer's output; see kernels.hip
 // ("Cooperative-tile kernels for SMALL graphs") for the design.  Shared by kernels.hip and train.hip.
 // ------------------------------------------------------------------------------------------------
-#ifndef MGN_COOP_PF
 #define MGN_COOP_PF 4
-#endif
 constexpr int COOP_PF = MGN_COOP_PF;   // weight ring depth in 16-byte fragments (4 k-steps each)
 
 // wt: this wave's t-slice of a chunk in t-major order [j/4][lane][4].  The weight ring of a chain can be primed ahead of
@@ -547,12 +501,8 @@ DEVINL void coop_layer_norm_reg(f32x16& mine, const f32x16 (&full)[4], const f32
 // XCD-aware persistent tile walk: blocks b and b+8 share an XCD (round-robin dispatch), so every XCD
 // gets one contiguous range of tiles and its waves sweep it interleaved -> gathered P/Q rows of
 // neighbouring tiles are served by that XCD's L2.  Speed only; any placement is correct.
-#ifndef MGN_SPREAD_ROUNDS
 #define MGN_SPREAD_ROUNDS 24
-#endif
-#ifndef MGN_SPREAD_ROUNDS_NODE
 #define MGN_SPREAD_ROUNDS_NODE MGN_SPREAD_ROUNDS
-#endif
 struct TileWalk {
     int tile, end, stride;
     DEVINL TileWalk(int ntiles, int wave, int spread_rounds = MGN_SPREAD_ROUNDS) {

@@ -82,9 +82,7 @@ DEVINL void gen_final(f32x16 (&acc)[NT], f32x16 (&y)[NT], const GenMlp& g, int l
 // a deeper weight ring, start stagger, a strict MFMA-pipe token between partner waves (all removed again).
 // Steps of the third chunk kept in the LDS left over by two resident chunks at L = 128 (0 when it is fully
 // resident anyway): 160 KiB - 2 x 64 KiB - tables - 64 spare bytes = 29 632 B = 28 k-steps of 1 KiB.
-#ifndef MGN_EDGE_JR
 #define MGN_EDGE_JR 28
-#endif
 template <int NT, int NRES, bool GEN = false>
 __global__ __launch_bounds__(512, 2) void k_edge_step(const EdgeArgs a) {
     constexpr int L = 32 * NT, CH = 16 * NT * 64 * NT;
@@ -201,11 +199,9 @@ __global__ __launch_bounds__(512, 2) void k_edge_step(const EdgeArgs a) {
 // V and AGG tile-major; CARRY, P, Q row-major.  CARRY row 2*ntiles_e is the all-zero row.
 // ================================================================================================
 
+// k_node_step's chains keep the builtin MFMAs and the plain ReLU (frag.hpp: the padded asm forms are slower here)
+constexpr bool NODE_PAD = false;
 // NAGG = 2: a second edge set's aggregate (AGG2 / CARRY2 / rowptr2) is a further layer-1 input, chunk[6] streamed.
-#ifndef MGN_NODE_PAD
-#define MGN_NODE_PAD 0
-#endif
-constexpr bool NODE_PAD = MGN_NODE_PAD != 0;
 template <int NT, int NRES, bool PROJECT, int NAGG = 1, bool GEN = false>
 __global__ __launch_bounds__(512, 2) void k_node_step(const NodeArgs a) {
     constexpr int L = 32 * NT, CH = 16 * NT * 64 * NT;
@@ -264,16 +260,10 @@ __global__ __launch_bounds__(512, 2) void k_node_step(const NodeArgs a) {
                 tab_frag<NT>(acc, tb + T_B3 * L, h);
                 mfma_chunk<NT, (NRES > 1), NODE_PAD>(acc, y, w3, lane);      // layer 3
             }
-#ifdef MGN_PRIO_NODE
-            __builtin_amdgcn_s_setprio(MGN_PRIO_NODE);
-#endif
             layer_norm_frag<NT>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
 #pragma unroll
             for (int t = 0; t < NT; ++t) v[t] += acc[t];        // v <- v + v'
             if (valid) store_frag<NT>(vtile, STRIDE_TILE, v);
-#ifdef MGN_PRIO_NODE
-            __builtin_amdgcn_s_setprio(0);
-#endif
         }
         if constexpr (PROJECT) {
             zero_frag<NT>(acc);
@@ -289,9 +279,7 @@ __global__ __launch_bounds__(512, 2) void k_node_step(const NodeArgs a) {
 // ================================================================================================
 // P,Q projection alone (both of its chunks LDS-resident: no weight streaming).  chunk[4]=WP chunk[5]=WQ
 // ================================================================================================
-#ifndef MGN_PROJ_WAVES
 #define MGN_PROJ_WAVES 8
-#endif
 template <int NT, bool RES>
 __global__ __launch_bounds__(MGN_PROJ_WAVES * 64, MGN_PROJ_WAVES / 4) void k_project(const NodeArgs a) {
     constexpr int L = 32 * NT, CH = 16 * NT * 64 * NT;
@@ -582,9 +570,7 @@ template <bool BF> DEVINL f32x4 c16_round(const f32x4 v) {
 // from L2 (a launch of one or two tiles per CU cannot amortise an LDS preload) through a register ring C16_PF k-groups deep, pinned
 // by scheduling fences (hipcc otherwise sinks every request to just before its use), and a chain's first fragments can be requested
 // ahead of time (c16_prime) -- before the previous chain or the exchange barrier.
-#ifndef C16_PF
 #define C16_PF 3
-#endif
 struct C16Ring { f32x4 r[2 * C16_PF]; };
 DEVINL void c16_prime(C16Ring& g, const float* wt, int lane) {
     const f32x4* wv = reinterpret_cast<const f32x4*>(wt) + lane;
@@ -776,9 +762,7 @@ DEVINL void c16s_exchange(C16X<NP> (&full)[RT][4], const f32x4 (&mine)[RT][2], u
 }
 // the weight pieces of a chunk stream from L2 through a register ring C16S_PF (k-step, block) steps deep; step s = 2 ks + j feeds
 // this wave's output block 2 wave + j
-#ifndef C16S_PF
 #define C16S_PF 3
-#endif
 template <int NP> struct C16SRingT { u32x4 r[NP * C16S_PF]; };
 DEVINL const u32x4* c16s_w(const uint16_t* chunk, int wave, int lane) { return reinterpret_cast<const u32x4*>(chunk) + (2 * wave) * 64 + lane; }
 template <int NP>
@@ -1746,116 +1730,7 @@ __global__ __launch_bounds__(512, 2) void k_decode(const DecArgs a) {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int BF_STRIDE_ROW = STRIDE_PROW, BF_STRIDE_TILE = 64;   // in 16-byte pieces (rows: blocks of eight, bf_prow_piece)
 
-DEVINL const bf16x8* bf_row_ptr(const uint16_t* base, int64_t row, int h) { return reinterpret_cast<const bf16x8*>(base) + bf_prow_piece(row, h); }
-DEVINL bf16x8* bf_row_ptr(uint16_t* base, int64_t row, int h) { return reinterpret_cast<bf16x8*>(base) + bf_prow_piece(row, h); }
-DEVINL const bf16x8* bf_tile_ptr(const uint16_t* base, int64_t tile, int lane) { return reinterpret_cast<const bf16x8*>(base + tile * (TILE * 128)) + lane; }
-DEVINL bf16x8* bf_tile_ptr(uint16_t* base, int64_t tile, int lane) { return reinterpret_cast<bf16x8*>(base + tile * (TILE * 128)) + lane; }
-
-DEVINL void bf_load(bf16x8 (&x)[8], const bf16x8* __restrict__ p, int stride) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) x[s] = p[s * stride];
-}
-DEVINL void bf_store(bf16x8* __restrict__ p, int stride, const bf16x8 (&x)[8]) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) p[s * stride] = x[s];
-}
-DEVINL void bf_pack(bf16x8 (&x)[8], const f32x16 (&acc)[4]) {          // accumulator -> B operand / storage
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[s][j] = (__bf16)acc[s >> 1][8 * (s & 1) + j];
-}
-DEVINL void bf_unpack_add(f32x16 (&acc)[4], const bf16x8 (&x)[8]) {    // acc += float(x)
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[s >> 1][8 * (s & 1) + j] += (float)x[s][j];
-}
-
-// one 128 x 128 chunk from LDS: w[(s*4 + t)*64 + lane] is the A fragment of k-step s, feature block t
-DEVINL void bf_chunk(f32x16 (&acc)[4], const bf16x8 (&in)[8], const bf16x8* w, int lane) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[(s * 4 + t) * 64 + lane], in[s], acc[t], 0, 0, 0);
-}
-
 constexpr int BF_CH = 128 * 128;   // bf16 elements per chunk (32 KiB)
-
-
-#ifndef MGN_BF_WAVES
-#define MGN_BF_WAVES 12   // waves per block of the bf16 edge kernel: 3 per SIMD (<= 168 VGPRs)
-#endif
-__global__ __launch_bounds__(MGN_BF_WAVES * 64, MGN_BF_WAVES / 4) void k_edge_bf16(const BfEdgeArgs a) {
-    constexpr int L = 128;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    uint16_t* wl = reinterpret_cast<uint16_t*>(smem);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) copy_to_lds16(wl + r * BF_CH, a.chunk[r], BF_CH, a.ntiles <= 16 * 1024);
-    float* tb = smem + 3 * BF_CH / 2;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const bf16x8* w2 = reinterpret_cast<const bf16x8*>(wl);
-    const bf16x8* w3 = reinterpret_cast<const bf16x8*>(wl + BF_CH);
-    const bf16x8* w1 = reinterpret_cast<const bf16x8*>(wl + 2 * BF_CH);
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    EdgeArgs ia{};   // load_edge_idx only needs the index arrays
-    ia.snd = a.snd; ia.rcv = a.rcv; ia.E = a.E;
-    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
-        OPAQUE_LANE();
-        const int tile = a.tile0 + tw.tile;
-        const EdgeIdx ix = load_edge_idx(ia, tile, c);
-        const bool valid = ix.r >= 0;
-        const int r = valid ? ix.r : 0;
-        bf16x8 x[8], in[8];
-        f32x16 acc[4];   // ONE fp32 accumulator array: the packed copy `in` is the next layer's operand
-        bf16x8* etile = bf_tile_ptr(a.Elat, tile, lane);
-        bf_load(x, etile, BF_STRIDE_TILE);
-        zero_frag<4>(acc);
-        bf_load(in, bf_row_ptr(a.P, ix.s, h), BF_STRIDE_ROW);
-        bf_unpack_add(acc, in);
-        bf_load(in, bf_row_ptr(a.Q, r, h), BF_STRIDE_ROW);
-        bf_unpack_add(acc, in);
-        bf_chunk(acc, x, w1, lane);                              // layer 1 (edge part; P, Q, b1 preloaded)
-        relu_frag<4>(acc);
-        bf_pack(in, acc);
-        tab_frag<4>(acc, tb + T_B2 * L, h);
-        bf_chunk(acc, in, w2, lane);                             // layer 2
-        relu_frag<4>(acc);
-        bf_pack(in, acc);
-        tab_frag<4>(acc, tb + T_B3 * L, h);
-        bf_chunk(acc, in, w3, lane);                             // layer 3
-        layer_norm_frag<4>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);   // acc = e' (fp32)
-        // residual in fp32, stored as bf16
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) in[s][j] = (__bf16)((float)x[s][j] + acc[s >> 1][8 * (s & 1) + j]);
-        if (valid) bf_store(etile, BF_STRIDE_TILE, in);
-        // segmented sum of e' (fp32) over runs of equal receiver
-        const int reff = valid ? r : (-4 - c);
-        const int rprev = __shfl_up(reff, 1, 32);
-        const int rnext = __shfl_down(reff, 1, 32);
-        const bool head = (c == 0) || (reff != rprev);
-        const unsigned hm = (unsigned)__ballot(head);
-        const int start = 31 - __clz((int)(hm & (0xFFFFFFFFu >> (31 - c))));
-        const int st_in = max(start, c & 16);
-        const bool c1 = (c - 1 >= st_in), c2 = (c - 2 >= st_in), c4 = (c - 4 >= st_in), c8 = (c - 8 >= st_in);
-        const bool cx = (c >= 16) && (start <= 15);
-        segmented_scan<4, true>(acc, c1, c2, c4, c8, cx);
-        const bool tail = valid && ((c == 31) || (reff != rnext));
-        const int r_first = __builtin_amdgcn_readfirstlane(reff);
-        const bool sl = (start == 0) && (ix.r_before == r_first);
-        const bool sr = (c == 31) && (ix.r_after == reff);
-        const bool to_carry = sl || sr;
-        bf16x8* dst = to_carry ? bf_row_ptr(a.CARRY, (int64_t)2 * tile + (sl ? 0 : 1), h)
-                               : bf_tile_ptr(a.AGG, r >> 5, 32 * h + (r & 31));
-        bf_pack(in, acc);
-        if (tail) bf_store(dst, to_carry ? BF_STRIDE_ROW : BF_STRIDE_TILE, in);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // bf16 processor, second generation (round 2).  What the rocprofv3 passes of the first version showed (profiles/r02/
@@ -1942,9 +1817,7 @@ DEVINL void bfq_pack(u32x4 (&x)[8], const f32x16 (&acc)[4]) {
 // flight, and the chains ran at LDS LATENCY, ~3 x the pipe's pace (deleting one of the three chains of the edge kernel took a
 // third off the whole kernel: 0.92 -> 0.61 ms).  Here the fragments go through a register ring MGN_BF_RING deep, pinned by
 // scheduling fences: MGN_BF_RING reads are in flight ahead of every MFMA.
-#ifndef MGN_BF_RING
 #define MGN_BF_RING 6
-#endif
 DEVINL void bfq_chunk(f32x16 (&acc)[4], const u32x4 (&in)[8], const bf16x8* w, int lane) {
     constexpr int D = MGN_BF_RING;
     const bf16x8* wl = w + lane;
@@ -2042,11 +1915,7 @@ DEVINL void bf_edge_tile(const BfEdgeArgs& a, const BfEdgeCtx& cx, int tile, int
     const bool valid = ix.r >= 0;
     const int r = valid ? ix.r : 0;
     u32x4 in[8], pn[8], qn[8];
-#ifdef MGN_EXP_NOGATHER
-    bfq_load<false>(pn, bfq_row_ptr(a.P, c, h), BF_STRIDE_ROW);
-#else
     bfq_load<false>(pn, bfq_row_ptr(a.P, ixn.s, h), BF_STRIDE_ROW);
-#endif
     bfq_load<true>(xn, bfq_tile_ptr(a.Elat, tile_next, lane), BF_STRIDE_TILE);
     const EdgeIdx ixnn = load_edge_idx_nb(a.snd, a.rcv, a.E, tile_next2, c);
     PHASE_FENCE();
@@ -2056,9 +1925,7 @@ DEVINL void bf_edge_tile(const BfEdgeArgs& a, const BfEdgeCtx& cx, int tile, int
     bfq_pack<true>(in, acc);
     PHASE_FENCE();      // the bias table must not be read into 64 NEW registers while the old accumulator is still being packed
     tab_frag<4>(acc, cx.tb + T_B2 * L, h);
-#ifndef MGN_EXP_NOL2
     bfq_chunk(acc, in, cx.w2, lane);                             // layer 2
-#endif
     STAMP(3);
     bfq_pack<true>(in, acc);
     PHASE_FENCE();
@@ -2080,11 +1947,7 @@ DEVINL void bf_edge_tile(const BfEdgeArgs& a, const BfEdgeCtx& cx, int tile, int
     if (valid) bfq_store<true>(bfq_tile_ptr(a.Elat, tile, lane), BF_STRIDE_TILE, in);
     PHASE_FENCE();
     STAMP(5);
-#ifdef MGN_EXP_NOGATHER
-    bfq_load<false>(qn, bfq_row_ptr(a.Q, c, h), BF_STRIDE_ROW);
-#else
     bfq_load<false>(qn, bfq_row_ptr(a.Q, ixn.r >= 0 ? ixn.r : 0, h), BF_STRIDE_ROW);           // next tile's Q rows
-#endif
     // segmented sum of e' (fp32) over runs of equal receiver
     const int reff = valid ? r : (-4 - c);
     const int rprev = __shfl_up(reff, 1, 32);
@@ -2095,9 +1958,7 @@ DEVINL void bf_edge_tile(const BfEdgeArgs& a, const BfEdgeCtx& cx, int tile, int
     const int st_in = max(start, c & 16);
     const bool c1 = (c - 1 >= st_in), c2 = (c - 2 >= st_in), c4 = (c - 4 >= st_in), c8 = (c - 8 >= st_in);
     const bool cxr = (c >= 16) && (start <= 15);
-#ifndef MGN_EXP_NOSCAN
     segmented_scan<4, true>(acc, c1, c2, c4, c8, cxr);
-#endif
     STAMP(6);
     const bool tail = valid && ((c == 31) || (reff != rnext));
     const int r_first = __builtin_amdgcn_readfirstlane(reff);
@@ -2168,84 +2029,6 @@ __global__ __launch_bounds__(512, 2) void k_edge_bf16_pipe(const BfEdgeArgs a) {
         bf_edge_tile(a, cx, a.tile0 + t + tw.stride, clampt(t + 2 * tw.stride), clampt(t + 3 * tw.stride), more2, acc, ix, ixn, xb, xa,
                      stamp_tile + 1, wave);
         if (!more2) break;
-    }
-}
-
-// bf16 twin of load_aggregate; `y` is scratch (carry rows are summed in fp32 and rounded once)
-DEVINL void bf_load_aggregate(bf16x8 (&in)[8], f32x16 (&y)[4], const int32_t* __restrict__ rowptr, const uint16_t* AGG, const uint16_t* CARRY,
-                              int64_t zero_row, int tile, int nn, bool valid, int lane, int h) {
-    const int a0 = valid ? rowptr[nn] : 0, a1 = valid ? rowptr[nn + 1] : 0;
-    const int T1 = a0 >> 5, T2 = (a1 - 1) >> 5;
-    const int extra = (a1 > a0 && T2 > T1) ? (T2 - T1) : 0;
-    const bool from_agg = (a1 > a0) && !extra;
-    const bf16x8* src0 = from_agg ? bf_tile_ptr(AGG, tile, lane) : bf_row_ptr(CARRY, extra ? (int64_t)(2 * T1 + 1) : zero_row, h);
-    bf_load(in, src0, from_agg ? BF_STRIDE_TILE : BF_STRIDE_ROW);
-    if (__any(extra > 0)) {
-        zero_frag<4>(y);
-        bf_unpack_add(y, in);
-        {   // the second carry row of a run that straddles one tile boundary (the common case) without a loop: the other lanes add the
-            // zero row (tile_common.hpp: LOAD_AGGREGATE); hub nodes continue in the loop
-            bf16x8 cr[8];
-            bf_load(cr, bf_row_ptr(CARRY, extra >= 1 ? (int64_t)2 * (T1 + 1) : zero_row, h), BF_STRIDE_ROW);
-            bf_unpack_add(y, cr);
-        }
-        if (__any(extra >= 2))
-            for (int q = 2; __any(q <= extra); ++q)
-                if (q <= extra) {
-                    bf16x8 cr[8];
-                    bf_load(cr, bf_row_ptr(CARRY, (int64_t)2 * (T1 + q), h), BF_STRIDE_ROW);
-                    bf_unpack_add(y, cr);
-                }
-        bf_pack(in, y);
-    }
-}
-
-// node MLP: chunk[0]=W2 [1]=W3 [2]=W1v [3]=W1a, all resident (128 KiB)
-__global__ __launch_bounds__(512, 2) void k_node_bf16(const BfNodeArgs a) {
-    constexpr int L = 128;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    uint16_t* wl = reinterpret_cast<uint16_t*>(smem);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) copy_to_lds16(wl + r * BF_CH, a.chunk[r], BF_CH, a.ntiles <= 16 * 1024);
-    float* tb = smem + 4 * BF_CH / 2;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const bf16x8* w2 = reinterpret_cast<const bf16x8*>(wl);
-    const bf16x8* w3 = reinterpret_cast<const bf16x8*>(wl + BF_CH);
-    const bf16x8* w1v = reinterpret_cast<const bf16x8*>(wl + 2 * BF_CH);
-    const bf16x8* w1a = reinterpret_cast<const bf16x8*>(wl + 3 * BF_CH);
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
-        OPAQUE_LANE();
-        const int tile = tw.tile;
-        const int n = tile * TILE + c;
-        const bool valid = n < a.n;
-        const int nn = valid ? n : 0;
-        bf16x8 v[8], in[8];
-        f32x16 acc[4], y[4];
-        bf16x8* vtile = bf_tile_ptr(a.V, tile, lane);
-        bf_load(v, vtile, BF_STRIDE_TILE);
-        bf_load_aggregate(in, y, a.rowptr, a.AGG, a.CARRY, a.zero_row, tile, nn, valid, lane, h);
-        tab_frag<4>(acc, tb + T_B1 * L, h);
-        bf_chunk(acc, v, w1v, lane);                             // layer 1, node part
-        bf_chunk(acc, in, w1a, lane);                            // layer 1, aggregate part
-        if (a.AGG2) {                                            // second edge set's aggregate (its chunk streams from L2)
-            bf_load_aggregate(in, y, a.rowptr2, a.AGG2, a.CARRY2, a.zero_row2, tile, nn, valid, lane, h);
-            bf_chunk(acc, in, reinterpret_cast<const bf16x8*>(a.chunk[6]), lane);
-        }
-        relu_frag<4>(acc);
-        bf_pack(in, acc);
-        tab_frag<4>(y, tb + T_B2 * L, h);
-        bf_chunk(y, in, w2, lane);
-        relu_frag<4>(y);
-        bf_pack(in, y);
-        tab_frag<4>(acc, tb + T_B3 * L, h);
-        bf_chunk(acc, in, w3, lane);
-        layer_norm_frag<4>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
-        bf_unpack_add(acc, v);                                   // v <- v + v'  (fp32 add, one rounding)
-        bf_pack(in, acc);
-        if (valid) bf_store(vtile, BF_STRIDE_TILE, in);
     }
 }
 
@@ -2431,40 +2214,6 @@ __global__ __launch_bounds__(512, 2) void k_project_bf16_pipe(const BfNodeArgs a
         if (t + tw.stride > last) break;
         body(t + tw.stride, vb, va);
         if (t + 2 * tw.stride > last) break;
-    }
-}
-
-// P,Q projection: chunk[4]=WP chunk[5]=WQ resident
-__global__ __launch_bounds__(512, 2) void k_project_bf16(const BfNodeArgs a) {
-    constexpr int L = 128;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    uint16_t* wl = reinterpret_cast<uint16_t*>(smem);
-    copy_to_lds16(wl, a.chunk[4], BF_CH, a.ntiles <= 16 * 1024);
-    copy_to_lds16(wl + BF_CH, a.chunk[5], BF_CH, a.ntiles <= 16 * 1024);
-    float* tb = smem + 2 * BF_CH / 2;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const bf16x8* wp = reinterpret_cast<const bf16x8*>(wl);
-    const bf16x8* wq = reinterpret_cast<const bf16x8*>(wl + BF_CH);
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
-        OPAQUE_LANE();
-        const int tile = a.tile0 + tw.tile;
-        const int n = tile * TILE + c;
-        const bool valid = n < a.n;
-        const int nn = valid ? n : 0;
-        bf16x8 v[8], out[8];
-        f32x16 acc[4];
-        bf_load(v, bf_tile_ptr(a.V, tile, lane), BF_STRIDE_TILE);
-        zero_frag<4>(acc);
-        bf_chunk(acc, v, wp, lane);
-        bf_pack(out, acc);
-        if (valid) bf_store(bf_row_ptr(a.P, nn, h), BF_STRIDE_ROW, out);
-        tab_frag<4>(acc, tb + T_BQ * L, h);
-        bf_chunk(acc, v, wq, lane);
-        bf_pack(out, acc);
-        if (valid) bf_store(bf_row_ptr(a.Q, nn, h), BF_STRIDE_ROW, out);
     }
 }
 
@@ -3128,22 +2877,17 @@ static LaunchCfg bf_launch(int ntiles, int nchunks) {
     lc.lds = (size_t)nchunks * BF_CH * 2 + (size_t)T_COUNT * 128 * 4;
     return lc;
 }
-static int g_bf_edge = [] { const char* e = getenv("MGN_BF_EDGE"); return e ? atoi(e) : 1; }();   // 0: first-generation kernel (A/B)
 hipError_t launch_edge_bf16(const BfEdgeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    LaunchCfg lc = bf_launch(a.ntiles, 3);
-    if (g_bf_edge) return launch_k(k_edge_bf16_pipe, a, lc, s);   // software-pipelined: two waves per SIMD, 256 registers
-    if (lc.threads == 512) lc.threads = MGN_BF_WAVES * 64;   // large launch: more waves per SIMD hide the memory phases
-    return launch_k(k_edge_bf16, a, lc, s);
+    return launch_k(k_edge_bf16_pipe, a, bf_launch(a.ntiles, 3), s);   // software-pipelined: two waves per SIMD, 256 registers
 }
-static int g_bf_node = [] { const char* e = getenv("MGN_BF_NODE"); return e ? atoi(e) : 1; }();   // 0: first-generation node kernels (A/B)
 hipError_t launch_node_bf16(const BfNodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    return g_bf_node ? launch_k(k_node_bf16_pipe, a, bf_launch(a.ntiles, 4), s) : launch_k(k_node_bf16, a, bf_launch(a.ntiles, 4), s);
+    return launch_k(k_node_bf16_pipe, a, bf_launch(a.ntiles, 4), s);
 }
 hipError_t launch_project_bf16(const BfNodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    return g_bf_node ? launch_k(k_project_bf16_pipe, a, bf_launch(a.ntiles, 2), s) : launch_k(k_project_bf16, a, bf_launch(a.ntiles, 2), s);
+    return launch_k(k_project_bf16_pipe, a, bf_launch(a.ntiles, 2), s);
 }
 hipError_t launch_tile_f32_to_bf16(const float* src, uint16_t* dst, int64_t ntiles, hipStream_t s) {
     const int64_t n = ntiles * 512;

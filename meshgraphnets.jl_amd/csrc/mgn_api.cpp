@@ -588,7 +588,7 @@ BfEdgeArgs bf_edge_args(mgn_engine* h, int k, int q = 0) {
     return a;
 }
 
-// project: the args feed k_project_bf16 (P,Q of set q); else k_node_bf16 (node MLP over all sets' aggregates)
+// project: the args feed k_project_bf16_pipe (P,Q of set q); else k_node_bf16_pipe (node MLP over all sets' aggregates)
 BfNodeArgs bf_node_args(mgn_engine* h, int k, int q = 0, bool project = false) {
     BfNodeArgs a{};
     const auto& so = h->bsoff[k];

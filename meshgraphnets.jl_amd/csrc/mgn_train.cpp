@@ -804,9 +804,8 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             HIPCHK(h, hipStreamWaitEvent(wst, T.ev_bwd, 0));
         }
         if (pwb.njobs > 0 && wgrad_blocks(plrows) > 0) {
-            static const int whatif = [] { const char* e = getenv("MGN_TRAIN_WHATIF"); return e ? atoi(e) : 0; }();   // diagnostic (wrong gradients): 1 no weight-gradient launches, 2 no reductions
-            if (!(whatif & 1)) HIPCHK(h, launch_wgrad(L, pwb, plrows, wst));
-            if (!(whatif & 2)) HIPCHK(h, launch_reduce_partials(prb, wst));
+            HIPCHK(h, launch_wgrad(L, pwb, plrows, wst));
+            HIPCHK(h, launch_reduce_partials(prb, wst));
         }
         if (overlap) HIPCHK(h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
         ++nbatch;
@@ -1038,9 +1037,8 @@ int train_run(mgn_handle* h, const TrainJob& J) {
 
     if (int rc = flush()) return rc;                     // the units left over from the last full group
     if (!deferred.empty()) {                             // every unit's reductions, REDUCE_MAX_JOBS per launch, behind the last weight-gradient launch
-        static const int whatif = [] { const char* e = getenv("MGN_TRAIN_WHATIF"); return e ? atoi(e) : 0; }();
         hipStream_t wst = overlap ? T.aux : st;
-        for (size_t i = 0; i < deferred.size() && !(whatif & 2); i += REDUCE_MAX_JOBS) {
+        for (size_t i = 0; i < deferred.size(); i += REDUCE_MAX_JOBS) {
             ReduceBatch rb{};
             for (size_t j = i; j < deferred.size() && j < i + REDUCE_MAX_JOBS; ++j) rb.job[rb.njobs++] = deferred[j];
             HIPCHK(h, launch_reduce_partials(rb, wst));

@@ -27,12 +27,6 @@
 
 namespace mgn {
 
-#ifndef MGN_SP_CARRY
-#define MGN_SP_CARRY 1            // k_node_split, k_project_split: weight rings carried from chain to chain (needs MGN_SP_BUFFER)
-#endif
-#ifndef MGN_SP_BUFFER
-#define MGN_SP_BUFFER 1           // sp_layer_otf: streamed weight pieces through buffer descriptors (0: 64-bit pointers)
-#endif
 
 // One L x L layer: acc += W^T in, `in` split on the fly.  p1 / p2 / p3: the chunk's hi / mid / lo piece ([s][t][lane] fragments of
 // 8 bf16).  p1 is LDS-resident; G2 / G3: p2 / p3 stream from L2 through register rings D (s, t) groups deep (else LDS too).  The
@@ -48,19 +42,13 @@ DEVINL void sp_layer_otf(f32x16 (&acc)[4], const f32x16 (&in)[4], const u32x4* p
     const u32x4* w1 = p1 + lane;
     const u32x4* w2 = p2 + lane;
     const u32x4* w3 = p3 + lane;
-#if MGN_SP_BUFFER
     // streamed pieces through buffer descriptors: the lane's offset is ONE register for all of them, the fragment index a scalar
     const N16Buf b1 = n16_buf(G1 ? p1 : nullptr), b2 = n16_buf(G2 ? p2 : nullptr), b3 = n16_buf(G3 ? p3 : nullptr);
     const unsigned voff = (unsigned)lane * 16u;
 #define SP_G1(IDX) n16_ldu(b1, voff, (IDX) * 1024)
 #define SP_G2(IDX) n16_ldu(b2, voff, (IDX) * 1024)
 #define SP_G3(IDX) n16_ldu(b3, voff, (IDX) * 1024)
-#else
-#define SP_G1(IDX) w1[(IDX) * 64]
-#define SP_G2(IDX) w2[(IDX) * 64]
-#define SP_G3(IDX) w3[(IDX) * 64]
-#endif
-    static_assert(!(PRIMED || NEXT) || (MGN_SP_BUFFER && !G1), "ring carry-over is written for the descriptor path, mid / lo streams");
+    static_assert(!(PRIMED || NEXT) || !G1, "ring carry-over is written for the mid / lo streams");
     u32x4 r1[G1 ? D : 1], r2[G2 ? D : 1], r3[G3 ? D : 1];      // G1: the hi piece streams from L2 as well (a chunk that has no room in LDS)
     if constexpr (PRIMED) {
 #pragma unroll
@@ -76,9 +64,7 @@ DEVINL void sp_layer_otf(f32x16 (&acc)[4], const f32x16 (&in)[4], const u32x4* p
             if constexpr (G3) r3[(d + OFF) % D] = SP_G3(d);
         }
     }
-#if MGN_SP_BUFFER
     const N16Buf c2 = n16_buf(NEXT && G2 ? nx2 : nullptr), c3 = n16_buf(NEXT && G3 ? nx3 : nullptr);
-#endif
     u32x4 n1, n2, n3;
     if constexpr (!G1) n1 = w1[0];
     if constexpr (!G2) n2 = w2[0];
@@ -107,43 +93,26 @@ DEVINL void sp_layer_otf(f32x16 (&acc)[4], const f32x16 (&in)[4], const u32x4* p
                 if constexpr (G2) r2[(it + OFF) % D] = SP_G2(it + D);
                 if constexpr (G3) r3[(it + OFF) % D] = SP_G3(it + D);
             } else if constexpr (NEXT) {
-#if MGN_SP_BUFFER
                 if constexpr (G2) r2[(it + OFF) % D] = n16_ldu(c2, voff, (it + D - 32) * 1024);
                 if constexpr (G3) r3[(it + OFF) % D] = n16_ldu(c3, voff, (it + D - 32) * 1024);
-#endif
             }
             if (s < 7) {
                 const int sn = s + 1;
                 sp_split_pair<RELU>(n.h[t], n.m[t], n.l[t], in[sn >> 1][8 * (sn & 1) + 2 * t], in[sn >> 1][8 * (sn & 1) + 2 * t + 1]);
             }
             const sp_bf16x8 bh = sp_op(p.h), bm = sp_op(p.m), bl = sp_op(p.l);
-#ifdef MGN_WHATIF_MFMA16_NODE   // diagnostic (wrong results): matrix time and operand traffic of this layer on v_mfma_f32_16x16x32_bf16
-#define OTF_MFMA(A_, B_)                                                                                               \
-            do {                                                                                                       \
-                f32x4 c0_, c1_;                                                                                        \
-                _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { c0_[i_] = acc[t][i_]; c1_[i_] = acc[t][4 + i_]; }     \
-                c0_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, c0_, 0, 0, 0);                                    \
-                c1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, c1_, 0, 0, 0);                                    \
-                _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { acc[t][i_] = c0_[i_]; acc[t][4 + i_] = c1_[i_]; }     \
-            } while (0)
-#else
-#define OTF_MFMA(A_, B_) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, acc[t], 0, 0, 0)
-#endif
-            OTF_MFMA(sp_wop(a3), bh);      // small terms first
-            OTF_MFMA(sp_wop(a2), bm);
-            OTF_MFMA(sp_wop(a1), bl);
-            OTF_MFMA(sp_wop(a2), bh);
-            OTF_MFMA(sp_wop(a1), bm);
-            OTF_MFMA(sp_wop(a1), bh);
-#undef OTF_MFMA
-#if MGN_SP2_INTERLEAVE
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a3), bh, acc[t], 0, 0, 0);      // small terms first
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a2), bm, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a1), bl, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a2), bh, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a1), bm, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a1), bh, acc[t], 0, 0, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
         p = n;
@@ -161,15 +130,8 @@ DEVINL void sp_layer_otf(f32x16 (&acc)[4], const f32x16 (&in)[4], const u32x4* p
 #undef SP_G2
 #undef SP_G3
 
-#ifndef MGN_SP2_D
 #define MGN_SP2_D 6
-#endif
-#ifndef MGN_NODE_VNEXT_FIRST
-#define MGN_NODE_VNEXT_FIRST 0   // node-side split kernels: 1 = the next tile's V requested ahead of this tile's stores (1.178 vs 1.170 ms: nothing; the waves of these kernels are not in lock-step)
-#endif
-#ifndef MGN_SP2_D1
 #define MGN_SP2_D1 8       // layer 2 streams one piece only
-#endif
 // ================================================================================================
 // Lock-step variant of the edge step: the streamed weight pieces go through ONE LDS ring per block instead of eight per-wave
 // register rings.  The register-ring kernel (k_edge_split2, docs/experiments/split_variants_r04.hip) reads 160 KiB of weight pieces per tile and wave from L2; stamps show what that costs: with ~100
@@ -184,7 +146,7 @@ DEVINL void sp_layer_otf(f32x16 (&acc)[4], const f32x16 (&in)[4], const u32x4* p
 //     is the same for every tile.
 // L2 weight traffic per tile: 192 KiB per EIGHT tiles.  All waves run the same number of tiles (stores of padding tiles masked).
 //
-// Turnover (round 4, MGN_RING_ENEXT = 1).  s_waitcnt vmcnt retires in order and counts stores: a load requested behind the tile's 16 KiB
+// Turnover (round 4).  s_waitcnt vmcnt retires in order and counts stores: a load requested behind the tile's 16 KiB
 // of e stores is not "back" before those stores are acknowledged, so round 3's order -- residual, store e, THEN request the next tile's e
 // and Q rows -- put the store tail (6-15 k cycles for sixteen store instructions of eight lock-step waves) in front of the next tile's
 // first MFMA.  Now layer 3's refill brings the NEXT tile's e tile into the registers its input releases (twelve pieces inside the layer,
@@ -229,42 +191,25 @@ DEVINL RingFrag ring_first(const u32x4* hi, const u32x4* ring, int lane) {
 // reloaded, as soon as the split has consumed them, with the two 16-byte pieces of k-step s + 2 of rf (piece m at rf[m * RFS]);
 // the pieces of k-steps 0 and 1 wait in a 16-register side buffer.  The last request goes out two k-steps before the layer ends;
 // `in` comes back holding rf's row in fragment order.  (In the epilogue these loads were two exposed memory round trips.)
-// When the requests go out (MGN_RING_REFILL_AT_REQUEST): 0 = two behind every k-step, side buffer at the top of the layer (the first
-// version); 1 = in batches of four right behind the window requests (vmcnt retires in order, so a request there is first waited for
-// at the NEXT window's LDS store, 5.4 k cycles later instead of 2.3-4.2 k): no gain, the e tile's latency is not what costs;
-// 2 (default) = one request every second step, and layer 3's side buffer requested the same way inside layer 2's last two k-steps
-// (NRFS, rf_next): 3.53 -> 3.46 ms.  What a request costs in the chain is its ISSUE: the eight waves are in lock-step, their
-// requests reach the CU's one memory pipeline together, and a wave whose request is not accepted issues no MFMA either (stamps:
-// every request adds ~500 cycles to its layer whether it hits L2 or not).
-// QP (layer 1, MGN_RING_QPSTREAM): the gathered rows P[s] and Q[r] that complete the layer stream THROUGH it instead of waiting in 64 + 64
-// registers: the accumulator starts from zero, every 16-byte piece is requested eight (s, t) steps before it is added, and it is added
-// into accumulator t + 2 while the MFMAs of step (s, t) run on accumulator t (written two steps ago, read again in two).  Per
-// accumulator: its four P pieces are added at k-steps 2 .. 5, its four Q pieces two by two at k-steps 6 and 7.  Nothing of the
-// turnover is then requested behind the tile's e stores, and no register waits for a row.
-template <int W, int LYR, bool RELU, int RFS = 0, int NRFS = 0, int NWV = 8, bool WRAP = false, bool QP = false>
+// When the requests go out: one request every second step, and layer 3's side buffer requested the same way inside layer 2's last
+// two k-steps (NRFS, rf_next): 3.53 -> 3.46 ms against two requests behind every k-step with the side buffer at the top of the layer
+// (the first version).  In batches of four right behind the window requests (vmcnt retires in order, so a request there is first
+// waited for at the NEXT window's LDS store, 5.4 k cycles later instead of 2.3-4.2 k): no gain, the e tile's latency is not what
+// costs.  What a request costs in the chain is its ISSUE: the eight waves are in lock-step, their requests reach the CU's one memory
+// pipeline together, and a wave whose request is not accepted issues no MFMA either (stamps: every request adds ~500 cycles to its
+// layer whether it hits L2 or not).
+template <int W, int LYR, bool RELU, int RFS = 0, int NRFS = 0, int NWV = 8, bool WRAP = false>
 DEVINL void sp_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, const u32x4* hi_next, u32x4* ring, const RingSrc& src,
                           RingFrag& nx, int lane, int tid, const f32x4* rf = nullptr, f32x4* side = nullptr,
-                          const f32x4* rf_next = nullptr, const f32x4* qp_p = nullptr, const f32x4* qp_q = nullptr) {
-#ifndef MGN_RING_ROT
-#define MGN_RING_ROT 2
-#endif
-#ifndef MGN_RING_REFILL_AT_REQUEST
-#define MGN_RING_REFILL_AT_REQUEST 2
-#endif
-    constexpr int ROT = MGN_RING_ROT;            // k-steps between a register's release and the use of what it is refilled with
-#ifndef MGN_RING_SIDE_EARLY
-#define MGN_RING_SIDE_EARLY 1                // bit 0: layer 3's side buffer requested inside layer 2, bit 1: layer 1's in the epilogue before
-#endif
-    constexpr int MODE = MGN_RING_REFILL_AT_REQUEST;                  // 0: two requests behind each k-step, 1: with the window requests, 2: one per two steps
-    constexpr bool ATREQ = MODE == 1;
-    static_assert(MODE == 0 || ROT == 2, "the other schedules are written for a rotation of two k-steps");
-    // WRAP (schedule 2 only; for a refill that is first used well after the layer, the e tile behind layer 3): no side buffer and no
+                          const f32x4* rf_next = nullptr) {
+    constexpr int ROT = 2;                       // k-steps between a register's release and the use of what it is refilled with
+    // WRAP (for a refill that is first used well after the layer, the e tile behind layer 3): no side buffer and no
     // rotation -- the registers of k-step s take the pieces of k-step s, for s < 8 - ROT; the last ROT k-steps' pieces (in[3][16 - 8 ROT ..])
     // are left to the caller, who requests them behind the layer (requested inside it they are spilled where they land, with an
     // s_waitcnt vmcnt(0) in the middle of the chain: the 64 registers of `in` are free only when the layer is done).
-    static_assert(!WRAP || (MODE == 2 && RFS > 0), "the plain refill is written for schedule 2");
+    static_assert(!WRAP || RFS > 0, "the plain refill needs a refill source");
     f32x4 side_local[2 * ROT];
-    if constexpr (!WRAP && RFS > 0 && (MODE == 0 || !((MGN_RING_SIDE_EARLY >> (LYR == 0 ? 1 : 0)) & 1))) {
+    if constexpr (!WRAP && RFS > 0 && LYR == 0) {
         side = side_local;
 #pragma unroll
         for (int m = 0; m < 2 * ROT; ++m) side[m] = rf[m * RFS];
@@ -277,7 +222,6 @@ DEVINL void sp_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
     u32x4 ld_m[LPT], ld_l[LPT];                  // this thread's share of window gw + 2 on its way to LDS
     unsigned voff = (unsigned)tid * 16u;
     asm volatile("" : "+v"(voff));
-    f32x4 qp[QP ? 4 : 1][QP ? 8 : 1];            // QP: the pieces in flight, per accumulator (SSA values: live from request to add)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -287,70 +231,25 @@ DEVINL void sp_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
             const int it = 4 * s + t;
             const int gw = WPL * LYR + it / W;                        // global window of this step
             const u32x4 a1 = nx.h, a2 = nx.m, a3 = nx.l;
-            if constexpr (QP) {
-                constexpr int STR = STRIDE_PROW;
-                const int tt = (t + 2) & 3;                            // the accumulator these pieces belong to
-                if (s < 4) {
-                    qp[tt][s] = qp_p[(4 * tt + s) * STR];
-                } else if (s < 6) {
-                    qp[tt][4 + 2 * (s - 4)] = qp_q[(4 * tt + 2 * (s - 4)) * STR];
-                    qp[tt][5 + 2 * (s - 4)] = qp_q[(4 * tt + 2 * (s - 4) + 1) * STR];
-                }
-                if (s >= 2 && s < 6) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[tt][4 * (s - 2) + i] += qp[tt][s - 2][i];
-                } else if (s >= 6) {
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[tt][4 * (2 * (s - 6) + u) + i] += qp[tt][4 + 2 * (s - 6) + u][i];
-                }
-            }
             if (it % W == 0) {                                         // request window gw + 2
                 const int g2 = (gw + 2) % NW, l2 = g2 / WPL, w2 = g2 % WPL;
                 // (uniform base + 32-bit lane offset: the scalar-base form of global_load; as per-thread 64-bit pointers
                 // hipcc hoists them out of the tile loop and spills them)
-#if !(defined(MGN_WHATIF_LOADER) && (MGN_WHATIF_LOADER & 1))     // diagnostic (wrong results): 1 = no window loads at all, 2 = no barriers
 #pragma unroll
                 for (int i = 0; i < LPT; ++i) {
                     ld_m[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(src.mid[l2] + w2 * W * 64 + i * NWV * 64) + voff);
                     ld_l[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(src.lo[l2] + w2 * W * 64 + i * NWV * 64) + voff);
                 }
-#endif
-                if constexpr (ATREQ && W == 8) {
-                    if constexpr (RFS > 0) {
-                        // the registers of k-steps s - 2 and s - 1 (released one and two k-steps ago: refilling k-step s's own as
-                        // well leaves the allocator nothing to work with, 70 spills)
-                        const int lo_k = s - 2, hi_k = s - 1;
+            }
+            if constexpr (RFS > 0) {
+                if ((t & 1) && s < 8 - ROT) {                          // registers of k-step s (free since the step began), half t >> 1
+                    const f32x4 v = rf[(2 * (WRAP ? s : s + ROT) + (t >> 1)) * RFS];
 #pragma unroll
-                        for (int k = 0; k < 6; ++k)
-#pragma unroll
-                            for (int u = 0; u < 2; ++u) {
-                                if (k < lo_k || k > hi_k) continue;
-                                const f32x4 v = rf[(2 * (k + ROT) + u) * RFS];
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) in[k >> 1][8 * (k & 1) + 4 * u + i] = v[i];
-                            }
-                    }
-                    if constexpr (NRFS > 0 && (MGN_RING_SIDE_EARLY & 1)) {
-                        if (s == 6) {
-#pragma unroll
-                            for (int m = 0; m < 2 * ROT; ++m) side[m] = rf_next[m * NRFS];
-                        }
-                    }
+                    for (int i = 0; i < 4; ++i) in[s >> 1][8 * (s & 1) + 4 * (t >> 1) + i] = v[i];
                 }
             }
-            if constexpr (MODE == 2) {
-                if constexpr (RFS > 0) {
-                    if ((t & 1) && s < 8 - ROT) {                      // registers of k-step s (free since the step began), half t >> 1
-                        const f32x4 v = rf[(2 * (WRAP ? s : s + ROT) + (t >> 1)) * RFS];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) in[s >> 1][8 * (s & 1) + 4 * (t >> 1) + i] = v[i];
-                    }
-                }
-                if constexpr (NRFS > 0 && (MGN_RING_SIDE_EARLY & 1)) {
-                    if ((t & 1) && s >= 6) side[2 * (s - 6) + (t >> 1)] = rf_next[(2 * (s - 6) + (t >> 1)) * NRFS];
-                }
+            if constexpr (NRFS > 0) {
+                if ((t & 1) && s >= 6) side[2 * (s - 6) + (t >> 1)] = rf_next[(2 * (s - 6) + (t >> 1)) * NRFS];
             }
             if (it + 1 < 32) {
                 const int gn = WPL * LYR + (it + 1) / W;
@@ -362,57 +261,27 @@ DEVINL void sp_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
             }
             if (it % W == W - 2) {                                     // ... and store it: its buffer was last read in window gw - 1
                 const int b2 = (gw + 2) % 3;
-#if !(defined(MGN_WHATIF_LOADER) && (MGN_WHATIF_LOADER & 1))
 #pragma unroll
                 for (int i = 0; i < LPT; ++i) {
                     ring[b2 * BUF + i * NWV * 64 + tid - lane] = ld_m[i];
                     ring[b2 * BUF + W * 64 + i * NWV * 64 + tid - lane] = ld_l[i];
                 }
-#endif
             }
             if (s < 7) {
                 const int sn = s + 1;
                 sp_split_pair<RELU>(n.h[t], n.m[t], n.l[t], in[sn >> 1][8 * (sn & 1) + 2 * t], in[sn >> 1][8 * (sn & 1) + 2 * t + 1]);
             }
             const sp_bf16x8 bh = sp_op(p.h), bm = sp_op(p.m), bl = sp_op(p.l);
-#ifdef MGN_WHATIF_MFMA16    // diagnostic (wrong results): the same operand traffic and matrix time on v_mfma_f32_16x16x32_bf16 -- what the
-                            // other shape's clock is worth to this kernel before anyone re-writes its layouts
-#define RING_MFMA(A_, B_)                                                                                          \
-            do {                                                                                                   \
-                f32x4 c0_, c1_;                                                                                    \
-                _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { c0_[i_] = acc[t][i_]; c1_[i_] = acc[t][4 + i_]; } \
-                c0_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, c0_, 0, 0, 0);                                \
-                c1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, c1_, 0, 0, 0);                                \
-                _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { acc[t][i_] = c0_[i_]; acc[t][4 + i_] = c1_[i_]; } \
-            } while (0)
-#else
-#define RING_MFMA(A_, B_) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, acc[t], 0, 0, 0)
-#endif
-            RING_MFMA(sp_wop(a3), bh);      // small terms first
-            RING_MFMA(sp_wop(a2), bm);
-            RING_MFMA(sp_wop(a1), bl);
-            RING_MFMA(sp_wop(a2), bh);
-            RING_MFMA(sp_wop(a1), bm);
-            RING_MFMA(sp_wop(a1), bh);
-#undef RING_MFMA
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a3), bh, acc[t], 0, 0, 0);      // small terms first
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a2), bm, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a1), bl, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a2), bh, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a1), bm, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_wop(a1), bh, acc[t], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-#if !(defined(MGN_WHATIF_LOADER) && (MGN_WHATIF_LOADER & 2))
             if (it % W == W - 1) ring_barrier();                       // window closed: every wave has read it, window gw + 2 is in LDS
-#endif
         }
         p = n;
-        if constexpr (RFS > 0 && MODE == 0) {
-            // (the eight waves of a block run in lock-step: without a per-wave delay all sixteen gather instructions of a k-step
-            // reach the CU's memory pipeline at once; 64 line visits each)
-            if (s < 8 - ROT) {                                         // registers of k-step s <- pieces of k-step s + ROT
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const f32x4 v = rf[(2 * (s + ROT) + u) * RFS];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) in[s >> 1][8 * (s & 1) + 4 * u + i] = v[i];
-                }
-            }
-        }
     }
     if constexpr (RFS > 0 && !WRAP) {                                  // un-rotate: k-step u's pieces sit in the registers of k-step u - 2
         f32x16 r[4];
@@ -435,60 +304,19 @@ DEVINL void sp_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
                 asm volatile("v_fmac_f32_dpp %0, %0, %1 " CTRL " bound_ctrl:0" : "+v"(ACC[t_][k_]) : "v"(m_));               \
     } while (0)
 
-// the e tile leaves the chip once per step and comes back 3 GB later: cache policy of its stores / loads (A/B switches)
-#ifndef MGN_RING_ESTORE
-#define MGN_RING_ESTORE 0        // 0 plain, 1 nt, 2 sc1, 3 sc0 sc1 (2, 3: inline assembly -- A/B ONLY: the compiler does not see a store there, so neither its
-#endif                           // hazard recogniser nor its counters do; with 3 the eight-partition M-1M test lost reproducibility.  The product's write-through stores: MGN_RING_EST_BUF)
-#ifndef MGN_RING_ELOAD
-#define MGN_RING_ELOAD 0         // 0 plain, 1 nt
-#endif
 DEVINL void ring_store_e(f32x4* p, const f32x16 (&x)[4]) {
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
         f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = x[m >> 2][4 * (m & 3) + i];
-        f32x4* q = p + m * STRIDE_TILE;
-        if constexpr (MGN_RING_ESTORE == 1) __builtin_nontemporal_store(v, q);
-        else if constexpr (MGN_RING_ESTORE == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(q), "v"(v) : "memory");
-        else if constexpr (MGN_RING_ESTORE == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(q), "v"(v) : "memory");
-        else *q = v;
+        p[m * STRIDE_TILE] = v;
     }
 }
-DEVINL void ring_store_e_piece(f32x4* q, f32x4 v) {
-    if constexpr (MGN_RING_ESTORE == 1) __builtin_nontemporal_store(v, q);
-    else if constexpr (MGN_RING_ESTORE == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(q), "v"(v) : "memory");
-    else if constexpr (MGN_RING_ESTORE == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(q), "v"(v) : "memory");
-    else *q = v;
-}
-// store_frag with a cache policy: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1 (write-through at system scope: the line does not stay dirty in L2)
-template <int NT, int POL>
-DEVINL void store_frag_pol(f32x4* __restrict__ p, int stride, const f32x16 (&x)[NT]) {
-#pragma unroll
-    for (int m = 0; m < 4 * NT; ++m) {
-        f32x4 v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = x[m >> 2][4 * (m & 3) + i];
-        f32x4* q = p + m * stride;
-        if constexpr (POL == 1) __builtin_nontemporal_store(v, q);
-        else if constexpr (POL == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(q), "v"(v) : "memory");
-        else if constexpr (POL == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(q), "v"(v) : "memory");
-        else *q = v;
-    }
-}
-#ifndef MGN_AGG_STORE
-#define MGN_AGG_STORE 0          // k_edge_ring_h: policy of the aggregate / carry-row stores
-#endif
-#ifndef MGN_NODE_STORE
-#define MGN_NODE_STORE 0         // k_node_split_h: policy of the v stores
-#endif
-#ifndef MGN_PROJ_STORE
-#define MGN_PROJ_STORE 0         // k_project_split_h: policy of the P / Q stores
-#endif
 DEVINL void ring_load_e(f32x16 (&x)[4], const f32x4* p) {
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
-        const f32x4 v = MGN_RING_ELOAD ? __builtin_nontemporal_load(p + m * STRIDE_TILE) : p[m * STRIDE_TILE];
+        const f32x4 v = p[m * STRIDE_TILE];
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[m >> 2][4 * (m & 3) + i] = v[i];
     }
@@ -552,24 +380,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
     // lock-step: every wave of the block runs as many tiles as its wave 0 (the longest walk); padding tiles compute, store nothing
     TileWalk tw0(a.ntiles, 0), tw(a.ntiles, wave);
     if (tw0.tile >= tw0.end) return;
-#ifndef MGN_RING_PHASES
 #define MGN_RING_PHASES 2
-#endif
-#ifndef MGN_RING_L3_WRAP
-#define MGN_RING_L3_WRAP 0       // 1: layer 3's refill without a side buffer (sp_layer_ring WRAP)
-#endif
-#ifndef MGN_RING_QPSTREAM
-#define MGN_RING_QPSTREAM 0      // 1: P[s] / Q[r] rows stream through layer 1 (sp_layer_ring QP): no Q gather / side buffer in the turnover
-#endif
-#ifndef MGN_RING_ENEXT_TAIL
-#define MGN_RING_ENEXT_TAIL 0    // where the last two k-steps of the next tile's e are requested: 0 = at the start of the epilogue (ahead of the e stores), 1 = at its end
-#endif
-#ifndef MGN_RING_ENEXT
-#define MGN_RING_ENEXT 1         // 1 (default): layer 3's refill fetches the NEXT tile's e, this tile's is read again in the epilogue; 2: and stored last (spills); 0: round 3's order
-#endif
-#ifndef MGN_RING_PHASE_UNITS
 #define MGN_RING_PHASE_UNITS 10
-#endif
     const int iters = (tw0.end - tw0.tile + tw0.stride - 1) / tw0.stride;
     // Blocks of one launch start together and keep the same period, so the memory phases (epilogues) of all CUs coincide.  Long
     // launches start every second block of an XCD half a period (10 x 4 096 cycles) late: 3.454 -> 3.413 ms on M-1M (four or eight
@@ -586,19 +398,15 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
     EdgeIdx ix = load_edge_idx_nb(a.snd, a.rcv, a.E, clamp(tw.tile), lane0 & 31);
     {
         const int h0 = lane0 >> 5;
-#if !MGN_RING_QPSTREAM
         load_frag<NT>(acc, prow_ptr(a.Q, ix.r >= 0 ? ix.r : 0, L, h0), STRIDE_PROW);
-#endif
         load_frag<NT>(y, tile_ptr(a.Elat, clamp(tw.tile), L, lane0), STRIDE_TILE);
     }
     f32x4 side[4];               // refill side buffer (sp_layer_ring): the first two k-steps of the P rows / of the e tile
-#if !MGN_RING_QPSTREAM
     {
         const f32x4* p0 = prow_ptr(a.P, ix.s, L, lane0 >> 5);
 #pragma unroll
         for (int m = 0; m < 4; ++m) side[m] = p0[m * STRIDE_PROW];
     }
-#endif
     int stamp_tile = 0;
     (void)stamp_tile;
     for (int j = 0; j < iters; ++j, ++stamp_tile) {
@@ -611,62 +419,30 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
         const int r = ix.r >= 0 ? ix.r : 0;
         f32x4* etile = tile_ptr(a.Elat, tile, L, lane);
         u32x4* ring = ringbase + lane;
-#ifdef MGN_WHATIF          // diagnostic builds (wrong results): which memory stream costs what
-        const f32x4* etile_rd = (MGN_WHATIF & 1) ? tile_ptr(a.Elat, a.tile0 + wave, L, lane) : etile;
-        const int ps_row = (MGN_WHATIF & 4) ? (lane & 31) : ix.s;
-#else
-        const f32x4* etile_rd = etile;
-        const int ps_row = ix.s;
-#endif
         STAMP(0);
         __builtin_amdgcn_s_setprio(0);
         RingFrag nx = ring_first<W, 0>(l1h, ring, lane);
         // layer 1 (edge part): y = e tile in, P[s] out (acc entered with Q[r], which carries b1)
-#if MGN_RING_QPSTREAM
-        zero_frag<NT>(acc);
-        sp_layer_ring<W, 0, false, 0, 0, NWV, false, true>(acc, y, l1h, l2h, ring, src, nx, lane, tid, nullptr, nullptr, nullptr,
-                                                          prow_ptr(a.P, ps_row, L, h), prow_ptr(a.Q, r, L, h));
-#else
-        sp_layer_ring<W, 0, false, STRIDE_PROW, 0, NWV>(acc, y, l1h, l2h, ring, src, nx, lane, tid, prow_ptr(a.P, ps_row, L, h), side);
+        sp_layer_ring<W, 0, false, STRIDE_PROW, 0, NWV>(acc, y, l1h, l2h, ring, src, nx, lane, tid, prow_ptr(a.P, ix.s, L, h), side);
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] += y[t];
-#endif
         CST(1);
         tab_frag<NT>(y, tb + T_B2 * L, h);
         CST(2);
-#if MGN_RING_L3_WRAP || MGN_RING_ENEXT
         sp_layer_ring<W, 1, true, 0, 0, NWV>(y, acc, l2h, l3h, ring, src, nx, lane, tid);   // layer 2 (ReLU folded into the split)
-#else
-        sp_layer_ring<W, 1, true, 0, STRIDE_TILE, NWV>(y, acc, l2h, l3h, ring, src, nx, lane, tid, nullptr, side, etile_rd);   // layer 2 (ReLU folded into the split)
-#endif
         CST(3);
         tab_frag<NT>(acc, tb + T_B3 * L, h);
         CST(4);
         // layer 3: y = layer 2's output in, the e tile (for the residual) out
-#if MGN_RING_ENEXT
         // ... or the NEXT tile's e: nothing of the turnover then waits behind this tile's e stores (s_waitcnt vmcnt retires in order)
-#if defined(MGN_WHATIF) && (MGN_WHATIF & 8)
-        sp_layer_ring<W, 2, true, STRIDE_TILE, 0, NWV, true>(acc, y, l3h, l1h, ring, src, nx, lane, tid, tile_ptr(a.Elat, a.tile0 + wave, L, lane));
-#else
         sp_layer_ring<W, 2, true, STRIDE_TILE, 0, NWV, true>(acc, y, l3h, l1h, ring, src, nx, lane, tid, tile_ptr(a.Elat, nxt, L, lane));
-#endif
-#elif MGN_RING_L3_WRAP
-        sp_layer_ring<W, 2, true, STRIDE_TILE, 0, NWV, true>(acc, y, l3h, l1h, ring, src, nx, lane, tid, etile_rd);
-        ring_load_e_tail(y, etile_rd);
-#else
-        sp_layer_ring<W, 2, true, STRIDE_TILE, 0, NWV>(acc, y, l3h, l1h, ring, src, nx, lane, tid, etile_rd, side);
-#endif
         CST(5);
         EST(1);
         PHASE_FENCE();
         __builtin_amdgcn_s_setprio(MGN_PRIO);
-#if MGN_RING_ENEXT
         f32x16 er[NT];               // this tile's e again, for the residual (y holds the next tile's): arrives during the LayerNorm
-        ring_load_e(er, etile_rd);
-#if MGN_RING_ENEXT_TAIL == 0
+        ring_load_e(er, etile);
         ring_load_e_tail(y, tile_ptr(a.Elat, nxt, L, lane));         // k-steps 6 and 7 of the next tile's e
-#endif
-#endif
         {   // LayerNorm (layer_norm_frag of frag.hpp in four slices): acc = e'
             constexpr float invL = 1.0f / 128;
             float sm = 0.f;
@@ -702,36 +478,11 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
         }
         CST(6);
         EST(2);
-#if MGN_RING_ENEXT
 #pragma unroll
         for (int t = 0; t < NT; ++t) er[t] += acc[t];                // e <- e + e'
-#if MGN_RING_ENEXT == 1
-#if defined(MGN_WHATIF) && (MGN_WHATIF & 2)
-        if (valid && a.E < 0) ring_store_e(etile, er);
-#elif defined(MGN_WHATIF) && (MGN_WHATIF & 64)          // the e stores issued, but into one tile per wave (no HBM traffic)
-        if (valid) ring_store_e(tile_ptr(a.Elat, a.tile0 + wave, L, lane), er);
-#else
         if (valid) ring_store_e(etile, er);                          // padding rows / tiles store nothing
-#endif
-#endif
         CST(7);
         EST(3);
-#else
-#pragma unroll
-        for (int t = 0; t < NT; ++t) y[t] += acc[t];                 // e <- e + e'
-#if defined(MGN_WHATIF) && (MGN_WHATIF & 2)
-        if (valid && a.E < 0) store_frag<NT>(etile, STRIDE_TILE, y);
-#else
-        if (valid) ring_store_e(etile, y);                           // padding rows / tiles store nothing
-#endif
-        CST(7);
-        EST(3);
-#if defined(MGN_WHATIF) && (MGN_WHATIF & 8)
-        load_frag<NT>(y, tile_ptr(a.Elat, a.tile0 + wave, L, lane), STRIDE_TILE);
-#else
-        ring_load_e(y, tile_ptr(a.Elat, nxt, L, lane));              // the next tile's e, ahead of everything else of the turnover
-#endif
-#endif
         const int reff = ix.r >= 0 ? r : (-4 - c);
         const int rprev = __shfl_up(reff, 1, 32);
         const int rnext = __shfl_down(reff, 1, 32);
@@ -757,37 +508,11 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
         const bool sr = (c == 31) && (ix.r_after == reff);
         const bool to_carry = sl || sr;
         f32x4* dst = to_carry ? prow_ptr(a.CARRY, (int64_t)2 * tile + (sl ? 0 : 1), L, h) : tile_ptr(a.AGG, r >> 5, L, 32 * h + (r & 31));
-#if defined(MGN_WHATIF) && (MGN_WHATIF & 32)
-        if (tail && a.E < 0) store_frag<NT>(dst, to_carry ? STRIDE_PROW : STRIDE_TILE, acc);
-#elif defined(MGN_WHATIF) && (MGN_WHATIF & 128)         // aggregate rows stored row-major (4 lines per row instead of 32)
-        if (tail) store_frag<NT>(to_carry ? dst : prow_ptr(a.AGG, r, L, h), STRIDE_PROW, acc);
-#else
         if (tail) store_frag<NT>(dst, to_carry ? STRIDE_PROW : STRIDE_TILE, acc);
-#endif
         EST(6);
         PHASE_FENCE();
         // turnover: the next tile's layer-1 accumulator starts from Q[r] (P[s] arrives during the layer)
-#if MGN_RING_QPSTREAM
-        // (nothing to request: the rows stream through layer 1)
-#elif defined(MGN_WHATIF) && (MGN_WHATIF & 16)
-        load_frag<NT>(acc, prow_ptr(a.Q, lane & 31, L, h), STRIDE_PROW);
-#else
         load_frag<NT>(acc, prow_ptr(a.Q, ixn.r >= 0 ? ixn.r : 0, L, h), STRIDE_PROW);
-#endif
-#if MGN_RING_REFILL_AT_REQUEST != 0 && (MGN_RING_SIDE_EARLY & 2) && !MGN_RING_QPSTREAM
-        {
-            const f32x4* pn = prow_ptr(a.P, ixn.s, L, h);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) side[m] = pn[m * STRIDE_PROW];
-        }
-#endif
-#if MGN_RING_ENEXT && MGN_RING_ENEXT_TAIL == 1
-        ring_load_e_tail(y, tile_ptr(a.Elat, nxt, L, lane));         // k-steps 6 and 7 of the next tile's e: first needed late in its layer 1
-#endif
-#if MGN_RING_ENEXT == 2
-        PHASE_FENCE();
-        if (valid) ring_store_e(etile, er);                          // the e stores last: every request of the turnover is older than they are
-#endif
         EST(7);
         ix = ixn;
         tw.tile += tw.stride;
@@ -808,9 +533,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
 //   * accumulators start from zero (the first MFMA of a block takes the constant), except layer 1's: Q[r] scaled INTO the
 //     accumulator's units (64 multiplications; P[s] is added by the FMA that un-scales), since nothing has 64 registers for Q.
 // ================================================================================================
-#ifndef MGN_RINGH_AHEAD
 #define MGN_RINGH_AHEAD 2        // windows between a window's request and its first use: 2 (default) = three buffers, stored in the window it is
-#endif                           // requested in (k_edge_ring's scheme); 3 = four buffers, stored one window LATER (below): 2.401 vs 2.408 ms, nothing
 template <int W>
 struct Rh {
     static constexpr int WPL = 32 / W;          // windows per layer
@@ -842,9 +565,9 @@ struct RhSrc {
 // One L x L layer (sp_layer_ring with two pieces).  sx: the row's scale; FIN / cfin / btab: see h2_split_pair (btab = the bias table of
 // the layer BEFORE, lane half's offset included).  Refill: schedule 2 of sp_layer_ring (one request every second step; WRAP: no
 // rotation, the last two k-steps' pieces are the caller's).
-// RFPOL >= 0 (WRAP refill only): the refill's requests as buffer loads with these cache-policy bits (rfb: the tile's descriptor; lane offset
-// 16 lane, piece m at m KiB) instead of plain loads through `rf`.
-template <int W, int LYR, int FIN, int RFS = 0, int NWV = 8, bool WRAP = false, int RFPOL = -1>
+// WRAP refill: its requests as buffer loads (rfb: the tile's descriptor; lane offset 16 lane, piece m at m KiB) instead of plain loads
+// through `rf`.
+template <int W, int LYR, int FIN, int RFS = 0, int NWV = 8, bool WRAP = false>
 DEVINL void h2_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, const u32x4* hi_next, u32x4* ring, const RhSrc& src,
                           RhFrag& nx, RhPend<W / NWV>& pend, int lane, int tid, float sx, float cfin = 0.f, const float* btab = nullptr,
                           const f32x4* rf = nullptr, const N16Buf* rfb = nullptr) {
@@ -879,19 +602,17 @@ DEVINL void h2_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
             const int it = 4 * s + t;
             const int gw = WPL * LYR + it / W;                        // global window of this step
             const u32x4 a1 = nx.h, a2 = nx.l;
-#ifndef MGN_WHATIF_FREE        // (MGN_WHATIF_FREE = n: timing-only build, wrong results -- no ring traffic, no barriers, waves 4..7 start n x 8 k cycles late)
             if (it % W == 0) {                                         // request window gw + AHEAD
                 const int g2 = (gw + AHEAD) % NW, l2 = g2 / WPL, w2 = g2 % WPL;
 #pragma unroll
                 for (int i = 0; i < LPT; ++i)
                     pend.v[AHEAD == 2 ? 0 : gw % 2][i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(src.lo[l2] + w2 * W * 64 + i * NWV * 64) + voff);
             }
-#endif
             if constexpr (RFS > 0) {
                 if ((t & 1) && s < 8 - ROT) {                          // registers of k-step s (free since the step began), half t >> 1
                     f32x4 v;
-                    if constexpr (WRAP && RFPOL >= 0) v = n16_ld_pol<RFPOL>(*rfb, (unsigned)lane * 16u, (2 * s + (t >> 1)) * 1024);
-                    else v = rf[(2 * (WRAP ? s : s + ROT) + (t >> 1)) * RFS];
+                    if constexpr (WRAP) v = n16_ld(*rfb, (unsigned)lane * 16u, (2 * s + (t >> 1)) * 1024);
+                    else v = rf[(2 * (s + ROT) + (t >> 1)) * RFS];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) in[s >> 1][8 * (s & 1) + 4 * (t >> 1) + i] = v[i];
                 }
@@ -903,14 +624,12 @@ DEVINL void h2_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
             } else if (LYR < 2) {
                 nx = rh_first<W, (LYR + 1) % 3>(hi_next, ring, lane);   // (that window was written two windows ago)
             }
-#ifndef MGN_WHATIF_FREE
             if (it % W == W - 2) {                                     // store window gw + 2 (AHEAD 3: requested in window gw - 1): its buffer was
                 const int b2 = (gw + 2) % NB;                          // last read as window gw + 2 - NB
                 const int slot = AHEAD == 2 ? 0 : (gw + 1) % 2;      // (AHEAD 2: a window is stored in the window it is requested in -- one slot)
 #pragma unroll
                 for (int i = 0; i < LPT; ++i) ring[b2 * BUF + i * NWV * 64 + tid - lane] = pend.v[slot][i];
             }
-#endif
             if (s < 7) {
                 const int sn = s + 1;
                 const f32x2 b = bias(sn, t);
@@ -921,9 +640,7 @@ DEVINL void h2_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a1), bl, acc[t], 0, 0, 0);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a1), bh, acc[t], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-#ifndef MGN_WHATIF_FREE
             if (it % W == W - 1) ring_barrier();                       // window closed: every wave has read it, window gw + 2 is in LDS
-#endif
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -943,33 +660,8 @@ DEVINL void h2_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], const u32x4* hi, co
     }
 }
 
-#ifndef MGN_RINGH_PHASE_UNITS
 #define MGN_RINGH_PHASE_UNITS 6     // half a period of k_edge_ring_h in 4 096-cycle units (k_edge_ring: 10)
-#endif
-#ifndef MGN_RINGH_ESTORE_LAST
-#define MGN_RINGH_ESTORE_LAST 0   // (1 spills 64 registers in the epilogue: not run) 1: this tile's e stores behind the next tile's Q request (0: right behind the residual, k_edge_ring's order)
-#endif
-#ifndef MGN_RING_EST_BUF
-#define MGN_RING_EST_BUF 0       // k_edge_ring_h (with MGN_RINGH_STORE_INTERLEAVE): the e stores as buffer stores with these policy bits (17 = sc0 sc1: write-through);
-                                 // 0: plain global stores.  As compiler-visible instructions write-through is worth nothing (2.299 -> 2.295 ms): the 1.5 % the
-                                 // inline-assembly form showed came with a lost reproducibility test (MGN_RING_ESTORE above)
-#endif
-#ifndef MGN_RING_ENEXT_POL
-#define MGN_RING_ENEXT_POL 0     // k_edge_ring_h: the next tile's e requests as buffer loads (a scalar descriptor + one lane offset: no 64-bit address arithmetic
-                                 // inside layer 3) with these cache-policy bits (1 sc0, 2 nt, 16 sc1; 0 = plain: 2.337 -> 2.304 ms, the policies add nothing); -1: global loads
-#endif
-#ifndef MGN_RING_ER_POL
-#define MGN_RING_ER_POL -1       // ... of the second read of this tile's e
-#endif
-#ifndef MGN_RINGH_STORE_INTERLEAVE
-#define MGN_RINGH_STORE_INTERLEAVE 1   // 1: a block's residual + e stores right behind its LayerNorm (0: all sixteen stores behind the LayerNorm)
-#endif
-#ifndef MGN_RINGH_SCAN_SKIP
-#define MGN_RINGH_SCAN_SKIP 1     // the scan's row_shr:8 level behind a wave-uniform branch (taken only by tiles with a receiver run of nine edges or more inside a 16-lane row)
-#endif
-#ifndef MGN_RINGH_W
 #define MGN_RINGH_W 8            // steps per window of k_edge_ring_h (8: 12 barriers per tile; 16: 6)
-#endif
 template <int NWV>
 __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArgs a) {
     constexpr int NT = 4, L = 128, PC = 16384;
@@ -1030,10 +722,6 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
     }
     int stamp_tile = 0;
     (void)stamp_tile;
-#ifdef MGN_WHATIF_FREE
-    if (wave >= NWV / 2)
-        for (int i = 0; i < MGN_WHATIF_FREE; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
     for (int j = 0; j < iters; ++j, ++stamp_tile) {
         OPAQUE_LANE();
         const bool on = tw.tile < tw.end;
@@ -1056,12 +744,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
 #pragma unroll
                 for (int k = 0; k < 16; ++k) acc[t][k] *= cinv;
         }
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 4)      // diagnostic builds (wrong results): which memory stream of this kernel costs what
-        const int ps_row = lane & 31;
-#else
-        const int ps_row = ix.s;
-#endif
-        h2_layer_ring<W, 0, 0, STRIDE_PROW, NWV>(acc, y, l1h, l2h, ring, src, nx, pend, lane, tid, x1.s, 0.f, nullptr, prow_ptr(a.P, ps_row, L, h));
+        h2_layer_ring<W, 0, 0, STRIDE_PROW, NWV>(acc, y, l1h, l2h, ring, src, nx, pend, lane, tid, x1.s, 0.f, nullptr, prow_ptr(a.P, ix.s, L, h));
         {
             const float c1 = x1.rs * rsw1;
 #pragma unroll
@@ -1080,53 +763,21 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
         zero_frag<NT>(acc);
         CST(4);
         // layer 3: y = layer 2's accumulators in (bias, un-scaling and ReLU in the split), the NEXT tile's e out
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 16)
-        const f32x4* enext = tile_ptr(a.Elat, a.tile0 + wave, L, lane);
-#else
         const f32x4* enext = tile_ptr(a.Elat, nxt, L, lane);
-#endif
-#if MGN_RING_ENEXT_POL >= 0
         const N16Buf enb = n16_buf(a.Elat + (int64_t)nxt * (TILE * L), TILE * L * 4);      // (nxt is wave-uniform)
-        h2_layer_ring<W, 2, 2, STRIDE_TILE, NWV, true, MGN_RING_ENEXT_POL>(acc, y, l3h, l1h, ring, src, nx, pend, lane, tid, x3.s, c2, tb + T_B2 * L + 4 * h, enext, &enb);
-#else
-        h2_layer_ring<W, 2, 2, STRIDE_TILE, NWV, true>(acc, y, l3h, l1h, ring, src, nx, pend, lane, tid, x3.s, c2, tb + T_B2 * L + 4 * h, enext);
-#endif
+        h2_layer_ring<W, 2, 2, STRIDE_TILE, NWV, true>(acc, y, l3h, l1h, ring, src, nx, pend, lane, tid, x3.s, c2, tb + T_B2 * L + 4 * h, enext, &enb);
         CST(5);
         EST(1);
         PHASE_FENCE();
         __builtin_amdgcn_s_setprio(MGN_PRIO);
         f32x16 er[NT];               // this tile's e again, for the residual (y holds the next tile's): arrives during the LayerNorm
-#if MGN_RING_EST_BUF
-        const N16Buf esb = n16_buf(a.Elat + (int64_t)tile * (TILE * L), TILE * L * 4);
-#endif
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 1)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) er[t] = acc[t];
-#else
-#if MGN_RING_ER_POL >= 0
-        {
-            const N16Buf erb = n16_buf(a.Elat + (int64_t)tile * (TILE * L), TILE * L * 4);
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const f32x4 v = n16_ld_pol<MGN_RING_ER_POL>(erb, (unsigned)lane * 16u, m * 1024);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) er[m >> 2][4 * (m & 3) + i] = v[i];
-            }
-        }
-#else
         ring_load_e(er, etile);
-#endif
-#endif
-#if MGN_RING_ENEXT_POL >= 0
 #pragma unroll
         for (int m = 12; m < 16; ++m) {
-            const f32x4 v = n16_ld_pol<MGN_RING_ENEXT_POL>(enb, (unsigned)lane * 16u, m * 1024);
+            const f32x4 v = n16_ld(enb, (unsigned)lane * 16u, m * 1024);
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[3][4 * (m & 3) + i] = v[i];
         }
-#else
-        ring_load_e_tail(y, enext);                                  // k-steps 6 and 7 of the next tile's e
-#endif
         {   // bias + un-scaling of layer 3, then LayerNorm: acc = e'
             constexpr float invL = 1.0f / 128;
             const float c3 = x3.rs * rsw3;
@@ -1168,47 +819,22 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
 #pragma unroll
                     for (int i = 0; i < 4; ++i) acc[t][4 * g + i] = acc[t][4 * g + i] * rstd * gv[i] + bv[i];
                 }
-#if MGN_RINGH_STORE_INTERLEAVE && !MGN_RINGH_ESTORE_LAST && !defined(MGN_WHATIF_H)
                 // the block's residual and its four stores right behind its LayerNorm: the stores of the first blocks are on their way while the
                 // others are still normalised
                 er[t] += acc[t];
-#if MGN_RING_EST_BUF
-                {   // as buffer stores (compiler-visible instructions, unlike ring_store_e_piece's inline assembly: hazards and counters are the compiler's)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        f32x4 v;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) v[i] = er[t][4 * g + i];
-                        if (valid) n16_st_pol<MGN_RING_EST_BUF>(esb, (unsigned)lane * 16u, (4 * t + g) * 1024, v);
-                    }
-                }
-#else
                 if (valid) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         f32x4 v;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = er[t][4 * g + i];
-                        ring_store_e_piece(etile + (4 * t + g) * STRIDE_TILE, v);
+                        etile[(4 * t + g) * STRIDE_TILE] = v;
                     }
                 }
-#endif
-#endif
             }
         }
         CST(6);
         EST(2);
-#if !(MGN_RINGH_STORE_INTERLEAVE && !MGN_RINGH_ESTORE_LAST && !defined(MGN_WHATIF_H))
-#pragma unroll
-        for (int t = 0; t < NT; ++t) er[t] += acc[t];                // e <- e + e'
-#endif
-#if !MGN_RINGH_ESTORE_LAST && !(MGN_RINGH_STORE_INTERLEAVE && !defined(MGN_WHATIF_H))
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 2)
-        if (valid && a.E < 0) ring_store_e(etile, er);
-#else
-        if (valid) ring_store_e(etile, er);                          // padding rows / tiles store nothing
-#endif
-#endif
         CST(7);
         EST(3);
         const int reff = ix.r >= 0 ? r : (-4 - c);
@@ -1226,10 +852,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
         RG_SCAN_LEVEL(acc, c1, "row_shr:1 row_mask:0xf bank_mask:0xf");
         RG_SCAN_LEVEL(acc, c2s, "row_shr:2 row_mask:0xf bank_mask:0xf");
         RG_SCAN_LEVEL(acc, c4, "row_shr:4 row_mask:0xf bank_mask:0xf");
-#if MGN_RINGH_SCAN_SKIP
         // receiver runs of nine edges and more are rare on a mesh (M-1M: none): their level only where a lane of the tile needs it
         if (__builtin_amdgcn_ballot_w64(c8) != 0)
-#endif
         {
             RG_SCAN_LEVEL(acc, c8, "row_shr:8 row_mask:0xf bank_mask:0xf");
         }
@@ -1242,31 +866,11 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
         const bool sr = (c == 31) && (ix.r_after == reff);
         const bool to_carry = sl || sr;
         f32x4* dst = to_carry ? prow_ptr(a.CARRY, (int64_t)2 * tile + (sl ? 0 : 1), L, h) : tile_ptr(a.AGG, r >> 5, L, 32 * h + (r & 31));
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 32)
-        if (tail && a.E < 0) store_frag<NT>(dst, to_carry ? STRIDE_PROW : STRIDE_TILE, acc);
-#else
-        if (tail) store_frag_pol<NT, MGN_AGG_STORE>(dst, to_carry ? STRIDE_PROW : STRIDE_TILE, acc);
-#endif
+        if (tail) store_frag<NT>(dst, to_carry ? STRIDE_PROW : STRIDE_TILE, acc);
         EST(6);
         PHASE_FENCE();
         // turnover: the next tile's layer-1 accumulator starts from Q[r] (P[s] arrives during the layer)
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 64)
-        zero_frag<NT>(acc);                                          // (no Q request at all: what the wait for it behind the stores costs)
-#elif defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 8)
-        load_frag<NT>(acc, prow_ptr(a.Q, lane & 31, L, h), STRIDE_PROW);
-#else
         load_frag<NT>(acc, prow_ptr(a.Q, ixn.r >= 0 ? ixn.r : 0, L, h), STRIDE_PROW);
-#endif
-#if MGN_RINGH_ESTORE_LAST
-        // the e stores LAST: s_waitcnt vmcnt retires in order and counts stores, so everything the next tile waits for first (its Q rows)
-        // is requested ahead of them; they drain under the next tile's layer 1
-        PHASE_FENCE();
-#if defined(MGN_WHATIF_H) && (MGN_WHATIF_H & 2)
-        if (valid && a.E < 0) ring_store_e(etile, er);
-#else
-        if (valid) ring_store_e(etile, er);                          // padding rows / tiles store nothing
-#endif
-#endif
         EST(7);
         ix = ixn;
         tw.tile += tw.stride;
@@ -1282,16 +886,9 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
 // requests loses its sixteen largest, and a block's LDS prologue is 28 KiB instead of 150.
 // ================================================================================================
 constexpr int HS_W = 4;
-#ifndef MGN_HS_PREMUL
-#define MGN_HS_PREMUL 0          // 1: the gathered Q rows are put into the accumulator's units block by block inside layer 1's first k-step (measured: no gain, 2.174 vs 2.165 ms)
-#endif
-#ifndef MGN_HS_REQ_STEP
 #define MGN_HS_REQ_STEP 0        // step of window gw (0 .. 3) at which window gw + MGN_HS_AHEAD is requested
-#endif
-#ifndef MGN_HS_AHEAD
 #define MGN_HS_AHEAD 4           // 3: two requests in flight (a request 7 steps before its LDS store), 4: three (11 steps).  M-1M: 2.336 (k_edge_ring_h) ->
                                  // 2.340 with the request in the window of its store -> 2.288 / 2.260 / 2.245 / 2.250 at AHEAD 3 (request at step 2 / 0), 4, 5
-#endif
 template <int NCH>                              // NCH: chains (L x L products) per tile, all through the one ring
 struct RsT {
     static constexpr int W = HS_W;
@@ -1506,9 +1103,6 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
         // layer 1 (edge part): y = e tile in, P[s] out; acc enters with Q[r] (which carries b1), put into the accumulator's units
         const H2Scale x1 = h2_scale(h2_rowmax<true>(y));
         const int ps_row = ix.s;
-#if MGN_HS_PREMUL
-        hs_layer_ring<0, 0, STRIDE_PROW, NWV, false, 3, true>(acc, y, ring, src, nx, pend, lane, tid, x1.s, 0.f, nullptr, prow_ptr(a.P, ps_row, L, h), nullptr, 0, x1.s * sw1);
-#else
         {
             const float cinv = x1.s * sw1;
 #pragma unroll
@@ -1517,7 +1111,6 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
                 for (int k = 0; k < 16; ++k) acc[t][k] *= cinv;
         }
         hs_layer_ring<0, 0, STRIDE_PROW, NWV>(acc, y, ring, src, nx, pend, lane, tid, x1.s, 0.f, nullptr, prow_ptr(a.P, ps_row, L, h));
-#endif
         {
             const float c1 = x1.rs * rsw1;
 #pragma unroll
@@ -1651,27 +1244,10 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
 // TWO: a second edge set -- its aggregate is one more layer-1 block (split[6] = W1[2L:3L]); LDS is full with four hi pieces, so all
 // three pieces of that chunk stream from L2 (rings four groups deep: the same 48 ring registers as two rings of six).
 // ================================================================================================
-// priorities of the node-side split kernels: inside the MFMA chains the older wave of a SIMD (waves 0-3) and the younger one (4-7) may
-// differ, so that the pipe's arbiter pulls the two waves of a SIMD apart instead of letting them share every chain and then both wait
-// in their memory phases at once
-#ifndef MGN_NODE_CPRIO_OLD
-#define MGN_NODE_CPRIO_OLD 0
-#endif
-#ifndef MGN_NODE_CPRIO_YOUNG
-#define MGN_NODE_CPRIO_YOUNG 0
-#endif
-#ifndef MGN_NODE_MPRIO
+// priorities of the node-side split kernels: 0 inside the MFMA chains, MGN_NODE_MPRIO outside them (different chain priorities for the
+// older and the younger wave of a SIMD: docs/experiments.md)
 #define MGN_NODE_MPRIO MGN_PRIO
-#endif
-#define NODE_CHAIN_PRIO()                                                        \
-    do {                                                                         \
-        if (MGN_NODE_CPRIO_OLD == MGN_NODE_CPRIO_YOUNG) __builtin_amdgcn_s_setprio(MGN_NODE_CPRIO_OLD); \
-        else if (wave < 4) __builtin_amdgcn_s_setprio(MGN_NODE_CPRIO_OLD);       \
-        else __builtin_amdgcn_s_setprio(MGN_NODE_CPRIO_YOUNG);                   \
-    } while (0)
-#ifndef MGN_SP2_D3
 #define MGN_SP2_D3 4
-#endif
 template <bool TWO>
 __global__ __launch_bounds__(512, 2) void k_node_split(const NodeArgs a) {
     constexpr int NT = 4, L = 128, PC = 16384, D = MGN_SP2_D;
@@ -1711,18 +1287,8 @@ __global__ __launch_bounds__(512, 2) void k_node_split(const NodeArgs a) {
         const bool valid = n < a.n;
         const int nn = valid ? n : 0;
         f32x4* vtile = tile_ptr(a.V, tile, L, lane);
-        NODE_CHAIN_PRIO();
+        __builtin_amdgcn_s_setprio(0);
         tab_frag<NT>(acc, tb + T_B1 * L, h);
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 1)   // diagnostic (wrong results): every piece from LDS
-        sp_layer_otf<false, false, false, D>(acc, x, lvh, lvh, lvh, lane);
-        LOAD_AGGREGATE(NT, x, a.rowptr, a.AGG, a.CARRY, a.zero_row);
-        sp_layer_otf<false, false, false, D>(acc, x, lah, lah, lah, lane);
-        tab_frag<NT>(x, tb + T_B2 * L, h);
-        sp_layer_otf<false, false, true, D>(x, acc, l2h, l2h, l2h, lane);
-        tab_frag<NT>(acc, tb + T_B3 * L, h);
-        sp_layer_otf<false, false, true, D>(acc, x, l3h, l3h, l3h, lane);
-#else
-#if MGN_SP_CARRY
         // the weight rings are carried from chain to chain: every chain requests the first fragments of the next one in its last steps
         constexpr int O1 = 32 % D, O2 = 64 % D, O3 = 96 % D;
         SpRing<D> rg;
@@ -1744,52 +1310,16 @@ __global__ __launch_bounds__(512, 2) void k_node_split(const NodeArgs a) {
             tab_frag<NT>(acc, tb + T_B3 * L, h);
             sp_layer_otf<true, true, true, D, false, O3, true, false>(acc, x, l3h, g3 + 2048, g3 + 4096, lane, &rg);                  // layer 3
         }
-#else
-        sp_layer_otf<true, true, false, D>(acc, x, lvh, gv + 2048, gv + 4096, lane);      // layer 1, node part
-        LOAD_AGGREGATE(NT, x, a.rowptr, a.AGG, a.CARRY, a.zero_row);
-        sp_layer_otf<true, true, false, D>(acc, x, lah, ga + 2048, ga + 4096, lane);      // layer 1, aggregate part
-        if constexpr (TWO) {                                                              // layer 1, the second edge set's aggregate
-            const u32x4* gb = reinterpret_cast<const u32x4*>(a.split[6]);
-            LOAD_AGGREGATE(NT, x, a.rowptr2, a.AGG2, a.CARRY2, a.zero_row2);
-            sp_layer_otf<true, true, false, MGN_SP2_D3, true>(acc, x, gb, gb + 2048, gb + 4096, lane);
-        }
-        tab_frag<NT>(x, tb + T_B2 * L, h);
-        sp_layer_otf<true, true, true, D>(x, acc, l2h, g2 + 2048, g2 + 4096, lane);       // layer 2 (ReLU folded into the split)
-        tab_frag<NT>(acc, tb + T_B3 * L, h);
-        sp_layer_otf<true, true, true, D>(acc, x, l3h, g3 + 2048, g3 + 4096, lane);       // layer 3
-#endif
-#endif
         PHASE_FENCE();
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 2)   // diagnostic: the residual reads one cached tile per wave
-        load_frag<NT>(x, tile_ptr(a.V, wave, L, lane), STRIDE_TILE);
-#else
         load_frag<NT>(x, vtile, STRIDE_TILE);                        // v again, for the residual
-#endif
         layer_norm_frag<NT>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
 #pragma unroll
         for (int t = 0; t < NT; ++t) x[t] += acc[t];                 // v <- v + v'
-#if MGN_NODE_VNEXT_FIRST
-        // the next tile's V is requested AHEAD of this tile's V stores, into the registers of v' (dead from here): s_waitcnt vmcnt
-        // retires in order and counts stores, so a load requested behind the sixteen stores is not back before they are acknowledged
-        // (k_edge_ring's turnover, docs/experiments.md round 4)
-        PHASE_FENCE();
-        if (has_next) load_frag<NT>(acc, tile_ptr(a.V, next, L, lane), STRIDE_TILE);
-        PHASE_FENCE();
-#endif
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 4)   // diagnostic: no store
-        if (valid && a.n < 0) store_frag<NT>(vtile, STRIDE_TILE, x);
-#else
         if (valid) store_frag<NT>(vtile, STRIDE_TILE, x);
-#endif
         if (!has_next) break;
         PHASE_FENCE();
-#if MGN_NODE_VNEXT_FIRST
-#pragma unroll
-        for (int t = 0; t < NT; ++t) x[t] = acc[t];
-#else
         load_frag<NT>(x, tile_ptr(a.V, next, L, lane), STRIDE_TILE);
-#endif
         tw.tile = next;
     }
 }
@@ -1828,55 +1358,20 @@ __global__ __launch_bounds__(512, 2) void k_project_split(const NodeArgs a) {
         const int n = tile * TILE + c;
         const bool valid = n < a.n;
         const int nn = valid ? n : 0;
-        NODE_CHAIN_PRIO();
+        __builtin_amdgcn_s_setprio(0);
         zero_frag<NT>(acc);
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 1)
-        sp_layer_otf<false, false, false, D1>(acc, x, lph, lpm, lpm, lane);
-#else
-#if MGN_SP_CARRY
         SpRing<D1> rg;                                               // WP's chain requests the first lo fragments of WQ in its last steps
         sp_layer_otf<false, true, false, D1, false, 0, false, true>(acc, x, lph, lpm, gp + 4096, lane, &rg, nullptr, gq + 4096);
-#else
-        sp_layer_otf<false, true, false, D1>(acc, x, lph, lpm, gp + 4096, lane);
-#endif
-#endif
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 8)      // diagnostic: P / Q stored tile-major (coalesced) instead of row-major
-        if (valid) store_frag<NT>(tile_ptr(a.P, tile, L, lane), STRIDE_TILE, acc);
-#elif defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 16)   // diagnostic: no P / Q stores
-        if (valid && a.n < 0) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
-#else
         if (valid) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
-#endif
-        NODE_CHAIN_PRIO();
+        __builtin_amdgcn_s_setprio(0);
         tab_frag<NT>(acc, tb + T_BQ * L, h);
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 1)
-        sp_layer_otf<false, false, false, D1>(acc, x, lqh, lqm, lqm, lane);
-#else
-#if MGN_SP_CARRY
         sp_layer_otf<false, true, false, D1, false, 32 % D1, true, false>(acc, x, lqh, lqm, gq + 4096, lane, &rg);
-#else
-        sp_layer_otf<false, true, false, D1>(acc, x, lqh, lqm, gq + 4096, lane);
-#endif
-#endif
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-#if MGN_NODE_VNEXT_FIRST
-        PHASE_FENCE();
-        if (has_next) load_frag<NT>(x, tile_ptr(a.V, a.tile0 + next, L, lane), STRIDE_TILE);   // ahead of the Q stores (x is dead: both projections read it)
-        PHASE_FENCE();
-#endif
-#if defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 8)
-        if (valid) store_frag<NT>(tile_ptr(a.Q, tile, L, lane), STRIDE_TILE, acc);
-#elif defined(MGN_WHATIF_NODE) && (MGN_WHATIF_NODE & 16)
-        if (valid && a.n < 0) store_frag<NT>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
-#else
         if (valid) store_frag<NT>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
-#endif
         if (!has_next) break;
-#if !MGN_NODE_VNEXT_FIRST
         PHASE_FENCE();
         load_frag<NT>(x, tile_ptr(a.V, a.tile0 + next, L, lane), STRIDE_TILE);
-#endif
         tw.tile = next;
     }
 }
@@ -1892,25 +1387,8 @@ __global__ __launch_bounds__(512, 2) void k_project_split(const NodeArgs a) {
 // second chain's units, 2 x 64 VALU instructions; layer 2's split takes the RAW accumulators of layer 1 -- a ReLU and a power of two
 // commute -- with the row maximum taken on the raw values, so nothing is finished there.
 // ================================================================================================
-#ifndef MGN_SPH_D
 #define MGN_SPH_D 8              // depth of the lo-piece ring of k_node_split_h
-#endif
-#ifndef MGN_NODE_NEXT_FIRST
-#define MGN_NODE_NEXT_FIRST 0    // k_node_split_h: the next tile's v requested ahead of this tile's stores (the residual's sum goes to the other array)
-#endif
-#ifndef MGN_PROJ_VREFILL
-#define MGN_PROJ_VREFILL 0       // k_project_split_h: k-steps of the Q chain's input refilled with the next tile's v inside the chain
-#endif
-#ifndef MGN_NRH_AGG_REFILL
-#define MGN_NRH_AGG_REFILL 0     // k_node_ring_hs: 1 = the aggregate rows requested inside the first chain (built, parity green, no gain: 0.810 vs 0.806 ms --
-                                 // the phase costs its bytes, 0.6 GB, not its latency); 0: between the chains, LOAD_AGGREGATE as it is
-#endif
-#ifndef MGN_NODE_VBUF
-#define MGN_NODE_VBUF 0          // k_node_split_h: its v loads (the refill inside layer 3, the next tile's v) as buffer loads through the tile's descriptor
-#endif
-#ifndef MGN_NODE_VREFILL
 #define MGN_NODE_VREFILL 6       // k_node_split_h: k-steps of layer 3's input refilled with v (for the residual) inside the chain; 0: v requested after the chain
-#endif
 __global__ __launch_bounds__(512, 2) void k_node_split_h(const NodeArgs a) {
     constexpr int NT = 4, L = 128, PC = 16384, D = MGN_SPH_D;
     static_assert(32 % D == 0, "the carried ring keeps offset 0 from chain to chain");
@@ -1954,101 +1432,42 @@ __global__ __launch_bounds__(512, 2) void k_node_split_h(const NodeArgs a) {
         const bool valid = n < a.n;
         const int nn = valid ? n : 0;
         f32x4* vtile = tile_ptr(a.V, tile, L, lane);
-        NODE_CHAIN_PRIO();
+        __builtin_amdgcn_s_setprio(0);
         SpRingH<D> rg;
         const H2Scale sv = h2_scale(h2_rowmax<true>(x));
         zero_frag<NT>(acc);
-#ifdef MGN_WHATIF_NODEH          // timing-only build (wrong results): every lo piece read from LDS (the hi piece's bytes): what the L2 stream costs
-        h2_layer_otf<false, 0, 1>(acc, x, lvh, lvh, lane, sv.s);
-#else
         h2_layer_otf<true, 0, D, 0, false, true>(acc, x, lvh, gv, lane, sv.s, 0.f, nullptr, &rg, ga);            // layer 1, node part
-#endif
         STAMP(1);
         LOAD_AGGREGATE(NT, x, a.rowptr, a.AGG, a.CARRY, a.zero_row);
         h2_finish_frag<NT>(acc, sv.rs * rswv, tb + T_B1 * L, h);                                                  // true units, b1 in
         const H2Scale sa = h2_scale(h2_rowmax<true>(x));
         h2_scale_frag<NT>(acc, sa.s * swa);                                                                       // the aggregate chain's units
         STAMP(2);
-#ifdef MGN_WHATIF_NODEH
-        h2_layer_otf<false, 0, 1>(acc, x, lah, lah, lane, sa.s);
-#else
         h2_layer_otf<true, 0, D, 0, true, true>(acc, x, lah, ga, lane, sa.s, 0.f, nullptr, &rg, g2);             // layer 1, aggregate part
-#endif
         STAMP(3);
         const H2Scale s2 = h2_scale(h2_rowmax<false>(acc));                                                       // (on the raw accumulators)
         zero_frag<NT>(x);
-#ifdef MGN_WHATIF_NODEH
-        h2_layer_otf<false, 1, 1>(x, acc, l2h, l2h, lane, s2.s);
-#else
         h2_layer_otf<true, 1, D, 0, true, true>(x, acc, l2h, g2, lane, s2.s, 0.f, nullptr, &rg, g3);             // layer 2
-#endif
         STAMP(4);
         const float c2 = s2.rs * rsw2 * (sa.rs * rswa);
         const H2Scale s3 = h2_scale(__builtin_fmaf(h2_rowmax<false>(x), c2, b2pos));
         zero_frag<NT>(acc);
-#ifdef MGN_WHATIF_NODEH
-        h2_layer_otf<false, 2, 1, 0, false, false, 6, STRIDE_TILE>(acc, x, l3h, l3h, lane, s3.s, c2, tb + T_B2 * L + 4 * h, nullptr, nullptr, vtile);
-        STAMP(5);
-        PHASE_FENCE();
-        __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-        h2_load_tail<6, STRIDE_TILE>(x, vtile);
-#elif MGN_NODE_VREFILL
         // layer 3; the registers of its input are refilled, as the split releases them, with v again (for the residual)
-#if MGN_NODE_VBUF
-        const N16Buf vb = n16_buf(a.V + (int64_t)tile * (TILE * L), TILE * L * 4);          // (tile is wave-uniform)
-        h2_layer_otf<true, 2, D, 0, true, false, MGN_NODE_VREFILL, STRIDE_TILE, true>(acc, x, l3h, g3, lane, s3.s, c2, tb + T_B2 * L + 4 * h, &rg, nullptr, vtile, &vb);
-        STAMP(5);
-        PHASE_FENCE();
-        __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-        h2_load_tile_buf<2 * MGN_NODE_VREFILL>(x, vb, lane);
-#else
         h2_layer_otf<true, 2, D, 0, true, false, MGN_NODE_VREFILL, STRIDE_TILE>(acc, x, l3h, g3, lane, s3.s, c2, tb + T_B2 * L + 4 * h, &rg, nullptr, vtile);
         STAMP(5);
         PHASE_FENCE();
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
         h2_load_tail<MGN_NODE_VREFILL, STRIDE_TILE>(x, vtile);
-#endif
-#else
-        h2_layer_otf<true, 2, D, 0, true, false>(acc, x, l3h, g3, lane, s3.s, c2, tb + T_B2 * L + 4 * h, &rg);   // layer 3
-        STAMP(5);
-        PHASE_FENCE();
-        __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-        load_frag<NT>(x, vtile, STRIDE_TILE);                        // v again, for the residual
-#endif
         h2_finish_frag<NT>(acc, s3.rs * rsw3, tb + T_B3 * L, h);
         layer_norm_frag<NT>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
-#if MGN_NODE_NEXT_FIRST
-        // the next tile's v is requested AHEAD of this tile's stores (s_waitcnt vmcnt retires in order and counts stores): it lands in acc's
-        // registers and moves over at the end of the tile (64 v_mov: hipcc spilled ~80 registers when the sum went to acc instead)
 #pragma unroll
         for (int t = 0; t < NT; ++t) x[t] += acc[t];                 // v <- v + v'
         STAMP(6);
-        PHASE_FENCE();
-        load_frag<NT>(acc, tile_ptr(a.V, has_next ? next : tile, L, lane), STRIDE_TILE);   // (the last tile requests itself: no branch around the request)
-        PHASE_FENCE();
-        if (valid) store_frag_pol<NT, MGN_NODE_STORE>(vtile, STRIDE_TILE, x);
+        if (valid) store_frag<NT>(vtile, STRIDE_TILE, x);
         STAMP(7);
         if (!has_next) break;
         PHASE_FENCE();
-#pragma unroll
-        for (int t = 0; t < NT; ++t) x[t] = acc[t];
-#else
-#pragma unroll
-        for (int t = 0; t < NT; ++t) x[t] += acc[t];                 // v <- v + v'
-        STAMP(6);
-        if (valid) store_frag_pol<NT, MGN_NODE_STORE>(vtile, STRIDE_TILE, x);
-        STAMP(7);
-        if (!has_next) break;
-        PHASE_FENCE();
-#if MGN_NODE_VBUF
-        {
-            const N16Buf nb = n16_buf(a.V + (int64_t)next * (TILE * L), TILE * L * 4);
-            h2_load_tile_buf<0>(x, nb, lane);
-        }
-#else
         load_frag<NT>(x, tile_ptr(a.V, next, L, lane), STRIDE_TILE);
-#endif
-#endif
         tw.tile = next;
     }
 }
@@ -2129,37 +1548,12 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
         }
         const H2Scale sv = h2_scale(h2_rowmax<true>(x));
         zero_frag<NT>(acc);
-#if MGN_NRH_AGG_REFILL
-        // LOAD_AGGREGATE (tile_common.hpp) in two parts: where a row's sum lives is known from the CSR requested a tile ahead; its sixteen pieces
-        // are requested inside the chain, into the registers of v as the split releases them; straddling runs add their other carry rows behind it
-        const int T1 = ra0 >> 5, T2 = (ra1 - 1) >> 5;
-        const int extra = (ra1 > ra0 && T2 > T1) ? (T2 - T1) : 0;
-        const bool from_agg = (ra1 > ra0) && !extra;
-        const f32x4* src0 = from_agg ? tile_ptr(a.AGG, tile, L, lane) : prow_ptr(a.CARRY, extra ? (int64_t)(2 * T1 + 1) : a.zero_row, L, h);
-        const int astride = from_agg ? STRIDE_TILE : STRIDE_PROW;
-        hs_layer_ring<0, 0, -1, NWV, true, NCH>(acc, x, ring, src, nx, pend, lane, tid, sv.s, 0.f, nullptr, src0, nullptr, astride);   // layer 1, node part
-#pragma unroll
-        for (int m = 12; m < 16; ++m) {
-            const f32x4 v = src0[(int64_t)m * astride];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[3][4 * (m & 3) + i] = v[i];
-        }
-        if (__any(extra >= 1)) add_frag<NT>(x, prow_ptr(a.CARRY, extra >= 1 ? (int64_t)2 * (T1 + 1) : a.zero_row, L, h), STRIDE_PROW);
-        if (__any(extra >= 2))
-            for (int q = 2; __any(q <= extra); ++q)
-                if (q <= extra) add_frag<NT>(x, prow_ptr(a.CARRY, (int64_t)2 * (T1 + q), L, h), STRIDE_PROW);
-#else
         hs_layer_ring<0, 0, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, sv.s);                    // layer 1, node part
         {
             const bool valid_row = n < a.n;                          // (LOAD_AGGREGATE reads `valid`, `nn`, `tile`: rows, not whether the tile stores)
             const bool valid = valid_row;
-#if defined(MGN_WHATIF_NRH) && (MGN_WHATIF_NRH & 1)      // timing-only builds (wrong results): what each memory phase of this kernel costs
-            (void)valid;
-#else
             LOAD_AGGREGATE(NT, x, a.rowptr, a.AGG, a.CARRY, a.zero_row);
-#endif
         }
-#endif
         h2_finish_frag<NT>(acc, sv.rs * rswv, tb + T_B1 * L, h);                                                  // true units, b1 in
         const H2Scale sa = h2_scale(h2_rowmax<true>(x));
         h2_scale_frag<NT>(acc, sa.s * swa);                                                                       // the aggregate chain's units
@@ -2181,11 +1575,7 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) x[m >> 2][4 * (m & 3) + i] = v[i] + acc[m >> 2][4 * (m & 3) + i];
         }
-#if defined(MGN_WHATIF_NRH) && (MGN_WHATIF_NRH & 2)
-        if (valid && a.n < 0) store_frag<NT>(tile_ptr(a.V, tile, L, lane), STRIDE_TILE, x);
-#else
         if (valid) store_frag<NT>(tile_ptr(a.V, tile, L, lane), STRIDE_TILE, x);
-#endif
         PHASE_FENCE();
         __builtin_amdgcn_s_setprio(0);
         const H2Scale sp = h2_scale(h2_rowmax<true>(x));
@@ -2193,11 +1583,7 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
         hs_layer_ring<4, 0, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, sp.s);                    // P = v W1s
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
         h2_scale_frag<NT>(acc, sp.rs * rswp);
-#if defined(MGN_WHATIF_NRH) && (MGN_WHATIF_NRH & 4)
-        if (valid && a.n < 0) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
-#else
         if (valid) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
-#endif
         __builtin_amdgcn_s_setprio(0);
         zero_frag<NT>(acc);
         // Q = v W1r + b1; its input registers are refilled, as the split releases them, with the NEXT tile's v
@@ -2216,11 +1602,7 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
             ra1 = n1 < a.n ? a.rowptr[n1 + 1] : 0;
         }
         h2_finish_frag<NT>(acc, sp.rs * rswq, tb + T_BQ * L, h);
-#if defined(MGN_WHATIF_NRH) && (MGN_WHATIF_NRH & 4)
-        if (valid && a.n < 0) store_frag<NT>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
-#else
         if (valid) store_frag<NT>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
-#endif
         tw.tile += tw.stride;
     }
 }
@@ -2256,33 +1638,22 @@ __global__ __launch_bounds__(512, 2) void k_project_split_h(const NodeArgs a) {
         const int n = tile * TILE + c;
         const bool valid = n < a.n;
         const int nn = valid ? n : 0;
-        NODE_CHAIN_PRIO();
+        __builtin_amdgcn_s_setprio(0);
         const H2Scale sv = h2_scale(h2_rowmax<true>(x));
         zero_frag<NT>(acc);
         h2_layer_otf<false, 0, 1>(acc, x, lph, lpl, lane, sv.s);
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
         h2_scale_frag<NT>(acc, sv.rs * rswp);
-        if (valid) store_frag_pol<NT, MGN_PROJ_STORE>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
-        NODE_CHAIN_PRIO();
+        if (valid) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
+        __builtin_amdgcn_s_setprio(0);
         zero_frag<NT>(acc);
-#if MGN_PROJ_VREFILL
-        // the second chain's input registers are refilled, as the split releases them, with the NEXT tile's v
-        const f32x4* vnext = tile_ptr(a.V, a.tile0 + (has_next ? next : tw.tile), L, lane);
-        h2_layer_otf<false, 0, 1, 0, false, false, MGN_PROJ_VREFILL, STRIDE_TILE>(acc, x, lqh, lql, lane, sv.s, 0.f, nullptr, nullptr, nullptr, vnext);
-        __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
-        h2_load_tail<MGN_PROJ_VREFILL, STRIDE_TILE>(x, vnext);
-        h2_finish_frag<NT>(acc, sv.rs * rswq, tb + T_BQ * L, h);
-        if (valid) store_frag_pol<NT, MGN_PROJ_STORE>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
-        if (!has_next) break;
-#else
         h2_layer_otf<false, 0, 1>(acc, x, lqh, lql, lane, sv.s);
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
         h2_finish_frag<NT>(acc, sv.rs * rswq, tb + T_BQ * L, h);
-        if (valid) store_frag_pol<NT, MGN_PROJ_STORE>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
+        if (valid) store_frag<NT>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, acc);
         if (!has_next) break;
         PHASE_FENCE();
         load_frag<NT>(x, tile_ptr(a.V, a.tile0 + next, L, lane), STRIDE_TILE);
-#endif
         tw.tile = next;
     }
 }

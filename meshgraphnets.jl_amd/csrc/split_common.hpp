@@ -5,26 +5,15 @@
 namespace mgn {
 
 typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sp_bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 DEVINL float sp_f(unsigned u) { return __builtin_bit_cast(float, u); }
 DEVINL unsigned sp_u(float f) { return __builtin_bit_cast(unsigned, f); }
-#ifndef MGN_SP_CVT_ASM
-#define MGN_SP_CVT_ASM 1
-#endif
 DEVINL unsigned sp_cvt_pk(float a, float b) {            // v_cvt_pk_bf16_f32: round to nearest even
-#if MGN_SP_CVT_ASM
     // as one opaque instruction: from the cast form hipcc converts the low element a second time (alone) for its unpacked copy
     unsigned r;
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    sp_bf16x2 p;
-    p[0] = (__bf16)a;
-    p[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, p);
-#endif
 }
 // ReLU on the bits: a signed-integer max with 0 (negative floats, -0 and negative NaNs -> +0): one instruction the compiler can see
 DEVINL float sp_relu(float v) {
@@ -126,20 +115,9 @@ DEVINL f32x4 n16_ld(const N16Buf& b, unsigned voff, int soff) {
 DEVINL void n16_st(const N16Buf& b, unsigned voff, int soff, f32x4 v) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), b.r, (int)voff, soff, 0);
 }
-template <int AUX>      // cache policy bits of the buffer instruction: 1 sc0, 2 nt, 16 sc1
-DEVINL f32x4 n16_ld_pol(const N16Buf& b, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b.r, (int)voff, soff, AUX));
-}
-template <int AUX>
-DEVINL void n16_st_pol(const N16Buf& b, unsigned voff, int soff, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), b.r, (int)voff, soff, AUX);
-}
 DEVINL u32x4 n16_ldu(const N16Buf& b, unsigned voff, int soff) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b.r, (int)voff, soff, 0)); }
 
 
-#ifndef MGN_SP2_INTERLEAVE
-#define MGN_SP2_INTERLEAVE 1      // 1: pin "one MFMA, n VALU" groups inside every (s, t) step (sched_group_barrier)
-#endif
 // One L x L layer on two fp16 pieces, `in` split on the fly with the row scale sx (split.hip: the node-side kernels; train.hip: the
 // streaming training kernels).  p_hi LDS-resident; p_lo LDS-resident too (GL = false) or streamed from L2 through ONE per-wave register
 // ring D fragments deep that can be carried from chain to chain (carry / PRIMED / NEXT / nx_lo: see sp_layer_otf in split.hip).
@@ -219,11 +197,9 @@ DEVINL void h2_layer_otf(f32x16 (&acc)[4], const f32x16 (&in)[4], const u32x4* p
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a2), bh, acc[t], 0, 0, 0);      // small terms first
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a1), bl, acc[t], 0, 0, 0);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a1), bh, acc[t], 0, 0, 0);
-#if MGN_SP2_INTERLEAVE
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll

@@ -5,9 +5,7 @@
 
 namespace mgn {
 
-#ifndef MGN_FAST_PRELOAD_TILES
 #define MGN_FAST_PRELOAD_TILES 8192     // node-side launches of up to 4 tiles per wave copy their weights with eight loads in flight
-#endif
 
 // Waves w and w+4 of a block share a SIMD and run the same program; started together they stay in
 // lockstep (both gather, then both want the MFMA pipe).  Delaying the second half once by about half a
@@ -58,15 +56,11 @@ DEVINL float dpp_zero(float v) {
 // lane would read as 0 on gfx9), hence the multiplicative mask; invalid source lanes (row boundaries) read 0 (bound_ctrl).
 // Inline asm: hipcc has no builtin that yields the DPP form of fmac.  Hazards: a DPP read needs 2 wait states after a VALU
 // write of the same VGPR -- consecutive levels touch a register NG * 16 >= 16 instructions apart, and an s_nop covers the
-// first level.  MGN_SCAN_FMAC = 0 restores the two-instruction form (also the reference for tests of this helper).
-#ifndef MGN_SCAN_FMAC
-#define MGN_SCAN_FMAC 1
-#endif
+// first level.
 // SKIP8: the reach-8 level runs only when some run of the tile reaches back 8 rows (in-degree >= 9; a wave-uniform branch).
 // bf16 edge kernel 0.918 -> 0.907 ms on M-1M; the fp32 kernel gets 3 % SLOWER with the branch (same-box A/B), so only bf16 uses it.
 template <int NG, bool SKIP8 = false>
 DEVINL void segmented_scan(f32x16 (&acc)[NG], bool c1, bool c2, bool c4, bool c8, bool cx) {
-#if MGN_SCAN_FMAC
     const float m1 = c1 ? 1.f : 0.f, m2 = c2 ? 1.f : 0.f, m4 = c4 ? 1.f : 0.f, m8 = c8 ? 1.f : 0.f, mx = cx ? 1.f : 0.f;
 #define MGN_SCAN_LEVEL(M, CTRL)                                                                                  \
     _Pragma("unroll") for (int t = 0; t < NG; ++t)                                                               \
@@ -83,23 +77,6 @@ DEVINL void segmented_scan(f32x16 (&acc)[NG], bool c1, bool c2, bool c4, bool c8
     MGN_SCAN_LEVEL(mx, "row_bcast:15 row_mask:0xa bank_mask:0xf")
 #undef MGN_SCAN_LEVEL
     PHASE_FENCE();
-#else
-#pragma unroll
-    for (int t = 0; t < NG; ++t) {
-        PHASE_FENCE();   // bound the scan's temporaries to one 16-register group at a time
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            float v = acc[t][k];
-            float u;
-            u = v + dpp_zero<0x111, 0xF>(v); v = c1 ? u : v;   // row_shr:1
-            u = v + dpp_zero<0x112, 0xF>(v); v = c2 ? u : v;   // row_shr:2
-            u = v + dpp_zero<0x114, 0xF>(v); v = c4 ? u : v;   // row_shr:4
-            u = v + dpp_zero<0x118, 0xF>(v); v = c8 ? u : v;   // row_shr:8
-            u = v + dpp_zero<0x142, 0xA>(v); v = cx ? u : v;   // row_bcast:15 into rows 1 and 3
-            acc[t][k] = v;
-        }
-    }
-#endif
 }
 
 
@@ -156,9 +133,6 @@ DEVINL void copy_to_lds16(uint16_t* dst, const uint16_t* __restrict__ src, int n
 // aggregated messages of the tile's nodes: the node's AGG slot, or carry rows when its edge run straddles edge tiles.
 // A macro on purpose: as a (force-inlined) function the same code costs k_node_step<4,*> 37 spilled VGPRs.
 // Uses tile, nn, valid, lane, h, L of the enclosing tile loop.
-#ifndef MGN_AGG_PEEL
-#define MGN_AGG_PEEL 1
-#endif
 #define LOAD_AGGREGATE(NT_, y_, rowptr_, AGG_, CARRY_, zero_row_)                                                        \
     do {                                                                                                                 \
         const int a0 = valid ? (rowptr_)[nn] : 0, a1 = valid ? (rowptr_)[nn + 1] : 0;                                     \
@@ -172,16 +146,11 @@ DEVINL void copy_to_lds16(uint16_t* dst, const uint16_t* __restrict__ src, int n
            without a loop and without a branch (the other lanes add the zero row); only hub nodes enter the loop behind it -- \
            as the loop's first trip this cost every tile 64 loop-carried register copies and a spill that was reloaded, with  \
            s_waitcnt vmcnt(0), in the middle of the next chain */                                                            \
-        if (MGN_AGG_PEEL) {                                                                                              \
-            if (__any(extra >= 1))                                                                                       \
-                add_frag<NT_>(y_, prow_ptr((CARRY_), extra >= 1 ? (int64_t)2 * (T1 + 1) : (zero_row_), L, h), STRIDE_PROW); \
-            if (__any(extra >= 2))                                                                                       \
-                for (int q = 2; __any(q <= extra); ++q)                                                                  \
-                    if (q <= extra) add_frag<NT_>(y_, prow_ptr((CARRY_), (int64_t)2 * (T1 + q), L, h), STRIDE_PROW);      \
-        } else {                                                                                                         \
-            for (int q = 1; __any(q <= extra); ++q)                                                                      \
-                if (q <= extra) add_frag<NT_>(y_, prow_ptr((CARRY_), (int64_t)2 * (T1 + q), L, h), STRIDE_PROW);          \
-        }                                                                                                                \
+        if (__any(extra >= 1))                                                                                           \
+            add_frag<NT_>(y_, prow_ptr((CARRY_), extra >= 1 ? (int64_t)2 * (T1 + 1) : (zero_row_), L, h), STRIDE_PROW);  \
+        if (__any(extra >= 2))                                                                                           \
+            for (int q = 2; __any(q <= extra); ++q)                                                                      \
+                if (q <= extra) add_frag<NT_>(y_, prow_ptr((CARRY_), (int64_t)2 * (T1 + q), L, h), STRIDE_PROW);         \
     } while (0)
 
 }  // namespace mgn

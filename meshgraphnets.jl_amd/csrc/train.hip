@@ -59,24 +59,11 @@ DEVINL void seg_sum_store(f32x16 (&acc)[NT], const int32_t* rcv, float* out, flo
     if (tail) store_frag<NT>(dst, STRIDE_ROW, acc);
 }
 
-// the kept activations are written once and read a whole pass later: stores that do not allocate in the caches (-DMGN_TRAIN_NT_STORES=1) were
-// tried -- M-1M step 0.308 -> 0.319 s on the same box -- and are off
-#ifndef MGN_TRAIN_NT_STORES
-#define MGN_TRAIN_NT_STORES 0
-#endif
+// the kept activations are written once and read a whole pass later: stores that do not allocate in the caches were tried -- M-1M step
+// 0.308 -> 0.319 s on the same box -- and dropped
 template <int NT>
 DEVINL void store_frag_keep(f32x4* __restrict__ p, int stride, const f32x16 (&x)[NT]) {
-#if MGN_TRAIN_NT_STORES
-#pragma unroll
-    for (int m = 0; m < 4 * NT; ++m) {
-        f32x4 v;
-        v[0] = x[m >> 2][4 * (m & 3) + 0]; v[1] = x[m >> 2][4 * (m & 3) + 1];
-        v[2] = x[m >> 2][4 * (m & 3) + 2]; v[3] = x[m >> 2][4 * (m & 3) + 3];
-        __builtin_nontemporal_store(v, &p[m * stride]);
-    }
-#else
     store_frag<NT>(p, stride, x);
-#endif
 }
 
 // ================================================================================================
@@ -725,9 +712,7 @@ __global__ __launch_bounds__(64 * WPB) void k_lin2(const Lin2Args a) {
 // half wave), B operand = G (lane (n, k) reads G[row 2q+k][32 tj + n]).  Wave ti of a block owns input-feature block ti
 // and all NT output blocks; a block owns a contiguous row range and writes its partial dW (and the column sums of G).
 // ================================================================================================
-#ifndef MGN_WG_ROWS
 #define MGN_WG_ROWS 128
-#endif
 constexpr int WG_ROWS = MGN_WG_ROWS;    // rows per block at least (k_wgrad_lds, cylinder mesh: 64 / 128 / 256 / 512 rows 2.49 / 2.41 / 2.56 / 3.39 ms per step: a block writes a 64 KiB partial whatever its rows)
 constexpr int WG_UNROLL = 8;   // k-steps (2 rows each) whose loads are issued together
 
@@ -930,12 +915,7 @@ constexpr int WH_BUF = WH_KB * WH_UPK;      // units per (array, piece) of a buf
 constexpr size_t WH_LDS = (size_t)4 * WH_BUF * 16 + 4 * sizeof(float) + 4 * 128 * sizeof(float);
 DEVINL int wh_unit(int f, int kb) { return kb * WH_UPK + (f & 3) * 36 + (f >> 2); }
 
-#ifndef MGN_WH_WHATIF
-#define MGN_WH_WHATIF 0        // timing builds (wrong gradients): 1 no products, 2 no split / LDS writes, 4 no partial store, 8 no maxima, 16 no loads after the first two chunks
-#endif
-#ifndef MGN_WH_BLOCKS
 #define MGN_WH_BLOCKS 2         // blocks per CU (3: the operand reads of a chunk no longer fit the 168 registers -- 317 spilled)
-#endif
 __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatch wb) {
     constexpr int NT = 4, L = 128;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1018,7 +998,6 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
 
     auto fetch = [&](int c, f32x4 (&d)[8]) {             // chunk c -> registers (rows past the end: row r0, zeroed in `amax_zero`)
         if (c >= nchunks || !loads) return;
-        if (MGN_WH_WHATIF & 16) { if (c > 1) return; }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int64_t row = r0 + (int64_t)c * WH_ROWS + 8 * rg + j;
@@ -1034,7 +1013,6 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
     // zero the rows past the end, then: this wave's largest magnitude of chunk c -> its slot
     auto amax_zero = [&](int c, f32x4 (&d)[8]) {
         if (c >= nchunks) return;
-        if (MGN_WH_WHATIF & 8) { if (lane == 0 && c == 0) smax[ti] = 1.f; return; }
         float mx = 0.f;
         if (loads) {
 #pragma unroll
@@ -1052,7 +1030,7 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
         if (lane == 0) smax[ti] = mx;
     };
     auto to_lds = [&](const f32x4 (&d)[8], float s) {
-        if (!loads || (MGN_WH_WHATIF & 2)) return;
+        if (!loads) return;
         u32x4* const ph = sP + (size_t)(2 * arr) * WH_BUF;
         u32x4* const pl = ph + WH_BUF;
 #pragma unroll
@@ -1070,7 +1048,7 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
         }
     };
     auto compute = [&]() {
-        if (!with_w || (MGN_WH_WHATIF & 1)) return;
+        if (!with_w) return;
         const u32x4* const xh = sP;
 #pragma unroll
         for (int ks = 0; ks < WH_ROWS / 16; ++ks) {
@@ -1128,7 +1106,7 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
         compute();
     }
     // D layout of the 32x32 MFMA: register r of lane l holds D[(r&3) + 8(r>>2) + 4(l>>5)][l&31]
-    if (with_w && !(MGN_WH_WHATIF & 4)) {
+    if (with_w) {
         const float cc = sx.rs * sg.rs;                   // back from the scaled units
         float* pw = jb.pw + (size_t)blockIdx.x * L * L;
 #pragma unroll
@@ -1146,33 +1124,11 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
     }
 }
 
-#ifndef MGN_REDUCE_VEC
-#define MGN_REDUCE_VEC 0     // 1: four outputs per thread, eight blocks in flight -- cylinder-mesh step 2.44 ms against 2.38 (a quarter of the threads: fewer loads in flight overall)
-#endif
-// out[r * cols + c] = sum_b partial[b][r * ld + c], fixed order (bitwise reproducible); one job per blockIdx.y.  Four consecutive outputs per
-// thread where the shapes allow 16-byte accesses (cols = ld, a multiple of 4: every weight chunk and bias of the model but the decoder's
-// last layer), eight partial blocks in flight (-DMGN_REDUCE_VEC=1; measured slower, off).
+// out[r * cols + c] = sum_b partial[b][r * ld + c], fixed order (bitwise reproducible); one job per blockIdx.y.  (Four consecutive outputs
+// per thread with eight partial blocks in flight was measured slower.)
 __global__ void k_reduce_partials(const ReduceBatch rb) {
     const ReduceJob& jb = rb.job[blockIdx.y];
     const int total = jb.nrows * jb.cols;
-    if (MGN_REDUCE_VEC && jb.cols == jb.ld && (jb.cols & 3) == 0 && (jb.block_stride & 3) == 0 && ((reinterpret_cast<uintptr_t>(jb.out) | reinterpret_cast<uintptr_t>(jb.partial)) & 15) == 0) {
-        const int i4 = blockIdx.x * blockDim.x + threadIdx.x;
-        if (4 * i4 >= total) return;
-        const f32x4* __restrict__ p = reinterpret_cast<const f32x4*>(jb.partial) + i4;
-        const size_t bs4 = (size_t)jb.block_stride / 4;
-        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-        int b = 0;
-        for (; b + 8 <= jb.nblocks; b += 8) {
-            f32x4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(b + u) * bs4];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; b < jb.nblocks; ++b) s += p[(size_t)b * bs4];
-        reinterpret_cast<f32x4*>(jb.out)[i4] = s;
-        return;
-    }
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int r = i / jb.cols, cidx = i - r * jb.cols;
