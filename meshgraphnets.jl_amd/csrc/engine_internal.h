@@ -49,6 +49,21 @@ struct MlpOff {
 struct GenOff {
     size_t ch[4] = {0, 0, 0, 0}, tabs = 0;
 };
+// One L x L chunk of the network's weights as the tuned kernels see it: the offset (in elements) of each device copy of it, NONE
+// where that copy is not built, and the power of two its fp16 pieces were multiplied by (1 without fp16 pieces).
+//   frag         wfrag: fp32 fragment order, its t-major copy at + L L, its 16x16x4 copy at + 2 L L
+//   sp32 / sp16  wsp: three bf16 pieces (WPackJob kinds 1 / 2) in the 32x32x16 / 16x16x32 fragment order
+//   h32 / h16    wsp: two fp16 pieces of the chunk times `scale` (kinds 4 / 5) in the same two orders
+//   bf           wbf: one bf16 copy (kind 3)
+// Which copies a chunk gets is decided by its role and the configuration alone (mgn_api.cpp, pack_inference_weights):
+//   frag: every chunk;  bf: processor chunks when dtype = MGN_BF16;  sp16, h16: processor chunks when L = 128 and hidden_layers = 2
+//   (the 16-row kernels, both storage modes);  sp32, h32: the same in fp32 storage only (the 32-row kernels of split.hip; no h32 of
+//   the second edge set's node-side chunks, which no kernel takes);  encoders and decoder: frag, and h32 under the same condition.
+struct ChunkRef {
+    static constexpr size_t NONE = ~(size_t)0;
+    size_t frag = NONE, sp32 = NONE, sp16 = NONE, h32 = NONE, h16 = NONE, bf = NONE;
+    float scale = 1.f;
+};
 
 enum Family { F_EDGE = 0, F_NODE, F_ENC, F_DEC, F_HALO, F_EDGE_BND, F_NFAM };   // F_EDGE_BND: boundary tiles of a split edge step
 
@@ -63,6 +78,7 @@ namespace mgn { struct TrainState; }
 using mgn::DevBuf;
 using mgn::MlpOff;
 using mgn::GenOff;
+using mgn::ChunkRef;
 using mgn::ProfRec;
 using mgn::LocalGraph;
 using mgn::MAX_EDGE_SETS;
@@ -87,14 +103,23 @@ struct mgn_engine {
     std::vector<float> params;  // packed, host
     MlpOff enc_node, dec;
     std::vector<MlpOff> pn;
-    DevBuf wfrag;     // all chunks + tables + small tensors, fragment order
-    // offsets into wfrag (floats).  e_ch / e_tabs: edge MLP of each set; n_ch: node MLP (0:W2 1:W3 2:W1v 3:W1a 6:W1a of
-    // set 1) and the projection onto the NEXT step's set-0 edge MLP (4:WP 5:WQ, bias in n_tabs[T_BQ]); p1_ch / p1_tabs:
-    // the same projection for set 1
-    struct StepOff { size_t e_ch[MAX_EDGE_SETS][3], e_tabs[MAX_EDGE_SETS], n_ch[7], n_tabs, p1_ch[2], p1_tabs; GenOff e_gen[MAX_EDGE_SETS], n_gen; };
-    std::vector<StepOff> soff;
-    size_t en_ch[4] = {0, 0, 0, 0}, en_tabs = 0, en_w1f = 0;
-    size_t de_ch[2] = {0, 0}, de_tabs = 0, de_w3f = 0, de_b3 = 0;
+    // the kernels' weight layouts: wfrag (fp32: all chunks + tables + small tensors, fragment order), wsp (16-bit pieces of the split
+    // path, split.hip), wbf (bf16 storage); which chunk has a copy where: ChunkRef
+    DevBuf wfrag, wsp, wbf;
+    // One processor step.  e[q][i]: the edge MLP of set q in EdgeArgs::chunk order (0 W2, 1 W3, 2 W1 rows [2L, 3L): the e block);
+    // n[i]: the node side in NodeArgs::chunk order -- 0 W2, 1 W3, 2 W1v = W1 rows [0, L), 3 W1a = rows [L, 2L) of the node MLP,
+    // 4 WP, 5 WQ = W1 rows [0, L), [L, 2L) of the NEXT step's set-0 edge MLP (the projection; its bias in n_tabs[T_BQ]), and with two
+    // edge sets 6 W1a of set 1 = rows [2L, 3L), 7 WP1, 8 WQ1 = the same projection onto set 1's edge MLP (bias in p1_tabs[T_BQ]).
+    // *_tabs, *_gen: tables and the GEN kernels' chunk lists in wfrag (floats); *_b2pos = max(0, max b2) where fp16 pieces exist.
+    struct StepChunks {
+        ChunkRef e[MAX_EDGE_SETS][3], n[9];
+        size_t e_tabs[MAX_EDGE_SETS], n_tabs, p1_tabs;
+        GenOff e_gen[MAX_EDGE_SETS], n_gen;
+        float e_b2pos[MAX_EDGE_SETS], n_b2pos;
+    };
+    std::vector<StepChunks> steps;   // [mps + 1]; [mps]: the "project only" pseudo-step of mgn_proc_begin -- step 0 with the projections onto step 0's own edge MLPs
+    ChunkRef en[4], de[2];           // node encoder in EncNodeArgs::chunk order (0 W2, 1 W3, 2 WP, 3 WQ of step 0, set 0), decoder (0 W1, 1 W2)
+    size_t en_tabs = 0, en_w1f = 0, de_tabs = 0, de_w3f = 0, de_b3 = 0;
     GenOff en_gen, de_gen;
 
     // norms (device): node scale/shift [Fn], edge [Fe], out [O]; null = identity
@@ -113,7 +138,8 @@ struct mgn_engine {
         int32_t Fe = 0;
         MlpOff enc;
         std::vector<MlpOff> pe;
-        size_t ee_ch[2] = {0, 0}, ee_tabs = 0, ee_w1f = 0;
+        ChunkRef ee[2];                       // edge encoder (0 W2, 1 W3)
+        size_t ee_tabs = 0, ee_w1f = 0;
         GenOff ee_gen;
         int32_t ntiles_e = 0;
         bool have_ef = false;
@@ -125,22 +151,9 @@ struct mgn_engine {
     } es[MAX_EDGE_SETS];
 
     // latents and I/O
-    // bf16 mode (cfg.dtype == MGN_BF16): bf16 copies of the processor state and weights; the fp32 V / Elat buffers
+    // bf16 mode (cfg.dtype == MGN_BF16): bf16 copies of the processor state (and weights: wbf); the fp32 V / Elat buffers
     // then only carry encoder output / decoder input
-    DevBuf wbf, bV;
-    struct BfStepOff { size_t e_ch[MAX_EDGE_SETS][3], n_ch[7], p1_ch[2]; };
-    std::vector<BfStepOff> bsoff;
-    // split path (csrc/split.hip: fp32 storage, products on the bf16 matrix cores): per step and set the three edge chunks, per step the
-    // node MLP's four and the projection's two, as 3 bf16 pieces each
-    DevBuf wsp;
-    struct SplitOff { size_t e_ch[MAX_EDGE_SETS][3], e16_ch[MAX_EDGE_SETS][3]; size_t n_ch[6], n2_ch[3], n16_ch[9]; bool have_n;
-                      // two fp16 pieces (kind 4 of WPackJob): offsets, the power of two each chunk was multiplied by, max(0, max b2)
-                      size_t eh_ch[MAX_EDGE_SETS][3], nh_ch[6], e16h_ch[MAX_EDGE_SETS][3], n16h_ch[9]; float eh_s[MAX_EDGE_SETS][3], nh_s[9], e_b2pos[MAX_EDGE_SETS], n_b2pos; bool have_h; };   // n2_ch (two edge sets): W1[2L:3L], WP / WQ of set 1
-    std::vector<SplitOff> spoff;
-    // encoders / decoder on two fp16 pieces (kind 4 of WPackJob): offsets into wsp and the chunks' powers of two; have_ench: built
-    size_t enh_ch[4] = {0, 0, 0, 0}, eeh_ch[MAX_EDGE_SETS][2] = {}, deh_ch[2] = {0, 0};
-    float enh_s[4] = {1, 1, 1, 1}, eeh_s[MAX_EDGE_SETS][2] = {}, deh_s[2] = {1, 1};
-    bool have_ench = false;
+    DevBuf bV;
     // static per-trajectory RHS inputs (mgn_set_static): cached encoded edge latents
     bool have_static = false;
     DevBuf stage;     // device staging image of caller-order latents (import / export)

@@ -286,6 +286,29 @@ struct ProfScope {
 
 const float* W(const mgn_engine* h, size_t off) { return h->wfrag.as<float>() + off; }
 
+// the device copies of one chunk (ChunkRef) as the kernels' argument blocks take them; null: that copy is not built
+struct ChunkPtrs {
+    const float *frag, *frag_t;                 // fragment order, t-major
+    const uint16_t *sp32, *sp16, *h32, *h16, *bf;
+    float s, rs;                                // the fp16 pieces' power of two and its inverse (1 without fp16 pieces)
+};
+ChunkPtrs chunk_ptrs(const mgn_engine* h, const ChunkRef& r) {
+    auto at = [](const DevBuf& b, size_t off) -> const uint16_t* { return off == ChunkRef::NONE ? nullptr : b.as<uint16_t>() + off; };
+    ChunkPtrs c{};
+    if (r.frag != ChunkRef::NONE) {
+        c.frag = W(h, r.frag);
+        c.frag_t = c.frag + (size_t)h->cfg.L * h->cfg.L;
+    }
+    c.sp32 = at(h->wsp, r.sp32);
+    c.sp16 = at(h->wsp, r.sp16);
+    c.h32 = at(h->wsp, r.h32);
+    c.h16 = at(h->wsp, r.h16);
+    c.bf = at(h->wbf, r.bf);
+    c.s = r.scale;
+    c.rs = 1.f / r.scale;
+    return c;
+}
+
 // tile-major storage: rows padded to whole 32-row tiles
 size_t tile_floats(int64_t ntiles, int L) { return (size_t)ntiles * TILE * L; }
 
@@ -439,23 +462,21 @@ EdgeArgs edge_args(mgn_engine* h, int k, int q = 0) {
     a.Elat = a.bf ? es.bElat.as<float>() : es.Elat.as<float>();
     a.AGG = a.bf ? es.bAGG.as<float>() : es.AGG.as<float>();
     a.CARRY = a.bf ? es.bCARRY.as<float>() : es.CARRY.as<float>();
+    const auto& so = h->steps[k];
     for (int i = 0; i < 3; ++i) {
-        a.chunk[i] = W(h, h->soff[k].e_ch[q][i]);
-        a.chunk_t[i] = a.chunk[i] + (size_t)h->cfg.L * h->cfg.L;
+        const ChunkPtrs c = chunk_ptrs(h, so.e[q][i]);
+        a.chunk[i] = c.frag;
+        a.chunk_t[i] = c.frag_t;
+        a.split[i] = c.sp32;
+        a.split16[i] = c.sp16;
+        a.splith[i] = c.h32;
+        a.split16h[i] = c.h16;
+        a.h2_s[i] = c.s;
+        a.h2_rs[i] = c.rs;
     }
-    a.tabs = W(h, h->soff[k].e_tabs[q]);
-    a.gen = gen_of(h, h->soff[k].e_gen[q], true);
-    const bool have_sp = k < (int)h->spoff.size() && h->wsp.p;
-    for (int i = 0; i < 3; ++i) a.split[i] = (!a.bf && have_sp) ? h->wsp.as<uint16_t>() + h->spoff[k].e_ch[q][i] : nullptr;
-    for (int i = 0; i < 3; ++i) a.split16[i] = have_sp ? h->wsp.as<uint16_t>() + h->spoff[k].e16_ch[q][i] : nullptr;
-    const bool have_h = have_sp && h->spoff[k].have_h;
-    for (int i = 0; i < 3; ++i) {
-        a.splith[i] = (have_h && !a.bf) ? h->wsp.as<uint16_t>() + h->spoff[k].eh_ch[q][i] : nullptr;
-        a.split16h[i] = have_h ? h->wsp.as<uint16_t>() + h->spoff[k].e16h_ch[q][i] : nullptr;
-        a.h2_s[i] = have_h ? h->spoff[k].eh_s[q][i] : 1.f;
-        a.h2_rs[i] = 1.f / a.h2_s[i];
-    }
-    a.h2_b2pos = have_h ? h->spoff[k].e_b2pos[q] : 0.f;
+    a.tabs = W(h, so.e_tabs[q]);
+    a.gen = gen_of(h, so.e_gen[q], true);
+    a.h2_b2pos = so.e_b2pos[q];
     a.c16 = use_c16(h);
     if (k == 0 && q == 0 && h->elat_src_override && a.c16 && !a.gen.use) a.ElatSrc = h->elat_src_override;
     a.stagger = h->stagger_edge;
@@ -470,11 +491,14 @@ inline int32_t boundary_tiles(const mgn_engine* h, int q) {
     return (int32_t)(tb < h->es[q].ntiles_e ? tb : h->es[q].ntiles_e);
 }
 
+// the chunk of StepChunks::n that slot i of a node-side argument block takes when the block projects onto set q: the projection of
+// set 1 is launched on its own (mode 2) and takes its WP / WQ (7, 8) in the projection slots 4, 5
+inline int node_slot(int i, int q) { return q == 1 && (i == 4 || i == 5) ? i + 3 : i; }
+
 // q: the edge set whose P,Q the projection part (modes 1, 2) writes
 NodeArgs node_args(mgn_engine* h, int k, int mode, int q = 0) {
     NodeArgs a{};
-    const size_t CH = (size_t)h->cfg.L * h->cfg.L;
-    const auto& so = h->soff[k];
+    const auto& so = h->steps[k];
     a.n = h->g.n_own;
     a.ntiles = h->ntiles_n;
     a.rowptr = h->es[0].d_rowptr.as<int32_t>();
@@ -485,35 +509,38 @@ NodeArgs node_args(mgn_engine* h, int k, int mode, int q = 0) {
     a.CARRY = bf ? h->es[0].bCARRY.as<float>() : h->es[0].CARRY.as<float>();
     a.P = bf ? h->es[q].bP.as<float>() : h->es[q].P.as<float>();
     a.Q = bf ? h->es[q].bQ.as<float>() : h->es[q].Q.as<float>();
-    for (int i = 0; i < 6; ++i) {
-        a.chunk[i] = W(h, so.n_ch[i]);
-        a.chunk_t[i] = a.chunk[i] + CH;
-    }
-    a.tabs = W(h, so.n_tabs);
-    if (q == 1) {
-        for (int i = 0; i < 2; ++i) {
-            a.chunk[4 + i] = W(h, so.p1_ch[i]);
-            a.chunk_t[4 + i] = a.chunk[4 + i] + CH;
-        }
-        a.tabs = W(h, so.p1_tabs);
-    }
-    if (h->nsets > 1 && mode != 2) {
+    a.tabs = W(h, q == 1 ? so.p1_tabs : so.n_tabs);
+    const bool agg2 = h->nsets > 1 && mode != 2;        // the node MLP reads the second set's aggregate
+    if (agg2) {
         a.rowptr2 = h->es[1].d_rowptr.as<int32_t>();
         a.AGG2 = bf ? h->es[1].bAGG.as<float>() : h->es[1].AGG.as<float>();
         a.CARRY2 = bf ? h->es[1].bCARRY.as<float>() : h->es[1].CARRY.as<float>();
         a.zero_row2 = 4 * tiles_or_one(h->es[1].ntiles_e);
-        a.chunk[6] = W(h, so.n_ch[6]);
-        a.chunk_t[6] = a.chunk[6] + CH;
         if (q == 0) {                                   // the 16-row kernels project both sets in one launch (mode 1)
             a.P2 = bf ? h->es[1].bP.as<float>() : h->es[1].P.as<float>();
             a.Q2 = bf ? h->es[1].bQ.as<float>() : h->es[1].Q.as<float>();
             a.tabs2 = W(h, so.p1_tabs);
-            for (int i = 0; i < 2; ++i) {
-                a.chunk[7 + i] = W(h, so.p1_ch[i]);
-                a.chunk_t[7 + i] = a.chunk[7 + i] + CH;
-            }
         }
     }
+    // A copy that is not built binds as null (slots 6 .. 8 with one edge set; the 32x32x16 pieces in bf16 storage).  The other
+    // conditions are policy -- what the kernels are given:
+    const bool projects_both = agg2 && q == 0;          // fp32 chunks 7, 8 (6: to every launch that runs the node MLP of two sets)
+    const bool set1_projection = q == 1;                // gets none of the node MLP's three-bf16-piece chunks 0 .. 3 in the 32x32x16 order
+    const bool fp16_pieces32 = h->nsets == 1;           // two fp16 pieces, 32x32x16 order: k_node_split_h / k_project_split_h, one edge set only
+    for (int i = 0; i < 9; ++i) {
+        const ChunkPtrs c = chunk_ptrs(h, so.n[node_slot(i, q)]);
+        if (i < 6 || (i == 6 && agg2) || (i > 6 && projects_both)) {
+            a.chunk[i] = c.frag;
+            a.chunk_t[i] = c.frag_t;
+        }
+        if (i < 7 && !(set1_projection && i < 4)) a.split[i] = c.sp32;
+        if (i < 6 && fp16_pieces32) a.splith[i] = c.h32;
+        a.split16[i] = c.sp16;
+        a.split16h[i] = c.h16;
+        a.h2_s[i] = c.s;
+        a.h2_rs[i] = c.rs;
+    }
+    a.h2_b2pos = a.splith[0] ? so.n_b2pos : 0.f;
     a.mode = mode;
     a.gen = gen_of(h, so.n_gen, true);
     a.stagger = h->stagger_node;
@@ -521,54 +548,8 @@ NodeArgs node_args(mgn_engine* h, int k, int mode, int q = 0) {
     a.c16 = use_c16(h);
     a.stamps = h->d_stamps.as<unsigned long long>();
     a.tile0 = 0;
-    const bool sp16 = k < (int)h->spoff.size() && h->spoff[k].have_n && h->wsp.p;
-    const bool sp = !bf && sp16;
-    for (int i = 0; i < 6; ++i) a.split[i] = (sp && q == 0) ? h->wsp.as<uint16_t>() + h->spoff[k].n_ch[i] : nullptr;
-    const bool sph = sp && q == 0 && h->nsets == 1 && h->spoff[k].have_h;        // two fp16 pieces, 32x32x16 order (fp32 storage, one edge set)
-    const bool sph16 = sp16 && h->spoff[k].have_h;                               // ... 16x16x32 order (16-row kernels: both storage modes, both sets)
-    for (int i = 0; i < 9; ++i) {
-        a.split16h[i] = nullptr;
-        a.h2_s[i] = 1.f;
-    }
-    for (int i = 0; i < 6; ++i) {
-        a.splith[i] = sph ? h->wsp.as<uint16_t>() + h->spoff[k].nh_ch[i] : nullptr;
-        if (sph16) {
-            a.split16h[i] = h->wsp.as<uint16_t>() + h->spoff[k].n16h_ch[i];
-            a.h2_s[i] = h->spoff[k].nh_s[i];
-        }
-    }
-    if (sph16 && h->nsets == 2) {
-        for (int i = 0; i < 3; ++i) {
-            a.split16h[6 + i] = h->wsp.as<uint16_t>() + h->spoff[k].n16h_ch[6 + i];
-            a.h2_s[6 + i] = h->spoff[k].nh_s[6 + i];
-        }
-        if (q == 1)                                     // the projection of set 1 (mode 2): its WP / WQ pieces in slots 4, 5
-            for (int i = 0; i < 2; ++i) {
-                a.split16h[4 + i] = a.split16h[7 + i];
-                a.h2_s[4 + i] = a.h2_s[7 + i];
-            }
-    }
-    for (int i = 0; i < 9; ++i) a.h2_rs[i] = 1.f / a.h2_s[i];
-    a.h2_b2pos = sph ? h->spoff[k].n_b2pos : 0.f;
-    if (sp && h->nsets == 2) {
-        if (q == 1)                                     // the projection of set 1 (mode 2): its WP / WQ pieces
-            for (int i = 0; i < 2; ++i) a.split[4 + i] = h->wsp.as<uint16_t>() + h->spoff[k].n2_ch[1 + i];
-        a.split[6] = h->wsp.as<uint16_t>() + h->spoff[k].n2_ch[0];
-    }
-    // the same chunks in the 16x16x32 fragment order, in NodeArgs.chunk numbering (16-row cooperative kernels on the split path)
-    for (int i = 0; i < 9; ++i) a.split16[i] = nullptr;
-    if (sp16) {
-        for (int i = 0; i < 6; ++i) a.split16[i] = h->wsp.as<uint16_t>() + h->spoff[k].n16_ch[i];
-        if (h->nsets == 2) {
-            for (int i = 0; i < 3; ++i) a.split16[6 + i] = h->wsp.as<uint16_t>() + h->spoff[k].n16_ch[6 + i];
-            if (q == 1)
-                for (int i = 0; i < 2; ++i) a.split16[4 + i] = a.split16[7 + i];
-        }
-    }
     return a;
 }
-
-const uint16_t* WB(const mgn_engine* h, size_t off) { return h->wbf.as<uint16_t>() + off; }
 
 BfEdgeArgs bf_edge_args(mgn_engine* h, int k, int q = 0) {
     BfEdgeArgs a{};
@@ -582,8 +563,8 @@ BfEdgeArgs bf_edge_args(mgn_engine* h, int k, int q = 0) {
     a.Elat = es.bElat.as<uint16_t>();
     a.AGG = es.bAGG.as<uint16_t>();
     a.CARRY = es.bCARRY.as<uint16_t>();
-    for (int i = 0; i < 3; ++i) a.chunk[i] = WB(h, h->bsoff[k].e_ch[q][i]);
-    a.tabs = W(h, h->soff[k].e_tabs[q]);
+    for (int i = 0; i < 3; ++i) a.chunk[i] = chunk_ptrs(h, h->steps[k].e[q][i]).bf;
+    a.tabs = W(h, h->steps[k].e_tabs[q]);
     a.stamps = h->d_stamps.as<unsigned long long>();
     return a;
 }
@@ -591,7 +572,7 @@ BfEdgeArgs bf_edge_args(mgn_engine* h, int k, int q = 0) {
 // project: the args feed k_project_bf16_pipe (P,Q of set q); else k_node_bf16_pipe (node MLP over all sets' aggregates)
 BfNodeArgs bf_node_args(mgn_engine* h, int k, int q = 0, bool project = false) {
     BfNodeArgs a{};
-    const auto& so = h->bsoff[k];
+    const auto& so = h->steps[k];
     a.n = h->g.n_own;
     a.ntiles = h->ntiles_n;
     a.rowptr = h->es[0].d_rowptr.as<int32_t>();
@@ -600,19 +581,14 @@ BfNodeArgs bf_node_args(mgn_engine* h, int k, int q = 0, bool project = false) {
     a.CARRY = h->es[0].bCARRY.as<uint16_t>();
     a.P = h->es[q].bP.as<uint16_t>();
     a.Q = h->es[q].bQ.as<uint16_t>();
-    for (int i = 0; i < 6; ++i) a.chunk[i] = WB(h, so.n_ch[i]);
-    a.tabs = W(h, h->soff[k].n_tabs);
-    if (q == 1) {
-        a.chunk[4] = WB(h, so.p1_ch[0]);
-        a.chunk[5] = WB(h, so.p1_ch[1]);
-        a.tabs = W(h, h->soff[k].p1_tabs);
-    }
-    if (h->nsets > 1 && !project) {
+    const bool agg2 = h->nsets > 1 && !project;
+    for (int i = 0; i < (agg2 ? 7 : 6); ++i) a.chunk[i] = chunk_ptrs(h, so.n[node_slot(i, q)]).bf;
+    a.tabs = W(h, q == 1 ? so.p1_tabs : so.n_tabs);
+    if (agg2) {
         a.rowptr2 = h->es[1].d_rowptr.as<int32_t>();
         a.AGG2 = h->es[1].bAGG.as<uint16_t>();
         a.CARRY2 = h->es[1].bCARRY.as<uint16_t>();
         a.zero_row2 = 4 * tiles_or_one(h->es[1].ntiles_e);
-        a.chunk[6] = WB(h, so.n_ch[6]);
     }
     a.zero_row = 4 * tiles_or_one(h->es[0].ntiles_e);
     a.tile0 = 0;
@@ -739,6 +715,18 @@ int mgn_set_params(mgn_handle* h, const float* packed, size_t n) try {
 }  // extern "C"
 
 namespace mgn {
+// the power of two that puts the largest entry of an L x L chunk (L rows of L floats at W) into [2^14, 2^15): its two fp16 pieces
+// are taken of the chunk times it (split_common.hpp)
+static float fp16_chunk_scale(const float* W, int L) {
+    float mx = 0.f;
+    for (size_t i = 0; i < (size_t)L * L; ++i) mx = std::max(mx, std::fabs(W[i]));
+    int e = 0;
+    (void)std::frexp(mx, &e);                                   // mx = m 2^e, m in [0.5, 1): floor(log2 mx) = e - 1
+    if (!(mx > 0.f) || e - 1 < -40) e = -39;
+    if (!std::isfinite(mx)) e = 128;
+    return std::ldexp(1.f, 15 - e);
+}
+
 int pack_inference_weights(mgn_engine* h) {
     layout_all(h);
     const float* p = h->params.data();
@@ -757,13 +745,41 @@ int pack_inference_weights(mgn_engine* h) {
     size_t seg0 = 0;
     // every chunk is stored three times: [lane-interleaved fragment order][t-major order (cooperative 32-row kernels)]
     // [16x16x4 fragment order (cooperative 16-row kernels, L = 128)]: copies of the chunk at offset `off` live at off + CH, off + 2 CH
-    auto add_chunk = [&](const float* Wm, int ldw, int kbase) {
+    auto add_chunk = [&](const float* Wm, int kbase) {
         const size_t off = f.size();
         if (off > seg0) small.push_back({seg0, off});
         f.resize(off + 3 * CH);
         seg0 = off + 3 * CH;
-        jobs.push_back({0, (long long)off, (long long)(Wm - p), ldw, kbase, 1.f});
+        jobs.push_back({0, (long long)off, (long long)(Wm - p), L, kbase, 1.f});
         return off;
+    };
+    // Which copies a chunk gets, by its role (ChunkRef, engine_internal.h) -- the one place that decides it.  The 16-bit pieces exist
+    // where the tuned kernels that take them do: L = 128, hidden_layers = 2; in the 16x16x32 order for the 16-row kernels of small
+    // meshes (in bf16 storage too, where they keep fp32-accurate arithmetic), in the 32x32x16 order for the 32-row kernels of split.hip
+    // (fp32 storage only), which are also the encoders' and the decoder's.
+    enum : unsigned { FRAG = 1, SP32 = 2, SP16 = 4, H32 = 8, H16 = 16, BF = 32 };
+    const bool pieces = L == 128 && c.hidden_layers == 2, f32 = c.dtype == MGN_F32;
+    const unsigned PROC = FRAG | (f32 ? 0 : BF) | (pieces ? SP16 | H16 : 0) | (pieces && f32 ? SP32 | H32 : 0);
+    // node-side chunks 6 .. 8 of the second edge set: NodeArgs::splith has no slot for them.  (With two edge sets node_args binds no
+    // splith at all, so the h32 copies of chunks 0 .. 5 are as unread there; they are built as they always were.)
+    const unsigned PROC_SET1 = PROC & ~H32;
+    const unsigned ENDS = FRAG | (pieces && f32 ? H32 : 0);  // encoders, decoder
+    // builds the copies in `want` that r does not hold yet, of rows [kbase, kbase + L) of the L-column matrix Wm
+    size_t sp_size = 0, bf_size = 0;                         // elements of wsp, wbf
+    auto place = [&](ChunkRef& r, const float* Wm, int kbase, unsigned want) {
+        if ((want & FRAG) && r.frag == ChunkRef::NONE) r.frag = add_chunk(Wm, kbase);
+        if ((want & (H32 | H16)) && r.h32 == ChunkRef::NONE && r.h16 == ChunkRef::NONE) r.scale = fp16_chunk_scale(Wm + (size_t)kbase * L, L);
+        auto copy = [&](unsigned bit, size_t& at, int kind, size_t& end, size_t n) {
+            if (!(want & bit) || at != ChunkRef::NONE) return;
+            jobs.push_back({kind, (long long)end, (long long)(Wm - p), L, kbase, kind >= 4 ? r.scale : 1.f});
+            at = end;
+            end += n;
+        };
+        copy(SP32, r.sp32, 1, sp_size, 3 * CH);              // (16-bit copies exist at L = 128 only: CH = 16384, the piece size of WPackJob)
+        copy(SP16, r.sp16, 2, sp_size, 3 * CH);
+        copy(H32, r.h32, 4, sp_size, 2 * CH);
+        copy(H16, r.h16, 5, sp_size, 2 * CH);
+        copy(BF, r.bf, 3, bf_size, CH);
     };
     auto add_tabs = [&](const float* b1, const float* b2, const float* b3, const float* ga, const float* be, const float* bq) {
         const size_t off = f.size();
@@ -791,73 +807,99 @@ int pack_inference_weights(mgn_engine* h) {
     const int nl = c.hidden_layers + 1, nmid = nl - 2;      // Dense layers per MLP; L x L middle layers
     const bool h2 = c.hidden_layers == 2;                   // the tuned kernel families are specialised for this
     // the Dense layers after the first one of MLP m (GenOff): middle layers W[1 .. nmid], then the last one when it is L x L
-    // (has_last: every MLP but the decoder), and their biases as tables.  Returns through g; ch[0] / ch[nmid] double as the
-    // classic "W2" / "W3" slots of the tuned kernels at hidden_layers = 2.
+    // (has_last: every MLP but the decoder), and their biases as tables.  Returns through g.
     auto add_gen = [&](const MlpOff& m, bool has_last, GenOff& g) {
-        for (int i = 0; i < nmid; ++i) g.ch[i] = add_chunk(p + m.W[1 + i], L, 0);
-        if (has_last) g.ch[nmid] = add_chunk(p + m.W[nl - 1], L, 0);
+        for (int i = 0; i < nmid; ++i) g.ch[i] = add_chunk(p + m.W[1 + i], 0);
+        if (has_last) g.ch[nmid] = add_chunk(p + m.W[nl - 1], 0);
         g.tabs = f.size();
         f.resize(f.size() + (size_t)(nmid + 1) * L);
         for (int i = 0; i < nmid; ++i) pack_tab(f.data() + g.tabs + (size_t)i * L, p + m.b[1 + i], L);
         pack_tab(f.data() + g.tabs + (size_t)nmid * L, has_last ? p + m.b[nl - 1] : nullptr, L);
     };
+    // the tuned kernels' "W2" / "W3" of MLP m -- its first and its last L x L layer, whose fp32 copies are ch[0] / ch[nmid] of its
+    // GEN list g (one and the same chunk at hidden_layers = 1) -- with the copies `want`
+    auto place_w23 = [&](ChunkRef& w2, ChunkRef& w3, const MlpOff& m, const GenOff& g, unsigned want) {
+        w2.frag = g.ch[0];
+        w3.frag = g.ch[nmid];
+        place(w2, p + m.W[1], 0, want);
+        place(w3, p + m.W[nl - 1], 0, want);
+    };
     auto b2 = [&](const MlpOff& m) { return h2 ? p + m.b[1] : nullptr; };
     auto b3 = [&](const MlpOff& m) { return h2 ? p + m.b[2] : nullptr; };
+    auto b2pos = [&](const MlpOff& m) {                      // max(0, max b2): with the fp16 pieces' scales, bounds the input of layer 3
+        float bp = 0.f;
+        for (int i = 0; i < L; ++i) bp = std::max(bp, p[m.b[1] + i]);
+        return bp;
+    };
+    // The walk: every chunk the tuned kernels take is named here, once, with its role.  (The order is that of wfrag: `small` follows it.)
     // encoder, node side (+ projection onto step-0 edge-MLP layer 1 of set 0)
+    for (ChunkRef& r : h->en) r = {};
+    for (ChunkRef& r : h->de) r = {};
     {
         const MlpOff& m = h->enc_node;
         add_gen(m, true, h->en_gen);
-        h->en_ch[0] = h->en_gen.ch[0];
-        h->en_ch[1] = h->en_gen.ch[nmid];
-        h->en_ch[2] = add_chunk(p + e0.W[0], L, 0);
-        h->en_ch[3] = add_chunk(p + e0.W[0], L, L);
+        place_w23(h->en[0], h->en[1], m, h->en_gen, ENDS);
+        place(h->en[2], p + e0.W[0], 0, ENDS);
+        place(h->en[3], p + e0.W[0], L, ENDS);
         h->en_tabs = add_tabs(p + m.b[0], b2(m), b3(m), p + m.gamma, p + m.beta, p + e0.b[0]);
         h->en_w1f = add_w1f(p + m.W[0], c.Fn);
     }
     for (int q = 0; q < S; ++q) {
         auto& es = h->es[q];
         const MlpOff& m = es.enc;
+        es.ee[0] = es.ee[1] = {};
         add_gen(m, true, es.ee_gen);
-        es.ee_ch[0] = es.ee_gen.ch[0];
-        es.ee_ch[1] = es.ee_gen.ch[nmid];
+        place_w23(es.ee[0], es.ee[1], m, es.ee_gen, ENDS);
         es.ee_tabs = add_tabs(p + m.b[0], b2(m), b3(m), p + m.gamma, p + m.beta, nullptr);
         es.ee_w1f = add_w1f(p + m.W[0], es.Fe);
     }
-    h->soff.assign(c.mps, {});
+    // node side of step k: the node MLP and the projections onto the next step's edge MLPs (after the last step, and for k = mps --
+    // the pseudo-step -- onto step 0's).  Builds the copies so.n[] does not hold yet.
+    auto node_side = [&](mgn_engine::StepChunks& so, int k) {
+        const bool pseudo = k == c.mps;
+        const MlpOff& mn = h->pn[pseudo ? 0 : k];
+        const int kn = k + 1 < c.mps ? k + 1 : 0;
+        const MlpOff& nx = h->es[0].pe[kn];
+        if (!pseudo) add_gen(mn, true, so.n_gen);
+        place_w23(so.n[0], so.n[1], mn, so.n_gen, PROC);
+        place(so.n[2], p + mn.W[0], 0, PROC);
+        place(so.n[3], p + mn.W[0], L, PROC);
+        place(so.n[4], p + nx.W[0], 0, PROC);
+        place(so.n[5], p + nx.W[0], L, PROC);
+        so.n_tabs = pseudo ? add_tabs(nullptr, nullptr, nullptr, nullptr, nullptr, p + nx.b[0])
+                           : add_tabs(p + mn.b[0], b2(mn), b3(mn), p + mn.gamma, p + mn.beta, p + nx.b[0]);
+        if (pieces) so.n_b2pos = b2pos(mn);
+        if (S > 1) {
+            const MlpOff& nx1 = h->es[1].pe[kn];
+            place(so.n[6], p + mn.W[0], 2 * L, PROC_SET1);
+            place(so.n[7], p + nx1.W[0], 0, PROC_SET1);
+            place(so.n[8], p + nx1.W[0], L, PROC_SET1);
+            so.p1_tabs = add_tabs(nullptr, nullptr, nullptr, nullptr, nullptr, p + nx1.b[0]);
+        }
+    };
+    h->steps.assign(c.mps, {});
     for (int k = 0; k < c.mps; ++k) {
-        const MlpOff& mn = h->pn[k];
-        const int kn = k + 1 < c.mps ? k + 1 : 0;                  // projection target (mode 2 at k=0 uses step 0 itself)
-        auto& so = h->soff[k];
+        auto& so = h->steps[k];
         for (int q = 0; q < S; ++q) {
             const MlpOff& me = h->es[q].pe[k];
             add_gen(me, true, so.e_gen[q]);
-            so.e_ch[q][0] = so.e_gen[q].ch[0];
-            so.e_ch[q][1] = so.e_gen[q].ch[nmid];
-            so.e_ch[q][2] = add_chunk(p + me.W[0], L, 2 * L);
+            place_w23(so.e[q][0], so.e[q][1], me, so.e_gen[q], PROC);
+            place(so.e[q][2], p + me.W[0], 2 * L, PROC);
             so.e_tabs[q] = add_tabs(nullptr, b2(me), b3(me), p + me.gamma, p + me.beta, nullptr);
+            if (pieces) so.e_b2pos[q] = b2pos(me);
         }
-        const MlpOff& nx = h->es[0].pe[kn];
-        add_gen(mn, true, so.n_gen);
-        so.n_ch[0] = so.n_gen.ch[0];
-        so.n_ch[1] = so.n_gen.ch[nmid];
-        so.n_ch[2] = add_chunk(p + mn.W[0], L, 0);
-        so.n_ch[3] = add_chunk(p + mn.W[0], L, L);
-        so.n_ch[4] = add_chunk(p + nx.W[0], L, 0);
-        so.n_ch[5] = add_chunk(p + nx.W[0], L, L);
-        so.n_tabs = add_tabs(p + mn.b[0], b2(mn), b3(mn), p + mn.gamma, p + mn.beta, p + nx.b[0]);
-        if (S > 1) {
-            const MlpOff& nx1 = h->es[1].pe[kn];
-            so.n_ch[6] = add_chunk(p + mn.W[0], L, 2 * L);
-            so.p1_ch[0] = add_chunk(p + nx1.W[0], L, 0);
-            so.p1_ch[1] = add_chunk(p + nx1.W[0], L, L);
-            so.p1_tabs = add_tabs(nullptr, nullptr, nullptr, nullptr, nullptr, p + nx1.b[0]);
-        }
+        node_side(so, k);
     }
     {
         const MlpOff& m = h->dec;
-        h->de_ch[0] = add_chunk(p + m.W[0], L, 0);
+        place(h->de[0], p + m.W[0], 0, ENDS);
         add_gen(m, false, h->de_gen);                                  // middle layers only: the last one (L -> O) runs on the VALU
-        h->de_ch[1] = nmid > 0 ? h->de_gen.ch[0] : h->de_ch[0];
+        if (nmid > 0) {
+            h->de[1].frag = h->de_gen.ch[0];
+            place(h->de[1], p + m.W[1], 0, ENDS);
+        } else {
+            h->de[1] = h->de[0];
+        }
         h->de_tabs = add_tabs(p + m.b[0], b2(m), nullptr, nullptr, nullptr, nullptr);
         h->de_w3f = f.size();
         f.resize(f.size() + (size_t)c.O * L);
@@ -866,168 +908,27 @@ int pack_inference_weights(mgn_engine* h) {
         for (int o = 0; o < c.O; ++o) f.push_back(p[m.b[nl - 1] + o]);
         while (f.size() % 4) f.push_back(0.f);
     }
-    // "project only" (mgn_proc_begin) needs step 0's own first layer in the projection slots of some NodeArgs: add a
-    // dedicated pseudo-step at index mps (slots 0..3 alias step 0; tables carry bq = b1 of step 0).
+    // "project only" (mgn_proc_begin) needs step 0's own first layer in the projection slots of some NodeArgs: a dedicated
+    // pseudo-step at index mps.  Its fp32 and bf16 copies of the node MLP's chunks (0 .. 3, 6) are step 0's, its fp32 copies of set 0's
+    // projection the node encoder's; everything else -- all of its 16-bit pieces -- it builds (tables: bq = b1 of step 0's edge MLP).
     {
-        mgn_engine::StepOff so = h->soff[0];
-        so.n_ch[4] = h->en_ch[2];
-        so.n_ch[5] = h->en_ch[3];
-        so.n_tabs = add_tabs(nullptr, nullptr, nullptr, nullptr, nullptr, p + e0.b[0]);
-        if (S > 1) {
-            const MlpOff& e1 = h->es[1].pe[0];
-            so.p1_ch[0] = add_chunk(p + e1.W[0], L, 0);
-            so.p1_ch[1] = add_chunk(p + e1.W[0], L, L);
-            so.p1_tabs = add_tabs(nullptr, nullptr, nullptr, nullptr, nullptr, p + e1.b[0]);
+        mgn_engine::StepChunks so = h->steps[0];
+        for (int i = 0; i < 9; ++i) {
+            ChunkRef r;
+            if (i < 4 || i == 6) {
+                r.frag = so.n[i].frag;
+                r.bf = so.n[i].bf;
+            }
+            so.n[i] = r;
         }
-        h->soff.push_back(so);
-    }
-    h->spoff.clear();
-    if (L == 128 && c.hidden_layers == 2) {                            // bf16 pieces of the split path (split.hip): 4.4 MB per edge set,
-        const bool node_side = S <= 2;                                  //   8.8 MB for the node side (+ 4.4 MB with a second edge set)
-        // every chunk twice: the 32x32x16 fragment order (k_edge_ring, k_node_split, k_project_split; fp32 storage only) and the
-        // 16x16x32 one (the 16-row cooperative kernels of small meshes -- in bf16 storage mode too, where they keep fp32-accurate
-        // arithmetic --)
-        const bool f32 = c.dtype == MGN_F32;
-        h->spoff.assign(c.mps + 1, {});
-        size_t off = 0;
-        auto put = [&](const float* src, int kb, size_t& o32, size_t& o16) {
-            o32 = 0;
-            if (f32) {
-                jobs.push_back({1, (long long)off, (long long)(src - p), L, kb, 1.f});
-                o32 = off;
-                off += (size_t)3 * 16384;
-            }
-            jobs.push_back({2, (long long)off, (long long)(src - p), L, kb, 1.f});
-            o16 = off;
-            off += (size_t)3 * 16384;
-        };
-        // two fp16 pieces of the same chunk times a power of two that puts its largest entry into [2^14, 2^15) (split_common.hpp): in the
-        // 32x32x16 fragment order (fp32 storage: k_edge_ring_h, k_node_split_h, k_project_split_h) and in the 16x16x32 one (16-row kernels)
-        auto puth = [&](const float* src, int kb, size_t& oh, size_t& o16h, float& sc) {
-            float mx = 0.f;
-            for (int k = 0; k < L; ++k)
-                for (int n = 0; n < L; ++n) mx = std::max(mx, std::fabs(src[(size_t)(kb + k) * L + n]));
-            int e = 0;
-            (void)std::frexp(mx, &e);                                   // mx = m 2^e, m in [0.5, 1): floor(log2 mx) = e - 1
-            if (!(mx > 0.f) || e - 1 < -40) e = -39;
-            if (!std::isfinite(mx)) e = 128;
-            sc = std::ldexp(1.f, 15 - e);
-            oh = 0;
-            if (f32) {
-                jobs.push_back({4, (long long)off, (long long)(src - p), L, kb, sc});
-                oh = off;
-                off += (size_t)2 * 16384;
-            }
-            jobs.push_back({5, (long long)off, (long long)(src - p), L, kb, sc});
-            o16h = off;
-            off += (size_t)2 * 16384;
-        };
-        for (int k = 0; k < c.mps; ++k)
-            for (int q = 0; q < S; ++q) {
-                const MlpOff& me = h->es[q].pe[k];
-                const float* src[3] = {p + me.W[1], p + me.W[2], p + me.W[0]};
-                const int kb[3] = {0, 0, 2 * L};
-                for (int i = 0; i < 3; ++i) put(src[i], kb[i], h->spoff[k].e_ch[q][i], h->spoff[k].e16_ch[q][i]);
-                for (int i = 0; i < 3; ++i) puth(src[i], kb[i], h->spoff[k].eh_ch[q][i], h->spoff[k].e16h_ch[q][i], h->spoff[k].eh_s[q][i]);
-                float bp = 0.f;
-                for (int i = 0; i < L; ++i) bp = std::max(bp, p[me.b[1] + i]);
-                h->spoff[k].e_b2pos[q] = bp;
-                h->spoff[k].have_h = true;
-            }
-        for (int k = 0; node_side && k <= c.mps; ++k) {                 // node MLP of step k + projection for step k + 1 (k = mps: the
-            const MlpOff& mn = h->pn[k < c.mps ? k : 0];                //   "project only" pseudo-step: step 0's own first layer)
-            const MlpOff& nx = h->es[0].pe[k + 1 < c.mps ? k + 1 : 0];
-            const float* src[6] = {p + mn.W[1], p + mn.W[2], p + mn.W[0], p + mn.W[0], p + nx.W[0], p + nx.W[0]};
-            const int kb[6] = {0, 0, 0, L, 0, L};
-            for (int i = 0; i < 6; ++i) put(src[i], kb[i], h->spoff[k].n_ch[i], h->spoff[k].n16_ch[i]);
-            for (int i = 0; i < 6; ++i) puth(src[i], kb[i], h->spoff[k].nh_ch[i], h->spoff[k].n16h_ch[i], h->spoff[k].nh_s[i]);
-            float bp = 0.f;
-            for (int i = 0; i < L; ++i) bp = std::max(bp, p[mn.b[1] + i]);
-            h->spoff[k].n_b2pos = bp;
-            h->spoff[k].have_h = true;
-            if (S == 2) {                                               // second edge set: its aggregate block of the node MLP, its projection
-                const MlpOff& n1 = h->es[1].pe[k + 1 < c.mps ? k + 1 : 0];
-                const float* src2[3] = {p + mn.W[0], p + n1.W[0], p + n1.W[0]};
-                const int kb2[3] = {2 * L, 0, L};
-                for (int i = 0; i < 3; ++i) put(src2[i], kb2[i], h->spoff[k].n2_ch[i], h->spoff[k].n16_ch[6 + i]);
-                size_t unused = 0;
-                for (int i = 0; i < 3; ++i) puth(src2[i], kb2[i], unused, h->spoff[k].n16h_ch[6 + i], h->spoff[k].nh_s[6 + i]);
-            }
-            h->spoff[k].have_n = true;
-        }
-        h->have_ench = false;
-        if (f32) {          // encoders and decoder (32x32x16 order only: their kernels are the 32-row ones)
-            size_t unused = 0;
-            auto only32 = [&](const float* src, int kb, size_t& oh, float& sc) {
-                const size_t before = jobs.size();
-                puth(src, kb, oh, unused, sc);
-                jobs.pop_back();                                          // (drop the 16x16x32 copy puth appended)
-                off -= (size_t)2 * 16384;
-                (void)before;
-            };
-            const MlpOff& mn = h->enc_node;
-            only32(p + mn.W[1], 0, h->enh_ch[0], h->enh_s[0]);
-            only32(p + mn.W[2], 0, h->enh_ch[1], h->enh_s[1]);
-            only32(p + e0.W[0], 0, h->enh_ch[2], h->enh_s[2]);
-            only32(p + e0.W[0], L, h->enh_ch[3], h->enh_s[3]);
-            for (int q = 0; q < S; ++q) {
-                const MlpOff& me = h->es[q].enc;
-                only32(p + me.W[1], 0, h->eeh_ch[q][0], h->eeh_s[q][0]);
-                only32(p + me.W[2], 0, h->eeh_ch[q][1], h->eeh_s[q][1]);
-            }
-            const MlpOff& md = h->dec;
-            only32(p + md.W[0], 0, h->deh_ch[0], h->deh_s[0]);
-            only32(p + md.W[1], 0, h->deh_ch[1], h->deh_s[1]);
-            h->have_ench = true;
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, h->wsp.ensure(off * 2));
-    }
-    size_t wb_size = 0;
-    if (c.dtype == MGN_BF16) {
-        auto addb = [&](const float* Wm, int kbase) {
-            const size_t off = wb_size;
-            wb_size += (size_t)L * L;
-            jobs.push_back({3, (long long)off, (long long)(Wm - p), L, kbase, 1.f});
-            return off;
-        };
-        h->bsoff.assign(c.mps + 1, {});
-        for (int k = 0; k < c.mps; ++k) {
-            const MlpOff& mn = h->pn[k];
-            const int kn = k + 1 < c.mps ? k + 1 : 0;
-            const MlpOff& nx = h->es[0].pe[kn];
-            auto& so = h->bsoff[k];
-            for (int q = 0; q < S; ++q) {
-                const MlpOff& me = h->es[q].pe[k];
-                so.e_ch[q][0] = addb(p + me.W[1], 0);
-                so.e_ch[q][1] = addb(p + me.W[2], 0);
-                so.e_ch[q][2] = addb(p + me.W[0], 2 * L);
-            }
-            so.n_ch[0] = addb(p + mn.W[1], 0);
-            so.n_ch[1] = addb(p + mn.W[2], 0);
-            so.n_ch[2] = addb(p + mn.W[0], 0);
-            so.n_ch[3] = addb(p + mn.W[0], L);
-            so.n_ch[4] = addb(p + nx.W[0], 0);
-            so.n_ch[5] = addb(p + nx.W[0], L);
-            if (S > 1) {
-                const MlpOff& nx1 = h->es[1].pe[kn];
-                so.n_ch[6] = addb(p + mn.W[0], 2 * L);
-                so.p1_ch[0] = addb(p + nx1.W[0], 0);
-                so.p1_ch[1] = addb(p + nx1.W[0], L);
-            }
-        }
-        h->bsoff[c.mps] = h->bsoff[0];                       // projection for step 0 (mgn_proc_begin)
-        h->bsoff[c.mps].n_ch[4] = addb(p + e0.W[0], 0);
-        h->bsoff[c.mps].n_ch[5] = addb(p + e0.W[0], L);
-        if (S > 1) {
-            const MlpOff& e1 = h->es[1].pe[0];
-            h->bsoff[c.mps].p1_ch[0] = addb(p + e1.W[0], 0);
-            h->bsoff[c.mps].p1_ch[1] = addb(p + e1.W[0], L);
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, h->wbf.ensure(wb_size * 2));
+        so.n[4].frag = h->en[2].frag;
+        so.n[5].frag = h->en[3].frag;
+        node_side(so, c.mps);
+        h->steps.push_back(so);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (sp_size) HIPCHK(h, h->wsp.ensure(sp_size * 2));
+    if (bf_size) HIPCHK(h, h->wbf.ensure(bf_size * 2));
     drop_graph(h);
     invalidate_static(h);
     if (f.size() > seg0) small.push_back({seg0, f.size()});
@@ -1383,10 +1284,11 @@ static int encode_impl(mgn_handle* h, bool use_norms, bool nodes = true, bool ed
         a.V = h->V.as<float>();
         a.P = h->es[0].P.as<float>();
         a.Q = h->es[0].Q.as<float>();
-        for (int i = 0; i < 4; ++i) a.chunk[i] = W(h, h->en_ch[i]);
         for (int i = 0; i < 4; ++i) {
-            a.splith[i] = (h->have_ench && h->wsp.p) ? h->wsp.as<uint16_t>() + h->enh_ch[i] : nullptr;
-            a.h2_rs[i] = h->have_ench ? 1.f / h->enh_s[i] : 1.f;
+            const ChunkPtrs w = chunk_ptrs(h, h->en[i]);
+            a.chunk[i] = w.frag;
+            a.splith[i] = w.h32;
+            a.h2_rs[i] = w.rs;
         }
         a.tabs = W(h, h->en_tabs);
         a.gen = gen_of(h, h->en_gen, true);
@@ -1410,10 +1312,11 @@ static int encode_impl(mgn_handle* h, bool use_norms, bool nodes = true, bool ed
             if (q == 0 && use_norms && h->have_enorm) { b.scale = nrm + 2 * c.Fn; b.shift = nrm + 2 * c.Fn + c.Fe; }
             b.w1f = W(h, es.ee_w1f);
             b.Elat = es.Elat.as<float>();
-            for (int i = 0; i < 2; ++i) b.chunk[i] = W(h, es.ee_ch[i]);
             for (int i = 0; i < 2; ++i) {
-                b.splith[i] = (h->have_ench && h->wsp.p) ? h->wsp.as<uint16_t>() + h->eeh_ch[q][i] : nullptr;
-                b.h2_rs[i] = h->have_ench ? 1.f / h->eeh_s[q][i] : 1.f;
+                const ChunkPtrs w = chunk_ptrs(h, es.ee[i]);
+                b.chunk[i] = w.frag;
+                b.splith[i] = w.h32;
+                b.h2_rs[i] = w.rs;
             }
             b.tabs = W(h, es.ee_tabs);
             b.gen = gen_of(h, es.ee_gen, true);
@@ -1508,7 +1411,7 @@ int mgn_proc_node(mgn_handle* h, int32_t k, int32_t project_next) try {
     // large meshes: MLP and projection as two launches (the projection then has both of its chunks LDS-resident);
     // small meshes are launch-latency-bound: one fused launch (M-cyl: 53.0 -> 50.8 us per step)
     // (... and from two tiles per CU where the split-path node kernels exist: they are two launches by construction)
-    const bool split_pair = !is_bf16(h) && h->cfg.L == 128 && k < (int)h->spoff.size() && h->spoff[k].have_n && h->wsp.p && node_split_size(h->ntiles_n);
+    const bool split_pair = h->steps[k].n[0].sp32 != ChunkRef::NONE && node_split_size(h->ntiles_n);
     if (project_next && !(h->nsets == 2 && use_c16(h)) && (h->nsets > 1 || split_pair || (h->node_split && !launch_is_small(h->ntiles_n)))) {
         // MLP (2 of its chunks LDS-resident, the others stream from L2), then per edge set the projection with both of
         // its chunks resident -- or, one edge set on two fp16 pieces, both in one lock-step launch (k_node_ring_hs)
@@ -1563,10 +1466,11 @@ static int decode_impl(mgn_handle* h, bool use_norms) {
     a.mask = (use_norms && h->have_mask) ? h->d_mask.as<float>() : nullptr;
     a.gid = h->d_own_gid.as<int32_t>();
     a.out = h->out_override ? h->out_override : h->d_out.as<float>();
-    for (int i = 0; i < 2; ++i) a.chunk[i] = W(h, h->de_ch[i]);
     for (int i = 0; i < 2; ++i) {
-        a.splith[i] = (h->have_ench && h->wsp.p) ? h->wsp.as<uint16_t>() + h->deh_ch[i] : nullptr;
-        a.h2_rs[i] = h->have_ench ? 1.f / h->deh_s[i] : 1.f;
+        const ChunkPtrs w = chunk_ptrs(h, h->de[i]);
+        a.chunk[i] = w.frag;
+        a.splith[i] = w.h32;
+        a.h2_rs[i] = w.rs;
     }
     a.tabs = W(h, h->de_tabs);
     a.gen = gen_of(h, h->de_gen, false);

@@ -276,7 +276,8 @@ def test_compute_from_plain_c(tmp_path):
     assert loss_py == loss_c and np.array_equal(gs_py, gs_c)
 
 
-@pytest.mark.parametrize("dtype,L,hl,two", [("f32", 128, 2, False), ("f32", 128, 3, False), ("f32", 64, 2, False), ("bf16", 128, 2, True), ("f32", 128, 2, True)])
+@pytest.mark.parametrize("dtype,L,hl,two", [("f32", 128, 2, False), ("f32", 128, 3, False), ("f32", 64, 2, False), ("bf16", 128, 2, True), ("f32", 128, 2, True),
+                                                ("f32", 32, 2, False), ("f32", 128, 1, False), ("f32", 128, 4, False), ("bf16", 128, 2, False)])
 def test_device_packed_weight_layouts_equal_the_host_specification(dtype, L, hl, two):
     """the kernels' weight layouts are written on the device from the uploaded parameter vector (k_pack_weights); the host functions
     pack_chunk / _tmajor / 16 / _bf16 / 16_bf16 / _split are their specification: every chunk must be bitwise equal"""
