@@ -277,6 +277,41 @@ typedef struct mgn_rollout_desc {
 typedef enum mgn_inflow_rule { MGN_INFLOW_REFERENCE = 0, MGN_INFLOW_TOLERANT = 1 } mgn_inflow_rule;
 int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d);
 
+/* ---- rollout with the errors reduced on the device: what _validation_step (reference src/strategies.jl:111-134, every strategy's
+ * validation_step, run over every validation trajectory at every checkpoint of train_mgn!, src/MeshGraphNets.jl:404-467) and
+ * eval_network! (:609-635) take from a rollout.  d is read exactly as mgn_rollout reads it (Euler or adaptive Tsit5, both time types,
+ * both inflow rules, the in-place inflow overwrite; the same launches in the same order), d->n_accept / n_reject / n_rhs are filled, and
+ * d->out MAY BE NULL: then no [n_saves][N][O] buffer is held on the device and nothing of that size is downloaded.  With d->out given
+ * the predicted saves are bit-identical to mgn_rollout's.  As each save i is produced it is compared with gt[i]:
+ *   mse_save[i][o] = mean over the N nodes of (x_i - gt_i)^2            eval_network!'s `error` (mean(...; dims = 2), :615-619)
+ *   mse_time[n][o] = mean over the n_saves saves of (x_i - gt_i)^2      _validation_step's `error` (mean(...; dims = 3), :131)
+ *   val_loss       = mean of mse_time over sel                         _validation_step's `mean(error[mask])`
+ * sel holds LINEAR indices into the row-major [N][O] array mse_time (the bytes of Julia's O x N `error`): the reference indexes that
+ * matrix with the vector of node indices `mask` (src/MeshGraphNets.jl:415-417), which is linear indexing -- element sel[i] -
+ * sel_index_base, not "all components of node sel[i]" -- so sel = mask with sel_index_base = 1 reproduces validation_step exactly.  A
+ * caller who wants whole nodes passes the expanded indices node * O + o.  Duplicates count as often as they are listed; indices refer
+ * to the caller's node order.  n_sel == 0: the mean over all N * O elements.
+ * gt: host or device pointer (hipMemcpyDefault), caller's order.  If gt is the same pointer as d->inflow_data (ground truth IS the
+ * inflow data in validation) and d->n_frames >= d->n_saves, the frames uploaded for the right-hand side are compared against and gt is
+ * not uploaded again; the results are the same bits either way.  mse_time: host or device pointer.
+ * Differences and squares are formed in double from the fp32 values and accumulated in double on the device; mse_time is rounded to
+ * float once, mse_save and val_loss come from the double sums.  Every reduction has a fixed order that depends on N, O and n_saves
+ * alone (no floating-point atomics): bitwise repeatable.  One synchronisation, at the end.
+ * Refusals: everything mgn_rollout refuses; MGN_E_ARG for a NULL e or gt, n_gt < n_saves, n_sel < 0, n_sel > 0 without sel, a
+ * sel_index_base other than 0 or 1, a sel entry outside [0, N * O); MGN_E_UNSUPPORTED on a partitioned handle (nranks != 1: call
+ * mgn_rollout and reduce on the host).  The handle stays usable after any of them.                                                 */
+typedef struct mgn_rollout_eval_desc {
+    const float* gt;        /* [n_gt][N][O], host or device, caller's node order; may be the same pointer as d->inflow_data         */
+    int32_t n_gt;           /* >= d->n_saves; save i is compared with gt[i]                                                          */
+    double* mse_save;       /* out, host [n_saves][O], or NULL                                                                       */
+    float* mse_time;        /* out, host or device [N][O], caller's node order, or NULL                                              */
+    const int32_t* sel;     /* host [n_sel] linear indices into [N][O], or NULL                                                      */
+    int64_t n_sel;
+    int32_t sel_index_base; /* 0 or 1                                                                                                */
+    double val_loss;        /* out                                                                                                   */
+} mgn_rollout_eval_desc;
+int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e);
+
 /* ---- solver-based training: the loss and d loss / d ps of one fixed-step Euler solve of ode_func_train (reference src/solve.jl:101-117,
  * strategies.jl:175-196) -- what train_step(::SolverTraining) (strategies.jl:257-292) and one window of train_step(::MultipleShooting)
  * (:312-383) differentiate, with no host work per step and one synchronisation at the end.

@@ -30,6 +30,7 @@ export FeatureGraph, GraphNetwork, step!, load, save!, shooting_grad
 # engine extras (optional fast paths; none is needed for the drop-in)
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
        native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
+export rollout_eval, native_validation_step
 export comm_unique_id, comm_init!, comm_init_file!, comm_barrier, processor_steps_dev!
 
 const LIB = get(ENV, "MGN_HIP_LIB", joinpath(@__DIR__, "..", "meshgraphnets.jl_amd", "lib", "libmgn_hip.so"))
@@ -102,6 +103,17 @@ mutable struct MgnShootingDesc   # mirrors `mgn_shooting_desc` (include/mgn_hip.
     max_batch_nodes::Int64
     n_groups::Int32
     n_passes::Int32
+end
+
+mutable struct MgnRolloutEvalDesc   # mirrors `mgn_rollout_eval_desc` (include/mgn_hip.h), field for field
+    gt::Ptr{Float32}
+    n_gt::Int32
+    mse_save::Ptr{Float64}
+    mse_time::Ptr{Float32}
+    sel::Ptr{Int32}
+    n_sel::Int64
+    sel_index_base::Int32
+    val_loss::Float64
 end
 
 function check(h::Ptr{Cvoid}, rc::Cint)
@@ -791,6 +803,66 @@ function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32
         gs_sum .+= gs; loss_sum += loss
     end
     return (Float32.(gs_sum),), Float32(loss_sum)
+end
+
+"""
+    rollout_eval(solver, mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, start, stop, dt, saves;
+                 sel = nothing, want_pred = false) -> (val_loss, mse_save, mse_time, pred, sol_t)
+
+`native_rollout` with the errors against `gt` (O x N x frames, at least `length(saves)` of them) reduced on the device
+(mgn_rollout_eval): `mse_time = mean((prediction - gt) .^ 2; dims = 3)` (O x N, `_validation_step`'s `error`), `mse_save =
+mean(...; dims = 2)` (O x saves, `eval_network!`'s `error[:, 1, :]`, Float64) and `val_loss = mean(mse_time[sel])` -- `sel` a vector
+of 1-based LINEAR indices into the O x N matrix, exactly what `error[mask]` does with the reference's vector of node indices
+(`nothing`: all elements).  Without `want_pred` the solution is neither kept on the device nor downloaded (`pred === nothing`).  Pass
+the same array as `gt` and `inflow_data` (validation: the ground truth is the inflow data) and it is uploaded once.
+"""
+function rollout_eval(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
+        val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
+        inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, start, stop, dt, saves;
+        sel::Union{Nothing, Vector{Int32}} = nothing, want_pred = false, abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false)
+    name = solver isa Symbol ? solver : nameof(typeof(solver))
+    name in (:Euler, :Tsit5) || throw(ArgumentError("rollout_eval drives Euler and Tsit5; got $name"))
+    sync_params!(mgn, mgn.ps::Vector{Float32})
+    O, N = size(x0)
+    ns = length(saves)
+    out = want_pred ? Array{Float32, 3}(undef, O, N, ns) : nothing
+    mse_save = Matrix{Float64}(undef, O, ns)
+    mse_time = Matrix{Float32}(undef, O, N)
+    sdt = ns > 1 ? saves[2] - saves[1] : one(eltype(saves))
+    f64 = eltype(saves) == Float64
+    d = MgnRolloutDesc(name == :Euler ? 0 : 1, start, stop, dt === nothing ? 0 : dt, sdt, ns, abstol, reltol,
+        pointer(x0), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
+        inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
+        inflow_data === nothing ? 0 : size(inflow_data, 3), out === nothing ? Ptr{Float32}(C_NULL) : pointer(out), 0, 0, 0,
+        tolerant_inflow ? 1 : 0, f64 ? 1 : 0, start, stop, dt === nothing ? 0 : dt, sdt)
+    e = MgnRolloutEvalDesc(pointer(gt), size(gt, 3), pointer(mse_save), pointer(mse_time), sel === nothing ? Ptr{Int32}(C_NULL) : pointer(sel),
+        sel === nothing ? 0 : length(sel), 1, 0.0)
+    # (@ccall: tests/test_rollout_eval_host.py checks this call against the header)
+    rc = GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out gt mse_save mse_time sel @ccall LIB.mgn_rollout_eval(
+        mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, e::Ref{MgnRolloutEvalDesc})::Cint
+    check(mgn.handle, rc)
+    return e.val_loss, mse_save, mse_time, out, collect(saves)
+end
+
+"""
+    native_validation_step(strategy, mgn, gt, node_type_onehot, edge_features, mask, val_mask_row, inflow_mask_row, solver, solver_dt;
+                           want_arrays = false) -> (loss, gt, prediction)
+
+`validation_step(strategy, t)` (src/strategies.jl:111-134 through every strategy's method; called at src/MeshGraphNets.jl:433) in
+one native call: the rollout from `gt[:, :, 1]` over the strategy's interval (`tstart:dt:tstop`; a strategy without one passes
+`sim_interval`), `error = mean((prediction - gt) .^ 2; dims = 3)` and `mean(error[mask])` on the device -- `mask` the reference's
+`Int32.(findall(...))`, indexing the matrix linearly as there.  `gt` (O x N x frames: `vcat` of the target fields) is the inflow data
+too.  The last two results are `nothing` unless `want_arrays` (train_mgn! keeps them for the first trajectory only).
+"""
+function native_validation_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
+        edge_features::Matrix{Float32}, mask::Vector{Int32}, val_mask_row::Union{Nothing, Vector{Float32}},
+        inflow_mask_row::Union{Nothing, Vector{UInt8}}, solver, solver_dt;
+        sim_interval = (strategy.tstart):(strategy.dt):(strategy.tstop), want_arrays = false)
+    ns = length(sim_interval)
+    loss, _, _, pred, _ = rollout_eval(solver, mgn, gt[:, :, 1], node_type_onehot, edge_features, val_mask_row, inflow_mask_row,
+        inflow_mask_row === nothing ? nothing : gt, gt, sim_interval[1], sim_interval[end], solver_dt, sim_interval;
+        sel = mask, want_pred = want_arrays)
+    return Float32(loss), want_arrays ? gt[:, :, 1:ns] : nothing, pred
 end
 
 # ---- multi-GPU: one Julia process per GPU (e.g. under MPI.jl or Distributed), one handle each; the halo exchange (RCCL grouped

@@ -47,6 +47,11 @@ class MgnShootingDesc(C.Structure):
                 ("max_batch_nodes", C.c_int64), ("n_groups", C.c_int32), ("n_passes", C.c_int32)]
 
 
+class MgnRolloutEvalDesc(C.Structure):
+    _fields_ = [("gt", C.POINTER(C.c_float)), ("n_gt", C.c_int32), ("mse_save", C.POINTER(C.c_double)), ("mse_time", C.POINTER(C.c_float)),
+                ("sel", C.POINTER(C.c_int32)), ("n_sel", C.c_int64), ("sel_index_base", C.c_int32), ("val_loss", C.c_double)]
+
+
 ABI_VERSION = 4      # MGN_ABI_VERSION of include/mgn_hip.h these mirrors were written against (tests/test_julia_shim.py compares)
 
 _f32p = C.POINTER(C.c_float)
@@ -95,6 +100,7 @@ PROTOTYPES = {
     "mgn_world_edges_dev": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_float, _i64p]),
     "mgn_edge_set_export": (C.c_int, [_H, C.c_int32, _i32p, _i32p]),
     "mgn_rollout": (C.c_int, [_H, C.POINTER(MgnRolloutDesc)]),
+    "mgn_rollout_eval": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnRolloutEvalDesc)]),
     "mgn_solver_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f32p, _f32p, _f32p, C.c_float, _f32p, C.c_size_t, _f32p]),
     "mgn_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float, _f32p,
                                         C.c_size_t, _f32p]),

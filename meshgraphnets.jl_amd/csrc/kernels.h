@@ -190,6 +190,23 @@ hipError_t launch_overwrite(float* x, const float* frame, const uint8_t* mask, i
 int errnorm_partials();
 hipError_t launch_errnorm(const float* u, const float* unew, const LinComb& lc, float dt, float atol, float rtol, int64_t n,
                           double* partial, hipStream_t s);
+// mgn_rollout_eval.  One save: acc[N][O] += (x - gt)^2 in double, part[save_error_blocks(N)][O] = the per-block sums per component.
+// The block count is a function of the row count alone, so every reduction has one order whatever the device.
+int save_error_blocks(int64_t rows);
+hipError_t launch_save_error(const float* x, const float* gt, double* acc, double* part, int64_t N, int O, hipStream_t s);
+struct EvalFinish {
+    const double* acc;        // [N][O] sums over the saves, the engine's order
+    const double* part;       // [n_saves][save_error_blocks(N)][O]
+    int64_t N; int O, n_saves;
+    const int32_t* gid;       // engine row -> the caller's row (null: the same order)
+    const int64_t* sel;       // [n_val] element indices into acc (null: elements 0 .. n_val - 1)
+    int64_t n_val;
+    float* mse_time;          // [N][O] in the caller's order, or null
+    double* mse_save;         // [n_saves][O], or null
+    double* vpart;            // [save_error_blocks(n_val)]: add them in order and divide by n_val
+    int blocks, val_blocks, time_blocks;   // filled by launch_eval_finish
+};
+hipError_t launch_eval_finish(EvalFinish f, hipStream_t s);
 
 // L in {32,64,128}.  All return hipError_t of the launch.
 bool launch_is_small(int ntiles);

@@ -2413,6 +2413,119 @@ hipError_t launch_errnorm(const float* u, const float* unew, const LinComb& lc, 
     return hipGetLastError();
 }
 
+// ---- rollout evaluation (mgn_rollout_eval): the squared error of every save against its ground-truth frame, reduced where it is made ----
+// One save: q = (x - gt)^2 formed in double from the fp32 values (the product rounded on its own, never contracted into the sums);
+// acc[n][o] += q (each element owned by one thread: the order of its additions is the order of the saves), and per block the sum of q
+// per component -> part[block][o]: a wave reduction, then the four waves through LDS, in a fixed order.  Components are taken four at
+// a time (one pass for O <= 4).  VEC: the row is one load of VEC floats (O == VEC), 1: scalar loads of any O.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_save_error(const float* __restrict__ x, const float* __restrict__ gt, double* __restrict__ acc,
+                                                    double* __restrict__ part, int64_t N, int O) {
+    __shared__ double sh[4][4];
+    for (int o0 = 0; o0 < O; o0 += 4) {
+        const int w = VEC > 1 ? VEC : (O - o0 < 4 ? O - o0 : 4);
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < N; r += (int64_t)gridDim.x * 256) {
+            const int64_t b = r * O + o0;
+            float xv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f};
+            if (VEC == 4) {
+                const float4 a = *reinterpret_cast<const float4*>(x + b), g = *reinterpret_cast<const float4*>(gt + b);
+                xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+                gv[0] = g.x; gv[1] = g.y; gv[2] = g.z; gv[3] = g.w;
+            } else if (VEC == 2) {
+                const float2 a = *reinterpret_cast<const float2*>(x + b), g = *reinterpret_cast<const float2*>(gt + b);
+                xv[0] = a.x; xv[1] = a.y;
+                gv[0] = g.x; gv[1] = g.y;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < w) { xv[j] = x[b + j]; gv[j] = gt[b + j]; }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < w) {
+                    const double dd = (double)xv[j] - (double)gv[j];
+                    const double q = __dmul_rn(dd, dd);
+                    acc[b + j] += q;
+                    s[j] += q;
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_xor(s[j], off, 64);
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sh[j][threadIdx.x >> 6] = s[j];
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < w) part[(int64_t)blockIdx.x * O + o0 + threadIdx.x] = ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
+        __syncthreads();
+    }
+}
+
+// Once after the solve, three groups of blocks (EvalFinish):
+//   val_blocks:   the mean over the saves, acc / n_saves, of the n_val selected elements (sel: their indices in the engine's order; null:
+//                 elements 0 .. n_val - 1), summed per block in k_save_error's order -> vpart[block]; the caller adds them in block order
+//   time_blocks:  mse_time[caller's row][o] = float(acc[row][o] / n_saves), rounded once
+//   the others:   mse_save[i][o] = (sum over the blocks, in block order, of part[i][block][o]) / N, one thread per (i, o)
+__global__ __launch_bounds__(256) void k_eval_finish(EvalFinish f) {
+    __shared__ double sh[4];
+    const double ns = (double)f.n_saves;
+    int blk = blockIdx.x;
+    if (blk < f.val_blocks) {
+        double s = 0.0;
+        for (int64_t j = (int64_t)blk * 256 + threadIdx.x; j < f.n_val; j += (int64_t)f.val_blocks * 256) s += f.acc[f.sel ? f.sel[j] : j] / ns;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) f.vpart[blk] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+        return;
+    }
+    blk -= f.val_blocks;
+    if (blk < f.time_blocks) {
+        const int64_t n = f.N * f.O;
+        for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < n; i += (int64_t)f.time_blocks * 256) {
+            const int64_t r = i / f.O;
+            const int o = (int)(i - r * f.O);
+            f.mse_time[(f.gid ? (int64_t)f.gid[r] : r) * f.O + o] = (float)(f.acc[i] / ns);
+        }
+        return;
+    }
+    blk -= f.time_blocks;
+    const int64_t t = (int64_t)blk * 256 + threadIdx.x;
+    if (t >= (int64_t)f.n_saves * f.O) return;
+    const int64_t i = t / f.O;
+    const int o = (int)(t - i * f.O);
+    const double* p = f.part + (size_t)i * f.blocks * f.O + o;
+    double s = 0.0;
+    for (int b = 0; b < f.blocks; ++b) s += p[(size_t)b * f.O];
+    f.mse_save[t] = s / (double)f.N;
+}
+
+int save_error_blocks(int64_t rows) {
+    const int64_t b = (rows + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
+hipError_t launch_save_error(const float* x, const float* gt, double* acc, double* part, int64_t N, int O, hipStream_t s) {
+    if (N <= 0 || O <= 0) return hipSuccess;
+    const dim3 grid((unsigned)save_error_blocks(N)), block(256);
+    if (O == 4) hipLaunchKernelGGL(k_save_error<4>, grid, block, 0, s, x, gt, acc, part, N, O);
+    else if (O == 2) hipLaunchKernelGGL(k_save_error<2>, grid, block, 0, s, x, gt, acc, part, N, O);
+    else hipLaunchKernelGGL(k_save_error<1>, grid, block, 0, s, x, gt, acc, part, N, O);
+    return hipGetLastError();
+}
+hipError_t launch_eval_finish(EvalFinish f, hipStream_t s) {
+    if (f.N <= 0 || f.O <= 0 || f.n_saves <= 0) return hipSuccess;
+    f.blocks = save_error_blocks(f.N);
+    f.val_blocks = save_error_blocks(f.n_val);
+    f.time_blocks = f.mse_time ? save_error_blocks(f.N * f.O) : 0;
+    const int save_blocks = f.mse_save ? (int)(((int64_t)f.n_saves * f.O + 255) / 256) : 0;
+    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)(f.val_blocks + f.time_blocks + save_blocks)), dim3(256), 0, s, f);
+    return hipGetLastError();
+}
+
 // ================================================================================================
 // launch wrappers
 // ================================================================================================

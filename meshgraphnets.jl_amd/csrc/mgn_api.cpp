@@ -1880,10 +1880,18 @@ struct Rollout {
     // ---- saves ----
     int saved = 0;                         // saves taken
     std::vector<int64_t> save_step;        // the accepted steps before each save taken
+    // mgn_rollout_eval: every save is compared with its ground-truth frame as it is produced (k_save_error) -- gt [n_saves][n] in the
+    // engine's order, acc [n] doubles, part [n_saves][save_error_blocks(nrows)][O] -- and kept only if the caller wants the solution
+    const float* ev_gt = nullptr;
+    double *ev_acc = nullptr, *ev_part = nullptr;
     // saves[saved] <- u, the state after steps_done accepted steps
     int save(int64_t steps_done) {
         save_step.push_back(steps_done);
-        HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved++ * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (ev_gt)
+            HIPCHK(h, launch_save_error(u, ev_gt + (size_t)saved * n, ev_acc, ev_part + (size_t)saved * save_error_blocks(nrows) * h->cfg.O, nrows,
+                                        h->cfg.O, h->stream));
+        if (saves) HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        ++saved;
         return MGN_OK;
     }
     // the saves a fixed-step plan (the accepted steps before every save, fixed_grid) takes after steps_done steps
@@ -2131,24 +2139,24 @@ int upload_statics(mgn_handle* h, const mgn_rollout_desc* d, const float* x0, ch
     return MGN_OK;
 }
 
-}  // namespace
-
-int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
+// mgn_rollout (e null) and mgn_rollout_eval (e: its checked descriptor, one partition): the same solve, the same launches in the same
+// order; with e every save is reduced against its ground-truth frame as it is produced (Rollout::save) and d->out is optional
+int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who) {
     const bool lnall = h && h->cfg.ln_dims == MGN_LN_ALL;
     if (int rc = need(h, true, true, !lnall, true)) return rc;
     const mgn_config& c = h->cfg;
     const bool part = c.nranks != 1;      // partitioned: every rank integrates the rows it owns; error norms are reduced over the ranks
-    if (part) if (int rc = need_comm(h, "mgn_rollout")) return rc;
-    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", "mgn_rollout");
-    if (!d || !d->x0 || !d->out || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "mgn_rollout: null argument");
-    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "mgn_rollout: Fn < O");
+    if (part) if (int rc = need_comm(h, who)) return rc;
+    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
+    if (!d || !d->x0 || (!d->out && !e) || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
     const TimeGrid T(d);
-    if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "mgn_rollout: bad time grid");
-    if (d->solver == 0 && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "mgn_rollout: Euler needs dt > 0");
-    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "mgn_rollout: unknown inflow_rule");
-    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "mgn_rollout: solver must be 0 (Euler) or 1 (Tsit5)");
-    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "mgn_rollout: inflow mask and data go together");
-    if (d->solver == 1 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "mgn_rollout: tolerances must be > 0");
+    if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (d->solver == 0 && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
+    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "%s: unknown inflow_rule", who);
+    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
+    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "%s: inflow mask and data go together", who);
+    if (d->solver == 1 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
     const LocalGraph& g = h->g;
     invalidate_static(h);
     Rollout R(h, d, T);
@@ -2157,24 +2165,63 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     R.n_global = (int64_t)g.N * c.O;
     R.nrows = nloc;
     const size_t nb = (size_t)R.n * 4;
-    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
+    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = d->out ? (size_t)d->n_saves * nb : 0;
     const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
+    // evaluation: ground truth that IS the inflow data is compared where upload_engine_order puts the frames; the selection in the
+    // engine's order (n_sel == 0: all elements, no index array)
+    const bool gt_is_frames = e && e->gt == d->inflow_data && d->n_frames >= d->n_saves;
+    const int eblk = e ? save_error_blocks(nloc) : 0;
+    const int64_t n_val = e ? (e->n_sel > 0 ? e->n_sel : R.n) : 0;
+    std::vector<int64_t> sel;
+    if (e && e->n_sel > 0) {
+        std::vector<int32_t> g2l;
+        if (g.renumbered) {
+            g2l.resize((size_t)g.N);
+            for (int32_t i = 0; i < g.N; ++i) g2l[(size_t)g.own_gid[i]] = i;
+        }
+        sel.resize((size_t)e->n_sel);
+        for (int64_t i = 0; i < e->n_sel; ++i) {
+            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;      // (checked by mgn_rollout_eval)
+            sel[(size_t)i] = g.renumbered ? (int64_t)g2l[(size_t)(li / c.O)] * c.O + li % c.O : li;
+        }
+    }
     Arena a;
     const size_t o_u = a.take(nb), o_un = a.take(nb), o_ut = a.take(nb);
     size_t o_k[7];
     for (auto& o : o_k) o = a.take(nb);
     const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)nloc), o_part = a.take(errnorm_partials() * sizeof(double));
     R.elat0_off = a.take(eb);
+    const size_t o_eacc = a.take(e ? (size_t)R.n * 8 : 0), o_epart = a.take((size_t)d->n_saves * eblk * c.O * 8),
+                 o_egt = a.take(e && !gt_is_frames ? (size_t)d->n_saves * nb : 0), o_etmp = a.take(e && !gt_is_frames && g.renumbered ? nb : 0),
+                 o_esel = a.take(sel.size() * 8), o_evp = a.take(e ? (size_t)save_error_blocks(n_val) * 8 : 0),
+                 o_ems = a.take(e && e->mse_save ? (size_t)d->n_saves * c.O * 8 : 0), o_emt = a.take(e && e->mse_time ? nb : 0);
     HIPCHK(h, h->ode.ensure(a.off));
     char* base = h->ode.as<char>();
     R.u = (float*)(base + o_u); R.unew = (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
     for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[j]);
     R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
-    R.saves = (float*)(base + o_sv);
+    R.saves = d->out ? (float*)(base + o_sv) : nullptr;
     R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
     R.partial = (double*)(base + o_part);
     if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
     if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
+    if (e) {
+        float* gtl = (float*)(base + o_egt);
+        for (int s = 0; s < d->n_saves && !gt_is_frames; ++s) {     // as solver_targets: host or device, gathered on the device when renumbered
+            const float* src = e->gt + (size_t)s * R.n;
+            if (!g.renumbered) {
+                HIPCHK(h, hipMemcpyAsync(gtl + (size_t)s * R.n, src, nb, hipMemcpyDefault, h->stream));
+            } else {
+                HIPCHK(h, hipMemcpyAsync(base + o_etmp, src, nb, hipMemcpyDefault, h->stream));
+                HIPCHK(h, launch_permute_rows(gtl + (size_t)s * R.n, (const float*)(base + o_etmp), h->d_own_gid.as<int32_t>(), g.N, c.O, false, h->stream));
+            }
+        }
+        if (!sel.empty()) HIPCHK(h, hipMemcpyAsync(base + o_esel, sel.data(), sel.size() * 8, hipMemcpyHostToDevice, h->stream));
+        R.ev_gt = gt_is_frames ? R.frames : gtl;
+        R.ev_acc = (double*)(base + o_eacc);
+        R.ev_part = (double*)(base + o_epart);
+        HIPCHK(h, hipMemsetAsync(R.ev_acc, 0, (size_t)R.n * 8, h->stream));
+    }
 
     d->n_accept = d->n_reject = 0;
     if (d->solver == 0) {
@@ -2196,17 +2243,67 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
         while (R.saved < d->n_saves)      // (t1 short of the last stop: repeat the final state)
             if (int rc = R.save(nsteps)) return rc;
     } else {
-        if (int rc = R.tsit5_adaptive("mgn_rollout", nullptr)) return rc;
+        if (int rc = R.tsit5_adaptive(who, nullptr)) return rc;
     }
     if (part) {     // every rank returns the complete solution
         for (int i = 0; i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
-    } else if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) {
-        return rc;
+    } else if (d->out) {
+        if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
+    }
+    std::vector<double> vpart;
+    if (e) {
+        EvalFinish f{};
+        f.acc = R.ev_acc; f.part = R.ev_part; f.N = g.N; f.O = c.O; f.n_saves = d->n_saves;
+        f.gid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+        f.sel = sel.empty() ? nullptr : (const int64_t*)(base + o_esel);
+        f.n_val = n_val;
+        f.mse_time = e->mse_time ? (float*)(base + o_emt) : nullptr;
+        f.mse_save = e->mse_save ? (double*)(base + o_ems) : nullptr;
+        f.vpart = (double*)(base + o_evp);
+        HIPCHK(h, launch_eval_finish(f, h->stream));
+        vpart.resize((size_t)save_error_blocks(n_val));
+        HIPCHK(h, hipMemcpyAsync(vpart.data(), f.vpart, vpart.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        if (e->mse_save) HIPCHK(h, hipMemcpyAsync(e->mse_save, f.mse_save, (size_t)d->n_saves * c.O * 8, hipMemcpyDeviceToHost, h->stream));
+        if (e->mse_time) HIPCHK(h, hipMemcpyAsync(e->mse_time, f.mse_time, nb, hipMemcpyDefault, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     d->n_rhs = R.n_rhs;
+    if (e) {      // the blocks' sums in block order
+        double s = 0.0;
+        for (double v : vpart) s += v;
+        e->val_loss = s / (double)n_val;
+    }
     return MGN_OK;
+}
+
+}  // namespace
+
+int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
+    return rollout_solve(h, d, nullptr, "mgn_rollout");
+} MGN_CATCH(h)
+
+int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) try {
+    static const char* who = "mgn_rollout_eval";
+    if (!h) return MGN_E_ARG;
+    // the descriptor first (a host-only handle answers it too)
+    if (!d || !e || !e->gt) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (e->n_gt < d->n_saves) return fail(h, MGN_E_ARG, "%s: n_gt = %d ground-truth frames for n_saves = %d saves", who, e->n_gt, d->n_saves);
+    if (e->n_sel < 0 || (e->n_sel > 0 && !e->sel)) return fail(h, MGN_E_ARG, "%s: n_sel must be >= 0, and sel given when it is > 0", who);
+    if (e->sel_index_base != 0 && e->sel_index_base != 1) return fail(h, MGN_E_ARG, "%s: sel_index_base must be 0 or 1", who);
+    if (h->cfg.nranks != 1)
+        return fail(h, MGN_E_UNSUPPORTED, "%s drives one partition: on a partitioned handle call mgn_rollout and reduce the solution on the host", who);
+    if (h->have_graph) {
+        const int64_t n = (int64_t)h->g.N * h->cfg.O;
+        for (int64_t i = 0; i < e->n_sel; ++i) {
+            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;
+            if (li < 0 || li >= n)
+                return fail(h, MGN_E_ARG, "%s: sel[%lld] = %d is outside the %lld elements of the [N][O] error array (index base %d)", who,
+                            (long long)i, e->sel[i], (long long)n, e->sel_index_base);
+        }
+    }
+    e->val_loss = 0.0;
+    return rollout_solve(h, d, e, who);      // (without a graph it refuses before sel is read)
 } MGN_CATCH(h)
 
 // ---- solver-based training (SolverTraining / MultipleShooting): loss and gradient of one solved window ------------------------------

@@ -316,12 +316,9 @@ class Engine:
         self._chk(self.lib.mgn_ode_step(self.h, f32(x), f32(oh), f32(ef), f32(vm), f32(out)))
         return out
 
-    def rollout(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None,
-                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32):
-        """Native device-side `rollout` (reference src/solve.jl:42-68).  solver: "Euler" (fixed dt) or "Tsit5".
-        inflow_rule: "reference" = `floor(Int, t / saves_dt) + 1` in the solver's time type, no tolerance, out of range raises
-        (src/solve.jl:151); "tolerant" = + 1e-3, clamped (step k reads frame k).  time_type: np.float32 (the example's `0.0f0:0.01f0:5.99f0`) or np.float64.
-        Returns (sol_u [n_saves][N][O], stats dict)."""
+    def _rollout_desc(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data, abstol,
+                      reltol, inflow_rule, time_type):
+        """The descriptor of a rollout / rollout_eval call, without `out`; returns (d, the arrays it points into: inflow data last)."""
         O, Fn = self.cfg.O, self.cfg.Fn
         d = _capi.MgnRolloutDesc()
         d.solver = {"Euler": 0, "Tsit5": 1}[solver]
@@ -337,14 +334,61 @@ class Engine:
         idata = _c32(inflow_data) if inflow_data is not None else None
         if idata is not None and idata.shape[1:] != (self.N, O):
             raise ValueError("DimensionMismatch: inflow_data must be [frames][N][O]")
-        out = np.zeros((n_saves, self.N, O), np.float32)
         d.x0, d.node_type_onehot, d.ef_raw, d.val_mask = f32(x0), f32(oh), f32(ef), f32(vm)
         d.inflow_mask = im.ctypes.data_as(C.POINTER(C.c_uint8)) if im is not None else None
         d.inflow_data = f32(idata)
         d.n_frames = idata.shape[0] if idata is not None else 0
+        return d, (x0, oh, ef, vm, im, idata)
+
+    def rollout(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None,
+                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32):
+        """Native device-side `rollout` (reference src/solve.jl:42-68).  solver: "Euler" (fixed dt) or "Tsit5".
+        inflow_rule: "reference" = `floor(Int, t / saves_dt) + 1` in the solver's time type, no tolerance, out of range raises
+        (src/solve.jl:151); "tolerant" = + 1e-3, clamped (step k reads frame k).  time_type: np.float32 (the example's `0.0f0:0.01f0:5.99f0`) or np.float64.
+        Returns (sol_u [n_saves][N][O], stats dict)."""
+        d, keep = self._rollout_desc(solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data,
+                                     abstol, reltol, inflow_rule, time_type)
+        out = np.zeros((n_saves, self.N, self.cfg.O), np.float32)
         d.out = f32(out)
         self._chk(self.lib.mgn_rollout(self.h, C.byref(d)))
+        del keep
         return out, dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)
+
+    def rollout_eval(self, solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None, inflow_mask=None,
+                     inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, sel=None, sel_index_base=0,
+                     want_pred=False, mse_time_out=None):
+        """`rollout` with the errors against gt [n_gt >= n_saves][N][O] reduced on the device (mgn_rollout_eval): what _validation_step
+        (reference src/strategies.jl:111-134) and eval_network! (src/MeshGraphNets.jl:609-635) take from a rollout.  The solve is
+        rollout's (same arguments, bit-identical saves); without want_pred the solution is neither kept on the device nor downloaded.
+        gt: NumPy array or contiguous fp32 device tensor; the SAME object as inflow_data reaches the C call as one pointer and is
+        uploaded once.  sel: LINEAR indices (sel_index_base 0 or 1) into the [N][O] array mse_time -- the reference's `error[mask]`
+        with its vector of node indices is this, not "every component of node sel[i]"; None: all N * O elements.  mse_time_out: a
+        NumPy array or device tensor [N][O] to receive mse_time (default: a new NumPy array).
+        Returns {"val_loss": mean(mse_time[sel]), "mse_save" [n_saves][O] float64 (mean over the nodes), "mse_time" [N][O] float32
+        (mean over the saves), "pred" [n_saves][N][O] or None, "stats"}."""
+        O = self.cfg.O
+        d, keep = self._rollout_desc(solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data,
+                                     abstol, reltol, inflow_rule, time_type)
+        e = _capi.MgnRolloutEvalDesc()
+        if gt is inflow_data:                           # validation: the ground truth is the inflow data -- one array, one pointer
+            gt_keep, e.gt, e.n_gt = keep[-1], d.inflow_data, d.n_frames
+        else:
+            if len(gt.shape) != 3:
+                raise ValueError("DimensionMismatch: gt must be [frames][N][O]")
+            gt_keep, e.gt = _host_or_device(gt, (gt.shape[0], self.N, O))
+            e.n_gt = gt.shape[0]
+        pred = np.zeros((n_saves, self.N, O), np.float32) if want_pred else None
+        d.out = f32(pred)
+        mse_save = np.zeros((max(int(n_saves), 0), O), np.float64)
+        e.mse_save = mse_save.ctypes.data_as(C.POINTER(C.c_double))
+        mse_time, e.mse_time = _host_or_device(np.zeros((self.N, O), np.float32) if mse_time_out is None else mse_time_out, (self.N, O),
+                                               writable=True)
+        si = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1) if sel is not None else None
+        e.sel, e.n_sel, e.sel_index_base = i32(si), (si.size if si is not None else 0), int(sel_index_base)
+        self._chk(self.lib.mgn_rollout_eval(self.h, C.byref(d), C.byref(e)))
+        del keep, gt_keep
+        return {"val_loss": e.val_loss, "mse_save": mse_save, "mse_time": mse_time, "pred": pred,
+                "stats": dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)}
 
     def _solver_desc(self, solver, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask, inflow_mask, inflow_data,
                      loss_scale, cont_target, inflow_rule, time_type, want_pred, out, abstol=0.0, reltol=0.0):

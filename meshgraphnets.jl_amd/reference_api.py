@@ -11,6 +11,7 @@ functions are written here in NumPy float32 to drive the engine exactly the way 
     rollout (Euler branch) reference src/solve.jl:42-68  (`solve(prob, solver; adaptive=false, dt, saveat)`)
     train_step (solver strategies with Euler() / Tsit5())  reference src/strategies.jl:175-196, 238-383 (Engine.solver_grad /
                            Engine.solver_grad_tsit5 per solved window)
+    validation_step, rollout_errors  reference src/strategies.jl:111-134, src/MeshGraphNets.jl:609-628 (Engine.rollout_eval)
     GraphNetCore surface   one_hot, triangles_to_edges, parse_edges, mse_reduce, NormaliserOfflineMinMax,
                            NormaliserOfflineMeanStd, NormaliserOnline, inverse_data (docs/src/graph_net_core.md)
 
@@ -572,3 +573,52 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
         gs_sum = np.asarray(gs, np.float64) if gs_sum is None else gs_sum + gs
         loss_sum += float(loss)
     return gs_sum, loss_sum
+
+
+def validation_step(eng, data_gt, node_type_onehot, ef_raw, sim_interval, mask, solver="Tsit5", solver_dt=None, val_mask=None,
+                    inflow_mask=None, mask_index_base=0, time_type=F32, inflow_rule="reference", abstol=1e-6, reltol=1e-3,
+                    want_arrays=False):
+    """_validation_step (reference src/strategies.jl:111-134; every strategy's validation_step) in one native call, Engine.rollout_eval:
+    a rollout from data_gt[0] over sim_interval = (tstart, dt, tstop) saved at tstart:dt:tstop, `error = mean((prediction - gt) .^ 2;
+    dims = 3)` and `mean(error[mask])` -- reduced on the device, the solution downloaded only with want_arrays.  data_gt [T][N][O]: the
+    trajectory's target fields (T >= the number of saves); with an inflow_mask [N] it is the inflow data too, and is uploaded once.
+    mask: the reference's vector of node indices (mask_index_base 0, or 1 as in Julia).  Indexing the O x N matrix `error` with it is
+    LINEAR indexing: it selects the elements mask[i] of the [N][O] array, not the rows -- reproduced as it is.
+    Returns (loss, None, None) or, with want_arrays, (loss, gt [n_saves][N][O], prediction [n_saves][N][O])."""
+    tstart, dt, tstop = sim_interval
+    n_saves = _range_length(tstart, dt, tstop)
+    if data_gt.shape[0] < n_saves:
+        raise ValueError(f"BoundsError: {n_saves} saves, {data_gt.shape[0]} ground-truth frames")
+    r = eng.rollout_eval(solver, np.asarray(data_gt[0]), node_type_onehot, ef_raw, data_gt, tstart, _range_at(tstart, dt, n_saves - 1, time_type),
+                         dt, n_saves, dt=solver_dt or 0.0, val_mask=val_mask, inflow_mask=inflow_mask,
+                         inflow_data=data_gt if inflow_mask is not None else None, abstol=abstol, reltol=reltol, inflow_rule=inflow_rule,
+                         time_type=time_type, sel=np.asarray(mask, np.int32), sel_index_base=mask_index_base, want_pred=want_arrays)
+    if not want_arrays:
+        return r["val_loss"], None, None
+    return r["val_loss"], np.asarray(data_gt[:n_saves]), r["pred"]
+
+
+def rollout_errors(eng, data_gt, node_type_onehot, ef_raw, start, stop, dt, saves, mse_steps, solver="Tsit5", val_mask=None, inflow_mask=None,
+                   time_type=F32, inflow_rule="reference", abstol=1e-6, reltol=1e-3):
+    """The error table of eval_network! (reference src/MeshGraphNets.jl:609-628) without the solution leaving the device: a rollout
+    from data_gt[0] over (start, stop) saved at `saves` (evenly spaced times from `start`), `error = mean((prediction - gt) .^ 2;
+    dims = 2)` as Engine.rollout_eval's mse_save, and for every horizon of mse_steps
+        mse = mean(error[:, 1, k]),  cum_mse = mean(error[:, 1, 1:k]),  cum_rmse = sqrt(cum_mse),   k = findfirst(==(horizon), saves).
+    dt: the fixed solver step, or None (adaptive Tsit5), as eval_network!'s.  Returns (error [n_saves][O] float64, {horizon: (mse,
+    cum_mse, cum_rmse)})."""
+    saves = np.asarray(saves, dtype=time_type)
+    n_saves = int(saves.size)
+    saves_dt = float(saves[1] - saves[0]) if n_saves > 1 else float(stop - start) or 1.0
+    r = eng.rollout_eval(solver, np.asarray(data_gt[0]), node_type_onehot, ef_raw, data_gt, start, stop, saves_dt, n_saves, dt=dt or 0.0,
+                         val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=data_gt if inflow_mask is not None else None,
+                         abstol=abstol, reltol=reltol, inflow_rule=inflow_rule, time_type=time_type)
+    error = r["mse_save"]
+    table = {}
+    for horizon in mse_steps:
+        hit = np.nonzero(saves == np.dtype(time_type).type(horizon))[0]
+        if hit.size == 0:
+            raise ValueError(f"horizon {horizon} is not a save point")     # (reference: findfirst gives nothing)
+        k = int(hit[0])
+        cum = float(np.mean(error[:k + 1]))
+        table[horizon] = (float(np.mean(error[k])), cum, float(np.sqrt(cum)))
+    return error, table
