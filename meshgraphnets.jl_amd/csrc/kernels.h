@@ -175,6 +175,7 @@ hipError_t launch_node_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream
 hipError_t launch_project_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);
 hipError_t launch_edge_ring_h(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip: the ring kernel on two fp16 pieces, three products
 size_t edge_ring_h_lds();
+int set_ringh_stream(int on);   // debug/tests: the switch edge_ring_h_streamed() reads (MGN_RINGH_STREAM is its initial value); returns the old value
 int edge_ring_h_streamed();     // 1: launch_edge_ring_h runs k_edge_ring_hs (family codes 16 / 17), 0: k_edge_ring_h (13 / 14)
 hipError_t launch_edge_ring(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip
 hipError_t launch_node_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip
@@ -227,12 +228,14 @@ int c16_split_enabled();
 int set_c16_row_tiles(int rt);  // debug/tests: 16-edge tiles per block of the small-graph edge kernel (0: chosen by size); returns the old value
 int set_kernel_path(int p);   // debug/tests: 0 auto, 1 resident, 2 streaming, 3 cooperative, 4 GEN (general hidden_layers) kernels; returns the old value
 int get_kernel_path();
+int set_num_cus(int n);        // debug/tests: the CU count every size decision of the inference launches reads (0: the device's; a multiple of NUM_XCD up to it); returns the old value, -1 if refused
 hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s);
 hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s);
 hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);   // mode-2 work with both chunks LDS-resident
 hipError_t launch_node_project_fused(int L, const NodeArgs& a, hipStream_t s, bool* launched);   // k_node_ring_hs where it applies (else *launched = false)
 hipError_t launch_node_ring_hs(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);            // split.hip
 int node_ring_hs_enabled();
+int set_node_ring_hs(int on);   // debug/tests: 1 (default) k_node_ring_hs where it applies, 0 k_node_split_h + k_project_split_h (MGN_NODE_RING_HS is its initial value); returns the old value
 hipError_t launch_enc_node(int L, const EncNodeArgs& a, hipStream_t s);
 hipError_t launch_enc_edge(int L, const EncEdgeArgs& a, hipStream_t s);
 hipError_t launch_decode(int L, const DecArgs& a, hipStream_t s);

@@ -2530,7 +2530,7 @@ hipError_t launch_eval_finish(EvalFinish f, hipStream_t s) {
 // launch wrappers
 // ================================================================================================
 static int g_num_cu = 0;
-static int num_cus() {
+static int device_cus() {
     if (g_num_cu == 0) {
         int dev = 0;
         hipDeviceProp_t p;
@@ -2540,6 +2540,17 @@ static int num_cus() {
             g_num_cu = 256;
     }
     return g_num_cu;
+}
+// Every size decision of the inference launches reads the CU count here.  Tests shrink it (mgn_debug_num_cus) so that a mesh of a few
+// thousand tiles walks the kernels the way a mesh of 32 times the size does on the whole device: placement is speed only (TileWalk,
+// frag.hpp), so a launch of 8 blocks must be as correct as one of 256.  0: the device's own count.
+static int g_num_cu_test = 0;
+static int num_cus() { return g_num_cu_test ? g_num_cu_test : device_cus(); }
+int set_num_cus(int n) {
+    if (n != 0 && (n < NUM_XCD || n > device_cus() || n % NUM_XCD != 0)) return -1;
+    const int old = g_num_cu_test;
+    g_num_cu_test = n;
+    return old;
 }
 
 constexpr size_t LDS_BYTES = 160 * 1024;
@@ -2681,7 +2692,7 @@ static LaunchCfg gen_launch(int L, int ntiles) {
 // pinned weight rings (coop_chain_primed<true>) while a launch has at most MGN_COOP_FENCE_TILES_PER_CU (default 4) tiles per CU
 static bool coop_fence(int ntiles) {
     static const int per_cu = [] { const char* e = getenv("MGN_COOP_FENCE_TILES_PER_CU"); return e ? atoi(e) : 4; }();
-    return ntiles <= per_cu * 256;
+    return ntiles <= per_cu * num_cus();
 }
 static size_t coop_lds() { return (size_t)2 * 16 * 64 * 16 + (size_t)T_COUNT * 128 * 4; }
 static bool coop_ok(int L, int ntiles, const float* const* chunk_t, bool edge = false) {

@@ -3701,6 +3701,16 @@ int mgn_debug_fp32_split(int on) { return set_fp32_split(on); }
 // 1 (default): the split path computes on two fp16 pieces per operand and three piece products (k_edge_ring_h), 0: on three bf16 pieces
 // and six products (k_edge_ring); returns the old value
 int mgn_debug_split_f16(int on) { return set_split_f16(on); }
+// split path on two fp16 pieces: 1 (default) k_edge_ring_hs (every weight piece streamed, family codes 16 / 17), 0 k_edge_ring_h (13 / 14);
+// MGN_RINGH_STREAM is the initial value; returns the old value
+int mgn_debug_ringh_stream(int on) { return set_ringh_stream(on); }
+// 1 (default): node MLP + projection of the next step as one k_node_ring_hs launch where both would run (family code 11), 0: k_node_split_h
+// (10) + k_project_split_h; MGN_NODE_RING_HS is the initial value; returns the old value
+int mgn_debug_node_ring_hs(int on) { return set_node_ring_hs(on); }
+// tests: the CU count that every size decision of the inference launches reads, so that a small mesh reaches the kernels, block shapes and
+// tile walks of a mesh (device CUs / n) times its size.  n = 0: the device's own count; otherwise a multiple of 8 (one block per XCD label)
+// from 8 up to the device's count.  Returns the old value (0: none was set), -1 if n is refused (nothing changes).
+int mgn_debug_num_cus(int n) { return set_num_cus(n); }
 // the same switch for the streaming kernels of the training step (train.hip: train_chunk); returns the old value
 int mgn_debug_train_f16(int on) { return set_train_f16(on); }
 // tests: every chunk the device packed (k_pack_weights) against the host functions that specify the layouts; returns the number of

@@ -1675,6 +1675,7 @@ hipError_t launch_edge_ring(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t 
 }
 static int g_ringh_stream = [] { const char* e = getenv("MGN_RINGH_STREAM"); return e ? atoi(e) : 1; }();   // 1 (default): k_edge_ring_hs (no resident weight piece, e parked in LDS: read once); 0: k_edge_ring_h
 int edge_ring_h_streamed() { return g_ringh_stream; }
+int set_ringh_stream(int on) { const int old = g_ringh_stream; g_ringh_stream = on; return old; }
 hipError_t launch_edge_ring_h(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s) {
     static bool attr_set8 = false, attr_set4 = false, attr_s8 = false, attr_s4 = false;
     if (g_ringh_stream) {
@@ -1699,6 +1700,7 @@ hipError_t launch_node_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream
 }
 static int g_node_ring_hs = [] { const char* e = getenv("MGN_NODE_RING_HS"); return e ? atoi(e) : 1; }();   // 1 (default): node MLP + projection as k_node_ring_hs where both would run; 0: k_node_split_h + k_project_split_h
 int node_ring_hs_enabled() { return g_node_ring_hs; }
+int set_node_ring_hs(int on) { const int old = g_node_ring_hs; g_node_ring_hs = on; return old; }
 hipError_t launch_node_ring_hs(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
     static bool attr_set = false;
     LaunchCfg ls = lc;

@@ -159,8 +159,12 @@ def test_error_paths():
 
 
 def test_mid_size_mesh_with_tail_split():
-    """90 000 nodes / 537 602 edges (16.8 k edge tiles): the LDS-resident persistent kernels with the last partial round of
-    the edge walk handed to the cooperative kernel -- two kernel families inside one edge step, against the oracle."""
+    """90 000 nodes / 537 602 edges (16.8 k edge tiles, 66 per CU; 2 813 node tiles) against the oracle: the default kernels of a mid-size
+    mesh -- k_edge_ring_hs<8> (family 16) on nine rounds of eight-wave blocks, the spread walk, and on the node side k_node_ring_hs with
+    k_node_split_h on the last step (10), which projects nothing.  (The name is history: when the fp32-MFMA persistent kernels ran here the
+    last partial round of the edge walk went to the cooperative kernel.  That hand-over needs mgn_debug_fp32_split(0) and 24 rounds today;
+    test_gpu_large_mesh_regimes.py::test_fp32_mfma_persistent_kernels_and_tail_split covers it.)"""
+    from util import last_kernels
     from mgn_amd import synth as sy
     pos, s, r = sy.mesh_1m(7, 300, 300)
     N, E = pos.shape[0], s.size
@@ -173,6 +177,7 @@ def test_mid_size_mesh_with_tail_split():
     eng.set_params(ps)
     eng.set_graph(s, r, N)
     v1, e1 = eng.processor_steps(v, e, 2)
+    assert last_kernels() == (16, 10), last_kernels()
     rv, re = orc.processor_steps(ps, cfg, v, e, s, r, 2)
     assert rel_max(v1, rv) <= TOL_15 and rel_max(e1, re) <= TOL_15
 

@@ -84,6 +84,41 @@ def set_split_f16(on):
     return lib.mgn_debug_split_f16(on)
 
 
+def set_ringh_stream(on):
+    """Split path on two fp16 pieces, edge step: 1 (default) = k_edge_ring_hs (every weight piece streamed, family codes 16 / 17),
+    0 = k_edge_ring_h (13 / 14).  Returns the old value."""
+    lib = mgn_amd.load()
+    lib.mgn_debug_ringh_stream.restype = __import__("ctypes").c_int
+    lib.mgn_debug_ringh_stream.argtypes = [__import__("ctypes").c_int]
+    return lib.mgn_debug_ringh_stream(on)
+
+
+def set_node_ring_hs(on):
+    """Split path on two fp16 pieces, node side: 1 (default) = node MLP + projection in one k_node_ring_hs launch (family code 11),
+    0 = k_node_split_h (10) + k_project_split_h.  Returns the old value."""
+    lib = mgn_amd.load()
+    lib.mgn_debug_node_ring_hs.restype = __import__("ctypes").c_int
+    lib.mgn_debug_node_ring_hs.argtypes = [__import__("ctypes").c_int]
+    return lib.mgn_debug_node_ring_hs(on)
+
+
+def set_num_cus(n):
+    """The CU count every size decision of the inference launches reads (tests only): 0 = the device's own, else a multiple of 8 from 8
+    up to the device's count.  Set it before the engine is created.  Returns the old value (0: no override), -1 if n is refused."""
+    lib = mgn_amd.load()
+    lib.mgn_debug_num_cus.restype = __import__("ctypes").c_int
+    lib.mgn_debug_num_cus.argtypes = [__import__("ctypes").c_int]
+    return lib.mgn_debug_num_cus(n)
+
+
+def last_kernels():
+    """(edge, node) family codes of the last launches (kernels.hip: launch_edge_step, launch_node_step; table in DESIGN.md)."""
+    lib = mgn_amd.load()
+    lib.mgn_debug_last_edge_kernel.restype = __import__("ctypes").c_int
+    lib.mgn_debug_last_node_kernel.restype = __import__("ctypes").c_int
+    return lib.mgn_debug_last_edge_kernel(), lib.mgn_debug_last_node_kernel()
+
+
 def set_renumber(mode):
     """Node numbering policy of the next set_graph calls: 0 never, 1 auto (default), 2 always breadth-first (tests only)."""
     lib = mgn_amd.load()
