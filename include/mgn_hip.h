@@ -403,8 +403,22 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
  *   target [N][O];  mask [nmask]: node indices (Int32, 1-based at the Julia boundary: mask_index_base = 1,
  *   src/MeshGraphNets.jl:352);  grads [n_grads = mgn_param_count]: packed order of mgn_set_params, so that
  *   Optimisers.update(opt_state, ps, gs) keeps working on the Julia side;  *loss: the scalar.
- * fp32, one partition; both ln_mode values and both ln_dims values; hidden_layers 1 .. 4; with two edge sets the second set's
- * features are the ones installed by mgn_set_edge_features (as in mgn_forward).  Memory: a large mesh stores the activations of as
+ * fp32; both ln_mode values and both ln_dims values; hidden_layers 1 .. 4; with two edge sets the second set's
+ * features are the ones installed by mgn_set_edge_features (as in mgn_forward).
+ * Partitioned mesh (nranks > 1, after mgn_comm_init; one edge set): every rank calls with the GLOBAL nf [N][Fn], ef [E][Fe],
+ * target [N][O] and the mask of the whole mesh (global node ids) and returns the COMPLETE gradient and the loss of the whole mesh,
+ * the same bits on every rank.  Each rank computes on the rows it owns plus its halo rows and takes the mask entries it owns (the
+ * divisor is nmask; a rank that owns none still takes part in every exchange).  Forward: the owned boundary rows of v go to the
+ * peers that list them as halo after the node encoder and after every node MLP but the last (mps exchanges of L floats per row).
+ * Reverse: the halo rows' gradients w.r.t. v_k go back over the same lists and the owner adds them to its own term before it
+ * unwinds node MLP k - 1 -- own term, then peers in ascending rank, then list order; no floating-point atomics.  Finish: the
+ * ranks' gradients and loss numerators are gathered and added in ascending rank order in double by the same kernel on every rank;
+ * the call blocks once, there.  It runs eagerly on the handle's stream (no hipGraph replay, no second stream); stored / recomputed
+ * steps are decided per rank for its own arena.  Refusals: MGN_E_STATE naming mgn_comm_init without a communicator,
+ * MGN_E_UNSUPPORTED with two edge sets, MGN_E_ARG for a wrong n_grads -- all before the first collective, so no rank is left
+ * waiting.  The other training entry points (mgn_ode_vjp, mgn_forward_vjp, mgn_solver_grad, mgn_solver_grad_tsit5,
+ * mgn_shooting_grad) drive one partition: MGN_E_STATE on a partitioned handle.
+ * Memory: a large mesh stores the activations of as
  * many processor steps as the device's free memory (hipMemGetInfo) minus MGN_TRAIN_RESERVE_GB (16) holds and recomputes the others
  * in the reverse pass -- the first handle on a device takes the stored steps, a later one recomputes; a refused allocation is retried
  * with fewer stored steps, MGN_E_OOM only when the arena without any does not fit (M-1M: 61 GB + 10.7 GB per stored step).  Deterministic: gradients are reduced in a fixed order; the only atomic
@@ -440,6 +454,10 @@ int mgn_forward_vjp(mgn_handle* h, const float* nf, const float* ef, const float
  * pair over its own xGMI link, on the communicator's stream) -> interior projection and interior edge tiles while the rows
  * are on the wire -> wait -> boundary edge tiles.  There is no precedent in the reference (single device,
  * src/MeshGraphNets.jl:255-263).
+ * Training: mgn_step runs at nranks > 1 as well (see there): the same exchange forward, its reverse -- halo gradients back to
+ * their owners, added in a fixed order -- in the backward pass, and a rank-ordered sum of the gradients at the end.  Without
+ * overlap: every exchange is waited for where it is started.  The solver-based training entry points and the two VJPs refuse a
+ * partitioned handle (MGN_E_STATE).
  *   transport MGN_COMM_RCCL: RCCL (needs one GPU per rank).
  *   transport MGN_COMM_HOST: POSIX shared memory on one node, rows staged through the host.  Lets several ranks share one GPU
  *     (tests), serves host-only handles, and is a fallback where RCCL cannot initialise; not the production wire.

@@ -476,6 +476,10 @@ end
 `mgn_step` copies with hipMemcpyDefault: with AMDGPU.jl arrays pass `pointer(graph.nf)` etc. of the ROCArrays and a
 `ROCVector{Float32}` for `gs` instead of the host copies made below, and the gradients never cross PCIe (the
 reference keeps graph, ps and gs on the GPU, src/MeshGraphNets.jl:255-263); `mask` stays a host vector.
+On a partitioned mesh (`nranks > 1`, after `comm_init!`; one edge set) every rank calls `step!` with the GLOBAL graph, target and
+mask, exactly as above, and every rank gets the complete gradient and the loss of the whole mesh with the same bits -- each rank's
+`Optimisers.update` then yields the same parameters and no broadcast is needed.  The library exchanges the halo rows (forward) and
+their gradients (reverse) and adds the ranks' gradients in rank order; the same `ccall`, nothing else changes on the Julia side.
 """
 function step!(mgn::GraphNetwork, graph::FeatureGraph, target::AbstractMatrix, mask::AbstractVector{<:Integer}, loss_function = nothing)
     ps = mgn.ps::Vector{Float32}

@@ -108,8 +108,18 @@ struct TrainState {
         for (hipEvent_t e : ev_wg) if (e) (void)hipEventDestroy(e);
         if (aux) (void)hipStreamDestroy(aux);
     }
-    // idx buffer (int32), per edge set: egid32 [E], perm_s [E], rowptr_s [N+1]
+    // idx buffer (int32), per edge set: egid32 [E], perm_s [E], rowptr_s [N + n_halo + 1] (halo rows send, too)
     size_t i_egid[MAX_EDGE_SETS] = {0, 0}, i_perm[MAX_EDGE_SETS] = {0, 0}, i_rowptr_s[MAX_EDGE_SETS] = {0, 0};
+    // Partitioned mesh (nranks > 1).  The forward exchange packs the owned boundary rows of v by the send index into hx_send and unpacks
+    // hx_recv into the halo rows; the reverse one sends the halo rows of the gradient as they lie and adds what arrives to the owners'
+    // rows through a CSR over the send index (idx buffer: acc_row [n_acc], acc_ptr [n_acc + 1], acc_pos [rows sent]).  Per-peer bytes /
+    // offsets of the owned-row side (own) and of the halo side (halo) of either direction.  fin_*: one rank's part of the finish
+    // (train.h: rank_sum_stride), all ranks' parts, the summed loss numerator.
+    DevBuf hx_send, hx_recv, fin_s, fin_r, fin_loss;
+    std::vector<size_t> hx_own_b, hx_own_o, hx_halo_b, hx_halo_o;
+    size_t i_acc_row = 0, i_acc_ptr = 0, i_acc_pos = 0;
+    int32_t n_acc = 0;
+    int64_t mask_n = 0;          // entries of the device mask: the whole mask, on a partition the entries this rank owns
 };
 
 void train_invalidate(mgn_engine* h, int what) {
@@ -238,8 +248,11 @@ int prepare_graph(mgn_engine* h) {
     TrainState& T = *h->train;
     const LocalGraph& g = h->g;
     const int L = h->cfg.L, mps = h->cfg.mps, S = h->nsets, NB = T.nblk;
-    const int64_t N = g.n_own;
-    const size_t NL = (size_t)(N > 0 ? N : 1) * L;
+    const bool part = g.nranks > 1;
+    // NT: rows of every node array -- the owned rows, then the halo rows that local senders index (V_k, P / Q, the gradients w.r.t. v).
+    // Launches over nodes cover the N owned rows unless they say otherwise.  A partition stages the caller's GLOBAL arrays: NG, EG rows.
+    const int64_t N = g.n_own, NT = N + g.n_halo, NG = part ? g.N : N;
+    const size_t NL = (size_t)(NT > 0 ? NT : 1) * L;
     size_t EL[MAX_EDGE_SETS] = {0, 0}, ELmax = 0;
     int64_t Emax = 0;
     // index arrays per set: edge_gid as int32, sender CSR over the receiver-sorted edge list
@@ -253,31 +266,65 @@ int prepare_graph(mgn_engine* h) {
         ELmax = std::max(ELmax, EL[q]);
         Emax = std::max(Emax, E);
         const size_t base = ix.size();
-        ix.resize(base + (size_t)2 * E + N + 1, 0);
+        ix.resize(base + (size_t)2 * E + NT + 1, 0);
         T.i_egid[q] = base;
         T.i_perm[q] = base + E;
         T.i_rowptr_s[q] = base + 2 * E;
         for (int64_t i = 0; i < E; ++i) ix[T.i_egid[q] + i] = (int32_t)t.edge_gid[i];
         int32_t* rp = ix.data() + T.i_rowptr_s[q];
         for (int64_t i = 0; i < E; ++i) ++rp[t.snd[i] + 1];
-        for (int64_t n = 0; n < N; ++n) rp[n + 1] += rp[n];
-        std::vector<int32_t> cur(rp, rp + N);
+        for (int64_t n = 0; n < NT; ++n) rp[n + 1] += rp[n];
+        std::vector<int32_t> cur(rp, rp + NT);
         for (int64_t i = 0; i < E; ++i) ix[T.i_perm[q] + cur[t.snd[i]]++] = (int32_t)i;   // stable: ascending edge position
+    }
+    T.n_acc = 0;
+    if (part) {   // the owners' side of the reverse exchange: positions of the receive buffer (== of the send index) grouped by owned row, ascending
+        const int P = g.nranks;
+        const int64_t ns = (int64_t)g.send_idx.size();
+        std::vector<int32_t> order((size_t)ns);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return g.send_idx[a] < g.send_idx[b]; });
+        std::vector<int32_t> row, ptr;
+        for (int64_t i = 0; i < ns; ++i)
+            if (i == 0 || g.send_idx[order[i]] != g.send_idx[order[i - 1]]) { row.push_back(g.send_idx[order[i]]); ptr.push_back((int32_t)i); }
+        ptr.push_back((int32_t)ns);
+        T.n_acc = (int32_t)row.size();
+        T.i_acc_row = ix.size(); ix.insert(ix.end(), row.begin(), row.end());
+        T.i_acc_ptr = ix.size(); ix.insert(ix.end(), ptr.begin(), ptr.end());
+        T.i_acc_pos = ix.size(); ix.insert(ix.end(), order.begin(), order.end());
+        const size_t rowb = (size_t)L * 4;
+        T.hx_own_b.assign(P, 0); T.hx_own_o.assign(P, 0); T.hx_halo_b.assign(P, 0); T.hx_halo_o.assign(P, 0);
+        size_t so = 0, ro = 0;
+        for (int q = 0; q < P; ++q) {
+            T.hx_own_b[q] = (size_t)g.send_rows[q] * rowb; T.hx_own_o[q] = so; so += T.hx_own_b[q];
+            T.hx_halo_b[q] = (size_t)g.recv_rows[q] * rowb; T.hx_halo_o[q] = ro; ro += T.hx_halo_b[q];
+        }
+        if (so != (size_t)ns * rowb || ro != (size_t)g.n_halo * rowb) return fail(h, MGN_E_STATE, "halo lists and halo counts of the partition disagree");
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, T.idx.ensure(ix.size() * 4));
     HIPCHK(h, hipMemcpy(T.idx.p, ix.data(), ix.size() * 4, hipMemcpyHostToDevice));
+    if (part) {
+        const size_t ns = g.send_idx.size();
+        HIPCHK(h, T.hx_send.ensure(ns * L * 4));
+        HIPCHK(h, T.hx_recv.ensure(std::max(ns, (size_t)g.n_halo) * L * 4));
+        const size_t stride = (size_t)rank_sum_stride((int64_t)h->params.size()) * 4;
+        HIPCHK(h, T.fin_s.ensure(stride));
+        HIPCHK(h, T.fin_r.ensure(stride * g.nranks));
+        HIPCHK(h, T.fin_loss.ensure(sizeof(double)));
+        HIPCHK(h, hipMemset(T.fin_s.p, 0, stride));           // (head and padding stay zero; the gradient is written per call)
+    }
 
     auto layout = [&](int keep) -> size_t {
         size_t off = 0;
         auto take = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
         auto take_acts = [&](size_t n) { Acts a; for (int b = 0; b < NB; ++b) for (int i = 0; i < 3; ++i) a.h[b][i] = take(n); return a; };
-        T.nf_raw = take((size_t)N * h->cfg.Fn);
+        T.nf_raw = take((size_t)NG * h->cfg.Fn);
         T.nf_pad = take(NL);
         T.a_en = take_acts(NL);
         T.a_de = take_acts(NL);
         for (int q = 0; q < S; ++q) {
-            T.ef_raw[q] = take((size_t)g.set[q].e_local * h->es[q].Fe);
+            T.ef_raw[q] = take((size_t)(part ? g.set[q].E : g.set[q].e_local) * h->es[q].Fe);
             T.ef_pad[q] = take(EL[q]);
             T.a_ee[q] = take_acts(EL[q]);
         }
@@ -340,7 +387,7 @@ int prepare_graph(mgn_engine* h) {
         {
             static const bool overlap_env = [] { const char* e = getenv("MGN_TRAIN_OVERLAP"); return !e || atoi(e) != 0; }();
             const int64_t big = Emax > N ? Emax : N;
-            T.gsets = (overlap_env && !T.recompute && !any_fact && L == 128 && big <= 2048 * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers)
+            T.gsets = (overlap_env && !part && !T.recompute && !any_fact && L == 128 && big <= 2048 * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers; a partition runs on one stream, eagerly: communicator calls sit between its launches)
         }
         // GT / G xhat rows only where some LayerNorm'd launch unit does not take its parameter sums inside the backward kernel (train.h: LNSUM)
         bool need_gt = h->cfg.ln_dims == MGN_LN_ALL || T.gsets > 1 || !train_bwd_ln_sums(L, (int)((N + TILE - 1) / TILE));
@@ -359,8 +406,8 @@ int prepare_graph(mgn_engine* h) {
         T.Gout = take(NL);
         T.gNF = take(NL);
         T.io = take((size_t)(N > 0 ? N : 1) * (2 * h->cfg.O + h->cfg.Fn + 1));
-        T.ptmp = take((size_t)(N > 0 ? N : 1) * (size_t)std::max(h->cfg.Fn, h->cfg.O));      // row permutations of a renumbered graph
-        const int nb = std::max(wgrad_blocks(N), wgrad_blocks(Emax));
+        T.ptmp = take((size_t)(NG > 0 ? NG : 1) * (size_t)std::max(h->cfg.Fn, h->cfg.O));      // row permutations of a renumbered graph
+        const int nb = std::max(wgrad_blocks(NT), wgrad_blocks(Emax));
         T.pw = take((size_t)5 * (T.gsets > 1 ? T.gsets / 2 : 1) * (nb > 0 ? nb : 1) * L * L);   // one partial-dW region per weight-gradient job of a launch (a group of units on small meshes)
         T.pb = take((size_t)(WGRAD_MAX_JOBS + 1) * (nb > 0 ? nb : 1) * L);   // (+ 1: the second output of a LayerNorm job)
         {   // Deferred reductions (MGN_TRAIN_DEFER_REDUCE = 1; built, same bits, off) where the weight gradients run on the second stream: the 33
@@ -430,8 +477,8 @@ int prepare_graph(mgn_engine* h) {
     HIPCHK(h, T.target.ensure((size_t)(N > 0 ? N : 1) * h->cfg.O * 4));
     T.g2l.clear();
     T.mask_valid = false;
-    if (h->g.renumbered) {
-        T.g2l.assign((size_t)h->g.N, 0);
+    if (h->g.renumbered || part) {      // (-1: a node another rank owns)
+        T.g2l.assign((size_t)h->g.N, part ? -1 : 0);
         for (int32_t i = 0; i < h->g.n_own; ++i) T.g2l[(size_t)h->g.own_gid[i]] = i;
     }
     T.graph_ready = true;
@@ -464,10 +511,14 @@ struct TrainJob {
     double* gacc = nullptr;
 };
 
-int train_prepare(mgn_handle* h, const char* who, size_t n_grads) {
+// partitions: the entry point runs on a partitioned mesh (mgn_step); every check comes before the first collective
+int train_prepare(mgn_handle* h, const char* who, size_t n_grads, bool partitions = false) {
     if (int rc = need(h, true, true, false, true)) return rc;    // (the training kernels pack their own weights from h->params)
     const mgn_config& c = h->cfg;
-    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (c.nranks != 1 && !partitions) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (c.nranks != 1 && h->nsets != 1) return fail(h, MGN_E_UNSUPPORTED, "%s on a partitioned mesh takes one edge set", who);
+    if (c.nranks != 1 && !h->comm)
+        return fail(h, MGN_E_STATE, "%s with nranks = %d needs a communicator: call mgn_comm_init on every rank first", who, c.nranks);
     if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
     for (int q = 1; q < h->nsets; ++q)
         if (h->g.set[q].E > 0 && !h->es[q].have_ef)
@@ -488,7 +539,9 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     TrainState& T = *h->train;
     const LocalGraph& g = h->g;
     const int S = h->nsets;
-    const int64_t N = g.n_own;
+    // a partition (train_prepare: mgn_step alone, one edge set): N owned rows, then the halo rows; the caller's arrays are the whole mesh's
+    const bool part = c.nranks > 1;
+    const int64_t N = g.n_own, NT = N + g.n_halo, NG = part ? g.N : N;
     const int L = c.L, mps = c.mps, O = c.O;
     hipStream_t st = h->stream;
     float* A = T.arena.as<float>();
@@ -504,14 +557,14 @@ int train_run(mgn_handle* h, const TrainJob& J) {
         sx[q].rcv = h->es[q].d_rcv.as<int32_t>();
         sx[q].rowptr = h->es[q].d_rowptr.as<int32_t>();
     }
-    const int32_t nt_n = (int32_t)((N + TILE - 1) / TILE);
-    float* G = T.grads.as<float>();
+    const int32_t nt_n = (int32_t)((N + TILE - 1) / TILE), nt_t = (int32_t)((NT + TILE - 1) / TILE);
+    float* G = part ? T.fin_s.as<float>() + RANK_SUM_HEAD : T.grads.as<float>();   // (a partition's gradient is its term of the finish)
 
     // ---- inputs
     const float* nrm = h->norms.as<float>();   // [node scale, shift (Fn) | edge scale, shift (Fe) | out scale, shift (O)]
     // A renumbered graph (graph_host.h: the engine's node order is not the caller's): per-node inputs are brought into the engine's
     // order as they arrive and per-node results go back through the inverse; `mask` is mapped on the host.  Edges go by edge_gid already.
-    const bool renum = g.renumbered;
+    const bool renum = g.renumbered || part;   // (a partition's rows are the rows it owns, wherever they lie in the caller's arrays)
     const int32_t* ngid = h->d_own_gid.as<int32_t>();
     auto to_local = [&](float* buf, int width) -> hipError_t {            // buf [N][width]: caller's order -> engine's, in place
         if (!renum || width <= 0) return hipSuccess;
@@ -539,9 +592,12 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     };
     if (!J.vjp || J.fvjp) {
         const float* src = nullptr;
-        HIPCHK(h, staged(J.nf, A + T.nf_raw, (size_t)N * c.Fn, src));
+        HIPCHK(h, staged(J.nf, A + T.nf_raw, (size_t)NG * c.Fn, src));
         HIPCHK(h, launch_affine_pad_gather(src, c.Fn, nullptr, 0, nullptr, nullptr, renum ? ngid : nullptr, A + T.nf_pad, L, N, st));
-        if (sx[0].E > 0) {
+        if (part && g.set[0].E > 0) {      // the local edges' rows of the global array, in the engine's order
+            HIPCHK(h, staged(J.ef, A + T.ef_raw[0], (size_t)g.set[0].E * c.Fe, src));
+            HIPCHK(h, launch_affine_pad_gather(src, c.Fe, nullptr, 0, nullptr, nullptr, sx[0].egid, A + T.ef_pad[0], L, sx[0].E, st));
+        } else if (sx[0].E > 0) {
             HIPCHK(h, staged(J.ef, A + T.ef_raw[0], (size_t)sx[0].E * c.Fe, src));
             HIPCHK(h, launch_affine_pad(src, c.Fe, nullptr, 0, nullptr, nullptr, A + T.ef_pad[0], L, sx[0].E, st));
         }
@@ -550,7 +606,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             HIPCHK(h, to_local(A + T.io + (size_t)N * O, O));
         } else {
             if (renum) {
-                HIPCHK(h, staged(J.target, A + T.ptmp, (size_t)N * O, src));
+                HIPCHK(h, staged(J.target, A + T.ptmp, (size_t)NG * O, src));
                 HIPCHK(h, launch_permute_rows(T.target.as<float>(), src, ngid, N, O, false, st));
             } else {
                 HIPCHK(h, hipMemcpyAsync(T.target.p, J.target, (size_t)N * O * 4, hipMemcpyDefault, st));
@@ -570,10 +626,15 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                         HIPCHK(h, hipMemcpy(host_mask.data(), J.mask, (size_t)J.nmask * 4, hipMemcpyDeviceToHost));
                         mk = host_mask.data();
                     }
-                    T.mask_host.resize((size_t)J.nmask);
-                    for (int64_t i = 0; i < J.nmask; ++i) T.mask_host[(size_t)i] = T.g2l[(size_t)(mk[i] - J.mask_index_base)];
-                    HIPCHK(h, hipMemcpyAsync(T.mask.p, T.mask_host.data(), (size_t)J.nmask * 4, hipMemcpyHostToDevice, st));
+                    T.mask_host.clear();
+                    for (int64_t i = 0; i < J.nmask; ++i) {
+                        const int32_t l = T.g2l[(size_t)(mk[i] - J.mask_index_base)];
+                        if (l >= 0) T.mask_host.push_back(l);       // (a partition takes the entries it owns, as often as they are listed)
+                    }
+                    T.mask_n = (int64_t)T.mask_host.size();
+                    HIPCHK(h, hipMemcpyAsync(T.mask.p, T.mask_host.data(), (size_t)T.mask_n * 4, hipMemcpyHostToDevice, st));
                 } else {
+                    T.mask_n = J.nmask;
                     HIPCHK(h, hipMemcpyAsync(T.mask.p, J.mask, (size_t)J.nmask * 4, hipMemcpyDefault, st));
                 }
                 if (!mask_dev) {
@@ -677,8 +738,8 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             a.X[2] = A + T.Ek[q][k];
             return run_fwd(m, a, -1, T.a_pe[q][k], resid, out, lnout, keep);
         }
-        Lin2Args p{};
-        p.rows = N; p.ntiles = nt_n;
+        Lin2Args p{};                     // (over the halo rows as well: local senders index them)
+        p.rows = NT; p.ntiles = nt_t;
         p.X0 = A + T.Vk[k]; p.W0 = Wt + m.b[0].W1[0]; p.W1 = Wt + m.b[0].W1[1];
         p.OUT0 = A + T.Pn; p.OUT1 = A + T.Qn;
         if (hipError_t e = launch_lin2(L, p, st)) return e;
@@ -688,6 +749,29 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     };
     auto fwd_node = [&](int k, const float* resid, float* out, bool keep = true) {
         return fwd(T.m_pn[k], N, nt_n, A + T.Vk[k], nullptr, A + T.agg[0][k], S > 1 ? A + T.agg[1][k] : nullptr, T.a_pn[k], resid, out, nullptr, keep);
+    };
+
+    // The halo exchange of the partitioned step, forward: the owned boundary rows of v go to the peers that list them as halo (packed by
+    // the send index; the halo rows are one block behind the owned rows, in the order they arrive).  Reverse: the halo rows of the
+    // gradient w.r.t. v go back over the same lists and the owner adds them to its own term (launch_halo_accumulate: a fixed order).
+    const int32_t* acc_row = T.idx.as<int32_t>() + T.i_acc_row;
+    const int32_t* acc_ptr = T.idx.as<int32_t>() + T.i_acc_ptr;
+    const int32_t* acc_pos = T.idx.as<int32_t>() + T.i_acc_pos;
+    auto comm_fail = [&](const char* what) { return fail(h, MGN_E_RCCL, "mgn_step: %s: %s", what, h->comm->err.c_str()); };
+    auto halo_forward = [&](float* v) -> int {
+        HIPCHK(h, launch_halo_pack(L, v, h->d_send_idx.as<int32_t>(), T.hx_send.as<float>(), (int64_t)g.send_idx.size(), st));
+        if (h->comm->a2a_start(T.hx_send.p, T.hx_own_b.data(), T.hx_own_o.data(), T.hx_recv.p, T.hx_halo_b.data(), T.hx_halo_o.data(), st) != 0 ||
+            h->comm->a2a_finish(st) != 0)
+            return comm_fail("halo exchange");
+        HIPCHK(h, launch_halo_unpack(L, T.hx_recv.as<float>(), v + (size_t)N * L, g.n_halo, st));
+        return MGN_OK;
+    };
+    auto halo_reverse = [&](float* gv) -> int {
+        if (h->comm->a2a_start(gv + (size_t)N * L, T.hx_halo_b.data(), T.hx_halo_o.data(), T.hx_recv.p, T.hx_own_b.data(), T.hx_own_o.data(), st) != 0 ||
+            h->comm->a2a_finish(st) != 0)
+            return comm_fail("reverse halo exchange");
+        HIPCHK(h, launch_halo_accumulate(L, T.hx_recv.as<float>(), acc_row, acc_ptr, acc_pos, gv, T.n_acc, st));
+        return MGN_OK;
     };
 
     // Small meshes replay both launch sequences from hipGraphs (everything they touch lives at fixed addresses in the arena;
@@ -730,8 +814,9 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     // ---- forward, keeping activations
     auto forward_launches = [&]() -> int {
     HIPCHK(h, fwd(T.m_en, N, nt_n, A + T.nf_pad, nullptr, nullptr, nullptr, T.a_en, nullptr, A + T.Vk[0], nullptr));
-    for (int q = 0; q < S; ++q)
-        HIPCHK(h, fwd(T.m_ee[q], sx[q].E, sx[q].nt, A + T.ef_pad[q], sx[q].egid, nullptr, nullptr, T.a_ee[q], nullptr, A + T.Ek[q][0], nullptr));
+    if (part) if (int rc = halo_forward(A + T.Vk[0])) return rc;
+    for (int q = 0; q < S; ++q)      // (a partition's ef_pad holds its local edges in the engine's order already)
+        HIPCHK(h, fwd(T.m_ee[q], sx[q].E, sx[q].nt, A + T.ef_pad[q], part ? nullptr : sx[q].egid, nullptr, nullptr, T.a_ee[q], nullptr, A + T.Ek[q][0], nullptr));
     for (int k = 0; k < mps; ++k) {
         for (int q = 0; q < S; ++q) {
             if (!lnall && sx[q].E > 0 && train_fwd_fused_agg(L, sx[q].nt)) {   // aggregation inside the edge launch (large meshes)
@@ -743,6 +828,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             HIPCHK(h, launch_segment_sum(L, A + T.Enew, sx[q].rowptr, nullptr, nullptr, A + T.agg[q][k], (int32_t)N, st));
         }
         HIPCHK(h, fwd_node(k, A + T.Vk[k], A + T.Vk[k + 1], T.kept(k, mps)));
+        if (part && k + 1 < mps) if (int rc = halo_forward(A + T.Vk[k + 1])) return rc;   // (the decoder reads owned rows only)
     }
     HIPCHK(h, fwd(T.m_de, N, nt_n, A + T.Vk[mps], nullptr, nullptr, nullptr, T.a_de, nullptr, nullptr, nullptr));
     return MGN_OK;
@@ -751,12 +837,12 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     const size_t y_out = T.a_de.h[T.m_de.nblk - 1][2];        // the decoder's output (its last unit's Y)
 
     // ---- seed of the reverse pass
-    const int nlb = J.vjp ? 0 : loss_blocks(J.nmask);
+    const int nlb = J.vjp ? 0 : loss_blocks(T.mask_n);
     HIPCHK(h, hipMemsetAsync(A + T.Gout, 0, (size_t)N * L * 4, st));
     if (!J.vjp) {   // loss = mean(mse_reduce(target, out)[mask]) and its gradient w.r.t. out
         HIPCHK(h, T.loss.ensure((size_t)nlb * sizeof(double)));
-        HIPCHK(h, launch_loss(A + y_out, L, T.target.as<float>(), O, T.mask.as<int32_t>(), J.nmask, renum ? 0 : J.mask_index_base, A + T.Gout,
-                              T.loss.as<double>(), st));
+        HIPCHK(h, launch_loss(A + y_out, L, T.target.as<float>(), O, T.mask.as<int32_t>(), T.mask_n, J.nmask, renum ? 0 : J.mask_index_base,
+                              A + T.Gout, T.loss.as<double>(), st));
     } else if (J.fvjp) {   // the cotangent of the model's output as given
         HIPCHK(h, launch_vjp_seed(A + y_out, L, O, A + T.io + (size_t)N * O, nullptr, nullptr, nullptr, A + T.Gout,
                                   J.out ? T.target.as<float>() : nullptr, N, st));
@@ -822,7 +908,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                         int fq = -1, const float* vin = nullptr, int lnslot = -1) -> int {
         const bool fact = fq >= 0;
         const bool wide = lnall && b.ln;
-        const int64_t node_rows = fact ? N : 0;
+        const int64_t node_rows = fact ? NT : 0;          // rows that send: SGs, dW1s (halo rows included); SGr and dW1r stop at the N owned rows
         const int nin_k = fact ? 1 : b.nin;               // input blocks the kernel unwinds
         const int gs = overlap ? n_bwd % T.gsets : 0;
         // buffer set gs is re-used: the launch that took its last occupant's weight gradients must have run (launches on the second stream are
@@ -868,10 +954,13 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             HIPCHK(h, launch_colsum_groups(A + T.lnsum, (ntiles + 7) / 8, 2 * L, LNSUM_GROUPS, A + T.lnsum2, st));
         if (fact) {   // gather <-> segmented-sum duality on GZ1 itself: SGr[n] = sum of GZ1 over edges received by n, SGs: sent by n
             if (sgr) {
-                HIPCHK(h, launch_seg_fixup(L, sx[fq].rowptr, A + T.segcarry, A + T.SGr, (int32_t)node_rows, st));
+                HIPCHK(h, launch_seg_fixup(L, sx[fq].rowptr, A + T.segcarry, A + T.SGr, (int32_t)N, st));
                 HIPCHK(h, launch_segment_sum(L, A + T.GZ1[gs], sx[fq].rowptr_s, sx[fq].perm_s, nullptr, A + T.SGs, (int32_t)node_rows, st));
-            } else
-            HIPCHK(h, launch_segment_sum_pair(L, A + T.GZ1[gs], sx[fq].rowptr, sx[fq].rowptr_s, sx[fq].perm_s, A + T.SGr, A + T.SGs, (int32_t)node_rows, st));
+            } else {
+                HIPCHK(h, launch_segment_sum_pair(L, A + T.GZ1[gs], sx[fq].rowptr, sx[fq].rowptr_s, sx[fq].perm_s, A + T.SGr, A + T.SGs, (int32_t)N, st));
+                HIPCHK(h, launch_segment_sum(L, A + T.GZ1[gs], sx[fq].rowptr_s + N, sx[fq].perm_s, nullptr, A + T.SGs + (size_t)N * L, g.n_halo, st));
+            }
+            if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.SGr + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (a halo row receives nothing here)
         }
         // every parameter gradient of this unit: jobs of one batched weight-gradient launch + one batched (ordered) reduction
         const int64_t lrows_u = rows > node_rows ? rows : node_rows;   // a launch covers its longest job (node jobs of a factored edge MLP)
@@ -921,7 +1010,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
         } else {   // dW1e = e^T GZ1 (+ db1) over the edges; dW1s = v^T SGs, dW1r = v^T SGr over the nodes
             job(xin[0], xi[0], A + T.GZ1[gs], b.gW[0] + (long)2 * L * L, L, L, b.gb[0], L);
             job(vin, nullptr, A + T.SGs, b.gW[0], L, L, -1, L, node_rows);
-            job(vin, nullptr, A + T.SGr, b.gW[0] + (long)L * L, L, L, -1, L, node_rows);
+            job(vin, nullptr, A + T.SGr, b.gW[0] + (long)L * L, L, L, -1, L, N);
         }
         if (lnsum) {
             const int ng = std::min(LNSUM_GROUPS, (int)((ntiles + 7) / 8));
@@ -1003,6 +1092,8 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                 // gather duality: the gradients of v[receivers] / v[senders] are segmented sums over the receiver / sender CSR
                 HIPCHK(h, launch_segment_sum2(L, A + T.GXr, sx[q].rowptr, A + T.GXs, sx[q].rowptr_s, sx[q].perm_s, A + T.gV[nxt], A + T.gV[nxt],
                                               (int32_t)N, st));
+                // halo rows only send
+                HIPCHK(h, launch_segment_sum(L, A + T.GXs, sx[q].rowptr_s + N, sx[q].perm_s, nullptr, A + T.gV[nxt] + (size_t)N * L, g.n_halo, st));
             } else {             // factored first layer: per edge only the e block; the v blocks per node from SGs / SGr
                 float* gx[3] = {A + T.gE[q][enxt], nullptr, nullptr};
                 const float* gxadd[3] = {A + T.gE[q][ecur], nullptr, nullptr};
@@ -1010,14 +1101,17 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                 const int32_t* xi[3] = {nullptr, nullptr, nullptr};
                 if (int rc = bwd(me, E, sx[q].nt, A + T.gE[q][ecur], A + T.gAgg[q], sx[q].rcv, T.a_pe[q][k], gx, gxadd, xin, xi, q, A + T.Vk[k]))
                     return rc;
+                if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.gV[nxt] + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (no node MLP wrote them)
                 Lin2Args l2{};    // gV += SGs W1s^T + SGr W1r^T
-                l2.rows = N; l2.ntiles = nt_n;
+                l2.rows = NT; l2.ntiles = nt_t;
                 l2.X0 = A + T.SGs; l2.X1 = A + T.SGr; l2.W0 = Wt + me.b[0].W1T[0]; l2.W1 = Wt + me.b[0].W1T[1];
                 l2.ADD = A + T.gV[nxt]; l2.OUT0 = A + T.gV[nxt];
                 HIPCHK(h, launch_lin2(L, l2, st));
             }
             if (E == 0) HIPCHK(h, hipMemsetAsync(A + T.gE[q][enxt], 0, (size_t)L * 4, st));
         }
+        // the halo rows' share of d loss / d v_k joins the owners' before node MLP k - 1 (the node encoder for k = 0) is unwound
+        if (part) if (int rc = halo_reverse(A + T.gV[nxt])) return rc;
         cur = nxt;
         ecur = enxt;
     }
@@ -1030,7 +1124,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
         if (int rc = bwd(T.m_en, N, nt_n, A + T.gV[cur], nullptr, nullptr, T.a_en, gx_n, gxadd, xin, xi)) return rc;
         for (int q = 0; q < S; ++q) {
             const float* xin_e[3] = {A + T.ef_pad[q], nullptr, nullptr};
-            const int32_t* xi_e[3] = {sx[q].egid, nullptr, nullptr};
+            const int32_t* xi_e[3] = {part ? nullptr : sx[q].egid, nullptr, nullptr};
             if (int rc = bwd(T.m_ee[q], sx[q].E, sx[q].nt, A + T.gE[q][ecur], nullptr, nullptr, T.a_ee[q], gx, gxadd, xin_e, xi_e)) return rc;
         }
     }
@@ -1058,6 +1152,20 @@ int train_run(mgn_handle* h, const TrainJob& J) {
     if (J.sweep) {     // xbar (engine order) into io for the adjoint kernel; the step's gradient into the double accumulator
         HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, A + T.io, N, st));
         HIPCHK(h, launch_grad_accum(G, J.gacc, (int64_t)h->params.size(), J.first, st));
+        return MGN_OK;
+    }
+    if (part) {
+        // Finish: every rank's gradient and loss numerator are gathered and added in ascending rank order, in double, by the same kernel on
+        // every rank: the same bits everywhere.  The call's one blocking point follows.
+        const int64_t np = (int64_t)h->params.size();
+        double num = 0.0;
+        HIPCHK(h, launch_loss_numerator(T.loss.as<double>(), nlb, T.fin_s.as<double>(), st));
+        if (h->comm->allgather(T.fin_s.p, (size_t)rank_sum_stride(np) * 4, T.fin_r.p, st) != 0) return comm_fail("allgather of the gradients");
+        HIPCHK(h, launch_rank_sum(T.fin_r.as<float>(), c.nranks, np, T.grads.as<float>(), T.fin_loss.as<double>(), st));
+        HIPCHK(h, hipMemcpyAsync(J.grads, T.grads.p, (size_t)np * 4, hipMemcpyDefault, st));
+        HIPCHK(h, hipMemcpyAsync(&num, T.fin_loss.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        *J.loss = (float)(num / (double)J.nmask);
         return MGN_OK;
     }
     std::vector<double> lp((size_t)nlb);
@@ -1098,13 +1206,14 @@ extern "C" int mgn_step(mgn_handle* h, const float* nf, const float* ef, const f
                         int32_t mask_index_base, float* grads, size_t n_grads, float* loss) try {
     if (!h) return MGN_E_ARG;
     if (!nf || !target || !mask || !grads || !loss) return fail(h, MGN_E_ARG, "mgn_step: null argument");
-    if (int rc = train_prepare(h, "mgn_step", n_grads)) return rc;
+    if (int rc = train_prepare(h, "mgn_step", n_grads, true)) return rc;
     if (!ef && h->g.set[0].E > 0) return fail(h, MGN_E_ARG, "mgn_step: null argument");
     if (nmask < 1) return fail(h, MGN_E_ARG, "mgn_step: empty mask");
     if (mask_index_base != 0 && mask_index_base != 1) return fail(h, MGN_E_ARG, "mgn_step: mask_index_base must be 0 or 1");
+    const int64_t n_nodes = h->cfg.nranks > 1 ? h->g.N : h->g.n_own;      // (a partition takes the mask of the whole mesh)
     for (int64_t i = 0; i < nmask; ++i) {
         const int64_t n = (int64_t)mask[i] - mask_index_base;
-        if (n < 0 || n >= h->g.n_own) return fail(h, MGN_E_ARG, "mgn_step: mask entry %lld out of range", (long long)i);
+        if (n < 0 || n >= n_nodes) return fail(h, MGN_E_ARG, "mgn_step: mask entry %lld out of range", (long long)i);
     }
     TrainJob J;
     J.nf = nf; J.ef = ef; J.target = target; J.mask = mask; J.nmask = nmask; J.mask_index_base = mask_index_base;

@@ -158,10 +158,28 @@ constexpr int STATS_ROWS = 2048;
 int stats_blocks(int64_t rows);
 hipError_t launch_col_stats(const float* x, int64_t rows, int dim, double* partial, hipStream_t s);
 // masked MSE: loss_partial[b] = sum over this block's mask entries of sum_o (out - target)^2;
-// G[n][o] += 2 (out[n][o] - target[n][o]) / nmask   (G [N][L] zeroed by the caller; out = first O columns of Y)
+// G[n][o] += 2 (out[n][o] - target[n][o]) / divisor   (G [N][L] zeroed by the caller; out = first O columns of Y; divisor = nmask, or on
+// a partition, which lists only the entries it owns, the length of the whole mask)
 int loss_blocks(int64_t nmask);
-hipError_t launch_loss(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int32_t index_base,
+hipError_t launch_loss(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int64_t divisor, int32_t index_base,
                        float* G, double* loss_partial, hipStream_t s);
+
+// mgn_step on a partitioned mesh (nranks > 1): rows of L fp32 between the node arrays and the exchange buffers, and the finish.
+//   pack        dst[r] = src[idx[r]]: the owned boundary rows in send-index order (peer-major), contiguous
+//   unpack      halo_rows[r] = recv[r]: the halo rows are one block behind the owned rows, in the receive buffer's order
+//   accumulate  g[row[b]] += recv[pos[p]], p in [ptr[b], ptr[b + 1]) in order: the halo rows' gradients arriving at their owner (a CSR
+//               over the owned rows that some peer lists, positions ascending: own term, then peers by rank, then list order)
+hipError_t launch_halo_pack(int L, const float* src, const int32_t* idx, float* dst, int64_t rows, hipStream_t s);
+hipError_t launch_halo_unpack(int L, const float* recv, float* halo_rows, int64_t rows, hipStream_t s);
+hipError_t launch_halo_accumulate(int L, const float* recv, const int32_t* row, const int32_t* ptr, const int32_t* pos, float* g, int32_t n,
+                                  hipStream_t s);
+// One rank's contribution to the finish: RANK_SUM_HEAD floats (the loss numerator as one double, the rest unused), then the n gradient
+// floats zero-padded to a multiple of four -- rank_sum_stride(n) floats.  launch_loss_numerator adds the rank's loss partials into the
+// head; launch_rank_sum adds all [nranks][stride] over the ranks in ascending order, in double: out [n] floats, loss[0] the numerator.
+constexpr int RANK_SUM_HEAD = 4;
+int64_t rank_sum_stride(int64_t n);
+hipError_t launch_loss_numerator(const double* partial, int nb, double* out, hipStream_t s);
+hipError_t launch_rank_sum(const float* all, int nranks, int64_t n, float* out, double* loss, hipStream_t s);
 
 // solver-based training (mgn_solver_grad), one step k of the reverse sweep of a fixed-step Euler solve, per element of the [N][O] state:
 //   a <- a + (xbar ? (inflow[n] ? 0 : xbar) : 0) + (gt ? -gscale ls[o]^2 (gt - xs) vm[n] : 0) + (ct ? cw sign(xend - ct) : 0);  lam <- dt a

@@ -1434,13 +1434,13 @@ __global__ void k_extract_cols(const float* __restrict__ src, int L, int O, cons
 }
 
 __global__ void k_loss(const float* __restrict__ Y, int L, const float* __restrict__ target, int O, const int32_t* __restrict__ mask,
-                       int64_t nmask, int32_t index_base, float* __restrict__ G, double* __restrict__ loss_partial) {
+                       int64_t nmask, int64_t divisor, int32_t index_base, float* __restrict__ G, double* __restrict__ loss_partial) {
     __shared__ double sh[4];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double e = 0.0;
     if (i < nmask) {
         const int64_t n = (int64_t)mask[i] - index_base;
-        const float scale = 2.0f / (float)nmask;
+        const float scale = 2.0f / (float)divisor;       // (a partition lists nmask of the divisor entries of the whole mesh)
         for (int o = 0; o < O; ++o) {
             const float d = Y[n * L + o] - target[n * O + o];
             e += (double)d * (double)d;
@@ -1946,11 +1946,11 @@ hipError_t launch_col_stats(const float* x, int64_t rows, int dim, double* parti
 
 int loss_blocks(int64_t nmask) { return nmask > 0 ? (int)((nmask + 255) / 256) : 0; }
 
-hipError_t launch_loss(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int32_t index_base,
+hipError_t launch_loss(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int64_t divisor, int32_t index_base,
                        float* G, double* loss_partial, hipStream_t s) {
     const int nb = loss_blocks(nmask);
     if (nb == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_loss, dim3(nb), dim3(256), 0, s, Y, L, target, O, mask, nmask, index_base, G, loss_partial);
+    hipLaunchKernelGGL(k_loss, dim3(nb), dim3(256), 0, s, Y, L, target, O, mask, nmask, divisor, index_base, G, loss_partial);
     return hipGetLastError();
 }
 
@@ -2233,6 +2233,102 @@ hipError_t launch_grad_accum(const float* g, double* acc, int64_t n, bool first,
 hipError_t launch_grad_finish(const double* acc, float* out, int64_t n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_grad_finish, dim3(grad_blocks(n)), dim3(256), 0, s, acc, out, n);
+    return hipGetLastError();
+}
+
+// ---- training step on a partitioned mesh (mgn_step at nranks > 1) -------------------------------------------------------------------
+// Row kernels of the halo exchange in both directions and of the rank-ordered finish.  Rows are L fp32; a thread moves 16 bytes, so a
+// wave covers 256 / L whole rows (L = 32, 64, 128) and a row is one contiguous run of lanes.  No LDS, nothing but memory traffic.
+
+// dst[r] = src[idx ? idx[r] : r]: the owned boundary rows into the send buffer (idx = the send index), the receive buffer into the halo rows (idx null)
+__global__ __launch_bounds__(256) void k_halo_rows(const float* __restrict__ src, const int32_t* __restrict__ idx, float* __restrict__ dst,
+                                                   int64_t rows, int L4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * L4) return;
+    const int64_t r = i / L4;
+    const int q = (int)(i - r * L4);
+    const int64_t sr = idx ? (int64_t)idx[r] : r;
+    reinterpret_cast<f32x4*>(dst)[i] = reinterpret_cast<const f32x4*>(src)[sr * L4 + q];
+}
+
+// The reverse exchange: g[row[b]] += recv[pos[p]] for p in [ptr[b], ptr[b + 1]), in that order.  One entry b per owned row that some
+// peer lists as halo; pos ascends inside an entry and the receive buffer is peer-major in list order, so the owner's own term comes
+// first, then the peers in ascending rank, then list order -- whatever the number of peers a row is halo to.  No atomics.
+__global__ __launch_bounds__(256) void k_halo_accumulate(const float* __restrict__ recv, const int32_t* __restrict__ row, const int32_t* __restrict__ ptr,
+                                                         const int32_t* __restrict__ pos, float* __restrict__ g, int32_t n, int L4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n * L4) return;
+    const int b = (int)(i / L4), q = (int)(i - (int64_t)b * L4);
+    f32x4* out = reinterpret_cast<f32x4*>(g) + (int64_t)row[b] * L4 + q;
+    const f32x4* R4 = reinterpret_cast<const f32x4*>(recv);
+    f32x4 s = *out;
+    const int e1 = ptr[b + 1];
+    for (int p = ptr[b]; p < e1; ++p) s += R4[(int64_t)pos[p] * L4 + q];
+    *out = s;
+}
+
+// out[0] = the sum of this rank's loss partials: lane l adds partials l, l + 64, ... in order, the lanes are combined by a fixed butterfly
+__global__ __launch_bounds__(64) void k_loss_numerator(const double* __restrict__ partial, int nb, double* __restrict__ out) {
+    double e = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 64) e += partial[b];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off, 64);
+    if (threadIdx.x == 0) out[0] = e;
+}
+
+// all [nranks][stride] floats, every rank's (loss numerator as one double | 2 floats unused | n gradient floats, zero-padded to 4):
+// out[i] = (float) sum over the ranks in ascending order of (double) gradient i; loss[0] = the sum of the numerators in the same order.
+// Every rank runs this on the same gathered bytes: the same bits everywhere.
+__global__ __launch_bounds__(256) void k_rank_sum(const float* __restrict__ all, int nranks, int64_t stride, int64_t n, float* __restrict__ out,
+                                                  double* __restrict__ loss) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // one f32x4 of the gradient each
+    if (i == 0) {
+        double s = 0.0;
+        for (int q = 0; q < nranks; ++q) s += *reinterpret_cast<const double*>(all + (int64_t)q * stride);
+        loss[0] = s;
+    }
+    if (4 * i >= n) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int q = 0; q < nranks; ++q) {
+        const f32x4 v = reinterpret_cast<const f32x4*>(all + (int64_t)q * stride + RANK_SUM_HEAD)[i];
+        s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2]; s3 += (double)v[3];
+    }
+    if (4 * i + 4 <= n) reinterpret_cast<f32x4*>(out)[i] = f32x4{(float)s0, (float)s1, (float)s2, (float)s3};
+    else {                                                                  // (out holds exactly n floats)
+        const double t[3] = {s0, s1, s2};
+        for (int k = 0; 4 * i + k < n; ++k) out[4 * i + k] = (float)t[k];
+    }
+}
+
+hipError_t launch_halo_pack(int L, const float* src, const int32_t* idx, float* dst, int64_t rows, hipStream_t s) {
+    const int64_t tot = rows * (L / 4);
+    if (tot <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_halo_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, src, idx, dst, rows, L / 4);
+    return hipGetLastError();
+}
+
+hipError_t launch_halo_unpack(int L, const float* recv, float* halo_rows, int64_t rows, hipStream_t s) {
+    return launch_halo_pack(L, recv, nullptr, halo_rows, rows, s);
+}
+
+hipError_t launch_halo_accumulate(int L, const float* recv, const int32_t* row, const int32_t* ptr, const int32_t* pos, float* g, int32_t n,
+                                  hipStream_t s) {
+    const int64_t tot = (int64_t)n * (L / 4);
+    if (tot <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_halo_accumulate, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, recv, row, ptr, pos, g, n, L / 4);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_numerator(const double* partial, int nb, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_loss_numerator, dim3(1), dim3(64), 0, s, partial, nb, out);
+    return hipGetLastError();
+}
+
+int64_t rank_sum_stride(int64_t n) { return RANK_SUM_HEAD + (n + 3) / 4 * 4; }
+
+hipError_t launch_rank_sum(const float* all, int nranks, int64_t n, float* out, double* loss, hipStream_t s) {
+    const int64_t n4 = (n + 3) / 4;
+    hipLaunchKernelGGL(k_rank_sum, dim3((unsigned)((n4 > 0 ? n4 + 255 : 256) / 256)), dim3(256), 0, s, all, nranks, rank_sum_stride(n), n, out, loss);
     return hipGetLastError();
 }
 

@@ -528,7 +528,11 @@ class Engine:
         """step!(mgn, graph, target, mask, mse_reduce) (reference src/strategies.jl:418-422): returns (gs, loss) with gs
         in the packed order of set_params.  nf / ef / target may be NumPy arrays or contiguous fp32 torch tensors on
         the engine's GPU (the reference keeps the graph on the device); `out`: a NumPy array or device tensor of
-        param_count floats that receives the gradients (device: no PCIe transfer, the optimiser runs where they are)."""
+        param_count floats that receives the gradients (device: no PCIe transfer, the optimiser runs where they are).
+        On a partitioned mesh (nranks > 1, after comm_init; one edge set) every rank calls with the GLOBAL arrays -- nf [N][Fn],
+        ef [E][Fe], target [N][O], mask with global node ids -- and gets the complete gradient and the loss of the whole mesh, the
+        same bits on every rank: halo rows go forward once per processor step, their gradients go back to the owners in the
+        reverse pass, the ranks' gradients are added in rank order at the end (mgn_step in include/mgn_hip.h)."""
         nf, p_nf = _host_or_device(nf, (self.N, self.cfg.Fn))
         ef, p_ef = _host_or_device(ef, (self.E, self.cfg.Fe))
         target, p_t = _host_or_device(target, (self.N, self.cfg.O))
