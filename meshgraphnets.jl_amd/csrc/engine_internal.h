@@ -1,4 +1,5 @@
-// Engine state shared by the C-ABI translation units (mgn_api.cpp: inference path, mgn_train.cpp: step!).
+// Engine state shared by the C-ABI translation units (mgn_api.cpp: inference path, mgn_solve.cpp: the ODE solve drivers,
+// mgn_train.cpp: step! and the reverse sweeps).
 // Internal; the public boundary is include/mgn_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -264,7 +265,26 @@ struct Tsit5Sweep {
     float* ybar;                         // scratch [5][N][O]: ybar_2 .. ybar_6 of the step being swept
 };
 int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5);
-double tsit5_a(int i, int j);          // the Tsit5 tableau (mgn_api.cpp), 1-based: A[i][j], b = A[7][j]
+double tsit5_a(int i, int j);          // the Tsit5 tableau (mgn_solve.cpp), 1-based: A[i][j], b = A[7][j]
+
+// mgn_api.cpp, for the solve drivers of mgn_solve.cpp.  Hidden: they were file-local before the drivers had a file of their own, and
+// with default visibility these mgn:: functions would join the library's dynamic symbols
+#pragma GCC visibility push(hidden)
+int encode_impl(mgn_engine* h, bool use_norms, bool nodes = true, bool edges = true);
+int decode_impl(mgn_engine* h, bool use_norms);
+int run_processor(mgn_engine* h, int nsteps);
+int upload_inputs(mgn_engine* h, const float* a, int wa, const float* b, int wb, const float* ef, bool engine_order = false);
+bool elat_src_ok(mgn_engine* h);
+void invalidate_static(mgn_engine* h);
+size_t tile_floats(int64_t ntiles, int L);
+int alloc_latents(mgn_engine* h);
+int rebuild_graph(mgn_engine* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner, const char* who,
+                  const int32_t* owner_in = nullptr, int renumber = -1);
+int need_comm(mgn_engine* h, const char* who);
+int gather_rows_global(mgn_engine* h, const float* local_dev, int W, float* out);
+bool is_bf16(const mgn_engine* h);
+void shoot_release(mgn_engine* h);     // mgn_solve.cpp: drops mgn_shooting_grad's companions and staging
+#pragma GCC visibility pop
 
 #define HIPCHK(h, expr)                                                                              \
     do {                                                                                             \

@@ -1,4 +1,4 @@
-// Kernel argument blocks and launch wrappers shared by kernels.hip and mgn_api.cpp.
+// Kernel argument blocks and launch wrappers shared by kernels.hip, mgn_api.cpp and mgn_solve.cpp.
 // Internal to the engine; the public boundary is include/mgn_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <ctime>
 #include <string>
 #include <sys/stat.h>
@@ -309,10 +308,6 @@ ChunkPtrs chunk_ptrs(const mgn_engine* h, const ChunkRef& r) {
     return c;
 }
 
-// tile-major storage: rows padded to whole 32-row tiles
-size_t tile_floats(int64_t ntiles, int L) { return (size_t)ntiles * TILE * L; }
-
-
 inline int64_t tiles_or_one(int32_t nt) { return nt > 0 ? nt : 1; }
 
 // per-set buffers (sized by that set's local edges and by the owned + halo nodes)
@@ -340,23 +335,6 @@ int alloc_edge_set(mgn_engine* h, int q) {
             HIPCHK(h, hipMemsetAsync(b.b->p, 0, b.bytes, h->stream));
         }
     }
-    return MGN_OK;
-}
-
-int alloc_latents(mgn_engine* h) {
-    const int L = h->cfg.L;
-    const LocalGraph& g = h->g;
-    const int64_t ntn = tiles_or_one(h->ntiles_n);
-    HIPCHK(h, h->V.ensure(tile_floats(ntn, L) * 4));
-    HIPCHK(h, h->d_out.ensure((size_t)(g.n_own + 1) * h->cfg.O * 4));
-    HIPCHK(h, h->d_sum.ensure(4 * sizeof(double)));
-    HIPCHK(h, hipMemsetAsync(h->V.p, 0, tile_floats(ntn, L) * 4, h->stream));
-    if (h->cfg.dtype == MGN_BF16) {
-        HIPCHK(h, h->bV.ensure(tile_floats(ntn, L) * 2));
-        HIPCHK(h, hipMemsetAsync(h->bV.p, 0, tile_floats(ntn, L) * 2, h->stream));
-    }
-    for (int q = 0; q < h->nsets; ++q)
-        if (int rc = alloc_edge_set(h, q)) return rc;
     return MGN_OK;
 }
 
@@ -407,18 +385,6 @@ int run_graphed(mgn_engine* h, hipGraphExec_t& exec, bool& warm, F&& launches) {
     return MGN_OK;
 }
 
-// the resident right-hand side (mgn_set_static) and the hipGraph captured over its buffers go together
-void invalidate_static(mgn_engine* h) {
-    h->have_static = false;
-    h->lnall_edges = false;
-    if (h->rhs_exec) {
-        if (!h->host_only) (void)hipStreamSynchronize(h->stream);
-        (void)hipGraphExecDestroy(h->rhs_exec);
-    }
-    h->rhs_exec = nullptr;
-    h->rhs_warm = false;
-}
-
 // 16-row cooperative tiles (v_mfma_f32_16x16x4_f32): both kernels of a processor step must agree (the carry rows are per 16-edge
 // tile then), so the choice is made per handle and graph: fp32, L = 128, hidden_layers = 2, and the node launch and EVERY edge
 // set's launch in the cooperative size range
@@ -441,12 +407,6 @@ GenMlp gen_of(const mgn_engine* h, const GenOff& g, bool has_last) {
     m.nmid = nmid;
     m.use = (h->cfg.hidden_layers != 2 || get_kernel_path() == 4) ? 1 : 0;
     return m;
-}
-
-// step 0's edge launch can read its e rows from a second array (EdgeArgs::ElatSrc): one edge set on the 16-row kernels, one partition
-static bool elat_src_ok(mgn_engine* h) {
-    static const int on = [] { const char* e = getenv("MGN_RHS_ELAT_SRC"); return e ? atoi(e) : 1; }();   // 0: restore copy per right-hand side
-    return on && h->nsets == 1 && h->cfg.nranks == 1 && h->cfg.L == 128 && h->cfg.hidden_layers == 2 && get_kernel_path() != 4 && use_c16(h);
 }
 
 EdgeArgs edge_args(mgn_engine* h, int k, int q = 0) {
@@ -595,14 +555,50 @@ BfNodeArgs bf_node_args(mgn_engine* h, int k, int q = 0, bool project = false) {
     return a;
 }
 
-inline bool is_bf16(const mgn_engine* h) { return h->cfg.dtype == MGN_BF16; }
-
 }  // namespace
+
+// ---- shared with the solve drivers (mgn_solve.cpp; declared in engine_internal.h) ----
+int mgn::alloc_latents(mgn_engine* h) {
+    const int L = h->cfg.L;
+    const LocalGraph& g = h->g;
+    const int64_t ntn = tiles_or_one(h->ntiles_n);
+    HIPCHK(h, h->V.ensure(tile_floats(ntn, L) * 4));
+    HIPCHK(h, h->d_out.ensure((size_t)(g.n_own + 1) * h->cfg.O * 4));
+    HIPCHK(h, h->d_sum.ensure(4 * sizeof(double)));
+    HIPCHK(h, hipMemsetAsync(h->V.p, 0, tile_floats(ntn, L) * 4, h->stream));
+    if (h->cfg.dtype == MGN_BF16) {
+        HIPCHK(h, h->bV.ensure(tile_floats(ntn, L) * 2));
+        HIPCHK(h, hipMemsetAsync(h->bV.p, 0, tile_floats(ntn, L) * 2, h->stream));
+    }
+    for (int q = 0; q < h->nsets; ++q)
+        if (int rc = alloc_edge_set(h, q)) return rc;
+    return MGN_OK;
+}
+
+// the resident right-hand side (mgn_set_static) and the hipGraph captured over its buffers go together
+void mgn::invalidate_static(mgn_engine* h) {
+    h->have_static = false;
+    h->lnall_edges = false;
+    if (h->rhs_exec) {
+        if (!h->host_only) (void)hipStreamSynchronize(h->stream);
+        (void)hipGraphExecDestroy(h->rhs_exec);
+    }
+    h->rhs_exec = nullptr;
+    h->rhs_warm = false;
+}
+
+// step 0's edge launch can read its e rows from a second array (EdgeArgs::ElatSrc): one edge set on the 16-row kernels, one partition
+bool mgn::elat_src_ok(mgn_engine* h) {
+    static const int on = [] { const char* e = getenv("MGN_RHS_ELAT_SRC"); return e ? atoi(e) : 1; }();   // 0: restore copy per right-hand side
+    return on && h->nsets == 1 && h->cfg.nranks == 1 && h->cfg.L == 128 && h->cfg.hidden_layers == 2 && get_kernel_path() != 4 && use_c16(h);
+}
+
+bool mgn::is_bf16(const mgn_engine* h) { return h->cfg.dtype == MGN_BF16; }
+// tile-major storage: rows padded to whole 32-row tiles
+size_t mgn::tile_floats(int64_t ntiles, int L) { return (size_t)ntiles * TILE * L; }
 
 // =================================================================================================
 extern "C" {
-
-static void shoot_release(mgn_handle* h);   // mgn_shooting_grad's companions (below)
 
 int mgn_abi_version(void) { return MGN_ABI_VERSION; }
 
@@ -989,8 +985,8 @@ int mgn_set_norms(mgn_handle* h, const float* ns, const float* nsh, const float*
 static int g_renumber = [] { const char* e = getenv("MGN_RENUMBER"); return e ? atoi(e) : 1; }();
 
 // (re)build the local graph from the kept global edge lists and upload it.  keep_owner: node partition unchanged
-static int rebuild_graph(mgn_handle* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner,
-                         const char* who, const int32_t* owner_in = nullptr, int renumber = -1) {
+extern "C++" int mgn::rebuild_graph(mgn_handle* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner,
+                                    const char* who, const int32_t* owner_in, int renumber) {
     shoot_release(h);                     // the companion of mgn_shooting_grad replicates the old graph
     h->have_graph = false;
     h->hx_ready = false;
@@ -1198,7 +1194,7 @@ int mgn_boundary_count(const mgn_handle* h, int32_t* n_boundary) try {
 // ---- staged pipeline ----------------------------------------------------------------------------
 // engine_order: the node rows must sit on the device in the ENGINE's order even on one partition -- the callers that later overwrite
 // the state slot of d_nfA with rows in that order (mgn_set_static + mgn_ode_step(x), mgn_rollout)
-static int upload_inputs(mgn_handle* h, const float* a, int wa, const float* b, int wb, const float* ef, bool engine_order = false) {
+extern "C++" int mgn::upload_inputs(mgn_handle* h, const float* a, int wa, const float* b, int wb, const float* ef, bool engine_order) {
     const LocalGraph& g = h->g;
     h->in_wa = wa;
     h->in_wb = wb;
@@ -1265,7 +1261,7 @@ static int project_set(mgn_handle* h, int k, int q, int32_t tile0 = 0, int32_t n
     return MGN_OK;
 }
 
-static int encode_impl(mgn_handle* h, bool use_norms, bool nodes = true, bool edges = true) {
+extern "C++" int mgn::encode_impl(mgn_handle* h, bool use_norms, bool nodes, bool edges) {
     const mgn_config& c = h->cfg;
     const LocalGraph& g = h->g;
     const float* nrm = h->norms.as<float>();
@@ -1447,7 +1443,7 @@ int mgn_proc_node_phase(mgn_handle* h, int32_t k, int32_t phase) try {
     return MGN_OK;
 } MGN_CATCH(h)
 
-static int decode_impl(mgn_handle* h, bool use_norms) {
+extern "C++" int mgn::decode_impl(mgn_handle* h, bool use_norms) {
     const mgn_config& c = h->cfg;
     ProfScope ps(h, F_DEC);
     if (is_bf16(h)) HIPCHK(h, launch_tile_bf16_to_f32(h->bV.as<uint16_t>(), h->V.as<float>(), h->ntiles_n, h->stream));
@@ -1496,9 +1492,7 @@ int mgn_fwd_download(mgn_handle* h, float* out) try {
 } MGN_CATCH(h)
 
 static int forward_partitioned(mgn_handle* h, const float* nf, const float* ef, float* out);
-static int gather_rows_global(mgn_handle* h, const float* local_dev, int W, float* out);
 static int processor_pass_staged(mgn_handle* h, int32_t nsteps, bool begin);
-static int need_comm(mgn_handle* h, const char* who);
 
 // the O x N state of a right-hand side: one partition takes it as it is, a partitioned handle the rows it owns
 static int upload_state(mgn_handle* h, const float* x) {
@@ -1515,7 +1509,7 @@ static int upload_state(mgn_handle* h, const float* x) {
     return MGN_OK;
 }
 
-static int run_processor(mgn_handle* h, int nsteps) {
+extern "C++" int mgn::run_processor(mgn_handle* h, int nsteps) {
     // partitioned: the staged schedule; P, Q of step 0 came from the encoder, so the pass starts with their exchange
     if (h->cfg.nranks != 1) return processor_pass_staged(h, nsteps, false);
     for (int k = 0; k < nsteps; ++k) {
@@ -1677,1296 +1671,6 @@ int mgn_ode_step(mgn_handle* h, const float* x, const float* onehot, const float
     return mgn_fwd_download(h, dxdt);
 } MGN_CATCH(h)
 
-// ---- native rollout driver (N1) -----------------------------------------------------------------------------
-namespace {
-
-// Tsitouras 5(4) tableau (the method OrdinaryDiffEq.jl calls Tsit5)
-const double TS_C[7] = {0.0, 0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0};
-const double TS_A[7][6] = {
-    {0, 0, 0, 0, 0, 0},
-    {0.161, 0, 0, 0, 0, 0},
-    {-0.008480655492356989, 0.335480655492357, 0, 0, 0, 0},
-    {2.8971530571054935, -6.359448489975075, 4.3622954328695815, 0, 0, 0},
-    {5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525, 0, 0},
-    {5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383, 0},
-    {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774}};
-const double TS_BT[7] = {-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629,
-                         0.5823571654525552, -0.45808210592918697, 0.015151515151515152};
-
-}  // namespace
-
-extern "C++" double mgn::tsit5_a(int i, int j) { return TS_A[i - 1][j - 1]; }   // (this region is extern "C")
-
-namespace {
-
-// mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
-// of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
-struct Tsit5Control {
-    static constexpr double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
-    double qold = 1e-4;
-    bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
-        const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
-        if (EEst <= 1.0) {
-            double q = q11 / std::pow(qold, beta2);
-            q = std::max(1.0 / qmax, std::min(1.0 / qmin, q / gamma));
-            qold = std::max(EEst, 1e-4);
-            if (!hit_stop || hstep >= dt * (1 - 1e-9)) dt = hstep / q;
-            else dt = std::max(dt, hstep / q);
-            return true;
-        }
-        dt = hstep / std::min(1.0 / qmin, q11 / gamma);
-        return false;
-    }
-};
-
-// The time grid of a solve.  The solver's time type (mgn_rollout_desc.time_f64): Float32 times are held in doubles and rounded after
-// every operation (a double operation on two floats, rounded to float, IS the float operation).
-struct TimeGrid {
-    bool f64 = false;
-    double t0 = 0.0, t1 = 0.0, dt = 0.0, sdt = 0.0;     // sdt: saves_dt
-    explicit TimeGrid(const mgn_rollout_desc* d)
-        : f64(d->time_f64 != 0), t0(f64 ? d->t0_f64 : (double)d->t0), t1(f64 ? d->t1_f64 : (double)d->t1),
-          dt(f64 ? d->dt_f64 : (double)d->dt), sdt(f64 ? d->saves_dt_f64 : (double)d->saves_dt) {}
-    double tt(double v) const { return f64 ? v : (double)(float)v; }
-    // the time of save point i
-    double stop_time(int i) const { return tt(t0 + (double)i * sdt); }
-    // the fixed-step grid: the time after step i of K is the integrator's own t <- t + dt in its time type, step after step (a fixed-step
-    // solve has no stops to snap to but the end of the interval); t0 + (i + 1) dt would floor differently at frame boundaries
-    double next(int64_t i, int64_t K, double t) const { return (i + 1 == K && std::fabs(tt(t + dt) - t1) <= 1e-5 * sdt) ? t1 : tt(t + dt); }
-};
-
-// one call's buffers carved out of one DevBuf: 256-byte aligned offsets, then one ensure of `off` bytes
-struct Arena {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
-
-struct Rollout {
-    mgn_engine* h;
-    mgn_rollout_desc* d;
-    TimeGrid tg;
-    int64_t n;                 // rows * O of the state this handle integrates (all N rows, or the owned rows of a partition)
-    int64_t n_global = 0;      // N * O
-    int32_t nrows = 0;
-    float *u, *unew, *utmp, *k[7], *frames, *saves;
-    uint8_t* mask;
-    double* partial;
-    int n_rhs = 0;
-    Rollout(mgn_engine* h_, mgn_rollout_desc* d_, const TimeGrid& g) : h(h_), d(d_), tg(g) {}
-    double tt(double v) const { return tg.tt(v); }
-
-    // One right-hand side is ~35 launches; on a small mesh they are latency-bound, so each distinct (x, kout) pair of the
-    // solver (1 for Euler, 7 for Tsit5) gets its launch sequence captured once and replayed (hipGraph).
-    struct RhsGraph { float* x; float* kout; hipGraphExec_t exec; };
-    std::vector<RhsGraph> graphs;
-    bool warmed = false;
-
-    bool lnall_edges_done = false;
-    int rhs_launches(float* x, float* kout) {
-        const mgn_config& c = h->cfg;
-        if (c.ln_dims == MGN_LN_ALL) {     // the unfused whole-array right-hand side (mgn_train.cpp); its first evaluation encodes the edges
-            const int rc = lnall_rhs_dev(h, x, kout, lnall_edges_done);
-            lnall_edges_done = true;
-            return rc;
-        }
-        h->srcA_override = x;
-        h->out_override = kout;
-        int rc = encode_impl(h, true, true, false);
-        if (!rc) {
-            // encoded edge latents are identical for every RHS of a trajectory (static edge features, frozen e_norm)
-            const bool bf = c.dtype == MGN_BF16;
-            const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * (bf ? 2 : 4);
-            if (elat_src_ok(h)) {
-                h->elat_src_override = reinterpret_cast<const float*>(h->ode.as<char>() + elat0_off);
-            } else {
-                hipError_t e = hipMemcpyAsync(bf ? h->es[0].bElat.p : h->es[0].Elat.p, h->ode.as<char>() + elat0_off, eb, hipMemcpyDeviceToDevice, h->stream);
-                if (e != hipSuccess) rc = fail(h, MGN_E_HIP, "rollout: Elat restore failed: %s", hipGetErrorString(e));
-            }
-        }
-        if (!rc) rc = run_processor(h, c.mps);
-        h->elat_src_override = nullptr;
-        if (!rc) rc = decode_impl(h, true);
-        h->srcA_override = nullptr;
-        h->out_override = nullptr;
-        return rc;
-    }
-
-    // data[field][:, :, floor(Int, t / saves_dt) + 1] (reference src/solve.jl:151): the quotient in the solver's own time type,
-    // no tolerance -- a t that sits an ulp below a frame boundary re-uses the previous frame there too -- and an index outside
-    // the data is the reference's BoundsError.  MGN_INFLOW_TOLERANT: nearest-below with a guard of 1e-3 frames (a Float32 time drifts by ~1e-4 frames), clamped.
-    int frame_index(double t, int64_t* out) const {
-        int64_t fr;
-        if (d->inflow_rule == MGN_INFLOW_TOLERANT) {
-            fr = (int64_t)std::floor(t / tg.sdt + 1e-3);
-            if (fr < 0) fr = 0;
-            if (fr >= d->n_frames) fr = d->n_frames - 1;
-        } else {
-            fr = (int64_t)std::floor(tt(t / tg.sdt));
-            if (fr < 0 || fr >= d->n_frames)
-                return fail(h, MGN_E_ARG, "mgn_rollout: inflow frame %lld at t = %.9g is outside the %d frames given (reference: BoundsError)",
-                            (long long)fr, t, d->n_frames);
-        }
-        *out = fr;
-        return MGN_OK;
-    }
-
-    // mgn_shooting_grad: the state holds windows of win_rows rows whose frames were chosen on the host, RHS evaluation e of the solve
-    // reading ftab[e * ftab_ld + window] (frames [n_frames][win_rows][O], mask [win_rows])
-    const int32_t* ftab = nullptr;
-    int64_t ftab_ld = 0, win_rows = 0;
-
-    // f(x, t): in-place inflow overwrite of x, then dx/dt -> kout    (ode_func_eval, reference src/solve.jl:147-158)
-    int rhs(float* x, double t, float* kout) {
-        const mgn_config& c = h->cfg;
-        if (mask && frames && ftab) {
-            HIPCHK(h, launch_shoot_overwrite(x, frames, mask, ftab + (size_t)n_rhs * ftab_ld, win_rows, c.O, nrows, h->stream));
-        } else if (mask && frames) {
-            int64_t fr;
-            if (int rc = frame_index(t, &fr)) return rc;
-            HIPCHK(h, launch_overwrite(x, frames + (size_t)fr * n, mask, nrows, c.O, h->stream));
-        }
-        ++n_rhs;
-        const bool graphable = h->use_graph && !h->prof && h->stream != nullptr && h->cfg.nranks == 1 && launch_is_small(h->ntiles_n);
-        if (!graphable || !warmed) {       // the first RHS runs eagerly: it sets the per-kernel attributes outside of any capture
-            warmed = true;
-            return rhs_launches(x, kout);
-        }
-        for (const RhsGraph& g : graphs)
-            if (g.x == x && g.kout == kout) {
-                HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
-                return MGN_OK;
-            }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            h->use_graph = 0;
-            return rhs_launches(x, kout);
-        }
-        const int rc = rhs_launches(x, kout);
-        const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-        hipGraphExec_t exec = nullptr;
-        if (rc != MGN_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            h->use_graph = 0;              // eager from here on
-            if (rc != MGN_OK) return rc;
-            return rhs_launches(x, kout);
-        }
-        (void)hipGraphDestroy(graph);
-        graphs.push_back({x, kout, exec});
-        HIPCHK(h, hipGraphLaunch(exec, h->stream));
-        return MGN_OK;
-    }
-    ~Rollout() {
-        for (RhsGraph& g : graphs) (void)hipGraphExecDestroy(g.exec);
-    }
-    size_t elat0_off = 0;
-
-    int norm(const float* a, const float* b, const LinComb& lc, float dt, double* out) {
-        const int np_ = errnorm_partials();
-        HIPCHK(h, launch_errnorm(a, b, lc, dt, d->abstol, d->reltol, n, partial, h->stream));
-        std::vector<double> r(np_);
-        HIPCHK(h, hipMemcpyAsync(r.data(), partial, np_ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        double s = 0;
-        for (double v : r) s += v;
-        if (h->cfg.nranks != 1) {      // the same bits on every rank -> the same accept / reject decisions
-            if (h->comm->allreduce_f64(&s, 1, 0, h->stream) != 0) return fail(h, MGN_E_RCCL, "rollout: error-norm reduction failed: %s", h->comm->err.c_str());
-        }
-        const int64_t ng = n_global > 0 ? n_global : n;
-        *out = std::sqrt(s / (double)(ng > 0 ? ng : 1));
-        return MGN_OK;
-    }
-
-    // ---- saves ----
-    int saved = 0;                         // saves taken
-    std::vector<int64_t> save_step;        // the accepted steps before each save taken
-    // mgn_rollout_eval: every save is compared with its ground-truth frame as it is produced (k_save_error) -- gt [n_saves][n] in the
-    // engine's order, acc [n] doubles, part [n_saves][save_error_blocks(nrows)][O] -- and kept only if the caller wants the solution
-    const float* ev_gt = nullptr;
-    double *ev_acc = nullptr, *ev_part = nullptr;
-    // saves[saved] <- u, the state after steps_done accepted steps
-    int save(int64_t steps_done) {
-        save_step.push_back(steps_done);
-        if (ev_gt)
-            HIPCHK(h, launch_save_error(u, ev_gt + (size_t)saved * n, ev_acc, ev_part + (size_t)saved * save_error_blocks(nrows) * h->cfg.O, nrows,
-                                        h->cfg.O, h->stream));
-        if (saves) HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-        ++saved;
-        return MGN_OK;
-    }
-    // the saves a fixed-step plan (the accepted steps before every save, fixed_grid) takes after steps_done steps
-    int saves_after(const std::vector<int64_t>& plan, int64_t steps_done) {
-        while (saved < (int)plan.size() && plan[saved] == steps_done)
-            if (int rc = save(steps_done)) return rc;
-        return MGN_OK;
-    }
-
-    // Training form (solver-based training, ode_func_train): the right-hand side sees a COPY of its input with the inflow rows written --
-    // utmp for Euler; za for Tsit5 stage 1 (z_{n,1}), zs for stages 2 .. 6, z7 for stage 7 (z_{n+1,1}) -- and the state is never
-    // overwritten.  mgn_rollout (train = false), or no inflow mask: the input itself (mgn_rollout overwrites it in place).
-    bool train = false;
-    float *za = nullptr, *zs = nullptr, *z7 = nullptr;
-    float* kept = nullptr;     // training form: the current Tsit5 trial's six stage inputs [6][n] (z_{n,1}, stages 2 .. 6), or null
-
-    // the array the right-hand side of input y sees (z: its training-form copy)
-    float* rhs_input(float* y, float* z) const { return (train && mask) ? z : y; }
-    int eval(float* y, float* z, double t, float* kout) {
-        float* x = rhs_input(y, z);
-        if (x != y) HIPCHK(h, hipMemcpyAsync(x, y, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-        return rhs(x, t, kout);
-    }
-
-    // ---- fixed-step Euler, training form: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k -> store[k] and x_K -> store[K]; saves from the plan ----
-    int euler_train(int64_t K, const std::vector<int64_t>& plan, float* store) {
-        double t = tg.t0;
-        if (int rc = saves_after(plan, 0)) return rc;
-        for (int64_t i = 0; i < K; ++i) {
-            float* xin = rhs_input(u, utmp);
-            if (int rc = eval(u, utmp, t, k[0])) return rc;
-            HIPCHK(h, hipMemcpyAsync(store + (size_t)i * n, xin, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-            LinComb lc{1, {1.f}, {k[0]}};
-            HIPCHK(h, launch_lincomb(u, u, lc, (float)tg.dt, n, h->stream));
-            t = tg.next(i, K, t);
-            ++d->n_accept;
-            if (int rc = saves_after(plan, i + 1)) return rc;
-        }
-        HIPCHK(h, hipMemcpyAsync(store + (size_t)K * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-        return MGN_OK;
-    }
-
-    // ---- Tsit5, shared by mgn_rollout, mgn_solver_grad_tsit5 and mgn_shooting_grad ----
-    // k1 = f(u) at t (FSAL afterwards)
-    int tsit5_first(double t) { return eval(u, za, t, k[0]); }
-    // Hairer-Wanner starting step from (u, k1)
-    int tsit5_h0(double t, double* dt) {
-        double d0, d1, d2;
-        LinComb l1{1, {1.f}, {k[0]}};
-        // d0 = ||u||, d1 = ||f0|| in the scaled norm: errnorm(dt = 1) of u and k1 themselves
-        LinComb lu{1, {1.f}, {u}};
-        if (int rc = norm(u, u, lu, 1.f, &d0)) return rc;
-        if (int rc = norm(u, u, l1, 1.f, &d1)) return rc;
-        const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        HIPCHK(h, launch_lincomb(utmp, u, l1, (float)h0, n, h->stream));
-        if (int rc = eval(utmp, zs, tt(t + h0), k[1])) return rc;
-        LinComb ld{2, {1.f, -1.f}, {k[1], k[0]}};
-        if (int rc = norm(u, u, ld, (float)(1.0 / h0), &d2)) return rc;
-        const double mx = d1 > d2 ? d1 : d2;
-        const double h1 = mx <= 1e-15 ? (h0 * 1e-3 > 1e-6 ? h0 * 1e-3 : 1e-6) : std::pow(0.01 / mx, 1.0 / 5);
-        *dt = 100 * h0 < h1 ? 100 * h0 : h1;
-        return MGN_OK;
-    }
-    // one trial step from (u, k1) over hstep: stages 2 .. 6 at tt(t + tt(c_i hstep)), unew = u + hstep sum_j A[7][j] k_j, and k7 = f(unew)
-    // at t7 (FSAL); EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H
-    int tsit5_trial(double t, double hstep, double t7, double* EEst) {
-        for (int sidx = 1; sidx < 7; ++sidx) {     // stages 2..7; stage 7 is evaluated on unew (FSAL)
-            LinComb lc{sidx, {}, {}};
-            for (int j = 0; j < sidx; ++j) { lc.c[j] = (float)TS_A[sidx][j]; lc.k[j] = k[j]; }
-            float* dst = (sidx == 6) ? unew : utmp;
-            HIPCHK(h, launch_lincomb(dst, u, lc, (float)hstep, n, h->stream));
-            float* z = (sidx == 6) ? z7 : zs;
-            if (int rc = eval(dst, z, sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep)), k[sidx])) return rc;
-            if (sidx < 6 && kept)
-                HIPCHK(h, hipMemcpyAsync(kept + (size_t)sidx * n, rhs_input(dst, z), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-        }
-        if (!EEst) return MGN_OK;
-        LinComb le{7, {}, {}};
-        for (int j = 0; j < 7; ++j) { le.c[j] = (float)TS_BT[j]; le.k[j] = k[j]; }
-        return norm(u, unew, le, (float)hstep, EEst);
-    }
-    // the accepted trial becomes the state: unew -> u, k7 -> k1 (FSAL), z_{n+1,1} -> za
-    void tsit5_advance() {
-        std::swap(u, unew);
-        std::swap(k[0], k[6]);
-        std::swap(za, z7);
-    }
-
-    // training form: slot(n, &p) gives accepted step n's storage for its six stage inputs
-    using Slot = std::function<int(int64_t, float**)>;
-    std::vector<double> step_t, step_h;    // training form: every accepted step's t and h
-    // before a trial of step n: its storage, and z_{n,1} (what k1's right-hand side saw) into it
-    int begin_trial(const Slot& slot, int64_t n_) {
-        if (int rc = slot(n_, &kept)) return rc;
-        HIPCHK(h, hipMemcpyAsync(kept, rhs_input(u, za), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-        return MGN_OK;
-    }
-
-    // fixed-step Tsit5 in the training form: K steps of dt on the fixed grid, stage 7 at t_{n+1}; saves from the plan
-    int tsit5_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot& slot) {
-        double t = tg.t0;
-        if (int rc = saves_after(plan, 0)) return rc;
-        if (int rc = tsit5_first(t)) return rc;
-        for (int64_t i = 0; i < K; ++i) {
-            const double tn = tg.next(i, K, t);
-            if (int rc = begin_trial(slot, i)) return rc;
-            if (int rc = tsit5_trial(t, tg.dt, tn, nullptr)) return rc;
-            tsit5_advance();
-            step_t.push_back(t); step_h.push_back(tg.dt);
-            t = tn;
-            ++d->n_accept;
-            if (int rc = saves_after(plan, i + 1)) return rc;
-        }
-        kept = nullptr;
-        return MGN_OK;
-    }
-
-    // adaptive Tsit5 from t0 to t1: mgn_rollout's PI controller (Tsit5Control), tstops = saves, a save on every stop it hits, missing saves
-    // (t1 short of the last stop) padded with the final state.  mgn_rollout (no slot): stage 7 at c7 h, and the iteration guard stops
-    // silently.  Training form (slot): every trial's stage inputs kept in slot(n), stage 7 is z_{n+1,1} and sees t_{n+1}, the accepted
-    // steps recorded, and the guard fails the call.
-    int tsit5_adaptive(const char* who, const Slot* slot) {
-        const int ns = d->n_saves;
-        double t = tg.t0;
-        if (int rc = save(0)) return rc;
-        if (int rc = tsit5_first(t)) return rc;     // k1 (FSAL afterwards)
-        double dt = tg.dt;
-        if (dt <= 0)   // Hairer-Wanner starting step
-            if (int rc = tsit5_h0(t, &dt)) return rc;
-        Tsit5Control ctl;
-        int64_t guard = 0, nacc = 0;
-        // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save periods is not worth a step
-        while (t < tg.t1 - 1e-5 * tg.sdt) {
-            if (++guard >= 10000000) {
-                if (!slot) break;
-                return fail(h, MGN_E_STATE, "%s: %lld trial steps without reaching t1", who, (long long)guard);
-            }
-            double tstop = saved < ns ? tg.stop_time(saved) : tg.t1;
-            if (tstop > tg.t1) tstop = tg.t1;
-            bool hit_stop = false;
-            double hstep = dt;
-            if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
-            const double tn = hit_stop ? tstop : tt(t + hstep);
-            // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
-            const double t7 = (slot || hit_stop) ? tn : tt(t + tt(TS_C[6] * hstep));
-            if (slot)
-                if (int rc = begin_trial(*slot, nacc)) return rc;
-            double EEst;
-            if (int rc = tsit5_trial(t, hstep, t7, &EEst)) return rc;
-            if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
-            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
-                tsit5_advance();
-                if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
-                t = tn;
-                ++nacc;
-                ++d->n_accept;
-                if (hit_stop && saved < ns && std::fabs(tg.stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12)
-                    if (int rc = save(nacc)) return rc;
-            } else {
-                ++d->n_reject;
-            }
-        }
-        kept = nullptr;
-        while (saved < ns)
-            if (int rc = save(nacc)) return rc;
-        return MGN_OK;
-    }
-};
-// b.ensure(bytes), or MGN_E_OOM (MGN_E_HIP for any other error) with the message "<what>: <the HIP error>"
-__attribute__((format(printf, 4, 5))) int ensure_or_fail(mgn_handle* h, DevBuf& b, size_t bytes, const char* what, ...) {
-    const hipError_t e = b.ensure(bytes);
-    if (e == hipSuccess) return MGN_OK;
-    (void)hipGetLastError();
-    char msg[400];
-    va_list ap;
-    va_start(ap, what);
-    vsnprintf(msg, sizeof msg, what, ap);
-    va_end(ap);
-    return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %s", msg, hipGetErrorString(e));
-}
-
-// x0 (u null: not wanted), the inflow frames and the inflow mask (null: none) of the caller's order into the engine's order on the device:
-// the rows this handle owns (all N, or a partition's), renumbered or not.  A reordered copy is staged on the host and synchronised.
-int upload_engine_order(mgn_handle* h, const mgn_rollout_desc* d, float* u, float* frames, uint8_t* mask) {
-    const LocalGraph& g = h->g;
-    const int O = h->cfg.O;
-    const bool part = h->cfg.nranks != 1;
-    const int32_t nloc = part ? g.n_own : g.N;
-    const int nf = frames ? d->n_frames : 0;
-    const size_t nb = (size_t)nloc * O * 4, fb = (size_t)nf * nb;
-    if (!part && !g.renumbered) {
-        if (u) HIPCHK(h, hipMemcpyAsync(u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
-        if (frames) HIPCHK(h, hipMemcpyAsync(frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
-        if (mask) HIPCHK(h, hipMemcpyAsync(mask, d->inflow_mask, (size_t)nloc, hipMemcpyHostToDevice, h->stream));
-        return MGN_OK;
-    }
-    std::vector<float> lx((size_t)nloc * O * (1 + nf));
-    std::vector<uint8_t> lm(mask ? (size_t)nloc : 0);
-    for (int32_t i = 0; i < nloc; ++i) {
-        const size_t gi = (size_t)g.own_gid[i];
-        if (u) memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
-        for (int f = 0; f < nf; ++f)
-            memcpy(lx.data() + ((size_t)(1 + f) * nloc + i) * O, d->inflow_data + ((size_t)f * g.N + gi) * O, (size_t)O * 4);
-        if (mask) lm[i] = d->inflow_mask[gi];
-    }
-    if (u) HIPCHK(h, hipMemcpyAsync(u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
-    if (frames) HIPCHK(h, hipMemcpyAsync(frames, lx.data() + (size_t)nloc * O, fb, hipMemcpyHostToDevice, h->stream));
-    if (mask) HIPCHK(h, hipMemcpyAsync(mask, lm.data(), (size_t)nloc, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MGN_OK;
-}
-
-// count [N][O] arrays in the engine's order on the device (one partition) into the caller's order on the host; the caller synchronises
-int saves_to_caller(mgn_handle* h, const float* src, int64_t count, float* out) {
-    const LocalGraph& g = h->g;
-    const int O = h->cfg.O;
-    const size_t bytes = (size_t)count * g.N * O * 4;
-    if (!g.renumbered) {
-        HIPCHK(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream));
-        return MGN_OK;
-    }
-    std::vector<float> sv((size_t)count * g.N * O);
-    HIPCHK(h, hipMemcpyAsync(sv.data(), src, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t i = 0; i < count; ++i)
-        for (int32_t j = 0; j < g.N; ++j)
-            memcpy(out + ((size_t)i * g.N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * g.N + j) * O, (size_t)O * 4);
-    return MGN_OK;
-}
-
-// the static inputs of a solve (one-hot node types, raw edge features, val_mask; x0 only fills the encoder's state slot: every right-hand
-// side reads its state through srcA_override), and the edges encoded ONCE per trajectory into elat0 (eb: its fp32 bytes)
-int upload_statics(mgn_handle* h, const mgn_rollout_desc* d, const float* x0, char* elat0, size_t eb) {
-    const mgn_config& c = h->cfg;
-    if (int rc = upload_inputs(h, x0, c.O, d->node_type_onehot, c.Fn - c.O, d->ef_raw, true)) return rc;
-    h->have_mask = d->val_mask != nullptr;
-    if (d->val_mask) {
-        HIPCHK(h, h->d_mask.ensure((size_t)h->g.N * 4));
-        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)h->g.N * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
-    if (int rc = encode_impl(h, true, false, true)) return rc;
-    const bool bf = is_bf16(h);
-    HIPCHK(h, hipMemcpyAsync(elat0, bf ? h->es[0].bElat.p : h->es[0].Elat.p, bf ? eb / 2 : eb, hipMemcpyDeviceToDevice, h->stream));
-    return MGN_OK;
-}
-
-// mgn_rollout (e null) and mgn_rollout_eval (e: its checked descriptor, one partition): the same solve, the same launches in the same
-// order; with e every save is reduced against its ground-truth frame as it is produced (Rollout::save) and d->out is optional
-int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who) {
-    const bool lnall = h && h->cfg.ln_dims == MGN_LN_ALL;
-    if (int rc = need(h, true, true, !lnall, true)) return rc;
-    const mgn_config& c = h->cfg;
-    const bool part = c.nranks != 1;      // partitioned: every rank integrates the rows it owns; error norms are reduced over the ranks
-    if (part) if (int rc = need_comm(h, who)) return rc;
-    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
-    if (!d || !d->x0 || (!d->out && !e) || !d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
-    const TimeGrid T(d);
-    if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (d->solver == 0 && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
-    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "%s: unknown inflow_rule", who);
-    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
-    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "%s: inflow mask and data go together", who);
-    if (d->solver == 1 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
-    const LocalGraph& g = h->g;
-    invalidate_static(h);
-    Rollout R(h, d, T);
-    const int32_t nloc = part ? g.n_own : g.N;        // rows of the state this handle integrates
-    R.n = (int64_t)nloc * c.O;
-    R.n_global = (int64_t)g.N * c.O;
-    R.nrows = nloc;
-    const size_t nb = (size_t)R.n * 4;
-    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = d->out ? (size_t)d->n_saves * nb : 0;
-    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
-    // evaluation: ground truth that IS the inflow data is compared where upload_engine_order puts the frames; the selection in the
-    // engine's order (n_sel == 0: all elements, no index array)
-    const bool gt_is_frames = e && e->gt == d->inflow_data && d->n_frames >= d->n_saves;
-    const int eblk = e ? save_error_blocks(nloc) : 0;
-    const int64_t n_val = e ? (e->n_sel > 0 ? e->n_sel : R.n) : 0;
-    std::vector<int64_t> sel;
-    if (e && e->n_sel > 0) {
-        std::vector<int32_t> g2l;
-        if (g.renumbered) {
-            g2l.resize((size_t)g.N);
-            for (int32_t i = 0; i < g.N; ++i) g2l[(size_t)g.own_gid[i]] = i;
-        }
-        sel.resize((size_t)e->n_sel);
-        for (int64_t i = 0; i < e->n_sel; ++i) {
-            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;      // (checked by mgn_rollout_eval)
-            sel[(size_t)i] = g.renumbered ? (int64_t)g2l[(size_t)(li / c.O)] * c.O + li % c.O : li;
-        }
-    }
-    Arena a;
-    const size_t o_u = a.take(nb), o_un = a.take(nb), o_ut = a.take(nb);
-    size_t o_k[7];
-    for (auto& o : o_k) o = a.take(nb);
-    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)nloc), o_part = a.take(errnorm_partials() * sizeof(double));
-    R.elat0_off = a.take(eb);
-    const size_t o_eacc = a.take(e ? (size_t)R.n * 8 : 0), o_epart = a.take((size_t)d->n_saves * eblk * c.O * 8),
-                 o_egt = a.take(e && !gt_is_frames ? (size_t)d->n_saves * nb : 0), o_etmp = a.take(e && !gt_is_frames && g.renumbered ? nb : 0),
-                 o_esel = a.take(sel.size() * 8), o_evp = a.take(e ? (size_t)save_error_blocks(n_val) * 8 : 0),
-                 o_ems = a.take(e && e->mse_save ? (size_t)d->n_saves * c.O * 8 : 0), o_emt = a.take(e && e->mse_time ? nb : 0);
-    HIPCHK(h, h->ode.ensure(a.off));
-    char* base = h->ode.as<char>();
-    R.u = (float*)(base + o_u); R.unew = (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
-    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[j]);
-    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
-    R.saves = d->out ? (float*)(base + o_sv) : nullptr;
-    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
-    R.partial = (double*)(base + o_part);
-    if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
-    if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
-    if (e) {
-        float* gtl = (float*)(base + o_egt);
-        for (int s = 0; s < d->n_saves && !gt_is_frames; ++s) {     // as solver_targets: host or device, gathered on the device when renumbered
-            const float* src = e->gt + (size_t)s * R.n;
-            if (!g.renumbered) {
-                HIPCHK(h, hipMemcpyAsync(gtl + (size_t)s * R.n, src, nb, hipMemcpyDefault, h->stream));
-            } else {
-                HIPCHK(h, hipMemcpyAsync(base + o_etmp, src, nb, hipMemcpyDefault, h->stream));
-                HIPCHK(h, launch_permute_rows(gtl + (size_t)s * R.n, (const float*)(base + o_etmp), h->d_own_gid.as<int32_t>(), g.N, c.O, false, h->stream));
-            }
-        }
-        if (!sel.empty()) HIPCHK(h, hipMemcpyAsync(base + o_esel, sel.data(), sel.size() * 8, hipMemcpyHostToDevice, h->stream));
-        R.ev_gt = gt_is_frames ? R.frames : gtl;
-        R.ev_acc = (double*)(base + o_eacc);
-        R.ev_part = (double*)(base + o_epart);
-        HIPCHK(h, hipMemsetAsync(R.ev_acc, 0, (size_t)R.n * 8, h->stream));
-    }
-
-    d->n_accept = d->n_reject = 0;
-    if (d->solver == 0) {
-        if (int rc = R.save(0)) return rc;   // solution at t0
-        double t = T.t0;
-        const int64_t nsteps = (int64_t)std::llround((T.t1 - T.t0) / T.dt);
-        for (int64_t i = 0; i < nsteps; ++i) {
-            if (int rc = R.rhs(R.u, t, R.k[0])) return rc;
-            LinComb lc{1, {1.f}, {R.k[0]}};
-            HIPCHK(h, launch_lincomb(R.u, R.u, lc, (float)T.dt, R.n, h->stream));
-            t = T.next(i, nsteps, t);
-            ++d->n_accept;
-            // saveat: the state of the step that ends at the save point.  In its own time type the integrator's t drifts off the
-            // save grid by a few ulps per step (Float32: ~1e-6 s after 600 steps of 0.01 s); the reference interpolates there, which
-            // moves the saved state by (drift / dt) of one step's change -- far below the rollout tolerance -- so: the nearest step.
-            while (R.saved < d->n_saves && T.stop_time(R.saved) <= t + 0.25 * T.dt)
-                if (int rc = R.save(i + 1)) return rc;
-        }
-        while (R.saved < d->n_saves)      // (t1 short of the last stop: repeat the final state)
-            if (int rc = R.save(nsteps)) return rc;
-    } else {
-        if (int rc = R.tsit5_adaptive(who, nullptr)) return rc;
-    }
-    if (part) {     // every rank returns the complete solution
-        for (int i = 0; i < d->n_saves; ++i)
-            if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
-    } else if (d->out) {
-        if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
-    }
-    std::vector<double> vpart;
-    if (e) {
-        EvalFinish f{};
-        f.acc = R.ev_acc; f.part = R.ev_part; f.N = g.N; f.O = c.O; f.n_saves = d->n_saves;
-        f.gid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
-        f.sel = sel.empty() ? nullptr : (const int64_t*)(base + o_esel);
-        f.n_val = n_val;
-        f.mse_time = e->mse_time ? (float*)(base + o_emt) : nullptr;
-        f.mse_save = e->mse_save ? (double*)(base + o_ems) : nullptr;
-        f.vpart = (double*)(base + o_evp);
-        HIPCHK(h, launch_eval_finish(f, h->stream));
-        vpart.resize((size_t)save_error_blocks(n_val));
-        HIPCHK(h, hipMemcpyAsync(vpart.data(), f.vpart, vpart.size() * 8, hipMemcpyDeviceToHost, h->stream));
-        if (e->mse_save) HIPCHK(h, hipMemcpyAsync(e->mse_save, f.mse_save, (size_t)d->n_saves * c.O * 8, hipMemcpyDeviceToHost, h->stream));
-        if (e->mse_time) HIPCHK(h, hipMemcpyAsync(e->mse_time, f.mse_time, nb, hipMemcpyDefault, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    d->n_rhs = R.n_rhs;
-    if (e) {      // the blocks' sums in block order
-        double s = 0.0;
-        for (double v : vpart) s += v;
-        e->val_loss = s / (double)n_val;
-    }
-    return MGN_OK;
-}
-
-}  // namespace
-
-int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
-    return rollout_solve(h, d, nullptr, "mgn_rollout");
-} MGN_CATCH(h)
-
-int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) try {
-    static const char* who = "mgn_rollout_eval";
-    if (!h) return MGN_E_ARG;
-    // the descriptor first (a host-only handle answers it too)
-    if (!d || !e || !e->gt) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (e->n_gt < d->n_saves) return fail(h, MGN_E_ARG, "%s: n_gt = %d ground-truth frames for n_saves = %d saves", who, e->n_gt, d->n_saves);
-    if (e->n_sel < 0 || (e->n_sel > 0 && !e->sel)) return fail(h, MGN_E_ARG, "%s: n_sel must be >= 0, and sel given when it is > 0", who);
-    if (e->sel_index_base != 0 && e->sel_index_base != 1) return fail(h, MGN_E_ARG, "%s: sel_index_base must be 0 or 1", who);
-    if (h->cfg.nranks != 1)
-        return fail(h, MGN_E_UNSUPPORTED, "%s drives one partition: on a partitioned handle call mgn_rollout and reduce the solution on the host", who);
-    if (h->have_graph) {
-        const int64_t n = (int64_t)h->g.N * h->cfg.O;
-        for (int64_t i = 0; i < e->n_sel; ++i) {
-            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;
-            if (li < 0 || li >= n)
-                return fail(h, MGN_E_ARG, "%s: sel[%lld] = %d is outside the %lld elements of the [N][O] error array (index base %d)", who,
-                            (long long)i, e->sel[i], (long long)n, e->sel_index_base);
-        }
-    }
-    e->val_loss = 0.0;
-    return rollout_solve(h, d, e, who);      // (without a graph it refuses before sel is read)
-} MGN_CATCH(h)
-
-// ---- solver-based training (SolverTraining / MultipleShooting): loss and gradient of one solved window ------------------------------
-// Forward: mgn_rollout's time loop on the resident right-hand side (the same launches, the same hipGraph replay), in the training form of
-// the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the arrays the RHS saw.
-// Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
-namespace {
-
-// the handle's state that solver-based training needs: a device handle, one partition, fp32, one edge set, parameters and a graph
-int solver_state_checks(mgn_handle* h, const char* who) {
-    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
-    const mgn_config& c = h->cfg;
-    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
-    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
-    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
-    return need(h, true, true, c.ln_dims != MGN_LN_ALL, true);
-}
-
-// the static inputs of the right-hand side
-int solver_static_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who) {
-    const mgn_config& c = h->cfg;
-    if (!d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
-    return MGN_OK;
-}
-
-// the inflow and the continuity weight
-int solver_inflow_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who, float cont_weight) {
-    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "%s: unknown inflow_rule", who);
-    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "%s: inflow mask and data go together", who);
-    if (d->inflow_data && d->n_frames < 1) return fail(h, MGN_E_ARG, "%s: inflow_data needs n_frames >= 1", who);
-    if (!std::isfinite(cont_weight)) return fail(h, MGN_E_ARG, "%s: cont_weight must be finite", who);
-    return MGN_OK;
-}
-
-// the fixed-step grid (TimeGrid::next) walked once on the host: K = round((t1 - t0) / dt) steps, and the step whose state each of the
-// n_saves saves is (every one must be reached)
-int fixed_grid(mgn_handle* h, const char* who, const TimeGrid& T, int n_saves, int64_t* K, std::vector<int64_t>& save_step) {
-    const double steps = (T.t1 - T.t0) / T.dt;
-    if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: %.3g steps", who, steps);
-    *K = (int64_t)std::llround(steps);
-    save_step.assign(1, 0);
-    double t = T.t0;
-    for (int64_t i = 0; i < *K && (int)save_step.size() < n_saves; ++i) {
-        t = T.next(i, *K, t);
-        while ((int)save_step.size() < n_saves && T.stop_time((int)save_step.size()) <= t + 0.25 * T.dt) save_step.push_back(i + 1);
-    }
-    if ((int)save_step.size() < n_saves)
-        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
-                    (int)save_step.size(), T.stop_time((int)save_step.size()), T.t1);
-    return MGN_OK;
-}
-
-// gt and cont_target (host or device, the caller's order) into the engine's order (gtl, ctl); loss_scale as given (lsd); tmp: [N][O] scratch
-int solver_targets(mgn_handle* h, mgn_rollout_desc* d, int64_t n, const float* gt, const float* cont_target, const float* loss_scale,
-                   float* gtl, float* ctl, float* lsd, float* tmp) {
-    const bool loc = h->g.renumbered;
-    const int32_t N = h->g.N;
-    const int O = h->cfg.O;
-    const size_t nb = (size_t)n * 4;
-    const int32_t* ngid = h->d_own_gid.as<int32_t>();
-    for (int s = 0; s < d->n_saves; ++s) {
-        if (!loc) {
-            HIPCHK(h, hipMemcpyAsync(gtl + (size_t)s * n, gt + (size_t)s * n, nb, hipMemcpyDefault, h->stream));
-        } else {
-            HIPCHK(h, hipMemcpyAsync(tmp, gt + (size_t)s * n, nb, hipMemcpyDefault, h->stream));
-            HIPCHK(h, launch_permute_rows(gtl + (size_t)s * n, tmp, ngid, N, O, false, h->stream));
-        }
-    }
-    if (ctl) {
-        HIPCHK(h, hipMemcpyAsync(loc ? tmp : ctl, cont_target, nb, hipMemcpyDefault, h->stream));
-        if (loc) HIPCHK(h, launch_permute_rows(ctl, tmp, ngid, N, O, false, h->stream));
-    }
-    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)O * 4, hipMemcpyDefault, h->stream));
-    return MGN_OK;
-}
-
-// mgn_solver_grad (o null: fixed-step Euler) and mgn_solver_grad_tsit5 (o: fixed steps, or adaptive), after their own checks: the time grid,
-// the forward loop keeping what the sweep needs (Euler: every step's RHS input; Tsit5: every accepted step's six stage inputs, in chunks on
-// the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves
-int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
-                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) {
-    const bool euler = !o, adaptive = o && o->adaptive != 0;
-    const TimeGrid T(d);
-    if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (!adaptive && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, euler ? "%s: Euler needs dt > 0" : "%s: fixed steps need dt > 0", who);
-    if (adaptive && !(T.dt >= 0.0)) return fail(h, MGN_E_ARG, "%s: dt must be >= 0 (0: the Hairer-Wanner start)", who);
-    if (adaptive && !(d->abstol > 0.f && d->reltol > 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
-    if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
-    if (o) {
-        o->n_steps = 0;
-        o->stored_bytes = 0;
-    }
-    int64_t K = 0;                       // fixed steps: the step count; adaptive: the accepted steps, after the solve
-    std::vector<int64_t> plan;
-    if (!adaptive) {
-        if (int rc = fixed_grid(h, who, T, d->n_saves, &K, plan)) return rc;
-    } else if (T.stop_time(d->n_saves - 1) > T.t1 + 1e-5 * T.sdt) {
-        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
-                    d->n_saves - 1, T.stop_time(d->n_saves - 1), T.t1);
-    }
-    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
-    const mgn_config& c = h->cfg;
-    const int32_t N = h->g.N;
-    const int O = c.O;
-    invalidate_static(h);
-    Rollout R(h, d, T);
-    R.train = true;
-    R.n = (int64_t)N * O;
-    R.n_global = R.n;
-    R.nrows = N;
-    const size_t nb = (size_t)R.n * 4;
-    const size_t P = h->params.size();
-    const int ablk = solver_adjoint_blocks(N, O);
-    if (euler && (size_t)(K + 1) > (SIZE_MAX / 2) / (nb > 0 ? nb : 1))
-        return fail(h, MGN_E_OOM, "%s: %lld stored states of %zu bytes overflow the address space", who, (long long)(K + 1), nb);
-    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
-    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
-    const bool zc = !euler && d->inflow_mask != nullptr;       // Tsit5's training-form copies
-    Arena a;
-    const size_t o_u = a.take(nb), o_un = a.take(euler ? 0 : nb), o_ut = a.take(nb);
-    size_t o_k[7];
-    for (int j = 0; j < 7; ++j) o_k[j] = a.take(euler && j > 0 ? 0 : nb);     // (Euler takes k[0] only)
-    const size_t o_za = a.take(zc ? nb : 0), o_zs = a.take(zc ? nb : 0), o_z7 = a.take(zc ? nb : 0);
-    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)N), o_pe = a.take(euler ? 0 : errnorm_partials() * sizeof(double));
-    R.elat0_off = a.take(eb);
-    const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb), o_tmp = a.take(nb),
-                 o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
-    const size_t o_st = a.take(euler ? (size_t)(K + 1) * nb : 0);
-    if (int rc = euler ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the %lld stored states of the solve and the call's buffers", who,
-                                        (double)a.off * 1e-9, (long long)(K + 1))
-                       : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
-        return rc;
-    char* base = h->ode.as<char>();
-    R.u = (float*)(base + o_u); R.unew = euler ? nullptr : (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
-    for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + o_k[euler ? 0 : j]);
-    if (zc) { R.za = (float*)(base + o_za); R.zs = (float*)(base + o_zs); R.z7 = (float*)(base + o_z7); }
-    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
-    R.saves = (float*)(base + o_sv);
-    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
-    R.partial = euler ? nullptr : (double*)(base + o_pe);
-    if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
-    if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
-
-    // Tsit5: the stored stage inputs, step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown
-    // geometrically (never reallocated: a stored step does not move)
-    const size_t stepb = 6 * nb;
-    const int64_t max_steps = 100000;
-    std::vector<float*> steps;
-    size_t chunk = 0, used_in_chunk = 0;
-    const Rollout::Slot slot = [&](int64_t n, float** out) -> int {
-        while ((int64_t)steps.size() <= n) {
-            if ((int64_t)steps.size() >= max_steps)
-                return fail(h, MGN_E_STATE, "%s: more than %lld accepted steps (maxiters)", who, (long long)max_steps);
-            if (o->max_store_bytes && (size_t)(steps.size() + 1) * stepb > o->max_store_bytes)
-                return fail(h, MGN_E_OOM, "%s: step %lld needs %zu bytes of stored stage inputs, beyond max_store_bytes = %zu", who,
-                            (long long)steps.size(), (size_t)(steps.size() + 1) * stepb, o->max_store_bytes);
-            DevBuf* cb = chunk < h->tsit5_store.size() ? h->tsit5_store[chunk].get() : nullptr;
-            if (cb && used_in_chunk + stepb <= cb->bytes) {
-                steps.push_back(reinterpret_cast<float*>(cb->as<char>() + used_in_chunk));
-                used_in_chunk += stepb;
-                continue;
-            }
-            if (cb && used_in_chunk > 0) { ++chunk; used_in_chunk = 0; continue; }
-            // a new chunk (or an earlier call's that holds no step of this size, regrown in place): as many steps as are stored so far (at
-            // least 8; a fixed-step solve: all it has left), within max_store_bytes
-            size_t want = (size_t)std::max<int64_t>(adaptive ? std::max<int64_t>((int64_t)steps.size(), 8) : K - (int64_t)steps.size(), 1);
-            if (o->max_store_bytes) want = std::min(want, o->max_store_bytes / stepb - steps.size());
-            if (want > (SIZE_MAX / 2) / stepb) return fail(h, MGN_E_OOM, "%s: %zu stored steps overflow the address space", who, want);
-            if (!cb) {
-                h->tsit5_store.push_back(std::make_unique<DevBuf>());
-                cb = h->tsit5_store.back().get();
-            }
-            if (int rc = ensure_or_fail(h, *cb, want * stepb, "%s: step %lld: %.3f GB more for the stored stage inputs (%.3f GB stored)", who,
-                                        (long long)steps.size(), (double)(want * stepb) * 1e-9, (double)(steps.size() * stepb) * 1e-9))
-                return rc;
-            used_in_chunk = 0;
-        }
-        *out = steps[n];
-        return MGN_OK;
-    };
-
-    d->n_accept = d->n_reject = 0;
-    float* states = (float*)(base + o_st);
-    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : R.tsit5_fixed(K, plan, slot)) return rc;
-    d->n_rhs = R.n_rhs;
-    if (!euler) {
-        K = (int64_t)R.step_h.size();
-        o->n_steps = (int32_t)K;
-        o->stored_bytes = (size_t)K * stepb;
-        for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
-            if (o->step_t) o->step_t[i] = R.step_t[i];
-            if (o->step_h) o->step_h[i] = R.step_h[i];
-        }
-    }
-
-    float* gtl = (float*)(base + o_gt);
-    float* ctl = cont_target ? (float*)(base + o_ct) : nullptr;
-    float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
-    if (int rc = solver_targets(h, d, R.n, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
-
-    SolverSweep S{};
-    S.K = K; S.states = euler ? states : nullptr; S.saves = R.saves; S.save_step = R.save_step.data(); S.n_saves = d->n_saves;
-    S.gt = gtl; S.loss_scale = lsd; S.inflow = R.mask; S.cont_target = ctl; S.cont_weight = ctl ? cont_weight : 0.f; S.dt = euler ? (float)T.dt : 0.f;
-    S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
-    S.a = (float*)(base + o_a); S.gacc = (double*)(base + o_gacc); S.part = (double*)(base + o_part);
-    S.grads = grads; S.loss = loss;
-    if (euler) {
-        if (int rc = solver_sweep(h, S)) return rc;
-    } else {
-        Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, (float*)(base + o_yb)};
-        if (int rc = tsit5_sweep(h, S, T5)) return rc;
-    }
-    if (d->out)      // the predicted saves in the caller's order
-        if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MGN_OK;
-}
-
-// the checks mgn_solver_grad and mgn_solver_grad_tsit5 share before their solver's
-int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss) {
-    if (int rc = solver_state_checks(h, who)) return rc;
-    if (!d || !gt || !grads || !loss || !d->x0) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    return solver_static_checks(h, d, who);
-}
-
-}  // namespace
-
-int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
-                    float* grads, size_t n_grads, float* loss) try {
-    static const char* who = "mgn_solver_grad";
-    if (!h) return MGN_E_ARG;
-    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
-    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
-    if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
-    return solver_grad(h, d, nullptr, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
-} MGN_CATCH(h)
-
-// Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_adaptive, Tsit5Control) or fixed steps on the Euler grid (Rollout::tsit5_fixed), in
-// the training form (za / zs / z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
-int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
-                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
-    static const char* who = "mgn_solver_grad_tsit5";
-    if (!h) return MGN_E_ARG;
-    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
-    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
-    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
-    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
-} MGN_CATCH(h)
-
-// ---- MultipleShooting as one batch (mgn_shooting_grad) ----------------------------------------------------------------------------------
-// The windows of one MultipleShooting loss are independent (each starts from gt; the continuity term couples a window to gt only), so
-// windows with the same step plan are solved together on a companion engine holding B copies of the graph: one solve of a block-diagonal
-// graph per pass instead of B launch-bound solves.  Per window the arithmetic is that of mgn_solver_grad / mgn_solver_grad_tsit5 (fixed
-// steps); the loss partials and the gradient accumulate over all passes and are finalised once.
-static void shoot_release(mgn_handle* h) {
-    if (!h) return;
-    for (auto& k : h->shoot_kids) mgn_destroy(k.e);
-    h->shoot_kids.clear();
-    h->shoot.release();
-}
-
-namespace {
-
-struct ShootGroup {
-    int64_t K = 0;
-    std::vector<int64_t> save_step;          // n_saves entries, the same for every window of the group
-    std::vector<int32_t> win;                // its windows, ascending
-    std::vector<std::vector<int32_t>> fr;    // per window: the inflow frame of every right-hand side evaluation (no inflow mask: empty)
-    size_t ftab_off = 0;                     // [n_evals][win.size()] in the int table
-    TimeGrid tg;                             // its first window's
-};
-
-// the companion for passes of B windows: B copies of h's graph in h's engine order (row w N + i = window w's engine row i), not renumbered;
-// parameters and normalisers brought up to date
-int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
-    static const char* who = "mgn_shooting_grad";
-    mgn_engine::ShootKid* kid = nullptr;
-    for (auto& k : h->shoot_kids)
-        if (k.b == B) kid = &k;
-    if (!kid) {
-        if (h->shoot_kids.size() >= 2) {     // the oldest size goes
-            mgn_destroy(h->shoot_kids.front().e);
-            h->shoot_kids.erase(h->shoot_kids.begin());
-        }
-        const LocalGraph& g = h->g;
-        const int32_t N = g.N;
-        const EdgeTopo& t = g.set[0];
-        const int64_t E = t.e_local;
-        if ((int64_t)B * N > INT32_MAX || (int64_t)B * E > INT32_MAX) return fail(h, MGN_E_ARG, "%s: %d windows of %d nodes overflow int32 node ids", who, B, N);
-        mgn_engine* c = nullptr;
-        mgn_config cfg = h->cfg;
-        if (mgn_create(&cfg, &c) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion engine: %s", who, mgn_last_error(nullptr));
-        c->companion = true;
-        std::vector<int32_t> snd((size_t)B * E), rcv((size_t)B * E);
-        for (int32_t w = 0; w < B; ++w)
-            for (int64_t j = 0; j < E; ++j) {
-                snd[(size_t)w * E + j] = w * N + t.snd[j];
-                rcv[(size_t)w * E + j] = w * N + t.rcv[j];
-            }
-        EdgeList sets[MAX_EDGE_SETS];
-        sets[0] = {(int64_t)B * E, snd.data(), rcv.data(), 0};
-        int rc = rebuild_graph(c, B * N, sets, nullptr, 0, false, who, nullptr, 0);
-        if (!rc) rc = alloc_latents(c);
-        if (rc) {
-            rc = fail(h, rc, "%s: companion graph: %s", who, c->err.c_str());
-            mgn_destroy(c);
-            return rc;
-        }
-        c->have_graph = true;
-        h->shoot_kids.push_back({B, c, 0, false});
-        kid = &h->shoot_kids.back();
-        // the copies keep h's engine order: no renumbering, edges in the replicated (receiver-sorted, stable) order
-        const LocalGraph& cg = c->g;
-        bool same = !cg.renumbered && cg.n_own == B * N && cg.set[0].e_local == (int64_t)B * E;
-        for (int32_t i = 0; same && i < cg.n_own; ++i) same = cg.own_gid[i] == i;
-        for (int64_t j = 0; same && j < cg.set[0].e_local; ++j) same = cg.set[0].edge_gid[j] == j;
-        if (!same) return fail(h, MGN_E_STATE, "%s: the companion graph does not keep the replicated order", who);
-    }
-    mgn_engine* c = kid->e;
-    if (c->stream != h->stream)
-        if (mgn_set_stream(c, (void*)h->stream) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion stream: %s", who, c->err.c_str());
-    if (!kid->params_set || kid->params_gen != h->params_gen) {      // parameters only when they changed
-        if (mgn_set_params(c, h->params.data(), h->params.size()) != MGN_OK) return fail(h, MGN_E_STATE, "%s: companion parameters: %s", who, c->err.c_str());
-        kid->params_set = true;
-        kid->params_gen = h->params_gen;
-    }
-    if (c->norms_host != h->norms_host || c->have_nnorm != h->have_nnorm || c->have_enorm != h->have_enorm || c->have_onorm != h->have_onorm) {
-        const mgn_config& k = h->cfg;
-        const float* v = h->norms_host.data();
-        const float* ne = v + 2 * k.Fn;
-        const float* no = ne + 2 * k.Fe;
-        if (mgn_set_norms(c, h->have_nnorm ? v : nullptr, h->have_nnorm ? v + k.Fn : nullptr, h->have_enorm ? ne : nullptr,
-                          h->have_enorm ? ne + k.Fe : nullptr, h->have_onorm ? no : nullptr, h->have_onorm ? no + k.O : nullptr) != MGN_OK)
-            return fail(h, MGN_E_STATE, "%s: companion normalisers: %s", who, c->err.c_str());
-        c->norms_host = h->norms_host;
-    }
-    if (int rc = need(c, true, true, true, true)) return fail(h, rc, "%s: companion: %s", who, c->err.c_str());
-    *out = c;
-    return MGN_OK;
-}
-
-// the static inputs of a companion pass: h's engine-order arrays replicated B times on the device, the edges encoded once into elat0
-int shoot_statics(mgn_engine* c, int32_t B, int32_t N, const float* oh, const float* vm, const float* ef, char* elat0, size_t eb) {
-    const mgn_config& k = c->cfg;
-    const int W1 = k.Fn - k.O, Fe = k.Fe;
-    const int64_t E = c->g.set[0].e_local / B, rows = (int64_t)B * N;
-    c->in_wa = k.O;
-    c->in_wb = W1;
-    c->in_local = true;                      // (the state slot d_nfA is never read: every right-hand side reads srcA_override)
-    HIPCHK(c, c->d_nfA.ensure(16));
-    HIPCHK(c, c->d_nfB.ensure((size_t)rows * (W1 > 0 ? W1 : 1) * 4));
-    if (W1 > 0) HIPCHK(c, launch_shoot_gather(c->d_nfB.as<float>(), oh, rows * W1, (int64_t)N * W1, 1, nullptr, nullptr, 0, c->stream));
-    c->have_mask = vm != nullptr;
-    if (vm) {
-        HIPCHK(c, c->d_mask.ensure((size_t)rows * 4));
-        HIPCHK(c, launch_shoot_gather(c->d_mask.as<float>(), vm, rows, N, 1, nullptr, nullptr, 0, c->stream));
-    }
-    HIPCHK(c, c->es[0].d_ef.ensure((size_t)B * E * Fe * 4 + 16));
-    if (E > 0) HIPCHK(c, launch_shoot_gather(c->es[0].d_ef.as<float>(), ef, (int64_t)B * E * Fe, E * Fe, 1, nullptr, nullptr, 0, c->stream));
-    if (int rc = encode_impl(c, true, false, true)) return rc;
-    HIPCHK(c, hipMemcpyAsync(elat0, c->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, c->stream));
-    return MGN_OK;
-}
-
-}  // namespace
-
-int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, const float* gt, const float* loss_scale, float cont_weight,
-                      float* grads, size_t n_grads, float* loss) try {
-    static const char* who = "mgn_shooting_grad";
-    if (!h) return MGN_E_ARG;
-    // the arguments first (a host-only handle answers them too)
-    if (!d || !s || !gt || !grads || !loss) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
-    if (d->solver == 1 && s->adaptive != 0)
-        return fail(h, MGN_E_UNSUPPORTED, "%s: adaptive Tsit5 windows need a step controller each: call mgn_solver_grad_tsit5 per window", who);
-    const int32_t W = s->n_windows;
-    if (W < 1 || !s->first || !s->last || !s->t0 || !s->t1) return fail(h, MGN_E_ARG, "%s: needs n_windows >= 1 and first / last / t0 / t1", who);
-    if (s->max_windows_per_pass < 0 || s->max_batch_nodes < 0) return fail(h, MGN_E_ARG, "%s: max_windows_per_pass and max_batch_nodes must be >= 0", who);
-    for (int32_t w = 0; w < W; ++w)
-        if (s->first[w] < 0 || s->last[w] <= s->first[w] || s->last[w] >= s->n_gt)
-            return fail(h, MGN_E_ARG, "%s: window %d = (%d, %d) must satisfy 0 <= first < last < n_gt = %d", who, w, s->first[w], s->last[w], s->n_gt);
-    s->n_groups = s->n_passes = 0;
-    if (int rc = solver_state_checks(h, who)) return rc;
-    if (int rc = solver_static_checks(h, d, who)) return rc;
-    const mgn_config& c = h->cfg;
-    const TimeGrid DG(d);                    // (its time type, dt and saves_dt; every window has its own t0 and t1)
-    if (!(DG.sdt > 0.0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (!(DG.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
-    if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
-    const bool euler = d->solver == 0, inflow = d->inflow_mask != nullptr;
-
-    // ---- plans on the host: every window walks the single-window grid; identical plans form a group
-    std::vector<ShootGroup> groups;
-    std::vector<int32_t> grp_of(W);
-    mgn_rollout_desc dw = *d;
-    for (int32_t w = 0; w < W; ++w) {
-        TimeGrid T = DG;
-        T.t0 = T.tt(s->t0[w]);
-        T.t1 = T.tt(s->t1[w]);
-        if (!(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: window %d: t1 < t0", who, w);
-        char ww[64];
-        snprintf(ww, sizeof ww, "%s: window %d", who, w);
-        int64_t K;
-        std::vector<int64_t> ss;
-        if (int rc = fixed_grid(h, ww, T, s->last[w] - s->first[w] + 1, &K, ss)) return rc;
-        std::vector<int32_t> fr;
-        if (inflow) {      // the frame of every right-hand side evaluation, in the order the solve makes them
-            const Rollout P(h, d, T);        // (its frame rule only)
-            auto push = [&](double t) -> int {
-                int64_t f;
-                if (int rc = P.frame_index(t, &f)) return rc;
-                fr.push_back((int32_t)f);
-                return MGN_OK;
-            };
-            double t = T.t0;
-            if (!euler)
-                if (int rc = push(t)) return rc;                 // k1
-            for (int64_t i = 0; i < K; ++i) {
-                const double tn = T.next(i, K, t);
-                if (euler) {
-                    if (int rc = push(t)) return rc;
-                } else {
-                    for (int sidx = 1; sidx < 6; ++sidx)
-                        if (int rc = push(T.tt(t + T.tt(TS_C[sidx] * T.dt)))) return rc;
-                    if (int rc = push(tn)) return rc;            // stage 7 = z_{n+1,1} sees t_{n+1}
-                }
-                t = tn;
-            }
-        }
-        int32_t gi = -1;
-        for (size_t q = 0; q < groups.size() && gi < 0; ++q)
-            if (groups[q].K == K && groups[q].save_step == ss) gi = (int32_t)q;
-        if (gi < 0) {
-            gi = (int32_t)groups.size();
-            groups.push_back({K, ss, {}, {}, 0, T});
-        }
-        groups[gi].win.push_back(w);
-        groups[gi].fr.push_back(std::move(fr));
-        grp_of[w] = gi;
-    }
-    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the handle's training state
-
-    // ---- passes: a group's windows in chunks of at most `cap` (sizes as even as the cap allows)
-    const LocalGraph& g = h->g;
-    const int32_t N = g.N;
-    const int O = c.O, W1 = c.Fn - c.O, Fe = c.Fe;
-    const int64_t E = g.set[0].e_local;
-    const int64_t nN = (int64_t)N * O;
-    int64_t cap = std::max<int64_t>(1, (s->max_batch_nodes > 0 ? s->max_batch_nodes : ((int64_t)1 << 20)) / std::max<int32_t>(N, 1));
-    if (s->max_windows_per_pass > 0) cap = std::min<int64_t>(cap, s->max_windows_per_pass);
-    if (c.ln_dims == MGN_LN_ALL) cap = 1;   // a whole-array LayerNorm would couple the copies
-    struct Pass { int32_t grp, j0, B; size_t idx_off, cw_off; };
-    std::vector<Pass> passes;
-    std::vector<int32_t> itab;               // int32 tables: per group the frame table, per pass x0 [B] | save targets [n_saves][B] | continuity [B]
-    std::vector<float> cwtab;
-    std::vector<int64_t> out_row(W + 1, 0);  // the first output save of every window
-    for (int32_t w = 0; w < W; ++w) out_row[w + 1] = out_row[w] + (s->last[w] - s->first[w] + 1);
-    int32_t Bmax = 1;
-    for (size_t q = 0; q < groups.size(); ++q) {
-        ShootGroup& G = groups[q];
-        const int32_t nw = (int32_t)G.win.size();
-        if (inflow) {
-            G.ftab_off = itab.size();
-            const size_t ne = G.fr[0].size();
-            for (size_t e = 0; e < ne; ++e)
-                for (int32_t j = 0; j < nw; ++j) itab.push_back(G.fr[j][e]);
-        }
-        const int32_t np = (int32_t)((nw + cap - 1) / cap);
-        for (int32_t p = 0, j0 = 0; p < np; ++p) {
-            const int32_t B = nw / np + (p < nw % np ? 1 : 0);
-            Pass ps{(int32_t)q, j0, B, itab.size(), cwtab.size()};
-            const int ns = (int)G.save_step.size();
-            for (int32_t j = 0; j < B; ++j) itab.push_back(s->first[G.win[j0 + j]]);
-            for (int sv = 0; sv < ns; ++sv)
-                for (int32_t j = 0; j < B; ++j) itab.push_back(s->first[G.win[j0 + j]] + sv);
-            for (int32_t j = 0; j < B; ++j) {
-                const int32_t w = G.win[j0 + j];
-                itab.push_back(w + 1 < W ? s->first[w + 1] : s->first[w]);
-                cwtab.push_back(w + 1 < W ? cont_weight : 0.f);
-            }
-            passes.push_back(ps);
-            Bmax = std::max(Bmax, B);
-            j0 += B;
-        }
-    }
-    s->n_groups = (int32_t)groups.size();
-    s->n_passes = (int32_t)passes.size();
-
-    // ---- the call's staging on the handle: gt (engine order), frames, masks, statics, tables, accumulators
-    const size_t P_ = h->params.size();
-    const int ld = solver_adjoint_blocks((int64_t)Bmax * N, O);
-    const bool any_batch = Bmax > 1;
-    const size_t gtb = (size_t)s->n_gt * nN * 4;
-    const size_t fb = inflow ? (size_t)d->n_frames * nN * 4 : 0;
-    Arena a;
-    const size_t o_gt = a.take(gtb), o_gtc = a.take(g.renumbered ? gtb : 0), o_fr = a.take(fb), o_mk = a.take(inflow ? (size_t)N : 0),
-                 o_oh = a.take(any_batch ? (size_t)N * W1 * 4 : 0), o_vm = a.take(any_batch && d->val_mask ? (size_t)N * 4 : 0),
-                 o_ef = a.take(any_batch ? (size_t)E * Fe * 4 : 0), o_out = a.take(d->out ? (size_t)out_row[W] * nN * 4 : 0),
-                 o_gacc = a.take(P_ * 8), o_lacc = a.take((size_t)2 * ld * 8), o_gf = a.take(P_ * 4), o_ls = a.take((size_t)O * 4),
-                 o_it = a.take(itab.size() * 4), o_cw = a.take(cwtab.size() * 4);
-    if (int rc = ensure_or_fail(h, h->shoot, a.off, "%s: %.3f GB for the call's staging", who, (double)a.off * 1e-9)) return rc;
-    hipStream_t st = h->stream;
-    char* sbase = h->shoot.as<char>();
-    float* gtl = (float*)(sbase + o_gt);
-    float* frl = inflow ? (float*)(sbase + o_fr) : nullptr;
-    uint8_t* mkl = inflow ? (uint8_t*)(sbase + o_mk) : nullptr;
-    double* gacc = (double*)(sbase + o_gacc);
-    double* lacc = (double*)(sbase + o_lacc);
-    float* lsd = loss_scale ? (float*)(sbase + o_ls) : nullptr;
-    const int32_t* itd = (const int32_t*)(sbase + o_it);
-    const float* cwd = (const float*)(sbase + o_cw);
-    const int32_t* ngid = h->d_own_gid.as<int32_t>();
-    if (!g.renumbered) {
-        HIPCHK(h, hipMemcpyAsync(gtl, gt, gtb, hipMemcpyDefault, st));
-    } else {
-        HIPCHK(h, hipMemcpyAsync(sbase + o_gtc, gt, gtb, hipMemcpyDefault, st));
-        HIPCHK(h, launch_shoot_gather(gtl, (const float*)(sbase + o_gtc), (int64_t)s->n_gt * nN, nN, s->n_gt, nullptr, ngid, O, st));
-    }
-    // host arrays (as mgn_rollout takes them) into the engine's order: frames, inflow mask, and the statics of companion passes (the node
-    // order of one partition: own_gid)
-    if (int rc = upload_engine_order(h, d, nullptr, frl, mkl)) return rc;
-    std::vector<float> hs;
-    if (any_batch) {
-        hs.resize((size_t)N * W1 + (d->val_mask ? (size_t)N : 0) + (size_t)E * Fe);
-        float* ho = hs.data();
-        float* hv = ho + (size_t)N * W1;
-        float* he = hv + (d->val_mask ? (size_t)N : 0);
-        for (int32_t i = 0; i < N; ++i) {
-            const size_t gi = (size_t)g.own_gid[i];
-            if (W1 > 0) memcpy(ho + (size_t)i * W1, d->node_type_onehot + gi * W1, (size_t)W1 * 4);
-            if (d->val_mask) hv[i] = d->val_mask[gi];
-        }
-        for (int64_t j = 0; j < E; ++j) memcpy(he + (size_t)j * Fe, d->ef_raw + (size_t)g.set[0].edge_gid[j] * Fe, (size_t)Fe * 4);
-        if (W1 > 0) HIPCHK(h, hipMemcpyAsync(sbase + o_oh, ho, (size_t)N * W1 * 4, hipMemcpyHostToDevice, st));
-        if (d->val_mask) HIPCHK(h, hipMemcpyAsync(sbase + o_vm, hv, (size_t)N * 4, hipMemcpyHostToDevice, st));
-        if (E > 0) HIPCHK(h, hipMemcpyAsync(sbase + o_ef, he, (size_t)E * Fe * 4, hipMemcpyHostToDevice, st));
-    }
-    if (!itab.empty()) HIPCHK(h, hipMemcpyAsync(sbase + o_it, itab.data(), itab.size() * 4, hipMemcpyHostToDevice, st));
-    if (!cwtab.empty()) HIPCHK(h, hipMemcpyAsync(sbase + o_cw, cwtab.data(), cwtab.size() * 4, hipMemcpyHostToDevice, st));
-    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)O * 4, hipMemcpyDefault, st));
-    HIPCHK(h, hipMemsetAsync(gacc, 0, P_ * 8, st));
-    HIPCHK(h, hipMemsetAsync(lacc, 0, (size_t)2 * ld * 8, st));
-    const std::vector<float> zero_x0((size_t)nN, 0.f);       // (the encoder's unused state slot of a one-window pass)
-
-    // ---- the passes
-    std::vector<std::unique_ptr<Rollout>> keep_alive;          // their captured right-hand sides live until the final synchronisation
-    d->n_accept = d->n_reject = d->n_rhs = 0;
-    for (const Pass& ps : passes) {
-        const ShootGroup& G = groups[ps.grp];
-        const int32_t B = ps.B;
-        const int64_t K = G.K;
-        const int ns = (int)G.save_step.size();
-        mgn_engine* e = h;
-        if (B > 1) {
-            if (int rc = shoot_companion(h, B, &e)) return rc;
-            if (int rc = solver_prepare(e, n_grads)) return fail(h, rc, "%s: companion: %s", who, e->err.c_str());
-        }
-        auto efail = [&](int rc) { return e == h ? rc : fail(h, rc, "%s: companion: %s", who, e->err.c_str()); };
-        invalidate_static(e);
-        dw.n_saves = ns;
-        keep_alive.push_back(std::make_unique<Rollout>(e, &dw, G.tg));
-        Rollout& R = *keep_alive.back();
-        R.train = true;
-        R.n = (int64_t)B * nN;
-        R.n_global = R.n;
-        R.nrows = B * N;
-        const size_t nb = (size_t)R.n * 4;
-        const size_t eb = tile_floats(e->es[0].ntiles_e, c.L) * 4;
-        const bool zc = !euler && inflow;
-        Arena ea;
-        const size_t o_u = ea.take(nb), o_un = ea.take(euler ? 0 : nb), o_ut = ea.take(nb);
-        size_t o_k[7];
-        for (int j = 0; j < 7; ++j) o_k[j] = ea.take(euler && j > 0 ? 0 : nb);
-        const size_t o_za = ea.take(zc ? nb : 0), o_zs = ea.take(zc ? nb : 0), o_z7 = ea.take(zc ? nb : 0);
-        const size_t o_sv = ea.take((size_t)ns * nb), o_el = ea.take(eb), o_tg = ea.take((size_t)ns * nb), o_ct = ea.take(nb), o_a = ea.take(nb),
-                     o_yb = ea.take(euler ? 0 : 5 * nb), o_mr = ea.take(inflow && B > 1 ? (size_t)B * N : 0);
-        if ((size_t)(K + 1) > (SIZE_MAX / 8) / (nb > 0 ? nb : 1)) return fail(h, MGN_E_OOM, "%s: %lld stored steps overflow the address space", who, (long long)K);
-        const size_t o_st = ea.take((size_t)(euler ? K + 1 : 6 * K) * nb);
-        if (int rc = ensure_or_fail(h, e->ode, ea.off, "%s: %.3f GB for a pass of %d windows (stored states and buffers)", who, (double)ea.off * 1e-9, B))
-            return rc;
-        char* base = e->ode.as<char>();
-        R.u = (float*)(base + o_u); R.unew = euler ? nullptr : (float*)(base + o_un); R.utmp = (float*)(base + o_ut);
-        for (int j = 0; j < 7; ++j) R.k[j] = (float*)(base + (euler ? o_k[0] : o_k[j]));
-        if (zc) { R.za = (float*)(base + o_za); R.zs = (float*)(base + o_zs); R.z7 = (float*)(base + o_z7); }
-        R.frames = frl;
-        R.mask = mkl;
-        R.ftab = inflow ? itd + G.ftab_off + ps.j0 : nullptr;
-        R.ftab_ld = (int64_t)G.win.size();
-        R.win_rows = N;
-        R.saves = (float*)(base + o_sv);
-        R.partial = nullptr;
-        R.elat0_off = o_el;
-        uint8_t* mrep = inflow ? (B > 1 ? (uint8_t*)(base + o_mr) : mkl) : nullptr;
-        float* store = (float*)(base + o_st);
-        if (e == h) {
-            if (int rc = upload_statics(h, d, zero_x0.data(), base + o_el, eb)) return rc;
-        } else {
-            if (int rc = shoot_statics(e, B, N, (const float*)(sbase + o_oh), d->val_mask ? (const float*)(sbase + o_vm) : nullptr,
-                                       (const float*)(sbase + o_ef), base + o_el, eb)) return efail(rc);
-            if (inflow) HIPCHK(h, launch_shoot_gather_u8(mrep, mkl, (int64_t)B * N, N, st));
-        }
-        const int32_t* ix = itd + ps.idx_off;
-        HIPCHK(h, launch_shoot_gather(R.u, gtl, R.n, nN, 0, ix, nullptr, 0, st));     // x0 = gt[first[w]]
-
-        // forward: the single-window loops, save points from the group's plan; Tsit5 keeps step i's stage inputs contiguously at steps[i]
-        std::vector<float*> steps;
-        for (int64_t i = 0; !euler && i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
-        const Rollout::Slot slot = [&](int64_t i, float** out) { *out = steps[i]; return MGN_OK; };
-        if (int rc = euler ? R.euler_train(K, G.save_step, store) : R.tsit5_fixed(K, G.save_step, slot)) return efail(rc);
-        if (R.saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", who, R.saved, ns);
-        d->n_accept += (int32_t)(K * B);
-        d->n_rhs += R.n_rhs * B;
-
-        // targets of the pass, gathered out of gt on the device
-        float* tg = (float*)(base + o_tg);
-        float* ctt = (float*)(base + o_ct);
-        bool has_ct = false;
-        for (int32_t j = 0; j < B; ++j) has_ct = has_ct || G.win[ps.j0 + j] + 1 < W;
-        HIPCHK(h, launch_shoot_gather(tg, gtl, (int64_t)ns * R.n, nN, 0, ix + B, nullptr, 0, st));
-        if (has_ct) HIPCHK(h, launch_shoot_gather(ctt, gtl, R.n, nN, 0, ix + B + (size_t)ns * B, nullptr, 0, st));
-
-        SolverSweep S{};
-        S.K = K; S.states = euler ? store : nullptr; S.saves = R.saves; S.save_step = G.save_step.data(); S.n_saves = ns;
-        S.gt = tg; S.loss_scale = lsd; S.inflow = mrep; S.cont_target = has_ct ? ctt : nullptr; S.cont_weight = 0.f; S.dt = euler ? (float)DG.dt : 0.f;
-        if (e == h) {
-            S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
-        } else {
-            S.onehot = W1 > 0 ? e->d_nfB.as<float>() : nullptr; S.ef_raw = e->es[0].d_ef.as<float>(); S.val_mask = d->val_mask ? e->d_mask.as<float>() : nullptr;
-        }
-        S.a = (float*)(base + o_a); S.gacc = gacc; S.part = nullptr; S.grads = nullptr; S.loss = nullptr;
-        S.cw_win = cwd + ps.cw_off; S.win_rows = N; S.lacc = lacc; S.lacc_ld = ld; S.lscale = 1.0 / ((double)ns * (double)nN);
-        if (euler) {
-            if (int rc = solver_sweep(e, S)) return efail(rc);
-        } else {
-            Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, (float*)(base + o_yb)};
-            if (int rc = tsit5_sweep(e, S, T5)) return efail(rc);
-        }
-        if (d->out) {       // the predicted saves in window order
-            float* oall = (float*)(sbase + o_out);
-            for (int sv = 0; sv < ns; ++sv)
-                for (int32_t j = 0; j < B; ++j)
-                    HIPCHK(h, hipMemcpyAsync(oall + (size_t)(out_row[G.win[ps.j0 + j]] + sv) * nN, R.saves + (size_t)sv * R.n + (size_t)j * nN,
-                                             (size_t)nN * 4, hipMemcpyDeviceToDevice, st));
-        }
-    }
-
-    // ---- results: the gradient finalised once, the loss partials added in a fixed order, one synchronisation
-    float* gf = (float*)(sbase + o_gf);
-    HIPCHK(h, launch_grad_finish(gacc, gf, (int64_t)P_, st));
-    HIPCHK(h, hipMemcpyAsync(grads, gf, P_ * 4, hipMemcpyDefault, st));
-    std::vector<double> lp((size_t)2 * ld);
-    HIPCHK(h, hipMemcpyAsync(lp.data(), lacc, lp.size() * 8, hipMemcpyDeviceToHost, st));
-    if (d->out)
-        if (int rc = saves_to_caller(h, (const float*)(sbase + o_out), out_row[W], d->out)) return rc;
-    HIPCHK(h, hipStreamSynchronize(st));
-    double se = 0.0, sa = 0.0;
-    for (int b = 0; b < ld; ++b) { se += lp[b]; sa += lp[(size_t)ld + b]; }
-    *loss = (float)(se + sa);
-    return MGN_OK;
-} MGN_CATCH(h)
-
 // ---- latents -------------------------------------------------------------------------------------
 // Host boundary of the latents: the caller's arrays travel over PCIe as they are (one contiguous copy each) and
 // the gather into engine order / tile-major storage runs on the device.
@@ -3102,7 +1806,7 @@ int mgn_latents_checksum(mgn_handle* h, double* sv, double* se, double* qv, doub
         if ((expr) != 0) return fail(h, MGN_E_RCCL, "%s: %s", #expr, (h)->comm ? (h)->comm->err.c_str() : "no communicator"); \
     } while (0)
 
-static int need_comm(mgn_handle* h, const char* who) {
+extern "C++" int mgn::need_comm(mgn_handle* h, const char* who) {
     if (!h->comm) return fail(h, MGN_E_RCCL, "%s with nranks = %d needs a communicator: call mgn_comm_init on every rank first", who, h->cfg.nranks);
     return MGN_OK;
 }
@@ -3196,7 +1900,7 @@ static int gather_plan(mgn_handle* h) {
 }
 
 // local_dev [n_own][W] of every rank -> out [N][W] on the host, complete on every rank
-static int gather_rows_global(mgn_handle* h, const float* local_dev, int W, float* out) {
+extern "C++" int mgn::gather_rows_global(mgn_handle* h, const float* local_dev, int W, float* out) {
     if (int rc = gather_plan(h)) return rc;
     const LocalGraph& g = h->g;
     const int P = h->cfg.nranks;

@@ -1,0 +1,1325 @@
+// The ODE solve drivers behind the C ABI (include/mgn_hip.h): mgn_rollout and mgn_rollout_eval (rollout_solve), mgn_solver_grad and
+// mgn_solver_grad_tsit5 (solver_grad), mgn_shooting_grad and its companion engines.  Host orchestration only: the time loops, their
+// workspaces and the hipGraph replay of the right-hand side, whose launches are mgn_api.cpp's (encode_impl, run_processor, decode_impl);
+// the reverse sweeps are mgn_train.cpp's.
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+
+#include "engine_internal.h"
+
+using namespace mgn;
+
+namespace {
+
+// Tsitouras 5(4) tableau (the method OrdinaryDiffEq.jl calls Tsit5)
+const double TS_C[7] = {0.0, 0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0};
+const double TS_A[7][6] = {
+    {0, 0, 0, 0, 0, 0},
+    {0.161, 0, 0, 0, 0, 0},
+    {-0.008480655492356989, 0.335480655492357, 0, 0, 0, 0},
+    {2.8971530571054935, -6.359448489975075, 4.3622954328695815, 0, 0, 0},
+    {5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525, 0, 0},
+    {5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383, 0},
+    {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774}};
+const double TS_BT[7] = {-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629,
+                         0.5823571654525552, -0.45808210592918697, 0.015151515151515152};
+
+}  // namespace
+
+double mgn::tsit5_a(int i, int j) { return TS_A[i - 1][j - 1]; }
+
+namespace {
+
+// mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
+// of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
+struct Tsit5Control {
+    static constexpr double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
+    double qold = 1e-4;
+    bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
+        const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
+        if (EEst <= 1.0) {
+            double q = q11 / std::pow(qold, beta2);
+            q = std::max(1.0 / qmax, std::min(1.0 / qmin, q / gamma));
+            qold = std::max(EEst, 1e-4);
+            if (!hit_stop || hstep >= dt * (1 - 1e-9)) dt = hstep / q;
+            else dt = std::max(dt, hstep / q);
+            return true;
+        }
+        dt = hstep / std::min(1.0 / qmin, q11 / gamma);
+        return false;
+    }
+};
+
+// The time grid of a solve.  The solver's time type (mgn_rollout_desc.time_f64): Float32 times are held in doubles and rounded after
+// every operation (a double operation on two floats, rounded to float, IS the float operation).
+struct TimeGrid {
+    bool f64 = false;
+    double t0 = 0.0, t1 = 0.0, dt = 0.0, sdt = 0.0;     // sdt: saves_dt
+    explicit TimeGrid(const mgn_rollout_desc* d)
+        : f64(d->time_f64 != 0), t0(f64 ? d->t0_f64 : (double)d->t0), t1(f64 ? d->t1_f64 : (double)d->t1),
+          dt(f64 ? d->dt_f64 : (double)d->dt), sdt(f64 ? d->saves_dt_f64 : (double)d->saves_dt) {}
+    double tt(double v) const { return f64 ? v : (double)(float)v; }
+    // the time of save point i
+    double stop_time(int i) const { return tt(t0 + (double)i * sdt); }
+    // the fixed-step grid: the time after step i of K is the integrator's own t <- t + dt in its time type, step after step (a fixed-step
+    // solve has no stops to snap to but the end of the interval); t0 + (i + 1) dt would floor differently at frame boundaries
+    double next(int64_t i, int64_t K, double t) const { return (i + 1 == K && std::fabs(tt(t + dt) - t1) <= 1e-5 * sdt) ? t1 : tt(t + dt); }
+};
+
+// one call's buffers carved out of one DevBuf: 256-byte aligned offsets, then one ensure of `off` bytes
+struct Arena {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+};
+
+// the state and stage arrays of a solve, nb bytes each, as offsets into the call's arena.  one_k: fixed-step Euler in the training form, which
+// takes k[0] only and no unew (Rollout::bind points k[1 .. 6] at k[0]); zc: Tsit5's training-form copies za / zs / z7 exist
+struct SolveWs { size_t u, un, ut, k[7], za, zs, z7; bool one_k, zc; };
+SolveWs carve_solve(Arena& a, size_t nb, bool one_k, bool zc) {
+    SolveWs w{};
+    w.one_k = one_k; w.zc = zc;
+    w.u = a.take(nb); w.un = a.take(one_k ? 0 : nb); w.ut = a.take(nb);
+    for (int j = 0; j < 7; ++j) w.k[j] = a.take(one_k && j > 0 ? 0 : nb);
+    w.za = a.take(zc ? nb : 0); w.zs = a.take(zc ? nb : 0); w.z7 = a.take(zc ? nb : 0);
+    return w;
+}
+
+struct Rollout {
+    mgn_engine* h;
+    mgn_rollout_desc* d;
+    TimeGrid tg;
+    int64_t n;                 // rows * O of the state this handle integrates (all N rows, or the owned rows of a partition)
+    int64_t n_global = 0;      // N * O
+    int32_t nrows = 0;
+    float *u, *unew, *utmp, *k[7], *frames, *saves;
+    uint8_t* mask;
+    double* partial;
+    int n_rhs = 0;
+    // rows: the rows of the state this handle integrates (all N, or the owned rows of a partition; B N for a pass of B windows)
+    Rollout(mgn_engine* h_, mgn_rollout_desc* d_, const TimeGrid& g, bool train_ = false, int32_t rows = 0, int32_t rows_global = 0)
+        : h(h_), d(d_), tg(g), n((int64_t)rows * h_->cfg.O), n_global((int64_t)rows_global * h_->cfg.O), nrows(rows) { train = train_; }
+    // the solve workspace (carve_solve) at base
+    void bind(char* base, const SolveWs& w) {
+        u = (float*)(base + w.u); unew = w.one_k ? nullptr : (float*)(base + w.un); utmp = (float*)(base + w.ut);
+        for (int j = 0; j < 7; ++j) k[j] = (float*)(base + w.k[w.one_k ? 0 : j]);
+        if (w.zc) { za = (float*)(base + w.za); zs = (float*)(base + w.zs); z7 = (float*)(base + w.z7); }
+    }
+    double tt(double v) const { return tg.tt(v); }
+
+    // One right-hand side is ~35 launches; on a small mesh they are latency-bound, so each distinct (x, kout) pair of the
+    // solver (1 for Euler, 7 for Tsit5) gets its launch sequence captured once and replayed (hipGraph).
+    struct RhsGraph { float* x; float* kout; hipGraphExec_t exec; };
+    std::vector<RhsGraph> graphs;
+    bool warmed = false;
+
+    bool lnall_edges_done = false;
+    int rhs_launches(float* x, float* kout) {
+        const mgn_config& c = h->cfg;
+        if (c.ln_dims == MGN_LN_ALL) {     // the unfused whole-array right-hand side (mgn_train.cpp); its first evaluation encodes the edges
+            const int rc = lnall_rhs_dev(h, x, kout, lnall_edges_done);
+            lnall_edges_done = true;
+            return rc;
+        }
+        h->srcA_override = x;
+        h->out_override = kout;
+        int rc = encode_impl(h, true, true, false);
+        if (!rc) {
+            // encoded edge latents are identical for every RHS of a trajectory (static edge features, frozen e_norm)
+            const bool bf = c.dtype == MGN_BF16;
+            const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * (bf ? 2 : 4);
+            if (elat_src_ok(h)) {
+                h->elat_src_override = reinterpret_cast<const float*>(h->ode.as<char>() + elat0_off);
+            } else {
+                hipError_t e = hipMemcpyAsync(bf ? h->es[0].bElat.p : h->es[0].Elat.p, h->ode.as<char>() + elat0_off, eb, hipMemcpyDeviceToDevice, h->stream);
+                if (e != hipSuccess) rc = fail(h, MGN_E_HIP, "rollout: Elat restore failed: %s", hipGetErrorString(e));
+            }
+        }
+        if (!rc) rc = run_processor(h, c.mps);
+        h->elat_src_override = nullptr;
+        if (!rc) rc = decode_impl(h, true);
+        h->srcA_override = nullptr;
+        h->out_override = nullptr;
+        return rc;
+    }
+
+    // data[field][:, :, floor(Int, t / saves_dt) + 1] (reference src/solve.jl:151): the quotient in the solver's own time type,
+    // no tolerance -- a t that sits an ulp below a frame boundary re-uses the previous frame there too -- and an index outside
+    // the data is the reference's BoundsError.  MGN_INFLOW_TOLERANT: nearest-below with a guard of 1e-3 frames (a Float32 time drifts by ~1e-4 frames), clamped.
+    int frame_index(double t, int64_t* out) const {
+        int64_t fr;
+        if (d->inflow_rule == MGN_INFLOW_TOLERANT) {
+            fr = (int64_t)std::floor(t / tg.sdt + 1e-3);
+            if (fr < 0) fr = 0;
+            if (fr >= d->n_frames) fr = d->n_frames - 1;
+        } else {
+            fr = (int64_t)std::floor(tt(t / tg.sdt));
+            if (fr < 0 || fr >= d->n_frames)
+                return fail(h, MGN_E_ARG, "mgn_rollout: inflow frame %lld at t = %.9g is outside the %d frames given (reference: BoundsError)",
+                            (long long)fr, t, d->n_frames);
+        }
+        *out = fr;
+        return MGN_OK;
+    }
+
+    // mgn_shooting_grad: the state holds windows of win_rows rows whose frames were chosen on the host, RHS evaluation e of the solve
+    // reading ftab[e * ftab_ld + window] (frames [n_frames][win_rows][O], mask [win_rows])
+    const int32_t* ftab = nullptr;
+    int64_t ftab_ld = 0, win_rows = 0;
+
+    // f(x, t): in-place inflow overwrite of x, then dx/dt -> kout    (ode_func_eval, reference src/solve.jl:147-158)
+    int rhs(float* x, double t, float* kout) {
+        const mgn_config& c = h->cfg;
+        if (mask && frames && ftab) {
+            HIPCHK(h, launch_shoot_overwrite(x, frames, mask, ftab + (size_t)n_rhs * ftab_ld, win_rows, c.O, nrows, h->stream));
+        } else if (mask && frames) {
+            int64_t fr;
+            if (int rc = frame_index(t, &fr)) return rc;
+            HIPCHK(h, launch_overwrite(x, frames + (size_t)fr * n, mask, nrows, c.O, h->stream));
+        }
+        ++n_rhs;
+        const bool graphable = h->use_graph && !h->prof && h->stream != nullptr && h->cfg.nranks == 1 && launch_is_small(h->ntiles_n);
+        if (!graphable || !warmed) {       // the first RHS runs eagerly: it sets the per-kernel attributes outside of any capture
+            warmed = true;
+            return rhs_launches(x, kout);
+        }
+        for (const RhsGraph& g : graphs)
+            if (g.x == x && g.kout == kout) {
+                HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
+                return MGN_OK;
+            }
+        hipGraph_t graph = nullptr;
+        if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+            (void)hipGetLastError();
+            h->use_graph = 0;
+            return rhs_launches(x, kout);
+        }
+        const int rc = rhs_launches(x, kout);
+        const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
+        hipGraphExec_t exec = nullptr;
+        if (rc != MGN_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+            if (graph) (void)hipGraphDestroy(graph);
+            h->use_graph = 0;              // eager from here on
+            if (rc != MGN_OK) return rc;
+            return rhs_launches(x, kout);
+        }
+        (void)hipGraphDestroy(graph);
+        graphs.push_back({x, kout, exec});
+        HIPCHK(h, hipGraphLaunch(exec, h->stream));
+        return MGN_OK;
+    }
+    ~Rollout() {
+        for (RhsGraph& g : graphs) (void)hipGraphExecDestroy(g.exec);
+    }
+    size_t elat0_off = 0;
+
+    int norm(const float* a, const float* b, const LinComb& lc, float dt, double* out) {
+        const int np_ = errnorm_partials();
+        HIPCHK(h, launch_errnorm(a, b, lc, dt, d->abstol, d->reltol, n, partial, h->stream));
+        std::vector<double> r(np_);
+        HIPCHK(h, hipMemcpyAsync(r.data(), partial, np_ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        double s = 0;
+        for (double v : r) s += v;
+        if (h->cfg.nranks != 1) {      // the same bits on every rank -> the same accept / reject decisions
+            if (h->comm->allreduce_f64(&s, 1, 0, h->stream) != 0) return fail(h, MGN_E_RCCL, "rollout: error-norm reduction failed: %s", h->comm->err.c_str());
+        }
+        const int64_t ng = n_global > 0 ? n_global : n;
+        *out = std::sqrt(s / (double)(ng > 0 ? ng : 1));
+        return MGN_OK;
+    }
+
+    // ---- saves ----
+    int saved = 0;                         // saves taken
+    std::vector<int64_t> save_step;        // the accepted steps before each save taken
+    // mgn_rollout_eval: every save is compared with its ground-truth frame as it is produced (k_save_error) -- gt [n_saves][n] in the
+    // engine's order, acc [n] doubles, part [n_saves][save_error_blocks(nrows)][O] -- and kept only if the caller wants the solution
+    const float* ev_gt = nullptr;
+    double *ev_acc = nullptr, *ev_part = nullptr;
+    // saves[saved] <- u, the state after steps_done accepted steps
+    int save(int64_t steps_done) {
+        save_step.push_back(steps_done);
+        if (ev_gt)
+            HIPCHK(h, launch_save_error(u, ev_gt + (size_t)saved * n, ev_acc, ev_part + (size_t)saved * save_error_blocks(nrows) * h->cfg.O, nrows,
+                                        h->cfg.O, h->stream));
+        if (saves) HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        ++saved;
+        return MGN_OK;
+    }
+    // the saves a fixed-step plan (the accepted steps before every save, fixed_grid) takes after steps_done steps
+    int saves_after(const std::vector<int64_t>& plan, int64_t steps_done) {
+        while (saved < (int)plan.size() && plan[saved] == steps_done)
+            if (int rc = save(steps_done)) return rc;
+        return MGN_OK;
+    }
+
+    // Training form (solver-based training, ode_func_train): the right-hand side sees a COPY of its input with the inflow rows written --
+    // utmp for Euler; za for Tsit5 stage 1 (z_{n,1}), zs for stages 2 .. 6, z7 for stage 7 (z_{n+1,1}) -- and the state is never
+    // overwritten.  mgn_rollout (train = false), or no inflow mask: the input itself (mgn_rollout overwrites it in place).
+    bool train = false;
+    float *za = nullptr, *zs = nullptr, *z7 = nullptr;
+    float* kept = nullptr;     // training form: the current Tsit5 trial's six stage inputs [6][n] (z_{n,1}, stages 2 .. 6), or null
+
+    // the array the right-hand side of input y sees (z: its training-form copy)
+    float* rhs_input(float* y, float* z) const { return (train && mask) ? z : y; }
+    int eval(float* y, float* z, double t, float* kout) {
+        float* x = rhs_input(y, z);
+        if (x != y) HIPCHK(h, hipMemcpyAsync(x, y, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return rhs(x, t, kout);
+    }
+
+    // ---- fixed-step Euler, training form: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k -> store[k] and x_K -> store[K]; saves from the plan ----
+    int euler_train(int64_t K, const std::vector<int64_t>& plan, float* store) {
+        double t = tg.t0;
+        if (int rc = saves_after(plan, 0)) return rc;
+        for (int64_t i = 0; i < K; ++i) {
+            float* xin = rhs_input(u, utmp);
+            if (int rc = eval(u, utmp, t, k[0])) return rc;
+            HIPCHK(h, hipMemcpyAsync(store + (size_t)i * n, xin, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+            LinComb lc{1, {1.f}, {k[0]}};
+            HIPCHK(h, launch_lincomb(u, u, lc, (float)tg.dt, n, h->stream));
+            t = tg.next(i, K, t);
+            ++d->n_accept;
+            if (int rc = saves_after(plan, i + 1)) return rc;
+        }
+        HIPCHK(h, hipMemcpyAsync(store + (size_t)K * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    }
+
+    // ---- fixed-step Euler as mgn_rollout runs it: the inflow rows written into the state itself, a save on every save point reached ----
+    int euler_rollout() {
+        if (int rc = save(0)) return rc;   // solution at t0
+        double t = tg.t0;
+        const int64_t nsteps = (int64_t)std::llround((tg.t1 - tg.t0) / tg.dt);
+        for (int64_t i = 0; i < nsteps; ++i) {
+            if (int rc = rhs(u, t, k[0])) return rc;
+            LinComb lc{1, {1.f}, {k[0]}};
+            HIPCHK(h, launch_lincomb(u, u, lc, (float)tg.dt, n, h->stream));
+            t = tg.next(i, nsteps, t);
+            ++d->n_accept;
+            // saveat: the state of the step that ends at the save point.  In its own time type the integrator's t drifts off the
+            // save grid by a few ulps per step (Float32: ~1e-6 s after 600 steps of 0.01 s); the reference interpolates there, which
+            // moves the saved state by (drift / dt) of one step's change -- far below the rollout tolerance -- so: the nearest step.
+            while (saved < d->n_saves && tg.stop_time(saved) <= t + 0.25 * tg.dt)
+                if (int rc = save(i + 1)) return rc;
+        }
+        while (saved < d->n_saves)      // (t1 short of the last stop: repeat the final state)
+            if (int rc = save(nsteps)) return rc;
+        return MGN_OK;
+    }
+
+    // ---- Tsit5, shared by mgn_rollout, mgn_solver_grad_tsit5 and mgn_shooting_grad ----
+    // k1 = f(u) at t (FSAL afterwards)
+    int tsit5_first(double t) { return eval(u, za, t, k[0]); }
+    // Hairer-Wanner starting step from (u, k1)
+    int tsit5_h0(double t, double* dt) {
+        double d0, d1, d2;
+        LinComb l1{1, {1.f}, {k[0]}};
+        // d0 = ||u||, d1 = ||f0|| in the scaled norm: errnorm(dt = 1) of u and k1 themselves
+        LinComb lu{1, {1.f}, {u}};
+        if (int rc = norm(u, u, lu, 1.f, &d0)) return rc;
+        if (int rc = norm(u, u, l1, 1.f, &d1)) return rc;
+        const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+        HIPCHK(h, launch_lincomb(utmp, u, l1, (float)h0, n, h->stream));
+        if (int rc = eval(utmp, zs, tt(t + h0), k[1])) return rc;
+        LinComb ld{2, {1.f, -1.f}, {k[1], k[0]}};
+        if (int rc = norm(u, u, ld, (float)(1.0 / h0), &d2)) return rc;
+        const double mx = d1 > d2 ? d1 : d2;
+        const double h1 = mx <= 1e-15 ? (h0 * 1e-3 > 1e-6 ? h0 * 1e-3 : 1e-6) : std::pow(0.01 / mx, 1.0 / 5);
+        *dt = 100 * h0 < h1 ? 100 * h0 : h1;
+        return MGN_OK;
+    }
+    // one trial step from (u, k1) over hstep: stages 2 .. 6 at tt(t + tt(c_i hstep)), unew = u + hstep sum_j A[7][j] k_j, and k7 = f(unew)
+    // at t7 (FSAL); EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H
+    int tsit5_trial(double t, double hstep, double t7, double* EEst) {
+        for (int sidx = 1; sidx < 7; ++sidx) {     // stages 2..7; stage 7 is evaluated on unew (FSAL)
+            LinComb lc{sidx, {}, {}};
+            for (int j = 0; j < sidx; ++j) { lc.c[j] = (float)TS_A[sidx][j]; lc.k[j] = k[j]; }
+            float* dst = (sidx == 6) ? unew : utmp;
+            HIPCHK(h, launch_lincomb(dst, u, lc, (float)hstep, n, h->stream));
+            float* z = (sidx == 6) ? z7 : zs;
+            if (int rc = eval(dst, z, sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep)), k[sidx])) return rc;
+            if (sidx < 6 && kept)
+                HIPCHK(h, hipMemcpyAsync(kept + (size_t)sidx * n, rhs_input(dst, z), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        }
+        if (!EEst) return MGN_OK;
+        LinComb le{7, {}, {}};
+        for (int j = 0; j < 7; ++j) { le.c[j] = (float)TS_BT[j]; le.k[j] = k[j]; }
+        return norm(u, unew, le, (float)hstep, EEst);
+    }
+    // the accepted trial becomes the state: unew -> u, k7 -> k1 (FSAL), z_{n+1,1} -> za
+    void tsit5_advance() {
+        std::swap(u, unew);
+        std::swap(k[0], k[6]);
+        std::swap(za, z7);
+    }
+
+    // training form: slot(n, &p) gives accepted step n's storage for its six stage inputs
+    using Slot = std::function<int(int64_t, float**)>;
+    std::vector<double> step_t, step_h;    // training form: every accepted step's t and h
+    // before a trial of step n: its storage, and z_{n,1} (what k1's right-hand side saw) into it
+    int begin_trial(const Slot& slot, int64_t n_) {
+        if (int rc = slot(n_, &kept)) return rc;
+        HIPCHK(h, hipMemcpyAsync(kept, rhs_input(u, za), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return MGN_OK;
+    }
+
+    // fixed-step Tsit5 in the training form: K steps of dt on the fixed grid, stage 7 at t_{n+1}; saves from the plan
+    int tsit5_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot& slot) {
+        double t = tg.t0;
+        if (int rc = saves_after(plan, 0)) return rc;
+        if (int rc = tsit5_first(t)) return rc;
+        for (int64_t i = 0; i < K; ++i) {
+            const double tn = tg.next(i, K, t);
+            if (int rc = begin_trial(slot, i)) return rc;
+            if (int rc = tsit5_trial(t, tg.dt, tn, nullptr)) return rc;
+            tsit5_advance();
+            step_t.push_back(t); step_h.push_back(tg.dt);
+            t = tn;
+            ++d->n_accept;
+            if (int rc = saves_after(plan, i + 1)) return rc;
+        }
+        kept = nullptr;
+        return MGN_OK;
+    }
+
+    // adaptive Tsit5 from t0 to t1: mgn_rollout's PI controller (Tsit5Control), tstops = saves, a save on every stop it hits, missing saves
+    // (t1 short of the last stop) padded with the final state.  mgn_rollout (no slot): stage 7 at c7 h, and the iteration guard stops
+    // silently.  Training form (slot): every trial's stage inputs kept in slot(n), stage 7 is z_{n+1,1} and sees t_{n+1}, the accepted
+    // steps recorded, and the guard fails the call.
+    int tsit5_adaptive(const char* who, const Slot* slot) {
+        const int ns = d->n_saves;
+        double t = tg.t0;
+        if (int rc = save(0)) return rc;
+        if (int rc = tsit5_first(t)) return rc;     // k1 (FSAL afterwards)
+        double dt = tg.dt;
+        if (dt <= 0)   // Hairer-Wanner starting step
+            if (int rc = tsit5_h0(t, &dt)) return rc;
+        Tsit5Control ctl;
+        int64_t guard = 0, nacc = 0;
+        // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save periods is not worth a step
+        while (t < tg.t1 - 1e-5 * tg.sdt) {
+            if (++guard >= 10000000) {
+                if (!slot) break;
+                return fail(h, MGN_E_STATE, "%s: %lld trial steps without reaching t1", who, (long long)guard);
+            }
+            double tstop = saved < ns ? tg.stop_time(saved) : tg.t1;
+            if (tstop > tg.t1) tstop = tg.t1;
+            bool hit_stop = false;
+            double hstep = dt;
+            if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
+            const double tn = hit_stop ? tstop : tt(t + hstep);
+            // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
+            const double t7 = (slot || hit_stop) ? tn : tt(t + tt(TS_C[6] * hstep));
+            if (slot)
+                if (int rc = begin_trial(*slot, nacc)) return rc;
+            double EEst;
+            if (int rc = tsit5_trial(t, hstep, t7, &EEst)) return rc;
+            if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
+            if (ctl.decide(EEst, hstep, hit_stop, dt)) {
+                tsit5_advance();
+                if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
+                t = tn;
+                ++nacc;
+                ++d->n_accept;
+                if (hit_stop && saved < ns && std::fabs(tg.stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12)
+                    if (int rc = save(nacc)) return rc;
+            } else {
+                ++d->n_reject;
+            }
+        }
+        kept = nullptr;
+        while (saved < ns)
+            if (int rc = save(nacc)) return rc;
+        return MGN_OK;
+    }
+};
+// b.ensure(bytes), or MGN_E_OOM (MGN_E_HIP for any other error) with the message "<what>: <the HIP error>"
+__attribute__((format(printf, 4, 5))) int ensure_or_fail(mgn_handle* h, DevBuf& b, size_t bytes, const char* what, ...) {
+    const hipError_t e = b.ensure(bytes);
+    if (e == hipSuccess) return MGN_OK;
+    (void)hipGetLastError();
+    char msg[400];
+    va_list ap;
+    va_start(ap, what);
+    vsnprintf(msg, sizeof msg, what, ap);
+    va_end(ap);
+    return fail(h, e == hipErrorOutOfMemory ? MGN_E_OOM : MGN_E_HIP, "%s: %s", msg, hipGetErrorString(e));
+}
+
+// x0 (u null: not wanted), the inflow frames and the inflow mask (null: none) of the caller's order into the engine's order on the device:
+// the rows this handle owns (all N, or a partition's), renumbered or not.  A reordered copy is staged on the host and synchronised.
+int upload_engine_order(mgn_handle* h, const mgn_rollout_desc* d, float* u, float* frames, uint8_t* mask) {
+    const LocalGraph& g = h->g;
+    const int O = h->cfg.O;
+    const bool part = h->cfg.nranks != 1;
+    const int32_t nloc = part ? g.n_own : g.N;
+    const int nf = frames ? d->n_frames : 0;
+    const size_t nb = (size_t)nloc * O * 4, fb = (size_t)nf * nb;
+    if (!part && !g.renumbered) {
+        if (u) HIPCHK(h, hipMemcpyAsync(u, d->x0, nb, hipMemcpyHostToDevice, h->stream));
+        if (frames) HIPCHK(h, hipMemcpyAsync(frames, d->inflow_data, fb, hipMemcpyHostToDevice, h->stream));
+        if (mask) HIPCHK(h, hipMemcpyAsync(mask, d->inflow_mask, (size_t)nloc, hipMemcpyHostToDevice, h->stream));
+        return MGN_OK;
+    }
+    std::vector<float> lx((size_t)nloc * O * (1 + nf));
+    std::vector<uint8_t> lm(mask ? (size_t)nloc : 0);
+    for (int32_t i = 0; i < nloc; ++i) {
+        const size_t gi = (size_t)g.own_gid[i];
+        if (u) memcpy(lx.data() + (size_t)i * O, d->x0 + gi * O, (size_t)O * 4);
+        for (int f = 0; f < nf; ++f)
+            memcpy(lx.data() + ((size_t)(1 + f) * nloc + i) * O, d->inflow_data + ((size_t)f * g.N + gi) * O, (size_t)O * 4);
+        if (mask) lm[i] = d->inflow_mask[gi];
+    }
+    if (u) HIPCHK(h, hipMemcpyAsync(u, lx.data(), nb, hipMemcpyHostToDevice, h->stream));
+    if (frames) HIPCHK(h, hipMemcpyAsync(frames, lx.data() + (size_t)nloc * O, fb, hipMemcpyHostToDevice, h->stream));
+    if (mask) HIPCHK(h, hipMemcpyAsync(mask, lm.data(), (size_t)nloc, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+}
+
+// count [N][O] arrays in the engine's order on the device (one partition) into the caller's order on the host; the caller synchronises
+int saves_to_caller(mgn_handle* h, const float* src, int64_t count, float* out) {
+    const LocalGraph& g = h->g;
+    const int O = h->cfg.O;
+    const size_t bytes = (size_t)count * g.N * O * 4;
+    if (!g.renumbered) {
+        HIPCHK(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream));
+        return MGN_OK;
+    }
+    std::vector<float> sv((size_t)count * g.N * O);
+    HIPCHK(h, hipMemcpyAsync(sv.data(), src, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < count; ++i)
+        for (int32_t j = 0; j < g.N; ++j)
+            memcpy(out + ((size_t)i * g.N + (size_t)g.own_gid[j]) * O, sv.data() + ((size_t)i * g.N + j) * O, (size_t)O * 4);
+    return MGN_OK;
+}
+
+// the static inputs of a solve (one-hot node types, raw edge features, val_mask; x0 only fills the encoder's state slot: every right-hand
+// side reads its state through srcA_override), and the edges encoded ONCE per trajectory into elat0 (eb: its fp32 bytes)
+int upload_statics(mgn_handle* h, const mgn_rollout_desc* d, const float* x0, char* elat0, size_t eb) {
+    const mgn_config& c = h->cfg;
+    if (int rc = upload_inputs(h, x0, c.O, d->node_type_onehot, c.Fn - c.O, d->ef_raw, true)) return rc;
+    h->have_mask = d->val_mask != nullptr;
+    if (d->val_mask) {
+        HIPCHK(h, h->d_mask.ensure((size_t)h->g.N * 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_mask.p, d->val_mask, (size_t)h->g.N * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (c.ln_dims == MGN_LN_ALL) return lnall_rhs_prepare(h);
+    if (int rc = encode_impl(h, true, false, true)) return rc;
+    const bool bf = is_bf16(h);
+    HIPCHK(h, hipMemcpyAsync(elat0, bf ? h->es[0].bElat.p : h->es[0].Elat.p, bf ? eb / 2 : eb, hipMemcpyDeviceToDevice, h->stream));
+    return MGN_OK;
+}
+
+// the handle's state that solver-based training needs: a device handle, one partition, fp32, one edge set, parameters and a graph
+int solver_state_checks(mgn_handle* h, const char* who) {
+    if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
+    const mgn_config& c = h->cfg;
+    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
+    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
+    return need(h, true, true, c.ln_dims != MGN_LN_ALL, true);
+}
+
+// the static inputs of the right-hand side
+int solver_static_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who) {
+    const mgn_config& c = h->cfg;
+    if (!d->ef_raw || (c.Fn > c.O && !d->node_type_onehot)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
+    return MGN_OK;
+}
+
+// the inflow rule and its arrays
+int inflow_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who) {
+    if (d->inflow_rule != MGN_INFLOW_REFERENCE && d->inflow_rule != MGN_INFLOW_TOLERANT) return fail(h, MGN_E_ARG, "%s: unknown inflow_rule", who);
+    if ((d->inflow_mask != nullptr) != (d->inflow_data != nullptr)) return fail(h, MGN_E_ARG, "%s: inflow mask and data go together", who);
+    return MGN_OK;
+}
+
+// count [N][O] arrays (host or device, the caller's order) into the engine's order at dst, gathered on the device through tmp ([N][O] scratch)
+// when the graph is renumbered
+int to_engine_order(mgn_handle* h, const float* src, int64_t count, float* dst, float* tmp) {
+    const int32_t N = h->g.N;
+    const int O = h->cfg.O;
+    const size_t n = (size_t)N * O;
+    for (int64_t s = 0; s < count; ++s) {
+        HIPCHK(h, hipMemcpyAsync(h->g.renumbered ? tmp : dst + s * n, src + s * n, n * 4, hipMemcpyDefault, h->stream));
+        if (h->g.renumbered) HIPCHK(h, launch_permute_rows(dst + s * n, tmp, h->d_own_gid.as<int32_t>(), N, O, false, h->stream));
+    }
+    return MGN_OK;
+}
+
+// mgn_rollout (e null) and mgn_rollout_eval (e: its checked descriptor, one partition): the same solve, the same launches in the same
+// order; with e every save is reduced against its ground-truth frame as it is produced (Rollout::save) and d->out is optional
+int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who) {
+    const bool lnall = h && h->cfg.ln_dims == MGN_LN_ALL;
+    if (int rc = need(h, true, true, !lnall, true)) return rc;
+    const mgn_config& c = h->cfg;
+    const bool part = c.nranks != 1;      // partitioned: every rank integrates the rows it owns; error norms are reduced over the ranks
+    if (part) if (int rc = need_comm(h, who)) return rc;
+    if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
+    if (!d || !d->x0 || (!d->out && !e)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (int rc = solver_static_checks(h, d, who)) return rc;
+    const TimeGrid T(d);
+    if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (d->solver == 0 && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
+    if (int rc = inflow_checks(h, d, who)) return rc;
+    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
+    if (d->solver == 1 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+    const LocalGraph& g = h->g;
+    invalidate_static(h);
+    const int32_t nloc = part ? g.n_own : g.N;        // rows of the state this handle integrates
+    Rollout R(h, d, T, false, nloc, g.N);
+    const size_t nb = (size_t)R.n * 4;
+    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = d->out ? (size_t)d->n_saves * nb : 0;
+    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
+    // evaluation: ground truth that IS the inflow data is compared where upload_engine_order puts the frames; the selection in the
+    // engine's order (n_sel == 0: all elements, no index array)
+    const bool gt_is_frames = e && e->gt == d->inflow_data && d->n_frames >= d->n_saves;
+    const int eblk = e ? save_error_blocks(nloc) : 0;
+    const int64_t n_val = e ? (e->n_sel > 0 ? e->n_sel : R.n) : 0;
+    std::vector<int64_t> sel;
+    if (e && e->n_sel > 0) {
+        std::vector<int32_t> g2l;
+        if (g.renumbered) {
+            g2l.resize((size_t)g.N);
+            for (int32_t i = 0; i < g.N; ++i) g2l[(size_t)g.own_gid[i]] = i;
+        }
+        sel.resize((size_t)e->n_sel);
+        for (int64_t i = 0; i < e->n_sel; ++i) {
+            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;      // (checked by mgn_rollout_eval)
+            sel[(size_t)i] = g.renumbered ? (int64_t)g2l[(size_t)(li / c.O)] * c.O + li % c.O : li;
+        }
+    }
+    Arena a;
+    const SolveWs ws = carve_solve(a, nb, false, false);      // (Euler too keeps all seven k and unew)
+    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)nloc), o_part = a.take(errnorm_partials() * sizeof(double));
+    R.elat0_off = a.take(eb);
+    const size_t o_eacc = a.take(e ? (size_t)R.n * 8 : 0), o_epart = a.take((size_t)d->n_saves * eblk * c.O * 8),
+                 o_egt = a.take(e && !gt_is_frames ? (size_t)d->n_saves * nb : 0), o_etmp = a.take(e && !gt_is_frames && g.renumbered ? nb : 0),
+                 o_esel = a.take(sel.size() * 8), o_evp = a.take(e ? (size_t)save_error_blocks(n_val) * 8 : 0),
+                 o_ems = a.take(e && e->mse_save ? (size_t)d->n_saves * c.O * 8 : 0), o_emt = a.take(e && e->mse_time ? nb : 0);
+    HIPCHK(h, h->ode.ensure(a.off));
+    char* base = h->ode.as<char>();
+    R.bind(base, ws);
+    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
+    R.saves = d->out ? (float*)(base + o_sv) : nullptr;
+    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
+    R.partial = (double*)(base + o_part);
+    if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
+    if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
+    if (e) {
+        float* gtl = (float*)(base + o_egt);
+        if (!gt_is_frames)      // (as solver_targets)
+            if (int rc = to_engine_order(h, e->gt, d->n_saves, gtl, (float*)(base + o_etmp))) return rc;
+        if (!sel.empty()) HIPCHK(h, hipMemcpyAsync(base + o_esel, sel.data(), sel.size() * 8, hipMemcpyHostToDevice, h->stream));
+        R.ev_gt = gt_is_frames ? R.frames : gtl;
+        R.ev_acc = (double*)(base + o_eacc);
+        R.ev_part = (double*)(base + o_epart);
+        HIPCHK(h, hipMemsetAsync(R.ev_acc, 0, (size_t)R.n * 8, h->stream));
+    }
+
+    d->n_accept = d->n_reject = 0;
+    if (int rc = d->solver == 0 ? R.euler_rollout() : R.tsit5_adaptive(who, nullptr)) return rc;
+    if (part) {     // every rank returns the complete solution
+        for (int i = 0; i < d->n_saves; ++i)
+            if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
+    } else if (d->out) {
+        if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
+    }
+    std::vector<double> vpart;
+    if (e) {
+        EvalFinish f{};
+        f.acc = R.ev_acc; f.part = R.ev_part; f.N = g.N; f.O = c.O; f.n_saves = d->n_saves;
+        f.gid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+        f.sel = sel.empty() ? nullptr : (const int64_t*)(base + o_esel);
+        f.n_val = n_val;
+        f.mse_time = e->mse_time ? (float*)(base + o_emt) : nullptr;
+        f.mse_save = e->mse_save ? (double*)(base + o_ems) : nullptr;
+        f.vpart = (double*)(base + o_evp);
+        HIPCHK(h, launch_eval_finish(f, h->stream));
+        vpart.resize((size_t)save_error_blocks(n_val));
+        HIPCHK(h, hipMemcpyAsync(vpart.data(), f.vpart, vpart.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        if (e->mse_save) HIPCHK(h, hipMemcpyAsync(e->mse_save, f.mse_save, (size_t)d->n_saves * c.O * 8, hipMemcpyDeviceToHost, h->stream));
+        if (e->mse_time) HIPCHK(h, hipMemcpyAsync(e->mse_time, f.mse_time, nb, hipMemcpyDefault, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    d->n_rhs = R.n_rhs;
+    if (e) {      // the blocks' sums in block order
+        double s = 0.0;
+        for (double v : vpart) s += v;
+        e->val_loss = s / (double)n_val;
+    }
+    return MGN_OK;
+}
+
+}  // namespace
+
+extern "C" int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
+    return rollout_solve(h, d, nullptr, "mgn_rollout");
+} MGN_CATCH(h)
+
+extern "C" int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) try {
+    static const char* who = "mgn_rollout_eval";
+    if (!h) return MGN_E_ARG;
+    // the descriptor first (a host-only handle answers it too)
+    if (!d || !e || !e->gt) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (e->n_gt < d->n_saves) return fail(h, MGN_E_ARG, "%s: n_gt = %d ground-truth frames for n_saves = %d saves", who, e->n_gt, d->n_saves);
+    if (e->n_sel < 0 || (e->n_sel > 0 && !e->sel)) return fail(h, MGN_E_ARG, "%s: n_sel must be >= 0, and sel given when it is > 0", who);
+    if (e->sel_index_base != 0 && e->sel_index_base != 1) return fail(h, MGN_E_ARG, "%s: sel_index_base must be 0 or 1", who);
+    if (h->cfg.nranks != 1)
+        return fail(h, MGN_E_UNSUPPORTED, "%s drives one partition: on a partitioned handle call mgn_rollout and reduce the solution on the host", who);
+    if (h->have_graph) {
+        const int64_t n = (int64_t)h->g.N * h->cfg.O;
+        for (int64_t i = 0; i < e->n_sel; ++i) {
+            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;
+            if (li < 0 || li >= n)
+                return fail(h, MGN_E_ARG, "%s: sel[%lld] = %d is outside the %lld elements of the [N][O] error array (index base %d)", who,
+                            (long long)i, e->sel[i], (long long)n, e->sel_index_base);
+        }
+    }
+    e->val_loss = 0.0;
+    return rollout_solve(h, d, e, who);      // (without a graph it refuses before sel is read)
+} MGN_CATCH(h)
+
+// ---- solver-based training (SolverTraining / MultipleShooting): loss and gradient of one solved window ------------------------------
+// Forward: mgn_rollout's time loop on the resident right-hand side (the same launches, the same hipGraph replay), in the training form of
+// the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the arrays the RHS saw.
+// Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
+namespace {
+
+// the inflow and the continuity weight
+int solver_inflow_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who, float cont_weight) {
+    if (int rc = inflow_checks(h, d, who)) return rc;
+    if (d->inflow_data && d->n_frames < 1) return fail(h, MGN_E_ARG, "%s: inflow_data needs n_frames >= 1", who);
+    if (!std::isfinite(cont_weight)) return fail(h, MGN_E_ARG, "%s: cont_weight must be finite", who);
+    return MGN_OK;
+}
+
+// the fixed-step grid (TimeGrid::next) walked once on the host: K = round((t1 - t0) / dt) steps, and the step whose state each of the
+// n_saves saves is (every one must be reached)
+int fixed_grid(mgn_handle* h, const char* who, const TimeGrid& T, int n_saves, int64_t* K, std::vector<int64_t>& save_step) {
+    const double steps = (T.t1 - T.t0) / T.dt;
+    if (!(steps < 1e9)) return fail(h, MGN_E_ARG, "%s: %.3g steps", who, steps);
+    *K = (int64_t)std::llround(steps);
+    save_step.assign(1, 0);
+    double t = T.t0;
+    for (int64_t i = 0; i < *K && (int)save_step.size() < n_saves; ++i) {
+        t = T.next(i, *K, t);
+        while ((int)save_step.size() < n_saves && T.stop_time((int)save_step.size()) <= t + 0.25 * T.dt) save_step.push_back(i + 1);
+    }
+    if ((int)save_step.size() < n_saves)
+        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
+                    (int)save_step.size(), T.stop_time((int)save_step.size()), T.t1);
+    return MGN_OK;
+}
+
+// gt and cont_target (host or device, the caller's order) into the engine's order (gtl, ctl); loss_scale as given (lsd); tmp: [N][O] scratch
+int solver_targets(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* cont_target, const float* loss_scale, float* gtl, float* ctl,
+                   float* lsd, float* tmp) {
+    if (int rc = to_engine_order(h, gt, d->n_saves, gtl, tmp)) return rc;
+    if (ctl)
+        if (int rc = to_engine_order(h, cont_target, 1, ctl, tmp)) return rc;
+    if (lsd) HIPCHK(h, hipMemcpyAsync(lsd, loss_scale, (size_t)h->cfg.O * 4, hipMemcpyDefault, h->stream));
+    return MGN_OK;
+}
+
+// the fields of a reverse sweep that every caller fills from its solve R (Euler: K steps over the stored states; Tsit5: K accepted steps).
+// R.save_step is the plan the solve was given once all its saves are taken (saves_after pushes the plan's own entries; the shooting pass
+// checks R.saved), and R.tg.dt is the call's dt for every window (a group's grid copies it)
+SolverSweep sweep_setup(const Rollout& R, bool euler, int64_t K, const float* states, const float* gt, const float* loss_scale, const uint8_t* inflow,
+                        const float* cont_target, float* a, double* gacc) {
+    SolverSweep S{};
+    S.K = K; S.states = euler ? states : nullptr; S.saves = R.saves; S.save_step = R.save_step.data(); S.n_saves = R.d->n_saves;
+    S.gt = gt; S.loss_scale = loss_scale; S.inflow = inflow; S.cont_target = cont_target; S.dt = euler ? (float)R.tg.dt : 0.f;
+    S.a = a; S.gacc = gacc;
+    return S;
+}
+// the sweep on engine e: Euler's, or Tsit5's over the stored stage inputs of R's accepted steps (ybar: scratch [5][n])
+int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler, const std::vector<float*>& steps, float* ybar) {
+    if (euler) return solver_sweep(e, S);
+    const Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, ybar};
+    return tsit5_sweep(e, S, T5);
+}
+
+// mgn_solver_grad (o null: fixed-step Euler) and mgn_solver_grad_tsit5 (o: fixed steps, or adaptive), after their own checks: the time grid,
+// the forward loop keeping what the sweep needs (Euler: every step's RHS input; Tsit5: every accepted step's six stage inputs, in chunks on
+// the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves
+int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
+                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) {
+    const bool euler = !o, adaptive = o && o->adaptive != 0;
+    const TimeGrid T(d);
+    if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (!adaptive && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, euler ? "%s: Euler needs dt > 0" : "%s: fixed steps need dt > 0", who);
+    if (adaptive && !(T.dt >= 0.0)) return fail(h, MGN_E_ARG, "%s: dt must be >= 0 (0: the Hairer-Wanner start)", who);
+    if (adaptive && !(d->abstol > 0.f && d->reltol > 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+    if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
+    if (o) {
+        o->n_steps = 0;
+        o->stored_bytes = 0;
+    }
+    int64_t K = 0;                       // fixed steps: the step count; adaptive: the accepted steps, after the solve
+    std::vector<int64_t> plan;
+    if (!adaptive) {
+        if (int rc = fixed_grid(h, who, T, d->n_saves, &K, plan)) return rc;
+    } else if (T.stop_time(d->n_saves - 1) > T.t1 + 1e-5 * T.sdt) {
+        return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
+                    d->n_saves - 1, T.stop_time(d->n_saves - 1), T.t1);
+    }
+    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
+    const mgn_config& c = h->cfg;
+    const int32_t N = h->g.N;
+    const int O = c.O;
+    invalidate_static(h);
+    Rollout R(h, d, T, true, N, N);
+    const size_t nb = (size_t)R.n * 4;
+    const size_t P = h->params.size();
+    const int ablk = solver_adjoint_blocks(N, O);
+    if (euler && (size_t)(K + 1) > (SIZE_MAX / 2) / (nb > 0 ? nb : 1))
+        return fail(h, MGN_E_OOM, "%s: %lld stored states of %zu bytes overflow the address space", who, (long long)(K + 1), nb);
+    const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
+    const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
+    Arena a;
+    const SolveWs ws = carve_solve(a, nb, euler, !euler && d->inflow_mask != nullptr);
+    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)N), o_pe = a.take(euler ? 0 : errnorm_partials() * sizeof(double));
+    R.elat0_off = a.take(eb);
+    const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb), o_tmp = a.take(nb),
+                 o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
+    const size_t o_st = a.take(euler ? (size_t)(K + 1) * nb : 0);
+    if (int rc = euler ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the %lld stored states of the solve and the call's buffers", who,
+                                        (double)a.off * 1e-9, (long long)(K + 1))
+                       : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
+        return rc;
+    char* base = h->ode.as<char>();
+    R.bind(base, ws);
+    R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
+    R.saves = (float*)(base + o_sv);
+    R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
+    R.partial = euler ? nullptr : (double*)(base + o_pe);
+    if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
+    if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
+
+    // Tsit5: the stored stage inputs, step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown
+    // geometrically (never reallocated: a stored step does not move)
+    const size_t stepb = 6 * nb;
+    const int64_t max_steps = 100000;
+    std::vector<float*> steps;
+    size_t chunk = 0, used_in_chunk = 0;
+    const Rollout::Slot slot = [&](int64_t n, float** out) -> int {
+        while ((int64_t)steps.size() <= n) {
+            if ((int64_t)steps.size() >= max_steps)
+                return fail(h, MGN_E_STATE, "%s: more than %lld accepted steps (maxiters)", who, (long long)max_steps);
+            if (o->max_store_bytes && (size_t)(steps.size() + 1) * stepb > o->max_store_bytes)
+                return fail(h, MGN_E_OOM, "%s: step %lld needs %zu bytes of stored stage inputs, beyond max_store_bytes = %zu", who,
+                            (long long)steps.size(), (size_t)(steps.size() + 1) * stepb, o->max_store_bytes);
+            DevBuf* cb = chunk < h->tsit5_store.size() ? h->tsit5_store[chunk].get() : nullptr;
+            if (cb && used_in_chunk + stepb <= cb->bytes) {
+                steps.push_back(reinterpret_cast<float*>(cb->as<char>() + used_in_chunk));
+                used_in_chunk += stepb;
+                continue;
+            }
+            if (cb && used_in_chunk > 0) { ++chunk; used_in_chunk = 0; continue; }
+            // a new chunk (or an earlier call's that holds no step of this size, regrown in place): as many steps as are stored so far (at
+            // least 8; a fixed-step solve: all it has left), within max_store_bytes
+            size_t want = (size_t)std::max<int64_t>(adaptive ? std::max<int64_t>((int64_t)steps.size(), 8) : K - (int64_t)steps.size(), 1);
+            if (o->max_store_bytes) want = std::min(want, o->max_store_bytes / stepb - steps.size());
+            if (want > (SIZE_MAX / 2) / stepb) return fail(h, MGN_E_OOM, "%s: %zu stored steps overflow the address space", who, want);
+            if (!cb) {
+                h->tsit5_store.push_back(std::make_unique<DevBuf>());
+                cb = h->tsit5_store.back().get();
+            }
+            if (int rc = ensure_or_fail(h, *cb, want * stepb, "%s: step %lld: %.3f GB more for the stored stage inputs (%.3f GB stored)", who,
+                                        (long long)steps.size(), (double)(want * stepb) * 1e-9, (double)(steps.size() * stepb) * 1e-9))
+                return rc;
+            used_in_chunk = 0;
+        }
+        *out = steps[n];
+        return MGN_OK;
+    };
+
+    d->n_accept = d->n_reject = 0;
+    float* states = (float*)(base + o_st);
+    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : R.tsit5_fixed(K, plan, slot)) return rc;
+    d->n_rhs = R.n_rhs;
+    if (!euler) {
+        K = (int64_t)R.step_h.size();
+        o->n_steps = (int32_t)K;
+        o->stored_bytes = (size_t)K * stepb;
+        for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
+            if (o->step_t) o->step_t[i] = R.step_t[i];
+            if (o->step_h) o->step_h[i] = R.step_h[i];
+        }
+    }
+
+    float* gtl = (float*)(base + o_gt);
+    float* ctl = cont_target ? (float*)(base + o_ct) : nullptr;
+    float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
+    if (int rc = solver_targets(h, d, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
+
+    SolverSweep S = sweep_setup(R, euler, K, states, gtl, lsd, R.mask, ctl, (float*)(base + o_a), (double*)(base + o_gacc));
+    S.cont_weight = ctl ? cont_weight : 0.f;
+    S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
+    S.part = (double*)(base + o_part); S.grads = grads; S.loss = loss;
+    if (int rc = run_sweep(h, S, R, euler, steps, (float*)(base + o_yb))) return rc;
+    if (d->out)      // the predicted saves in the caller's order
+        if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+}
+
+// the checks mgn_solver_grad and mgn_solver_grad_tsit5 share before their solver's
+int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss) {
+    if (int rc = solver_state_checks(h, who)) return rc;
+    if (!d || !gt || !grads || !loss || !d->x0) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    return solver_static_checks(h, d, who);
+}
+
+}  // namespace
+
+extern "C" int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
+                    float* grads, size_t n_grads, float* loss) try {
+    static const char* who = "mgn_solver_grad";
+    if (!h) return MGN_E_ARG;
+    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
+    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
+    if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
+    return solver_grad(h, d, nullptr, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+} MGN_CATCH(h)
+
+// Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_adaptive, Tsit5Control) or fixed steps on the Euler grid (Rollout::tsit5_fixed), in
+// the training form (za / zs / z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
+extern "C" int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
+                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
+    static const char* who = "mgn_solver_grad_tsit5";
+    if (!h) return MGN_E_ARG;
+    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
+    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
+    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
+    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+} MGN_CATCH(h)
+
+// ---- MultipleShooting as one batch (mgn_shooting_grad) ----------------------------------------------------------------------------------
+// The windows of one MultipleShooting loss are independent (each starts from gt; the continuity term couples a window to gt only), so
+// windows with the same step plan are solved together on a companion engine holding B copies of the graph: one solve of a block-diagonal
+// graph per pass instead of B launch-bound solves.  Per window the arithmetic is that of mgn_solver_grad / mgn_solver_grad_tsit5 (fixed
+// steps); the loss partials and the gradient accumulate over all passes and are finalised once.
+void mgn::shoot_release(mgn_engine* h) {
+    if (!h) return;
+    for (auto& k : h->shoot_kids) mgn_destroy(k.e);
+    h->shoot_kids.clear();
+    h->shoot.release();
+}
+
+namespace {
+
+const char* const shoot_who = "mgn_shooting_grad";
+
+struct ShootGroup {
+    int64_t K = 0;
+    std::vector<int64_t> save_step;          // n_saves entries, the same for every window of the group
+    std::vector<int32_t> win;                // its windows, ascending
+    std::vector<std::vector<int32_t>> fr;    // per window: the inflow frame of every right-hand side evaluation (no inflow mask: empty)
+    size_t ftab_off = 0;                     // [n_evals][win.size()] in the int table
+    TimeGrid tg;                             // its first window's
+};
+
+// the companion for passes of B windows: B copies of h's graph in h's engine order (row w N + i = window w's engine row i), not renumbered;
+// parameters and normalisers brought up to date
+int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
+    const char* who = shoot_who;
+    mgn_engine::ShootKid* kid = nullptr;
+    for (auto& k : h->shoot_kids)
+        if (k.b == B) kid = &k;
+    if (!kid) {
+        if (h->shoot_kids.size() >= 2) {     // the oldest size goes
+            mgn_destroy(h->shoot_kids.front().e);
+            h->shoot_kids.erase(h->shoot_kids.begin());
+        }
+        const LocalGraph& g = h->g;
+        const int32_t N = g.N;
+        const EdgeTopo& t = g.set[0];
+        const int64_t E = t.e_local;
+        if ((int64_t)B * N > INT32_MAX || (int64_t)B * E > INT32_MAX) return fail(h, MGN_E_ARG, "%s: %d windows of %d nodes overflow int32 node ids", who, B, N);
+        mgn_engine* c = nullptr;
+        mgn_config cfg = h->cfg;
+        if (mgn_create(&cfg, &c) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion engine: %s", who, mgn_last_error(nullptr));
+        c->companion = true;
+        std::vector<int32_t> snd((size_t)B * E), rcv((size_t)B * E);
+        for (int32_t w = 0; w < B; ++w)
+            for (int64_t j = 0; j < E; ++j) {
+                snd[(size_t)w * E + j] = w * N + t.snd[j];
+                rcv[(size_t)w * E + j] = w * N + t.rcv[j];
+            }
+        EdgeList sets[MAX_EDGE_SETS];
+        sets[0] = {(int64_t)B * E, snd.data(), rcv.data(), 0};
+        int rc = rebuild_graph(c, B * N, sets, nullptr, 0, false, who, nullptr, 0);
+        if (!rc) rc = alloc_latents(c);
+        if (rc) {
+            rc = fail(h, rc, "%s: companion graph: %s", who, c->err.c_str());
+            mgn_destroy(c);
+            return rc;
+        }
+        c->have_graph = true;
+        h->shoot_kids.push_back({B, c, 0, false});
+        kid = &h->shoot_kids.back();
+        // the copies keep h's engine order: no renumbering, edges in the replicated (receiver-sorted, stable) order
+        const LocalGraph& cg = c->g;
+        bool same = !cg.renumbered && cg.n_own == B * N && cg.set[0].e_local == (int64_t)B * E;
+        for (int32_t i = 0; same && i < cg.n_own; ++i) same = cg.own_gid[i] == i;
+        for (int64_t j = 0; same && j < cg.set[0].e_local; ++j) same = cg.set[0].edge_gid[j] == j;
+        if (!same) return fail(h, MGN_E_STATE, "%s: the companion graph does not keep the replicated order", who);
+    }
+    mgn_engine* c = kid->e;
+    if (c->stream != h->stream)
+        if (mgn_set_stream(c, (void*)h->stream) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion stream: %s", who, c->err.c_str());
+    if (!kid->params_set || kid->params_gen != h->params_gen) {      // parameters only when they changed
+        if (mgn_set_params(c, h->params.data(), h->params.size()) != MGN_OK) return fail(h, MGN_E_STATE, "%s: companion parameters: %s", who, c->err.c_str());
+        kid->params_set = true;
+        kid->params_gen = h->params_gen;
+    }
+    if (c->norms_host != h->norms_host || c->have_nnorm != h->have_nnorm || c->have_enorm != h->have_enorm || c->have_onorm != h->have_onorm) {
+        const mgn_config& k = h->cfg;
+        const float* v = h->norms_host.data();
+        const float* ne = v + 2 * k.Fn;
+        const float* no = ne + 2 * k.Fe;
+        if (mgn_set_norms(c, h->have_nnorm ? v : nullptr, h->have_nnorm ? v + k.Fn : nullptr, h->have_enorm ? ne : nullptr,
+                          h->have_enorm ? ne + k.Fe : nullptr, h->have_onorm ? no : nullptr, h->have_onorm ? no + k.O : nullptr) != MGN_OK)
+            return fail(h, MGN_E_STATE, "%s: companion normalisers: %s", who, c->err.c_str());
+        c->norms_host = h->norms_host;
+    }
+    if (int rc = need(c, true, true, true, true)) return fail(h, rc, "%s: companion: %s", who, c->err.c_str());
+    *out = c;
+    return MGN_OK;
+}
+
+// the static inputs of a companion pass: h's engine-order arrays replicated B times on the device, the edges encoded once into elat0
+int shoot_statics(mgn_engine* c, int32_t B, int32_t N, const float* oh, const float* vm, const float* ef, char* elat0, size_t eb) {
+    const mgn_config& k = c->cfg;
+    const int W1 = k.Fn - k.O, Fe = k.Fe;
+    const int64_t E = c->g.set[0].e_local / B, rows = (int64_t)B * N;
+    c->in_wa = k.O;
+    c->in_wb = W1;
+    c->in_local = true;                      // (the state slot d_nfA is never read: every right-hand side reads srcA_override)
+    HIPCHK(c, c->d_nfA.ensure(16));
+    HIPCHK(c, c->d_nfB.ensure((size_t)rows * (W1 > 0 ? W1 : 1) * 4));
+    if (W1 > 0) HIPCHK(c, launch_shoot_gather(c->d_nfB.as<float>(), oh, rows * W1, (int64_t)N * W1, 1, nullptr, nullptr, 0, c->stream));
+    c->have_mask = vm != nullptr;
+    if (vm) {
+        HIPCHK(c, c->d_mask.ensure((size_t)rows * 4));
+        HIPCHK(c, launch_shoot_gather(c->d_mask.as<float>(), vm, rows, N, 1, nullptr, nullptr, 0, c->stream));
+    }
+    HIPCHK(c, c->es[0].d_ef.ensure((size_t)B * E * Fe * 4 + 16));
+    if (E > 0) HIPCHK(c, launch_shoot_gather(c->es[0].d_ef.as<float>(), ef, (int64_t)B * E * Fe, E * Fe, 1, nullptr, nullptr, 0, c->stream));
+    if (int rc = encode_impl(c, true, false, true)) return rc;
+    HIPCHK(c, hipMemcpyAsync(elat0, c->es[0].Elat.p, eb, hipMemcpyDeviceToDevice, c->stream));
+    return MGN_OK;
+}
+
+struct ShootPass { int32_t grp, j0, B; size_t idx_off, cw_off; };
+
+// what the steps of one mgn_shooting_grad call hand on: the checked call, the host plan (shoot_plans), the staging on h->shoot (shoot_stage)
+struct ShootCtx {
+    mgn_handle* h; mgn_rollout_desc* d; mgn_shooting_desc* s;
+    float cont_weight; size_t n_grads;
+    TimeGrid DG;                             // (its time type, dt and saves_dt; every window has its own t0 and t1)
+    bool euler, inflow;
+    int32_t N; int O, W1, Fe; int64_t E, nN;
+    mgn_rollout_desc dw;                     // a pass's descriptor: d with its group's n_saves
+    std::vector<ShootGroup> groups;
+    std::vector<ShootPass> passes;
+    std::vector<int32_t> itab;               // int32 tables: per group the frame table, per pass x0 [B] | save targets [n_saves][B] | continuity [B]
+    std::vector<float> cwtab;
+    std::vector<int64_t> out_row;            // the first output save of every window
+    int32_t Bmax = 1;
+    int ld = 0;
+    char* sbase = nullptr;
+    size_t o_oh = 0, o_vm = 0, o_ef = 0, o_out = 0, o_gf = 0;
+    float *gtl = nullptr, *frl = nullptr, *lsd = nullptr; uint8_t* mkl = nullptr; double *gacc = nullptr, *lacc = nullptr;
+    const int32_t* itd = nullptr; const float* cwd = nullptr;
+    // host arrays that asynchronous copies read, and the captured right-hand sides: alive until the final synchronisation
+    std::vector<float> hs, zero_x0;          // the statics of companion passes in the engine's order; the encoder's unused state slot of a one-window pass
+    std::vector<std::unique_ptr<Rollout>> keep_alive;
+    ShootCtx(mgn_handle* h_, mgn_rollout_desc* d_, mgn_shooting_desc* s_, float cw, size_t ng)
+        : h(h_), d(d_), s(s_), cont_weight(cw), n_grads(ng), DG(d_), euler(d_->solver == 0), inflow(d_->inflow_mask != nullptr), N(h_->g.N), O(h_->cfg.O),
+          W1(h_->cfg.Fn - O), Fe(h_->cfg.Fe), E(h_->g.set[0].e_local), nN((int64_t)N * O), dw(*d_) {}
+};
+
+// ---- plans on the host: every window walks the single-window grid; identical plans form a group; then the passes and their tables
+int shoot_plans(ShootCtx& X) {
+    mgn_handle* h = X.h; mgn_rollout_desc* d = X.d; mgn_shooting_desc* s = X.s;
+    for (int32_t w = 0; w < s->n_windows; ++w) {
+        TimeGrid T = X.DG;
+        T.t0 = T.tt(s->t0[w]);
+        T.t1 = T.tt(s->t1[w]);
+        if (!(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: window %d: t1 < t0", shoot_who, w);
+        char ww[64];
+        snprintf(ww, sizeof ww, "%s: window %d", shoot_who, w);
+        int64_t K;
+        std::vector<int64_t> ss;
+        if (int rc = fixed_grid(h, ww, T, s->last[w] - s->first[w] + 1, &K, ss)) return rc;
+        std::vector<int32_t> fr;
+        if (X.inflow) {      // the frame of every right-hand side evaluation, in the order the solve makes them
+            const Rollout P(h, d, T);        // (its frame rule only)
+            auto push = [&](double t) -> int {
+                int64_t f;
+                if (int rc = P.frame_index(t, &f)) return rc;
+                fr.push_back((int32_t)f);
+                return MGN_OK;
+            };
+            double t = T.t0;
+            if (!X.euler)
+                if (int rc = push(t)) return rc;                 // k1
+            for (int64_t i = 0; i < K; ++i) {
+                const double tn = T.next(i, K, t);
+                if (X.euler) {
+                    if (int rc = push(t)) return rc;
+                } else {
+                    for (int sidx = 1; sidx < 6; ++sidx)
+                        if (int rc = push(T.tt(t + T.tt(TS_C[sidx] * T.dt)))) return rc;
+                    if (int rc = push(tn)) return rc;            // stage 7 = z_{n+1,1} sees t_{n+1}
+                }
+                t = tn;
+            }
+        }
+        int32_t gi = -1;
+        for (size_t q = 0; q < X.groups.size() && gi < 0; ++q)
+            if (X.groups[q].K == K && X.groups[q].save_step == ss) gi = (int32_t)q;
+        if (gi < 0) {
+            gi = (int32_t)X.groups.size();
+            X.groups.push_back({K, ss, {}, {}, 0, T});
+        }
+        X.groups[gi].win.push_back(w);
+        X.groups[gi].fr.push_back(std::move(fr));
+    }
+
+    // passes: a group's windows in chunks of at most `cap` (sizes as even as the cap allows)
+    int64_t cap = std::max<int64_t>(1, (s->max_batch_nodes > 0 ? s->max_batch_nodes : ((int64_t)1 << 20)) / std::max<int32_t>(X.N, 1));
+    if (s->max_windows_per_pass > 0) cap = std::min<int64_t>(cap, s->max_windows_per_pass);
+    if (h->cfg.ln_dims == MGN_LN_ALL) cap = 1;   // a whole-array LayerNorm would couple the copies
+    X.out_row.assign(s->n_windows + 1, 0);
+    for (int32_t w = 0; w < s->n_windows; ++w) X.out_row[w + 1] = X.out_row[w] + (s->last[w] - s->first[w] + 1);
+    for (size_t q = 0; q < X.groups.size(); ++q) {
+        ShootGroup& G = X.groups[q];
+        const int32_t nw = (int32_t)G.win.size();
+        if (X.inflow) {
+            G.ftab_off = X.itab.size();
+            const size_t ne = G.fr[0].size();
+            for (size_t e = 0; e < ne; ++e)
+                for (int32_t j = 0; j < nw; ++j) X.itab.push_back(G.fr[j][e]);
+        }
+        const int32_t np = (int32_t)((nw + cap - 1) / cap);
+        for (int32_t p = 0, j0 = 0; p < np; ++p) {
+            const int32_t B = nw / np + (p < nw % np ? 1 : 0);
+            ShootPass ps{(int32_t)q, j0, B, X.itab.size(), X.cwtab.size()};
+            const int ns = (int)G.save_step.size();
+            for (int32_t j = 0; j < B; ++j) X.itab.push_back(s->first[G.win[j0 + j]]);
+            for (int sv = 0; sv < ns; ++sv)
+                for (int32_t j = 0; j < B; ++j) X.itab.push_back(s->first[G.win[j0 + j]] + sv);
+            for (int32_t j = 0; j < B; ++j) {
+                const int32_t w = G.win[j0 + j];
+                X.itab.push_back(w + 1 < s->n_windows ? s->first[w + 1] : s->first[w]);
+                X.cwtab.push_back(w + 1 < s->n_windows ? X.cont_weight : 0.f);
+            }
+            X.passes.push_back(ps);
+            X.Bmax = std::max(X.Bmax, B);
+            j0 += B;
+        }
+    }
+    return MGN_OK;
+}
+
+// ---- the call's staging on the handle: gt (engine order), frames, masks, statics, tables, accumulators
+int shoot_stage(ShootCtx& X, const float* gt, const float* loss_scale) {
+    mgn_handle* h = X.h; mgn_rollout_desc* d = X.d; mgn_shooting_desc* s = X.s;
+    const size_t P_ = h->params.size();
+    X.ld = solver_adjoint_blocks((int64_t)X.Bmax * X.N, X.O);
+    const bool any_batch = X.Bmax > 1;
+    const size_t gtb = (size_t)s->n_gt * X.nN * 4;
+    const size_t fb = X.inflow ? (size_t)d->n_frames * X.nN * 4 : 0;
+    Arena a;
+    const size_t o_gt = a.take(gtb), o_gtc = a.take(h->g.renumbered ? gtb : 0), o_fr = a.take(fb), o_mk = a.take(X.inflow ? (size_t)X.N : 0);
+    X.o_oh = a.take(any_batch ? (size_t)X.N * X.W1 * 4 : 0); X.o_vm = a.take(any_batch && d->val_mask ? (size_t)X.N * 4 : 0);
+    X.o_ef = a.take(any_batch ? (size_t)X.E * X.Fe * 4 : 0); X.o_out = a.take(d->out ? (size_t)X.out_row[s->n_windows] * X.nN * 4 : 0);
+    const size_t o_gacc = a.take(P_ * 8), o_lacc = a.take((size_t)2 * X.ld * 8);
+    X.o_gf = a.take(P_ * 4);
+    const size_t o_ls = a.take((size_t)X.O * 4), o_it = a.take(X.itab.size() * 4), o_cw = a.take(X.cwtab.size() * 4);
+    if (int rc = ensure_or_fail(h, h->shoot, a.off, "%s: %.3f GB for the call's staging", shoot_who, (double)a.off * 1e-9)) return rc;
+    X.sbase = h->shoot.as<char>();
+    X.gtl = (float*)(X.sbase + o_gt);
+    X.frl = X.inflow ? (float*)(X.sbase + o_fr) : nullptr;
+    X.mkl = X.inflow ? (uint8_t*)(X.sbase + o_mk) : nullptr;
+    X.gacc = (double*)(X.sbase + o_gacc);
+    X.lacc = (double*)(X.sbase + o_lacc);
+    X.lsd = loss_scale ? (float*)(X.sbase + o_ls) : nullptr;
+    X.itd = (const int32_t*)(X.sbase + o_it);
+    X.cwd = (const float*)(X.sbase + o_cw);
+    const int32_t* ngid = h->d_own_gid.as<int32_t>();
+    if (!h->g.renumbered) {
+        HIPCHK(h, hipMemcpyAsync(X.gtl, gt, gtb, hipMemcpyDefault, h->stream));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(X.sbase + o_gtc, gt, gtb, hipMemcpyDefault, h->stream));
+        HIPCHK(h, launch_shoot_gather(X.gtl, (const float*)(X.sbase + o_gtc), (int64_t)s->n_gt * X.nN, X.nN, s->n_gt, nullptr, ngid, X.O, h->stream));
+    }
+    // host arrays (as mgn_rollout takes them) into the engine's order: frames, inflow mask, and the statics of companion passes (the node
+    // order of one partition: own_gid)
+    if (int rc = upload_engine_order(h, d, nullptr, X.frl, X.mkl)) return rc;
+    if (any_batch) {
+        X.hs.resize((size_t)X.N * X.W1 + (d->val_mask ? (size_t)X.N : 0) + (size_t)X.E * X.Fe);
+        float* ho = X.hs.data();
+        float* hv = ho + (size_t)X.N * X.W1;
+        float* he = hv + (d->val_mask ? (size_t)X.N : 0);
+        for (int32_t i = 0; i < X.N; ++i) {
+            const size_t gi = (size_t)h->g.own_gid[i];
+            if (X.W1 > 0) memcpy(ho + (size_t)i * X.W1, d->node_type_onehot + gi * X.W1, (size_t)X.W1 * 4);
+            if (d->val_mask) hv[i] = d->val_mask[gi];
+        }
+        for (int64_t j = 0; j < X.E; ++j) memcpy(he + (size_t)j * X.Fe, d->ef_raw + (size_t)h->g.set[0].edge_gid[j] * X.Fe, (size_t)X.Fe * 4);
+        if (X.W1 > 0) HIPCHK(h, hipMemcpyAsync(X.sbase + X.o_oh, ho, (size_t)X.N * X.W1 * 4, hipMemcpyHostToDevice, h->stream));
+        if (d->val_mask) HIPCHK(h, hipMemcpyAsync(X.sbase + X.o_vm, hv, (size_t)X.N * 4, hipMemcpyHostToDevice, h->stream));
+        if (X.E > 0) HIPCHK(h, hipMemcpyAsync(X.sbase + X.o_ef, he, (size_t)X.E * X.Fe * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (!X.itab.empty()) HIPCHK(h, hipMemcpyAsync(X.sbase + o_it, X.itab.data(), X.itab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    if (!X.cwtab.empty()) HIPCHK(h, hipMemcpyAsync(X.sbase + o_cw, X.cwtab.data(), X.cwtab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    if (X.lsd) HIPCHK(h, hipMemcpyAsync(X.lsd, loss_scale, (size_t)X.O * 4, hipMemcpyDefault, h->stream));
+    HIPCHK(h, hipMemsetAsync(X.gacc, 0, P_ * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(X.lacc, 0, (size_t)2 * X.ld * 8, h->stream));
+    X.zero_x0.assign((size_t)X.nN, 0.f);
+    return MGN_OK;
+}
+
+// ---- one pass: B windows of a group as one state on h itself (B = 1) or on the companion of B copies; solve, then sweep
+int shoot_pass(ShootCtx& X, const ShootPass& ps) {
+    mgn_handle* h = X.h; mgn_rollout_desc* d = X.d; mgn_shooting_desc* s = X.s;
+    const ShootGroup& G = X.groups[ps.grp];
+    const int32_t B = ps.B;
+    const int64_t K = G.K;
+    const int ns = (int)G.save_step.size();
+    mgn_engine* e = h;
+    if (B > 1) {
+        if (int rc = shoot_companion(h, B, &e)) return rc;
+        if (int rc = solver_prepare(e, X.n_grads)) return fail(h, rc, "%s: companion: %s", shoot_who, e->err.c_str());
+    }
+    auto efail = [&](int rc) { return e == h ? rc : fail(h, rc, "%s: companion: %s", shoot_who, e->err.c_str()); };
+    invalidate_static(e);
+    X.dw.n_saves = ns;
+    X.keep_alive.push_back(std::make_unique<Rollout>(e, &X.dw, G.tg, true, B * X.N, B * X.N));
+    Rollout& R = *X.keep_alive.back();
+    const size_t nb = (size_t)R.n * 4;
+    const size_t eb = tile_floats(e->es[0].ntiles_e, h->cfg.L) * 4;
+    Arena ea;
+    const SolveWs ws = carve_solve(ea, nb, X.euler, !X.euler && X.inflow);
+    const size_t o_sv = ea.take((size_t)ns * nb), o_el = ea.take(eb), o_tg = ea.take((size_t)ns * nb), o_ct = ea.take(nb), o_a = ea.take(nb),
+                 o_yb = ea.take(X.euler ? 0 : 5 * nb), o_mr = ea.take(X.inflow && B > 1 ? (size_t)B * X.N : 0);
+    if ((size_t)(K + 1) > (SIZE_MAX / 8) / (nb > 0 ? nb : 1)) return fail(h, MGN_E_OOM, "%s: %lld stored steps overflow the address space", shoot_who, (long long)K);
+    const size_t o_st = ea.take((size_t)(X.euler ? K + 1 : 6 * K) * nb);
+    if (int rc = ensure_or_fail(h, e->ode, ea.off, "%s: %.3f GB for a pass of %d windows (stored states and buffers)", shoot_who, (double)ea.off * 1e-9, B))
+        return rc;
+    char* base = e->ode.as<char>();
+    R.bind(base, ws);
+    R.frames = X.frl;
+    R.mask = X.mkl;
+    R.ftab = X.inflow ? X.itd + G.ftab_off + ps.j0 : nullptr;
+    R.ftab_ld = (int64_t)G.win.size();
+    R.win_rows = X.N;
+    R.saves = (float*)(base + o_sv);
+    R.partial = nullptr;
+    R.elat0_off = o_el;
+    uint8_t* mrep = X.inflow ? (B > 1 ? (uint8_t*)(base + o_mr) : X.mkl) : nullptr;
+    float* store = (float*)(base + o_st);
+    if (e == h) {
+        if (int rc = upload_statics(h, d, X.zero_x0.data(), base + o_el, eb)) return rc;
+    } else {
+        if (int rc = shoot_statics(e, B, X.N, (const float*)(X.sbase + X.o_oh), d->val_mask ? (const float*)(X.sbase + X.o_vm) : nullptr,
+                                   (const float*)(X.sbase + X.o_ef), base + o_el, eb)) return efail(rc);
+        if (X.inflow) HIPCHK(h, launch_shoot_gather_u8(mrep, X.mkl, (int64_t)B * X.N, X.N, h->stream));
+    }
+    const int32_t* ix = X.itd + ps.idx_off;
+    HIPCHK(h, launch_shoot_gather(R.u, X.gtl, R.n, X.nN, 0, ix, nullptr, 0, h->stream));     // x0 = gt[first[w]]
+
+    // forward: the single-window loops, save points from the group's plan; Tsit5 keeps step i's stage inputs contiguously at steps[i]
+    std::vector<float*> steps;
+    for (int64_t i = 0; !X.euler && i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
+    const Rollout::Slot slot = [&](int64_t i, float** out) { *out = steps[i]; return MGN_OK; };
+    if (int rc = X.euler ? R.euler_train(K, G.save_step, store) : R.tsit5_fixed(K, G.save_step, slot)) return efail(rc);
+    if (R.saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", shoot_who, R.saved, ns);
+    d->n_accept += (int32_t)(K * B);
+    d->n_rhs += R.n_rhs * B;
+
+    // targets of the pass, gathered out of gt on the device
+    float* tg = (float*)(base + o_tg);
+    float* ctt = (float*)(base + o_ct);
+    bool has_ct = false;
+    for (int32_t j = 0; j < B; ++j) has_ct = has_ct || G.win[ps.j0 + j] + 1 < s->n_windows;
+    HIPCHK(h, launch_shoot_gather(tg, X.gtl, (int64_t)ns * R.n, X.nN, 0, ix + B, nullptr, 0, h->stream));
+    if (has_ct) HIPCHK(h, launch_shoot_gather(ctt, X.gtl, R.n, X.nN, 0, ix + B + (size_t)ns * B, nullptr, 0, h->stream));
+
+    SolverSweep S = sweep_setup(R, X.euler, K, store, tg, X.lsd, mrep, has_ct ? ctt : nullptr, (float*)(base + o_a), X.gacc);
+    if (e == h) {
+        S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
+    } else {
+        S.onehot = X.W1 > 0 ? e->d_nfB.as<float>() : nullptr; S.ef_raw = e->es[0].d_ef.as<float>(); S.val_mask = d->val_mask ? e->d_mask.as<float>() : nullptr;
+    }
+    S.cw_win = X.cwd + ps.cw_off; S.win_rows = X.N; S.lacc = X.lacc; S.lacc_ld = X.ld; S.lscale = 1.0 / ((double)ns * (double)X.nN);
+    if (int rc = run_sweep(e, S, R, X.euler, steps, (float*)(base + o_yb))) return efail(rc);
+    if (d->out) {       // the predicted saves in window order
+        float* oall = (float*)(X.sbase + X.o_out);
+        for (int sv = 0; sv < ns; ++sv)
+            for (int32_t j = 0; j < B; ++j)
+                HIPCHK(h, hipMemcpyAsync(oall + (size_t)(X.out_row[G.win[ps.j0 + j]] + sv) * X.nN, R.saves + (size_t)sv * R.n + (size_t)j * X.nN,
+                                         (size_t)X.nN * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return MGN_OK;
+}
+
+}  // namespace
+
+extern "C" int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, const float* gt, const float* loss_scale, float cont_weight,
+                                 float* grads, size_t n_grads, float* loss) try {
+    const char* who = shoot_who;
+    if (!h) return MGN_E_ARG;
+    // the arguments first (a host-only handle answers them too)
+    if (!d || !s || !gt || !grads || !loss) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
+    if (d->solver == 1 && s->adaptive != 0)
+        return fail(h, MGN_E_UNSUPPORTED, "%s: adaptive Tsit5 windows need a step controller each: call mgn_solver_grad_tsit5 per window", who);
+    const int32_t W = s->n_windows;
+    if (W < 1 || !s->first || !s->last || !s->t0 || !s->t1) return fail(h, MGN_E_ARG, "%s: needs n_windows >= 1 and first / last / t0 / t1", who);
+    if (s->max_windows_per_pass < 0 || s->max_batch_nodes < 0) return fail(h, MGN_E_ARG, "%s: max_windows_per_pass and max_batch_nodes must be >= 0", who);
+    for (int32_t w = 0; w < W; ++w)
+        if (s->first[w] < 0 || s->last[w] <= s->first[w] || s->last[w] >= s->n_gt)
+            return fail(h, MGN_E_ARG, "%s: window %d = (%d, %d) must satisfy 0 <= first < last < n_gt = %d", who, w, s->first[w], s->last[w], s->n_gt);
+    s->n_groups = s->n_passes = 0;
+    if (int rc = solver_state_checks(h, who)) return rc;
+    if (int rc = solver_static_checks(h, d, who)) return rc;
+    ShootCtx X(h, d, s, cont_weight, n_grads);
+    if (!(X.DG.sdt > 0.0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
+    if (!(X.DG.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
+    if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
+    if (int rc = shoot_plans(X)) return rc;
+    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the handle's training state
+    s->n_groups = (int32_t)X.groups.size();
+    s->n_passes = (int32_t)X.passes.size();
+    if (int rc = shoot_stage(X, gt, loss_scale)) return rc;
+    d->n_accept = d->n_reject = d->n_rhs = 0;
+    for (const ShootPass& ps : X.passes)
+        if (int rc = shoot_pass(X, ps)) return rc;
+    // results: the gradient finalised once, the loss partials added in a fixed order, one synchronisation
+    float* gf = (float*)(X.sbase + X.o_gf);
+    HIPCHK(h, launch_grad_finish(X.gacc, gf, (int64_t)h->params.size(), h->stream));
+    HIPCHK(h, hipMemcpyAsync(grads, gf, h->params.size() * 4, hipMemcpyDefault, h->stream));
+    std::vector<double> lp((size_t)2 * X.ld);
+    HIPCHK(h, hipMemcpyAsync(lp.data(), X.lacc, lp.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    if (d->out)
+        if (int rc = saves_to_caller(h, (const float*)(X.sbase + X.o_out), X.out_row[s->n_windows], d->out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double se = 0.0, sa = 0.0;
+    for (int b = 0; b < X.ld; ++b) { se += lp[b]; sa += lp[(size_t)X.ld + b]; }
+    *loss = (float)(se + sa);
+    return MGN_OK;
+} MGN_CATCH(h)
