@@ -228,7 +228,8 @@ int c16_split_enabled();
 int set_c16_row_tiles(int rt);  // debug/tests: 16-edge tiles per block of the small-graph edge kernel (0: chosen by size); returns the old value
 int set_kernel_path(int p);   // debug/tests: 0 auto, 1 resident, 2 streaming, 3 cooperative, 4 GEN (general hidden_layers) kernels; returns the old value
 int get_kernel_path();
-int set_num_cus(int n);        // debug/tests: the CU count every size decision of the inference launches reads (0: the device's; a multiple of NUM_XCD up to it); returns the old value, -1 if refused
+int set_num_cus(int n);        // debug/tests: the CU count every size decision of the inference launches reads, and the one that scales the size rules of the training step (train.hip: train_size_cus) (0: the device's -- training: its literals; a multiple of NUM_XCD up to the device's); returns the old value, -1 if refused
+int num_cus_override();        // what set_num_cus installed (0: no override)
 hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s);
 hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s);
 hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);   // mode-2 work with both chunks LDS-resident

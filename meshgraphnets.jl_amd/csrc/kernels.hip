@@ -2552,6 +2552,7 @@ int set_num_cus(int n) {
     g_num_cu_test = n;
     return old;
 }
+int num_cus_override() { return g_num_cu_test; }
 
 constexpr size_t LDS_BYTES = 160 * 1024;
 

@@ -85,6 +85,8 @@ struct TrainState {
     int defer_units = 0;
     bool need_gt = true;              // GT / GXH are full arrays (else 64-float stubs: every LayerNorm'd unit runs with LNSUM)
     size_t lnsum = 0, lnsum2 = 0;     // per-block LayerNorm-parameter sums of the streaming backward kernel and their first-level reduction (TrainBwdArgs::LNSUM)
+    int size_cus = 0;                 // train_size_cus() the arena was laid out for: the launches decide by the same count (train_prepare lays it out again when the test CU count changed)
+    int64_t wg_rpb_last = 0, wg_rpb_node = 0, wg_rpb_edge[MAX_EDGE_SETS] = {0, 0};   // rows per block of the last weight-gradient launch unit, of the processor's node MLP and of its edge MLPs (mgn_debug_train_regime)
     size_t segcarry = 0;              // carry rows of the fused aggregation (2 per edge tile; TrainFwdArgs::SEG_CARRY)
     size_t lnrow = 0;                 // (mean, 1 / denominator) per row of the MLP being unwound (TrainBwdArgs::LNROW)
     // weight gradients + their reductions go to a second stream (small meshes leave most of the chip idle during k_mlp_bwd)
@@ -387,7 +389,7 @@ int prepare_graph(mgn_engine* h) {
         {
             static const bool overlap_env = [] { const char* e = getenv("MGN_TRAIN_OVERLAP"); return !e || atoi(e) != 0; }();
             const int64_t big = Emax > N ? Emax : N;
-            T.gsets = (overlap_env && !part && !T.recompute && !any_fact && L == 128 && big <= 2048 * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers; a partition runs on one stream, eagerly: communicator calls sit between its launches)
+            T.gsets = (overlap_env && !part && !T.recompute && !any_fact && L == 128 && big <= (int64_t)8 * train_size_cus() * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers; a partition runs on one stream, eagerly: communicator calls sit between its launches)
         }
         // GT / G xhat rows only where some LayerNorm'd launch unit does not take its parameter sums inside the backward kernel (train.h: LNSUM)
         bool need_gt = h->cfg.ln_dims == MGN_LN_ALL || T.gsets > 1 || !train_bwd_ln_sums(L, (int)((N + TILE - 1) / TILE));
@@ -407,7 +409,8 @@ int prepare_graph(mgn_engine* h) {
         T.gNF = take(NL);
         T.io = take((size_t)(N > 0 ? N : 1) * (2 * h->cfg.O + h->cfg.Fn + 1));
         T.ptmp = take((size_t)(NG > 0 ? NG : 1) * (size_t)std::max(h->cfg.Fn, h->cfg.O));      // row permutations of a renumbered graph
-        const int nb = std::max(wgrad_blocks(NT), wgrad_blocks(Emax));
+        int nb = std::max(wgrad_blocks(NT), wgrad_blocks(N));   // the most blocks of any launch unit (the count is not monotonic in the rows once rows per block grow)
+        for (int q = 0; q < S; ++q) nb = std::max(nb, wgrad_blocks(g.set[q].e_local));
         T.pw = take((size_t)5 * (T.gsets > 1 ? T.gsets / 2 : 1) * (nb > 0 ? nb : 1) * L * L);   // one partial-dW region per weight-gradient job of a launch (a group of units on small meshes)
         T.pb = take((size_t)(WGRAD_MAX_JOBS + 1) * (nb > 0 ? nb : 1) * L);   // (+ 1: the second output of a LayerNorm job)
         {   // Deferred reductions (MGN_TRAIN_DEFER_REDUCE = 1; built, same bits, off) where the weight gradients run on the second stream: the 33
@@ -463,6 +466,9 @@ int prepare_graph(mgn_engine* h) {
         if (const char* e = getenv("MGN_TRAIN_KEEP_STEPS")) keep0 = std::max(0, std::min(mps, atoi(e)));
     }
     T.drop_graphs();
+    T.size_cus = train_size_cus();
+    T.wg_rpb_last = T.wg_rpb_node = 0;
+    for (int64_t& v : T.wg_rpb_edge) v = 0;
     size_t off = 0;
     int test_fail = 0;                                    // MGN_TRAIN_TEST_FAIL_ALLOCS = n: the first n requests count as refused (tests of the retry)
     if (const char* e = getenv("MGN_TRAIN_TEST_FAIL_ALLOCS")) test_fail = atoi(e);
@@ -528,7 +534,7 @@ int train_prepare(mgn_handle* h, const char* who, size_t n_grads, bool partition
     if (!h->train) return fail(h, MGN_E_OOM, "host allocation failed");
     if (!h->train->packed)
         if (int rc = pack_training_weights(h)) return rc;
-    if (!h->train->graph_ready)
+    if (!h->train->graph_ready || h->train->size_cus != train_size_cus())   // (the arena's placeholders follow the size rules the launches read)
         if (int rc = prepare_graph(h)) return rc;
     return MGN_OK;
 }
@@ -966,6 +972,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
         const int64_t lrows_u = rows > node_rows ? rows : node_rows;   // a launch covers its longest job (node jobs of a factored edge MLP)
         const int64_t lrows = overlap ? lrows_all : lrows_u;           // (a group's launch: the longest job of the model; 128-row blocks either way)
         const int nb = wgrad_blocks(lrows);
+        T.wg_rpb_last = wgrad_rows_per_block(lrows);
         if (pwb.njobs + 10 > WGRAD_MAX_JOBS || prb.njobs + 14 > REDUCE_MAX_JOBS)   // (a unit adds at most 8 + 12 jobs)
             if (int rc = flush()) return rc;
         ++punits;
@@ -1079,6 +1086,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             const float* xin[3] = {A + T.Vk[k], A + T.agg[0][k], S > 1 ? A + T.agg[1][k] : nullptr};
             const int32_t* xi[3] = {nullptr, nullptr, nullptr};
             if (int rc = bwd(T.m_pn[k], N, nt_n, A + T.gV[cur], nullptr, nullptr, T.a_pn[k], gx, gxadd, xin, xi)) return rc;
+            T.wg_rpb_node = T.wg_rpb_last;
         }
         for (int q = 0; q < S; ++q) {
             const TrainMlp& me = T.m_pe[q][k];
@@ -1089,6 +1097,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                 const float* xin[3] = {A + T.Vk[k], A + T.Vk[k], A + T.Ek[q][k]};
                 const int32_t* xi[3] = {sx[q].snd, sx[q].rcv, nullptr};
                 if (int rc = bwd(me, E, sx[q].nt, A + T.gE[q][ecur], A + T.gAgg[q], sx[q].rcv, T.a_pe[q][k], gx, gxadd, xin, xi)) return rc;
+                T.wg_rpb_edge[q] = T.wg_rpb_last;
                 // gather duality: the gradients of v[receivers] / v[senders] are segmented sums over the receiver / sender CSR
                 HIPCHK(h, launch_segment_sum2(L, A + T.GXr, sx[q].rowptr, A + T.GXs, sx[q].rowptr_s, sx[q].perm_s, A + T.gV[nxt], A + T.gV[nxt],
                                               (int32_t)N, st));
@@ -1101,6 +1110,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
                 const int32_t* xi[3] = {nullptr, nullptr, nullptr};
                 if (int rc = bwd(me, E, sx[q].nt, A + T.gE[q][ecur], A + T.gAgg[q], sx[q].rcv, T.a_pe[q][k], gx, gxadd, xin, xi, q, A + T.Vk[k]))
                     return rc;
+                T.wg_rpb_edge[q] = T.wg_rpb_last;
                 if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.gV[nxt] + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (no node MLP wrote them)
                 Lin2Args l2{};    // gV += SGs W1s^T + SGr W1r^T
                 l2.rows = NT; l2.ntiles = nt_t;
@@ -1754,5 +1764,24 @@ extern "C" int mgn_feature_stats(mgn_handle* h, const float* x, int64_t rows, in
     return MGN_OK;
 } MGN_CATCH(h)
 
+// tests: which regime the training launches ran in (beside the family codes).  out[0 .. 11]: launches of launch_mlp_fwd,
+// launch_mlp_bwd and launch_lin2 since the last reset, four counters each -- cooperative, four-tile streaming, eight-tile streaming, and how
+// many of the three ran on fp16 pieces (process-wide; a replayed hipGraph launches nothing here).  out[12 .. 19]: the plan of h's training
+// state after a step -- factored (set 0, set 1), gsets, need_gt, keep_steps, rows per block of the weight-gradient launch of the processor's
+// node MLP and of its edge MLPs (set 0, set 1) -- or -1 each without one.  h may be null (counts only); reset != 0 zeroes the counts
+// after reading them.  Returns 0.
+extern "C" int mgn_debug_train_regime(mgn_handle* h, int reset, int32_t* out /* [20] */) {
+    int cnt[12];
+    train_regime_counts(cnt, reset != 0);
+    if (!out) return 0;
+    for (int i = 0; i < 12; ++i) out[i] = cnt[i];
+    for (int i = 12; i < 20; ++i) out[i] = -1;
+    if (h && h->train && h->train->graph_ready) {
+        const TrainState& T = *h->train;
+        out[12] = T.factored[0]; out[13] = T.factored[1]; out[14] = T.gsets; out[15] = T.need_gt; out[16] = T.keep_steps;
+        out[17] = (int32_t)T.wg_rpb_node; out[18] = (int32_t)T.wg_rpb_edge[0]; out[19] = (int32_t)T.wg_rpb_edge[1];
+    }
+    return 0;
+}
 // tests / bench: how many processor steps of the training arena keep their activations (-1: no training arena yet)
 extern "C" int mgn_debug_train_keep_steps(mgn_handle* h) { return (h && h->train && h->train->graph_ready) ? h->train->keep_steps : -1; }

@@ -59,6 +59,8 @@ bool train_fwd_fused_agg(int L, int ntiles);   // the forward launch of this siz
 hipError_t launch_seg_fixup(int L, const int32_t* rowptr, const float* carry, float* agg, int32_t n, hipStream_t s);
 hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s);
 bool train_uses_coop(int L, int ntiles);
+int train_size_cus();                      // the CU count the size rules of the training step are scaled by: 256 on every device, or the test CU count (kernels.h: set_num_cus)
+void train_regime_counts(int* out /* [12] */, bool reset);   // launches since the last reset: [launch_mlp_fwd, launch_mlp_bwd, launch_lin2][cooperative, 4-tile streaming, 8-tile streaming, on fp16 pieces]
 int set_train_f16(int on);                 // 1 (default): streaming training kernels at L = 128 on two fp16 pieces / three products, 0: fp32 MFMA; returns the old value     // the cooperative 4-wave MLP kernels serve this launch size
 
 // Two L x L products per row tile (the per-node halves of the factored first edge layer):
@@ -93,6 +95,7 @@ hipError_t launch_colsum_groups(const float* part, int nblocks, int cols, int gr
 bool wgrad_ln_jobs(int L);                   // the weight-gradient launch at this L takes LayerNorm jobs
 struct WgradBatch { int32_t njobs; int64_t rows_per_block; WgradJob job[WGRAD_MAX_JOBS]; };
 int wgrad_blocks(int64_t rows);
+int64_t wgrad_rows_per_block(int64_t launch_rows);   // rows per block of a weight-gradient launch sized for launch_rows
 int wgrad_blocks_of_job(int64_t launch_rows, int64_t job_rows);   // blocks of a launch sized for launch_rows that touch a job with fewer rows
 // one L x L chunk of the inference layouts, from rows [kbase, kbase + L) of the matrix at params + src (leading dimension ldw).
 // kind 0: fp32, three copies at wfrag + off (fragment order, t-major at + L L, 16x16x4 order at + 2 L L when L = 128);

@@ -5,7 +5,9 @@
 // version of SURVEY.md N2: the same lane-per-row MFMA building blocks as the inference kernels (frag.hpp), one
 // MLP per launch, row-major activations, weights streamed from L2.  See train.h for the kernel inventory.
 #include "train.h"
+#include "kernels.h"
 
+#include <atomic>
 #include <cstdlib>
 #include <mutex>
 #include <unordered_map>
@@ -1506,18 +1508,40 @@ static hipError_t launch_tiles(K kern, const A& a, int ntiles, int L, hipStream_
     return hipGetLastError();
 }
 
+// The size rules of the training step are written for 256 CUs, on every device: cooperative tiles up to per_cu * 256 tiles, eight-tile
+// blocks above 8 * 256, at most 4 * 256 weight-gradient blocks, second-stream gradient sets up to 8 * 256 tiles (mgn_train.cpp).  The test
+// CU count (mgn_debug_num_cus) replaces that 256, so that a graph the float64 oracle can check reaches every regime; without an override
+// the literals stand -- the device's own count is never read here.
+int train_size_cus() { const int c = num_cus_override(); return c ? c : 256; }
+
+// what the three launch wrappers below chose since the last reset (mgn_debug_train_regime): [fwd, bwd, lin2][cooperative, four-tile
+// streaming, eight-tile streaming, of these on fp16 pieces]
+// (relaxed atomics: handles may step from several host threads; the counts order nothing)
+static std::atomic<int> g_regime[3][4] = {};
+static void count_launch(int which, int form, bool f16) {
+    g_regime[which][form].fetch_add(1, std::memory_order_relaxed);
+    if (f16) g_regime[which][3].fetch_add(1, std::memory_order_relaxed);
+}
+void train_regime_counts(int* out /* [12] */, bool reset) {
+    for (int i = 0; i < 12; ++i) {
+        std::atomic<int>& c = g_regime[i / 4][i % 4];
+        const int v = reset ? c.exchange(0, std::memory_order_relaxed) : c.load(std::memory_order_relaxed);
+        if (out) out[i] = v;
+    }
+}
+
 // eight tiles per block once a launch fills the chip twice over with four (L = 128; MGN_TRAIN_WPB = 4 / 8 forces)
 static bool train_wpb8(int L, int ntiles) {
     static const int forced = [] { const char* e = getenv("MGN_TRAIN_WPB"); return e ? atoi(e) : 0; }();
     if (L != 128) return false;
     if (forced) return forced == 8;
-    return ntiles > 2048;
+    return ntiles > 8 * train_size_cus();
 }
 
 // Cooperative tiles while a launch has fewer than MGN_TRAIN_COOP_TILES_PER_CU tiles per CU (default 8), L = 128.
 static bool train_coop(int L, int ntiles) {
     static const int per_cu = [] { const char* e = getenv("MGN_TRAIN_COOP_TILES_PER_CU"); return e ? atoi(e) : 8; }();
-    return L == 128 && ntiles > 0 && ntiles <= per_cu * 256;
+    return L == 128 && ntiles > 0 && ntiles <= per_cu * train_size_cus();
 }
 template <typename K, typename A>
 static hipError_t launch_coop(K kern, const A& a, int ntiles, hipStream_t s) {
@@ -1541,6 +1565,7 @@ static int g_train_f16 = [] { const char* e = getenv("MGN_TRAIN_F16"); return e 
 int set_train_f16(int on) { const int old = g_train_f16; g_train_f16 = on; return old; }
 
 hipError_t launch_lin2(int L, const Lin2Args& a, hipStream_t s) {
+    if (a.ntiles > 0) count_launch(2, train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
     if (train_wpb8(L, a.ntiles)) return g_train_f16 ? launch_tiles(k_lin2<4, 8, true>, a, a.ntiles, L, s, 8) : launch_tiles(k_lin2<4, 8>, a, a.ntiles, L, s, 8);
     if (L == 128) return g_train_f16 ? launch_tiles(k_lin2<4, 4, true>, a, a.ntiles, L, s) : launch_tiles(k_lin2<4, 4>, a, a.ntiles, L, s);
     if (L == 64) return launch_tiles(k_lin2<2, 4>, a, a.ntiles, L, s);
@@ -1549,6 +1574,7 @@ hipError_t launch_lin2(int L, const Lin2Args& a, hipStream_t s) {
 }
 
 hipError_t launch_mlp_fwd(int L, int nin, const TrainFwdArgs& a, hipStream_t s) {
+    if (a.ntiles > 0) count_launch(0, train_coop(L, a.ntiles) ? 0 : train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
     if (train_coop(L, a.ntiles)) {
         if (g_train_f16) {
             if (nin == 1) return launch_coop(k_mlp_fwd_coop<1, true>, a, a.ntiles, s);
@@ -1583,6 +1609,7 @@ hipError_t launch_mlp_fwd(int L, int nin, const TrainFwdArgs& a, hipStream_t s) 
 }
 
 hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s) {
+    if (a.ntiles > 0) count_launch(1, train_coop(L, a.ntiles) ? 0 : train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
     if (train_coop(L, a.ntiles)) {
         if (g_train_f16) {
             if (nin == 1) return launch_coop(k_mlp_bwd_coop<1, true>, a, a.ntiles, s);
@@ -1617,7 +1644,7 @@ hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s) 
     return hipErrorInvalidValue;
 }
 
-static int64_t wgrad_rows_per_block(int64_t rows) {
+int64_t wgrad_rows_per_block(int64_t rows) {
     // (A/B on the cylinder mesh, k_wgrad_lds: 64 / 128 rows 3.13 / 3.11 ms per step, 256: 3.68, 512: 4.90 -- a block's row loop is a latency chain;
     // round 6, k_wgrad_h2 (two blocks per CU): 128 / 160 / 192 / 224 / 256 / 384 rows 2.45 / 2.39 / 2.38 / 2.43 / 2.53 / 2.90 ms, k_wgrad_lds 2.44 at 128, 2.48 at 192)
     static const int min_rows = [] {
@@ -1626,7 +1653,8 @@ static int64_t wgrad_rows_per_block(int64_t rows) {
         const char* h = getenv("MGN_WGRAD_H2");
         return (h && atoi(h) == 0) ? WG_ROWS : 192;
     }();
-    int64_t rpb = (rows + 1023) / 1024;              // at most 1024 blocks
+    const int64_t cap = 4 * train_size_cus();        // at most 1024 blocks (4 per CU of the size rules' 256)
+    int64_t rpb = (rows + cap - 1) / cap;
     if (rpb < min_rows) rpb = min_rows;
     return (rpb + 2 * WG_UNROLL - 1) / (2 * WG_UNROLL) * (2 * WG_UNROLL);
 }

@@ -103,12 +103,39 @@ def set_node_ring_hs(on):
 
 
 def set_num_cus(n):
-    """The CU count every size decision of the inference launches reads (tests only): 0 = the device's own, else a multiple of 8 from 8
-    up to the device's count.  Set it before the engine is created.  Returns the old value (0: no override), -1 if n is refused."""
+    """The CU count every size decision of the inference launches reads, and the one that scales the size rules of the training step
+    (cooperative up to 8 n tiles, eight-tile blocks above 8 n, at most 4 n weight-gradient blocks, second-stream gradient sets up to
+    8 n tiles) (tests only): 0 = the device's own -- for training: the literals 256 CUs stand for -- else a multiple of 8 from 8 up to the
+    device's count.  Set it before the engine is created.  Returns the old value (0: no override), -1 if n is refused."""
     lib = mgn_amd.load()
     lib.mgn_debug_num_cus.restype = __import__("ctypes").c_int
     lib.mgn_debug_num_cus.argtypes = [__import__("ctypes").c_int]
     return lib.mgn_debug_num_cus(n)
+
+
+def set_train_f16(on):
+    """Training kernels at L = 128: 1 (default) = two fp16 pieces per operand, 0 = the fp32-MFMA forms (tests only).  Returns the old value."""
+    lib = mgn_amd.load()
+    lib.mgn_debug_train_f16.restype = __import__("ctypes").c_int
+    lib.mgn_debug_train_f16.argtypes = [__import__("ctypes").c_int]
+    return lib.mgn_debug_train_f16(on)
+
+
+def train_regime(eng=None, reset=False):
+    """mgn_debug_train_regime: launches of launch_mlp_fwd / launch_mlp_bwd / launch_lin2 since the last reset as
+    (cooperative, four-tile streaming, eight-tile streaming, of these on fp16 pieces) under "fwd" / "bwd" / "lin2", and -- with an engine
+    that has run a training step -- the plan of its training state: factored0 / factored1, gsets, need_gt, keep_steps, rows per block of
+    the weight-gradient launches of the processor's node MLP (rpb_node) and edge MLPs (rpb_edge0 / rpb_edge1); -1 without one."""
+    C = __import__("ctypes")
+    lib = mgn_amd.load()
+    lib.mgn_debug_train_regime.restype = C.c_int
+    lib.mgn_debug_train_regime.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    out = (C.c_int32 * 20)()
+    assert lib.mgn_debug_train_regime(eng.h if eng is not None else None, int(reset), out) == 0
+    v = list(out)
+    d = {"fwd": tuple(v[0:4]), "bwd": tuple(v[4:8]), "lin2": tuple(v[8:12])}
+    d.update(zip(("factored0", "factored1", "gsets", "need_gt", "keep_steps", "rpb_node", "rpb_edge0", "rpb_edge1"), v[12:20]))
+    return d
 
 
 def last_kernels():
