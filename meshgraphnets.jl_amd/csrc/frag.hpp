@@ -305,6 +305,39 @@ DEVINL float ln_rstd(float var, const float* gamma, int L) {
 }
 DEVINL float ln_rstd_at(float var, const float* lnp) { return 1.0f / (sqrtf(var + lnp[0]) + lnp[1]); }   // lnp: the T_LN slot itself
 
+// Exchange between the two lane halves of a wave (lane c of the lower half and lane c + 32 hold the two halves of row c) on
+// v_permlane32_swap_b32 (gfx950): one vector instruction, where __shfl_xor(v, 32, 64) is a ds_bpermute_b32 and a wait for LDS.  The
+// instruction is a HALF swap -- lanes 32-63 of its first operand trade places with lanes 0-31 of its second, the other two halves stay --
+// so it is given two copies of the value: afterwards the first holds the lower half's value in BOTH halves and the second the upper half's.
+// Through the builtin, so that hipcc supplies the wait states between a vector write and the swap that reads it.
+struct HalfPair { float lo, hi; };                // the values of lanes c and c + 32, the same pair in both
+DEVINL HalfPair half_pair(float v) {
+    // opaque, so that the pair (v, v) is formed HERE: otherwise hipcc widens the sum that ends in v into packed operations on the pair (an
+    // s_nop behind each) and fuses q + d d differently than it did in front of a __shfl_xor -- other bits.  With it every kernel keeps the
+    // multiplies, adds and FMAs it had (counted per kernel in the assembly of kernels.hip, split.hip and train.hip).
+    asm("" : "+v"(v));
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return {__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1])};
+}
+// own + other: an IEEE addition does not depend on the order of its two terms, so lo + hi is that sum, bit for bit, in both halves
+DEVINL float half_sum(float v) {
+    const HalfPair p = half_pair(v);
+    return p.lo + p.hi;
+}
+// max(own, other) of two values that are not signalling NaNs (as an instruction: fmaxf would quiet both operands first)
+DEVINL float half_max(float v) {
+    const HalfPair p = half_pair(v);
+    float m;
+    asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(p.lo), "v"(p.hi));
+    return m;
+}
+// the value of the lane before / behind this one, as one DPP move (wave_shr:1 / wave_shl:1) where __shfl_up / __shfl_down(v, 1, 32) are a
+// ds_bpermute_b32 each.  Lanes 0 / 63 keep their own value; the shift runs through the whole wave, so lane 32 sees lane 31 and lane 31
+// lane 32 -- callers look at the result only where c != 0 / c != 31.
+DEVINL int lane_prev(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+DEVINL int lane_next(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false); }
+
 // LayerNorm over the row's L features: 16*NT in this lane + 16*NT in lane^32.  Biased variance.
 template <int NT>
 DEVINL void layer_norm_frag(f32x16 (&x)[NT], const float* gamma, const float* beta, int h) {
@@ -314,7 +347,7 @@ DEVINL void layer_norm_frag(f32x16 (&x)[NT], const float* gamma, const float* be
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int k = 0; k < 16; ++k) s += x[t][k];
-    s += __shfl_xor(s, 32, 64);
+    s = half_sum(s);
     const float mean = s * invL;
     float q = 0.f;
 #pragma unroll
@@ -325,7 +358,7 @@ DEVINL void layer_norm_frag(f32x16 (&x)[NT], const float* gamma, const float* be
             x[t][k] = d;
             q += d * d;
         }
-    q += __shfl_xor(q, 32, 64);
+    q = half_sum(q);
     const float rstd = ln_rstd(q * invL, gamma, 32 * NT);
     const f32x4* g4 = reinterpret_cast<const f32x4*>(gamma) + h;
     const f32x4* b4 = reinterpret_cast<const f32x4*>(beta) + h;

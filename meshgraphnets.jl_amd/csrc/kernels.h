@@ -218,6 +218,8 @@ int set_c16_edge_tiles(int t);   // edge tiles per CU up to which a handle takes
 bool ring_hs_default();          // fp32 launches above the cooperative range would run k_edge_ring_hs (split path on two fp16 pieces, streamed pieces)
 bool coop16_size(int ntiles_e, int ntiles_n, bool ring_hs = false);   // the launch wrappers' rule for the cooperative node kernels (<= 8 tiles per CU)
 int last_edge_kernel();
+// tests (split.hip): h2_rowmax<abs> and h2_scale of nrows rows of 128 floats, host arrays in and out (one wave per 32 rows)
+hipError_t debug_rowmax(const float* rows, int nrows, int abs, float* amax, float* s, float* rs);
 int last_node_kernel();         // family of the last fp32 edge launch (kernels.hip: launch_edge_step)
 int set_fp32_split(int on);     // debug/tests: 0 = fp32-MFMA kernels, 1 = split path (default); returns the old value
 int fp32_split_enabled();

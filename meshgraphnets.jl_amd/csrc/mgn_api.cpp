@@ -2457,6 +2457,12 @@ int mgn_debug_last_node_kernel(void) { return last_node_kernel(); }   // the sam
 int mgn_debug_last_edge_kernel(void) { return last_edge_kernel(); }   // kernels.hip: which family the last fp32 edge launch ran on
 // node numbering policy of the NEXT mgn_set_graph calls (0 never, 1 auto, 2 always breadth-first); returns the old value
 int mgn_debug_renumber(int mode) { const int old = g_renumber; g_renumber = mode; return old; }
+// tests: the row maximum the two-piece split kernels scale a row by (split_common.hpp: h2_rowmax<abs != 0>) and h2_scale's pair for it, of
+// nrows >= 1 rows of 128 floats each (host arrays; amax, s, rs: [nrows]).  abs != 0: max |x|; abs == 0: max(x, 0)
+int mgn_debug_rowmax(const float* rows, int nrows, int abs, float* amax, float* s, float* rs) {
+    if (!rows || !amax || !s || !rs || nrows < 1) return MGN_E_ARG;
+    return debug_rowmax(rows, nrows, abs, amax, s, rs) == hipSuccess ? MGN_OK : MGN_E_HIP;
+}
 int mgn_debug_renumbered(const mgn_handle* h) { return h && h->have_graph && h->g.renumbered ? 1 : 0; }
 
 int mgn_debug_edge_stamps(mgn_handle* h, int32_t k, unsigned long long* out /* [32768] */) try {

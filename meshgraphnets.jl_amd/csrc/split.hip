@@ -450,7 +450,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int k = 0; k < 16; ++k) sm += acc[t][k];
-            sm += __shfl_xor(sm, 32, 64);
+            sm = half_sum(sm);
             const float mean = sm * invL;
             float q = 0.f;
 #pragma unroll
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
                     acc[t][k] = d;
                     q += d * d;
                 }
-            q += __shfl_xor(q, 32, 64);
+            q = half_sum(q);
             const float rstd = ln_rstd_at(q * invL, tb + T_LN * L);
             const f32x4* g4 = reinterpret_cast<const f32x4*>(tb + T_GAMMA * L) + h;
             const f32x4* b4 = reinterpret_cast<const f32x4*>(tb + T_BETA * L) + h;
@@ -484,8 +484,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring(const EdgeArgs 
         CST(7);
         EST(3);
         const int reff = ix.r >= 0 ? r : (-4 - c);
-        const int rprev = __shfl_up(reff, 1, 32);
-        const int rnext = __shfl_down(reff, 1, 32);
+        const int rprev = lane_prev(reff);
+        const int rnext = lane_next(reff);
         const bool head = (c == 0) || (reff != rprev);
         const unsigned hm = (unsigned)__ballot(head);
         const int start = 31 - __clz((int)(hm & (0xFFFFFFFFu >> (31 - c))));
@@ -759,7 +759,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
         h2_layer_ring<W, 1, 1, 0, NWV>(y, acc, l2h, l3h, ring, src, nx, pend, lane, tid, x2.s);   // layer 2 (ReLU folded into the split)
         CST(3);
         const float c2 = x2.rs * rsw2;
-        const H2Scale x3 = h2_scale(__builtin_fmaf(h2_rowmax<false>(y), c2, b2pos));
+        const H2Scale x3 = h2_scale(__builtin_fmaf(h2_rowmax<false, true>(y), c2, b2pos));
         zero_frag<NT>(acc);
         CST(4);
         // layer 3: y = layer 2's accumulators in (bias, un-scaling and ReLU in the split), the NEXT tile's e out
@@ -795,7 +795,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
                         sm += v;
                     }
                 }
-            sm += __shfl_xor(sm, 32, 64);
+            sm = half_sum(sm);
             const float mean = sm * invL;
             float q = 0.f;
 #pragma unroll
@@ -806,7 +806,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
                     acc[t][k] = d;
                     q += d * d;
                 }
-            q += __shfl_xor(q, 32, 64);
+            q = half_sum(q);
             const float rstd = ln_rstd_at(q * invL, tb + T_LN * L);
             const f32x4* g4 = reinterpret_cast<const f32x4*>(tb + T_GAMMA * L) + h;
             const f32x4* b4 = reinterpret_cast<const f32x4*>(tb + T_BETA * L) + h;
@@ -838,8 +838,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
         CST(7);
         EST(3);
         const int reff = ix.r >= 0 ? r : (-4 - c);
-        const int rprev = __shfl_up(reff, 1, 32);
-        const int rnext = __shfl_down(reff, 1, 32);
+        const int rprev = lane_prev(reff);
+        const int rnext = lane_next(reff);
         const bool head = (c == 0) || (reff != rprev);
         const unsigned hm = (unsigned)__ballot(head);
         const int start = 31 - __clz((int)(hm & (0xFFFFFFFFu >> (31 - c))));
@@ -918,11 +918,9 @@ typedef RsSrcT<3> RsSrc;
 DEVINL const u32x4* rs_src(const u32x4* chunk, int w, int e) { return chunk + ((e >> 6) & 1) * 2048 + (w * Rs::W + (e >> 7)) * 64 + (e & 63); }
 // One L x L layer with both pieces from the ring.  Otherwise h2_layer_ring (same split, same products, same order; refill as there).
 // LYR: the chain's place among the NCH chains of a tile (the ring's schedule); WRAP refill: through the descriptor rfb.
-// PREMUL: acc enters in other units (the gathered Q rows): block t is multiplied by `premul` at step (0, t), just ahead of its first product --
-// its four pieces are waited for there, not all sixteen before the chain.
-template <int LYR, int FIN, int RFS = 0, int NWV = 8, bool WRAP = false, int NCH = 3, bool PREMUL = false>
+template <int LYR, int FIN, int RFS = 0, int NWV = 8, bool WRAP = false, int NCH = 3>
 DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const RsSrcT<NCH>& src, RhFrag& nx, u32x4 (&pend)[Rs::SLOTS][Rs::BUF / (NWV * 64)], int lane,
-                          int tid, float sx, float cfin = 0.f, const float* btab = nullptr, const f32x4* rf = nullptr, const N16Buf* rfb = nullptr, int rfs_rt = 0, float premul = 1.f) {
+                          int tid, float sx, float cfin = 0.f, const float* btab = nullptr, const f32x4* rf = nullptr, const N16Buf* rfb = nullptr, int rfs_rt = 0) {
     constexpr int ROT = 2;
     constexpr int W = Rs::W, WPL = Rs::WPL, NW = RsT<NCH>::NW, BUF = Rs::BUF, NB = Rs::NB;
     constexpr int LPT = BUF / (NWV * 64);        // fragments per thread in a window
@@ -994,12 +992,6 @@ DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const 
                 const int sn = s + 1;
                 const f32x2 b = bias(sn, t);
                 h2_split_pair<FIN>(nh[t], nl[t], in[sn >> 1][8 * (sn & 1) + 2 * t], in[sn >> 1][8 * (sn & 1) + 2 * t + 1], sx, cfin, b[0], b[1]);
-            }
-            if constexpr (PREMUL) {
-                if (s == 0) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) acc[t][k] *= premul;
-                }
             }
             const sp_f16x8 bh = h2_op(ph), bl = h2_op(pl);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a2), bh, acc[t], 0, 0, 0);      // small terms first
@@ -1125,7 +1117,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
         hs_layer_ring<1, 1, 0, NWV>(y, acc, ring, src, nx, pend, lane, tid, x2.s);   // layer 2 (ReLU folded into the split)
         CST(3);
         const float c2 = x2.rs * rsw2;
-        const H2Scale x3 = h2_scale(__builtin_fmaf(h2_rowmax<false>(y), c2, b2pos));
+        const H2Scale x3 = h2_scale(__builtin_fmaf(h2_rowmax<false, true>(y), c2, b2pos));
         zero_frag<NT>(acc);
         CST(4);
         // layer 3: y = layer 2's accumulators in (bias, un-scaling and ReLU in the split), the NEXT tile's e out
@@ -1158,7 +1150,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
                         sm += v;
                     }
                 }
-            sm += __shfl_xor(sm, 32, 64);
+            sm = half_sum(sm);
             const float mean = sm * invL;
             float q = 0.f;
 #pragma unroll
@@ -1169,7 +1161,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
                     acc[t][k] = d;
                     q += d * d;
                 }
-            q += __shfl_xor(q, 32, 64);
+            q = half_sum(q);
             const float rstd = ln_rstd_at(q * invL, tb + T_LN * L);
             const f32x4* g4 = reinterpret_cast<const f32x4*>(tb + T_GAMMA * L) + h;
             const f32x4* b4 = reinterpret_cast<const f32x4*>(tb + T_BETA * L) + h;
@@ -1197,8 +1189,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
         CST(7);
         EST(3);
         const int reff = ix.r >= 0 ? r : (-4 - c);
-        const int rprev = __shfl_up(reff, 1, 32);
-        const int rnext = __shfl_down(reff, 1, 32);
+        const int rprev = lane_prev(reff);
+        const int rnext = lane_next(reff);
         const bool head = (c == 0) || (reff != rprev);
         const unsigned hm = (unsigned)__ballot(head);
         const int start = 31 - __clz((int)(hm & (0xFFFFFFFFu >> (31 - c))));
@@ -1445,12 +1437,12 @@ __global__ __launch_bounds__(512, 2) void k_node_split_h(const NodeArgs a) {
         STAMP(2);
         h2_layer_otf<true, 0, D, 0, true, true>(acc, x, lah, ga, lane, sa.s, 0.f, nullptr, &rg, g2);             // layer 1, aggregate part
         STAMP(3);
-        const H2Scale s2 = h2_scale(h2_rowmax<false>(acc));                                                       // (on the raw accumulators)
+        const H2Scale s2 = h2_scale(h2_rowmax<false, true>(acc));                                                       // (on the raw accumulators)
         zero_frag<NT>(x);
         h2_layer_otf<true, 1, D, 0, true, true>(x, acc, l2h, g2, lane, s2.s, 0.f, nullptr, &rg, g3);             // layer 2
         STAMP(4);
         const float c2 = s2.rs * rsw2 * (sa.rs * rswa);
-        const H2Scale s3 = h2_scale(__builtin_fmaf(h2_rowmax<false>(x), c2, b2pos));
+        const H2Scale s3 = h2_scale(__builtin_fmaf(h2_rowmax<false, true>(x), c2, b2pos));
         zero_frag<NT>(acc);
         // layer 3; the registers of its input are refilled, as the split releases them, with v again (for the residual)
         h2_layer_otf<true, 2, D, 0, true, false, MGN_NODE_VREFILL, STRIDE_TILE>(acc, x, l3h, g3, lane, s3.s, c2, tb + T_B2 * L + 4 * h, &rg, nullptr, vtile);
@@ -1558,11 +1550,11 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
         const H2Scale sa = h2_scale(h2_rowmax<true>(x));
         h2_scale_frag<NT>(acc, sa.s * swa);                                                                       // the aggregate chain's units
         hs_layer_ring<1, 0, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, sa.s);                    // layer 1, aggregate part
-        const H2Scale s2 = h2_scale(h2_rowmax<false>(acc));
+        const H2Scale s2 = h2_scale(h2_rowmax<false, true>(acc));
         zero_frag<NT>(x);
         hs_layer_ring<2, 1, 0, NWV, false, NCH>(x, acc, ring, src, nx, pend, lane, tid, s2.s);                    // layer 2
         const float c2 = s2.rs * rsw2 * (sa.rs * rswa);
-        const H2Scale s3 = h2_scale(__builtin_fmaf(h2_rowmax<false>(x), c2, b2pos));
+        const H2Scale s3 = h2_scale(__builtin_fmaf(h2_rowmax<false, true>(x), c2, b2pos));
         zero_frag<NT>(acc);
         hs_layer_ring<3, 2, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, s3.s, c2, tb + T_B2 * L + 4 * h);   // layer 3
         PHASE_FENCE();
@@ -1718,5 +1710,46 @@ hipError_t launch_project_split(const NodeArgs& a, const LaunchCfg& lc, hipStrea
 }
 
 int split_prow_block() { return MGN_PROW_BLOCK; }
+
+// ---- tests: h2_rowmax + h2_scale on their own (mgn_debug_rowmax) ----------------------------------------------------------------------
+// One wave per 32 rows of 128 floats, loaded row-major into the kernels' fragment layout (lane (c, h): pieces 2 m + h of row c); rows past
+// nrows are zeros and write nothing.  Both halves of a row must hold the same maximum: the lower one writes it, the upper one the
+// scale pair made from its own copy, so the exchange is checked in both directions.
+template <bool ABS>
+__global__ __launch_bounds__(64) void k_debug_rowmax(const float* rows, int nrows, float* amax, float* s, float* rs) {
+    constexpr int NT = 4, L = 128;
+    const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+    const int row = (int)blockIdx.x * TILE + c;
+    f32x16 x[NT];
+    zero_frag<NT>(x);
+    if (row < nrows) load_frag<NT>(x, row_ptr(rows, row, L, h), STRIDE_ROW);
+    const float m = h2_rowmax<ABS>(x);
+    const H2Scale sc = h2_scale(m);
+    if (row < nrows) {
+        if (h == 0) amax[row] = m;
+        else s[row] = sc.s, rs[row] = sc.rs;
+    }
+}
+// host arrays in and out; the launch's error (hipSuccess: the three arrays are filled)
+hipError_t debug_rowmax(const float* rows, int nrows, int abs, float* amax, float* s, float* rs) {
+    float* d = nullptr;
+    const size_t nin = (size_t)nrows * 128, nout = (size_t)nrows;
+    hipError_t e = hipMalloc(&d, (nin + 3 * nout) * sizeof(float));
+    if (e != hipSuccess) return e;
+    float* o = d + nin;
+    e = hipMemcpy(d, rows, nin * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((nrows + TILE - 1) / TILE));
+        if (abs) hipLaunchKernelGGL(k_debug_rowmax<true>, grid, dim3(64), 0, 0, d, nrows, o, o + nout, o + 2 * nout);
+        else hipLaunchKernelGGL(k_debug_rowmax<false>, grid, dim3(64), 0, 0, d, nrows, o, o + nout, o + 2 * nout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(amax, o, nout * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(s, o + nout, nout * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(rs, o + 2 * nout, nout * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return e;
+}
 
 }  // namespace mgn

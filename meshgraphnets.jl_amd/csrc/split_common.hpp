@@ -89,19 +89,43 @@ DEVINL void h2_split_pair(unsigned& hi, unsigned& lo, float v0, float v1, float 
     hi = h;
     lo = l;
 }
-// largest |x| (ABS) or largest x, at least 0 (!ABS: what survives a ReLU) of a lane's 64 values and of its row's other half
-template <bool ABS>
+// largest |x| (ABS) or largest x, at least 0 (!ABS: what survives a ReLU) of a lane's 64 values and of its row's other half.
+// 32 v_max3_f32 (two new values per instruction, |.| as source modifiers) + the half exchange + one v_max_f32.  Written as instructions
+// because fmaxf costs more than it shows: hipcc quiets signalling NaNs ahead of every fmaxf whose input comes from a load or an MFMA
+// (`v_max_f32 v, x, x` / `v_max_f32 v, |x|, |x|` per value: 112 instructions per call) and pairs the maxima before it folds them (48
+// where the inputs are FMA results).  Non-volatile and tied to its registers like h2_split_pair: the scheduler may move it.
+// Every non-NaN input gives what fmaxf gave (maxima are exact; +-0, subnormals and infinities included; the running value starts at 0).
+// NaN: v_max3_f32 drops a quiet NaN operand like fmaxf, so a row of quiet NaNs still gives the maximum of its other values (0 if it has
+// none); a SIGNALLING NaN is no longer quieted first and comes out as a quiet NaN (h2_scale then sees exponent 255).  No arithmetic
+// instruction produces one; only a latent array that already holds one can bring it here.
+// RAW: x holds the raw results of the MFMA chain just ahead.  hipcc's hazard recogniser does not look into inline asm, so the wait states
+// between an 8-pass MFMA's write and a vector read of its result (11) are supplied here, tied to all four blocks (cf. mfma_chain_end).
+// One asm statement per block of sixteen values: between two DEPENDENT asm statements hipcc puts an `s_nop 0` of its own (it must assume
+// that the first one wrote its result with a destination select).
+#define H2_MAX3_8(A, M0)                                                                                                              \
+    "v_max3_f32 %0, " M0 ", " A "%1" A ", " A "%2" A "\n\tv_max3_f32 %0, %0, " A "%3" A ", " A "%4" A "\n\t"                                \
+    "v_max3_f32 %0, %0, " A "%5" A ", " A "%6" A "\n\tv_max3_f32 %0, %0, " A "%7" A ", " A "%8" A "\n\t"                                   \
+    "v_max3_f32 %0, %0, " A "%9" A ", " A "%10" A "\n\tv_max3_f32 %0, %0, " A "%11" A ", " A "%12" A "\n\t"                                \
+    "v_max3_f32 %0, %0, " A "%13" A ", " A "%14" A "\n\tv_max3_f32 %0, %0, " A "%15" A ", " A "%16" A
+#define H2_MAX3_IN(X)                                                                                                                 \
+    "v"(X[0]), "v"(X[1]), "v"(X[2]), "v"(X[3]), "v"(X[4]), "v"(X[5]), "v"(X[6]), "v"(X[7]), "v"(X[8]), "v"(X[9]), "v"(X[10]), "v"(X[11]),   \
+        "v"(X[12]), "v"(X[13]), "v"(X[14]), "v"(X[15])
+template <bool ABS, bool RAW = false>
 DEVINL float h2_rowmax(const f32x16 (&x)[4]) {
-    float m = 0.f;
+    static_assert(!(ABS && RAW), "accumulators are read raw only where a ReLU follows");
+    float m;                                                          // (the running value starts as the inline constant 0)
+    if constexpr (RAW) asm("s_nop 7\n\ts_nop 3\n\t" H2_MAX3_8("", "0") : "=&v"(m) : H2_MAX3_IN(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]));
+    else if constexpr (ABS) asm(H2_MAX3_8("|", "0") : "=&v"(m) : H2_MAX3_IN(x[0]));
+    else asm(H2_MAX3_8("", "0") : "=&v"(m) : H2_MAX3_IN(x[0]));
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int k = 0; k < 16; k += 2) {
-            const float a = ABS ? __builtin_fabsf(x[t][k]) : x[t][k], b = ABS ? __builtin_fabsf(x[t][k + 1]) : x[t][k + 1];
-            m = __builtin_fmaxf(m, __builtin_fmaxf(a, b));
-        }
-    return __builtin_fmaxf(m, __shfl_xor(m, 32, 64));
+    for (int t = 1; t < 4; ++t) {
+        if constexpr (ABS) asm(H2_MAX3_8("|", "%0") : "+v"(m) : H2_MAX3_IN(x[t]));
+        else asm(H2_MAX3_8("", "%0") : "+v"(m) : H2_MAX3_IN(x[t]));
+    }
+    return half_max(m);
 }
+#undef H2_MAX3_8
+#undef H2_MAX3_IN
 
 // Buffer descriptors (a wave-uniform 64-bit base in four scalar registers) + a 32-bit byte offset per lane + a scalar / immediate offset:
 // one address register per stream where 64-bit pointers cost a pair per 4 KiB of reach.  Used where registers are the limit.
