@@ -294,6 +294,46 @@ void shoot_release(mgn_engine* h);     // mgn_solve.cpp: drops mgn_shooting_grad
                              hipGetErrorString(_e), __FILE__, __LINE__);                             \
     } while (0)
 
+// The one place a launch sequence becomes a hipGraph: `launches` is issued under stream capture, the graph instantiated into `exec` and
+// launched.  A stream that cannot be captured, a failed capture or a failed instantiation leave exec null and turn graph replay off
+// for the handle (use_graph = 0: eager from here on); the sequence's own error is returned, otherwise it runs eagerly.
+template <typename F>
+int capture_and_launch(mgn_engine* h, hipStream_t st, hipGraphExec_t& exec, F&& launches) {
+    exec = nullptr;
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+        (void)hipGetLastError();
+        h->use_graph = 0;
+        return launches();
+    }
+    hipGraph_t graph = nullptr;
+    const int rc = launches();
+    const bool ok = hipStreamEndCapture(st, &graph) == hipSuccess && rc == MGN_OK && graph &&
+                    hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!ok) {
+        exec = nullptr;
+        h->use_graph = 0;
+        return rc != MGN_OK ? rc : launches();
+    }
+    HIPCHK(h, hipGraphLaunch(exec, st));
+    return MGN_OK;
+}
+// Small meshes: a launch sequence over buffers with fixed addresses runs eagerly once (per-kernel attributes are set outside of any
+// capture), is captured on the next call and replayed afterwards.  graphable: the caller's size rule, with use_graph, no profiling and
+// a stream other than the legacy NULL stream (mgn_set_stream(h, NULL)), which cannot be captured.
+template <typename F>
+int run_graphed(mgn_engine* h, hipStream_t st, bool graphable, hipGraphExec_t& exec, bool& warm, F&& launches) {
+    if (graphable && exec) {
+        HIPCHK(h, hipGraphLaunch(exec, st));
+        return MGN_OK;
+    }
+    if (!graphable || !warm) {
+        warm = true;
+        return launches();
+    }
+    return capture_and_launch(h, st, exec, launches);
+}
+
 }  // namespace mgn
 
 // No C++ exception crosses the C ABI (a Julia or C host would see std::terminate): every entry point is a function-try-block.

@@ -351,39 +351,9 @@ void drop_graph(mgn_engine* h) {
     h->graph_warm = -1;
 }
 
-// Small meshes: a launch sequence over buffers with fixed addresses runs eagerly once (per-kernel attributes are set outside
-// of any capture), is captured on the next call and replayed afterwards.
-template <typename F>
-int run_graphed(mgn_engine* h, hipGraphExec_t& exec, bool& warm, F&& launches) {
-    // (the legacy NULL stream -- mgn_set_stream(h, NULL) -- cannot be captured: eager there)
-    const bool graphable = h->use_graph && !h->prof && h->stream != nullptr && launch_is_small(h->ntiles_n);
-    if (graphable && exec) {
-        HIPCHK(h, hipGraphLaunch(exec, h->stream));
-        return MGN_OK;
-    }
-    if (!graphable || !warm) {
-        warm = true;
-        return launches();
-    }
-    hipGraph_t graph = nullptr;
-    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        h->use_graph = 0;               // a stream that cannot be captured: eager from here on
-        return launches();
-    }
-    const int rc = launches();
-    const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-    if (rc != MGN_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        exec = nullptr;
-        h->use_graph = 0;               // eager from here on
-        if (rc != MGN_OK) return rc;
-        return launches();
-    }
-    (void)hipGraphDestroy(graph);
-    HIPCHK(h, hipGraphLaunch(exec, h->stream));
-    return MGN_OK;
-}
+// run_graphed's size rule for mgn_forward and the resident right-hand sides: launch-bound (small) passes on a capturable stream
+// (the legacy NULL stream -- mgn_set_stream(h, NULL) -- cannot be captured: eager there)
+bool small_graphable(const mgn_engine* h) { return h->use_graph && !h->prof && h->stream != nullptr && launch_is_small(h->ntiles_n); }
 
 // 16-row cooperative tiles (v_mfma_f32_16x16x4_f32): both kernels of a processor step must agree (the carry rows are per 16-edge
 // tile then), so the choice is made per handle and graph: fp32, L = 128, hidden_layers = 2, and the node launch and EVERY edge
@@ -1538,7 +1508,7 @@ int mgn_forward(mgn_handle* h, const float* nf, const float* ef, float* out) try
         if (int rc = run_processor(h, h->cfg.mps)) return rc;
         return decode_impl(h, false);
     };
-    if (int rc = run_graphed(h, h->fwd_exec, h->fwd_warm, launches)) return rc;
+    if (int rc = run_graphed(h, h->stream, small_graphable(h), h->fwd_exec, h->fwd_warm, launches)) return rc;
     return mgn_fwd_download(h, out);
 } MGN_CATCH(h)
 
@@ -1596,7 +1566,7 @@ static int lnall_ode_step(mgn_handle* h, const float* x, const float* onehot, co
             h->lnall_edges = true;
         } else {                      // afterwards the ~130 launches of a right-hand side replay from one launch graph (small meshes)
             auto launches = [&]() -> int { return lnall_rhs_dev(h, h->d_nfA.as<float>(), h->d_out.as<float>(), true); };
-            if (int rc = run_graphed(h, h->rhs_exec, h->rhs_warm, launches)) return rc;
+            if (int rc = run_graphed(h, h->stream, small_graphable(h), h->rhs_exec, h->rhs_warm, launches)) return rc;
         }
         return mgn_fwd_download(h, dxdt);
     }
@@ -1653,7 +1623,7 @@ int mgn_ode_step(mgn_handle* h, const float* x, const float* onehot, const float
             if (int rc = launches()) return rc;
             return gather_rows_global(h, h->d_out.as<float>(), c.O, dxdt);
         }
-        if (int rc = run_graphed(h, h->rhs_exec, h->rhs_warm, launches)) return rc;
+        if (int rc = run_graphed(h, h->stream, small_graphable(h), h->rhs_exec, h->rhs_warm, launches)) return rc;
         return mgn_fwd_download(h, dxdt);
     }
     if (!ef_raw || (c.Fn > c.O && !onehot)) return fail(h, MGN_E_ARG, "mgn_ode_step: null argument");
@@ -1987,32 +1957,10 @@ int mgn_processor_steps_dev(mgn_handle* h, int32_t nsteps) try {
         return processor_pass(h, nsteps);
     }
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    h->graph_exec = nullptr;
     h->graph_nsteps = -1;
-    hipGraph_t graph = nullptr;
-    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        h->use_graph = 0;
-        return processor_pass(h, nsteps);
-    }
-    const int rc = processor_pass(h, nsteps);
-    const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-    if (rc != MGN_OK || ce != hipSuccess || !graph) {
-        if (graph) (void)hipGraphDestroy(graph);
-        h->use_graph = 0;                       // fall back to eager launches for good
-        if (rc != MGN_OK) return rc;
-        return processor_pass(h, nsteps);
-    }
-    const hipError_t ie = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-        h->graph_exec = nullptr;
-        h->use_graph = 0;
-        return processor_pass(h, nsteps);
-    }
-    h->graph_nsteps = nsteps;
-    HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
-    return MGN_OK;
+    const int rc = capture_and_launch(h, h->stream, h->graph_exec, [&]() -> int { return processor_pass(h, nsteps); });
+    if (h->graph_exec) h->graph_nsteps = nsteps;
+    return rc;
 } MGN_CATCH(h)
 
 int mgn_processor_steps(mgn_handle* h, float* v, float* e, int32_t nsteps) try {

@@ -191,25 +191,10 @@ struct Rollout {
                 HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
                 return MGN_OK;
             }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            h->use_graph = 0;
-            return rhs_launches(x, kout);
-        }
-        const int rc = rhs_launches(x, kout);
-        const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
         hipGraphExec_t exec = nullptr;
-        if (rc != MGN_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            h->use_graph = 0;              // eager from here on
-            if (rc != MGN_OK) return rc;
-            return rhs_launches(x, kout);
-        }
-        (void)hipGraphDestroy(graph);
-        graphs.push_back({x, kout, exec});
-        HIPCHK(h, hipGraphLaunch(exec, h->stream));
-        return MGN_OK;
+        const int rc = capture_and_launch(h, h->stream, exec, [&]() -> int { return rhs_launches(x, kout); });
+        if (exec) graphs.push_back({x, kout, exec});
+        return rc;
     }
     ~Rollout() {
         for (RhsGraph& g : graphs) (void)hipGraphExecDestroy(g.exec);

@@ -498,8 +498,12 @@ using namespace mgn;
 
 namespace {
 
+// The four kinds of job that differentiate the model: step! (mgn_step), the pullback of the model call (mgn_forward_vjp), of the right-hand
+// side (mgn_ode_vjp), and one step of a reverse sweep (mgn_solver_grad and its kin: the right-hand side's, on resident inputs)
+enum JobKind { JOB_STEP, JOB_FORWARD_VJP, JOB_RHS_VJP, JOB_SWEEP_STEP };
+
 struct TrainJob {
-    bool vjp = false;
+    JobKind kind = JOB_STEP;
     // step!: the FeatureGraph as given, target, mask
     const float* nf = nullptr; const float* ef = nullptr; const float* target = nullptr;
     const int32_t* mask = nullptr; int64_t nmask = 0; int32_t mask_index_base = 0;
@@ -509,11 +513,10 @@ struct TrainJob {
     float* dxdt = nullptr; float* xbar = nullptr;
     float* grads = nullptr;
     // vjp of the model itself (mgn_forward_vjp): nf / ef as in step!, cotangent `lambda` of the output, gradient of all of nf out
-    bool fvjp = false;
     float* nfbar = nullptr; float* out = nullptr;
-    // one step of the reverse sweep of mgn_solver_grad (with vjp): x is a device slot in the engine's order, lambda is already in its io slot
-    // and the statics in theirs (solver_sweep staged them); xbar stays in io, the gradient is added to gacc (first: gacc = it), no synchronisation
-    bool sweep = false, first = false;
+    // one step of the reverse sweep of mgn_solver_grad: x is a device slot in the engine's order, lambda is already in its io slot
+    // and the statics in theirs (Sweep::begin staged them); xbar stays in io, the gradient is added to gacc (first: gacc = it), no synchronisation
+    bool first = false;
     double* gacc = nullptr;
 };
 
@@ -539,64 +542,174 @@ int train_prepare(mgn_handle* h, const char* who, size_t n_grads, bool partition
     return MGN_OK;
 }
 
-// forward with kept activations, seed, reverse pass, all parameter gradients (+ the input gradient for the VJP)
-int train_run(mgn_handle* h, const TrainJob& J) {
-    const mgn_config& c = h->cfg;
-    TrainState& T = *h->train;
-    const LocalGraph& g = h->g;
-    const int S = h->nsets;
-    // a partition (train_prepare: mgn_step alone, one edge set): N owned rows, then the halo rows; the caller's arrays are the whole mesh's
-    const bool part = c.nranks > 1;
-    const int64_t N = g.n_own, NT = N + g.n_halo, NG = part ? g.N : N;
-    const int L = c.L, mps = c.mps, O = c.O;
-    hipStream_t st = h->stream;
-    float* A = T.arena.as<float>();
-    const float* Wt = T.w.as<float>();
-    struct SetIdx { int64_t E; int32_t nt; const int32_t *egid, *perm_s, *rowptr_s, *snd, *rcv, *rowptr; } sx[MAX_EDGE_SETS] = {};
-    for (int q = 0; q < S; ++q) {
-        sx[q].E = g.set[q].e_local;
-        sx[q].nt = (int32_t)((sx[q].E + TILE - 1) / TILE);
-        sx[q].egid = T.idx.as<int32_t>() + T.i_egid[q];
-        sx[q].perm_s = T.idx.as<int32_t>() + T.i_perm[q];
-        sx[q].rowptr_s = T.idx.as<int32_t>() + T.i_rowptr_s[q];
-        sx[q].snd = h->es[q].d_snd.as<int32_t>();
-        sx[q].rcv = h->es[q].d_rcv.as<int32_t>();
-        sx[q].rowptr = h->es[q].d_rowptr.as<int32_t>();
+// The first launch unit's inputs of an MLP forward: rows / ntiles and up to three blocks of rows, gathered where an index is given
+TrainFwdArgs fwd_inputs(int64_t rows, int32_t ntiles, const float* x0, const int32_t* i0 = nullptr, const float* x1 = nullptr,
+                        const int32_t* i1 = nullptr, const float* x2 = nullptr) {
+    TrainFwdArgs a{};
+    a.rows = rows; a.ntiles = ntiles;
+    a.X[0] = x0; a.xidx[0] = i0; a.X[1] = x1; a.xidx[1] = i1; a.X[2] = x2;
+    return a;
+}
+// One MLP forward = one or two launch units (TrainPass::run_fwd, LnAll::mlp).  What unit bi's launch takes from the MLP itself: `in` carries
+// rows / ntiles and the first unit's inputs (X, xidx, PRE, preidx); w1sel >= 0: only block w1sel of W1 is applied per row (the factored
+// edge MLP: the e block); the second unit reads the first one's output `chained` (its Y: no LayerNorm, no residual).  Where the
+// activations and the output go is the caller's.  Returns the launch's layer-1 input blocks.
+int fwd_unit(const TrainMlp& m, int bi, const TrainFwdArgs& in, int w1sel, const float* Wt, const float* chained, TrainFwdArgs& a) {
+    const TrainBlock& b = m.b[bi];
+    a = TrainFwdArgs{};
+    a.rows = in.rows; a.ntiles = in.ntiles;
+    a.W2 = Wt + b.W2; a.W3 = Wt + b.W3; a.tabs = Wt + b.tabs;
+    if (bi > 0) {
+        a.X[0] = chained;
+        a.W1[0] = Wt + b.W1[0];
+        return b.nin;
     }
-    const int32_t nt_n = (int32_t)((N + TILE - 1) / TILE), nt_t = (int32_t)((NT + TILE - 1) / TILE);
-    float* G = part ? T.fin_s.as<float>() + RANK_SUM_HEAD : T.grads.as<float>();   // (a partition's gradient is its term of the finish)
+    for (int j = 0; j < 3; ++j) { a.X[j] = in.X[j]; a.xidx[j] = in.xidx[j]; }
+    for (int j = 0; j < 2; ++j) { a.PRE[j] = in.PRE[j]; a.preidx[j] = in.preidx[j]; }
+    if (w1sel >= 0) { a.W1[0] = Wt + b.W1[w1sel]; return 1; }
+    for (int j = 0; j < b.nin; ++j) a.W1[j] = Wt + b.W1[j];
+    return b.nin;
+}
 
-    // ---- inputs
-    const float* nrm = h->norms.as<float>();   // [node scale, shift (Fn) | edge scale, shift (Fe) | out scale, shift (O)]
+// What the backward of one launch unit reads and leaves besides its block and its kept activations: the upstream gradient g0[row]
+// (+ g1[g1i[row]]); per layer-1 input block j the gradient gx[j] = (gxadd[j]) + GZ1 W1T[j] (null: not wanted) and the input xin[j], gathered by
+// xi[j], that the block's weight gradient takes.
+// fq >= 0: first unit of the edge MLP of set fq with the factored first layer -- only the e block of W1 is unwound per edge
+// (gx[0] / gxadd[0] / xin[0] describe it); the v blocks follow per node from the summed rows of GZ1 (SGs, SGr) and the node latents vin.
+struct BwdIo {
+    const float* g0 = nullptr; const float* g1 = nullptr; const int32_t* g1i = nullptr;
+    float* gx[3] = {}; const float* gxadd[3] = {};
+    const float* xin[3] = {}; const int32_t* xi[3] = {};
+    int fq = -1; const float* vin = nullptr;
+};
+
+struct TrainPass;
+// one launch unit as the weight-gradient queue sees it, after its activation backward has been issued into gradient-buffer set gs
+struct WgradUnit {
+    const TrainBlock& b; const BwdIo& io;
+    const size_t* hb;            // its kept H1, H2, Y
+    int64_t rows, node_rows; int32_t ntiles; int gs;
+    bool wide, lnsum, lnjob;     // how its LayerNorm parameters get their sums (TrainPass::bwd_unit)
+};
+
+// The weight-gradient launches of one reverse pass.
+// The parameter gradients of unit i (k_wgrad + k_reduce_partials: they only read what k_mlp_bwd left in gradient-buffer
+// set i % gsets and the kept activations) run on a second stream beside the activation backward of the next units.  Not in
+// recompute mode (there the kept activations are shared buffers which the next step's recomputation overwrites) and not
+// on large meshes, which fill the chip on their own (prepare_graph).  MGN_TRAIN_OVERLAP = 0 keeps everything on one stream.
+// Small meshes: the weight-gradient jobs of `group` consecutive launch units go out as ONE k_wgrad + ONE k_reduce_partials launch on the
+// second stream (two groups of gradient-buffer sets in flight).  Per unit they were 66 launches per processor step!, each a
+// cross-stream dependency both ways: the main stream's backward kernels started ~10 us apart (rocprofv3 timeline, docs/experiments.md)
+// and the second stream was the critical path.  Same partial blocks (128 rows), same order of the reduction: the same bits.
+// The reverse pass is issued twice per handle -- eagerly, then under stream capture -- and both must issue the same launches: all
+// state that the batching carries from unit to unit is here, and reset() is the one place that sets it.
+struct WgradQueue {
+    WgradBatch pwb; ReduceBatch prb;     // the launch being filled, its jobs' reductions
+    int pnw, punits;                     // ... its partial-dW regions taken, the units in it
+    int64_t plrows;                      // ... the rows it covers
+    int nbatch;                          // launches issued (their events are indexed by it)
+    std::vector<ReduceJob> deferred;     // (T.defer_reduce) the reductions of all units, launched behind the last weight-gradient launch
+    int unit_no, n_bwd;                  // units that took deferred slots; activation backwards issued
+    int set_batch[TrainState::GSETS_MAX];   // launch number that takes the weight gradients of the unit in each buffer set
+
+    void new_batch() { pwb = WgradBatch{}; prb = ReduceBatch{}; pnw = punits = 0; plrows = 0; }
+    void reset() {
+        new_batch();
+        nbatch = unit_no = n_bwd = 0;
+        deferred.clear();
+        for (int& v : set_batch) v = -1;
+    }
+    int acquire(TrainPass& P, int& gs);              // the buffer set of the next activation backward, free to be written
+    int add_unit(TrainPass& P, const WgradUnit& u);  // every parameter gradient of a unit joins the launch being filled
+    int flush(TrainPass& P);
+    int drain(TrainPass& P);                         // end of the pass: what is left, the deferred reductions, the join
+};
+
+// One pass of the model and its pullback over the training arena: forward with kept activations, seed, reverse pass, all parameter
+// gradients (+ the input gradient for the VJPs).  Built per call from the handle and the job; train_run below is the sequence of its stages.
+struct TrainPass {
+    struct SetIdx { int64_t E; int32_t nt; const int32_t *egid, *perm_s, *rowptr_s, *snd, *rcv, *rowptr; };
+    mgn_engine* h;
+    const TrainJob& J;
+    const mgn_config& c;
+    TrainState& T;
+    const LocalGraph& g;
+    const int S, L, mps, O;
+    // a partition (train_prepare: mgn_step alone, one edge set): N owned rows, then the halo rows; the caller's arrays are the whole mesh's
+    const bool part;
+    const int64_t N, NT, NG;
+    const int32_t nt_n, nt_t;
+    hipStream_t st;
+    float* A;
+    const float* Wt;
+    SetIdx sx[MAX_EDGE_SETS] = {};
+    float* G;                    // the gradient of this pass (a partition's is its term of the finish)
+    const float* nrm;            // [node scale, shift (Fn) | edge scale, shift (Fe) | out scale, shift (O)]
     // A renumbered graph (graph_host.h: the engine's node order is not the caller's): per-node inputs are brought into the engine's
     // order as they arrive and per-node results go back through the inverse; `mask` is mapped on the host.  Edges go by edge_gid already.
-    const bool renum = g.renumbered || part;   // (a partition's rows are the rows it owns, wherever they lie in the caller's arrays)
-    const int32_t* ngid = h->d_own_gid.as<int32_t>();
-    auto to_local = [&](float* buf, int width) -> hipError_t {            // buf [N][width]: caller's order -> engine's, in place
+    const bool renum;            // (a partition's rows are the rows it owns, wherever they lie in the caller's arrays)
+    const int32_t* ngid;
+    const int32_t *acc_row, *acc_ptr, *acc_pos;   // the owners' side of the reverse halo exchange (prepare_graph)
+    // ln_dims = MGN_LN_ALL: every LayerNorm takes its statistics over the whole rows x L output of its MLP (DESIGN.md section 2): the MLP
+    // kernels run without their row-wise LayerNorm; two reductions and an elementwise pass follow them in both directions
+    const bool lnall;
+    const float ln_eps_in, ln_eps_out;
+    const bool overlap;          // weight gradients on the second stream (WgradQueue)
+    int group = 1;               // launch units per weight-gradient launch
+    int64_t lrows_all;           // the longest job of the model: what a group's launch covers
+    int nlb = 0;                 // partial sums of the loss (seed -> results)
+    WgradQueue wq;
+
+    TrainPass(mgn_engine* h_, const TrainJob& J_)
+        : h(h_), J(J_), c(h_->cfg), T(*h_->train), g(h_->g), S(h_->nsets), L(c.L), mps(c.mps), O(c.O), part(c.nranks > 1), N(g.n_own),
+          NT(N + g.n_halo), NG(part ? g.N : N), nt_n((int32_t)((N + TILE - 1) / TILE)), nt_t((int32_t)((NT + TILE - 1) / TILE)), st(h_->stream),
+          A(T.arena.as<float>()), Wt(T.w.as<float>()), G(part ? T.fin_s.as<float>() + RANK_SUM_HEAD : T.grads.as<float>()),
+          nrm(h_->norms.as<float>()), renum(g.renumbered || part), ngid(h_->d_own_gid.as<int32_t>()),
+          acc_row(T.idx.as<int32_t>() + T.i_acc_row), acc_ptr(T.idx.as<int32_t>() + T.i_acc_ptr), acc_pos(T.idx.as<int32_t>() + T.i_acc_pos),
+          lnall(c.ln_dims == MGN_LN_ALL), ln_eps_in(c.ln_mode == MGN_LN_STD_EPS ? 0.f : 1e-5f), ln_eps_out(c.ln_mode == MGN_LN_STD_EPS ? 1e-5f : 0.f),
+          overlap(T.gsets > 1), lrows_all(N) {
+        for (int q = 0; q < S; ++q) {
+            sx[q].E = g.set[q].e_local;
+            sx[q].nt = (int32_t)((sx[q].E + TILE - 1) / TILE);
+            sx[q].egid = T.idx.as<int32_t>() + T.i_egid[q];
+            sx[q].perm_s = T.idx.as<int32_t>() + T.i_perm[q];
+            sx[q].rowptr_s = T.idx.as<int32_t>() + T.i_rowptr_s[q];
+            sx[q].snd = h->es[q].d_snd.as<int32_t>();
+            sx[q].rcv = h->es[q].d_rcv.as<int32_t>();
+            sx[q].rowptr = h->es[q].d_rowptr.as<int32_t>();
+            lrows_all = std::max<int64_t>(lrows_all, sx[q].E);
+        }
+        static const int group_env = [] { const char* e = getenv("MGN_TRAIN_WG_GROUP"); return e ? atoi(e) : 1; }();
+        if (overlap) group = std::max(1, std::min(group_env, T.gsets / 2));
+    }
+    bool vjp() const { return J.kind != JOB_STEP; }
+    float* io() const { return A + T.io; }    // the VJPs' rows: x [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N]
+    int comm_fail(const char* what) { return fail(h, MGN_E_RCCL, "mgn_step: %s: %s", what, h->comm->err.c_str()); }
+
+    // ---- inputs
+    hipError_t permute(float* buf, int width, bool inverse) {
         if (!renum || width <= 0) return hipSuccess;
-        if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, false, st)) return e;
+        if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, inverse, st)) return e;
         return hipMemcpyAsync(buf, A + T.ptmp, (size_t)N * width * 4, hipMemcpyDeviceToDevice, st);
-    };
-    auto to_global = [&](float* buf, int width) -> hipError_t {           // ... and back
-        if (!renum || width <= 0) return hipSuccess;
-        if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, true, st)) return e;
-        return hipMemcpyAsync(buf, A + T.ptmp, (size_t)N * width * 4, hipMemcpyDeviceToDevice, st);
-    };
+    }
+    hipError_t to_local(float* buf, int width) { return permute(buf, width, false); }    // buf [N][width]: caller's order -> engine's, in place
+    hipError_t to_global(float* buf, int width) { return permute(buf, width, true); }    // ... and back
     // An array the caller keeps on the device is read where it is; a host array is staged first.  Gather (renumbered graph) and padding
     // run in the one kernel that reads it (as copy + permute + copy back + pad the eager prologue of a step was 14 launches, 0.24 ms on
     // the cylinder mesh).
-    auto on_device = [&](const void* ptr) {
+    static bool on_device(const void* ptr) {
         hipPointerAttribute_t at{};
         const bool dev = ptr && hipPointerGetAttributes(&at, ptr) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
         (void)hipGetLastError();
         return dev;
-    };
-    auto staged = [&](const float* user, float* stage, size_t floats, const float*& out) -> hipError_t {
+    }
+    hipError_t staged(const float* user, float* stage, size_t floats, const float*& out) {
         if (on_device(user)) { out = user; return hipSuccess; }
         out = stage;
         return hipMemcpyAsync(stage, user, floats * 4, hipMemcpyHostToDevice, st);
-    };
-    if (!J.vjp || J.fvjp) {
+    }
+    // step! and the model's VJP: the FeatureGraph's node and edge features as given
+    int stage_features() {
         const float* src = nullptr;
         HIPCHK(h, staged(J.nf, A + T.nf_raw, (size_t)NG * c.Fn, src));
         HIPCHK(h, launch_affine_pad_gather(src, c.Fn, nullptr, 0, nullptr, nullptr, renum ? ngid : nullptr, A + T.nf_pad, L, N, st));
@@ -607,103 +720,114 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             HIPCHK(h, staged(J.ef, A + T.ef_raw[0], (size_t)sx[0].E * c.Fe, src));
             HIPCHK(h, launch_affine_pad(src, c.Fe, nullptr, 0, nullptr, nullptr, A + T.ef_pad[0], L, sx[0].E, st));
         }
-        if (J.fvjp) {
-            HIPCHK(h, hipMemcpyAsync(A + T.io + (size_t)N * O, J.lambda, (size_t)N * O * 4, hipMemcpyDefault, st));
-            HIPCHK(h, to_local(A + T.io + (size_t)N * O, O));
+        return MGN_OK;
+    }
+    int stage_step() {
+        if (int rc = stage_features()) return rc;
+        if (renum) {
+            const float* src = nullptr;
+            HIPCHK(h, staged(J.target, A + T.ptmp, (size_t)NG * O, src));
+            HIPCHK(h, launch_permute_rows(T.target.as<float>(), src, ngid, N, O, false, st));
         } else {
-            if (renum) {
-                HIPCHK(h, staged(J.target, A + T.ptmp, (size_t)NG * O, src));
-                HIPCHK(h, launch_permute_rows(T.target.as<float>(), src, ngid, N, O, false, st));
-            } else {
-                HIPCHK(h, hipMemcpyAsync(T.target.p, J.target, (size_t)N * O * 4, hipMemcpyDefault, st));
-            }
-            // the mask of the previous call is usually this call's (one trajectory, one mask: reference src/MeshGraphNets.jl:352): uploaded once
-            const bool mask_dev = on_device(J.mask);
-            const bool same = !mask_dev && T.mask_valid && T.mask_base == J.mask_index_base && (int64_t)T.mask_seen.size() == J.nmask &&
-                              (J.nmask == 0 || memcmp(T.mask_seen.data(), J.mask, (size_t)J.nmask * 4) == 0);
-            if (!same) {
-                HIPCHK(h, T.mask.ensure((size_t)J.nmask * 4));
-                T.mask_valid = false;
-                if (renum) {                       // the caller's node ids -> engine rows (0-based from here on)
-                    std::vector<int32_t> host_mask;
-                    const int32_t* mk = J.mask;
-                    if (mask_dev) {
-                        host_mask.resize((size_t)J.nmask);
-                        HIPCHK(h, hipMemcpy(host_mask.data(), J.mask, (size_t)J.nmask * 4, hipMemcpyDeviceToHost));
-                        mk = host_mask.data();
-                    }
-                    T.mask_host.clear();
-                    for (int64_t i = 0; i < J.nmask; ++i) {
-                        const int32_t l = T.g2l[(size_t)(mk[i] - J.mask_index_base)];
-                        if (l >= 0) T.mask_host.push_back(l);       // (a partition takes the entries it owns, as often as they are listed)
-                    }
-                    T.mask_n = (int64_t)T.mask_host.size();
-                    HIPCHK(h, hipMemcpyAsync(T.mask.p, T.mask_host.data(), (size_t)T.mask_n * 4, hipMemcpyHostToDevice, st));
-                } else {
-                    T.mask_n = J.nmask;
-                    HIPCHK(h, hipMemcpyAsync(T.mask.p, J.mask, (size_t)J.nmask * 4, hipMemcpyDefault, st));
-                }
-                if (!mask_dev) {
-                    T.mask_seen.assign(J.mask, J.mask + J.nmask);
-                    T.mask_base = J.mask_index_base;
-                    T.mask_valid = true;
-                }
-            }
+            HIPCHK(h, hipMemcpyAsync(T.target.p, J.target, (size_t)N * O * 4, hipMemcpyDefault, st));
         }
-    } else if (J.sweep) {
-        // the state this step's RHS saw; one-hot node types, val_mask and the normalised edge features were staged once for the sweep
-        float* io = A + T.io;
-        HIPCHK(h, launch_affine_pad(J.x, O, io + (size_t)2 * N * O, c.Fn - O, h->have_nnorm ? nrm : nullptr, h->have_nnorm ? nrm + c.Fn : nullptr,
+        // the mask of the previous call is usually this call's (one trajectory, one mask: reference src/MeshGraphNets.jl:352): uploaded once
+        const bool mask_dev = on_device(J.mask);
+        const bool same = !mask_dev && T.mask_valid && T.mask_base == J.mask_index_base && (int64_t)T.mask_seen.size() == J.nmask &&
+                          (J.nmask == 0 || memcmp(T.mask_seen.data(), J.mask, (size_t)J.nmask * 4) == 0);
+        if (same) return MGN_OK;
+        HIPCHK(h, T.mask.ensure((size_t)J.nmask * 4));
+        T.mask_valid = false;
+        if (renum) {                       // the caller's node ids -> engine rows (0-based from here on)
+            std::vector<int32_t> host_mask;
+            const int32_t* mk = J.mask;
+            if (mask_dev) {
+                host_mask.resize((size_t)J.nmask);
+                HIPCHK(h, hipMemcpy(host_mask.data(), J.mask, (size_t)J.nmask * 4, hipMemcpyDeviceToHost));
+                mk = host_mask.data();
+            }
+            T.mask_host.clear();
+            for (int64_t i = 0; i < J.nmask; ++i) {
+                const int32_t l = T.g2l[(size_t)(mk[i] - J.mask_index_base)];
+                if (l >= 0) T.mask_host.push_back(l);       // (a partition takes the entries it owns, as often as they are listed)
+            }
+            T.mask_n = (int64_t)T.mask_host.size();
+            HIPCHK(h, hipMemcpyAsync(T.mask.p, T.mask_host.data(), (size_t)T.mask_n * 4, hipMemcpyHostToDevice, st));
+        } else {
+            T.mask_n = J.nmask;
+            HIPCHK(h, hipMemcpyAsync(T.mask.p, J.mask, (size_t)J.nmask * 4, hipMemcpyDefault, st));
+        }
+        if (!mask_dev) {
+            T.mask_seen.assign(J.mask, J.mask + J.nmask);
+            T.mask_base = J.mask_index_base;
+            T.mask_valid = true;
+        }
+        return MGN_OK;
+    }
+    int stage_forward_vjp() {
+        if (int rc = stage_features()) return rc;
+        HIPCHK(h, hipMemcpyAsync(io() + (size_t)N * O, J.lambda, (size_t)N * O * 4, hipMemcpyDefault, st));
+        HIPCHK(h, to_local(io() + (size_t)N * O, O));
+        return MGN_OK;
+    }
+    // RHS inputs exactly as mgn_ode_step takes them: nf = [n_norm(x); n_norm(onehot)], ef = e_norm(ef_raw).
+    // The padded node features from a state x [N][O] in the engine's order and the one-hot rows in io
+    int pad_state(const float* x) {
+        HIPCHK(h, launch_affine_pad(x, O, io() + (size_t)2 * N * O, c.Fn - O, h->have_nnorm ? nrm : nullptr, h->have_nnorm ? nrm + c.Fn : nullptr,
                                     A + T.nf_pad, L, N, st));
-    } else {
-        // RHS inputs exactly as mgn_ode_step takes them: nf = [n_norm(x); n_norm(onehot)], ef = e_norm(ef_raw)
-        float* io = A + T.io;                  // x [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N]
-        HIPCHK(h, hipMemcpyAsync(io, J.x, (size_t)N * O * 4, hipMemcpyDefault, st));
-        HIPCHK(h, hipMemcpyAsync(io + (size_t)N * O, J.lambda, (size_t)N * O * 4, hipMemcpyDefault, st));
-        if (c.Fn > O) HIPCHK(h, hipMemcpyAsync(io + (size_t)2 * N * O, J.onehot, (size_t)N * (c.Fn - O) * 4, hipMemcpyDefault, st));
-        if (J.val_mask) HIPCHK(h, hipMemcpyAsync(io + (size_t)N * (O + c.Fn), J.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
-        HIPCHK(h, to_local(io, O));
-        HIPCHK(h, to_local(io + (size_t)N * O, O));
-        if (c.Fn > O) HIPCHK(h, to_local(io + (size_t)2 * N * O, c.Fn - O));
-        if (J.val_mask) HIPCHK(h, to_local(io + (size_t)N * (O + c.Fn), 1));
-        HIPCHK(h, launch_affine_pad(io, O, io + (size_t)2 * N * O, c.Fn - O, h->have_nnorm ? nrm : nullptr, h->have_nnorm ? nrm + c.Fn : nullptr,
-                                    A + T.nf_pad, L, N, st));
+        return MGN_OK;
+    }
+    // The statics of a right-hand side -- one-hot node types and val_mask into io, the normalised raw edge features into ef_pad -- per call of
+    // mgn_ode_vjp, once per sweep (Sweep::begin: no state yet, x = null); the state's padding sits between them as the launches always ran
+    int stage_statics(const float* x) {
+        if (c.Fn > O) {
+            HIPCHK(h, hipMemcpyAsync(io() + (size_t)2 * N * O, J.onehot, (size_t)N * (c.Fn - O) * 4, hipMemcpyDefault, st));
+            HIPCHK(h, to_local(io() + (size_t)2 * N * O, c.Fn - O));
+        }
+        if (J.val_mask) {
+            HIPCHK(h, hipMemcpyAsync(io() + (size_t)N * (O + c.Fn), J.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
+            HIPCHK(h, to_local(io() + (size_t)N * (O + c.Fn), 1));
+        }
+        if (x) if (int rc = pad_state(x)) return rc;
         if (sx[0].E > 0) {
             HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], J.ef, (size_t)sx[0].E * c.Fe * 4, hipMemcpyDefault, st));
             HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
                                         h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, A + T.ef_pad[0], L, sx[0].E, st));
         }
+        return MGN_OK;
     }
-    // further edge sets: the features installed by mgn_set_edge_features, as given (the forward path does not normalise them either)
-    for (int q = 1; q < S; ++q)
-        if (sx[q].E > 0)
-            HIPCHK(h, launch_affine_pad(h->es[q].d_ef.as<float>(), h->es[q].Fe, nullptr, 0, nullptr, nullptr, A + T.ef_pad[q], L, sx[q].E, st));
+    int stage_rhs_vjp() {
+        HIPCHK(h, hipMemcpyAsync(io(), J.x, (size_t)N * O * 4, hipMemcpyDefault, st));
+        HIPCHK(h, hipMemcpyAsync(io() + (size_t)N * O, J.lambda, (size_t)N * O * 4, hipMemcpyDefault, st));
+        HIPCHK(h, to_local(io(), O));
+        HIPCHK(h, to_local(io() + (size_t)N * O, O));
+        return stage_statics(io());
+    }
+    int stage_inputs() {
+        int rc = MGN_OK;
+        switch (J.kind) {
+            case JOB_STEP: rc = stage_step(); break;
+            case JOB_FORWARD_VJP: rc = stage_forward_vjp(); break;
+            case JOB_RHS_VJP: rc = stage_rhs_vjp(); break;
+            // the state this step's RHS saw; one-hot node types, val_mask and the normalised edge features were staged once for the sweep
+            case JOB_SWEEP_STEP: rc = pad_state(J.x); break;
+        }
+        if (rc) return rc;
+        // further edge sets: the features installed by mgn_set_edge_features, as given (the forward path does not normalise them either)
+        for (int q = 1; q < S; ++q)
+            if (sx[q].E > 0)
+                HIPCHK(h, launch_affine_pad(h->es[q].d_ef.as<float>(), h->es[q].Fe, nullptr, 0, nullptr, nullptr, A + T.ef_pad[q], L, sx[q].E, st));
+        return MGN_OK;
+    }
 
-    // ln_dims = MGN_LN_ALL: every LayerNorm takes its statistics over the whole rows x L output of its MLP (DESIGN.md section 2): the MLP
-    // kernels run without their row-wise LayerNorm; two reductions and an elementwise pass follow them in both directions
-    const bool lnall = c.ln_dims == MGN_LN_ALL;
-    const float ln_eps_in = c.ln_mode == MGN_LN_STD_EPS ? 0.f : 1e-5f, ln_eps_out = c.ln_mode == MGN_LN_STD_EPS ? 1e-5f : 0.f;
-    // One MLP forward = one or two launch units.  `in` carries rows / ntiles and the first unit's inputs (X, xidx, PRE, preidx);
-    // w1sel >= 0: only block w1sel of W1 is applied per row (the factored edge MLP: the e block).
+    // ---- forward, keeping activations
     // keep = false: first pass of recompute mode -- H1 / H2 / Y are regenerated right before the backward, not stored here
-    auto run_fwd = [&](const TrainMlp& m, const TrainFwdArgs& in, int w1sel, const Acts& act, const float* resid, float* out, float* lnout,
-                       bool keep) -> hipError_t {
+    hipError_t run_fwd(const TrainMlp& m, const TrainFwdArgs& in, int w1sel, const Acts& act, const float* resid, float* out, float* lnout, bool keep) {
         for (int bi = 0; bi < m.nblk; ++bi) {
             const TrainBlock& b = m.b[bi];
             const bool last = bi == m.nblk - 1;
-            TrainFwdArgs a{};
-            a.rows = in.rows; a.ntiles = in.ntiles;
-            int nin = b.nin;
-            if (bi == 0) {
-                for (int j = 0; j < 3; ++j) { a.X[j] = in.X[j]; a.xidx[j] = in.xidx[j]; }
-                for (int j = 0; j < 2; ++j) { a.PRE[j] = in.PRE[j]; a.preidx[j] = in.preidx[j]; }
-                if (w1sel >= 0) { a.W1[0] = Wt + b.W1[w1sel]; nin = 1; }
-                else for (int j = 0; j < b.nin; ++j) a.W1[j] = Wt + b.W1[j];
-            } else {                                        // the second unit reads the first one's output (its Y: no LayerNorm, no residual)
-                a.X[0] = A + act.h[bi - 1][2];
-                a.W1[0] = Wt + b.W1[0];
-            }
-            a.W2 = Wt + b.W2; a.W3 = Wt + b.W3; a.tabs = Wt + b.tabs;
+            TrainFwdArgs a;
+            const int nin = fwd_unit(m, bi, in, w1sel, Wt, bi > 0 ? A + act.h[bi - 1][2] : nullptr, a);
             if (keep) { a.H1 = A + act.h[bi][0]; a.H2 = A + act.h[bi][1]; a.Y = A + act.h[bi][2]; }
             if (last) { a.resid = resid; a.OUT = out; a.LNOUT = lnout; a.SEG_RCV = in.SEG_RCV; a.SEG_AGG = in.SEG_AGG; a.SEG_CARRY = in.SEG_CARRY; }
             else if (!keep) a.OUT = A + act.h[bi][2];
@@ -722,219 +846,133 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             }
         }
         return hipSuccess;
-    };
-    auto fwd = [&](const TrainMlp& m, int64_t rows, int32_t ntiles, const float* x0, const int32_t* i0, const float* x1, const float* x2,
-                   const Acts& act, const float* resid, float* out, float* lnout, bool keep = true) {
-        TrainFwdArgs a{};
-        a.rows = rows; a.ntiles = ntiles;
-        a.X[0] = x0; a.X[1] = x1; a.X[2] = x2;
-        a.xidx[0] = i0;
-        return run_fwd(m, a, -1, act, resid, out, lnout, keep);
-    };
+    }
+    hipError_t fwd(const TrainMlp& m, const TrainFwdArgs& in, const Acts& act, const float* resid, float* out, float* lnout, bool keep = true) {
+        return run_fwd(m, in, -1, act, resid, out, lnout, keep);
+    }
     // edge MLP of step k, set q: [v_s; v_r; e] -> MLP + LayerNorm; with the factored first layer P[s] + Q[r] + e W1e
     // segagg != null: the launch aggregates e' itself (train.h: SEG_*; the caller follows up with launch_seg_fixup)
-    auto fwd_edge = [&](int q, int k, const float* resid, float* out, float* lnout, bool keep = true, float* segagg = nullptr) -> hipError_t {
+    hipError_t fwd_edge(int q, int k, const float* resid, float* out, float* lnout, bool keep = true, float* segagg = nullptr) {
         const TrainMlp& m = T.m_pe[q][k];
-        TrainFwdArgs a{};
-        a.rows = sx[q].E; a.ntiles = sx[q].nt;
+        const float* v = A + T.Vk[k];
+        TrainFwdArgs a = T.factored[q] ? fwd_inputs(sx[q].E, sx[q].nt, A + T.Ek[q][k]) : fwd_inputs(sx[q].E, sx[q].nt, v, sx[q].snd, v, sx[q].rcv, A + T.Ek[q][k]);
         if (segagg) { a.SEG_RCV = sx[q].rcv; a.SEG_AGG = segagg; a.SEG_CARRY = A + T.segcarry; }
-        if (!T.factored[q]) {
-            a.X[0] = A + T.Vk[k]; a.xidx[0] = sx[q].snd;
-            a.X[1] = A + T.Vk[k]; a.xidx[1] = sx[q].rcv;
-            a.X[2] = A + T.Ek[q][k];
-            return run_fwd(m, a, -1, T.a_pe[q][k], resid, out, lnout, keep);
-        }
+        if (!T.factored[q]) return run_fwd(m, a, -1, T.a_pe[q][k], resid, out, lnout, keep);
         Lin2Args p{};                     // (over the halo rows as well: local senders index them)
         p.rows = NT; p.ntiles = nt_t;
-        p.X0 = A + T.Vk[k]; p.W0 = Wt + m.b[0].W1[0]; p.W1 = Wt + m.b[0].W1[1];
+        p.X0 = v; p.W0 = Wt + m.b[0].W1[0]; p.W1 = Wt + m.b[0].W1[1];
         p.OUT0 = A + T.Pn; p.OUT1 = A + T.Qn;
         if (hipError_t e = launch_lin2(L, p, st)) return e;
-        a.X[0] = A + T.Ek[q][k];
         a.PRE[0] = A + T.Pn; a.preidx[0] = sx[q].snd; a.PRE[1] = A + T.Qn; a.preidx[1] = sx[q].rcv;
         return run_fwd(m, a, 2, T.a_pe[q][k], resid, out, lnout, keep);
-    };
-    auto fwd_node = [&](int k, const float* resid, float* out, bool keep = true) {
-        return fwd(T.m_pn[k], N, nt_n, A + T.Vk[k], nullptr, A + T.agg[0][k], S > 1 ? A + T.agg[1][k] : nullptr, T.a_pn[k], resid, out, nullptr, keep);
-    };
+    }
+    hipError_t fwd_node(int k, const float* resid, float* out, bool keep = true) {
+        return fwd(T.m_pn[k], fwd_inputs(N, nt_n, A + T.Vk[k], nullptr, A + T.agg[0][k], nullptr, S > 1 ? A + T.agg[1][k] : nullptr), T.a_pn[k], resid, out,
+                   nullptr, keep);
+    }
 
     // The halo exchange of the partitioned step, forward: the owned boundary rows of v go to the peers that list them as halo (packed by
     // the send index; the halo rows are one block behind the owned rows, in the order they arrive).  Reverse: the halo rows of the
     // gradient w.r.t. v go back over the same lists and the owner adds them to its own term (launch_halo_accumulate: a fixed order).
-    const int32_t* acc_row = T.idx.as<int32_t>() + T.i_acc_row;
-    const int32_t* acc_ptr = T.idx.as<int32_t>() + T.i_acc_ptr;
-    const int32_t* acc_pos = T.idx.as<int32_t>() + T.i_acc_pos;
-    auto comm_fail = [&](const char* what) { return fail(h, MGN_E_RCCL, "mgn_step: %s: %s", what, h->comm->err.c_str()); };
-    auto halo_forward = [&](float* v) -> int {
+    int halo_forward(float* v) {
         HIPCHK(h, launch_halo_pack(L, v, h->d_send_idx.as<int32_t>(), T.hx_send.as<float>(), (int64_t)g.send_idx.size(), st));
         if (h->comm->a2a_start(T.hx_send.p, T.hx_own_b.data(), T.hx_own_o.data(), T.hx_recv.p, T.hx_halo_b.data(), T.hx_halo_o.data(), st) != 0 ||
             h->comm->a2a_finish(st) != 0)
             return comm_fail("halo exchange");
         HIPCHK(h, launch_halo_unpack(L, T.hx_recv.as<float>(), v + (size_t)N * L, g.n_halo, st));
         return MGN_OK;
-    };
-    auto halo_reverse = [&](float* gv) -> int {
+    }
+    int halo_reverse(float* gv) {
         if (h->comm->a2a_start(gv + (size_t)N * L, T.hx_halo_b.data(), T.hx_halo_o.data(), T.hx_recv.p, T.hx_own_b.data(), T.hx_own_o.data(), st) != 0 ||
             h->comm->a2a_finish(st) != 0)
             return comm_fail("reverse halo exchange");
         HIPCHK(h, launch_halo_accumulate(L, T.hx_recv.as<float>(), acc_row, acc_ptr, acc_pos, gv, T.n_acc, st));
         return MGN_OK;
-    };
+    }
 
     // Small meshes replay both launch sequences from hipGraphs (everything they touch lives at fixed addresses in the arena;
     // the inputs, the seed of the reverse pass and the results stay outside).  The captured pointers are checked per call.
-    const bool graphable = h->use_graph && !h->prof && st != nullptr && T.gsets > 1;   // the NULL stream cannot be captured
-    if (T.exec_arena != T.arena.p || T.exec_w != T.w.p) {
+    void drop_stale_graphs() {
+        if (T.exec_arena == T.arena.p && T.exec_w == T.w.p) return;
         T.drop_graphs();
         T.exec_arena = T.arena.p;
         T.exec_w = T.w.p;
     }
-    auto graphed = [&](int slot, auto&& launches) -> int {
-        if (graphable && T.exec[slot]) {
-            HIPCHK(h, hipGraphLaunch(T.exec[slot], st));
-            return MGN_OK;
-        }
-        if (!graphable || !T.warm[slot]) {
-            T.warm[slot] = true;
-            return launches();
-        }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            h->use_graph = 0;
-            return launches();
-        }
-        const int rc = launches();
-        const hipError_t ce = hipStreamEndCapture(st, &graph);
-        if (rc != MGN_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&T.exec[slot], graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            T.exec[slot] = nullptr;
-            h->use_graph = 0;             // eager from here on
-            if (rc != MGN_OK) return rc;
-            return launches();
-        }
-        (void)hipGraphDestroy(graph);
-        HIPCHK(h, hipGraphLaunch(T.exec[slot], st));
-        return MGN_OK;
-    };
-
-    // ---- forward, keeping activations
-    auto forward_launches = [&]() -> int {
-    HIPCHK(h, fwd(T.m_en, N, nt_n, A + T.nf_pad, nullptr, nullptr, nullptr, T.a_en, nullptr, A + T.Vk[0], nullptr));
-    if (part) if (int rc = halo_forward(A + T.Vk[0])) return rc;
-    for (int q = 0; q < S; ++q)      // (a partition's ef_pad holds its local edges in the engine's order already)
-        HIPCHK(h, fwd(T.m_ee[q], sx[q].E, sx[q].nt, A + T.ef_pad[q], part ? nullptr : sx[q].egid, nullptr, nullptr, T.a_ee[q], nullptr, A + T.Ek[q][0], nullptr));
-    for (int k = 0; k < mps; ++k) {
-        for (int q = 0; q < S; ++q) {
-            if (!lnall && sx[q].E > 0 && train_fwd_fused_agg(L, sx[q].nt)) {   // aggregation inside the edge launch (large meshes)
-                HIPCHK(h, fwd_edge(q, k, A + T.Ek[q][k], A + T.Ek[q][k + 1], nullptr, T.kept(k, mps), A + T.agg[q][k]));
-                HIPCHK(h, launch_seg_fixup(L, sx[q].rowptr, A + T.segcarry, A + T.agg[q][k], (int32_t)N, st));
-                continue;
-            }
-            HIPCHK(h, fwd_edge(q, k, A + T.Ek[q][k], A + T.Ek[q][k + 1], A + T.Enew, T.kept(k, mps)));
-            HIPCHK(h, launch_segment_sum(L, A + T.Enew, sx[q].rowptr, nullptr, nullptr, A + T.agg[q][k], (int32_t)N, st));
-        }
-        HIPCHK(h, fwd_node(k, A + T.Vk[k], A + T.Vk[k + 1], T.kept(k, mps)));
-        if (part && k + 1 < mps) if (int rc = halo_forward(A + T.Vk[k + 1])) return rc;   // (the decoder reads owned rows only)
+    template <typename F> int graphed(int slot, F&& launches) {
+        const bool graphable = h->use_graph && !h->prof && st != nullptr && T.gsets > 1;   // the NULL stream cannot be captured
+        return run_graphed(h, st, graphable, T.exec[slot], T.warm[slot], launches);
     }
-    HIPCHK(h, fwd(T.m_de, N, nt_n, A + T.Vk[mps], nullptr, nullptr, nullptr, T.a_de, nullptr, nullptr, nullptr));
-    return MGN_OK;
-    };
-    if (int rc = graphed(0, forward_launches)) return rc;
-    const size_t y_out = T.a_de.h[T.m_de.nblk - 1][2];        // the decoder's output (its last unit's Y)
+
+    int forward() {
+        HIPCHK(h, fwd(T.m_en, fwd_inputs(N, nt_n, A + T.nf_pad), T.a_en, nullptr, A + T.Vk[0], nullptr));
+        if (part) if (int rc = halo_forward(A + T.Vk[0])) return rc;
+        for (int q = 0; q < S; ++q)      // (a partition's ef_pad holds its local edges in the engine's order already)
+            HIPCHK(h, fwd(T.m_ee[q], fwd_inputs(sx[q].E, sx[q].nt, A + T.ef_pad[q], part ? nullptr : sx[q].egid), T.a_ee[q], nullptr, A + T.Ek[q][0], nullptr));
+        for (int k = 0; k < mps; ++k) {
+            for (int q = 0; q < S; ++q) {
+                if (!lnall && sx[q].E > 0 && train_fwd_fused_agg(L, sx[q].nt)) {   // aggregation inside the edge launch (large meshes)
+                    HIPCHK(h, fwd_edge(q, k, A + T.Ek[q][k], A + T.Ek[q][k + 1], nullptr, T.kept(k, mps), A + T.agg[q][k]));
+                    HIPCHK(h, launch_seg_fixup(L, sx[q].rowptr, A + T.segcarry, A + T.agg[q][k], (int32_t)N, st));
+                    continue;
+                }
+                HIPCHK(h, fwd_edge(q, k, A + T.Ek[q][k], A + T.Ek[q][k + 1], A + T.Enew, T.kept(k, mps)));
+                HIPCHK(h, launch_segment_sum(L, A + T.Enew, sx[q].rowptr, nullptr, nullptr, A + T.agg[q][k], (int32_t)N, st));
+            }
+            HIPCHK(h, fwd_node(k, A + T.Vk[k], A + T.Vk[k + 1], T.kept(k, mps)));
+            if (part && k + 1 < mps) if (int rc = halo_forward(A + T.Vk[k + 1])) return rc;   // (the decoder reads owned rows only)
+        }
+        HIPCHK(h, fwd(T.m_de, fwd_inputs(N, nt_n, A + T.Vk[mps]), T.a_de, nullptr, nullptr, nullptr));
+        return MGN_OK;
+    }
 
     // ---- seed of the reverse pass
-    const int nlb = J.vjp ? 0 : loss_blocks(T.mask_n);
-    HIPCHK(h, hipMemsetAsync(A + T.Gout, 0, (size_t)N * L * 4, st));
-    if (!J.vjp) {   // loss = mean(mse_reduce(target, out)[mask]) and its gradient w.r.t. out
-        HIPCHK(h, T.loss.ensure((size_t)nlb * sizeof(double)));
-        HIPCHK(h, launch_loss(A + y_out, L, T.target.as<float>(), O, T.mask.as<int32_t>(), T.mask_n, J.nmask, renum ? 0 : J.mask_index_base,
-                              A + T.Gout, T.loss.as<double>(), st));
-    } else if (J.fvjp) {   // the cotangent of the model's output as given
-        HIPCHK(h, launch_vjp_seed(A + y_out, L, O, A + T.io + (size_t)N * O, nullptr, nullptr, nullptr, A + T.Gout,
-                                  J.out ? T.target.as<float>() : nullptr, N, st));
-    } else {        // dx/dt = inverse_data(o_norm, out) .* val_mask  =>  d/d out = lambda .* val_mask .* out_scale
-        const float* os = h->have_onorm ? nrm + 2 * c.Fn + 2 * c.Fe : nullptr;
-        const float* vm = J.val_mask ? A + T.io + (size_t)N * (O + c.Fn) : nullptr;
-        HIPCHK(h, launch_vjp_seed(A + y_out, L, O, A + T.io + (size_t)N * O, vm, os, os ? os + O : nullptr, A + T.Gout,
-                                  J.dxdt ? T.target.as<float>() : nullptr, N, st));
+    int seed() {
+        const size_t y_out = T.a_de.h[T.m_de.nblk - 1][2];        // the decoder's output (its last unit's Y)
+        nlb = vjp() ? 0 : loss_blocks(T.mask_n);
+        HIPCHK(h, hipMemsetAsync(A + T.Gout, 0, (size_t)N * L * 4, st));
+        if (!vjp()) {   // loss = mean(mse_reduce(target, out)[mask]) and its gradient w.r.t. out
+            HIPCHK(h, T.loss.ensure((size_t)nlb * sizeof(double)));
+            HIPCHK(h, launch_loss(A + y_out, L, T.target.as<float>(), O, T.mask.as<int32_t>(), T.mask_n, J.nmask, renum ? 0 : J.mask_index_base,
+                                  A + T.Gout, T.loss.as<double>(), st));
+        } else if (J.kind == JOB_FORWARD_VJP) {   // the cotangent of the model's output as given
+            HIPCHK(h, launch_vjp_seed(A + y_out, L, O, io() + (size_t)N * O, nullptr, nullptr, nullptr, A + T.Gout,
+                                      J.out ? T.target.as<float>() : nullptr, N, st));
+        } else {        // dx/dt = inverse_data(o_norm, out) .* val_mask  =>  d/d out = lambda .* val_mask .* out_scale
+            const float* os = h->have_onorm ? nrm + 2 * c.Fn + 2 * c.Fe : nullptr;
+            const float* vm = J.val_mask ? io() + (size_t)N * (O + c.Fn) : nullptr;
+            HIPCHK(h, launch_vjp_seed(A + y_out, L, O, io() + (size_t)N * O, vm, os, os ? os + O : nullptr, A + T.Gout,
+                                      J.dxdt ? T.target.as<float>() : nullptr, N, st));
+        }
+        return MGN_OK;
     }
 
     // ---- backward
-    // activation backward of one launch unit + all of its parameter gradients
-    // The parameter gradients of unit i (k_wgrad + k_reduce_partials: they only read what k_mlp_bwd left in gradient-buffer
-    // set i % gsets and the kept activations) run on a second stream beside the activation backward of the next units.  Not in
-    // recompute mode (there the kept activations are shared buffers which the next step's recomputation overwrites) and not
-    // on large meshes, which fill the chip on their own (prepare_graph).  MGN_TRAIN_OVERLAP = 0 keeps everything on one stream.
-    const bool overlap = T.gsets > 1;
-    if (overlap && !T.aux) {
+    int second_stream() {   // (created outside of any capture)
+        if (!overlap || T.aux) return MGN_OK;
         HIPCHK(h, hipStreamCreateWithFlags(&T.aux, hipStreamNonBlocking));
         HIPCHK(h, hipEventCreateWithFlags(&T.ev_bwd, hipEventDisableTiming));
         for (hipEvent_t& e : T.ev_wg) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    int n_bwd = 0;
-    // Small meshes: the weight-gradient jobs of `group` consecutive launch units go out as ONE k_wgrad + ONE k_reduce_partials launch on the
-    // second stream (two groups of gradient-buffer sets in flight).  Per unit they were 66 launches per processor step!, each a
-    // cross-stream dependency both ways: the main stream's backward kernels started ~10 us apart (rocprofv3 timeline, docs/experiments.md)
-    // and the second stream was the critical path.  Same partial blocks (128 rows), same order of the reduction: the same bits.
-    static const int group_env = [] { const char* e = getenv("MGN_TRAIN_WG_GROUP"); return e ? atoi(e) : 1; }();
-    const int group = overlap ? std::max(1, std::min(group_env, T.gsets / 2)) : 1;
-    int64_t lrows_all = N;
-    for (int q = 0; q < S; ++q) lrows_all = std::max<int64_t>(lrows_all, sx[q].E);
-    WgradBatch pwb{};
-    ReduceBatch prb{};
-    int pnw = 0, punits = 0, nbatch = 0;
-    int64_t plrows = 0;
-    std::vector<ReduceJob> deferred;                     // (T.defer_reduce) the reductions of all units, launched behind the last weight-gradient launch
-    int unit_no = 0;
-    int set_batch[TrainState::GSETS_MAX];                // launch number that takes the weight gradients of the unit in each buffer set
-    for (int& v : set_batch) v = -1;
-    auto flush = [&]() -> int {
-        if (punits == 0) return MGN_OK;
-        hipStream_t wst = overlap ? T.aux : st;
-        if (overlap) {
-            HIPCHK(h, hipEventRecord(T.ev_bwd, st));
-            HIPCHK(h, hipStreamWaitEvent(wst, T.ev_bwd, 0));
-        }
-        if (pwb.njobs > 0 && wgrad_blocks(plrows) > 0) {
-            HIPCHK(h, launch_wgrad(L, pwb, plrows, wst));
-            HIPCHK(h, launch_reduce_partials(prb, wst));
-        }
-        if (overlap) HIPCHK(h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
-        ++nbatch;
-        pwb = WgradBatch{};
-        prb = ReduceBatch{};
-        pnw = punits = 0;
-        plrows = 0;
         return MGN_OK;
-    };
-    // `fq` >= 0: first unit of the edge MLP of set fq with the factored first layer -- only the e block of W1 is unwound per edge
-    // (gx[0] / gxadd[0] / xin[0] describe it); the v blocks follow per node from the summed rows of GZ1 (SGs, SGr) after this call.
-    auto bwd_unit = [&](const TrainBlock& b, int64_t rows, int32_t ntiles, const float* g0, const float* g1, const int32_t* g1i, const size_t (&hb)[3],
-                        float* const gx[3], const float* const gxadd[3], const float* const xin[3], const int32_t* const xi[3],
-                        int fq = -1, const float* vin = nullptr, int lnslot = -1) -> int {
+    }
+    // activation backward of one launch unit (kept activations hb) + all of its parameter gradients
+    int bwd_unit(const TrainBlock& b, int64_t rows, int32_t ntiles, const size_t (&hb)[3], const BwdIo& io_, int lnslot) {
+        const int fq = io_.fq;
         const bool fact = fq >= 0;
         const bool wide = lnall && b.ln;
         const int64_t node_rows = fact ? NT : 0;          // rows that send: SGs, dW1s (halo rows included); SGr and dW1r stop at the N owned rows
         const int nin_k = fact ? 1 : b.nin;               // input blocks the kernel unwinds
-        const int gs = overlap ? n_bwd % T.gsets : 0;
-        // buffer set gs is re-used: the launch that took its last occupant's weight gradients must have run (launches on the second stream are
-        // in order; their events are indexed by launch number)
-        if (overlap && set_batch[gs] >= 0) {
-            if (set_batch[gs] == nbatch && punits > 0)
-                if (int rc = flush()) return rc;
-            HIPCHK(h, hipStreamWaitEvent(st, T.ev_wg[set_batch[gs] % TrainState::GSETS_MAX], 0));
-        }
-        ++n_bwd;
+        int gs = 0;
+        if (int rc = wq.acquire(*this, gs)) return rc;
         TrainBwdArgs a{};
         a.rows = rows; a.ntiles = ntiles;
-        a.G0 = g0; a.G1 = g1; a.g1idx = g1i;
+        a.G0 = io_.g0; a.G1 = io_.g1; a.g1idx = io_.g1i;
         a.H1 = A + hb[0]; a.H2 = A + hb[1]; a.Y = A + hb[2];
         a.W3T = Wt + b.W3T; a.W2T = Wt + b.W2T;
         for (int j = 0; j < nin_k; ++j) {
             const int jw = fact ? 2 : j;                   // factored: block 2 (e) of W1
-            a.W1T[j] = (b.has_w1t && gx[j]) ? Wt + b.W1T[jw] : nullptr;
-            a.GX[j] = gx[j];
-            a.GXadd[j] = gxadd[j];
+            a.W1T[j] = (b.has_w1t && io_.gx[j]) ? Wt + b.W1T[jw] : nullptr;
+            a.GX[j] = io_.gx[j];
+            a.GXadd[j] = io_.gxadd[j];
         }
         a.tabs = Wt + b.tabs;
         a.ln = b.ln ? 1 : 0;
@@ -947,7 +985,7 @@ int train_run(mgn_handle* h, const TrainJob& J) {
         if (lnsum) { a.GT = nullptr; a.GXH = nullptr; a.LNSUM = A + T.lnsum; }
         if (b.ln && !wide && !lnsum && !T.need_gt && rows > 0) return fail(h, MGN_E_STATE, "training arena laid out without GT / GXH rows but a launch unit needs them");
         if (wide && rows > 0) {   // pullback of the whole-array LayerNorm: dgamma, dbeta and the two means first (two column reductions)
-            HIPCHK(h, launch_lnall_bwd(g0, g1, g1i, A + hb[2], A + T.lnstats + (size_t)64 * lnslot, Wt + b.tabs + (size_t)T_GAMMA * L, rows, L,
+            HIPCHK(h, launch_lnall_bwd(io_.g0, io_.g1, io_.g1i, A + hb[2], A + T.lnstats + (size_t)64 * lnslot, Wt + b.tabs + (size_t)T_GAMMA * L, rows, L,
                                        reinterpret_cast<double*>(A + T.lnpart), A + T.lnm, G + b.ggamma, G + b.gbeta, st));
             a.ln = 2;                   // the kernel maps G to the gradient at Y as it loads it
             a.LNS = A + T.lnstats + (size_t)64 * lnslot;
@@ -968,205 +1006,103 @@ int train_run(mgn_handle* h, const TrainJob& J) {
             }
             if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.SGr + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (a halo row receives nothing here)
         }
-        // every parameter gradient of this unit: jobs of one batched weight-gradient launch + one batched (ordered) reduction
-        const int64_t lrows_u = rows > node_rows ? rows : node_rows;   // a launch covers its longest job (node jobs of a factored edge MLP)
-        const int64_t lrows = overlap ? lrows_all : lrows_u;           // (a group's launch: the longest job of the model; 128-row blocks either way)
-        const int nb = wgrad_blocks(lrows);
-        T.wg_rpb_last = wgrad_rows_per_block(lrows);
-        if (pwb.njobs + 10 > WGRAD_MAX_JOBS || prb.njobs + 14 > REDUCE_MAX_JOBS)   // (a unit adds at most 8 + 12 jobs)
-            if (int rc = flush()) return rc;
-        ++punits;
-        set_batch[gs] = nbatch;
-        if (nb == 0 || lrows_u == 0) return punits >= group ? flush() : MGN_OK;
-        plrows = std::max(plrows, lrows);
-        WgradBatch& wb = pwb;
-        ReduceBatch& rb = prb;
-        int& nw = pnw;
-        const bool defer = T.defer_reduce && unit_no < T.defer_units;
-        const int this_unit = unit_no++;
-        int unw = 0, unb = 0;                                  // (deferred) weight / column-sum partial slots of this unit
-        auto job = [&](const float* X, const int32_t* xi_, const float* Gm, long woff, int nrows, int cols, long boff, int bcols,
-                       int64_t jrows = -1) {
-            if (woff < 0 && boff < 0) return;              // identity slot
-            WgradJob& j = wb.job[wb.njobs];
-            if (jrows < 0) jrows = rows;
-            const int nbj = wgrad_blocks_of_job(lrows, jrows);     // blocks of this launch that hold rows of the job
-            j.X = X; j.xidx = xi_; j.G = Gm; j.rows = jrows;
-            if (defer) {
-                j.pw = woff >= 0 ? A + T.pw_all + ((size_t)this_unit * 5 + unw) * nb * L * L : nullptr;
-                j.pb = boff >= 0 ? A + T.pb_all + ((size_t)this_unit * DEFER_PB_JOBS + unb) * nb * L : nullptr;
-                if (woff >= 0) { deferred.push_back(ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff}); ++unw; }
-                if (boff >= 0) { deferred.push_back(ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff}); ++unb; }
-                ++wb.njobs;
-                return;
-            }
-            j.pw = woff >= 0 ? A + T.pw + (size_t)nw * nb * L * L : nullptr;
-            j.pb = boff >= 0 ? A + T.pb + (size_t)wb.njobs * nb * L : nullptr;
-            if (woff >= 0) {
-                rb.job[rb.njobs++] = ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff};
-                ++nw;
-            }
-            if (boff >= 0) rb.job[rb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff};
-            ++wb.njobs;
-        };
-        job(A + hb[1], nullptr, A + T.GY[gs], b.gW[2], L, b.out_cols, b.gb[2], b.out_cols);
-        job(A + hb[0], nullptr, A + T.GZ2[gs], b.gW[1], L, L, b.gb[1], L);
-        if (!fact) {
-            for (int j = 0; j < b.nin; ++j)
-                job(xin[j], xi[j], A + T.GZ1[gs], b.gW[0] + (long)j * L * L, b.in_rows, L, j == 0 ? b.gb[0] : -1, L);
-        } else {   // dW1e = e^T GZ1 (+ db1) over the edges; dW1s = v^T SGs, dW1r = v^T SGr over the nodes
-            job(xin[0], xi[0], A + T.GZ1[gs], b.gW[0] + (long)2 * L * L, L, L, b.gb[0], L);
-            job(vin, nullptr, A + T.SGs, b.gW[0], L, L, -1, L, node_rows);
-            job(vin, nullptr, A + T.SGr, b.gW[0] + (long)L * L, L, L, -1, L, N);
-        }
-        if (lnsum) {
-            const int ng = std::min(LNSUM_GROUPS, (int)((ntiles + 7) / 8));
-            rb.job[rb.njobs++] = ReduceJob{A + T.lnsum2, ng, (int64_t)2 * L, 1, L, L, G + b.gbeta};
-            rb.job[rb.njobs++] = ReduceJob{A + T.lnsum2 + L, ng, (int64_t)2 * L, 1, L, L, G + b.ggamma};
-        } else if (lnjob) {
-            WgradJob& j = wb.job[wb.njobs];
-            const int nbj = wgrad_blocks_of_job(lrows, rows);
-            j = WgradJob{};
-            j.G = g0; j.rows = rows;
-            j.Y = A + hb[2]; j.LNROW = A + T.lnrow; j.G1 = g1; j.g1idx = g1i;
-            j.pb = A + T.pb + (size_t)wb.njobs * nb * L;
-            j.pb2 = A + T.pb + (size_t)WGRAD_MAX_JOBS * nb * L;
-            rb.job[rb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, L, L, G + b.gbeta};
-            rb.job[rb.njobs++] = ReduceJob{j.pb2, nbj, (int64_t)L, 1, L, L, G + b.ggamma};
-            ++wb.njobs;
-        } else if (b.ln && !wide) {
-            job(nullptr, nullptr, A + T.GXH[gs], -1, 0, 0, b.ggamma, L);
-            job(nullptr, nullptr, A + T.GT[gs], -1, 0, 0, b.gbeta, L);
-        }
-        return punits >= group ? flush() : MGN_OK;
-    };
+        return wq.add_unit(*this, WgradUnit{b, io_, hb, rows, node_rows, ntiles, gs, wide, lnsum, lnjob});
+    }
     // one MLP: its second unit (if any) first, handing the gradient w.r.t. its input to the first through GXB
-    auto bwd = [&](const TrainMlp& m, int64_t rows, int32_t ntiles, const float* g0, const float* g1, const int32_t* g1i, const Acts& act,
-                   float* const gx[3], const float* const gxadd[3], const float* const xin[3], const int32_t* const xi[3],
-                   int fq = -1, const float* vin = nullptr) -> int {
-        if (m.nblk == 2) {
-            float* gx1[3] = {A + T.GXB, nullptr, nullptr};
-            const float* none[3] = {nullptr, nullptr, nullptr};
-            const float* xin1[3] = {A + act.h[0][2], nullptr, nullptr};
-            const int32_t* xi1[3] = {nullptr, nullptr, nullptr};
-            if (int rc = bwd_unit(m.b[1], rows, ntiles, g0, g1, g1i, act.h[1], gx1, none, xin1, xi1, -1, nullptr, m.lnslot)) return rc;
-            return bwd_unit(m.b[0], rows, ntiles, A + T.GXB, nullptr, nullptr, act.h[0], gx, gxadd, xin, xi, fq, vin, m.lnslot);
-        }
-        return bwd_unit(m.b[0], rows, ntiles, g0, g1, g1i, act.h[0], gx, gxadd, xin, xi, fq, vin, m.lnslot);
-    };
-
-    auto backward_launches = [&]() -> int {
-    HIPCHK(h, hipMemsetAsync(G, 0, h->params.size() * 4, st));   // (inside the replayed sequence: G is the engine's own buffer)
-    n_bwd = 0;
-    unit_no = 0;
-    deferred.clear();
-    pwb = WgradBatch{}; prb = ReduceBatch{};
-    pnw = punits = nbatch = 0;
-    plrows = 0;
-    for (int& v : set_batch) v = -1;
-    int cur = 0;   // gV[cur], gE[q][ecur] hold the gradients w.r.t. the latents entering the part of the model already unwound
-    {
-        float* gx[3] = {A + T.gV[cur], nullptr, nullptr};
-        const float* gxadd[3] = {nullptr, nullptr, nullptr};
-        const float* xin[3] = {A + T.Vk[mps], nullptr, nullptr};
-        const int32_t* xi[3] = {nullptr, nullptr, nullptr};
-        if (int rc = bwd(T.m_de, N, nt_n, A + T.Gout, nullptr, nullptr, T.a_de, gx, gxadd, xin, xi)) return rc;
+    int bwd(const TrainMlp& m, int64_t rows, int32_t ntiles, const Acts& act, const BwdIo& io_) {
+        if (m.nblk == 1) return bwd_unit(m.b[0], rows, ntiles, act.h[0], io_, m.lnslot);
+        BwdIo u1, u0 = io_;
+        u1.g0 = io_.g0; u1.g1 = io_.g1; u1.g1i = io_.g1i;
+        u1.gx[0] = A + T.GXB; u1.xin[0] = A + act.h[0][2];
+        if (int rc = bwd_unit(m.b[1], rows, ntiles, act.h[1], u1, m.lnslot)) return rc;
+        u0.g0 = A + T.GXB; u0.g1 = nullptr; u0.g1i = nullptr;
+        return bwd_unit(m.b[0], rows, ntiles, act.h[0], u0, m.lnslot);
     }
-    int ecur = 0;
-    for (int q = 0; q < S; ++q) HIPCHK(h, hipMemsetAsync(A + T.gE[q][ecur], 0, (size_t)(sx[q].E > 0 ? sx[q].E : 1) * L * 4, st));
-    for (int k = mps - 1; k >= 0; --k) {
-        const int nxt = cur ^ 1, enxt = ecur ^ 1;
-        if (!T.kept(k, mps)) {   // regenerate H1, H2, Y of the MLPs of this step from their kept inputs
-            HIPCHK(h, fwd_node(k, nullptr, nullptr));
-            for (int q = 0; q < S; ++q) HIPCHK(h, fwd_edge(q, k, nullptr, nullptr, nullptr));
+    // the edge MLP of step k, set q: d loss / d e_{k+1} in gE[ecur], d loss / d agg_k in gAgg -> gE[ecur ^ 1], and its share of gV[nxt]
+    int bwd_edge(int q, int k, int nxt, int ecur) {
+        const TrainMlp& me = T.m_pe[q][k];
+        const int64_t E = sx[q].E;
+        const int enxt = ecur ^ 1;
+        BwdIo u;
+        u.g0 = A + T.gE[q][ecur]; u.g1 = A + T.gAgg[q]; u.g1i = sx[q].rcv;
+        if (!T.factored[q]) {   // edge MLP: e' feeds e_{k+1} = e_k + e' and agg_k[receiver]
+            u.gx[0] = A + T.GXs; u.gx[1] = A + T.GXr; u.gx[2] = A + T.gE[q][enxt];
+            u.gxadd[2] = A + T.gE[q][ecur];
+            u.xin[0] = A + T.Vk[k]; u.xin[1] = A + T.Vk[k]; u.xin[2] = A + T.Ek[q][k];
+            u.xi[0] = sx[q].snd; u.xi[1] = sx[q].rcv;
+            if (int rc = bwd(me, E, sx[q].nt, T.a_pe[q][k], u)) return rc;
+            T.wg_rpb_edge[q] = T.wg_rpb_last;
+            // gather duality: the gradients of v[receivers] / v[senders] are segmented sums over the receiver / sender CSR
+            HIPCHK(h, launch_segment_sum2(L, A + T.GXr, sx[q].rowptr, A + T.GXs, sx[q].rowptr_s, sx[q].perm_s, A + T.gV[nxt], A + T.gV[nxt],
+                                          (int32_t)N, st));
+            // halo rows only send
+            HIPCHK(h, launch_segment_sum(L, A + T.GXs, sx[q].rowptr_s + N, sx[q].perm_s, nullptr, A + T.gV[nxt] + (size_t)N * L, g.n_halo, st));
+        } else {             // factored first layer: per edge only the e block; the v blocks per node from SGs / SGr
+            u.gx[0] = A + T.gE[q][enxt];
+            u.gxadd[0] = A + T.gE[q][ecur];
+            u.xin[0] = A + T.Ek[q][k];
+            u.fq = q; u.vin = A + T.Vk[k];
+            if (int rc = bwd(me, E, sx[q].nt, T.a_pe[q][k], u)) return rc;
+            T.wg_rpb_edge[q] = T.wg_rpb_last;
+            if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.gV[nxt] + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (no node MLP wrote them)
+            Lin2Args l2{};    // gV += SGs W1s^T + SGr W1r^T
+            l2.rows = NT; l2.ntiles = nt_t;
+            l2.X0 = A + T.SGs; l2.X1 = A + T.SGr; l2.W0 = Wt + me.b[0].W1T[0]; l2.W1 = Wt + me.b[0].W1T[1];
+            l2.ADD = A + T.gV[nxt]; l2.OUT0 = A + T.gV[nxt];
+            HIPCHK(h, launch_lin2(L, l2, st));
         }
-        {   // node MLP: v_{k+1} = v_k + MLP_v([v_k; agg_k (per set)])
-            float* gx[3] = {A + T.gV[nxt], A + T.gAgg[0], S > 1 ? A + T.gAgg[1] : nullptr};
-            const float* gxadd[3] = {A + T.gV[cur], nullptr, nullptr};
-            const float* xin[3] = {A + T.Vk[k], A + T.agg[0][k], S > 1 ? A + T.agg[1][k] : nullptr};
-            const int32_t* xi[3] = {nullptr, nullptr, nullptr};
-            if (int rc = bwd(T.m_pn[k], N, nt_n, A + T.gV[cur], nullptr, nullptr, T.a_pn[k], gx, gxadd, xin, xi)) return rc;
-            T.wg_rpb_node = T.wg_rpb_last;
-        }
-        for (int q = 0; q < S; ++q) {
-            const TrainMlp& me = T.m_pe[q][k];
-            const int64_t E = sx[q].E;
-            if (!T.factored[q]) {   // edge MLP: e' feeds e_{k+1} = e_k + e' and agg_k[receiver]
-                float* gx[3] = {A + T.GXs, A + T.GXr, A + T.gE[q][enxt]};
-                const float* gxadd[3] = {nullptr, nullptr, A + T.gE[q][ecur]};
-                const float* xin[3] = {A + T.Vk[k], A + T.Vk[k], A + T.Ek[q][k]};
-                const int32_t* xi[3] = {sx[q].snd, sx[q].rcv, nullptr};
-                if (int rc = bwd(me, E, sx[q].nt, A + T.gE[q][ecur], A + T.gAgg[q], sx[q].rcv, T.a_pe[q][k], gx, gxadd, xin, xi)) return rc;
-                T.wg_rpb_edge[q] = T.wg_rpb_last;
-                // gather duality: the gradients of v[receivers] / v[senders] are segmented sums over the receiver / sender CSR
-                HIPCHK(h, launch_segment_sum2(L, A + T.GXr, sx[q].rowptr, A + T.GXs, sx[q].rowptr_s, sx[q].perm_s, A + T.gV[nxt], A + T.gV[nxt],
-                                              (int32_t)N, st));
-                // halo rows only send
-                HIPCHK(h, launch_segment_sum(L, A + T.GXs, sx[q].rowptr_s + N, sx[q].perm_s, nullptr, A + T.gV[nxt] + (size_t)N * L, g.n_halo, st));
-            } else {             // factored first layer: per edge only the e block; the v blocks per node from SGs / SGr
-                float* gx[3] = {A + T.gE[q][enxt], nullptr, nullptr};
-                const float* gxadd[3] = {A + T.gE[q][ecur], nullptr, nullptr};
-                const float* xin[3] = {A + T.Ek[q][k], nullptr, nullptr};
-                const int32_t* xi[3] = {nullptr, nullptr, nullptr};
-                if (int rc = bwd(me, E, sx[q].nt, A + T.gE[q][ecur], A + T.gAgg[q], sx[q].rcv, T.a_pe[q][k], gx, gxadd, xin, xi, q, A + T.Vk[k]))
-                    return rc;
-                T.wg_rpb_edge[q] = T.wg_rpb_last;
-                if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.gV[nxt] + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (no node MLP wrote them)
-                Lin2Args l2{};    // gV += SGs W1s^T + SGr W1r^T
-                l2.rows = NT; l2.ntiles = nt_t;
-                l2.X0 = A + T.SGs; l2.X1 = A + T.SGr; l2.W0 = Wt + me.b[0].W1T[0]; l2.W1 = Wt + me.b[0].W1T[1];
-                l2.ADD = A + T.gV[nxt]; l2.OUT0 = A + T.gV[nxt];
-                HIPCHK(h, launch_lin2(L, l2, st));
-            }
-            if (E == 0) HIPCHK(h, hipMemsetAsync(A + T.gE[q][enxt], 0, (size_t)L * 4, st));
-        }
-        // the halo rows' share of d loss / d v_k joins the owners' before node MLP k - 1 (the node encoder for k = 0) is unwound
-        if (part) if (int rc = halo_reverse(A + T.gV[nxt])) return rc;
-        cur = nxt;
-        ecur = enxt;
-    }
-    {
-        float* gx_n[3] = {J.vjp ? A + T.gNF : nullptr, nullptr, nullptr};
-        float* gx[3] = {nullptr, nullptr, nullptr};
-        const float* gxadd[3] = {nullptr, nullptr, nullptr};
-        const float* xin[3] = {A + T.nf_pad, nullptr, nullptr};
-        const int32_t* xi[3] = {nullptr, nullptr, nullptr};
-        if (int rc = bwd(T.m_en, N, nt_n, A + T.gV[cur], nullptr, nullptr, T.a_en, gx_n, gxadd, xin, xi)) return rc;
-        for (int q = 0; q < S; ++q) {
-            const float* xin_e[3] = {A + T.ef_pad[q], nullptr, nullptr};
-            const int32_t* xi_e[3] = {part ? nullptr : sx[q].egid, nullptr, nullptr};
-            if (int rc = bwd(T.m_ee[q], sx[q].E, sx[q].nt, A + T.gE[q][ecur], nullptr, nullptr, T.a_ee[q], gx, gxadd, xin_e, xi_e)) return rc;
-        }
-    }
-
-    if (int rc = flush()) return rc;                     // the units left over from the last full group
-    if (!deferred.empty()) {                             // every unit's reductions, REDUCE_MAX_JOBS per launch, behind the last weight-gradient launch
-        hipStream_t wst = overlap ? T.aux : st;
-        for (size_t i = 0; i < deferred.size(); i += REDUCE_MAX_JOBS) {
-            ReduceBatch rb{};
-            for (size_t j = i; j < deferred.size() && j < i + REDUCE_MAX_JOBS; ++j) rb.job[rb.njobs++] = deferred[j];
-            HIPCHK(h, launch_reduce_partials(rb, wst));
-        }
-        if (overlap) {
-            HIPCHK(h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
-            ++nbatch;
-        }
-    }
-    if (overlap && nbatch > 0)                           // join: the second stream is in order, its last event covers all of it
-        HIPCHK(h, hipStreamWaitEvent(st, T.ev_wg[(nbatch - 1) % TrainState::GSETS_MAX], 0));
-    return MGN_OK;
-    };
-    if (int rc = graphed(J.vjp ? 2 : 1, backward_launches)) return rc;
-
-    // ---- results
-    if (J.sweep) {     // xbar (engine order) into io for the adjoint kernel; the step's gradient into the double accumulator
-        HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, A + T.io, N, st));
-        HIPCHK(h, launch_grad_accum(G, J.gacc, (int64_t)h->params.size(), J.first, st));
+        if (E == 0) HIPCHK(h, hipMemsetAsync(A + T.gE[q][enxt], 0, (size_t)L * 4, st));
         return MGN_OK;
     }
-    if (part) {
-        // Finish: every rank's gradient and loss numerator are gathered and added in ascending rank order, in double, by the same kernel on
-        // every rank: the same bits everywhere.  The call's one blocking point follows.
+    int backward() {
+        wq.reset();
+        HIPCHK(h, hipMemsetAsync(G, 0, h->params.size() * 4, st));   // (inside the replayed sequence: G is the engine's own buffer)
+        int cur = 0, ecur = 0;   // gV[cur], gE[q][ecur] hold the gradients w.r.t. the latents entering the part of the model already unwound
+        {
+            BwdIo u;
+            u.g0 = A + T.Gout; u.gx[0] = A + T.gV[cur]; u.xin[0] = A + T.Vk[mps];
+            if (int rc = bwd(T.m_de, N, nt_n, T.a_de, u)) return rc;
+        }
+        for (int q = 0; q < S; ++q) HIPCHK(h, hipMemsetAsync(A + T.gE[q][ecur], 0, (size_t)(sx[q].E > 0 ? sx[q].E : 1) * L * 4, st));
+        for (int k = mps - 1; k >= 0; --k) {
+            const int nxt = cur ^ 1;
+            if (!T.kept(k, mps)) {   // regenerate H1, H2, Y of the MLPs of this step from their kept inputs
+                HIPCHK(h, fwd_node(k, nullptr, nullptr));
+                for (int q = 0; q < S; ++q) HIPCHK(h, fwd_edge(q, k, nullptr, nullptr, nullptr));
+            }
+            {   // node MLP: v_{k+1} = v_k + MLP_v([v_k; agg_k (per set)])
+                BwdIo u;
+                u.g0 = A + T.gV[cur];
+                u.gx[0] = A + T.gV[nxt]; u.gx[1] = A + T.gAgg[0]; u.gx[2] = S > 1 ? A + T.gAgg[1] : nullptr;
+                u.gxadd[0] = A + T.gV[cur];
+                u.xin[0] = A + T.Vk[k]; u.xin[1] = A + T.agg[0][k]; u.xin[2] = S > 1 ? A + T.agg[1][k] : nullptr;
+                if (int rc = bwd(T.m_pn[k], N, nt_n, T.a_pn[k], u)) return rc;
+                T.wg_rpb_node = T.wg_rpb_last;
+            }
+            for (int q = 0; q < S; ++q)
+                if (int rc = bwd_edge(q, k, nxt, ecur)) return rc;
+            // the halo rows' share of d loss / d v_k joins the owners' before node MLP k - 1 (the node encoder for k = 0) is unwound
+            if (part) if (int rc = halo_reverse(A + T.gV[nxt])) return rc;
+            cur = nxt;
+            ecur ^= 1;
+        }
+        {
+            BwdIo u;
+            u.g0 = A + T.gV[cur]; u.gx[0] = vjp() ? A + T.gNF : nullptr; u.xin[0] = A + T.nf_pad;
+            if (int rc = bwd(T.m_en, N, nt_n, T.a_en, u)) return rc;
+        }
+        for (int q = 0; q < S; ++q) {
+            BwdIo u;
+            u.g0 = A + T.gE[q][ecur]; u.xin[0] = A + T.ef_pad[q]; u.xi[0] = part ? nullptr : sx[q].egid;
+            if (int rc = bwd(T.m_ee[q], sx[q].E, sx[q].nt, T.a_ee[q], u)) return rc;
+        }
+        return wq.drain(*this);
+    }
+
+    // ---- results
+    // Finish of a partition: every rank's gradient and loss numerator are gathered and added in ascending rank order, in double, by the same
+    // kernel on every rank: the same bits everywhere.  The call's one blocking point follows.
+    int finish_partition() {
         const int64_t np = (int64_t)h->params.size();
         double num = 0.0;
         HIPCHK(h, launch_loss_numerator(T.loss.as<double>(), nlb, T.fin_s.as<double>(), st));
@@ -1178,37 +1114,180 @@ int train_run(mgn_handle* h, const TrainJob& J) {
         *J.loss = (float)(num / (double)J.nmask);
         return MGN_OK;
     }
-    std::vector<double> lp((size_t)nlb);
-    HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
-    if (!J.vjp) {
-        HIPCHK(h, hipMemcpyAsync(lp.data(), T.loss.p, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    } else if (J.fvjp) {
-        HIPCHK(h, launch_extract_cols(A + T.gNF, L, c.Fn, nullptr, A + T.io, N, st));
-        HIPCHK(h, to_global(A + T.io, c.Fn));
-        HIPCHK(h, hipMemcpyAsync(J.nfbar, A + T.io, (size_t)N * c.Fn * 4, hipMemcpyDefault, st));
-        if (J.out) {
-            HIPCHK(h, to_global(T.target.as<float>(), O));
-            HIPCHK(h, hipMemcpyAsync(J.out, T.target.p, (size_t)N * O * 4, hipMemcpyDefault, st));
-        }
-    } else {
-        // x enters through the node normaliser: xbar = (d / d nf)[:, 0:O] .* node_scale[0:O]
-        HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, A + T.io, N, st));
-        HIPCHK(h, to_global(A + T.io, O));
-        HIPCHK(h, hipMemcpyAsync(J.xbar, A + T.io, (size_t)N * O * 4, hipMemcpyDefault, st));
-        if (J.dxdt) {
-            HIPCHK(h, to_global(T.target.as<float>(), O));
-            HIPCHK(h, hipMemcpyAsync(J.dxdt, T.target.p, (size_t)N * O * 4, hipMemcpyDefault, st));
-        }
+    // a per-node result [N][width] of a VJP: back into the caller's order and out
+    int give(float* buf, int width, float* user) {
+        HIPCHK(h, to_global(buf, width));
+        HIPCHK(h, hipMemcpyAsync(user, buf, (size_t)N * width * 4, hipMemcpyDefault, st));
+        return MGN_OK;
     }
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (!J.vjp) {
-        double s = 0.0;
-        for (double v : lp) s += v;
-        *J.loss = (float)(s / (double)J.nmask);
+    int results() {
+        if (J.kind == JOB_SWEEP_STEP) {     // xbar (engine order) into io for the adjoint kernel; the step's gradient into the double accumulator
+            HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, io(), N, st));
+            HIPCHK(h, launch_grad_accum(G, J.gacc, (int64_t)h->params.size(), J.first, st));
+            return MGN_OK;
+        }
+        if (part) return finish_partition();
+        std::vector<double> lp((size_t)nlb);
+        HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
+        if (J.kind == JOB_STEP) {
+            HIPCHK(h, hipMemcpyAsync(lp.data(), T.loss.p, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        } else if (J.kind == JOB_FORWARD_VJP) {
+            HIPCHK(h, launch_extract_cols(A + T.gNF, L, c.Fn, nullptr, io(), N, st));
+            if (int rc = give(io(), c.Fn, J.nfbar)) return rc;
+            if (J.out) if (int rc = give(T.target.as<float>(), O, J.out)) return rc;
+        } else {
+            // x enters through the node normaliser: xbar = (d / d nf)[:, 0:O] .* node_scale[0:O]
+            HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, io(), N, st));
+            if (int rc = give(io(), O, J.xbar)) return rc;
+            if (J.dxdt) if (int rc = give(T.target.as<float>(), O, J.dxdt)) return rc;
+        }
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (J.kind == JOB_STEP) {
+            double s = 0.0;
+            for (double v : lp) s += v;
+            *J.loss = (float)(s / (double)J.nmask);
+        }
+        return MGN_OK;
     }
+};
+
+// buffer set gs is re-used: the launch that took its last occupant's weight gradients must have run (launches on the second stream are
+// in order; their events are indexed by launch number)
+int WgradQueue::acquire(TrainPass& P, int& gs) {
+    gs = P.overlap ? n_bwd % P.T.gsets : 0;
+    if (P.overlap && set_batch[gs] >= 0) {
+        if (set_batch[gs] == nbatch && punits > 0)
+            if (int rc = flush(P)) return rc;
+        HIPCHK(P.h, hipStreamWaitEvent(P.st, P.T.ev_wg[set_batch[gs] % TrainState::GSETS_MAX], 0));
+    }
+    ++n_bwd;
     return MGN_OK;
 }
 
+int WgradQueue::flush(TrainPass& P) {
+    if (punits == 0) return MGN_OK;
+    TrainState& T = P.T;
+    hipStream_t wst = P.overlap ? T.aux : P.st;
+    if (P.overlap) {
+        HIPCHK(P.h, hipEventRecord(T.ev_bwd, P.st));
+        HIPCHK(P.h, hipStreamWaitEvent(wst, T.ev_bwd, 0));
+    }
+    if (pwb.njobs > 0 && wgrad_blocks(plrows) > 0) {
+        HIPCHK(P.h, launch_wgrad(P.L, pwb, plrows, wst));
+        HIPCHK(P.h, launch_reduce_partials(prb, wst));
+    }
+    if (P.overlap) HIPCHK(P.h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
+    ++nbatch;
+    new_batch();
+    return MGN_OK;
+}
+
+// every parameter gradient of the unit: jobs of one batched weight-gradient launch + one batched (ordered) reduction
+int WgradQueue::add_unit(TrainPass& P, const WgradUnit& u) {
+    TrainState& T = P.T;
+    const TrainBlock& b = u.b;
+    const int L = P.L, gs = u.gs;
+    float* const A = P.A;
+    float* const G = P.G;
+    const int64_t rows = u.rows;
+    const int64_t lrows_u = rows > u.node_rows ? rows : u.node_rows;   // a launch covers its longest job (node jobs of a factored edge MLP)
+    const int64_t lrows = P.overlap ? P.lrows_all : lrows_u;           // (a group's launch: the longest job of the model; 128-row blocks either way)
+    const int nb = wgrad_blocks(lrows);
+    T.wg_rpb_last = wgrad_rows_per_block(lrows);
+    if (pwb.njobs + 10 > WGRAD_MAX_JOBS || prb.njobs + 14 > REDUCE_MAX_JOBS)   // (a unit adds at most 8 + 12 jobs)
+        if (int rc = flush(P)) return rc;
+    ++punits;
+    set_batch[gs] = nbatch;
+    if (nb == 0 || lrows_u == 0) return punits >= P.group ? flush(P) : MGN_OK;
+    plrows = std::max(plrows, lrows);
+    const bool defer = T.defer_reduce && unit_no < T.defer_units;
+    const int this_unit = unit_no++;
+    int unw = 0, unb = 0;                                  // (deferred) weight / column-sum partial slots of this unit
+    auto job = [&](const float* X, const int32_t* xi_, const float* Gm, long woff, int nrows, int cols, long boff, int bcols, int64_t jrows = -1) {
+        if (woff < 0 && boff < 0) return;              // identity slot
+        WgradJob& j = pwb.job[pwb.njobs];
+        if (jrows < 0) jrows = rows;
+        const int nbj = wgrad_blocks_of_job(lrows, jrows);     // blocks of this launch that hold rows of the job
+        j.X = X; j.xidx = xi_; j.G = Gm; j.rows = jrows;
+        if (defer) {
+            j.pw = woff >= 0 ? A + T.pw_all + ((size_t)this_unit * 5 + unw) * nb * L * L : nullptr;
+            j.pb = boff >= 0 ? A + T.pb_all + ((size_t)this_unit * DEFER_PB_JOBS + unb) * nb * L : nullptr;
+            if (woff >= 0) { deferred.push_back(ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff}); ++unw; }
+            if (boff >= 0) { deferred.push_back(ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff}); ++unb; }
+            ++pwb.njobs;
+            return;
+        }
+        j.pw = woff >= 0 ? A + T.pw + (size_t)pnw * nb * L * L : nullptr;
+        j.pb = boff >= 0 ? A + T.pb + (size_t)pwb.njobs * nb * L : nullptr;
+        if (woff >= 0) {
+            prb.job[prb.njobs++] = ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff};
+            ++pnw;
+        }
+        if (boff >= 0) prb.job[prb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff};
+        ++pwb.njobs;
+    };
+    job(A + u.hb[1], nullptr, A + T.GY[gs], b.gW[2], L, b.out_cols, b.gb[2], b.out_cols);
+    job(A + u.hb[0], nullptr, A + T.GZ2[gs], b.gW[1], L, L, b.gb[1], L);
+    if (u.io.fq < 0) {
+        for (int j = 0; j < b.nin; ++j)
+            job(u.io.xin[j], u.io.xi[j], A + T.GZ1[gs], b.gW[0] + (long)j * L * L, b.in_rows, L, j == 0 ? b.gb[0] : -1, L);
+    } else {   // dW1e = e^T GZ1 (+ db1) over the edges; dW1s = v^T SGs, dW1r = v^T SGr over the nodes
+        job(u.io.xin[0], u.io.xi[0], A + T.GZ1[gs], b.gW[0] + (long)2 * L * L, L, L, b.gb[0], L);
+        job(u.io.vin, nullptr, A + T.SGs, b.gW[0], L, L, -1, L, u.node_rows);
+        job(u.io.vin, nullptr, A + T.SGr, b.gW[0] + (long)L * L, L, L, -1, L, P.N);
+    }
+    if (u.lnsum) {
+        const int ng = std::min(LNSUM_GROUPS, (int)((u.ntiles + 7) / 8));
+        prb.job[prb.njobs++] = ReduceJob{A + T.lnsum2, ng, (int64_t)2 * L, 1, L, L, G + b.gbeta};
+        prb.job[prb.njobs++] = ReduceJob{A + T.lnsum2 + L, ng, (int64_t)2 * L, 1, L, L, G + b.ggamma};
+    } else if (u.lnjob) {
+        WgradJob& j = pwb.job[pwb.njobs];
+        const int nbj = wgrad_blocks_of_job(lrows, rows);
+        j = WgradJob{};
+        j.G = u.io.g0; j.rows = rows;
+        j.Y = A + u.hb[2]; j.LNROW = A + T.lnrow; j.G1 = u.io.g1; j.g1idx = u.io.g1i;
+        j.pb = A + T.pb + (size_t)pwb.njobs * nb * L;
+        j.pb2 = A + T.pb + (size_t)WGRAD_MAX_JOBS * nb * L;
+        prb.job[prb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, L, L, G + b.gbeta};
+        prb.job[prb.njobs++] = ReduceJob{j.pb2, nbj, (int64_t)L, 1, L, L, G + b.ggamma};
+        ++pwb.njobs;
+    } else if (b.ln && !u.wide) {
+        job(nullptr, nullptr, A + T.GXH[gs], -1, 0, 0, b.ggamma, L);
+        job(nullptr, nullptr, A + T.GT[gs], -1, 0, 0, b.gbeta, L);
+    }
+    return punits >= P.group ? flush(P) : MGN_OK;
+}
+
+int WgradQueue::drain(TrainPass& P) {
+    TrainState& T = P.T;
+    if (int rc = flush(P)) return rc;                    // the units left over from the last full group
+    if (!deferred.empty()) {                             // every unit's reductions, REDUCE_MAX_JOBS per launch, behind the last weight-gradient launch
+        hipStream_t wst = P.overlap ? T.aux : P.st;
+        for (size_t i = 0; i < deferred.size(); i += REDUCE_MAX_JOBS) {
+            ReduceBatch rb{};
+            for (size_t j = i; j < deferred.size() && j < i + REDUCE_MAX_JOBS; ++j) rb.job[rb.njobs++] = deferred[j];
+            HIPCHK(P.h, launch_reduce_partials(rb, wst));
+        }
+        if (P.overlap) {
+            HIPCHK(P.h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
+            ++nbatch;
+        }
+    }
+    if (P.overlap && nbatch > 0)                         // join: the second stream is in order, its last event covers all of it
+        HIPCHK(P.h, hipStreamWaitEvent(P.st, T.ev_wg[(nbatch - 1) % TrainState::GSETS_MAX], 0));
+    return MGN_OK;
+}
+
+int train_run(mgn_handle* h, const TrainJob& J) {
+    TrainPass P(h, J);
+    if (int rc = P.stage_inputs()) return rc;
+    P.drop_stale_graphs();
+    if (int rc = P.graphed(0, [&] { return P.forward(); })) return rc;
+    if (int rc = P.seed()) return rc;
+    if (int rc = P.second_stream()) return rc;
+    if (int rc = P.graphed(P.vjp() ? 2 : 1, [&] { return P.backward(); })) return rc;
+    return P.results();
+}
 
 }  // namespace
 
@@ -1240,7 +1319,7 @@ extern "C" int mgn_ode_vjp(mgn_handle* h, const float* x, const float* node_type
     if (c.Fn < c.O) return fail(h, MGN_E_ARG, "mgn_ode_vjp: Fn < O");
     if ((c.Fn > c.O && !node_type_onehot) || (!ef_raw && h->g.set[0].E > 0)) return fail(h, MGN_E_ARG, "mgn_ode_vjp: null argument");
     TrainJob J;
-    J.vjp = true;
+    J.kind = JOB_RHS_VJP;
     J.x = x; J.onehot = node_type_onehot; J.ef = ef_raw; J.val_mask = val_mask; J.lambda = lambda;
     J.dxdt = dxdt; J.xbar = xbar; J.grads = grads;
     return train_run(h, J);
@@ -1261,7 +1340,7 @@ struct Sweep {
     const float* xend;                         // x_K (continuity term)
     int64_t N = 0, n = 0;
     int O = 0, nb = 0;
-    float* io = nullptr;                       // xbar [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N], as train_run lays them out
+    float* io = nullptr;                       // xbar [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N], as TrainPass lays them out
     float* vm = nullptr;
     float gscale = 0.f;
     int64_t sidx = 0;                          // saves are visited last to first; save_step is non-decreasing
@@ -1271,39 +1350,15 @@ struct Sweep {
 
     int begin() {
         const mgn_config& c = h->cfg;
-        TrainState& T = *h->train;
-        const LocalGraph& g = h->g;
-        N = g.n_own;
-        n = N * c.O;
-        O = c.O;
-        const int64_t E = g.set[0].e_local;
-        const int W1 = c.Fn - c.O;
-        hipStream_t st = h->stream;
-        float* A = T.arena.as<float>();
-        io = A + T.io;
-        const float* nrm = h->norms.as<float>();
-        const int32_t* ngid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
-        auto to_local = [&](float* buf, int width) -> hipError_t {
-            if (!ngid || width <= 0) return hipSuccess;
-            if (hipError_t e = launch_permute_rows(A + T.ptmp, buf, ngid, N, width, false, st)) return e;
-            return hipMemcpyAsync(buf, A + T.ptmp, (size_t)N * width * 4, hipMemcpyDeviceToDevice, st);
-        };
-        // the statics, once per call
-        if (W1 > 0) {
-            HIPCHK(h, hipMemcpyAsync(io + 2 * n, S.onehot, (size_t)N * W1 * 4, hipMemcpyDefault, st));
-            HIPCHK(h, to_local(io + 2 * n, W1));
-        }
+        N = h->g.n_own; O = c.O; n = N * O;
+        TrainJob J;                                // the statics, once per call
+        J.kind = JOB_SWEEP_STEP;
+        J.onehot = S.onehot; J.val_mask = S.val_mask; J.ef = S.ef_raw;
+        TrainPass P(h, J);
+        io = P.io();
         vm = S.val_mask ? io + (size_t)N * (O + c.Fn) : nullptr;
-        if (vm) {
-            HIPCHK(h, hipMemcpyAsync(vm, S.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
-            HIPCHK(h, to_local(vm, 1));
-        }
-        if (E > 0) {
-            HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], S.ef_raw, (size_t)E * c.Fe * 4, hipMemcpyDefault, st));
-            HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
-                                        h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, A + T.ef_pad[0], c.L, E, st));
-        }
-        HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, st));
+        if (int rc = P.stage_statics(nullptr)) return rc;
+        HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, h->stream));
         nb = solver_adjoint_blocks(N, O);
         gscale = (float)(2.0 / ((double)S.n_saves * (double)(S.win_rows > 0 ? S.win_rows * O : n)));
         sidx = S.n_saves - 1;
@@ -1344,7 +1399,7 @@ struct Sweep {
     // gradient into the double accumulator (first: assigned)
     int vjp(const float* x, bool first) {
         TrainJob J;
-        J.vjp = J.sweep = true;
+        J.kind = JOB_SWEEP_STEP;
         J.first = first && !S.lacc;       // (mgn_shooting_grad: every pass adds to the zeroed accumulator)
         J.x = x;
         J.val_mask = vm;
@@ -1447,26 +1502,20 @@ struct LnAll {
     int64_t slots = 0;           // (sum, sum of squares) slots the last MLP launch left in `part` (TrainFwdArgs::STATS)
     bool factored = false;       // large launches: the first edge layer per NODE (P = v W1s, Q = v W1r; launch_lin2) as in the training step
 
-    // Y <- MLP(x) without LayerNorm / residual (launch units chained through Hb)
-    hipError_t mlp(const TrainMlp& m, int64_t rows, int32_t ntiles, const float* x0, const int32_t* i0, const float* x1, const int32_t* i1,
-                   const float* x2, float* yout) {
+    void attach() {               // the device pointers, once the arena and the index arrays are there (lnall_bind)
+        A = T.la.as<float>();
+        snd = h->es[0].d_snd.as<int32_t>(); rcv = h->es[0].d_rcv.as<int32_t>(); rowptr = h->es[0].d_rowptr.as<int32_t>();
+        egid = T.la_idx.as<int32_t>();
+    }
+    // Y <- MLP(x) without LayerNorm / residual (launch units chained through Hb); `in`, w1sel: as TrainPass::run_fwd takes them
+    hipError_t mlp(const TrainMlp& m, const TrainFwdArgs& in, float* yout, int w1sel = -1) {
         for (int bi = 0; bi < m.nblk; ++bi) {
-            const TrainBlock& b = m.b[bi];
-            TrainFwdArgs a{};
-            a.rows = rows; a.ntiles = ntiles;
-            int nin = b.nin;
-            if (bi == 0) {
-                a.X[0] = x0; a.xidx[0] = i0; a.X[1] = x1; a.xidx[1] = i1; a.X[2] = x2;
-                for (int j = 0; j < b.nin; ++j) a.W1[j] = Wt + b.W1[j];
-            } else {
-                a.X[0] = A + Hb;
-                a.W1[0] = Wt + b.W1[0];
-                nin = 1;
-            }
-            a.W2 = Wt + b.W2; a.W3 = Wt + b.W3; a.tabs = Wt + b.tabs;
+            const bool last = bi == m.nblk - 1;
+            TrainFwdArgs a;
+            const int nin = fwd_unit(m, bi, in, w1sel, Wt, A + Hb, a);
             a.ln = 0;
-            a.OUT = bi == m.nblk - 1 ? yout : A + Hb;
-            if (bi == m.nblk - 1 && b.ln) { a.STATS = reinterpret_cast<double*>(A + part); slots = train_fwd_stat_slots(L, ntiles); }
+            a.OUT = last ? yout : A + Hb;
+            if (last && m.b[bi].ln) { a.STATS = reinterpret_cast<double*>(A + part); slots = train_fwd_stat_slots(L, in.ntiles); }
             if (hipError_t e = launch_mlp_fwd(L, nin, a, st)) return e;
         }
         return hipSuccess;
@@ -1496,36 +1545,23 @@ struct LnAll {
             p.X0 = v; p.W0 = Wt + m.b[0].W1[0]; p.W1 = Wt + m.b[0].W1[1];
             p.OUT0 = A + Pn; p.OUT1 = A + Qn;
             HIPCHK(h, launch_lin2(L, p, st));
-            for (int bi = 0; bi < m.nblk; ++bi) {
-                const TrainBlock& b = m.b[bi];
-                TrainFwdArgs a{};
-                a.rows = E; a.ntiles = nt_e;
-                if (bi == 0) {
-                    a.X[0] = e; a.W1[0] = Wt + b.W1[2];
-                    a.PRE[0] = A + Pn; a.preidx[0] = snd; a.PRE[1] = A + Qn; a.preidx[1] = rcv;
-                } else {
-                    a.X[0] = A + Hb; a.W1[0] = Wt + b.W1[0];
-                }
-                a.W2 = Wt + b.W2; a.W3 = Wt + b.W3; a.tabs = Wt + b.tabs;
-                a.ln = 0;
-                a.OUT = bi == m.nblk - 1 ? y : A + Hb;
-                if (bi == m.nblk - 1) { a.STATS = reinterpret_cast<double*>(A + part); slots = train_fwd_stat_slots(L, nt_e); }
-                HIPCHK(h, launch_mlp_fwd(L, 1, a, st));
-            }
+            TrainFwdArgs in = fwd_inputs(E, nt_e, e);
+            in.PRE[0] = A + Pn; in.preidx[0] = snd; in.PRE[1] = A + Qn; in.preidx[1] = rcv;
+            HIPCHK(h, mlp(m, in, y, 2));                                     // (the e block of W1 per edge)
             HIPCHK(h, ln_edges(m, y, e));                                    // e <- e + LN(y), agg <- segmented sum of LN(y)
         } else if (E > 0) {
-            HIPCHK(h, mlp(T.m_pe[0][k], E, nt_e, v, snd, v, rcv, e, y));
+            HIPCHK(h, mlp(T.m_pe[0][k], fwd_inputs(E, nt_e, v, snd, v, rcv, e), y));
             HIPCHK(h, ln_edges(T.m_pe[0][k], y, e));
         } else {
             HIPCHK(h, launch_segment_sum(L, y, rowptr, nullptr, nullptr, A + agg, (int32_t)N, st));   // (no edges: zero aggregates)
         }
-        HIPCHK(h, mlp(T.m_pn[k], N, nt_n, v, nullptr, A + agg, nullptr, nullptr, y));
+        HIPCHK(h, mlp(T.m_pn[k], fwd_inputs(N, nt_n, v, nullptr, A + agg), y));
         HIPCHK(h, ln(T.m_pn[k], y, N, v, v, nullptr));                       // v <- v + LN(MLP_v([v; agg]))
         return MGN_OK;
     }
 };
 
-int lnall_prepare(mgn_engine* h, const char* who, bool with_encoders) {
+int lnall_prepare(mgn_engine* h) {
     if (!h) return MGN_E_ARG;
     if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
     if (!h->have_params) return fail(h, MGN_E_STATE, "mgn_set_params has not been called");
@@ -1535,7 +1571,6 @@ int lnall_prepare(mgn_engine* h, const char* who, bool with_encoders) {
     TrainState& T = *h->train;
     if (!T.packed)
         if (int rc = pack_training_weights(h)) return rc;
-    (void)who; (void)with_encoders;
     return MGN_OK;
 }
 
@@ -1581,11 +1616,7 @@ int lnall_bind(mgn_engine* h, LnAll& X, size_t floats) {
         HIPCHK(h, hipMemcpy(T.la_idx.p, eg.data(), eg.size() * 4, hipMemcpyHostToDevice));
         T.la_ready = true;
     }
-    X.A = T.la.as<float>();
-    X.snd = h->es[0].d_snd.as<int32_t>();
-    X.rcv = h->es[0].d_rcv.as<int32_t>();
-    X.rowptr = h->es[0].d_rowptr.as<int32_t>();
-    X.egid = T.la_idx.as<int32_t>();
+    X.attach();
     return MGN_OK;
 }
 
@@ -1594,7 +1625,7 @@ int lnall_bind(mgn_engine* h, LnAll& X, size_t floats) {
 namespace mgn {
 
 int lnall_forward(mgn_engine* h, const float* nf, const float* ef, float* out) {
-    if (int rc = lnall_prepare(h, "mgn_forward", true)) return rc;
+    if (int rc = lnall_prepare(h)) return rc;
     h->lnall_edges = false;                             // (the arena is shared with the resident right-hand side)
     const mgn_config& c = h->cfg;
     const LocalGraph& g = h->g;
@@ -1616,16 +1647,16 @@ int lnall_forward(mgn_engine* h, const float* nf, const float* ef, float* out) {
         HIPCHK(h, launch_affine_pad(A + X.ef_raw, c.Fe, nullptr, 0, nullptr, nullptr, A + X.ef_pad, L, g.set[0].E, st));
     }
     // encoders
-    HIPCHK(h, X.mlp(T.m_en, X.N, X.nt_n, A + X.nf_pad, nullptr, nullptr, nullptr, nullptr, A + X.Y));
+    HIPCHK(h, X.mlp(T.m_en, fwd_inputs(X.N, X.nt_n, A + X.nf_pad), A + X.Y));
     HIPCHK(h, X.ln(T.m_en, A + X.Y, X.N, nullptr, A + X.V, nullptr));
     if (X.E > 0) {
-        HIPCHK(h, X.mlp(T.m_ee[0], X.E, X.nt_e, A + X.ef_pad, X.egid, nullptr, nullptr, nullptr, A + X.Y));
+        HIPCHK(h, X.mlp(T.m_ee[0], fwd_inputs(X.E, X.nt_e, A + X.ef_pad, X.egid), A + X.Y));
         HIPCHK(h, X.ln(T.m_ee[0], A + X.Y, X.E, nullptr, A + X.Ecur, nullptr));
     }
     for (int k = 0; k < c.mps; ++k)
         if (int rc = X.step(k)) return rc;
     // decoder (no LayerNorm): the first O columns of its output, back in the caller's row order
-    HIPCHK(h, X.mlp(T.m_de, X.N, X.nt_n, A + X.V, nullptr, nullptr, nullptr, nullptr, A + X.Y));
+    HIPCHK(h, X.mlp(T.m_de, fwd_inputs(X.N, X.nt_n, A + X.V), A + X.Y));
     HIPCHK(h, launch_extract_cols(A + X.Y, L, c.O, nullptr, A + X.agg, X.N, st));
     HIPCHK(h, launch_permute_rows(A + X.tmp, A + X.agg, ngid, X.N, c.O, true, st));
     HIPCHK(h, hipMemcpyAsync(out, A + X.tmp, (size_t)X.N * c.O * 4, hipMemcpyDefault, st));
@@ -1634,7 +1665,7 @@ int lnall_forward(mgn_engine* h, const float* nf, const float* ef, float* out) {
 }
 
 int lnall_processor_steps(mgn_engine* h, float* v, float* e, int32_t nsteps) {
-    if (int rc = lnall_prepare(h, "mgn_processor_steps", false)) return rc;
+    if (int rc = lnall_prepare(h)) return rc;
     h->lnall_edges = false;
     const mgn_config& c = h->cfg;
     const LocalGraph& g = h->g;
@@ -1673,7 +1704,7 @@ int lnall_processor_steps(mgn_engine* h, float* v, float* e, int32_t nsteps) {
 // features, frozen e_norm: the edge encoder runs once per trajectory).  Launches only -- no host copy, no synchronisation -- once
 // lnall_rhs_prepare has bound the arena, so the rollout driver can capture it.
 int lnall_rhs_prepare(mgn_engine* h) {
-    if (int rc = lnall_prepare(h, "right-hand side", true)) return rc;
+    if (int rc = lnall_prepare(h)) return rc;
     size_t floats = 0;
     LnAll X = lnall_layout(h, true, floats);
     return lnall_bind(h, X, floats);
@@ -1685,11 +1716,7 @@ int lnall_rhs_dev(mgn_engine* h, const float* srcA, float* out, bool reuse_edges
     LnAll X = lnall_layout(h, true, floats);
     TrainState& T = X.T;
     if (!T.la.p || T.la.bytes < floats * 4 || !T.la_ready) return fail(h, MGN_E_STATE, "whole-array LayerNorm: the right-hand side was not prepared");
-    X.A = T.la.as<float>();
-    X.snd = h->es[0].d_snd.as<int32_t>();
-    X.rcv = h->es[0].d_rcv.as<int32_t>();
-    X.rowptr = h->es[0].d_rowptr.as<int32_t>();
-    X.egid = T.la_idx.as<int32_t>();
+    X.attach();
     float* A = X.A;
     hipStream_t st = X.st;
     const int L = c.L;
@@ -1700,20 +1727,20 @@ int lnall_rhs_dev(mgn_engine* h, const float* srcA, float* out, bool reuse_edges
     float* padded = ngid ? A + X.tmp : A + X.nf_pad;
     HIPCHK(h, launch_affine_pad(srcA, h->in_wa, h->d_nfB.as<float>(), h->in_wb, ns, ns ? ns + c.Fn : nullptr, padded, L, X.N, st));
     if (ngid) HIPCHK(h, launch_permute_rows(A + X.nf_pad, A + X.tmp, ngid, X.N, L, false, st));
-    HIPCHK(h, X.mlp(T.m_en, X.N, X.nt_n, A + X.nf_pad, nullptr, nullptr, nullptr, nullptr, A + X.Y));
+    HIPCHK(h, X.mlp(T.m_en, fwd_inputs(X.N, X.nt_n, A + X.nf_pad), A + X.Y));
     HIPCHK(h, X.ln(T.m_en, A + X.Y, X.N, nullptr, A + X.V, nullptr));
     if (X.E > 0) {
         if (!reuse_edges) {
             const float* es = h->have_enorm ? nrm + 2 * c.Fn : nullptr;
             HIPCHK(h, launch_affine_pad(h->es[0].d_ef.as<float>(), c.Fe, nullptr, 0, es, es ? es + c.Fe : nullptr, A + X.ef_pad, L, X.E, st));
-            HIPCHK(h, X.mlp(T.m_ee[0], X.E, X.nt_e, A + X.ef_pad, h->in_local ? nullptr : X.egid, nullptr, nullptr, nullptr, A + X.Y));
+            HIPCHK(h, X.mlp(T.m_ee[0], fwd_inputs(X.E, X.nt_e, A + X.ef_pad, h->in_local ? nullptr : X.egid), A + X.Y));
             HIPCHK(h, X.ln(T.m_ee[0], A + X.Y, X.E, nullptr, A + X.E0, nullptr));
         }
         HIPCHK(h, hipMemcpyAsync(A + X.Ecur, A + X.E0, (size_t)X.E * L * 4, hipMemcpyDeviceToDevice, st));
     }
     for (int k = 0; k < c.mps; ++k)
         if (int rc = X.step(k)) return rc;
-    HIPCHK(h, X.mlp(T.m_de, X.N, X.nt_n, A + X.V, nullptr, nullptr, nullptr, nullptr, A + X.Y));
+    HIPCHK(h, X.mlp(T.m_de, fwd_inputs(X.N, X.nt_n, A + X.V), A + X.Y));
     const float* os = h->have_onorm ? nrm + 2 * c.Fn + 2 * c.Fe : nullptr;
     HIPCHK(h, launch_rhs_epilogue(A + X.Y, L, c.O, os, os ? os + c.O : nullptr, h->have_mask ? h->d_mask.as<float>() : nullptr,
                                   h->d_own_gid.as<int32_t>(), out, X.N, st));
@@ -1732,8 +1759,7 @@ extern "C" int mgn_forward_vjp(mgn_handle* h, const float* nf, const float* ef, 
     if (int rc = train_prepare(h, "mgn_forward_vjp", n_grads)) return rc;
     if (!ef && h->g.set[0].E > 0) return fail(h, MGN_E_ARG, "mgn_forward_vjp: null argument");
     TrainJob J;
-    J.vjp = true;
-    J.fvjp = true;
+    J.kind = JOB_FORWARD_VJP;
     J.nf = nf; J.ef = ef; J.lambda = ybar; J.out = out; J.nfbar = nfbar; J.grads = grads;
     return train_run(h, J);
 } MGN_CATCH(h)

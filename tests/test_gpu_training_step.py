@@ -331,6 +331,55 @@ def test_step_device_arrays_and_graph_replay():
         eng.step(nf, ef, target, mask, out=np.zeros(eng.param_count + 1, np.float32))
 
 
+def test_graph_slots_shared_across_entry_points():
+    """mgn_step, mgn_ode_vjp and mgn_forward_vjp interleaved on one handle: the forward sequence (graph slot 0) is every entry's, the step's
+    reverse pass has slot 1 and the two VJPs share slot 2.  Four rounds take each slot through eager run, capture and replay with another
+    entry's launches in between; every output has to be bitwise the same in all rounds and equal to what a fresh handle returns on its
+    first (eager) call of that entry alone.  New inputs must show through the replays: the step against the oracle."""
+    cfg = cfg_dict(L=128, mps=3)
+    pos, s, r = small_mesh(14, 11)
+    N = pos.shape[0]
+    ps = make_params(cfg)
+    nf, ef, target, mask = problem(cfg, pos, s, r, seed=41)
+    rng = np.random.default_rng(42)
+    onehot = orc.one_hot(rng.integers(0, 7, N), 7, 0).astype(np.float32)
+    ef_raw = orc.edge_features(pos, s, r).astype(np.float32)
+    x = rng.standard_normal((N, 2)).astype(np.float32)
+    lam = rng.standard_normal((N, 2)).astype(np.float32)
+    ybar = rng.standard_normal((N, 2)).astype(np.float32)
+    vm = (rng.random(N) < 0.7).astype(np.float32)
+    ns, nsh = orc.NormMeanStd(np.array([1.0, 0.1]), np.array([0.4, 0.2])).affine(2)
+    ts, tsh = orc.NormMinMax(0.0, 1.0).affine(7)
+    es, esh = orc.NormMeanStd(ef_raw.mean(0), ef_raw.std(0)).affine(3)
+
+    def engine():
+        eng = engine_for(cfg)
+        eng.set_params(ps)
+        eng.set_graph(s, r, N)
+        eng.set_norms(node=(np.concatenate([ns, ts]), np.concatenate([nsh, tsh])), edge=(es, esh), out=(np.array([0.5, 0.4]), np.array([0.01, -0.02])))
+        return eng
+
+    entries = {
+        "step": lambda e, d=0.0: e.step(nf + d, ef, target, mask),
+        "ode_vjp": lambda e, d=0.0: e.ode_vjp(x + d, onehot, ef_raw, lam, val_mask=vm, want_dxdt=True),
+        "forward_vjp": lambda e, d=0.0: e.forward_vjp(nf + d, ef, ybar, want_out=True),
+    }
+    same = lambda a, b: all(np.array_equal(np.asarray(u), np.asarray(v)) for u, v in zip(a, b))
+    eng = engine()
+    rounds = [{k: f(eng) for k, f in entries.items()} for _ in range(4)]
+    for k, f in entries.items():
+        for rd in rounds[1:]:
+            assert same(rd[k], rounds[0][k]), k
+            assert k != "step" or rd[k][1] == rounds[0][k][1]
+        assert same(f(engine()), rounds[0][k]), k                  # a fresh handle's first call of this entry alone
+    fifth = {k: f(eng, np.float32(0.25)) for k, f in entries.items()}     # replayed graphs, new inputs
+    for k in entries:
+        assert not any(np.array_equal(np.asarray(u), np.asarray(v)) for u, v in zip(fifth[k], rounds[0][k])), k
+    ref, rl = orc.step_grads(ps, cfg, nf + np.float32(0.25), ef, s, r, target, mask)
+    assert abs(fifth["step"][1] - rl) <= TOL_LOSS * abs(rl)
+    check_grads(fifth["step"][0], ref, cfg)
+
+
 def test_step_factored_first_layer_above_the_cooperative_range(monkeypatch):
     """Above 2048 edge tiles the edge MLPs run with the factored first layer (P = v W1s, Q = v W1r per node; backward and
     weight gradients through the summed rows of GZ1): against the float64 oracle and against the un-factored kernels on
