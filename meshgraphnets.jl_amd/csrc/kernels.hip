@@ -2703,7 +2703,8 @@ static bool coop_ok(int L, int ntiles, const float* const* chunk_t, bool edge = 
 // which kernel family the last fp32 edge launch went to (bench.py labels its roofline with what RAN, not with the global switches):
 // 1 generic hidden_layers, 2 16-row small-graph, 3 cooperative 4-wave tiles, 4 all-streaming, (5, 6: kernels retired in round 5,)
 // 7 k_edge_ring<8>, 8 k_edge_ring<4>, 9 k_edge_step<4,2> (fp32-MFMA persistent), (10, 11: retired,) 12 k_edge_coop16m on the
-// split path, 13 / 14 k_edge_ring_h<8 / 4> (two fp16 pieces: the default of large fp32 launches)
+// split path, 13 / 14 k_edge_ring_h<8 / 4> (two fp16 pieces: the default of large fp32 launches); bf16 mode: 18 k_edge_bf16_pipe
+// (its small graphs run the 16-row kernels on the bf16 arrays and record their codes)
 static int g_last_edge_kernel = 0;
 int last_edge_kernel() { return g_last_edge_kernel; }
 // the family of the launch that carries a set's edges: a launch over less than half of the set's tiles (the boundary tiles of a partitioned pass,
@@ -2831,7 +2832,7 @@ hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 static int g_last_node_kernel = 0;    // family of the last node-MLP launch (tests / bench): 1 general, 2 16-row cooperative, 3 cooperative,
-int last_node_kernel() { return g_last_node_kernel; }   // 5 k_node_split, 6 k_node_split<two sets>, 7 fp32-MFMA k_node_step, 8 / 9 16-row kernels on the split path, 10 k_node_split_h
+int last_node_kernel() { return g_last_node_kernel; }   // 5 k_node_split, 6 k_node_split<two sets>, 7 fp32-MFMA k_node_step, 8 / 9 16-row kernels on the split path, 10 k_node_split_h, 12 k_node_bf16_pipe
 hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
     if (a.mode != 2) g_last_node_kernel = a.gen.use ? 1 : (a.c16 && L == 128 && a.chunk_t[0]) ? 2 : coop_ok(L, a.ntiles, a.chunk_t) ? 3 : 7;
@@ -3004,10 +3005,12 @@ static LaunchCfg bf_launch(int ntiles, int nchunks) {
 }
 hipError_t launch_edge_bf16(const BfEdgeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
+    SET_LAST_EDGE(a, 18);
     return launch_k(k_edge_bf16_pipe, a, bf_launch(a.ntiles, 3), s);   // software-pipelined: two waves per SIMD, 256 registers
 }
 hipError_t launch_node_bf16(const BfNodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
+    g_last_node_kernel = 12;
     return launch_k(k_node_bf16_pipe, a, bf_launch(a.ntiles, 4), s);
 }
 hipError_t launch_project_bf16(const BfNodeArgs& a, hipStream_t s) {

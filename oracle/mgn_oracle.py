@@ -594,3 +594,138 @@ def tsit5_rollout(f, x0, t0, t1, saves, abstol=1e-6, reltol=1e-3, dt0=0.0):
     while len(out) < len(saves):
         out.append(u.copy())
     return np.stack(out), dict(n_accept=nacc, n_reject=nrej, n_rhs=nrhs)
+
+
+# --------------------------------------------------------------------------------------------
+# bf16 mode of the processor: where the engine's kernels round  (DESIGN.md "bf16 rounding model")
+# The float64 oracle above with a rounding to bf16 (nearest even) at every point at which the engine's bf16 mode rounds, and the
+# per-receiver sums split into the pieces the edge kernels form.  What is left between this model and the kernels is fp32
+# accumulation order, which acc = np.float32 samples a second time.
+# --------------------------------------------------------------------------------------------
+def round_bf16(x):
+    """x rounded to bf16 (nearest, ties to even) as float32: u += 0x7FFF + ((u >> 16) & 1); u &= 0xFFFF0000 on the float32 bits, the
+    engine's f32_to_bf16 (mgn_api.cpp) -- bit-equal to it on finite input, denormals included."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    u = (u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) & np.uint32(0xFFFF0000)
+    return u.view(np.float32)
+
+
+def edge_pieces(receivers, order, tile_rows=32):
+    """The pieces of the aggregate: a piece is one receiver's edges inside one tile of `tile_rows` consecutive engine rows (engine
+    row j holds input edge order[j]).  Returns (start row of every piece, its receiver); a piece ends where the next one starts."""
+    r = np.asarray(receivers)[np.asarray(order)]
+    E = r.size
+    if E == 0:
+        return np.zeros(0, np.int64), np.zeros(0, r.dtype)
+    head = np.ones(E, bool)
+    head[1:] = r[1:] != r[:-1]
+    head[::tile_rows] = True
+    starts = np.nonzero(head)[0]
+    return starts, r[starts]
+
+
+def _bf16_edge_set(pe, WP, WQ, W1e, W2, W3, v, e, s, r, order, tile_rows, mfma, rnd, acc, fault):
+    """One edge set of one step: (e stored, the node aggregate).  fault: the sensitivity conditions of tests/test_bf16_model_host.py."""
+    N = v.shape[0]
+    Pm = rnd(v @ WP).astype(acc)                                     # k_project_bf16_pipe: bfq_pack<false> before both stores
+    Qm = rnd(v @ WQ + pe["b1"]).astype(acc)                          # (16-row kernels: c16_st_row<BF>)
+    h = Pm[s] + Qm[r] + e @ W1e                                      # fp32: bfq_unpack + bfq_acc_add, then the chain on top
+    h = np.maximum(h, 0)
+    if mfma:
+        h = rnd(h).astype(acc)                                       # bf_edge_tile: bfq_pack<true> after layer 1
+    h = np.maximum(h @ W2 + pe["b2"], 0)
+    if mfma:
+        h = rnd(h).astype(acc)                                       # ... after layer 2
+    e_new = layer_norm(h @ W3 + pe["b3"], pe["ln_scale"], pe["ln_bias"])     # fp32 up to here
+    e_out = rnd(e + e_new).astype(acc)                               # one rounding of the fp32 sum (bf_pk2 / c16_st_tile<BF>)
+    en = e_new[order]
+    if fault and "no_residual" in fault:
+        i = fault["no_residual"]
+        e_out[i] = rnd(e_new[i]).astype(acc)
+    if fault and "drop_row" in fault:                                # engine row j is not computed: no store, no share of the sum
+        j = fault["drop_row"]
+        en = en.copy()
+        en[j] = 0
+        e_out[order[j]] = e[order[j]]
+    starts, pr = edge_pieces(r, order, tile_rows)
+    if starts.size:
+        pieces = rnd(np.add.reduceat(en, starts, axis=0)).astype(acc)    # summed unrounded, one rounding per piece (AGG / CARRY row)
+    else:
+        pieces = np.zeros((0, v.shape[1]), acc)
+    if fault and "piece_src" in fault:
+        orig = pieces.copy()
+        for p, q in fault["piece_src"].items():
+            pieces[p] = orig[q] if q >= 0 else 0
+    agg = np.zeros((N, v.shape[1]), acc)
+    np.add.at(agg, pr, pieces)                                       # the node kernel adds the pieces of a run in fp32
+    if mfma:
+        agg = rnd(agg).astype(acc)                                   # bf_agg_sum: bf_pk2 of the sum (one piece: unchanged)
+    if fault and "agg_from" in fault:
+        for n, m in fault["agg_from"].items():
+            agg[n] = agg[m]
+    return e_out, agg
+
+
+def processor_steps_bf16(packed, cfg, v, e, senders, receivers, nsteps, order, tile_rows=32, mode="mfma", acc=np.float64, set2=None,
+                         fault=None, all_steps=False):
+    """processor_steps as the engine's bf16 mode computes it, up to fp32 summation order.
+    order: the engine's edge order (Engine.local_edges(); one partition: the stable sort by receiver).
+    mode "mfma": k_edge_bf16_pipe / k_node_bf16_pipe / k_project_bf16_pipe -- bf16 weight chunks (pack_chunk_bf16), latents rounded
+        on import (k_tile_f32_to_bf16), P and Q rounded, the edge and node MLPs rounded after the ReLUs of layers 1 and 2, layer 3 and
+        LayerNorm fp32, e and v stored as round(x + x'), e' summed unrounded per piece (edge_pieces, 32-edge tiles), one rounding per
+        piece, the pieces of a receiver added and rounded once more.
+    mode "storage": the 16-row kernels on the bf16 arrays -- fp32 weights and arithmetic, rounding at the stores of V, E, P, Q and of
+        the pieces only (tile_rows = 16); the sum of a receiver's pieces stays fp32.
+    mode "exact": no rounding at all (== processor_steps).
+    acc: the type of every product and sum; np.float32 samples the kernels' fp32 accumulation a second time.
+    set2 = (e2, senders2, receivers2, order2).  fault = dict(step = k, ...): one fault planted in step k of set 1 (_bf16_edge_set).
+    Returns (v, e[, e2]) after nsteps, or with all_steps the list of these after every step."""
+    if mode not in ("mfma", "storage", "exact"):
+        raise ValueError("mode must be mfma, storage or exact")
+    mfma = mode == "mfma"
+    rnd = (lambda x: x) if mode == "exact" else round_bf16
+    h, L = cfg["hidden_layers"], cfg["L"]
+    if h != 2:
+        raise ValueError("the bf16 mode exists for hidden_layers = 2")
+    P32 = _unpack(packed, cfg, np.float32)
+
+    def blk(name):
+        d = {}
+        for key, val in P32[name].items():
+            d[key] = (rnd(val) if (mfma and key.startswith("W")) else val).astype(acc)     # chunks rounded; biases and LayerNorm tables fp32
+        return d
+
+    senders, receivers, order = np.asarray(senders), np.asarray(receivers), np.asarray(order)
+    v = rnd(np.asarray(v, np.float32)).astype(acc)
+    e = rnd(np.asarray(e, np.float32)).astype(acc)
+    if set2 is not None:
+        e2, s2, r2, order2 = set2
+        e2, s2, r2, order2 = rnd(np.asarray(e2, np.float32)).astype(acc), np.asarray(s2), np.asarray(r2), np.asarray(order2)
+    out = []
+    for k in range(nsteps):
+        f = fault if (fault and fault.get("step", 0) == k) else None
+        pe = blk("proc%d_edge" % k)
+        W1 = pe["W1"]
+        e, agg = _bf16_edge_set(pe, W1[:L], W1[L:2 * L], W1[2 * L:], pe["W2"], pe["W3"], v, e, senders, receivers, order, tile_rows, mfma,
+                                rnd, acc, f)
+        aggs = [agg]
+        if set2 is not None:
+            pe2 = blk("proc%d_edge2" % k)
+            W1 = pe2["W1"]
+            e2, agg2 = _bf16_edge_set(pe2, W1[:L], W1[L:2 * L], W1[2 * L:], pe2["W2"], pe2["W3"], v, e2, s2, r2, order2, tile_rows, mfma,
+                                      rnd, acc, None)
+            aggs.append(agg2)
+        pn = blk("proc%d_node" % k)
+        x = pn["b1"] + v @ pn["W1"][:L]                              # k_node_bf16_pipe: b1, the node part, the aggregate part(s)
+        for q, a_ in enumerate(aggs):
+            x = x + a_ @ pn["W1"][(1 + q) * L:(2 + q) * L]
+        x = np.maximum(x, 0)
+        if mfma:
+            x = rnd(x).astype(acc)
+        x = np.maximum(x @ pn["W2"] + pn["b2"], 0)
+        if mfma:
+            x = rnd(x).astype(acc)
+        v_new = layer_norm(x @ pn["W3"] + pn["b3"], pn["ln_scale"], pn["ln_bias"])
+        v = rnd(v + v_new).astype(acc)
+        out.append((v, e) if set2 is None else (v, e, e2))
+    return out if all_steps else out[-1]

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 import mgn_oracle as orc
-from util import cfg_dict, engine_for, make_params, random_inputs, small_mesh
+from bf16_cases import rmax, row_rel
+from util import cfg_dict, engine_for, last_kernels, make_params, random_inputs, small_mesh
 
 import mgn_amd
 from mgn_amd import synth
@@ -19,6 +20,32 @@ TOL_BF16 = 3e-2
 
 def rel_l2(a, ref):
     return float(np.linalg.norm(np.asarray(a, np.float64) - ref) / np.linalg.norm(ref))
+
+
+def model_of_what_ran(path):
+    """(mode, tile_rows) of mgn_oracle.processor_steps_bf16 for the kernels of the last step: kernel path 1 runs the bf16-MFMA kernels
+    (18 / 12) whatever the size; chosen automatically, these small graphs run the 16-row kernels on the bf16 arrays"""
+    fam = last_kernels()
+    if path == 1:
+        assert fam == (18, 12), fam
+        return "mfma", 32
+    assert fam[0] in (2, 12, 15) and fam[1] in (2, 8), fam
+    return "storage", 16
+
+
+def per_row_checks(what, path, got, ref, m64, m32, outside=0.0):
+    """assertion 4 of tests/test_gpu_bf16_regimes.py: per row against the float64 oracle <= 2 x the largest per-row error of the bf16
+    rounding model, globally <= 2 x the model's own; under kernel path 1, where one kernel family runs, assertion 3 too: per row
+    against the model <= 2 x the largest per-row difference between the model with float32 sums and with float64 sums.
+    outside: what the fp32 stages around the processor, which the model does not cover, may add to a row"""
+    to_orc, own = rmax(row_rel(got, ref)), rmax(row_rel(m64, ref))
+    to_model, spread = rmax(row_rel(got, m64)), rmax(row_rel(m32, m64))
+    print(f"{what} path {path}: per row to the oracle {to_orc:.2e} (model {own:.2e}), global {rel_l2(got, ref):.2e} (model {rel_l2(m64, ref):.2e}), "
+          f"per row to the model {to_model:.2e} (spread {spread:.2e})")
+    assert to_orc <= 2.0 * own, (what, to_orc, own)
+    assert rel_l2(got, ref) <= 2.0 * rel_l2(m64, ref), what
+    if path == 1:
+        assert to_model <= 2.0 * spread + outside, (what, to_model, spread)
 
 
 @pytest.fixture(autouse=True, params=[0, 1], ids=["auto", "bf16-mfma"])
@@ -32,7 +59,7 @@ def bf16_family(request):
 
 
 @pytest.mark.parametrize("nsteps", [1, 15])
-def test_bf16_processor_steps(nsteps):
+def test_bf16_processor_steps(nsteps, bf16_family):
     cfg = cfg_dict(mps=15)
     pos, cells, _, _ = synth.mesh_cyl(1234, 500)
     s, r = synth.cells_to_edges(cells)
@@ -47,6 +74,12 @@ def test_bf16_processor_steps(nsteps):
     v1, e1 = eng.processor_steps(v, e, nsteps)
     rv, re = orc.processor_steps(ps, cfg, v, e, s, r, nsteps)
     assert rel_l2(v1, rv) <= TOL_BF16 and rel_l2(e1, re) <= TOL_BF16, (rel_l2(v1, rv), rel_l2(e1, re))
+    mode, tile_rows = model_of_what_ran(bf16_family)
+    kw = dict(tile_rows=tile_rows, mode=mode)
+    m64 = orc.processor_steps_bf16(ps, cfg, v, e, s, r, nsteps, eng.local_edges(), **kw)
+    m32 = orc.processor_steps_bf16(ps, cfg, v, e, s, r, nsteps, eng.local_edges(), acc=np.float32, **kw)
+    per_row_checks(f"v after {nsteps} steps", bf16_family, v1, rv, m64[0], m32[0])
+    per_row_checks(f"e after {nsteps} steps", bf16_family, e1, re, m64[1], m32[1])
     # and it is genuinely bf16: not bit-identical to the fp32 engine
     f32 = engine_for(cfg)
     f32.set_params(ps)
@@ -55,7 +88,17 @@ def test_bf16_processor_steps(nsteps):
     assert rel_l2(v2, rv) < rel_l2(v1, rv)
 
 
-def test_bf16_forward_and_ragged():
+def model_forward(ps, cfg, nf, ef, s, r, order, **kw):
+    """mgn_forward in bf16 mode: the encoders and the decoder are fp32 (float64 here), the processor is the rounding model on the
+    encoders' latents (rounded on their way into the bf16 arrays)"""
+    acc = kw.get("acc", np.float64)
+    P = orc._unpack(ps, cfg, acc)
+    v, e = orc.encode(P, np.asarray(nf, acc), np.asarray(ef, acc), 2)
+    v, e = orc.processor_steps_bf16(ps, cfg, v, e, s, r, cfg["mps"], order, **kw)
+    return orc.decode(P, np.asarray(v, acc), 2)
+
+
+def test_bf16_forward_and_ragged(bf16_family):
     cfg = cfg_dict(mps=3)
     ps = make_params(cfg)
     for (N, E, seed) in [(5, 1, 1), (40, 700, 3), (70, 2049, 5)]:
@@ -69,6 +112,13 @@ def test_bf16_forward_and_ragged():
         out = eng.forward(nf, ef)
         ref = orc.forward(ps, cfg, nf, ef, s, r)
         assert rel_l2(out, ref) <= TOL_BF16, (N, E, rel_l2(out, ref))
+        mode, tile_rows = model_of_what_ran(bf16_family)
+        kw = dict(tile_rows=tile_rows, mode=mode)
+        m64 = model_forward(ps, cfg, nf, ef, s, r, eng.local_edges(), **kw)
+        m32 = model_forward(ps, cfg, nf, ef, s, r, eng.local_edges(), acc=np.float32, **kw)
+        # the encoders and the decoder are the fp32 kernels: per row they are held to 2e-5 (ROW_TOL of
+        # tests/test_gpu_large_mesh_regimes.py), which is what they may add where no bf16 rounding differs (N = 5: spread 0)
+        per_row_checks(f"output N={N} E={E}", bf16_family, out, ref, m64, m32, outside=2e-5)
         assert np.array_equal(out, eng.forward(nf, ef))      # deterministic
 
 
