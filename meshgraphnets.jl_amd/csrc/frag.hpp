@@ -482,6 +482,11 @@ DEVINL void relu_quarter(f32x16& q) {
     for (int k = 0; k < 16; ++k) q[k] = fmaxf(q[k], 0.f);
 }
 
+DEVINL void zero_quarter(f32x16& q) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) q[k] = 0.f;
+}
+
 // LayerNorm statistics from the full row fragment, applied to this wave's quarter
 DEVINL void coop_layer_norm(f32x16& mine, const f32x16 (&full)[4], const float* gamma, const float* beta, int t, int h) {
     float s = 0.f;

@@ -93,6 +93,17 @@ struct NodeArgs {
     float h2_s[9], h2_rs[9], h2_b2pos;
 };
 
+// The weights of an encoder / decoder stage that chains N chunks (launch_enc_node: 0 W2, 1 W3, 2 WP, 3 WQ; launch_enc_edge: 0 W2, 1 W3;
+// launch_decode: 0 W1, 1 W2).  mgn_api.cpp fills it from the stage's ChunkRefs (stage_weights).
+template <int N>
+struct StageW {
+    const float* chunk[N];       // fragment order; the t-major copy of a chunk follows its fragment-major copy (mgn_set_params)
+    const uint16_t* splith[N];   // the same chunks as two fp16 pieces (split_common.hpp); null: not built
+    float h2_rs[N];              // 1 / chunk i's power of two
+    const float* tabs;           // encoders: b1, b2, b3, gamma, beta (node encoder: T_BQ = b1 of step 0's edge MLP); decoder: b1, b2
+    GenMlp gen;                  // decoder: chunk[0 .. nmid-1] = W2 .. W_h, no last chunk (L -> O runs on the VALU)
+};
+
 struct EncNodeArgs {
     int32_t n, ntiles;
     const int32_t* gid;     // [n] global node id of each owned node (row into srcA/srcB)
@@ -102,11 +113,7 @@ struct EncNodeArgs {
     const float* shift;
     const float* w1f;       // [Fn][L] first-layer weights, fragment order per input feature
     float* V; float* P; float* Q;
-    const float* chunk[MAX_CHUNKS];  // 0:W2 1:W3 2:WP 3:WQ
-    const float* tabs;
-    GenMlp gen;
-    const uint16_t* splith[4];       // the same chunks as two fp16 pieces (split_common.hpp), h2_rs[i] = 1 / chunk i's power of two; null: not built
-    float h2_rs[4];
+    StageW<4> w;
 };
 
 struct EncEdgeArgs {
@@ -116,11 +123,7 @@ struct EncEdgeArgs {
     const float* scale; const float* shift;
     const float* w1f;
     float* Elat;
-    const float* chunk[MAX_CHUNKS];  // 0:W2 1:W3
-    const float* tabs;
-    GenMlp gen;
-    const uint16_t* splith[2];       // see EncNodeArgs
-    float h2_rs[2];
+    StageW<2> w;
 };
 
 struct DecArgs {
@@ -133,11 +136,7 @@ struct DecArgs {
     const float* mask;      // [N] global val_mask, may be null
     const int32_t* gid;
     float* out;             // [n][O] local order
-    const float* chunk[MAX_CHUNKS];  // 0:W1 1:W2
-    const float* tabs;      // b1,b2
-    GenMlp gen;             // decoder: chunk[0 .. nmid-1] = W2 .. W_h, no last chunk (L -> O runs on the VALU)
-    const uint16_t* splith[2];       // see EncNodeArgs
-    float h2_rs[2];
+    StageW<2> w;
 };
 
 // ---- bf16 processor (BASELINE cfg-3 precision): bf16 storage + bf16 MFMA, fp32 accumulate / LayerNorm / residual /

@@ -1397,327 +1397,308 @@ DEVINL void e_chain_primed(f32x16& acc, const f32x16 (&in)[4], const float* chun
 }
 
 // ================================================================================================
-// Encoder, node side (K0a+K1) + projection of step-0 P,Q.  chunk[0]=W2 [1]=W3 [2]=WP [3]=WQ
+// Encoder and decoder stages: the node encoder (K0a+K1, + the projection of step-0 P, Q), the edge encoder (K0b+K2) and the decoder
+// (K7, + inverse normaliser + val_mask epilogue, K8).  Two skeletons -- stage_tiles, one wave per tile, and stage_coop, four waves per
+// tile like k_node_coop (L = 128: on a cylinder-sized mesh the one-wave-per-tile encoder / decoder cost 60 + 32 us of every 840 us
+// right-hand side of a rollout) -- over one policy per stage, which says where a row's input comes from, how many chunks the stage
+// chains and what follows the two hidden layers.  Chunk order (StageW): node encoder 0 W2, 1 W3, 2 WP, 3 WQ; edge encoder 0 W2, 1 W3;
+// decoder 0 W1, 1 W2 (its last layer, L -> O, runs on the VALU).
 // ================================================================================================
-template <int NT, int NRES, bool GEN = false, bool H2 = false>
-__global__ __launch_bounds__(512, 2) void k_enc_node(const EncNodeArgs a) {
+// this lane's row of a tile: whether it exists, the row -- 0 on a padding lane, so that every address stays in bounds -- and the source
+// row of its input features (null gid: the source rows are already in local order)
+template <class I>
+struct StageRow { bool valid; I r; int64_t g; };
+template <class I, class G>
+DEVINL StageRow<I> stage_row(int tile, int c, I rows, const G* gid) {
+    const I i = (I)tile * TILE + c;
+    const bool valid = i < rows;
+    const I r = valid ? i : 0;
+    return {valid, r, gid ? (int64_t)gid[r] : (int64_t)r};
+}
+
+// block prologue of the one-wave kernels: the first NRES chunks and the tables go to LDS; w[i] is where chunk i is read from, LDS or L2,
+// as fp32 fragments or (H2) as its fp16 pieces.  Returns the tables.
+template <int NT, int NRES, bool H2, int N>
+DEVINL const float* stage_prologue(float* smem, const StageW<N>& sw, const float* (&w)[N]) {
     constexpr int L = 32 * NT, CH = 16 * NT * 64 * NT;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+    static_assert(NRES <= N, "a stage has no more chunks than it chains");
 #pragma unroll
-    for (int r = 0; r < NRES; ++r) copy_to_lds(smem + r * CH, H2 ? reinterpret_cast<const float*>(a.splith[r]) : a.chunk[r], CH);
+    for (int i = 0; i < N; ++i) {
+        const float* src = H2 ? reinterpret_cast<const float*>(sw.splith[i]) : sw.chunk[i];
+        if (i < NRES) copy_to_lds(smem + i * CH, src, CH);
+        w[i] = i < NRES ? smem + i * CH : src;
+    }
     float* tb = smem + NRES * CH;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
+    copy_to_lds(tb, sw.tabs, T_COUNT * L);
     __syncthreads();
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float* w2 = NRES > 0 ? smem : (H2 ? reinterpret_cast<const float*>(a.splith[0]) : a.chunk[0]);
-    const float* w3 = NRES > 1 ? smem + CH : (H2 ? reinterpret_cast<const float*>(a.splith[1]) : a.chunk[1]);
-    const float* wp = NRES > 2 ? smem + 2 * CH : (H2 ? reinterpret_cast<const float*>(a.splith[2]) : a.chunk[2]);
-    const float* wq = NRES > 3 ? smem + 3 * CH : (H2 ? reinterpret_cast<const float*>(a.splith[3]) : a.chunk[3]);
+    return tb;
+}
 
-    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
-        OPAQUE_LANE();
-        const int n = tw.tile * TILE + c;
-        const bool valid = n < a.n;
-        const int nn = valid ? n : 0;
-        const int64_t g = a.gid ? a.gid[nn] : nn;     // null gid: the source rows are already in local order
-        f32x16 acc[NT], y[NT];
-        tab_frag<NT>(acc, tb + T_B1 * L, h);
-        const int Fn = a.wa + a.wb;
-        for (int k = 0; k < Fn; ++k) {
-            float xk = (k < a.wa) ? a.srcA[g * a.wa + k] : a.srcB[g * a.wb + (k - a.wa)];
-            if (a.scale) xk = fmaf(xk, a.scale[k], a.shift[k]);
-            first_layer<NT>(acc, a.w1f, k, xk, h);
-        }
-        if constexpr (GEN) {
-            gen_hidden<NT>(acc, y, a.gen, lane, h);
-            gen_final<NT>(acc, y, a.gen, lane, h);
-        } else {
-            relu_frag<NT>(acc);
-            tab_frag<NT>(y, tb + T_B2 * L, h);
-            enc_chunk<NT, (NRES > 0), H2>(y, acc, w2, lane, a.h2_rs[0]);
-            relu_frag<NT>(y);
-            tab_frag<NT>(acc, tb + T_B3 * L, h);
-            enc_chunk<NT, (NRES > 1), H2>(acc, y, w3, lane, a.h2_rs[1]);
-        }
-        layer_norm_frag<NT>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
-        if (!valid) zero_frag<NT>(acc);                          // padding rows stay zero (checksums)
-        store_frag<NT>(tile_ptr(a.V, tw.tile, L, lane), STRIDE_TILE, acc);
-        zero_frag<NT>(y);
-        enc_chunk<NT, (NRES > 2), H2>(y, acc, wp, lane, a.h2_rs[2]);
-        if (valid) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, y);
-        tab_frag<NT>(y, tb + T_BQ * L, h);
-        enc_chunk<NT, (NRES > 3), H2>(y, acc, wq, lane, a.h2_rs[3]);
-        if (valid) store_frag<NT>(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, y);
+// layer 1 of an encoder (a handful of input features: VALU): the bias table, then per feature the optional input normaliser and
+// first_layer.  S::feature reads feature k of source row g.
+template <class S, int NT>
+DEVINL void input_layer(f32x16 (&acc)[NT], const typename S::Args& a, const float* tb, int64_t g, int h) {
+    tab_frag<NT>(acc, tb + T_B1 * 32 * NT, h);
+    const int F = S::width(a);
+    for (int k = 0; k < F; ++k) {
+        float xk = S::feature(a, g, k);
+        if (a.scale) xk = fmaf(xk, a.scale[k], a.shift[k]);
+        first_layer<NT>(acc, a.w1f, k, xk, h);
     }
 }
 
-// ================================================================================================
-// Cooperative node encoder and decoder for small meshes (L = 128): 4 waves per tile like k_node_coop.  On a cylinder-sized
-// mesh the one-wave-per-tile encoder / decoder cost 60 + 32 us of every 840 us right-hand side of a rollout.
-// ================================================================================================
-// chunk[0]=W2 [1]=W3 [2]=WP [3]=WQ; the t-major copy of a chunk follows its fragment-major copy (mgn_set_params)
-template <bool FENCE, bool H2 = false>
-__global__ __launch_bounds__(256, 2) void k_enc_node_coop(const EncNodeArgs a) {
-    constexpr int L = 128, CH = L * L;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* xch0 = reinterpret_cast<f32x4*>(smem);
-    f32x4* xch1 = xch0 + 16 * 64;
-    float* tb = smem + 2 * 16 * 64 * 4;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tq = wave;
-    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        OPAQUE_LANE();
-        const int n = tile * TILE + c;
-        const bool valid = n < a.n;
-        const int nn = valid ? n : 0;
-        const int64_t g = a.gid ? a.gid[nn] : nn;     // null gid: the source rows are already in local order
-        f32x16 in[4], acc;
-        ERing<H2> r2, r3;
-        e_prime<H2>(r2, a.chunk[0], a.splith[0], tq, lane);
-        // layer 1 (a handful of input features: VALU), every wave the full row
-        tab_frag<4>(in, tb + T_B1 * L, h);
-        const int Fn = a.wa + a.wb;
-        for (int k = 0; k < Fn; ++k) {
-            float xk = (k < a.wa) ? a.srcA[g * a.wa + k] : a.srcB[g * a.wb + (k - a.wa)];
-            if (a.scale) xk = fmaf(xk, a.scale[k], a.shift[k]);
-            first_layer<4>(in, a.w1f, k, xk, h);
-        }
-        relu_frag<4>(in);
-        tab_quarter(acc, tb + T_B2 * L, tq, h);
-        e_prime<H2>(r3, a.chunk[1], a.splith[1], tq, lane);
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[0], a.splith[0], a.h2_rs[0], tq, lane, r2);                            // layer 2
-        relu_quarter(acc);
-        coop_exchange(in, acc, xch0, wave, lane);
-        tab_quarter(acc, tb + T_B3 * L, tq, h);
-        e_prime<H2>(r2, a.chunk[2], a.splith[2], tq, lane);
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[1], a.splith[1], a.h2_rs[1], tq, lane, r3);                            // layer 3
-        coop_exchange(in, acc, xch1, wave, lane);
-        coop_layer_norm(acc, in, tb + T_GAMMA * L, tb + T_BETA * L, tq, h);
-        if (!valid) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc[k] = 0.f;                        // padding rows stay zero (checksums)
-        }
-        store_quarter(tile_ptr(a.V, tile, L, lane), STRIDE_TILE, tq, acc);
-        e_prime<H2>(r3, a.chunk[3], a.splith[3], tq, lane);
-        coop_exchange(in, acc, xch0, wave, lane);                            // full latent row for the projection
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[2], a.splith[2], a.h2_rs[2], tq, lane, r2);
-        if (valid) store_quarter(prow_ptr(a.P, nn, L, h), STRIDE_PROW, tq, acc);
-        tab_quarter(acc, tb + T_BQ * L, tq, h);
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[3], a.splith[3], a.h2_rs[3], tq, lane, r3);
-        if (valid) store_quarter(prow_ptr(a.Q, nn, L, h), STRIDE_PROW, tq, acc);
-        __syncthreads();
+// layers 2 and 3 of an encoder on layer 1's pre-activations in acc; the result is in acc, y is scratch
+template <int NT, int NRES, bool GEN, bool H2, int N>
+DEVINL void enc_middle(f32x16 (&acc)[NT], f32x16 (&y)[NT], const StageW<N>& sw, const float* const (&w)[N], const float* tb, int lane, int h) {
+    constexpr int L = 32 * NT;
+    if constexpr (GEN) {
+        gen_hidden<NT>(acc, y, sw.gen, lane, h);
+        gen_final<NT>(acc, y, sw.gen, lane, h);
+    } else {
+        relu_frag<NT>(acc);
+        tab_frag<NT>(y, tb + T_B2 * L, h);
+        enc_chunk<NT, (NRES > 0), H2>(y, acc, w[0], lane, sw.h2_rs[0]);
+        relu_frag<NT>(y);
+        tab_frag<NT>(acc, tb + T_B3 * L, h);
+        enc_chunk<NT, (NRES > 1), H2>(acc, y, w[1], lane, sw.h2_rs[1]);
     }
 }
 
-// edge encoder: chunk[0]=W2 [1]=W3
-template <bool FENCE, bool H2 = false>
-__global__ __launch_bounds__(256, 2) void k_enc_edge_coop(const EncEdgeArgs a) {
-    constexpr int L = 128, CH = L * L;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* xch0 = reinterpret_cast<f32x4*>(smem);
-    f32x4* xch1 = xch0 + 16 * 64;
-    float* tb = smem + 2 * 16 * 64 * 4;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tq = wave;
-    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        OPAQUE_LANE();
-        const int64_t eid = (int64_t)tile * TILE + c;
-        const bool valid = eid < a.E;
-        const int64_t g = a.gid ? a.gid[valid ? eid : 0] : (valid ? eid : 0);
-        f32x16 in[4], acc;
-        ERing<H2> r2, r3;
-        e_prime<H2>(r2, a.chunk[0], a.splith[0], tq, lane);
-        tab_frag<4>(in, tb + T_B1 * L, h);
-        for (int k = 0; k < a.Fe; ++k) {
-            float xk = a.ef[g * a.Fe + k];
-            if (a.scale) xk = fmaf(xk, a.scale[k], a.shift[k]);
-            first_layer<4>(in, a.w1f, k, xk, h);
-        }
-        relu_frag<4>(in);
-        tab_quarter(acc, tb + T_B2 * L, tq, h);
-        e_prime<H2>(r3, a.chunk[1], a.splith[1], tq, lane);
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[0], a.splith[0], a.h2_rs[0], tq, lane, r2);
-        relu_quarter(acc);
-        coop_exchange(in, acc, xch0, wave, lane);
-        tab_quarter(acc, tb + T_B3 * L, tq, h);
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[1], a.splith[1], a.h2_rs[1], tq, lane, r3);
-        coop_exchange(in, acc, xch1, wave, lane);
-        coop_layer_norm(acc, in, tb + T_GAMMA * L, tb + T_BETA * L, tq, h);
-        if (!valid) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-        }
-        store_quarter(tile_ptr(a.Elat, tile, L, lane), STRIDE_TILE, tq, acc);
-        __syncthreads();
-    }
+// an encoder's finish: LayerNorm, zero rows on the padding lanes (the checksums and the aggregation read whole tiles), tile store
+template <int NT>
+DEVINL void store_latents(f32x16 (&acc)[NT], float* lat, const float* tb, int tile, bool valid, int lane, int h) {
+    constexpr int L = 32 * NT;
+    layer_norm_frag<NT>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
+    if (!valid) zero_frag<NT>(acc);
+    store_frag<NT>(tile_ptr(lat, tile, L, lane), STRIDE_TILE, acc);
+}
+// ... and of a cooperative encoder: the statistics from the exchanged row, this wave's quarter normalised and stored
+DEVINL void coop_store_latents(f32x16& acc, const f32x16 (&full)[4], float* lat, const float* tb, int tile, bool valid, int tq, int lane, int h) {
+    coop_layer_norm(acc, full, tb + T_GAMMA * 128, tb + T_BETA * 128, tq, h);
+    // The LayerNorm is where a cooperative encoder holds most: the full row, this wave's quarter, gamma, beta and (node encoder) a primed
+    // ring.  Nothing of the store and the next phase moves up into it: k_enc_node_coop<false, false> keeps the 128 VGPRs of four waves
+    // per SIMD, which it misses by one register when hipcc is left to interleave them.
+    __builtin_amdgcn_sched_barrier(0);
+    if (!valid) zero_quarter(acc);
+    store_quarter(tile_ptr(lat, tile, 128, lane), STRIDE_TILE, tq, acc);
 }
 
-// chunk[0]=W1 [1]=W2; last layer (L -> O) by wave 0 from the exchanged row
-template <bool FENCE, bool H2 = false>
-__global__ __launch_bounds__(256, 2) void k_decode_coop(const DecArgs a) {
-    constexpr int L = 128, CH = L * L;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* xch0 = reinterpret_cast<f32x4*>(smem);
-    f32x4* xch1 = xch0 + 16 * 64;
-    float* tb = smem + 2 * 16 * 64 * 4;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tq = wave;
-    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        OPAQUE_LANE();
-        const int n = tile * TILE + c;
-        const bool valid = n < a.n;
-        const int nn = valid ? n : 0;
-        f32x16 in[4], acc;
-        ERing<H2> r2;
-        e_prime<H2>(r2, a.chunk[1], a.splith[1], tq, lane);
-        load_frag<4>(in, tile_ptr(a.V, tile, L, lane), STRIDE_TILE);
-        tab_quarter(acc, tb + T_B1 * L, tq, h);
-        { ERing<H2> r1; e_prime<H2>(r1, a.chunk[0], a.splith[0], tq, lane); __builtin_amdgcn_sched_barrier(0); e_chain_primed<H2, FENCE>(acc, in, a.chunk[0], a.splith[0], a.h2_rs[0], tq, lane, r1); }
-        relu_quarter(acc);
-        coop_exchange(in, acc, xch0, wave, lane);
-        tab_quarter(acc, tb + T_B2 * L, tq, h);
-        e_chain_primed<H2, FENCE>(acc, in, a.chunk[1], a.splith[1], a.h2_rs[1], tq, lane, r2);
-        relu_quarter(acc);
-        coop_exchange(in, acc, xch1, wave, lane);
-        if (wave == 0) {
-            const float m = a.mask ? a.mask[a.gid ? a.gid[nn] : nn] : 1.0f;
-            for (int o = 0; o < a.O; ++o) {
-                const f32x4* w4 = reinterpret_cast<const f32x4*>(a.w3f + (int64_t)o * L) + h;
-                float sacc = 0.f;
+// the decoder's L -> O layer on the VALU from the full hidden row v: dot products, the two lane halves added, b3, inverse normaliser,
+// val_mask, store by the lower half
+template <int NT>
+DEVINL void decode_head(const f32x16 (&v)[NT], const DecArgs& a, bool valid, int nn, int h) {
+    constexpr int L = 32 * NT;
+    const float m = a.mask ? a.mask[a.gid ? a.gid[nn] : nn] : 1.0f;
+    for (int o = 0; o < a.O; ++o) {
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(a.w3f + (int64_t)o * L) + h;
+        float s = 0.f;
 #pragma unroll
-                for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 w = w4[2 * (4 * t + g)];
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 w = w4[2 * (4 * t + g)];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) sacc = fmaf(in[t][4 * g + i], w[i], sacc);
-                    }
-                sacc += __shfl_xor(sacc, 32, 64);
-                sacc += a.b3[o];
-                if (a.oscale) sacc = fmaf(sacc, a.oscale[o], a.oshift[o]);
-                sacc *= m;
-                if (valid && h == 0) a.out[(int64_t)nn * a.O + o] = sacc;
+                for (int i = 0; i < 4; ++i) s = fmaf(v[t][4 * g + i], w[i], s);
             }
-        }
+        s += __shfl_xor(s, 32, 64);
+        s += a.b3[o];
+        if (a.oscale) s = fmaf(s, a.oscale[o], a.oshift[o]);
+        s *= m;
+        if (valid && h == 0) a.out[(int64_t)nn * a.O + o] = s;
+    }
+}
+
+// this wave's ring and chain of chunk i of a stage (cooperative kernels)
+template <bool H2, int N>
+DEVINL void stage_prime(ERing<H2>& g, const StageW<N>& sw, int i, int tq, int lane) { e_prime<H2>(g, sw.chunk[i], sw.splith[i], tq, lane); }
+template <bool H2, bool FENCE, int N>
+DEVINL void stage_chain(f32x16& acc, const f32x16 (&in)[4], const StageW<N>& sw, int i, int tq, int lane, ERing<H2>& g) {
+    e_chain_primed<H2, FENCE>(acc, in, sw.chunk[i], sw.splith[i], sw.h2_rs[i], tq, lane, g);
+}
+
+// The stage policies.  INPUT_LAYER: the stage's first layer is input_layer, so its two chained layers are layers 2 and 3 (tables T_B2,
+// T_B3) and the last has no ReLU; without it (the decoder) they are layers 1 and 2 (T_B1, T_B2) on a latent row, each with its ReLU.
+// input: the row the first chained layer reads (before its ReLU, where it has one).  finish / coop_finish: what follows the second one.
+struct EncEdge {
+    using Args = EncEdgeArgs;
+    static constexpr int NCH = 2;
+    static constexpr bool INPUT_LAYER = true;
+    static DEVINL StageRow<int64_t> row(const Args& a, int tile, int c) { return stage_row<int64_t>(tile, c, a.E, a.gid); }
+    static DEVINL int width(const Args& a) { return a.Fe; }
+    static DEVINL float feature(const Args& a, int64_t g, int k) { return a.ef[g * a.Fe + k]; }
+    template <int NT>
+    static DEVINL void input(f32x16 (&x)[NT], const Args& a, const float* tb, int, const StageRow<int64_t>& row, int, int h) {
+        input_layer<EncEdge, NT>(x, a, tb, row.g, h);
+    }
+    template <int NT, int NRES, bool H2>
+    static DEVINL void finish(f32x16 (&acc)[NT], f32x16 (&)[NT], const Args& a, const float* const (&)[NCH], const float* tb, int tile,
+                              const StageRow<int64_t>& row, int lane, int h) {
+        store_latents<NT>(acc, a.Elat, tb, tile, row.valid, lane, h);
+    }
+    template <bool FENCE, bool H2>
+    static DEVINL void coop_finish(f32x16& acc, f32x16 (&in)[4], const Args& a, ERing<H2>&, ERing<H2>&, f32x4*, const float* tb, int tile,
+                                   const StageRow<int64_t>& row, int wave, int lane, int h) {
+        coop_store_latents(acc, in, a.Elat, tb, tile, row.valid, wave, lane, h);
+    }
+};
+
+struct EncNode {
+    using Args = EncNodeArgs;
+    static constexpr int NCH = 4;
+    static constexpr bool INPUT_LAYER = true;
+    static DEVINL StageRow<int> row(const Args& a, int tile, int c) { return stage_row<int>(tile, c, a.n, a.gid); }
+    static DEVINL int width(const Args& a) { return a.wa + a.wb; }
+    static DEVINL float feature(const Args& a, int64_t g, int k) { return (k < a.wa) ? a.srcA[g * a.wa + k] : a.srcB[g * a.wb + (k - a.wa)]; }
+    template <int NT>
+    static DEVINL void input(f32x16 (&x)[NT], const Args& a, const float* tb, int, const StageRow<int>& row, int, int h) {
+        input_layer<EncNode, NT>(x, a, tb, row.g, h);
+    }
+    // V, then P = v WP and Q = v WQ + b1 of step 0's edge MLP from the stored rows
+    template <int NT, int NRES, bool H2>
+    static DEVINL void finish(f32x16 (&acc)[NT], f32x16 (&y)[NT], const Args& a, const float* const (&w)[NCH], const float* tb, int tile,
+                              const StageRow<int>& row, int lane, int h) {
+        constexpr int L = 32 * NT;
+        store_latents<NT>(acc, a.V, tb, tile, row.valid, lane, h);
+        zero_frag<NT>(y);
+        enc_chunk<NT, (NRES > 2), H2>(y, acc, w[2], lane, a.w.h2_rs[2]);
+        if (row.valid) store_frag<NT>(prow_ptr(a.P, row.r, L, h), STRIDE_PROW, y);
+        tab_frag<NT>(y, tb + T_BQ * L, h);
+        enc_chunk<NT, (NRES > 3), H2>(y, acc, w[3], lane, a.w.h2_rs[3]);
+        if (row.valid) store_frag<NT>(prow_ptr(a.Q, row.r, L, h), STRIDE_PROW, y);
+    }
+    // r0 arrives primed with WP (stage_coop requested it under layer 3); WQ is requested here, behind the V store
+    template <bool FENCE, bool H2>
+    static DEVINL void coop_finish(f32x16& acc, f32x16 (&in)[4], const Args& a, ERing<H2>& r0, ERing<H2>& r1, f32x4* xch0, const float* tb, int tile,
+                                   const StageRow<int>& row, int wave, int lane, int h) {
+        coop_store_latents(acc, in, a.V, tb, tile, row.valid, wave, lane, h);
+        stage_prime<H2>(r1, a.w, 3, wave, lane);
+        coop_exchange(in, acc, xch0, wave, lane);                            // full latent row for the projection
+        zero_quarter(acc);
+        stage_chain<H2, FENCE>(acc, in, a.w, 2, wave, lane, r0);
+        if (row.valid) store_quarter(prow_ptr(a.P, row.r, 128, h), STRIDE_PROW, wave, acc);
+        tab_quarter(acc, tb + T_BQ * 128, wave, h);
+        stage_chain<H2, FENCE>(acc, in, a.w, 3, wave, lane, r1);
+        if (row.valid) store_quarter(prow_ptr(a.Q, row.r, 128, h), STRIDE_PROW, wave, acc);
+    }
+};
+
+struct Dec {
+    using Args = DecArgs;
+    static constexpr int NCH = 2;
+    static constexpr bool INPUT_LAYER = false;
+    // (the source row of a decoder row is its own tile; gid only selects the val_mask entry, in decode_head)
+    static DEVINL StageRow<int> row(const Args& a, int tile, int c) { return stage_row<int>(tile, c, a.n, (const int32_t*)nullptr); }
+    template <int NT>
+    static DEVINL void input(f32x16 (&x)[NT], const Args& a, const float*, int tile, const StageRow<int>&, int lane, int) {
+        load_frag<NT>(x, tile_ptr(a.V, tile, 32 * NT, lane), STRIDE_TILE);
+    }
+    template <int NT, int NRES, bool H2>
+    static DEVINL void finish(f32x16 (&v)[NT], f32x16 (&)[NT], const Args& a, const float* const (&)[NCH], const float*, int,
+                              const StageRow<int>& row, int, int h) {
+        decode_head<NT>(v, a, row.valid, row.r, h);
+    }
+    // by wave 0 from the exchanged row
+    template <bool FENCE, bool H2>
+    static DEVINL void coop_finish(f32x16&, f32x16 (&in)[4], const Args& a, ERing<H2>&, ERing<H2>&, f32x4*, const float*, int,
+                                   const StageRow<int>& row, int wave, int, int h) {
+        if (wave == 0) decode_head<4>(in, a, row.valid, row.r, h);
+    }
+};
+
+// the decoder's layers 1 and 2 (or, GEN, layer 1 and the middle layers) on the latent row in v; the result is in v, acc is scratch
+template <int NT, int NRES, bool GEN, bool H2, int N>
+DEVINL void dec_middle(f32x16 (&v)[NT], f32x16 (&acc)[NT], const StageW<N>& sw, const float* const (&w)[N], const float* tb, int lane, int h) {
+    constexpr int L = 32 * NT;
+    tab_frag<NT>(acc, tb + T_B1 * L, h);
+    enc_chunk<NT, (NRES > 0), H2>(acc, v, w[0], lane, sw.h2_rs[0]);
+    if constexpr (GEN) {
+        gen_hidden<NT>(acc, v, sw.gen, lane, h);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) v[t] = acc[t];
+    } else {
+        relu_frag<NT>(acc);
+        tab_frag<NT>(v, tb + T_B2 * L, h);
+        enc_chunk<NT, (NRES > 1), H2>(v, acc, w[1], lane, sw.h2_rs[1]);
+        relu_frag<NT>(v);
+    }
+}
+
+// One wave per tile: NRES chunks LDS-resident, the rest streamed from L2; GEN: any hidden_layers, every chunk streamed.
+template <class S, int NT, int NRES, bool GEN, bool H2>
+DEVINL void stage_tiles(const typename S::Args& a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const float* w[S::NCH];
+    const float* tb = stage_prologue<NT, NRES, H2>(smem, a.w, w);
+    const int lane0 = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
+        OPAQUE_LANE();
+        const auto row = S::row(a, tw.tile, c);
+        f32x16 x[NT], y[NT];
+        S::template input<NT>(x, a, tb, tw.tile, row, lane, h);
+        if constexpr (S::INPUT_LAYER) enc_middle<NT, NRES, GEN, H2>(x, y, a.w, w, tb, lane, h);
+        else dec_middle<NT, NRES, GEN, H2>(x, y, a.w, w, tb, lane, h);
+        S::template finish<NT, NRES, H2>(x, y, a, w, tb, tw.tile, row, lane, h);
+    }
+}
+
+// Four waves per tile (L = 128): every wave holds the full input row and computes its quarter tq of each layer from the t-major copy
+// of the chunk (or its fp16 pieces), two LDS exchanges hand the quarters round.  The weight rings are requested a phase ahead: r0, the
+// first chain's, under the input layer, r1 under the first chain, and the node encoder's WP into the freed r0 under the second.
+template <class S, bool FENCE, bool H2>
+DEVINL void stage_coop(const typename S::Args& a) {
+    constexpr int L = 128, T1 = S::INPUT_LAYER ? T_B2 : T_B1;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f32x4* xch0 = reinterpret_cast<f32x4*>(smem);
+    f32x4* xch1 = xch0 + 16 * 64;
+    float* tb = smem + 2 * 16 * 64 * 4;
+    copy_to_lds(tb, a.w.tabs, T_COUNT * L);
+    __syncthreads();
+    const int lane0 = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tq = wave;
+    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+        OPAQUE_LANE();
+        const auto row = S::row(a, tile, c);
+        f32x16 in[4], acc;
+        ERing<H2> r0, r1;
+        // The decoder's input is one tile load, too short to cover a ring: there r1 is requested first, ahead of that load, and r0
+        // directly in front of its own chain.  With nothing between them hipcc sinks r0's four requests into the chain, each to just
+        // before its use; the scheduling barrier keeps them in flight together (coop_chain does the same for a ring it primes itself).
+        // The encoders' rings need none: the input layer's loop or an exchange barrier separates every request from its chain.
+        stage_prime<H2>(S::INPUT_LAYER ? r0 : r1, a.w, S::INPUT_LAYER ? 0 : 1, tq, lane);
+        S::template input<4>(in, a, tb, tile, row, lane, h);                 // every wave the full row
+        if constexpr (S::INPUT_LAYER) relu_frag<4>(in);
+        tab_quarter(acc, tb + T1 * L, tq, h);
+        stage_prime<H2>(S::INPUT_LAYER ? r1 : r0, a.w, S::INPUT_LAYER ? 1 : 0, tq, lane);
+        if constexpr (!S::INPUT_LAYER) __builtin_amdgcn_sched_barrier(0);
+        stage_chain<H2, FENCE>(acc, in, a.w, 0, tq, lane, r0);
+        relu_quarter(acc);
+        coop_exchange(in, acc, xch0, wave, lane);
+        tab_quarter(acc, tb + (T1 + 1) * L, tq, h);
+        if constexpr (S::NCH > 2) stage_prime<H2>(r0, a.w, 2, tq, lane);
+        stage_chain<H2, FENCE>(acc, in, a.w, 1, tq, lane, r1);
+        if constexpr (!S::INPUT_LAYER) relu_quarter(acc);
+        coop_exchange(in, acc, xch1, wave, lane);
+        S::template coop_finish<FENCE, H2>(acc, in, a, r0, r1, xch0, tb, tile, row, wave, lane, h);
         __syncthreads();
     }
 }
 
-// ================================================================================================
-// Encoder, edge side (K0b+K2).  chunk[0]=W2 [1]=W3
-// ================================================================================================
+// The entry points (traces, profiles/ and DESIGN.md name them): each carries its launch bounds and runs its stage's skeleton.
 template <int NT, int NRES, bool GEN = false, bool H2 = false>
-__global__ __launch_bounds__(512, 2) void k_enc_edge(const EncEdgeArgs a) {
-    constexpr int L = 32 * NT, CH = 16 * NT * 64 * NT;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-#pragma unroll
-    for (int r = 0; r < NRES; ++r) copy_to_lds(smem + r * CH, H2 ? reinterpret_cast<const float*>(a.splith[r]) : a.chunk[r], CH);
-    float* tb = smem + NRES * CH;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float* w2 = NRES > 0 ? smem : (H2 ? reinterpret_cast<const float*>(a.splith[0]) : a.chunk[0]);
-    const float* w3 = NRES > 1 ? smem + CH : (H2 ? reinterpret_cast<const float*>(a.splith[1]) : a.chunk[1]);
-
-    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
-        OPAQUE_LANE();
-        const int64_t eid = (int64_t)tw.tile * TILE + c;
-        const bool valid = eid < a.E;
-        const int64_t ee = valid ? eid : 0;
-        const int64_t g = a.gid ? a.gid[ee] : ee;
-        f32x16 acc[NT], y[NT];
-        tab_frag<NT>(acc, tb + T_B1 * L, h);
-        for (int k = 0; k < a.Fe; ++k) {
-            float xk = a.ef[g * a.Fe + k];
-            if (a.scale) xk = fmaf(xk, a.scale[k], a.shift[k]);
-            first_layer<NT>(acc, a.w1f, k, xk, h);
-        }
-        if constexpr (GEN) {
-            gen_hidden<NT>(acc, y, a.gen, lane, h);
-            gen_final<NT>(acc, y, a.gen, lane, h);
-        } else {
-            relu_frag<NT>(acc);
-            tab_frag<NT>(y, tb + T_B2 * L, h);
-            enc_chunk<NT, (NRES > 0), H2>(y, acc, w2, lane, a.h2_rs[0]);
-            relu_frag<NT>(y);
-            tab_frag<NT>(acc, tb + T_B3 * L, h);
-            enc_chunk<NT, (NRES > 1), H2>(acc, y, w3, lane, a.h2_rs[1]);
-        }
-        layer_norm_frag<NT>(acc, tb + T_GAMMA * L, tb + T_BETA * L, h);
-        if (!valid) zero_frag<NT>(acc);
-        store_frag<NT>(tile_ptr(a.Elat, tw.tile, L, lane), STRIDE_TILE, acc);
-    }
-}
-
-// ================================================================================================
-// Decoder (K7) + inverse normaliser + val_mask epilogue (K8).  chunk[0]=W1 [1]=W2
-// ================================================================================================
+__global__ __launch_bounds__(512, 2) void k_enc_node(const EncNodeArgs a) { stage_tiles<EncNode, NT, NRES, GEN, H2>(a); }
 template <int NT, int NRES, bool GEN = false, bool H2 = false>
-__global__ __launch_bounds__(512, 2) void k_decode(const DecArgs a) {
-    constexpr int L = 32 * NT, CH = 16 * NT * 64 * NT;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-#pragma unroll
-    for (int r = 0; r < NRES; ++r) copy_to_lds(smem + r * CH, H2 ? reinterpret_cast<const float*>(a.splith[r]) : a.chunk[r], CH);
-    float* tb = smem + NRES * CH;
-    copy_to_lds(tb, a.tabs, T_COUNT * L);
-    __syncthreads();
-    const int lane0 = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float* w1 = NRES > 0 ? smem : (H2 ? reinterpret_cast<const float*>(a.splith[0]) : a.chunk[0]);
-    const float* w2 = NRES > 1 ? smem + CH : (H2 ? reinterpret_cast<const float*>(a.splith[1]) : a.chunk[1]);
-
-    for (TileWalk tw(a.ntiles, wave); tw.tile < tw.end; tw.tile += tw.stride) {
-        OPAQUE_LANE();
-        const int n = tw.tile * TILE + c;
-        const bool valid = n < a.n;
-        const int nn = valid ? n : 0;
-        f32x16 v[NT], acc[NT];
-        load_frag<NT>(v, tile_ptr(a.V, tw.tile, L, lane), STRIDE_TILE);
-        tab_frag<NT>(acc, tb + T_B1 * L, h);
-        enc_chunk<NT, (NRES > 0), H2>(acc, v, w1, lane, a.h2_rs[0]);
-        if constexpr (GEN) {                                    // middle layers, then the L -> O layer below reads v
-            gen_hidden<NT>(acc, v, a.gen, lane, h);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) v[t] = acc[t];
-        } else {
-            relu_frag<NT>(acc);
-            tab_frag<NT>(v, tb + T_B2 * L, h);
-            enc_chunk<NT, (NRES > 1), H2>(v, acc, w2, lane, a.h2_rs[1]);
-            relu_frag<NT>(v);
-        }
-        const float m = a.mask ? a.mask[a.gid ? a.gid[nn] : nn] : 1.0f;
-        for (int o = 0; o < a.O; ++o) {
-            const f32x4* w4 = reinterpret_cast<const f32x4*>(a.w3f + (int64_t)o * L) + h;
-            float s = 0.f;
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 w = w4[2 * (4 * t + g)];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) s = fmaf(v[t][4 * g + i], w[i], s);
-                }
-            s += __shfl_xor(s, 32, 64);
-            s += a.b3[o];
-            if (a.oscale) s = fmaf(s, a.oscale[o], a.oshift[o]);
-            s *= m;
-            if (valid && h == 0) a.out[(int64_t)nn * a.O + o] = s;
-        }
-    }
-}
+__global__ __launch_bounds__(512, 2) void k_enc_edge(const EncEdgeArgs a) { stage_tiles<EncEdge, NT, NRES, GEN, H2>(a); }
+template <int NT, int NRES, bool GEN = false, bool H2 = false>
+__global__ __launch_bounds__(512, 2) void k_decode(const DecArgs a) { stage_tiles<Dec, NT, NRES, GEN, H2>(a); }
+template <bool FENCE, bool H2 = false>
+__global__ __launch_bounds__(256, 2) void k_enc_node_coop(const EncNodeArgs a) { stage_coop<EncNode, FENCE, H2>(a); }
+template <bool FENCE, bool H2 = false>
+__global__ __launch_bounds__(256, 2) void k_enc_edge_coop(const EncEdgeArgs a) { stage_coop<EncEdge, FENCE, H2>(a); }
+template <bool FENCE, bool H2 = false>
+__global__ __launch_bounds__(256, 2) void k_decode_coop(const DecArgs a) { stage_coop<Dec, FENCE, H2>(a); }
 
 // ================================================================================================
 // bf16 processor kernels (L = 128): bf16 storage, v_mfma_f32_32x32x16_bf16, fp32 accumulate / LayerNorm / residual /
@@ -2654,24 +2635,6 @@ static hipError_t launch_k(K kern, const A& a, const LaunchCfg& lc, hipStream_t 
     return hipGetLastError();
 }
 
-#define DISPATCH_L(KERN, WANT, ARGS, NTILES)                                                   \
-    do {                                                                                       \
-        if ((NTILES) <= 0) return hipSuccess;                                                  \
-        const int nres = resident_chunks(L, WANT);                                             \
-        const LaunchCfg lc = tile_launch(L, NTILES, nres);                                     \
-        const bool h2_ = L == 128 && g_fp32_split && g_split_f16 && (ARGS).splith[0];          \
-        if (L == 128 && small_launch(NTILES)) {                                                \
-            LaunchCfg l0 = lc;                                                                 \
-            l0.lds = (size_t)T_COUNT * L * 4 + 64;                                             \
-            return h2_ ? launch_k(KERN<4, 0, false, true>, ARGS, l0, s) : launch_k(KERN<4, 0>, ARGS, l0, s); \
-        }                                                                                      \
-        if (L == 128 && h2_) return launch_k(KERN<4, (WANT < 2 ? WANT : 2), false, true>, ARGS, lc, s); \
-        if (L == 128) return launch_k(KERN<4, (WANT < 2 ? WANT : 2)>, ARGS, lc, s);            \
-        if (L == 64) return launch_k(KERN<2, WANT>, ARGS, lc, s);                              \
-        if (L == 32) return launch_k(KERN<1, WANT>, ARGS, lc, s);                              \
-        return hipErrorInvalidValue;                                                           \
-    } while (0)
-
 hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);
 
 // hidden_layers != 2 (GenMlp): the GEN instantiations, every weight chunk streamed from L2, tables only in LDS
@@ -2970,33 +2933,54 @@ hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s) {
     if (L == 32) return launch_k(k_project<1, true>, a, lc, s);
     return hipErrorInvalidValue;
 }
-hipError_t launch_enc_node(int L, const EncNodeArgs& a, hipStream_t s) {
-    if (a.gen.use) DISPATCH_GEN(L, (k_enc_node<4, 0, true>), (k_enc_node<2, 0, true>), (k_enc_node<1, 0, true>), a, a.ntiles);
-    if (a.ntiles > 0 && L == 128 && coop_size(a.ntiles, false)) {
-        LaunchCfg c4{a.ntiles, 256, coop_lds()};
-        if (g_fp32_split && g_split_f16 && a.splith[0]) return coop_fence(a.ntiles) ? launch_k(k_enc_node_coop<true, true>, a, c4, s) : launch_k(k_enc_node_coop<false, true>, a, c4, s);
-        return coop_fence(a.ntiles) ? launch_k(k_enc_node_coop<true>, a, c4, s) : launch_k(k_enc_node_coop<false>, a, c4, s);
+// The encoder / decoder stages: a stage's two kernel templates, the chunks it keeps in LDS where they fit (WANT) and the cooperative
+// size range it follows.  launch_stage picks, in this order: the GEN instantiation (hidden_layers != 2); at L = 128 the cooperative
+// kernel in its size range, fenced on small launches, on the fp16 pieces where they are built; then at L = 128 the streaming
+// instantiation on a small launch, else two resident chunks; at L = 64 and L = 32 all WANT chunks resident.
+struct EncNodeK {
+    static constexpr int WANT = 4;
+    static constexpr bool EDGE = false;
+    template <int NT, int NRES, bool GEN = false, bool H2 = false> static auto tiles() { return k_enc_node<NT, NRES, GEN, H2>; }
+    template <bool FENCE, bool H2> static auto coop() { return k_enc_node_coop<FENCE, H2>; }
+};
+struct EncEdgeK {
+    static constexpr int WANT = 2;
+    static constexpr bool EDGE = true;
+    template <int NT, int NRES, bool GEN = false, bool H2 = false> static auto tiles() { return k_enc_edge<NT, NRES, GEN, H2>; }
+    template <bool FENCE, bool H2> static auto coop() { return k_enc_edge_coop<FENCE, H2>; }
+};
+struct DecK {
+    static constexpr int WANT = 2;
+    static constexpr bool EDGE = false;
+    template <int NT, int NRES, bool GEN = false, bool H2 = false> static auto tiles() { return k_decode<NT, NRES, GEN, H2>; }
+    template <bool FENCE, bool H2> static auto coop() { return k_decode_coop<FENCE, H2>; }
+};
+template <class K, class A>
+static hipError_t launch_stage(int L, const A& a, hipStream_t s) {
+    const int nt = a.ntiles;
+    if (a.w.gen.use) DISPATCH_GEN(L, (K::template tiles<4, 0, true>()), (K::template tiles<2, 0, true>()), (K::template tiles<1, 0, true>()), a, nt);
+    if (nt <= 0) return hipSuccess;
+    constexpr int R128 = K::WANT < 2 ? K::WANT : 2;
+    const bool h2 = L == 128 && g_fp32_split && g_split_f16 && a.w.splith[0];
+    if (L == 128 && coop_size(nt, K::EDGE)) {
+        const LaunchCfg c4{nt, 256, coop_lds()};
+        if (h2) return coop_fence(nt) ? launch_k(K::template coop<true, true>(), a, c4, s) : launch_k(K::template coop<false, true>(), a, c4, s);
+        return coop_fence(nt) ? launch_k(K::template coop<true, false>(), a, c4, s) : launch_k(K::template coop<false, false>(), a, c4, s);
     }
-    DISPATCH_L(k_enc_node, 4, a, a.ntiles);
-}
-hipError_t launch_enc_edge(int L, const EncEdgeArgs& a, hipStream_t s) {
-    if (a.gen.use) DISPATCH_GEN(L, (k_enc_edge<4, 0, true>), (k_enc_edge<2, 0, true>), (k_enc_edge<1, 0, true>), a, a.ntiles);
-    if (a.ntiles > 0 && L == 128 && coop_size(a.ntiles, true)) {
-        LaunchCfg c4{a.ntiles, 256, coop_lds()};
-        if (g_fp32_split && g_split_f16 && a.splith[0]) return coop_fence(a.ntiles) ? launch_k(k_enc_edge_coop<true, true>, a, c4, s) : launch_k(k_enc_edge_coop<false, true>, a, c4, s);
-        return coop_fence(a.ntiles) ? launch_k(k_enc_edge_coop<true>, a, c4, s) : launch_k(k_enc_edge_coop<false>, a, c4, s);
+    const LaunchCfg lc = tile_launch(L, nt, resident_chunks(L, K::WANT));
+    if (L == 128 && small_launch(nt)) {
+        LaunchCfg l0 = lc;
+        l0.lds = (size_t)T_COUNT * L * 4 + 64;
+        return h2 ? launch_k(K::template tiles<4, 0, false, true>(), a, l0, s) : launch_k(K::template tiles<4, 0>(), a, l0, s);
     }
-    DISPATCH_L(k_enc_edge, 2, a, a.ntiles);
+    if (L == 128) return h2 ? launch_k(K::template tiles<4, R128, false, true>(), a, lc, s) : launch_k(K::template tiles<4, R128>(), a, lc, s);
+    if (L == 64) return launch_k(K::template tiles<2, K::WANT>(), a, lc, s);
+    if (L == 32) return launch_k(K::template tiles<1, K::WANT>(), a, lc, s);
+    return hipErrorInvalidValue;
 }
-hipError_t launch_decode(int L, const DecArgs& a, hipStream_t s) {
-    if (a.gen.use) DISPATCH_GEN(L, (k_decode<4, 0, true>), (k_decode<2, 0, true>), (k_decode<1, 0, true>), a, a.ntiles);
-    if (a.ntiles > 0 && L == 128 && coop_size(a.ntiles, false)) {
-        LaunchCfg c4{a.ntiles, 256, coop_lds()};
-        if (g_fp32_split && g_split_f16 && a.splith[0]) return coop_fence(a.ntiles) ? launch_k(k_decode_coop<true, true>, a, c4, s) : launch_k(k_decode_coop<false, true>, a, c4, s);
-        return coop_fence(a.ntiles) ? launch_k(k_decode_coop<true>, a, c4, s) : launch_k(k_decode_coop<false>, a, c4, s);
-    }
-    DISPATCH_L(k_decode, 2, a, a.ntiles);
-}
+hipError_t launch_enc_node(int L, const EncNodeArgs& a, hipStream_t s) { return launch_stage<EncNodeK>(L, a, s); }
+hipError_t launch_enc_edge(int L, const EncEdgeArgs& a, hipStream_t s) { return launch_stage<EncEdgeK>(L, a, s); }
+hipError_t launch_decode(int L, const DecArgs& a, hipStream_t s) { return launch_stage<DecK>(L, a, s); }
 
 static LaunchCfg bf_launch(int ntiles, int nchunks) {
     LaunchCfg lc = tile_launch(128, ntiles, 0);

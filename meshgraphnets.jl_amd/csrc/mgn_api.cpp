@@ -379,6 +379,21 @@ GenMlp gen_of(const mgn_engine* h, const GenOff& g, bool has_last) {
     return m;
 }
 
+// the weights of an encoder / decoder stage (StageW, kernels.h) from its chunks, its tables and its GenOff
+template <int N>
+StageW<N> stage_weights(const mgn_engine* h, const ChunkRef (&refs)[N], size_t tabs, const GenOff& g, bool has_last) {
+    StageW<N> w{};
+    for (int i = 0; i < N; ++i) {
+        const ChunkPtrs c = chunk_ptrs(h, refs[i]);
+        w.chunk[i] = c.frag;
+        w.splith[i] = c.h32;
+        w.h2_rs[i] = c.rs;
+    }
+    w.tabs = W(h, tabs);
+    w.gen = gen_of(h, g, has_last);
+    return w;
+}
+
 EdgeArgs edge_args(mgn_engine* h, int k, int q = 0) {
     EdgeArgs a{};
     auto& es = h->es[q];
@@ -1250,14 +1265,7 @@ extern "C++" int mgn::encode_impl(mgn_handle* h, bool use_norms, bool nodes, boo
         a.V = h->V.as<float>();
         a.P = h->es[0].P.as<float>();
         a.Q = h->es[0].Q.as<float>();
-        for (int i = 0; i < 4; ++i) {
-            const ChunkPtrs w = chunk_ptrs(h, h->en[i]);
-            a.chunk[i] = w.frag;
-            a.splith[i] = w.h32;
-            a.h2_rs[i] = w.rs;
-        }
-        a.tabs = W(h, h->en_tabs);
-        a.gen = gen_of(h, h->en_gen, true);
+        a.w = stage_weights(h, h->en, h->en_tabs, h->en_gen, true);
         HIPCHK(h, launch_enc_node(c.L, a, h->stream));
         if (is_bf16(h)) {   // fp32 encoder output -> bf16 state; P,Q of step 0 from the bf16 latents
             HIPCHK(h, launch_tile_f32_to_bf16(h->V.as<float>(), h->bV.as<uint16_t>(), h->ntiles_n, h->stream));
@@ -1278,14 +1286,7 @@ extern "C++" int mgn::encode_impl(mgn_handle* h, bool use_norms, bool nodes, boo
             if (q == 0 && use_norms && h->have_enorm) { b.scale = nrm + 2 * c.Fn; b.shift = nrm + 2 * c.Fn + c.Fe; }
             b.w1f = W(h, es.ee_w1f);
             b.Elat = es.Elat.as<float>();
-            for (int i = 0; i < 2; ++i) {
-                const ChunkPtrs w = chunk_ptrs(h, es.ee[i]);
-                b.chunk[i] = w.frag;
-                b.splith[i] = w.h32;
-                b.h2_rs[i] = w.rs;
-            }
-            b.tabs = W(h, es.ee_tabs);
-            b.gen = gen_of(h, es.ee_gen, true);
+            b.w = stage_weights(h, es.ee, es.ee_tabs, es.ee_gen, true);
             HIPCHK(h, launch_enc_edge(c.L, b, h->stream));
             if (is_bf16(h)) HIPCHK(h, launch_tile_f32_to_bf16(es.Elat.as<float>(), es.bElat.as<uint16_t>(), es.ntiles_e, h->stream));
         }
@@ -1432,14 +1433,7 @@ extern "C++" int mgn::decode_impl(mgn_handle* h, bool use_norms) {
     a.mask = (use_norms && h->have_mask) ? h->d_mask.as<float>() : nullptr;
     a.gid = h->d_own_gid.as<int32_t>();
     a.out = h->out_override ? h->out_override : h->d_out.as<float>();
-    for (int i = 0; i < 2; ++i) {
-        const ChunkPtrs w = chunk_ptrs(h, h->de[i]);
-        a.chunk[i] = w.frag;
-        a.splith[i] = w.h32;
-        a.h2_rs[i] = w.rs;
-    }
-    a.tabs = W(h, h->de_tabs);
-    a.gen = gen_of(h, h->de_gen, false);
+    a.w = stage_weights(h, h->de, h->de_tabs, h->de_gen, false);
     HIPCHK(h, launch_decode(c.L, a, h->stream));
     return MGN_OK;
 }
