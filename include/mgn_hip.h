@@ -461,12 +461,17 @@ int mgn_forward_vjp(mgn_handle* h, const float* nf, const float* ef, const float
  *   transport MGN_COMM_RCCL: RCCL (needs one GPU per rank).
  *   transport MGN_COMM_HOST: POSIX shared memory on one node, rows staged through the host.  Lets several ranks share one GPU
  *     (tests), serves host-only handles, and is a fallback where RCCL cannot initialise; not the production wire.
+ *   transport MGN_COMM_LOCAL: the ranks are THREADS of one process (what mgn_group is inside) and find each other through the id in a
+ *     process-wide registry.  Device rows never leave the device: the receiving rank copies them out of the peer's send buffer with one
+ *     kernel launch, ordered against the peer by HIP events alone -- no host staging, no stream synchronisation.  Ranks may share a
+ *     device; peers on different devices are read in place where hipDeviceCanAccessPeer allows it and with hipMemcpyPeerAsync otherwise.
+ *     Host-only handles exchange by memcpy.  An id made for one of HOST / LOCAL is refused by the other.
  * Bootstrap: ONE rank calls mgn_comm_unique_id and the host distributes the MGN_COMM_ID_BYTES bytes (MPI.bcast, a
  * torch.distributed store, a file), then every rank calls mgn_comm_init with them (collective: returns when all ranks have
  * joined).  mgn_comm_init_file does the distribution through a file on a shared filesystem: rank 0 writes it, the others wait
  * for it.  Errors of this group: MGN_E_RCCL.                                                                          */
 #define MGN_COMM_ID_BYTES 128
-typedef enum mgn_comm_transport { MGN_COMM_RCCL = 0, MGN_COMM_HOST = 1 } mgn_comm_transport;
+typedef enum mgn_comm_transport { MGN_COMM_RCCL = 0, MGN_COMM_HOST = 1, MGN_COMM_LOCAL = 2 } mgn_comm_transport;
 int mgn_comm_unique_id(void* id /* [MGN_COMM_ID_BYTES] */, int32_t transport);
 int mgn_comm_init(mgn_handle* h, const void* id, size_t id_bytes, int32_t transport);
 int mgn_comm_init_file(mgn_handle* h, const char* path, int32_t transport);
@@ -480,6 +485,48 @@ int mgn_halo_exchange(mgn_handle* h);
 /* Any per-node rows on the HOST: own_rows [n_own][width] -> halo_rows [n_halo][width] (order of mgn_halo_nodes) through the
  * communicator; works on host-only handles (MGN_COMM_HOST transport).  E.g. positions of halo nodes. */
 int mgn_halo_exchange_host(mgn_handle* h, const float* own_rows, float* halo_rows, int32_t width);
+
+/* ---- one process, P partitions: a group drives every rank of an edge-cut partitioned mesh from ONE caller thread ---------------
+ * What an MPI-style program does with one process, one handle and mgn_comm_init per rank, for callers that are one process holding
+ * one model (the reference's train_network / eval_network, src/MeshGraphNets.jl:255-263).  mgn_group_create starts one worker thread
+ * per rank (nranks of them, nothing is sized by the machine); worker k selects devices[k] once, owns an ordinary handle made by
+ * mgn_create with rank = k, nranks and device = devices[k] (cfg->rank, cfg->nranks and cfg->device are ignored; ordinals may repeat:
+ * ranks may share a GPU), and the ranks are joined by one MGN_COMM_LOCAL communicator.  devices[k] = MGN_DEVICE_NONE for every k gives
+ * a host-only group: mgn_group_set_graph and the introspection of its rank handles work, compute answers MGN_E_HIP.
+ * Every mgn_group_* call below takes the arguments of the mgn_* call of the same name, hands that call to every worker, waits for all
+ * of them and returns MGN_OK or the status of the rank that failed FIRST, with that rank's text behind "rank k: " in
+ * mgn_group_last_error.  Inputs are host pointers that every rank reads in place (the nranks > 1 contract: GLOBAL arrays in, the
+ * complete result on every rank).  Rank 0 writes the caller's output buffers (out, dxdt, d->out and d's counters, grads, *loss); the
+ * other ranks write scratch the group owns.  grads of mgn_group_step may also be device memory of devices[0].
+ * mgn_group_latents_checksum adds the ranks' sums in ascending rank order.
+ * A rank that fails while its peers are inside a collective does not cost them MGN_COMM_TIMEOUT_S: the group raises the communicator's
+ * abort flag the moment a rank returns an error, the peers leave with MGN_E_RCCL, and before the call returns the group replaces the
+ * communicator with a fresh one: the group stays usable (graph, parameters and static inputs of the ranks are kept).
+ * A group is no more thread-safe than a handle: one call in flight.  mgn_group_rank_handle lends rank k's handle for introspection
+ * (mgn_partition_info, mgn_owned_nodes, mgn_halo_*, mgn_profile_*): no compute and no collective through it.
+ * Refusals of mgn_group_create: MGN_E_ARG for nranks < 1, nranks > 64, NULL cfg / devices / out, a mix of MGN_DEVICE_NONE and devices;
+ * MGN_E_UNSUPPORTED for n_edge_sets == 2 or ln_dims = MGN_LN_ALL with nranks > 1 (single-partition modes); whatever mgn_create
+ * refuses.  nranks == 1 is a plain handle on a thread.                                                                            */
+typedef struct mgn_group mgn_group;
+int mgn_group_create(const mgn_config* cfg, int32_t nranks, const int32_t* devices /* [nranks] HIP ordinals; may repeat */, mgn_group** out);
+void mgn_group_destroy(mgn_group* g);
+const char* mgn_group_last_error(const mgn_group* g); /* g may be NULL: error of the last failed mgn_group_create */
+mgn_handle* mgn_group_rank_handle(mgn_group* g, int32_t rank);
+int mgn_group_set_params(mgn_group* g, const float* packed, size_t n);
+int mgn_group_set_norms(mgn_group* g, const float* node_scale, const float* node_shift, const float* edge_scale, const float* edge_shift,
+                        const float* out_scale, const float* out_shift);
+int mgn_group_set_graph(mgn_group* g, int32_t N, int64_t E, const int32_t* senders, const int32_t* receivers, int32_t index_base,
+                        const float* mesh_pos, int32_t pos_dim);
+int mgn_group_set_static(mgn_group* g, const float* node_type_onehot, const float* ef_raw, const float* val_mask);
+int mgn_group_forward(mgn_group* g, const float* nf, const float* ef, float* out);
+int mgn_group_ode_step(mgn_group* g, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask, float* dxdt);
+int mgn_group_rollout(mgn_group* g, mgn_rollout_desc* d);
+int mgn_group_step(mgn_group* g, const float* nf, const float* ef, const float* target, const int32_t* mask, int64_t nmask,
+                   int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
+int mgn_group_latents_randn(mgn_group* g, uint64_t seed);
+int mgn_group_processor_steps_dev(mgn_group* g, int32_t nsteps);
+int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, double* sumsq_v, double* sumsq_e);
+int mgn_group_synchronize(mgn_group* g);
 
 /* ---- the benchmarked unit: nsteps processor steps on given latents -------------
  * v [N][L], e [E][L] in caller order, updated in place (host buffers).                          */

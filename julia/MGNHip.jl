@@ -875,6 +875,7 @@ end
 const COMM_ID_BYTES = 128
 const COMM_RCCL = Int32(0)
 const COMM_HOST = Int32(1)      # shared memory on one node (several ranks on one GPU; tests)
+const COMM_LOCAL = Int32(2)     # the ranks are threads (tasks on distinct threads) of THIS process; device rows stay on the device
 
 "Made on ONE rank; distribute the bytes to the others (`MPI.Bcast!(id, 0, comm)`), then every rank calls `comm_init!`."
 function comm_unique_id(transport::Int32 = COMM_RCCL)

@@ -17,7 +17,8 @@ MGN_OK, MGN_E_ARG, MGN_E_HIP, MGN_E_STATE, MGN_E_OOM, MGN_E_UNSUPPORTED, MGN_E_R
 STATUS_NAMES = {0: "MGN_OK", -1: "MGN_E_ARG", -2: "MGN_E_HIP", -3: "MGN_E_STATE", -4: "MGN_E_OOM", -5: "MGN_E_UNSUPPORTED",
                 -6: "MGN_E_RCCL"}
 MGN_COMM_ID_BYTES = 128
-MGN_COMM_RCCL, MGN_COMM_HOST = 0, 1
+MGN_COMM_RCCL, MGN_COMM_HOST, MGN_COMM_LOCAL = 0, 1, 2
+TRANSPORTS = {"rccl": MGN_COMM_RCCL, "host": MGN_COMM_HOST, "local": MGN_COMM_LOCAL}
 
 
 class MgnConfig(C.Structure):
@@ -136,6 +137,22 @@ PROTOTYPES = {
     "mgn_comm_allreduce": (C.c_int, [_H, _f64p, C.c_int32, C.c_int32]),
     "mgn_halo_exchange": (C.c_int, [_H]),
     "mgn_halo_exchange_host": (C.c_int, [_H, _f32p, _f32p, C.c_int32]),
+    "mgn_group_create": (C.c_int, [C.POINTER(MgnConfig), C.c_int32, _i32p, C.POINTER(_H)]),
+    "mgn_group_destroy": (None, [_H]),
+    "mgn_group_last_error": (C.c_char_p, [_H]),
+    "mgn_group_rank_handle": (_H, [_H, C.c_int32]),
+    "mgn_group_set_params": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_group_set_norms": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "mgn_group_set_graph": (C.c_int, [_H, C.c_int32, C.c_int64, _i32p, _i32p, C.c_int32, _f32p, C.c_int32]),
+    "mgn_group_set_static": (C.c_int, [_H, _f32p, _f32p, _f32p]),
+    "mgn_group_forward": (C.c_int, [_H, _f32p, _f32p, _f32p]),
+    "mgn_group_ode_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "mgn_group_rollout": (C.c_int, [_H, C.POINTER(MgnRolloutDesc)]),
+    "mgn_group_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
+    "mgn_group_latents_randn": (C.c_int, [_H, C.c_uint64]),
+    "mgn_group_processor_steps_dev": (C.c_int, [_H, C.c_int32]),
+    "mgn_group_latents_checksum": (C.c_int, [_H, _f64p, _f64p, _f64p, _f64p]),
+    "mgn_group_synchronize": (C.c_int, [_H]),
     "mgn_tfrecord_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_H)]),
     "mgn_tfrecord_next": (C.c_int, [_H]),
     "mgn_tfrecord_feature_count": (C.c_int, [_H]),

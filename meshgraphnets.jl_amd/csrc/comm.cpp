@@ -1,4 +1,4 @@
-// Engine-owned communicator: RCCL (run-time bound) and a shared-memory host transport.  See comm.h.
+// Engine-owned communicator: RCCL (run-time bound), a shared-memory host transport and an in-process transport.  See comm.h.
 #include "comm.h"
 
 #include <dlfcn.h>
@@ -14,6 +14,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -470,7 +472,304 @@ struct HostComm final : Comm {
     }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Local transport: the ranks are THREADS of one process (mgn_group; tests that run ranks as threads) and meet in a process-global
+// registry keyed by the communicator id.  Device buffers never leave the device: the receiving rank's k_a2a_pull (comm_pull.hip)
+// reads every peer's send buffer in place.
+//
+// Protocol of a device collective (a2a_start + a2a_finish, allgather), generation g = 1, 2, ... counted alike on every rank:
+//   post   R records ready_R[g & 1] on its compute stream (everything enqueued before it wrote `send`), stores its send pointer and
+//          per-peer offsets / sizes in its slot and publishes ready_gen = g with a release store.
+//   pull   R spins (host, in process) until every peer Q it receives from has published ready_gen = g, makes its stream wait for
+//          ready_Q[g & 1], launches ONE k_a2a_pull over all peers' segments, records pulled_R[g & 1] and publishes pulled_gen = g.
+//   fence  R spins until every peer Q that reads from it has published pulled_gen = g and makes its stream wait for pulled_Q[g & 1]:
+//          whatever R enqueues after the collective -- the next pack into the same send buffer -- runs after Q's copy (write after
+//          read).  Then R publishes done_gen = g.
+// Invariant 1, events only: ranks are ordered on the GPU by hipStreamWaitEvent alone.  No kernel polls memory a peer writes, there is
+//   no host staging and no stream or device synchronisation.  A hipStreamWaitEvent on an event that was never recorded is a no-op, which
+//   is why every wait is issued only after the acquire load that proves the peer's hipEventRecord call has RETURNED (the record comes
+//   before the release store in program order).  Since waits only ever refer to records already issued, the GPU-side dependencies
+//   follow the host order of the records: they cannot form a cycle, and an aborted collective leaves no GPU work waiting on something
+//   that will never come.
+// Invariant 2, publish before spin: inside a collective a rank spins only for publications of the SAME generation, and each of those
+//   is made before its maker's spin of that step (ready_gen before the pull's spin; pulled_gen before the fence's spin, and it
+//   depends only on ready_gen values).  So the spins cannot form a cycle either.
+// Event ring, two deep by generation parity.  Reuse: ready_R[g & 1] / pulled_R[g & 1] are recorded again in generation g + 2.  Before
+//   post(g + 2) a rank waits until EVERY rank has published done_gen >= g, i.e. has returned from every hipStreamWaitEvent it issues in
+//   generation g; so no wait of generation g can see the record of generation g + 2.  (That wait is for a generation two back, whose
+//   publications depend on nothing later: it cannot join a cycle.  One generation of slack is what lets a fast rank post g + 1 while
+//   a slow one is still fencing g -- with a ring of one it would have to wait there.)  The slot's send table is safe the same way: R
+//   overwrites it in post(g + 1), after its fence(g), by which time every reader of generation g has published pulled_gen = g, which it
+//   does after reading the table.
+// Host spins follow HostComm::wait_barrier: yield after a short spin, a shared abort flag, MGN_COMM_TIMEOUT_S.  After an abort or a
+// time-out the communicator is dead: destroy it on every rank and make a new one.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t LOCAL_MAGIC = 0x4D474E4Cu;   // "MGNL"
+
+struct LocalShared {
+    int nranks = 0;
+    std::atomic<int32_t> bar_count{0}, bar_gen{0}, abort_flag{0}, attached{0};
+    struct alignas(64) Slot {
+        std::atomic<uint64_t> ready_gen{0}, pulled_gen{0}, done_gen{0};
+        const char* send = nullptr;                       // of generation ready_gen
+        size_t soff[COMM_MAX_RANKS], sbytes[COMM_MAX_RANKS];
+        hipEvent_t ready[2] = {nullptr, nullptr}, pulled[2] = {nullptr, nullptr};
+        int device = -1;                                  // HIP ordinal, -1: host-only rank
+        // host collectives (a2a_host, allreduce_f64): valid between their two barriers
+        const char* hsend = nullptr;
+        const size_t *hoff = nullptr, *hbytes = nullptr;  // null: every peer reads hsend[0 .. hall)
+        size_t hall = 0;
+    } slot[COMM_MAX_RANKS];
+    // the events live as long as any rank does: a slow peer may still name them in a hipStreamWaitEvent after their owner has left
+    ~LocalShared() {
+        for (Slot& s : slot)
+            for (int i = 0; i < 2; ++i) {
+                if (s.ready[i]) (void)hipEventDestroy(s.ready[i]);
+                if (s.pulled[i]) (void)hipEventDestroy(s.pulled[i]);
+            }
+    }
+};
+
+struct LocalKey {
+    unsigned char b[12];
+    bool operator<(const LocalKey& o) const { return memcmp(b, o.b, sizeof b) < 0; }
+};
+std::mutex g_local_mu;
+std::map<LocalKey, std::weak_ptr<LocalShared>>& local_registry() {
+    static std::map<LocalKey, std::weak_ptr<LocalShared>> m;
+    return m;
+}
+
+struct LocalComm final : Comm {
+    std::shared_ptr<LocalShared> sh;
+    bool device_ok = false;
+    int device = -1;
+    double timeout_s = 120.0;
+    uint64_t gen = 0;                        // device collectives posted so far
+    bool direct[COMM_MAX_RANKS];             // peer's memory is readable by a kernel on this rank's device
+    // pending device exchange (between a2a_start and a2a_finish)
+    bool pending = false;
+    void* pend_recv = nullptr;
+    std::vector<size_t> pend_rbytes, pend_roff, my_sbytes;
+
+    int fail_abort() {
+        if (sh) sh->abort_flag.store(1);
+        return -1;
+    }
+    // spin until ok() holds; the abort flag and the time limit end it with an error
+    template <typename F>
+    int spin(F ok) {
+        const double t0 = now_s();
+        int spins = 0;
+        while (!ok()) {
+            if (sh->abort_flag.load(std::memory_order_relaxed)) { err = "a peer rank aborted the exchange"; return -1; }
+            if (++spins > 200) {
+                sched_yield();
+                if ((spins & 1023) == 0 && now_s() - t0 > timeout_s) {
+                    sh->abort_flag.store(1);
+                    err = "timed out waiting for the peer ranks (MGN_COMM_TIMEOUT_S)";
+                    return -1;
+                }
+            }
+        }
+        return 0;
+    }
+    int wait_barrier() {
+        const int32_t g = sh->bar_gen.load(std::memory_order_acquire);
+        if (sh->bar_count.fetch_add(1, std::memory_order_acq_rel) + 1 == nranks) {
+            sh->bar_count.store(0, std::memory_order_relaxed);
+            sh->bar_gen.store(g + 1, std::memory_order_release);
+            return 0;
+        }
+        return spin([&] { return sh->bar_gen.load(std::memory_order_acquire) != g; });
+    }
+    int init(const void* id, std::string& why) {
+        const unsigned char* u = static_cast<const unsigned char*>(id);
+        uint32_t magic;
+        memcpy(&magic, u, 4);
+        if (magic != LOCAL_MAGIC) { why = "the communicator id was not made for the MGN_COMM_LOCAL transport"; return -1; }
+        if (nranks > COMM_MAX_RANKS) { why = "MGN_COMM_LOCAL supports up to 64 ranks"; return -1; }
+        if (const char* e = getenv("MGN_COMM_TIMEOUT_S")) timeout_s = atof(e);
+        LocalKey key;
+        memcpy(key.b, u + 4, sizeof key.b);
+        {
+            std::lock_guard<std::mutex> lock(g_local_mu);
+            auto& reg = local_registry();
+            for (auto it = reg.begin(); it != reg.end();) it = it->second.expired() ? reg.erase(it) : std::next(it);
+            sh = reg[key].lock();
+            if (!sh) {
+                sh = std::make_shared<LocalShared>();
+                sh->nranks = nranks;
+                reg[key] = sh;
+            }
+        }
+        if (sh->nranks != nranks) { why = "the ranks of a MGN_COMM_LOCAL communicator disagree on nranks"; sh.reset(); return -1; }
+        if (sh->attached.fetch_add(1) >= nranks) { why = "the communicator id is in use already: make a new one with mgn_comm_unique_id"; sh.reset(); return -1; }
+        LocalShared::Slot& me = sh->slot[rank];
+        if (device_ok) {
+            if (hipGetDevice(&device) != hipSuccess) { why = "hipGetDevice failed"; fail_abort(); return -1; }
+            for (int i = 0; i < 2; ++i)
+                if (hipEventCreateWithFlags(&me.ready[i], hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&me.pulled[i], hipEventDisableTiming) != hipSuccess) {
+                    why = "hipEventCreate failed";
+                    fail_abort();
+                    return -1;
+                }
+        }
+        me.device = device_ok ? device : -1;
+        if (wait_barrier() != 0) { why = err; return -1; }
+        // Peers on other devices: read in place where the devices can reach each other, one hipMemcpyPeerAsync per peer otherwise.
+        // (Only the same-device path has run on hardware: see DESIGN.md, section 5.)
+        for (int q = 0; q < nranks; ++q) {
+            const int qd = sh->slot[q].device;
+            direct[q] = qd == device;
+            if (!device_ok || qd < 0 || qd == device) continue;
+            int can = 0;
+            if (hipDeviceCanAccessPeer(&can, device, qd) == hipSuccess && can) {
+                const hipError_t e = hipDeviceEnablePeerAccess(qd, 0);
+                direct[q] = e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled;
+                (void)hipGetLastError();
+            }
+        }
+        return 0;
+    }
+    int need_device() {
+        if (device_ok) return 0;
+        err = "a host-only handle has no device buffers to exchange";
+        return -1;
+    }
+    // post: see the protocol above
+    int post(const void* send, const size_t* sbytes, const size_t* soff, hipStream_t compute) {
+        LocalShared::Slot& me = sh->slot[rank];
+        const uint64_t g = gen + 1;
+        if (g >= 3)                                            // the event ring: nobody is still inside generation g - 2
+            for (int q = 0; q < nranks; ++q)
+                if (spin([&] { return sh->slot[q].done_gen.load(std::memory_order_acquire) >= g - 2; }) != 0) return fail_abort();
+        HIPC_ABORT(hipEventRecord(me.ready[g & 1], compute));
+        me.send = static_cast<const char*>(send);
+        for (int q = 0; q < nranks; ++q) { me.sbytes[q] = sbytes[q]; me.soff[q] = soff[q]; }
+        my_sbytes.assign(sbytes, sbytes + nranks);
+        gen = g;
+        me.ready_gen.store(g, std::memory_order_release);
+        return 0;
+    }
+    // pull + fence
+    int pull(void* recv, const size_t* rbytes, const size_t* roff, hipStream_t compute) {
+        LocalShared::Slot& me = sh->slot[rank];
+        const uint64_t g = gen;
+        PullTable tab;
+        tab.n = 0;
+        for (int q = 0; q < nranks; ++q) {
+            if (!rbytes[q]) continue;
+            LocalShared::Slot& pq = sh->slot[q];
+            if (q != rank) {
+                if (spin([&] { return pq.ready_gen.load(std::memory_order_acquire) >= g; }) != 0) return fail_abort();
+                // a peer that lists nothing for this rank does not wait for it and may be a generation ahead
+                if (pq.ready_gen.load(std::memory_order_acquire) != g || pq.sbytes[rank] != rbytes[q] || pq.device < 0) {
+                    err = "halo exchange size mismatch between ranks (did every rank call mgn_set_graph with the same mesh?)";
+                    return fail_abort();
+                }
+                HIPC_ABORT(hipStreamWaitEvent(compute, pq.ready[g & 1], 0));
+            } else if (me.sbytes[rank] != rbytes[rank]) {
+                err = "halo exchange size mismatch between ranks (a rank's segment to itself)";
+                return fail_abort();
+            }
+            const char* src = pq.send + pq.soff[rank];
+            if (direct[q]) tab.seg[tab.n++] = PullSeg{src, roff[q], rbytes[q]};
+            else HIPC_ABORT(hipMemcpyPeerAsync(static_cast<char*>(recv) + roff[q], device, src, pq.device, rbytes[q], compute));
+        }
+        if (tab.n) HIPC_ABORT(launch_a2a_pull(tab, recv, compute));
+        HIPC_ABORT(hipEventRecord(me.pulled[g & 1], compute));
+        me.pulled_gen.store(g, std::memory_order_release);
+        for (int q = 0; q < nranks; ++q) {
+            if (q == rank || !my_sbytes[q]) continue;
+            LocalShared::Slot& pq = sh->slot[q];
+            if (spin([&] { return pq.pulled_gen.load(std::memory_order_acquire) >= g; }) != 0) return fail_abort();
+            HIPC_ABORT(hipStreamWaitEvent(compute, pq.pulled[g & 1], 0));
+        }
+        me.done_gen.store(g, std::memory_order_release);
+        return 0;
+    }
+    int a2a_start(const void* send, const size_t* sbytes, const size_t* soff, void* recv, const size_t* rbytes, const size_t* roff,
+                  hipStream_t compute) override {
+        pending = false;
+        if (need_device() != 0) return fail_abort();
+        if (post(send, sbytes, soff, compute) != 0) return -1;
+        pend_recv = recv;
+        pend_rbytes.assign(rbytes, rbytes + nranks);
+        pend_roff.assign(roff, roff + nranks);
+        pending = true;
+        return 0;
+    }
+    int a2a_finish(hipStream_t compute) override {
+        if (!pending) { err = "a2a_finish without a pending a2a_start"; return fail_abort(); }
+        pending = false;
+        return pull(pend_recv, pend_rbytes.data(), pend_roff.data(), compute);
+    }
+    int allgather(const void* send, size_t bytes, void* recv, hipStream_t compute) override {
+        if (need_device() != 0) return fail_abort();
+        std::vector<size_t> sb(nranks, bytes), so(nranks, 0), ro(nranks);
+        for (int q = 0; q < nranks; ++q) ro[q] = (size_t)q * bytes;
+        if (post(send, sb.data(), so.data(), compute) != 0) return -1;
+        return pull(recv, sb.data(), ro.data(), compute);
+    }
+    // host collectives: publish pointers -> barrier -> copy out of the peers' buffers -> barrier (the buffers are the callers' own)
+    int a2a_host(const void* send, const size_t* sbytes, const size_t* soff, void* recv, const size_t* rbytes, const size_t* roff) override {
+        LocalShared::Slot& me = sh->slot[rank];
+        me.hsend = static_cast<const char*>(send);
+        me.hoff = soff;
+        me.hbytes = sbytes;
+        if (wait_barrier() != 0) return fail_abort();
+        for (int q = 0; q < nranks; ++q) {
+            if (!rbytes[q]) continue;
+            const LocalShared::Slot& pq = sh->slot[q];
+            if (!pq.hbytes || pq.hbytes[rank] != rbytes[q]) {
+                err = "halo exchange size mismatch between ranks (did every rank call mgn_set_graph with the same mesh?)";
+                return fail_abort();
+            }
+            memcpy(static_cast<char*>(recv) + roff[q], pq.hsend + pq.hoff[rank], rbytes[q]);
+        }
+        return wait_barrier() != 0 ? fail_abort() : 0;
+    }
+    int allreduce_f64(double* x, int n, int op, hipStream_t) override {
+        LocalShared::Slot& me = sh->slot[rank];
+        me.hsend = reinterpret_cast<const char*>(x);
+        me.hoff = me.hbytes = nullptr;
+        me.hall = (size_t)n * sizeof(double);
+        if (wait_barrier() != 0) return fail_abort();
+        std::vector<double> all((size_t)n * nranks);
+        for (int q = 0; q < nranks; ++q) {
+            if (sh->slot[q].hall != me.hall) { err = "allreduce length mismatch between ranks"; return fail_abort(); }
+            memcpy(all.data() + (size_t)q * n, sh->slot[q].hsend, me.hall);
+        }
+        if (wait_barrier() != 0) return fail_abort();          // everyone has read x: it may be overwritten
+        for (int i = 0; i < n; ++i) {                          // rank order: the same bits on every rank
+            double a = all[i];
+            for (int q = 1; q < nranks; ++q) {
+                const double v = all[(size_t)q * n + i];
+                a = op == 1 ? (v > a ? v : a) : a + v;
+            }
+            x[i] = a;
+        }
+        return 0;
+    }
+    int barrier(hipStream_t compute) override {
+        if (device_ok) HIPC(hipStreamSynchronize(compute));
+        return wait_barrier();
+    }
+};
+
 }  // namespace
+
+void comm_local_abort(const void* id) {
+    LocalKey key;
+    memcpy(key.b, static_cast<const unsigned char*>(id) + 4, sizeof key.b);
+    std::lock_guard<std::mutex> lock(g_local_mu);
+    auto& reg = local_registry();
+    auto it = reg.find(key);
+    if (it == reg.end()) return;
+    if (std::shared_ptr<LocalShared> sh = it->second.lock()) sh->abort_flag.store(1);
+}
 
 int comm_unique_id(void* id, int transport, std::string& why) {
     memset(id, 0, COMM_ID_BYTES);
@@ -483,9 +782,9 @@ int comm_unique_id(void* id, int transport, std::string& why) {
         memcpy(id, &uid, sizeof uid);
         return 0;
     }
-    if (transport == 1) {
+    if (transport == 1 || transport == 2) {
         unsigned char* u = static_cast<unsigned char*>(id);
-        memcpy(u, &HOST_MAGIC, 4);
+        memcpy(u, transport == 1 ? &HOST_MAGIC : &LOCAL_MAGIC, 4);
         bool ok = false;
         if (FILE* f = fopen("/dev/urandom", "rb")) {
             ok = fread(u + 4, 1, 12, f) == 12;
@@ -516,6 +815,13 @@ Comm* comm_create(const void* id, int transport, int rank, int nranks, bool devi
         HostComm* c = new (std::nothrow) HostComm();
         if (!c) { why = "host allocation failed"; return nullptr; }
         c->rank = rank; c->nranks = nranks; c->transport = 1; c->device_ok = device_ok;
+        if (c->init(id, why) != 0) { delete c; return nullptr; }
+        return c;
+    }
+    if (transport == 2) {
+        LocalComm* c = new (std::nothrow) LocalComm();
+        if (!c) { why = "host allocation failed"; return nullptr; }
+        c->rank = rank; c->nranks = nranks; c->transport = 2; c->device_ok = device_ok;
         if (c->init(id, why) != 0) { delete c; return nullptr; }
         return c;
     }

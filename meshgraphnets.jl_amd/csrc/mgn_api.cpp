@@ -2176,7 +2176,8 @@ int mgn_comm_unique_id(void* id, int32_t transport) try {
 int mgn_comm_init(mgn_handle* h, const void* id, size_t id_bytes, int32_t transport) try {
     if (!h) return MGN_E_ARG;
     if (!id || id_bytes != MGN_COMM_ID_BYTES) return fail(h, MGN_E_ARG, "mgn_comm_init: id must be MGN_COMM_ID_BYTES (%d) bytes", MGN_COMM_ID_BYTES);
-    if (transport != MGN_COMM_RCCL && transport != MGN_COMM_HOST) return fail(h, MGN_E_ARG, "mgn_comm_init: unknown transport %d", transport);
+    if (transport != MGN_COMM_RCCL && transport != MGN_COMM_HOST && transport != MGN_COMM_LOCAL)
+        return fail(h, MGN_E_ARG, "mgn_comm_init: unknown transport %d", transport);
     if (h->comm) return fail(h, MGN_E_STATE, "mgn_comm_init: the handle already has a communicator (mgn_comm_destroy first)");
     if (!h->host_only) HIPCHK(h, hipStreamSynchronize(h->stream));
     std::string why;
@@ -2333,6 +2334,19 @@ int mgn_halo_exchange_host(mgn_handle* h, const float* own_rows, float* halo_row
         rb[q] = (size_t)g.recv_rows[q] * rowb; ro[q] = r0; r0 += rb[q];
     }
     COMMCHK(h, h->comm->a2a_host(send.data(), sb.data(), so.data(), halo_rows, rb.data(), ro.data()));
+    return MGN_OK;
+} MGN_CATCH(h)
+
+// tests (not part of the public header): one sparse all-to-all-v through the handle's communicator on the handle's stream, at sizes
+// and alignments the engine never produces.  send_dev / recv_dev: device buffers; sbytes, soff, rbytes, roff: [nranks] as Comm::a2a_start
+// takes them.  Enqueues only; mgn_synchronize before reading recv_dev.
+int mgn_debug_comm_a2a(mgn_handle* h, const void* send_dev, const size_t* sbytes, const size_t* soff, void* recv_dev, const size_t* rbytes,
+                       const size_t* roff) try {
+    if (int rc = need(h, false, false)) return rc;
+    if (int rc = need_comm(h, "mgn_debug_comm_a2a")) return rc;
+    if (!sbytes || !soff || !rbytes || !roff) return fail(h, MGN_E_ARG, "mgn_debug_comm_a2a: null argument");
+    COMMCHK(h, h->comm->a2a_start(send_dev, sbytes, soff, recv_dev, rbytes, roff, h->stream));
+    COMMCHK(h, h->comm->a2a_finish(h->stream));
     return MGN_OK;
 } MGN_CATCH(h)
 

@@ -12,6 +12,7 @@ GPU raises.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -672,21 +673,22 @@ class Engine:
         """MGN_COMM_ID_BYTES bytes made on ONE rank; the host distributes them (a torch.distributed store, MPI, a file)."""
         lib = _capi.load()
         buf = C.create_string_buffer(_capi.MGN_COMM_ID_BYTES)
-        rc = lib.mgn_comm_unique_id(buf, {"rccl": 0, "host": 1}[transport])
+        rc = lib.mgn_comm_unique_id(buf, _capi.TRANSPORTS[transport])
         if rc != 0:
             raise MgnError(rc, lib.mgn_last_error(None).decode())
         return buf.raw
 
     def comm_init(self, comm_id, transport="rccl"):
         """Collective over the nranks handles of the partitioned mesh; afterwards processor_steps_dev / forward run at
-        nranks > 1 with the halo exchange inside the library.  transport "rccl" (one GPU per rank) or "host" (shared memory)."""
+        nranks > 1 with the halo exchange inside the library.  transport "rccl" (one GPU per rank), "host" (shared memory) or
+        "local" (the ranks are threads of this process; rows stay on the device)."""
         if len(comm_id) != _capi.MGN_COMM_ID_BYTES:
             raise ValueError("comm_id must be MGN_COMM_ID_BYTES bytes")
         buf = C.create_string_buffer(bytes(comm_id), _capi.MGN_COMM_ID_BYTES)
-        self._chk(self.lib.mgn_comm_init(self.h, buf, _capi.MGN_COMM_ID_BYTES, {"rccl": 0, "host": 1}[transport]))
+        self._chk(self.lib.mgn_comm_init(self.h, buf, _capi.MGN_COMM_ID_BYTES, _capi.TRANSPORTS[transport]))
 
     def comm_init_file(self, path, transport="rccl"):
-        self._chk(self.lib.mgn_comm_init_file(self.h, str(path).encode(), {"rccl": 0, "host": 1}[transport]))
+        self._chk(self.lib.mgn_comm_init_file(self.h, str(path).encode(), _capi.TRANSPORTS[transport]))
 
     def comm_destroy(self):
         self._chk(self.lib.mgn_comm_destroy(self.h))
@@ -721,6 +723,168 @@ class Engine:
         self._chk(self.lib.mgn_profile_read(self.h, ms, cnt))
         names = ["edge_step", "node_step", "encode", "decode", "halo", "edge_boundary"]
         return {n: dict(avg_ms=ms[i], count=cnt[i]) for i, n in enumerate(names)}
+
+
+class _RankView(Engine):
+    """Rank k of a GroupEngine: the group's own handle, borrowed for introspection (partition_info, owned_nodes, halo_*, profile_*).
+    No compute and no collective through it; it is never destroyed from here."""
+
+    def __init__(self, group, k):   # (no mgn_create: the handle is the group's)
+        self.lib = group.lib
+        self.cfg = MgnConfig.from_buffer_copy(group.cfg)
+        self.cfg.rank, self.cfg.nranks, self.cfg.device = k, group.nranks, group.devices[k]
+        self.h = C.c_void_p(self.lib.mgn_group_rank_handle(group.g, k))
+        if not self.h.value:
+            raise MgnError(_capi.MGN_E_ARG, f"no rank {k} in this group")
+        self.N, self.E, self.E2 = group.N, group.E, 0
+        self.n_own = self.n_halo = self.e_local = 0
+        if group.N:
+            self._refresh_partition()
+
+    def close(self):
+        self.h = C.c_void_p()
+
+
+class GroupEngine:
+    """All P partitions of a mesh driven from this one thread (mgn_group): rank k runs on devices[k] (ordinals may repeat), joined by an
+    in-process "local" communicator.  The mirrored calls have Engine's names and take the GLOBAL arrays; results are the complete ones
+    (rank 0's).  `with GroupEngine(...) as g:` or close()."""
+
+    def __init__(self, Fn, Fe, O, L=128, hidden_layers=2, mps=15, devices=(0,), dtype="f32", Fe2=None, ln_mode=0, ln_dims=0):
+        self.lib = _capi.load()
+        self.devices = [int(d) for d in devices]
+        self.nranks = len(self.devices)
+        self.cfg = MgnConfig(Fn, Fe, O, L, hidden_layers, mps, {"f32": 0, "bf16": 1}[dtype], 0, 1, -1,
+                             2 if Fe2 else 1, Fe2 or 0, ln_mode, {0: 0, 1: 1, "rows": 0, "all": 1}[ln_dims])
+        self.g = C.c_void_p()
+        dev = np.ascontiguousarray(self.devices, np.int32)
+        rc = self.lib.mgn_group_create(C.byref(self.cfg), self.nranks, i32(dev) if dev.size else None, C.byref(self.g))
+        if rc != 0:
+            raise MgnError(rc, self.lib.mgn_group_last_error(None).decode())
+        self.N = self.E = 0
+
+    def close(self):
+        if getattr(self, "g", None) is not None and self.g.value:
+            self.lib.mgn_group_destroy(self.g)
+            self.g = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise MgnError(rc, self.lib.mgn_group_last_error(self.g).decode())
+
+    def rank_engine(self, k):
+        return _RankView(self, k)
+
+    @property
+    def param_count(self):
+        return int(self.lib.mgn_param_count(C.byref(self.cfg)))
+
+    def synchronize(self):
+        self._chk(self.lib.mgn_group_synchronize(self.g))
+
+    def set_params(self, packed):
+        packed = _c32(packed).ravel()
+        self._chk(self.lib.mgn_group_set_params(self.g, f32(packed), packed.size))
+
+    def set_norms(self, node=None, edge=None, out=None):
+        def sp(p, n):
+            if p is None:
+                return None, None
+            return _c32(p[0], (n,)), _c32(p[1], (n,))
+        ns, nsh = sp(node, self.cfg.Fn)
+        es, esh = sp(edge, self.cfg.Fe)
+        os_, osh = sp(out, self.cfg.O)
+        self._chk(self.lib.mgn_group_set_norms(self.g, f32(ns), f32(nsh), f32(es), f32(esh), f32(os_), f32(osh)))
+
+    def set_graph(self, senders, receivers, N, index_base=0, mesh_pos=None):
+        s = np.ascontiguousarray(senders, dtype=np.int32).ravel()
+        r = np.ascontiguousarray(receivers, dtype=np.int32).ravel()
+        if s.size != r.size:
+            raise ValueError("DimensionMismatch: senders and receivers differ in length")
+        pos, pd = None, 0
+        if mesh_pos is not None:
+            pos = _c32(mesh_pos)
+            if pos.ndim != 2 or pos.shape[0] != N:
+                raise ValueError("DimensionMismatch: mesh_pos must be [N][dim]")
+            pd = pos.shape[1]
+        self._chk(self.lib.mgn_group_set_graph(self.g, N, s.size, i32(s), i32(r), index_base, f32(pos), pd))
+        self.N, self.E = int(N), int(s.size)
+
+    def set_static(self, node_type_onehot, ef_raw, val_mask=None):
+        O, Fn = self.cfg.O, self.cfg.Fn
+        oh = _c32(node_type_onehot, (self.N, Fn - O)) if Fn > O else None
+        ef = _c32(ef_raw, (self.E, self.cfg.Fe))
+        vm = _c32(val_mask, (self.N,)) if val_mask is not None else None
+        self._chk(self.lib.mgn_group_set_static(self.g, f32(oh), f32(ef), f32(vm)))
+
+    def forward(self, nf, ef):
+        nf = _c32(nf, (self.N, self.cfg.Fn))
+        ef = _c32(ef, (self.E, self.cfg.Fe))
+        out = np.zeros((self.N, self.cfg.O), np.float32)
+        self._chk(self.lib.mgn_group_forward(self.g, f32(nf), f32(ef), f32(out)))
+        return out
+
+    def ode_step(self, x, node_type_onehot=None, ef_raw=None, val_mask=None):
+        O, Fn = self.cfg.O, self.cfg.Fn
+        x = _c32(x, (self.N, O))
+        out = np.zeros((self.N, O), np.float32)
+        if node_type_onehot is None and ef_raw is None and val_mask is None:
+            self._chk(self.lib.mgn_group_ode_step(self.g, f32(x), None, None, None, f32(out)))
+            return out
+        oh = _c32(node_type_onehot, (self.N, Fn - O)) if Fn > O else None
+        ef = _c32(ef_raw, (self.E, self.cfg.Fe))
+        vm = _c32(val_mask, (self.N,)) if val_mask is not None else None
+        self._chk(self.lib.mgn_group_ode_step(self.g, f32(x), f32(oh), f32(ef), f32(vm), f32(out)))
+        return out
+
+    def rollout(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None,
+                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32):
+        """Engine.rollout on the partitioned mesh: (sol_u [n_saves][N][O], stats)."""
+        d, keep = Engine._rollout_desc(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask,
+                                       inflow_data, abstol, reltol, inflow_rule, time_type)
+        out = np.zeros((n_saves, self.N, self.cfg.O), np.float32)
+        d.out = f32(out)
+        self._chk(self.lib.mgn_group_rollout(self.g, C.byref(d)))
+        del keep
+        return out, dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)
+
+    def step(self, nf, ef, target, mask, mask_index_base=0, out=None):
+        """Engine.step on the partitioned mesh: (gs, loss).  nf / ef / target: host arrays (every rank reads them in place); `out`: a
+        NumPy array or a tensor on devices[0] for the gradient."""
+        nf = _c32(nf, (self.N, self.cfg.Fn))
+        ef = _c32(ef, (self.E, self.cfg.Fe))
+        target = _c32(target, (self.N, self.cfg.O))
+        mask = np.ascontiguousarray(mask, dtype=np.int32).ravel()
+        if out is None:
+            out = np.zeros(self.param_count, np.float32)
+        gs, p_gs = _host_or_device(out, (self.param_count,), writable=True)
+        loss = C.c_float()
+        self._chk(self.lib.mgn_group_step(self.g, f32(nf), f32(ef), f32(target), i32(mask), mask.size, mask_index_base, p_gs,
+                                          self.param_count, C.byref(loss)))
+        return gs, loss.value
+
+    def latents_randn(self, seed):
+        self._chk(self.lib.mgn_group_latents_randn(self.g, C.c_uint64(seed)))
+
+    def processor_steps_dev(self, nsteps):
+        self._chk(self.lib.mgn_group_processor_steps_dev(self.g, nsteps))
+
+    def latents_checksum(self):
+        a, b, c, d = (C.c_double() for _ in range(4))
+        self._chk(self.lib.mgn_group_latents_checksum(self.g, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(sum_v=a.value, sum_e=b.value, sumsq_v=c.value, sumsq_e=d.value)
 
 
 def triangles_to_edges_native(cells):
@@ -800,8 +964,15 @@ class GraphNetwork:
     owned by the caller so an optimiser can update it in place; it is re-uploaded when it changes."""
 
     def __init__(self, quantities, dims, e_norm, n_norm, o_norm, outputs, mps=15, layer_size=128,
-                 hidden_layers=2, ps=None, index_base=0, device=-1):
-        self.engine = Engine(quantities, dims + 1, outputs, layer_size, hidden_layers, mps, device=device)
+                 hidden_layers=2, ps=None, index_base=0, device=-1, gpus=None):
+        """gpus: HIP ordinals (may repeat), one edge-cut partition each, all driven from this process through a GroupEngine; None: the
+        environment variable MGN_GPUS (a comma list) if set, else one partition on `device`."""
+        if gpus is None and os.environ.get("MGN_GPUS"):
+            gpus = [int(x) for x in os.environ["MGN_GPUS"].split(",") if x.strip()]
+        if gpus:
+            self.engine = GroupEngine(quantities, dims + 1, outputs, layer_size, hidden_layers, mps, devices=gpus)
+        else:
+            self.engine = Engine(quantities, dims + 1, outputs, layer_size, hidden_layers, mps, device=device)
         self.e_norm, self.n_norm, self.o_norm = e_norm, n_norm, o_norm
         self.st = None
         self.index_base = index_base
@@ -860,12 +1031,13 @@ def init_params(cfg, seed=None):
 
 
 def load(quantities, dims, e_norms, n_norms, o_norms, outputs, mps, layer_size, hidden_layers, opt, device, path, index_base=0,
-         hip_device=-1, seed=None):
+         hip_device=-1, seed=None, gpus=None):
     """`load(...) -> (mgn, opt_state, df_train, df_valid)` with the twelve positional arguments of the reference's call sites
     (src/MeshGraphNets.jl:282-285, 537-540).  With a checkpoint written by `save` in `path`, ALL of its state comes back: parameters,
     loss log, the normalisers' statistics restored over the freshly built `e_norms` / `n_norms` / `o_norms` (what `eval_network`
     relies on, :529-540) and `opt_state` (kept on resume, :287-289; None without a checkpoint or when `opt` is None).  `device` (the
-    reference's Lux device function) is accepted and ignored."""
+    reference's Lux device function) is accepted and ignored.  gpus (or MGN_GPUS, a comma list, for the unchanged twelve-positional
+    call): one partition per listed HIP ordinal behind the same `mgn` (GraphNetwork)."""
     from . import checkpoint as ck
     probe = _capi.load().mgn_param_count
     cfg = MgnConfig(Fn=quantities, Fe=dims + 1, O=outputs, L=layer_size, hidden_layers=hidden_layers, mps=mps, n_edge_sets=1)
@@ -876,7 +1048,7 @@ def load(quantities, dims, e_norms, n_norms, o_norms, outputs, mps, layer_size, 
     else:
         ps, e_norms, n_norms, o_norms, opt_state, df_train, df_valid = got
     mgn = GraphNetwork(quantities, dims, e_norms, n_norms, o_norms, outputs, mps, layer_size, hidden_layers, ps=ps,
-                       index_base=index_base, device=hip_device)
+                       index_base=index_base, device=hip_device, gpus=gpus)
     return mgn, opt_state, df_train, df_valid
 
 
