@@ -429,6 +429,77 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
 int mgn_step(mgn_handle* h, const float* nf, const float* ef, const float* target, const int32_t* mask, int64_t nmask,
              int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
 
+/* ---- derivative training on a device-resident trajectory -----------------------------------------------------------------
+ * The loop `for datapoint in 1:delta` of the reference's default strategy (DerivativeTraining, src/MeshGraphNets.jl:364-378:
+ * init_train_step -> step! -> Optimisers.update) without host work per datapoint.  The reference puts the fields, their `target|`
+ * copies and the noise on the device once per trajectory (add_targets! and preprocess!, src/dataset.jl:461-509) and forms
+ * o_norm((next - cur) / dt) and build_graph there once per datapoint (init_train_step of the derivative strategies,
+ * src/strategies.jl:395-416); these entry points do the same.  Optimisers.update and the order in which datapoints are visited
+ * stay with the caller.  fp32, one partition (MGN_E_STATE otherwise); every array may be a host or a device pointer unless noted.
+ *
+ * mgn_train_set_trajectory, once per trajectory and after the graph is complete (mgn_set_graph, and mgn_set_edge_set where there
+ * is a second set): frames [T][N][O] holds frame t = data[field][:, :, t] of the target fields, concatenated in output order, in
+ * the caller's node order; T >= 2, and the last frame is only ever a target (what add_targets! makes of a trajectory), so the
+ * datapoints are 0 .. T - 2.  The time step of datapoint t is times[t + 1] - times[t] (fp32), or dt when times == NULL.
+ * node_type_onehot [N][Fn - O]: the one-hot columns that follow the O state columns, as in mgn_ode_step; ef_raw [E][Fe] in the
+ * caller's edge order.  All three are brought into the engine's order here, once: no gather per step remains.  A new graph and
+ * mgn_destroy drop the trajectory and the noise settings; mgn_set_params (a training loop calls it before every step) and
+ * mgn_set_norms do not.  The call blocks until the arrays have left the caller's memory.
+ *
+ * mgn_train_set_noise (preprocess!, src/dataset.jl:496-509): the input state of datapoint t is
+ *     cur_t[n][o] = frames[t][n][o] + stddev[o] * z(seed, t, n, o)     on nodes with noisy[n] != 0 (noisy == NULL: every node),
+ * frames[t] exactly on the others, and everywhere when stddev == NULL.  z is the engine's N(0,1) generator (splitmix64 of the
+ * key, Box-Muller; the one mgn_latents_randn uses) on the trajectory as a [T N][O] array: key (seed, row t N + n, column o) with n
+ * the CALLER's node id, so the noise does not depend on the engine's numbering.  The product and the sum are rounded one by one.
+ * The next state frames[t + 1] carries no noise: the reference adds it to data[field], not to data["target|field"].  noisy [N] is
+ * read on the host.  The settings hold for later trajectories on the same graph.
+ *
+ * What a datapoint is made of, all in fp32 with IEEE subtraction and division, one rounding each (no contraction, no fast divide):
+ *     d      = (frames[t + 1] - cur_t) / delta                    the raw target
+ *     target = (d - out_shift) / out_scale                        the forward of the normaliser whose inverse mgn_set_norms holds
+ *     nf     = [cur_t ; onehot] * node_scale + node_shift         ef = ef_raw * edge_scale + edge_shift
+ * nf and ef are zero-padded to L and use the very expression the right-hand side's inputs are staged with, so they carry the bits
+ * mgn_ode_vjp computes with for the same raw inputs.  A map mgn_set_norms left out is the identity.
+ *
+ * mgn_step_datapoint is mgn_step on these arrays: mask, mask_index_base, grads, n_grads and loss as there (mask on the host, grads a
+ * host or device pointer), its argument checks, one or two edge sets (the second set's features installed by
+ * mgn_set_edge_features), hidden_layers, ln_mode, ln_dims, the arena plan and the hipGraph replay of small meshes all unchanged.
+ * The normalised edge rows are kept and rebuilt only when the trajectory or the norms change.
+ *
+ * Online normalisers (GraphNetCore NormaliserOnline): mgn_train_online_norms switches a group -- the node STATE columns, the edge
+ * features, the output -- to online and zeroes its totals (sum, sum of squares, count, calls); a group left off keeps what
+ * mgn_set_norms gave it, and the one-hot columns are never online (the reference gives node_type an offline min-max normaliser).
+ * The state outlives graphs and trajectories, as the normalisers of the reference's model do.  With accumulate != 0 every online
+ * group with calls < max_accumulations first adds this datapoint's raw rows -- cur_t (N rows), ef_raw (E rows), d (N rows), in the
+ * caller's order -- to double totals that live on the device: mgn_feature_stats' reduction in mgn_feature_stats' order, so the
+ * totals are bitwise repeatable and equal the running sum of that entry point's results on the exported raw arrays (the sums of
+ * ef_raw are formed once per trajectory and added per call).  One small kernel then rewrites the group's entries of the norms:
+ * mean and std = sqrt(max(sumsq / c - mean^2, 0)) in double, rounded to float, std = max(std, std_epsilon); scale = 1.0f / std,
+ * shift = -mean * scale; the output group stores std, mean.  The datapoint is normalised with the updated maps (the reference's
+ * normaliser call accumulates, then normalises).  No copy to the host and no synchronisation are added; count and calls are host
+ * numbers.  With accumulate == 0 the maps are used as they stand (a later mgn_set_norms overwrites an online group's entries, too,
+ * until that group's next accumulating step).  Every later entry point on the handle computes with the
+ * rewritten norms; the resident right-hand side of mgn_set_static is invalidated as mgn_set_norms invalidates it.
+ * mgn_train_norm_state reads (write = 0) or restores (write = 1) a group's totals and count_and_calls = {count, calls}: the
+ * checkpoint hook for save! / load.  Restored totals give the group's map at the next datapoint; sum and sum_squares are host
+ * arrays of O, Fe, O doubles for groups 0, 1, 2.
+ *
+ * mgn_datapoint_export returns, in the caller's order, what the step consumes (normalised != 0: nf, ef, target as above, unpadded)
+ * or the raw arrays (normalised == 0: [cur_t ; onehot], ef_raw and d).  Any output may be NULL.  It never accumulates.
+ *
+ * Refusals, all before any launch, the handle stays usable: MGN_E_STATE without a graph, without a trajectory (step, export), on
+ * a partitioned handle or with dtype != MGN_F32; MGN_E_ARG for T < 2, a datapoint outside [0, T - 2], Fn < O, a missing onehot
+ * when Fn > O, a missing ef_raw with E > 0, a zero time step (checked on the host at upload), max_accumulations <= 0 or
+ * std_epsilon <= 0, a group outside 0 .. 2, and what mgn_step refuses in its own arguments.                                   */
+int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int32_t T, const float* times, float dt,
+                             const float* node_type_onehot, const float* ef_raw);
+int mgn_train_set_noise(mgn_handle* h, const float* stddev, const uint8_t* noisy, uint64_t seed);
+int mgn_train_online_norms(mgn_handle* h, int32_t node_on, int32_t edge_on, int32_t out_on, double max_accumulations, float std_epsilon);
+int mgn_train_norm_state(mgn_handle* h, int32_t group, int32_t write, double* sum, double* sum_squares, double* count_and_calls);
+int mgn_step_datapoint(mgn_handle* h, int32_t datapoint, int32_t accumulate, const int32_t* mask, int64_t nmask,
+                       int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
+int mgn_datapoint_export(mgn_handle* h, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target);
+
 /* Vector-Jacobian product of the right-hand side f = mgn_ode_step (reference ode_step, src/solve.jl:188-219) for the
  * solver-based training strategies, where the adjoint of `solve` needs lambda^T df/dx and lambda^T df/dps per RHS
  * evaluation (ZygoteVJP inside the sensitivity algorithm, src/strategies.jl:175-196).  Inputs as mgn_ode_step (raw edge

@@ -31,6 +31,7 @@ export FeatureGraph, GraphNetwork, step!, load, save!, shooting_grad
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
        native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
 export rollout_eval, native_validation_step
+export train_trajectory!, step_datapoint!, online_norms!, norm_state, norm_state!, datapoint_export
 export comm_unique_id, comm_init!, comm_init_file!, comm_barrier, processor_steps_dev!
 
 const LIB = get(ENV, "MGN_HIP_LIB", joinpath(@__DIR__, "..", "meshgraphnets.jl_amd", "lib", "libmgn_hip.so"))
@@ -504,6 +505,86 @@ function feature_stats(mgn::GraphNetwork, x::Matrix{Float32})
         ccall((:mgn_feature_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int32, Ptr{Float64}, Ptr{Float64}),
             mgn.handle, x, rows, dim, s, q))
     return s, q
+end
+
+# ---- derivative training on a device-resident trajectory: src/MeshGraphNets.jl:364-378 over src/strategies.jl:395-416 ---------------
+"""
+`train_trajectory!(mgn, frames, dt, node_type_onehot, edge_features; noise_stddev, noisy_nodes, seed)`: once per trajectory, after
+`set_trajectory_graph!` -- what `add_targets!` and `preprocess!` (src/dataset.jl:461-509) do for the derivative strategies, on the
+device.  `frames` is O x N x T: `vcat([data[field] for field in target_fields]...)` of every frame, the last one only ever a target;
+`dt` is `meta["dt"]`, a number or the vector of times.  `noise_stddev` (length O) and `noisy_nodes` (length N, nonzero = noisy;
+`nothing` = every node) replace the noise `preprocess!` adds to `data[field]`; the targets carry none.
+`step_datapoint!(mgn, datapoint, mask; accumulate)` is then `init_train_step` + `step!` for `datapoint` (1-based, as the loop
+`for datapoint in 1:delta` counts): it returns `((gs,), loss)` as `step!` does, so `Optimisers.update` runs unchanged on `gs[1]`.
+`online_norms!(mgn; node, edge, out, max_acc, std_epsilon)` switches normalisers to `NormaliserOnline` on the device; with
+`accumulate = true` a step adds its raw rows to their totals and renews their maps first.  `norm_state` / `norm_state!` read and
+restore one group's totals (0 node state columns, 1 edge features, 2 output) for `save!` / `load`; `datapoint_export` returns the
+arrays a step consumes.
+"""
+function train_trajectory!(mgn::GraphNetwork, frames::Array{Float32, 3}, dt, node_type_onehot::Union{Nothing, Matrix{Float32}},
+        edge_features::Matrix{Float32}; noise_stddev::Union{Nothing, Vector{Float32}} = nothing,
+        noisy_nodes::Union{Nothing, AbstractVector} = nothing, seed::Integer = 0)
+    T = size(frames, 3)
+    times = dt isa AbstractArray ? Vector{Float32}(vec(dt)) : nothing
+    step = times === nothing ? Float32(dt) : 0.0f0
+    GC.@preserve frames times node_type_onehot edge_features check(mgn.handle,
+        ccall((:mgn_train_set_trajectory, LIB), Cint,
+            (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}, Float32, Ptr{Float32}, Ptr{Float32}),
+            mgn.handle, frames, T, opt_ptr(times), step, opt_ptr(node_type_onehot), edge_features))
+    noisy = noisy_nodes === nothing ? nothing : Vector{UInt8}(noisy_nodes .!= 0)
+    nz = noisy === nothing ? Ptr{UInt8}(C_NULL) : pointer(noisy)
+    GC.@preserve noise_stddev noisy check(mgn.handle,
+        ccall((:mgn_train_set_noise, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{UInt8}, UInt64),
+            mgn.handle, opt_ptr(noise_stddev), nz, UInt64(seed)))
+    return mgn
+end
+
+function step_datapoint!(mgn::GraphNetwork, datapoint::Integer, mask::AbstractVector{<:Integer}; accumulate::Bool = false)
+    ps = mgn.ps::Vector{Float32}
+    sync_params!(mgn, ps)
+    gs = Vector{Float32}(undef, length(ps))
+    loss = Ref{Float32}(0)
+    mk = Vector{Int32}(Array(mask))
+    GC.@preserve mk gs check(mgn.handle,
+        ccall((:mgn_step_datapoint, LIB), Cint,
+            (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Int64, Int32, Ptr{Float32}, Csize_t, Ref{Float32}),
+            mgn.handle, datapoint - 1, accumulate ? 1 : 0, mk, length(mk), 1, gs, length(gs), loss))
+    return (gs,), loss[]
+end
+
+function online_norms!(mgn::GraphNetwork; node::Bool = true, edge::Bool = true, out::Bool = true, max_acc::Real = 1e6,
+        std_epsilon::Real = 1.0f-8)
+    check(mgn.handle, ccall((:mgn_train_online_norms, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Float64, Float32),
+        mgn.handle, node ? 1 : 0, edge ? 1 : 0, out ? 1 : 0, Float64(max_acc), Float32(std_epsilon)))
+    return mgn
+end
+
+norm_dim(mgn::GraphNetwork, group::Integer) = group == 1 ? Int(mgn.cfg.Fe) : Int(mgn.cfg.O)
+
+"(sum, sum_squares, count, calls) of an online group, Float64 as on the device."
+function norm_state(mgn::GraphNetwork, group::Integer)
+    s = zeros(Float64, norm_dim(mgn, group)); q = zeros(Float64, norm_dim(mgn, group)); cc = zeros(Float64, 2)
+    GC.@preserve s q cc check(mgn.handle,
+        ccall((:mgn_train_norm_state, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            mgn.handle, group, 0, s, q, cc))
+    return s, q, cc[1], cc[2]
+end
+
+function norm_state!(mgn::GraphNetwork, group::Integer, s::Vector{Float64}, q::Vector{Float64}, count::Real, calls::Real)
+    cc = Float64[count, calls]
+    GC.@preserve s q cc check(mgn.handle,
+        ccall((:mgn_train_norm_state, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            mgn.handle, group, 1, s, q, cc))
+    return mgn
+end
+
+"(nf Fn x N, ef Fe x E, target O x N) of `datapoint` (1-based): normalised as the step consumes them, or raw."
+function datapoint_export(mgn::GraphNetwork, datapoint::Integer, N::Integer, E::Integer; normalised::Bool = true)
+    nf = Matrix{Float32}(undef, mgn.cfg.Fn, N); ef = Matrix{Float32}(undef, mgn.cfg.Fe, E); tg = Matrix{Float32}(undef, mgn.cfg.O, N)
+    GC.@preserve nf ef tg check(mgn.handle,
+        ccall((:mgn_datapoint_export, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+            mgn.handle, datapoint - 1, normalised ? 1 : 0, nf, ef, tg))
+    return nf, ef, tg
 end
 
 # ---- fused right-hand side and native rollout (optional fast paths) ---------------------------------------------------------------

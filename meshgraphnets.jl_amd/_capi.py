@@ -108,6 +108,12 @@ PROTOTYPES = {
     "mgn_shooting_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnShootingDesc), _f32p, _f32p, C.c_float, _f32p, C.c_size_t,
                                     _f32p]),
     "mgn_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
+    "mgn_train_set_trajectory": (C.c_int, [_H, _f32p, C.c_int32, _f32p, C.c_float, _f32p, _f32p]),
+    "mgn_train_set_noise": (C.c_int, [_H, _f32p, C.POINTER(C.c_uint8), C.c_uint64]),
+    "mgn_train_online_norms": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_float]),
+    "mgn_train_norm_state": (C.c_int, [_H, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
+    "mgn_step_datapoint": (C.c_int, [_H, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
+    "mgn_datapoint_export": (C.c_int, [_H, C.c_int32, C.c_int32, _f32p, _f32p, _f32p]),
     "mgn_ode_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
     "mgn_forward_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
     "mgn_processor_steps": (C.c_int, [_H, _f32p, _f32p, C.c_int32]),

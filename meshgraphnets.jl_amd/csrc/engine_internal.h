@@ -127,6 +127,7 @@ struct mgn_engine {
     DevBuf norms;
     std::vector<float> norms_host;   // the same affine maps on the host (the whole-array LayerNorm mode's mgn_ode_step builds its inputs there)
     bool have_nnorm = false, have_enorm = false, have_onorm = false;
+    bool norms_host_stale = false;   // the device rewrote `norms` (online normalisers of mgn_step_datapoint): sync_norms_host before norms_host is read
 
     // graph
     bool have_graph = false;
@@ -224,7 +225,8 @@ void pack_chunk_tmajor(float* dst, const float* frag, int L);
 void pack_chunk16(float* dst, const float* W, int ldw, int kbase);
 // vector of L values (stride between consecutive features = stride) -> table fragment order
 void pack_tab(float* dst, const float* vec, int L, int stride = 1);
-// mgn_train.cpp: drop training-side state that depends on the parameters (what & 1) or the graph (what & 2); free it all
+// mgn_train.cpp: drop training-side state that depends on the parameters (what & 1), the graph (what & 2: the resident trajectory of
+// mgn_train_set_trajectory goes with it) or the norms (what & 4: that trajectory's normalised edge rows); free it all
 void train_invalidate(mgn_engine* h, int what);
 void train_free(mgn_engine* h);
 // mgn_config.ln_dims = MGN_LN_ALL (whole-array LayerNorm): the unfused forward (mgn_train.cpp)
@@ -276,6 +278,7 @@ int run_processor(mgn_engine* h, int nsteps);
 int upload_inputs(mgn_engine* h, const float* a, int wa, const float* b, int wb, const float* ef, bool engine_order = false);
 bool elat_src_ok(mgn_engine* h);
 void invalidate_static(mgn_engine* h);
+int sync_norms_host(mgn_engine* h);    // norms_host <- norms where the device rewrote them (a copy of 2 (Fn + Fe + O) floats, blocking); else nothing
 size_t tile_floats(int64_t ntiles, int L);
 int alloc_latents(mgn_engine* h);
 int rebuild_graph(mgn_engine* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner, const char* who,

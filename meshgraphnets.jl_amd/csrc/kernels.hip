@@ -2286,13 +2286,6 @@ __global__ void k_tiles_to_rows(const float* __restrict__ src, const int64_t* __
         reinterpret_cast<const f32x4*>(src)[(r / TILE) * (TILE * pieces) + (int64_t)m * 64 + 32 * hh + (r % TILE)];
 }
 
-DEVINL uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // N(0,1) keyed by (seed, global row id, feature): identical whatever the partition (KAT-7 at scale).
 // dst is TILE-MAJOR storage of `rows` rows padded to whole 32-row tiles; padding rows are zeroed.
 __global__ void k_randn_rows(float* __restrict__ dst, const int64_t* __restrict__ gid64, const int32_t* __restrict__ gid32,
@@ -2307,10 +2300,7 @@ __global__ void k_randn_rows(float* __restrict__ dst, const int64_t* __restrict_
     const int f = 32 * (m >> 2) + 8 * (m & 3) + 4 * (lane >> 5) + q;
     if (r >= rows) { dst[i] = 0.f; return; }
     const uint64_t g = gid64 ? (uint64_t)gid64[r] : (gid32 ? (uint64_t)gid32[r] : (uint64_t)r);
-    const uint64_t bits = splitmix64(seed ^ splitmix64(g * (uint64_t)L + (uint64_t)f));
-    const float u1 = ((float)(uint32_t)(bits >> 40) + 1.0f) * (1.0f / 16777216.0f);  // (0,1]
-    const float u2 = (float)(uint32_t)((bits >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-    dst[i] = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    dst[i] = randn_keyed(seed, g * (uint64_t)L + (uint64_t)f);
 }
 
 // deterministic: every block writes its own partial (fixed grid, fixed per-thread stride), the host adds

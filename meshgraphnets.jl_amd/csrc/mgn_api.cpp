@@ -572,6 +572,16 @@ void mgn::invalidate_static(mgn_engine* h) {
     h->rhs_warm = false;
 }
 
+int mgn::sync_norms_host(mgn_engine* h) {
+    if (!h->norms_host_stale) return MGN_OK;
+    const size_t n = (size_t)2 * (h->cfg.Fn + h->cfg.Fe + h->cfg.O);
+    h->norms_host.resize(n);
+    HIPCHK(h, hipMemcpyAsync(h->norms_host.data(), h->norms.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->norms_host_stale = false;
+    return MGN_OK;
+}
+
 // step 0's edge launch can read its e rows from a second array (EdgeArgs::ElatSrc): one edge set on the 16-row kernels, one partition
 bool mgn::elat_src_ok(mgn_engine* h) {
     static const int on = [] { const char* e = getenv("MGN_RHS_ELAT_SRC"); return e ? atoi(e) : 1; }();   // 0: restore copy per right-hand side
@@ -956,7 +966,9 @@ int mgn_set_norms(mgn_handle* h, const float* ns, const float* nsh, const float*
     HIPCHK(h, h->norms.ensure(v.size() * 4));
     HIPCHK(h, hipMemcpy(h->norms.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
     h->norms_host = v;
+    h->norms_host_stale = false;
     invalidate_static(h);
+    train_invalidate(h, 4);
     h->have_nnorm = ns != nullptr;
     h->have_enorm = es != nullptr;
     h->have_onorm = os != nullptr;
@@ -1566,6 +1578,7 @@ static int lnall_ode_step(mgn_handle* h, const float* x, const float* onehot, co
     }
     if (!ef_raw || (c.Fn > c.O && !onehot)) return fail(h, MGN_E_ARG, "mgn_ode_step: null argument");
     invalidate_static(h);   // the one-shot path overwrites the resident inputs
+    if (int rc = sync_norms_host(h)) return rc;
     const int64_t N = h->g.N, E = h->g.set[0].E;
     const float* nrm = h->norms_host.empty() ? nullptr : h->norms_host.data();   // [node scale, shift | edge scale, shift | out scale, shift]
     const float* ns = (nrm && h->have_nnorm) ? nrm : nullptr;

@@ -968,6 +968,7 @@ int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
         kid->params_set = true;
         kid->params_gen = h->params_gen;
     }
+    if (int rc = sync_norms_host(h)) return rc;
     if (c->norms_host != h->norms_host || c->have_nnorm != h->have_nnorm || c->have_enorm != h->have_enorm || c->have_onorm != h->have_onorm) {
         const mgn_config& k = h->cfg;
         const float* v = h->norms_host.data();

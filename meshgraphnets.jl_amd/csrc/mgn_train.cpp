@@ -122,12 +122,41 @@ struct TrainState {
     size_t i_acc_row = 0, i_acc_ptr = 0, i_acc_pos = 0;
     int32_t n_acc = 0;
     int64_t mask_n = 0;          // entries of the device mask: the whole mask, on a partition the entries this rank owns
+    // mgn_step_datapoint: the trajectory of mgn_train_set_trajectory, resident in the engine's node order, and the noise settings.
+    // Dropped with the graph (train_invalidate & 2); mgn_set_params and mgn_set_norms leave it alone.
+    struct Trajectory {
+        bool have = false;
+        int32_t T = 0;
+        DevBuf frames, onehot, ef_raw;   // [T][N][O], [N][Fn - O] in the engine's node order; [E][Fe] in the caller's edge order (as ef_pad holds it)
+        std::vector<float> delta;        // [T - 1]: dt, or times[t + 1] - times[t]
+        bool noise = false, some_nodes = false;
+        DevBuf stddev, noisy;            // [O]; [N] 0/1 in the engine's order (some_nodes)
+        uint64_t seed = 0;
+        bool ef_pad_ok = false;          // the arena's ef_pad[0] holds this trajectory's edge features under the norms as they stand
+        bool ef_sums_ok = false;         // ef_sums holds ef_raw's column sums
+        DevBuf ef_sums;                  // [2][Fe] doubles: what one accumulation of ef_raw adds (mgn_feature_stats' sums, formed once)
+        DevBuf work;                     // accumulating steps: cur and d [N][O] each in the caller's order, then launch_col_stats' partials of both
+        void drop() {
+            have = false; T = 0; noise = some_nodes = false; ef_pad_ok = ef_sums_ok = false;
+            delta.clear();
+            for (DevBuf* b : {&frames, &onehot, &ef_raw, &stddev, &noisy, &ef_sums, &work}) b->release();
+        }
+    } traj;
+    // The online normalisers (GraphNetCore NormaliserOnline) of mgn_train_online_norms: group 0 the node state columns, 1 the edge
+    // features, 2 the output.  They outlive graphs and trajectories, like the normalisers of the reference's model.
+    struct OnlineGroup {
+        bool online = false, dirty = false;   // dirty: the totals were restored; the maps follow at the next datapoint
+        double count = 0.0, calls = 0.0, max_acc = 1e6;
+        float eps = 1e-8f;
+    } on[3];
+    DevBuf on_totals;            // doubles [node sum, sum of squares (O each) | edge (Fe each) | output (O each)]
 };
 
 void train_invalidate(mgn_engine* h, int what) {
     if (!h || !h->train) return;
     if (what & 1) h->train->packed = false;
-    if (what & 2) { h->train->graph_ready = false; h->train->la_ready = false; }
+    if (what & 2) { h->train->graph_ready = false; h->train->la_ready = false; h->train->traj.drop(); }
+    if (what & 4) h->train->traj.ef_pad_ok = false;
 }
 
 void train_free(mgn_engine* h) {
@@ -466,6 +495,7 @@ int prepare_graph(mgn_engine* h) {
         if (const char* e = getenv("MGN_TRAIN_KEEP_STEPS")) keep0 = std::max(0, std::min(mps, atoi(e)));
     }
     T.drop_graphs();
+    T.traj.ef_pad_ok = false;
     T.size_cus = train_size_cus();
     T.wg_rpb_last = T.wg_rpb_node = 0;
     for (int64_t& v : T.wg_rpb_edge) v = 0;
@@ -498,9 +528,10 @@ using namespace mgn;
 
 namespace {
 
-// The four kinds of job that differentiate the model: step! (mgn_step), the pullback of the model call (mgn_forward_vjp), of the right-hand
-// side (mgn_ode_vjp), and one step of a reverse sweep (mgn_solver_grad and its kin: the right-hand side's, on resident inputs)
-enum JobKind { JOB_STEP, JOB_FORWARD_VJP, JOB_RHS_VJP, JOB_SWEEP_STEP };
+// The five kinds of job that differentiate the model: step! (mgn_step), the pullback of the model call (mgn_forward_vjp), of the right-hand
+// side (mgn_ode_vjp), one step of a reverse sweep (mgn_solver_grad and its kin: the right-hand side's, on resident inputs), and step! on
+// one datapoint of the resident trajectory (mgn_step_datapoint: init_train_step on the device, then mgn_step's stages)
+enum JobKind { JOB_STEP, JOB_FORWARD_VJP, JOB_RHS_VJP, JOB_SWEEP_STEP, JOB_DATAPOINT };
 
 struct TrainJob {
     JobKind kind = JOB_STEP;
@@ -518,6 +549,8 @@ struct TrainJob {
     // and the statics in theirs (Sweep::begin staged them); xbar stays in io, the gradient is added to gacc (first: gacc = it), no synchronisation
     bool first = false;
     double* gacc = nullptr;
+    // step! on a datapoint of the resident trajectory (TrainState::traj): mask, loss and grads as for step!
+    int32_t datapoint = 0; bool accumulate = false;
 };
 
 // partitions: the entry point runs on a partitioned mesh (mgn_step); every check comes before the first collective
@@ -539,6 +572,155 @@ int train_prepare(mgn_handle* h, const char* who, size_t n_grads, bool partition
         if (int rc = pack_training_weights(h)) return rc;
     if (!h->train->graph_ready || h->train->size_cus != train_size_cus())   // (the arena's placeholders follow the size rules the launches read)
         if (int rc = prepare_graph(h)) return rc;
+    return MGN_OK;
+}
+
+// ---- mgn_step_datapoint: one datapoint's nf_pad, target and ef_pad from the resident trajectory (TrainState::traj) ----
+int online_dim(const mgn_config& c, int g) { return g == 1 ? c.Fe : c.O; }
+size_t online_off(const mgn_config& c, int g) { return g == 0 ? 0 : (g == 1 ? (size_t)2 * c.O : (size_t)2 * c.O + 2 * c.Fe); }
+int online_totals_ready(mgn_engine* h) {
+    DevBuf& b = h->train->on_totals;
+    if (b.p) return MGN_OK;
+    const size_t bytes = (size_t)(4 * h->cfg.O + 2 * h->cfg.Fe) * sizeof(double);
+    HIPCHK(h, b.ensure(bytes));
+    HIPCHK(h, hipMemsetAsync(b.p, 0, bytes, h->stream));
+    return MGN_OK;
+}
+// h->norms exists (identity maps where mgn_set_norms was never called) and an online group's map is applied
+int datapoint_norms_ready(mgn_engine* h) {
+    const mgn_config& c = h->cfg;
+    const size_t n = (size_t)2 * (c.Fn + c.Fe + c.O);
+    if (!h->norms.p || h->norms.bytes < n * 4) {
+        std::vector<float> v(n, 0.f);
+        float* q = v.data();
+        for (int d : {c.Fn, c.Fe, c.O}) {
+            for (int i = 0; i < d; ++i) q[i] = 1.f;
+            q += 2 * d;
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, h->norms.ensure(n * 4));
+        HIPCHK(h, hipMemcpy(h->norms.p, v.data(), n * 4, hipMemcpyHostToDevice));
+        h->norms_host = v;
+        h->norms_host_stale = false;
+    }
+    const TrainState& T = *h->train;
+    if (T.on[0].online) h->have_nnorm = true;
+    if (T.on[1].online) h->have_enorm = true;
+    if (T.on[2].online) h->have_onorm = true;
+    return MGN_OK;
+}
+DatapointArgs datapoint_args(mgn_engine* h, int32_t t, bool normalised) {
+    const TrainState::Trajectory& R = h->train->traj;
+    const mgn_config& c = h->cfg;
+    const int64_t N = h->g.n_own;
+    const float* nrm = h->norms.as<float>();
+    DatapointArgs a{};
+    a.cur = R.frames.as<float>() + (size_t)t * (size_t)N * c.O;       // (64-bit: T N O passes 2^31 on the largest meshes)
+    a.nxt = a.cur + (size_t)N * c.O;
+    a.onehot = c.Fn > c.O ? R.onehot.as<float>() : nullptr;
+    a.gid = h->g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+    a.noisy = R.noise && R.some_nodes ? R.noisy.as<uint8_t>() : nullptr;
+    a.stddev = R.noise ? R.stddev.as<float>() : nullptr;
+    a.nrm_n = normalised && h->have_nnorm ? nrm : nullptr;
+    a.nrm_o = normalised && h->have_onorm ? nrm + 2 * c.Fn + 2 * c.Fe : nullptr;
+    a.N = N; a.O = c.O; a.Fn = c.Fn; a.ld = c.Fn; a.t = t;
+    a.delta = R.delta[(size_t)t];
+    a.seed = R.seed;
+    return a;
+}
+// The normaliser call of the reference accumulates, then normalises: an accumulating step adds the datapoint's raw rows (cur, ef_raw, d)
+// to the totals of every online group that still accumulates and rewrites that group's entries of h->norms, all on the device; restored
+// totals (mgn_train_norm_state) get their maps here as well.  No copy to the host, no synchronisation; count and calls are host numbers.
+int datapoint_norms(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
+    if (int rc = datapoint_norms_ready(h)) return rc;
+    TrainState& T = *h->train;
+    TrainState::Trajectory& R = T.traj;
+    const mgn_config& c = h->cfg;
+    const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    bool add[3], write[3], any = false;
+    for (int g = 0; g < 3; ++g) {
+        const int64_t rows = g == 1 ? E : N;
+        add[g] = accumulate && T.on[g].online && T.on[g].calls < T.on[g].max_acc && rows > 0;
+        write[g] = T.on[g].online && (add[g] || T.on[g].dirty);
+        any = any || write[g];
+    }
+    if (!any) return MGN_OK;
+    if (int rc = online_totals_ready(h)) return rc;
+    const int nb = stats_blocks(N);
+    const double *p0 = nullptr, *p2 = nullptr;
+    if (add[0] || add[2]) {
+        const size_t rawf = ((size_t)N * c.O + 63) / 64 * 64, partd = (size_t)nb * 2 * c.O;
+        HIPCHK(h, R.work.ensure(2 * rawf * 4 + 2 * partd * sizeof(double)));
+        float* rcur = R.work.as<float>();
+        float* rd = rcur + rawf;
+        double* part = reinterpret_cast<double*>(rd + rawf);
+        DatapointArgs a = datapoint_args(h, t, false);
+        a.ld = c.O; a.raw_cur = rcur; a.raw_d = rd;
+        HIPCHK(h, launch_datapoint_assemble(a, st));
+        if (add[0]) { HIPCHK(h, launch_col_stats(rcur, N, c.O, part, st)); p0 = part; }
+        if (add[2]) { HIPCHK(h, launch_col_stats(rd, N, c.O, part + partd, st)); p2 = part + partd; }
+    }
+    if (add[1] && !R.ef_sums_ok) {     // what one accumulation of ef_raw adds: the same terms in the same order, formed once per trajectory
+        const int nbe = stats_blocks(E);
+        const size_t head = (size_t)2 * c.Fe * sizeof(double);
+        HIPCHK(h, R.ef_sums.ensure(head + (size_t)nbe * head));
+        double* sums = R.ef_sums.as<double>();
+        HIPCHK(h, hipMemsetAsync(sums, 0, head, st));
+        HIPCHK(h, launch_col_stats(R.ef_raw.as<float>(), E, c.Fe, sums + 2 * c.Fe, st));
+        NormsFromTotalsArgs z{};
+        z.g[0].partial = sums + 2 * c.Fe; z.g[0].totals = sums; z.g[0].nb = nbe; z.g[0].dim = c.Fe; z.g[0].add = 1;
+        HIPCHK(h, launch_norms_from_totals(z, st));
+        R.ef_sums_ok = true;
+    }
+    float* nrm = h->norms.as<float>();
+    float* scale[3] = {nrm, nrm + 2 * c.Fn, nrm + 2 * c.Fn + 2 * c.Fe};
+    const int stride[3] = {c.Fn, c.Fe, c.O};
+    NormsFromTotalsArgs a{};
+    for (int g = 0; g < 3; ++g) {
+        if (!write[g]) continue;
+        TrainState::OnlineGroup& o = T.on[g];
+        if (add[g]) { o.count += (double)(g == 1 ? E : N); o.calls += 1.0; }
+        NormGroupArgs& q = a.g[g];
+        q.partial = g == 0 ? p0 : (g == 2 ? p2 : nullptr);
+        q.call_sums = g == 1 ? R.ef_sums.as<double>() : nullptr;
+        q.totals = T.on_totals.as<double>() + online_off(c, g);
+        q.scale = scale[g]; q.shift = scale[g] + stride[g];
+        q.count = o.count; q.eps = o.eps; q.nb = nb; q.dim = online_dim(c, g);
+        q.add = add[g] ? 1 : 0; q.write = 1; q.inverse = g == 2 ? 1 : 0;
+        o.dirty = false;
+    }
+    HIPCHK(h, launch_norms_from_totals(a, st));
+    h->norms_host_stale = true;        // (its two readers refresh it: sync_norms_host)
+    invalidate_static(h);              // as mgn_set_norms does
+    if (write[1]) R.ef_pad_ok = false;
+    return MGN_OK;
+}
+int datapoint_stage(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
+    if (int rc = datapoint_norms(h, t, accumulate, st)) return rc;
+    TrainState& T = *h->train;
+    TrainState::Trajectory& R = T.traj;
+    const mgn_config& c = h->cfg;
+    float* A = T.arena.as<float>();
+    DatapointArgs a = datapoint_args(h, t, true);
+    a.nf = A + T.nf_pad; a.ld = c.L; a.target = T.target.as<float>();
+    HIPCHK(h, launch_datapoint_assemble(a, st));
+    const int64_t E = h->g.set[0].e_local;
+    if (!R.ef_pad_ok && E > 0) {       // a constant of the trajectory: rebuilt when the trajectory, the norms or the arena changed
+        const float* es = h->have_enorm ? h->norms.as<float>() + 2 * c.Fn : nullptr;
+        HIPCHK(h, launch_affine_pad(R.ef_raw.as<float>(), c.Fe, nullptr, 0, es, es ? es + c.Fe : nullptr, A + T.ef_pad[0], c.L, E, st));
+    }
+    R.ef_pad_ok = true;
+    return MGN_OK;
+}
+// what every entry point of the datapoint family asks of the handle before it looks at its arguments
+int datapoint_need(mgn_handle* h, const char* who, bool graph, bool trajectory) {
+    if (int rc = need(h, false, graph)) return rc;
+    if (h->cfg.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (h->cfg.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
+    if (trajectory && (!h->train || !h->train->traj.have))
+        return fail(h, MGN_E_STATE, "%s: no trajectory: call mgn_train_set_trajectory after mgn_set_graph (a new graph drops it)", who);
+    if (!h->train) h->train = new (std::nothrow) TrainState();
+    if (!h->train) return fail(h, MGN_E_OOM, "host allocation failed");
     return MGN_OK;
 }
 
@@ -682,7 +864,7 @@ struct TrainPass {
         static const int group_env = [] { const char* e = getenv("MGN_TRAIN_WG_GROUP"); return e ? atoi(e) : 1; }();
         if (overlap) group = std::max(1, std::min(group_env, T.gsets / 2));
     }
-    bool vjp() const { return J.kind != JOB_STEP; }
+    bool vjp() const { return J.kind != JOB_STEP && J.kind != JOB_DATAPOINT; }
     float* io() const { return A + T.io; }    // the VJPs' rows: x [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N]
     int comm_fail(const char* what) { return fail(h, MGN_E_RCCL, "mgn_step: %s: %s", what, h->comm->err.c_str()); }
 
@@ -711,6 +893,7 @@ struct TrainPass {
     // step! and the model's VJP: the FeatureGraph's node and edge features as given
     int stage_features() {
         const float* src = nullptr;
+        T.traj.ef_pad_ok = false;
         HIPCHK(h, staged(J.nf, A + T.nf_raw, (size_t)NG * c.Fn, src));
         HIPCHK(h, launch_affine_pad_gather(src, c.Fn, nullptr, 0, nullptr, nullptr, renum ? ngid : nullptr, A + T.nf_pad, L, N, st));
         if (part && g.set[0].E > 0) {      // the local edges' rows of the global array, in the engine's order
@@ -731,6 +914,9 @@ struct TrainPass {
         } else {
             HIPCHK(h, hipMemcpyAsync(T.target.p, J.target, (size_t)N * O * 4, hipMemcpyDefault, st));
         }
+        return stage_mask();
+    }
+    int stage_mask() {
         // the mask of the previous call is usually this call's (one trajectory, one mask: reference src/MeshGraphNets.jl:352): uploaded once
         const bool mask_dev = on_device(J.mask);
         const bool same = !mask_dev && T.mask_valid && T.mask_base == J.mask_index_base && (int64_t)T.mask_seen.size() == J.nmask &&
@@ -789,6 +975,7 @@ struct TrainPass {
             HIPCHK(h, to_local(io() + (size_t)N * (O + c.Fn), 1));
         }
         if (x) if (int rc = pad_state(x)) return rc;
+        T.traj.ef_pad_ok = false;
         if (sx[0].E > 0) {
             HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], J.ef, (size_t)sx[0].E * c.Fe * 4, hipMemcpyDefault, st));
             HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
@@ -811,6 +998,11 @@ struct TrainPass {
             case JOB_RHS_VJP: rc = stage_rhs_vjp(); break;
             // the state this step's RHS saw; one-hot node types, val_mask and the normalised edge features were staged once for the sweep
             case JOB_SWEEP_STEP: rc = pad_state(J.x); break;
+            // nf_pad, target and (when stale) ef_pad from the resident trajectory: no host array, no gather
+            case JOB_DATAPOINT:
+                rc = datapoint_stage(h, J.datapoint, J.accumulate, st);
+                if (!rc) rc = stage_mask();
+                break;
         }
         if (rc) return rc;
         // further edge sets: the features installed by mgn_set_edge_features, as given (the forward path does not normalise them either)
@@ -1129,7 +1321,7 @@ struct TrainPass {
         if (part) return finish_partition();
         std::vector<double> lp((size_t)nlb);
         HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
-        if (J.kind == JOB_STEP) {
+        if (!vjp()) {
             HIPCHK(h, hipMemcpyAsync(lp.data(), T.loss.p, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         } else if (J.kind == JOB_FORWARD_VJP) {
             HIPCHK(h, launch_extract_cols(A + T.gNF, L, c.Fn, nullptr, io(), N, st));
@@ -1142,7 +1334,7 @@ struct TrainPass {
             if (J.dxdt) if (int rc = give(T.target.as<float>(), O, J.dxdt)) return rc;
         }
         HIPCHK(h, hipStreamSynchronize(st));
-        if (J.kind == JOB_STEP) {
+        if (!vjp()) {
             double s = 0.0;
             for (double v : lp) s += v;
             *J.loss = (float)(s / (double)J.nmask);
@@ -1308,6 +1500,180 @@ extern "C" int mgn_step(mgn_handle* h, const float* nf, const float* ef, const f
     J.nf = nf; J.ef = ef; J.target = target; J.mask = mask; J.nmask = nmask; J.mask_index_base = mask_index_base;
     J.loss = loss; J.grads = grads;
     return train_run(h, J);
+} MGN_CATCH(h)
+
+// ---- Derivative training on a resident trajectory (reference src/MeshGraphNets.jl:364-378 over src/strategies.jl:395-416) ----
+extern "C" int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int32_t T_, const float* times, float dt,
+                                        const float* node_type_onehot, const float* ef_raw) try {
+    const char* who = "mgn_train_set_trajectory";
+    if (!h) return MGN_E_ARG;
+    if (int rc = datapoint_need(h, who, true, false)) return rc;
+    const mgn_config& c = h->cfg;
+    const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    if (!frames) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (T_ < 2) return fail(h, MGN_E_ARG, "%s: a trajectory has at least two frames, got %d", who, (int)T_);
+    if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
+    if ((c.Fn > c.O && !node_type_onehot) || (!ef_raw && E > 0)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    std::vector<float> delta((size_t)T_ - 1, dt);
+    if (times) {
+        std::vector<float> tm((size_t)T_);
+        HIPCHK(h, hipMemcpy(tm.data(), times, (size_t)T_ * 4, hipMemcpyDefault));
+        for (int32_t t = 0; t + 1 < T_; ++t) delta[(size_t)t] = tm[(size_t)t + 1] - tm[(size_t)t];
+    }
+    for (int32_t t = 0; t + 1 < T_; ++t)
+        if (!(delta[(size_t)t] != 0.f)) return fail(h, MGN_E_ARG, "%s: the time step of datapoint %d is zero (or not a number)", who, (int)t);
+    TrainState::Trajectory& R = h->train->traj;
+    R.have = false; R.ef_pad_ok = false; R.ef_sums_ok = false;
+    const hipStream_t st = h->stream;
+    const size_t fl = (size_t)T_ * (size_t)N * c.O, ol = (size_t)N * (c.Fn - c.O), el = (size_t)E * c.Fe;
+    HIPCHK(h, R.frames.ensure(fl * 4));
+    HIPCHK(h, R.onehot.ensure(ol * 4));
+    HIPCHK(h, R.ef_raw.ensure(el * 4));
+    if (h->g.renumbered) {             // into the engine's node order once, here: no gather per step
+        const int32_t* gid = h->d_own_gid.as<int32_t>();
+        HIPCHK(h, h->stage.ensure(std::max(fl, ol) * 4));
+        HIPCHK(h, hipMemcpyAsync(h->stage.p, frames, fl * 4, hipMemcpyDefault, st));
+        HIPCHK(h, launch_shoot_gather(R.frames.as<float>(), h->stage.as<float>(), (int64_t)fl, N * c.O, T_, nullptr, gid, c.O, st));
+        if (ol) {
+            HIPCHK(h, hipMemcpyAsync(h->stage.p, node_type_onehot, ol * 4, hipMemcpyDefault, st));
+            HIPCHK(h, launch_permute_rows(R.onehot.as<float>(), h->stage.as<float>(), gid, N, c.Fn - c.O, false, st));
+        }
+    } else {
+        HIPCHK(h, hipMemcpyAsync(R.frames.p, frames, fl * 4, hipMemcpyDefault, st));
+        if (ol) HIPCHK(h, hipMemcpyAsync(R.onehot.p, node_type_onehot, ol * 4, hipMemcpyDefault, st));
+    }
+    if (el) HIPCHK(h, hipMemcpyAsync(R.ef_raw.p, ef_raw, el * 4, hipMemcpyDefault, st));   // (edge rows stay in the caller's order: the edge encoder reads them by edge_gid)
+    HIPCHK(h, hipStreamSynchronize(st));
+    R.T = T_;
+    R.delta = std::move(delta);
+    R.have = true;
+    return MGN_OK;
+} MGN_CATCH(h)
+
+extern "C" int mgn_train_set_noise(mgn_handle* h, const float* stddev, const uint8_t* noisy, uint64_t seed) try {
+    const char* who = "mgn_train_set_noise";
+    if (!h) return MGN_E_ARG;
+    if (int rc = datapoint_need(h, who, true, false)) return rc;
+    TrainState::Trajectory& R = h->train->traj;
+    const int64_t N = h->g.n_own;
+    R.seed = seed;
+    R.noise = false; R.some_nodes = false;
+    if (!stddev) return MGN_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, R.stddev.ensure((size_t)h->cfg.O * 4));
+    HIPCHK(h, hipMemcpy(R.stddev.p, stddev, (size_t)h->cfg.O * 4, hipMemcpyDefault));
+    if (noisy) {
+        std::vector<uint8_t> in((size_t)N), loc((size_t)N);
+        HIPCHK(h, hipMemcpy(in.data(), noisy, (size_t)N, hipMemcpyDefault));
+        for (int64_t i = 0; i < N; ++i) loc[(size_t)i] = in[(size_t)(h->g.renumbered ? h->g.own_gid[(size_t)i] : i)] ? 1 : 0;
+        HIPCHK(h, R.noisy.ensure((size_t)N));
+        HIPCHK(h, hipMemcpy(R.noisy.p, loc.data(), (size_t)N, hipMemcpyHostToDevice));
+        R.some_nodes = true;
+    }
+    R.noise = true;
+    return MGN_OK;
+} MGN_CATCH(h)
+
+extern "C" int mgn_train_online_norms(mgn_handle* h, int32_t node_on, int32_t edge_on, int32_t out_on, double max_accumulations,
+                                      float std_epsilon) try {
+    const char* who = "mgn_train_online_norms";
+    if (!h) return MGN_E_ARG;
+    if (int rc = datapoint_need(h, who, false, false)) return rc;
+    if (!(max_accumulations > 0.0) || !(std_epsilon > 0.f)) return fail(h, MGN_E_ARG, "%s: max_accumulations and std_epsilon must be positive", who);
+    if (int rc = online_totals_ready(h)) return rc;
+    if (int rc = datapoint_norms_ready(h)) return rc;
+    TrainState& T = *h->train;
+    const int32_t on[3] = {node_on, edge_on, out_on};
+    for (int g = 0; g < 3; ++g) {
+        TrainState::OnlineGroup& o = T.on[g];
+        if (!on[g]) { o.online = false; o.dirty = false; continue; }      // (its entries of h->norms stay as they are)
+        o = TrainState::OnlineGroup();
+        o.online = true; o.max_acc = max_accumulations; o.eps = std_epsilon;
+        HIPCHK(h, hipMemsetAsync(T.on_totals.as<double>() + online_off(h->cfg, g), 0, (size_t)2 * online_dim(h->cfg, g) * sizeof(double), h->stream));
+    }
+    return datapoint_norms_ready(h);
+} MGN_CATCH(h)
+
+extern "C" int mgn_train_norm_state(mgn_handle* h, int32_t group, int32_t write, double* sum, double* sum_squares, double* count_and_calls) try {
+    const char* who = "mgn_train_norm_state";
+    if (!h) return MGN_E_ARG;
+    if (int rc = datapoint_need(h, who, false, false)) return rc;
+    if (group < 0 || group > 2) return fail(h, MGN_E_ARG, "%s: group %d (0 node state columns, 1 edge, 2 output)", who, (int)group);
+    if (!sum || !sum_squares || !count_and_calls) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (int rc = online_totals_ready(h)) return rc;
+    TrainState::OnlineGroup& o = h->train->on[group];
+    const int dim = online_dim(h->cfg, group);
+    double* tot = h->train->on_totals.as<double>() + online_off(h->cfg, group);
+    const hipStream_t st = h->stream;
+    if (write) {
+        if (!(count_and_calls[0] >= 0.0) || !(count_and_calls[1] >= 0.0)) return fail(h, MGN_E_ARG, "%s: negative count", who);
+        HIPCHK(h, hipMemcpyAsync(tot, sum, (size_t)dim * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(tot + dim, sum_squares, (size_t)dim * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        o.count = count_and_calls[0]; o.calls = count_and_calls[1];
+        o.dirty = true;
+    } else {
+        HIPCHK(h, hipMemcpyAsync(sum, tot, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(sum_squares, tot + dim, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        count_and_calls[0] = o.count; count_and_calls[1] = o.calls;
+    }
+    return MGN_OK;
+} MGN_CATCH(h)
+
+extern "C" int mgn_step_datapoint(mgn_handle* h, int32_t datapoint, int32_t accumulate, const int32_t* mask, int64_t nmask,
+                                  int32_t mask_index_base, float* grads, size_t n_grads, float* loss) try {
+    const char* who = "mgn_step_datapoint";
+    if (!h) return MGN_E_ARG;
+    if (!mask || !grads || !loss) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (int rc = datapoint_need(h, who, true, true)) return rc;
+    if (datapoint < 0 || datapoint > h->train->traj.T - 2)
+        return fail(h, MGN_E_ARG, "%s: datapoint %d outside [0, %d]", who, (int)datapoint, (int)h->train->traj.T - 2);
+    if (nmask < 1) return fail(h, MGN_E_ARG, "%s: empty mask", who);
+    if (mask_index_base != 0 && mask_index_base != 1) return fail(h, MGN_E_ARG, "%s: mask_index_base must be 0 or 1", who);
+    for (int64_t i = 0; i < nmask; ++i) {
+        const int64_t n = (int64_t)mask[i] - mask_index_base;
+        if (n < 0 || n >= h->g.n_own) return fail(h, MGN_E_ARG, "%s: mask entry %lld out of range", who, (long long)i);
+    }
+    if (int rc = train_prepare(h, who, n_grads)) return rc;
+    TrainJob J;
+    J.kind = JOB_DATAPOINT;
+    J.datapoint = datapoint; J.accumulate = accumulate != 0;
+    J.mask = mask; J.nmask = nmask; J.mask_index_base = mask_index_base;
+    J.loss = loss; J.grads = grads;
+    return train_run(h, J);
+} MGN_CATCH(h)
+
+extern "C" int mgn_datapoint_export(mgn_handle* h, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target) try {
+    const char* who = "mgn_datapoint_export";
+    if (!h) return MGN_E_ARG;
+    if (int rc = datapoint_need(h, who, true, true)) return rc;
+    TrainState::Trajectory& R = h->train->traj;
+    if (datapoint < 0 || datapoint > R.T - 2) return fail(h, MGN_E_ARG, "%s: datapoint %d outside [0, %d]", who, (int)datapoint, (int)R.T - 2);
+    const mgn_config& c = h->cfg;
+    const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    const hipStream_t st = h->stream;
+    if (int rc = normalised ? datapoint_norms(h, datapoint, false, st) : datapoint_norms_ready(h)) return rc;
+    const size_t nfl = ((size_t)N * c.Fn + 63) / 64 * 64, tl = ((size_t)N * c.O + 63) / 64 * 64, el = (size_t)E * c.Fe;
+    HIPCHK(h, h->stage.ensure((nfl + tl + el) * 4));
+    float* snf = h->stage.as<float>();
+    float* stg = snf + nfl;
+    float* sef = stg + tl;
+    if (nf || target) {
+        DatapointArgs a = datapoint_args(h, datapoint, normalised != 0);
+        a.nf = nf ? snf : nullptr; a.target = target ? stg : nullptr; a.scatter = 1;
+        if (!nf) a.ld = c.O;
+        HIPCHK(h, launch_datapoint_assemble(a, st));
+        if (nf) HIPCHK(h, hipMemcpyAsync(nf, snf, (size_t)N * c.Fn * 4, hipMemcpyDefault, st));
+        if (target) HIPCHK(h, hipMemcpyAsync(target, stg, (size_t)N * c.O * 4, hipMemcpyDefault, st));
+    }
+    if (ef && el) {
+        const float* es = normalised && h->have_enorm ? h->norms.as<float>() + 2 * c.Fn : nullptr;
+        HIPCHK(h, launch_affine_pad(R.ef_raw.as<float>(), c.Fe, nullptr, 0, es, es ? es + c.Fe : nullptr, sef, c.Fe, E, st));
+        HIPCHK(h, hipMemcpyAsync(ef, sef, el * 4, hipMemcpyDefault, st));
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    return MGN_OK;
 } MGN_CATCH(h)
 
 extern "C" int mgn_ode_vjp(mgn_handle* h, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask,

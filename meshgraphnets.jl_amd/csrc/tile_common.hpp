@@ -5,6 +5,21 @@
 
 namespace mgn {
 
+// The engine's N(0,1) generator: splitmix64 of (seed, key), Box-Muller on two 24-bit uniforms.  key = row * width + column of the array
+// the value belongs to, rows by the CALLER's ids: the same value whatever the partition or the engine's numbering.
+DEVINL uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+DEVINL float randn_keyed(uint64_t seed, uint64_t key) {
+    const uint64_t bits = splitmix64(seed ^ splitmix64(key));
+    const float u1 = ((float)(uint32_t)(bits >> 40) + 1.0f) * (1.0f / 16777216.0f);  // (0,1]
+    const float u2 = (float)(uint32_t)((bits >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+
 #define MGN_FAST_PRELOAD_TILES 8192     // node-side launches of up to 4 tiles per wave copy their weights with eight loads in flight
 
 // Waves w and w+4 of a block share a SIMD and run the same program; started together they stay in

@@ -160,6 +160,34 @@ hipError_t launch_extract_cols(const float* src, int L, int O, const float* scal
 constexpr int STATS_ROWS = 2048;
 int stats_blocks(int64_t rows);
 hipError_t launch_col_stats(const float* x, int64_t rows, int dim, double* partial, hipStream_t s);
+// mgn_step_datapoint (reference src/strategies.jl:395-416, init_train_step of the derivative strategies): datapoint t of a resident
+// trajectory, rows in the engine's order (gid[r]: the caller's id of row r, null: r).  Per state column o < O of row r:
+//   cur = frame_t + stddev[o] z(seed, t, gid[r], o) where noisy[r] (stddev null: no noise; noisy null: every row); z: the generator of
+//         k_randn_rows on the trajectory as a [T N][O] array;   d = (frame_{t+1} - cur) / delta;   target = (d - osh) / os
+//   (nrm_o = [os | osh], null: target = d), IEEE fp32 operations one by one.
+//   nf [N][ld] = [ [cur | onehot] * scale + shift | 0 ]  (nrm_n = [scale | shift] over Fn columns, null: as they are; k_affine_pad's expression)
+// scatter: rows of nf / target go to gid[r] (the caller's order: exports).  raw_cur / raw_d [N][O] (null: not written): cur and d in
+// the CALLER's order, what the online normalisers accumulate.  nf / target may be null.
+struct DatapointArgs {
+    const float* cur; const float* nxt; const float* onehot;
+    const int32_t* gid; const uint8_t* noisy; const float* stddev;
+    const float* nrm_n; const float* nrm_o;
+    float* nf; float* target; float* raw_cur; float* raw_d;
+    int64_t N; int32_t O, Fn, ld, t, scatter;
+    float delta; uint64_t seed;
+};
+hipError_t launch_datapoint_assemble(const DatapointArgs& a, hipStream_t s);
+// The online normalisers' maps from device-resident double totals [sum (dim) | sum of squares (dim)], one group each for the node state
+// columns, the edge features and the output.  add: totals += this call's sums first -- `partial` (launch_col_stats' nb blocks, added in
+// block order from zero: mgn_feature_stats' result) or, partial null, call_sums [2][dim] formed that way earlier.  write: scale / shift
+// from the totals over `count` rows: mean and std in double, rounded to float, std = max(std, eps); scale = 1 / std, shift = -mean scale,
+// or with `inverse` scale = std, shift = mean.  dim = 0: nothing.
+struct NormGroupArgs {
+    const double* partial; const double* call_sums; double* totals; float* scale; float* shift;
+    double count; float eps; int32_t nb, dim, add, write, inverse;
+};
+struct NormsFromTotalsArgs { NormGroupArgs g[3]; };
+hipError_t launch_norms_from_totals(const NormsFromTotalsArgs& a, hipStream_t s);
 // masked MSE: loss_partial[b] = sum over this block's mask entries of sum_o (out - target)^2;
 // G[n][o] += 2 (out[n][o] - target[n][o]) / divisor   (G [N][L] zeroed by the caller; out = first O columns of Y; divisor = nmask, or on
 // a partition, which lists only the entries it owns, the length of the whole mask)

@@ -1485,6 +1485,93 @@ __global__ __launch_bounds__(256) void k_col_stats(const float* __restrict__ x, 
     }
 }
 
+// ---- mgn_step_datapoint: one datapoint of a device-resident trajectory (reference src/strategies.jl:395-416) ----
+// One thread per four consecutive columns of a destination row of nf (an f32x4 store where ld is a multiple of four).  The thread
+// that holds state column o < O forms that element's cur, d and target as well, so every element is computed exactly once.
+__global__ __launch_bounds__(256) void k_datapoint_assemble(const DatapointArgs a) {
+    const int quads = (a.ld + 3) >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N * quads) return;
+    const int64_t r = i / quads;
+    const int q = (int)(i - r * quads);
+    const int O = a.O, W1 = a.Fn - a.O;
+    const int64_t node = a.gid ? (int64_t)a.gid[r] : r;        // the caller's id of engine row r
+    const int64_t ro = a.scatter ? node : r;                   // the row the results go to
+    const bool noisy = a.stddev && (!a.noisy || a.noisy[r] != 0);
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int f = 4 * q + j;
+        float x = 0.f;
+        if (f < O) {
+            const float clean = a.cur[r * O + f];
+            float cur = clean;
+            if (noisy) cur = __fadd_rn(clean, __fmul_rn(a.stddev[f], randn_keyed(a.seed, ((uint64_t)a.t * (uint64_t)a.N + (uint64_t)node) * (uint64_t)O + (uint64_t)f)));
+            const float d = __fdiv_rn(__fsub_rn(a.nxt[r * O + f], cur), a.delta);
+            if (a.target) a.target[ro * O + f] = a.nrm_o ? __fdiv_rn(__fsub_rn(d, a.nrm_o[O + f]), a.nrm_o[f]) : d;
+            if (a.raw_cur) { a.raw_cur[node * O + f] = cur; a.raw_d[node * O + f] = d; }
+            x = cur;
+        } else if (f < a.Fn) {
+            x = a.onehot[r * W1 + (f - O)];
+        }
+        if (f < a.Fn && a.nrm_n) x = x * a.nrm_n[f] + a.nrm_n[a.Fn + f];      // the expression of k_affine_pad
+        v[j] = x;
+    }
+    if (!a.nf) return;
+    float* dst = a.nf + ro * a.ld + 4 * q;
+    if ((a.ld & 3) == 0) {
+        *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * q + j < a.ld) dst[j] = v[j];
+    }
+}
+
+// One block.  Per group (node state columns, edge, output) and column: totals += this call's sums -- the block partials of k_col_stats
+// added in block order from 0, as mgn_feature_stats adds them on the host, or sums formed that way before -- and the group's affine map
+// from the totals: mean, std = sqrt(max(sumsq / c - mean^2, 0)) in double, rounded to float, std = max(std, eps);
+// forward map scale = 1 / std, shift = -mean scale; the output group keeps the inverse map std, mean (mgn_set_norms: out_scale, out_shift).
+__global__ __launch_bounds__(256) void k_norms_from_totals(const NormsFromTotalsArgs a) {
+    for (int gi = 0; gi < 3; ++gi) {
+        const NormGroupArgs& g = a.g[gi];
+        for (int f = threadIdx.x; f < g.dim; f += blockDim.x) {
+            double s = g.totals[f], q = g.totals[g.dim + f];
+            if (g.add) {
+                double cs = 0.0, cq = 0.0;
+                if (g.partial) {
+                    for (int b = 0; b < g.nb; ++b) {
+                        cs += g.partial[((size_t)b * 2 + 0) * g.dim + f];
+                        cq += g.partial[((size_t)b * 2 + 1) * g.dim + f];
+                    }
+                } else {
+                    cs = g.call_sums[f];
+                    cq = g.call_sums[g.dim + f];
+                }
+                s += cs;
+                q += cq;
+                g.totals[f] = s;
+                g.totals[g.dim + f] = q;
+            }
+            if (!g.write) continue;
+            const double c = g.count > 1.0 ? g.count : 1.0;
+            const double mean_d = s / c;
+            const double var_d = __dsub_rn(q / c, __dmul_rn(mean_d, mean_d));      // (no contraction: the host's two roundings)
+            const float mean = (float)mean_d;
+            float sd = (float)sqrt(var_d > 0.0 ? var_d : 0.0);
+            sd = fmaxf(fmaxf(sd, g.eps), 1e-8f);
+            if (g.inverse) {
+                g.scale[f] = sd;
+                g.shift[f] = mean;
+            } else {
+                const float sc = __fdiv_rn(1.0f, sd);
+                g.scale[f] = sc;
+                g.shift[f] = __fmul_rn(-mean, sc);
+            }
+        }
+    }
+}
+
 // ================================================================================================
 // launch wrappers
 // ================================================================================================
@@ -1969,6 +2056,19 @@ hipError_t launch_col_stats(const float* x, int64_t rows, int dim, double* parti
     const int nb = stats_blocks(rows);
     if (nb == 0 || dim <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_col_stats, dim3(nb), dim3(256), 0, s, x, rows, dim, partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_datapoint_assemble(const DatapointArgs& a, hipStream_t s) {
+    const int64_t tot = a.N * ((a.ld + 3) / 4);
+    if (tot <= 0) return hipSuccess;
+    if ((a.nf && a.ld < a.Fn) || a.ld < a.O || a.Fn < a.O || (a.Fn > a.O && !a.onehot) || !a.cur || !a.nxt || (a.raw_cur && !a.raw_d)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_datapoint_assemble, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_norms_from_totals(const NormsFromTotalsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_norms_from_totals, dim3(1), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

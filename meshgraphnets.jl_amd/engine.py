@@ -546,6 +546,92 @@ class Engine:
                                     C.byref(loss)))
         return gs, loss.value
 
+    # -- derivative training on a device-resident trajectory (mgn_train_* / mgn_step_datapoint) --------
+    def set_trajectory(self, frames, dt=None, times=None, node_type_onehot=None, ef_raw=None):
+        """Once per trajectory, after the graph is complete (add_targets! / preprocess!, reference src/dataset.jl:461-509):
+        frames [T][N][O] (the target fields of every frame, concatenated in output order; the last frame is only ever a target),
+        the time step as the scalar `dt` or as `times` [T], node_type_onehot [N][Fn-O], ef_raw [E][Fe].  NumPy arrays or
+        contiguous fp32 device tensors, in the caller's node / edge order.  A new graph drops the trajectory, set_params and
+        set_norms do not."""
+        O, Fn = self.cfg.O, self.cfg.Fn
+        shape = tuple(frames.shape)
+        if len(shape) != 3 or shape[1:] != (self.N, O):
+            raise ValueError(f"DimensionMismatch: frames must be [T][{self.N}][{O}], got {shape}")
+        if (dt is None) == (times is None):
+            raise ValueError("give either dt or times")
+        frames, p_fr = _host_or_device(frames, shape)
+        tm = _c32(times, (shape[0],)) if times is not None else None
+        oh, p_oh = _host_or_device(node_type_onehot, (self.N, Fn - O)) if node_type_onehot is not None else (None, None)
+        ef, p_ef = _host_or_device(ef_raw, (self.E, self.cfg.Fe)) if ef_raw is not None else (None, None)
+        self._chk(self.lib.mgn_train_set_trajectory(self.h, p_fr, shape[0], f32(tm), 0.0 if dt is None else float(dt), p_oh, p_ef))
+        self.T = shape[0]
+
+    def set_noise(self, stddev=None, noisy_nodes=None, seed=0):
+        """Noise of the input state (preprocess!, reference src/dataset.jl:496-509): stddev [O] (None: no noise), noisy_nodes [N]
+        0/1 or bool in the caller's node order (None: every node), seed.  N(0,1) keyed by (seed, datapoint, caller's node id,
+        column): independent of the engine's numbering.  The next state inside the target carries no noise."""
+        sd = _c32(stddev, (self.cfg.O,)) if stddev is not None else None
+        nz = None
+        if noisy_nodes is not None:
+            nz = np.ascontiguousarray(np.asarray(noisy_nodes).reshape(-1) != 0, dtype=np.uint8)
+            if nz.shape != (self.N,):
+                raise ValueError(f"DimensionMismatch: noisy_nodes must be [{self.N}]")
+        self._chk(self.lib.mgn_train_set_noise(self.h, f32(sd), nz.ctypes.data_as(C.POINTER(C.c_uint8)) if nz is not None else None,
+                                               int(seed)))
+
+    def online_norms(self, node=True, edge=True, out=True, max_acc=1e6, std_epsilon=1e-8):
+        """Switch the chosen groups (node state columns, edge features, output) to NormaliserOnline and zero their totals; a
+        group left off keeps what set_norms gave it.  The one-hot columns are never online."""
+        self._chk(self.lib.mgn_train_online_norms(self.h, int(bool(node)), int(bool(edge)), int(bool(out)), float(max_acc),
+                                                  float(std_epsilon)))
+
+    def _norm_dim(self, group):
+        if group not in (0, 1, 2):
+            return 1                   # (the library refuses the group)
+        return self.cfg.Fe if group == 1 else self.cfg.O
+
+    def norm_state(self, group):
+        """(sum, sum_squares, count, calls) of an online group (0 node state columns, 1 edge, 2 output): float64 totals as they
+        stand on the device -- what save! writes of a NormaliserOnline."""
+        dim = self._norm_dim(group)
+        s, q, cc = np.zeros(dim, np.float64), np.zeros(dim, np.float64), np.zeros(2, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.mgn_train_norm_state(self.h, int(group), 0, s.ctypes.data_as(dp), q.ctypes.data_as(dp), cc.ctypes.data_as(dp)))
+        return s, q, float(cc[0]), float(cc[1])
+
+    def set_norm_state(self, group, sum, sum_squares, count, calls):
+        """Restore an online group's totals (load): its affine map follows at the next datapoint."""
+        dim = self._norm_dim(group)
+        s = np.ascontiguousarray(sum, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(sum_squares, dtype=np.float64).reshape(-1)
+        if s.shape != (dim,) or q.shape != (dim,):
+            raise ValueError(f"DimensionMismatch: expected ({dim},) totals")
+        cc = np.array([count, calls], np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.mgn_train_norm_state(self.h, int(group), 1, s.ctypes.data_as(dp), q.ctypes.data_as(dp), cc.ctypes.data_as(dp)))
+
+    def step_datapoint(self, t, mask, mask_index_base=0, accumulate=False, out=None):
+        """init_train_step + step! of the derivative strategies (reference src/strategies.jl:395-422) on datapoint t (0-based,
+        < T-1) of the resident trajectory: returns (gs, loss) like step().  accumulate: the online groups take this datapoint's
+        raw rows into their totals and renew their maps first, on the device.  `out` as in step()."""
+        mask = np.ascontiguousarray(mask, dtype=np.int32).ravel()
+        if out is None:
+            out = np.zeros(self.param_count, np.float32)
+        gs, p_gs = _host_or_device(out, (self.param_count,), writable=True)
+        loss = C.c_float()
+        self._chk(self.lib.mgn_step_datapoint(self.h, int(t), int(bool(accumulate)), i32(mask), mask.size, mask_index_base, p_gs,
+                                              self.param_count, C.byref(loss)))
+        return gs, loss.value
+
+    def datapoint_export(self, t, normalised=True):
+        """(nf [N][Fn], ef [E][Fe], target [N][O]) of datapoint t in the caller's order: what step_datapoint consumes
+        (normalised) or the raw [cur ; onehot], ef_raw and d = (next - cur) / dt.  Never accumulates."""
+        nf = np.zeros((self.N, self.cfg.Fn), np.float32)
+        ef = np.zeros((self.E, self.cfg.Fe), np.float32)
+        tg = np.zeros((self.N, self.cfg.O), np.float32)
+        self._chk(self.lib.mgn_datapoint_export(self.h, int(t), int(bool(normalised)), f32(nf), f32(ef), f32(tg)))
+        return nf, ef, tg
+
     def feature_stats(self, x):
         """Per-feature (sum, sum of squares) of x [rows][dim] in float64 on the device: one NormaliserOnline accumulation
         (GraphNetCore; normalisers of reference src/MeshGraphNets.jl:92,193-199).  x: NumPy array or device tensor."""

@@ -11,6 +11,7 @@ functions are written here in NumPy float32 to drive the engine exactly the way 
     rollout (Euler branch) reference src/solve.jl:42-68  (`solve(prob, solver; adaptive=false, dt, saveat)`)
     train_step (solver strategies with Euler() / Tsit5())  reference src/strategies.jl:175-196, 238-383 (Engine.solver_grad /
                            Engine.solver_grad_tsit5 per solved window)
+    init_train_step_derivative  reference src/strategies.jl:395-416 (Engine.step_datapoint is its device form plus step!)
     validation_step, rollout_errors  reference src/strategies.jl:111-134, src/MeshGraphNets.jl:609-628 (Engine.rollout_eval)
     GraphNetCore surface   one_hot, triangles_to_edges, parse_edges, mse_reduce, NormaliserOfflineMinMax,
                            NormaliserOfflineMeanStd, NormaliserOnline, inverse_data (docs/src/graph_net_core.md)
@@ -202,6 +203,29 @@ def build_graph(mgn, data, fields, datapoint, node_type, edge_features, senders,
         cols.append(mgn.n_norm[field](d))
     cols.append(mgn.n_norm["node_type"](node_type))
     return FeatureGraph(np.concatenate(cols, 1).astype(F32), mgn.e_norm(edge_features).astype(F32), senders, receivers)
+
+
+# ---- src/strategies.jl (derivative strategies) ---------------------------------------------------------
+def init_train_step_derivative(mgn, data, meta, fields, target_fields, node_type, edge_features, senders, receivers, datapoint):
+    """init_train_step(::DerivativeStrategy, ...) at src/strategies.jl:395-416: the normalised change of the target fields over
+    one step, then build_graph.  data[field] and data['target|' + field]: [T-1][N][dim] as add_targets! leaves them
+    (src/dataset.jl:461-481: the field without its last frame, the target without its first); meta['dt']: a scalar, or an array of
+    times, of which the step from `datapoint` to `datapoint + 1` is taken.  datapoint is 0-based here.  Float32 throughout, one
+    rounding per operation; the normalisers are called as the reference calls them (an online one accumulates, then normalises).
+    Returns (graph, target_quantities_change [N][sum of dims]); Engine.step_datapoint is the device form of this plus step!."""
+    dt = meta["dt"]
+    if np.ndim(dt) > 0:
+        tm = np.asarray(dt, F32)
+        delta = F32(tm[datapoint + 1] - tm[datapoint])
+    else:
+        delta = F32(dt)
+    cols = []
+    for field in target_fields:
+        nxt = np.asarray(data["target|" + field], F32)[datapoint]
+        cur = np.asarray(data[field], F32)[datapoint]
+        cols.append(np.asarray(mgn.o_norm[field](((nxt - cur) / delta).astype(F32)), F32))
+    graph = build_graph(mgn, data, fields, datapoint, node_type, edge_features, senders, receivers)
+    return graph, np.concatenate(cols, 1).astype(F32)
 
 
 # ---- src/solve.jl ------------------------------------------------------------------------------------
