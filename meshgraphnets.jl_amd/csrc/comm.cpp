@@ -1,5 +1,6 @@
 // Engine-owned communicator: RCCL (run-time bound), a shared-memory host transport and an in-process transport.  See comm.h.
 #include "comm.h"
+#include "launch.hpp"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -268,7 +269,7 @@ struct HostComm final : Comm {
         char hex[40];
         for (int i = 0; i < 12; ++i) snprintf(hex + 2 * i, 3, "%02x", u[4 + i]);
         name = std::string("/mgn_") + hex;
-        if (const char* e = getenv("MGN_COMM_TIMEOUT_S")) timeout_s = atof(e);
+        timeout_s = env_double("MGN_COMM_TIMEOUT_S", timeout_s);
         const int fd = shm_open(name.c_str(), O_CREAT | O_RDWR, 0600);
         if (fd < 0) { why = "shm_open failed for the communicator's control segment"; return -1; }
         if (ftruncate(fd, sizeof(ShmCtl)) != 0) { close(fd); why = "ftruncate failed on the control segment"; return -1; }
@@ -589,7 +590,7 @@ struct LocalComm final : Comm {
         memcpy(&magic, u, 4);
         if (magic != LOCAL_MAGIC) { why = "the communicator id was not made for the MGN_COMM_LOCAL transport"; return -1; }
         if (nranks > COMM_MAX_RANKS) { why = "MGN_COMM_LOCAL supports up to 64 ranks"; return -1; }
-        if (const char* e = getenv("MGN_COMM_TIMEOUT_S")) timeout_s = atof(e);
+        timeout_s = env_double("MGN_COMM_TIMEOUT_S", timeout_s);
         LocalKey key;
         memcpy(key.b, u + 4, sizeof key.b);
         {

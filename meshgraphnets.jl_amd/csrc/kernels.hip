@@ -30,9 +30,7 @@
 #include "tile_common.hpp"
 #include "split_common.hpp"
 
-#include <cstdlib>
-#include <mutex>
-#include <unordered_map>
+#include "launch.hpp"
 
 namespace mgn {
 
@@ -2500,30 +2498,16 @@ hipError_t launch_eval_finish(EvalFinish f, hipStream_t s) {
 // ================================================================================================
 // launch wrappers
 // ================================================================================================
-static int g_num_cu = 0;
-static int device_cus() {
-    if (g_num_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-            g_num_cu = p.multiProcessorCount;
-        else
-            g_num_cu = 256;
-    }
-    return g_num_cu;
-}
 // Every size decision of the inference launches reads the CU count here.  Tests shrink it (mgn_debug_num_cus) so that a mesh of a few
 // thousand tiles walks the kernels the way a mesh of 32 times the size does on the whole device: placement is speed only (TileWalk,
 // frag.hpp), so a launch of 8 blocks must be as correct as one of 256.  0: the device's own count.
-static int g_num_cu_test = 0;
-static int num_cus() { return g_num_cu_test ? g_num_cu_test : device_cus(); }
+static std::atomic<int> g_num_cu_test{0};
+int num_cus_override() { return g_num_cu_test.load(std::memory_order_relaxed); }
+static int num_cus() { const int t = num_cus_override(); return t ? t : device_cus(); }
 int set_num_cus(int n) {
     if (n != 0 && (n < NUM_XCD || n > device_cus() || n % NUM_XCD != 0)) return -1;
-    const int old = g_num_cu_test;
-    g_num_cu_test = n;
-    return old;
+    return g_num_cu_test.exchange(n, std::memory_order_relaxed);
 }
-int num_cus_override() { return g_num_cu_test; }
 
 constexpr size_t LDS_BYTES = 160 * 1024;
 
@@ -2538,54 +2522,54 @@ static int resident_chunks(int L, int want) {
 // 64-128 threads = 10-17 us): such launches use the all-streaming instantiations (weights stay in L2).
 // g_path: 0 auto, 1 force the LDS-resident persistent kernels, 2 force all-streaming, 3 force cooperative
 // (tests exercise every path on small graphs through mgn_debug_kernel_path)
-static int g_path = [] { const char* e = getenv("MGN_KERNEL_PATH"); return e ? atoi(e) : 0; }();   // experiments
-int set_kernel_path(int p) { const int old = g_path; g_path = p; return old; }
-static int g_c16_rt = [] { const char* e = getenv("MGN_C16_RT"); return e ? atoi(e) : 0; }();   // 0: by size; 1..3: 16-edge tiles per block
+static Switch g_path{"MGN_KERNEL_PATH", 0};   // experiments
+int set_kernel_path(int p) { return g_path.set(p); }
+static Switch g_c16_rt{"MGN_C16_RT", 0};   // 0: by size; 1..3: 16-edge tiles per block
 // Large fp32 launches at L = 128, hidden_layers = 2 run on the bf16 matrix cores with every operand split exactly into three bf16
 // pieces (split.hip / split_ws.hip: fp32 storage, fp32 accumulation, error against float64 no worse than the fp32-MFMA kernels').
 // MGN_FP32_SPLIT: 0 = the fp32-MFMA kernels (v_mfma_f32_32x32x2_f32: the fp32 reference path), 1 = default (edge step: the
 // lock-step kernel with the shared LDS weight ring), 2 = the edge step with per-wave register rings (A/B).
-static int g_fp32_split = [] { const char* e = getenv("MGN_FP32_SPLIT"); return e ? atoi(e) : 1; }();
-int set_fp32_split(int on) { const int old = g_fp32_split; g_fp32_split = on; return old; }
+static Switch g_fp32_split{"MGN_FP32_SPLIT", 1};
+int set_fp32_split(int on) { return g_fp32_split.set(on); }
 int fp32_split_enabled() { return g_fp32_split; }
 // 16-row cooperative kernels on the split path: bit 0 the edge kernel (with two or three row tiles per block its chains are
 // matrix-bound on the fp32 pipe: 17.2 -> 14.1 us on the cylinder mesh), bit 1 the node kernel (one row tile per block streams 96 KiB of
 // weight pieces per chunk where the fp32 fragments are 64 and is bound by that stream either way: 11.6 -> 11.3 us), bit 2 the edge
 // kernel at one row tile per block as well.  Cylinder mesh, per processor step: 29.3 us (0), 26.1 (1), 25.8 (3, the default).
-static int g_c16_split = [] { const char* e = getenv("MGN_C16_SPLIT"); return e ? atoi(e) : 3; }();
-int set_c16_split(int on) { const int old = g_c16_split; g_c16_split = on; return old; }
+static Switch g_c16_split{"MGN_C16_SPLIT", 3};
+int set_c16_split(int on) { return g_c16_split.set(on); }
 int c16_split_enabled() { return g_c16_split; }
 // two fp16 pieces and three products instead of three bf16 pieces and six (k_edge_ring_h, split.hip); MGN_SPLIT_F16=0: the bf16 pieces
-static int g_split_f16 = [] { const char* e = getenv("MGN_SPLIT_F16"); return e ? atoi(e) : 1; }();
-int set_split_f16(int on) { const int old = g_split_f16; g_split_f16 = on; return old; }
+static Switch g_split_f16{"MGN_SPLIT_F16", 1};
+int set_split_f16(int on) { return g_split_f16.set(on); }
 int split_f16_enabled() { return g_split_f16; }
-int set_c16_row_tiles(int rt) { const int old = g_c16_rt; g_c16_rt = rt; return old; }
+int set_c16_row_tiles(int rt) { return g_c16_rt.set(rt); }
 int get_kernel_path() { return g_path; }
 static bool small_launch(int ntiles) { return g_path == 0 ? ntiles <= 4 * num_cus() : g_path >= 2; }
 // cooperative (4 waves per tile) kernels: up to this many tiles per CU for the edge / node kernels (size sweep)
-static int g_tail_coop = [] { const char* e = getenv("MGN_TAIL_COOP"); return e ? atoi(e) : 1; }();   // 0: whole launch persistent
-static int g_coop_edge = [] { const char* e = getenv("MGN_COOP_EDGE_TILES_PER_CU"); return e ? atoi(e) : 16; }();
-static int g_coop_node = [] { const char* e = getenv("MGN_COOP_NODE_TILES_PER_CU"); return e ? atoi(e) : 8; }();
-static int g_coop16 = [] { const char* e = getenv("MGN_COOP16"); return e ? atoi(e) : 1; }();   // 16-row cooperative tiles on small graphs
+static Switch g_tail_coop{"MGN_TAIL_COOP", 1};   // 0: whole launch persistent
+static Switch g_coop_edge{"MGN_COOP_EDGE_TILES_PER_CU", 16};
+static Switch g_coop_node{"MGN_COOP_NODE_TILES_PER_CU", 8};
+static Switch g_coop16{"MGN_COOP16", 1};   // 16-row cooperative tiles on small graphs
 int coop16_enabled() { return (g_coop16 && (g_path == 0 || g_path == 5)) ? 1 : 0; }
 // the 16-row tiles pay while the launches are latency-bound: up to this many 32-row tiles per CU (size sweep, docs/experiments.md)
 // (`ring_hs`: the handle's large-mesh edge kernel would be k_edge_ring_hs -- fp32, one edge set, two fp16 pieces -- whose 28 KiB LDS prologue
 // lets it take over a tile per CU earlier: 3 025 nodes 38 -> 35 us per step, 4 096 nodes 42 -> 37)
-static int g_c16_edge = [] { const char* e = getenv("MGN_C16_EDGE_TILES_PER_CU"); return e ? atoi(e) : 0; }();   // 0: 3, or 2 with ring_hs
-static int g_c16_node = [] { const char* e = getenv("MGN_C16_NODE_TILES_PER_CU"); return e ? atoi(e) : 1; }();
+static Switch g_c16_edge{"MGN_C16_EDGE_TILES_PER_CU", 0};   // 0: 3, or 2 with ring_hs
+static Switch g_c16_node{"MGN_C16_NODE_TILES_PER_CU", 1};
 bool coop16_size(int ntiles_e, int ntiles_n, bool ring_hs) {
     if (g_path == 5) return true;
     const int lim = g_c16_edge > 0 ? g_c16_edge : (ring_hs ? 2 : 3);
     return ntiles_e <= lim * num_cus() && ntiles_n <= g_c16_node * num_cus();
 }
-int set_c16_edge_tiles(int t) { const int old = g_c16_edge; g_c16_edge = t; return old; }   // (tests: 0 = by the handle, n = n tiles per CU)
+int set_c16_edge_tiles(int t) { return g_c16_edge.set(t); }   // (tests: 0 = by the handle, n = n tiles per CU)
 bool ring_hs_default() { return g_fp32_split == 1 && g_split_f16 != 0 && g_path == 0 && edge_ring_h_streamed() != 0; }
 static bool coop_size(int ntiles, bool edge) { return g_path == 0 ? ntiles <= (edge ? g_coop_edge : g_coop_node) * num_cus() : (g_path == 3 || g_path == 5); }
 bool launch_is_small(int ntiles) { return coop_size(ntiles, false); }
 // where the split-path node kernels (k_node_split + k_project_split) take the node side from the cooperative tiles: above two tiles per CU
 // (19.6 k nodes: 50 -> 43 us, 32 k: 66 -> 50, 62 k: 131 -> 98; at 16 k, two tiles per CU, the cooperative kernels are faster: 37 vs 48)
-static int g_node16_mid = [] { const char* e = getenv("MGN_NODE16_MID"); return e ? atoi(e) : 1; }();   // 0: cooperative 32-row node kernel (fp32 pipe) there
-static const int g_node_split_min = [] { const char* e = getenv("MGN_NODE_SPLIT_MIN_TILES_PER_CU"); return e ? atoi(e) : 2; }();
+static Switch g_node16_mid{"MGN_NODE16_MID", 1};   // 0: cooperative 32-row node kernel (fp32 pipe) there
+static const int g_node_split_min = env_int("MGN_NODE_SPLIT_MIN_TILES_PER_CU", 2);
 bool node_split_size(int ntiles) { return g_fp32_split != 0 && g_path == 0 && ntiles > g_node_split_min * num_cus(); }
 bool launch_is_small_edge(int ntiles_e) { return coop_size(ntiles_e, true); }
 
@@ -2608,21 +2592,7 @@ static LaunchCfg tile_launch(int L, int ntiles, int nres) {
 
 template <typename K, typename A>
 static hipError_t launch_k(K kern, const A& a, const LaunchCfg& lc, hipStream_t s) {
-    // opt in to > 64 KiB dynamic LDS once per kernel and size (small meshes are launch-bound: keep this off the
-    // per-launch path)
-    {
-        static std::mutex mu;
-        static std::unordered_map<const void*, size_t> granted;   // keyed by kernel: K is only the signature type
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& g = granted[reinterpret_cast<const void*>(kern)];
-        if (lc.lds > g) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lc.lds);
-            if (e != hipSuccess) return e;
-            g = lc.lds;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(lc.blocks), dim3(lc.threads), lc.lds, s, a);
-    return hipGetLastError();
+    return launch_kernel(kern, lc.blocks, lc.threads, lc.lds, s, a);
 }
 
 hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);
@@ -2645,7 +2615,7 @@ static LaunchCfg gen_launch(int L, int ntiles) {
 
 // pinned weight rings (coop_chain_primed<true>) while a launch has at most MGN_COOP_FENCE_TILES_PER_CU (default 4) tiles per CU
 static bool coop_fence(int ntiles) {
-    static const int per_cu = [] { const char* e = getenv("MGN_COOP_FENCE_TILES_PER_CU"); return e ? atoi(e) : 4; }();
+    static const int per_cu = env_int("MGN_COOP_FENCE_TILES_PER_CU", 4);
     return ntiles <= per_cu * num_cus();
 }
 static size_t coop_lds() { return (size_t)2 * 16 * 64 * 16 + (size_t)T_COUNT * 128 * 4; }
@@ -2658,13 +2628,15 @@ static bool coop_ok(int L, int ntiles, const float* const* chunk_t, bool edge = 
 // 7 k_edge_ring<8>, 8 k_edge_ring<4>, 9 k_edge_step<4,2> (fp32-MFMA persistent), (10, 11: retired,) 12 k_edge_coop16m on the
 // split path, 13 / 14 k_edge_ring_h<8 / 4> (two fp16 pieces: the default of large fp32 launches); bf16 mode: 18 k_edge_bf16_pipe
 // (its small graphs run the 16-row kernels on the bf16 arrays and record their codes)
-static int g_last_edge_kernel = 0;
-int last_edge_kernel() { return g_last_edge_kernel; }
+// (relaxed atomics, like the switches: every rank thread's launches write the two family records)
+static std::atomic<int> g_last_edge_kernel{0};
+static void set_last(std::atomic<int>& rec, int code) { rec.store(code, std::memory_order_relaxed); }
+int last_edge_kernel() { return g_last_edge_kernel.load(std::memory_order_relaxed); }
 // the family of the launch that carries a set's edges: a launch over less than half of the set's tiles (the boundary tiles of a partitioned pass,
 // launched AFTER the interior ones) does not speak for the step
 #define SET_LAST_EDGE(A, CODE)                                                            \
     do {                                                                                  \
-        if (2 * (int64_t)(A).ntiles * TILE >= (A).E) g_last_edge_kernel = (CODE);         \
+        if (2 * (int64_t)(A).ntiles * TILE >= (A).E) set_last(g_last_edge_kernel, CODE);  \
     } while (0)
 
 hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
@@ -2715,7 +2687,7 @@ hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
     if (a.ElatSrc) return hipErrorInvalidValue;      // only the 16-row kernel reads its e rows from a second array
     // where the ring kernel of the split path is available it takes over from the cooperative tiles at 3 tiles per CU already
     // (four-wave blocks; 5 k nodes: 50 vs 68 us per step, 10 k: 85 vs 110, 16 k: 110 vs 146), the fp32-MFMA persistent kernels only at 16
-    static const int coop_edge_ring_env = [] { const char* e = getenv("MGN_COOP_EDGE_TILES_PER_CU_RING"); return e ? atoi(e) : 0; }();
+    static const int coop_edge_ring_env = env_int("MGN_COOP_EDGE_TILES_PER_CU_RING", 0);
     const bool ring_ok = L == 128 && g_fp32_split == 1 && a.split[0] && g_path == 0;
     const int coop_edge_ring = coop_edge_ring_env > 0 ? coop_edge_ring_env : ((ring_ok && g_split_f16 && a.splith[0] && edge_ring_h_streamed()) ? 2 : 3);
     if (coop_ok(L, a.ntiles, a.chunk_t, true) && !(ring_ok && a.ntiles > coop_edge_ring * num_cus())) {   // small graph: 4 waves per tile
@@ -2732,7 +2704,7 @@ hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
         if (g_fp32_split && a.split[0] && g_path == 0) {   // split path (split.hip): fp32 accuracy on the bf16 matrix cores
             LaunchCfg ls = lc;
             ls.lds = (size_t)3 * 32768 + (size_t)3 * 16384 + (size_t)T_COUNT * L * 4 + 64;
-            static const int ring_waves = [] { const char* e = getenv("MGN_RING_WAVES"); return e ? atoi(e) : 0; }();   // 0: by size
+            static const int ring_waves = env_int("MGN_RING_WAVES", 0);   // 0: by size
             // four-wave blocks (one wave per SIMD) up to 2.5 rounds of eight-wave blocks: 16 k nodes 75 vs 83 us, 25.6 k 115 vs 120,
             // 40 k 175 vs 160 (docs/experiments.md)
             // k_edge_ring_hs (28 KiB of LDS prologue per block instead of 150): a round of four-wave blocks takes ~0.62 of a round of eight-wave
@@ -2784,11 +2756,11 @@ hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
     if (L == 32) return launch_k(k_edge_step<1, 3>, a, lc, s);
     return hipErrorInvalidValue;
 }
-static int g_last_node_kernel = 0;    // family of the last node-MLP launch (tests / bench): 1 general, 2 16-row cooperative, 3 cooperative,
-int last_node_kernel() { return g_last_node_kernel; }   // 5 k_node_split, 6 k_node_split<two sets>, 7 fp32-MFMA k_node_step, 8 / 9 16-row kernels on the split path, 10 k_node_split_h, 12 k_node_bf16_pipe
+static std::atomic<int> g_last_node_kernel{0};    // family of the last node-MLP launch (tests / bench): 1 general, 2 16-row cooperative, 3 cooperative,
+int last_node_kernel() { return g_last_node_kernel.load(std::memory_order_relaxed); }   // 5 k_node_split, 6 k_node_split<two sets>, 7 fp32-MFMA k_node_step, 8 / 9 16-row kernels on the split path, 10 k_node_split_h, 12 k_node_bf16_pipe
 hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    if (a.mode != 2) g_last_node_kernel = a.gen.use ? 1 : (a.c16 && L == 128 && a.chunk_t[0]) ? 2 : coop_ok(L, a.ntiles, a.chunk_t) ? 3 : 7;
+    if (a.mode != 2) set_last(g_last_node_kernel, a.gen.use ? 1 : (a.c16 && L == 128 && a.chunk_t[0]) ? 2 : coop_ok(L, a.ntiles, a.chunk_t) ? 3 : 7);
     if (a.gen.use) {
         if (a.mode == 2) return launch_project(L, a, s);
         if (a.AGG2) {
@@ -2802,7 +2774,7 @@ hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
         LaunchCfg c16{2 * a.ntiles, 256, (size_t)4 * 8 * 64 * 16 + 2 * 64 * 4};
         if (g_fp32_split && (g_c16_split & 2) && a.split16[0] && (!a.AGG2 || a.split16[6])) {   // split path (pieces exchanged: 12 KiB per buffer)
             c16.lds = (size_t)4 * 12 * 64 * 16 + 2 * 64 * 4;
-            if (a.mode != 2) g_last_node_kernel = 8;
+            if (a.mode != 2) set_last(g_last_node_kernel, 8);
             if (g_split_f16 && a.split16h[0] && (!a.AGG2 || a.split16h[6])) {      // two fp16 pieces
                 if (a.bf) return a.AGG2 ? launch_k(k_node_coop16<2, true, 2>, a, c16, s) : launch_k(k_node_coop16<1, true, 2>, a, c16, s);
                 return a.AGG2 ? launch_k(k_node_coop16<2, false, 2>, a, c16, s) : launch_k(k_node_coop16<1, false, 2>, a, c16, s);
@@ -2820,7 +2792,7 @@ hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
     if (g_node16_mid && g_fp32_split && (g_c16_split & 2) && g_path == 0 && L == 128 && !a.bf && !a.AGG2 && a.mode != 2 && a.split16[0] &&
         coop_ok(L, a.ntiles, a.chunk_t) && !split_node) {
         LaunchCfg c16{2 * a.ntiles, 256, (size_t)4 * 12 * 64 * 16 + 2 * 64 * 4};
-        g_last_node_kernel = 9;
+        set_last(g_last_node_kernel, 9);
         if (g_split_f16 && a.split16h[0]) return launch_k(k_node_coop16<1, false, 2, 5>, a, c16, s);
         return launch_k(k_node_coop16<1, false, 1, 5>, a, c16, s);
     }
@@ -2835,10 +2807,10 @@ hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
         LaunchCfg ls = tile_launch(L, a.ntiles, 2);
         ls.lds = (size_t)4 * 16384 * 2 + (size_t)T_COUNT * L * 4 + 64;
         if (g_split_f16 && a.splith[0] && !a.AGG2) {   // two fp16 pieces, three products
-            g_last_node_kernel = 10;
+            set_last(g_last_node_kernel, 10);
             return launch_node_split_h(a, ls, s);
         }
-        g_last_node_kernel = a.AGG2 ? 6 : 5;
+        set_last(g_last_node_kernel, a.AGG2 ? 6 : 5);
         return launch_node_split(a, ls, s);
     }
     const int nres = resident_chunks(L, proj ? 6 : 4);
@@ -2881,7 +2853,7 @@ hipError_t launch_node_project_fused(int L, const NodeArgs& a, hipStream_t s, bo
     int blocks = (a.ntiles + 7) / 8;
     if (blocks > num_cus()) blocks = num_cus();
     ls.blocks = ((blocks + NUM_XCD - 1) / NUM_XCD) * NUM_XCD;
-    g_last_node_kernel = 11;
+    set_last(g_last_node_kernel, 11);
     *launched = true;
     return launch_node_ring_hs(a, ls, s);
 }
@@ -2984,7 +2956,7 @@ hipError_t launch_edge_bf16(const BfEdgeArgs& a, hipStream_t s) {
 }
 hipError_t launch_node_bf16(const BfNodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    g_last_node_kernel = 12;
+    set_last(g_last_node_kernel, 12);
     return launch_k(k_node_bf16_pipe, a, bf_launch(a.ntiles, 4), s);
 }
 hipError_t launch_project_bf16(const BfNodeArgs& a, hipStream_t s) {

@@ -19,6 +19,7 @@
 #include "engine_internal.h"
 #include "train.h"
 #include "graph_dev.h"
+#include "launch.hpp"
 
 using namespace mgn;
 
@@ -584,7 +585,7 @@ int mgn::sync_norms_host(mgn_engine* h) {
 
 // step 0's edge launch can read its e rows from a second array (EdgeArgs::ElatSrc): one edge set on the 16-row kernels, one partition
 bool mgn::elat_src_ok(mgn_engine* h) {
-    static const int on = [] { const char* e = getenv("MGN_RHS_ELAT_SRC"); return e ? atoi(e) : 1; }();   // 0: restore copy per right-hand side
+    static const int on = env_int("MGN_RHS_ELAT_SRC", 1);   // 0: restore copy per right-hand side
     return on && h->nsets == 1 && h->cfg.nranks == 1 && h->cfg.L == 128 && h->cfg.hidden_layers == 2 && get_kernel_path() != 4 && use_c16(h);
 }
 
@@ -631,10 +632,10 @@ int mgn_create(const mgn_config* cfg, mgn_handle** out) try {
         return fail(nullptr, MGN_E_HIP, "mgn_create: hipStreamCreate failed");
     }
     h->stream = h->own_stream;
-    if (const char* e = getenv("MGN_STAGGER_EDGE")) h->stagger_edge = atoi(e);
-    if (const char* e = getenv("MGN_STAGGER_NODE")) h->stagger_node = atoi(e);
-    if (const char* e = getenv("MGN_NODE_SPLIT")) h->node_split = atoi(e);
-    if (const char* e = getenv("MGN_GRAPH")) h->use_graph = atoi(e);
+    h->stagger_edge = env_int("MGN_STAGGER_EDGE", h->stagger_edge);
+    h->stagger_node = env_int("MGN_STAGGER_NODE", h->stagger_node);
+    h->node_split = env_int("MGN_NODE_SPLIT", h->node_split);
+    h->use_graph = env_int("MGN_GRAPH", h->use_graph);
     layout_all(h);
     *out = h;
     return MGN_OK;
@@ -979,7 +980,7 @@ int mgn_set_norms(mgn_handle* h, const float* ns, const float* nsh, const float*
 // order of the mesh is RENUMBER_GAIN times more local (DeepMind's trajectories carry arbitrary node numbers and create_base_graph
 // passes them through, reference src/graph.jl:30-36; the processor kernels gather sender rows and lose 4-9 % (fp32) / 25 % (bf16)
 // on a scattered numbering), 0 = never, 2 = always.  Invisible at the boundary: every array crosses it in the caller's order.
-static int g_renumber = [] { const char* e = getenv("MGN_RENUMBER"); return e ? atoi(e) : 1; }();
+static Switch g_renumber{"MGN_RENUMBER", 1};
 
 // (re)build the local graph from the kept global edge lists and upload it.  keep_owner: node partition unchanged
 extern "C++" int mgn::rebuild_graph(mgn_handle* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner,
@@ -2196,7 +2197,7 @@ int mgn_comm_init(mgn_handle* h, const void* id, size_t id_bytes, int32_t transp
     std::string why;
     h->comm = comm_create(id, transport, h->cfg.rank, h->cfg.nranks, !h->host_only, why);
     if (!h->comm) return fail(h, MGN_E_RCCL, "mgn_comm_init: %s", why.c_str());
-    if (const char* e = getenv("MGN_FORCE_STAGED")) h->force_staged = atoi(e);
+    h->force_staged = env_int("MGN_FORCE_STAGED", h->force_staged);
     h->hx_ready = false;
     h->all_gid.clear();
     if (!h->host_only) drop_graph(h);
@@ -2239,7 +2240,7 @@ void nap20ms() {
 
 int mgn_comm_init_file(mgn_handle* h, const char* path, int32_t transport) try {
     if (!h || !path) return fail(h, MGN_E_ARG, "mgn_comm_init_file: null argument");
-    const double limit = getenv("MGN_COMM_TIMEOUT_S") ? atof(getenv("MGN_COMM_TIMEOUT_S")) : 120.0;
+    const double limit = env_double("MGN_COMM_TIMEOUT_S", 120.0);
     const std::string base(path), go = base + ".go";
     const int rank = h->cfg.rank, nranks = h->cfg.nranks;
     auto ack_of = [&](int r) { return base + ".ack." + std::to_string(r); };
@@ -2425,7 +2426,7 @@ int mgn_debug_c16_split(int on) { return set_c16_split(on); }   // bits: 1 edge 
 int mgn_debug_last_node_kernel(void) { return last_node_kernel(); }   // the same for the node MLP (codes: kernels.hip, launch_node_step)
 int mgn_debug_last_edge_kernel(void) { return last_edge_kernel(); }   // kernels.hip: which family the last fp32 edge launch ran on
 // node numbering policy of the NEXT mgn_set_graph calls (0 never, 1 auto, 2 always breadth-first); returns the old value
-int mgn_debug_renumber(int mode) { const int old = g_renumber; g_renumber = mode; return old; }
+int mgn_debug_renumber(int mode) { return g_renumber.set(mode); }
 // tests: the row maximum the two-piece split kernels scale a row by (split_common.hpp: h2_rowmax<abs != 0>) and h2_scale's pair for it, of
 // nrows >= 1 rows of 128 floats each (host arrays; amax, s, rs: [nrows]).  abs != 0: max |x|; abs == 0: max(x, 0)
 int mgn_debug_rowmax(const float* rows, int nrows, int abs, float* amax, float* s, float* rs) {

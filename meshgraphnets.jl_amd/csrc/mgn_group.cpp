@@ -117,7 +117,7 @@ struct mgn_group {
 #pragma GCC visibility pop
 
 namespace {
-std::string g_group_create_error;
+thread_local std::string g_group_create_error;   // like g_create_error (mgn_api.cpp): a failed create reports to its own thread
 int create_fail(int code, const std::string& what) {
     g_group_create_error = what;
     return code;

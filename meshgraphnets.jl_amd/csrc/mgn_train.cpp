@@ -3,12 +3,13 @@
 // Host orchestration only -- weights repacked into training order (forward and transposed chunks), an arena of kept
 // activations, kernel sequencing; all arithmetic is in train.hip.  No CPU compute path.
 #include <algorithm>
-#include <cstdlib>
+#include <climits>
 #include <cstring>
 #include <numeric>
 
 #include "engine_internal.h"
 #include "train.h"
+#include "launch.hpp"
 
 namespace mgn {
 
@@ -72,7 +73,7 @@ struct TrainState {
     std::vector<Acts> a_pe[MAX_EDGE_SETS], a_pn;
     std::vector<size_t> Ek[MAX_EDGE_SETS], Vk, agg[MAX_EDGE_SETS];
     static constexpr int GSETS_MAX = 72;
-    static inline int GSETS = [] { const char* e = getenv("MGN_TRAIN_GSETS"); const int v = e ? atoi(e) : 4; return v < 2 ? 2 : (v > 72 ? 72 : v); }();   // gradient-buffer sets: the weight gradients of unit i run beside the backward of units i+1 .. i+3
+    static inline int GSETS = std::clamp(env_int("MGN_TRAIN_GSETS", 4), 2, GSETS_MAX);   // gradient-buffer sets: the weight gradients of unit i run beside the backward of units i+1 .. i+3
     int gsets = 1;                    // sets allocated for the current graph (GSETS on small meshes, else 1: no overlap)
     size_t GT[GSETS_MAX], GXH[GSETS_MAX], GY[GSETS_MAX], GZ2[GSETS_MAX], GZ1[GSETS_MAX];
     size_t GXs, GXr, GXB, gV[2], gE[MAX_EDGE_SETS][2], gAgg[MAX_EDGE_SETS], Gout, gNF, io, ptmp, pw, pb;
@@ -408,7 +409,7 @@ int prepare_graph(mgn_engine* h) {
         for (int q = 0; q < S; ++q) {
             const int64_t E = g.set[q].e_local;
             T.factored[q] = !train_uses_coop(128, (int)((E + TILE - 1) / TILE));   // the size rule of the cooperative kernels, for every L
-            if (const char* e = getenv("MGN_TRAIN_FACTORED")) T.factored[q] = atoi(e) != 0;
+            T.factored[q] = env_int("MGN_TRAIN_FACTORED", T.factored[q]) != 0;
             if (E == 0) T.factored[q] = false;
             any_fact = any_fact || T.factored[q];
             all_fact = all_fact && T.factored[q];
@@ -416,7 +417,7 @@ int prepare_graph(mgn_engine* h) {
         // Small meshes (the cooperative-tile regime: a launch leaves most of the chip idle) get GSETS sets of gradient buffers so
         // that the parameter gradients can run on a second stream; larger ones fill the chip on their own and keep one set.
         {
-            static const bool overlap_env = [] { const char* e = getenv("MGN_TRAIN_OVERLAP"); return !e || atoi(e) != 0; }();
+            static const bool overlap_env = env_int("MGN_TRAIN_OVERLAP", 1) != 0;
             const int64_t big = Emax > N ? Emax : N;
             T.gsets = (overlap_env && !part && !T.recompute && !any_fact && L == 128 && big <= (int64_t)8 * train_size_cus() * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers; a partition runs on one stream, eagerly: communicator calls sit between its launches)
         }
@@ -444,7 +445,7 @@ int prepare_graph(mgn_engine* h) {
         T.pb = take((size_t)(WGRAD_MAX_JOBS + 1) * (nb > 0 ? nb : 1) * L);   // (+ 1: the second output of a LayerNorm job)
         {   // Deferred reductions (MGN_TRAIN_DEFER_REDUCE = 1; built, same bits, off) where the weight gradients run on the second stream: the 33
             // k_reduce_partials launches of a step as five at its end.
-            static const int defer_env = [] { const char* e = getenv("MGN_TRAIN_DEFER_REDUCE"); return e ? atoi(e) : 0; }();   // (measured: 2.54 ms against 2.36 -- the per-unit partial blocks, re-used, stay in the caches; 680 MB of them do not)
+            static const int defer_env = env_int("MGN_TRAIN_DEFER_REDUCE", 0);   // (measured: 2.54 ms against 2.36 -- the per-unit partial blocks, re-used, stay in the caches; 680 MB of them do not)
             const int units = (2 + S + mps * (S + 1)) * NB;
             const size_t per_unit = ((size_t)5 * L * L + (size_t)DEFER_PB_JOBS * L) * (nb > 0 ? nb : 1);
             T.defer_reduce = defer_env && T.gsets > 1 && per_unit * units * 4 <= ((size_t)8 << 30);
@@ -484,15 +485,15 @@ int prepare_graph(mgn_engine* h) {
             size_t free_b = 0, total_b = 0;
             // a companion (mgn_shooting_grad) recomputes: the free memory belongs to its parent's own training arena
             if (!h->companion && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                double reserve = 16e9;
-                if (const char* e = getenv("MGN_TRAIN_RESERVE_GB")) reserve = atof(e) * 1e9;
+                const double reserve = env_double("MGN_TRAIN_RESERVE_GB", 16.0) * 1e9;
                 const double base = (double)layout(0) * 4.0;          // the arena with every step recomputed: a dry run of the layout below
                 const double room = (double)free_b - base - reserve;
                 if (room > 0) keep0 = (int)std::min<double>((double)mps, room / per_step);
             }
         }
-        if (const char* e = getenv("MGN_TRAIN_RECOMPUTE")) keep0 = atoi(e) != 0 ? 0 : mps;
-        if (const char* e = getenv("MGN_TRAIN_KEEP_STEPS")) keep0 = std::max(0, std::min(mps, atoi(e)));
+        const int recompute = env_int("MGN_TRAIN_RECOMPUTE", INT_MIN);   // unset: by the rule above
+        if (recompute != INT_MIN) keep0 = recompute != 0 ? 0 : mps;
+        keep0 = std::max(0, std::min(mps, env_int("MGN_TRAIN_KEEP_STEPS", keep0)));
     }
     T.drop_graphs();
     T.traj.ef_pad_ok = false;
@@ -500,8 +501,7 @@ int prepare_graph(mgn_engine* h) {
     T.wg_rpb_last = T.wg_rpb_node = 0;
     for (int64_t& v : T.wg_rpb_edge) v = 0;
     size_t off = 0;
-    int test_fail = 0;                                    // MGN_TRAIN_TEST_FAIL_ALLOCS = n: the first n requests count as refused (tests of the retry)
-    if (const char* e = getenv("MGN_TRAIN_TEST_FAIL_ALLOCS")) test_fail = atoi(e);
+    int test_fail = env_int("MGN_TRAIN_TEST_FAIL_ALLOCS", 0);   // n: the first n requests count as refused (tests of the retry)
     for (int keep = keep0;; keep = keep / 2) {            // an allocation that fails is retried with fewer stored steps (none at last)
         off = layout(keep);
         if (test_fail-- <= 0 && T.arena.ensure(off * 4) == hipSuccess) break;
@@ -861,7 +861,7 @@ struct TrainPass {
             sx[q].rowptr = h->es[q].d_rowptr.as<int32_t>();
             lrows_all = std::max<int64_t>(lrows_all, sx[q].E);
         }
-        static const int group_env = [] { const char* e = getenv("MGN_TRAIN_WG_GROUP"); return e ? atoi(e) : 1; }();
+        static const int group_env = env_int("MGN_TRAIN_WG_GROUP", 1);
         if (overlap) group = std::max(1, std::min(group_env, T.gsets / 2));
     }
     bool vjp() const { return J.kind != JOB_STEP && J.kind != JOB_DATAPOINT; }
@@ -1951,8 +1951,7 @@ LnAll lnall_layout(mgn_engine* h, bool with_inputs, size_t& floats) {
     size_t off = 0;
     auto take = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
     X.V = take(NL); X.Ecur = take(EL); X.Y = take(ML); X.Hb = T.nblk > 1 ? take(ML) : 0; X.agg = take(NL);
-    X.factored = !train_uses_coop(128, X.nt_e) && X.E > 0;
-    if (const char* e = getenv("MGN_TRAIN_FACTORED")) X.factored = atoi(e) != 0 && X.E > 0;
+    X.factored = env_int("MGN_TRAIN_FACTORED", !train_uses_coop(128, X.nt_e)) != 0 && X.E > 0;
     X.Pn = X.Qn = 0;
     if (X.factored) { X.Pn = take(NL); X.Qn = take(NL); }
     X.stats = take(64);

@@ -19,11 +19,11 @@
 // split's subtractions sit between inline-asm conversions and scheduling fences, where hipcc's SLP vectoriser does not pair them --
 // the shipped object has its v_pk_* instructions in the epilogue only -- so no -fno-slp-vectorize is passed; MGN_SPLIT_FLAGS adds it
 // for A/B runs.)
-#include <cstdlib>
 
 #include "kernels.h"
 #include "tile_common.hpp"
 #include "split_common.hpp"
+#include "launch.hpp"
 
 namespace mgn {
 
@@ -1650,63 +1650,46 @@ __global__ __launch_bounds__(512, 2) void k_project_split_h(const NodeArgs a) {
     }
 }
 
-template <typename K, typename A>
-static hipError_t sp_launch(K kern, const A& a, const LaunchCfg& lc, hipStream_t s, bool& attr_set) {
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(lc.blocks), dim3(lc.threads), lc.lds, s, a);
-    return hipGetLastError();
-}
+// (the launches: launch.hpp raises each kernel's dynamic-LDS grant to the size it is launched with)
 hipError_t launch_edge_ring(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set8 = false, attr_set4 = false;
-    if (lc.threads == 256) return sp_launch(k_edge_ring<4>, a, lc, s, attr_set4);
-    return sp_launch(k_edge_ring<8>, a, lc, s, attr_set8);
+    if (lc.threads == 256) return launch_kernel(k_edge_ring<4>, lc.blocks, lc.threads, lc.lds, s, a);
+    return launch_kernel(k_edge_ring<8>, lc.blocks, lc.threads, lc.lds, s, a);
 }
-static int g_ringh_stream = [] { const char* e = getenv("MGN_RINGH_STREAM"); return e ? atoi(e) : 1; }();   // 1 (default): k_edge_ring_hs (no resident weight piece, e parked in LDS: read once); 0: k_edge_ring_h
+static Switch g_ringh_stream{"MGN_RINGH_STREAM", 1};   // 1 (default): k_edge_ring_hs (no resident weight piece, e parked in LDS: read once); 0: k_edge_ring_h
 int edge_ring_h_streamed() { return g_ringh_stream; }
-int set_ringh_stream(int on) { const int old = g_ringh_stream; g_ringh_stream = on; return old; }
+int set_ringh_stream(int on) { return g_ringh_stream.set(on); }
 hipError_t launch_edge_ring_h(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set8 = false, attr_set4 = false, attr_s8 = false, attr_s4 = false;
     if (g_ringh_stream) {
         LaunchCfg ls = lc;
         ls.lds = (size_t)Rs::NB * Rs::BUF * 16 + (size_t)(lc.threads / 64) * 16384 + (size_t)T_COUNT * 128 * 4 + 64;
-        if (lc.threads == 256) return sp_launch(k_edge_ring_hs<4>, a, ls, s, attr_s4);
-        return sp_launch(k_edge_ring_hs<8>, a, ls, s, attr_s8);
+        if (lc.threads == 256) return launch_kernel(k_edge_ring_hs<4>, ls.blocks, ls.threads, ls.lds, s, a);
+        return launch_kernel(k_edge_ring_hs<8>, ls.blocks, ls.threads, ls.lds, s, a);
     }
-    if (lc.threads == 256) return sp_launch(k_edge_ring_h<4>, a, lc, s, attr_set4);
-    return sp_launch(k_edge_ring_h<8>, a, lc, s, attr_set8);
+    if (lc.threads == 256) return launch_kernel(k_edge_ring_h<4>, lc.blocks, lc.threads, lc.lds, s, a);
+    return launch_kernel(k_edge_ring_h<8>, lc.blocks, lc.threads, lc.lds, s, a);
 }
 size_t edge_ring_h_lds() { return (size_t)3 * 32768 + (size_t)Rh<MGN_RINGH_W>::NB * Rh<MGN_RINGH_W>::BUF * 16 + (size_t)T_COUNT * 128 * 4 + 64; }
 hipError_t launch_node_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set = false;
-    static bool attr_set2 = false;
-    if (a.AGG2) return sp_launch(k_node_split<true>, a, lc, s, attr_set2);
-    return sp_launch(k_node_split<false>, a, lc, s, attr_set);
+    if (a.AGG2) return launch_kernel(k_node_split<true>, lc.blocks, lc.threads, lc.lds, s, a);
+    return launch_kernel(k_node_split<false>, lc.blocks, lc.threads, lc.lds, s, a);
 }
 hipError_t launch_node_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set = false;
-    return sp_launch(k_node_split_h, a, lc, s, attr_set);
+    return launch_kernel(k_node_split_h, lc.blocks, lc.threads, lc.lds, s, a);
 }
-static int g_node_ring_hs = [] { const char* e = getenv("MGN_NODE_RING_HS"); return e ? atoi(e) : 1; }();   // 1 (default): node MLP + projection as k_node_ring_hs where both would run; 0: k_node_split_h + k_project_split_h
+static Switch g_node_ring_hs{"MGN_NODE_RING_HS", 1};   // 1 (default): node MLP + projection as k_node_ring_hs where both would run; 0: k_node_split_h + k_project_split_h
 int node_ring_hs_enabled() { return g_node_ring_hs; }
-int set_node_ring_hs(int on) { const int old = g_node_ring_hs; g_node_ring_hs = on; return old; }
+int set_node_ring_hs(int on) { return g_node_ring_hs.set(on); }
 hipError_t launch_node_ring_hs(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set = false;
     LaunchCfg ls = lc;
     ls.threads = 512;
     ls.lds = (size_t)Rs::NB * Rs::BUF * 16 + (size_t)8 * 16384 + (size_t)T_COUNT * 128 * 4 + 64;
-    return sp_launch(k_node_ring_hs, a, ls, s, attr_set);
+    return launch_kernel(k_node_ring_hs, ls.blocks, ls.threads, ls.lds, s, a);
 }
 hipError_t launch_project_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set = false;
-    return sp_launch(k_project_split_h, a, lc, s, attr_set);
+    return launch_kernel(k_project_split_h, lc.blocks, lc.threads, lc.lds, s, a);
 }
 hipError_t launch_project_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    static bool attr_set = false;
-    return sp_launch(k_project_split, a, lc, s, attr_set);
+    return launch_kernel(k_project_split, lc.blocks, lc.threads, lc.lds, s, a);
 }
 
 int split_prow_block() { return MGN_PROW_BLOCK; }

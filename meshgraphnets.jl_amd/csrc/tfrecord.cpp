@@ -13,35 +13,34 @@
 
 namespace {
 
-uint32_t g_crc_table[8][256];
-bool g_crc_ready = false;
-
-void crc_init() {
-    if (g_crc_ready) return;
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : c >> 1;   // CRC-32C (Castagnoli), reflected
-        g_crc_table[0][i] = c;
+struct CrcTable {
+    uint32_t t[8][256];
+    CrcTable() {
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : c >> 1;   // CRC-32C (Castagnoli), reflected
+            t[0][i] = c;
+        }
+        for (uint32_t i = 0; i < 256; ++i)
+            for (int k = 1; k < 8; ++k) t[k][i] = (t[k - 1][i] >> 8) ^ t[0][t[k - 1][i] & 0xFF];
     }
-    for (uint32_t i = 0; i < 256; ++i)
-        for (int t = 1; t < 8; ++t) g_crc_table[t][i] = (g_crc_table[t - 1][i] >> 8) ^ g_crc_table[0][g_crc_table[t - 1][i] & 0xFF];
-    g_crc_ready = true;
-}
+};
 
 uint32_t crc32c(const uint8_t* p, size_t n) {
-    crc_init();
+    static const CrcTable table;   // built by the first caller (function-local static: thread-safe)
+    const auto& tab = table.t;
     uint32_t c = 0xFFFFFFFFu;
     while (n >= 8) {   // slicing-by-8
         uint32_t lo, hi;
         memcpy(&lo, p, 4);
         memcpy(&hi, p + 4, 4);
         lo ^= c;
-        c = g_crc_table[7][lo & 0xFF] ^ g_crc_table[6][(lo >> 8) & 0xFF] ^ g_crc_table[5][(lo >> 16) & 0xFF] ^ g_crc_table[4][lo >> 24] ^
-            g_crc_table[3][hi & 0xFF] ^ g_crc_table[2][(hi >> 8) & 0xFF] ^ g_crc_table[1][(hi >> 16) & 0xFF] ^ g_crc_table[0][hi >> 24];
+        c = tab[7][lo & 0xFF] ^ tab[6][(lo >> 8) & 0xFF] ^ tab[5][(lo >> 16) & 0xFF] ^ tab[4][lo >> 24] ^
+            tab[3][hi & 0xFF] ^ tab[2][(hi >> 8) & 0xFF] ^ tab[1][(hi >> 16) & 0xFF] ^ tab[0][hi >> 24];
         p += 8;
         n -= 8;
     }
-    while (n--) c = (c >> 8) ^ g_crc_table[0][(c ^ *p++) & 0xFF];
+    while (n--) c = (c >> 8) ^ tab[0][(c ^ *p++) & 0xFF];
     return c ^ 0xFFFFFFFFu;
 }
 

@@ -7,14 +7,10 @@
 #include "train.h"
 #include "kernels.h"
 
-#include <atomic>
-#include <cstdlib>
-#include <mutex>
-#include <unordered_map>
-
 #include "frag.hpp"
 #include "tile_common.hpp"
 #include "split_common.hpp"
+#include "launch.hpp"
 
 namespace mgn {
 
@@ -1575,24 +1571,12 @@ __global__ __launch_bounds__(256) void k_norms_from_totals(const NormsFromTotals
 // ================================================================================================
 // launch wrappers
 // ================================================================================================
-// 4 tiles per block; two L x L chunk buffers of dynamic LDS (128 KiB at L = 128: the attribute is raised once per kernel)
+// 4 tiles per block; two L x L chunk buffers of dynamic LDS (128 KiB at L = 128: launch.hpp raises the grant)
 template <typename K, typename A>
 static hipError_t launch_tiles(K kern, const A& a, int ntiles, int L, hipStream_t s, int wpb = 4, size_t extra_lds = 0) {
     if (ntiles <= 0) return hipSuccess;
     const size_t lds = (size_t)2 * L * L * sizeof(float) + extra_lds;
-    static std::mutex mu;
-    static std::unordered_map<const void*, size_t> granted;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        size_t& g = granted[reinterpret_cast<const void*>(kern)];
-        if (lds > 48 * 1024 && g < lds) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            g = lds;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((ntiles + wpb - 1) / wpb)), dim3(64 * wpb), lds, s, a);
-    return hipGetLastError();
+    return launch_kernel(kern, (unsigned)((ntiles + wpb - 1) / wpb), 64 * wpb, lds, s, a);
 }
 
 // The size rules of the training step are written for 256 CUs, on every device: cooperative tiles up to per_cu * 256 tiles, eight-tile
@@ -1619,7 +1603,7 @@ void train_regime_counts(int* out /* [12] */, bool reset) {
 
 // eight tiles per block once a launch fills the chip twice over with four (L = 128; MGN_TRAIN_WPB = 4 / 8 forces)
 static bool train_wpb8(int L, int ntiles) {
-    static const int forced = [] { const char* e = getenv("MGN_TRAIN_WPB"); return e ? atoi(e) : 0; }();
+    static const int forced = env_int("MGN_TRAIN_WPB", 0);
     if (L != 128) return false;
     if (forced) return forced == 8;
     return ntiles > 8 * train_size_cus();
@@ -1627,7 +1611,7 @@ static bool train_wpb8(int L, int ntiles) {
 
 // Cooperative tiles while a launch has fewer than MGN_TRAIN_COOP_TILES_PER_CU tiles per CU (default 8), L = 128.
 static bool train_coop(int L, int ntiles) {
-    static const int per_cu = [] { const char* e = getenv("MGN_TRAIN_COOP_TILES_PER_CU"); return e ? atoi(e) : 8; }();
+    static const int per_cu = env_int("MGN_TRAIN_COOP_TILES_PER_CU", 8);
     return L == 128 && ntiles > 0 && ntiles <= per_cu * train_size_cus();
 }
 template <typename K, typename A>
@@ -1638,7 +1622,7 @@ static hipError_t launch_coop(K kern, const A& a, int ntiles, hipStream_t s) {
 
 bool train_uses_coop(int L, int ntiles) { return train_coop(L, ntiles); }
 bool train_fwd_fused_agg(int L, int ntiles) {
-    static const int on = [] { const char* e = getenv("MGN_TRAIN_FUSED_AGG"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("MGN_TRAIN_FUSED_AGG", 1);
     return on && L == 128 && !train_coop(L, ntiles) && train_wpb8(L, ntiles);
 }
 hipError_t launch_seg_fixup(int L, const int32_t* rowptr, const float* carry, float* agg, int32_t n, hipStream_t s) {
@@ -1648,8 +1632,8 @@ hipError_t launch_seg_fixup(int L, const int32_t* rowptr, const float* carry, fl
     return hipGetLastError();
 }
 // the streaming kernels at L = 128 compute on two fp16 pieces per operand, three piece products (train_chunk); MGN_TRAIN_F16=0: fp32 MFMA
-static int g_train_f16 = [] { const char* e = getenv("MGN_TRAIN_F16"); return e ? atoi(e) : 1; }();
-int set_train_f16(int on) { const int old = g_train_f16; g_train_f16 = on; return old; }
+static Switch g_train_f16{"MGN_TRAIN_F16", 1};
+int set_train_f16(int on) { return g_train_f16.set(on); }
 
 hipError_t launch_lin2(int L, const Lin2Args& a, hipStream_t s) {
     if (a.ntiles > 0) count_launch(2, train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
@@ -1734,27 +1718,22 @@ hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s) 
 int64_t wgrad_rows_per_block(int64_t rows) {
     // (A/B on the cylinder mesh, k_wgrad_lds: 64 / 128 rows 3.13 / 3.11 ms per step, 256: 3.68, 512: 4.90 -- a block's row loop is a latency chain;
     // round 6, k_wgrad_h2 (two blocks per CU): 128 / 160 / 192 / 224 / 256 / 384 rows 2.45 / 2.39 / 2.38 / 2.43 / 2.53 / 2.90 ms, k_wgrad_lds 2.44 at 128, 2.48 at 192)
-    static const int min_rows = [] {
-        const char* e = getenv("MGN_WG_MIN_ROWS");
-        if (e) return atoi(e);
-        const char* h = getenv("MGN_WGRAD_H2");
-        return (h && atoi(h) == 0) ? WG_ROWS : 192;
-    }();
+    static const int min_rows = env_int("MGN_WG_MIN_ROWS", env_int("MGN_WGRAD_H2", 1) == 0 ? WG_ROWS : 192);
     const int64_t cap = 4 * train_size_cus();        // at most 1024 blocks (4 per CU of the size rules' 256)
     int64_t rpb = (rows + cap - 1) / cap;
     if (rpb < min_rows) rpb = min_rows;
     return (rpb + 2 * WG_UNROLL - 1) / (2 * WG_UNROLL) * (2 * WG_UNROLL);
 }
 static bool wgrad_h2_on(int L) {
-    static const int h2 = [] { const char* e = getenv("MGN_WGRAD_H2"); return e ? atoi(e) : 1; }();      // 0: the fp32 MFMA forms
+    static const int h2 = env_int("MGN_WGRAD_H2", 1);      // 0: the fp32 MFMA forms
     return L == 128 && h2 && g_train_f16;
 }
 bool train_bwd_fused_sgr(int L, int ntiles) {
-    static const int on = [] { const char* e = getenv("MGN_TRAIN_FUSED_SGR"); return e ? atoi(e) : 0; }();   // (built, parity green, same box 0.304 s against 0.302 with k_segment_sum_pair: off)
+    static const int on = env_int("MGN_TRAIN_FUSED_SGR", 0);   // (built, parity green, same box 0.304 s against 0.302 with k_segment_sum_pair: off)
     return on && L == 128 && !train_coop(L, ntiles) && train_wpb8(L, ntiles);
 }
 bool train_bwd_ln_sums(int L, int ntiles) {
-    static const int on = [] { const char* e = getenv("MGN_TRAIN_BWD_LN_SUMS"); return e ? atoi(e) : 1; }();   // LayerNorm-parameter sums inside the streaming backward kernel (0: the LayerNorm job of the weight-gradient launch)
+    static const int on = env_int("MGN_TRAIN_BWD_LN_SUMS", 1);   // LayerNorm-parameter sums inside the streaming backward kernel (0: the LayerNorm job of the weight-gradient launch)
     return on && L == 128 && !train_coop(L, ntiles) && train_wpb8(L, ntiles);
 }
 hipError_t launch_colsum_groups(const float* part, int nblocks, int cols, int groups, float* out, hipStream_t s) {
@@ -1763,7 +1742,7 @@ hipError_t launch_colsum_groups(const float* part, int nblocks, int cols, int gr
     return hipGetLastError();
 }
 bool wgrad_ln_jobs(int L) {
-    static const int on = [] { const char* e = getenv("MGN_WGRAD_LN_JOBS"); return e ? atoi(e) : 1; }();  // 0: GT / G xhat rows written by the backward kernel, two column-sum jobs
+    static const int on = env_int("MGN_WGRAD_LN_JOBS", 1);  // 0: GT / G xhat rows written by the backward kernel, two column-sum jobs
     return on && wgrad_h2_on(L);
 }
 int wgrad_blocks_of_job(int64_t launch_rows, int64_t job_rows) {
@@ -1918,12 +1897,9 @@ hipError_t launch_wgrad(int L, WgradBatch wb, int64_t rows, hipStream_t s) {
     if (nb == 0 || wb.njobs <= 0) return hipSuccess;
     wb.rows_per_block = wgrad_rows_per_block(rows);
     const dim3 grid(nb, wb.njobs);
-    static const int lds = [] { const char* e = getenv("MGN_WGRAD_LDS"); return e ? atoi(e) : 1; }();   // 0: k_wgrad<4> (4-byte operand loads)
-    if (wgrad_h2_on(L)) {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_h2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WH_LDS);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(k_wgrad_h2, grid, dim3(256), WH_LDS, s, wb);
-    } else if (L == 128 && lds) hipLaunchKernelGGL(k_wgrad_lds, grid, dim3(256), 0, s, wb);
+    static const int lds = env_int("MGN_WGRAD_LDS", 1);   // 0: k_wgrad<4> (4-byte operand loads)
+    if (wgrad_h2_on(L)) return launch_kernel(k_wgrad_h2, grid, 256, WH_LDS, s, wb);
+    if (L == 128 && lds) hipLaunchKernelGGL(k_wgrad_lds, grid, dim3(256), 0, s, wb);
     else if (L == 128) hipLaunchKernelGGL(k_wgrad<4>, grid, dim3(256), 0, s, wb);
     else if (L == 64) hipLaunchKernelGGL(k_wgrad<2>, grid, dim3(128), 0, s, wb);
     else if (L == 32) hipLaunchKernelGGL(k_wgrad<1>, grid, dim3(64), 0, s, wb);

@@ -377,6 +377,17 @@ def test_c_abi_from_plain_c(lib_built, tmp_path):
     assert out.returncode == 0 and "abi_check OK" in out.stdout, out.stdout + out.stderr
 
 
+def test_launch_state_under_eight_threads(tmp_path):
+    """csrc/launch.hpp's plain C++ part (switches, per-device LDS grants, per-device CU cache) and tfrecord.cpp's CRC table hold under
+    eight threads: tests/c_abi/launch_state.cpp, a stand-alone program that needs neither HIP nor the library."""
+    import subprocess
+    src = os.path.join(ROOT, "tests", "c_abi", "launch_state.cpp")
+    exe = str(tmp_path / "launch_state")
+    subprocess.check_call(["g++", "-std=c++17", "-pthread", src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "launch_state OK" in out.stdout, out.stdout + out.stderr
+
+
 def test_integration_doc_names_every_symbol(lib_built):
     """INTEGRATION.md maps every entry point of include/mgn_hip.h to the reference interface it replaces: no symbol may be
     missing from it (a slash list such as `mgn_fwd_upload/encode/decode` counts)."""
