@@ -435,7 +435,8 @@ int mgn_step(mgn_handle* h, const float* nf, const float* ef, const float* targe
  * copies and the noise on the device once per trajectory (add_targets! and preprocess!, src/dataset.jl:461-509) and forms
  * o_norm((next - cur) / dt) and build_graph there once per datapoint (init_train_step of the derivative strategies,
  * src/strategies.jl:395-416); these entry points do the same.  Optimisers.update and the order in which datapoints are visited
- * stay with the caller.  fp32, one partition (MGN_E_STATE otherwise); every array may be a host or a device pointer unless noted.
+ * stay with the caller.  fp32 (MGN_E_STATE otherwise); every array may be a host or a device pointer unless noted.  One partition,
+ * or a partitioned mesh after mgn_comm_init: "On a partitioned mesh" below.
  *
  * mgn_train_set_trajectory, once per trajectory and after the graph is complete (mgn_set_graph, and mgn_set_edge_set where there
  * is a second set): frames [T][N][O] holds frame t = data[field][:, :, t] of the target fields, concatenated in output order, in
@@ -487,8 +488,29 @@ int mgn_step(mgn_handle* h, const float* nf, const float* ef, const float* targe
  * mgn_datapoint_export returns, in the caller's order, what the step consumes (normalised != 0: nf, ef, target as above, unpadded)
  * or the raw arrays (normalised == 0: [cur_t ; onehot], ef_raw and d).  Any output may be NULL.  It never accumulates.
  *
+ * On a partitioned mesh (nranks > 1, after mgn_comm_init; one edge set, MGN_E_UNSUPPORTED with two) all six calls follow the
+ * nranks > 1 contract of mgn_step: every rank is given the same arrays of the WHOLE mesh -- frames [T][N][O], node_type_onehot, ef_raw
+ * [E][Fe], noisy [N], mask with the caller's node ids -- and the same arguments, and every rank gets the complete gradient and the loss,
+ * the same bits on every rank.  A rank keeps on the device only the rows of the nodes it owns ([T][n_own][O], [n_own][Fn - O]) and of
+ * its local edges, in the engine's order; the mesh's arrays pass through a staging buffer that does not grow with T (a whole number
+ * of frames, at least one, at a time; the one-hot rows; the edge features).  The noise key is (seed, row t N + n, column o) with N and
+ * n of the whole mesh: the noisy state of a node is the same bits for every number of ranks and every partition.
+ * mgn_step_datapoint is mgn_step's partitioned path on the rank's rows (eager; forward and reverse halo exchange, rank-ordered finish);
+ * every argument check precedes the first collective, so a refused call leaves no rank waiting.
+ * Online normalisers: an accumulating step forms each rank's column sums and sums of squares of the cur_t and d rows it owns (block
+ * partials added in block order), one allgather on the handle's stream brings the 4 O doubles of every rank to every rank, and the
+ * ranks' parts are added to the totals in ASCENDING RANK ORDER in double.  Totals and maps are the same bits on every rank and
+ * repeatable for a given partition; they agree with the single-partition totals up to double rounding, NOT bitwise (other partial
+ * sums).  The sums of ef_raw are formed the same way once per trajectory (every edge lives on one rank).  count advances by N and E of
+ * the whole mesh; whether a group accumulates depends only on arguments and counters all ranks share, so every rank -- one that owns
+ * no edge, too -- joins every allgather.  No host copy and no synchronisation per step.  mgn_train_norm_state reads the totals of
+ * the rank asked (all ranks hold the same); a restore must be given the same values on every rank.
+ * mgn_datapoint_export on a partitioned handle takes HOST arrays of the whole mesh's shapes and writes the rows of the nodes this
+ * rank owns and of its local edges (mgn_owned_nodes, mgn_local_edges), leaving the others untouched, as mgn_fwd_download does; it
+ * joins no collective, so one rank may call it alone.
+ *
  * Refusals, all before any launch, the handle stays usable: MGN_E_STATE without a graph, without a trajectory (step, export), on
- * a partitioned handle or with dtype != MGN_F32; MGN_E_ARG for T < 2, a datapoint outside [0, T - 2], Fn < O, a missing onehot
+ * a partitioned handle without a communicator (call mgn_comm_init) or with dtype != MGN_F32; MGN_E_ARG for T < 2, a datapoint outside [0, T - 2], Fn < O, a missing onehot
  * when Fn > O, a missing ef_raw with E > 0, a zero time step (checked on the host at upload), max_accumulations <= 0 or
  * std_epsilon <= 0, a group outside 0 .. 2, and what mgn_step refuses in its own arguments.                                   */
 int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int32_t T, const float* times, float dt,
@@ -568,7 +590,11 @@ int mgn_halo_exchange_host(mgn_handle* h, const float* own_rows, float* halo_row
  * of them and returns MGN_OK or the status of the rank that failed FIRST, with that rank's text behind "rank k: " in
  * mgn_group_last_error.  Inputs are host pointers that every rank reads in place (the nranks > 1 contract: GLOBAL arrays in, the
  * complete result on every rank).  Rank 0 writes the caller's output buffers (out, dxdt, d->out and d's counters, grads, *loss); the
- * other ranks write scratch the group owns.  grads of mgn_group_step may also be device memory of devices[0].
+ * other ranks write scratch the group owns.  grads of mgn_group_step and mgn_group_step_datapoint may also be device memory of devices[0].
+ * The datapoint family (mgn_group_train_*, mgn_group_step_datapoint, mgn_group_datapoint_export) is the partitioned form of the calls of
+ * the same names: mgn_group_train_norm_state reads rank 0's totals (all ranks hold the same bits) and restores the given ones on every
+ * rank; for mgn_group_datapoint_export every rank writes its own, disjoint rows straight into the caller's host arrays, which come
+ * back complete.
  * mgn_group_latents_checksum adds the ranks' sums in ascending rank order.
  * A rank that fails while its peers are inside a collective does not cost them MGN_COMM_TIMEOUT_S: the group raises the communicator's
  * abort flag the moment a rank returns an error, the peers leave with MGN_E_RCCL, and before the call returns the group replaces the
@@ -594,6 +620,14 @@ int mgn_group_ode_step(mgn_group* g, const float* x, const float* node_type_oneh
 int mgn_group_rollout(mgn_group* g, mgn_rollout_desc* d);
 int mgn_group_step(mgn_group* g, const float* nf, const float* ef, const float* target, const int32_t* mask, int64_t nmask,
                    int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
+int mgn_group_train_set_trajectory(mgn_group* g, const float* frames, int32_t T, const float* times, float dt,
+                                   const float* node_type_onehot, const float* ef_raw);
+int mgn_group_train_set_noise(mgn_group* g, const float* stddev, const uint8_t* noisy, uint64_t seed);
+int mgn_group_train_online_norms(mgn_group* g, int32_t node_on, int32_t edge_on, int32_t out_on, double max_accumulations, float std_epsilon);
+int mgn_group_train_norm_state(mgn_group* g, int32_t group, int32_t write, double* sum, double* sum_squares, double* count_and_calls);
+int mgn_group_step_datapoint(mgn_group* g, int32_t datapoint, int32_t accumulate, const int32_t* mask, int64_t nmask,
+                             int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
+int mgn_group_datapoint_export(mgn_group* g, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target);
 int mgn_group_latents_randn(mgn_group* g, uint64_t seed);
 int mgn_group_processor_steps_dev(mgn_group* g, int32_t nsteps);
 int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, double* sumsq_v, double* sumsq_e);

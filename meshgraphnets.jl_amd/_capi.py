@@ -155,6 +155,12 @@ PROTOTYPES = {
     "mgn_group_ode_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "mgn_group_rollout": (C.c_int, [_H, C.POINTER(MgnRolloutDesc)]),
     "mgn_group_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
+    "mgn_group_train_set_trajectory": (C.c_int, [_H, _f32p, C.c_int32, _f32p, C.c_float, _f32p, _f32p]),
+    "mgn_group_train_set_noise": (C.c_int, [_H, _f32p, C.POINTER(C.c_uint8), C.c_uint64]),
+    "mgn_group_train_online_norms": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_float]),
+    "mgn_group_train_norm_state": (C.c_int, [_H, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
+    "mgn_group_step_datapoint": (C.c_int, [_H, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
+    "mgn_group_datapoint_export": (C.c_int, [_H, C.c_int32, C.c_int32, _f32p, _f32p, _f32p]),
     "mgn_group_latents_randn": (C.c_int, [_H, C.c_uint64]),
     "mgn_group_processor_steps_dev": (C.c_int, [_H, C.c_int32]),
     "mgn_group_latents_checksum": (C.c_int, [_H, _f64p, _f64p, _f64p, _f64p]),

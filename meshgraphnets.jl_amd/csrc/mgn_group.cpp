@@ -268,6 +268,51 @@ int mgn_group_step(mgn_group* g, const float* nf, const float* ef, const float* 
     } GROUP_CATCH(g)
 }
 
+// The datapoint family: the same call on every rank (the nranks > 1 contract of mgn_step_datapoint; a group of one is the plain handle).
+int mgn_group_train_set_trajectory(mgn_group* g, const float* frames, int32_t T, const float* times, float dt, const float* node_type_onehot,
+                                   const float* ef_raw) {
+    GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_train_set_trajectory(h, frames, T, times, dt, node_type_onehot, ef_raw); }); } GROUP_CATCH(g)
+}
+
+int mgn_group_train_set_noise(mgn_group* g, const float* stddev, const uint8_t* noisy, uint64_t seed) {
+    GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_train_set_noise(h, stddev, noisy, seed); }); } GROUP_CATCH(g)
+}
+
+int mgn_group_train_online_norms(mgn_group* g, int32_t node_on, int32_t edge_on, int32_t out_on, double max_accumulations, float std_epsilon) {
+    GROUP_TRY(g) {
+        return g->run([&](int, mgn_handle* h) { return mgn_train_online_norms(h, node_on, edge_on, out_on, max_accumulations, std_epsilon); });
+    } GROUP_CATCH(g)
+}
+
+// read: rank 0's totals (every rank holds the same bits); write: the same values on every rank
+int mgn_group_train_norm_state(mgn_group* g, int32_t group, int32_t write, double* sum, double* sum_squares, double* count_and_calls) {
+    GROUP_TRY(g) {
+        const size_t dim = group == 1 ? (size_t)g->cfg.Fe : (size_t)g->cfg.O;
+        std::vector<double> sink((size_t)g->P * (2 * dim + 2), 0.0);       // what the ranks other than 0 read
+        return g->run([&](int k, mgn_handle* h) {
+            if (write || k == 0) return mgn_train_norm_state(h, group, write, sum, sum_squares, count_and_calls);
+            double* s = sink.data() + (size_t)k * (2 * dim + 2);
+            return mgn_train_norm_state(h, group, 0, s, s + dim, s + 2 * dim);
+        });
+    } GROUP_CATCH(g)
+}
+
+int mgn_group_step_datapoint(mgn_group* g, int32_t datapoint, int32_t accumulate, const int32_t* mask, int64_t nmask, int32_t mask_index_base,
+                             float* grads, size_t n_grads, float* loss) {
+    GROUP_TRY(g) {
+        std::vector<float> losses(g->P, 0.f);
+        return g->run([&](int k, mgn_handle* h) {
+            return mgn_step_datapoint(h, datapoint, accumulate, mask, nmask, mask_index_base, g->out_of(k, grads, n_grads), n_grads,
+                                      k == 0 || !loss ? loss : &losses[k]);
+        });
+    } GROUP_CATCH(g)
+}
+
+// every rank writes the rows of its own nodes and edges into the caller's arrays: disjoint rows, complete arrays
+int mgn_group_datapoint_export(mgn_group* g, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target) {
+    GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_datapoint_export(h, datapoint, normalised, nf, ef, target); }); } GROUP_CATCH(g)
+}
+
 int mgn_group_latents_randn(mgn_group* g, uint64_t seed) {
     GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_latents_randn(h, seed); }); } GROUP_CATCH(g)
 }

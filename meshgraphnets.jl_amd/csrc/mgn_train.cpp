@@ -129,6 +129,7 @@ struct TrainState {
         bool have = false;
         int32_t T = 0;
         DevBuf frames, onehot, ef_raw;   // [T][N][O], [N][Fn - O] in the engine's node order; [E][Fe] in the caller's edge order (as ef_pad holds it)
+                                         // A partition keeps the rows it owns: N = n_own, and its e_local edges in the ENGINE's order (as its ef_pad holds them)
         std::vector<float> delta;        // [T - 1]: dt, or times[t + 1] - times[t]
         bool noise = false, some_nodes = false;
         DevBuf stddev, noisy;            // [O]; [N] 0/1 in the engine's order (some_nodes)
@@ -136,11 +137,12 @@ struct TrainState {
         bool ef_pad_ok = false;          // the arena's ef_pad[0] holds this trajectory's edge features under the norms as they stand
         bool ef_sums_ok = false;         // ef_sums holds ef_raw's column sums
         DevBuf ef_sums;                  // [2][Fe] doubles: what one accumulation of ef_raw adds (mgn_feature_stats' sums, formed once)
-        DevBuf work;                     // accumulating steps: cur and d [N][O] each in the caller's order, then launch_col_stats' partials of both
+        DevBuf work;                     // accumulating steps: cur and d [N][O] each in the caller's order (a partition: its rows, the engine's order), then launch_col_stats' partials of both
+        DevBuf xsum;                     // a partition's sums on their way to the peers: this rank's [cur | d] ([2][O] each) and its ef_raw's [2][Fe], then every rank's of either
         void drop() {
             have = false; T = 0; noise = some_nodes = false; ef_pad_ok = ef_sums_ok = false;
             delta.clear();
-            for (DevBuf* b : {&frames, &onehot, &ef_raw, &stddev, &noisy, &ef_sums, &work}) b->release();
+            for (DevBuf* b : {&frames, &onehot, &ef_raw, &stddev, &noisy, &ef_sums, &work, &xsum}) b->release();
         }
     } traj;
     // The online normalisers (GraphNetCore NormaliserOnline) of mgn_train_online_norms: group 0 the node state columns, 1 the edge
@@ -618,12 +620,13 @@ DatapointArgs datapoint_args(mgn_engine* h, int32_t t, bool normalised) {
     a.cur = R.frames.as<float>() + (size_t)t * (size_t)N * c.O;       // (64-bit: T N O passes 2^31 on the largest meshes)
     a.nxt = a.cur + (size_t)N * c.O;
     a.onehot = c.Fn > c.O ? R.onehot.as<float>() : nullptr;
-    a.gid = h->g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+    a.gid = h->g.renumbered || c.nranks > 1 ? h->d_own_gid.as<int32_t>() : nullptr;   // (a partition's rows are the nodes it owns)
     a.noisy = R.noise && R.some_nodes ? R.noisy.as<uint8_t>() : nullptr;
     a.stddev = R.noise ? R.stddev.as<float>() : nullptr;
     a.nrm_n = normalised && h->have_nnorm ? nrm : nullptr;
     a.nrm_o = normalised && h->have_onorm ? nrm + 2 * c.Fn + 2 * c.Fe : nullptr;
     a.N = N; a.O = c.O; a.Fn = c.Fn; a.ld = c.Fn; a.t = t;
+    a.Nkey = c.nranks > 1 ? h->g.N : N;               // the noise is keyed by the caller's node id among all nodes of the mesh
     a.delta = R.delta[(size_t)t];
     a.seed = R.seed;
     return a;
@@ -631,22 +634,37 @@ DatapointArgs datapoint_args(mgn_engine* h, int32_t t, bool normalised) {
 // The normaliser call of the reference accumulates, then normalises: an accumulating step adds the datapoint's raw rows (cur, ef_raw, d)
 // to the totals of every online group that still accumulates and rewrites that group's entries of h->norms, all on the device; restored
 // totals (mgn_train_norm_state) get their maps here as well.  No copy to the host, no synchronisation; count and calls are host numbers.
+// A partition (nranks > 1) forms the sums of the rows it owns -- every node and every edge lives on exactly one rank --, folds its
+// block partials in block order, and one allgather on the handle's stream brings every rank's sums to every rank; they are added to
+// the totals in ascending rank order, so totals and maps are the same bits on all ranks.  Whether a group accumulates is decided
+// from the mesh's counts and from host state that all ranks share, never from what this rank owns: every rank joins every allgather.
 int datapoint_norms(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
     if (int rc = datapoint_norms_ready(h)) return rc;
     TrainState& T = *h->train;
     TrainState::Trajectory& R = T.traj;
     const mgn_config& c = h->cfg;
+    const bool multi = c.nranks > 1;
+    const int P = c.nranks;
     const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    const int64_t NG = multi ? h->g.N : N, EG = multi ? h->g.set[0].E : E;    // rows of the whole mesh
+    // this rank's sums and all ranks' (doubles): [cur sum, sum of squares | d ...] = 4 O per rank, then the edge features' 2 Fe per rank
+    const size_t xs_n = (size_t)4 * c.O, xs_e = (size_t)2 * c.Fe;
+    auto comm_fail = [&](const char* what) { return fail(h, MGN_E_RCCL, "mgn_step_datapoint: %s: %s", what, h->comm->err.c_str()); };
     bool add[3], write[3], any = false;
     for (int g = 0; g < 3; ++g) {
-        const int64_t rows = g == 1 ? E : N;
+        const int64_t rows = g == 1 ? EG : NG;
         add[g] = accumulate && T.on[g].online && T.on[g].calls < T.on[g].max_acc && rows > 0;
         write[g] = T.on[g].online && (add[g] || T.on[g].dirty);
         any = any || write[g];
     }
     if (!any) return MGN_OK;
     if (int rc = online_totals_ready(h)) return rc;
-    const int nb = stats_blocks(N);
+    if (multi && !R.xsum.p) HIPCHK(h, R.xsum.ensure((size_t)(P + 1) * (xs_n + xs_e) * sizeof(double)));
+    double* const xs = multi ? R.xsum.as<double>() : nullptr;
+    double* const xs_all_n = multi ? xs + xs_n + xs_e : nullptr;
+    double* const xs_all_e = multi ? xs_all_n + (size_t)P * xs_n : nullptr;
+    int nb = stats_blocks(N);
+    int pstride = 0;
     const double *p0 = nullptr, *p2 = nullptr;
     if (add[0] || add[2]) {
         const size_t rawf = ((size_t)N * c.O + 63) / 64 * 64, partd = (size_t)nb * 2 * c.O;
@@ -655,21 +673,39 @@ int datapoint_norms(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
         float* rd = rcur + rawf;
         double* part = reinterpret_cast<double*>(rd + rawf);
         DatapointArgs a = datapoint_args(h, t, false);
-        a.ld = c.O; a.raw_cur = rcur; a.raw_d = rd;
+        a.ld = c.O; a.raw_cur = rcur; a.raw_d = rd; a.raw_local = multi ? 1 : 0;
         HIPCHK(h, launch_datapoint_assemble(a, st));
         if (add[0]) { HIPCHK(h, launch_col_stats(rcur, N, c.O, part, st)); p0 = part; }
         if (add[2]) { HIPCHK(h, launch_col_stats(rd, N, c.O, part + partd, st)); p2 = part + partd; }
+        if (multi) {                   // the owned rows' sums, folded in block order; then all ranks' sums, which the totals take in rank order
+            HIPCHK(h, hipMemsetAsync(xs, 0, xs_n * sizeof(double), st));
+            NormsFromTotalsArgs z{};
+            if (add[0]) { z.g[0].partial = p0; z.g[0].totals = xs; z.g[0].nb = nb; z.g[0].dim = c.O; z.g[0].add = 1; }
+            if (add[2]) { z.g[2].partial = p2; z.g[2].totals = xs + 2 * c.O; z.g[2].nb = nb; z.g[2].dim = c.O; z.g[2].add = 1; }
+            HIPCHK(h, launch_norms_from_totals(z, st));
+            if (h->comm->allgather(xs, xs_n * sizeof(double), xs_all_n, st) != 0) return comm_fail("allgather of the normalisers' sums");
+            p0 = xs_all_n; p2 = xs_all_n + 2 * c.O;
+            nb = P; pstride = (int)xs_n;
+        }
     }
     if (add[1] && !R.ef_sums_ok) {     // what one accumulation of ef_raw adds: the same terms in the same order, formed once per trajectory
         const int nbe = stats_blocks(E);
         const size_t head = (size_t)2 * c.Fe * sizeof(double);
         HIPCHK(h, R.ef_sums.ensure(head + (size_t)nbe * head));
         double* sums = R.ef_sums.as<double>();
-        HIPCHK(h, hipMemsetAsync(sums, 0, head, st));
+        double* own = multi ? xs + xs_n : sums;            // (a partition: its local edges' sums first, the mesh's from all ranks' below)
+        HIPCHK(h, hipMemsetAsync(own, 0, head, st));
         HIPCHK(h, launch_col_stats(R.ef_raw.as<float>(), E, c.Fe, sums + 2 * c.Fe, st));
         NormsFromTotalsArgs z{};
-        z.g[0].partial = sums + 2 * c.Fe; z.g[0].totals = sums; z.g[0].nb = nbe; z.g[0].dim = c.Fe; z.g[0].add = 1;
+        z.g[0].partial = sums + 2 * c.Fe; z.g[0].totals = own; z.g[0].nb = nbe; z.g[0].dim = c.Fe; z.g[0].add = 1;
         HIPCHK(h, launch_norms_from_totals(z, st));
+        if (multi) {                   // (a rank without an edge sends zeros)
+            if (h->comm->allgather(own, head, xs_all_e, st) != 0) return comm_fail("allgather of the edge features' sums");
+            HIPCHK(h, hipMemsetAsync(sums, 0, head, st));
+            NormsFromTotalsArgs y{};
+            y.g[0].partial = xs_all_e; y.g[0].totals = sums; y.g[0].nb = P; y.g[0].dim = c.Fe; y.g[0].add = 1;
+            HIPCHK(h, launch_norms_from_totals(y, st));
+        }
         R.ef_sums_ok = true;
     }
     float* nrm = h->norms.as<float>();
@@ -679,13 +715,13 @@ int datapoint_norms(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
     for (int g = 0; g < 3; ++g) {
         if (!write[g]) continue;
         TrainState::OnlineGroup& o = T.on[g];
-        if (add[g]) { o.count += (double)(g == 1 ? E : N); o.calls += 1.0; }
+        if (add[g]) { o.count += (double)(g == 1 ? EG : NG); o.calls += 1.0; }
         NormGroupArgs& q = a.g[g];
         q.partial = g == 0 ? p0 : (g == 2 ? p2 : nullptr);
         q.call_sums = g == 1 ? R.ef_sums.as<double>() : nullptr;
         q.totals = T.on_totals.as<double>() + online_off(c, g);
         q.scale = scale[g]; q.shift = scale[g] + stride[g];
-        q.count = o.count; q.eps = o.eps; q.nb = nb; q.dim = online_dim(c, g);
+        q.count = o.count; q.eps = o.eps; q.nb = nb; q.pstride = pstride; q.dim = online_dim(c, g);
         q.add = add[g] ? 1 : 0; q.write = 1; q.inverse = g == 2 ? 1 : 0;
         o.dirty = false;
     }
@@ -715,7 +751,9 @@ int datapoint_stage(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
 // what every entry point of the datapoint family asks of the handle before it looks at its arguments
 int datapoint_need(mgn_handle* h, const char* who, bool graph, bool trajectory) {
     if (int rc = need(h, false, graph)) return rc;
-    if (h->cfg.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (h->cfg.nranks != 1 && h->nsets != 1) return fail(h, MGN_E_UNSUPPORTED, "%s on a partitioned mesh takes one edge set", who);
+    if (h->cfg.nranks != 1 && !h->comm)
+        return fail(h, MGN_E_STATE, "%s with nranks = %d needs a communicator: call mgn_comm_init on every rank first", who, h->cfg.nranks);
     if (h->cfg.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
     if (trajectory && (!h->train || !h->train->traj.have))
         return fail(h, MGN_E_STATE, "%s: no trajectory: call mgn_train_set_trajectory after mgn_set_graph (a new graph drops it)", who);
@@ -1509,11 +1547,12 @@ extern "C" int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int3
     if (!h) return MGN_E_ARG;
     if (int rc = datapoint_need(h, who, true, false)) return rc;
     const mgn_config& c = h->cfg;
-    const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    const bool part = c.nranks > 1;    // every rank is given the arrays of the whole mesh and keeps the rows it owns
+    const int64_t N = h->g.n_own, E = h->g.set[0].e_local, NG = part ? h->g.N : N, EG = part ? h->g.set[0].E : E;
     if (!frames) return fail(h, MGN_E_ARG, "%s: null argument", who);
     if (T_ < 2) return fail(h, MGN_E_ARG, "%s: a trajectory has at least two frames, got %d", who, (int)T_);
     if (c.Fn < c.O) return fail(h, MGN_E_ARG, "%s: Fn < O", who);
-    if ((c.Fn > c.O && !node_type_onehot) || (!ef_raw && E > 0)) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if ((c.Fn > c.O && !node_type_onehot) || (!ef_raw && EG > 0)) return fail(h, MGN_E_ARG, "%s: null argument", who);
     std::vector<float> delta((size_t)T_ - 1, dt);
     if (times) {
         std::vector<float> tm((size_t)T_);
@@ -1529,7 +1568,36 @@ extern "C" int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int3
     HIPCHK(h, R.frames.ensure(fl * 4));
     HIPCHK(h, R.onehot.ensure(ol * 4));
     HIPCHK(h, R.ef_raw.ensure(el * 4));
-    if (h->g.renumbered) {             // into the engine's node order once, here: no gather per step
+    if (part) {
+        // The mesh's arrays pass through a staging buffer whose size does not grow with T: a whole number of frames of the mesh (at least
+        // one; MGN_TRAJ_STAGE_BYTES, 64 MB) per pass, or the one-hot rows, or the edge features.  Each pass is gathered into the rows this rank
+        // owns -- frames and one-hot rows by own_gid, the local edges by edge_gid, in the engine's order: datapoint_stage's launch_affine_pad
+        // then leaves in ef_pad what stage_features gathers out of a caller's [E][Fe] array.
+        const int32_t* gid = h->d_own_gid.as<int32_t>();
+        const size_t frame = (size_t)NG * c.O, olg = (size_t)NG * (c.Fn - c.O), elg = (size_t)EG * c.Fe;
+        const size_t budget = (size_t)std::max(4, env_int("MGN_TRAJ_STAGE_BYTES", 64 << 20)) / 4;   // floats
+        const int64_t per = std::max<int64_t>(1, std::min<int64_t>(T_, frame ? (int64_t)(budget / frame) : T_));
+        std::vector<int32_t> egid((size_t)E);
+        for (int64_t i = 0; i < E; ++i) egid[(size_t)i] = (int32_t)h->g.set[0].edge_gid[(size_t)i];
+        HIPCHK(h, h->stage.ensure((std::max({(size_t)per * frame, olg, elg}) + (size_t)E) * 4));
+        float* stg = h->stage.as<float>();
+        int32_t* d_egid = reinterpret_cast<int32_t*>(stg + std::max({(size_t)per * frame, olg, elg}));
+        for (int64_t f0 = 0; f0 < T_; f0 += per) {
+            const int64_t nf = std::min<int64_t>(per, T_ - f0);
+            HIPCHK(h, hipMemcpyAsync(stg, frames + (size_t)f0 * frame, (size_t)nf * frame * 4, hipMemcpyDefault, st));
+            for (int64_t j = 0; j < nf; ++j)
+                HIPCHK(h, launch_permute_rows(R.frames.as<float>() + (size_t)(f0 + j) * (size_t)N * c.O, stg + (size_t)j * frame, gid, N, c.O, false, st));
+        }
+        if (ol) {
+            HIPCHK(h, hipMemcpyAsync(stg, node_type_onehot, olg * 4, hipMemcpyDefault, st));
+            HIPCHK(h, launch_permute_rows(R.onehot.as<float>(), stg, gid, N, c.Fn - c.O, false, st));
+        }
+        if (el) {
+            HIPCHK(h, hipMemcpyAsync(d_egid, egid.data(), (size_t)E * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(stg, ef_raw, elg * 4, hipMemcpyDefault, st));
+            HIPCHK(h, launch_affine_pad_gather(stg, c.Fe, nullptr, 0, nullptr, nullptr, d_egid, R.ef_raw.as<float>(), c.Fe, E, st));
+        }
+    } else if (h->g.renumbered) {      // into the engine's node order once, here: no gather per step
         const int32_t* gid = h->d_own_gid.as<int32_t>();
         HIPCHK(h, h->stage.ensure(std::max(fl, ol) * 4));
         HIPCHK(h, hipMemcpyAsync(h->stage.p, frames, fl * 4, hipMemcpyDefault, st));
@@ -1542,7 +1610,7 @@ extern "C" int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int3
         HIPCHK(h, hipMemcpyAsync(R.frames.p, frames, fl * 4, hipMemcpyDefault, st));
         if (ol) HIPCHK(h, hipMemcpyAsync(R.onehot.p, node_type_onehot, ol * 4, hipMemcpyDefault, st));
     }
-    if (el) HIPCHK(h, hipMemcpyAsync(R.ef_raw.p, ef_raw, el * 4, hipMemcpyDefault, st));   // (edge rows stay in the caller's order: the edge encoder reads them by edge_gid)
+    if (el && !part) HIPCHK(h, hipMemcpyAsync(R.ef_raw.p, ef_raw, el * 4, hipMemcpyDefault, st));   // (edge rows stay in the caller's order: the edge encoder reads them by edge_gid)
     HIPCHK(h, hipStreamSynchronize(st));
     R.T = T_;
     R.delta = std::move(delta);
@@ -1563,9 +1631,11 @@ extern "C" int mgn_train_set_noise(mgn_handle* h, const float* stddev, const uin
     HIPCHK(h, R.stddev.ensure((size_t)h->cfg.O * 4));
     HIPCHK(h, hipMemcpy(R.stddev.p, stddev, (size_t)h->cfg.O * 4, hipMemcpyDefault));
     if (noisy) {
-        std::vector<uint8_t> in((size_t)N), loc((size_t)N);
-        HIPCHK(h, hipMemcpy(in.data(), noisy, (size_t)N, hipMemcpyDefault));
-        for (int64_t i = 0; i < N; ++i) loc[(size_t)i] = in[(size_t)(h->g.renumbered ? h->g.own_gid[(size_t)i] : i)] ? 1 : 0;
+        const bool by_gid = h->g.renumbered || h->cfg.nranks > 1;     // (a partition: `noisy` covers the mesh, the rank takes its own nodes' entries)
+        const int64_t NG = h->cfg.nranks > 1 ? h->g.N : N;
+        std::vector<uint8_t> in((size_t)NG), loc((size_t)N);
+        HIPCHK(h, hipMemcpy(in.data(), noisy, (size_t)NG, hipMemcpyDefault));
+        for (int64_t i = 0; i < N; ++i) loc[(size_t)i] = in[(size_t)(by_gid ? h->g.own_gid[(size_t)i] : i)] ? 1 : 0;
         HIPCHK(h, R.noisy.ensure((size_t)N));
         HIPCHK(h, hipMemcpy(R.noisy.p, loc.data(), (size_t)N, hipMemcpyHostToDevice));
         R.some_nodes = true;
@@ -1631,11 +1701,12 @@ extern "C" int mgn_step_datapoint(mgn_handle* h, int32_t datapoint, int32_t accu
         return fail(h, MGN_E_ARG, "%s: datapoint %d outside [0, %d]", who, (int)datapoint, (int)h->train->traj.T - 2);
     if (nmask < 1) return fail(h, MGN_E_ARG, "%s: empty mask", who);
     if (mask_index_base != 0 && mask_index_base != 1) return fail(h, MGN_E_ARG, "%s: mask_index_base must be 0 or 1", who);
+    const int64_t n_nodes = h->cfg.nranks > 1 ? h->g.N : h->g.n_own;      // (a partition takes the mask of the whole mesh)
     for (int64_t i = 0; i < nmask; ++i) {
         const int64_t n = (int64_t)mask[i] - mask_index_base;
-        if (n < 0 || n >= h->g.n_own) return fail(h, MGN_E_ARG, "%s: mask entry %lld out of range", who, (long long)i);
+        if (n < 0 || n >= n_nodes) return fail(h, MGN_E_ARG, "%s: mask entry %lld out of range", who, (long long)i);
     }
-    if (int rc = train_prepare(h, who, n_grads)) return rc;
+    if (int rc = train_prepare(h, who, n_grads, true)) return rc;       // (the last check: the collectives begin behind it)
     TrainJob J;
     J.kind = JOB_DATAPOINT;
     J.datapoint = datapoint; J.accumulate = accumulate != 0;
@@ -1659,20 +1730,37 @@ extern "C" int mgn_datapoint_export(mgn_handle* h, int32_t datapoint, int32_t no
     float* snf = h->stage.as<float>();
     float* stg = snf + nfl;
     float* sef = stg + tl;
+    // A partition assembles the rows it owns in the engine's order and the host puts them at their places in the caller's arrays of the
+    // whole mesh (host arrays): rows of other ranks' nodes and edges are left as they are.  No collective.
+    const bool part = c.nranks > 1;
+    std::vector<float> hnf, htg, hef;
     if (nf || target) {
         DatapointArgs a = datapoint_args(h, datapoint, normalised != 0);
-        a.nf = nf ? snf : nullptr; a.target = target ? stg : nullptr; a.scatter = 1;
+        a.nf = nf ? snf : nullptr; a.target = target ? stg : nullptr; a.scatter = part ? 0 : 1;
         if (!nf) a.ld = c.O;
         HIPCHK(h, launch_datapoint_assemble(a, st));
-        if (nf) HIPCHK(h, hipMemcpyAsync(nf, snf, (size_t)N * c.Fn * 4, hipMemcpyDefault, st));
-        if (target) HIPCHK(h, hipMemcpyAsync(target, stg, (size_t)N * c.O * 4, hipMemcpyDefault, st));
+        if (part) {
+            if (nf) { hnf.resize((size_t)N * c.Fn); HIPCHK(h, hipMemcpyAsync(hnf.data(), snf, hnf.size() * 4, hipMemcpyDeviceToHost, st)); }
+            if (target) { htg.resize((size_t)N * c.O); HIPCHK(h, hipMemcpyAsync(htg.data(), stg, htg.size() * 4, hipMemcpyDeviceToHost, st)); }
+        } else {
+            if (nf) HIPCHK(h, hipMemcpyAsync(nf, snf, (size_t)N * c.Fn * 4, hipMemcpyDefault, st));
+            if (target) HIPCHK(h, hipMemcpyAsync(target, stg, (size_t)N * c.O * 4, hipMemcpyDefault, st));
+        }
     }
     if (ef && el) {
         const float* es = normalised && h->have_enorm ? h->norms.as<float>() + 2 * c.Fn : nullptr;
         HIPCHK(h, launch_affine_pad(R.ef_raw.as<float>(), c.Fe, nullptr, 0, es, es ? es + c.Fe : nullptr, sef, c.Fe, E, st));
-        HIPCHK(h, hipMemcpyAsync(ef, sef, el * 4, hipMemcpyDefault, st));
+        if (part) { hef.resize(el); HIPCHK(h, hipMemcpyAsync(hef.data(), sef, el * 4, hipMemcpyDeviceToHost, st)); }
+        else HIPCHK(h, hipMemcpyAsync(ef, sef, el * 4, hipMemcpyDefault, st));
     }
     HIPCHK(h, hipStreamSynchronize(st));
+    if (part) {
+        const std::vector<int32_t>& own = h->g.own_gid;
+        const std::vector<int64_t>& egid = h->g.set[0].edge_gid;
+        for (int64_t i = 0; i < N && !hnf.empty(); ++i) memcpy(nf + (size_t)own[(size_t)i] * c.Fn, hnf.data() + (size_t)i * c.Fn, (size_t)c.Fn * 4);
+        for (int64_t i = 0; i < N && !htg.empty(); ++i) memcpy(target + (size_t)own[(size_t)i] * c.O, htg.data() + (size_t)i * c.O, (size_t)c.O * 4);
+        for (int64_t i = 0; i < E && !hef.empty(); ++i) memcpy(ef + (size_t)egid[(size_t)i] * c.Fe, hef.data() + (size_t)i * c.Fe, (size_t)c.Fe * 4);
+    }
     return MGN_OK;
 } MGN_CATCH(h)
 

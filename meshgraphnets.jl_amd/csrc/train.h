@@ -168,12 +168,15 @@ hipError_t launch_col_stats(const float* x, int64_t rows, int dim, double* parti
 //   nf [N][ld] = [ [cur | onehot] * scale + shift | 0 ]  (nrm_n = [scale | shift] over Fn columns, null: as they are; k_affine_pad's expression)
 // scatter: rows of nf / target go to gid[r] (the caller's order: exports).  raw_cur / raw_d [N][O] (null: not written): cur and d in
 // the CALLER's order, what the online normalisers accumulate.  nf / target may be null.
+// A partition (mgn_step_datapoint at nranks > 1) holds the N rows it owns, gid[r] is a node id of the whole mesh: Nkey, the rows of
+// the noise generator's [T Nkey][O] array, is the mesh's node count (the noise of a node does not depend on the partition), and with
+// raw_local the raw rows stay in the engine's order (raw_cur / raw_d have N rows, not Nkey).
 struct DatapointArgs {
     const float* cur; const float* nxt; const float* onehot;
     const int32_t* gid; const uint8_t* noisy; const float* stddev;
     const float* nrm_n; const float* nrm_o;
     float* nf; float* target; float* raw_cur; float* raw_d;
-    int64_t N; int32_t O, Fn, ld, t, scatter;
+    int64_t N, Nkey; int32_t O, Fn, ld, t, scatter, raw_local;
     float delta; uint64_t seed;
 };
 hipError_t launch_datapoint_assemble(const DatapointArgs& a, hipStream_t s);
@@ -182,9 +185,11 @@ hipError_t launch_datapoint_assemble(const DatapointArgs& a, hipStream_t s);
 // block order from zero: mgn_feature_stats' result) or, partial null, call_sums [2][dim] formed that way earlier.  write: scale / shift
 // from the totals over `count` rows: mean and std in double, rounded to float, std = max(std, eps); scale = 1 / std, shift = -mean scale,
 // or with `inverse` scale = std, shift = mean.  dim = 0: nothing.
+// pstride: doubles from one block of `partial` to the next (0: 2 dim, launch_col_stats' layout).  A partitioned mesh adds the ranks'
+// sums this way -- block b is rank b's [sum | sum of squares] inside the allgathered rows, nb = nranks: ascending rank order.
 struct NormGroupArgs {
     const double* partial; const double* call_sums; double* totals; float* scale; float* shift;
-    double count; float eps; int32_t nb, dim, add, write, inverse;
+    double count; float eps; int32_t nb, dim, add, write, inverse, pstride;
 };
 struct NormsFromTotalsArgs { NormGroupArgs g[3]; };
 hipError_t launch_norms_from_totals(const NormsFromTotalsArgs& a, hipStream_t s);

@@ -1493,6 +1493,7 @@ __global__ __launch_bounds__(256) void k_datapoint_assemble(const DatapointArgs 
     const int O = a.O, W1 = a.Fn - a.O;
     const int64_t node = a.gid ? (int64_t)a.gid[r] : r;        // the caller's id of engine row r
     const int64_t ro = a.scatter ? node : r;                   // the row the results go to
+    const int64_t rr = a.raw_local ? r : node;                 // ... and the raw rows
     const bool noisy = a.stddev && (!a.noisy || a.noisy[r] != 0);
     float v[4];
 #pragma unroll
@@ -1502,10 +1503,10 @@ __global__ __launch_bounds__(256) void k_datapoint_assemble(const DatapointArgs 
         if (f < O) {
             const float clean = a.cur[r * O + f];
             float cur = clean;
-            if (noisy) cur = __fadd_rn(clean, __fmul_rn(a.stddev[f], randn_keyed(a.seed, ((uint64_t)a.t * (uint64_t)a.N + (uint64_t)node) * (uint64_t)O + (uint64_t)f)));
+            if (noisy) cur = __fadd_rn(clean, __fmul_rn(a.stddev[f], randn_keyed(a.seed, ((uint64_t)a.t * (uint64_t)a.Nkey + (uint64_t)node) * (uint64_t)O + (uint64_t)f)));
             const float d = __fdiv_rn(__fsub_rn(a.nxt[r * O + f], cur), a.delta);
             if (a.target) a.target[ro * O + f] = a.nrm_o ? __fdiv_rn(__fsub_rn(d, a.nrm_o[O + f]), a.nrm_o[f]) : d;
-            if (a.raw_cur) { a.raw_cur[node * O + f] = cur; a.raw_d[node * O + f] = d; }
+            if (a.raw_cur) { a.raw_cur[rr * O + f] = cur; a.raw_d[rr * O + f] = d; }
             x = cur;
         } else if (f < a.Fn) {
             x = a.onehot[r * W1 + (f - O)];
@@ -1536,9 +1537,10 @@ __global__ __launch_bounds__(256) void k_norms_from_totals(const NormsFromTotals
             if (g.add) {
                 double cs = 0.0, cq = 0.0;
                 if (g.partial) {
+                    const size_t ps = g.pstride > 0 ? (size_t)g.pstride : (size_t)2 * g.dim;
                     for (int b = 0; b < g.nb; ++b) {
-                        cs += g.partial[((size_t)b * 2 + 0) * g.dim + f];
-                        cq += g.partial[((size_t)b * 2 + 1) * g.dim + f];
+                        cs += g.partial[(size_t)b * ps + f];
+                        cq += g.partial[(size_t)b * ps + g.dim + f];
                     }
                 } else {
                     cs = g.call_sums[f];
@@ -2039,6 +2041,7 @@ hipError_t launch_datapoint_assemble(const DatapointArgs& a, hipStream_t s) {
     const int64_t tot = a.N * ((a.ld + 3) / 4);
     if (tot <= 0) return hipSuccess;
     if ((a.nf && a.ld < a.Fn) || a.ld < a.O || a.Fn < a.O || (a.Fn > a.O && !a.onehot) || !a.cur || !a.nxt || (a.raw_cur && !a.raw_d)) return hipErrorInvalidValue;
+    if (a.Nkey < a.N || ((a.scatter || (a.raw_cur && !a.raw_local)) && a.gid && a.Nkey != a.N)) return hipErrorInvalidValue;   // (rows scattered by gid need Nkey of them)
     hipLaunchKernelGGL(k_datapoint_assemble, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
