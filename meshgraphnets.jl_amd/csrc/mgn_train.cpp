@@ -23,8 +23,13 @@ namespace {
 //   hidden_layers = 3:  [D0, I, I] -> [D1, D2, D3]        (the first block's output is ReLU(z0): no LayerNorm, no residual)
 //   hidden_layers = 4:  [D0, D1, I] -> [D2, D3, D4]
 // One such launch unit with its device offsets (floats into TrainState::w) in training order:
-constexpr int DEFER_PB_JOBS = 12;  // column-sum slots per launch unit of the deferred reduction (a unit has at most 3 + 5 + 2)
 constexpr int LNSUM_GROUPS = 64;   // first-level groups of the in-kernel LayerNorm-parameter sums
+// What one launch unit adds to its weight-gradient launch and to the reduction behind it: dW3, dW2 and up to three blocks of dW1 (the
+// inputs of an MLP, or the e block and the two per-node blocks of a factored edge MLP), a column-sum job each for dgamma and dbeta where
+// the backward kernel wrote GT / GXH rows; the reduction adds db3, db2, db1 and the two LayerNorm sums, from jobs or from LNSUM.
+constexpr int UNIT_W_JOBS = 5;
+static_assert(WGRAD_MAX_JOBS == UNIT_W_JOBS + 2, "a weight-gradient launch holds one unit's weight jobs and its two LayerNorm column sums");
+static_assert(REDUCE_MAX_JOBS == UNIT_W_JOBS + 3 + 2, "a reduction holds one unit's weight blocks, its three biases, dgamma and dbeta");
 
 struct TrainBlock {
     int nin = 1;                 // L-wide layer-1 input blocks
@@ -72,27 +77,22 @@ struct TrainState {
     Acts a_en, a_de, a_ee[MAX_EDGE_SETS];
     std::vector<Acts> a_pe[MAX_EDGE_SETS], a_pn;
     std::vector<size_t> Ek[MAX_EDGE_SETS], Vk, agg[MAX_EDGE_SETS];
-    static constexpr int GSETS_MAX = 72;
-    static inline int GSETS = std::clamp(env_int("MGN_TRAIN_GSETS", 4), 2, GSETS_MAX);   // gradient-buffer sets: the weight gradients of unit i run beside the backward of units i+1 .. i+3
+    static constexpr int GSETS = 4;   // gradient-buffer sets: the weight gradients of unit i run beside the backward of units i+1 .. i+3 (8, 16 and 40 sets measured slower)
     int gsets = 1;                    // sets allocated for the current graph (GSETS on small meshes, else 1: no overlap)
-    size_t GT[GSETS_MAX], GXH[GSETS_MAX], GY[GSETS_MAX], GZ2[GSETS_MAX], GZ1[GSETS_MAX];
+    size_t GT[GSETS], GXH[GSETS], GY[GSETS], GZ2[GSETS], GZ1[GSETS];
     size_t GXs, GXr, GXB, gV[2], gE[MAX_EDGE_SETS][2], gAgg[MAX_EDGE_SETS], Gout, gNF, io, ptmp, pw, pb;
     size_t Pn, Qn, SGs, SGr;     // factored first layer: per-node projections (forward) and summed GZ1 rows (backward)
     // whole-array LayerNorm in the training step: per-MLP statistics of the forward (64 floats each), the double partials of the two
     // reductions, (m1, m2) of the pullback
     size_t lnstats = 0, lnpart = 0, lnm = 0;
-    bool defer_reduce = false;        // small meshes (second stream): every unit's partial sums are kept and reduced in a few launches at the end of the reverse pass
-    size_t pw_all = 0, pb_all = 0;    // ... their partial blocks: [unit][5][nb][L][L], [unit][DEFER_PB_JOBS][nb][L]
-    int defer_units = 0;
     bool need_gt = true;              // GT / GXH are full arrays (else 64-float stubs: every LayerNorm'd unit runs with LNSUM)
     size_t lnsum = 0, lnsum2 = 0;     // per-block LayerNorm-parameter sums of the streaming backward kernel and their first-level reduction (TrainBwdArgs::LNSUM)
     int size_cus = 0;                 // train_size_cus() the arena was laid out for: the launches decide by the same count (train_prepare lays it out again when the test CU count changed)
     int64_t wg_rpb_last = 0, wg_rpb_node = 0, wg_rpb_edge[MAX_EDGE_SETS] = {0, 0};   // rows per block of the last weight-gradient launch unit, of the processor's node MLP and of its edge MLPs (mgn_debug_train_regime)
     size_t segcarry = 0;              // carry rows of the fused aggregation (2 per edge tile; TrainFwdArgs::SEG_CARRY)
-    size_t lnrow = 0;                 // (mean, 1 / denominator) per row of the MLP being unwound (TrainBwdArgs::LNROW)
     // weight gradients + their reductions go to a second stream (small meshes leave most of the chip idle during k_mlp_bwd)
     hipStream_t aux = nullptr;
-    hipEvent_t ev_bwd = nullptr, ev_wg[GSETS_MAX] = {};
+    hipEvent_t ev_bwd = nullptr, ev_wg[GSETS] = {};   // ev_wg[i]: the weight gradients of the unit in buffer set i have run
     // hipGraph replay of the two launch sequences over fixed buffers (small meshes): [0] forward, [1] backward of mgn_step,
     // [2] backward of mgn_ode_vjp (it also produces the input gradient).  Eager once, captured on the next call.
     hipGraphExec_t exec[3] = {nullptr, nullptr, nullptr};
@@ -419,9 +419,8 @@ int prepare_graph(mgn_engine* h) {
         // Small meshes (the cooperative-tile regime: a launch leaves most of the chip idle) get GSETS sets of gradient buffers so
         // that the parameter gradients can run on a second stream; larger ones fill the chip on their own and keep one set.
         {
-            static const bool overlap_env = env_int("MGN_TRAIN_OVERLAP", 1) != 0;
             const int64_t big = Emax > N ? Emax : N;
-            T.gsets = (overlap_env && !part && !T.recompute && !any_fact && L == 128 && big <= (int64_t)8 * train_size_cus() * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers; a partition runs on one stream, eagerly: communicator calls sit between its launches)
+            T.gsets = (!part && !T.recompute && !any_fact && L == 128 && big <= (int64_t)TRAIN_COOP_TILES_PER_CU * train_size_cus() * TILE) ? TrainState::GSETS : 1;   // (SGs / SGr are single buffers; a partition runs on one stream, eagerly: communicator calls sit between its launches)
         }
         // GT / G xhat rows only where some LayerNorm'd launch unit does not take its parameter sums inside the backward kernel (train.h: LNSUM)
         bool need_gt = h->cfg.ln_dims == MGN_LN_ALL || T.gsets > 1 || !train_bwd_ln_sums(L, (int)((N + TILE - 1) / TILE));
@@ -443,21 +442,8 @@ int prepare_graph(mgn_engine* h) {
         T.ptmp = take((size_t)(NG > 0 ? NG : 1) * (size_t)std::max(h->cfg.Fn, h->cfg.O));      // row permutations of a renumbered graph
         int nb = std::max(wgrad_blocks(NT), wgrad_blocks(N));   // the most blocks of any launch unit (the count is not monotonic in the rows once rows per block grow)
         for (int q = 0; q < S; ++q) nb = std::max(nb, wgrad_blocks(g.set[q].e_local));
-        T.pw = take((size_t)5 * (T.gsets > 1 ? T.gsets / 2 : 1) * (nb > 0 ? nb : 1) * L * L);   // one partial-dW region per weight-gradient job of a launch (a group of units on small meshes)
-        T.pb = take((size_t)(WGRAD_MAX_JOBS + 1) * (nb > 0 ? nb : 1) * L);   // (+ 1: the second output of a LayerNorm job)
-        {   // Deferred reductions (MGN_TRAIN_DEFER_REDUCE = 1; built, same bits, off) where the weight gradients run on the second stream: the 33
-            // k_reduce_partials launches of a step as five at its end.
-            static const int defer_env = env_int("MGN_TRAIN_DEFER_REDUCE", 0);   // (measured: 2.54 ms against 2.36 -- the per-unit partial blocks, re-used, stay in the caches; 680 MB of them do not)
-            const int units = (2 + S + mps * (S + 1)) * NB;
-            const size_t per_unit = ((size_t)5 * L * L + (size_t)DEFER_PB_JOBS * L) * (nb > 0 ? nb : 1);
-            T.defer_reduce = defer_env && T.gsets > 1 && per_unit * units * 4 <= ((size_t)8 << 30);
-            T.defer_units = units;
-            if (T.defer_reduce) {
-                T.pw_all = take((size_t)units * 5 * (nb > 0 ? nb : 1) * L * L);
-                T.pb_all = take((size_t)units * DEFER_PB_JOBS * (nb > 0 ? nb : 1) * L);
-            }
-        }
-        T.lnrow = take((size_t)2 * (ML / L));
+        T.pw = take((size_t)UNIT_W_JOBS * (nb > 0 ? nb : 1) * L * L);   // one partial-dW region per weight job of a launch, one partial column-sum region per job
+        T.pb = take((size_t)WGRAD_MAX_JOBS * (nb > 0 ? nb : 1) * L);
         T.lnsum = take(((ML / L + TILE - 1) / TILE + 7) / 8 * (size_t)2 * L + 2 * L);
         T.lnsum2 = take((size_t)LNSUM_GROUPS * 2 * L);
         T.segcarry = take((size_t)2 * ((ELmax / L + TILE - 1) / TILE + 1) * L);
@@ -803,46 +789,12 @@ struct BwdIo {
     int fq = -1; const float* vin = nullptr;
 };
 
-struct TrainPass;
-// one launch unit as the weight-gradient queue sees it, after its activation backward has been issued into gradient-buffer set gs
+// one launch unit as its weight-gradient launch sees it, after its activation backward has been issued into gradient-buffer set gs
 struct WgradUnit {
     const TrainBlock& b; const BwdIo& io;
     const size_t* hb;            // its kept H1, H2, Y
     int64_t rows, node_rows; int32_t ntiles; int gs;
-    bool wide, lnsum, lnjob;     // how its LayerNorm parameters get their sums (TrainPass::bwd_unit)
-};
-
-// The weight-gradient launches of one reverse pass.
-// The parameter gradients of unit i (k_wgrad + k_reduce_partials: they only read what k_mlp_bwd left in gradient-buffer
-// set i % gsets and the kept activations) run on a second stream beside the activation backward of the next units.  Not in
-// recompute mode (there the kept activations are shared buffers which the next step's recomputation overwrites) and not
-// on large meshes, which fill the chip on their own (prepare_graph).  MGN_TRAIN_OVERLAP = 0 keeps everything on one stream.
-// Small meshes: the weight-gradient jobs of `group` consecutive launch units go out as ONE k_wgrad + ONE k_reduce_partials launch on the
-// second stream (two groups of gradient-buffer sets in flight).  Per unit they were 66 launches per processor step!, each a
-// cross-stream dependency both ways: the main stream's backward kernels started ~10 us apart (rocprofv3 timeline, docs/experiments.md)
-// and the second stream was the critical path.  Same partial blocks (128 rows), same order of the reduction: the same bits.
-// The reverse pass is issued twice per handle -- eagerly, then under stream capture -- and both must issue the same launches: all
-// state that the batching carries from unit to unit is here, and reset() is the one place that sets it.
-struct WgradQueue {
-    WgradBatch pwb; ReduceBatch prb;     // the launch being filled, its jobs' reductions
-    int pnw, punits;                     // ... its partial-dW regions taken, the units in it
-    int64_t plrows;                      // ... the rows it covers
-    int nbatch;                          // launches issued (their events are indexed by it)
-    std::vector<ReduceJob> deferred;     // (T.defer_reduce) the reductions of all units, launched behind the last weight-gradient launch
-    int unit_no, n_bwd;                  // units that took deferred slots; activation backwards issued
-    int set_batch[TrainState::GSETS_MAX];   // launch number that takes the weight gradients of the unit in each buffer set
-
-    void new_batch() { pwb = WgradBatch{}; prb = ReduceBatch{}; pnw = punits = 0; plrows = 0; }
-    void reset() {
-        new_batch();
-        nbatch = unit_no = n_bwd = 0;
-        deferred.clear();
-        for (int& v : set_batch) v = -1;
-    }
-    int acquire(TrainPass& P, int& gs);              // the buffer set of the next activation backward, free to be written
-    int add_unit(TrainPass& P, const WgradUnit& u);  // every parameter gradient of a unit joins the launch being filled
-    int flush(TrainPass& P);
-    int drain(TrainPass& P);                         // end of the pass: what is left, the deferred reductions, the join
+    bool wide, lnsum;            // how its LayerNorm parameters get their sums (TrainPass::bwd_unit)
 };
 
 // One pass of the model and its pullback over the training arena: forward with kept activations, seed, reverse pass, all parameter
@@ -874,11 +826,10 @@ struct TrainPass {
     // kernels run without their row-wise LayerNorm; two reductions and an elementwise pass follow them in both directions
     const bool lnall;
     const float ln_eps_in, ln_eps_out;
-    const bool overlap;          // weight gradients on the second stream (WgradQueue)
-    int group = 1;               // launch units per weight-gradient launch
-    int64_t lrows_all;           // the longest job of the model: what a group's launch covers
+    const bool overlap;          // weight gradients on the second stream (wgrad_unit)
+    int64_t lrows_all;           // the longest job of the model: what a launch on the second stream is sized for
     int nlb = 0;                 // partial sums of the loss (seed -> results)
-    WgradQueue wq;
+    int n_bwd = 0;               // activation backwards issued in this reverse pass
 
     TrainPass(mgn_engine* h_, const TrainJob& J_)
         : h(h_), J(J_), c(h_->cfg), T(*h_->train), g(h_->g), S(h_->nsets), L(c.L), mps(c.mps), O(c.O), part(c.nranks > 1), N(g.n_own),
@@ -899,8 +850,6 @@ struct TrainPass {
             sx[q].rowptr = h->es[q].d_rowptr.as<int32_t>();
             lrows_all = std::max<int64_t>(lrows_all, sx[q].E);
         }
-        static const int group_env = env_int("MGN_TRAIN_WG_GROUP", 1);
-        if (overlap) group = std::max(1, std::min(group_env, T.gsets / 2));
     }
     bool vjp() const { return J.kind != JOB_STEP && J.kind != JOB_DATAPOINT; }
     float* io() const { return A + T.io; }    // the VJPs' rows: x [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N]
@@ -1184,6 +1133,82 @@ struct TrainPass {
         for (hipEvent_t& e : T.ev_wg) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         return MGN_OK;
     }
+    // The parameter gradients of a launch unit are one k_wgrad launch and one k_reduce_partials launch behind its activation backward.
+    // Small meshes (overlap): the pair of unit i only reads what k_mlp_bwd left in gradient-buffer set i % gsets and the kept activations,
+    // and runs on a second stream beside the activation backward of the next units.  Not in recompute mode (there the kept activations
+    // are shared buffers which the next step's recomputation overwrites) and not on large meshes, which fill the chip on their own
+    // (prepare_graph).  The reverse pass is issued twice per handle -- eagerly, then under stream capture -- and both must issue the same
+    // launches: n_bwd is all the state that passes from unit to unit, and backward() sets it.
+    // The buffer set of the next activation backward, free to be written: its last occupant's weight gradients have run.  ev_wg[gs] is
+    // recorded once per unit in set gs.  The second stream is in order and a set comes round again only gsets units later, so the record
+    // of unit i - gsets is the last one issued when unit i waits here, and the next one (unit i's own) is issued behind this wait: no
+    // wait can see a re-recorded event.
+    int wgrad_acquire(int& gs) {
+        gs = overlap ? n_bwd % T.gsets : 0;
+        if (overlap && n_bwd >= T.gsets) HIPCHK(h, hipStreamWaitEvent(st, T.ev_wg[gs], 0));
+        ++n_bwd;
+        return MGN_OK;
+    }
+    int wgrad_unit(const WgradUnit& u) {
+        const TrainBlock& b = u.b;
+        const int gs = u.gs;
+        const int64_t rows = u.rows;
+        const int64_t lrows_u = rows > u.node_rows ? rows : u.node_rows;   // a launch covers its longest job (node jobs of a factored edge MLP)
+        const int64_t lrows = overlap ? lrows_all : lrows_u;               // (second stream: the longest job of the model; 128-row blocks either way)
+        const int nb = wgrad_blocks(lrows);
+        T.wg_rpb_last = wgrad_rows_per_block(lrows);
+        const hipStream_t wst = overlap ? T.aux : st;
+        if (overlap) {
+            HIPCHK(h, hipEventRecord(T.ev_bwd, st));
+            HIPCHK(h, hipStreamWaitEvent(wst, T.ev_bwd, 0));
+        }
+        if (nb > 0 && lrows_u > 0) {
+            WgradBatch wb{};
+            ReduceBatch rb{};
+            int nw = 0;                                    // partial-dW regions taken
+            auto job = [&](const float* X, const int32_t* xi_, const float* Gm, long woff, int nrows, int cols, long boff, int bcols, int64_t jrows = -1) {
+                if (woff < 0 && boff < 0) return;          // identity slot
+                WgradJob& j = wb.job[wb.njobs];
+                if (jrows < 0) jrows = rows;
+                const int nbj = wgrad_blocks_of_job(lrows, jrows);     // blocks of this launch that hold rows of the job
+                j.X = X; j.xidx = xi_; j.G = Gm; j.rows = jrows;
+                j.pw = woff >= 0 ? A + T.pw + (size_t)nw * nb * L * L : nullptr;
+                j.pb = boff >= 0 ? A + T.pb + (size_t)wb.njobs * nb * L : nullptr;
+                if (woff >= 0) {
+                    rb.job[rb.njobs++] = ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff};
+                    ++nw;
+                }
+                if (boff >= 0) rb.job[rb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff};
+                ++wb.njobs;
+            };
+            job(A + u.hb[1], nullptr, A + T.GY[gs], b.gW[2], L, b.out_cols, b.gb[2], b.out_cols);
+            job(A + u.hb[0], nullptr, A + T.GZ2[gs], b.gW[1], L, L, b.gb[1], L);
+            if (u.io.fq < 0) {
+                for (int j = 0; j < b.nin; ++j)
+                    job(u.io.xin[j], u.io.xi[j], A + T.GZ1[gs], b.gW[0] + (long)j * L * L, b.in_rows, L, j == 0 ? b.gb[0] : -1, L);
+            } else {   // dW1e = e^T GZ1 (+ db1) over the edges; dW1s = v^T SGs, dW1r = v^T SGr over the nodes
+                job(u.io.xin[0], u.io.xi[0], A + T.GZ1[gs], b.gW[0] + (long)2 * L * L, L, L, b.gb[0], L);
+                job(u.io.vin, nullptr, A + T.SGs, b.gW[0], L, L, -1, L, u.node_rows);
+                job(u.io.vin, nullptr, A + T.SGr, b.gW[0] + (long)L * L, L, L, -1, L, N);
+            }
+            if (u.lnsum) {
+                const int ng = std::min(LNSUM_GROUPS, (int)((u.ntiles + 7) / 8));
+                rb.job[rb.njobs++] = ReduceJob{A + T.lnsum2, ng, (int64_t)2 * L, 1, L, L, G + b.gbeta};
+                rb.job[rb.njobs++] = ReduceJob{A + T.lnsum2 + L, ng, (int64_t)2 * L, 1, L, L, G + b.ggamma};
+            } else if (b.ln && !u.wide) {
+                job(nullptr, nullptr, A + T.GXH[gs], -1, 0, 0, b.ggamma, L);
+                job(nullptr, nullptr, A + T.GT[gs], -1, 0, 0, b.gbeta, L);
+            }
+            HIPCHK(h, launch_wgrad(L, wb, lrows, wst));
+            HIPCHK(h, launch_reduce_partials(rb, wst));
+        }
+        if (overlap) HIPCHK(h, hipEventRecord(T.ev_wg[gs], wst));
+        return MGN_OK;
+    }
+    int wgrad_join() {   // the second stream is in order: the event of its last unit covers all of it
+        if (overlap && n_bwd > 0) HIPCHK(h, hipStreamWaitEvent(st, T.ev_wg[(n_bwd - 1) % T.gsets], 0));
+        return MGN_OK;
+    }
     // activation backward of one launch unit (kept activations hb) + all of its parameter gradients
     int bwd_unit(const TrainBlock& b, int64_t rows, int32_t ntiles, const size_t (&hb)[3], const BwdIo& io_, int lnslot) {
         const int fq = io_.fq;
@@ -1192,7 +1217,7 @@ struct TrainPass {
         const int64_t node_rows = fact ? NT : 0;          // rows that send: SGs, dW1s (halo rows included); SGr and dW1r stop at the N owned rows
         const int nin_k = fact ? 1 : b.nin;               // input blocks the kernel unwinds
         int gs = 0;
-        if (int rc = wq.acquire(*this, gs)) return rc;
+        if (int rc = wgrad_acquire(gs)) return rc;
         TrainBwdArgs a{};
         a.rows = rows; a.ntiles = ntiles;
         a.G0 = io_.g0; a.G1 = io_.g1; a.g1idx = io_.g1i;
@@ -1207,11 +1232,8 @@ struct TrainPass {
         a.tabs = Wt + b.tabs;
         a.ln = b.ln ? 1 : 0;
         a.GT = A + T.GT[gs]; a.GXH = A + T.GXH[gs]; a.GY = A + T.GY[gs]; a.GZ2 = A + T.GZ2[gs]; a.GZ1 = A + T.GZ1[gs];
-        // One stream (large meshes): the LayerNorm-parameter sums come from a job that re-reads G0 (+ G1) and Y -- they are intact until this
-        // unit's weight-gradient launch has run -- and the row statistics, instead of from GT / G xhat rows written here and read there.
-        const bool lnsum = b.ln && !wide && !overlap && rows > 0 && train_bwd_ln_sums(L, ntiles);     // the sums inside the backward kernel (per block) ...
-        const bool lnjob = !lnsum && b.ln && !wide && !overlap && rows > 0 && wgrad_ln_jobs(L) && !train_uses_coop(L, ntiles);   // ... or a job that re-reads G0 / Y (the cooperative backward kernels write GT / G xhat)
-        if (lnjob) { a.GT = nullptr; a.GXH = nullptr; a.LNROW = A + T.lnrow; }
+        // LayerNorm-parameter sums: inside the eight-tile backward kernel (per block), else GT / G xhat rows written here feed two column-sum jobs
+        const bool lnsum = b.ln && !wide && !overlap && rows > 0 && train_bwd_ln_sums(L, ntiles);
         if (lnsum) { a.GT = nullptr; a.GXH = nullptr; a.LNSUM = A + T.lnsum; }
         if (b.ln && !wide && !lnsum && !T.need_gt && rows > 0) return fail(h, MGN_E_STATE, "training arena laid out without GT / GXH rows but a launch unit needs them");
         if (wide && rows > 0) {   // pullback of the whole-array LayerNorm: dgamma, dbeta and the two means first (two column reductions)
@@ -1221,22 +1243,15 @@ struct TrainPass {
             a.LNS = A + T.lnstats + (size_t)64 * lnslot;
             a.LNM = A + T.lnm;
         }
-        const bool sgr = fact && rows > 0 && train_bwd_fused_sgr(L, ntiles);   // SGr inside the launch (segmented scan over the receiver runs of GZ1)
-        if (sgr) { a.SEG_RCV = sx[fq].rcv; a.SEG_OUT = A + T.SGr; a.SEG_CARRY = A + T.segcarry; }
         HIPCHK(h, launch_mlp_bwd(L, nin_k, a, st));
         if (lnsum)    // [blocks][2 L] -> [LNSUM_GROUPS][2 L], in order; the unit's reduction launch adds the groups
             HIPCHK(h, launch_colsum_groups(A + T.lnsum, (ntiles + 7) / 8, 2 * L, LNSUM_GROUPS, A + T.lnsum2, st));
         if (fact) {   // gather <-> segmented-sum duality on GZ1 itself: SGr[n] = sum of GZ1 over edges received by n, SGs: sent by n
-            if (sgr) {
-                HIPCHK(h, launch_seg_fixup(L, sx[fq].rowptr, A + T.segcarry, A + T.SGr, (int32_t)N, st));
-                HIPCHK(h, launch_segment_sum(L, A + T.GZ1[gs], sx[fq].rowptr_s, sx[fq].perm_s, nullptr, A + T.SGs, (int32_t)node_rows, st));
-            } else {
-                HIPCHK(h, launch_segment_sum_pair(L, A + T.GZ1[gs], sx[fq].rowptr, sx[fq].rowptr_s, sx[fq].perm_s, A + T.SGr, A + T.SGs, (int32_t)N, st));
-                HIPCHK(h, launch_segment_sum(L, A + T.GZ1[gs], sx[fq].rowptr_s + N, sx[fq].perm_s, nullptr, A + T.SGs + (size_t)N * L, g.n_halo, st));
-            }
+            HIPCHK(h, launch_segment_sum_pair(L, A + T.GZ1[gs], sx[fq].rowptr, sx[fq].rowptr_s, sx[fq].perm_s, A + T.SGr, A + T.SGs, (int32_t)N, st));
+            HIPCHK(h, launch_segment_sum(L, A + T.GZ1[gs], sx[fq].rowptr_s + N, sx[fq].perm_s, nullptr, A + T.SGs + (size_t)N * L, g.n_halo, st));
             if (g.n_halo > 0) HIPCHK(h, hipMemsetAsync(A + T.SGr + (size_t)N * L, 0, (size_t)g.n_halo * L * 4, st));   // (a halo row receives nothing here)
         }
-        return wq.add_unit(*this, WgradUnit{b, io_, hb, rows, node_rows, ntiles, gs, wide, lnsum, lnjob});
+        return wgrad_unit(WgradUnit{b, io_, hb, rows, node_rows, ntiles, gs, wide, lnsum});
     }
     // one MLP: its second unit (if any) first, handing the gradient w.r.t. its input to the first through GXB
     int bwd(const TrainMlp& m, int64_t rows, int32_t ntiles, const Acts& act, const BwdIo& io_) {
@@ -1285,7 +1300,7 @@ struct TrainPass {
         return MGN_OK;
     }
     int backward() {
-        wq.reset();
+        n_bwd = 0;
         HIPCHK(h, hipMemsetAsync(G, 0, h->params.size() * 4, st));   // (inside the replayed sequence: G is the engine's own buffer)
         int cur = 0, ecur = 0;   // gV[cur], gE[q][ecur] hold the gradients w.r.t. the latents entering the part of the model already unwound
         {
@@ -1326,7 +1341,7 @@ struct TrainPass {
             u.g0 = A + T.gE[q][ecur]; u.xin[0] = A + T.ef_pad[q]; u.xi[0] = part ? nullptr : sx[q].egid;
             if (int rc = bwd(T.m_ee[q], sx[q].E, sx[q].nt, T.a_ee[q], u)) return rc;
         }
-        return wq.drain(*this);
+        return wgrad_join();
     }
 
     // ---- results
@@ -1380,133 +1395,6 @@ struct TrainPass {
         return MGN_OK;
     }
 };
-
-// buffer set gs is re-used: the launch that took its last occupant's weight gradients must have run (launches on the second stream are
-// in order; their events are indexed by launch number)
-int WgradQueue::acquire(TrainPass& P, int& gs) {
-    gs = P.overlap ? n_bwd % P.T.gsets : 0;
-    if (P.overlap && set_batch[gs] >= 0) {
-        if (set_batch[gs] == nbatch && punits > 0)
-            if (int rc = flush(P)) return rc;
-        HIPCHK(P.h, hipStreamWaitEvent(P.st, P.T.ev_wg[set_batch[gs] % TrainState::GSETS_MAX], 0));
-    }
-    ++n_bwd;
-    return MGN_OK;
-}
-
-int WgradQueue::flush(TrainPass& P) {
-    if (punits == 0) return MGN_OK;
-    TrainState& T = P.T;
-    hipStream_t wst = P.overlap ? T.aux : P.st;
-    if (P.overlap) {
-        HIPCHK(P.h, hipEventRecord(T.ev_bwd, P.st));
-        HIPCHK(P.h, hipStreamWaitEvent(wst, T.ev_bwd, 0));
-    }
-    if (pwb.njobs > 0 && wgrad_blocks(plrows) > 0) {
-        HIPCHK(P.h, launch_wgrad(P.L, pwb, plrows, wst));
-        HIPCHK(P.h, launch_reduce_partials(prb, wst));
-    }
-    if (P.overlap) HIPCHK(P.h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
-    ++nbatch;
-    new_batch();
-    return MGN_OK;
-}
-
-// every parameter gradient of the unit: jobs of one batched weight-gradient launch + one batched (ordered) reduction
-int WgradQueue::add_unit(TrainPass& P, const WgradUnit& u) {
-    TrainState& T = P.T;
-    const TrainBlock& b = u.b;
-    const int L = P.L, gs = u.gs;
-    float* const A = P.A;
-    float* const G = P.G;
-    const int64_t rows = u.rows;
-    const int64_t lrows_u = rows > u.node_rows ? rows : u.node_rows;   // a launch covers its longest job (node jobs of a factored edge MLP)
-    const int64_t lrows = P.overlap ? P.lrows_all : lrows_u;           // (a group's launch: the longest job of the model; 128-row blocks either way)
-    const int nb = wgrad_blocks(lrows);
-    T.wg_rpb_last = wgrad_rows_per_block(lrows);
-    if (pwb.njobs + 10 > WGRAD_MAX_JOBS || prb.njobs + 14 > REDUCE_MAX_JOBS)   // (a unit adds at most 8 + 12 jobs)
-        if (int rc = flush(P)) return rc;
-    ++punits;
-    set_batch[gs] = nbatch;
-    if (nb == 0 || lrows_u == 0) return punits >= P.group ? flush(P) : MGN_OK;
-    plrows = std::max(plrows, lrows);
-    const bool defer = T.defer_reduce && unit_no < T.defer_units;
-    const int this_unit = unit_no++;
-    int unw = 0, unb = 0;                                  // (deferred) weight / column-sum partial slots of this unit
-    auto job = [&](const float* X, const int32_t* xi_, const float* Gm, long woff, int nrows, int cols, long boff, int bcols, int64_t jrows = -1) {
-        if (woff < 0 && boff < 0) return;              // identity slot
-        WgradJob& j = pwb.job[pwb.njobs];
-        if (jrows < 0) jrows = rows;
-        const int nbj = wgrad_blocks_of_job(lrows, jrows);     // blocks of this launch that hold rows of the job
-        j.X = X; j.xidx = xi_; j.G = Gm; j.rows = jrows;
-        if (defer) {
-            j.pw = woff >= 0 ? A + T.pw_all + ((size_t)this_unit * 5 + unw) * nb * L * L : nullptr;
-            j.pb = boff >= 0 ? A + T.pb_all + ((size_t)this_unit * DEFER_PB_JOBS + unb) * nb * L : nullptr;
-            if (woff >= 0) { deferred.push_back(ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff}); ++unw; }
-            if (boff >= 0) { deferred.push_back(ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff}); ++unb; }
-            ++pwb.njobs;
-            return;
-        }
-        j.pw = woff >= 0 ? A + T.pw + (size_t)pnw * nb * L * L : nullptr;
-        j.pb = boff >= 0 ? A + T.pb + (size_t)pwb.njobs * nb * L : nullptr;
-        if (woff >= 0) {
-            prb.job[prb.njobs++] = ReduceJob{j.pw, nbj, (int64_t)L * L, nrows, cols, L, G + woff};
-            ++pnw;
-        }
-        if (boff >= 0) prb.job[prb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, bcols, L, G + boff};
-        ++pwb.njobs;
-    };
-    job(A + u.hb[1], nullptr, A + T.GY[gs], b.gW[2], L, b.out_cols, b.gb[2], b.out_cols);
-    job(A + u.hb[0], nullptr, A + T.GZ2[gs], b.gW[1], L, L, b.gb[1], L);
-    if (u.io.fq < 0) {
-        for (int j = 0; j < b.nin; ++j)
-            job(u.io.xin[j], u.io.xi[j], A + T.GZ1[gs], b.gW[0] + (long)j * L * L, b.in_rows, L, j == 0 ? b.gb[0] : -1, L);
-    } else {   // dW1e = e^T GZ1 (+ db1) over the edges; dW1s = v^T SGs, dW1r = v^T SGr over the nodes
-        job(u.io.xin[0], u.io.xi[0], A + T.GZ1[gs], b.gW[0] + (long)2 * L * L, L, L, b.gb[0], L);
-        job(u.io.vin, nullptr, A + T.SGs, b.gW[0], L, L, -1, L, u.node_rows);
-        job(u.io.vin, nullptr, A + T.SGr, b.gW[0] + (long)L * L, L, L, -1, L, P.N);
-    }
-    if (u.lnsum) {
-        const int ng = std::min(LNSUM_GROUPS, (int)((u.ntiles + 7) / 8));
-        prb.job[prb.njobs++] = ReduceJob{A + T.lnsum2, ng, (int64_t)2 * L, 1, L, L, G + b.gbeta};
-        prb.job[prb.njobs++] = ReduceJob{A + T.lnsum2 + L, ng, (int64_t)2 * L, 1, L, L, G + b.ggamma};
-    } else if (u.lnjob) {
-        WgradJob& j = pwb.job[pwb.njobs];
-        const int nbj = wgrad_blocks_of_job(lrows, rows);
-        j = WgradJob{};
-        j.G = u.io.g0; j.rows = rows;
-        j.Y = A + u.hb[2]; j.LNROW = A + T.lnrow; j.G1 = u.io.g1; j.g1idx = u.io.g1i;
-        j.pb = A + T.pb + (size_t)pwb.njobs * nb * L;
-        j.pb2 = A + T.pb + (size_t)WGRAD_MAX_JOBS * nb * L;
-        prb.job[prb.njobs++] = ReduceJob{j.pb, nbj, (int64_t)L, 1, L, L, G + b.gbeta};
-        prb.job[prb.njobs++] = ReduceJob{j.pb2, nbj, (int64_t)L, 1, L, L, G + b.ggamma};
-        ++pwb.njobs;
-    } else if (b.ln && !u.wide) {
-        job(nullptr, nullptr, A + T.GXH[gs], -1, 0, 0, b.ggamma, L);
-        job(nullptr, nullptr, A + T.GT[gs], -1, 0, 0, b.gbeta, L);
-    }
-    return punits >= P.group ? flush(P) : MGN_OK;
-}
-
-int WgradQueue::drain(TrainPass& P) {
-    TrainState& T = P.T;
-    if (int rc = flush(P)) return rc;                    // the units left over from the last full group
-    if (!deferred.empty()) {                             // every unit's reductions, REDUCE_MAX_JOBS per launch, behind the last weight-gradient launch
-        hipStream_t wst = P.overlap ? T.aux : P.st;
-        for (size_t i = 0; i < deferred.size(); i += REDUCE_MAX_JOBS) {
-            ReduceBatch rb{};
-            for (size_t j = i; j < deferred.size() && j < i + REDUCE_MAX_JOBS; ++j) rb.job[rb.njobs++] = deferred[j];
-            HIPCHK(P.h, launch_reduce_partials(rb, wst));
-        }
-        if (P.overlap) {
-            HIPCHK(P.h, hipEventRecord(T.ev_wg[nbatch % TrainState::GSETS_MAX], wst));
-            ++nbatch;
-        }
-    }
-    if (P.overlap && nbatch > 0)                         // join: the second stream is in order, its last event covers all of it
-        HIPCHK(P.h, hipStreamWaitEvent(P.st, T.ev_wg[(nbatch - 1) % TrainState::GSETS_MAX], 0));
-    return MGN_OK;
-}
 
 int train_run(mgn_handle* h, const TrainJob& J) {
     TrainPass P(h, J);

@@ -44,20 +44,19 @@ struct TrainBwdArgs {
     int32_t ln;                                  // 1: row-wise LayerNorm pullback here; 2: the whole-array one -- gy = rden (gamma g - m1 - xhat m2) with
     const float* LNS; const float* LNM;          //    LNS = (mean, rden, kappa) of the forward and LNM = (m1, m2) of launch_lnall_bwd; 0: none
     float* GT; float* GXH;                       // ln: total upstream gradient and G * xhat (-> dbeta, dgamma by column sums)
-    // streaming kernels, 8 tiles per block (train_bwd_fused_sgr): the receiver-side segmented sum of GZ1 inside the launch, as the forward does it for e'
-    // (TrainFwdArgs::SEG_*): runs inside a tile to SEG_OUT[receiver], pieces of runs that cross tile borders to SEG_CARRY, launch_seg_fixup after it
-    const int32_t* SEG_RCV; float* SEG_OUT; float* SEG_CARRY;
-    float* LNSUM;                                // ln == 1, non-null (streaming kernels, 8 tiles per block; train_bwd_ln_sums): [block][2][L] column sums of the block's rows of g (dbeta) and g * xhat (dgamma), reduced inside the kernel (DPP adds over a tile's 32 rows, the block's waves through LDS) -- neither GT / GXH nor LNROW is written then
-    float* LNROW;                                // ln == 1, non-null: (mean, 1 / denominator) of every row instead of GT / GXH -- the LayerNorm job of the weight-gradient launch rebuilds both from G0 (+ G1) and Y (round 6: - 6 GB written per edge MLP on M-1M)
+    float* LNSUM;                                // ln == 1, non-null (streaming kernels, 8 tiles per block; train_bwd_ln_sums): [block][2][L] column sums of the block's rows of g (dbeta) and g * xhat (dgamma), reduced inside the kernel (DPP adds over a tile's 32 rows, the block's waves through LDS) -- GT / GXH are not written then
     float* GY; float* GZ2; float* GZ1;           // gradients at the three Dense outputs (-> weight / bias gradients)
     float* GX[3]; const float* GXadd[3];         // GX[j][row] = (GXadd[j] ? GXadd[j][row] : 0) + GZ1[row] * W1T[j]
 };
 
 hipError_t launch_mlp_fwd(int L, int nin, const TrainFwdArgs& a, hipStream_t s);
-bool train_fwd_fused_agg(int L, int ntiles);   // the forward launch of this size takes SEG_* (streaming kernels at L = 128; MGN_TRAIN_FUSED_AGG = 0: never)
+bool train_fwd_fused_agg(int L, int ntiles);   // the forward launch of this size takes SEG_* (eight-tile streaming kernels)
 // agg[n] = 0 for a node without edges, the sum of its carry rows for a node whose run of edges crosses tile borders (others: written by the forward kernel)
 hipError_t launch_seg_fixup(int L, const int32_t* rowptr, const float* carry, float* agg, int32_t n, hipStream_t s);
 hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s);
+// L = 128: a non-empty MLP launch of at most this many tiles per CU of train_size_cus() runs the cooperative kernels, a larger one the
+// eight-tile streaming kernels.  The same boundary decides the factored first edge layer and the second stream (mgn_train.cpp: prepare_graph).
+constexpr int TRAIN_COOP_TILES_PER_CU = 8;
 bool train_uses_coop(int L, int ntiles);
 int train_size_cus();                      // the CU count the size rules of the training step are scaled by: 256 on every device, or the test CU count (kernels.h: set_num_cus)
 void train_regime_counts(int* out /* [12] */, bool reset);   // launches since the last reset: [launch_mlp_fwd, launch_mlp_bwd, launch_lin2][cooperative, 4-tile streaming, 8-tile streaming, on fp16 pieces]
@@ -81,18 +80,13 @@ hipError_t launch_segment_sum_pair(int L, const float* src, const int32_t* rowpt
 //   dW[in][out] = sum_rows X[xidx ? xidx[row] : row][in] * G[row][out];   db[out] = sum_rows G[row][out]
 // The row range is split over wgrad_blocks(rows) blocks: pw [nblocks][L][L], pb [nblocks][L] hold per-block partials.
 // pw == null: column sums only (LayerNorm parameter gradients); pb == null: no column sums.
-constexpr int WGRAD_MAX_JOBS = 32;   // (a launch may carry the jobs of several launch units: mgn_train.cpp, weight-gradient groups)
-struct WgradJob {
-    const float* X; const int32_t* xidx; const float* G; int64_t rows; float* pw; float* pb;
-    // LayerNorm job (Y != null; X == null, pw == null; k_wgrad_h2 only -- wgrad_ln_jobs()): g = G[row] + (G1 ? G1[g1idx ? g1idx[row] : row] : 0),
-    // xhat = (Y[row] - LNROW[2 row]) * LNROW[2 row + 1];  pb <- column sums of g (dbeta), pb2 <- column sums of g * xhat (dgamma)
-    const float* Y; const float* LNROW; const float* G1; const int32_t* g1idx; float* pb2;
-};
-bool train_bwd_fused_sgr(int L, int ntiles);  // the backward launch of this size takes SEG_* (MGN_TRAIN_FUSED_SGR)
-bool train_bwd_ln_sums(int L, int ntiles);   // the backward launch of this size takes LNSUM (MGN_TRAIN_BWD_LN_SUMS, default in train.hip)
+// A launch carries the jobs of one launch unit: dW3, dW2, up to three blocks of dW1 (a factored edge MLP: the e block and the two node
+// blocks) and the two column-sum jobs of the LayerNorm parameters.
+constexpr int WGRAD_MAX_JOBS = 7;
+struct WgradJob { const float* X; const int32_t* xidx; const float* G; int64_t rows; float* pw; float* pb; };
+bool train_bwd_ln_sums(int L, int ntiles);   // the backward launch of this size takes LNSUM (eight-tile streaming kernels)
 // out[g][c] = sum of part[b][c] over the g-th of `groups` equal ranges of the nblocks blocks, in order (c < cols): the first level of the LNSUM reduction
 hipError_t launch_colsum_groups(const float* part, int nblocks, int cols, int groups, float* out, hipStream_t s);
-bool wgrad_ln_jobs(int L);                   // the weight-gradient launch at this L takes LayerNorm jobs
 struct WgradBatch { int32_t njobs; int64_t rows_per_block; WgradJob job[WGRAD_MAX_JOBS]; };
 int wgrad_blocks(int64_t rows);
 int64_t wgrad_rows_per_block(int64_t launch_rows);   // rows per block of a weight-gradient launch sized for launch_rows
@@ -112,7 +106,7 @@ struct PackJob { long long off, src; int ldw, r0, nr, nc, transpose, kind; float
 hipError_t launch_pack_train(int L, const PackJob* jobs, int njobs, const float* params, const float* tabs, unsigned* jobmax /* [njobs] scratch */, float* out, hipStream_t s);
 hipError_t launch_wgrad(int L, WgradBatch wb, int64_t rows, hipStream_t s);
 // out[r * cols + c] = sum_b partial[b * block_stride + r * ld + c]   (fixed order: bitwise reproducible), one job per blockIdx.y
-constexpr int REDUCE_MAX_JOBS = 64;
+constexpr int REDUCE_MAX_JOBS = 10;   // one launch unit: five weight blocks, three biases, dgamma and dbeta
 struct ReduceJob { const float* partial; int32_t nblocks; int64_t block_stride; int32_t nrows, cols, ld; float* out; };
 struct ReduceBatch { int32_t njobs; ReduceJob job[REDUCE_MAX_JOBS]; };
 hipError_t launch_reduce_partials(const ReduceBatch& rb, hipStream_t s);

@@ -318,7 +318,6 @@ __global__ __launch_bounds__(64 * WPB) void k_mlp_bwd(const TrainBwdArgs a) {
         const float lsq = sqrtf(q * invL + a.tabs[T_LN * L]);
         const float rstd = 1.0f / (lsq + a.tabs[T_LN * L + 1]);
         const float kappa = lsq > 0.f ? (lsq + a.tabs[T_LN * L + 1]) / lsq : 1.f;
-        if (a.LNROW && rw.valid && h == 0) *reinterpret_cast<float2*>(a.LNROW + 2 * rw.row) = float2{mean, rstd};
         tab_frag<NT>(acc, a.tabs + T_GAMMA * L, h);           // acc = gamma
         float m1 = 0.f, m2 = 0.f;
 #pragma unroll
@@ -381,7 +380,6 @@ __global__ __launch_bounds__(64 * WPB) void k_mlp_bwd(const TrainBwdArgs a) {
         if (rw.valid) store_frag<NT>(row_ptr(a.GX[j], rw.row, L, h), STRIDE_ROW, acc);
     }
     if constexpr (NT == 4 && WPB == 8) {
-        if (a.SEG_RCV) seg_sum_store<NT>(g, a.SEG_RCV, a.SEG_OUT, a.SEG_CARRY, tile, a.rows, rw, c, h);   // g = GZ1, dead from here: SGr
         if (a.ln == 1 && a.LNSUM) {              // the block's eight waves, added in order
             __syncthreads();
             if (threadIdx.x < 2 * L) {
@@ -930,59 +928,6 @@ __global__ __launch_bounds__(256, MGN_WH_BLOCKS) void k_wgrad_h2(const WgradBatc
     const float* __restrict__ G = jb.G;
     const int32_t* __restrict__ xidx = jb.xidx;
     const bool with_w = jb.pw != nullptr;
-    if (jb.Y) {
-        // LayerNorm job: dbeta = column sums of g, dgamma = column sums of g * xhat, with g and xhat rebuilt from the arrays the backward
-        // kernel read (G0 (+ G1), Y) and the row statistics it left -- the same operations in the same order as there.  Thread (rl, lc):
-        // rows r0 + rl, r0 + rl + 8, ..., features 4 lc .. 4 lc + 3, four rows in flight; the eight row lanes are added in a fixed order.
-        const int rl = threadIdx.x >> 5, lc4 = threadIdx.x & 31;
-        const float* __restrict__ Y = jb.Y;
-        const float* __restrict__ G1 = jb.G1;
-        const int32_t* __restrict__ g1i = jb.g1idx;
-        const float2* __restrict__ ST = reinterpret_cast<const float2*>(jb.LNROW);
-        f32x4 sb = {0.f, 0.f, 0.f, 0.f}, sg = {0.f, 0.f, 0.f, 0.f};
-        for (int64_t row = r0 + rl; row < r1; row += 32) {
-            f32x4 gv[4], yv[4], g1v[4];
-            float2 st[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t rr = row + 8 * u < r1 ? row + 8 * u : r0;
-                gv[u] = reinterpret_cast<const f32x4*>(G + rr * L)[lc4];
-                yv[u] = reinterpret_cast<const f32x4*>(Y + rr * L)[lc4];
-                st[u] = ST[rr];
-                if (G1) g1v[u] = reinterpret_cast<const f32x4*>(G1 + (g1i ? (int64_t)g1i[rr] : rr) * L)[lc4];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (row + 8 * u >= r1) break;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float gg = G1 ? gv[u][i] + g1v[u][i] : gv[u][i];
-                    // (one value at a time, fenced: as packed fp32 instructions with op_sel / neg on the loaded (mean, 1 / denominator) pair --
-                    // what hipcc makes of the plain expression, and of an fma form -- the sums of features 4 lc, 4 lc + 2, lc >= 16 differed from
-                    // run to run by ~1e-5 of their value, on every MLP alike; Y alone or the pair alone: stable.  docs/experiments.md)
-                    float d = yv[u][i] - st[u].x;
-                    asm volatile("" : "+v"(d));
-                    float xh = d * st[u].y;
-                    asm volatile("" : "+v"(xh));
-                    sb[i] += gg;
-                    sg[i] += gg * xh;
-                }
-            }
-        }
-        float* const red = smem;                          // [2][8 row lanes][L]
-        *reinterpret_cast<f32x4*>(&red[rl * L + 4 * lc4]) = sb;
-        *reinterpret_cast<f32x4*>(&red[(8 + rl) * L + 4 * lc4]) = sg;
-        __syncthreads();
-        {
-            const int which = threadIdx.x >> 7, f = threadIdx.x & 127;
-            float sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) sum += red[(8 * which + q) * L + f];
-            float* const out = which ? jb.pb2 : jb.pb;
-            if (out) out[(size_t)blockIdx.x * L + f] = sum;
-        }
-        return;
-    }
     // loader role: array (X: threads 0..127, G: 128..255), row group rg (8 rows of the chunk), lc: features 4 lc .. 4 lc + 3
     const int arr = threadIdx.x >> 7, rg = (threadIdx.x >> 5) & 3, lc = threadIdx.x & 31;
     const bool loads = arr == 1 || with_w;
@@ -1581,8 +1526,8 @@ static hipError_t launch_tiles(K kern, const A& a, int ntiles, int L, hipStream_
     return launch_kernel(kern, (unsigned)((ntiles + wpb - 1) / wpb), 64 * wpb, lds, s, a);
 }
 
-// The size rules of the training step are written for 256 CUs, on every device: cooperative tiles up to per_cu * 256 tiles, eight-tile
-// blocks above 8 * 256, at most 4 * 256 weight-gradient blocks, second-stream gradient sets up to 8 * 256 tiles (mgn_train.cpp).  The test
+// The size rules of the training step are written for 256 CUs, on every device: cooperative tiles up to TRAIN_COOP_TILES_PER_CU * 256 tiles,
+// eight-tile blocks above, at most 4 * 256 weight-gradient blocks, second-stream gradient sets over the cooperative range (mgn_train.cpp).  The test
 // CU count (mgn_debug_num_cus) replaces that 256, so that a graph the float64 oracle can check reaches every regime; without an override
 // the literals stand -- the device's own count is never read here.
 int train_size_cus() { const int c = num_cus_override(); return c ? c : 256; }
@@ -1603,19 +1548,10 @@ void train_regime_counts(int* out /* [12] */, bool reset) {
     }
 }
 
-// eight tiles per block once a launch fills the chip twice over with four (L = 128; MGN_TRAIN_WPB = 4 / 8 forces)
-static bool train_wpb8(int L, int ntiles) {
-    static const int forced = env_int("MGN_TRAIN_WPB", 0);
-    if (L != 128) return false;
-    if (forced) return forced == 8;
-    return ntiles > 8 * train_size_cus();
-}
-
-// Cooperative tiles while a launch has fewer than MGN_TRAIN_COOP_TILES_PER_CU tiles per CU (default 8), L = 128.
-static bool train_coop(int L, int ntiles) {
-    static const int per_cu = env_int("MGN_TRAIN_COOP_TILES_PER_CU", 8);
-    return L == 128 && ntiles > 0 && ntiles <= per_cu * train_size_cus();
-}
+// L = 128: a non-empty MLP launch is cooperative up to TRAIN_COOP_TILES_PER_CU tiles per CU and streams with eight tiles per block above
+// (there a launch fills the chip twice over with four).  L = 64 and 32 run the four-tile fp32 kernels at every size.
+static bool train_wpb8(int L, int ntiles) { return L == 128 && ntiles > TRAIN_COOP_TILES_PER_CU * train_size_cus(); }
+static bool train_coop(int L, int ntiles) { return L == 128 && ntiles > 0 && ntiles <= TRAIN_COOP_TILES_PER_CU * train_size_cus(); }
 template <typename K, typename A>
 static hipError_t launch_coop(K kern, const A& a, int ntiles, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), 2 * 16 * 64 * sizeof(f32x4), s, a);
@@ -1623,10 +1559,7 @@ static hipError_t launch_coop(K kern, const A& a, int ntiles, hipStream_t s) {
 }
 
 bool train_uses_coop(int L, int ntiles) { return train_coop(L, ntiles); }
-bool train_fwd_fused_agg(int L, int ntiles) {
-    static const int on = env_int("MGN_TRAIN_FUSED_AGG", 1);
-    return on && L == 128 && !train_coop(L, ntiles) && train_wpb8(L, ntiles);
-}
+bool train_fwd_fused_agg(int L, int ntiles) { return train_wpb8(L, ntiles); }
 hipError_t launch_seg_fixup(int L, const int32_t* rowptr, const float* carry, float* agg, int32_t n, hipStream_t s) {
     const int64_t tot = (int64_t)n * (L / 4);
     if (tot <= 0) return hipSuccess;
@@ -1647,7 +1580,8 @@ hipError_t launch_lin2(int L, const Lin2Args& a, hipStream_t s) {
 }
 
 hipError_t launch_mlp_fwd(int L, int nin, const TrainFwdArgs& a, hipStream_t s) {
-    if (a.ntiles > 0) count_launch(0, train_coop(L, a.ntiles) ? 0 : train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
+    if (a.ntiles <= 0) return hipSuccess;        // (an edge set with E = 0)
+    count_launch(0, train_coop(L, a.ntiles) ? 0 : train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
     if (train_coop(L, a.ntiles)) {
         if (g_train_f16) {
             if (nin == 1) return launch_coop(k_mlp_fwd_coop<1, true>, a, a.ntiles, s);
@@ -1669,12 +1603,6 @@ hipError_t launch_mlp_fwd(int L, int nin, const TrainFwdArgs& a, hipStream_t s) 
         if (nin == 2) return launch_tiles(k_mlp_fwd<4, 2, 8>, a, a.ntiles, L, s, 8);
         if (nin == 3) return launch_tiles(k_mlp_fwd<4, 3, 8>, a, a.ntiles, L, s, 8);
     }
-    if (L == 128 && g_train_f16) {
-        if (nin == 1) return launch_tiles(k_mlp_fwd<4, 1, 4, true>, a, a.ntiles, L, s);
-        if (nin == 2) return launch_tiles(k_mlp_fwd<4, 2, 4, true>, a, a.ntiles, L, s);
-        if (nin == 3) return launch_tiles(k_mlp_fwd<4, 3, 4, true>, a, a.ntiles, L, s);
-    }
-    FWD_CASE(4, 1); FWD_CASE(4, 2); FWD_CASE(4, 3);
     FWD_CASE(2, 1); FWD_CASE(2, 2); FWD_CASE(2, 3);
     FWD_CASE(1, 1); FWD_CASE(1, 2); FWD_CASE(1, 3);
 #undef FWD_CASE
@@ -1682,7 +1610,8 @@ hipError_t launch_mlp_fwd(int L, int nin, const TrainFwdArgs& a, hipStream_t s) 
 }
 
 hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s) {
-    if (a.ntiles > 0) count_launch(1, train_coop(L, a.ntiles) ? 0 : train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
+    if (a.ntiles <= 0) return hipSuccess;
+    count_launch(1, train_coop(L, a.ntiles) ? 0 : train_wpb8(L, a.ntiles) ? 2 : 1, L == 128 && g_train_f16);
     if (train_coop(L, a.ntiles)) {
         if (g_train_f16) {
             if (nin == 1) return launch_coop(k_mlp_bwd_coop<1, true>, a, a.ntiles, s);
@@ -1705,12 +1634,6 @@ hipError_t launch_mlp_bwd(int L, int nin, const TrainBwdArgs& a, hipStream_t s) 
         if (nin == 2) return launch_tiles(k_mlp_bwd<4, 2, 8>, a, a.ntiles, L, s, 8, xl);
         if (nin == 3) return launch_tiles(k_mlp_bwd<4, 3, 8>, a, a.ntiles, L, s, 8, xl);
     }
-    if (L == 128 && g_train_f16) {
-        if (nin == 1) return launch_tiles(k_mlp_bwd<4, 1, 4, true>, a, a.ntiles, L, s);
-        if (nin == 2) return launch_tiles(k_mlp_bwd<4, 2, 4, true>, a, a.ntiles, L, s);
-        if (nin == 3) return launch_tiles(k_mlp_bwd<4, 3, 4, true>, a, a.ntiles, L, s);
-    }
-    BWD_CASE(4, 1); BWD_CASE(4, 2); BWD_CASE(4, 3);
     BWD_CASE(2, 1); BWD_CASE(2, 2); BWD_CASE(2, 3);
     BWD_CASE(1, 1); BWD_CASE(1, 2); BWD_CASE(1, 3);
 #undef BWD_CASE
@@ -1730,22 +1653,11 @@ static bool wgrad_h2_on(int L) {
     static const int h2 = env_int("MGN_WGRAD_H2", 1);      // 0: the fp32 MFMA forms
     return L == 128 && h2 && g_train_f16;
 }
-bool train_bwd_fused_sgr(int L, int ntiles) {
-    static const int on = env_int("MGN_TRAIN_FUSED_SGR", 0);   // (built, parity green, same box 0.304 s against 0.302 with k_segment_sum_pair: off)
-    return on && L == 128 && !train_coop(L, ntiles) && train_wpb8(L, ntiles);
-}
-bool train_bwd_ln_sums(int L, int ntiles) {
-    static const int on = env_int("MGN_TRAIN_BWD_LN_SUMS", 1);   // LayerNorm-parameter sums inside the streaming backward kernel (0: the LayerNorm job of the weight-gradient launch)
-    return on && L == 128 && !train_coop(L, ntiles) && train_wpb8(L, ntiles);
-}
+bool train_bwd_ln_sums(int L, int ntiles) { return train_wpb8(L, ntiles); }
 hipError_t launch_colsum_groups(const float* part, int nblocks, int cols, int groups, float* out, hipStream_t s) {
     if (nblocks <= 0 || groups <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_colsum_groups, dim3(groups), dim3(256), 0, s, part, nblocks, cols, groups, out);
     return hipGetLastError();
-}
-bool wgrad_ln_jobs(int L) {
-    static const int on = env_int("MGN_WGRAD_LN_JOBS", 1);  // 0: GT / G xhat rows written by the backward kernel, two column-sum jobs
-    return on && wgrad_h2_on(L);
 }
 int wgrad_blocks_of_job(int64_t launch_rows, int64_t job_rows) {
     if (launch_rows <= 0 || job_rows <= 0) return 0;
@@ -1899,10 +1811,8 @@ hipError_t launch_wgrad(int L, WgradBatch wb, int64_t rows, hipStream_t s) {
     if (nb == 0 || wb.njobs <= 0) return hipSuccess;
     wb.rows_per_block = wgrad_rows_per_block(rows);
     const dim3 grid(nb, wb.njobs);
-    static const int lds = env_int("MGN_WGRAD_LDS", 1);   // 0: k_wgrad<4> (4-byte operand loads)
     if (wgrad_h2_on(L)) return launch_kernel(k_wgrad_h2, grid, 256, WH_LDS, s, wb);
-    if (L == 128 && lds) hipLaunchKernelGGL(k_wgrad_lds, grid, dim3(256), 0, s, wb);
-    else if (L == 128) hipLaunchKernelGGL(k_wgrad<4>, grid, dim3(256), 0, s, wb);
+    if (L == 128) hipLaunchKernelGGL(k_wgrad_lds, grid, dim3(256), 0, s, wb);
     else if (L == 64) hipLaunchKernelGGL(k_wgrad<2>, grid, dim3(128), 0, s, wb);
     else if (L == 32) hipLaunchKernelGGL(k_wgrad<1>, grid, dim3(64), 0, s, wb);
     else return hipErrorInvalidValue;
