@@ -299,7 +299,8 @@ int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d);
  * alone (no floating-point atomics): bitwise repeatable.  One synchronisation, at the end.
  * Refusals: everything mgn_rollout refuses; MGN_E_ARG for a NULL e or gt, n_gt < n_saves, n_sel < 0, n_sel > 0 without sel, a
  * sel_index_base other than 0 or 1, a sel entry outside [0, N * O); MGN_E_UNSUPPORTED on a partitioned handle (nranks != 1: call
- * mgn_rollout and reduce on the host).  The handle stays usable after any of them.                                                 */
+ * mgn_rollout and reduce on the host, or drive the partitions through a group: mgn_group_rollout_eval reduces on the ranks).  The
+ * handle stays usable after any of them.                                                                                           */
 typedef struct mgn_rollout_eval_desc {
     const float* gt;        /* [n_gt][N][O], host or device, caller's node order; may be the same pointer as d->inflow_data         */
     int32_t n_gt;           /* >= d->n_saves; save i is compared with gt[i]                                                          */
@@ -352,7 +353,8 @@ int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt /* [n_sa
  * Every save is stepped onto (tstops = saves); a MultipleShooting window solved without tstops interpolates its saves in the reference.
  * Memory: the six stage inputs z_{n,1..6} of every accepted step, 6 N O floats per step, in chunks kept on the handle and grown as steps
  * are accepted; allocation failure or more than o->max_store_bytes (0: no limit) is MGN_E_OOM, and the handle stays usable.
- * Bitwise repeatable.                                                                                                               */
+ * Through mgn_group_solver_grad_tsit5 the memory and max_store_bytes are PER RANK (6 n_own O floats per step on each rank).
+ * Bitwise repeatable.                                                                                                             */
 typedef struct mgn_solver_grad_opts {
     int32_t adaptive;          /* 1: PI-controlled steps with tstops = saves (mgn_rollout's Tsit5); 0: fixed steps of d->dt         */
     int32_t step_cap;          /* capacity of step_t / step_h (0: no record)                                                       */
@@ -417,7 +419,8 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
  * steps are decided per rank for its own arena.  Refusals: MGN_E_STATE naming mgn_comm_init without a communicator,
  * MGN_E_UNSUPPORTED with two edge sets, MGN_E_ARG for a wrong n_grads -- all before the first collective, so no rank is left
  * waiting.  The other training entry points (mgn_ode_vjp, mgn_forward_vjp, mgn_solver_grad, mgn_solver_grad_tsit5,
- * mgn_shooting_grad) drive one partition: MGN_E_STATE on a partitioned handle.
+ * mgn_shooting_grad) drive one partition on rank handles: MGN_E_STATE on a partitioned handle.  Their partitioned forms are reached
+ * through the group: see mgn_group_ode_vjp, mgn_group_forward_vjp, mgn_group_solver_grad and mgn_group_solver_grad_tsit5.
  * Memory: a large mesh stores the activations of as
  * many processor steps as the device's free memory (hipMemGetInfo) minus MGN_TRAIN_RESERVE_GB (16) holds and recomputes the others
  * in the reverse pass -- the first handle on a device takes the stored steps, a later one recomputes; a refused allocation is retried
@@ -628,6 +631,38 @@ int mgn_group_train_norm_state(mgn_group* g, int32_t group, int32_t write, doubl
 int mgn_group_step_datapoint(mgn_group* g, int32_t datapoint, int32_t accumulate, const int32_t* mask, int64_t nmask,
                              int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
 int mgn_group_datapoint_export(mgn_group* g, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target);
+/* Solver-based training (SolverTraining; MultipleShooting window by window) and the validation rollout on the partitioned mesh.  The
+ * rank-handle symbols of the same names keep refusing a partitioned handle; these five reach the same drivers with partitions served.
+ * Arguments are those of the namesake with GLOBAL host arrays (x, lambda, nf, ybar, gt, cont_target, val_mask, inflow mask and data,
+ * sel: indices into the whole mesh's [N][O]); results are complete and in the caller's order (xbar, nfbar, dxdt, out, d->out,
+ * mse_time through a row gather), the same bits on every rank, rank 0's returned.  nranks == 1: the plain call, the same bits.
+ *   Each rank integrates and sweeps the rows it owns; every right-hand side and every VJP of the sweep exchanges halo rows as mgn_step
+ *   does (mps forward exchanges, and mps reverse ones per VJP, each before the node MLP below is unwound); the solve runs eagerly.
+ *   The adaptive controller's error norm is reduced over the ranks to the same bits, so every rank takes the same steps.
+ *   Divisors are the whole mesh's: the save term of the loss and its seed use n_saves N O, mse_save N, val_loss n_sel (N O when
+ *   n_sel == 0); a sel entry counts on the rank that owns its node, as often as it is listed; a rank that owns none of sel, or whose
+ *   share of val_mask is zero, still takes part in every exchange.
+ *   Finish, once per call: mgn_group_solver_grad* gathers every rank's DOUBLE gradient accumulator and its two loss sums (save terms,
+ *   continuity term) and adds them in ascending rank order in double with one kernel on every rank; the gradient is rounded to fp32
+ *   there, once.  mgn_group_rollout_eval folds the [n_saves][O] per-save sums and the val_loss numerator the same way.  mgn_group_ode_vjp
+ *   and mgn_group_forward_vjp fold the fp32 gradient as mgn_step's finish does.  No floating-point atomics: bitwise repeatable.
+ *   Memory is per rank: fixed-step Euler stores (K + 1) n_own O floats of states, Tsit5 6 n_own O floats per accepted step;
+ *   mgn_solver_grad_opts.max_store_bytes bounds EACH rank's stored stage inputs, and stored_bytes, n_steps and the step record are
+ *   rank 0's (the steps are the same on every rank, stored_bytes is rank 0's own 24 n_own O bytes per step).
+ *   mgn_group_rollout_eval with d->out == NULL gathers and downloads nothing of [n_saves][N][O] on any rank.
+ *   Every argument check (time grid, n_grads, fp32, one edge set, communicator, sel range) comes before the first collective; the
+ *   status is the rank-handle call's for the same mistake.  A rank-local failure later (an allocation) releases the peers through the
+ *   group's abort.  Not built: a group form of mgn_shooting_grad -- loop over the windows with mgn_group_solver_grad*; bf16, two edge sets and
+ *   ln_dims = MGN_LN_ALL stay single-partition.                                                                                    */
+int mgn_group_ode_vjp(mgn_group* g, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask,
+                      const float* lambda, float* dxdt, float* xbar, float* grads, size_t n_grads);
+int mgn_group_forward_vjp(mgn_group* g, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads,
+                          size_t n_grads);
+int mgn_group_solver_grad(mgn_group* g, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target,
+                          float cont_weight, float* grads, size_t n_grads, float* loss);
+int mgn_group_solver_grad_tsit5(mgn_group* g, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
+                                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss);
+int mgn_group_rollout_eval(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e);
 int mgn_group_latents_randn(mgn_group* g, uint64_t seed);
 int mgn_group_processor_steps_dev(mgn_group* g, int32_t nsteps);
 int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, double* sumsq_v, double* sumsq_e);

@@ -161,6 +161,12 @@ PROTOTYPES = {
     "mgn_group_train_norm_state": (C.c_int, [_H, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
     "mgn_group_step_datapoint": (C.c_int, [_H, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
     "mgn_group_datapoint_export": (C.c_int, [_H, C.c_int32, C.c_int32, _f32p, _f32p, _f32p]),
+    "mgn_group_ode_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
+    "mgn_group_forward_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
+    "mgn_group_solver_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f32p, _f32p, _f32p, C.c_float, _f32p, C.c_size_t, _f32p]),
+    "mgn_group_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float,
+                                              _f32p, C.c_size_t, _f32p]),
+    "mgn_group_rollout_eval": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnRolloutEvalDesc)]),
     "mgn_group_latents_randn": (C.c_int, [_H, C.c_uint64]),
     "mgn_group_processor_steps_dev": (C.c_int, [_H, C.c_int32]),
     "mgn_group_latents_checksum": (C.c_int, [_H, _f64p, _f64p, _f64p, _f64p]),

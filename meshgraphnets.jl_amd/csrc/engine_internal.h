@@ -189,6 +189,7 @@ struct mgn_engine {
     mgn::Comm* comm = nullptr;
     int32_t force_staged = 0;                 // MGN_FORCE_STAGED=1: staged schedule even at nranks == 1 (self-test)
     DevBuf halo_send, halo_recv, gath_s, gath_r;
+    DevBuf fold_s, fold_r;                    // rank_fold_f64: this rank's doubles, then every rank's and the folded head
     std::vector<size_t> hx_sb, hx_so, hx_rb, hx_ro;   // per-peer byte counts / offsets of one exchange (rebuilt per graph)
     bool hx_ready = false;
     bool hx_direct = false;                   // rows are received straight into the halo block of P (one edge set)
@@ -285,8 +286,21 @@ int rebuild_graph(mgn_engine* h, int32_t N, const EdgeList* sets, const float* m
                   const int32_t* owner_in = nullptr, int renumber = -1);
 int need_comm(mgn_engine* h, const char* who);
 int gather_rows_global(mgn_engine* h, const float* local_dev, int W, float* out);
+int rank_fold_f64(mgn_engine* h, double* head, int64_t nhead, const double* acc, int64_t n, float* out);
 bool is_bf16(const mgn_engine* h);
 void shoot_release(mgn_engine* h);     // mgn_solve.cpp: drops mgn_shooting_grad's companions and staging
+// The drivers behind mgn_ode_vjp, mgn_forward_vjp (mgn_train.cpp), mgn_solver_grad, mgn_solver_grad_tsit5 and mgn_rollout_eval
+// (mgn_solve.cpp): the public symbols' checks and work, with `partitions` saying whether a partitioned handle (nranks > 1) is served.
+// The rank-handle symbols pass false and keep their refusals; mgn_group_* (mgn_group.cpp) passes true.  On a partitioned call every
+// check comes before the first collective; inputs are the GLOBAL host arrays, results the complete ones on every rank.
+int ode_vjp_run(mgn_engine* h, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask, const float* lambda,
+                float* dxdt, float* xbar, float* grads, size_t n_grads, bool partitions);
+int forward_vjp_run(mgn_engine* h, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads, size_t n_grads,
+                    bool partitions);
+int solver_grad_run(mgn_engine* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
+                    const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions);
+int rollout_eval_run(mgn_engine* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions);
+int solver_prepare_partitions(mgn_engine* h, const char* who, size_t n_grads);   // solver_prepare for a call that serves partitions too
 #pragma GCC visibility pop
 
 #define HIPCHK(h, expr)                                                                              \

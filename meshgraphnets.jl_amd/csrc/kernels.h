@@ -204,6 +204,7 @@ struct EvalFinish {
     float* mse_time;          // [N][O] in the caller's order, or null
     double* mse_save;         // [n_saves][O], or null
     double* vpart;            // [save_error_blocks(n_val)]: add them in order and divide by n_val
+    double save_div;          // mse_save's divisor (0: N; a partition passes 1 and divides the ranks' folded sums by the mesh's N)
     int blocks, val_blocks, time_blocks;   // filled by launch_eval_finish
 };
 hipError_t launch_eval_finish(EvalFinish f, hipStream_t s);

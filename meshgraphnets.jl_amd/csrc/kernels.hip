@@ -2437,7 +2437,7 @@ __global__ __launch_bounds__(256) void k_save_error(const float* __restrict__ x,
 //   val_blocks:   the mean over the saves, acc / n_saves, of the n_val selected elements (sel: their indices in the engine's order; null:
 //                 elements 0 .. n_val - 1), summed per block in k_save_error's order -> vpart[block]; the caller adds them in block order
 //   time_blocks:  mse_time[caller's row][o] = float(acc[row][o] / n_saves), rounded once
-//   the others:   mse_save[i][o] = (sum over the blocks, in block order, of part[i][block][o]) / N, one thread per (i, o)
+//   the others:   mse_save[i][o] = (sum over the blocks, in block order, of part[i][block][o]) / N (save_div > 0: / save_div), one thread per (i, o)
 __global__ __launch_bounds__(256) void k_eval_finish(EvalFinish f) {
     __shared__ double sh[4];
     const double ns = (double)f.n_saves;
@@ -2470,7 +2470,7 @@ __global__ __launch_bounds__(256) void k_eval_finish(EvalFinish f) {
     const double* p = f.part + (size_t)i * f.blocks * f.O + o;
     double s = 0.0;
     for (int b = 0; b < f.blocks; ++b) s += p[(size_t)b * f.O];
-    f.mse_save[t] = s / (double)f.N;
+    f.mse_save[t] = s / (f.save_div > 0.0 ? f.save_div : (double)f.N);
 }
 
 int save_error_blocks(int64_t rows) {

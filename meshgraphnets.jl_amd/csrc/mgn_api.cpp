@@ -1899,6 +1899,27 @@ extern "C++" int mgn::gather_rows_global(mgn_handle* h, const float* local_dev, 
     return MGN_OK;
 }
 
+// The once-per-call fold of a partitioned solve's sums (mgn_group_solver_grad*, mgn_group_rollout_eval): this rank's head [nhead] doubles
+// (host) and acc [n] doubles (device; null: zeros) are gathered from every rank and added in ascending rank order, in double, by
+// k_rank_sum_f64 on every rank -- head comes back as the ranks' sums, out [n] (device) as their sum rounded to fp32 once.  The same bits
+// on every rank; blocks.  An allgather and one kernel, not allreduce_f64: the RCCL transport's allreduce does not promise an order.
+extern "C++" int mgn::rank_fold_f64(mgn_handle* h, double* head, int64_t nhead, const double* acc, int64_t n, float* out) {
+    const int P = h->cfg.nranks;
+    const size_t stride = (size_t)rank_sum_f64_stride(nhead, n);
+    HIPCHK(h, h->fold_s.ensure(stride * 8));
+    HIPCHK(h, h->fold_r.ensure((stride * P + (size_t)nhead) * 8));
+    double* s = h->fold_s.as<double>();
+    double* r = h->fold_r.as<double>();
+    HIPCHK(h, hipMemsetAsync(s, 0, stride * 8, h->stream));
+    if (nhead > 0) HIPCHK(h, hipMemcpyAsync(s, head, (size_t)nhead * 8, hipMemcpyHostToDevice, h->stream));
+    if (acc && n > 0) HIPCHK(h, hipMemcpyAsync(s + nhead, acc, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+    COMMCHK(h, h->comm->allgather(s, stride * 8, r, h->stream));
+    HIPCHK(h, launch_rank_sum_f64(r, P, nhead, n, r + stride * P, out, h->stream));
+    if (nhead > 0) HIPCHK(h, hipMemcpyAsync(head, r + stride * P, (size_t)nhead * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+}
+
 // mgn.model(graph, ps, st) on a partitioned mesh: every rank encodes what it owns, the processor runs the staged schedule,
 // the decoded rows are gathered so that every rank returns the complete output
 static int forward_partitioned(mgn_handle* h, const float* nf, const float* ef, float* out) {

@@ -113,6 +113,24 @@ struct mgn_group {
         if (scratch[k].size() < count * sizeof(T)) scratch[k].resize(count * sizeof(T));
         return reinterpret_cast<T*>(scratch[k].data());
     }
+    // A call with up to three float outputs.  out_of hands out the START of the rank's scratch, so two uses in one call would alias and
+    // the second could move the first: here the pieces lie one behind the other in one allocation.  A NULL of the caller stays NULL.
+    struct Outs { float* p[3]; };
+    Outs outs_of(int k, float* c0, size_t n0, float* c1, size_t n1, float* c2 = nullptr, size_t n2 = 0) {
+        if (k == 0) return Outs{{c0, c1, c2}};
+        float* const callers[3] = {c0, c1, c2};
+        const size_t counts[3] = {n0, n1, n2};
+        size_t total = 0;
+        for (int i = 0; i < 3; ++i) total += callers[i] ? counts[i] : 0;
+        float* base = out_of<float>(k, c0 ? c0 : (c1 ? c1 : c2), total);
+        Outs o{};
+        size_t off = 0;
+        for (int i = 0; i < 3; ++i) {
+            o.p[i] = callers[i] ? base + off : nullptr;
+            off += callers[i] ? counts[i] : 0;
+        }
+        return o;
+    }
 };
 #pragma GCC visibility pop
 
@@ -311,6 +329,122 @@ int mgn_group_step_datapoint(mgn_group* g, int32_t datapoint, int32_t accumulate
 // every rank writes the rows of its own nodes and edges into the caller's arrays: disjoint rows, complete arrays
 int mgn_group_datapoint_export(mgn_group* g, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target) {
     GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_datapoint_export(h, datapoint, normalised, nf, ef, target); }); } GROUP_CATCH(g)
+}
+
+// Solver-based training and the validation rollout on the partitioned mesh: the drivers behind the rank-handle symbols of the same
+// names, told to serve partitions (the symbols themselves keep refusing them).  Every rank is handed the caller's GLOBAL host arrays
+// and returns the complete result; rank 0 writes the caller's buffers, descriptors and counters.  A group of one is the plain call.
+extern "C++" {
+namespace {
+// the driver's C++ exceptions end here, as MGN_CATCH ends them in the rank-handle symbols
+template <typename F> int guarded(mgn_handle* h, F&& f) try { return f(); } MGN_CATCH(h)
+}  // namespace
+}
+
+int mgn_group_ode_vjp(mgn_group* g, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask, const float* lambda,
+                      float* dxdt, float* xbar, float* grads, size_t n_grads) {
+    GROUP_TRY(g) {
+        const size_t n = (size_t)g->N * g->cfg.O;
+        return g->run([&](int k, mgn_handle* h) {
+            return guarded(h, [&] {
+                const mgn_group::Outs o = g->outs_of(k, dxdt, n, xbar, n, grads, n_grads);
+                return mgn::ode_vjp_run(h, x, node_type_onehot, ef_raw, val_mask, lambda, o.p[0], o.p[1], o.p[2], n_grads, true);
+            });
+        });
+    } GROUP_CATCH(g)
+}
+
+int mgn_group_forward_vjp(mgn_group* g, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads, size_t n_grads) {
+    GROUP_TRY(g) {
+        const size_t N = (size_t)g->N;
+        return g->run([&](int k, mgn_handle* h) {
+            return guarded(h, [&] {
+                const mgn_group::Outs o = g->outs_of(k, out, N * g->cfg.O, nfbar, N * g->cfg.Fn, grads, n_grads);
+                return mgn::forward_vjp_run(h, nf, ef, ybar, o.p[0], o.p[1], o.p[2], n_grads, true);
+            });
+        });
+    } GROUP_CATCH(g)
+}
+
+extern "C++" {
+namespace {
+// mgn_group_solver_grad (o null) and mgn_group_solver_grad_tsit5: every rank its own copy of the descriptors (counters, the step record),
+// rank 0's go back
+int group_solver_grad(mgn_group* g, const char* who, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
+                      const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) {
+    if (!d || (tsit5 && !o)) return gfail(g, MGN_E_ARG, (std::string(who) + ": null argument").c_str());
+    const size_t n = (size_t)(d->n_saves > 0 ? d->n_saves : 0) * g->N * g->cfg.O;
+    const size_t cap = o && o->step_cap > 0 ? (size_t)o->step_cap : 0;
+    std::vector<mgn_rollout_desc> ds(g->P, *d);
+    std::vector<mgn_solver_grad_opts> os(g->P, o ? *o : mgn_solver_grad_opts{});
+    std::vector<std::vector<double>> rec(g->P);          // the step records of the ranks other than 0
+    std::vector<float> losses(g->P, 0.f);
+    const int rc = g->run([&](int k, mgn_handle* h) {
+        return guarded(h, [&] {
+            const mgn_group::Outs outs = g->outs_of(k, d->out, n, grads, n_grads);
+            ds[k].out = outs.p[0];
+            if (o && k > 0) {
+                rec[k].assign(2 * cap, 0.0);
+                if (o->step_t) os[k].step_t = rec[k].data();
+                if (o->step_h) os[k].step_h = rec[k].data() + cap;
+            }
+            return mgn::solver_grad_run(h, &ds[k], o ? &os[k] : nullptr, tsit5, gt, loss_scale, cont_target, cont_weight, outs.p[1], n_grads,
+                                        k == 0 || !loss ? loss : &losses[k], true);
+        });
+    });
+    d->n_accept = ds[0].n_accept;
+    d->n_reject = ds[0].n_reject;
+    d->n_rhs = ds[0].n_rhs;
+    if (o) {
+        o->n_steps = os[0].n_steps;
+        o->stored_bytes = os[0].stored_bytes;
+    }
+    return rc;
+}
+}  // namespace
+}
+
+int mgn_group_solver_grad(mgn_group* g, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
+                          float* grads, size_t n_grads, float* loss) {
+    GROUP_TRY(g) {
+        return group_solver_grad(g, "mgn_group_solver_grad", d, nullptr, false, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+    } GROUP_CATCH(g)
+}
+
+int mgn_group_solver_grad_tsit5(mgn_group* g, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
+                                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) {
+    GROUP_TRY(g) {
+        return group_solver_grad(g, "mgn_group_solver_grad_tsit5", d, o, true, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+    } GROUP_CATCH(g)
+}
+
+int mgn_group_rollout_eval(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) {
+    GROUP_TRY(g) {
+        if (!d || !e) return gfail(g, MGN_E_ARG, "mgn_group_rollout_eval: null argument");
+        const size_t no = (size_t)g->N * g->cfg.O, ns = (size_t)(d->n_saves > 0 ? d->n_saves : 0);
+        std::vector<mgn_rollout_desc> ds(g->P, *d);
+        std::vector<mgn_rollout_eval_desc> es(g->P, *e);
+        std::vector<std::vector<double>> ms(g->P);       // mse_save of the ranks other than 0 (doubles; the float outputs share the scratch)
+        const int rc = g->run([&](int k, mgn_handle* h) {
+            return guarded(h, [&] {
+                if (k > 0) {      // d->out [n_saves][N][O], then mse_time [N][O], in this rank's scratch
+                    const mgn_group::Outs o = g->outs_of(k, d->out, ns * no, e->mse_time, no);
+                    ds[k].out = o.p[0];
+                    es[k].mse_time = o.p[1];
+                    if (e->mse_save) {
+                        ms[k].assign(ns * g->cfg.O, 0.0);
+                        es[k].mse_save = ms[k].data();
+                    }
+                }
+                return mgn::rollout_eval_run(h, &ds[k], &es[k], true);
+            });
+        });
+        d->n_accept = ds[0].n_accept;
+        d->n_reject = ds[0].n_reject;
+        d->n_rhs = ds[0].n_rhs;
+        e->val_loss = es[0].val_loss;
+        return rc;
+    } GROUP_CATCH(g)
 }
 
 int mgn_group_latents_randn(mgn_group* g, uint64_t seed) {

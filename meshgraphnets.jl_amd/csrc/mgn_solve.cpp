@@ -502,10 +502,10 @@ int upload_statics(mgn_handle* h, const mgn_rollout_desc* d, const float* x0, ch
 }
 
 // the handle's state that solver-based training needs: a device handle, one partition, fp32, one edge set, parameters and a graph
-int solver_state_checks(mgn_handle* h, const char* who) {
+int solver_state_checks(mgn_handle* h, const char* who, bool partitions = false) {
     if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
     const mgn_config& c = h->cfg;
-    if (c.nranks != 1) return fail(h, MGN_E_STATE, "%s drives one partition", who);
+    if (c.nranks != 1 && !partitions) return fail(h, MGN_E_STATE, "%s drives one partition", who);
     if (c.dtype != MGN_F32) return fail(h, MGN_E_STATE, "%s computes in fp32: create the handle with dtype MGN_F32", who);
     if (h->nsets != 1) return fail(h, MGN_E_STATE, "%s mirrors the reference's single-edge-set RHS (src/solve.jl:188-219); this handle has two edge sets", who);
     return need(h, true, true, c.ln_dims != MGN_LN_ALL, true);
@@ -527,11 +527,19 @@ int inflow_checks(mgn_handle* h, const mgn_rollout_desc* d, const char* who) {
 }
 
 // count [N][O] arrays (host or device, the caller's order) into the engine's order at dst, gathered on the device through tmp ([N][O] scratch)
-// when the graph is renumbered
+// when the graph is renumbered.  A partition keeps the rows it owns of every array: dst is [count][n_own][O], tmp still [N][O]
 int to_engine_order(mgn_handle* h, const float* src, int64_t count, float* dst, float* tmp) {
     const int32_t N = h->g.N;
     const int O = h->cfg.O;
     const size_t n = (size_t)N * O;
+    if (h->cfg.nranks != 1) {
+        const size_t nl = (size_t)h->g.n_own * O;
+        for (int64_t s = 0; s < count; ++s) {
+            HIPCHK(h, hipMemcpyAsync(tmp, src + s * n, n * 4, hipMemcpyDefault, h->stream));
+            HIPCHK(h, launch_permute_rows(dst + s * nl, tmp, h->d_own_gid.as<int32_t>(), h->g.n_own, O, false, h->stream));
+        }
+        return MGN_OK;
+    }
     for (int64_t s = 0; s < count; ++s) {
         HIPCHK(h, hipMemcpyAsync(h->g.renumbered ? tmp : dst + s * n, src + s * n, n * 4, hipMemcpyDefault, h->stream));
         if (h->g.renumbered) HIPCHK(h, launch_permute_rows(dst + s * n, tmp, h->d_own_gid.as<int32_t>(), N, O, false, h->stream));
@@ -539,8 +547,12 @@ int to_engine_order(mgn_handle* h, const float* src, int64_t count, float* dst, 
     return MGN_OK;
 }
 
-// mgn_rollout (e null) and mgn_rollout_eval (e: its checked descriptor, one partition): the same solve, the same launches in the same
-// order; with e every save is reduced against its ground-truth frame as it is produced (Rollout::save) and d->out is optional
+// mgn_rollout (e null) and mgn_rollout_eval (e: its checked descriptor): the same solve, the same launches in the same order; with e
+// every save is reduced against its ground-truth frame as it is produced (Rollout::save) and d->out is optional.
+// e on a partitioned mesh (mgn_group_rollout_eval): every rank reduces the rows it owns -- sel's entries whose node it owns, mapped to
+// its rows, as often as they are listed --, then the ranks' sums ([n_saves][O] per-save sums and the val_loss numerator, undivided) are
+// folded once in ascending rank order (rank_fold_f64) and divided by the whole mesh's counts; mse_time's rows go through
+// gather_rows_global.  Without d->out no save is kept, gathered or downloaded on any rank.
 int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who) {
     const bool lnall = h && h->cfg.ln_dims == MGN_LN_ALL;
     if (int rc = need(h, true, true, !lnall, true)) return rc;
@@ -567,9 +579,19 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     // engine's order (n_sel == 0: all elements, no index array)
     const bool gt_is_frames = e && e->gt == d->inflow_data && d->n_frames >= d->n_saves;
     const int eblk = e ? save_error_blocks(nloc) : 0;
-    const int64_t n_val = e ? (e->n_sel > 0 ? e->n_sel : R.n) : 0;
+    int64_t n_val = e ? (e->n_sel > 0 ? e->n_sel : R.n) : 0;      // the elements this handle sums (a partition: those it owns)
+    const int64_t n_val_all = e ? (e->n_sel > 0 ? e->n_sel : R.n_global) : 0;   // the divisor: the whole mesh's
     std::vector<int64_t> sel;
-    if (e && e->n_sel > 0) {
+    if (e && e->n_sel > 0 && part) {
+        std::vector<int32_t> g2l((size_t)g.N, -1);
+        for (int32_t i = 0; i < g.n_own; ++i) g2l[(size_t)g.own_gid[i]] = i;
+        for (int64_t i = 0; i < e->n_sel; ++i) {
+            const int64_t li = (int64_t)e->sel[i] - e->sel_index_base;      // (checked by rollout_eval_run)
+            const int32_t l = g2l[(size_t)(li / c.O)];
+            if (l >= 0) sel.push_back((int64_t)l * c.O + li % c.O);
+        }
+        n_val = (int64_t)sel.size();       // (0: this rank owns none of sel and still takes part in every exchange)
+    } else if (e && e->n_sel > 0) {
         std::vector<int32_t> g2l;
         if (g.renumbered) {
             g2l.resize((size_t)g.N);
@@ -586,7 +608,8 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)nloc), o_part = a.take(errnorm_partials() * sizeof(double));
     R.elat0_off = a.take(eb);
     const size_t o_eacc = a.take(e ? (size_t)R.n * 8 : 0), o_epart = a.take((size_t)d->n_saves * eblk * c.O * 8),
-                 o_egt = a.take(e && !gt_is_frames ? (size_t)d->n_saves * nb : 0), o_etmp = a.take(e && !gt_is_frames && g.renumbered ? nb : 0),
+                 o_egt = a.take(e && !gt_is_frames ? (size_t)d->n_saves * nb : 0),
+                 o_etmp = a.take(e && !gt_is_frames && (g.renumbered || part) ? (size_t)g.N * c.O * 4 : 0),
                  o_esel = a.take(sel.size() * 8), o_evp = a.take(e ? (size_t)save_error_blocks(n_val) * 8 : 0),
                  o_ems = a.take(e && e->mse_save ? (size_t)d->n_saves * c.O * 8 : 0), o_emt = a.take(e && e->mse_time ? nb : 0);
     HIPCHK(h, h->ode.ensure(a.off));
@@ -611,8 +634,8 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
 
     d->n_accept = d->n_reject = 0;
     if (int rc = d->solver == 0 ? R.euler_rollout() : R.tsit5_adaptive(who, nullptr)) return rc;
-    if (part) {     // every rank returns the complete solution
-        for (int i = 0; i < d->n_saves; ++i)
+    if (part) {     // every rank returns the complete solution (mgn_rollout_eval without d->out: none is kept)
+        for (int i = 0; d->out && i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
     } else if (d->out) {
         if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
@@ -620,8 +643,9 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     std::vector<double> vpart;
     if (e) {
         EvalFinish f{};
-        f.acc = R.ev_acc; f.part = R.ev_part; f.N = g.N; f.O = c.O; f.n_saves = d->n_saves;
-        f.gid = g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+        f.acc = R.ev_acc; f.part = R.ev_part; f.N = nloc; f.O = c.O; f.n_saves = d->n_saves;
+        f.gid = g.renumbered && !part ? h->d_own_gid.as<int32_t>() : nullptr;     // (a partition's mse_time rows stay in its order: gathered below)
+        f.save_div = part ? 1.0 : 0.0;                                            // (a partition's per-save SUMS: divided after the fold)
         f.sel = sel.empty() ? nullptr : (const int64_t*)(base + o_esel);
         f.n_val = n_val;
         f.mse_time = e->mse_time ? (float*)(base + o_emt) : nullptr;
@@ -630,6 +654,22 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
         HIPCHK(h, launch_eval_finish(f, h->stream));
         vpart.resize((size_t)save_error_blocks(n_val));
         HIPCHK(h, hipMemcpyAsync(vpart.data(), f.vpart, vpart.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        if (part) {
+            // this rank's sums -- [n_saves][O] per-save sums (zeros when not wanted), then the val_loss numerator, the blocks' sums in
+            // block order -- folded over the ranks in ascending order by one kernel on the gathered doubles (rank_fold_f64; not
+            // allreduce_f64: only the host and local transports add in rank order there)
+            const size_t ns = (size_t)d->n_saves * c.O;
+            std::vector<double> head(ns + 1, 0.0);
+            if (e->mse_save) HIPCHK(h, hipMemcpyAsync(head.data(), f.mse_save, ns * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (double v : vpart) head[ns] += v;
+            if (int rc = rank_fold_f64(h, head.data(), (int64_t)head.size(), nullptr, 0, nullptr)) return rc;
+            for (size_t i = 0; e->mse_save && i < ns; ++i) e->mse_save[i] = head[i] / (double)g.N;
+            if (e->mse_time) if (int rc = gather_rows_global(h, f.mse_time, c.O, e->mse_time)) return rc;
+            d->n_rhs = R.n_rhs;
+            e->val_loss = head[ns] / (double)n_val_all;
+            return MGN_OK;
+        }
         if (e->mse_save) HIPCHK(h, hipMemcpyAsync(e->mse_save, f.mse_save, (size_t)d->n_saves * c.O * 8, hipMemcpyDeviceToHost, h->stream));
         if (e->mse_time) HIPCHK(h, hipMemcpyAsync(e->mse_time, f.mse_time, nb, hipMemcpyDefault, h->stream));
     }
@@ -649,15 +689,14 @@ extern "C" int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     return rollout_solve(h, d, nullptr, "mgn_rollout");
 } MGN_CATCH(h)
 
-extern "C" int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) try {
+int mgn::rollout_eval_run(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions) {
     static const char* who = "mgn_rollout_eval";
-    if (!h) return MGN_E_ARG;
     // the descriptor first (a host-only handle answers it too)
     if (!d || !e || !e->gt) return fail(h, MGN_E_ARG, "%s: null argument", who);
     if (e->n_gt < d->n_saves) return fail(h, MGN_E_ARG, "%s: n_gt = %d ground-truth frames for n_saves = %d saves", who, e->n_gt, d->n_saves);
     if (e->n_sel < 0 || (e->n_sel > 0 && !e->sel)) return fail(h, MGN_E_ARG, "%s: n_sel must be >= 0, and sel given when it is > 0", who);
     if (e->sel_index_base != 0 && e->sel_index_base != 1) return fail(h, MGN_E_ARG, "%s: sel_index_base must be 0 or 1", who);
-    if (h->cfg.nranks != 1)
+    if (h->cfg.nranks != 1 && !partitions)
         return fail(h, MGN_E_UNSUPPORTED, "%s drives one partition: on a partitioned handle call mgn_rollout and reduce the solution on the host", who);
     if (h->have_graph) {
         const int64_t n = (int64_t)h->g.N * h->cfg.O;
@@ -670,12 +709,19 @@ extern "C" int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_
     }
     e->val_loss = 0.0;
     return rollout_solve(h, d, e, who);      // (without a graph it refuses before sel is read)
+}
+
+extern "C" int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) try {
+    if (!h) return MGN_E_ARG;
+    return rollout_eval_run(h, d, e, false);
 } MGN_CATCH(h)
 
 // ---- solver-based training (SolverTraining / MultipleShooting): loss and gradient of one solved window ------------------------------
 // Forward: mgn_rollout's time loop on the resident right-hand side (the same launches, the same hipGraph replay), in the training form of
 // the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the arrays the RHS saw.
-// Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One partition, one edge set, fp32; the state in the engine's order throughout.
+// Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One edge set, fp32; the state in the engine's order throughout.  One partition
+// on a rank handle; through the group (partitions = true) the state is the rows a rank owns, every VJP of the sweep runs the partitioned
+// TrainPass, and the sweep's finish folds the ranks' loss sums and double gradient accumulators once (Sweep::finish, rank_fold_f64).
 namespace {
 
 // the inflow and the continuity weight
@@ -736,7 +782,7 @@ int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler,
 // the forward loop keeping what the sweep needs (Euler: every step's RHS input; Tsit5: every accepted step's six stage inputs, in chunks on
 // the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves
 int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
-                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) {
+                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
     const bool euler = !o, adaptive = o && o->adaptive != 0;
     const TimeGrid T(d);
     if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
@@ -756,12 +802,15 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
         return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
                     d->n_saves - 1, T.stop_time(d->n_saves - 1), T.t1);
     }
-    if (int rc = solver_prepare(h, n_grads)) return rc;     // fp32, one partition, parameter count; the training arena
+    // fp32, one partition (partitions: or a partitioned mesh with one edge set and a communicator), parameter count; the training arena.
+    // These were the last checks: on a partitioned mesh no rank refuses after its peers have entered a collective
+    if (int rc = partitions ? solver_prepare_partitions(h, who, n_grads) : solver_prepare(h, n_grads)) return rc;
     const mgn_config& c = h->cfg;
-    const int32_t N = h->g.N;
+    const bool part = c.nranks != 1;       // every rank integrates and sweeps the rows it owns (rollout_solve's state)
+    const int32_t N = part ? h->g.n_own : h->g.N;
     const int O = c.O;
     invalidate_static(h);
-    Rollout R(h, d, T, true, N, N);
+    Rollout R(h, d, T, true, N, h->g.N);
     const size_t nb = (size_t)R.n * 4;
     const size_t P = h->params.size();
     const int ablk = solver_adjoint_blocks(N, O);
@@ -773,8 +822,8 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     const SolveWs ws = carve_solve(a, nb, euler, !euler && d->inflow_mask != nullptr);
     const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)N), o_pe = a.take(euler ? 0 : errnorm_partials() * sizeof(double));
     R.elat0_off = a.take(eb);
-    const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb), o_tmp = a.take(nb),
-                 o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
+    const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb),
+                 o_tmp = a.take(part ? (size_t)h->g.N * O * 4 : nb), o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
     const size_t o_st = a.take(euler ? (size_t)(K + 1) * nb : 0);
     if (int rc = euler ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the %lld stored states of the solve and the call's buffers", who,
                                         (double)a.off * 1e-9, (long long)(K + 1))
@@ -851,42 +900,53 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
     S.part = (double*)(base + o_part); S.grads = grads; S.loss = loss;
     if (int rc = run_sweep(h, S, R, euler, steps, (float*)(base + o_yb))) return rc;
-    if (d->out)      // the predicted saves in the caller's order
+    if (d->out && part) {      // the predicted saves, complete on every rank (every rank was given d->out, or none)
+        for (int i = 0; i < d->n_saves; ++i)
+            if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, O, d->out + (size_t)i * h->g.N * O)) return rc;
+    } else if (d->out) {       // the predicted saves in the caller's order
         if (int rc = saves_to_caller(h, R.saves, d->n_saves, d->out)) return rc;
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MGN_OK;
 }
 
 // the checks mgn_solver_grad and mgn_solver_grad_tsit5 share before their solver's
-int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss) {
-    if (int rc = solver_state_checks(h, who)) return rc;
+int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const float* gt, float* grads, float* loss, bool partitions) {
+    if (int rc = solver_state_checks(h, who, partitions)) return rc;
     if (!d || !gt || !grads || !loss || !d->x0) return fail(h, MGN_E_ARG, "%s: null argument", who);
     return solver_static_checks(h, d, who);
 }
 
 }  // namespace
 
+// mgn_solver_grad (tsit5 false; o unused) and mgn_solver_grad_tsit5 behind their symbols, and behind mgn_group_solver_grad* (partitions)
+int mgn::solver_grad_run(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
+                         const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
+    const char* who = tsit5 ? "mgn_solver_grad_tsit5" : "mgn_solver_grad";
+    if (int rc = solver_checks(h, d, who, gt, grads, loss, partitions)) return rc;
+    if (!tsit5) {
+        if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
+        if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
+        return solver_grad(h, d, nullptr, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, partitions);
+    }
+    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
+    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
+    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, partitions);
+}
+
 extern "C" int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
                     float* grads, size_t n_grads, float* loss) try {
-    static const char* who = "mgn_solver_grad";
     if (!h) return MGN_E_ARG;
-    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
-    if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
-    if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
-    return solver_grad(h, d, nullptr, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+    return solver_grad_run(h, d, nullptr, false, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
 } MGN_CATCH(h)
 
 // Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_adaptive, Tsit5Control) or fixed steps on the Euler grid (Rollout::tsit5_fixed), in
 // the training form (za / zs / z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
 extern "C" int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
                           const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
-    static const char* who = "mgn_solver_grad_tsit5";
     if (!h) return MGN_E_ARG;
-    if (int rc = solver_checks(h, d, who, gt, grads, loss)) return rc;
-    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
-    if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
-    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
-    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss);
+    return solver_grad_run(h, d, o, true, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
 } MGN_CATCH(h)
 
 // ---- MultipleShooting as one batch (mgn_shooting_grad) ----------------------------------------------------------------------------------

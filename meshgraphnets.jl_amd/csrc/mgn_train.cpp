@@ -807,7 +807,7 @@ struct TrainPass {
     TrainState& T;
     const LocalGraph& g;
     const int S, L, mps, O;
-    // a partition (train_prepare: mgn_step alone, one edge set): N owned rows, then the halo rows; the caller's arrays are the whole mesh's
+    // a partition (train_prepare with `partitions`: mgn_step, the datapoint step, and through the group the VJPs and the sweeps; one edge set): N owned rows, then the halo rows; the caller's arrays are the whole mesh's
     const bool part;
     const int64_t N, NT, NG;
     const int32_t nt_n, nt_t;
@@ -937,11 +937,22 @@ struct TrainPass {
         }
         return MGN_OK;
     }
+    // A per-node input [rows of the caller's array][width] of a VJP into dst [N][width] in the engine's order.  One partition: copied and
+    // permuted in place as ever; a partition takes the rows it owns out of the whole mesh's array (staged in ptmp when it is on the host)
+    int stage_rows(const float* user, int width, float* dst) {
+        if (!part) {
+            HIPCHK(h, hipMemcpyAsync(dst, user, (size_t)N * width * 4, hipMemcpyDefault, st));
+            HIPCHK(h, to_local(dst, width));
+            return MGN_OK;
+        }
+        const float* src = nullptr;
+        HIPCHK(h, staged(user, A + T.ptmp, (size_t)NG * width, src));
+        HIPCHK(h, launch_permute_rows(dst, src, ngid, N, width, false, st));
+        return MGN_OK;
+    }
     int stage_forward_vjp() {
         if (int rc = stage_features()) return rc;
-        HIPCHK(h, hipMemcpyAsync(io() + (size_t)N * O, J.lambda, (size_t)N * O * 4, hipMemcpyDefault, st));
-        HIPCHK(h, to_local(io() + (size_t)N * O, O));
-        return MGN_OK;
+        return stage_rows(J.lambda, O, io() + (size_t)N * O);
     }
     // RHS inputs exactly as mgn_ode_step takes them: nf = [n_norm(x); n_norm(onehot)], ef = e_norm(ef_raw).
     // The padded node features from a state x [N][O] in the engine's order and the one-hot rows in io
@@ -953,17 +964,18 @@ struct TrainPass {
     // The statics of a right-hand side -- one-hot node types and val_mask into io, the normalised raw edge features into ef_pad -- per call of
     // mgn_ode_vjp, once per sweep (Sweep::begin: no state yet, x = null); the state's padding sits between them as the launches always ran
     int stage_statics(const float* x) {
-        if (c.Fn > O) {
-            HIPCHK(h, hipMemcpyAsync(io() + (size_t)2 * N * O, J.onehot, (size_t)N * (c.Fn - O) * 4, hipMemcpyDefault, st));
-            HIPCHK(h, to_local(io() + (size_t)2 * N * O, c.Fn - O));
-        }
-        if (J.val_mask) {
-            HIPCHK(h, hipMemcpyAsync(io() + (size_t)N * (O + c.Fn), J.val_mask, (size_t)N * 4, hipMemcpyDefault, st));
-            HIPCHK(h, to_local(io() + (size_t)N * (O + c.Fn), 1));
-        }
+        if (c.Fn > O)
+            if (int rc = stage_rows(J.onehot, c.Fn - O, io() + (size_t)2 * N * O)) return rc;
+        if (J.val_mask)
+            if (int rc = stage_rows(J.val_mask, 1, io() + (size_t)N * (O + c.Fn))) return rc;
         if (x) if (int rc = pad_state(x)) return rc;
         T.traj.ef_pad_ok = false;
-        if (sx[0].E > 0) {
+        if (part && g.set[0].E > 0) {      // the local edges' rows of the whole mesh's array, in the engine's order (as stage_features)
+            const float* src = nullptr;
+            HIPCHK(h, staged(J.ef, A + T.ef_raw[0], (size_t)g.set[0].E * c.Fe, src));
+            HIPCHK(h, launch_affine_pad_gather(src, c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
+                                               h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, sx[0].egid, A + T.ef_pad[0], L, sx[0].E, st));
+        } else if (sx[0].E > 0) {
             HIPCHK(h, hipMemcpyAsync(A + T.ef_raw[0], J.ef, (size_t)sx[0].E * c.Fe * 4, hipMemcpyDefault, st));
             HIPCHK(h, launch_affine_pad(A + T.ef_raw[0], c.Fe, nullptr, 0, h->have_enorm ? nrm + 2 * c.Fn : nullptr,
                                         h->have_enorm ? nrm + 2 * c.Fn + c.Fe : nullptr, A + T.ef_pad[0], L, sx[0].E, st));
@@ -971,6 +983,11 @@ struct TrainPass {
         return MGN_OK;
     }
     int stage_rhs_vjp() {
+        if (part) {
+            if (int rc = stage_rows(J.x, O, io())) return rc;
+            if (int rc = stage_rows(J.lambda, O, io() + (size_t)N * O)) return rc;
+            return stage_statics(io());
+        }
         HIPCHK(h, hipMemcpyAsync(io(), J.x, (size_t)N * O * 4, hipMemcpyDefault, st));
         HIPCHK(h, hipMemcpyAsync(io() + (size_t)N * O, J.lambda, (size_t)N * O * 4, hipMemcpyDefault, st));
         HIPCHK(h, to_local(io(), O));
@@ -1359,6 +1376,26 @@ struct TrainPass {
         *J.loss = (float)(num / (double)J.nmask);
         return MGN_OK;
     }
+    // Finish of a VJP on a partition: the ranks' gradients through finish_partition's float exchange without its loss part (the head of
+    // this rank's part is zeroed: mgn_step leaves its loss numerator there), then the per-node results row by row through
+    // gather_rows_global, which blocks: complete arrays in the caller's order on every rank.
+    int finish_partition_vjp() {
+        const int64_t np = (int64_t)h->params.size();
+        HIPCHK(h, hipMemsetAsync(T.fin_s.p, 0, (size_t)RANK_SUM_HEAD * 4, st));
+        if (h->comm->allgather(T.fin_s.p, (size_t)rank_sum_stride(np) * 4, T.fin_r.p, st) != 0) return comm_fail("allgather of the gradients");
+        HIPCHK(h, launch_rank_sum(T.fin_r.as<float>(), c.nranks, np, T.grads.as<float>(), T.fin_loss.as<double>(), st));
+        HIPCHK(h, hipMemcpyAsync(J.grads, T.grads.p, (size_t)np * 4, hipMemcpyDefault, st));
+        if (J.kind == JOB_FORWARD_VJP) {
+            HIPCHK(h, launch_extract_cols(A + T.gNF, L, c.Fn, nullptr, io(), N, st));
+            if (int rc = gather_rows_global(h, io(), c.Fn, J.nfbar)) return rc;
+            if (J.out) if (int rc = gather_rows_global(h, T.target.as<float>(), O, J.out)) return rc;
+        } else {
+            HIPCHK(h, launch_extract_cols(A + T.gNF, L, O, h->have_nnorm ? nrm : nullptr, io(), N, st));
+            if (int rc = gather_rows_global(h, io(), O, J.xbar)) return rc;
+            if (J.dxdt) if (int rc = gather_rows_global(h, T.target.as<float>(), O, J.dxdt)) return rc;
+        }
+        return MGN_OK;
+    }
     // a per-node result [N][width] of a VJP: back into the caller's order and out
     int give(float* buf, int width, float* user) {
         HIPCHK(h, to_global(buf, width));
@@ -1371,7 +1408,7 @@ struct TrainPass {
             HIPCHK(h, launch_grad_accum(G, J.gacc, (int64_t)h->params.size(), J.first, st));
             return MGN_OK;
         }
-        if (part) return finish_partition();
+        if (part) return vjp() ? finish_partition_vjp() : finish_partition();
         std::vector<double> lp((size_t)nlb);
         HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
         if (!vjp()) {
@@ -1652,11 +1689,10 @@ extern "C" int mgn_datapoint_export(mgn_handle* h, int32_t datapoint, int32_t no
     return MGN_OK;
 } MGN_CATCH(h)
 
-extern "C" int mgn_ode_vjp(mgn_handle* h, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask,
-                           const float* lambda, float* dxdt, float* xbar, float* grads, size_t n_grads) try {
-    if (!h) return MGN_E_ARG;
+int mgn::ode_vjp_run(mgn_handle* h, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask, const float* lambda,
+                     float* dxdt, float* xbar, float* grads, size_t n_grads, bool partitions) {
     if (!x || !lambda || !xbar || !grads) return fail(h, MGN_E_ARG, "mgn_ode_vjp: null argument");
-    if (int rc = train_prepare(h, "mgn_ode_vjp", n_grads)) return rc;
+    if (int rc = train_prepare(h, "mgn_ode_vjp", n_grads, partitions)) return rc;
     const mgn_config& c = h->cfg;
     if (c.Fn < c.O) return fail(h, MGN_E_ARG, "mgn_ode_vjp: Fn < O");
     if ((c.Fn > c.O && !node_type_onehot) || (!ef_raw && h->g.set[0].E > 0)) return fail(h, MGN_E_ARG, "mgn_ode_vjp: null argument");
@@ -1665,11 +1701,18 @@ extern "C" int mgn_ode_vjp(mgn_handle* h, const float* x, const float* node_type
     J.x = x; J.onehot = node_type_onehot; J.ef = ef_raw; J.val_mask = val_mask; J.lambda = lambda;
     J.dxdt = dxdt; J.xbar = xbar; J.grads = grads;
     return train_run(h, J);
+}
+
+extern "C" int mgn_ode_vjp(mgn_handle* h, const float* x, const float* node_type_onehot, const float* ef_raw, const float* val_mask,
+                           const float* lambda, float* dxdt, float* xbar, float* grads, size_t n_grads) try {
+    if (!h) return MGN_E_ARG;
+    return ode_vjp_run(h, x, node_type_onehot, ef_raw, val_mask, lambda, dxdt, xbar, grads, n_grads, false);
 } MGN_CATCH(h)
 
 namespace mgn {
 
 int solver_prepare(mgn_engine* h, size_t n_grads) { return train_prepare(h, "mgn_solver_grad", n_grads); }
+int solver_prepare_partitions(mgn_engine* h, const char* who, size_t n_grads) { return train_prepare(h, who, n_grads, true); }
 
 namespace {
 
@@ -1680,7 +1723,8 @@ struct Sweep {
     mgn_engine* h;
     const SolverSweep& S;
     const float* xend;                         // x_K (continuity term)
-    int64_t N = 0, n = 0;
+    int64_t N = 0, n = 0, n_loss = 0;
+    bool part = false;                         // a partition: N owned rows; the loss and the gradient fold over the ranks in finish()
     int O = 0, nb = 0;
     float* io = nullptr;                       // xbar [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N], as TrainPass lays them out
     float* vm = nullptr;
@@ -1702,7 +1746,9 @@ struct Sweep {
         if (int rc = P.stage_statics(nullptr)) return rc;
         HIPCHK(h, hipMemsetAsync(S.a, 0, (size_t)n * 4, h->stream));
         nb = solver_adjoint_blocks(N, O);
-        gscale = (float)(2.0 / ((double)S.n_saves * (double)(S.win_rows > 0 ? S.win_rows * O : n)));
+        part = c.nranks > 1;
+        n_loss = part ? (int64_t)h->g.N * O : n;       // the divisor of the save term: the whole mesh's N O, not a partition's rows
+        gscale = (float)(2.0 / ((double)S.n_saves * (double)(S.win_rows > 0 ? S.win_rows * O : n_loss)));
         sidx = S.n_saves - 1;
         return MGN_OK;
     }
@@ -1754,9 +1800,11 @@ struct Sweep {
         hipStream_t st = h->stream;
         const int64_t P = (int64_t)h->params.size();
         float* G = h->train->grads.as<float>();
-        if (S.K > 0) HIPCHK(h, launch_grad_finish(S.gacc, G, P, st));
-        else HIPCHK(h, hipMemsetAsync(G, 0, (size_t)P * 4, st));
-        HIPCHK(h, hipMemcpyAsync(S.grads, G, (size_t)P * 4, hipMemcpyDefault, st));
+        if (!part) {
+            if (S.K > 0) HIPCHK(h, launch_grad_finish(S.gacc, G, P, st));
+            else HIPCHK(h, hipMemsetAsync(G, 0, (size_t)P * 4, st));
+            HIPCHK(h, hipMemcpyAsync(S.grads, G, (size_t)P * 4, hipMemcpyDefault, st));
+        }
         std::vector<double> lp((size_t)slot * 2 * nb);
         if (!lp.empty()) HIPCHK(h, hipMemcpyAsync(lp.data(), S.part, lp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
@@ -1766,7 +1814,17 @@ struct Sweep {
                 se += lp[(size_t)i * 2 * nb + b];
                 sa += lp[(size_t)i * 2 * nb + nb + b];
             }
-        *S.loss = (float)(se / ((double)S.n_saves * (double)n) + (double)S.cont_weight * sa);
+        if (part) {
+            // once per call: this rank's two loss sums (the save terms, the continuity term) and its double accumulator, as it stands,
+            // are gathered and added over the ranks in ascending order in double; the gradient is rounded to fp32 there, once, as
+            // launch_grad_finish rounds it on one partition.  The same bits on every rank, the same bits on every call.
+            double head[2] = {se, sa};
+            if (int rc = rank_fold_f64(h, head, 2, S.K > 0 ? S.gacc : nullptr, P, G)) return rc;
+            se = head[0]; sa = head[1];
+            HIPCHK(h, hipMemcpyAsync(S.grads, G, (size_t)P * 4, hipMemcpyDefault, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+        }
+        *S.loss = (float)(se / ((double)S.n_saves * (double)n_loss) + (double)S.cont_weight * sa);
         return MGN_OK;
     }
 };
@@ -2093,16 +2151,21 @@ int lnall_rhs_dev(mgn_engine* h, const float* srcA, float* out, bool reuse_edges
 // Pullback of mgn_forward == the model call `mgn.model(graph, ps, st)` at reference src/solve.jl:200 (what a ChainRulesCore.rrule of
 // the Julia shim's model function returns to Zygote inside the pullback of ode_func_train, src/strategies.jl:183-195): given the
 // cotangent ybar of the output, nfbar = ybar^T d out / d nf (all Fn columns) and grads = ybar^T d out / d ps.
-extern "C" int mgn_forward_vjp(mgn_handle* h, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads,
-                               size_t n_grads) try {
-    if (!h) return MGN_E_ARG;
+int mgn::forward_vjp_run(mgn_handle* h, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads, size_t n_grads,
+                         bool partitions) {
     if (!nf || !ybar || !nfbar || !grads) return fail(h, MGN_E_ARG, "mgn_forward_vjp: null argument");
-    if (int rc = train_prepare(h, "mgn_forward_vjp", n_grads)) return rc;
+    if (int rc = train_prepare(h, "mgn_forward_vjp", n_grads, partitions)) return rc;
     if (!ef && h->g.set[0].E > 0) return fail(h, MGN_E_ARG, "mgn_forward_vjp: null argument");
     TrainJob J;
     J.kind = JOB_FORWARD_VJP;
     J.nf = nf; J.ef = ef; J.lambda = ybar; J.out = out; J.nfbar = nfbar; J.grads = grads;
     return train_run(h, J);
+}
+
+extern "C" int mgn_forward_vjp(mgn_handle* h, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads,
+                               size_t n_grads) try {
+    if (!h) return MGN_E_ARG;
+    return forward_vjp_run(h, nf, ef, ybar, out, nfbar, grads, n_grads, false);
 } MGN_CATCH(h)
 
 // Online-normaliser accumulation (GraphNetCore NormaliserOnline, used at reference src/MeshGraphNets.jl:92,193-199 and inside

@@ -210,6 +210,13 @@ constexpr int RANK_SUM_HEAD = 4;
 int64_t rank_sum_stride(int64_t n);
 hipError_t launch_loss_numerator(const double* partial, int nb, double* out, hipStream_t s);
 hipError_t launch_rank_sum(const float* all, int nranks, int64_t n, float* out, double* loss, hipStream_t s);
+// The finish in double (solver-based training and rollout evaluation on a partitioned mesh): one rank's part is nhead sums (loss partials,
+// evaluation sums), then n entries of a double accumulator, padded to rank_sum_f64_stride(nhead, n) doubles.  launch_rank_sum_f64 adds
+// all [nranks][stride] over the ranks in ascending order, in double: head [nhead] doubles, out [n] floats (each rounded once).
+#pragma GCC visibility push(hidden)   // (new host functions stay out of the library's dynamic symbols)
+int64_t rank_sum_f64_stride(int64_t nhead, int64_t n);
+hipError_t launch_rank_sum_f64(const double* all, int nranks, int64_t nhead, int64_t n, double* head, float* out, hipStream_t s);
+#pragma GCC visibility pop
 
 // solver-based training (mgn_solver_grad), one step k of the reverse sweep of a fixed-step Euler solve, per element of the [N][O] state:
 //   a <- a + (xbar ? (inflow[n] ? 0 : xbar) : 0) + (gt ? -gscale ls[o]^2 (gt - xs) vm[n] : 0) + (ct ? cw sign(xend - ct) : 0);  lam <- dt a

@@ -2317,6 +2317,20 @@ __global__ __launch_bounds__(256) void k_rank_sum(const float* __restrict__ all,
     }
 }
 
+// The double-precision sibling of k_rank_sum (the finish of mgn_group_solver_grad*, the reductions of mgn_group_rollout_eval):
+// all [nranks][stride] doubles, every rank's (nhead sums | n accumulator entries | padding).  Entry i of a rank's part is added over the
+// ranks in ascending order, in double; the first nhead sums stay doubles (head), the others are rounded to fp32 once (out).  A plain
+// grid-stride loop, one entry per thread and pass, no atomics: every rank runs it on the same gathered bytes, the same bits everywhere.
+__global__ __launch_bounds__(256) void k_rank_sum_f64(const double* __restrict__ all, int nranks, int64_t stride, int64_t nhead, int64_t n,
+                                                      double* __restrict__ head, float* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nhead + n; i += (int64_t)gridDim.x * blockDim.x) {
+        double s = all[i];
+        for (int q = 1; q < nranks; ++q) s += all[(int64_t)q * stride + i];
+        if (i < nhead) head[i] = s;
+        else out[i - nhead] = (float)s;
+    }
+}
+
 hipError_t launch_halo_pack(int L, const float* src, const int32_t* idx, float* dst, int64_t rows, hipStream_t s) {
     const int64_t tot = rows * (L / 4);
     if (tot <= 0) return hipSuccess;
@@ -2346,6 +2360,15 @@ int64_t rank_sum_stride(int64_t n) { return RANK_SUM_HEAD + (n + 3) / 4 * 4; }
 hipError_t launch_rank_sum(const float* all, int nranks, int64_t n, float* out, double* loss, hipStream_t s) {
     const int64_t n4 = (n + 3) / 4;
     hipLaunchKernelGGL(k_rank_sum, dim3((unsigned)((n4 > 0 ? n4 + 255 : 256) / 256)), dim3(256), 0, s, all, nranks, rank_sum_stride(n), n, out, loss);
+    return hipGetLastError();
+}
+
+int64_t rank_sum_f64_stride(int64_t nhead, int64_t n) { return (nhead + n + 1) / 2 * 2; }
+
+hipError_t launch_rank_sum_f64(const double* all, int nranks, int64_t nhead, int64_t n, double* head, float* out, hipStream_t s) {
+    if (nranks < 1 || nhead < 0 || n < 0) return hipErrorInvalidValue;
+    if (nhead + n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rank_sum_f64, dim3(grad_blocks(nhead + n)), dim3(256), 0, s, all, nranks, rank_sum_f64_stride(nhead, n), nhead, n, head, out);
     return hipGetLastError();
 }
 

@@ -1033,6 +1033,51 @@ class GroupEngine:
                                                     self.param_count, C.byref(loss)))
         return gs, loss.value
 
+    # -- solver-based training and the validation rollout on the partitioned mesh (mgn_group_solver_grad*, mgn_group_*_vjp,
+    #    mgn_group_rollout_eval): Engine's methods, bodies included, run on the group's handle and the group's symbols --
+    @staticmethod
+    def _host_arrays(**arrays):
+        for name, a in arrays.items():
+            if a is not None and not isinstance(a, np.ndarray):
+                raise TypeError(f"{name}: a group takes host (NumPy) arrays; every rank reads them in place")
+
+    def solver_grad(self, x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask=None, inflow_mask=None,
+                    inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0, inflow_rule="reference", time_type=np.float32,
+                    want_pred=False, out=None, solver="Euler"):
+        """Engine.solver_grad on the partitioned mesh (mgn_group_solver_grad): the loss and the complete gradient of the whole mesh; the
+        save term divides by n_saves * N * O of the whole mesh.  Host arrays of the whole mesh."""
+        self._host_arrays(gt=gt, cont_target=cont_target, out=out)
+        return Engine.solver_grad(_GroupCalls(self), x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves, val_mask, inflow_mask,
+                                  inflow_data, loss_scale, cont_target, cont_weight, inflow_rule, time_type, want_pred, out, solver)
+
+    def solver_grad_tsit5(self, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, adaptive=True, abstol=1e-6, reltol=1e-3,
+                          val_mask=None, inflow_mask=None, inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0,
+                          inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0):
+        """Engine.solver_grad_tsit5 on the partitioned mesh (mgn_group_solver_grad_tsit5).  max_store_bytes bounds each rank's stored stage
+        inputs; stats' stored_bytes is rank 0's (24 * n_own * O bytes per accepted step), the step record is the same on every rank."""
+        self._host_arrays(gt=gt, cont_target=cont_target, out=out)
+        return Engine.solver_grad_tsit5(_GroupCalls(self), x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, adaptive, abstol,
+                                        reltol, val_mask, inflow_mask, inflow_data, loss_scale, cont_target, cont_weight, inflow_rule,
+                                        time_type, want_pred, out, step_cap, max_store_bytes)
+
+    def ode_vjp(self, x, node_type_onehot, ef_raw, lam, val_mask=None, want_dxdt=False):
+        """Engine.ode_vjp on the partitioned mesh (mgn_group_ode_vjp): (xbar [N][O], gs, dxdt or None), complete and in the caller's order."""
+        return Engine.ode_vjp(_GroupCalls(self), x, node_type_onehot, ef_raw, lam, val_mask, want_dxdt)
+
+    def forward_vjp(self, nf, ef, ybar, want_out=False):
+        """Engine.forward_vjp on the partitioned mesh (mgn_group_forward_vjp): (nfbar [N][Fn], gs, out or None)."""
+        return Engine.forward_vjp(_GroupCalls(self), nf, ef, ybar, want_out)
+
+    def rollout_eval(self, solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None, inflow_mask=None,
+                     inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, sel=None, sel_index_base=0,
+                     want_pred=False, mse_time_out=None):
+        """Engine.rollout_eval on the partitioned mesh (mgn_group_rollout_eval): sel indexes the whole mesh's [N][O]; val_loss divides by
+        len(sel) (N * O without sel), mse_save by N.  Without want_pred no rank keeps, gathers or downloads the solution."""
+        self._host_arrays(gt=gt, mse_time_out=mse_time_out)
+        return Engine.rollout_eval(_GroupCalls(self), solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, val_mask,
+                                   inflow_mask, inflow_data, abstol, reltol, inflow_rule, time_type, sel, sel_index_base, want_pred,
+                                   mse_time_out)
+
     def datapoint_export(self, t, normalised=True):
         """(nf [N][Fn], ef [E][Fe], target [N][O]) of datapoint t for the whole mesh: every rank writes the rows it owns."""
         nf = np.zeros((self.N, self.cfg.Fn), np.float32)
@@ -1051,6 +1096,29 @@ class GroupEngine:
         a, b, c, d = (C.c_double() for _ in range(4))
         self._chk(self.lib.mgn_group_latents_checksum(self.g, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(sum_v=a.value, sum_e=b.value, sumsq_v=c.value, sumsq_e=d.value)
+
+
+class _GroupSymbols:
+    """The library with mgn_group_X answering for mgn_X: what Engine's method bodies call when they run on a group."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name.replace("mgn_", "mgn_group_", 1))
+
+
+class _GroupCalls:
+    """A GroupEngine as the solver methods of Engine see `self`: the mesh's sizes, the group's handle and error text, the group's symbols.
+    Their bodies then serve both classes: one descriptor builder, one set of array checks, one return convention."""
+
+    def __init__(self, group):
+        self.lib, self.h, self.cfg = _GroupSymbols(group.lib), group.g, group.cfg
+        self.N, self.E, self.param_count, self._chk = group.N, group.E, group.param_count, group._chk
+
+    _rollout_desc, _solver_desc = Engine._rollout_desc, Engine._solver_desc
+    solver_grad, solver_grad_tsit5, ode_vjp, forward_vjp, rollout_eval = (Engine.solver_grad, Engine.solver_grad_tsit5, Engine.ode_vjp,
+                                                                          Engine.forward_vjp, Engine.rollout_eval)
 
 
 def triangles_to_edges_native(cells):
