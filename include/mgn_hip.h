@@ -343,26 +343,45 @@ int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt /* [n_sa
  * differentiating through an adaptive integrator; it is not InterpolatingAdjoint's continuous adjoint.  Reverse, from lam = dL/dx_{n+1}:
  *   for i = 6 .. 1:  kbar_i = h_n (A[7][i] lam + sum_{j>i} A[j][i] ybar_j);  zbar_i, g_i = VJP of f at z_{n,i};  ybar_i = zbar_i with
  *   the inflow rows zeroed;  gs += g_i.        dL/dx_n = lam + sum_i ybar_i + the save / continuity terms at x_n.
- * Step modes (o->adaptive):
+ * Step modes (o->adaptive, a set of flags: MGN_TSIT5_ADAPTIVE | MGN_TSIT5_DENSE_SAVES; any other bit is MGN_E_ARG):
  *   1: solve(prob, Tsit5(); saveat = saves, tstops = saves) -- mgn_rollout's Tsit5 unchanged: first step d->dt (0: Hairer-Wanner), PI
  *      controller, d->abstol / d->reltol, stops, stage times.  The error norm is taken on the states, which are not overwritten: with an
  *      inflow mask the steps can differ from mgn_rollout's, which overwrites in place.  The stage-7 input is z_{n+1,1} and sees t_{n+1}.
  *      More than 100 000 accepted steps (OrdinaryDiffEq's maxiters) or a NaN error estimate: MGN_E_STATE.
  *   0: solve(...; adaptive = false, dt): steps of d->dt on mgn_solver_grad's Euler time grid and save rule (last step snapped onto t1;
  *      every save must be reached, else MGN_E_ARG).  Its loss is a smooth function of the parameters.
- * Every save is stepped onto (tstops = saves); a MultipleShooting window solved without tstops interpolates its saves in the reference.
+ *   In modes 0 and 1 every save is stepped onto (tstops = saves) and d->out is bit-identical to mgn_rollout's solution.
+ *   3: solve(prob, Tsit5(); saveat = saves), NO tstops -- what the reference's MultipleShooting solves every window with
+ *      (src/strategies.jl:343-355).  Controller, first step and stage times as mode 1; the only stop is t1.
+ *   2: solve(...; adaptive = false, dt, saveat = saves): t <- t + dt in the solver's time type with h = dt; a step whose end lies within
+ *      1e-5 saves_dt of t1 snaps onto t1, one that would pass t1 is cut to h = t1 - t.  dt need not divide saves_dt.
+ *   Dense saves (modes 2 and 3): after accepted step n (t_n to t_{n+1}, size h_n) every pending save time t_s <= t_{n+1} is taken.  One
+ *   with |t_s - t_{n+1}| <= 1e-9 |t_{n+1}| + 1e-12 is x_{n+1} itself, a loss term of that state as in modes 0 and 1.  Any other is
+ *   Tsit5's dense output xhat_s = x_n + h_n sum_{i=1..7} b_i(theta_s) k_{n,i}, theta_s = (t_s - t_n) / h_n in double (at most 1), b from
+ *   mgn_tsit5_interp_weights rounded to float once, k_{n,7} = f(z_{n+1,1}).  The save at t0 is x0; saves the solve stops short of are
+ *   the final state.  The adjoint holds h_n and theta_s fixed: with ghat_s = dL/dxhat_s and S_n the interpolated saves of step n,
+ *     lam_n += sum_{S_n} ghat_s;  kbar_{n,i} += h_n sum_{S_n} b_i(theta_s) ghat_s (i = 1 .. 6);  kbar_{n+1,1} += h_n sum_{S_n} b_7(theta_s) ghat_s
+ *   (k_{n,7} is the evaluation k_{n+1,1}; for the last step one extra VJP at z_{K,1}, its output with the inflow rows zeroed added to lam_K).
+ *   step_t / step_h record the h every step used.  A save time an ulp short of t1 is interpolated at theta just below 1: pass the t1 the
+ *   save grid gives (t0 + (n_saves - 1) saves_dt in the solver's time type) to have the last save be the final state.
  * Memory: the six stage inputs z_{n,1..6} of every accepted step, 6 N O floats per step, in chunks kept on the handle and grown as steps
- * are accepted; allocation failure or more than o->max_store_bytes (0: no limit) is MGN_E_OOM, and the handle stays usable.
- * Through mgn_group_solver_grad_tsit5 the memory and max_store_bytes are PER RANK (6 n_own O floats per step on each rank).
+ * are accepted, and with dense saves 7 N O floats of sums; allocation failure or more than o->max_store_bytes (0: no limit) of the two
+ * together is MGN_E_OOM, and the handle stays usable.
+ * Through mgn_group_solver_grad_tsit5 the memory and max_store_bytes are PER RANK (6 n_own O floats per step on each rank, 7 n_own O of sums).
  * Bitwise repeatable.                                                                                                             */
+#define MGN_TSIT5_ADAPTIVE 1     /* PI-controlled steps (else fixed steps of d->dt)                                                  */
+#define MGN_TSIT5_DENSE_SAVES 2  /* no stop but t1; saves between steps come from Tsit5's dense output (else tstops = saves)          */
+/* Tsit5's dense-output weights b_1 .. b_7 at theta in [0, 1] (the free 4th-order interpolant of Tsitouras 2011, as OrdinaryDiffEq.jl's):
+ * x(t_n + theta h) = x_n + h sum_i b[i - 1] k_i.  Host only, no handle.  MGN_E_ARG for a theta outside [0, 1] (NaN included) or b NULL. */
+int mgn_tsit5_interp_weights(double theta, double b[7]);
 typedef struct mgn_solver_grad_opts {
-    int32_t adaptive;          /* 1: PI-controlled steps with tstops = saves (mgn_rollout's Tsit5); 0: fixed steps of d->dt         */
+    int32_t adaptive;          /* step mode: MGN_TSIT5_ADAPTIVE | MGN_TSIT5_DENSE_SAVES (0 .. 3, see above)                        */
     int32_t step_cap;          /* capacity of step_t / step_h (0: no record)                                                       */
     double* step_t;            /* out [step_cap] or NULL: start time of every accepted step, in the solver's time type               */
     double* step_h;            /* out [step_cap] or NULL: the h the stage combinations of that step used                             */
-    size_t max_store_bytes;    /* 0: bounded by device memory only; else the stored stage inputs may not exceed it (MGN_E_OOM)       */
+    size_t max_store_bytes;    /* 0: bounded by device memory only; else the stored stage inputs (+ dense sums) may not exceed it    */
     int32_t n_steps;           /* out: accepted steps (only the first step_cap are recorded)                                         */
-    size_t stored_bytes;       /* out: bytes the stored stage inputs took                                                            */
+    size_t stored_bytes;       /* out: bytes the stored stage inputs took (+ the 7 N O floats of sums with dense saves)              */
 } mgn_solver_grad_opts;
 int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt /* [n_saves][N][O] */,
                           const float* loss_scale /* [O] or NULL */, const float* cont_target /* [N][O] or NULL */, float cont_weight,

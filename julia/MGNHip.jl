@@ -751,18 +751,22 @@ end
 
 """
     solver_grad_tsit5(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, start, stop, saves;
-                      dt = 0, adaptive = true, abstol = 1f-6, reltol = 1f-3, loss_scale = nothing, cont_target = nothing,
-                      cont_weight = 0f0) -> (gs, loss, pred::Array{Float32, 3}, step_t::Vector{Float64}, step_h::Vector{Float64})
+                      dt = 0, adaptive = true, dense_saves = false, abstol = 1f-6, reltol = 1f-3, loss_scale = nothing,
+                      cont_target = nothing, cont_weight = 0f0)
+                      -> (gs, loss, pred::Array{Float32, 3}, step_t::Vector{Float64}, step_h::Vector{Float64})
 
 `solver_grad` for Tsit5 (mgn_solver_grad_tsit5): `adaptive = true` is `solve(prob, Tsit5(); saveat = saves, tstops = saves)` with
 native_rollout's controller (first step `dt`, 0: Hairer-Wanner); `adaptive = false` is fixed steps of `dt` on solver_grad's time grid.
+`dense_saves = true` (MGN_TSIT5_DENSE_SAVES) drops the tstops: `solve(prob, Tsit5(); saveat = saves)`, what the reference's
+MultipleShooting calls (src/strategies.jl:343-355) -- the only stop is `stop`, a save no step ends on comes from Tsit5's dense output, and
+the adjoint carries its loss term with the steps and interpolation points held fixed; fixed steps then need not divide the save period.
 `gs` is the discrete adjoint of the computed solution with the accepted step sequence (returned) held fixed -- not
 InterpolatingAdjoint's continuous adjoint.
 """
 function solver_grad_tsit5(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
         val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
         inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, start, stop, saves;
-        dt = zero(eltype(saves)), adaptive = true, abstol = 1.0f-6, reltol = 1.0f-3,
+        dt = zero(eltype(saves)), adaptive = true, dense_saves = false, abstol = 1.0f-6, reltol = 1.0f-3,
         loss_scale::Union{Nothing, Vector{Float32}} = nothing, cont_target::Union{Nothing, Matrix{Float32}} = nothing, cont_weight = 0.0f0,
         tolerant_inflow = false)
     ps = mgn.ps::Vector{Float32}
@@ -784,7 +788,7 @@ function solver_grad_tsit5(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_one
             inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
             inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
             start, stop, dt, sdt)
-        o = MgnSolverGradOpts(adaptive ? 1 : 0, cap, pointer(st), pointer(sh), 0, 0, 0)
+        o = MgnSolverGradOpts((adaptive ? 1 : 0) | (dense_saves ? 2 : 0), cap, pointer(st), pointer(sh), 0, 0, 0)
         # (@ccall: tests/test_solver_train_tsit5_host.py checks this call against the header)
         rc = GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out g loss_scale cont_target gs st sh @ccall LIB.mgn_solver_grad_tsit5(
             mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, o::Ref{MgnSolverGradOpts}, g::Ptr{Float32}, opt_ptr(loss_scale)::Ptr{Float32},
@@ -840,7 +844,8 @@ end
 
 `train_step(::SolverTraining)` / `train_step(::MultipleShooting)` (src/strategies.jl:175-196, 257-292, 312-383) for a strategy with
 `Euler()` or `Tsit5()` as its solver, through `solver_grad` / `solver_grad_tsit5` (Tsit5: adaptive unless `solargs.adaptive == false`,
-`abstol` / `reltol` from `solargs`, default 1e-6 / 1e-3; every window steps onto its saves): SolverTraining is one solve from `gt[:, :, 1]` over `tstart:dt:tstop` with the field
+`abstol` / `reltol` from `solargs`, default 1e-6 / 1e-3; every window steps onto its saves unless `dense_saves = true`, which solves
+the windows as the reference does -- saveat without tstops, the saves interpolated -- and is not batched): SolverTraining is one solve from `gt[:, :, 1]` over `tstart:dt:tstop` with the field
 normaliser's scale `n_scale` in the loss; MultipleShooting one solve per window of the reference's own
 `[i:min(T, i + interval_size - 1) for i in 1:(interval_size - 1):(T - 1)]` from `gt[:, :, first(rg)]`, no normaliser, and the continuity
 term of window i attached to window i - 1.  The Euler step is `solargs.dt` when given, else `strategy.dt` (the example's
@@ -853,8 +858,11 @@ Tsit5 keeps the per-window loop.
 """
 function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
         edge_features::Matrix{Float32}, val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}};
-        n_scale::Union{Nothing, Vector{Float32}} = nothing, inflow_data::Union{Nothing, Array{Float32, 3}} = gt, batched = false)
+        n_scale::Union{Nothing, Vector{Float32}} = nothing, inflow_data::Union{Nothing, Array{Float32, 3}} = gt, batched = false,
+        dense_saves = false)
     sname = nameof(typeof(strategy.solver))
+    dense_saves && sname != :Tsit5 && throw(ArgumentError("dense_saves is Tsit5's dense output"))
+    dense_saves && batched && throw(ArgumentError("dense_saves solves window by window: shooting_grad steps onto every save"))
     sname in (:Euler, :Tsit5) || throw(ArgumentError("native_solver_train_step drives Euler() and Tsit5(); got $(strategy.solver)"))
     tsteps = (strategy.tstart):(strategy.dt):(strategy.tstop)
     sargs = hasproperty(strategy, :solargs) ? strategy.solargs : (;)
@@ -865,7 +873,7 @@ function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32
     function window(x0, g, t0, t1, saves; kw...)
         sname == :Euler && return solver_grad(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, dt, saves; kw...)
         gs, loss, pred, _, _ = solver_grad_tsit5(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, saves;
-            dt = dt, adaptive = adaptive, abstol = abstol, reltol = reltol, kw...)
+            dt = dt, adaptive = adaptive, dense_saves = dense_saves, abstol = abstol, reltol = reltol, kw...)
         return gs, loss, pred
     end
     if !hasproperty(strategy, :interval_size)      # SolverTraining

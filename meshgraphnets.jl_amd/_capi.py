@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libmgn_hip.so")
 
 MGN_DEVICE_NONE = -2
 MGN_OK, MGN_E_ARG, MGN_E_HIP, MGN_E_STATE, MGN_E_OOM, MGN_E_UNSUPPORTED, MGN_E_RCCL = 0, -1, -2, -3, -4, -5, -6
+MGN_TSIT5_ADAPTIVE, MGN_TSIT5_DENSE_SAVES = 1, 2     # mgn_solver_grad_opts.adaptive: a set of flags
 STATUS_NAMES = {0: "MGN_OK", -1: "MGN_E_ARG", -2: "MGN_E_HIP", -3: "MGN_E_STATE", -4: "MGN_E_OOM", -5: "MGN_E_UNSUPPORTED",
                 -6: "MGN_E_RCCL"}
 MGN_COMM_ID_BYTES = 128
@@ -105,6 +106,7 @@ PROTOTYPES = {
     "mgn_solver_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f32p, _f32p, _f32p, C.c_float, _f32p, C.c_size_t, _f32p]),
     "mgn_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float, _f32p,
                                         C.c_size_t, _f32p]),
+    "mgn_tsit5_interp_weights": (C.c_int, [C.c_double, _f64p]),
     "mgn_shooting_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnShootingDesc), _f32p, _f32p, C.c_float, _f32p, C.c_size_t,
                                     _f32p]),
     "mgn_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),

@@ -266,6 +266,12 @@ struct Tsit5Sweep {
     const double* h;                     // [K] (host): the step sizes
     const float* xend;                   // [N][O]: x_K (continuity term)
     float* ybar;                         // scratch [5][N][O]: ybar_2 .. ybar_6 of the step being swept
+    // dense saves (MGN_TSIT5_DENSE_SAVES; theta null: every save is a state).  Save s with theta[s] >= 0 was interpolated inside accepted
+    // step S.save_step[s] at that theta (save_step stays non-decreasing); its loss terms reach lam_n, kbar_{n,1 .. 6} and kbar_{n+1,1}
+    // through k_tsit5_dense_adjoint, not through the adjoint launch of a state.
+    const double* theta = nullptr;       // [n_saves] (host); < 0: the save is state save_step[s]
+    const float* zend = nullptr;         // [N][O]: z_{K,1}, the input k_{K-1,7} was evaluated on (the extra VJP of a last step with such saves)
+    float* dense = nullptr;              // scratch [7][N][O]: the step's sum of seeds, then W_1 .. W_6
 };
 int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5);
 double tsit5_a(int i, int j);          // the Tsit5 tableau (mgn_solve.cpp), 1-based: A[i][j], b = A[7][j]

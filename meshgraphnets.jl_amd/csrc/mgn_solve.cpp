@@ -32,6 +32,22 @@ const double TS_BT[7] = {-0.00178001105222577714, -0.0008164344596567469, 0.0078
 
 double mgn::tsit5_a(int i, int j) { return TS_A[i - 1][j - 1]; }
 
+// Tsit5's dense output, the free 4th-order interpolant of Tsitouras 2011 (what OrdinaryDiffEq.jl evaluates between the steps of a Tsit5
+// solve):  x(t_n + theta h) = x_n + h sum_i b_i(theta) k_i,  b_i(theta) = r_i1 theta + r_i2 theta^2 + r_i3 theta^3 + r_i4 theta^4, with
+// k_7 = f(x_{n+1}).  b(1) is row 7 of the tableau (b_7(1) = 0).  Host only; the one place the constants live.
+extern "C" int mgn_tsit5_interp_weights(double theta, double b[7]) {
+    static const double R[7][4] = {{1.0, -2.763706197274826, 2.9132554618219126, -1.0530884977290216},
+                                   {0.0, 0.13169999999999998, -0.2234, 0.1017},
+                                   {0.0, 3.9302962368947516, -5.941033872131505, 2.490627285651253},
+                                   {0.0, -12.411077166933676, 30.33818863028232, -16.548102889244902},
+                                   {0.0, 37.50931341651104, -88.1789048947664, 47.37952196281928},
+                                   {0.0, -27.896526289197286, 65.09189467479366, -34.87065786149661},
+                                   {0.0, 1.5, -4.0, 2.5}};
+    if (!b || !(theta >= 0.0 && theta <= 1.0)) return MGN_E_ARG;
+    for (int i = 0; i < 7; ++i) b[i] = theta * (R[i][0] + theta * (R[i][1] + theta * (R[i][2] + theta * R[i][3])));
+    return MGN_OK;
+}
+
 namespace {
 
 // mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
@@ -220,6 +236,10 @@ struct Rollout {
     // ---- saves ----
     int saved = 0;                         // saves taken
     std::vector<int64_t> save_step;        // the accepted steps before each save taken
+    // dense saves (mgn_solver_grad_tsit5 with MGN_TSIT5_DENSE_SAVES): the only stop is t1, and a save no step ends on is interpolated
+    // inside the accepted step that passes it -- save_step its index, save_theta where (< 0: the save is the state after save_step steps)
+    bool dense = false;
+    std::vector<double> save_theta;
     // mgn_rollout_eval: every save is compared with its ground-truth frame as it is produced (k_save_error) -- gt [n_saves][n] in the
     // engine's order, acc [n] doubles, part [n_saves][save_error_blocks(nrows)][O] -- and kept only if the caller wants the solution
     const float* ev_gt = nullptr;
@@ -227,11 +247,39 @@ struct Rollout {
     // saves[saved] <- u, the state after steps_done accepted steps
     int save(int64_t steps_done) {
         save_step.push_back(steps_done);
+        save_theta.push_back(-1.0);
         if (ev_gt)
             HIPCHK(h, launch_save_error(u, ev_gt + (size_t)saved * n, ev_acc, ev_part + (size_t)saved * save_error_blocks(nrows) * h->cfg.O, nrows,
                                         h->cfg.O, h->stream));
         if (saves) HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         ++saved;
+        return MGN_OK;
+    }
+    // does pending save time ts sit on a step's end tn?  (at most tn, and within the tolerance the stops are hit with)
+    static bool hits(double ts, double tn) { return ts <= tn && std::fabs(ts - tn) <= 1e-9 * std::fabs(tn) + 1e-12; }
+    // dense saves: the pending saves strictly inside the accepted trial of step nstep from t to tn with size hstep, before tsit5_advance
+    // (u = x_n, k[0 .. 6] = k_{n,1 .. 7}): saves[saved] <- x_n + hstep sum_i b_i(theta) k_{n,i}, theta = (ts - t) / hstep formed in double
+    // from the time-type values (at most 1: tn is rounded), the weights rounded to float once
+    int saves_inside(int64_t nstep, double t, double hstep, double tn) {
+        while (saved < d->n_saves) {
+            const double ts = tg.stop_time(saved);
+            if (ts > tn || hits(ts, tn)) break;
+            const double theta = std::min((ts - t) / hstep, 1.0);
+            double b[7];
+            if (mgn_tsit5_interp_weights(theta, b) != MGN_OK) return fail(h, MGN_E_STATE, "dense save %d: theta = %g", saved, theta);
+            LinComb lc{7, {}, {}};
+            for (int j = 0; j < 7; ++j) { lc.c[j] = (float)b[j]; lc.k[j] = k[j]; }
+            HIPCHK(h, launch_lincomb(saves + (size_t)saved * n, u, lc, (float)hstep, n, h->stream));
+            save_step.push_back(nstep);
+            save_theta.push_back(theta);
+            ++saved;
+        }
+        return MGN_OK;
+    }
+    // ... and, after the advance to t (nacc steps done), the save that sits on it
+    int saves_on(int64_t nacc, double t) {
+        while (saved < d->n_saves && hits(tg.stop_time(saved), t))
+            if (int rc = save(nacc)) return rc;
         return MGN_OK;
     }
     // the saves a fixed-step plan (the accepted steps before every save, fixed_grid) takes after steps_done steps
@@ -371,10 +419,38 @@ struct Rollout {
         return MGN_OK;
     }
 
+    // fixed steps with dense saves, solve(...; adaptive = false, dt, saveat = saves): t <- tt(t + dt) with h = dt until t1; a step whose
+    // end lies within 1e-5 saves_dt of t1 snaps onto it (TimeGrid::next's rule), one that would pass t1 is cut to h = tt(t1 - t).  dt
+    // need not divide saves_dt; the saves are interpolated (saves_inside) or sit on a step's end
+    int tsit5_fixed_dense(const Slot& slot) {
+        double t = tg.t0;
+        if (int rc = save(0)) return rc;
+        if (int rc = tsit5_first(t)) return rc;
+        int64_t nacc = 0;
+        while (t < tg.t1 - 1e-5 * tg.sdt) {
+            double hstep = tg.dt, tn = tt(t + tg.dt);
+            if (std::fabs(tn - tg.t1) <= 1e-5 * tg.sdt) tn = tg.t1;
+            else if (tn > tg.t1) { hstep = tt(tg.t1 - t); tn = tg.t1; }
+            if (int rc = begin_trial(slot, nacc)) return rc;
+            if (int rc = tsit5_trial(t, hstep, tn, nullptr)) return rc;
+            if (int rc = saves_inside(nacc, t, hstep, tn)) return rc;
+            tsit5_advance();
+            step_t.push_back(t); step_h.push_back(hstep);
+            t = tn;
+            ++nacc;
+            ++d->n_accept;
+            if (int rc = saves_on(nacc, t)) return rc;
+        }
+        kept = nullptr;
+        while (saved < d->n_saves)      // (saves the solve stops an ulp short of: the final state)
+            if (int rc = save(nacc)) return rc;
+        return MGN_OK;
+    }
+
     // adaptive Tsit5 from t0 to t1: mgn_rollout's PI controller (Tsit5Control), tstops = saves, a save on every stop it hits, missing saves
     // (t1 short of the last stop) padded with the final state.  mgn_rollout (no slot): stage 7 at c7 h, and the iteration guard stops
     // silently.  Training form (slot): every trial's stage inputs kept in slot(n), stage 7 is z_{n+1,1} and sees t_{n+1}, the accepted
-    // steps recorded, and the guard fails the call.
+    // steps recorded, and the guard fails the call.  dense (training form only): no stop but t1, the saves as tsit5_fixed_dense takes them.
     int tsit5_adaptive(const char* who, const Slot* slot) {
         const int ns = d->n_saves;
         double t = tg.t0;
@@ -391,7 +467,7 @@ struct Rollout {
                 if (!slot) break;
                 return fail(h, MGN_E_STATE, "%s: %lld trial steps without reaching t1", who, (long long)guard);
             }
-            double tstop = saved < ns ? tg.stop_time(saved) : tg.t1;
+            double tstop = (saved < ns && !dense) ? tg.stop_time(saved) : tg.t1;
             if (tstop > tg.t1) tstop = tg.t1;
             bool hit_stop = false;
             double hstep = dt;
@@ -405,13 +481,18 @@ struct Rollout {
             if (int rc = tsit5_trial(t, hstep, t7, &EEst)) return rc;
             if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
             if (ctl.decide(EEst, hstep, hit_stop, dt)) {
+                if (dense)
+                    if (int rc = saves_inside(nacc, t, hstep, tn)) return rc;
                 tsit5_advance();
                 if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
                 t = tn;
                 ++nacc;
                 ++d->n_accept;
-                if (hit_stop && saved < ns && std::fabs(tg.stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12)
+                if (dense) {
+                    if (int rc = saves_on(nacc, t)) return rc;
+                } else if (hit_stop && saved < ns && std::fabs(tg.stop_time(saved) - t) <= 1e-9 * std::fabs(t) + 1e-12) {
                     if (int rc = save(nacc)) return rc;
+                }
             } else {
                 ++d->n_reject;
             }
@@ -772,9 +853,15 @@ SolverSweep sweep_setup(const Rollout& R, bool euler, int64_t K, const float* st
     return S;
 }
 // the sweep on engine e: Euler's, or Tsit5's over the stored stage inputs of R's accepted steps (ybar: scratch [5][n])
-int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler, const std::vector<float*>& steps, float* ybar) {
+// (dense: the scratch of a solve with dense saves, whose plan is R.save_step / R.save_theta; null otherwise)
+int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler, const std::vector<float*>& steps, float* ybar, float* dense = nullptr) {
     if (euler) return solver_sweep(e, S);
-    const Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, ybar};
+    Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, ybar};
+    if (dense) {
+        T5.theta = R.save_theta.data();
+        T5.zend = R.rhs_input(R.u, R.za);      // z_{K,1}: what stage 7 of the last accepted trial was evaluated on
+        T5.dense = dense;
+    }
     return tsit5_sweep(e, S, T5);
 }
 
@@ -783,7 +870,7 @@ int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler,
 // the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves
 int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
                 const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
-    const bool euler = !o, adaptive = o && o->adaptive != 0;
+    const bool euler = !o, adaptive = o && (o->adaptive & MGN_TSIT5_ADAPTIVE), dense = o && (o->adaptive & MGN_TSIT5_DENSE_SAVES);
     const TimeGrid T(d);
     if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
     if (!adaptive && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, euler ? "%s: Euler needs dt > 0" : "%s: fixed steps need dt > 0", who);
@@ -796,7 +883,7 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     }
     int64_t K = 0;                       // fixed steps: the step count; adaptive: the accepted steps, after the solve
     std::vector<int64_t> plan;
-    if (!adaptive) {
+    if (!adaptive && !dense) {
         if (int rc = fixed_grid(h, who, T, d->n_saves, &K, plan)) return rc;
     } else if (T.stop_time(d->n_saves - 1) > T.t1 + 1e-5 * T.sdt) {
         return fail(h, MGN_E_ARG, "%s: save point %d (t = %.9g) lies beyond the end of the solve (t1 = %.9g): every save must be reached", who,
@@ -825,9 +912,12 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb),
                  o_tmp = a.take(part ? (size_t)h->g.N * O * 4 : nb), o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
     const size_t o_st = a.take(euler ? (size_t)(K + 1) * nb : 0);
+    const size_t o_dn = a.take(dense ? 7 * nb : 0);      // dense saves: the sweep's sums of a step's interpolated saves (Tsit5Sweep::dense)
     if (int rc = euler ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the %lld stored states of the solve and the call's buffers", who,
                                         (double)a.off * 1e-9, (long long)(K + 1))
-                       : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
+                 : dense ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers (%.3f GB of them the sums of the interpolated saves)", who,
+                                          (double)a.off * 1e-9, (double)(7 * nb) * 1e-9)
+                         : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
         return rc;
     char* base = h->ode.as<char>();
     R.bind(base, ws);
@@ -841,6 +931,7 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     // Tsit5: the stored stage inputs, step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown
     // geometrically (never reallocated: a stored step does not move)
     const size_t stepb = 6 * nb;
+    const size_t denseb = dense ? 7 * nb : 0;      // counted with the stored stage inputs (max_store_bytes, stored_bytes)
     const int64_t max_steps = 100000;
     std::vector<float*> steps;
     size_t chunk = 0, used_in_chunk = 0;
@@ -848,9 +939,10 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
         while ((int64_t)steps.size() <= n) {
             if ((int64_t)steps.size() >= max_steps)
                 return fail(h, MGN_E_STATE, "%s: more than %lld accepted steps (maxiters)", who, (long long)max_steps);
-            if (o->max_store_bytes && (size_t)(steps.size() + 1) * stepb > o->max_store_bytes)
-                return fail(h, MGN_E_OOM, "%s: step %lld needs %zu bytes of stored stage inputs, beyond max_store_bytes = %zu", who,
-                            (long long)steps.size(), (size_t)(steps.size() + 1) * stepb, o->max_store_bytes);
+            if (o->max_store_bytes && (size_t)(steps.size() + 1) * stepb + denseb > o->max_store_bytes)
+                return fail(h, MGN_E_OOM, "%s: step %lld needs %zu bytes of stored stage inputs%s, beyond max_store_bytes = %zu", who,
+                            (long long)steps.size(), (size_t)(steps.size() + 1) * stepb + denseb, dense ? " and sums of the interpolated saves" : "",
+                            o->max_store_bytes);
             DevBuf* cb = chunk < h->tsit5_store.size() ? h->tsit5_store[chunk].get() : nullptr;
             if (cb && used_in_chunk + stepb <= cb->bytes) {
                 steps.push_back(reinterpret_cast<float*>(cb->as<char>() + used_in_chunk));
@@ -860,8 +952,8 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
             if (cb && used_in_chunk > 0) { ++chunk; used_in_chunk = 0; continue; }
             // a new chunk (or an earlier call's that holds no step of this size, regrown in place): as many steps as are stored so far (at
             // least 8; a fixed-step solve: all it has left), within max_store_bytes
-            size_t want = (size_t)std::max<int64_t>(adaptive ? std::max<int64_t>((int64_t)steps.size(), 8) : K - (int64_t)steps.size(), 1);
-            if (o->max_store_bytes) want = std::min(want, o->max_store_bytes / stepb - steps.size());
+            size_t want = (size_t)std::max<int64_t>((adaptive || dense) ? std::max<int64_t>((int64_t)steps.size(), 8) : K - (int64_t)steps.size(), 1);
+            if (o->max_store_bytes) want = std::min(want, (o->max_store_bytes - denseb) / stepb - steps.size());
             if (want > (SIZE_MAX / 2) / stepb) return fail(h, MGN_E_OOM, "%s: %zu stored steps overflow the address space", who, want);
             if (!cb) {
                 h->tsit5_store.push_back(std::make_unique<DevBuf>());
@@ -878,12 +970,14 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
 
     d->n_accept = d->n_reject = 0;
     float* states = (float*)(base + o_st);
-    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : R.tsit5_fixed(K, plan, slot)) return rc;
+    R.dense = dense;
+    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(slot) : R.tsit5_fixed(K, plan, slot))
+        return rc;
     d->n_rhs = R.n_rhs;
     if (!euler) {
         K = (int64_t)R.step_h.size();
         o->n_steps = (int32_t)K;
-        o->stored_bytes = (size_t)K * stepb;
+        o->stored_bytes = (size_t)K * stepb + denseb;
         for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
             if (o->step_t) o->step_t[i] = R.step_t[i];
             if (o->step_h) o->step_h[i] = R.step_h[i];
@@ -899,7 +993,7 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     S.cont_weight = ctl ? cont_weight : 0.f;
     S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
     S.part = (double*)(base + o_part); S.grads = grads; S.loss = loss;
-    if (int rc = run_sweep(h, S, R, euler, steps, (float*)(base + o_yb))) return rc;
+    if (int rc = run_sweep(h, S, R, euler, steps, (float*)(base + o_yb), dense ? (float*)(base + o_dn) : nullptr)) return rc;
     if (d->out && part) {      // the predicted saves, complete on every rank (every rank was given d->out, or none)
         for (int i = 0; i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, O, d->out + (size_t)i * h->g.N * O)) return rc;
@@ -923,6 +1017,9 @@ int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const flo
 int mgn::solver_grad_run(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
     const char* who = tsit5 ? "mgn_solver_grad_tsit5" : "mgn_solver_grad";
+    // the step mode first: a host-only handle answers it too
+    if (tsit5 && o && (o->adaptive & ~(MGN_TSIT5_ADAPTIVE | MGN_TSIT5_DENSE_SAVES)))
+        return fail(h, MGN_E_ARG, "%s: adaptive = %d: the step mode is MGN_TSIT5_ADAPTIVE | MGN_TSIT5_DENSE_SAVES, nothing else", who, o->adaptive);
     if (int rc = solver_checks(h, d, who, gt, grads, loss, partitions)) return rc;
     if (!tsit5) {
         if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");

@@ -1731,6 +1731,13 @@ struct Sweep {
     float gscale = 0.f;
     int64_t sidx = 0;                          // saves are visited last to first; save_step is non-decreasing
     int slot = 0;
+    const double* theta = nullptr;             // Tsit5 with dense saves: theta[s] >= 0 marks a save interpolated inside a step (skipped here)
+
+    // is the last save not yet visited state k's?
+    bool save_at(int64_t k) {
+        while (theta && sidx >= 0 && theta[sidx] >= 0.0) --sidx;
+        return sidx >= 0 && S.save_step[sidx] == k;
+    }
 
     Sweep(mgn_engine* h_, const SolverSweep& S_, const float* xend_) : h(h_), S(S_), xend(xend_) {}
 
@@ -1761,13 +1768,13 @@ struct Sweep {
             p.a = S.a;
             p.xbar = (first && with_xbar) ? io : nullptr;
             p.inflow = S.inflow;
-            const bool has_save = sidx >= 0 && S.save_step[sidx] == k;
+            const bool has_save = save_at(k);
             if (has_save) {
                 p.xs = S.saves + (size_t)sidx * n; p.gt = S.gt + (size_t)sidx * n; p.ls = S.loss_scale; p.vm = vm; p.gscale = gscale;
                 --sidx;
             }
             if (first && k == S.K && S.cont_target) { p.xend = xend; p.ct = S.cont_target; p.cw = S.cont_weight; }
-            const bool more = sidx >= 0 && S.save_step[sidx] == k;
+            const bool more = save_at(k);
             p.lam = (!more && k > 0) ? io + n : nullptr;
             p.dt = seed; p.N = N; p.O = O;
             if (S.lacc) {          // mgn_shooting_grad: per-window continuity weights, partials added across the call
@@ -1847,16 +1854,60 @@ int solver_sweep(mgn_engine* h, const SolverSweep& S) {
 // of stage 6 is written by the adjoint launch of state n + 1 (h_n A[7][6] lam); k_tsit5_stage_seed masks zbar_{i+1} into ybar_{i+1} and
 // writes kbar_i = h_n (A[7][i] lam + sum_{j>i} A[j][i] ybar_j) for i = 5 .. 1, and before stage 1's VJP adds sum_{j>=2} ybar_j to lam;
 // the adjoint launch of state n folds in ybar_1 and the loss terms of x_n.  No host synchronisation until the end.
+//
+// Dense saves (T5.theta): the saves interpolated inside step n, xhat_s = x_n + h_n sum_i b_i(theta_s) k_{n,i}, seed lam_n with sum ghat_s,
+// kbar_{n,i} with h_n W_i (W_i = sum_s b_i(theta_s) ghat_s, i = 1 .. 6) and, k_{n,7} being the evaluation at z_{n+1,1} (FSAL),
+// kbar_{n+1,1} with h_n W_7.  ghat_s needs forward values only, so one k_tsit5_dense_adjoint launch per TSIT5_DENSE_MAX saves of step n
+// runs right before the VJP at z_{n+1,1} -- stage 1 of step n + 1, whose seed launch has just consumed that step's own sums, or for the
+// last step one extra VJP at z_{K,1} before the sweep starts, its masked output folded into lam_K by the adjoint launch of state K.
 int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
     Sweep W(h, S, T5.xend);
     if (int rc = W.begin()) return rc;
+    W.theta = T5.theta;
+    // the interpolated saves of every step, ascending
+    std::vector<std::vector<int32_t>> inner(T5.theta ? (size_t)S.K : 0);
+    for (int32_t s = 0; T5.theta && s < S.n_saves; ++s)
+        if (T5.theta[s] >= 0.0) {
+            if (S.save_step[s] < 0 || S.save_step[s] >= S.K || !T5.dense || !T5.zend || S.lacc) return fail(h, MGN_E_STATE, "tsit5_sweep: bad dense-save plan");
+            inner[(size_t)S.save_step[s]].push_back(s);
+        }
+    auto has_inner = [&](int64_t k) { return k >= 0 && k < (int64_t)inner.size() && !inner[(size_t)k].empty(); };
+    // the launches of step m's interpolated saves: T5.dense <- its sums, the VJP's lambda slot (+)= h_m W_7
+    auto dense = [&](int64_t m, bool kbar_add) -> int {
+        const std::vector<int32_t>& sv = inner[(size_t)m];
+        for (size_t j0 = 0; j0 < sv.size(); j0 += TSIT5_DENSE_MAX) {
+            Tsit5DenseArgs p{};
+            p.ns = (int32_t)std::min<size_t>(TSIT5_DENSE_MAX, sv.size() - j0);
+            for (int j = 0; j < p.ns; ++j) {
+                const int32_t s = sv[j0 + j];
+                double b[7];
+                if (mgn_tsit5_interp_weights(T5.theta[s], b) != MGN_OK) return fail(h, MGN_E_STATE, "tsit5_sweep: theta = %g of save %d", T5.theta[s], s);
+                for (int i = 0; i < 7; ++i) p.b[j][i] = (float)b[i];
+                p.xs[j] = S.saves + (size_t)s * W.n; p.gt[j] = S.gt + (size_t)s * W.n;
+                p.part[j] = S.part + (size_t)W.slot++ * 2 * W.nb;
+            }
+            p.ls = S.loss_scale; p.vm = W.vm; p.gscale = W.gscale;
+            p.w = T5.dense; p.kbar = W.io + W.n; p.h = (float)T5.h[m];
+            p.accumulate = j0 > 0; p.kbar_add = kbar_add || j0 > 0;
+            p.N = W.N; p.O = W.O; p.nblk = W.nb;
+            HIPCHK(h, launch_tsit5_dense_adjoint(p, h->stream));
+        }
+        return MGN_OK;
+    };
     auto seed6 = [&](int64_t k) { return k > 0 ? (float)(T5.h[k - 1] * tsit5_a(7, 6)) : 0.f; };
-    if (int rc = W.adjoint(S.K, false, seed6(S.K))) return rc;
+    bool first = true;                          // no VJP has run yet (the first one assigns the gradient accumulator)
+    if (has_inner(S.K - 1)) {
+        if (int rc = dense(S.K - 1, false)) return rc;
+        if (int rc = W.vjp(T5.zend, true)) return rc;
+        first = false;
+    }
+    if (int rc = W.adjoint(S.K, !first, seed6(S.K))) return rc;
     for (int64_t k = S.K - 1; k >= 0; --k) {
+        const bool di = has_inner(k);
         for (int i = 6; i >= 1; --i) {
-            if (i < 6) {
+            if (i < 6 || di) {                  // (stage 6's seed h_k A[7][6] lam is the adjoint launch's; with dense saves it takes h_k W_6)
                 Tsit5SeedArgs p{};
-                p.xbar = W.io;
+                p.xbar = i < 6 ? W.io : nullptr;
                 p.inflow = S.inflow;
                 p.ybar = T5.ybar;
                 p.a = S.a;
@@ -1866,9 +1917,13 @@ int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
                 p.i = i;
                 p.N = W.N;
                 p.O = W.O;
+                if (di) { p.w = T5.dense + (size_t)i * W.n; p.g = i == 1 ? T5.dense : nullptr; p.hw = (float)T5.h[k]; }
                 HIPCHK(h, launch_tsit5_stage_seed(p, h->stream));
             }
-            if (int rc = W.vjp(T5.steps[k] + (size_t)(i - 1) * W.n, k == S.K - 1 && i == 6)) return rc;
+            if (i == 1 && has_inner(k - 1))
+                if (int rc = dense(k - 1, true)) return rc;
+            if (int rc = W.vjp(T5.steps[k] + (size_t)(i - 1) * W.n, first)) return rc;
+            first = false;
         }
         if (int rc = W.adjoint(k, true, seed6(k))) return rc;
     }

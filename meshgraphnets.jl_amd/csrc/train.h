@@ -234,12 +234,33 @@ hipError_t launch_solver_adjoint(const SolverAdjArgs& p, hipStream_t s);
 // state, before the VJP of stage i:
 //   ybar_{i+1} <- inflow[n] ? 0 : xbar  (the VJP of stage i + 1 just finished);   kbar <- cb lam + sum_{j>i} ca[j - 1] ybar_j
 //   (cb = h A[7][i], ca[j - 1] = h A[j][i]);   i = 1: lam <- lam + sum_{j=2..6} ybar_j as well.   ybar: [5][N][O], ybar_j at j - 2.
+// Dense saves (a step with interpolated saves, below): w (null: none) is the step's weighted sum W_i, added as kbar += hw w; g (i = 1
+// only, null: none) the sum of the interpolated saves' seeds, added to lam with the ybar.  i = 6 with xbar null is kbar <- cb lam (+ hw w),
+// what the adjoint launch of the state after the step wrote.
 struct Tsit5SeedArgs {
     const float* xbar; const uint8_t* inflow; float* ybar; float* a; float* kbar;
     float cb; float ca[6];
     int32_t i; int64_t N; int32_t O;
+    const float* w; const float* g; float hw;
 };
 hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s);
+// mgn_solver_grad_tsit5 with MGN_TSIT5_DENSE_SAVES: the loss terms of ns <= TSIT5_DENSE_MAX saves interpolated inside one accepted step,
+// xs[s] = x_n + h sum_i b[s][i - 1] k_{n,i}, per element of the [N][O] state.  With ghat_s = -gscale ls[o]^2 (gt[s] - xs[s]) vm[n]:
+//   w[0] (+)= sum_s ghat_s;   w[i] (+)= sum_s b[s][i - 1] ghat_s, i = 1 .. 6   (w: [7][N][O]; accumulate: added to what is there);
+//   kbar (+)= h sum_s b[s][6] ghat_s   (the seed of the VJP at z_{n+1,1}, whose output is k_{n,7}; kbar_add: added to what is there)
+// part[s]: [2][nblk] doubles as k_solver_adjoint leaves them, nblk = solver_adjoint_blocks(N, O) -- per block the sum of
+// (ls (gt[s] - xs[s]))^2 vm, the rest zero.  Every element is owned by one thread and the saves are taken in order: no atomics.
+constexpr int TSIT5_DENSE_MAX = 4;
+struct Tsit5DenseArgs {
+    const float* xs[TSIT5_DENSE_MAX]; const float* gt[TSIT5_DENSE_MAX]; double* part[TSIT5_DENSE_MAX];
+    float b[TSIT5_DENSE_MAX][7];
+    int32_t ns;
+    const float* ls; const float* vm; float gscale;
+    float* w; float* kbar; float h;
+    int32_t accumulate, kbar_add;
+    int64_t N; int32_t O; int32_t nblk;
+};
+hipError_t launch_tsit5_dense_adjoint(const Tsit5DenseArgs& p, hipStream_t s);
 // mgn_shooting_grad: the state holds B windows of N rows each (row r is window r / N's row r mod N).
 // The windowed adjoint step: k_solver_adjoint per element with the continuity weight of the row's window (cw_win[n / win_rows]: 0 for a
 // window with no successor), and its loss terms ADDED to running per-block partials acc[0][b] (mse times lscale = 1 / (n_saves N O) of the

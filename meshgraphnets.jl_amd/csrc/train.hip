@@ -2067,12 +2067,121 @@ __global__ __launch_bounds__(256) void k_tsit5_stage_seed(Tsit5SeedArgs p) {
 #pragma unroll
         for (int q = 0; q < V; ++q) { kb[q] = fmaf(cj, y[q], kb[q]); ys[q] += y[q]; }
     }
+    if (p.w) {                              // a step with interpolated saves: kbar_i += h W_i
+        float wv[V];
+        ldv<V>(wv, p.w + e);
+#pragma unroll
+        for (int q = 0; q < V; ++q) kb[q] = fmaf(p.hw, wv[q], kb[q]);
+    }
     stv<V>(p.kbar + e, kb);
     if (p.i == 1) {
 #pragma unroll
         for (int q = 0; q < V; ++q) lam[q] += ys[q];
+        if (p.g) {                          // ... and lam_n takes the sum of their seeds
+            float gv[V];
+            ldv<V>(gv, p.g + e);
+#pragma unroll
+            for (int q = 0; q < V; ++q) lam[q] += gv[q];
+        }
         stv<V>(p.a + e, lam);
     }
+}
+
+// ---- mgn_solver_grad_tsit5 with dense saves: the loss terms of the saves interpolated inside one accepted step ----------------------
+// V consecutive elements per thread, as k_tsit5_stage_seed.  Streaming: per launch 2 ns arrays read (each save's xs and gt once), 7 written
+// (+ 7 read when accumulating) and kbar.  The save loop is unrolled over TSIT5_DENSE_MAX with a predicate, so the pointers and the 7
+// weights of every save stay in scalar registers.  The squared errors are summed in double per block: a wave reduction, then the four
+// waves through LDS in a fixed order (k_solver_adjoint's partials, one slot per save).
+template <int V>
+__global__ __launch_bounds__(256) void k_tsit5_dense_adjoint(Tsit5DenseArgs p) {
+    __shared__ double sh[TSIT5_DENSE_MAX][4];
+    const int64_t n = p.N * p.O;
+    const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    double e2[TSIT5_DENSE_MAX];
+#pragma unroll
+    for (int s = 0; s < TSIT5_DENSE_MAX; ++s) e2[s] = 0.0;
+    if (e < n) {                            // n is a multiple of V
+        float acc[8][V], sc[V], m[V];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            if (p.accumulate) {
+                ldv<V>(acc[i], p.w + (int64_t)i * n + e);
+            } else {
+#pragma unroll
+                for (int q = 0; q < V; ++q) acc[i][q] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            const int64_t row = (e + q) / p.O;
+            sc[q] = p.ls ? p.ls[(int)(e + q - row * p.O)] : 1.f;
+            m[q] = p.vm ? p.vm[row] : 1.f;
+            acc[7][q] = 0.f;
+        }
+#pragma unroll
+        for (int s = 0; s < TSIT5_DENSE_MAX; ++s) {
+            if (s >= p.ns) continue;
+            float x[V], g[V];
+            ldv<V>(x, p.xs[s] + e);
+            ldv<V>(g, p.gt[s] + e);
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                const float d = g[q] - x[q];
+                const double ed = (double)sc[q] * ((double)g[q] - (double)x[q]);
+                e2[s] += ed * ed * (double)m[q];
+                const float gh = -(p.gscale * sc[q] * sc[q] * d * m[q]);
+                acc[0][q] += gh;
+#pragma unroll
+                for (int i = 0; i < 7; ++i) acc[1 + i][q] = fmaf(p.b[s][i], gh, acc[1 + i][q]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 7; ++i) stv<V>(p.w + (int64_t)i * n + e, acc[i]);
+        float kb[V];
+        if (p.kbar_add) {
+            ldv<V>(kb, p.kbar + e);
+        } else {
+#pragma unroll
+            for (int q = 0; q < V; ++q) kb[q] = 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) kb[q] = fmaf(p.h, acc[7][q], kb[q]);
+        stv<V>(p.kbar + e, kb);
+    }
+#pragma unroll
+    for (int s = 0; s < TSIT5_DENSE_MAX; ++s) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) e2[s] += __shfl_xor(e2[s], off, 64);
+        if ((threadIdx.x & 63) == 0) sh[s][threadIdx.x >> 6] = e2[s];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int s = 0; s < TSIT5_DENSE_MAX; ++s) {
+            if (s >= p.ns) continue;
+            p.part[s][blockIdx.x] = sh[s][0] + sh[s][1] + sh[s][2] + sh[s][3];
+            for (int j = (int)(blockIdx.x + gridDim.x); j < 2 * p.nblk; j += (int)gridDim.x) p.part[s][j] = 0.0;     // the slot's other entries
+        }
+    }
+}
+
+hipError_t launch_tsit5_dense_adjoint(const Tsit5DenseArgs& p, hipStream_t s) {
+    const int64_t n = p.N * p.O;
+    if (n <= 0) return hipSuccess;
+    if (p.ns < 1 || p.ns > TSIT5_DENSE_MAX || !p.w || !p.kbar || p.nblk != solver_adjoint_blocks(p.N, p.O)) return hipErrorInvalidValue;
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    bool v4 = n % 4 == 0 && al16(p.w) && al16(p.kbar);
+    for (int i = 0; i < p.ns; ++i) {
+        if (!p.xs[i] || !p.gt[i] || !p.part[i]) return hipErrorInvalidValue;
+        v4 = v4 && al16(p.xs[i]) && al16(p.gt[i]);
+    }
+    // (either grid has at most nblk blocks, so a save's per-block sums fit its [2][nblk] slot)
+    if (v4) {
+        hipLaunchKernelGGL(k_tsit5_dense_adjoint<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, p);
+    } else {
+        hipLaunchKernelGGL(k_tsit5_dense_adjoint<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s) {

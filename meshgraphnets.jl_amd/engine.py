@@ -488,12 +488,18 @@ class Engine:
 
     def solver_grad_tsit5(self, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, adaptive=True, abstol=1e-6, reltol=1e-3,
                           val_mask=None, inflow_mask=None, inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0,
-                          inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0):
+                          inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0,
+                          dense_saves=False):
         """Loss and gradient of one Tsit5 solve of ode_func_train on the device (mgn_solver_grad_tsit5): solver_grad's loss, arguments
         and array rules, with
           adaptive=True:  rollout("Tsit5", ...)'s PI-controlled steps (first step dt, 0: the Hairer-Wanner start; abstol / reltol;
                           tstops = the saves), the error norm on the states (not overwritten);
           adaptive=False: fixed steps of dt on solver_grad's Euler time grid and save rule.
+          dense_saves=True: no tstops -- `solve(...; saveat = saves)` as the reference's MultipleShooting calls it.  The only stop is t1
+                          (adaptive: the controller steps freely; fixed: steps of dt, which need not divide saves_dt, the last one cut
+                          or snapped onto t1); a save no step ends on is Tsit5's dense output inside the step that passes it, and the
+                          adjoint carries its loss term with the steps and the interpolation points held fixed.  stored_bytes and
+                          max_store_bytes then count 7 * N * O floats of sums as well.
         The gradient is the discrete adjoint of the computed solution with the accepted step sequence held fixed (step sizes and
         accept / reject decisions are constants); not InterpolatingAdjoint's continuous adjoint.
         Returns (grads, loss, stats): stats has n_accept, n_reject, n_rhs, step_t, step_h (the accepted steps' start times and sizes,
@@ -502,7 +508,7 @@ class Engine:
                                                                    val_mask, inflow_mask, inflow_data, loss_scale, cont_target, inflow_rule,
                                                                    time_type, want_pred, out, abstol, reltol)
         o = _capi.MgnSolverGradOpts()
-        o.adaptive = 1 if adaptive else 0
+        o.adaptive = (_capi.MGN_TSIT5_ADAPTIVE if adaptive else 0) | (_capi.MGN_TSIT5_DENSE_SAVES if dense_saves else 0)
         o.max_store_bytes = int(max_store_bytes)
         cap = step_cap
         if cap is None:                      # enough for every step a fixed-step solve takes, or a generous start for an adaptive one
@@ -516,7 +522,7 @@ class Engine:
         if step_cap is None and o.n_steps > cap:     # the record was cut: the call again with room for every step (bitwise repeatable)
             return self.solver_grad_tsit5(x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, adaptive, abstol, reltol, val_mask,
                                           inflow_mask, inflow_data, loss_scale, cont_target, cont_weight, inflow_rule, time_type, want_pred,
-                                          out, o.n_steps, max_store_bytes)
+                                          out, o.n_steps, max_store_bytes, dense_saves)
         del keep
         nrec = min(int(o.n_steps), int(cap))
         stats = dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs, n_steps=int(o.n_steps), step_t=st[:nrec].copy(),
@@ -1052,13 +1058,15 @@ class GroupEngine:
 
     def solver_grad_tsit5(self, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, adaptive=True, abstol=1e-6, reltol=1e-3,
                           val_mask=None, inflow_mask=None, inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0,
-                          inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0):
+                          inflow_rule="reference", time_type=np.float32, want_pred=False, out=None, step_cap=None, max_store_bytes=0,
+                          dense_saves=False):
         """Engine.solver_grad_tsit5 on the partitioned mesh (mgn_group_solver_grad_tsit5).  max_store_bytes bounds each rank's stored stage
-        inputs; stats' stored_bytes is rank 0's (24 * n_own * O bytes per accepted step), the step record is the same on every rank."""
+        inputs; stats' stored_bytes is rank 0's (24 * n_own * O bytes per accepted step, with dense_saves 28 * n_own * O more), the step
+        record is the same on every rank."""
         self._host_arrays(gt=gt, cont_target=cont_target, out=out)
         return Engine.solver_grad_tsit5(_GroupCalls(self), x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, adaptive, abstol,
                                         reltol, val_mask, inflow_mask, inflow_data, loss_scale, cont_target, cont_weight, inflow_rule,
-                                        time_type, want_pred, out, step_cap, max_store_bytes)
+                                        time_type, want_pred, out, step_cap, max_store_bytes, dense_saves)
 
     def ode_vjp(self, x, node_type_onehot, ef_raw, lam, val_mask=None, want_dxdt=False):
         """Engine.ode_vjp on the partitioned mesh (mgn_group_ode_vjp): (xbar [N][O], gs, dxdt or None), complete and in the caller's order."""

@@ -455,6 +455,16 @@ TSIT5_A = ((0, 0, 0, 0, 0, 0),
            (5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525, 0, 0),
            (5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383, 0),
            (0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774))
+# Tsit5's dense output (the free 4th-order interpolant of Tsitouras 2011, as OrdinaryDiffEq.jl's): x(t_n + theta h) = x_n + h sum_i
+# b_i(theta) k_i over the seven stages (k_7 = f(x_{n+1})), b_i(theta) = sum_p TSIT5_R[i][p] theta^(p + 1).  The library's own copy is
+# behind mgn_tsit5_interp_weights.
+TSIT5_R = ((1.0, -2.763706197274826, 2.9132554618219126, -1.0530884977290216),
+           (0.0, 0.13169999999999998, -0.2234, 0.1017),
+           (0.0, 3.9302962368947516, -5.941033872131505, 2.490627285651253),
+           (0.0, -12.411077166933676, 30.33818863028232, -16.548102889244902),
+           (0.0, 37.50931341651104, -88.1789048947664, 47.37952196281928),
+           (0.0, -27.896526289197286, 65.09189467479366, -34.87065786149661),
+           (0.0, 1.5, -4.0, 2.5))
 
 
 def solver_training_tsit5(rhs, vjp, x0, gt, step_t, step_h, val_mask=None, n_scale=None, save_step=None, cont_target=None,
@@ -566,12 +576,15 @@ def train_step_solver_training(eng, gt, node_type_onehot, ef_raw, tstart, dt, ts
 
 def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, tstop, interval_size, continuity_term, val_mask=None,
                                  inflow_mask=None, inflow_data=None, solver_dt=None, time_type=F32, inflow_rule="reference", solver="Euler",
-                                 adaptive=True, abstol=1e-6, reltol=1e-3, batched=False, max_windows_per_pass=0):
+                                 adaptive=True, abstol=1e-6, reltol=1e-3, batched=False, max_windows_per_pass=0, interpolate_saves=False):
     """train_step(::MultipleShooting) with a fixed-step Euler solver (reference src/strategies.jl:312-383): one Engine.solver_grad per
     window rg of multiple_shooting_ranges, u0 = gt[first(rg)], saveat = tsteps[rg], loss = mean((gt[rg] - pred) .^ 2 .* val_mask) (no
     normaliser); the continuity term continuity_term * sum(abs, pred_{i-1}[end] - gt[first(rg_i)]) goes with window i - 1.  solver,
-    adaptive, abstol, reltol as for train_step_solver_training (every window steps onto its saves: tstops = saveat, where the reference
-    interpolates a window solved without tstops).  Returns the summed (gs, loss).
+    adaptive, abstol, reltol as for train_step_solver_training.  Returns the summed (gs, loss).
+    interpolate_saves (solver="Tsit5"): False (the default, the bits this function has always returned) steps every window onto its
+    saves, tstops = saveat.  True is what the reference computes: it solves every window with saveat and NO tstops
+    (src/strategies.jl:343-355), so the steps end on the window's end only and the saves between them come from Tsit5's dense output
+    (Engine.solver_grad_tsit5(dense_saves=True)); per window, not with batched=True.
     batched=True: Euler and fixed-step Tsit5 (adaptive=False) solve all windows in one Engine.shooting_grad call (windows with the same
     step plan as one batch of graph copies, at most max_windows_per_pass per pass, 0: no cap) -- the same sum.  Adaptive Tsit5 keeps the
     per-window loop (each window would need its own step controller)."""
@@ -579,6 +592,11 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
     ranges = multiple_shooting_ranges(T, interval_size)
     if inflow_mask is not None and inflow_data is None:
         inflow_data = gt
+    if interpolate_saves and solver != "Tsit5":
+        raise ValueError("interpolate_saves is Tsit5's dense output: solver must be 'Tsit5'")
+    if interpolate_saves and batched:
+        raise ValueError("interpolate_saves solves window by window: Engine.shooting_grad steps onto every save (batched must be False)")
+    dense = {"dense_saves": True} if interpolate_saves else {}
     if batched and not (solver == "Tsit5" and adaptive):
         gs, loss = eng.shooting_grad(node_type_onehot, ef_raw, gt, ranges, [_range_at(tstart, dt, a, time_type) for a, _ in ranges],
                                      [_range_at(tstart, dt, b, time_type) for _, b in ranges], solver_dt or dt, dt, val_mask=val_mask,
@@ -593,7 +611,7 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
                                   _range_at(tstart, dt, a, time_type), _range_at(tstart, dt, b, time_type), sdt, dt, b - a + 1,
                                   val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=inflow_data,
                                   cont_target=None if nxt is None else gt[nxt], cont_weight=float(continuity_term) if nxt is not None else 0.0,
-                                  inflow_rule=inflow_rule, time_type=time_type)
+                                  inflow_rule=inflow_rule, time_type=time_type, **dense)
         gs_sum = np.asarray(gs, np.float64) if gs_sum is None else gs_sum + gs
         loss_sum += float(loss)
     return gs_sum, loss_sum
