@@ -544,6 +544,43 @@ int mgn_step_datapoint(mgn_handle* h, int32_t datapoint, int32_t accumulate, con
                        int32_t mask_index_base, float* grads, size_t n_grads, float* loss);
 int mgn_datapoint_export(mgn_handle* h, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target);
 
+/* A minibatch of datapoints of the resident trajectory in one training step: the reference's Args.batchsize ("Size per batch (not
+ * implemented yet)", src/MeshGraphNets.jl:39,224) for the loop of src/MeshGraphNets.jl:364-378.  The result is step! on the
+ * block-diagonal FeatureGraph of the B datapoints datapoints[0 .. B - 1] (host array; they may repeat and come in any order) with the
+ * mask repeated per copy:
+ *     loss_b = mgn_step_datapoint's loss on datapoint datapoints[b]: the mean of (out - target)^2 over the nmask x O masked entries
+ *     loss   = (1 / B) sum_b loss_b            grads = the gradient of loss = the mean of the per-datapoint gradients, packed order
+ *     losses[b] = loss_b                       (host [B]; NULL: not wanted)
+ * mask (listed once), mask_index_base, grads (host or device pointer), n_grads and the argument checks are mgn_step_datapoint's.  The
+ * noise of datapoint t is the same bits as in the single call: the key (seed, t N + caller's node id, o) does not know the batch.
+ *
+ * B == 1 is mgn_step_datapoint in every respect -- the same path, the same bits, two edge sets, ln_dims = MGN_LN_ALL and a partitioned
+ * handle included -- with losses[0] = loss.  B > 1 runs on a companion engine holding B copies of the handle's graph in the handle's
+ * own engine order (the one mgn_shooting_grad uses: two batch sizes are kept per handle, parameters are packed again only after
+ * mgn_set_params changed them, a new graph and mgn_destroy drop them).  One launch assembles the B datapoints' nf and target into the
+ * companion's arena; the trajectory's normalised edge rows are replicated there and rebuilt only when the trajectory, the norms, that
+ * arena or B change; the masked loss keeps per-copy double partials in fixed slots and one fold yields every loss_b and their mean in
+ * double, each rounded once.  Every later stage is mgn_step's on B N nodes and B E edges: its size regimes, arena plan and hipGraph
+ * replay.  The handle's own training state is not touched: a later mgn_step_datapoint returns the bits it returned before.  Loss and
+ * gradients are bitwise repeatable (where no mask entry repeats, as for mgn_step).
+ *
+ * Online normalisers (accumulate != 0) ACCUMULATE FIRST AND NORMALISE AFTERWARDS: the B datapoints' raw rows are added to the totals
+ * one datapoint at a time in the order listed, each as one call -- count and calls advance per datapoint, a group stops adding once
+ * calls reaches max_accumulations, each with mgn_step_datapoint's reduction in its order, so the totals after the call are bitwise
+ * those that B accumulating mgn_step_datapoint calls leave -- and all B datapoints are then normalised with the resulting maps.  This
+ * is NOT what B sequential calls compute: there datapoint b is normalised with the maps after b + 1 accumulations.  No host copy of
+ * the norms and no synchronisation are added.
+ *
+ * Refusals, all before any launch, the handle stays usable.  MGN_E_ARG: NULL datapoints, mask, grads or loss; B < 1 or
+ * B > MGN_DATAPOINT_BATCH_MAX; a datapoint outside [0, T - 2]; what mgn_step_datapoint refuses in its own arguments; B N or B E beyond
+ * INT32_MAX.  MGN_E_STATE: no graph, no trajectory, dtype != MGN_F32, and for B > 1 a partitioned handle (nranks != 1: it drives one
+ * partition).  MGN_E_UNSUPPORTED for B > 1 with two edge sets (the companion replicates one) and with ln_dims = MGN_LN_ALL (whole-array
+ * statistics would span the batch, which is a different model).  MGN_E_OOM when the companion's arena does not fit.                  */
+#define MGN_DATAPOINT_BATCH_MAX 64
+int mgn_step_datapoints(mgn_handle* h, const int32_t* datapoints /* host [B] */, int32_t B, int32_t accumulate,
+                        const int32_t* mask, int64_t nmask, int32_t mask_index_base,
+                        float* grads, size_t n_grads, float* loss, float* losses /* host [B] or NULL */);
+
 /* Vector-Jacobian product of the right-hand side f = mgn_ode_step (reference ode_step, src/solve.jl:188-219) for the
  * solver-based training strategies, where the adjoint of `solve` needs lambda^T df/dx and lambda^T df/dps per RHS
  * evaluation (ZygoteVJP inside the sensitivity algorithm, src/strategies.jl:175-196).  Inputs as mgn_ode_step (raw edge

@@ -31,7 +31,7 @@ export FeatureGraph, GraphNetwork, step!, load, save!, shooting_grad
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
        native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
 export rollout_eval, native_validation_step
-export train_trajectory!, step_datapoint!, online_norms!, norm_state, norm_state!, datapoint_export
+export train_trajectory!, step_datapoint!, step_datapoints!, online_norms!, norm_state, norm_state!, datapoint_export
 export comm_unique_id, comm_init!, comm_init_file!, comm_barrier, processor_steps_dev!
 
 const LIB = get(ENV, "MGN_HIP_LIB", joinpath(@__DIR__, "..", "meshgraphnets.jl_amd", "lib", "libmgn_hip.so"))
@@ -550,6 +550,26 @@ function step_datapoint!(mgn::GraphNetwork, datapoint::Integer, mask::AbstractVe
             (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Int64, Int32, Ptr{Float32}, Csize_t, Ref{Float32}),
             mgn.handle, datapoint - 1, accumulate ? 1 : 0, mk, length(mk), 1, gs, length(gs), loss))
     return (gs,), loss[]
+end
+
+"""
+`step!` on the block-diagonal graph of the datapoints `datapoints` (1-based, repeats allowed, at most 64) of the resident trajectory with
+the mask repeated per copy (`Args.batchsize`): `((gs,), loss, losses)` with `loss` the mean of the per-datapoint `losses` and `gs`
+its gradient.  `accumulate`: the online normalisers take all the datapoints first, then every one is normalised with the result.
+"""
+function step_datapoints!(mgn::GraphNetwork, datapoints::AbstractVector{<:Integer}, mask::AbstractVector{<:Integer}; accumulate::Bool = false)
+    ps = mgn.ps::Vector{Float32}
+    sync_params!(mgn, ps)
+    gs = Vector{Float32}(undef, length(ps))
+    loss = Ref{Float32}(0)
+    dp = Vector{Int32}(Array(datapoints) .- 1)
+    losses = zeros(Float32, max(length(dp), 1))
+    mk = Vector{Int32}(Array(mask))
+    GC.@preserve dp mk gs losses check(mgn.handle,
+        ccall((:mgn_step_datapoints, LIB), Cint,
+            (Ptr{Cvoid}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int64, Int32, Ptr{Float32}, Csize_t, Ref{Float32}, Ptr{Float32}),
+            mgn.handle, dp, length(dp), accumulate ? 1 : 0, mk, length(mk), 1, gs, length(gs), loss, losses))
+    return (gs,), loss[], losses[1:length(dp)]
 end
 
 function online_norms!(mgn::GraphNetwork; node::Bool = true, edge::Bool = true, out::Bool = true, max_acc::Real = 1e6,

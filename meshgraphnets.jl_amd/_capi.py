@@ -115,6 +115,7 @@ PROTOTYPES = {
     "mgn_train_online_norms": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_float]),
     "mgn_train_norm_state": (C.c_int, [_H, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
     "mgn_step_datapoint": (C.c_int, [_H, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
+    "mgn_step_datapoints": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p, _f32p]),
     "mgn_datapoint_export": (C.c_int, [_H, C.c_int32, C.c_int32, _f32p, _f32p, _f32p]),
     "mgn_ode_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),
     "mgn_forward_vjp": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t]),

@@ -203,7 +203,7 @@ struct mgn_engine {
     // mgn_shooting_grad: the companion engine solving B windows at once on B copies of this handle's graph (engine order, node offset
     // w N), one per pass size B, kept until the graph changes, with the generation of the parameters it holds; the call's staging
     uint64_t params_gen = 0;               // bumped by every mgn_set_params that changes the parameters
-    struct ShootKid { int32_t b = 0; mgn_engine* e = nullptr; uint64_t params_gen = 0; bool params_set = false; };
+    struct ShootKid { int32_t b = 0; mgn_engine* e = nullptr; uint64_t params_gen = 0; bool params_set = false; bool latents = false; };   // latents: the inference latents exist (a solve asked for them; mgn_step_datapoints never does)
     std::vector<ShootKid> shoot_kids;      // at most two pass sizes (a group's full passes and its remainder)
     DevBuf shoot;
     bool companion = false;                // this is a companion: its training arena never sizes itself from the device's free memory
@@ -295,6 +295,8 @@ int gather_rows_global(mgn_engine* h, const float* local_dev, int W, float* out)
 int rank_fold_f64(mgn_engine* h, double* head, int64_t nhead, const double* acc, int64_t n, float* out);
 bool is_bf16(const mgn_engine* h);
 void shoot_release(mgn_engine* h);     // mgn_solve.cpp: drops mgn_shooting_grad's companions and staging
+// mgn_solve.cpp: the cached companion engine of B block-diagonal copies of h's graph (mgn_shooting_grad: inference = true; mgn_step_datapoints: false)
+int companion_engine(mgn_engine* h, int32_t B, const char* who, bool inference, mgn_engine** out);
 // The drivers behind mgn_ode_vjp, mgn_forward_vjp (mgn_train.cpp), mgn_solver_grad, mgn_solver_grad_tsit5 and mgn_rollout_eval
 // (mgn_solve.cpp): the public symbols' checks and work, with `partitions` saying whether a partitioned handle (nranks > 1) is served.
 // The rank-handle symbols pass false and keep their refusals; mgn_group_* (mgn_group.cpp) passes true.  On a partitioned call every

@@ -1071,10 +1071,13 @@ struct ShootGroup {
     TimeGrid tg;                             // its first window's
 };
 
-// the companion for passes of B windows: B copies of h's graph in h's engine order (row w N + i = window w's engine row i), not renumbered;
-// parameters and normalisers brought up to date
-int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
-    const char* who = shoot_who;
+}  // namespace
+
+// The companion of B copies of h's graph in h's engine order (row w N + i = copy w's engine row i), not renumbered, on h's stream and with
+// h's parameters (packed again only when they changed).  inference: what a solve on it needs as well -- the inference latents, h's
+// normalisers (a blocking copy where the device rewrote them) and the inference weight layouts.  The batched training step
+// (mgn_step_datapoints) takes normalised inputs and trains: it asks for none of the three.
+int mgn::companion_engine(mgn_handle* h, int32_t B, const char* who, bool inference, mgn_engine** out) {
     mgn_engine::ShootKid* kid = nullptr;
     for (auto& k : h->shoot_kids)
         if (k.b == B) kid = &k;
@@ -1101,14 +1104,13 @@ int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
         EdgeList sets[MAX_EDGE_SETS];
         sets[0] = {(int64_t)B * E, snd.data(), rcv.data(), 0};
         int rc = rebuild_graph(c, B * N, sets, nullptr, 0, false, who, nullptr, 0);
-        if (!rc) rc = alloc_latents(c);
         if (rc) {
             rc = fail(h, rc, "%s: companion graph: %s", who, c->err.c_str());
             mgn_destroy(c);
             return rc;
         }
         c->have_graph = true;
-        h->shoot_kids.push_back({B, c, 0, false});
+        h->shoot_kids.push_back({B, c, 0, false, false});
         kid = &h->shoot_kids.back();
         // the copies keep h's engine order: no renumbering, edges in the replicated (receiver-sorted, stable) order
         const LocalGraph& cg = c->g;
@@ -1125,6 +1127,12 @@ int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
         kid->params_set = true;
         kid->params_gen = h->params_gen;
     }
+    *out = c;
+    if (!inference) return MGN_OK;
+    if (!kid->latents) {
+        if (int rc = alloc_latents(c)) return fail(h, rc, "%s: companion graph: %s", who, c->err.c_str());
+        kid->latents = true;
+    }
     if (int rc = sync_norms_host(h)) return rc;
     if (c->norms_host != h->norms_host || c->have_nnorm != h->have_nnorm || c->have_enorm != h->have_enorm || c->have_onorm != h->have_onorm) {
         const mgn_config& k = h->cfg;
@@ -1137,9 +1145,13 @@ int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) {
         c->norms_host = h->norms_host;
     }
     if (int rc = need(c, true, true, true, true)) return fail(h, rc, "%s: companion: %s", who, c->err.c_str());
-    *out = c;
     return MGN_OK;
 }
+
+namespace {
+
+// the companion for passes of B windows: parameters and normalisers brought up to date
+int shoot_companion(mgn_handle* h, int32_t B, mgn_engine** out) { return companion_engine(h, B, shoot_who, true, out); }
 
 // the static inputs of a companion pass: h's engine-order arrays replicated B times on the device, the edges encoded once into elat0
 int shoot_statics(mgn_engine* c, int32_t B, int32_t N, const float* oh, const float* vm, const float* ef, char* elat0, size_t eb) {

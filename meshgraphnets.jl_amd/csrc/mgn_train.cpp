@@ -135,12 +135,14 @@ struct TrainState {
         DevBuf stddev, noisy;            // [O]; [N] 0/1 in the engine's order (some_nodes)
         uint64_t seed = 0;
         bool ef_pad_ok = false;          // the arena's ef_pad[0] holds this trajectory's edge features under the norms as they stand
+        uint64_t ef_gen = 0;             // bumped when the trajectory or the edge normaliser changes: what a companion's replicated edge rows were built from (Batch::ef_gen)
         bool ef_sums_ok = false;         // ef_sums holds ef_raw's column sums
         DevBuf ef_sums;                  // [2][Fe] doubles: what one accumulation of ef_raw adds (mgn_feature_stats' sums, formed once)
         DevBuf work;                     // accumulating steps: cur and d [N][O] each in the caller's order (a partition: its rows, the engine's order), then launch_col_stats' partials of both
         DevBuf xsum;                     // a partition's sums on their way to the peers: this rank's [cur | d] ([2][O] each) and its ef_raw's [2][Fe], then every rank's of either
         void drop() {
             have = false; T = 0; noise = some_nodes = false; ef_pad_ok = ef_sums_ok = false;
+            ++ef_gen;
             delta.clear();
             for (DevBuf* b : {&frames, &onehot, &ef_raw, &stddev, &noisy, &ef_sums, &work, &xsum}) b->release();
         }
@@ -153,13 +155,23 @@ struct TrainState {
         float eps = 1e-8f;
     } on[3];
     DevBuf on_totals;            // doubles [node sum, sum of squares (O each) | edge (Fe each) | output (O each)]
+    // mgn_step_datapoints, on the companion of B copies (engine_internal.h: companion_engine) -- the parent's state holds the trajectory
+    // and the normalisers, this one the batch: whether ef_pad[0] holds the parent trajectory's normalised edge rows B times and from which
+    // Trajectory::ef_gen (a new arena resets ef_ok: prepare_graph), the parent's node map for the mask (a renumbered parent), and the
+    // fold's result [loss_0 .. loss_{B-1} | mean].  The per-copy loss partials live in `loss`, the mask in `mask`.
+    struct Batch {
+        bool ef_ok = false;
+        uint64_t ef_gen = 0;
+        std::vector<int32_t> g2l;
+        DevBuf out;
+    } batch;
 };
 
 void train_invalidate(mgn_engine* h, int what) {
     if (!h || !h->train) return;
     if (what & 1) h->train->packed = false;
     if (what & 2) { h->train->graph_ready = false; h->train->la_ready = false; h->train->traj.drop(); }
-    if (what & 4) h->train->traj.ef_pad_ok = false;
+    if (what & 4) { h->train->traj.ef_pad_ok = false; ++h->train->traj.ef_gen; }
 }
 
 void train_free(mgn_engine* h) {
@@ -485,6 +497,7 @@ int prepare_graph(mgn_engine* h) {
     }
     T.drop_graphs();
     T.traj.ef_pad_ok = false;
+    T.batch.ef_ok = false;
     T.size_cus = train_size_cus();
     T.wg_rpb_last = T.wg_rpb_node = 0;
     for (int64_t& v : T.wg_rpb_edge) v = 0;
@@ -518,8 +531,9 @@ namespace {
 
 // The five kinds of job that differentiate the model: step! (mgn_step), the pullback of the model call (mgn_forward_vjp), of the right-hand
 // side (mgn_ode_vjp), one step of a reverse sweep (mgn_solver_grad and its kin: the right-hand side's, on resident inputs), and step! on
-// one datapoint of the resident trajectory (mgn_step_datapoint: init_train_step on the device, then mgn_step's stages)
-enum JobKind { JOB_STEP, JOB_FORWARD_VJP, JOB_RHS_VJP, JOB_SWEEP_STEP, JOB_DATAPOINT };
+// one datapoint of the resident trajectory (mgn_step_datapoint: init_train_step on the device, then mgn_step's stages).  JOB_DATAPOINTS
+// is step! on B datapoints at once (mgn_step_datapoints): it runs on the companion of B copies, its inputs come from the parent handle
+enum JobKind { JOB_STEP, JOB_FORWARD_VJP, JOB_RHS_VJP, JOB_SWEEP_STEP, JOB_DATAPOINT, JOB_DATAPOINTS };
 
 struct TrainJob {
     JobKind kind = JOB_STEP;
@@ -539,6 +553,9 @@ struct TrainJob {
     double* gacc = nullptr;
     // step! on a datapoint of the resident trajectory (TrainState::traj): mask, loss and grads as for step!
     int32_t datapoint = 0; bool accumulate = false;
+    // step! on B datapoints of the PARENT's resident trajectory (the job's own handle is the companion of B copies): mask (listed once,
+    // the parent's node ids), loss (the mean) and grads as for step!, losses [B] (null: not wanted)
+    mgn_engine* parent = nullptr; const int32_t* datapoints = nullptr; int32_t B = 0; float* losses = nullptr;
 };
 
 // partitions: the entry point runs on a partitioned mesh (mgn_step); every check comes before the first collective
@@ -714,7 +731,7 @@ int datapoint_norms(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
     HIPCHK(h, launch_norms_from_totals(a, st));
     h->norms_host_stale = true;        // (its two readers refresh it: sync_norms_host)
     invalidate_static(h);              // as mgn_set_norms does
-    if (write[1]) R.ef_pad_ok = false;
+    if (write[1]) { R.ef_pad_ok = false; ++R.ef_gen; }
     return MGN_OK;
 }
 int datapoint_stage(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
@@ -732,6 +749,44 @@ int datapoint_stage(mgn_engine* h, int32_t t, bool accumulate, hipStream_t st) {
         HIPCHK(h, launch_affine_pad(R.ef_raw.as<float>(), c.Fe, nullptr, 0, es, es ? es + c.Fe : nullptr, A + T.ef_pad[0], c.L, E, st));
     }
     R.ef_pad_ok = true;
+    return MGN_OK;
+}
+// mgn_step_datapoints: nf_pad, target and (when stale) ef_pad of the companion c's arena from the parent h's resident trajectory, under
+// h's device norms as they stand after the call's accumulations -- accumulate first, normalise afterwards: the B datapoints' raw rows go
+// into the totals one datapoint at a time in the order listed, each as one call of datapoint_norms (its reduction, its order, count and
+// calls per datapoint), then one launch assembles all B under the resulting maps.  No copy of the norms, no synchronisation.
+int datapoints_stage(mgn_engine* h, mgn_engine* c, const int32_t* ts, int32_t B, bool accumulate, hipStream_t st) {
+    if (accumulate) {
+        for (int32_t b = 0; b < B; ++b)
+            if (int rc = datapoint_norms(h, ts[b], true, st)) return rc;
+    } else if (int rc = datapoint_norms(h, ts[0], false, st)) {    // (restored totals get their maps here)
+        return rc;
+    }
+    const TrainState::Trajectory& R = h->train->traj;
+    TrainState& T = *c->train;
+    const mgn_config& k = h->cfg;
+    const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    float* A = T.arena.as<float>();
+    const float* nrm = h->norms.as<float>();
+    DatapointBatchArgs a{};
+    a.frames = R.frames.as<float>();
+    a.onehot = k.Fn > k.O ? R.onehot.as<float>() : nullptr;
+    a.gid = h->g.renumbered ? h->d_own_gid.as<int32_t>() : nullptr;
+    a.noisy = R.noise && R.some_nodes ? R.noisy.as<uint8_t>() : nullptr;
+    a.stddev = R.noise ? R.stddev.as<float>() : nullptr;
+    a.nrm_n = h->have_nnorm ? nrm : nullptr;
+    a.nrm_o = h->have_onorm ? nrm + 2 * k.Fn + 2 * k.Fe : nullptr;
+    a.nf = A + T.nf_pad; a.target = T.target.as<float>();
+    a.N = N; a.B = B; a.O = k.O; a.Fn = k.Fn; a.ld = k.L;
+    a.seed = R.seed;
+    for (int32_t b = 0; b < B; ++b) { a.t[b] = ts[b]; a.delta[b] = R.delta[(size_t)ts[b]]; }
+    HIPCHK(h, launch_datapoints_assemble(a, st));
+    if (E > 0 && (!T.batch.ef_ok || T.batch.ef_gen != R.ef_gen)) {   // a constant of the trajectory: rebuilt when the trajectory, the norms or the companion's arena changed
+        const float* es = h->have_enorm ? nrm + 2 * k.Fn : nullptr;
+        HIPCHK(h, launch_datapoints_edges(R.ef_raw.as<float>(), k.Fe, es, es ? es + k.Fe : nullptr, h->es[0].d_edge_gid.as<int64_t>(), A + T.ef_pad[0], k.L, E, B, st));
+    }
+    T.batch.ef_ok = true;
+    T.batch.ef_gen = R.ef_gen;
     return MGN_OK;
 }
 // what every entry point of the datapoint family asks of the handle before it looks at its arguments
@@ -851,7 +906,7 @@ struct TrainPass {
             lrows_all = std::max<int64_t>(lrows_all, sx[q].E);
         }
     }
-    bool vjp() const { return J.kind != JOB_STEP && J.kind != JOB_DATAPOINT; }
+    bool vjp() const { return J.kind != JOB_STEP && J.kind != JOB_DATAPOINT && J.kind != JOB_DATAPOINTS; }
     float* io() const { return A + T.io; }    // the VJPs' rows: x [N][O] | lambda [N][O] | onehot [N][Fn-O] | val_mask [N]
     int comm_fail(const char* what) { return fail(h, MGN_E_RCCL, "mgn_step: %s: %s", what, h->comm->err.c_str()); }
 
@@ -881,6 +936,7 @@ struct TrainPass {
     int stage_features() {
         const float* src = nullptr;
         T.traj.ef_pad_ok = false;
+        T.batch.ef_ok = false;             // (a companion's arena: mgn_shooting_grad's sweep writes its own edge rows here)
         HIPCHK(h, staged(J.nf, A + T.nf_raw, (size_t)NG * c.Fn, src));
         HIPCHK(h, launch_affine_pad_gather(src, c.Fn, nullptr, 0, nullptr, nullptr, renum ? ngid : nullptr, A + T.nf_pad, L, N, st));
         if (part && g.set[0].E > 0) {      // the local edges' rows of the global array, in the engine's order
@@ -903,7 +959,9 @@ struct TrainPass {
         }
         return stage_mask();
     }
-    int stage_mask() {
+    int stage_mask() { return stage_mask_by(renum, T.g2l); }
+    // map: the mask lists the caller's node ids of a renumbered graph (or of a partition), g2l takes them to engine rows
+    int stage_mask_by(bool map, const std::vector<int32_t>& g2l) {
         // the mask of the previous call is usually this call's (one trajectory, one mask: reference src/MeshGraphNets.jl:352): uploaded once
         const bool mask_dev = on_device(J.mask);
         const bool same = !mask_dev && T.mask_valid && T.mask_base == J.mask_index_base && (int64_t)T.mask_seen.size() == J.nmask &&
@@ -911,7 +969,7 @@ struct TrainPass {
         if (same) return MGN_OK;
         HIPCHK(h, T.mask.ensure((size_t)J.nmask * 4));
         T.mask_valid = false;
-        if (renum) {                       // the caller's node ids -> engine rows (0-based from here on)
+        if (map) {                         // the caller's node ids -> engine rows (0-based from here on)
             std::vector<int32_t> host_mask;
             const int32_t* mk = J.mask;
             if (mask_dev) {
@@ -921,7 +979,7 @@ struct TrainPass {
             }
             T.mask_host.clear();
             for (int64_t i = 0; i < J.nmask; ++i) {
-                const int32_t l = T.g2l[(size_t)(mk[i] - J.mask_index_base)];
+                const int32_t l = g2l[(size_t)(mk[i] - J.mask_index_base)];
                 if (l >= 0) T.mask_host.push_back(l);       // (a partition takes the entries it owns, as often as they are listed)
             }
             T.mask_n = (int64_t)T.mask_host.size();
@@ -970,6 +1028,7 @@ struct TrainPass {
             if (int rc = stage_rows(J.val_mask, 1, io() + (size_t)N * (O + c.Fn))) return rc;
         if (x) if (int rc = pad_state(x)) return rc;
         T.traj.ef_pad_ok = false;
+        T.batch.ef_ok = false;             // (a companion's arena: mgn_shooting_grad's sweep writes its own edge rows here)
         if (part && g.set[0].E > 0) {      // the local edges' rows of the whole mesh's array, in the engine's order (as stage_features)
             const float* src = nullptr;
             HIPCHK(h, staged(J.ef, A + T.ef_raw[0], (size_t)g.set[0].E * c.Fe, src));
@@ -1006,6 +1065,11 @@ struct TrainPass {
             case JOB_DATAPOINT:
                 rc = datapoint_stage(h, J.datapoint, J.accumulate, st);
                 if (!rc) rc = stage_mask();
+                break;
+            // the same for B datapoints, from the parent's trajectory into this companion's arena; the mask is listed once
+            case JOB_DATAPOINTS:
+                rc = datapoints_stage(J.parent, h, J.datapoints, J.B, J.accumulate, st);
+                if (!rc) rc = stage_mask_by(J.parent->g.renumbered, T.batch.g2l);
                 break;
         }
         if (rc) return rc;
@@ -1126,7 +1190,12 @@ struct TrainPass {
         const size_t y_out = T.a_de.h[T.m_de.nblk - 1][2];        // the decoder's output (its last unit's Y)
         nlb = vjp() ? 0 : loss_blocks(T.mask_n);
         HIPCHK(h, hipMemsetAsync(A + T.Gout, 0, (size_t)N * L * 4, st));
-        if (!vjp()) {   // loss = mean(mse_reduce(target, out)[mask]) and its gradient w.r.t. out
+        if (J.kind == JOB_DATAPOINTS) {   // the mean over the B copies of the masked loss of each, and its gradient: per-copy partials, one fold
+            HIPCHK(h, T.loss.ensure((size_t)J.B * nlb * sizeof(double)));
+            HIPCHK(h, T.batch.out.ensure((size_t)(J.B + 1) * 4));
+            HIPCHK(h, launch_loss_batch(A + y_out, L, T.target.as<float>(), O, T.mask.as<int32_t>(), T.mask_n, N / J.B, J.B,
+                                        J.parent->g.renumbered ? 0 : J.mask_index_base, A + T.Gout, T.loss.as<double>(), T.batch.out.as<float>(), st));
+        } else if (!vjp()) {   // loss = mean(mse_reduce(target, out)[mask]) and its gradient w.r.t. out
             HIPCHK(h, T.loss.ensure((size_t)nlb * sizeof(double)));
             HIPCHK(h, launch_loss(A + y_out, L, T.target.as<float>(), O, T.mask.as<int32_t>(), T.mask_n, J.nmask, renum ? 0 : J.mask_index_base,
                                   A + T.Gout, T.loss.as<double>(), st));
@@ -1409,6 +1478,15 @@ struct TrainPass {
             return MGN_OK;
         }
         if (part) return vjp() ? finish_partition_vjp() : finish_partition();
+        if (J.kind == JOB_DATAPOINTS) {     // the fold kernel rounded every loss once: [loss_0 .. loss_{B-1} | mean]
+            std::vector<float> lo((size_t)J.B + 1);
+            HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
+            HIPCHK(h, hipMemcpyAsync(lo.data(), T.batch.out.p, lo.size() * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+            *J.loss = lo[(size_t)J.B];
+            if (J.losses) memcpy(J.losses, lo.data(), (size_t)J.B * 4);
+            return MGN_OK;
+        }
         std::vector<double> lp((size_t)nlb);
         HIPCHK(h, hipMemcpyAsync(J.grads, G, h->params.size() * 4, hipMemcpyDefault, st));
         if (!vjp()) {
@@ -1488,6 +1566,7 @@ extern "C" int mgn_train_set_trajectory(mgn_handle* h, const float* frames, int3
         if (!(delta[(size_t)t] != 0.f)) return fail(h, MGN_E_ARG, "%s: the time step of datapoint %d is zero (or not a number)", who, (int)t);
     TrainState::Trajectory& R = h->train->traj;
     R.have = false; R.ef_pad_ok = false; R.ef_sums_ok = false;
+    ++R.ef_gen;
     const hipStream_t st = h->stream;
     const size_t fl = (size_t)T_ * (size_t)N * c.O, ol = (size_t)N * (c.Fn - c.O), el = (size_t)E * c.Fe;
     HIPCHK(h, R.frames.ensure(fl * 4));
@@ -1638,6 +1717,61 @@ extern "C" int mgn_step_datapoint(mgn_handle* h, int32_t datapoint, int32_t accu
     J.mask = mask; J.nmask = nmask; J.mask_index_base = mask_index_base;
     J.loss = loss; J.grads = grads;
     return train_run(h, J);
+} MGN_CATCH(h)
+
+// step! on the block-diagonal FeatureGraph of B datapoints (the reference's Args.batchsize, src/MeshGraphNets.jl:39,224): B times the rows
+// per launch, one weight-gradient pass, one set of launches.  B = 1 is mgn_step_datapoint itself.  B > 1 runs train_run on the cached
+// companion of B copies (mgn_solve.cpp: companion_engine; no norms, no inference latents), whose inputs datapoints_stage assembles from
+// this handle's trajectory; this handle's own training arena, mask cache and captured graphs are not touched.
+extern "C" int mgn_step_datapoints(mgn_handle* h, const int32_t* datapoints, int32_t B, int32_t accumulate, const int32_t* mask, int64_t nmask,
+                                   int32_t mask_index_base, float* grads, size_t n_grads, float* loss, float* losses) try {
+    const char* who = "mgn_step_datapoints";
+    static_assert(DATAPOINT_BATCH_MAX == MGN_DATAPOINT_BATCH_MAX, "the launch's table holds the ABI's largest batch");
+    if (!h) return MGN_E_ARG;
+    if (!datapoints || !mask || !grads || !loss) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > MGN_DATAPOINT_BATCH_MAX) return fail(h, MGN_E_ARG, "%s: B = %d outside [1, %d]", who, (int)B, MGN_DATAPOINT_BATCH_MAX);
+    if (B == 1) {
+        const int rc = mgn_step_datapoint(h, datapoints[0], accumulate, mask, nmask, mask_index_base, grads, n_grads, loss);
+        if (!rc && losses) losses[0] = *loss;
+        return rc;
+    }
+    if (int rc = datapoint_need(h, who, true, true)) return rc;
+    if (h->cfg.nranks != 1) return fail(h, MGN_E_STATE, "%s with B > 1 drives one partition", who);
+    const int32_t T_ = h->train->traj.T;
+    for (int32_t b = 0; b < B; ++b)
+        if (datapoints[b] < 0 || datapoints[b] > T_ - 2)
+            return fail(h, MGN_E_ARG, "%s: datapoint %d (entry %d) outside [0, %d]", who, (int)datapoints[b], (int)b, (int)T_ - 2);
+    if (nmask < 1) return fail(h, MGN_E_ARG, "%s: empty mask", who);
+    if (mask_index_base != 0 && mask_index_base != 1) return fail(h, MGN_E_ARG, "%s: mask_index_base must be 0 or 1", who);
+    const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+    for (int64_t i = 0; i < nmask; ++i) {
+        const int64_t n = (int64_t)mask[i] - mask_index_base;
+        if (n < 0 || n >= N) return fail(h, MGN_E_ARG, "%s: mask entry %lld out of range", who, (long long)i);
+    }
+    if ((int64_t)B * N > INT32_MAX || (int64_t)B * E > INT32_MAX)
+        return fail(h, MGN_E_ARG, "%s: %d copies of %lld nodes and %lld edges overflow int32 ids", who, (int)B, (long long)N, (long long)E);
+    if (h->nsets != 1) return fail(h, MGN_E_UNSUPPORTED, "%s with B > 1 takes one edge set (the companion replicates one)", who);
+    if (h->cfg.ln_dims == MGN_LN_ALL)
+        return fail(h, MGN_E_UNSUPPORTED, "%s with B > 1 and ln_dims = MGN_LN_ALL: whole-array statistics would span the batch, a different model", who);
+    if (int rc = need(h, true, true, false, true)) return rc;
+    if (n_grads != h->params.size()) return fail(h, MGN_E_ARG, "%s: grads has %zu floats, model has %zu", who, n_grads, h->params.size());
+    mgn_engine* c = nullptr;
+    if (int rc = companion_engine(h, B, who, false, &c)) return rc;
+    c->err.clear();
+    if (int rc = train_prepare(c, who, n_grads)) return fail(h, rc, "%s: companion: %s", who, c->err.c_str());
+    TrainState::Batch& X = c->train->batch;
+    if (h->g.renumbered && X.g2l.empty()) {
+        X.g2l.assign((size_t)h->g.N, 0);
+        for (int32_t i = 0; i < h->g.n_own; ++i) X.g2l[(size_t)h->g.own_gid[i]] = i;
+    }
+    TrainJob J;
+    J.kind = JOB_DATAPOINTS;
+    J.parent = h; J.datapoints = datapoints; J.B = B; J.accumulate = accumulate != 0; J.losses = losses;
+    J.mask = mask; J.nmask = nmask; J.mask_index_base = mask_index_base;
+    J.loss = loss; J.grads = grads;
+    const int rc = train_run(c, J);
+    if (rc && !c->err.empty()) return fail(h, rc, "%s: companion: %s", who, c->err.c_str());   // (an error of the parent's own stage stands as it is)
+    return rc;
 } MGN_CATCH(h)
 
 extern "C" int mgn_datapoint_export(mgn_handle* h, int32_t datapoint, int32_t normalised, float* nf, float* ef, float* target) try {

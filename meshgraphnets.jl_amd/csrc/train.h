@@ -174,6 +174,32 @@ struct DatapointArgs {
     float delta; uint64_t seed;
 };
 hipError_t launch_datapoint_assemble(const DatapointArgs& a, hipStream_t s);
+// mgn_step_datapoints: B <= DATAPOINT_BATCH_MAX datapoints of the resident trajectory (one partition) as one block-diagonal FeatureGraph.
+// Row r of the B N destination rows is copy w = r / N, engine row n = r mod N of datapoint t[w] (frames [T][N][O]; delta[w] its time
+// step); per element the operations, the noise key (seed, t[w] N + gid[n], o) and the gid / noisy handling of launch_datapoint_assemble:
+// nf [B N][ld] and target [B N][O] are the single launch's rows, copy after copy.  The table travels by value with the launch.
+constexpr int DATAPOINT_BATCH_MAX = 64;
+struct DatapointBatchArgs {
+    const float* frames; const float* onehot;
+    const int32_t* gid; const uint8_t* noisy; const float* stddev;
+    const float* nrm_n; const float* nrm_o;
+    float* nf; float* target;
+    int64_t N; int32_t B, O, Fn, ld;
+    uint64_t seed;
+    int32_t t[DATAPOINT_BATCH_MAX]; float delta[DATAPOINT_BATCH_MAX];
+};
+#pragma GCC visibility push(hidden)   // (new host functions stay out of the library's dynamic symbols)
+hipError_t launch_datapoints_assemble(const DatapointBatchArgs& a, hipStream_t s);
+// dst [B E][L]: row w E + j = [ src[egid ? egid[j] : j][0:Fe] * scale + shift | 0 ] for every copy w (launch_affine_pad's expression, each
+// row formed once): the trajectory's edge features, kept in the caller's order, in the engine's edge order of every copy
+hipError_t launch_datapoints_edges(const float* src, int Fe, const float* scale, const float* shift, const int64_t* egid, float* dst, int L,
+                                   int64_t E, int B, hipStream_t s);
+// launch_loss over B copies of N rows with the mask listed once (entries of one copy): G[n + w N][o] += 2 (out - target) / (B nmask);
+// partial [B][loss_blocks(nmask)] doubles in fixed slots; then one fold launch: out[w] = loss of copy w (its blocks added in order, over
+// nmask), out[B] = the mean of the B, formed in double, each rounded once.  Bitwise repeatable where no mask entry repeats.
+hipError_t launch_loss_batch(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int64_t N, int B,
+                             int32_t index_base, float* G, double* partial, float* out, hipStream_t s);
+#pragma GCC visibility pop
 // The online normalisers' maps from device-resident double totals [sum (dim) | sum of squares (dim)], one group each for the node state
 // columns, the edge features and the output.  add: totals += this call's sums first -- `partial` (launch_col_stats' nb blocks, added in
 // block order from zero: mgn_feature_stats' result) or, partial null, call_sums [2][dim] formed that way earlier.  write: scale / shift

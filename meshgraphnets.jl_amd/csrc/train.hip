@@ -1470,6 +1470,124 @@ __global__ __launch_bounds__(256) void k_datapoint_assemble(const DatapointArgs 
     }
 }
 
+// ---- mgn_step_datapoints: B datapoints of the resident trajectory as one block-diagonal FeatureGraph ----
+// k_datapoint_assemble for B datapoints in one launch: destination row r of B N is copy w = r / N, engine row n = r mod N of datapoint
+// a.t[w].  The same IEEE operations one by one and the same noise key (seed, t N + caller's node id, o) as the single kernel -- the key
+// does not know about the batch --, every element computed once, f32x4 stores where ld is a multiple of four.
+__global__ __launch_bounds__(256) void k_datapoints_assemble(const DatapointBatchArgs a) {
+    const int quads = (a.ld + 3) >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)a.B * a.N * quads) return;
+    const int64_t r = i / quads;
+    const int q = (int)(i - r * quads);
+    const int w = (int)(r / a.N);
+    const int64_t n = r - (int64_t)w * a.N;
+    const int O = a.O, W1 = a.Fn - a.O;
+    const int32_t t = a.t[w];
+    const float delta = a.delta[w];
+    const float* __restrict__ cur_t = a.frames + ((size_t)t * (size_t)a.N + (size_t)n) * O;
+    const float* __restrict__ nxt_t = cur_t + (size_t)a.N * O;
+    const int64_t node = a.gid ? (int64_t)a.gid[n] : n;        // the caller's id of engine row n
+    const bool noisy = a.stddev && (!a.noisy || a.noisy[n] != 0);
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int f = 4 * q + j;
+        float x = 0.f;
+        if (f < O) {
+            const float clean = cur_t[f];
+            float cur = clean;
+            if (noisy) cur = __fadd_rn(clean, __fmul_rn(a.stddev[f], randn_keyed(a.seed, ((uint64_t)t * (uint64_t)a.N + (uint64_t)node) * (uint64_t)O + (uint64_t)f)));
+            const float d = __fdiv_rn(__fsub_rn(nxt_t[f], cur), delta);
+            a.target[r * O + f] = a.nrm_o ? __fdiv_rn(__fsub_rn(d, a.nrm_o[O + f]), a.nrm_o[f]) : d;
+            x = cur;
+        } else if (f < a.Fn) {
+            x = a.onehot[n * W1 + (f - O)];
+        }
+        if (f < a.Fn && a.nrm_n) x = x * a.nrm_n[f] + a.nrm_n[a.Fn + f];      // the expression of k_affine_pad
+        v[j] = x;
+    }
+    float* dst = a.nf + r * a.ld + 4 * q;
+    if ((a.ld & 3) == 0) {
+        *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * q + j < a.ld) dst[j] = v[j];
+    }
+}
+
+// The trajectory's edge rows for the B copies: dst row w E + j = [ src[egid[j]][0:Fe] * scale + shift | 0 ] (k_affine_pad's expression;
+// scale null: as they are), j in the engine's edge order, egid[j] the caller's id of engine edge j.  One thread per four columns of an
+// engine edge: the row is formed once and stored B times (L a multiple of four).
+__global__ __launch_bounds__(256) void k_datapoints_edges(const float* __restrict__ src, int Fe, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, const int64_t* __restrict__ egid,
+                                                          float* __restrict__ dst, int L, int64_t E, int B) {
+    const int quads = L >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= E * quads) return;
+    const int64_t j = i / quads;
+    const int q = (int)(i - j * quads);
+    const int64_t sr = egid ? egid[j] : j;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int f = 4 * q + k;
+        float x = 0.f;
+        if (f < Fe) {
+            x = src[sr * Fe + f];
+            if (scale) x = x * scale[f] + shift[f];
+        }
+        v[k] = x;
+    }
+    const f32x4 row = f32x4{v[0], v[1], v[2], v[3]};
+    for (int w = 0; w < B; ++w) *reinterpret_cast<f32x4*>(dst + ((size_t)w * (size_t)E + (size_t)j) * L + 4 * q) = row;
+}
+
+// k_loss over B copies with the mask listed once: block (x, w) takes its 256 mask entries on copy w (row n + w N); the seed is
+// 2 d / (B nmask), the expression of k_loss with that divisor; partial[w nb + x]: the block's sum in double, a fixed slot.
+__global__ __launch_bounds__(256) void k_loss_batch(const float* __restrict__ Y, int L, const float* __restrict__ target, int O,
+                                                    const int32_t* __restrict__ mask, int64_t nmask, int64_t N, int64_t divisor,
+                                                    int32_t index_base, float* __restrict__ G, double* __restrict__ partial) {
+    __shared__ double sh[4];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double e = 0.0;
+    if (i < nmask) {
+        const int64_t n = (int64_t)mask[i] - index_base + (int64_t)blockIdx.y * N;
+        const float scale = 2.0f / (float)divisor;
+        for (int o = 0; o < O; ++o) {
+            const float d = Y[n * L + o] - target[n * O + o];
+            e += (double)d * (double)d;
+            atomicAdd(&G[n * L + o], scale * d);     // a node listed twice contributes twice, like err[mask]
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// One block of 64 threads, B <= 64.  Thread w adds copy w's block partials in block order (the order in which mgn_step_datapoint's host
+// adds them) and divides by nmask: out[w] = loss_w; thread 0 adds the B double means in order: out[B] = their mean.  Each rounded once.
+__global__ __launch_bounds__(64) void k_loss_batch_fold(const double* __restrict__ partial, int nb, int B, int64_t nmask, float* __restrict__ out) {
+    __shared__ double lw[64];
+    const int w = threadIdx.x;
+    if (w < B) {
+        double s = 0.0;
+        for (int b = 0; b < nb; ++b) s += partial[(size_t)w * nb + b];
+        s /= (double)nmask;
+        lw[w] = s;
+        out[w] = (float)s;
+    }
+    __syncthreads();
+    if (w == 0) {
+        double m = 0.0;
+        for (int b = 0; b < B; ++b) m += lw[b];
+        out[B] = (float)(m / (double)B);
+    }
+}
+
 // One block.  Per group (node state columns, edge, output) and column: totals += this call's sums -- the block partials of k_col_stats
 // added in block order from 0, as mgn_feature_stats adds them on the host, or sums formed that way before -- and the group's affine map
 // from the totals: mean, std = sqrt(max(sumsq / c - mean^2, 0)) in double, rounded to float, std = max(std, eps);
@@ -1968,6 +2086,32 @@ hipError_t launch_loss(const float* Y, int L, const float* target, int O, const 
     const int nb = loss_blocks(nmask);
     if (nb == 0) return hipSuccess;
     hipLaunchKernelGGL(k_loss, dim3(nb), dim3(256), 0, s, Y, L, target, O, mask, nmask, divisor, index_base, G, loss_partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_datapoints_assemble(const DatapointBatchArgs& a, hipStream_t s) {
+    const int64_t tot = (int64_t)a.B * a.N * ((a.ld + 3) / 4);
+    if (tot <= 0) return hipSuccess;
+    if (a.B > DATAPOINT_BATCH_MAX || a.ld < a.Fn || a.Fn < a.O || (a.Fn > a.O && !a.onehot) || !a.frames || !a.nf || !a.target) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_datapoints_assemble, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_datapoints_edges(const float* src, int Fe, const float* scale, const float* shift, const int64_t* egid, float* dst, int L,
+                                   int64_t E, int B, hipStream_t s) {
+    const int64_t tot = E * (L / 4);
+    if (tot <= 0 || B <= 0) return hipSuccess;
+    if ((L & 3) != 0 || Fe > L) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_datapoints_edges, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, src, Fe, scale, shift, egid, dst, L, E, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_batch(const float* Y, int L, const float* target, int O, const int32_t* mask, int64_t nmask, int64_t N, int B,
+                             int32_t index_base, float* G, double* partial, float* out, hipStream_t s) {
+    const int nb = loss_blocks(nmask);
+    if (nb == 0 || B < 1 || B > DATAPOINT_BATCH_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_loss_batch, dim3(nb, B), dim3(256), 0, s, Y, L, target, O, mask, nmask, N, (int64_t)B * nmask, index_base, G, partial);
+    hipLaunchKernelGGL(k_loss_batch_fold, dim3(1), dim3(64), 0, s, partial, nb, B, nmask, out);
     return hipGetLastError();
 }
 

@@ -629,6 +629,23 @@ class Engine:
                                               self.param_count, C.byref(loss)))
         return gs, loss.value
 
+    def step_datapoints(self, ts, mask, mask_index_base=0, accumulate=False, out=None):
+        """step! on the block-diagonal FeatureGraph of the B datapoints ts (0-based, each < T-1, repeats and any order allowed;
+        B <= 64) of the resident trajectory, the mask repeated per copy (the reference's Args.batchsize): returns
+        (gs, loss, losses) with loss the mean of the per-datapoint losses [B] and gs its gradient, the mean of the per-datapoint
+        gradients.  accumulate: the online groups take the B datapoints' raw rows into their totals first, one datapoint at a
+        time, and all B are normalised with the resulting maps.  `out` as in step()."""
+        ts = np.ascontiguousarray(ts, dtype=np.int32).ravel()
+        mask = np.ascontiguousarray(mask, dtype=np.int32).ravel()
+        if out is None:
+            out = np.zeros(self.param_count, np.float32)
+        gs, p_gs = _host_or_device(out, (self.param_count,), writable=True)
+        loss = C.c_float()
+        losses = np.zeros(max(ts.size, 1), np.float32)
+        self._chk(self.lib.mgn_step_datapoints(self.h, i32(ts), ts.size, int(bool(accumulate)), i32(mask), mask.size, mask_index_base,
+                                               p_gs, self.param_count, C.byref(loss), f32(losses)))
+        return gs, loss.value, losses[:ts.size]
+
     def datapoint_export(self, t, normalised=True):
         """(nf [N][Fn], ef [E][Fe], target [N][O]) of datapoint t in the caller's order: what step_datapoint consumes
         (normalised) or the raw [cur ; onehot], ef_raw and d = (next - cur) / dt.  Never accumulates."""
