@@ -886,6 +886,10 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_h(const EdgeArg
 // requests loses its sixteen largest, and a block's LDS prologue is 28 KiB instead of 150.
 // ================================================================================================
 constexpr int HS_W = 4;
+// Fragment prefetch depth (hs_layer_ring: D) of the chains that have no register refill.  Edge kernel, layer 2: two steps ahead fit the
+// registers (249 either way) and measured 1.5 % slower on the kernel than one (docs/experiments.md), so every edge chain runs one step
+// ahead.  Node kernel, chains 0 - 4: two steps ahead, no register more, a third fewer LDS wait cycles, the same time.
+constexpr int HS_D_EDGE2 = 1, HS_D_NODE = 2;
 #define MGN_HS_REQ_STEP 0        // step of window gw (0 .. 3) at which window gw + MGN_HS_AHEAD is requested
 #define MGN_HS_AHEAD 4           // 3: two requests in flight (a request 7 steps before its LDS store), 4: three (11 steps).  M-1M: 2.336 (k_edge_ring_h) ->
                                  // 2.340 with the request in the window of its store -> 2.288 / 2.260 / 2.245 / 2.250 at AHEAD 3 (request at step 2 / 0), 4, 5
@@ -905,8 +909,8 @@ template <int LYR>                              // (window -> buffer is window %
 DEVINL RhFrag rs_first(const u32x4* ring) {
     constexpr int b = (Rs::WPL * LYR) % Rs::NB;
     RhFrag f;
+    f.l = ring[b * Rs::BUF + 64];                // lo first: the step's first MFMA takes it
     f.h = ring[b * Rs::BUF];
-    f.l = ring[b * Rs::BUF + 64];
     return f;
 }
 template <int NCH>
@@ -918,7 +922,8 @@ typedef RsSrcT<3> RsSrc;
 DEVINL const u32x4* rs_src(const u32x4* chunk, int w, int e) { return chunk + ((e >> 6) & 1) * 2048 + (w * Rs::W + (e >> 7)) * 64 + (e & 63); }
 // One L x L layer with both pieces from the ring.  Otherwise h2_layer_ring (same split, same products, same order; refill as there).
 // LYR: the chain's place among the NCH chains of a tile (the ring's schedule); WRAP refill: through the descriptor rfb.
-template <int LYR, int FIN, int RFS = 0, int NWV = 8, bool WRAP = false, int NCH = 3>
+// D: how many steps ahead of its MFMAs a fragment pair is read from the ring (a pair in flight is 8 registers).
+template <int LYR, int FIN, int RFS = 0, int NWV = 8, bool WRAP = false, int NCH = 3, int D = 1>
 DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const RsSrcT<NCH>& src, RhFrag& nx, u32x4 (&pend)[Rs::SLOTS][Rs::BUF / (NWV * 64)], int lane,
                           int tid, float sx, float cfin = 0.f, const float* btab = nullptr, const f32x4* rf = nullptr, const N16Buf* rfb = nullptr, int rfs_rt = 0) {
     constexpr int ROT = 2;
@@ -949,6 +954,24 @@ DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const 
         voff[i] = (unsigned)((((e >> 6) & 1) * 2048 + (e >> 7) * 64 + (e & 63)) * 16);
         asm volatile("" : "+v"(voff[i]));
     }
+    // Fragment prefetch, D steps deep: step st's pair lives in q[st % (D + 1)] (the pair of the step in progress and D pairs on their
+    // way).  Step `it` asks for step it + D before it waits for its own pair, lo ahead of hi, so the wait in front of the first MFMA
+    // covers one lo fragment and the wait in front of the second one hi fragment, with everything younger still in flight.
+    // The ring's invariant: during window gw only windows gw and gw + 1 may be read (window gw + 2 goes to LDS at the last step of gw,
+    // the barrier behind it).  Step it + D with D <= W lies in window gw + 1 at most.  The buffer that store overwrites was window
+    // gw - 1's: its last read was issued at step W - 1 - D of gw - 1 or earlier and drained by the ring_barrier that closed gw - 1.
+    // Hand-over: a chain passes on one pair as before (nx = step 0 of chain LYR + 1, read at step 31; window WPL (LYR + 1) was stored
+    // at the last step of window WPL (LYR + 1) - 2), and the next chain asks for its steps 1 .. D itself, all inside that window.
+    // The last chain of a tile reads nothing beyond its step 31: window 0 of the next tile is the tile top's (rs_first<0>, behind the
+    // barrier that followed its store in window NW - 2).  NWV = 4 doubles LPT (requests and stores per thread), not the reads.
+    static_assert(D >= 1 && D <= W, "a step's fragments are read at most one window ahead");
+    RhFrag q[D + 1];
+    q[0] = nx;
+    auto rd = [&](int st) {
+        const int gn = WPL * LYR + st / W;
+        q[st % (D + 1)].l = ring[(gn % NB) * BUF + ((st % W) * 2 + 1) * 64];
+        q[st % (D + 1)].h = ring[(gn % NB) * BUF + ((st % W) * 2) * 64];
+    };
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -957,7 +980,16 @@ DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const 
         for (int t = 0; t < 4; ++t) {
             const int it = 4 * s + t;
             const int gw = WPL * LYR + it / W;                        // global window of this step
-            const u32x4 a1 = nx.h, a2 = nx.l;
+            // (FIN 2: the bias pair of this step's split is asked for ahead of the fragments -- the LDS queue retires in order, so behind them
+            // its wait would drain them too)
+            const f32x2 b = bias(s < 7 ? s + 1 : 0, t);
+            if (it == 0) {
+#pragma unroll
+                for (int d = 1; d < D; ++d) rd(d);
+            }
+            if (it + D < 32) rd(it + D);
+            else if (it == 31 && LYR < NCH - 1) nx = rs_first<LYR + 1>(ring);
+            const u32x4 a1 = q[it % (D + 1)].h, a2 = q[it % (D + 1)].l;
             // window gw + AHEAD is requested at step MGN_HS_REQ_STEP of window gw and goes to LDS at the last step of window gw + AHEAD - 2 (into
             // the buffer that window gw + AHEAD - 3 has just closed on): AHEAD - 1 requests in flight, one register slot each
             if (it % W == MGN_HS_REQ_STEP) {
@@ -976,13 +1008,6 @@ DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const 
                     for (int i = 0; i < 4; ++i) in[s >> 1][8 * (s & 1) + 4 * (t >> 1) + i] = v[i];
                 }
             }
-            if (it + 1 < 32) {
-                const int gn = WPL * LYR + (it + 1) / W;
-                nx.h = ring[(gn % NB) * BUF + (((it + 1) % W) * 2) * 64];
-                nx.l = ring[(gn % NB) * BUF + (((it + 1) % W) * 2 + 1) * 64];
-            } else if (LYR < NCH - 1) {
-                nx = rs_first<LYR + 1>(ring);                          // (that window was written two windows ago)
-            }
             if (it % W == W - 1) {                                     // store window gw + 2 (requested in window gw + 2 - AHEAD): its buffer was last read as window gw - 1
                 const int b2 = (gw + 2) % NB;
 #pragma unroll
@@ -990,13 +1015,17 @@ DEVINL void hs_layer_ring(f32x16 (&acc)[4], f32x16 (&in)[4], u32x4* ring, const 
             }
             if (s < 7) {
                 const int sn = s + 1;
-                const f32x2 b = bias(sn, t);
                 h2_split_pair<FIN>(nh[t], nl[t], in[sn >> 1][8 * (sn & 1) + 2 * t], in[sn >> 1][8 * (sn & 1) + 2 * t + 1], sx, cfin, b[0], b[1]);
             }
             const sp_f16x8 bh = h2_op(ph), bl = h2_op(pl);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a2), bh, acc[t], 0, 0, 0);      // small terms first
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a1), bl, acc[t], 0, 0, 0);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2_wop(a1), bh, acc[t], 0, 0, 0);
+            if (FIN == 2 && s < 7) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            // the step's fragment reads ahead of its first MFMA (left alone, hipcc moves that MFMA above them)
+            if (it == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2 * D, 0);
+            else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (it % W == W - 1) ring_barrier();                       // window closed: every wave has read it, window gw + 2 is in LDS
         }
@@ -1114,7 +1143,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_edge_ring_hs(const EdgeAr
         const H2Scale x2 = h2_scale(h2_rowmax<false>(acc));
         zero_frag<NT>(y);
         CST(2);
-        hs_layer_ring<1, 1, 0, NWV>(y, acc, ring, src, nx, pend, lane, tid, x2.s);   // layer 2 (ReLU folded into the split)
+        hs_layer_ring<1, 1, 0, NWV, false, 3, HS_D_EDGE2>(y, acc, ring, src, nx, pend, lane, tid, x2.s);   // layer 2 (ReLU folded into the split)
         CST(3);
         const float c2 = x2.rs * rsw2;
         const H2Scale x3 = h2_scale(__builtin_fmaf(h2_rowmax<false, true>(y), c2, b2pos));
@@ -1540,7 +1569,7 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
         }
         const H2Scale sv = h2_scale(h2_rowmax<true>(x));
         zero_frag<NT>(acc);
-        hs_layer_ring<0, 0, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, sv.s);                    // layer 1, node part
+        hs_layer_ring<0, 0, 0, NWV, false, NCH, HS_D_NODE>(acc, x, ring, src, nx, pend, lane, tid, sv.s);         // layer 1, node part
         {
             const bool valid_row = n < a.n;                          // (LOAD_AGGREGATE reads `valid`, `nn`, `tile`: rows, not whether the tile stores)
             const bool valid = valid_row;
@@ -1549,14 +1578,14 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
         h2_finish_frag<NT>(acc, sv.rs * rswv, tb + T_B1 * L, h);                                                  // true units, b1 in
         const H2Scale sa = h2_scale(h2_rowmax<true>(x));
         h2_scale_frag<NT>(acc, sa.s * swa);                                                                       // the aggregate chain's units
-        hs_layer_ring<1, 0, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, sa.s);                    // layer 1, aggregate part
+        hs_layer_ring<1, 0, 0, NWV, false, NCH, HS_D_NODE>(acc, x, ring, src, nx, pend, lane, tid, sa.s);         // layer 1, aggregate part
         const H2Scale s2 = h2_scale(h2_rowmax<false, true>(acc));
         zero_frag<NT>(x);
-        hs_layer_ring<2, 1, 0, NWV, false, NCH>(x, acc, ring, src, nx, pend, lane, tid, s2.s);                    // layer 2
+        hs_layer_ring<2, 1, 0, NWV, false, NCH, HS_D_NODE>(x, acc, ring, src, nx, pend, lane, tid, s2.s);         // layer 2
         const float c2 = s2.rs * rsw2 * (sa.rs * rswa);
         const H2Scale s3 = h2_scale(__builtin_fmaf(h2_rowmax<false, true>(x), c2, b2pos));
         zero_frag<NT>(acc);
-        hs_layer_ring<3, 2, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, s3.s, c2, tb + T_B2 * L + 4 * h);   // layer 3
+        hs_layer_ring<3, 2, 0, NWV, false, NCH, HS_D_NODE>(acc, x, ring, src, nx, pend, lane, tid, s3.s, c2, tb + T_B2 * L + 4 * h);   // layer 3
         PHASE_FENCE();
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
         h2_finish_frag<NT>(acc, s3.rs * rsw3, tb + T_B3 * L, h);
@@ -1572,7 +1601,7 @@ __global__ __launch_bounds__(512, 2) void k_node_ring_hs(const NodeArgs a) {
         __builtin_amdgcn_s_setprio(0);
         const H2Scale sp = h2_scale(h2_rowmax<true>(x));
         zero_frag<NT>(acc);
-        hs_layer_ring<4, 0, 0, NWV, false, NCH>(acc, x, ring, src, nx, pend, lane, tid, sp.s);                    // P = v W1s
+        hs_layer_ring<4, 0, 0, NWV, false, NCH, HS_D_NODE>(acc, x, ring, src, nx, pend, lane, tid, sp.s);         // P = v W1s
         __builtin_amdgcn_s_setprio(MGN_NODE_MPRIO);
         h2_scale_frag<NT>(acc, sp.rs * rswp);
         if (valid) store_frag<NT>(prow_ptr(a.P, nn, L, h), STRIDE_PROW, acc);
