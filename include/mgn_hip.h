@@ -110,10 +110,55 @@ int mgn_synchronize(mgn_handle* h);
  * mgn_set_params copies the vector (0.1 ms for the 15-step model) and is meant to be called whenever the caller's
  * parameters MAY have changed -- the reference's loop updates them before every step! (src/MeshGraphNets.jl:375-377):
  * values equal to the ones held invalidate nothing; new ones are turned into the kernels' layouts on the device by the
- * next call that computes with them (1.5 ms for the inference kernels, 0.4 ms inside mgn_step).               */
+ * next call that computes with them (1.5 ms for the inference kernels, 0.4 ms inside mgn_step).
+ * The handle keeps two copies of the vector, one on the host and one resident on the device, and knows which is
+ * authoritative: after mgn_set_params the host copy (the device copy follows at the next pack), after
+ * mgn_set_params_dev / mgn_adam_update the device copy (mgn_get_params, the inference layouts and the debug checks
+ * refresh the host copy first: one copy and one synchronisation, only when it is stale).  The "same values again"
+ * shortcut of mgn_set_params is taken only while the host copy is current.                                     */
 size_t mgn_param_count(const mgn_config* cfg);
 int mgn_set_params(mgn_handle* h, const float* packed, size_t n);
 int mgn_get_params(mgn_handle* h, float* packed, size_t n);
+
+/* ---- parameters that stay on the device; Optimisers.Adam there (reference src/MeshGraphNets.jl:288,375-377) ----
+ * mgn_step / mgn_step_datapoint(s) leave the gradient in device memory; these calls are the way back, so that one
+ * iteration of the reference's loop -- gs = step!(...); opt_state, ps = Optimisers.update(opt_state, ps, gs) -- is two
+ * calls with nothing of parameter size crossing PCIe.  The loop stays the caller's.
+ *
+ * mgn_set_params_dev: packed [n = mgn_param_count] (host or device pointer) is copied into the resident vector with
+ * hipMemcpyDefault on the handle's stream.  It always counts as a change: nothing is compared, and it invalidates
+ * exactly what mgn_set_params does (training layouts, inference layouts, captured inference graphs, the static RHS
+ * cache).  With a device source there is no host work and no synchronisation (a captured inference graph, where one
+ * exists, is waited for before it is destroyed); a host source has left the caller's memory on return.  The next
+ * training call re-packs its weights with a memset and the pack launches alone: the chunk list and the description of
+ * the bias / LayerNorm tables depend on the configuration only and stay on the device.
+ * mgn_get_params_dev: the parameters as they stand into packed (host or device pointer); blocks for a host one.
+ *
+ * mgn_adam_init (Optimisers.setup(Optimisers.Adam(eta, (beta1, beta2), epsilon), ps)): mt = vt = 0, beta_t = (beta1,
+ * beta2); calling it again resets the state.  mgn_set_params* do not touch it, a new graph keeps it, mgn_destroy
+ * frees it.
+ * mgn_adam_update (Optimisers.update): one launch over the resident vector, per element in fp32 with every
+ * operation rounded once and nothing contracted:
+ *     m <- b1 m + (1 - b1) g      v <- b2 v + (1 - b2) (g g)      p <- p - ((m / c1) / (sqrt(v / c2) + eps)) eta
+ * with c_i = (float)(1 - beta_t[i]) formed from the double beta_t, then beta_t[i] *= beta_i in double -- the order of
+ * operations of Optimisers.Adam (and of checkpoint.Adam.update, its Python twin).  grads [n_grads = mgn_param_count]
+ * host or device; a device gradient adds no copy and no synchronisation.  Invalidates as mgn_set_params_dev does.
+ * g g that overflows or is subnormal is not specified.
+ * mgn_adam_state, the checkpoint hook: write = 0 copies mt, vt ([mgn_param_count] each, host or device) and beta_t
+ * out, write = 1 in (the descriptor of mgn_adam_init stays); blocks where a pointer is host memory.
+ *
+ * Any dtype, any ln_mode / ln_dims; rank handles of a partitioned mesh take all five calls (every rank holds the whole
+ * vector and mgn_step hands every rank the same gradient bits, so the ranks stay in step).  Refusals, all before any
+ * launch, the handle stays usable.  MGN_E_ARG: NULL pointers, n != mgn_param_count, write other than 0 / 1, a
+ * descriptor that is not finite or outside eta > 0, 0 <= beta < 1, epsilon > 0.  MGN_E_HIP: a host-only handle.
+ * MGN_E_STATE: mgn_adam_update / mgn_adam_state before mgn_adam_init, mgn_adam_update / mgn_get_params_dev before
+ * any parameters were set.                                                                                      */
+int mgn_set_params_dev(mgn_handle* h, const float* packed, size_t n);
+int mgn_get_params_dev(mgn_handle* h, float* packed, size_t n);
+typedef struct mgn_adam_desc { float eta, beta1, beta2, epsilon; } mgn_adam_desc;
+int mgn_adam_init(mgn_handle* h, const mgn_adam_desc* a);
+int mgn_adam_update(mgn_handle* h, const float* grads, size_t n_grads);
+int mgn_adam_state(mgn_handle* h, int32_t write, float* mt, float* vt, double beta_t[2]);
 
 /* ---- normalisers: mgn.n_norm / e_norm / o_norm frozen to per-feature affine maps --------------
  * forward:  y = x*scale + shift  (covers NormaliserOfflineMinMax, OfflineMeanStd and a frozen

@@ -32,6 +32,7 @@ export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms
        native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
 export rollout_eval, native_validation_step
 export train_trajectory!, step_datapoint!, step_datapoints!, online_norms!, norm_state, norm_state!, datapoint_export
+export adam_init!, adam_update!, adam_state, adam_state!, set_params_dev!, get_params_dev!, resident_params!
 export comm_unique_id, comm_init!, comm_init_file!, comm_barrier, processor_steps_dev!
 
 const LIB = get(ENV, "MGN_HIP_LIB", joinpath(@__DIR__, "..", "meshgraphnets.jl_amd", "lib", "libmgn_hip.so"))
@@ -147,6 +148,7 @@ mutable struct GraphNetwork
     n_norm
     o_norm
     graph_key::Tuple{Int, Int, UInt, UInt}     # (E, N, hash(senders), hash(receivers)) of the graph the engine holds
+    resident::Bool                             # the engine's device copy of the parameters is the authoritative one (adam_init!): `ps` is not handed over before a call
 end
 
 # `rank` / `nranks`: this process's partition of an edge-cut mesh (one process per GPU; see comm_init!).  The reference
@@ -160,7 +162,7 @@ function GraphNetwork(quantities, dims, e_norm, n_norm, o_norm, outputs, mps, la
     h = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:mgn_create, LIB), Cint, (Ref{MgnConfig}, Ref{Ptr{Cvoid}}), cfg, h)
     rc == 0 || error(unsafe_string(ccall((:mgn_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
-    mgn = GraphNetwork(h[], cfg, identity, ps, NamedTuple(), e_norm, n_norm, o_norm, (-1, -1, UInt(0), UInt(0)))
+    mgn = GraphNetwork(h[], cfg, identity, ps, NamedTuple(), e_norm, n_norm, o_norm, (-1, -1, UInt(0), UInt(0)), false)
     mgn.model = (graph, ps_, st) -> (forward(mgn, graph, ps_), st)      # mgn.model(graph, ps, st) -> (output, st)
     finalizer(m -> ccall((:mgn_destroy, LIB), Cvoid, (Ptr{Cvoid},), m.handle), mgn)
     return mgn
@@ -416,6 +418,7 @@ sync_graph!(mgn::GraphNetwork, graph, N) =
 # whether it changed.  mgn_set_params compares with what it holds and returns at once when nothing did (0.3 ms for 9 MB); when something
 # did it only stores the vector (0.1 ms) -- the kernels' weight layouts are written on the device by the call that needs them.
 function sync_params!(mgn::GraphNetwork, packed::Vector{Float32})
+    mgn.resident && return                     # (adam_init!: the parameters live on the device; resident_params! brings `ps` up to date)
     check(mgn.handle, ccall((:mgn_set_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), mgn.handle, packed, length(packed)))
     return
 end
@@ -570,6 +573,71 @@ function step_datapoints!(mgn::GraphNetwork, datapoints::AbstractVector{<:Intege
             (Ptr{Cvoid}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int64, Int32, Ptr{Float32}, Csize_t, Ref{Float32}, Ptr{Float32}),
             mgn.handle, dp, length(dp), accumulate ? 1 : 0, mk, length(mk), 1, gs, length(gs), loss, losses))
     return (gs,), loss[], losses[1:length(dp)]
+end
+
+# ---- parameters that stay on the device, and Optimisers.Adam there (opt-in) ---------------------------------------------------------
+mutable struct MgnAdamDesc   # mirrors `mgn_adam_desc` (include/mgn_hip.h), field for field
+    eta::Float32
+    beta1::Float32
+    beta2::Float32
+    epsilon::Float32
+end
+
+"New parameters from `packed`, a host `Vector{Float32}` or a device array's pointer (no host work, no synchronisation for the latter)."
+function set_params_dev!(mgn::GraphNetwork, packed::Union{Vector{Float32}, Ptr{Float32}}, n::Integer = length(mgn.ps))
+    GC.@preserve packed check(mgn.handle,
+        ccall((:mgn_set_params_dev, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), mgn.handle, packed, n))
+    return mgn
+end
+
+"The parameters as they stand on the device into `packed` (a host vector or a device array's pointer)."
+function get_params_dev!(mgn::GraphNetwork, packed::Union{Vector{Float32}, Ptr{Float32}}, n::Integer = length(mgn.ps))
+    GC.@preserve packed check(mgn.handle,
+        ccall((:mgn_get_params_dev, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), mgn.handle, packed, n))
+    return packed
+end
+
+"`mgn.ps` brought up to date with the device (before `save!`, or to leave the resident mode by hand)."
+resident_params!(mgn::GraphNetwork) = (get_params_dev!(mgn, mgn.ps::Vector{Float32}); mgn.ps)
+
+"""
+`Optimisers.setup(Optimisers.Adam(eta, beta, epsilon), mgn.ps)` on the device, opt-in: the parameters `mgn.ps` go to the engine once and
+live there from now on (`mgn.ps` is no longer handed over before a call; `resident_params!` reads them back), so that the loop of
+src/MeshGraphNets.jl:364-378 becomes `gs, loss = step_datapoint!(mgn, t, mask); adam_update!(mgn, gs)`: no parameters cross PCIe and
+no layouts are described on the host per iteration (the gradient still does while `step_datapoint!` returns a host vector; a caller
+that holds a device array hands `adam_update!` its pointer).
+"""
+function adam_init!(mgn::GraphNetwork; eta::Real = 1.0f-3, beta = (0.9f0, 0.999f0), epsilon::Real = 1.0f-8)
+    set_params_dev!(mgn, mgn.ps::Vector{Float32})
+    mgn.resident = true
+    d = MgnAdamDesc(Float32(eta), Float32(beta[1]), Float32(beta[2]), Float32(epsilon))
+    # (@ccall: tests/test_params_dev_host.py looks for this call)
+    rc = @ccall LIB.mgn_adam_init(mgn.handle::Ptr{Cvoid}, d::Ref{MgnAdamDesc})::Cint
+    check(mgn.handle, rc)
+    return mgn
+end
+
+"`Optimisers.update` on the device: `gs` is what `step!` / `step_datapoint!` returned (`(gs,)` or the vector), or a device array's pointer."
+function adam_update!(mgn::GraphNetwork, gs)
+    g = gs isa Tuple ? gs[1] : gs
+    GC.@preserve g check(mgn.handle,
+        ccall((:mgn_adam_update, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), mgn.handle, g, length(mgn.ps)))
+    return mgn
+end
+
+"(mt, vt, beta_t) of the device Adam: Float32 moments and the Float64 powers of beta, as `Optimisers` keeps them per leaf."
+function adam_state(mgn::GraphNetwork)
+    n = length(mgn.ps)
+    mt = Vector{Float32}(undef, n); vt = Vector{Float32}(undef, n); bt = zeros(Float64, 2)
+    GC.@preserve mt vt bt check(mgn.handle,
+        ccall((:mgn_adam_state, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}), mgn.handle, 0, mt, vt, bt))
+    return mt, vt, bt
+end
+
+function adam_state!(mgn::GraphNetwork, mt::Vector{Float32}, vt::Vector{Float32}, beta_t::Vector{Float64})
+    GC.@preserve mt vt beta_t check(mgn.handle,
+        ccall((:mgn_adam_state, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}), mgn.handle, 1, mt, vt, beta_t))
+    return mgn
 end
 
 function online_norms!(mgn::GraphNetwork; node::Bool = true, edge::Bool = true, out::Bool = true, max_acc::Real = 1e6,

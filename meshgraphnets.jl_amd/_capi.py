@@ -54,6 +54,10 @@ class MgnRolloutEvalDesc(C.Structure):
                 ("sel", C.POINTER(C.c_int32)), ("n_sel", C.c_int64), ("sel_index_base", C.c_int32), ("val_loss", C.c_double)]
 
 
+class MgnAdamDesc(C.Structure):
+    _fields_ = [("eta", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float)]
+
+
 ABI_VERSION = 4      # MGN_ABI_VERSION of include/mgn_hip.h these mirrors were written against (tests/test_julia_shim.py compares)
 
 _f32p = C.POINTER(C.c_float)
@@ -73,6 +77,11 @@ PROTOTYPES = {
     "mgn_param_count": (C.c_size_t, [C.POINTER(MgnConfig)]),
     "mgn_set_params": (C.c_int, [_H, _f32p, C.c_size_t]),
     "mgn_get_params": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_set_params_dev": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_get_params_dev": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_adam_init": (C.c_int, [_H, C.POINTER(MgnAdamDesc)]),
+    "mgn_adam_update": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_adam_state": (C.c_int, [_H, C.c_int32, _f32p, _f32p, _f64p]),
     "mgn_set_norms": (C.c_int, [_H, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "mgn_set_graph": (C.c_int, [_H, C.c_int32, C.c_int64, _i32p, _i32p, C.c_int32, _f32p, C.c_int32]),
     "mgn_partition_nodes": (C.c_int, [C.c_int32, _f32p, C.c_int32, C.c_int32, _i32p]),

@@ -97,11 +97,21 @@ struct mgn_engine {
 
     // parameters
     bool have_params = false;
-    DevBuf d_params, d_wjobs;   // the parameter vector and the chunk list on the device: what k_pack_weights builds the layouts from
+    DevBuf d_params, d_wjobs;   // the RESIDENT parameter vector (what k_pack_weights and k_pack_train build every layout from, what mgn_adam_update rewrites) and the inference chunk list on the device
     std::vector<mgn::WPackJob> wjobs;   // (the list, kept for mgn_debug_pack_check)
     bool packed_ok = false;     // the kernels' weight layouts (wfrag, wsp, wbf) are those of `params`: mgn_set_params only stores the vector,
                                 // the first compute call that reads them packs (a training loop -- set_params, step!, ... -- never does)
-    std::vector<float> params;  // packed, host
+    std::vector<float> params;  // packed, host: always param_count long once parameters were set; its VALUES only through host_params()
+    // Which copy of the parameter vector is authoritative.  mgn_set_params fills the host copy (d_params follows at the next pack:
+    // params_dev_ok says whether it has); mgn_set_params_dev and mgn_adam_update write d_params and leave the host copy stale
+    // (params_host_stale), which host_params() mends with one copy and one synchronisation -- as sync_norms_host does for the norms.
+    bool params_dev_ok = false, params_host_stale = false;
+    // Optimisers.Adam on d_params (mgn_adam_*): moments [param_count] each, beta_t = (beta1^t, beta2^t) in double as Optimisers keeps
+    // it, the gradient's staging buffer for a caller whose gradient is host memory.  Independent of the parameters and of the graph.
+    bool adam_ready = false;
+    mgn_adam_desc adam{};
+    double adam_beta_t[2] = {0.0, 0.0};
+    DevBuf adam_m, adam_v, adam_g;
     MlpOff enc_node, dec;
     std::vector<MlpOff> pn;
     // the kernels' weight layouts: wfrag (fp32: all chunks + tables + small tensors, fragment order), wsp (16-bit pieces of the split
@@ -286,6 +296,17 @@ int upload_inputs(mgn_engine* h, const float* a, int wa, const float* b, int wb,
 bool elat_src_ok(mgn_engine* h);
 void invalidate_static(mgn_engine* h);
 int sync_norms_host(mgn_engine* h);    // norms_host <- norms where the device rewrote them (a copy of 2 (Fn + Fe + O) floats, blocking); else nothing
+// The parameter vector's two copies (mgn_engine::params_dev_ok / params_host_stale).  host_params: the host copy, refreshed from the
+// device first where that one is newer (one copy, blocking) -- every host reader of h->params' values goes through it.  dev_params: the
+// resident device copy, uploaded from the host first where that one is newer (blocking only then: the upload reads pageable memory).
+// set_params_resident: new values from src (host or device) into the resident copy on the handle's stream, with everything
+// mgn_set_params invalidates; no comparison, no host work and, for a device source outside of captured inference graphs, no
+// synchronisation.  params_changed_on_device: that invalidation alone (mgn_adam_update rewrote the resident copy in place).
+int host_params(mgn_engine* h, const float** p);
+int dev_params(mgn_engine* h, const float** p);
+int set_params_resident(mgn_engine* h, const float* src, size_t n, const char* who);
+int params_changed_on_device(mgn_engine* h);
+bool is_device_pointer(const void* p);   // device (or managed) memory, as hipPointerGetAttributes sees it; plain host memory: false
 size_t tile_floats(int64_t ntiles, int L);
 int alloc_latents(mgn_engine* h);
 int rebuild_graph(mgn_engine* h, int32_t N, const EdgeList* sets, const float* mesh_pos, int32_t pos_dim, bool keep_owner, const char* who,

@@ -690,8 +690,11 @@ int mgn_set_params(mgn_handle* h, const float* packed, size_t n) try {
     if (n != want) return fail(h, MGN_E_ARG, "mgn_set_params: got %zu floats, model needs %zu", n, want);
     // the same values again (a caller that cannot tell whether its parameters changed calls this before every forward: 0.3 ms for the
     // comparison of 9 MB): nothing is invalidated, captured graphs and packed layouts stay
-    if (h->have_params && h->params.size() == n && memcmp(h->params.data(), packed, n * sizeof(float)) == 0) return MGN_OK;
+    // (only while the host copy is the authoritative one: after a device-side change it holds older values)
+    if (h->have_params && !h->params_host_stale && h->params.size() == n && memcmp(h->params.data(), packed, n * sizeof(float)) == 0) return MGN_OK;
     h->params.assign(packed, packed + n);
+    h->params_host_stale = false;
+    h->params_dev_ok = false;
     ++h->params_gen;
     train_invalidate(h, 1);
     // The kernels' own weight layouts (three fp32 fragment orders, the bf16 pieces of the split path in two, the bf16 copies) take
@@ -702,6 +705,153 @@ int mgn_set_params(mgn_handle* h, const float* packed, size_t n) try {
     invalidate_static(h);
     h->packed_ok = false;
     h->have_params = true;
+    return MGN_OK;
+} MGN_CATCH(h)
+}  // extern "C"
+
+namespace mgn {
+bool is_device_pointer(const void* p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {   // (memory HIP never saw: an error on some runtimes, "unregistered" on others)
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+int host_params(mgn_engine* h, const float** p) {
+    if (h->params_host_stale) {
+        HIPCHK(h, hipMemcpyAsync(h->params.data(), h->d_params.p, h->params.size() * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->params_host_stale = false;
+    }
+    *p = h->params.data();
+    return MGN_OK;
+}
+
+int dev_params(mgn_engine* h, const float** p) {
+    if (!h->params_dev_ok) {
+        HIPCHK(h, h->d_params.ensure(h->params.size() * 4));
+        HIPCHK(h, hipMemcpyAsync(h->d_params.p, h->params.data(), h->params.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));       // (the host vector may be assigned to again as soon as this returns)
+        h->params_dev_ok = true;
+    }
+    *p = h->d_params.as<float>();
+    return MGN_OK;
+}
+
+int params_changed_on_device(mgn_engine* h) {
+    h->params_dev_ok = true;
+    h->params_host_stale = true;
+    h->have_params = true;
+    h->packed_ok = false;
+    ++h->params_gen;
+    train_invalidate(h, 1);
+    // a captured inference graph must have run before it is destroyed; a training loop holds none and is not waited for
+    if (h->graph_exec || h->fwd_exec || h->rhs_exec) HIPCHK(h, hipStreamSynchronize(h->stream));
+    drop_graph(h);
+    invalidate_static(h);
+    return MGN_OK;
+}
+
+int set_params_resident(mgn_engine* h, const float* src, size_t n, const char* who) {
+    const size_t want = layout_all(h);
+    if (n != want) return fail(h, MGN_E_ARG, "%s: got %zu floats, model needs %zu", who, n, want);
+    const bool from_device = is_device_pointer(src);
+    HIPCHK(h, h->d_params.ensure(n * 4));
+    HIPCHK(h, hipMemcpyAsync(h->d_params.p, src, n * 4, hipMemcpyDefault, h->stream));
+    if (!from_device) HIPCHK(h, hipStreamSynchronize(h->stream));   // (pageable memory: it has left the caller's array on return)
+    if (h->params.size() != n) h->params.resize(n);                  // (its length is the model's size everywhere; its values are stale)
+    return params_changed_on_device(h);
+}
+}  // namespace mgn
+
+extern "C" {
+int mgn_set_params_dev(mgn_handle* h, const float* packed, size_t n) try {
+    if (!h || !packed) return fail(h, MGN_E_ARG, "mgn_set_params_dev: null argument");
+    if (n != layout_all(h)) return fail(h, MGN_E_ARG, "mgn_set_params_dev: got %zu floats, model needs %zu", n, layout_all(h));
+    if (int rc = need(h, false, false)) return rc;
+    return set_params_resident(h, packed, n, "mgn_set_params_dev");
+} MGN_CATCH(h)
+
+int mgn_get_params_dev(mgn_handle* h, float* packed, size_t n) try {
+    if (!h || !packed) return fail(h, MGN_E_ARG, "mgn_get_params_dev: null argument");
+    if (n != layout_all(h)) return fail(h, MGN_E_ARG, "mgn_get_params_dev: got %zu floats, model needs %zu", n, layout_all(h));
+    if (int rc = need(h, true, false, false)) return rc;
+    const float* dp = nullptr;
+    if (int rc = dev_params(h, &dp)) return rc;
+    HIPCHK(h, hipMemcpyAsync(packed, dp, n * 4, hipMemcpyDefault, h->stream));
+    if (!is_device_pointer(packed)) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGN_OK;
+} MGN_CATCH(h)
+
+int mgn_adam_init(mgn_handle* h, const mgn_adam_desc* a) try {
+    if (!h || !a) return fail(h, MGN_E_ARG, "mgn_adam_init: null argument");
+    if (!(std::isfinite(a->eta) && std::isfinite(a->beta1) && std::isfinite(a->beta2) && std::isfinite(a->epsilon)) ||
+        !(a->eta > 0.f) || !(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f) || !(a->epsilon > 0.f))
+        return fail(h, MGN_E_ARG, "mgn_adam_init: Adam needs finite eta > 0, 0 <= beta1, beta2 < 1 and epsilon > 0 (got %g, (%g, %g), %g)",
+                    (double)a->eta, (double)a->beta1, (double)a->beta2, (double)a->epsilon);
+    if (int rc = need(h, false, false)) return rc;
+    const size_t bytes = layout_all(h) * 4;
+    HIPCHK(h, h->adam_m.ensure(bytes));
+    HIPCHK(h, h->adam_v.ensure(bytes));
+    HIPCHK(h, hipMemsetAsync(h->adam_m.p, 0, bytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->adam_v.p, 0, bytes, h->stream));
+    h->adam = *a;
+    h->adam_beta_t[0] = (double)a->beta1;
+    h->adam_beta_t[1] = (double)a->beta2;
+    h->adam_ready = true;
+    return MGN_OK;
+} MGN_CATCH(h)
+
+int mgn_adam_update(mgn_handle* h, const float* grads, size_t n_grads) try {
+    if (!h || !grads) return fail(h, MGN_E_ARG, "mgn_adam_update: null argument");
+    if (n_grads != layout_all(h)) return fail(h, MGN_E_ARG, "mgn_adam_update: grads has %zu floats, model has %zu", n_grads, layout_all(h));
+    if (int rc = need(h, false, false)) return rc;
+    if (!h->adam_ready) return fail(h, MGN_E_STATE, "mgn_adam_update: mgn_adam_init has not been called");
+    if (!h->have_params) return fail(h, MGN_E_STATE, "mgn_adam_update: no parameters have been set (mgn_set_params / mgn_set_params_dev)");
+    const float* dp = nullptr;
+    if (int rc = dev_params(h, &dp)) return rc;
+    const float* g = grads;
+    if (!is_device_pointer(grads)) {
+        HIPCHK(h, h->adam_g.ensure(n_grads * 4));
+        HIPCHK(h, hipMemcpyAsync(h->adam_g.p, grads, n_grads * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));       // (pageable memory: it has left the caller's array on return)
+        g = h->adam_g.as<float>();
+    } else if (reinterpret_cast<uintptr_t>(grads) & 15) {   // (the kernel's 16-byte accesses: a view into a larger device array goes through the staging buffer)
+        HIPCHK(h, h->adam_g.ensure(n_grads * 4));
+        HIPCHK(h, hipMemcpyAsync(h->adam_g.p, grads, n_grads * 4, hipMemcpyDeviceToDevice, h->stream));
+        g = h->adam_g.as<float>();
+    }
+    const mgn_adam_desc& a = h->adam;
+    const float c1 = (float)(1.0 - h->adam_beta_t[0]), c2 = (float)(1.0 - h->adam_beta_t[1]);
+    HIPCHK(h, launch_adam(h->d_params.as<float>(), h->adam_m.as<float>(), h->adam_v.as<float>(), g, (int64_t)n_grads, a.eta, a.beta1, a.beta2,
+                          a.epsilon, c1, c2, h->stream));
+    h->adam_beta_t[0] *= (double)a.beta1;
+    h->adam_beta_t[1] *= (double)a.beta2;
+    return params_changed_on_device(h);
+} MGN_CATCH(h)
+
+int mgn_adam_state(mgn_handle* h, int32_t write, float* mt, float* vt, double beta_t[2]) try {
+    if (!h || !mt || !vt || !beta_t) return fail(h, MGN_E_ARG, "mgn_adam_state: null argument");
+    if (write != 0 && write != 1) return fail(h, MGN_E_ARG, "mgn_adam_state: write must be 0 or 1, got %d", write);
+    if (write && !(std::isfinite(beta_t[0]) && std::isfinite(beta_t[1])))
+        return fail(h, MGN_E_ARG, "mgn_adam_state: beta_t is not finite");
+    if (int rc = need(h, false, false)) return rc;
+    if (!h->adam_ready) return fail(h, MGN_E_STATE, "mgn_adam_state: mgn_adam_init has not been called");
+    const size_t bytes = layout_all(h) * 4;
+    if (write) {
+        HIPCHK(h, hipMemcpyAsync(h->adam_m.p, mt, bytes, hipMemcpyDefault, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->adam_v.p, vt, bytes, hipMemcpyDefault, h->stream));
+        h->adam_beta_t[0] = beta_t[0];
+        h->adam_beta_t[1] = beta_t[1];
+    } else {
+        HIPCHK(h, hipMemcpyAsync(mt, h->adam_m.p, bytes, hipMemcpyDefault, h->stream));
+        HIPCHK(h, hipMemcpyAsync(vt, h->adam_v.p, bytes, hipMemcpyDefault, h->stream));
+        beta_t[0] = h->adam_beta_t[0];
+        beta_t[1] = h->adam_beta_t[1];
+    }
+    if (!is_device_pointer(mt) || !is_device_pointer(vt)) HIPCHK(h, hipStreamSynchronize(h->stream));
     return MGN_OK;
 } MGN_CATCH(h)
 }  // extern "C"
@@ -721,7 +871,8 @@ static float fp16_chunk_scale(const float* W, int L) {
 
 int pack_inference_weights(mgn_engine* h) {
     layout_all(h);
-    const float* p = h->params.data();
+    const float* p = nullptr;                         // (the small tables and the fp16 scales are formed on the host: its copy, refreshed)
+    if (int rc = host_params(h, &p)) return rc;
     const mgn_config& c = h->cfg;
     const int L = c.L;
     const size_t CH = (size_t)L * L, TB = (size_t)T_COUNT * L;
@@ -925,13 +1076,13 @@ int pack_inference_weights(mgn_engine* h) {
     invalidate_static(h);
     if (f.size() > seg0) small.push_back({seg0, f.size()});
     HIPCHK(h, h->wfrag.ensure(f.size() * 4));
-    HIPCHK(h, h->d_params.ensure(h->params.size() * 4));
+    const float* dp = nullptr;
+    if (int rc = dev_params(h, &dp)) return rc;
     HIPCHK(h, h->d_wjobs.ensure(jobs.size() * sizeof(WPackJob)));
-    HIPCHK(h, hipMemcpyAsync(h->d_params.p, p, h->params.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_wjobs.p, jobs.data(), jobs.size() * sizeof(WPackJob), hipMemcpyHostToDevice, h->stream));
     for (const auto& sg : small)
         HIPCHK(h, hipMemcpyAsync(h->wfrag.as<float>() + sg.first, f.data() + sg.first, (sg.second - sg.first) * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_pack_weights(L, h->d_wjobs.as<WPackJob>(), (int)jobs.size(), h->d_params.as<float>(), h->wfrag.as<float>(),
+    HIPCHK(h, launch_pack_weights(L, h->d_wjobs.as<WPackJob>(), (int)jobs.size(), dp, h->wfrag.as<float>(),
                                   h->wsp.as<uint16_t>(), h->wbf.as<uint16_t>(), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));       // (f and jobs are locals: their copies must have left the host)
     h->wjobs = std::move(jobs);
@@ -944,7 +1095,9 @@ extern "C" {
 int mgn_get_params(mgn_handle* h, float* packed, size_t n) try {
     if (int rc = need(h, true, false, false)) return rc;
     if (!packed || n != h->params.size()) return fail(h, MGN_E_ARG, "mgn_get_params: size mismatch");
-    memcpy(packed, h->params.data(), n * sizeof(float));
+    const float* p = nullptr;
+    if (int rc = host_params(h, &p)) return rc;
+    memcpy(packed, p, n * sizeof(float));
     return MGN_OK;
 } MGN_CATCH(h)
 
@@ -2414,7 +2567,8 @@ long long mgn_debug_pack_check(mgn_handle* h) try {
     if (int rc = need(h, true, false)) return -rc;
     const int L = h->cfg.L;
     const size_t CH = (size_t)L * L;
-    const float* p = h->params.data();
+    const float* p = nullptr;
+    if (int rc = host_params(h, &p)) return -rc;
     long long bad = 0;
     std::vector<float> hf(3 * CH), df(3 * CH);
     std::vector<uint16_t> hb(3 * 16384), db(3 * 16384);

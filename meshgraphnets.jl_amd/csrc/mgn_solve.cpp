@@ -1123,7 +1123,10 @@ int mgn::companion_engine(mgn_handle* h, int32_t B, const char* who, bool infere
     if (c->stream != h->stream)
         if (mgn_set_stream(c, (void*)h->stream) != MGN_OK) return fail(h, MGN_E_HIP, "%s: companion stream: %s", who, c->err.c_str());
     if (!kid->params_set || kid->params_gen != h->params_gen) {      // parameters only when they changed
-        if (mgn_set_params(c, h->params.data(), h->params.size()) != MGN_OK) return fail(h, MGN_E_STATE, "%s: companion parameters: %s", who, c->err.c_str());
+        // device to device, on the stream both share: whichever door h's parameters came through, its resident copy is the source
+        const float* dp = nullptr;
+        if (int rc = dev_params(h, &dp)) return rc;
+        if (set_params_resident(c, dp, h->params.size(), who) != MGN_OK) return fail(h, MGN_E_STATE, "%s: companion parameters: %s", who, c->err.c_str());
         kid->params_set = true;
         kid->params_gen = h->params_gen;
     }

@@ -59,7 +59,9 @@ struct TrainState {
     bool kept(int k, int mps) const { return k >= mps - keep_steps; }
     int nblk = 1;                // launch units per MLP (2 for hidden_layers 3, 4)
     DevBuf w;                    // training-order weights
-    DevBuf pk_params, pk_tabs, pk_jobs, pk_max;   // what k_pack_train builds them from: the parameter vector, the packed tables, the chunk list
+    DevBuf pk_tabs, pk_jobs, pk_max;   // what k_pack_train builds them from, beside the resident parameter vector (mgn_engine::d_params): the units' table descriptions, the chunk list
+    bool pk_described = false;         // ... which follow from the configuration alone: formed and uploaded once (pack_describe)
+    int pk_njobs = 0;
     // enc-node, enc-edge (per set), per step: edge (per set), node; decoder
     TrainMlp m_en, m_de, m_ee[MAX_EDGE_SETS];
     std::vector<TrainMlp> m_pe[MAX_EDGE_SETS], m_pn;
@@ -182,31 +184,32 @@ void train_free(mgn_engine* h) {
 
 namespace {
 
-int pack_training_weights(mgn_engine* h) {
+// The training layouts from the resident parameter vector.  What they are built FROM -- the ~300 chunk jobs, the description of every
+// launch unit's tables, the offsets in TrainMlp -- depends on the configuration alone, so it is formed once per handle and kept on the
+// device (pack_describe); a re-pack, which a training loop needs after every optimiser update, is the jobmax memset and the pack
+// launches: no host pass over the parameters, no upload of them unless the host copy is the newer one (mgn_set_params: dev_params), no
+// synchronisation.  Both doors for parameters end in the same buffer and the same kernels: the same bits.
+int pack_describe(mgn_engine* h) {
     TrainState& T = *h->train;
     const mgn_config& c = h->cfg;
     const int L = c.L;
     const size_t CH = (size_t)L * L;
-    const float* p = h->params.data();
-    // A training loop re-packs after every optimiser update (the parameters change before every step!).  The host only describes the
-    // ~300 chunk copies and packs the small tables; the parameter vector goes to the device once (9 MB instead of 42 MB of packed
-    // copies) and k_pack_train writes every fragment-order / t-major / transposed / padded chunk there: 26 ms of host packing and
-    // upload -> ~2 ms per update, against a 3.4 ms step on the cylinder mesh.
     size_t fsz = 0;                                   // floats of the packed buffer T.w
     std::vector<PackJob> jobs;
-    std::vector<float> tabs;                          // the tables, compact (T_COUNT * L per block), scattered by the same kernel
-    // rows [r0, r0 + nr) x cols [0, nc) of W (leading dimension ldw), zero-padded to L x L; transposed on request
+    std::vector<PackTab> tabs;                        // one per launch unit
+    // rows [r0, r0 + nr) x cols [0, nc) of the matrix at parameter offset src (leading dimension ldw; src < 0: the identity), zero-padded
+    // to L x L; transposed on request
     // L = 128: every chunk also as two fp16 pieces times a power of two that puts its largest entry into [2^14, 2^15) (split_common.hpp;
     // the streaming kernels of large launches compute on them), at + 2 CH, and 1 / that power at + 3 CH
     const bool pieces = L == 128;
-    auto block = [&](const float* Wm, int ldw, int r0, int nr, int nc, bool transpose) {
+    auto block = [&](long long src, int ldw, int r0, int nr, int nc, bool transpose) {
         const size_t off = fsz;
         fsz += pieces ? 3 * CH + 4 : 2 * CH;          // fragment order, then the t-major copy (cooperative kernels) at + CH
         const float sc = pieces ? 1.f : 0.f;          // (> 0: pieces wanted; their scale is found on the device, k_pack_absmax)
-        jobs.push_back({(long long)off, Wm ? (long long)(Wm - p) : -1LL, ldw, r0, nr, nc, transpose ? 1 : 0, 0, sc});
+        jobs.push_back({(long long)off, src, ldw, r0, nr, nc, transpose ? 1 : 0, 0, sc});
         return off;
     };
-    const size_t ident = block(nullptr, 0, 0, 0, 0, false);   // (its own transpose)
+    const size_t ident = block(-1LL, 0, 0, 0, 0, false);   // (its own transpose)
     auto build = [&](const MlpOff& m, bool need_input_grad) {
         TrainMlp t;
         const int nd = m.nl;                          // Dense layers: hidden_layers + 1
@@ -223,43 +226,39 @@ int pack_training_weights(mgn_engine* h) {
             b.in_rows = (bi == 0 && m.in < L) ? m.in : L;
             b.has_w1t = need_input_grad || bi > 0;    // (a second block always hands its input gradient to the first)
             for (int j = 0; j < b.nin; ++j) {
-                b.W1[j] = block(p + m.W[d0], L, j * L, b.in_rows, L, false);
-                if (b.has_w1t) b.W1T[j] = block(p + m.W[d0], L, j * L, b.in_rows, L, true);
+                b.W1[j] = block((long long)m.W[d0], L, j * L, b.in_rows, L, false);
+                if (b.has_w1t) b.W1T[j] = block((long long)m.W[d0], L, j * L, b.in_rows, L, true);
             }
             b.gW[0] = (long)m.W[d0]; b.gb[0] = (long)m.b[d0];
             if (d1 >= 0) {
-                b.W2 = block(p + m.W[d1], L, 0, L, L, false);
-                b.W2T = block(p + m.W[d1], L, 0, L, L, true);
+                b.W2 = block((long long)m.W[d1], L, 0, L, L, false);
+                b.W2T = block((long long)m.W[d1], L, 0, L, L, true);
                 b.gW[1] = (long)m.W[d1]; b.gb[1] = (long)m.b[d1];
             } else b.W2 = b.W2T = ident;
             b.out_cols = L;
             if (d2 >= 0) {
                 b.out_cols = d2 == nd - 1 ? m.out : L;
-                b.W3 = block(p + m.W[d2], b.out_cols, 0, L, b.out_cols, false);
-                b.W3T = block(p + m.W[d2], b.out_cols, 0, L, b.out_cols, true);
+                b.W3 = block((long long)m.W[d2], b.out_cols, 0, L, b.out_cols, false);
+                b.W3T = block((long long)m.W[d2], b.out_cols, 0, L, b.out_cols, true);
                 b.gW[2] = (long)m.W[d2]; b.gb[2] = (long)m.b[d2];
             } else b.W3 = b.W3T = ident;
             b.ln = last && m.ln;
             // tables: biases (zero behind an identity slot), LayerNorm parameters of the last block
-            const size_t off = fsz, tpos = tabs.size();
+            const size_t off = fsz;
             fsz += (size_t)T_COUNT * L;
-            tabs.resize(tpos + (size_t)T_COUNT * L, 0.f);
-            jobs.push_back({(long long)off, (long long)tpos, 0, 0, 0, 0, 0, 1, 0.f});
-            float* tb_ = tabs.data() + tpos;
-            std::vector<float> bias(L, 0.f);
-            pack_tab(tb_ + (size_t)T_B1 * L, p + m.b[d0], L);
-            if (d1 >= 0) pack_tab(tb_ + (size_t)T_B2 * L, p + m.b[d1], L);
-            if (d2 >= 0) {
-                for (int i = 0; i < b.out_cols; ++i) bias[i] = p[m.b[d2] + i];
-                pack_tab(tb_ + (size_t)T_B3 * L, bias.data(), L);
-            }
+            jobs.push_back({(long long)off, (long long)tabs.size(), 0, 0, 0, 0, 0, 1, 0.f});
+            PackTab tb{{-1, -1, -1, -1, -1}, {0, 0, 0, 0, 0}, 0.f, 0.f};
+            tb.src[T_B1] = (long long)m.b[d0]; tb.cnt[T_B1] = L;
+            if (d1 >= 0) { tb.src[T_B2] = (long long)m.b[d1]; tb.cnt[T_B2] = L; }
+            if (d2 >= 0) { tb.src[T_B3] = (long long)m.b[d2]; tb.cnt[T_B3] = b.out_cols; }
             if (b.ln) {
-                pack_tab(tb_ + (size_t)T_GAMMA * L, p + m.gamma, L);
-                pack_tab(tb_ + (size_t)T_BETA * L, p + m.beta, L);
+                tb.src[T_GAMMA] = (long long)m.gamma; tb.cnt[T_GAMMA] = L;
+                tb.src[T_BETA] = (long long)m.beta; tb.cnt[T_BETA] = L;
                 b.ggamma = (long)m.gamma; b.gbeta = (long)m.beta;
             }
-            tb_[(size_t)T_LN * L] = c.ln_mode == MGN_LN_STD_EPS ? 0.f : 1e-5f;         // (eps_in, eps_out) of the LayerNorm variant
-            tb_[(size_t)T_LN * L + 1] = c.ln_mode == MGN_LN_STD_EPS ? 1e-5f : 0.f;     // (frag.hpp: ln_rstd_at; both are trained)
+            tb.eps_in = c.ln_mode == MGN_LN_STD_EPS ? 0.f : 1e-5f;          // (eps_in, eps_out) of the LayerNorm variant
+            tb.eps_out = c.ln_mode == MGN_LN_STD_EPS ? 1e-5f : 0.f;         // (frag.hpp: ln_rstd_at; both are trained)
+            tabs.push_back(tb);
             b.tabs = off;
         }
         return t;
@@ -276,16 +275,25 @@ int pack_training_weights(mgn_engine* h) {
     T.m_de = build(h->dec, true);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, T.w.ensure(fsz * 4));
-    HIPCHK(h, T.pk_params.ensure(h->params.size() * 4));
-    HIPCHK(h, T.pk_tabs.ensure(tabs.size() * 4));
+    HIPCHK(h, T.pk_tabs.ensure(tabs.size() * sizeof(PackTab)));
     HIPCHK(h, T.pk_jobs.ensure(jobs.size() * sizeof(PackJob)));
     HIPCHK(h, T.pk_max.ensure(jobs.size() * sizeof(unsigned)));
-    HIPCHK(h, hipMemcpyAsync(T.pk_params.p, p, h->params.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.pk_tabs.p, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.pk_jobs.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_pack_train(L, T.pk_jobs.as<PackJob>(), (int)jobs.size(), T.pk_params.as<float>(), T.pk_tabs.as<float>(), T.pk_max.as<unsigned>(), T.w.as<float>(), h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));       // (jobs / tabs are locals: their copies must have left the host)
     HIPCHK(h, T.grads.ensure(h->params.size() * 4));
+    HIPCHK(h, hipMemcpyAsync(T.pk_tabs.p, tabs.data(), tabs.size() * sizeof(PackTab), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.pk_jobs.p, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));       // (jobs / tabs are locals: their copies must have left the host)
+    T.pk_njobs = (int)jobs.size();
+    T.pk_described = true;
+    return MGN_OK;
+}
+
+int pack_training_weights(mgn_engine* h) {
+    TrainState& T = *h->train;
+    if (!T.pk_described)
+        if (int rc = pack_describe(h)) return rc;
+    const float* dp = nullptr;
+    if (int rc = dev_params(h, &dp)) return rc;
+    HIPCHK(h, launch_pack_train(h->cfg.L, T.pk_jobs.as<PackJob>(), T.pk_njobs, dp, T.pk_tabs.as<PackTab>(), T.pk_max.as<unsigned>(), T.w.as<float>(), h->stream));
     T.packed = true;
     return MGN_OK;
 }

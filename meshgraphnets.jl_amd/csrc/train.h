@@ -101,9 +101,18 @@ struct WPackJob { int kind; long long off, src; int ldw, kbase; float scale; };
 hipError_t launch_pack_weights(int L, const WPackJob* jobs, int njobs, const float* params, float* wfrag, uint16_t* wsp, uint16_t* wbf, hipStream_t s);
 // one packed copy of the training weights: kind 0 = an L x L chunk in fragment order + its t-major copy at + L * L, from rows [r0, r0 + nr)
 // x cols [0, nc) of the matrix at params + src (leading dimension ldw; src < 0: the identity), zero-padded, transposed on request;
-// kind 1 = T_COUNT * L table floats copied from tabs + src
+// kind 1 = the T_COUNT * L table floats of one launch unit, built from the parameter vector as tabs[src] describes them
 struct PackJob { long long off, src; int ldw, r0, nr, nc, transpose, kind; float scale; };   // scale > 0 (L = 128): + the chunk's two fp16 pieces at off + 2 L L (32x32x16 fragment order: hi, lo), times the power of two that puts its largest entry into [2^14, 2^15) (taken on the device), and the inverse of that power at off + 3 L L
-hipError_t launch_pack_train(int L, const PackJob* jobs, int njobs, const float* params, const float* tabs, unsigned* jobmax /* [njobs] scratch */, float* out, hipStream_t s);
+// The tables of one launch unit: rows T_B1 .. T_BETA hold the first cnt[t] floats at params + src[t] (src < 0: none) in pack_tab's
+// order, zero behind them (an identity slot's bias, the decoder's O-wide last bias, no LayerNorm); T_BQ stays zero; T_LN holds
+// (eps_in, eps_out).  Like the chunk list it depends on the configuration alone, never on the parameter values.
+struct PackTab { long long src[5]; int cnt[5]; float eps_in, eps_out; };
+hipError_t launch_pack_train(int L, const PackJob* jobs, int njobs, const float* params, const PackTab* tabs, unsigned* jobmax /* [njobs] scratch */, float* out, hipStream_t s);
+// Optimisers.Adam on n floats, every operation rounded once in fp32 (mgn_hip.h: mgn_adam_update): c1, c2 = (float)(1 - beta_t)
+#pragma GCC visibility push(hidden)   // (new host functions stay out of the library's dynamic symbols)
+hipError_t launch_adam(float* p, float* m, float* v, const float* g, int64_t n, float eta, float b1, float b2, float eps, float c1, float c2,
+                       hipStream_t s);
+#pragma GCC visibility pop
 hipError_t launch_wgrad(int L, WgradBatch wb, int64_t rows, hipStream_t s);
 // out[r * cols + c] = sum_b partial[b * block_stride + r * ld + c]   (fixed order: bitwise reproducible), one job per blockIdx.y
 constexpr int REDUCE_MAX_JOBS = 10;   // one launch unit: five weight blocks, three biases, dgamma and dbeta

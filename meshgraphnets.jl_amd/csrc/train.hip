@@ -1880,12 +1880,23 @@ __global__ void k_pack_absmax(const PackJob* __restrict__ jobs, const float* __r
     if (threadIdx.x == 0)
         atomicMax(jobmax + blockIdx.y, __builtin_bit_cast(unsigned, __builtin_fmaxf(__builtin_fmaxf(wm[0], wm[1]), __builtin_fmaxf(wm[2], wm[3]))));
 }
-__global__ void k_pack_train(const PackJob* __restrict__ jobs, const float* __restrict__ params, const float* __restrict__ tabs,
+__global__ void k_pack_train(const PackJob* __restrict__ jobs, const float* __restrict__ params, const PackTab* __restrict__ tabs,
                              const unsigned* __restrict__ jobmax, float* __restrict__ out, int L) {
     const PackJob jb = jobs[blockIdx.y];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (jb.kind == 1) {
-        if (idx < T_COUNT * L) out[jb.off + idx] = tabs[jb.src + idx];
+    static_assert(T_BETA == 4 && T_B1 == 0, "PackTab describes the rows T_B1 .. T_BETA");
+    if (jb.kind == 1) {   // the unit's tables (PackTab): position d of row t holds feature 32 (m >> 2) + 8 (m & 3) + 4 hh + i, d = (2 m + hh) 4 + i (pack_tab)
+        if (idx >= T_COUNT * L) return;
+        const PackTab& tb = tabs[jb.src];
+        const int t = idx / L, d = idx % L;
+        float v = 0.f;
+        if (t <= T_BETA) {
+            const int m = d >> 3, f = 32 * (m >> 2) + 8 * (m & 3) + (d & 7);
+            if (tb.src[t] >= 0 && f < tb.cnt[t]) v = params[tb.src[t] + f];
+        } else if (t == T_LN) {
+            v = d == 0 ? tb.eps_in : (d == 1 ? tb.eps_out : 0.f);
+        }
+        out[jb.off + idx] = v;
         return;
     }
     const int NT = L / 32, J = L / 2;
@@ -1914,13 +1925,70 @@ __global__ void k_pack_train(const PackJob* __restrict__ jobs, const float* __re
         if (idx == 0) out[jb.off + 3LL * L * L] = sc.rs;
     }
 }
-hipError_t launch_pack_train(int L, const PackJob* jobs, int njobs, const float* params, const float* tabs, unsigned* jobmax, float* out,
+hipError_t launch_pack_train(int L, const PackJob* jobs, int njobs, const float* params, const PackTab* tabs, unsigned* jobmax, float* out,
                              hipStream_t s) {
     if (njobs <= 0) return hipSuccess;
     const int n = L * L > T_COUNT * L ? L * L : T_COUNT * L;
     if (hipError_t e = hipMemsetAsync(jobmax, 0, (size_t)njobs * sizeof(unsigned), s)) return e;
     if (L == 128) hipLaunchKernelGGL(k_pack_absmax, dim3((L * L + 255) / 256, njobs), dim3(256), 0, s, jobs, params, jobmax, L);
     hipLaunchKernelGGL(k_pack_train, dim3((n + 255) / 256, njobs), dim3(256), 0, s, jobs, params, tabs, jobmax, out, L);
+    return hipGetLastError();
+}
+
+// Optimisers.Adam over the resident parameter vector (mgn_adam_update).  Memory-bound: four arrays read, three written, so each thread
+// takes 16 bytes of each at a time; the vector's length is no multiple of 4 in general, and the up to three floats behind the last
+// whole quad go one by one.  Every operation is a correctly rounded fp32 one and none is contracted: the result is the bits of a
+// float32 restatement of Optimisers.Adam's apply!.  The products and sums are plain operators under `fp contract(off)`, not
+// __fmul_rn / __fadd_rn: those are inline functions compiled under the default contraction mode, and a product that feeds a sum
+// through them came out as one v_pk_fma_f32 here.  The division is the IEEE sequence (v_div_scale / v_div_fmas / v_div_fixup); the
+// square root is __builtin_sqrtf, which this compiler rounds correctly (v_sqrt_f32 and a residual step) -- HIP's __fsqrt_rn is the
+// NATIVE square root (one ulp): 17 of 16 321 parameters came out one ulp off with it.
+DEVINL void adam_elem(float& p, float& m, float& v, float g, float eta, float b1, float b2, float omb1, float omb2, float eps, float c1, float c2) {
+#pragma clang fp contract(off)
+    const float m1 = b1 * m, m2 = omb1 * g;
+    m = m1 + m2;
+    const float gg = g * g;
+    const float v1 = b2 * v, v2 = omb2 * gg;
+    v = v1 + v2;
+    const float mhat = __fdiv_rn(m, c1);
+    const float den = __builtin_sqrtf(__fdiv_rn(v, c2)) + eps;
+    const float dx = __fdiv_rn(mhat, den) * eta;
+    p = p - dx;
+}
+__global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
+                                              long long n, float eta, float b1, float b2, float eps, float c1, float c2) {
+    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+    const long long nq = n >> 2, stride = (long long)gridDim.x * blockDim.x;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    for (long long q = tid; q < nq; q += stride) {
+        f32x4 pp = p4[q], mm = m4[q], vv = v4[q];
+        const f32x4 gg = g4[q];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float pi = pp[i], mi = mm[i], vi = vv[i];
+            adam_elem(pi, mi, vi, gg[i], eta, b1, b2, omb1, omb2, eps, c1, c2);
+            pp[i] = pi; mm[i] = mi; vv[i] = vi;
+        }
+        p4[q] = pp; m4[q] = mm; v4[q] = vv;
+    }
+    const long long i = 4 * nq + tid;                 // the tail: n - 4 nq <= 3 elements, thread tid of block 0 takes element tid of it
+    if (i < n && tid < 4) adam_elem(p[i], m[i], v[i], g[i], eta, b1, b2, omb1, omb2, eps, c1, c2);
+}
+hipError_t launch_adam(float* p, float* m, float* v, const float* g, int64_t n, float eta, float b1, float b2, float eps, float c1, float c2,
+                       hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    // 16-byte accesses need 16-byte aligned bases: the engine's own buffers are (hipMalloc), a caller's gradient need not be
+    const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+    if (!aligned) return hipErrorInvalidValue;
+    const int64_t nq = n >> 2;
+    int64_t blocks = (nq + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 256 * 8) blocks = 256 * 8;           // 8 blocks per CU, grid-stride above
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, g, (long long)n, eta, b1, b2, eps, c1, c2);
     return hipGetLastError();
 }
 

@@ -108,10 +108,50 @@ class Engine:
         packed = _c32(packed).ravel()
         self._chk(self.lib.mgn_set_params(self.h, f32(packed), packed.size))
 
-    def get_params(self):
-        out = np.empty(self.param_count, np.float32)
-        self._chk(self.lib.mgn_get_params(self.h, f32(out), out.size))
-        return out
+    def get_params(self, out=None):
+        """The parameters as they stand, whichever door they came through.  out: None (a new NumPy array), a writable float32
+        NumPy array or a contiguous fp32 torch tensor, host or device (a device tensor is filled without a host round trip, on
+        the engine's stream: synchronize() before another stream reads it)."""
+        if out is None:
+            out = np.empty(self.param_count, np.float32)
+            self._chk(self.lib.mgn_get_params(self.h, f32(out), out.size))
+            return out
+        keep, p = _host_or_device(out, (self.param_count,), writable=True)
+        self._chk(self.lib.mgn_get_params_dev(self.h, p, self.param_count))
+        return keep
+
+    def set_params_dev(self, packed):
+        """New parameters into the engine's resident device vector: a contiguous fp32 torch tensor on the device (no host work, no
+        synchronisation: the caller's optimiser lives on the GPU) or a host array.  Always counts as a change."""
+        keep, p = _host_or_device(packed, (self.param_count,))
+        self._chk(self.lib.mgn_set_params_dev(self.h, p, self.param_count))
+
+    # -- Optimisers.Adam on the resident parameters ---------------------------------------------------
+    def adam_init(self, eta=1e-3, beta=(0.9, 0.999), epsilon=1e-8):
+        """Optimisers.setup(Optimisers.Adam(eta, beta, epsilon), ps): zero moments, beta_t = beta.  Resets an earlier state."""
+        d = _capi.MgnAdamDesc(float(eta), float(beta[0]), float(beta[1]), float(epsilon))
+        self._chk(self.lib.mgn_adam_init(self.h, C.byref(d)))
+
+    def adam_update(self, grads):
+        """Optimisers.update on the resident parameters, one kernel: grads as step() / step_datapoint() return them, NumPy or a
+        contiguous fp32 torch tensor (with a device tensor nothing crosses PCIe and nothing blocks)."""
+        keep, p = _host_or_device(grads, (self.param_count,))
+        self._chk(self.lib.mgn_adam_update(self.h, p, self.param_count))
+
+    def adam_state(self):
+        """{"mt", "vt", "beta_t"}: the keys and dtypes of checkpoint.Adam's state, so save / write_checkpoint carry it unchanged."""
+        mt, vt = np.empty(self.param_count, np.float32), np.empty(self.param_count, np.float32)
+        bt = np.zeros(2, np.float64)
+        self._chk(self.lib.mgn_adam_state(self.h, 0, f32(mt), f32(vt), bt.ctypes.data_as(C.POINTER(C.c_double))))
+        return {"mt": mt, "vt": vt, "beta_t": bt}
+
+    def set_adam_state(self, d):
+        """Restore a state of adam_state() or of checkpoint.Adam (after adam_init, which gives eta, beta and epsilon)."""
+        mt, vt = _c32(d["mt"]).ravel(), _c32(d["vt"]).ravel()
+        bt = np.ascontiguousarray(d["beta_t"], dtype=np.float64).ravel()
+        if mt.shape != (self.param_count,) or vt.shape != (self.param_count,) or bt.shape != (2,):
+            raise ValueError(f"DimensionMismatch: expected mt, vt of ({self.param_count},) and beta_t of (2,)")
+        self._chk(self.lib.mgn_adam_state(self.h, 1, f32(mt), f32(vt), bt.ctypes.data_as(C.POINTER(C.c_double))))
 
     def set_norms(self, node=None, edge=None, out=None):
         """Each argument: None (identity) or (scale[F], shift[F]) with forward y = x*scale + shift;
