@@ -170,15 +170,16 @@ bool prows_blocked();        // P / Q / CARRY rows are stored in blocks of eight
 hipError_t launch_gather_rows16(const uint16_t* src, const int32_t* idx, uint16_t* dst, int64_t rows, int dst_stride /* elements */, hipStream_t s);
 
 struct LaunchCfg { int blocks; int threads; size_t lds; };
-hipError_t launch_node_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip: node MLP / projection on two fp16 pieces
-hipError_t launch_project_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);
-hipError_t launch_edge_ring_h(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip: the ring kernel on two fp16 pieces, three products
-size_t edge_ring_h_lds();
-int set_ringh_stream(int on);   // debug/tests: the switch edge_ring_h_streamed() reads (MGN_RINGH_STREAM is its initial value); returns the old value
-int edge_ring_h_streamed();     // 1: launch_edge_ring_h runs k_edge_ring_hs (family codes 16 / 17), 0: k_edge_ring_h (13 / 14)
-hipError_t launch_edge_ring(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip
-hipError_t launch_node_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);    // split.hip
-hipError_t launch_project_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s); // split.hip
+// split.hip, one launcher per kernel (each knows its kernel's LDS; kernels.hip chooses kernel, blocks and threads).  Edge rings: three
+// bf16 pieces; two fp16 pieces with resident hi pieces (_h); two fp16 pieces, all streamed (_hs).  256 threads: four-wave blocks, else eight
+hipError_t launch_edge_ring(const EdgeArgs& a, int blocks, int threads, hipStream_t s);
+hipError_t launch_edge_ring_h(const EdgeArgs& a, int blocks, int threads, hipStream_t s);
+hipError_t launch_edge_ring_hs(const EdgeArgs& a, int blocks, int threads, hipStream_t s);
+hipError_t launch_node_split(const NodeArgs& a, int blocks, int threads, hipStream_t s);      // node MLP / projection on three bf16 pieces
+hipError_t launch_project_split(const NodeArgs& a, int blocks, int threads, hipStream_t s);
+hipError_t launch_node_split_h(const NodeArgs& a, int blocks, int threads, hipStream_t s);    // ... on two fp16 pieces
+hipError_t launch_project_split_h(const NodeArgs& a, int blocks, int threads, hipStream_t s);
+hipError_t launch_node_ring_hs(const NodeArgs& a, int blocks, hipStream_t s);                 // node MLP + the next step's P / Q (eight waves)
 
 struct LinComb {            // sum_j c[j] * k[j]
     int n;
@@ -210,35 +211,34 @@ struct EvalFinish {
 hipError_t launch_eval_finish(EvalFinish f, hipStream_t s);
 
 // L in {32,64,128}.  All return hipError_t of the launch.
-bool launch_is_small(int ntiles);
-bool node_split_size(int ntiles);   // the split-path node kernels take launches of this many node tiles (above two per CU)
-bool launch_is_small_edge(int ntiles_e);   // the same rule for edge launches (<= 16 tiles per CU)
-int coop16_enabled();
-int set_c16_edge_tiles(int t);   // edge tiles per CU up to which a handle takes the 16-row kernels (0: 3, or 2 where k_edge_ring_hs is the next family); returns the old value
-bool ring_hs_default();          // fp32 launches above the cooperative range would run k_edge_ring_hs (split path on two fp16 pieces, streamed pieces)
-bool coop16_size(int ntiles_e, int ntiles_n, bool ring_hs = false);   // the launch wrappers' rule for the cooperative node kernels (<= 8 tiles per CU)
-int last_edge_kernel();
-// tests (split.hip): h2_rowmax<abs> and h2_scale of nrows rows of 128 floats, host arrays in and out (one wave per 32 rows)
-hipError_t debug_rowmax(const float* rows, int nrows, int abs, float* amax, float* s, float* rs);
-int last_node_kernel();         // family of the last fp32 edge launch (kernels.hip: launch_edge_step)
-int set_fp32_split(int on);     // debug/tests: 0 = fp32-MFMA kernels, 1 = split path (default); returns the old value
-int fp32_split_enabled();
-int set_split_f16(int on);     // 1 (default): the split path on two fp16 pieces / three products where built (k_edge_ring_h), 0: three bf16 pieces / six products; MGN_SPLIT_F16; returns the old value
-int split_f16_enabled();
-int set_c16_split(int on);      // 16-row cooperative kernels on the split path (where fp32_split is on): bit 0 edge kernel at >= 2 row tiles, bit 1 node kernel (default 3), bit 2 edge kernel at one row tile too; MGN_C16_SPLIT
-int c16_split_enabled();
-int set_c16_row_tiles(int rt);  // debug/tests: 16-edge tiles per block of the small-graph edge kernel (0: chosen by size); returns the old value
-int set_kernel_path(int p);   // debug/tests: 0 auto, 1 resident, 2 streaming, 3 cooperative, 4 GEN (general hidden_layers) kernels; returns the old value
+// The processor step's launches choose their kernel family themselves (kernels.hip: edge_family, node_family, project_family); what a
+// handle has to know of that choice:
+bool launch_is_small(int ntiles);   // a pass over this many node tiles is launch-bound: worth replaying as a captured graph
+// the handle runs its processor steps on the 16-row kernels (EdgeArgs::c16): both kernels of a step and every edge set must agree
+bool coop16_handle(int L, int hidden_layers, bool f32, int nsets, int ntiles_n, const int32_t* ntiles_e /* [nsets] */);
+// launch_node_step with these mode-1 arguments runs the node MLP and the next step's projection in ONE launch; false: the caller
+// launches mode 0 and then launch_project per edge set
+bool node_step_projects(int L, const NodeArgs& a);
 int get_kernel_path();
+hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s);
+hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s);   // mode 0 or 1
+hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);     // mode 2
+int last_edge_kernel();         // family of the last edge / node-MLP launch (kernels.hip: EdgeFamily, NodeFamily)
+int last_node_kernel();
+// debug/tests: process-wide switches behind the mgn_debug_* setters (meaning and environment variable at each switch in kernels.hip);
+// every setter returns the old value
+int set_kernel_path(int p);
+int set_fp32_split(int on);
+int set_split_f16(int on);
+int set_c16_split(int bits);
+int set_c16_row_tiles(int rt);
+int set_c16_edge_tiles(int t);
+int set_ringh_stream(int on);
+int set_node_ring_hs(int on);
 int set_num_cus(int n);        // debug/tests: the CU count every size decision of the inference launches reads, and the one that scales the size rules of the training step (train.hip: train_size_cus) (0: the device's -- training: its literals; a multiple of NUM_XCD up to the device's); returns the old value, -1 if refused
 int num_cus_override();        // what set_num_cus installed (0: no override)
-hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s);
-hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s);
-hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);   // mode-2 work with both chunks LDS-resident
-hipError_t launch_node_project_fused(int L, const NodeArgs& a, hipStream_t s, bool* launched);   // k_node_ring_hs where it applies (else *launched = false)
-hipError_t launch_node_ring_hs(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s);            // split.hip
-int node_ring_hs_enabled();
-int set_node_ring_hs(int on);   // debug/tests: 1 (default) k_node_ring_hs where it applies, 0 k_node_split_h + k_project_split_h (MGN_NODE_RING_HS is its initial value); returns the old value
+// tests (split.hip): h2_rowmax<abs> and h2_scale of nrows rows of 128 floats, host arrays in and out (one wave per 32 rows)
+hipError_t debug_rowmax(const float* rows, int nrows, int abs, float* amax, float* s, float* rs);
 hipError_t launch_enc_node(int L, const EncNodeArgs& a, hipStream_t s);
 hipError_t launch_enc_edge(int L, const EncEdgeArgs& a, hipStream_t s);
 hipError_t launch_decode(int L, const DecArgs& a, hipStream_t s);

@@ -30,6 +30,7 @@
 #include "tile_common.hpp"
 #include "split_common.hpp"
 
+#include <algorithm>
 #include "launch.hpp"
 
 namespace mgn {
@@ -2518,65 +2519,86 @@ static int resident_chunks(int L, int want) {
     return r < want ? r : want;
 }
 
-// Launches with at most one tile per SIMD cannot amortise a per-block LDS weight preload (up to 156 KB copied by
-// 64-128 threads = 10-17 us): such launches use the all-streaming instantiations (weights stay in L2).
-// g_path: 0 auto, 1 force the LDS-resident persistent kernels, 2 force all-streaming, 3 force cooperative
-// (tests exercise every path on small graphs through mgn_debug_kernel_path)
-static Switch g_path{"MGN_KERNEL_PATH", 0};   // experiments
+// ---- the switches: process-wide, initial value from the environment, changed by the mgn_debug_* setter of the same name (the tests
+// reach every kernel through them) ----
+// 0 auto by size, 1 force the LDS-resident persistent kernels, 2 force all-streaming, 3 force cooperative, 4 the GEN (general
+// hidden_layers) kernels, 5 the 16-row kernels at every size
+static Switch g_path{"MGN_KERNEL_PATH", 0};
 int set_kernel_path(int p) { return g_path.set(p); }
-static Switch g_c16_rt{"MGN_C16_RT", 0};   // 0: by size; 1..3: 16-edge tiles per block
-// Large fp32 launches at L = 128, hidden_layers = 2 run on the bf16 matrix cores with every operand split exactly into three bf16
-// pieces (split.hip / split_ws.hip: fp32 storage, fp32 accumulation, error against float64 no worse than the fp32-MFMA kernels').
-// MGN_FP32_SPLIT: 0 = the fp32-MFMA kernels (v_mfma_f32_32x32x2_f32: the fp32 reference path), 1 = default (edge step: the
-// lock-step kernel with the shared LDS weight ring), 2 = the edge step with per-wave register rings (A/B).
+int get_kernel_path() { return g_path; }
+// Large fp32 launches at L = 128, hidden_layers = 2 run on the 16-bit matrix cores with every operand split exactly into pieces
+// (split.hip: fp32 storage, fp32 accumulation, error against float64 no worse than the fp32-MFMA kernels').  On (default) / off:
+// 0 = the fp32-MFMA kernels (v_mfma_f32_32x32x2_f32: the fp32 reference path)
 static Switch g_fp32_split{"MGN_FP32_SPLIT", 1};
 int set_fp32_split(int on) { return g_fp32_split.set(on); }
-int fp32_split_enabled() { return g_fp32_split; }
+// two fp16 pieces and three products instead of three bf16 pieces and six (split.hip); 0: the bf16 pieces
+static Switch g_split_f16{"MGN_SPLIT_F16", 1};
+int set_split_f16(int on) { return g_split_f16.set(on); }
 // 16-row cooperative kernels on the split path: bit 0 the edge kernel (with two or three row tiles per block its chains are
 // matrix-bound on the fp32 pipe: 17.2 -> 14.1 us on the cylinder mesh), bit 1 the node kernel (one row tile per block streams 96 KiB of
 // weight pieces per chunk where the fp32 fragments are 64 and is bound by that stream either way: 11.6 -> 11.3 us), bit 2 the edge
 // kernel at one row tile per block as well.  Cylinder mesh, per processor step: 29.3 us (0), 26.1 (1), 25.8 (3, the default).
 static Switch g_c16_split{"MGN_C16_SPLIT", 3};
 int set_c16_split(int on) { return g_c16_split.set(on); }
-int c16_split_enabled() { return g_c16_split; }
-// two fp16 pieces and three products instead of three bf16 pieces and six (k_edge_ring_h, split.hip); MGN_SPLIT_F16=0: the bf16 pieces
-static Switch g_split_f16{"MGN_SPLIT_F16", 1};
-int set_split_f16(int on) { return g_split_f16.set(on); }
-int split_f16_enabled() { return g_split_f16; }
+static Switch g_c16_rt{"MGN_C16_RT", 0};   // 16-edge tiles per block of the 16-row edge kernel; 0: by size
 int set_c16_row_tiles(int rt) { return g_c16_rt.set(rt); }
-int get_kernel_path() { return g_path; }
-static bool small_launch(int ntiles) { return g_path == 0 ? ntiles <= 4 * num_cus() : g_path >= 2; }
-// cooperative (4 waves per tile) kernels: up to this many tiles per CU for the edge / node kernels (size sweep)
-static Switch g_tail_coop{"MGN_TAIL_COOP", 1};   // 0: whole launch persistent
-static Switch g_coop_edge{"MGN_COOP_EDGE_TILES_PER_CU", 16};
-static Switch g_coop_node{"MGN_COOP_NODE_TILES_PER_CU", 8};
-static Switch g_coop16{"MGN_COOP16", 1};   // 16-row cooperative tiles on small graphs
-int coop16_enabled() { return (g_coop16 && (g_path == 0 || g_path == 5)) ? 1 : 0; }
-// the 16-row tiles pay while the launches are latency-bound: up to this many 32-row tiles per CU (size sweep, docs/experiments.md)
-// (`ring_hs`: the handle's large-mesh edge kernel would be k_edge_ring_hs -- fp32, one edge set, two fp16 pieces -- whose 28 KiB LDS prologue
-// lets it take over a tile per CU earlier: 3 025 nodes 38 -> 35 us per step, 4 096 nodes 42 -> 37)
-static Switch g_c16_edge{"MGN_C16_EDGE_TILES_PER_CU", 0};   // 0: 3, or 2 with ring_hs
+// split path on two fp16 pieces: 1 k_edge_ring_hs (no resident weight piece, e parked in LDS: read once), 0 k_edge_ring_h
+static Switch g_ringh_stream{"MGN_RINGH_STREAM", 1};
+int set_ringh_stream(int on) { return g_ringh_stream.set(on); }
+// 1: node MLP + the next step's projection as one k_node_ring_hs launch where both would run, 0: k_node_split_h + k_project_split_h
+static Switch g_node_ring_hs{"MGN_NODE_RING_HS", 1};
+int set_node_ring_hs(int on) { return g_node_ring_hs.set(on); }
+// 16-row cooperative tiles on small graphs, and the 32-row tiles per CU up to which a handle takes them (tools/size_sweep16.py)
+static Switch g_coop16{"MGN_COOP16", 1};
+static Switch g_c16_edge{"MGN_C16_EDGE_TILES_PER_CU", 0};   // 0: where the ring kernel would take over (Switches::ring_from)
 static Switch g_c16_node{"MGN_C16_NODE_TILES_PER_CU", 1};
-bool coop16_size(int ntiles_e, int ntiles_n, bool ring_hs) {
-    if (g_path == 5) return true;
-    const int lim = g_c16_edge > 0 ? g_c16_edge : (ring_hs ? 2 : 3);
-    return ntiles_e <= lim * num_cus() && ntiles_n <= g_c16_node * num_cus();
+int set_c16_edge_tiles(int t) { return g_c16_edge.set(t); }
+
+// What one launch decision sees: every switch and the CU count read once, so that no decision meets two values of a switch, and the
+// size rules on them.  Sizes are 32-row tiles per CU; every threshold is named here and nowhere else.
+struct Switches {
+    const int path = g_path, cus = num_cus(), c16_split = g_c16_split, c16_rt = g_c16_rt, c16_edge = g_c16_edge, c16_node = g_c16_node;
+    const bool split = g_fp32_split != 0, f16 = g_split_f16 != 0, ringh_stream = g_ringh_stream != 0, node_ring_hs = g_node_ring_hs != 0;
+    const bool coop16 = g_coop16 != 0 && (path == 0 || path == 5);
+    // cooperative (4 waves per tile) kernels: up to this many tiles per CU for the edge / node kernels (size sweep)
+    bool coop_size(int ntiles, bool edge) const {
+        constexpr int COOP_EDGE = 16, COOP_NODE = 8;
+        return path == 0 ? ntiles <= (edge ? COOP_EDGE : COOP_NODE) * cus : (path == 3 || path == 5);
+    }
+    // ... with pinned weight rings (coop_chain_primed<true>) while a launch has at most this many
+    bool coop_fenced(int ntiles) const { constexpr int COOP_FENCE = 4; return ntiles <= COOP_FENCE * cus; }
+    // Launches with at most one tile per SIMD cannot amortise a per-block LDS weight preload (up to 156 KB copied by
+    // 64-128 threads = 10-17 us): such launches use the all-streaming instantiations (weights stay in L2).
+    bool streams(int ntiles) const { constexpr int STREAM = 4; return path == 0 ? ntiles <= STREAM * cus : path >= 2; }
+    // where the split-path node kernels (k_node_split + k_project_split) take the node side from the cooperative tiles: above two tiles per CU
+    // (19.6 k nodes: 50 -> 43 us, 32 k: 66 -> 50, 62 k: 131 -> 98; at 16 k, two tiles per CU, the cooperative kernels are faster: 37 vs 48)
+    bool node_split_size(int ntiles) const { constexpr int NODE_SPLIT_MIN = 2; return split && path == 0 && ntiles > NODE_SPLIT_MIN * cus; }
+    // fp32 launches of one edge set above the cooperative range run k_edge_ring_hs where its pieces are built
+    bool ring_hs() const { return split && f16 && ringh_stream && path == 0; }
+    // Where the ring kernel of the split path is available it takes over from the cooperative tiles above 3 tiles per CU already
+    // (four-wave blocks; 5 k nodes: 50 vs 68 us per step, 10 k: 85 vs 110, 16 k: 110 vs 146; the fp32-MFMA persistent kernels only at 16),
+    // k_edge_ring_hs, whose LDS prologue is 28 KiB instead of 150, above 2 (3 025 nodes 38 -> 35 us per step, 4 096 nodes 42 -> 37).
+    // The 16-row kernels pay while the launches are latency-bound: up to the same size (size sweep, docs/experiments.md).
+    static int ring_from(bool hs) { return hs ? 2 : 3; }
+};
+bool launch_is_small(int ntiles) { return Switches().coop_size(ntiles, false); }
+
+// 16-row cooperative tiles (v_mfma_f32_16x16x4_f32): both kernels of a processor step must agree (the carry rows are per 16-edge
+// tile then), so the choice is made per handle: L = 128, hidden_layers = 2, the node launch within c16_node tiles per CU and EVERY
+// edge set's launch within ring_from (mgn_debug_c16_edge_tiles overrides it).  bf16 storage included: the 16-row kernels then read
+// and write the bf16 arrays and keep fp32 weights and arithmetic.
+bool coop16_handle(int L, int hidden_layers, bool f32, int nsets, int ntiles_n, const int32_t* ntiles_e) {
+    const Switches w;
+    if (!(w.coop16 && L == 128 && hidden_layers == 2 && w.coop_size(ntiles_n, false))) return false;
+    if (w.path == 5) return true;
+    const int lim = w.c16_edge > 0 ? w.c16_edge : Switches::ring_from(f32 && nsets == 1 && w.ring_hs());
+    for (int q = 0; q < nsets; ++q)
+        if (!(w.coop_size(ntiles_e[q], true) && ntiles_e[q] <= lim * w.cus)) return false;
+    return ntiles_n <= w.c16_node * w.cus;
 }
-int set_c16_edge_tiles(int t) { return g_c16_edge.set(t); }   // (tests: 0 = by the handle, n = n tiles per CU)
-bool ring_hs_default() { return g_fp32_split == 1 && g_split_f16 != 0 && g_path == 0 && edge_ring_h_streamed() != 0; }
-static bool coop_size(int ntiles, bool edge) { return g_path == 0 ? ntiles <= (edge ? g_coop_edge : g_coop_node) * num_cus() : (g_path == 3 || g_path == 5); }
-bool launch_is_small(int ntiles) { return coop_size(ntiles, false); }
-// where the split-path node kernels (k_node_split + k_project_split) take the node side from the cooperative tiles: above two tiles per CU
-// (19.6 k nodes: 50 -> 43 us, 32 k: 66 -> 50, 62 k: 131 -> 98; at 16 k, two tiles per CU, the cooperative kernels are faster: 37 vs 48)
-static Switch g_node16_mid{"MGN_NODE16_MID", 1};   // 0: cooperative 32-row node kernel (fp32 pipe) there
-static const int g_node_split_min = env_int("MGN_NODE_SPLIT_MIN_TILES_PER_CU", 2);
-bool node_split_size(int ntiles) { return g_fp32_split != 0 && g_path == 0 && ntiles > g_node_split_min * num_cus(); }
-bool launch_is_small_edge(int ntiles_e) { return coop_size(ntiles_e, true); }
 
-
-static LaunchCfg tile_launch(int L, int ntiles, int nres) {
+static LaunchCfg tile_launch(int L, int ntiles, int nres, int cus = num_cus()) {
     LaunchCfg lc;
-    const int cus = num_cus();
     int wpb = 8;
     if (ntiles <= cus) wpb = 1;
     else if (ntiles <= 2 * cus) wpb = 2;
@@ -2589,149 +2611,155 @@ static LaunchCfg tile_launch(int L, int ntiles, int nres) {
     lc.lds = (size_t)nres * L * L * 4 + (size_t)T_COUNT * L * 4 + 64;  // + spare
     return lc;
 }
+// no resident chunk: tables only in LDS, every weight chunk streamed from L2
+static LaunchCfg stream_launch(int L, int ntiles, int cus) { return tile_launch(L, ntiles, 0, cus); }
+// as few blocks of `per` tiles a round as `rounds` rounds allow, at most one per CU, whole XCD groups
+static int ring_blocks(int ntiles, int per, int cus) {
+    const int blocks = std::min((ntiles + per - 1) / per, cus);
+    return ((blocks + NUM_XCD - 1) / NUM_XCD) * NUM_XCD;
+}
 
 template <typename K, typename A>
 static hipError_t launch_k(K kern, const A& a, const LaunchCfg& lc, hipStream_t s) {
     return launch_kernel(kern, lc.blocks, lc.threads, lc.lds, s, a);
 }
-
-hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s);
-
-// hidden_layers != 2 (GenMlp): the GEN instantiations, every weight chunk streamed from L2, tables only in LDS
-static LaunchCfg gen_launch(int L, int ntiles) {
-    LaunchCfg lc = tile_launch(L, ntiles, 0);
-    lc.lds = (size_t)T_COUNT * L * 4 + 64;
-    return lc;
-}
-#define DISPATCH_GEN(L_, KERN4, KERN2, KERN1, ARGS, NTILES)                          \
-    do {                                                                             \
-        if ((NTILES) <= 0) return hipSuccess;                                        \
-        const LaunchCfg lg = gen_launch(L_, NTILES);                                 \
-        if ((L_) == 128) return launch_k(KERN4, ARGS, lg, s);                        \
-        if ((L_) == 64) return launch_k(KERN2, ARGS, lg, s);                         \
-        if ((L_) == 32) return launch_k(KERN1, ARGS, lg, s);                         \
-        return hipErrorInvalidValue;                                                 \
-    } while (0)
-
-// pinned weight rings (coop_chain_primed<true>) while a launch has at most MGN_COOP_FENCE_TILES_PER_CU (default 4) tiles per CU
-static bool coop_fence(int ntiles) {
-    static const int per_cu = env_int("MGN_COOP_FENCE_TILES_PER_CU", 4);
-    return ntiles <= per_cu * num_cus();
+// the instantiation of a kernel for L = 128 / 64 / 32
+template <typename K4, typename K2, typename K1, typename A>
+static hipError_t launch_by_L(int L, K4 k4, K2 k2, K1 k1, const A& a, const LaunchCfg& lc, hipStream_t s) {
+    if (L == 128) return launch_k(k4, a, lc, s);
+    if (L == 64) return launch_k(k2, a, lc, s);
+    if (L == 32) return launch_k(k1, a, lc, s);
+    return hipErrorInvalidValue;
 }
 static size_t coop_lds() { return (size_t)2 * 16 * 64 * 16 + (size_t)T_COUNT * 128 * 4; }
-static bool coop_ok(int L, int ntiles, const float* const* chunk_t, bool edge = false) {
-    return L == 128 && chunk_t[0] != nullptr && coop_size(ntiles, edge);
+// 16-row kernels: bytes of LDS per exchange buffer of 64 lanes x 16 bytes -- 8 KiB of fp32 rows, 12 KiB of pieces on the split path
+static size_t c16_buf(bool split_path) { return (size_t)(split_path ? 12 : 8) * 64 * 16; }
+
+// k_edge_coop16m<RT, BF, SP> at rt row tiles per block: one to three, the split path in fp32 storage up to six
+template <bool BF, int SP, int RT = (SP != 0 && !BF) ? 6 : 3>
+static hipError_t launch_edge_coop16(int rt, const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s) {
+    if constexpr (RT > 1)
+        if (rt < RT) return launch_edge_coop16<BF, SP, RT - 1>(rt, a, lc, s);
+    return launch_k(k_edge_coop16m<RT, BF, SP>, a, lc, s);
+}
+template <int SP>
+static hipError_t launch_node_coop16(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
+    if (a.bf) return a.AGG2 ? launch_k(k_node_coop16<2, true, SP>, a, lc, s) : launch_k(k_node_coop16<1, true, SP>, a, lc, s);
+    return a.AGG2 ? launch_k(k_node_coop16<2, false, SP>, a, lc, s) : launch_k(k_node_coop16<1, false, SP>, a, lc, s);
+}
+static hipError_t launch_node_coop(const NodeArgs& a, bool fenced, hipStream_t s) {
+    const LaunchCfg c4{a.ntiles, 256, coop_lds()};
+    if (fenced) return a.AGG2 ? launch_k(k_node_coop<true, true>, a, c4, s) : launch_k(k_node_coop<false, true>, a, c4, s);
+    return a.AGG2 ? launch_k(k_node_coop<true, false>, a, c4, s) : launch_k(k_node_coop<false, false>, a, c4, s);
 }
 
-// which kernel family the last fp32 edge launch went to (bench.py labels its roofline with what RAN, not with the global switches):
-// 1 generic hidden_layers, 2 16-row small-graph, 3 cooperative 4-wave tiles, 4 all-streaming, (5, 6: kernels retired in round 5,)
-// 7 k_edge_ring<8>, 8 k_edge_ring<4>, 9 k_edge_step<4,2> (fp32-MFMA persistent), (10, 11: retired,) 12 k_edge_coop16m on the
-// split path, 13 / 14 k_edge_ring_h<8 / 4> (two fp16 pieces: the default of large fp32 launches); bf16 mode: 18 k_edge_bf16_pipe
-// (its small graphs run the 16-row kernels on the bf16 arrays and record their codes)
+// The kernel family of a processor-step launch.  The values are what mgn_debug_last_edge_kernel / mgn_debug_last_node_kernel report:
+// tests and bench.py compare the integers (bench.py labels its roofline with what RAN, not with the switches), and DESIGN.md section 2
+// has the same table.  bf16 mode's small graphs run the 16-row kernels on the bf16 arrays and record their codes.
+enum EdgeFamily {
+    E_INVALID = -1,                   // no kernel takes these arguments
+    E_SMALL_L = 0,                    // L = 64 / 32: k_edge_step<2 / 1, 3>; records nothing
+    E_GEN = 1,                        // general hidden_layers: k_edge_step<.., 0, true>
+    E_COOP16 = 2,                     // k_edge_coop16m, fp32 pipe
+    E_COOP = 3,                       // k_edge_coop (four waves per tile)
+    E_STREAM = 4,                     // k_edge_step<4, 0> (all-streaming)                         (5, 6, 10, 11: kernels retired)
+    E_RING8 = 7, E_RING4 = 8,         // k_edge_ring<8 / 4> (three bf16 pieces)
+    E_STEP = 9,                       // k_edge_step<4, 2> (fp32 MFMA, persistent; a short last round goes to k_edge_coop<false>)
+    E_COOP16_SPLIT = 12,              // k_edge_coop16m on three bf16 pieces
+    E_RING_H8 = 13, E_RING_H4 = 14,   // k_edge_ring_h<8 / 4> (two fp16 pieces; mgn_debug_ringh_stream(0))
+    E_COOP16_H = 15,                  // k_edge_coop16m on two fp16 pieces
+    E_RING_HS8 = 16, E_RING_HS4 = 17, // k_edge_ring_hs<8 / 4> (the default of large fp32 launches)
+    E_BF16_PIPE = 18,                 // k_edge_bf16_pipe (bf16 mode)
+};
+enum NodeFamily {                     // (the projection records nothing; project_family names its kernel by the node kernel it goes with)
+    N_INVALID = -1,
+    N_GEN = 1,                        // general hidden_layers: k_node_step<.., 0, .., true>
+    N_COOP16 = 2,                     // k_node_coop16, fp32 pipe
+    N_COOP = 3,                       // k_node_coop
+    N_SPLIT = 5, N_SPLIT2 = 6,        // k_node_split (one / two edge sets) + k_project_split
+    N_STEP = 7,                       // k_node_step / k_project (fp32 MFMA, persistent or all-streaming)
+    N_COOP16_SPLIT = 8,               // k_node_coop16 on the split path
+    N_COOP16_MID = 9,                 // k_node_coop16 on the split path behind a 32-row edge kernel
+    N_SPLIT_H = 10,                   // k_node_split_h (+ k_project_split_h): partitioned runs, the last step, mgn_debug_node_ring_hs(0)
+    N_RING_HS = 11,                   // k_node_ring_hs (MLP + the next step's P / Q)
+    N_BF16_PIPE = 12,                 // k_node_bf16_pipe (bf16 mode; k_project_bf16_pipe records none)
+};
 // (relaxed atomics, like the switches: every rank thread's launches write the two family records)
-static std::atomic<int> g_last_edge_kernel{0};
-static void set_last(std::atomic<int>& rec, int code) { rec.store(code, std::memory_order_relaxed); }
+static std::atomic<int> g_last_edge_kernel{0}, g_last_node_kernel{0};
 int last_edge_kernel() { return g_last_edge_kernel.load(std::memory_order_relaxed); }
-// the family of the launch that carries a set's edges: a launch over less than half of the set's tiles (the boundary tiles of a partitioned pass,
-// launched AFTER the interior ones) does not speak for the step
-#define SET_LAST_EDGE(A, CODE)                                                            \
-    do {                                                                                  \
-        if (2 * (int64_t)(A).ntiles * TILE >= (A).E) set_last(g_last_edge_kernel, CODE);  \
-    } while (0)
+int last_node_kernel() { return g_last_node_kernel.load(std::memory_order_relaxed); }
+static void record_node(NodeFamily f) { g_last_node_kernel.store(f, std::memory_order_relaxed); }
+// the family of the launch that carries a set's edges: a launch over less than half of the set's tiles (the boundary tiles of a
+// partitioned pass, launched AFTER the interior ones) does not speak for the step
+static void record_edge(EdgeFamily f, int ntiles, int64_t E) {
+    if (f > 0 && 2 * (int64_t)ntiles * TILE >= E) g_last_edge_kernel.store(f, std::memory_order_relaxed);
+}
+
+// *rt16: 16-edge tiles per block of the 16-row kernel -- about one block per CU (mgn_debug_c16_row_tiles pins 1..3)
+static EdgeFamily edge_family(int L, const EdgeArgs& a, const Switches& w, int* rt16) {
+    if (a.gen.use) return a.ElatSrc ? E_INVALID : E_GEN;
+    if (a.c16 && L == 128 && a.chunk_t[0]) {   // small graph: 16-row tiles, 4 waves each (the handle decided for both kernels)
+        const bool sp16 = w.split && (w.c16_split & 1) && a.split16[0];
+        // (four to six row tiles per block exist on the split path only: one round of blocks up to 24.5 k edges instead of a second,
+        // partly filled one behind three tiles per block -- 12.5 k edges: 35.4 -> 2x us per step)
+        const int rt_max = (sp16 && !a.bf && !w.c16_rt) ? 6 : 3;
+        const int rt = std::max(1, std::min(rt_max, w.c16_rt ? w.c16_rt : (2 * a.ntiles + w.cus - 1) / w.cus));
+        *rt16 = rt;
+        if (!(sp16 && (rt >= 2 || (w.c16_split & 4)))) return E_COOP16;
+        return w.f16 && a.split16h[0] && rt <= 4 ? E_COOP16_H : E_COOP16_SPLIT;   // (five and six row tiles spill with two pieces)
+    }
+    if (a.ElatSrc) return E_INVALID;      // only the 16-row kernel reads its e rows from a second array
+    if (L != 128) return L == 64 || L == 32 ? E_SMALL_L : E_INVALID;
+    const bool ring = w.split && w.path == 0 && a.split[0];       // split path (split.hip): fp32 accuracy on the 16-bit matrix cores
+    const bool h = ring && w.f16 && a.splith[0], hs = h && w.ringh_stream;
+    if (!(ring && a.ntiles > Switches::ring_from(hs) * w.cus)) {
+        if (a.chunk_t[0] && w.coop_size(a.ntiles, true)) return E_COOP;
+        if (w.streams(a.ntiles)) return E_STREAM;
+    }
+    if (!ring) return E_STEP;
+    // four-wave blocks (one wave per SIMD) up to 2.5 rounds of eight-wave blocks: 16 k nodes 75 vs 83 us, 25.6 k 115 vs 120,
+    // 40 k 175 vs 160 (docs/experiments.md)
+    bool four = a.ntiles <= 20 * w.cus;
+    // k_edge_ring_hs (28 KiB of LDS prologue per block instead of 150): a round of four-wave blocks takes ~0.62 of a round of eight-wave
+    // blocks for half the tiles, so the shape with the shorter sum of rounds runs -- four waves up to 4 and from 8 to 12 tiles per CU
+    // (M-1M slices of 100 / 128 / 145 / 160 nodes a side: 34 vs 39, 57 vs 55, 59 vs 70, 79 vs 83 us for eight vs four waves)
+    if (hs) four = 0.62 * ((a.ntiles + 4 * w.cus - 1) / (4 * w.cus)) < (double)((a.ntiles + 8 * w.cus - 1) / (8 * w.cus));
+    if (hs) return four ? E_RING_HS4 : E_RING_HS8;
+    if (h) return four ? E_RING_H4 : E_RING_H8;
+    return four ? E_RING4 : E_RING8;
+}
 
 hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    if (a.gen.use && a.ElatSrc) return hipErrorInvalidValue;
-    if (a.gen.use) SET_LAST_EDGE(a, 1);
-    if (a.gen.use) DISPATCH_GEN(L, (k_edge_step<4, 0, true>), (k_edge_step<2, 0, true>), (k_edge_step<1, 0, true>), a, a.ntiles);
-    const int nres = resident_chunks(L, 3);
-    LaunchCfg lc = tile_launch(L, a.ntiles, nres);
-    if (a.c16 && L == 128 && a.chunk_t[0]) {        // small graph: 16-row tiles, 4 waves each (the handle decided for both kernels)
-        // RT 16-edge tiles per block: about one block per CU (MGN_C16_RT = 1..3 pins it)
-        SET_LAST_EDGE(a, 2);
-        const int nht = 2 * a.ntiles;
-        int rt = g_c16_rt ? g_c16_rt : (nht + num_cus() - 1) / num_cus();
-        const bool sp16 = g_fp32_split && (g_c16_split & 1) && a.split16[0];
-        // (four to six row tiles per block exist on the split path only: one round of blocks up to 24.5 k edges instead of a second,
-        // partly filled one behind three tiles per block -- 12.5 k edges: 35.4 -> 2x us per step)
-        const int rt_max = (sp16 && !a.bf && !g_c16_rt) ? 6 : 3;
-        rt = rt < 1 ? 1 : (rt > rt_max ? rt_max : rt);
-        LaunchCfg c16{(nht + rt - 1) / rt, 256, (size_t)rt * 2 * 8 * 64 * 16 + (size_t)rt * 2 * 64 * 4};
-        if (g_fp32_split && (g_c16_split & 1) && a.split16[0] && (rt >= 2 || (g_c16_split & 4))) {   // split path: bf16 matrix cores at fp32 accuracy (pieces exchanged: 12 KiB per tile)
-            c16.lds = (size_t)rt * 2 * 12 * 64 * 16 + (size_t)rt * 2 * 64 * 4;
-            const bool h2 = g_split_f16 && a.split16h[0] && rt <= 4;   // two fp16 pieces, three products (else three bf16 pieces, six; five and six row tiles spill with two)
-            SET_LAST_EDGE(a, h2 ? 15 : 12);
-#define C16E(RT_, BF_) (h2 ? launch_k(k_edge_coop16m<RT_, BF_, 2>, a, c16, s) : launch_k(k_edge_coop16m<RT_, BF_, 1>, a, c16, s))
-            if (a.bf) {
-                if (rt == 3) return C16E(3, true);
-                if (rt == 2) return C16E(2, true);
-                return C16E(1, true);
-            }
-            if (rt == 6) return C16E(6, false);
-            if (rt == 5) return C16E(5, false);
-            if (rt == 4) return C16E(4, false);
-            if (rt == 3) return C16E(3, false);
-            if (rt == 2) return C16E(2, false);
-            return C16E(1, false);
-#undef C16E
-        }
-        if (a.bf) {
-            if (rt == 3) return launch_k(k_edge_coop16m<3, true>, a, c16, s);
-            if (rt == 2) return launch_k(k_edge_coop16m<2, true>, a, c16, s);
-            return launch_k(k_edge_coop16m<1, true>, a, c16, s);
-        }
-        if (rt == 3) return launch_k(k_edge_coop16m<3, false>, a, c16, s);
-        if (rt == 2) return launch_k(k_edge_coop16m<2, false>, a, c16, s);
-        return launch_k(k_edge_coop16m<1, false>, a, c16, s);
+    const Switches w;
+    int rt = 0;
+    const EdgeFamily f = edge_family(L, a, w, &rt);
+    record_edge(f, a.ntiles, a.E);
+    LaunchCfg lc = tile_launch(L, a.ntiles, resident_chunks(L, 3), w.cus);
+    switch (f) {
+    case E_GEN:
+        return launch_by_L(L, k_edge_step<4, 0, true>, k_edge_step<2, 0, true>, k_edge_step<1, 0, true>, a, stream_launch(L, a.ntiles, w.cus), s);
+    case E_COOP16: case E_COOP16_SPLIT: case E_COOP16_H: {
+        const LaunchCfg c16{(2 * a.ntiles + rt - 1) / rt, 256, (size_t)rt * 2 * c16_buf(f != E_COOP16) + (size_t)rt * 2 * 64 * 4};
+        if (f == E_COOP16) return a.bf ? launch_edge_coop16<true, 0>(rt, a, c16, s) : launch_edge_coop16<false, 0>(rt, a, c16, s);
+        if (f == E_COOP16_SPLIT) return a.bf ? launch_edge_coop16<true, 1>(rt, a, c16, s) : launch_edge_coop16<false, 1>(rt, a, c16, s);
+        return a.bf ? launch_edge_coop16<true, 2>(rt, a, c16, s) : launch_edge_coop16<false, 2>(rt, a, c16, s);
     }
-    if (a.ElatSrc) return hipErrorInvalidValue;      // only the 16-row kernel reads its e rows from a second array
-    // where the ring kernel of the split path is available it takes over from the cooperative tiles at 3 tiles per CU already
-    // (four-wave blocks; 5 k nodes: 50 vs 68 us per step, 10 k: 85 vs 110, 16 k: 110 vs 146), the fp32-MFMA persistent kernels only at 16
-    static const int coop_edge_ring_env = env_int("MGN_COOP_EDGE_TILES_PER_CU_RING", 0);
-    const bool ring_ok = L == 128 && g_fp32_split == 1 && a.split[0] && g_path == 0;
-    const int coop_edge_ring = coop_edge_ring_env > 0 ? coop_edge_ring_env : ((ring_ok && g_split_f16 && a.splith[0] && edge_ring_h_streamed()) ? 2 : 3);
-    if (coop_ok(L, a.ntiles, a.chunk_t, true) && !(ring_ok && a.ntiles > coop_edge_ring * num_cus())) {   // small graph: 4 waves per tile
-        SET_LAST_EDGE(a, 3);
-        LaunchCfg c4{a.ntiles, 256, coop_lds()};
-        return coop_fence(a.ntiles) ? launch_k(k_edge_coop<true>, a, c4, s) : launch_k(k_edge_coop<false>, a, c4, s);
+    case E_COOP: {
+        const LaunchCfg c4{a.ntiles, 256, coop_lds()};
+        return w.coop_fenced(a.ntiles) ? launch_k(k_edge_coop<true>, a, c4, s) : launch_k(k_edge_coop<false>, a, c4, s);
     }
-    if (L == 128) {
-        if (small_launch(a.ntiles) && !(ring_ok && a.ntiles > coop_edge_ring * num_cus())) {   // few tiles: the per-block LDS preload would dominate -> stream everything from L2
-            SET_LAST_EDGE(a, 4);
-            lc.lds = (size_t)T_COUNT * L * 4 + 64;
-            return launch_k(k_edge_step<4, 0>, a, lc, s);
-        }
-        if (g_fp32_split && a.split[0] && g_path == 0) {   // split path (split.hip): fp32 accuracy on the bf16 matrix cores
-            LaunchCfg ls = lc;
-            ls.lds = (size_t)3 * 32768 + (size_t)3 * 16384 + (size_t)T_COUNT * L * 4 + 64;
-            static const int ring_waves = env_int("MGN_RING_WAVES", 0);   // 0: by size
-            // four-wave blocks (one wave per SIMD) up to 2.5 rounds of eight-wave blocks: 16 k nodes 75 vs 83 us, 25.6 k 115 vs 120,
-            // 40 k 175 vs 160 (docs/experiments.md)
-            // k_edge_ring_hs (28 KiB of LDS prologue per block instead of 150): a round of four-wave blocks takes ~0.62 of a round of eight-wave
-            // blocks for half the tiles, so the shape with the shorter sum of rounds runs -- four waves up to 4 and from 8 to 12 tiles per CU
-            // (M-1M slices of 100 / 128 / 145 / 160 nodes a side: 34 vs 39, 57 vs 55, 59 vs 70, 79 vs 83 us for eight vs four waves)
-            bool four = a.ntiles <= 20 * num_cus();
-            if (g_split_f16 && a.splith[0] && edge_ring_h_streamed()) {
-                const int r4 = (a.ntiles + 4 * num_cus() - 1) / (4 * num_cus()), r8 = (a.ntiles + 8 * num_cus() - 1) / (8 * num_cus());
-                four = 0.62 * r4 < (double)r8;
-            }
-            if (ring_waves == 4 || (ring_waves == 0 && four)) {
-                ls.threads = 256;
-                // as few blocks as the number of rounds allows (every block pays the 150 KiB LDS prologue)
-                const int rounds = (a.ntiles + 4 * num_cus() - 1) / (4 * num_cus());
-                int blocks = (a.ntiles + 4 * rounds - 1) / (4 * rounds);
-                if (blocks > num_cus()) blocks = num_cus();
-                ls.blocks = ((blocks + NUM_XCD - 1) / NUM_XCD) * NUM_XCD;
-            }
-            if (g_split_f16 && a.splith[0]) {
-                ls.lds = edge_ring_h_lds();
-                SET_LAST_EDGE(a, edge_ring_h_streamed() ? (ls.threads == 256 ? 17 : 16) : (ls.threads == 256 ? 14 : 13));
-                return launch_edge_ring_h(a, ls, s);
-            }
-            SET_LAST_EDGE(a, ls.threads == 256 ? 8 : 7);
-            return launch_edge_ring(a, ls, s);
-        }
-        SET_LAST_EDGE(a, 9);
+    case E_STREAM:   // few tiles: the per-block LDS preload would dominate
+        return launch_k(k_edge_step<4, 0>, a, stream_launch(L, a.ntiles, w.cus), s);
+    case E_RING4: case E_RING_H4: case E_RING_HS4: {
+        // as few blocks as the number of rounds allows (every block pays the LDS prologue)
+        const int rounds = (a.ntiles + 4 * w.cus - 1) / (4 * w.cus), blocks = ring_blocks(a.ntiles, 4 * rounds, w.cus);
+        return f == E_RING4 ? launch_edge_ring(a, blocks, 256, s) : f == E_RING_H4 ? launch_edge_ring_h(a, blocks, 256, s) : launch_edge_ring_hs(a, blocks, 256, s);
+    }
+    case E_RING8: return launch_edge_ring(a, lc.blocks, lc.threads, s);
+    case E_RING_H8: return launch_edge_ring_h(a, lc.blocks, lc.threads, s);
+    case E_RING_HS8: return launch_edge_ring_hs(a, lc.blocks, lc.threads, s);
+    case E_STEP: {
         lc.lds += (size_t)MGN_EDGE_JR * 64 * 4 * 4;   // partially resident third chunk
         // Tail of the persistent walk: with r = ntiles / (8 waves x 256 blocks) rounds, a last round that is less than
         // ~60 % full costs a whole tile-time (11.4 tiles per wave on an 8-GPU partition of M-1M: 5 %).  Those tiles go to
@@ -2740,160 +2768,131 @@ hipError_t launch_edge_step(int L, const EdgeArgs& a, hipStream_t s) {
         const int rem = a.ntiles % nw, rounds = a.ntiles / nw;
         // (Launches with fewer than MGN_SPREAD_ROUNDS rounds spread their last round over all CUs instead -- TileWalk -- and
         // are faster without the split: -2.7 % at 125 k nodes, the per-GPU share of M-1M on 8 GPUs.)
-        if (g_tail_coop && g_path == 0 && a.chunk_t[0] && rounds >= MGN_SPREAD_ROUNDS && rem > 0 && rem * 10 < nw * 6) {
+        if (w.path == 0 && a.chunk_t[0] && rounds >= MGN_SPREAD_ROUNDS && rem > 0 && rem * 10 < nw * 6) {
             EdgeArgs body = a, tail = a;
             body.ntiles = a.ntiles - rem;
             tail.tile0 = a.tile0 + body.ntiles;
             tail.ntiles = rem;
             const hipError_t e = launch_k(k_edge_step<4, 2>, body, lc, s);
             if (e != hipSuccess) return e;
-            LaunchCfg c4{rem, 256, coop_lds()};
+            const LaunchCfg c4{rem, 256, coop_lds()};
             return launch_k(k_edge_coop<false>, tail, c4, s);
         }
         return launch_k(k_edge_step<4, 2>, a, lc, s);
     }
-    if (L == 64) return launch_k(k_edge_step<2, 3>, a, lc, s);
-    if (L == 32) return launch_k(k_edge_step<1, 3>, a, lc, s);
-    return hipErrorInvalidValue;
-}
-static std::atomic<int> g_last_node_kernel{0};    // family of the last node-MLP launch (tests / bench): 1 general, 2 16-row cooperative, 3 cooperative,
-int last_node_kernel() { return g_last_node_kernel.load(std::memory_order_relaxed); }   // 5 k_node_split, 6 k_node_split<two sets>, 7 fp32-MFMA k_node_step, 8 / 9 16-row kernels on the split path, 10 k_node_split_h, 12 k_node_bf16_pipe
-hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
-    if (a.ntiles <= 0) return hipSuccess;
-    if (a.mode != 2) set_last(g_last_node_kernel, a.gen.use ? 1 : (a.c16 && L == 128 && a.chunk_t[0]) ? 2 : coop_ok(L, a.ntiles, a.chunk_t) ? 3 : 7);
-    if (a.gen.use) {
-        if (a.mode == 2) return launch_project(L, a, s);
-        if (a.AGG2) {
-            if (a.mode == 1) return hipErrorInvalidValue;      // two edge sets: the host projects per set
-            DISPATCH_GEN(L, (k_node_step<4, 0, false, 2, true>), (k_node_step<2, 0, false, 2, true>), (k_node_step<1, 0, false, 2, true>), a, a.ntiles);
-        }
-        if (a.mode == 1) DISPATCH_GEN(L, (k_node_step<4, 0, true, 1, true>), (k_node_step<2, 0, true, 1, true>), (k_node_step<1, 0, true, 1, true>), a, a.ntiles);
-        DISPATCH_GEN(L, (k_node_step<4, 0, false, 1, true>), (k_node_step<2, 0, false, 1, true>), (k_node_step<1, 0, false, 1, true>), a, a.ntiles);
-    }
-    if (a.c16 && L == 128 && a.chunk_t[0]) {
-        LaunchCfg c16{2 * a.ntiles, 256, (size_t)4 * 8 * 64 * 16 + 2 * 64 * 4};
-        if (g_fp32_split && (g_c16_split & 2) && a.split16[0] && (!a.AGG2 || a.split16[6])) {   // split path (pieces exchanged: 12 KiB per buffer)
-            c16.lds = (size_t)4 * 12 * 64 * 16 + 2 * 64 * 4;
-            if (a.mode != 2) set_last(g_last_node_kernel, 8);
-            if (g_split_f16 && a.split16h[0] && (!a.AGG2 || a.split16h[6])) {      // two fp16 pieces
-                if (a.bf) return a.AGG2 ? launch_k(k_node_coop16<2, true, 2>, a, c16, s) : launch_k(k_node_coop16<1, true, 2>, a, c16, s);
-                return a.AGG2 ? launch_k(k_node_coop16<2, false, 2>, a, c16, s) : launch_k(k_node_coop16<1, false, 2>, a, c16, s);
-            }
-            if (a.bf) return a.AGG2 ? launch_k(k_node_coop16<2, true, 1>, a, c16, s) : launch_k(k_node_coop16<1, true, 1>, a, c16, s);
-            return a.AGG2 ? launch_k(k_node_coop16<2, false, 1>, a, c16, s) : launch_k(k_node_coop16<1, false, 1>, a, c16, s);
-        }
-        if (a.bf) return a.AGG2 ? launch_k(k_node_coop16<2, true>, a, c16, s) : launch_k(k_node_coop16<1, true>, a, c16, s);
-        return a.AGG2 ? launch_k(k_node_coop16<2, false>, a, c16, s) : launch_k(k_node_coop16<1, false>, a, c16, s);
-    }
-    const bool split_node = L == 128 && a.mode == 0 && a.split[0] && (!a.AGG2 || a.split[6]) && node_split_size(a.ntiles);
-    // between the 16-row kernels' range and the split-path node kernels (8 k .. 16 k nodes on a mesh): the edge step ran a 32-row
-    // kernel, the node side still fits half tiles of 16 rows two blocks per CU -- the 16-row node kernel on the split path, reading
-    // the 32-edge-tile carry rows (16 k nodes: 37 -> 2x us against the cooperative 32-row kernel on the fp32 pipe)
-    if (g_node16_mid && g_fp32_split && (g_c16_split & 2) && g_path == 0 && L == 128 && !a.bf && !a.AGG2 && a.mode != 2 && a.split16[0] &&
-        coop_ok(L, a.ntiles, a.chunk_t) && !split_node) {
-        LaunchCfg c16{2 * a.ntiles, 256, (size_t)4 * 12 * 64 * 16 + 2 * 64 * 4};
-        set_last(g_last_node_kernel, 9);
-        if (g_split_f16 && a.split16h[0]) return launch_k(k_node_coop16<1, false, 2, 5>, a, c16, s);
-        return launch_k(k_node_coop16<1, false, 1, 5>, a, c16, s);
-    }
-    if (coop_ok(L, a.ntiles, a.chunk_t) && !split_node) {
-        LaunchCfg c4{a.ntiles, 256, coop_lds()};
-        if (coop_fence(a.ntiles)) return a.AGG2 ? launch_k(k_node_coop<true, true>, a, c4, s) : launch_k(k_node_coop<false, true>, a, c4, s);
-        return a.AGG2 ? launch_k(k_node_coop<true, false>, a, c4, s) : launch_k(k_node_coop<false, false>, a, c4, s);
-    }
-    if (a.mode == 2) return launch_project(L, a, s);
-    const bool proj = a.mode == 1;
-    if (split_node) {   // split path (split.hip)
-        LaunchCfg ls = tile_launch(L, a.ntiles, 2);
-        ls.lds = (size_t)4 * 16384 * 2 + (size_t)T_COUNT * L * 4 + 64;
-        if (g_split_f16 && a.splith[0] && !a.AGG2) {   // two fp16 pieces, three products
-            set_last(g_last_node_kernel, 10);
-            return launch_node_split_h(a, ls, s);
-        }
-        set_last(g_last_node_kernel, a.AGG2 ? 6 : 5);
-        return launch_node_split(a, ls, s);
-    }
-    const int nres = resident_chunks(L, proj ? 6 : 4);
-    const LaunchCfg lc = tile_launch(L, a.ntiles, nres);
-    if (a.AGG2) {   // two edge sets: MLP only here, the host projects per set in separate launches
-        if (proj) return hipErrorInvalidValue;
-        if (L == 128) {
-            if (small_launch(a.ntiles)) {
-                LaunchCfg l0 = lc;
-                l0.lds = (size_t)T_COUNT * L * 4 + 64;
-                return launch_k(k_node_step<4, 0, false, 2>, a, l0, s);
-            }
-            return launch_k(k_node_step<4, 2, false, 2>, a, lc, s);
-        }
-        if (L == 64) return launch_k(k_node_step<2, 4, false, 2>, a, lc, s);
-        if (L == 32) return launch_k(k_node_step<1, 4, false, 2>, a, lc, s);
+    case E_SMALL_L:
+        return L == 64 ? launch_k(k_edge_step<2, 3>, a, lc, s) : launch_k(k_edge_step<1, 3>, a, lc, s);
+    default:
         return hipErrorInvalidValue;
     }
-    if (L == 128) {
-        if (small_launch(a.ntiles)) {
-            LaunchCfg l0 = lc;
-            l0.lds = (size_t)T_COUNT * L * 4 + 64;
+}
+
+// Node MLP of a step (mode 0), or the MLP and the next step's P / Q in one launch (mode 1)
+static bool node_split_pair(const NodeArgs& a, const Switches& w) { return a.split[0] && w.node_split_size(a.ntiles); }
+// k_node_ring_hs takes mode 1 where k_node_split_h + k_project_split_h would run: fp32, one edge set, two fp16 pieces, the whole node range
+static bool node_ring_hs_ok(int L, const NodeArgs& a, const Switches& w) {
+    return w.node_ring_hs && L == 128 && w.f16 && !a.bf && !a.AGG2 && !a.gen.use && !a.c16 && a.mode == 1 && a.tile0 == 0 && a.splith[0] && a.splith[4] &&
+           a.splith[5] && node_split_pair(a, w);
+}
+// Large meshes run MLP and projection as two launches (the projection then has both of its chunks LDS-resident), and so does the split
+// path from two tiles per CU, whose node kernels are two by construction -- unless k_node_ring_hs takes both; small meshes are
+// launch-latency-bound: one launch (M-cyl: 53.0 -> 50.8 us per step).  Two edge sets: one launch on the 16-row kernels only.
+static bool one_node_launch(int L, const NodeArgs& a, const Switches& w) {
+    if (a.AGG2) return a.c16 != 0;
+    return (w.coop_size(a.ntiles, false) && !node_split_pair(a, w)) || node_ring_hs_ok(L, a, w);
+}
+bool node_step_projects(int L, const NodeArgs& a) { return one_node_launch(L, a, Switches()); }
+
+static NodeFamily node_family(int L, const NodeArgs& a, const Switches& w) {
+    if (a.gen.use) return a.AGG2 && a.mode == 1 ? N_INVALID : N_GEN;      // two edge sets: the host projects per set
+    if (a.c16 && L == 128 && a.chunk_t[0])
+        return w.split && (w.c16_split & 2) && a.split16[0] && (!a.AGG2 || a.split16[6]) ? N_COOP16_SPLIT : N_COOP16;
+    if (node_ring_hs_ok(L, a, w)) return N_RING_HS;
+    if (L == 128 && a.mode == 0 && a.split[0] && (!a.AGG2 || a.split[6]) && w.node_split_size(a.ntiles))   // split path (split.hip)
+        return w.f16 && a.splith[0] && !a.AGG2 ? N_SPLIT_H : a.AGG2 ? N_SPLIT2 : N_SPLIT;
+    if (L == 128 && a.chunk_t[0] && w.coop_size(a.ntiles, false)) {
+        // between the 16-row kernels' range and the split-path node kernels (8 k .. 16 k nodes on a mesh): the edge step ran a 32-row
+        // kernel, the node side still fits half tiles of 16 rows two blocks per CU -- the 16-row node kernel on the split path, reading
+        // the 32-edge-tile carry rows (16 k nodes: 37 -> 2x us against the cooperative 32-row kernel on the fp32 pipe)
+        return w.split && (w.c16_split & 2) && w.path == 0 && !a.bf && !a.AGG2 && a.split16[0] ? N_COOP16_MID : N_COOP;
+    }
+    return a.AGG2 && a.mode == 1 ? N_INVALID : N_STEP;                      // two edge sets: MLP only, the host projects per set
+}
+
+hipError_t launch_node_step(int L, const NodeArgs& a, hipStream_t s) {
+    if (a.ntiles <= 0) return hipSuccess;
+    if (a.mode == 2) return launch_project(L, a, s);
+    const Switches w;
+    const NodeFamily f = node_family(L, a, w);
+    if (f != N_INVALID) record_node(f);
+    const bool proj = a.mode == 1;
+    switch (f) {
+    case N_GEN: {
+        const LaunchCfg lg = stream_launch(L, a.ntiles, w.cus);
+        if (a.AGG2) return launch_by_L(L, k_node_step<4, 0, false, 2, true>, k_node_step<2, 0, false, 2, true>, k_node_step<1, 0, false, 2, true>, a, lg, s);
+        if (proj) return launch_by_L(L, k_node_step<4, 0, true, 1, true>, k_node_step<2, 0, true, 1, true>, k_node_step<1, 0, true, 1, true>, a, lg, s);
+        return launch_by_L(L, k_node_step<4, 0, false, 1, true>, k_node_step<2, 0, false, 1, true>, k_node_step<1, 0, false, 1, true>, a, lg, s);
+    }
+    case N_COOP16:
+        return launch_node_coop16<0>(a, {2 * a.ntiles, 256, 4 * c16_buf(false) + 2 * 64 * 4}, s);
+    case N_COOP16_SPLIT: {
+        const LaunchCfg c16{2 * a.ntiles, 256, 4 * c16_buf(true) + 2 * 64 * 4};
+        return w.f16 && a.split16h[0] && (!a.AGG2 || a.split16h[6]) ? launch_node_coop16<2>(a, c16, s) : launch_node_coop16<1>(a, c16, s);
+    }
+    case N_COOP16_MID: {
+        const LaunchCfg c16{2 * a.ntiles, 256, 4 * c16_buf(true) + 2 * 64 * 4};
+        return w.f16 && a.split16h[0] ? launch_k(k_node_coop16<1, false, 2, 5>, a, c16, s) : launch_k(k_node_coop16<1, false, 1, 5>, a, c16, s);
+    }
+    case N_RING_HS: return launch_node_ring_hs(a, ring_blocks(a.ntiles, 8, w.cus), s);
+    case N_COOP: return launch_node_coop(a, w.coop_fenced(a.ntiles), s);
+    case N_SPLIT: case N_SPLIT2: case N_SPLIT_H: {
+        const LaunchCfg ls = tile_launch(L, a.ntiles, 2, w.cus);
+        return f == N_SPLIT_H ? launch_node_split_h(a, ls.blocks, ls.threads, s) : launch_node_split(a, ls.blocks, ls.threads, s);
+    }
+    case N_STEP: {
+        const LaunchCfg lc = tile_launch(L, a.ntiles, resident_chunks(L, proj ? 6 : 4), w.cus);
+        if (L == 128 && w.streams(a.ntiles)) {
+            const LaunchCfg l0 = stream_launch(L, a.ntiles, w.cus);
+            if (a.AGG2) return launch_k(k_node_step<4, 0, false, 2>, a, l0, s);
             return proj ? launch_k(k_node_step<4, 0, true>, a, l0, s) : launch_k(k_node_step<4, 0, false>, a, l0, s);
         }
-        return proj ? launch_k(k_node_step<4, 2, true>, a, lc, s) : launch_k(k_node_step<4, 2, false>, a, lc, s);
+        if (a.AGG2) return launch_by_L(L, k_node_step<4, 2, false, 2>, k_node_step<2, 4, false, 2>, k_node_step<1, 4, false, 2>, a, lc, s);
+        if (proj) return launch_by_L(L, k_node_step<4, 2, true>, k_node_step<2, 6, true>, k_node_step<1, 6, true>, a, lc, s);
+        return launch_by_L(L, k_node_step<4, 2, false>, k_node_step<2, 4, false>, k_node_step<1, 4, false>, a, lc, s);
     }
-    if (L == 64) return proj ? launch_k(k_node_step<2, 6, true>, a, lc, s) : launch_k(k_node_step<2, 4, false>, a, lc, s);
-    if (L == 32) return proj ? launch_k(k_node_step<1, 6, true>, a, lc, s) : launch_k(k_node_step<1, 4, false>, a, lc, s);
-    return hipErrorInvalidValue;
+    default:
+        return hipErrorInvalidValue;
+    }
 }
-// node MLP + residual + P / Q of the next step in one launch (split.hip: k_node_ring_hs) where launch_node_step + launch_project would run
-// k_node_split_h + k_project_split_h: fp32, one edge set, two fp16 pieces, whole node range.  *launched = false: not this size / mode.
-hipError_t launch_node_project_fused(int L, const NodeArgs& a, hipStream_t s, bool* launched) {
-    *launched = false;
-    if (!(node_ring_hs_enabled() && L == 128 && g_fp32_split == 1 && g_split_f16 && g_path == 0 && !a.bf && !a.AGG2 && !a.gen.use && a.mode == 0 &&
-          a.tile0 == 0 && a.splith[0] && a.splith[4] && a.splith[5] && node_split_size(a.ntiles)))
-        return hipSuccess;
-    LaunchCfg ls = tile_launch(L, a.ntiles, 2);
-    ls.threads = 512;
-    int blocks = (a.ntiles + 7) / 8;
-    if (blocks > num_cus()) blocks = num_cus();
-    ls.blocks = ((blocks + NUM_XCD - 1) / NUM_XCD) * NUM_XCD;
-    set_last(g_last_node_kernel, 11);
-    *launched = true;
-    return launch_node_ring_hs(a, ls, s);
+
+// P, Q of a set over the node tiles [tile0, tile0 + ntiles) (mode 2; boundary / interior halves of a partition: the family follows
+// the part's size)
+static NodeFamily project_family(int L, const NodeArgs& a, const Switches& w) {
+    const bool tuned = !a.gen.use && a.mode == 2;
+    if (tuned && a.c16 && L == 128 && a.chunk_t[0] && !a.AGG2) return w.split && (w.c16_split & 2) && a.split16[4] ? N_COOP16_SPLIT : N_COOP16;
+    if (tuned && L == 128 && a.split[4] && w.node_split_size(a.ntiles)) return w.f16 && a.splith[4] ? N_SPLIT_H : N_SPLIT;
+    if (tuned && a.tile0 == 0 && L == 128 && a.chunk_t[0] && w.coop_size(a.ntiles, false)) return N_COOP;
+    return N_STEP;
 }
 
 hipError_t launch_project(int L, const NodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    LaunchCfg lc = tile_launch(L, a.ntiles, 2);
-    if (!a.gen.use && a.c16 && L == 128 && a.chunk_t[0] && !a.AGG2 && a.mode == 2) {
-        LaunchCfg c16{2 * a.ntiles, 256, (size_t)4 * 8 * 64 * 16 + 2 * 64 * 4};
-        if (g_fp32_split && (g_c16_split & 2) && a.split16[4]) {
-            c16.lds = (size_t)4 * 12 * 64 * 16 + 2 * 64 * 4;
-            if (g_split_f16 && a.split16h[4]) return a.bf ? launch_k(k_node_coop16<1, true, 2>, a, c16, s) : launch_k(k_node_coop16<1, false, 2>, a, c16, s);
-            return a.bf ? launch_k(k_node_coop16<1, true, 1>, a, c16, s) : launch_k(k_node_coop16<1, false, 1>, a, c16, s);
-        }
-        return a.bf ? launch_k(k_node_coop16<1, true>, a, c16, s) : launch_k(k_node_coop16<1, false>, a, c16, s);
+    const Switches w;
+    LaunchCfg lc = tile_launch(L, a.ntiles, 2, w.cus);   // both chunks LDS-resident
+    switch (project_family(L, a, w)) {
+    case N_COOP16: return launch_node_coop16<0>(a, {2 * a.ntiles, 256, 4 * c16_buf(false) + 2 * 64 * 4}, s);
+    case N_COOP16_SPLIT: {
+        const LaunchCfg c16{2 * a.ntiles, 256, 4 * c16_buf(true) + 2 * 64 * 4};
+        return w.f16 && a.split16h[4] ? launch_node_coop16<2>(a, c16, s) : launch_node_coop16<1>(a, c16, s);
     }
-    if (!a.gen.use && a.tile0 == 0 && a.mode == 2 && coop_ok(L, a.ntiles, a.chunk_t) && !(L == 128 && a.split[4] && node_split_size(a.ntiles))) {
-        LaunchCfg c4{a.ntiles, 256, coop_lds()};
-        if (coop_fence(a.ntiles)) return a.AGG2 ? launch_k(k_node_coop<true, true>, a, c4, s) : launch_k(k_node_coop<false, true>, a, c4, s);
-        return a.AGG2 ? launch_k(k_node_coop<true, false>, a, c4, s) : launch_k(k_node_coop<false, false>, a, c4, s);
+    case N_COOP: return launch_node_coop(a, w.coop_fenced(a.ntiles), s);
+    case N_SPLIT: return launch_project_split(a, lc.blocks, lc.threads, s);
+    case N_SPLIT_H: return launch_project_split_h(a, lc.blocks, lc.threads, s);
+    default:
+        if (L == 128 && w.streams(a.ntiles)) return launch_k(k_project<4, false>, a, stream_launch(L, a.ntiles, w.cus), s);
+        if (L == 128 && lc.threads == 512) lc.threads = MGN_PROJ_WAVES * 64;
+        return launch_by_L(L, k_project<4, true>, k_project<2, true>, k_project<1, true>, a, lc, s);
     }
-    // (a.ntiles may be a part of the node tiles -- boundary / interior halves of a partition: the kernel family follows the part's size)
-    const bool split_ok = !a.gen.use && a.mode == 2 && a.split[4] && node_split_size(a.ntiles);
-    if (L == 128 && small_launch(a.ntiles) && !split_ok) {
-        lc.lds = (size_t)T_COUNT * L * 4 + 64;
-        return launch_k(k_project<4, false>, a, lc, s);
-    }
-    if (L == 128) {
-        if (split_ok) {   // split path (split.hip)
-            LaunchCfg ls = lc;
-            ls.lds = (size_t)4 * 16384 * 2 + (size_t)T_COUNT * L * 4 + 64;
-            if (g_split_f16 && a.splith[4]) return launch_project_split_h(a, ls, s);
-            return launch_project_split(a, ls, s);
-        }
-        if (lc.threads == 512) lc.threads = MGN_PROJ_WAVES * 64;
-        return launch_k(k_project<4, true>, a, lc, s);
-    }
-    if (L == 64) return launch_k(k_project<2, true>, a, lc, s);
-    if (L == 32) return launch_k(k_project<1, true>, a, lc, s);
-    return hipErrorInvalidValue;
 }
 // The encoder / decoder stages: a stage's two kernel templates, the chunks it keeps in LDS where they fit (WANT) and the cooperative
 // size range it follows.  launch_stage picks, in this order: the GEN instantiation (hidden_layers != 2); at L = 128 the cooperative
@@ -2920,25 +2919,23 @@ struct DecK {
 template <class K, class A>
 static hipError_t launch_stage(int L, const A& a, hipStream_t s) {
     const int nt = a.ntiles;
-    if (a.w.gen.use) DISPATCH_GEN(L, (K::template tiles<4, 0, true>()), (K::template tiles<2, 0, true>()), (K::template tiles<1, 0, true>()), a, nt);
     if (nt <= 0) return hipSuccess;
+    const Switches w;
+    if (a.w.gen.use) return launch_by_L(L, K::template tiles<4, 0, true>(), K::template tiles<2, 0, true>(), K::template tiles<1, 0, true>(), a, stream_launch(L, nt, w.cus), s);
     constexpr int R128 = K::WANT < 2 ? K::WANT : 2;
-    const bool h2 = L == 128 && g_fp32_split && g_split_f16 && a.w.splith[0];
-    if (L == 128 && coop_size(nt, K::EDGE)) {
+    const bool h2 = L == 128 && w.split && w.f16 && a.w.splith[0];
+    if (L == 128 && w.coop_size(nt, K::EDGE)) {
         const LaunchCfg c4{nt, 256, coop_lds()};
-        if (h2) return coop_fence(nt) ? launch_k(K::template coop<true, true>(), a, c4, s) : launch_k(K::template coop<false, true>(), a, c4, s);
-        return coop_fence(nt) ? launch_k(K::template coop<true, false>(), a, c4, s) : launch_k(K::template coop<false, false>(), a, c4, s);
+        if (h2) return w.coop_fenced(nt) ? launch_k(K::template coop<true, true>(), a, c4, s) : launch_k(K::template coop<false, true>(), a, c4, s);
+        return w.coop_fenced(nt) ? launch_k(K::template coop<true, false>(), a, c4, s) : launch_k(K::template coop<false, false>(), a, c4, s);
     }
-    const LaunchCfg lc = tile_launch(L, nt, resident_chunks(L, K::WANT));
-    if (L == 128 && small_launch(nt)) {
-        LaunchCfg l0 = lc;
-        l0.lds = (size_t)T_COUNT * L * 4 + 64;
+    const LaunchCfg lc = tile_launch(L, nt, resident_chunks(L, K::WANT), w.cus);
+    if (L == 128 && w.streams(nt)) {
+        const LaunchCfg l0 = stream_launch(L, nt, w.cus);
         return h2 ? launch_k(K::template tiles<4, 0, false, true>(), a, l0, s) : launch_k(K::template tiles<4, 0>(), a, l0, s);
     }
     if (L == 128) return h2 ? launch_k(K::template tiles<4, R128, false, true>(), a, lc, s) : launch_k(K::template tiles<4, R128>(), a, lc, s);
-    if (L == 64) return launch_k(K::template tiles<2, K::WANT>(), a, lc, s);
-    if (L == 32) return launch_k(K::template tiles<1, K::WANT>(), a, lc, s);
-    return hipErrorInvalidValue;
+    return launch_by_L(L, K::template tiles<4, R128>(), K::template tiles<2, K::WANT>(), K::template tiles<1, K::WANT>(), a, lc, s);
 }
 hipError_t launch_enc_node(int L, const EncNodeArgs& a, hipStream_t s) { return launch_stage<EncNodeK>(L, a, s); }
 hipError_t launch_enc_edge(int L, const EncEdgeArgs& a, hipStream_t s) { return launch_stage<EncEdgeK>(L, a, s); }
@@ -2951,12 +2948,12 @@ static LaunchCfg bf_launch(int ntiles, int nchunks) {
 }
 hipError_t launch_edge_bf16(const BfEdgeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    SET_LAST_EDGE(a, 18);
+    record_edge(E_BF16_PIPE, a.ntiles, a.E);
     return launch_k(k_edge_bf16_pipe, a, bf_launch(a.ntiles, 3), s);   // software-pipelined: two waves per SIMD, 256 registers
 }
 hipError_t launch_node_bf16(const BfNodeArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
-    set_last(g_last_node_kernel, 12);
+    record_node(N_BF16_PIPE);
     return launch_k(k_node_bf16_pipe, a, bf_launch(a.ntiles, 4), s);
 }
 hipError_t launch_project_bf16(const BfNodeArgs& a, hipStream_t s) {

@@ -356,18 +356,14 @@ void drop_graph(mgn_engine* h) {
 // (the legacy NULL stream -- mgn_set_stream(h, NULL) -- cannot be captured: eager there)
 bool small_graphable(const mgn_engine* h) { return h->use_graph && !h->prof && h->stream != nullptr && launch_is_small(h->ntiles_n); }
 
-// 16-row cooperative tiles (v_mfma_f32_16x16x4_f32): both kernels of a processor step must agree (the carry rows are per 16-edge
-// tile then), so the choice is made per handle and graph: fp32, L = 128, hidden_layers = 2, and the node launch and EVERY edge
-// set's launch in the cooperative size range
+// the 16-row kernels run this handle's processor steps (kernels.hip: coop16_handle): one choice per handle and graph
 int32_t use_c16(const mgn_engine* h) {
-    // (bf16 mode included: the 16-row kernels then read and write the bf16 arrays and keep fp32 weights and arithmetic)
-    if (!(coop16_enabled() && h->cfg.L == 128 && h->cfg.hidden_layers == 2 && get_kernel_path() != 4 && launch_is_small(h->ntiles_n)))
-        return 0;
-    const bool ring_hs = h->cfg.dtype == MGN_F32 && h->nsets == 1 && ring_hs_default();
-    for (int q = 0; q < h->nsets; ++q)
-        if (!(launch_is_small_edge(h->es[q].ntiles_e) && coop16_size(h->es[q].ntiles_e, h->ntiles_n, ring_hs))) return 0;
-    return 1;
+    int32_t nte[MAX_EDGE_SETS] = {};
+    for (int q = 0; q < h->nsets; ++q) nte[q] = h->es[q].ntiles_e;
+    return coop16_handle(h->cfg.L, h->cfg.hidden_layers, h->cfg.dtype == MGN_F32, h->nsets, h->ntiles_n, nte) ? 1 : 0;
 }
+// bf16 storage runs its own pipelined kernels wherever the 16-row kernels do not take the handle
+bool bf16_pipe(const mgn_engine* h) { return h->cfg.dtype == MGN_BF16 && !use_c16(h); }
 
 // GenMlp of an MLP: used when hidden_layers != 2 (or when tests force the GEN kernels, kernel path 4)
 GenMlp gen_of(const mgn_engine* h, const GenOff& g, bool has_last) {
@@ -425,7 +421,8 @@ EdgeArgs edge_args(mgn_engine* h, int k, int q = 0) {
     a.h2_b2pos = so.e_b2pos[q];
     a.c16 = use_c16(h);
     if (k == 0 && q == 0 && h->elat_src_override && a.c16 && !a.gen.use) a.ElatSrc = h->elat_src_override;
-    a.stagger = h->stagger_edge;
+    constexpr int32_t STAGGER_EDGE = 0;   // start stagger of waves 4..7: none since the padded MFMAs (sweep 0..64: 4.558 .. 4.621 ms)
+    a.stagger = STAGGER_EDGE;
     a.tile0 = 0;
     a.stamps = h->d_stamps.as<unsigned long long>();
     return a;
@@ -489,7 +486,8 @@ NodeArgs node_args(mgn_engine* h, int k, int mode, int q = 0) {
     a.h2_b2pos = a.splith[0] ? so.n_b2pos : 0.f;
     a.mode = mode;
     a.gen = gen_of(h, so.n_gen, true);
-    a.stagger = h->stagger_node;
+    constexpr int32_t STAGGER_NODE = 8;   // start stagger of waves 4..7, s_sleep(127) units
+    a.stagger = STAGGER_NODE;
     a.zero_row = 4 * tiles_or_one(h->es[0].ntiles_e);
     a.c16 = use_c16(h);
     a.stamps = h->d_stamps.as<unsigned long long>();
@@ -584,10 +582,8 @@ int mgn::sync_norms_host(mgn_engine* h) {
 }
 
 // step 0's edge launch can read its e rows from a second array (EdgeArgs::ElatSrc): one edge set on the 16-row kernels, one partition
-bool mgn::elat_src_ok(mgn_engine* h) {
-    static const int on = env_int("MGN_RHS_ELAT_SRC", 1);   // 0: restore copy per right-hand side
-    return on && h->nsets == 1 && h->cfg.nranks == 1 && h->cfg.L == 128 && h->cfg.hidden_layers == 2 && get_kernel_path() != 4 && use_c16(h);
-}
+// (in place of a restore copy per right-hand side)
+bool mgn::elat_src_ok(mgn_engine* h) { return h->nsets == 1 && h->cfg.nranks == 1 && use_c16(h); }
 
 bool mgn::is_bf16(const mgn_engine* h) { return h->cfg.dtype == MGN_BF16; }
 // tile-major storage: rows padded to whole 32-row tiles
@@ -632,9 +628,6 @@ int mgn_create(const mgn_config* cfg, mgn_handle** out) try {
         return fail(nullptr, MGN_E_HIP, "mgn_create: hipStreamCreate failed");
     }
     h->stream = h->own_stream;
-    h->stagger_edge = env_int("MGN_STAGGER_EDGE", h->stagger_edge);
-    h->stagger_node = env_int("MGN_STAGGER_NODE", h->stagger_node);
-    h->node_split = env_int("MGN_NODE_SPLIT", h->node_split);
     h->use_graph = env_int("MGN_GRAPH", h->use_graph);
     layout_all(h);
     *out = h;
@@ -1398,7 +1391,7 @@ int mgn_fwd_upload(mgn_handle* h, const float* nf, const float* ef) try {
 
 static int project_set(mgn_handle* h, int k, int q, int32_t tile0 = 0, int32_t ntiles = -1) {   // P,Q of set q for step k (k = mps: step 0)
     if (ntiles < 0) ntiles = h->ntiles_n;
-    if (is_bf16(h) && !use_c16(h)) {
+    if (bf16_pipe(h)) {
         BfNodeArgs b = bf_node_args(h, k, q, true);
         b.tile0 = tile0;
         b.ntiles = ntiles;
@@ -1494,7 +1487,7 @@ static int proc_edge_range(mgn_handle* h, int32_t k, int32_t phase) {   // phase
         const int32_t tb = boundary_tiles(h, q), nt = h->es[q].ntiles_e;
         const int32_t t0 = phase == 1 ? tb : 0, n = phase == 0 ? nt : (phase == 1 ? nt - tb : tb);
         if (n <= 0) continue;
-        if (is_bf16(h) && !use_c16(h)) {
+        if (bf16_pipe(h)) {
             BfEdgeArgs a = bf_edge_args(h, k, q);
             a.tile0 = t0;
             a.ntiles = n;
@@ -1530,37 +1523,29 @@ int mgn_edge_boundary_tiles(const mgn_handle* h, int32_t set, int32_t* boundary,
     return MGN_OK;
 } MGN_CATCH(nullptr)
 
+// the node MLP of step k and, with project_next, P / Q of step k + 1 for every edge set: in the MLP's launch where the kernels have
+// that form at this size (kernels.hip: node_step_projects), else one projection launch per set behind it
+static int node_side(mgn_handle* h, int32_t k, bool project_next) {
+    bool projected = false;
+    if (bf16_pipe(h)) {
+        HIPCHK(h, launch_node_bf16(bf_node_args(h, k), h->stream));
+    } else {
+        NodeArgs a = node_args(h, k, project_next ? 1 : 0);
+        projected = project_next && node_step_projects(h->cfg.L, a);
+        a.mode = projected ? 1 : 0;      // (the mode is all that differs between the two argument blocks)
+        HIPCHK(h, launch_node_step(h->cfg.L, a, h->stream));
+    }
+    for (int q = 0; project_next && !projected && q < h->nsets; ++q)
+        if (int rc = project_set(h, k, q)) return rc;
+    return MGN_OK;
+}
+
 int mgn_proc_node(mgn_handle* h, int32_t k, int32_t project_next) try {
     if (int rc = need(h, true, true)) return rc;
     if (k < 0 || k >= h->cfg.mps) return fail(h, MGN_E_ARG, "mgn_proc_node: step %d out of range", k);
     if (project_next && k + 1 >= h->cfg.mps) return fail(h, MGN_E_ARG, "mgn_proc_node: no step %d to project for", k + 1);
     ProfScope ps(h, F_NODE);
-    if (is_bf16(h) && !use_c16(h)) {
-        HIPCHK(h, launch_node_bf16(bf_node_args(h, k), h->stream));
-        for (int q = 0; project_next && q < h->nsets; ++q)
-            if (int rc = project_set(h, k, q)) return rc;
-        return MGN_OK;
-    }
-    // large meshes: MLP and projection as two launches (the projection then has both of its chunks LDS-resident);
-    // small meshes are launch-latency-bound: one fused launch (M-cyl: 53.0 -> 50.8 us per step)
-    // (... and from two tiles per CU where the split-path node kernels exist: they are two launches by construction)
-    const bool split_pair = h->steps[k].n[0].sp32 != ChunkRef::NONE && node_split_size(h->ntiles_n);
-    if (project_next && !(h->nsets == 2 && use_c16(h)) && (h->nsets > 1 || split_pair || (h->node_split && !launch_is_small(h->ntiles_n)))) {
-        // MLP (2 of its chunks LDS-resident, the others stream from L2), then per edge set the projection with both of
-        // its chunks resident -- or, one edge set on two fp16 pieces, both in one lock-step launch (k_node_ring_hs)
-        if (h->nsets == 1 && split_pair) {
-            bool fused = false;
-            HIPCHK(h, launch_node_project_fused(h->cfg.L, node_args(h, k, 0), h->stream, &fused));
-            if (fused) return MGN_OK;
-        }
-        HIPCHK(h, launch_node_step(h->cfg.L, node_args(h, k, 0), h->stream));
-        for (int q = 0; q < h->nsets; ++q)
-            if (int rc = project_set(h, k, q)) return rc;
-        return MGN_OK;
-    }
-    const NodeArgs a = node_args(h, k, project_next ? 1 : 0);
-    HIPCHK(h, launch_node_step(h->cfg.L, a, h->stream));
-    return MGN_OK;
+    return node_side(h, k, project_next != 0);
 } MGN_CATCH(h)
 
 int mgn_proc_node_phase(mgn_handle* h, int32_t k, int32_t phase) try {
@@ -1570,10 +1555,8 @@ int mgn_proc_node_phase(mgn_handle* h, int32_t k, int32_t phase) try {
     ProfScope ps(h, F_NODE);
     const int ntb_all = (h->g.n_boundary + TILE - 1) / TILE;   // tiles that contain a boundary node
     const int ntb = ntb_all < h->ntiles_n ? ntb_all : h->ntiles_n;
-    if (phase == 1 && k >= 0) {
-        if (is_bf16(h) && !use_c16(h)) HIPCHK(h, launch_node_bf16(bf_node_args(h, k), h->stream));
-        else HIPCHK(h, launch_node_step(h->cfg.L, node_args(h, k, 0), h->stream));
-    }
+    if (phase == 1 && k >= 0)
+        if (int rc = node_side(h, k, false)) return rc;
     const int32_t tile0 = phase == 1 ? 0 : ntb, nt = phase == 1 ? ntb : h->ntiles_n - ntb;
     for (int q = 0; q < h->nsets; ++q)
         if (int rc = project_set(h, k >= 0 ? k : h->cfg.mps, q, tile0, nt)) return rc;

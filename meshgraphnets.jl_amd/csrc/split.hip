@@ -1679,46 +1679,40 @@ __global__ __launch_bounds__(512, 2) void k_project_split_h(const NodeArgs a) {
     }
 }
 
-// (the launches: launch.hpp raises each kernel's dynamic-LDS grant to the size it is launched with)
-hipError_t launch_edge_ring(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    if (lc.threads == 256) return launch_kernel(k_edge_ring<4>, lc.blocks, lc.threads, lc.lds, s, a);
-    return launch_kernel(k_edge_ring<8>, lc.blocks, lc.threads, lc.lds, s, a);
+// The launches, one per kernel: kernels.hip chooses the kernel, the blocks and the waves per block (256 threads: the <4> instantiation of
+// an edge ring kernel, else <8>); each launcher knows its kernel's LDS (launch.hpp raises the grant to it).
+constexpr size_t TABS_LDS = (size_t)T_COUNT * 128 * 4 + 64;
+constexpr size_t NODE_SPLIT_LDS = (size_t)4 * 16384 * 2 + TABS_LDS;   // four resident pieces
+hipError_t launch_edge_ring(const EdgeArgs& a, int blocks, int threads, hipStream_t s) {
+    const size_t lds = (size_t)3 * 32768 + (size_t)3 * 16384 + TABS_LDS;
+    if (threads == 256) return launch_kernel(k_edge_ring<4>, blocks, threads, lds, s, a);
+    return launch_kernel(k_edge_ring<8>, blocks, threads, lds, s, a);
 }
-static Switch g_ringh_stream{"MGN_RINGH_STREAM", 1};   // 1 (default): k_edge_ring_hs (no resident weight piece, e parked in LDS: read once); 0: k_edge_ring_h
-int edge_ring_h_streamed() { return g_ringh_stream; }
-int set_ringh_stream(int on) { return g_ringh_stream.set(on); }
-hipError_t launch_edge_ring_h(const EdgeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    if (g_ringh_stream) {
-        LaunchCfg ls = lc;
-        ls.lds = (size_t)Rs::NB * Rs::BUF * 16 + (size_t)(lc.threads / 64) * 16384 + (size_t)T_COUNT * 128 * 4 + 64;
-        if (lc.threads == 256) return launch_kernel(k_edge_ring_hs<4>, ls.blocks, ls.threads, ls.lds, s, a);
-        return launch_kernel(k_edge_ring_hs<8>, ls.blocks, ls.threads, ls.lds, s, a);
-    }
-    if (lc.threads == 256) return launch_kernel(k_edge_ring_h<4>, lc.blocks, lc.threads, lc.lds, s, a);
-    return launch_kernel(k_edge_ring_h<8>, lc.blocks, lc.threads, lc.lds, s, a);
+hipError_t launch_edge_ring_h(const EdgeArgs& a, int blocks, int threads, hipStream_t s) {
+    const size_t lds = (size_t)3 * 32768 + (size_t)Rh<MGN_RINGH_W>::NB * Rh<MGN_RINGH_W>::BUF * 16 + TABS_LDS;
+    if (threads == 256) return launch_kernel(k_edge_ring_h<4>, blocks, threads, lds, s, a);
+    return launch_kernel(k_edge_ring_h<8>, blocks, threads, lds, s, a);
 }
-size_t edge_ring_h_lds() { return (size_t)3 * 32768 + (size_t)Rh<MGN_RINGH_W>::NB * Rh<MGN_RINGH_W>::BUF * 16 + (size_t)T_COUNT * 128 * 4 + 64; }
-hipError_t launch_node_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    if (a.AGG2) return launch_kernel(k_node_split<true>, lc.blocks, lc.threads, lc.lds, s, a);
-    return launch_kernel(k_node_split<false>, lc.blocks, lc.threads, lc.lds, s, a);
+hipError_t launch_edge_ring_hs(const EdgeArgs& a, int blocks, int threads, hipStream_t s) {
+    const size_t lds = (size_t)Rs::NB * Rs::BUF * 16 + (size_t)(threads / 64) * 16384 + TABS_LDS;
+    if (threads == 256) return launch_kernel(k_edge_ring_hs<4>, blocks, threads, lds, s, a);
+    return launch_kernel(k_edge_ring_hs<8>, blocks, threads, lds, s, a);
 }
-hipError_t launch_node_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    return launch_kernel(k_node_split_h, lc.blocks, lc.threads, lc.lds, s, a);
+hipError_t launch_node_split(const NodeArgs& a, int blocks, int threads, hipStream_t s) {
+    if (a.AGG2) return launch_kernel(k_node_split<true>, blocks, threads, NODE_SPLIT_LDS, s, a);
+    return launch_kernel(k_node_split<false>, blocks, threads, NODE_SPLIT_LDS, s, a);
 }
-static Switch g_node_ring_hs{"MGN_NODE_RING_HS", 1};   // 1 (default): node MLP + projection as k_node_ring_hs where both would run; 0: k_node_split_h + k_project_split_h
-int node_ring_hs_enabled() { return g_node_ring_hs; }
-int set_node_ring_hs(int on) { return g_node_ring_hs.set(on); }
-hipError_t launch_node_ring_hs(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    LaunchCfg ls = lc;
-    ls.threads = 512;
-    ls.lds = (size_t)Rs::NB * Rs::BUF * 16 + (size_t)8 * 16384 + (size_t)T_COUNT * 128 * 4 + 64;
-    return launch_kernel(k_node_ring_hs, ls.blocks, ls.threads, ls.lds, s, a);
+hipError_t launch_node_split_h(const NodeArgs& a, int blocks, int threads, hipStream_t s) {
+    return launch_kernel(k_node_split_h, blocks, threads, NODE_SPLIT_LDS, s, a);
 }
-hipError_t launch_project_split_h(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    return launch_kernel(k_project_split_h, lc.blocks, lc.threads, lc.lds, s, a);
+hipError_t launch_node_ring_hs(const NodeArgs& a, int blocks, hipStream_t s) {
+    return launch_kernel(k_node_ring_hs, blocks, 512, (size_t)Rs::NB * Rs::BUF * 16 + (size_t)8 * 16384 + TABS_LDS, s, a);
 }
-hipError_t launch_project_split(const NodeArgs& a, const LaunchCfg& lc, hipStream_t s) {
-    return launch_kernel(k_project_split, lc.blocks, lc.threads, lc.lds, s, a);
+hipError_t launch_project_split_h(const NodeArgs& a, int blocks, int threads, hipStream_t s) {
+    return launch_kernel(k_project_split_h, blocks, threads, NODE_SPLIT_LDS, s, a);
+}
+hipError_t launch_project_split(const NodeArgs& a, int blocks, int threads, hipStream_t s) {
+    return launch_kernel(k_project_split, blocks, threads, NODE_SPLIT_LDS, s, a);
 }
 
 int split_prow_block() { return MGN_PROW_BLOCK; }

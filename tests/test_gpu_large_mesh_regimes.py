@@ -318,6 +318,33 @@ def test_fp32_mfma_cooperative_tiles(T_per_C, extra, tail):
     check(n_edge_case(C8), rows_of(T_per_C * C8 + extra, tail), C8, 3, 3, fp32_split=0, kernel_path=0)
 
 
+# The size thresholds of kernels.hip (struct Switches) that are constants, each with the smallest tile counts on both sides of it where the
+# cases above hold only one (the other side is then named in the key).  (node tiles, edge tiles, edge code, node codes, switches) at
+# C = 8; tails of 31 / 1 rows on the odd counts.
+F32 = dict(fp32_split=0)
+THRESHOLDS = {
+    "edge coop <= 16C": (2 * C8 + 1, 16 * C8, 3, 3, F32),
+    "edge coop > 16C: k_edge_step<4, 2>": (2 * C8 + 1, 16 * C8 + 1, 9, 3, F32),
+    "node coop <= 8C": (8 * C8, 2 * C8 + 1, 3, 3, F32),
+    "node coop > 8C: k_node_step": (8 * C8 + 1, 2 * C8 + 1, 3, 7, F32),
+    "fenced rings <= 4C": (4 * C8, 4 * C8, 3, 3, F32),
+    "no fence > 4C": (4 * C8 + 1, 4 * C8 + 1, 3, 3, F32),
+    "16-row node kernel behind 32-row edge tiles <= 2C (case 6: 2C + 1)": (2 * C8, 12 * C8, 17, 9, {}),
+    "k_edge_ring_hs takes over > 2C: not at 2C (case 1: 2C + 1)": (2 * C8 + 1, 2 * C8, 3, NODE_DEFAULT, {}),
+    "k_edge_ring_h takes over > 3C: not at 3C": (2 * C8 + 1, 3 * C8, 3, NODE_DEFAULT, dict(ringh_stream=0)),
+    "k_edge_ring_h takes over > 3C": (2 * C8 + 1, 3 * C8 + 1, 14, NODE_DEFAULT, dict(ringh_stream=0)),
+    "four waves <= 20C": (2 * C8 + 1, 20 * C8, 14, NODE_DEFAULT, dict(ringh_stream=0)),
+    "eight waves > 20C": (2 * C8 + 1, 20 * C8 + 1, 13, NODE_DEFAULT, dict(ringh_stream=0)),
+    "k_edge_ring_hs: eight waves at 12C + 1 (case 3: 12C)": (2 * C8 + 1, 12 * C8 + 1, 16, NODE_DEFAULT, {}),
+}
+
+
+@pytest.mark.parametrize("name", list(THRESHOLDS))
+def test_family_on_both_sides_of_every_size_threshold(name):
+    Tn, Te, edge_code, node_codes, sw = THRESHOLDS[name]
+    check(rows_of(Tn, 31 if Tn % 2 else 32), rows_of(Te, 1 if Te % 2 else 32), C8, edge_code, node_codes, **sw)
+
+
 def test_two_partitions_node_split_h_with_tile_offset():
     """case 12: two partitions of a 48 x 48 mesh in one process (loopback halo exchange), C = 8: 36 node tiles per part (1 152 on 256 CUs:
     36.9 k nodes per part).  Each part runs k_node_split_h (10) over its nodes and k_project_split_h twice, over the boundary tiles and,

@@ -58,8 +58,8 @@ def set_c16_row_tiles(rt):
 
 
 def set_fp32_split(on):
-    """Large fp32 launches: 1 = the split path (bf16 matrix cores at fp32 accuracy: the default), 2 / 3 = its other edge kernels,
-    0 = the fp32-MFMA kernels (tests only).  Returns the old value."""
+    """Large fp32 launches: 1 = the split path (16-bit matrix cores at fp32 accuracy: the default), 0 = the fp32-MFMA kernels (tests
+    only; any other value counts as 1).  Returns the old value."""
     lib = mgn_amd.load()
     lib.mgn_debug_fp32_split.restype = __import__("ctypes").c_int
     lib.mgn_debug_fp32_split.argtypes = [__import__("ctypes").c_int]

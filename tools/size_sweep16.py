@@ -21,7 +21,6 @@ for nx in (24, 32, 45, 64, 90, 128):
 print(out)
 ''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL = {"MGN_C16_EDGE_TILES_PER_CU": "99", "MGN_C16_NODE_TILES_PER_CU": "99"}
-for name, env in (("32-row cooperative (MGN_COOP16=0)", {"MGN_COOP16": "0"}), ("default thresholds", {}), ("16-row at every size", ALL),
-                  ("16-row at every size, RT=1 through the RT kernel", dict(ALL, MGN_C16_M1="1"))) * 2:
+for name, env in (("32-row cooperative (MGN_COOP16=0)", {"MGN_COOP16": "0"}), ("default thresholds", {}), ("16-row at every size", ALL)) * 2:
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True)
     print("%-50s" % name, r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-500:])
