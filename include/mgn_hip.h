@@ -263,10 +263,14 @@ int mgn_edge_features(const float* mesh_pos, int32_t pos_dim, const int32_t* sen
  *   one_hot(node_type, depth = type_max - type_min + 1, offset = 1 - type_min) and edge_features = [mesh_pos[s] - mesh_pos[r]; norm]
  *   are computed by kernels in engine order -- no [E][Fe] host array, no PCIe transfer of it -- then the edge encoder runs once, as
  *   in mgn_set_static; afterwards mgn_ode_step(x, NULL, NULL, NULL) / the resident fast path apply.  Needs Fn - O == depth, Fe == pos_dim + 1.
+ *   A node whose type lies outside [type_min, type_max] gets a one-hot row of zeros (no error; the reference's one_hot would throw).
  * mgn_world_edges_dev: the world-edge set `set` (>= 1) of a cloth-like mesh searched on the device (uniform grid, radix sort by cell)
  *   and installed WITHOUT a host round trip (what mgn_world_edges + mgn_set_edge_set do on the host; cloth rollouts re-search every
- *   step); with Fe2 == dim + 1 its features [rel world pos; norm] are written too.  One partition.  The same edges in the same
- *   order as mgn_world_edges (receiver-major, ascending senders).  mgn_edge_set_export hands the installed lists back (0-based). */
+ *   step); with Fe2 == dim + 1 its features [rel world pos; norm] are written too.  One partition.  The same edges as
+ *   mgn_world_edges, receiver-major with ascending senders IN THE ENGINE'S NODE NUMBERING: on a handle that mgn_set_graph did not
+ *   renumber that is mgn_world_edges' order entry for entry; on a renumbered handle (scattered node labels) the same SET of edges,
+ *   ordered by the engine's ids (position in mgn_owned_nodes) of receiver, then sender.  mgn_edge_set_export hands the installed lists
+ *   back in that order, in the caller's ids (0-based). */
 int mgn_triangles_to_edges_dev(mgn_handle* h, const int32_t* cells, int64_t n_cells, int32_t* senders, int32_t* receivers, int64_t capacity,
                                int64_t* n_directed);
 int mgn_set_static_mesh(mgn_handle* h, const int32_t* node_type /* [N] */, int32_t type_min, int32_t type_max, const float* mesh_pos /* [N][pos_dim] */,

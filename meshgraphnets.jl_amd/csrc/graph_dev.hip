@@ -111,7 +111,11 @@ __global__ void k_cell_start(const uint32_t* __restrict__ cid_sorted, int32_t N,
 }
 // FILL = false: cnt[r] = number of world edges ending at r.  FILL = true: senders of r written at rowptr[r].., ascending
 // (the cells are visited in the host version's order, the candidates of a receiver then sorted: here by insertion, lists are short).
-// Distances in double (exact differences and products of floats): no dependence on fma contraction -> the host's decisions.
+// Distances in double.  The difference of two floats is exact there only while their exponents differ by less than 30, and its
+// square only while the difference has at most 26 significant bits (coordinates of similar magnitude; 100.0 and 0.001 are not): in
+// general d2 is a rounded sum of rounded products.  The accumulation is therefore compiled with contraction OFF, so that every
+// product and every sum rounds once, as in the host version (csrc/graph_prologue.cpp): the host's decisions by construction, not
+// by the inputs.
 template <bool FILL>
 __global__ void k_world_search(const float* __restrict__ pos, Grid g, int32_t N, double r2, const int32_t* __restrict__ start,
                                const uint32_t* __restrict__ order, const int32_t* __restrict__ mesh_rowptr, const int32_t* __restrict__ mesh_snd,
@@ -133,9 +137,12 @@ __global__ void k_world_search(const float* __restrict__ pos, Grid g, int32_t N,
                     const int32_t s_ = (int32_t)order[p];
                     if (s_ == r) continue;
                     double d2 = 0.0;
-                    for (int d = 0; d < g.dim; ++d) {
-                        const double dd = (double)pos[(int64_t)s_ * g.dim + d] - (double)pr[d];
-                        d2 += dd * dd;
+                    {
+#pragma clang fp contract(off)
+                        for (int d = 0; d < g.dim; ++d) {
+                            const double dd = (double)pos[(int64_t)s_ * g.dim + d] - (double)pr[d];
+                            d2 += dd * dd;
+                        }
                     }
                     if (!(d2 < r2)) continue;
                     bool mesh = false;

@@ -105,8 +105,11 @@ int mgn_world_edges(const float* world_pos, int32_t dim, int32_t N, float radius
         std::vector<int32_t> cur(mrp.begin(), mrp.end() - 1);
         for (int64_t e = 0; e < n_mesh; ++e) msnd[cur[mesh_receivers[e] - index_base]++] = mesh_senders[e] - index_base;
     }
-    // distances in double: differences and products of floats are exact there, so the decision d2 < r2 does not depend on how a
-    // compiler contracts the sum (the device version, csrc/graph_dev.hip, takes the same decisions bit for bit)
+    // distances in double: the difference of two floats is exact there while their exponents differ by less than 30, its square
+    // only while the difference has at most 26 significant bits (coordinates of similar magnitude); otherwise the products round,
+    // and a contracted d2 += dd * dd would round differently.  The x86-64 baseline this file is compiled for has no fused
+    // multiply-add, and the device version (csrc/graph_dev.hip) turns contraction off for the same loop: every product and every
+    // sum rounds once on both sides, the same decisions bit for bit.
     const double r2 = (double)radius * (double)radius;
     int64_t count = 0;
     std::vector<int32_t> cand;
