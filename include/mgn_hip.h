@@ -290,17 +290,23 @@ int mgn_feature_stats(mgn_handle* h, const float* x, int64_t rows, int32_t dim, 
  * ode_func_eval (inflow overwrite from `inflow_data[floor(t / saves_dt)]`, src/solve.jl:151-152 -- see inflow_rule --, applied IN PLACE to
  * the array the RHS is evaluated on, like the reference) -> ode_step (mgn_ode_step semantics).  No host round trip
  * per RHS; one small D2H (error norm) per adaptive step.  Normalisers must be set with mgn_set_norms.
+ * MGN_SOLVER_TSIT5_FIXED is solve(prob, Tsit5(); adaptive = false, dt = dt, saveat = saves): the time grid, stage times and dense saves
+ * of step mode 2 of mgn_solver_grad_tsit5 (below; the same time loop runs both), in the evaluation form -- the state, the stage inputs
+ * and x_{n+1} each take, in place, the inflow rows of the frame of the time their stage sees (stage sum and rows are one launch); save 0
+ * is x0 untouched.  dt <= 0 is MGN_E_ARG before any launch; abstol / reltol are ignored.  No error norm: no D2H and, on partitions, no
+ * reduction per step.  On return n_accept is the number of steps, n_reject 0, n_rhs = 1 + 6 n_accept.
+ * A solver value outside 0 .. 2 is MGN_E_ARG.
  * With nranks > 1 (after mgn_comm_init) every rank passes the GLOBAL arrays and integrates the rows it owns; the error norm of
  * the step controller is reduced over the ranks (the same bits everywhere: the same accept / reject decisions), the halo exchange
  * runs inside every right-hand side, and every rank returns the complete solution.  mgn_ode_step and mgn_set_static likewise
  * (global arrays in, complete dx/dt out on every rank). */
 typedef struct mgn_rollout_desc {
-    int32_t solver;          /* 0 = Euler fixed step, 1 = Tsit5 adaptive                                     */
+    int32_t solver;          /* mgn_solver: 0 = Euler fixed step, 1 = Tsit5 adaptive, 2 = Tsit5 fixed step   */
     float t0, t1;            /* integration interval                                                         */
-    float dt;                /* Euler: step; Tsit5: initial step (0 = automatic)                             */
+    float dt;                /* Euler, Tsit5 fixed step: the step (> 0); Tsit5 adaptive: initial step (0 = automatic) */
     float saves_dt;          /* spacing of the save points AND of the inflow_data frames                     */
     int32_t n_saves;         /* solution is stored at t0 + i*saves_dt, i = 0..n_saves-1                      */
-    float abstol, reltol;    /* Tsit5 only (OrdinaryDiffEq defaults: 1e-6, 1e-3)                             */
+    float abstol, reltol;    /* adaptive Tsit5 only (OrdinaryDiffEq defaults: 1e-6, 1e-3); solvers 0 and 2 ignore them */
     const float* x0;               /* [N][O]                                                                 */
     const float* node_type_onehot; /* [N][Fn-O]                                                              */
     const float* ef_raw;           /* [E][Fe]                                                                */
@@ -324,11 +330,17 @@ typedef struct mgn_rollout_desc {
     double t0_f64, t1_f64, dt_f64, saves_dt_f64;
 } mgn_rollout_desc;
 typedef enum mgn_inflow_rule { MGN_INFLOW_REFERENCE = 0, MGN_INFLOW_TOLERANT = 1 } mgn_inflow_rule;
+/* mgn_rollout_desc.solver.  The reference's `rollout` branches on dt alone (src/solve.jl:57-61): without dt it is
+ * solve(prob, solver; saveat = saves, tstops = saves) -- MGN_SOLVER_TSIT5 --, with dt it is solve(prob, solver; adaptive = false, dt = dt,
+ * saveat = saves) whatever the solver -- MGN_SOLVER_EULER, and for Tsit5 (`solver_valid_dt`, `eval_network(...; dt)`) MGN_SOLVER_TSIT5_FIXED.
+ * MGN_SOLVER_TSIT5_FIXED is served by mgn_rollout, mgn_rollout_eval and their group forms on every handle that serves MGN_SOLVER_TSIT5;
+ * the training entry points answer it as any value they do not know (MGN_E_ARG).                                                      */
+typedef enum mgn_solver { MGN_SOLVER_EULER = 0, MGN_SOLVER_TSIT5 = 1, MGN_SOLVER_TSIT5_FIXED = 2 } mgn_solver;
 int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d);
 
 /* ---- rollout with the errors reduced on the device: what _validation_step (reference src/strategies.jl:111-134, every strategy's
  * validation_step, run over every validation trajectory at every checkpoint of train_mgn!, src/MeshGraphNets.jl:404-467) and
- * eval_network! (:609-635) take from a rollout.  d is read exactly as mgn_rollout reads it (Euler or adaptive Tsit5, both time types,
+ * eval_network! (:609-635) take from a rollout.  d is read exactly as mgn_rollout reads it (Euler, adaptive or fixed-step Tsit5, both time types,
  * both inflow rules, the in-place inflow overwrite; the same launches in the same order), d->n_accept / n_reject / n_rhs are filled, and
  * d->out MAY BE NULL: then no [n_saves][N][O] buffer is held on the device and nothing of that size is downloaded.  With d->out given
  * the predicted saves are bit-identical to mgn_rollout's.  As each save i is produced it is compared with gt[i]:

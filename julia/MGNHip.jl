@@ -774,13 +774,17 @@ end
 `rollout` of src/solve.jl:42-68 on the device (mgn_rollout): the ODEProblem over `ode_func_eval` solved with fixed-step Euler
 (`dt` given: `solve(prob, solver; adaptive = false, dt = dt, saveat = saves)`) or adaptive Tsit5 (`dt === nothing`:
 `solve(prob, solver; saveat = saves, tstops = saves)`), no host round trip per right-hand side.  `solver` is `:Euler`, `:Tsit5` or
-an OrdinaryDiffEq algorithm object of those names.  The inflow frame of a right-hand side is the reference's own
+an OrdinaryDiffEq algorithm object of those names.  The reference's own branch (src/solve.jl:57-61) is on `dt` alone, whatever the
+solver: `fixed_step = true` is that branch for `:Tsit5` with a `dt` given (`adaptive = false, dt = dt`: fixed steps that need not divide
+the save spacing, saves from the dense output; MGN_SOLVER_TSIT5_FIXED); the default `false` keeps the results this function has always
+returned (adaptive Tsit5 with `dt` as its first step).  `:Euler` ignores it.  The inflow frame of a right-hand side is the reference's own
 `floor(Int, t / saves_dt) + 1` in the element type of `saves` (src/solve.jl:151; MGN_INFLOW_REFERENCE), `inflow_data` being
 (O x N x frames).  Needs frozen normalisers (freeze_norms!) and the trajectory's graph (set_trajectory_graph!).
 """
 function native_rollout(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
         val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
-        inflow_data::Union{Nothing, Array{Float32, 3}}, start, stop, dt, saves; abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false)
+        inflow_data::Union{Nothing, Array{Float32, 3}}, start, stop, dt, saves; abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false,
+        fixed_step = false)
     name = solver isa Symbol ? solver : nameof(typeof(solver))
     name in (:Euler, :Tsit5) || throw(ArgumentError("native_rollout drives Euler and Tsit5; got $name"))
     sync_params!(mgn, mgn.ps::Vector{Float32})
@@ -789,7 +793,7 @@ function native_rollout(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_typ
     out = Array{Float32, 3}(undef, O, N, ns)
     sdt = ns > 1 ? saves[2] - saves[1] : one(eltype(saves))
     f64 = eltype(saves) == Float64
-    d = MgnRolloutDesc(name == :Euler ? 0 : 1, start, stop, dt === nothing ? 0 : dt, sdt, ns, abstol, reltol,
+    d = MgnRolloutDesc(name == :Euler ? 0 : (fixed_step ? 2 : 1), start, stop, dt === nothing ? 0 : dt, sdt, ns, abstol, reltol,
         pointer(x0), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
         inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
         inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
@@ -995,12 +999,14 @@ end
 mean(...; dims = 2)` (O x saves, `eval_network!`'s `error[:, 1, :]`, Float64) and `val_loss = mean(mse_time[sel])` -- `sel` a vector
 of 1-based LINEAR indices into the O x N matrix, exactly what `error[mask]` does with the reference's vector of node indices
 (`nothing`: all elements).  Without `want_pred` the solution is neither kept on the device nor downloaded (`pred === nothing`).  Pass
-the same array as `gt` and `inflow_data` (validation: the ground truth is the inflow data) and it is uploaded once.
+the same array as `gt` and `inflow_data` (validation: the ground truth is the inflow data) and it is uploaded once.  `fixed_step`: as
+`native_rollout`'s.
 """
 function rollout_eval(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
         val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
         inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, start, stop, dt, saves;
-        sel::Union{Nothing, Vector{Int32}} = nothing, want_pred = false, abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false)
+        sel::Union{Nothing, Vector{Int32}} = nothing, want_pred = false, abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false,
+        fixed_step = false)
     name = solver isa Symbol ? solver : nameof(typeof(solver))
     name in (:Euler, :Tsit5) || throw(ArgumentError("rollout_eval drives Euler and Tsit5; got $name"))
     sync_params!(mgn, mgn.ps::Vector{Float32})
@@ -1011,7 +1017,7 @@ function rollout_eval(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_
     mse_time = Matrix{Float32}(undef, O, N)
     sdt = ns > 1 ? saves[2] - saves[1] : one(eltype(saves))
     f64 = eltype(saves) == Float64
-    d = MgnRolloutDesc(name == :Euler ? 0 : 1, start, stop, dt === nothing ? 0 : dt, sdt, ns, abstol, reltol,
+    d = MgnRolloutDesc(name == :Euler ? 0 : (fixed_step ? 2 : 1), start, stop, dt === nothing ? 0 : dt, sdt, ns, abstol, reltol,
         pointer(x0), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
         inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
         inflow_data === nothing ? 0 : size(inflow_data, 3), out === nothing ? Ptr{Float32}(C_NULL) : pointer(out), 0, 0, 0,
@@ -1033,16 +1039,18 @@ end
 one native call: the rollout from `gt[:, :, 1]` over the strategy's interval (`tstart:dt:tstop`; a strategy without one passes
 `sim_interval`), `error = mean((prediction - gt) .^ 2; dims = 3)` and `mean(error[mask])` on the device -- `mask` the reference's
 `Int32.(findall(...))`, indexing the matrix linearly as there.  `gt` (O x N x frames: `vcat` of the target fields) is the inflow data
-too.  The last two results are `nothing` unless `want_arrays` (train_mgn! keeps them for the first trajectory only).
+too.  The last two results are `nothing` unless `want_arrays` (train_mgn! keeps them for the first trajectory only).  `fixed_step =
+true` with a `solver_dt` is the reference's own call (`_validation_step` hands `solver_valid_dt` to `rollout`'s `adaptive = false`
+branch); the default keeps the results this function has always returned.
 """
 function native_validation_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
         edge_features::Matrix{Float32}, mask::Vector{Int32}, val_mask_row::Union{Nothing, Vector{Float32}},
         inflow_mask_row::Union{Nothing, Vector{UInt8}}, solver, solver_dt;
-        sim_interval = (strategy.tstart):(strategy.dt):(strategy.tstop), want_arrays = false)
+        sim_interval = (strategy.tstart):(strategy.dt):(strategy.tstop), want_arrays = false, fixed_step = false)
     ns = length(sim_interval)
     loss, _, _, pred, _ = rollout_eval(solver, mgn, gt[:, :, 1], node_type_onehot, edge_features, val_mask_row, inflow_mask_row,
         inflow_mask_row === nothing ? nothing : gt, gt, sim_interval[1], sim_interval[end], solver_dt, sim_interval;
-        sel = mask, want_pred = want_arrays)
+        sel = mask, want_pred = want_arrays, fixed_step = fixed_step && solver_dt !== nothing)
     return Float32(loss), want_arrays ? gt[:, :, 1:ns] : nothing, pred
 end
 

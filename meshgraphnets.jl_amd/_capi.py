@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libmgn_hip.so")
 MGN_DEVICE_NONE = -2
 MGN_OK, MGN_E_ARG, MGN_E_HIP, MGN_E_STATE, MGN_E_OOM, MGN_E_UNSUPPORTED, MGN_E_RCCL = 0, -1, -2, -3, -4, -5, -6
 MGN_TSIT5_ADAPTIVE, MGN_TSIT5_DENSE_SAVES = 1, 2     # mgn_solver_grad_opts.adaptive: a set of flags
+MGN_SOLVER_EULER, MGN_SOLVER_TSIT5, MGN_SOLVER_TSIT5_FIXED = 0, 1, 2     # mgn_rollout_desc.solver
 STATUS_NAMES = {0: "MGN_OK", -1: "MGN_E_ARG", -2: "MGN_E_HIP", -3: "MGN_E_STATE", -4: "MGN_E_OOM", -5: "MGN_E_UNSUPPORTED",
                 -6: "MGN_E_RCCL"}
 MGN_COMM_ID_BYTES = 128

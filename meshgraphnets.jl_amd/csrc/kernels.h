@@ -188,6 +188,10 @@ struct LinComb {            // sum_j c[j] * k[j]
 };
 hipError_t launch_lincomb(float* out, const float* u, const LinComb& lc, float dt, int64_t n, hipStream_t s);
 hipError_t launch_overwrite(float* x, const float* frame, const uint8_t* mask, int64_t N, int O, hipStream_t s);
+// launch_lincomb over N * O elements, then launch_overwrite, in one launch (frame and mask both null: launch_lincomb's bits alone);
+// out must not alias u or a k[j]
+hipError_t launch_tsit5_stage_input(float* out, const float* u, const LinComb& lc, float dt, const float* frame, const uint8_t* mask, int64_t N,
+                                    int O, hipStream_t s);
 int errnorm_partials();
 hipError_t launch_errnorm(const float* u, const float* unew, const LinComb& lc, float dt, float atol, float rtol, int64_t n,
                           double* partial, hipStream_t s);

@@ -2345,6 +2345,56 @@ __global__ void k_overwrite(float* __restrict__ x, const float* __restrict__ fra
     if (mask[i / O]) x[i] = frame[i];
 }
 
+// A stage input of fixed-step Tsit5 in the evaluation form, one launch: k_lincomb's element (the same fmaf chain, the same bits), then
+// k_overwrite's rows.  n = N * O elements: 16-byte accesses over the first nq quads (nq = n / 4 where the launcher finds every base
+// 16-byte aligned, else 0), scalar accesses over the 4 nq .. n - 1 that remain; both grid-stride.  A quad spans rows when O is not a
+// multiple of 4, so the mask is read per element and the frame's quad only where one of the four is marked.  frame / mask null: the
+// linear combination alone.  Memory-bound: lc.n + 1 arrays read (+ the marked rows of the frame), one written; no LDS, no cross-lane work.
+DEVINL float stage_elem(const LinComb& lc, float dt, float u, const float (&kv)[7]) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+        if (j < lc.n) s = fmaf(lc.c[j], kv[j], s);
+    return fmaf(dt, s, u);
+}
+__global__ __launch_bounds__(256) void k_tsit5_stage_input(float* __restrict__ out, const float* __restrict__ u, LinComb lc, float dt,
+                                                           const float* __restrict__ frame, const uint8_t* __restrict__ mask, int64_t n,
+                                                           int64_t nq, int O) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t q = tid; q < nq; q += stride) {
+        const f32x4 uv = reinterpret_cast<const f32x4*>(u)[q];
+        f32x4 kq[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) kq[j] = j < lc.n ? reinterpret_cast<const f32x4*>(lc.k[j])[q] : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float kv[7] = {kq[0][e], kq[1][e], kq[2][e], kq[3][e], kq[4][e], kq[5][e], kq[6][e]};
+            r[e] = stage_elem(lc, dt, uv[e], kv);
+        }
+        if (mask) {
+            bool m[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = mask[(4 * q + e) / O] != 0;
+            if (m[0] | m[1] | m[2] | m[3]) {
+                const f32x4 fv = reinterpret_cast<const f32x4*>(frame)[q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (m[e]) r[e] = fv[e];
+            }
+        }
+        reinterpret_cast<f32x4*>(out)[q] = r;
+    }
+    for (int64_t i = 4 * nq + tid; i < n; i += stride) {
+        float kv[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) kv[j] = j < lc.n ? lc.k[j][i] : 0.f;
+        const float v = stage_elem(lc, dt, u[i], kv);
+        out[i] = (mask && mask[i / O]) ? frame[i] : v;
+    }
+}
+
 // partial sums of ((dt * sum_j c[j] k[j]) / (atol + rtol * max(|u|, |unew|)))^2 : deterministic per-block partials
 __global__ void k_errnorm(const float* __restrict__ u, const float* __restrict__ unew, LinComb lc, float dt, float atol,
                           float rtol, int64_t n, double* __restrict__ partial) {
@@ -2374,6 +2424,20 @@ hipError_t launch_lincomb(float* out, const float* u, const LinComb& lc, float d
 hipError_t launch_overwrite(float* x, const float* frame, const uint8_t* mask, int64_t N, int O, hipStream_t s) {
     if (N <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_overwrite, dim3((unsigned)((N * O + 255) / 256)), dim3(256), 0, s, x, frame, mask, N, O);
+    return hipGetLastError();
+}
+hipError_t launch_tsit5_stage_input(float* out, const float* u, const LinComb& lc, float dt, const float* frame, const uint8_t* mask, int64_t N,
+                                    int O, hipStream_t s) {
+    const int64_t n = N * O;
+    if (n <= 0) return hipSuccess;
+    if ((frame != nullptr) != (mask != nullptr) || lc.n < 0 || lc.n > 7) return hipErrorInvalidValue;
+    // 16-byte accesses need 16-byte aligned bases: the solve's arrays are, frame f of an [n_frames][n] array only when f n is a multiple of 4
+    uintptr_t bases = reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(frame);
+    for (int j = 0; j < lc.n; ++j) bases |= reinterpret_cast<uintptr_t>(lc.k[j]);
+    const int64_t nq = (bases & 15) == 0 ? n >> 2 : 0;
+    int64_t blocks = (std::max(nq, n - 4 * nq) + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;           // 8 blocks per CU, grid-stride above
+    hipLaunchKernelGGL(k_tsit5_stage_input, dim3((unsigned)blocks), dim3(256), 0, s, out, u, lc, dt, frame, mask, n, nq, O);
     return hipGetLastError();
 }
 int errnorm_partials() { return 64; }

@@ -187,11 +187,13 @@ struct Rollout {
     int64_t ftab_ld = 0, win_rows = 0;
 
     // f(x, t): in-place inflow overwrite of x, then dx/dt -> kout    (ode_func_eval, reference src/solve.jl:147-158)
-    int rhs(float* x, double t, float* kout) {
+    // written: x already holds the inflow rows of t's frame (launch_tsit5_stage_input wrote them with the stage sum)
+    int rhs(float* x, double t, float* kout, bool written = false) {
         const mgn_config& c = h->cfg;
-        if (mask && frames && ftab) {
+        const bool overwrite = mask && frames && !written;
+        if (overwrite && ftab) {
             HIPCHK(h, launch_shoot_overwrite(x, frames, mask, ftab + (size_t)n_rhs * ftab_ld, win_rows, c.O, nrows, h->stream));
-        } else if (mask && frames) {
+        } else if (overwrite) {
             int64_t fr;
             if (int rc = frame_index(t, &fr)) return rc;
             HIPCHK(h, launch_overwrite(x, frames + (size_t)fr * n, mask, nrows, c.O, h->stream));
@@ -244,13 +246,18 @@ struct Rollout {
     // engine's order, acc [n] doubles, part [n_saves][save_error_blocks(nrows)][O] -- and kept only if the caller wants the solution
     const float* ev_gt = nullptr;
     double *ev_acc = nullptr, *ev_part = nullptr;
+    // mgn_rollout_eval: save number `saved`, held in x, against its ground-truth frame
+    int save_error(const float* x) {
+        if (ev_gt)
+            HIPCHK(h, launch_save_error(x, ev_gt + (size_t)saved * n, ev_acc, ev_part + (size_t)saved * save_error_blocks(nrows) * h->cfg.O, nrows,
+                                        h->cfg.O, h->stream));
+        return MGN_OK;
+    }
     // saves[saved] <- u, the state after steps_done accepted steps
     int save(int64_t steps_done) {
         save_step.push_back(steps_done);
         save_theta.push_back(-1.0);
-        if (ev_gt)
-            HIPCHK(h, launch_save_error(u, ev_gt + (size_t)saved * n, ev_acc, ev_part + (size_t)saved * save_error_blocks(nrows) * h->cfg.O, nrows,
-                                        h->cfg.O, h->stream));
+        if (int rc = save_error(u)) return rc;
         if (saves) HIPCHK(h, hipMemcpyAsync(saves + (size_t)saved * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         ++saved;
         return MGN_OK;
@@ -259,7 +266,9 @@ struct Rollout {
     static bool hits(double ts, double tn) { return ts <= tn && std::fabs(ts - tn) <= 1e-9 * std::fabs(tn) + 1e-12; }
     // dense saves: the pending saves strictly inside the accepted trial of step nstep from t to tn with size hstep, before tsit5_advance
     // (u = x_n, k[0 .. 6] = k_{n,1 .. 7}): saves[saved] <- x_n + hstep sum_i b_i(theta) k_{n,i}, theta = (ts - t) / hstep formed in double
-    // from the time-type values (at most 1: tn is rounded), the weights rounded to float once
+    // from the time-type values (at most 1: tn is rounded), the weights rounded to float once.  The interpolant is formed once, in the save's
+    // slot or -- mgn_rollout_eval without d->out -- in utmp (the stage-6 input, free once k6 exists), and reduced from there as save()
+    // reduces the state: the error outputs are the same bits with and without a solution buffer
     int saves_inside(int64_t nstep, double t, double hstep, double tn) {
         while (saved < d->n_saves) {
             const double ts = tg.stop_time(saved);
@@ -269,7 +278,9 @@ struct Rollout {
             if (mgn_tsit5_interp_weights(theta, b) != MGN_OK) return fail(h, MGN_E_STATE, "dense save %d: theta = %g", saved, theta);
             LinComb lc{7, {}, {}};
             for (int j = 0; j < 7; ++j) { lc.c[j] = (float)b[j]; lc.k[j] = k[j]; }
-            HIPCHK(h, launch_lincomb(saves + (size_t)saved * n, u, lc, (float)hstep, n, h->stream));
+            float* xs = saves ? saves + (size_t)saved * n : utmp;
+            HIPCHK(h, launch_lincomb(xs, u, lc, (float)hstep, n, h->stream));
+            if (int rc = save_error(xs)) return rc;
             save_step.push_back(nstep);
             save_theta.push_back(theta);
             ++saved;
@@ -366,15 +377,30 @@ struct Rollout {
         return MGN_OK;
     }
     // one trial step from (u, k1) over hstep: stages 2 .. 6 at tt(t + tt(c_i hstep)), unew = u + hstep sum_j A[7][j] k_j, and k7 = f(unew)
-    // at t7 (FSAL); EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H
+    // at t7 (FSAL); EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H.
+    // fused_input (mgn_rollout's fixed-step Tsit5): the stage sum and the in-place inflow rows of its stage time in one launch
+    // (launch_tsit5_stage_input: launch_lincomb's bits, then launch_overwrite's rows) where the other loops issue two
+    bool fused_input = false;
     int tsit5_trial(double t, double hstep, double t7, double* EEst) {
         for (int sidx = 1; sidx < 7; ++sidx) {     // stages 2..7; stage 7 is evaluated on unew (FSAL)
             LinComb lc{sidx, {}, {}};
             for (int j = 0; j < sidx; ++j) { lc.c[j] = (float)TS_A[sidx][j]; lc.k[j] = k[j]; }
             float* dst = (sidx == 6) ? unew : utmp;
+            const double ts = sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep));
+            if (fused_input) {
+                const float* fr = nullptr;
+                if (mask && frames) {
+                    int64_t f;
+                    if (int rc = frame_index(ts, &f)) return rc;
+                    fr = frames + (size_t)f * n;
+                }
+                HIPCHK(h, launch_tsit5_stage_input(dst, u, lc, (float)hstep, fr, fr ? mask : nullptr, nrows, h->cfg.O, h->stream));
+                if (int rc = rhs(dst, ts, k[sidx], true)) return rc;
+                continue;
+            }
             HIPCHK(h, launch_lincomb(dst, u, lc, (float)hstep, n, h->stream));
             float* z = (sidx == 6) ? z7 : zs;
-            if (int rc = eval(dst, z, sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep)), k[sidx])) return rc;
+            if (int rc = eval(dst, z, ts, k[sidx])) return rc;
             if (sidx < 6 && kept)
                 HIPCHK(h, hipMemcpyAsync(kept + (size_t)sidx * n, rhs_input(dst, z), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         }
@@ -421,8 +447,10 @@ struct Rollout {
 
     // fixed steps with dense saves, solve(...; adaptive = false, dt, saveat = saves): t <- tt(t + dt) with h = dt until t1; a step whose
     // end lies within 1e-5 saves_dt of t1 snaps onto it (TimeGrid::next's rule), one that would pass t1 is cut to h = tt(t1 - t).  dt
-    // need not divide saves_dt; the saves are interpolated (saves_inside) or sit on a step's end
-    int tsit5_fixed_dense(const Slot& slot) {
+    // need not divide saves_dt; the saves are interpolated (saves_inside) or sit on a step's end.  One loop for mode 2 of
+    // mgn_solver_grad_tsit5 (slot: the training form, every step's stage inputs and record kept) and solver MGN_SOLVER_TSIT5_FIXED of
+    // mgn_rollout (no slot: the evaluation form, nothing stored)
+    int tsit5_fixed_dense(const Slot* slot) {
         double t = tg.t0;
         if (int rc = save(0)) return rc;
         if (int rc = tsit5_first(t)) return rc;
@@ -431,11 +459,12 @@ struct Rollout {
             double hstep = tg.dt, tn = tt(t + tg.dt);
             if (std::fabs(tn - tg.t1) <= 1e-5 * tg.sdt) tn = tg.t1;
             else if (tn > tg.t1) { hstep = tt(tg.t1 - t); tn = tg.t1; }
-            if (int rc = begin_trial(slot, nacc)) return rc;
+            if (slot)
+                if (int rc = begin_trial(*slot, nacc)) return rc;
             if (int rc = tsit5_trial(t, hstep, tn, nullptr)) return rc;
             if (int rc = saves_inside(nacc, t, hstep, tn)) return rc;
             tsit5_advance();
-            step_t.push_back(t); step_h.push_back(hstep);
+            if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
             t = tn;
             ++nacc;
             ++d->n_accept;
@@ -645,10 +674,12 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     if (int rc = solver_static_checks(h, d, who)) return rc;
     const TimeGrid T(d);
     if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (d->solver == 0 && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
+    if (d->solver == MGN_SOLVER_EULER && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
+    if (d->solver == MGN_SOLVER_TSIT5_FIXED && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
     if (int rc = inflow_checks(h, d, who)) return rc;
-    if (d->solver != 0 && d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler) or 1 (Tsit5)", who);
-    if (d->solver == 1 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+    if (d->solver < MGN_SOLVER_EULER || d->solver > MGN_SOLVER_TSIT5_FIXED)
+        return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler), 1 (Tsit5) or 2 (Tsit5 with fixed steps)", who);
+    if (d->solver == MGN_SOLVER_TSIT5 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
     const LocalGraph& g = h->g;
     invalidate_static(h);
     const int32_t nloc = part ? g.n_own : g.N;        // rows of the state this handle integrates
@@ -714,7 +745,9 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     }
 
     d->n_accept = d->n_reject = 0;
-    if (int rc = d->solver == 0 ? R.euler_rollout() : R.tsit5_adaptive(who, nullptr)) return rc;
+    R.fused_input = d->solver == MGN_SOLVER_TSIT5_FIXED;
+    if (int rc = d->solver == MGN_SOLVER_EULER ? R.euler_rollout() : d->solver == MGN_SOLVER_TSIT5 ? R.tsit5_adaptive(who, nullptr) : R.tsit5_fixed_dense(nullptr))
+        return rc;
     if (part) {     // every rank returns the complete solution (mgn_rollout_eval without d->out: none is kept)
         for (int i = 0; d->out && i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
@@ -971,7 +1004,7 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     d->n_accept = d->n_reject = 0;
     float* states = (float*)(base + o_st);
     R.dense = dense;
-    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(slot) : R.tsit5_fixed(K, plan, slot))
+    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(&slot) : R.tsit5_fixed(K, plan, slot))
         return rc;
     d->n_rhs = R.n_rhs;
     if (!euler) {

@@ -358,11 +358,14 @@ class Engine:
         return out
 
     def _rollout_desc(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data, abstol,
-                      reltol, inflow_rule, time_type):
-        """The descriptor of a rollout / rollout_eval call, without `out`; returns (d, the arrays it points into: inflow data last)."""
+                      reltol, inflow_rule, time_type, adaptive=True):
+        """The descriptor of a rollout / rollout_eval call, without `out`; returns (d, the arrays it points into: inflow data last).
+        adaptive=False with "Tsit5": fixed steps of dt (MGN_SOLVER_TSIT5_FIXED; the library refuses dt <= 0); "Euler" ignores it."""
         O, Fn = self.cfg.O, self.cfg.Fn
         d = _capi.MgnRolloutDesc()
-        d.solver = {"Euler": 0, "Tsit5": 1}[solver]
+        d.solver = {"Euler": _capi.MGN_SOLVER_EULER, "Tsit5": _capi.MGN_SOLVER_TSIT5}[solver]
+        if solver == "Tsit5" and not adaptive:
+            d.solver = _capi.MGN_SOLVER_TSIT5_FIXED
         d.t0, d.t1, d.dt, d.saves_dt, d.n_saves, d.abstol, d.reltol = t0, t1, dt, saves_dt, n_saves, abstol, reltol
         d.inflow_rule = {"reference": 0, "tolerant": 1}[inflow_rule]
         d.time_f64 = 1 if np.dtype(time_type) == np.float64 else 0
@@ -382,13 +385,16 @@ class Engine:
         return d, (x0, oh, ef, vm, im, idata)
 
     def rollout(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None,
-                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32):
+                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, adaptive=True):
         """Native device-side `rollout` (reference src/solve.jl:42-68).  solver: "Euler" (fixed dt) or "Tsit5".
+        adaptive: "Tsit5" only ("Euler" ignores it).  True: `solve(prob, Tsit5(); saveat = saves, tstops = saves)`, dt the first step.
+        False: `solve(prob, Tsit5(); adaptive = false, dt = dt, saveat = saves)` -- fixed steps of dt > 0 that need not divide
+        saves_dt, saves between step ends from Tsit5's dense output, no error norm (MGN_SOLVER_TSIT5_FIXED, include/mgn_hip.h).
         inflow_rule: "reference" = `floor(Int, t / saves_dt) + 1` in the solver's time type, no tolerance, out of range raises
         (src/solve.jl:151); "tolerant" = + 1e-3, clamped (step k reads frame k).  time_type: np.float32 (the example's `0.0f0:0.01f0:5.99f0`) or np.float64.
         Returns (sol_u [n_saves][N][O], stats dict)."""
         d, keep = self._rollout_desc(solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data,
-                                     abstol, reltol, inflow_rule, time_type)
+                                     abstol, reltol, inflow_rule, time_type, adaptive)
         out = np.zeros((n_saves, self.N, self.cfg.O), np.float32)
         d.out = f32(out)
         self._chk(self.lib.mgn_rollout(self.h, C.byref(d)))
@@ -397,7 +403,7 @@ class Engine:
 
     def rollout_eval(self, solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None, inflow_mask=None,
                      inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, sel=None, sel_index_base=0,
-                     want_pred=False, mse_time_out=None):
+                     want_pred=False, mse_time_out=None, adaptive=True):
         """`rollout` with the errors against gt [n_gt >= n_saves][N][O] reduced on the device (mgn_rollout_eval): what _validation_step
         (reference src/strategies.jl:111-134) and eval_network! (src/MeshGraphNets.jl:609-635) take from a rollout.  The solve is
         rollout's (same arguments, bit-identical saves); without want_pred the solution is neither kept on the device nor downloaded.
@@ -406,10 +412,10 @@ class Engine:
         with its vector of node indices is this, not "every component of node sel[i]"; None: all N * O elements.  mse_time_out: a
         NumPy array or device tensor [N][O] to receive mse_time (default: a new NumPy array).
         Returns {"val_loss": mean(mse_time[sel]), "mse_save" [n_saves][O] float64 (mean over the nodes), "mse_time" [N][O] float32
-        (mean over the saves), "pred" [n_saves][N][O] or None, "stats"}."""
+        (mean over the saves), "pred" [n_saves][N][O] or None, "stats"}.  adaptive: as rollout's."""
         O = self.cfg.O
         d, keep = self._rollout_desc(solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data,
-                                     abstol, reltol, inflow_rule, time_type)
+                                     abstol, reltol, inflow_rule, time_type, adaptive)
         e = _capi.MgnRolloutEvalDesc()
         if gt is inflow_data:                           # validation: the ground truth is the inflow data -- one array, one pointer
             gt_keep, e.gt, e.n_gt = keep[-1], d.inflow_data, d.n_frames
@@ -999,10 +1005,10 @@ class GroupEngine:
         return out
 
     def rollout(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None,
-                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32):
+                inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, adaptive=True):
         """Engine.rollout on the partitioned mesh: (sol_u [n_saves][N][O], stats)."""
         d, keep = Engine._rollout_desc(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask,
-                                       inflow_data, abstol, reltol, inflow_rule, time_type)
+                                       inflow_data, abstol, reltol, inflow_rule, time_type, adaptive)
         out = np.zeros((n_saves, self.N, self.cfg.O), np.float32)
         d.out = f32(out)
         self._chk(self.lib.mgn_group_rollout(self.g, C.byref(d)))
@@ -1135,13 +1141,13 @@ class GroupEngine:
 
     def rollout_eval(self, solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None, inflow_mask=None,
                      inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, sel=None, sel_index_base=0,
-                     want_pred=False, mse_time_out=None):
+                     want_pred=False, mse_time_out=None, adaptive=True):
         """Engine.rollout_eval on the partitioned mesh (mgn_group_rollout_eval): sel indexes the whole mesh's [N][O]; val_loss divides by
         len(sel) (N * O without sel), mse_save by N.  Without want_pred no rank keeps, gathers or downloads the solution."""
         self._host_arrays(gt=gt, mse_time_out=mse_time_out)
         return Engine.rollout_eval(_GroupCalls(self), solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, val_mask,
                                    inflow_mask, inflow_data, abstol, reltol, inflow_rule, time_type, sel, sel_index_base, want_pred,
-                                   mse_time_out)
+                                   mse_time_out, adaptive)
 
     def datapoint_export(self, t, normalised=True):
         """(nf [N][Fn], ef [E][Fe], target [N][O]) of datapoint t for the whole mesh: every rank writes the rows it owns."""

@@ -617,15 +617,24 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
     return gs_sum, loss_sum
 
 
+def _fixed_step_kw(fixed_step, solver, step):
+    """rollout_eval's extra keywords for the reference's `adaptive = false, dt = dt` branch: Tsit5 with a step given, when asked for"""
+    return {"adaptive": False} if (fixed_step and solver == "Tsit5" and step) else {}
+
+
 def validation_step(eng, data_gt, node_type_onehot, ef_raw, sim_interval, mask, solver="Tsit5", solver_dt=None, val_mask=None,
                     inflow_mask=None, mask_index_base=0, time_type=F32, inflow_rule="reference", abstol=1e-6, reltol=1e-3,
-                    want_arrays=False):
+                    want_arrays=False, fixed_step=False):
     """_validation_step (reference src/strategies.jl:111-134; every strategy's validation_step) in one native call, Engine.rollout_eval:
     a rollout from data_gt[0] over sim_interval = (tstart, dt, tstop) saved at tstart:dt:tstop, `error = mean((prediction - gt) .^ 2;
     dims = 3)` and `mean(error[mask])` -- reduced on the device, the solution downloaded only with want_arrays.  data_gt [T][N][O]: the
     trajectory's target fields (T >= the number of saves); with an inflow_mask [N] it is the inflow data too, and is uploaded once.
     mask: the reference's vector of node indices (mask_index_base 0, or 1 as in Julia).  Indexing the O x N matrix `error` with it is
     LINEAR indexing: it selects the elements mask[i] of the [N][O] array, not the rows -- reproduced as it is.
+    fixed_step: the reference's own branch on dt (src/solve.jl:57-61) is fixed_step=True whenever a step is given -- `solve(prob, solver;
+    adaptive = false, dt = dt, saveat = saves)` whatever the solver, which is how _validation_step hands `solver_valid_dt` on.  With
+    solver="Tsit5" and a solver_dt it passes adaptive=False (fixed steps of solver_dt, saves from the dense output); "Euler" steps that way
+    already.  The default False is kept for the results this function has always returned: adaptive Tsit5 with solver_dt as its first step.
     Returns (loss, None, None) or, with want_arrays, (loss, gt [n_saves][N][O], prediction [n_saves][N][O])."""
     tstart, dt, tstop = sim_interval
     n_saves = _range_length(tstart, dt, tstop)
@@ -634,26 +643,30 @@ def validation_step(eng, data_gt, node_type_onehot, ef_raw, sim_interval, mask, 
     r = eng.rollout_eval(solver, np.asarray(data_gt[0]), node_type_onehot, ef_raw, data_gt, tstart, _range_at(tstart, dt, n_saves - 1, time_type),
                          dt, n_saves, dt=solver_dt or 0.0, val_mask=val_mask, inflow_mask=inflow_mask,
                          inflow_data=data_gt if inflow_mask is not None else None, abstol=abstol, reltol=reltol, inflow_rule=inflow_rule,
-                         time_type=time_type, sel=np.asarray(mask, np.int32), sel_index_base=mask_index_base, want_pred=want_arrays)
+                         time_type=time_type, sel=np.asarray(mask, np.int32), sel_index_base=mask_index_base, want_pred=want_arrays,
+                         **_fixed_step_kw(fixed_step, solver, solver_dt))
     if not want_arrays:
         return r["val_loss"], None, None
     return r["val_loss"], np.asarray(data_gt[:n_saves]), r["pred"]
 
 
 def rollout_errors(eng, data_gt, node_type_onehot, ef_raw, start, stop, dt, saves, mse_steps, solver="Tsit5", val_mask=None, inflow_mask=None,
-                   time_type=F32, inflow_rule="reference", abstol=1e-6, reltol=1e-3):
+                   time_type=F32, inflow_rule="reference", abstol=1e-6, reltol=1e-3, fixed_step=False):
     """The error table of eval_network! (reference src/MeshGraphNets.jl:609-628) without the solution leaving the device: a rollout
     from data_gt[0] over (start, stop) saved at `saves` (evenly spaced times from `start`), `error = mean((prediction - gt) .^ 2;
     dims = 2)` as Engine.rollout_eval's mse_save, and for every horizon of mse_steps
         mse = mean(error[:, 1, k]),  cum_mse = mean(error[:, 1, 1:k]),  cum_rmse = sqrt(cum_mse),   k = findfirst(==(horizon), saves).
-    dt: the fixed solver step, or None (adaptive Tsit5), as eval_network!'s.  Returns (error [n_saves][O] float64, {horizon: (mse,
+    dt: the fixed solver step, or None (adaptive Tsit5), as eval_network!'s.  fixed_step: the reference's own branch on dt
+    (src/solve.jl:57-61) is fixed_step=True whenever a step is given (`adaptive = false, dt = dt` whatever the solver); with solver="Tsit5"
+    and a dt it passes adaptive=False.  The default False is kept for the results this function has always returned (adaptive Tsit5
+    with dt as its first step).  Returns (error [n_saves][O] float64, {horizon: (mse,
     cum_mse, cum_rmse)})."""
     saves = np.asarray(saves, dtype=time_type)
     n_saves = int(saves.size)
     saves_dt = float(saves[1] - saves[0]) if n_saves > 1 else float(stop - start) or 1.0
     r = eng.rollout_eval(solver, np.asarray(data_gt[0]), node_type_onehot, ef_raw, data_gt, start, stop, saves_dt, n_saves, dt=dt or 0.0,
                          val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=data_gt if inflow_mask is not None else None,
-                         abstol=abstol, reltol=reltol, inflow_rule=inflow_rule, time_type=time_type)
+                         abstol=abstol, reltol=reltol, inflow_rule=inflow_rule, time_type=time_type, **_fixed_step_kw(fixed_step, solver, dt))
     error = r["mse_save"]
     table = {}
     for horizon in mse_steps:
