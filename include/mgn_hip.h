@@ -374,6 +374,55 @@ typedef struct mgn_rollout_eval_desc {
 } mgn_rollout_eval_desc;
 int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e);
 
+/* ---- explicit Runge-Kutta by tableau: the reference types every solver argument as OrdinaryDiffEqAlgorithm (`solver_valid`, the
+ * `solver` of eval_network, src/MeshGraphNets.jl:53), so RK4(), BS3(), DP5(), Heun() or Midpoint() may arrive.  A Butcher tableau is
+ * DATA here: a flat array of MGN_ERK_TABLEAU_DOUBLES doubles, filled by mgn_erk_named or by the caller, checked by mgn_erk_check, and
+ * handed to the *_erk entry points below, which drive the same resident right-hand side, saves, error reduction, controller and
+ * partitions as mgn_rollout.  Up to MGN_ERK_MAX_STAGES stages; host only, no handle.
+ *   tab[0] stages s (1..7)   tab[1] order p (>= 1)   tab[2] fsal (0/1)   tab[3] embedded (0/1)
+ *   tab[4] beta1  tab[5] beta2  (PI controller; 0, 0 = the defaults 7/(10 p), 2/(5 p))
+ *   tab[6 + 7 i + j] = A[i][j], 0-based, used for j < i      tab[55 + i] = b[i]
+ *   tab[62 + i] = c[i]      tab[69 + i] = btilde[i] = b[i] - bhat[i]  (embedded only)
+ * mgn_erk_check answers MGN_E_ARG for: a NULL tab; stages outside 1..7; a non-integral header entry (stages, order, fsal, embedded);
+ * anything non-finite; a non-zero A[i][j] with j >= i inside the s x s block; |sum b - 1| > 1e-10; order < 1; embedded with
+ * |sum btilde| > 1e-10; fsal without b[s-1] == 0, c[s-1] == 1 and A[s-1][j] == b[j] for all j (compared exactly); a negative beta.
+ * mgn_erk_named fills tab (zeros elsewhere) with a named method: Euler; Heun (OrdinaryDiffEq's explicit trapezoid), Midpoint, Ralston
+ * (p = 2); RK4 (the classical one); BS3 (Bogacki-Shampine 3(2), FSAL, embedded); DP5 (Dormand-Prince 5(4), FSAL, embedded, beta1 = 0.17,
+ * beta2 = 0.04); Tsit5 (the tableau MGN_SOLVER_TSIT5 drives: FSAL, embedded, the default betas 7/50 and 2/25).  MGN_E_ARG for a name
+ * outside the enum or a NULL tab.                                                                                                    */
+#define MGN_ERK_MAX_STAGES 7
+#define MGN_ERK_TABLEAU_DOUBLES 76
+typedef enum mgn_erk_name { MGN_ERK_EULER = 0, MGN_ERK_HEUN = 1, MGN_ERK_MIDPOINT = 2, MGN_ERK_RALSTON = 3,
+                            MGN_ERK_RK4 = 4, MGN_ERK_BS3 = 5, MGN_ERK_DP5 = 6, MGN_ERK_TSIT5 = 7 } mgn_erk_name;
+int mgn_erk_named(int32_t name, double* tab /* [MGN_ERK_TABLEAU_DOUBLES] */);
+int mgn_erk_check(const double* tab);   /* MGN_OK or MGN_E_ARG */
+
+/* mgn_rollout / mgn_rollout_eval with the method given by a tableau.  d is read as mgn_rollout reads it -- both time types, both inflow
+ * rules, the in-place inflow overwrite, d->out optional in the eval form, n_accept / n_reject / n_rhs filled -- except d->solver, which
+ * is ignored.  mgn_erk_check runs before anything else (a bad tableau is MGN_E_ARG on every handle, a host-only one included).
+ *   Stage input y_i = x_n + h sum_{j<i} A[i][j] k_j: coefficients rounded to float once, terms whose coefficient is exactly 0 left out,
+ *   the rest in ascending j through mgn_rollout's fmaf chain.  Stage 1 sees t_n; the FSAL stage (stage s of an FSAL tableau) is evaluated
+ *   on x_{n+1} and sees t_{n+1}; every other stage sees t_n + c_i h, each operation rounded to the time type.  Each right-hand side
+ *   overwrites the inflow rows of the array it is evaluated on, in place: with FSAL a saved x_{n+1} carries the rows of frame(t_{n+1});
+ *   without, the save is x_{n+1} as the update left it and stage 1 of the next step overwrites it (what MGN_SOLVER_EULER does).
+ *   FSAL: the last stage of an accepted step is k_1 of the next, n_rhs = 1 + (s - 1)(n_accept + n_reject).  Otherwise k_1 is evaluated
+ *   once per state that starts a step (a retrial reuses it), n_rhs = n_accept + (s - 1)(n_accept + n_reject).
+ * adaptive = 0: solve(prob, alg; adaptive = false, dt, saveat = saves).  dt > 0, else MGN_E_ARG.  K = round((t1 - t0) / dt) steps,
+ *   t <- t + dt in the time type (the last step snaps onto t1), every save must be reached.  A general tableau has no dense output here:
+ *   saves_dt / dt must be an integer >= 1 to within 1e-6 relative, else MGN_E_ARG (Tsit5 with other steps is MGN_SOLVER_TSIT5_FIXED).
+ *   abstol / reltol are ignored; no error norm: no D2H copy per step and, on partitions, no reduction per step.
+ * adaptive = 1: solve(prob, alg; saveat = saves, tstops = saves): MGN_SOLVER_TSIT5's loop -- stops, padding, the rank-reduced error norm,
+ *   the iteration guard -- with the tableau's stages and btilde, the PI controller's beta1 / beta2 from the tableau and the exponent 1/p
+ *   in the Hairer-Wanner start (d->dt == 0).  Needs an embedded pair, else MGN_E_UNSUPPORTED, and tolerances > 0, else MGN_E_ARG.
+ *   With mgn_erk_named's Tsit5 tableau the result is MGN_SOLVER_TSIT5's, bit for bit, counters included.
+ * Any other value of adaptive is MGN_E_ARG.  The group forms serve partitions as mgn_group_rollout / mgn_group_rollout_eval do.
+ * d->dt == 0 with adaptive = 1 costs one more right-hand side than the formulas above (the Hairer-Wanner start's probe), as it does
+ * for MGN_SOLVER_TSIT5.
+ * Not built: dense output for a general tableau; adaptive training, mgn_shooting_grad and a group form of mgn_solver_grad_erk with a
+ * tableau; implicit or stabilised methods; more than seven stages.                                                                     */
+int mgn_rollout_erk(mgn_handle* h, mgn_rollout_desc* d, const double* tab, int32_t adaptive);
+int mgn_rollout_eval_erk(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const double* tab, int32_t adaptive);
+
 /* ---- solver-based training: the loss and d loss / d ps of one fixed-step Euler solve of ode_func_train (reference src/solve.jl:101-117,
  * strategies.jl:175-196) -- what train_step(::SolverTraining) (strategies.jl:257-292) and one window of train_step(::MultipleShooting)
  * (:312-383) differentiate, with no host work per step and one synchronisation at the end.
@@ -474,6 +523,21 @@ typedef struct mgn_shooting_desc {
     int64_t max_batch_nodes;      /* 0: 1 << 20; a pass holds at most max(1, floor(this / N)) windows                                */
     int32_t n_groups, n_passes;   /* out                                                                                             */
 } mgn_shooting_desc;
+/* ---- mgn_solver_grad_tsit5's loss and gradient for an explicit Runge-Kutta tableau (mgn_erk_named / mgn_erk_check above): the `solver` of
+ * SolverTraining and MultipleShooting is any OrdinaryDiffEqAlgorithm (reference src/strategies.jl:242,316).  Arguments, host-or-device
+ * rules and refusals are mgn_solver_grad_tsit5's; d->solver is not read; mgn_erk_check runs before anything else.  Fixed steps only:
+ * o->adaptive must be 0, MGN_E_UNSUPPORTED otherwise.  The grid and saves are those of mgn_rollout_erk with adaptive = 0 (dt > 0,
+ * saves_dt / dt an integer >= 1, every save reached), the inflow overwrite takes the training form (copies; the state is never
+ * overwritten).  With s' = s - fsal active stages (s' <= 6, else MGN_E_UNSUPPORTED):
+ *   forward   z_{n,i} = x_n + h sum_{j<i} A[i][j] k_{n,j} with the inflow rows of frame(t_{n,i}), in a copy;  k_{n,i} = f(z_{n,i});
+ *             x_{n+1} = x_n + h sum_i b_i k_{n,i}
+ *   reverse   from lam = dL/dx_{n+1}, for i = s' .. 1:  kbar_i = h (b_i lam + sum_{j>i} A[j][i] ybar_j);  (zbar_i, g_i) = VJP at z_{n,i};
+ *             ybar_i = zbar_i with the inflow rows zeroed;  gs += g_i;  then dL/dx_n = lam + sum_i ybar_i + the save / continuity terms
+ * -- the exact gradient of the computed solution.  Stored: s' N O floats per step in the chunks mgn_solver_grad_tsit5 uses;
+ * max_store_bytes, stored_bytes, step_t, step_h and n_steps behave as there.  d->out is bit-identical to mgn_rollout_erk's solution
+ * where there is no inflow mask.  With mgn_erk_named's Tsit5 tableau: mgn_solver_grad_tsit5's bits in step mode 0.                       */
+int mgn_solver_grad_erk(mgn_handle* h, mgn_rollout_desc* d, const double* tab, mgn_solver_grad_opts* o, const float* gt,
+                        const float* loss_scale, const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss);
 int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, const float* gt /* [n_gt][N][O] */,
                       const float* loss_scale /* [O] or NULL */, float cont_weight, float* grads, size_t n_grads, float* loss);
 
@@ -780,6 +844,9 @@ int mgn_group_solver_grad(mgn_group* g, mgn_rollout_desc* d, const float* gt, co
 int mgn_group_solver_grad_tsit5(mgn_group* g, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
                                 const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss);
 int mgn_group_rollout_eval(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e);
+/* mgn_rollout_erk / mgn_rollout_eval_erk on the partitioned mesh: the same tableau and step mode on every rank, rank 0's counters back */
+int mgn_group_rollout_erk(mgn_group* g, mgn_rollout_desc* d, const double* tab, int32_t adaptive);
+int mgn_group_rollout_eval_erk(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const double* tab, int32_t adaptive);
 int mgn_group_latents_randn(mgn_group* g, uint64_t seed);
 int mgn_group_processor_steps_dev(mgn_group* g, int32_t nsteps);
 int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, double* sumsq_v, double* sumsq_e);

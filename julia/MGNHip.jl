@@ -29,7 +29,7 @@ export NormaliserOffline, NormaliserOfflineMinMax, NormaliserOfflineMeanStd, Nor
 export FeatureGraph, GraphNetwork, step!, load, save!, shooting_grad
 # engine extras (optional fast paths; none is needed for the drop-in)
 export set_trajectory_graph!, pack_params, init_params, set_norms!, freeze_norms!, set_static!, ode_step_resident, ode_step_fused,
-       native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, native_solver_train_step
+       native_rollout, ode_vjp, forward_vjp, feature_stats, solver_grad, solver_grad_tsit5, solver_grad_erk, native_solver_train_step
 export rollout_eval, native_validation_step
 export train_trajectory!, step_datapoint!, step_datapoints!, online_norms!, norm_state, norm_state!, datapoint_export
 export adam_init!, adam_update!, adam_state, adam_state!, set_params_dev!, get_params_dev!, resident_params!
@@ -767,6 +767,27 @@ function ode_vjp(mgn::GraphNetwork, x::Matrix{Float32}, node_type_onehot::Matrix
     return xbar, gs, dxdt
 end
 
+# ---- explicit Runge-Kutta by tableau (mgn_erk_named, the *_erk entry points): the reference types every solver argument as
+# OrdinaryDiffEqAlgorithm, so RK4(), BS3(), DP5(), Heun(), Midpoint() or Ralston() may arrive where Euler() and Tsit5() do
+const ERK_NAMES = (Euler = 0, Heun = 1, Midpoint = 2, Ralston = 3, RK4 = 4, BS3 = 5, DP5 = 6, Tsit5 = 7)
+const ERK_EMBEDDED = (:BS3, :DP5, :Tsit5)
+const ERK_TABLEAU_DOUBLES = 76
+
+"the flat tableau (include/mgn_hip.h, MGN_ERK_TABLEAU_DOUBLES) of a named method"
+function erk_named(name::Symbol)
+    haskey(ERK_NAMES, name) || throw(ArgumentError("no tableau named $name; the names are $(keys(ERK_NAMES))"))
+    tab = zeros(Float64, ERK_TABLEAU_DOUBLES)
+    rc = ccall((:mgn_erk_named, LIB), Cint, (Int32, Ptr{Float64}), Int32(ERK_NAMES[name]), tab)
+    rc == 0 || throw(ArgumentError("mgn_erk_named($name) returned $rc"))
+    ccall((:mgn_erk_check, LIB), Cint, (Ptr{Float64},), tab) == 0 || throw(ArgumentError("the tableau of $name does not pass mgn_erk_check"))
+    return tab
+end
+
+# the tableau a rollout of `name` goes through (nothing: Euler and Tsit5 keep mgn_rollout's own solvers), and its step mode: a method
+# with an embedded pair follows Tsit5's rule (adaptive unless fixed_step with a dt given), one without steps by dt
+erk_route(name::Symbol) = name in (:Euler, :Tsit5) ? nothing : erk_named(name)
+erk_adaptive(name::Symbol, dt, fixed_step) = Int32(name in ERK_EMBEDDED && !(fixed_step && dt !== nothing) ? 1 : 0)
+
 """
     native_rollout(solver, mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, start, stop, dt, saves)
         -> (sol_u::Vector{Matrix{Float32}}, sol_t)
@@ -780,13 +801,17 @@ the save spacing, saves from the dense output; MGN_SOLVER_TSIT5_FIXED); the defa
 returned (adaptive Tsit5 with `dt` as its first step).  `:Euler` ignores it.  The inflow frame of a right-hand side is the reference's own
 `floor(Int, t / saves_dt) + 1` in the element type of `saves` (src/solve.jl:151; MGN_INFLOW_REFERENCE), `inflow_data` being
 (O x N x frames).  Needs frozen normalisers (freeze_norms!) and the trajectory's graph (set_trajectory_graph!).
+`:Heun`, `:Midpoint`, `:Ralston`, `:RK4`, `:BS3`, `:DP5` (or the OrdinaryDiffEq objects of those names) go through mgn_rollout_erk with
+mgn_erk_named's tableau: `:BS3` and `:DP5` follow Tsit5's rule (adaptive unless `fixed_step` with a `dt`), the others step by `dt`;
+fixed steps of a tableau need `saves_dt / dt` integral.
 """
 function native_rollout(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
         val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
         inflow_data::Union{Nothing, Array{Float32, 3}}, start, stop, dt, saves; abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false,
         fixed_step = false)
     name = solver isa Symbol ? solver : nameof(typeof(solver))
-    name in (:Euler, :Tsit5) || throw(ArgumentError("native_rollout drives Euler and Tsit5; got $name"))
+    haskey(ERK_NAMES, name) || throw(ArgumentError("native_rollout drives Euler, Tsit5, Heun, Midpoint, Ralston, RK4, BS3 and DP5; got $name"))
+    erk = erk_route(name)
     sync_params!(mgn, mgn.ps::Vector{Float32})
     O, N = size(x0)
     ns = length(saves)
@@ -798,8 +823,14 @@ function native_rollout(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_typ
         inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
         inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
         start, stop, dt === nothing ? 0 : dt, sdt)
-    GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out check(mgn.handle,
-        ccall((:mgn_rollout, LIB), Cint, (Ptr{Cvoid}, Ref{MgnRolloutDesc}), mgn.handle, d))
+    if erk === nothing
+        GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out check(mgn.handle,
+            ccall((:mgn_rollout, LIB), Cint, (Ptr{Cvoid}, Ref{MgnRolloutDesc}), mgn.handle, d))
+    else      # (d.solver is not read)
+        GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out erk check(mgn.handle,
+            ccall((:mgn_rollout_erk, LIB), Cint, (Ptr{Cvoid}, Ref{MgnRolloutDesc}, Ptr{Float64}, Int32), mgn.handle, d, erk,
+                erk_adaptive(name, dt, fixed_step)))
+    end
     return [out[:, :, i] for i in 1:ns], collect(saves)
 end
 
@@ -894,6 +925,47 @@ function solver_grad_tsit5(mgn::GraphNetwork, x0::Matrix{Float32}, node_type_one
 end
 
 """
+    solver_grad_erk(name, mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, start, stop, dt, saves;
+                    loss_scale = nothing, cont_target = nothing, cont_weight = 0f0) -> (gs, loss, pred, step_t, step_h)
+
+`solver_grad_tsit5(...; adaptive = false)` for the explicit Runge-Kutta method `name` (`:Heun`, `:Midpoint`, `:Ralston`, `:RK4`, `:BS3`,
+`:DP5`; also `:Euler`, `:Tsit5`) through mgn_solver_grad_erk and mgn_erk_named's tableau: fixed steps of `dt` (the save spacing must be
+a whole number of them), the inflow rows written into copies, `gs` the exact discrete adjoint of the computed solution.
+"""
+function solver_grad_erk(name::Symbol, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
+        val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
+        inflow_data::Union{Nothing, Array{Float32, 3}}, gt::Array{Float32, 3}, start, stop, dt, saves;
+        loss_scale::Union{Nothing, Vector{Float32}} = nothing, cont_target::Union{Nothing, Matrix{Float32}} = nothing, cont_weight = 0.0f0,
+        tolerant_inflow = false)
+    erk = erk_named(name)
+    ps = mgn.ps::Vector{Float32}
+    sync_params!(mgn, ps)
+    O, N = size(x0)
+    ns = length(saves)
+    size(gt, 3) >= ns || throw(DimensionMismatch("gt has $(size(gt, 3)) frames, the solve saves $ns"))
+    g = Array{Float32, 3}(gt[:, :, 1:ns])
+    out = Array{Float32, 3}(undef, O, N, ns)
+    gs = Vector{Float32}(undef, length(ps))
+    loss = Ref{Float32}(0)
+    sdt = ns > 1 ? saves[2] - saves[1] : one(eltype(saves))
+    f64 = eltype(saves) == Float64
+    cap = round(Int, (stop - start) / dt) + 2
+    st = Vector{Float64}(undef, cap); sh = Vector{Float64}(undef, cap)
+    d = MgnRolloutDesc(0, start, stop, dt, sdt, ns, 0, 0,      # (solver and tolerances are not read)
+        pointer(x0), pointer(node_type_onehot), pointer(edge_features), opt_ptr(val_mask_row),
+        inflow_mask_row === nothing ? Ptr{UInt8}(C_NULL) : pointer(inflow_mask_row), inflow_data === nothing ? Ptr{Float32}(C_NULL) : pointer(inflow_data),
+        inflow_data === nothing ? 0 : size(inflow_data, 3), pointer(out), 0, 0, 0, tolerant_inflow ? 1 : 0, f64 ? 1 : 0,
+        start, stop, dt, sdt)
+    o = MgnSolverGradOpts(0, cap, pointer(st), pointer(sh), 0, 0, 0)
+    rc = GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out g loss_scale cont_target gs st sh erk @ccall LIB.mgn_solver_grad_erk(
+        mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, erk::Ptr{Float64}, o::Ref{MgnSolverGradOpts}, g::Ptr{Float32}, opt_ptr(loss_scale)::Ptr{Float32},
+        opt_ptr(cont_target)::Ptr{Float32}, Float32(cont_weight)::Float32, gs::Ptr{Float32}, length(gs)::Csize_t, loss::Ref{Float32})::Cint
+    check(mgn.handle, rc)
+    n = min(o.n_steps, cap)
+    return gs, loss[], out, st[1:n], sh[1:n]
+end
+
+"""
     shooting_grad(mgn, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, inflow_data, gt, ranges, tsteps, dt;
                   solver = :Euler, cont_weight = 0f0, max_windows_per_pass = 0) -> (gs, loss, pred::Array{Float32, 3})
 
@@ -945,7 +1017,8 @@ term of window i attached to window i - 1.  The Euler step is `solargs.dt` when 
 InterpolatingAdjoint's continuous approximation the reference defaults to.  Opt-in for `train_network`:
 `gs, loss = native_solver_train_step(strategy, mgn, gt, ...)` in place of `train_step(strategy, t)`.  `batched = true` routes a
 MultipleShooting strategy with Euler or fixed-step Tsit5 through `shooting_grad` (all windows in one call; the same sum); adaptive
-Tsit5 keeps the per-window loop.
+Tsit5 keeps the per-window loop.  A strategy whose solver is `Heun()`, `Midpoint()`, `Ralston()`, `RK4()`, `BS3()` or `DP5()` is served
+by `solver_grad_erk` window by window, with fixed steps (`BS3()` and `DP5()` need `adaptive = false` in the solargs).
 (Julia is not available where this shim is tested: its ccalls are checked against the header by tests/test_julia_shim.py.)
 """
 function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32, 3}, node_type_onehot::Matrix{Float32},
@@ -955,15 +1028,23 @@ function native_solver_train_step(strategy, mgn::GraphNetwork, gt::Array{Float32
     sname = nameof(typeof(strategy.solver))
     dense_saves && sname != :Tsit5 && throw(ArgumentError("dense_saves is Tsit5's dense output"))
     dense_saves && batched && throw(ArgumentError("dense_saves solves window by window: shooting_grad steps onto every save"))
-    sname in (:Euler, :Tsit5) || throw(ArgumentError("native_solver_train_step drives Euler() and Tsit5(); got $(strategy.solver)"))
+    haskey(ERK_NAMES, sname) || throw(ArgumentError("native_solver_train_step drives Euler(), Tsit5(), Heun(), Midpoint(), Ralston(), RK4(), BS3() and DP5(); got $(strategy.solver)"))
     tsteps = (strategy.tstart):(strategy.dt):(strategy.tstop)
     sargs = hasproperty(strategy, :solargs) ? strategy.solargs : (;)
+    by_tableau = !(sname in (:Euler, :Tsit5))      # mgn_solver_grad_erk: fixed steps only
+    by_tableau && sname in ERK_EMBEDDED && get(sargs, :adaptive, true) != false &&
+        throw(ArgumentError("native_solver_train_step trains $(sname)() with fixed steps: pass adaptive = false and dt in the strategy's solargs"))
+    by_tableau && batched && throw(ArgumentError("batched = true (shooting_grad) drives Euler() and Tsit5()"))
     adaptive = sname == :Tsit5 && get(sargs, :adaptive, true) != false
     dt = haskey(sargs, :dt) ? sargs[:dt] : (adaptive ? zero(strategy.dt) : strategy.dt)
     abstol = Float32(get(sargs, :abstol, 1e-6)); reltol = Float32(get(sargs, :reltol, 1e-3))
     im = inflow_mask_row === nothing ? nothing : inflow_data
     function window(x0, g, t0, t1, saves; kw...)
         sname == :Euler && return solver_grad(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, dt, saves; kw...)
+        if by_tableau
+            gs, loss, pred, _, _ = solver_grad_erk(sname, mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, dt, saves; kw...)
+            return gs, loss, pred
+        end
         gs, loss, pred, _, _ = solver_grad_tsit5(mgn, x0, node_type_onehot, edge_features, val_mask_row, inflow_mask_row, im, g, t0, t1, saves;
             dt = dt, adaptive = adaptive, dense_saves = dense_saves, abstol = abstol, reltol = reltol, kw...)
         return gs, loss, pred
@@ -999,8 +1080,8 @@ end
 mean(...; dims = 2)` (O x saves, `eval_network!`'s `error[:, 1, :]`, Float64) and `val_loss = mean(mse_time[sel])` -- `sel` a vector
 of 1-based LINEAR indices into the O x N matrix, exactly what `error[mask]` does with the reference's vector of node indices
 (`nothing`: all elements).  Without `want_pred` the solution is neither kept on the device nor downloaded (`pred === nothing`).  Pass
-the same array as `gt` and `inflow_data` (validation: the ground truth is the inflow data) and it is uploaded once.  `fixed_step`: as
-`native_rollout`'s.
+the same array as `gt` and `inflow_data` (validation: the ground truth is the inflow data) and it is uploaded once.  `solver` (the
+tableau names included, through mgn_rollout_eval_erk) and `fixed_step`: as `native_rollout`'s.
 """
 function rollout_eval(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_onehot::Matrix{Float32}, edge_features::Matrix{Float32},
         val_mask_row::Union{Nothing, Vector{Float32}}, inflow_mask_row::Union{Nothing, Vector{UInt8}},
@@ -1008,7 +1089,8 @@ function rollout_eval(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_
         sel::Union{Nothing, Vector{Int32}} = nothing, want_pred = false, abstol = 1.0f-6, reltol = 1.0f-3, tolerant_inflow = false,
         fixed_step = false)
     name = solver isa Symbol ? solver : nameof(typeof(solver))
-    name in (:Euler, :Tsit5) || throw(ArgumentError("rollout_eval drives Euler and Tsit5; got $name"))
+    haskey(ERK_NAMES, name) || throw(ArgumentError("rollout_eval drives Euler, Tsit5, Heun, Midpoint, Ralston, RK4, BS3 and DP5; got $name"))
+    erk = erk_route(name)
     sync_params!(mgn, mgn.ps::Vector{Float32})
     O, N = size(x0)
     ns = length(saves)
@@ -1025,8 +1107,14 @@ function rollout_eval(solver, mgn::GraphNetwork, x0::Matrix{Float32}, node_type_
     e = MgnRolloutEvalDesc(pointer(gt), size(gt, 3), pointer(mse_save), pointer(mse_time), sel === nothing ? Ptr{Int32}(C_NULL) : pointer(sel),
         sel === nothing ? 0 : length(sel), 1, 0.0)
     # (@ccall: tests/test_rollout_eval_host.py checks this call against the header)
-    rc = GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out gt mse_save mse_time sel @ccall LIB.mgn_rollout_eval(
-        mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, e::Ref{MgnRolloutEvalDesc})::Cint
+    rc = if erk === nothing
+        GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out gt mse_save mse_time sel @ccall LIB.mgn_rollout_eval(
+            mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, e::Ref{MgnRolloutEvalDesc})::Cint
+    else      # (d.solver is not read)
+        adaptive = erk_adaptive(name, dt, fixed_step)
+        GC.@preserve x0 node_type_onehot edge_features val_mask_row inflow_mask_row inflow_data out gt mse_save mse_time sel erk @ccall LIB.mgn_rollout_eval_erk(
+            mgn.handle::Ptr{Cvoid}, d::Ref{MgnRolloutDesc}, e::Ref{MgnRolloutEvalDesc}, erk::Ptr{Float64}, adaptive::Int32)::Cint
+    end
     check(mgn.handle, rc)
     return e.val_loss, mse_save, mse_time, out, collect(saves)
 end

@@ -16,6 +16,9 @@ MGN_DEVICE_NONE = -2
 MGN_OK, MGN_E_ARG, MGN_E_HIP, MGN_E_STATE, MGN_E_OOM, MGN_E_UNSUPPORTED, MGN_E_RCCL = 0, -1, -2, -3, -4, -5, -6
 MGN_TSIT5_ADAPTIVE, MGN_TSIT5_DENSE_SAVES = 1, 2     # mgn_solver_grad_opts.adaptive: a set of flags
 MGN_SOLVER_EULER, MGN_SOLVER_TSIT5, MGN_SOLVER_TSIT5_FIXED = 0, 1, 2     # mgn_rollout_desc.solver
+MGN_ERK_MAX_STAGES, MGN_ERK_TABLEAU_DOUBLES = 7, 76
+# mgn_erk_name, by the names Engine.rollout takes as `solver`
+ERK_NAMES = {"Euler": 0, "Heun": 1, "Midpoint": 2, "Ralston": 3, "RK4": 4, "BS3": 5, "DP5": 6, "Tsit5": 7}
 STATUS_NAMES = {0: "MGN_OK", -1: "MGN_E_ARG", -2: "MGN_E_HIP", -3: "MGN_E_STATE", -4: "MGN_E_OOM", -5: "MGN_E_UNSUPPORTED",
                 -6: "MGN_E_RCCL"}
 MGN_COMM_ID_BYTES = 128
@@ -113,10 +116,16 @@ PROTOTYPES = {
     "mgn_edge_set_export": (C.c_int, [_H, C.c_int32, _i32p, _i32p]),
     "mgn_rollout": (C.c_int, [_H, C.POINTER(MgnRolloutDesc)]),
     "mgn_rollout_eval": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnRolloutEvalDesc)]),
+    "mgn_erk_named": (C.c_int, [C.c_int32, _f64p]),
+    "mgn_erk_check": (C.c_int, [_f64p]),
+    "mgn_rollout_erk": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f64p, C.c_int32]),
+    "mgn_rollout_eval_erk": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnRolloutEvalDesc), _f64p, C.c_int32]),
     "mgn_solver_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f32p, _f32p, _f32p, C.c_float, _f32p, C.c_size_t, _f32p]),
     "mgn_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float, _f32p,
                                         C.c_size_t, _f32p]),
     "mgn_tsit5_interp_weights": (C.c_int, [C.c_double, _f64p]),
+    "mgn_solver_grad_erk": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f64p, C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float, _f32p,
+                                      C.c_size_t, _f32p]),
     "mgn_shooting_grad": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnShootingDesc), _f32p, _f32p, C.c_float, _f32p, C.c_size_t,
                                     _f32p]),
     "mgn_step": (C.c_int, [_H, _f32p, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p]),
@@ -180,6 +189,8 @@ PROTOTYPES = {
     "mgn_group_solver_grad_tsit5": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnSolverGradOpts), _f32p, _f32p, _f32p, C.c_float,
                                               _f32p, C.c_size_t, _f32p]),
     "mgn_group_rollout_eval": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnRolloutEvalDesc)]),
+    "mgn_group_rollout_erk": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), _f64p, C.c_int32]),
+    "mgn_group_rollout_eval_erk": (C.c_int, [_H, C.POINTER(MgnRolloutDesc), C.POINTER(MgnRolloutEvalDesc), _f64p, C.c_int32]),
     "mgn_group_latents_randn": (C.c_int, [_H, C.c_uint64]),
     "mgn_group_processor_steps_dev": (C.c_int, [_H, C.c_int32]),
     "mgn_group_latents_checksum": (C.c_int, [_H, _f64p, _f64p, _f64p, _f64p]),

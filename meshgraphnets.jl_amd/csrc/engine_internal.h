@@ -268,9 +268,11 @@ struct SolverSweep {
 };
 int solver_prepare(mgn_engine* h, size_t n_grads);
 int solver_sweep(mgn_engine* h, const SolverSweep& S);
-// mgn_solver_grad_tsit5: S as for Euler with K = the accepted Tsit5 steps, save_step counting them, states / dt unused, a = dL/dx (lam)
+// mgn_solver_grad_tsit5 and mgn_solver_grad_erk: S as for Euler with K = the accepted steps, save_step counting them, states / dt unused,
+// a = dL/dx (lam).  The method is data: its `stages` active stages s (those whose right-hand side is evaluated on a stage input of the
+// step: all of them, less the FSAL stage; Tsit5: 6), b[0 .. s) and A[j][i], 0-based
 struct Tsit5Sweep {
-    const float* const* steps;           // [K] (host): step n's stored stage inputs z_{n,1 .. 6}, [6][N][O] each
+    const float* const* steps;           // [K] (host): step n's stored stage inputs z_{n,1 .. s}, [s][N][O] each
     const double* h;                     // [K] (host): the step sizes
     const float* xend;                   // [N][O]: x_K (continuity term)
     float* ybar;                         // scratch [5][N][O]: ybar_2 .. ybar_6 of the step being swept
@@ -280,9 +282,11 @@ struct Tsit5Sweep {
     const double* theta = nullptr;       // [n_saves] (host); < 0: the save is state save_step[s]
     const float* zend = nullptr;         // [N][O]: z_{K,1}, the input k_{K-1,7} was evaluated on (the extra VJP of a last step with such saves)
     float* dense = nullptr;              // scratch [7][N][O]: the step's sum of seeds, then W_1 .. W_6
+    int32_t stages = 0;                  // s, 1 .. 6
+    const double* b = nullptr;           // [s]
+    const double (*A)[7] = nullptr;      // [s][7]
 };
 int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5);
-double tsit5_a(int i, int j);          // the Tsit5 tableau (mgn_solve.cpp), 1-based: A[i][j], b = A[7][j]
 
 // mgn_api.cpp, for the solve drivers of mgn_solve.cpp.  Hidden: they were file-local before the drivers had a file of their own, and
 // with default visibility these mgn:: functions would join the library's dynamic symbols
@@ -326,7 +330,8 @@ int forward_vjp_run(mgn_engine* h, const float* nf, const float* ef, const float
                     bool partitions);
 int solver_grad_run(mgn_engine* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
                     const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions);
-int rollout_eval_run(mgn_engine* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions);
+// (tab: mgn_rollout_eval_erk's tableau, checked here before anything else, and its step mode; null: the solver d->solver names)
+int rollout_eval_run(mgn_engine* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions, const double* tab = nullptr, int32_t adaptive = 0);
 int solver_prepare_partitions(mgn_engine* h, const char* who, size_t n_grads);   // solver_prepare for a call that serves partitions too
 #pragma GCC visibility pop
 

@@ -259,19 +259,33 @@ int mgn_group_ode_step(mgn_group* g, const float* x, const float* onehot, const 
     } GROUP_CATCH(g)
 }
 
+extern "C++" {
+namespace {
+// mgn_group_rollout (tab null) and mgn_group_rollout_erk (its tableau and step mode)
+int group_rollout(mgn_group* g, const char* who, mgn_rollout_desc* d, const double* tab, int32_t adaptive) {
+    if (!d) return gfail(g, MGN_E_ARG, (std::string(who) + ": null argument").c_str());
+    const size_t n = (size_t)(d->n_saves > 0 ? d->n_saves : 0) * g->N * g->cfg.O;
+    std::vector<mgn_rollout_desc> ds(g->P, *d);         // every rank fills its own counters; rank 0's go back
+    const int rc = g->run([&](int k, mgn_handle* h) {
+        ds[k].out = g->out_of(k, d->out, n);
+        return tab ? mgn_rollout_erk(h, &ds[k], tab, adaptive) : mgn_rollout(h, &ds[k]);
+    });
+    d->n_accept = ds[0].n_accept;
+    d->n_reject = ds[0].n_reject;
+    d->n_rhs = ds[0].n_rhs;
+    return rc;
+}
+}  // namespace
+}
+
 int mgn_group_rollout(mgn_group* g, mgn_rollout_desc* d) {
+    GROUP_TRY(g) { return group_rollout(g, "mgn_group_rollout", d, nullptr, 0); } GROUP_CATCH(g)
+}
+
+int mgn_group_rollout_erk(mgn_group* g, mgn_rollout_desc* d, const double* tab, int32_t adaptive) {
     GROUP_TRY(g) {
-        if (!d) return gfail(g, MGN_E_ARG, "mgn_group_rollout: null argument");
-        const size_t n = (size_t)(d->n_saves > 0 ? d->n_saves : 0) * g->N * g->cfg.O;
-        std::vector<mgn_rollout_desc> ds(g->P, *d);         // every rank fills its own counters; rank 0's go back
-        const int rc = g->run([&](int k, mgn_handle* h) {
-            ds[k].out = g->out_of(k, d->out, n);
-            return mgn_rollout(h, &ds[k]);
-        });
-        d->n_accept = ds[0].n_accept;
-        d->n_reject = ds[0].n_reject;
-        d->n_rhs = ds[0].n_rhs;
-        return rc;
+        if (mgn_erk_check(tab) != MGN_OK) return gfail(g, MGN_E_ARG, "mgn_group_rollout_erk: the tableau does not pass mgn_erk_check");
+        return group_rollout(g, "mgn_group_rollout_erk", d, tab, adaptive);
     } GROUP_CATCH(g)
 }
 
@@ -418,32 +432,46 @@ int mgn_group_solver_grad_tsit5(mgn_group* g, mgn_rollout_desc* d, mgn_solver_gr
     } GROUP_CATCH(g)
 }
 
-int mgn_group_rollout_eval(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) {
-    GROUP_TRY(g) {
-        if (!d || !e) return gfail(g, MGN_E_ARG, "mgn_group_rollout_eval: null argument");
-        const size_t no = (size_t)g->N * g->cfg.O, ns = (size_t)(d->n_saves > 0 ? d->n_saves : 0);
-        std::vector<mgn_rollout_desc> ds(g->P, *d);
-        std::vector<mgn_rollout_eval_desc> es(g->P, *e);
-        std::vector<std::vector<double>> ms(g->P);       // mse_save of the ranks other than 0 (doubles; the float outputs share the scratch)
-        const int rc = g->run([&](int k, mgn_handle* h) {
-            return guarded(h, [&] {
-                if (k > 0) {      // d->out [n_saves][N][O], then mse_time [N][O], in this rank's scratch
-                    const mgn_group::Outs o = g->outs_of(k, d->out, ns * no, e->mse_time, no);
-                    ds[k].out = o.p[0];
-                    es[k].mse_time = o.p[1];
-                    if (e->mse_save) {
-                        ms[k].assign(ns * g->cfg.O, 0.0);
-                        es[k].mse_save = ms[k].data();
-                    }
+extern "C++" {
+namespace {
+// mgn_group_rollout_eval (tab null) and mgn_group_rollout_eval_erk (its tableau and step mode)
+int group_rollout_eval(mgn_group* g, const char* who, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const double* tab, int32_t adaptive) {
+    if (!d || !e) return gfail(g, MGN_E_ARG, (std::string(who) + ": null argument").c_str());
+    const size_t no = (size_t)g->N * g->cfg.O, ns = (size_t)(d->n_saves > 0 ? d->n_saves : 0);
+    std::vector<mgn_rollout_desc> ds(g->P, *d);
+    std::vector<mgn_rollout_eval_desc> es(g->P, *e);
+    std::vector<std::vector<double>> ms(g->P);       // mse_save of the ranks other than 0 (doubles; the float outputs share the scratch)
+    const int rc = g->run([&](int k, mgn_handle* h) {
+        return guarded(h, [&] {
+            if (k > 0) {      // d->out [n_saves][N][O], then mse_time [N][O], in this rank's scratch
+                const mgn_group::Outs o = g->outs_of(k, d->out, ns * no, e->mse_time, no);
+                ds[k].out = o.p[0];
+                es[k].mse_time = o.p[1];
+                if (e->mse_save) {
+                    ms[k].assign(ns * g->cfg.O, 0.0);
+                    es[k].mse_save = ms[k].data();
                 }
-                return mgn::rollout_eval_run(h, &ds[k], &es[k], true);
-            });
+            }
+            return mgn::rollout_eval_run(h, &ds[k], &es[k], true, tab, adaptive);
         });
-        d->n_accept = ds[0].n_accept;
-        d->n_reject = ds[0].n_reject;
-        d->n_rhs = ds[0].n_rhs;
-        e->val_loss = es[0].val_loss;
-        return rc;
+    });
+    d->n_accept = ds[0].n_accept;
+    d->n_reject = ds[0].n_reject;
+    d->n_rhs = ds[0].n_rhs;
+    e->val_loss = es[0].val_loss;
+    return rc;
+}
+}  // namespace
+}
+
+int mgn_group_rollout_eval(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) {
+    GROUP_TRY(g) { return group_rollout_eval(g, "mgn_group_rollout_eval", d, e, nullptr, 0); } GROUP_CATCH(g)
+}
+
+int mgn_group_rollout_eval_erk(mgn_group* g, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const double* tab, int32_t adaptive) {
+    GROUP_TRY(g) {
+        if (mgn_erk_check(tab) != MGN_OK) return gfail(g, MGN_E_ARG, "mgn_group_rollout_eval_erk: the tableau does not pass mgn_erk_check");
+        return group_rollout_eval(g, "mgn_group_rollout_eval_erk", d, e, tab, adaptive);
     } GROUP_CATCH(g)
 }
 

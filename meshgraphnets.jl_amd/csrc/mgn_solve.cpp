@@ -28,9 +28,145 @@ const double TS_A[7][6] = {
 const double TS_BT[7] = {-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629,
                          0.5823571654525552, -0.45808210592918697, 0.015151515151515152};
 
+// An explicit Runge-Kutta method as the time loops read it: the flat tableau of include/mgn_hip.h (MGN_ERK_TABLEAU_DOUBLES) unpacked.
+// beta1 / beta2 are the PI controller's, the defaults 7/(10 p) and 2/(5 p) filled in.
+struct Erk {
+    int s = 1, p = 1;
+    bool fsal = false, embedded = false;
+    double beta1 = 0.7, beta2 = 0.4;
+    double A[7][7] = {}, b[7] = {}, c[7] = {}, bt[7] = {};
+};
+
+enum { ERK_A = 6, ERK_B = 55, ERK_C = 62, ERK_BT = 69 };     // offsets into the flat tableau
+
+// a tableau mgn_erk_check has passed, unpacked
+Erk erk_unpack(const double* tab) {
+    Erk e;
+    e.s = (int)tab[0]; e.p = (int)tab[1]; e.fsal = tab[2] != 0.0; e.embedded = tab[3] != 0.0;
+    const bool defaults = tab[4] == 0.0 && tab[5] == 0.0;
+    e.beta1 = defaults ? 7.0 / (10 * e.p) : tab[4];
+    e.beta2 = defaults ? 2.0 / (5 * e.p) : tab[5];
+    for (int i = 0; i < e.s; ++i) {
+        for (int j = 0; j < i; ++j) e.A[i][j] = tab[ERK_A + 7 * i + j];
+        e.b[i] = tab[ERK_B + i]; e.c[i] = tab[ERK_C + i];
+        e.bt[i] = e.embedded ? tab[ERK_BT + i] : 0.0;
+    }
+    return e;
+}
+
+// the flat tableau of a method given by rows (row i of A holds i entries); bt null: no embedded pair
+void erk_fill(double* tab, int s, int p, bool fsal, const double* const* rows, const double* b, const double* c, const double* bt, double beta1,
+              double beta2) {
+    std::fill(tab, tab + MGN_ERK_TABLEAU_DOUBLES, 0.0);
+    tab[0] = s; tab[1] = p; tab[2] = fsal ? 1.0 : 0.0; tab[3] = bt ? 1.0 : 0.0; tab[4] = beta1; tab[5] = beta2;
+    for (int i = 0; i < s; ++i) {
+        for (int j = 0; j < i; ++j) tab[ERK_A + 7 * i + j] = rows[i][j];
+        tab[ERK_B + i] = b[i]; tab[ERK_C + i] = c[i];
+        if (bt) tab[ERK_BT + i] = bt[i];
+    }
+}
+
+// Tsit5 as a tableau: TS_A / TS_C / TS_BT above, b = row 7 (FSAL), order 5, the default betas
+void erk_fill_tsit5(double* tab) {
+    const double* rows[7];
+    double b[7] = {};
+    for (int i = 0; i < 7; ++i) rows[i] = TS_A[i];
+    for (int j = 0; j < 6; ++j) b[j] = TS_A[6][j];
+    erk_fill(tab, 7, 5, true, rows, b, TS_C, TS_BT, 0.0, 0.0);
+}
+
+// the tableau MGN_SOLVER_TSIT5 and the Tsit5 training loops drive
+const Erk& erk_tsit5() {
+    static const Erk e = [] {
+        double tab[MGN_ERK_TABLEAU_DOUBLES];
+        erk_fill_tsit5(tab);
+        return erk_unpack(tab);
+    }();
+    return e;
+}
+
 }  // namespace
 
-double mgn::tsit5_a(int i, int j) { return TS_A[i - 1][j - 1]; }
+extern "C" int mgn_erk_check(const double* tab) {
+    if (!tab) return MGN_E_ARG;
+    for (int i = 0; i < MGN_ERK_TABLEAU_DOUBLES; ++i)
+        if (!std::isfinite(tab[i])) return MGN_E_ARG;
+    for (int i = 0; i < 4; ++i)
+        if (tab[i] != std::floor(tab[i])) return MGN_E_ARG;
+    if (tab[0] < 1 || tab[0] > MGN_ERK_MAX_STAGES || tab[1] < 1 || tab[1] > 1e6) return MGN_E_ARG;
+    if ((tab[2] != 0 && tab[2] != 1) || (tab[3] != 0 && tab[3] != 1)) return MGN_E_ARG;
+    if (tab[4] < 0 || tab[5] < 0) return MGN_E_ARG;
+    const int s = (int)tab[0];
+    const double *A = tab + ERK_A, *b = tab + ERK_B, *c = tab + ERK_C, *bt = tab + ERK_BT;
+    double sb = 0.0, sbt = 0.0;
+    for (int i = 0; i < s; ++i) {
+        for (int j = i; j < s; ++j)
+            if (A[7 * i + j] != 0.0) return MGN_E_ARG;       // explicit methods only
+        sb += b[i];
+        sbt += bt[i];
+    }
+    if (std::fabs(sb - 1.0) > 1e-10) return MGN_E_ARG;
+    if (tab[3] != 0 && std::fabs(sbt) > 1e-10) return MGN_E_ARG;
+    if (tab[2] != 0) {         // first same as last: stage s is f(x_{n+1})
+        if (b[s - 1] != 0.0 || c[s - 1] != 1.0) return MGN_E_ARG;
+        for (int j = 0; j < s; ++j)
+            if (A[7 * (s - 1) + j] != b[j]) return MGN_E_ARG;
+    }
+    return MGN_OK;
+}
+
+// The named methods, their coefficients entered as rationals and rounded once (a quotient of two exactly representable integers).
+extern "C" int mgn_erk_named(int32_t name, double* tab) {
+    if (!tab) return MGN_E_ARG;
+    static const double z1[1] = {0};
+    switch (name) {
+    case MGN_ERK_EULER: {
+        const double b[1] = {1}, c[1] = {0};
+        const double* rows[1] = {z1};
+        erk_fill(tab, 1, 1, false, rows, b, c, nullptr, 0, 0);
+        return MGN_OK;
+    }
+    case MGN_ERK_HEUN: case MGN_ERK_MIDPOINT: case MGN_ERK_RALSTON: {
+        const double a21 = name == MGN_ERK_HEUN ? 1.0 : name == MGN_ERK_MIDPOINT ? 1.0 / 2 : 2.0 / 3;
+        const double r1[1] = {a21};
+        const double* rows[2] = {z1, r1};
+        const double bh[2] = {1.0 / 2, 1.0 / 2}, bm[2] = {0, 1}, br[2] = {1.0 / 4, 3.0 / 4};
+        const double c[2] = {0, a21};
+        erk_fill(tab, 2, 2, false, rows, name == MGN_ERK_HEUN ? bh : name == MGN_ERK_MIDPOINT ? bm : br, c, nullptr, 0, 0);
+        return MGN_OK;
+    }
+    case MGN_ERK_RK4: {
+        const double r1[1] = {1.0 / 2}, r2[2] = {0, 1.0 / 2}, r3[3] = {0, 0, 1};
+        const double* rows[4] = {z1, r1, r2, r3};
+        const double b[4] = {1.0 / 6, 1.0 / 3, 1.0 / 3, 1.0 / 6}, c[4] = {0, 1.0 / 2, 1.0 / 2, 1};
+        erk_fill(tab, 4, 4, false, rows, b, c, nullptr, 0, 0);
+        return MGN_OK;
+    }
+    case MGN_ERK_BS3: {
+        const double r1[1] = {1.0 / 2}, r2[2] = {0, 3.0 / 4}, b[4] = {2.0 / 9, 1.0 / 3, 4.0 / 9, 0};
+        const double* rows[4] = {z1, r1, r2, b};
+        const double c[4] = {0, 1.0 / 2, 3.0 / 4, 1}, bt[4] = {-5.0 / 72, 1.0 / 12, 1.0 / 9, -1.0 / 8};
+        erk_fill(tab, 4, 3, true, rows, b, c, bt, 0, 0);
+        return MGN_OK;
+    }
+    case MGN_ERK_DP5: {
+        const double r1[1] = {1.0 / 5}, r2[2] = {3.0 / 40, 9.0 / 40}, r3[3] = {44.0 / 45, -56.0 / 15, 32.0 / 9};
+        const double r4[4] = {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729};
+        const double r5[5] = {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656};
+        const double b[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
+        const double* rows[7] = {z1, r1, r2, r3, r4, r5, b};
+        const double c[7] = {0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1, 1};
+        const double bt[7] = {71.0 / 57600, 0, -71.0 / 16695, 71.0 / 1920, -17253.0 / 339200, 22.0 / 525, -1.0 / 40};
+        erk_fill(tab, 7, 5, true, rows, b, c, bt, 0.17, 0.04);
+        return MGN_OK;
+    }
+    case MGN_ERK_TSIT5:
+        erk_fill_tsit5(tab);
+        return MGN_OK;
+    default:
+        return MGN_E_ARG;
+    }
+}
 
 // Tsit5's dense output, the free 4th-order interpolant of Tsitouras 2011 (what OrdinaryDiffEq.jl evaluates between the steps of a Tsit5
 // solve):  x(t_n + theta h) = x_n + h sum_i b_i(theta) k_i,  b_i(theta) = r_i1 theta + r_i2 theta^2 + r_i3 theta^3 + r_i4 theta^4, with
@@ -50,11 +186,13 @@ extern "C" int mgn_tsit5_interp_weights(double theta, double b[7]) {
 
 namespace {
 
-// mgn_rollout's PI controller (beta1 = 7/50, beta2 = 2/25, gamma = 0.9, qmin = 0.2, qmax = 10): the accept / reject decision for a trial
-// of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
+// mgn_rollout's PI controller (beta1, beta2 the tableau's: 7/50 and 2/25 for Tsit5; gamma = 0.9, qmin = 0.2, qmax = 10): the accept /
+// reject decision for a trial of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
 struct Tsit5Control {
-    static constexpr double beta1 = 7.0 / 50, beta2 = 2.0 / 25, gamma = 0.9, qmin = 0.2, qmax = 10.0;
+    static constexpr double gamma = 0.9, qmin = 0.2, qmax = 10.0;
+    double beta1, beta2;
     double qold = 1e-4;
+    explicit Tsit5Control(const Erk& e) : beta1(e.beta1), beta2(e.beta2) {}
     bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
         const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
         if (EEst <= 1.0) {
@@ -355,9 +493,22 @@ struct Rollout {
         return MGN_OK;
     }
 
-    // ---- Tsit5, shared by mgn_rollout, mgn_solver_grad_tsit5 and mgn_shooting_grad ----
+    // ---- explicit Runge-Kutta by tableau (tb: Tsit5's unless mgn_rollout_erk gave another), shared by mgn_rollout, mgn_rollout_erk,
+    // mgn_solver_grad_tsit5 and mgn_shooting_grad ----
+    const Erk* tb = &erk_tsit5();
+    bool have_k1 = false;      // k[0] = f(u): kept over the retrials of a step; FSAL keeps it over accepted steps too
     // k1 = f(u) at t (FSAL afterwards)
-    int tsit5_first(double t) { return eval(u, za, t, k[0]); }
+    int tsit5_first(double t) {
+        have_k1 = true;
+        return eval(u, za, t, k[0]);
+    }
+    // sum over the stages j < m of coef[j] k_j, coefficients rounded to float once, terms whose coefficient is exactly 0 left out
+    LinComb stage_sum(const double* coef, int m) const {
+        LinComb lc{0, {}, {}};
+        for (int j = 0; j < m; ++j)
+            if (coef[j] != 0.0) { lc.c[lc.n] = (float)coef[j]; lc.k[lc.n] = k[j]; ++lc.n; }
+        return lc;
+    }
     // Hairer-Wanner starting step from (u, k1)
     int tsit5_h0(double t, double* dt) {
         double d0, d1, d2;
@@ -372,21 +523,24 @@ struct Rollout {
         LinComb ld{2, {1.f, -1.f}, {k[1], k[0]}};
         if (int rc = norm(u, u, ld, (float)(1.0 / h0), &d2)) return rc;
         const double mx = d1 > d2 ? d1 : d2;
-        const double h1 = mx <= 1e-15 ? (h0 * 1e-3 > 1e-6 ? h0 * 1e-3 : 1e-6) : std::pow(0.01 / mx, 1.0 / 5);
+        const double h1 = mx <= 1e-15 ? (h0 * 1e-3 > 1e-6 ? h0 * 1e-3 : 1e-6) : std::pow(0.01 / mx, 1.0 / tb->p);
         *dt = 100 * h0 < h1 ? 100 * h0 : h1;
         return MGN_OK;
     }
-    // one trial step from (u, k1) over hstep: stages 2 .. 6 at tt(t + tt(c_i hstep)), unew = u + hstep sum_j A[7][j] k_j, and k7 = f(unew)
-    // at t7 (FSAL); EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H.
-    // fused_input (mgn_rollout's fixed-step Tsit5): the stage sum and the in-place inflow rows of its stage time in one launch
-    // (launch_tsit5_stage_input: launch_lincomb's bits, then launch_overwrite's rows) where the other loops issue two
+    // one trial step from (u, k1) over hstep: stages 2 .. s at tt(t + tt(c_i hstep)) on utmp; the FSAL stage (stage s of an FSAL tableau:
+    // Tsit5's k7) is f(unew), unew = u + hstep sum_j b_j k_j, at t7; without FSAL unew is formed after the last stage and not evaluated.
+    // EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H.
+    // fused_input (the fixed-step loops of mgn_rollout and mgn_rollout_erk): the stage sum and the in-place inflow rows of its stage time
+    // in one launch (launch_tsit5_stage_input: launch_lincomb's bits, then launch_overwrite's rows) where the other loops issue two
     bool fused_input = false;
     int tsit5_trial(double t, double hstep, double t7, double* EEst) {
-        for (int sidx = 1; sidx < 7; ++sidx) {     // stages 2..7; stage 7 is evaluated on unew (FSAL)
-            LinComb lc{sidx, {}, {}};
-            for (int j = 0; j < sidx; ++j) { lc.c[j] = (float)TS_A[sidx][j]; lc.k[j] = k[j]; }
-            float* dst = (sidx == 6) ? unew : utmp;
-            const double ts = sidx == 6 ? t7 : tt(t + tt(TS_C[sidx] * hstep));
+        const Erk& e = *tb;
+        const int last = e.s - 1, active = e.s - (e.fsal ? 1 : 0);      // active: the stages whose inputs the training form keeps
+        for (int sidx = 1; sidx < e.s; ++sidx) {     // stages 2..s
+            const bool on_new = e.fsal && sidx == last;
+            const LinComb lc = stage_sum(e.A[sidx], sidx);
+            float* dst = on_new ? unew : utmp;
+            const double ts = on_new ? t7 : tt(t + tt(e.c[sidx] * hstep));
             if (fused_input) {
                 const float* fr = nullptr;
                 if (mask && frames) {
@@ -399,21 +553,24 @@ struct Rollout {
                 continue;
             }
             HIPCHK(h, launch_lincomb(dst, u, lc, (float)hstep, n, h->stream));
-            float* z = (sidx == 6) ? z7 : zs;
+            float* z = on_new ? z7 : zs;
             if (int rc = eval(dst, z, ts, k[sidx])) return rc;
-            if (sidx < 6 && kept)
+            if (sidx < active && kept)
                 HIPCHK(h, hipMemcpyAsync(kept + (size_t)sidx * n, rhs_input(dst, z), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         }
+        if (!e.fsal) HIPCHK(h, launch_lincomb(unew, u, stage_sum(e.b, e.s), (float)hstep, n, h->stream));
         if (!EEst) return MGN_OK;
-        LinComb le{7, {}, {}};
-        for (int j = 0; j < 7; ++j) { le.c[j] = (float)TS_BT[j]; le.k[j] = k[j]; }
-        return norm(u, unew, le, (float)hstep, EEst);
+        return norm(u, unew, stage_sum(e.bt, e.s), (float)hstep, EEst);
     }
-    // the accepted trial becomes the state: unew -> u, k7 -> k1 (FSAL), z_{n+1,1} -> za
+    // the accepted trial becomes the state: unew -> u; FSAL: the last stage -> k1 (Tsit5: k7), z_{n+1,1} -> za; otherwise k1 is due again
     void tsit5_advance() {
         std::swap(u, unew);
-        std::swap(k[0], k[6]);
-        std::swap(za, z7);
+        if (tb->fsal) {
+            std::swap(k[0], k[tb->s - 1]);
+            std::swap(za, z7);
+        } else {
+            have_k1 = false;
+        }
     }
 
     // training form: slot(n, &p) gives accepted step n's storage for its six stage inputs
@@ -426,17 +583,23 @@ struct Rollout {
         return MGN_OK;
     }
 
-    // fixed-step Tsit5 in the training form: K steps of dt on the fixed grid, stage 7 at t_{n+1}; saves from the plan
-    int tsit5_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot& slot) {
+    // fixed steps of the tableau: K steps of dt on the fixed grid, the FSAL stage at t_{n+1}; saves from the plan.  slot: the training
+    // form (mgn_solver_grad_tsit5, mgn_solver_grad_erk, mgn_shooting_grad), every step's stage inputs and record kept; none: the
+    // evaluation form of mgn_rollout_erk, nothing stored
+    int tsit5_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot* slot) {
         double t = tg.t0;
         if (int rc = saves_after(plan, 0)) return rc;
-        if (int rc = tsit5_first(t)) return rc;
+        if (tb->fsal)
+            if (int rc = tsit5_first(t)) return rc;
         for (int64_t i = 0; i < K; ++i) {
             const double tn = tg.next(i, K, t);
-            if (int rc = begin_trial(slot, i)) return rc;
+            if (!have_k1)
+                if (int rc = tsit5_first(t)) return rc;
+            if (slot)
+                if (int rc = begin_trial(*slot, i)) return rc;
             if (int rc = tsit5_trial(t, tg.dt, tn, nullptr)) return rc;
             tsit5_advance();
-            step_t.push_back(t); step_h.push_back(tg.dt);
+            if (slot) { step_t.push_back(t); step_h.push_back(tg.dt); }
             t = tn;
             ++d->n_accept;
             if (int rc = saves_after(plan, i + 1)) return rc;
@@ -484,11 +647,12 @@ struct Rollout {
         const int ns = d->n_saves;
         double t = tg.t0;
         if (int rc = save(0)) return rc;
-        if (int rc = tsit5_first(t)) return rc;     // k1 (FSAL afterwards)
         double dt = tg.dt;
+        if (tb->fsal || dt <= 0)
+            if (int rc = tsit5_first(t)) return rc;     // k1 (FSAL afterwards; otherwise once per state that starts a step, below)
         if (dt <= 0)   // Hairer-Wanner starting step
             if (int rc = tsit5_h0(t, &dt)) return rc;
-        Tsit5Control ctl;
+        Tsit5Control ctl(*tb);
         int64_t guard = 0, nacc = 0;
         // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save periods is not worth a step
         while (t < tg.t1 - 1e-5 * tg.sdt) {
@@ -503,7 +667,9 @@ struct Rollout {
             if (t + hstep >= tstop - 1e-9 * std::fabs(tstop)) { hstep = tstop - t; hit_stop = true; }
             const double tn = hit_stop ? tstop : tt(t + hstep);
             // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
-            const double t7 = (slot || hit_stop) ? tn : tt(t + tt(TS_C[6] * hstep));
+            const double t7 = (slot || hit_stop) ? tn : tt(t + tt(tb->c[tb->s - 1] * hstep));
+            if (!have_k1)
+                if (int rc = tsit5_first(t)) return rc;
             if (slot)
                 if (int rc = begin_trial(*slot, nacc)) return rc;
             double EEst;
@@ -663,9 +829,18 @@ int to_engine_order(mgn_handle* h, const float* src, int64_t count, float* dst, 
 // its rows, as often as they are listed --, then the ranks' sums ([n_saves][O] per-save sums and the val_loss numerator, undivided) are
 // folded once in ascending rank order (rank_fold_f64) and divided by the whole mesh's counts; mse_time's rows go through
 // gather_rows_global.  Without d->out no save is kept, gathered or downloaded on any rank.
-int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who) {
+// tab (mgn_rollout_erk and its kin; null: the solver d->solver names): the method is this tableau, already checked, d->solver is not read,
+// and adaptive chooses between the fixed grid (Rollout::tsit5_fixed without a slot) and the controller's loop (Rollout::tsit5_adaptive)
+int fixed_grid(mgn_handle* h, const char* who, const TimeGrid& T, int n_saves, int64_t* K, std::vector<int64_t>& save_step);
+int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who, const double* tab = nullptr, int32_t adaptive = 0) {
     const bool lnall = h && h->cfg.ln_dims == MGN_LN_ALL;
     if (int rc = need(h, true, true, !lnall, true)) return rc;
+    if (tab) {
+        if (!d) return fail(h, MGN_E_ARG, "%s: null argument", who);
+        if (adaptive != 0 && adaptive != 1) return fail(h, MGN_E_ARG, "%s: adaptive must be 0 or 1", who);
+        if (adaptive && tab[3] == 0.0)
+            return fail(h, MGN_E_UNSUPPORTED, "%s: adaptive = 1 needs a tableau with an embedded pair (btilde); this one has none", who);
+    }
     const mgn_config& c = h->cfg;
     const bool part = c.nranks != 1;      // partitioned: every rank integrates the rows it owns; error norms are reduced over the ranks
     if (part) if (int rc = need_comm(h, who)) return rc;
@@ -674,12 +849,28 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     if (int rc = solver_static_checks(h, d, who)) return rc;
     const TimeGrid T(d);
     if (d->n_saves < 1 || !(T.sdt > 0.0) || T.t1 < T.t0) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (d->solver == MGN_SOLVER_EULER && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
-    if (d->solver == MGN_SOLVER_TSIT5_FIXED && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
-    if (int rc = inflow_checks(h, d, who)) return rc;
-    if (d->solver < MGN_SOLVER_EULER || d->solver > MGN_SOLVER_TSIT5_FIXED)
-        return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler), 1 (Tsit5) or 2 (Tsit5 with fixed steps)", who);
-    if (d->solver == MGN_SOLVER_TSIT5 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+    int64_t erk_K = 0;                      // a tableau with fixed steps: the step count and the accepted steps before every save
+    std::vector<int64_t> erk_plan;
+    if (tab) {
+        if (!adaptive) {
+            if (!(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
+            const double per = T.sdt / T.dt, m = std::round(per);
+            if (!(m >= 1.0) || std::fabs(per - m) > 1e-6 * m)
+                return fail(h, MGN_E_ARG, "%s: saves_dt / dt = %.9g is not an integer >= 1: a general tableau has no dense output (Tsit5 with other "
+                            "steps: mgn_rollout with MGN_SOLVER_TSIT5_FIXED)", who, per);
+            if (int rc = fixed_grid(h, who, T, d->n_saves, &erk_K, erk_plan)) return rc;
+        } else if (d->abstol <= 0.f || d->reltol <= 0.f) {
+            return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+        }
+        if (int rc = inflow_checks(h, d, who)) return rc;
+    } else {
+        if (d->solver == MGN_SOLVER_EULER && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: Euler needs dt > 0", who);
+        if (d->solver == MGN_SOLVER_TSIT5_FIXED && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, "%s: fixed steps need dt > 0", who);
+        if (int rc = inflow_checks(h, d, who)) return rc;
+        if (d->solver < MGN_SOLVER_EULER || d->solver > MGN_SOLVER_TSIT5_FIXED)
+            return fail(h, MGN_E_ARG, "%s: solver must be 0 (Euler), 1 (Tsit5) or 2 (Tsit5 with fixed steps)", who);
+        if (d->solver == MGN_SOLVER_TSIT5 && (d->abstol <= 0.f || d->reltol <= 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
+    }
     const LocalGraph& g = h->g;
     invalidate_static(h);
     const int32_t nloc = part ? g.n_own : g.N;        // rows of the state this handle integrates
@@ -745,9 +936,17 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
     }
 
     d->n_accept = d->n_reject = 0;
-    R.fused_input = d->solver == MGN_SOLVER_TSIT5_FIXED;
-    if (int rc = d->solver == MGN_SOLVER_EULER ? R.euler_rollout() : d->solver == MGN_SOLVER_TSIT5 ? R.tsit5_adaptive(who, nullptr) : R.tsit5_fixed_dense(nullptr))
-        return rc;
+    Erk erk;
+    if (tab) {
+        erk = erk_unpack(tab);
+        R.tb = &erk;
+        R.fused_input = !adaptive;
+        if (int rc = adaptive ? R.tsit5_adaptive(who, nullptr) : R.tsit5_fixed(erk_K, erk_plan, nullptr)) return rc;
+    } else {
+        R.fused_input = d->solver == MGN_SOLVER_TSIT5_FIXED;
+        if (int rc = d->solver == MGN_SOLVER_EULER ? R.euler_rollout() : d->solver == MGN_SOLVER_TSIT5 ? R.tsit5_adaptive(who, nullptr) : R.tsit5_fixed_dense(nullptr))
+            return rc;
+    }
     if (part) {     // every rank returns the complete solution (mgn_rollout_eval without d->out: none is kept)
         for (int i = 0; d->out && i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, c.O, d->out + (size_t)i * g.N * c.O)) return rc;
@@ -803,8 +1002,22 @@ extern "C" int mgn_rollout(mgn_handle* h, mgn_rollout_desc* d) try {
     return rollout_solve(h, d, nullptr, "mgn_rollout");
 } MGN_CATCH(h)
 
-int mgn::rollout_eval_run(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions) {
-    static const char* who = "mgn_rollout_eval";
+// the tableau of an *_erk entry point, before anything else
+static int erk_checked(mgn_handle* h, const double* tab, const char* who) {
+    if (mgn_erk_check(tab) != MGN_OK) return fail(h, MGN_E_ARG, "%s: the tableau does not pass mgn_erk_check", who);
+    return MGN_OK;
+}
+
+extern "C" int mgn_rollout_erk(mgn_handle* h, mgn_rollout_desc* d, const double* tab, int32_t adaptive) try {
+    if (!h) return MGN_E_ARG;
+    if (int rc = erk_checked(h, tab, "mgn_rollout_erk")) return rc;
+    return rollout_solve(h, d, nullptr, "mgn_rollout_erk", tab, adaptive);
+} MGN_CATCH(h)
+
+int mgn::rollout_eval_run(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions, const double* tab, int32_t adaptive) {
+    const char* who = tab ? "mgn_rollout_eval_erk" : "mgn_rollout_eval";
+    if (tab)
+        if (int rc = erk_checked(h, tab, who)) return rc;
     // the descriptor first (a host-only handle answers it too)
     if (!d || !e || !e->gt) return fail(h, MGN_E_ARG, "%s: null argument", who);
     if (e->n_gt < d->n_saves) return fail(h, MGN_E_ARG, "%s: n_gt = %d ground-truth frames for n_saves = %d saves", who, e->n_gt, d->n_saves);
@@ -822,8 +1035,13 @@ int mgn::rollout_eval_run(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_d
         }
     }
     e->val_loss = 0.0;
-    return rollout_solve(h, d, e, who);      // (without a graph it refuses before sel is read)
+    return rollout_solve(h, d, e, who, tab, adaptive);      // (without a graph it refuses before sel is read)
 }
+
+extern "C" int mgn_rollout_eval_erk(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const double* tab, int32_t adaptive) try {
+    if (!h || !tab) return MGN_E_ARG;
+    return rollout_eval_run(h, d, e, false, tab, adaptive);
+} MGN_CATCH(h)
 
 extern "C" int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e) try {
     if (!h) return MGN_E_ARG;
@@ -890,6 +1108,7 @@ SolverSweep sweep_setup(const Rollout& R, bool euler, int64_t K, const float* st
 int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler, const std::vector<float*>& steps, float* ybar, float* dense = nullptr) {
     if (euler) return solver_sweep(e, S);
     Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, ybar};
+    T5.stages = R.tb->s - (R.tb->fsal ? 1 : 0); T5.b = R.tb->b; T5.A = R.tb->A;
     if (dense) {
         T5.theta = R.save_theta.data();
         T5.zend = R.rhs_input(R.u, R.za);      // z_{K,1}: what stage 7 of the last accepted trial was evaluated on
@@ -900,9 +1119,10 @@ int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler,
 
 // mgn_solver_grad (o null: fixed-step Euler) and mgn_solver_grad_tsit5 (o: fixed steps, or adaptive), after their own checks: the time grid,
 // the forward loop keeping what the sweep needs (Euler: every step's RHS input; Tsit5: every accepted step's six stage inputs, in chunks on
-// the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves
+// the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves.  tb (mgn_solver_grad_erk; null: Tsit5's): the tableau the
+// forward loop and the sweep drive, its s' = s - fsal active stages' inputs stored per step
 int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
-                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
+                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions, const Erk* tb = nullptr) {
     const bool euler = !o, adaptive = o && (o->adaptive & MGN_TSIT5_ADAPTIVE), dense = o && (o->adaptive & MGN_TSIT5_DENSE_SAVES);
     const TimeGrid T(d);
     if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
@@ -931,6 +1151,7 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     const int O = c.O;
     invalidate_static(h);
     Rollout R(h, d, T, true, N, h->g.N);
+    if (tb) R.tb = tb;
     const size_t nb = (size_t)R.n * 4;
     const size_t P = h->params.size();
     const int ablk = solver_adjoint_blocks(N, O);
@@ -961,9 +1182,9 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
     if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
 
-    // Tsit5: the stored stage inputs, step n's six [N][O] arrays at steps[n], carved out of chunks kept on the handle and grown
-    // geometrically (never reallocated: a stored step does not move)
-    const size_t stepb = 6 * nb;
+    // Tsit5 or a tableau: the stored stage inputs, step n's s' [N][O] arrays (Tsit5: six) at steps[n], carved out of chunks kept on the
+    // handle and grown geometrically (never reallocated: a stored step does not move)
+    const size_t stepb = (size_t)(R.tb->s - (R.tb->fsal ? 1 : 0)) * nb;
     const size_t denseb = dense ? 7 * nb : 0;      // counted with the stored stage inputs (max_store_bytes, stored_bytes)
     const int64_t max_steps = 100000;
     std::vector<float*> steps;
@@ -1004,7 +1225,7 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     d->n_accept = d->n_reject = 0;
     float* states = (float*)(base + o_st);
     R.dense = dense;
-    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(&slot) : R.tsit5_fixed(K, plan, slot))
+    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(&slot) : R.tsit5_fixed(K, plan, &slot))
         return rc;
     d->n_rhs = R.n_rhs;
     if (!euler) {
@@ -1069,6 +1290,33 @@ extern "C" int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* 
                     float* grads, size_t n_grads, float* loss) try {
     if (!h) return MGN_E_ARG;
     return solver_grad_run(h, d, nullptr, false, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
+} MGN_CATCH(h)
+
+// mgn_solver_grad_tsit5's loss and gradient for any explicit Runge-Kutta tableau with at most six active stages, fixed steps only: the
+// grid and saves of mgn_rollout_erk(adaptive = 0) in the training form, the s' stage inputs of every step kept in h->tsit5_store, then
+// the same table-driven sweep.  d->solver is not read.
+extern "C" int mgn_solver_grad_erk(mgn_handle* h, mgn_rollout_desc* d, const double* tab, mgn_solver_grad_opts* o, const float* gt,
+                                   const float* loss_scale, const float* cont_target, float cont_weight, float* grads, size_t n_grads,
+                                   float* loss) try {
+    static const char* who = "mgn_solver_grad_erk";
+    if (!h) return MGN_E_ARG;
+    if (int rc = erk_checked(h, tab, who)) return rc;
+    // the step mode and the stage count next: a host-only handle answers them too
+    if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
+    if (o->adaptive != 0)
+        return fail(h, MGN_E_UNSUPPORTED, "%s: adaptive = %d: fixed steps only (adaptive training is mgn_solver_grad_tsit5's, with Tsit5)", who, o->adaptive);
+    const Erk erk = erk_unpack(tab);
+    if (erk.s - (erk.fsal ? 1 : 0) > 6)
+        return fail(h, MGN_E_UNSUPPORTED, "%s: %d active stages; the sweep holds six", who, erk.s - (erk.fsal ? 1 : 0));
+    if (int rc = solver_checks(h, d, who, gt, grads, loss, false)) return rc;
+    if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
+    const TimeGrid T(d);
+    if (T.dt > 0.0 && T.sdt > 0.0) {      // (solver_grad refuses the rest of a bad grid)
+        const double per = T.sdt / T.dt, m = std::round(per);
+        if (!(m >= 1.0) || std::fabs(per - m) > 1e-6 * m)
+            return fail(h, MGN_E_ARG, "%s: saves_dt / dt = %.9g is not an integer >= 1: a general tableau has no dense output", who, per);
+    }
+    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false, &erk);
 } MGN_CATCH(h)
 
 // Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_adaptive, Tsit5Control) or fixed steps on the Euler grid (Rollout::tsit5_fixed), in
@@ -1437,7 +1685,7 @@ int shoot_pass(ShootCtx& X, const ShootPass& ps) {
     std::vector<float*> steps;
     for (int64_t i = 0; !X.euler && i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
     const Rollout::Slot slot = [&](int64_t i, float** out) { *out = steps[i]; return MGN_OK; };
-    if (int rc = X.euler ? R.euler_train(K, G.save_step, store) : R.tsit5_fixed(K, G.save_step, slot)) return efail(rc);
+    if (int rc = X.euler ? R.euler_train(K, G.save_step, store) : R.tsit5_fixed(K, G.save_step, &slot)) return efail(rc);
     if (R.saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", shoot_who, R.saved, ns);
     d->n_accept += (int32_t)(K * B);
     d->n_rhs += R.n_rhs * B;

@@ -1992,10 +1992,12 @@ int solver_sweep(mgn_engine* h, const SolverSweep& S) {
     return W.finish();
 }
 
-// Reverse sweep of mgn_solver_grad_tsit5: steps n = K-1 .. 0, stages i = 6 .. 1, one VJP per stage on its stored input z_{n,i}.  The seed
-// of stage 6 is written by the adjoint launch of state n + 1 (h_n A[7][6] lam); k_tsit5_stage_seed masks zbar_{i+1} into ybar_{i+1} and
-// writes kbar_i = h_n (A[7][i] lam + sum_{j>i} A[j][i] ybar_j) for i = 5 .. 1, and before stage 1's VJP adds sum_{j>=2} ybar_j to lam;
-// the adjoint launch of state n folds in ybar_1 and the loss terms of x_n.  No host synchronisation until the end.
+// Reverse sweep of mgn_solver_grad_tsit5 and mgn_solver_grad_erk, driven by the tableau (T5.stages active stages s, T5.b, T5.A; Tsit5:
+// s = 6, b = A[7]): steps n = K-1 .. 0, stages i = s .. 1, one VJP per stage on its stored input z_{n,i}.  The seed of stage s is written
+// by the adjoint launch of state n + 1 (h_n b_s lam); k_erk_stage_seed masks zbar_{i+1} into ybar_{i+1} and writes
+// kbar_i = h_n (b_i lam + sum_{j>i} A[j][i] ybar_j) for i = s-1 .. 1, and before stage 1's VJP adds sum_{j>=2} ybar_j to lam; the adjoint
+// launch of state n folds in ybar_1 and the loss terms of x_n.  One stage: no seed launch at all (Euler's sweep).  No host
+// synchronisation until the end.
 //
 // Dense saves (T5.theta): the saves interpolated inside step n, xhat_s = x_n + h_n sum_i b_i(theta_s) k_{n,i}, seed lam_n with sum ghat_s,
 // kbar_{n,i} with h_n W_i (W_i = sum_s b_i(theta_s) ghat_s, i = 1 .. 6) and, k_{n,7} being the evaluation at z_{n+1,1} (FSAL),
@@ -2003,6 +2005,9 @@ int solver_sweep(mgn_engine* h, const SolverSweep& S) {
 // runs right before the VJP at z_{n+1,1} -- stage 1 of step n + 1, whose seed launch has just consumed that step's own sums, or for the
 // last step one extra VJP at z_{K,1} before the sweep starts, its masked output folded into lam_K by the adjoint launch of state K.
 int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
+    const int sp = T5.stages;
+    if (sp < 1 || sp > 6 || !T5.b || !T5.A) return fail(h, MGN_E_STATE, "tsit5_sweep: %d stages", sp);
+    if (T5.theta && sp != 6) return fail(h, MGN_E_STATE, "tsit5_sweep: interpolated saves are Tsit5's dense output");
     Sweep W(h, S, T5.xend);
     if (int rc = W.begin()) return rc;
     W.theta = T5.theta;
@@ -2036,7 +2041,7 @@ int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
         }
         return MGN_OK;
     };
-    auto seed6 = [&](int64_t k) { return k > 0 ? (float)(T5.h[k - 1] * tsit5_a(7, 6)) : 0.f; };
+    auto seed6 = [&](int64_t k) { return k > 0 ? (float)(T5.h[k - 1] * T5.b[sp - 1]) : 0.f; };      // the last stage's seed: h b_s lam
     bool first = true;                          // no VJP has run yet (the first one assigns the gradient accumulator)
     if (has_inner(S.K - 1)) {
         if (int rc = dense(S.K - 1, false)) return rc;
@@ -2046,21 +2051,22 @@ int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
     if (int rc = W.adjoint(S.K, !first, seed6(S.K))) return rc;
     for (int64_t k = S.K - 1; k >= 0; --k) {
         const bool di = has_inner(k);
-        for (int i = 6; i >= 1; --i) {
-            if (i < 6 || di) {                  // (stage 6's seed h_k A[7][6] lam is the adjoint launch's; with dense saves it takes h_k W_6)
-                Tsit5SeedArgs p{};
-                p.xbar = i < 6 ? W.io : nullptr;
+        for (int i = sp; i >= 1; --i) {
+            if (i < sp || di) {                 // (stage s's seed h_k b_s lam is the adjoint launch's; with dense saves it takes h_k W_6)
+                ErkSeedArgs p{};
+                p.xbar = i < sp ? W.io : nullptr;
                 p.inflow = S.inflow;
                 p.ybar = T5.ybar;
                 p.a = S.a;
                 p.kbar = W.io + W.n;
-                p.cb = (float)(T5.h[k] * tsit5_a(7, i));
-                for (int j = i + 1; j <= 6; ++j) p.ca[j - 1] = (float)(T5.h[k] * tsit5_a(j, i));
+                p.cb = (float)(T5.h[k] * T5.b[i - 1]);
+                for (int j = i + 1; j <= sp; ++j) p.ca[j - 1] = (float)(T5.h[k] * T5.A[j - 1][i - 1]);
                 p.i = i;
+                p.s = sp;
                 p.N = W.N;
                 p.O = W.O;
                 if (di) { p.w = T5.dense + (size_t)i * W.n; p.g = i == 1 ? T5.dense : nullptr; p.hw = (float)T5.h[k]; }
-                HIPCHK(h, launch_tsit5_stage_seed(p, h->stream));
+                HIPCHK(h, launch_erk_stage_seed(p, h->stream));
             }
             if (i == 1 && has_inner(k - 1))
                 if (int rc = dense(k - 1, true)) return rc;

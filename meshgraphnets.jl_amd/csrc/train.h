@@ -265,20 +265,22 @@ struct SolverAdjArgs {
 };
 int solver_adjoint_blocks(int64_t N, int O);
 hipError_t launch_solver_adjoint(const SolverAdjArgs& p, hipStream_t s);
-// solver-based training with Tsit5 (mgn_solver_grad_tsit5), stage i (1 .. 5) of the reverse pass of one step, per element of the [N][O]
-// state, before the VJP of stage i:
-//   ybar_{i+1} <- inflow[n] ? 0 : xbar  (the VJP of stage i + 1 just finished);   kbar <- cb lam + sum_{j>i} ca[j - 1] ybar_j
-//   (cb = h A[7][i], ca[j - 1] = h A[j][i]);   i = 1: lam <- lam + sum_{j=2..6} ybar_j as well.   ybar: [5][N][O], ybar_j at j - 2.
-// Dense saves (a step with interpolated saves, below): w (null: none) is the step's weighted sum W_i, added as kbar += hw w; g (i = 1
-// only, null: none) the sum of the interpolated saves' seeds, added to lam with the ybar.  i = 6 with xbar null is kbar <- cb lam (+ hw w),
-// what the adjoint launch of the state after the step wrote.
-struct Tsit5SeedArgs {
+// solver-based training with an explicit Runge-Kutta tableau of s <= 6 active stages (mgn_solver_grad_tsit5: s = 6; mgn_solver_grad_erk),
+// stage i (1 .. s - 1) of the reverse pass of one step, per element of the [N][O] state, before the VJP of stage i:
+//   ybar_{i+1} <- inflow[n] ? 0 : xbar  (the VJP of stage i + 1 just finished);   kbar <- cb lam + sum_{i<j<=s} ca[j - 1] ybar_j
+//   (cb = h b[i], ca[j - 1] = h A[j][i]);   i = 1: lam <- lam + sum_{j=2..s} ybar_j as well.   ybar: [5][N][O], ybar_j at j - 2.
+// A stage j whose coefficient is exactly 0 is left out of kbar without its ybar being read (i = 1 reads it for the sum); no slot of a
+// stage beyond s is read.
+// Dense saves (Tsit5; a step with interpolated saves, below): w (null: none) is the step's weighted sum W_i, added as kbar += hw w; g
+// (i = 1 only, null: none) the sum of the interpolated saves' seeds, added to lam with the ybar.  i = s with xbar null is
+// kbar <- cb lam (+ hw w), what the adjoint launch of the state after the step wrote.
+struct ErkSeedArgs {
     const float* xbar; const uint8_t* inflow; float* ybar; float* a; float* kbar;
     float cb; float ca[6];
-    int32_t i; int64_t N; int32_t O;
+    int32_t i, s; int64_t N; int32_t O;
     const float* w; const float* g; float hw;
 };
-hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s);
+hipError_t launch_erk_stage_seed(const ErkSeedArgs& p, hipStream_t s);
 // mgn_solver_grad_tsit5 with MGN_TSIT5_DENSE_SAVES: the loss terms of ns <= TSIT5_DENSE_MAX saves interpolated inside one accepted step,
 // xs[s] = x_n + h sum_i b[s][i - 1] k_{n,i}, per element of the [N][O] state.  With ghat_s = -gscale ls[o]^2 (gt[s] - xs[s]) vm[n]:
 //   w[0] (+)= sum_s ghat_s;   w[i] (+)= sum_s b[s][i - 1] ghat_s, i = 1 .. 6   (w: [7][N][O]; accumulate: added to what is there);

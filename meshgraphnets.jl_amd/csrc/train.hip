@@ -2224,9 +2224,11 @@ __global__ __launch_bounds__(256) void k_solver_adjoint(SolverAdjArgs p) {
     }
 }
 
-// ---- solver-based training with Tsit5 (mgn_solver_grad_tsit5): one stage of the reverse pass of a step -----------------------------
-// V consecutive elements per thread (V = 4: dwordx4 loads and stores where N * O and the pointers allow).  The stage index is a kernel
-// argument; the j loop is unrolled over 2 .. 6 with a predicate, so the coefficients stay in scalar registers (no indexed array, no scratch).
+// ---- solver-based training with a tableau (mgn_solver_grad_tsit5, mgn_solver_grad_erk): one stage of the reverse pass of a step ------
+// V consecutive elements per thread (V = 4: dwordx4 loads and stores where N * O and the pointers allow).  The stage index, the stage
+// count and the coefficients are kernel arguments; the j loop is unrolled over 2 .. 6 with predicates, so the coefficients stay in scalar
+// registers (no indexed array, no scratch) and every branch is uniform.  Memory-bound: lam, the VJP output and the ybar of the later
+// stages with a non-zero coefficient are read once, kbar (and ybar_{i+1}; lam for i = 1) written once.
 template <int V>
 __device__ inline void ldv(float (&r)[V], const float* p) {
     if constexpr (V == 4) {
@@ -2248,7 +2250,7 @@ __device__ inline void stv(float* p, const float (&r)[V]) {
 }
 
 template <int V>
-__global__ __launch_bounds__(256) void k_tsit5_stage_seed(Tsit5SeedArgs p) {
+__global__ __launch_bounds__(256) void k_erk_stage_seed(ErkSeedArgs p) {
     const int64_t n = p.N * p.O;
     const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
     if (e >= n) return;                     // n is a multiple of V
@@ -2267,7 +2269,9 @@ __global__ __launch_bounds__(256) void k_tsit5_stage_seed(Tsit5SeedArgs p) {
     for (int q = 0; q < V; ++q) { kb[q] = p.cb * lam[q]; ys[q] = 0.f; }
 #pragma unroll
     for (int j = 2; j <= 6; ++j) {
-        if (j <= p.i) continue;
+        if (j <= p.i || j > p.s) continue;          // (never a slot of a stage the tableau does not have)
+        const float cj = p.ca[j - 1];
+        if (cj == 0.f && p.i != 1) continue;        // no term in kbar, and only stage 1 sums the ybar
         float y[V];
         if (j == p.i + 1 && p.xbar) {
 #pragma unroll
@@ -2275,7 +2279,6 @@ __global__ __launch_bounds__(256) void k_tsit5_stage_seed(Tsit5SeedArgs p) {
         } else {
             ldv<V>(y, p.ybar + (int64_t)(j - 2) * n + e);
         }
-        const float cj = p.ca[j - 1];
 #pragma unroll
         for (int q = 0; q < V; ++q) { kb[q] = fmaf(cj, y[q], kb[q]); ys[q] += y[q]; }
     }
@@ -2300,7 +2303,7 @@ __global__ __launch_bounds__(256) void k_tsit5_stage_seed(Tsit5SeedArgs p) {
 }
 
 // ---- mgn_solver_grad_tsit5 with dense saves: the loss terms of the saves interpolated inside one accepted step ----------------------
-// V consecutive elements per thread, as k_tsit5_stage_seed.  Streaming: per launch 2 ns arrays read (each save's xs and gt once), 7 written
+// V consecutive elements per thread, as k_erk_stage_seed.  Streaming: per launch 2 ns arrays read (each save's xs and gt once), 7 written
 // (+ 7 read when accumulating) and kbar.  The save loop is unrolled over TSIT5_DENSE_MAX with a predicate, so the pointers and the 7
 // weights of every save stay in scalar registers.  The squared errors are summed in double per block: a wave reduction, then the four
 // waves through LDS in a fixed order (k_solver_adjoint's partials, one slot per save).
@@ -2396,14 +2399,15 @@ hipError_t launch_tsit5_dense_adjoint(const Tsit5DenseArgs& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_tsit5_stage_seed(const Tsit5SeedArgs& p, hipStream_t s) {
+hipError_t launch_erk_stage_seed(const ErkSeedArgs& p, hipStream_t s) {
     const int64_t n = p.N * p.O;
     if (n <= 0) return hipSuccess;
+    if (p.s < 1 || p.s > 6 || p.i < 1 || p.i > p.s) return hipErrorInvalidValue;      // ybar holds the five slots of stages 2 .. 6
     auto al16 = [](const void* q) { return q == nullptr || ((uintptr_t)q & 15) == 0; };
     if (n % 4 == 0 && al16(p.xbar) && al16(p.ybar) && al16(p.a) && al16(p.kbar)) {
-        hipLaunchKernelGGL(k_tsit5_stage_seed<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k_erk_stage_seed<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, p);
     } else {
-        hipLaunchKernelGGL(k_tsit5_stage_seed<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k_erk_stage_seed<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
     }
     return hipGetLastError();
 }

@@ -53,6 +53,75 @@ def _host_or_device(a, shape, writable=False):
     return a, f32(a)
 
 
+class ErkTableau:
+    """An explicit Runge-Kutta method as data: the MGN_ERK_TABLEAU_DOUBLES doubles of include/mgn_hip.h that the *_erk entry points take
+    (make one with erk_tableau).  A [s][s] strictly lower triangular, b, c, btilde = b - bhat (zeros without an embedded pair)."""
+
+    def __init__(self, tab, name=None):
+        self.tab = np.ascontiguousarray(tab, dtype=np.float64).reshape(_capi.MGN_ERK_TABLEAU_DOUBLES).copy()
+        self.name = name
+        if _capi.load().mgn_erk_check(self._ptr()) != _capi.MGN_OK:
+            raise ValueError("not an explicit Runge-Kutta tableau the library accepts (mgn_erk_check, include/mgn_hip.h)")
+
+    def _ptr(self):
+        return self.tab.ctypes.data_as(C.POINTER(C.c_double))
+
+    stages = property(lambda self: int(self.tab[0]))
+    order = property(lambda self: int(self.tab[1]))
+    fsal = property(lambda self: bool(self.tab[2]))
+    embedded = property(lambda self: bool(self.tab[3]))
+    betas = property(lambda self: (float(self.tab[4]), float(self.tab[5])))
+    A = property(lambda self: self.tab[6:55].reshape(7, 7)[:self.stages, :self.stages].copy())
+    b = property(lambda self: self.tab[55:55 + self.stages].copy())
+    c = property(lambda self: self.tab[62:62 + self.stages].copy())
+    btilde = property(lambda self: self.tab[69:69 + self.stages].copy())
+
+    def __repr__(self):
+        return "ErkTableau(%s: %d stages, order %d%s%s)" % (self.name or "custom", self.stages, self.order, ", FSAL" if self.fsal else "",
+                                                            ", embedded" if self.embedded else "")
+
+
+def erk_tableau(name_or_A, b=None, c=None, btilde=None, order=None, fsal=False, betas=(0.0, 0.0)):
+    """erk_tableau("RK4") -- one of "Euler", "Heun", "Midpoint", "Ralston", "RK4", "BS3", "DP5", "Tsit5" (mgn_erk_named) -- or
+    erk_tableau(A, b, c[, btilde], order=p[, fsal, betas]): A [s][s] (its strictly lower triangle is used), s <= 7; btilde = b - bhat
+    makes the pair embedded (adaptive steps); betas: the PI controller's (0, 0: the defaults 7/(10 p), 2/(5 p)).  ValueError for a
+    tableau mgn_erk_check refuses."""
+    tab = np.zeros(_capi.MGN_ERK_TABLEAU_DOUBLES, np.float64)
+    if isinstance(name_or_A, str):
+        if name_or_A not in _capi.ERK_NAMES:
+            raise KeyError(name_or_A)
+        rc = _capi.load().mgn_erk_named(_capi.ERK_NAMES[name_or_A], tab.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != _capi.MGN_OK:
+            raise MgnError(rc, "mgn_erk_named(%r)" % name_or_A)
+        return ErkTableau(tab, name_or_A)
+    if b is None or c is None or order is None:
+        raise ValueError("erk_tableau(A, b, c[, btilde], order=p): b, c and order are required")
+    A = np.atleast_2d(np.asarray(name_or_A, np.float64))
+    b, c = np.asarray(b, np.float64).reshape(-1), np.asarray(c, np.float64).reshape(-1)
+    s = b.size
+    if not 1 <= s <= _capi.MGN_ERK_MAX_STAGES or A.shape != (s, s) or c.size != s or (btilde is not None and np.size(btilde) != s):
+        raise ValueError("erk_tableau: A must be [s][s], b, c (and btilde) [s], 1 <= s <= %d" % _capi.MGN_ERK_MAX_STAGES)
+    tab[:6] = s, order, 1.0 if fsal else 0.0, 0.0 if btilde is None else 1.0, betas[0], betas[1]
+    tab[6:55].reshape(7, 7)[:s, :s] = A
+    tab[55:55 + s], tab[62:62 + s] = b, c
+    if btilde is not None:
+        tab[69:69 + s] = np.asarray(btilde, np.float64).reshape(-1)
+    return ErkTableau(tab)
+
+
+def _erk_route(solver, adaptive):
+    """How a rollout's `solver` reaches the library: None for "Euler" / "Tsit5" (mgn_rollout_desc.solver, today's calls), else
+    (ErkTableau, adaptive flag) for the *_erk symbols -- a tableau without an embedded pair ignores `adaptive`, as "Euler" does; one with
+    a pair follows it, as "Tsit5" does."""
+    if isinstance(solver, str):
+        if solver in ("Euler", "Tsit5") or solver not in _capi.ERK_NAMES:
+            return None                                   # (an unknown name: _rollout_desc raises as it always has)
+        solver = erk_tableau(solver)
+    elif not isinstance(solver, ErkTableau):
+        raise TypeError("solver must be a name or an ErkTableau, got %r" % type(solver).__name__)
+    return solver, 1 if (solver.embedded and adaptive) else 0
+
+
 class Engine:
     """One engine handle == one mesh partition on one GPU (rank/nranks select the partition)."""
 
@@ -358,12 +427,13 @@ class Engine:
         return out
 
     def _rollout_desc(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data, abstol,
-                      reltol, inflow_rule, time_type, adaptive=True):
+                      reltol, inflow_rule, time_type, adaptive=True, erk=None):
         """The descriptor of a rollout / rollout_eval call, without `out`; returns (d, the arrays it points into: inflow data last).
-        adaptive=False with "Tsit5": fixed steps of dt (MGN_SOLVER_TSIT5_FIXED; the library refuses dt <= 0); "Euler" ignores it."""
+        adaptive=False with "Tsit5": fixed steps of dt (MGN_SOLVER_TSIT5_FIXED; the library refuses dt <= 0); "Euler" ignores it.
+        erk (_erk_route's answer, not None): the call goes to an *_erk symbol, which does not read d.solver."""
         O, Fn = self.cfg.O, self.cfg.Fn
         d = _capi.MgnRolloutDesc()
-        d.solver = {"Euler": _capi.MGN_SOLVER_EULER, "Tsit5": _capi.MGN_SOLVER_TSIT5}[solver]
+        d.solver = {"Euler": _capi.MGN_SOLVER_EULER, "Tsit5": _capi.MGN_SOLVER_TSIT5}[solver] if erk is None else 0
         if solver == "Tsit5" and not adaptive:
             d.solver = _capi.MGN_SOLVER_TSIT5_FIXED
         d.t0, d.t1, d.dt, d.saves_dt, d.n_saves, d.abstol, d.reltol = t0, t1, dt, saves_dt, n_saves, abstol, reltol
@@ -392,12 +462,19 @@ class Engine:
         saves_dt, saves between step ends from Tsit5's dense output, no error norm (MGN_SOLVER_TSIT5_FIXED, include/mgn_hip.h).
         inflow_rule: "reference" = `floor(Int, t / saves_dt) + 1` in the solver's time type, no tolerance, out of range raises
         (src/solve.jl:151); "tolerant" = + 1e-3, clamped (step k reads frame k).  time_type: np.float32 (the example's `0.0f0:0.01f0:5.99f0`) or np.float64.
+        solver may also be "Heun", "Midpoint", "Ralston", "RK4", "BS3", "DP5" or an ErkTableau (erk_tableau): any explicit Runge-Kutta
+        method of up to seven stages, through mgn_rollout_erk.  Without an embedded pair: fixed steps of dt whatever `adaptive` says;
+        with one ("BS3", "DP5"): `adaptive` as for "Tsit5".  Fixed steps of a tableau need saves_dt / dt integral (no dense output).
         Returns (sol_u [n_saves][N][O], stats dict)."""
+        erk = _erk_route(solver, adaptive)
         d, keep = self._rollout_desc(solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data,
-                                     abstol, reltol, inflow_rule, time_type, adaptive)
+                                     abstol, reltol, inflow_rule, time_type, adaptive, erk)
         out = np.zeros((n_saves, self.N, self.cfg.O), np.float32)
         d.out = f32(out)
-        self._chk(self.lib.mgn_rollout(self.h, C.byref(d)))
+        if erk is None:
+            self._chk(self.lib.mgn_rollout(self.h, C.byref(d)))
+        else:
+            self._chk(self.lib.mgn_rollout_erk(self.h, C.byref(d), erk[0]._ptr(), erk[1]))
         del keep
         return out, dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)
 
@@ -412,10 +489,12 @@ class Engine:
         with its vector of node indices is this, not "every component of node sel[i]"; None: all N * O elements.  mse_time_out: a
         NumPy array or device tensor [N][O] to receive mse_time (default: a new NumPy array).
         Returns {"val_loss": mean(mse_time[sel]), "mse_save" [n_saves][O] float64 (mean over the nodes), "mse_time" [N][O] float32
-        (mean over the saves), "pred" [n_saves][N][O] or None, "stats"}.  adaptive: as rollout's."""
+        (mean over the saves), "pred" [n_saves][N][O] or None, "stats"}.  solver, adaptive: as rollout's (a tableau goes through
+        mgn_rollout_eval_erk)."""
         O = self.cfg.O
+        erk = _erk_route(solver, adaptive)
         d, keep = self._rollout_desc(solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask, inflow_data,
-                                     abstol, reltol, inflow_rule, time_type, adaptive)
+                                     abstol, reltol, inflow_rule, time_type, adaptive, erk)
         e = _capi.MgnRolloutEvalDesc()
         if gt is inflow_data:                           # validation: the ground truth is the inflow data -- one array, one pointer
             gt_keep, e.gt, e.n_gt = keep[-1], d.inflow_data, d.n_frames
@@ -432,7 +511,10 @@ class Engine:
                                                writable=True)
         si = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1) if sel is not None else None
         e.sel, e.n_sel, e.sel_index_base = i32(si), (si.size if si is not None else 0), int(sel_index_base)
-        self._chk(self.lib.mgn_rollout_eval(self.h, C.byref(d), C.byref(e)))
+        if erk is None:
+            self._chk(self.lib.mgn_rollout_eval(self.h, C.byref(d), C.byref(e)))
+        else:
+            self._chk(self.lib.mgn_rollout_eval_erk(self.h, C.byref(d), C.byref(e), erk[0]._ptr(), erk[1]))
         del keep, gt_keep
         return {"val_loss": e.val_loss, "mse_save": mse_save, "mse_time": mse_time, "pred": pred,
                 "stats": dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)}
@@ -569,6 +651,36 @@ class Engine:
             return self.solver_grad_tsit5(x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, adaptive, abstol, reltol, val_mask,
                                           inflow_mask, inflow_data, loss_scale, cont_target, cont_weight, inflow_rule, time_type, want_pred,
                                           out, o.n_steps, max_store_bytes, dense_saves)
+        del keep
+        nrec = min(int(o.n_steps), int(cap))
+        stats = dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs, n_steps=int(o.n_steps), step_t=st[:nrec].copy(),
+                     step_h=sh[:nrec].copy(), stored_bytes=int(o.stored_bytes))
+        if want_pred:
+            stats["pred"] = pred
+        return gs, loss.value, stats
+
+    def solver_grad_erk(self, tableau, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt, val_mask=None, inflow_mask=None,
+                        inflow_data=None, loss_scale=None, cont_target=None, cont_weight=0.0, inflow_rule="reference", time_type=np.float32,
+                        want_pred=False, out=None, step_cap=None, max_store_bytes=0):
+        """solver_grad_tsit5(adaptive=False) for any explicit Runge-Kutta method with at most six active stages (mgn_solver_grad_erk):
+        tableau is an ErkTableau or one of erk_tableau's names.  Fixed steps of dt > 0 on rollout's grid for a tableau (saves_dt / dt
+        integral), the inflow rows written into copies; the gradient is the exact discrete adjoint of the computed solution.
+        Returns (grads, loss, stats) as solver_grad_tsit5 does."""
+        tab = tableau if isinstance(tableau, ErkTableau) else erk_tableau(tableau)
+        d, keep, p_gt, ls, p_ct, gs, p_gs, pred = self._solver_desc("Euler", x0, node_type_onehot, ef_raw, gt, t0, t1, dt, saves_dt, n_saves,
+                                                                   val_mask, inflow_mask, inflow_data, loss_scale, cont_target, inflow_rule,
+                                                                   time_type, want_pred, out)      # (d.solver is not read)
+        o = _capi.MgnSolverGradOpts()
+        o.adaptive, o.max_store_bytes = 0, int(max_store_bytes)
+        cap = step_cap
+        if cap is None:
+            cap = int(round((float(t1) - float(t0)) / float(dt))) + 2 if dt > 0 else 1
+        st, sh = np.zeros(max(int(cap), 1), np.float64), np.zeros(max(int(cap), 1), np.float64)
+        o.step_cap = int(cap)
+        o.step_t, o.step_h = st.ctypes.data_as(C.POINTER(C.c_double)), sh.ctypes.data_as(C.POINTER(C.c_double))
+        loss = C.c_float()
+        self._chk(self.lib.mgn_solver_grad_erk(self.h, C.byref(d), tab._ptr(), C.byref(o), p_gt, f32(ls), p_ct, float(cont_weight), p_gs,
+                                               self.param_count, C.byref(loss)))
         del keep
         nrec = min(int(o.n_steps), int(cap))
         stats = dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs, n_steps=int(o.n_steps), step_t=st[:nrec].copy(),
@@ -1007,11 +1119,15 @@ class GroupEngine:
     def rollout(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt=0.0, val_mask=None,
                 inflow_mask=None, inflow_data=None, abstol=1e-6, reltol=1e-3, inflow_rule="reference", time_type=np.float32, adaptive=True):
         """Engine.rollout on the partitioned mesh: (sol_u [n_saves][N][O], stats)."""
+        erk = _erk_route(solver, adaptive)
         d, keep = Engine._rollout_desc(self, solver, x0, node_type_onehot, ef_raw, t0, t1, saves_dt, n_saves, dt, val_mask, inflow_mask,
-                                       inflow_data, abstol, reltol, inflow_rule, time_type, adaptive)
+                                       inflow_data, abstol, reltol, inflow_rule, time_type, adaptive, erk)
         out = np.zeros((n_saves, self.N, self.cfg.O), np.float32)
         d.out = f32(out)
-        self._chk(self.lib.mgn_group_rollout(self.g, C.byref(d)))
+        if erk is None:
+            self._chk(self.lib.mgn_group_rollout(self.g, C.byref(d)))
+        else:
+            self._chk(self.lib.mgn_group_rollout_erk(self.g, C.byref(d), erk[0]._ptr(), erk[1]))
         del keep
         return out, dict(n_accept=d.n_accept, n_reject=d.n_reject, n_rhs=d.n_rhs)
 

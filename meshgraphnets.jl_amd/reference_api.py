@@ -25,6 +25,7 @@ import os
 
 import numpy as np
 
+from . import _capi
 from .engine import FeatureGraph
 
 F32 = np.float32
@@ -544,11 +545,15 @@ def multiple_shooting_ranges(T, interval_size):
 
 
 def _solver_window(eng, solver, adaptive, abstol, reltol, x0, node_type_onehot, ef_raw, gt, t0, t1, solver_dt, saves_dt, n_saves, **kw):
-    """One solved window through Engine.solver_grad (Euler) or Engine.solver_grad_tsit5 (Tsit5): (gs, loss)."""
-    if solver == "Euler":
+    """One solved window through Engine.solver_grad (Euler), Engine.solver_grad_tsit5 (Tsit5) or, for another method Engine.rollout
+    takes ("RK4", "BS3", ..., an ErkTableau), Engine.solver_grad_erk with fixed steps of solver_dt: (gs, loss)."""
+    if isinstance(solver, str) and solver == "Euler":
         return eng.solver_grad(x0, node_type_onehot, ef_raw, gt, t0, t1, solver_dt, saves_dt, n_saves, **kw)
-    if solver != "Tsit5":
-        raise ValueError(f"solver must be 'Euler' or 'Tsit5', got {solver!r}")
+    if not (isinstance(solver, str) and solver == "Tsit5"):
+        if isinstance(solver, str) and solver not in _capi.ERK_NAMES:
+            raise ValueError(f"solver must be 'Euler', 'Tsit5', another of {sorted(_capi.ERK_NAMES)} or an ErkTableau, got {solver!r}")
+        gs, loss, _ = eng.solver_grad_erk(solver, x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, solver_dt, **kw)
+        return gs, loss
     gs, loss, _ = eng.solver_grad_tsit5(x0, node_type_onehot, ef_raw, gt, t0, t1, saves_dt, n_saves, dt=solver_dt or 0.0, adaptive=adaptive,
                                         abstol=abstol, reltol=reltol, **kw)
     return gs, loss
@@ -563,12 +568,13 @@ def train_step_solver_training(eng, gt, node_type_onehot, ef_raw, tstart, dt, ts
     rows overwritten inside the right-hand side from inflow_data [frames][N][O] (default: gt itself, data[field] of ode_func_train,
     src/solve.jl:101-117); solver_dt: the Euler step (default dt, the example's tstops = saveat).  solver="Tsit5":
     Engine.solver_grad_tsit5, adaptive (first step solver_dt, default 0: the Hairer-Wanner start; abstol / reltol) or, with
-    adaptive=False, fixed steps of solver_dt (default dt).  Returns (gs, loss): the discrete adjoint of the computed solution (Tsit5: with
-    the accepted steps held fixed)."""
+    adaptive=False, fixed steps of solver_dt (default dt).  solver="RK4", "Heun", "BS3", "DP5", ... or an ErkTableau:
+    Engine.solver_grad_erk, fixed steps of solver_dt (default dt) whatever `adaptive` says.  Returns (gs, loss): the discrete adjoint of
+    the computed solution (Tsit5: with the accepted steps held fixed)."""
     n_saves = _range_length(tstart, dt, tstop)
     if inflow_mask is not None and inflow_data is None:
         inflow_data = gt
-    sdt = solver_dt if (solver == "Tsit5" and adaptive) else (solver_dt or dt)
+    sdt = solver_dt if (isinstance(solver, str) and solver == "Tsit5" and adaptive) else (solver_dt or dt)
     return _solver_window(eng, solver, adaptive, abstol, reltol, np.asarray(gt[0]), node_type_onehot, ef_raw, gt[:n_saves], tstart, tstop,
                           sdt, dt, n_saves, val_mask=val_mask, inflow_mask=inflow_mask, inflow_data=inflow_data, loss_scale=n_scale,
                           inflow_rule=inflow_rule, time_type=time_type, out=out)
@@ -597,6 +603,8 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
     if interpolate_saves and batched:
         raise ValueError("interpolate_saves solves window by window: Engine.shooting_grad steps onto every save (batched must be False)")
     dense = {"dense_saves": True} if interpolate_saves else {}
+    if batched and solver not in ("Euler", "Tsit5"):
+        raise ValueError("batched=True (Engine.shooting_grad) drives 'Euler' and 'Tsit5'; other methods go window by window")
     if batched and not (solver == "Tsit5" and adaptive):
         gs, loss = eng.shooting_grad(node_type_onehot, ef_raw, gt, ranges, [_range_at(tstart, dt, a, time_type) for a, _ in ranges],
                                      [_range_at(tstart, dt, b, time_type) for _, b in ranges], solver_dt or dt, dt, val_mask=val_mask,
@@ -618,8 +626,9 @@ def train_step_multiple_shooting(eng, gt, node_type_onehot, ef_raw, tstart, dt, 
 
 
 def _fixed_step_kw(fixed_step, solver, step):
-    """rollout_eval's extra keywords for the reference's `adaptive = false, dt = dt` branch: Tsit5 with a step given, when asked for"""
-    return {"adaptive": False} if (fixed_step and solver == "Tsit5" and step) else {}
+    """rollout_eval's extra keywords for the reference's `adaptive = false, dt = dt` branch: Tsit5 -- or any other method Engine.rollout
+    takes ("RK4", "BS3", "DP5", ..., an ErkTableau) -- with a step given, when asked for; "Euler" steps that way already"""
+    return {"adaptive": False} if (fixed_step and not (isinstance(solver, str) and solver == "Euler") and step) else {}
 
 
 def validation_step(eng, data_gt, node_type_onehot, ef_raw, sim_interval, mask, solver="Tsit5", solver_dt=None, val_mask=None,
@@ -635,6 +644,7 @@ def validation_step(eng, data_gt, node_type_onehot, ef_raw, sim_interval, mask, 
     adaptive = false, dt = dt, saveat = saves)` whatever the solver, which is how _validation_step hands `solver_valid_dt` on.  With
     solver="Tsit5" and a solver_dt it passes adaptive=False (fixed steps of solver_dt, saves from the dense output); "Euler" steps that way
     already.  The default False is kept for the results this function has always returned: adaptive Tsit5 with solver_dt as its first step.
+    solver: any `solver` of Engine.rollout ("Heun", "Midpoint", "Ralston", "RK4", "BS3", "DP5", an ErkTableau); fixed_step as for "Tsit5".
     Returns (loss, None, None) or, with want_arrays, (loss, gt [n_saves][N][O], prediction [n_saves][N][O])."""
     tstart, dt, tstop = sim_interval
     n_saves = _range_length(tstart, dt, tstop)
@@ -659,8 +669,8 @@ def rollout_errors(eng, data_gt, node_type_onehot, ef_raw, start, stop, dt, save
     dt: the fixed solver step, or None (adaptive Tsit5), as eval_network!'s.  fixed_step: the reference's own branch on dt
     (src/solve.jl:57-61) is fixed_step=True whenever a step is given (`adaptive = false, dt = dt` whatever the solver); with solver="Tsit5"
     and a dt it passes adaptive=False.  The default False is kept for the results this function has always returned (adaptive Tsit5
-    with dt as its first step).  Returns (error [n_saves][O] float64, {horizon: (mse,
-    cum_mse, cum_rmse)})."""
+    with dt as its first step).  solver: any `solver` of Engine.rollout, a tableau included; fixed_step as for "Tsit5".
+    Returns (error [n_saves][O] float64, {horizon: (mse, cum_mse, cum_rmse)})."""
     saves = np.asarray(saves, dtype=time_type)
     n_saves = int(saves.size)
     saves_dt = float(saves[1] - saves[0]) if n_saves > 1 else float(stop - start) or 1.0
