@@ -851,6 +851,9 @@ int mgn_group_latents_randn(mgn_group* g, uint64_t seed);
 int mgn_group_processor_steps_dev(mgn_group* g, int32_t nsteps);
 int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, double* sumsq_v, double* sumsq_e);
 int mgn_group_synchronize(mgn_group* g);
+/* Replica groups (a minibatch of datapoints split over devices that each hold the whole mesh) and the group forms of Adam and of the
+ * resident parameters: seven more calls on the group, declared and documented in the file next to this one.                      */
+#include "mgn_hip_replica.h"
 
 /* ---- the benchmarked unit: nsteps processor steps on given latents -------------
  * v [N][L], e [E][L] in caller order, updated in place (host buffers).                          */

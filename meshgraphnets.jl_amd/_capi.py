@@ -207,6 +207,19 @@ PROTOTYPES = {
     "mgn_profile_enable": (C.c_int, [_H, C.c_int32]),
     "mgn_profile_read": (C.c_int, [_H, _f64p, _i64p]),
 }
+# The symbols of include/mgn_hip_replica.h (the part of the header mgn_hip.h includes): replica groups and the group forms of Adam and
+# of the resident parameters.  load() binds them exactly as it binds PROTOTYPES.  A table of their own, as they have a file of their
+# own: PROTOTYPES mirrors the symbol list read from mgn_hip.h itself (tests/test_abi_and_host.py), and the checks of the handle forms
+# (tests/test_params_dev_host.py, tests/test_step_datapoints_host.py) pin that it holds no group form of them.
+REPLICA_PROTOTYPES = {
+    "mgn_group_create_replicas": (C.c_int, [C.POINTER(MgnConfig), C.c_int32, _i32p, C.POINTER(_H)]),
+    "mgn_group_step_datapoints": (C.c_int, [_H, _i32p, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t, _f32p, _f32p]),
+    "mgn_group_set_params_dev": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_group_get_params_dev": (C.c_int, [_H, C.c_int32, _f32p, C.c_size_t]),
+    "mgn_group_adam_init": (C.c_int, [_H, C.POINTER(MgnAdamDesc)]),
+    "mgn_group_adam_update": (C.c_int, [_H, _f32p, C.c_size_t]),
+    "mgn_group_adam_state": (C.c_int, [_H, C.c_int32, _f32p, _f32p, _f64p]),
+}
 
 _lib = None
 
@@ -230,7 +243,7 @@ def load(path: str | None = None):
         except ImportError:
             pass
     lib = C.CDLL(p, mode=C.RTLD_LOCAL)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(REPLICA_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

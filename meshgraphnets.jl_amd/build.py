@@ -21,7 +21,7 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 REF_LIB = os.path.join(ORACLE_DIR, "_build", "libmgn_ref.so")
 
 HIP_SOURCES = ["kernels.hip", "split.hip", "train.hip", "mgn_api.cpp", "mgn_solve.cpp", "mgn_train.cpp", "graph_host.cpp", "graph_prologue.cpp", "tfrecord.cpp", "comm.cpp", "comm_pull.hip", "mgn_group.cpp", "graph_dev.hip"]
-HIP_HEADERS = ["kernels.h", "graph_host.h", "frag.hpp", "tile_common.hpp", "split_common.hpp", "engine_internal.h", "train.h", "comm.h", "graph_dev.h", "launch.hpp", os.path.join(ROOT, "include", "mgn_hip.h")]
+HIP_HEADERS = ["kernels.h", "graph_host.h", "frag.hpp", "tile_common.hpp", "split_common.hpp", "engine_internal.h", "train.h", "comm.h", "graph_dev.h", "launch.hpp", os.path.join(ROOT, "include", "mgn_hip.h"), os.path.join(ROOT, "include", "mgn_hip_replica.h")]
 
 
 def _newer(target, deps):

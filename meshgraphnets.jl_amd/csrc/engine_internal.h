@@ -333,6 +333,15 @@ int solver_grad_run(mgn_engine* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o,
 // (tab: mgn_rollout_eval_erk's tableau, checked here before anything else, and its step mode; null: the solver d->solver names)
 int rollout_eval_run(mgn_engine* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions, const double* tab = nullptr, int32_t adaptive = 0);
 int solver_prepare_partitions(mgn_engine* h, const char* who, size_t n_grads);   // solver_prepare for a call that serves partitions too
+// mgn_train.cpp, for mgn_group_step_datapoints (mgn_group.cpp).
+// step_datapoints_check: every refusal of mgn_step_datapoint (share == 1) or mgn_step_datapoints (share > 1) for a list of B datapoints
+// of which this handle takes at most `share`, with that call's status, in its order; host work only -- nothing is launched, packed or
+// allocated on the device, no collective is entered.
+// datapoint_accumulate: datapoint_norms(h, t, true, h->stream), the online normalisers' accumulation of one datapoint (what
+// mgn_step_datapoint(s) runs per entry with accumulate != 0); the handle has passed step_datapoints_check.
+int step_datapoints_check(mgn_engine* h, const char* who, const int32_t* datapoints, int32_t B, int32_t share, const int32_t* mask, int64_t nmask,
+                          int32_t mask_index_base, size_t n_grads);
+int datapoint_accumulate(mgn_engine* h, int32_t t);
 #pragma GCC visibility pop
 
 #define HIPCHK(h, expr)                                                                              \

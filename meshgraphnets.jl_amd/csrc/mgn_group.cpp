@@ -1,6 +1,8 @@
 // mgn_group: one handle that drives the P partitions of a mesh from one caller thread (include/mgn_hip.h, "one process, P partitions").
 // Inside it is what the tests' thread-ranks are: one worker thread per rank, each owning an ordinary rank handle, joined by one
 // MGN_COMM_LOCAL communicator (comm.cpp).  A group call is the same mgn_* call on every worker.
+// A replica group (mgn_group_create_replicas) is the same machinery around P whole copies of the model: every handle is rank 0 of 1,
+// the communicator is the group's own, and mgn_group_step_datapoints splits a minibatch over the replicas (below).
 #include <atomic>
 #include <condition_variable>
 #include <cstdarg>
@@ -23,6 +25,16 @@ struct mgn_group {
     unsigned char id[MGN_COMM_ID_BYTES] = {};
     bool have_comm = false;
     int32_t N = 0;                                   // of the last mgn_group_set_graph (sizes of the scratch outputs)
+    // A replica group (mgn_group_create_replicas): every handle is a whole one-partition handle (rank 0 of 1), and the communicator that
+    // joins them belongs to the group, one end per worker -- the handles themselves have none.
+    bool replicas = false;
+    std::vector<mgn::Comm*> rcomm;
+    std::vector<std::shared_ptr<std::mutex>> turn;   // [rank]: shared by the replicas on one device (run())
+    // mgn_group_step_datapoints, per rank, on the rank's device: res the gradient the call leaves (what mgn_group_adam_update(NULL) reads);
+    // replica groups of more than one: share, the replica's own gradient as it goes into the gather, and all, the gathered [P][stride]
+    struct RankBufs { DevBuf res, share, all; };
+    std::unique_ptr<RankBufs[]> bufs;
+    bool have_grad = false;                          // res holds the gradient of a successful mgn_group_step_datapoints
 
     // dispatch: `job` is run by every worker (or by `only` alone) for ticket `epoch`; the caller waits for `left` to reach 0
     std::vector<std::thread> workers;
@@ -90,15 +102,33 @@ struct mgn_group {
         if (P == 1) return MGN_OK;
         if (int r = mgn_comm_unique_id(id, MGN_COMM_LOCAL)) { err = mgn_last_error(nullptr); return r; }
         have_comm = true;
+        if (replicas) {
+            dispatch([this](int k) {
+                delete rcomm[k];
+                std::string why;
+                rcomm[k] = mgn::comm_create(id, MGN_COMM_LOCAL, k, P, !host_only, why);
+                return rcomm[k] ? MGN_OK : mgn::fail(h[k], MGN_E_RCCL, "the replicas' communicator: %s", why.c_str());
+            }, -1);
+            return verdict();
+        }
         dispatch([this](int k) {
             (void)mgn_comm_destroy(h[k]);
             return mgn_comm_init(h[k], id, MGN_COMM_ID_BYTES, MGN_COMM_LOCAL);
         }, -1);
         return verdict();
     }
-    // every rank runs f(rank, handle); on failure the communicator is replaced before the status goes back
-    int run(const std::function<int(int, mgn_handle*)>& f) {
-        dispatch([&](int k) { return f(k, h[k]); }, -1);
+    // every rank runs f(rank, handle); on failure the communicator is replaced before the status goes back.
+    // Replicas that share a device take turns (turn[k]: one mutex per distinct ordinal) unless f holds a collective, which needs all of
+    // them inside at once.  A replica is a one-partition handle, and those capture and replay hipGraphs with parallel branches (the
+    // training step's second stream, the small-mesh inference passes); partitions run eagerly.  Two workers capturing on one device at
+    // the same time have ended in a segmentation fault inside a worker thread (docs/experiments.md), so a device's graph capture,
+    // instantiation and replay are entered by one thread at a time.  Replicas on different devices do not wait for each other.
+    int run(const std::function<int(int, mgn_handle*)>& f, bool collective = false) {
+        dispatch([&](int k) {
+            if (!replicas || collective || !turn[k]) return f(k, h[k]);
+            std::lock_guard<std::mutex> mine(*turn[k]);
+            return f(k, h[k]);
+        }, -1);
         const int r = verdict();
         if (r != MGN_OK && P > 1) {
             const std::string keep = err;
@@ -195,11 +225,70 @@ int mgn_group_create(const mgn_config* cfg, int32_t nranks, const int32_t* devic
     return MGN_OK;
 } catch (...) { return create_fail(MGN_E_OOM, "mgn_group_create: host allocation failed"); }
 
+// A replica group: mgn_group_create's workers and dispatch around P whole copies of the model (every handle rank 0 of 1, so the
+// single-partition modes are legal), joined by a communicator of the group's own (mgn_group::connect).
+int mgn_group_create_replicas(const mgn_config* cfg, int32_t nreplicas, const int32_t* devices, mgn_group** out) try {
+    const char* who = "mgn_group_create_replicas";
+    if (!out) return create_fail(MGN_E_ARG, std::string(who) + ": null out pointer");
+    *out = nullptr;
+    if (!cfg || !devices) return create_fail(MGN_E_ARG, std::string(who) + ": null argument");
+    if (nreplicas < 1 || nreplicas > mgn::COMM_MAX_RANKS) return create_fail(MGN_E_ARG, std::string(who) + ": nreplicas must be 1 .. 64");
+    static_assert(mgn::REPLICA_FOLD_MAX == mgn::COMM_MAX_RANKS, "the fold's weight table holds the communicator's largest group");
+    int none = 0;
+    for (int k = 0; k < nreplicas; ++k) {
+        if (devices[k] < 0 && devices[k] != MGN_DEVICE_NONE)
+            return create_fail(MGN_E_ARG, std::string(who) + ": devices[] holds HIP ordinals (or MGN_DEVICE_NONE for every replica)");
+        none += devices[k] == MGN_DEVICE_NONE;
+    }
+    if (none != 0 && none != nreplicas) return create_fail(MGN_E_ARG, std::string(who) + ": MGN_DEVICE_NONE for some replicas only");
+    std::unique_ptr<mgn_group> g(new mgn_group());
+    g->cfg = *cfg;
+    g->P = nreplicas;
+    g->replicas = true;
+    g->host_only = none != 0;
+    g->devices.assign(devices, devices + nreplicas);
+    g->h.assign(nreplicas, nullptr);
+    g->rcomm.assign(nreplicas, nullptr);
+    g->turn.assign(nreplicas, nullptr);
+    for (int k = 0; k < nreplicas; ++k) {                 // one turn-taking mutex per distinct device (mgn_group::run)
+        for (int j = 0; j < k && !g->turn[k]; ++j)
+            if (devices[j] == devices[k]) g->turn[k] = g->turn[j];
+        if (!g->turn[k]) g->turn[k] = std::make_shared<std::mutex>();
+    }
+    g->rc.assign(nreplicas, MGN_OK);
+    g->order.assign(nreplicas, 0);
+    g->scratch.resize(nreplicas);
+    for (int k = 0; k < nreplicas; ++k) g->workers.emplace_back([p = g.get(), k] { p->work(k); });
+    int rc = MGN_OK;
+    std::string why;
+    for (int k = 0; k < nreplicas && rc == MGN_OK; ++k) {   // one at a time: the text of a failed mgn_create is process-wide
+        g->dispatch([&](int r) {
+            mgn_config c = g->cfg;
+            c.rank = 0;
+            c.nranks = 1;
+            c.device = g->devices[r];
+            const int e = mgn_create(&c, &g->h[r]);
+            if (e != MGN_OK) why = "replica " + std::to_string(r) + ": " + mgn_last_error(nullptr);
+            return e;
+        }, k);
+        rc = g->rc[k];
+    }
+    if (rc == MGN_OK && (rc = g->connect()) != MGN_OK) why = g->err;
+    if (rc != MGN_OK) {
+        mgn_group_destroy(g.release());
+        return create_fail(rc, std::string(who) + ": " + why);
+    }
+    *out = g.release();
+    return MGN_OK;
+} catch (...) { return create_fail(MGN_E_OOM, "mgn_group_create_replicas: host allocation failed"); }
+
 void mgn_group_destroy(mgn_group* g) {
     if (!g) return;
     try {
         if (!g->workers.empty()) {
             g->dispatch([g](int k) {                  // each rank's handle goes where it was made and used
+                if (g->bufs) { g->bufs[k].res.release(); g->bufs[k].share.release(); g->bufs[k].all.release(); }
+                if (k < (int)g->rcomm.size()) { delete g->rcomm[k]; g->rcomm[k] = nullptr; }
                 if (g->h[k]) mgn_destroy(g->h[k]);
                 g->h[k] = nullptr;
                 return MGN_OK;
@@ -492,7 +581,7 @@ int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, doubl
         });
         if (rc != MGN_OK) return rc;
         double acc[4] = {0, 0, 0, 0};
-        for (int k = 0; k < g->P; ++k)                       // ascending rank order: repeatable
+        for (int k = 0; k < (g->replicas ? 1 : g->P); ++k)   // ascending rank order: repeatable (replicas hold the same latents: replica 0's sums)
             for (int i = 0; i < 4; ++i) acc[i] += part[(size_t)4 * k + i];
         if (sum_v) *sum_v = acc[0];
         if (sum_e) *sum_e = acc[1];
@@ -504,6 +593,143 @@ int mgn_group_latents_checksum(mgn_group* g, double* sum_v, double* sum_e, doubl
 
 int mgn_group_synchronize(mgn_group* g) {
     GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_synchronize(h); }); } GROUP_CATCH(g)
+}
+
+// ---- a minibatch of datapoints over the group, and Adam in place (include/mgn_hip_replica.h) ----
+// Replica group of P > 1: the list is split into contiguous chunks in listed order (replica k: B_k = B / P + (k < B % P) entries from
+// k (B / P) + min(k, B % P)); every replica runs the plain handle call on its chunk with a device buffer of the group's as grads, one
+// allgather brings all of them to every replica and launch_replica_fold writes their weighted sum into the rank's resident buffer.
+// Everything else (one replica, a partition group) is the handle call itself with the resident buffer as grads.
+// Every check is made here, on the caller's thread and for every rank, before a worker is woken: no rank can be left in a collective by
+// a refusal.  A share that fails behind the checks (an allocation) ends the call before the gather is entered; a failure inside the gather
+// releases the peers through the group's abort, as everywhere.
+int mgn_group_step_datapoints(mgn_group* g, const int32_t* datapoints, int32_t B, int32_t accumulate, const int32_t* mask, int64_t nmask,
+                              int32_t mask_index_base, float* grads, size_t n_grads, float* loss, float* losses) {
+    GROUP_TRY(g) {
+        const char* who = "mgn_group_step_datapoints";
+        if (!datapoints || !mask || !loss) return gfail(g, MGN_E_ARG, "mgn_group_step_datapoints: null argument");
+        if (B < 1) return gfail(g, MGN_E_ARG, "mgn_group_step_datapoints: B must be at least 1");
+        const int P = g->P;
+        const bool split = g->replicas && P > 1;
+        if (!g->replicas && P > 1 && B > 1) return gfail(g, MGN_E_STATE, "mgn_group_step_datapoints with B > 1 drives one partition (or a replica group)");
+        const int32_t q = split ? B / P : B, r = split ? B % P : 0;
+        const int32_t share = q + (r > 0 ? 1 : 0);                      // the largest share: its rule is the call's
+        if (share > MGN_DATAPOINT_BATCH_MAX)
+            return gfail(g, MGN_E_ARG, ("mgn_group_step_datapoints: a share of " + std::to_string(share) + " datapoints is more than MGN_DATAPOINT_BATCH_MAX").c_str());
+        for (int k = 0; k < P; ++k)
+            if (const int rc = mgn::step_datapoints_check(g->h[k], who, datapoints, B, share, mask, nmask, mask_index_base, n_grads)) {
+                g->err = "rank " + std::to_string(k) + ": " + mgn_last_error(g->h[k]);
+                return rc;
+            }
+        if (!g->bufs) g->bufs.reset(new mgn_group::RankBufs[P]);
+        g->have_grad = false;
+        std::vector<float> own_losses;
+        float* const L = losses ? losses : (own_losses.assign((size_t)B, 0.f), own_losses.data());
+        const size_t n = n_grads, stride = (size_t)mgn::replica_fold_stride((int64_t)n);
+        mgn::ReplicaFoldW w{};
+        uint64_t active = 0;
+        auto first_of = [&](int k) { return k * q + (k < r ? k : r); };
+        auto count_of = [&](int k) { return split ? q + (k < r ? 1 : 0) : B; };
+        for (int k = 0; split && k < P; ++k)
+            if (count_of(k) > 0) {
+                w.w[k] = (double)count_of(k) / (double)B;
+                active |= (uint64_t)1 << k;
+            }
+        float mean0 = 0.f;                                               // rank 0's, where the handle call takes the whole list
+        const int rc = g->run([&](int k, mgn_handle* h) {
+            return guarded(h, [&]() -> int {
+                mgn_group::RankBufs& rb = g->bufs[k];
+                HIPCHK(h, rb.res.ensure(stride * 4));
+                float* gk = rb.res.as<float>();
+                if (split) {
+                    HIPCHK(h, rb.share.ensure(stride * 4));
+                    HIPCHK(h, rb.all.ensure((size_t)P * stride * 4));
+                    gk = rb.share.as<float>();
+                    // accumulate first, normalise afterwards: all B, in listed order, on every replica; the share then runs without
+                    if (accumulate)
+                        for (int32_t b = 0; b < B; ++b)
+                            if (int e = mgn::datapoint_accumulate(h, datapoints[b])) return e;
+                }
+                const int32_t acc = split ? 0 : accumulate, s0 = split ? first_of(k) : 0, Bk = count_of(k);
+                float mean = 0.f, one = 0.f;                             // (ranks other than 0 of a partition group compute the same loss)
+                float* const Lk = split || k == 0 ? L + s0 : &one;
+                int e = MGN_OK;
+                if (Bk == 1) e = mgn_step_datapoint(h, datapoints[s0], acc, mask, nmask, mask_index_base, gk, n, Lk);
+                else if (Bk > 1) e = mgn_step_datapoints(h, datapoints + s0, Bk, acc, mask, nmask, mask_index_base, gk, n, &mean, Lk);
+                if (e != MGN_OK) return e;
+                if (k == 0) mean0 = mean;
+                if (split) return MGN_OK;                                // (the gather is the second phase)
+                if (k == 0 && grads) HIPCHK(h, hipMemcpyAsync(grads, rb.res.p, n * 4, hipMemcpyDefault, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                return MGN_OK;
+            });
+        });
+        if (rc != MGN_OK) return rc;
+        // The gather and the fold, every replica at once: launches and event calls only, what the ranks of a partition group issue side
+        // by side.  The shares above ran under mgn_group::run's turns (replicas that share a device), so they come as a phase of their own.
+        if (split) {
+            const int rc2 = g->run([&](int k, mgn_handle* h) {
+                return guarded(h, [&]() -> int {
+                    mgn_group::RankBufs& rb = g->bufs[k];
+                    if (g->rcomm[k]->allgather(rb.share.p, stride * 4, rb.all.p, h->stream) != 0)
+                        return mgn::fail(h, MGN_E_RCCL, "%s: allgather of the replicas' gradients: %s", who, g->rcomm[k]->err.c_str());
+                    HIPCHK(h, mgn::launch_replica_fold(rb.all.as<float>(), P, (int64_t)n, w, active, rb.res.as<float>(), h->stream));
+                    if (k == 0 && grads) HIPCHK(h, hipMemcpyAsync(grads, rb.res.p, n * 4, hipMemcpyDefault, h->stream));
+                    HIPCHK(h, hipStreamSynchronize(h->stream));
+                    return MGN_OK;
+                });
+            }, true);
+            if (rc2 != MGN_OK) return rc2;
+        }
+        if (!g->replicas && B > 1) {
+            *loss = mean0;                                               // a partition group of one: the plain call
+        } else {
+            double s = 0.0;
+            for (int32_t b = 0; b < B; ++b) s += (double)L[b];
+            *loss = (float)(s / (double)B);
+        }
+        g->have_grad = true;
+        return MGN_OK;
+    } GROUP_CATCH(g)
+}
+
+int mgn_group_set_params_dev(mgn_group* g, const float* packed, size_t n) {
+    GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_set_params_dev(h, packed, n); }); } GROUP_CATCH(g)
+}
+
+int mgn_group_get_params_dev(mgn_group* g, int32_t rank, float* packed, size_t n) {
+    GROUP_TRY(g) {
+        if (rank < 0 || rank >= g->P) return gfail(g, MGN_E_ARG, "mgn_group_get_params_dev: rank outside [0, P)");
+        g->dispatch([&](int k) { return mgn_get_params_dev(g->h[k], packed, n); }, rank);   // (no collective: this rank alone)
+        return g->verdict();
+    } GROUP_CATCH(g)
+}
+
+int mgn_group_adam_init(mgn_group* g, const mgn_adam_desc* a) {
+    GROUP_TRY(g) { return g->run([&](int, mgn_handle* h) { return mgn_adam_init(h, a); }); } GROUP_CATCH(g)
+}
+
+// grads NULL: every rank's update reads the gradient the last mgn_group_step_datapoints left on its own device
+int mgn_group_adam_update(mgn_group* g, const float* grads, size_t n_grads) {
+    GROUP_TRY(g) {
+        if (!grads && g->host_only) return gfail(g, MGN_E_HIP, "mgn_group_adam_update: host-only group (MGN_DEVICE_NONE): no compute path");
+        if (!grads && !g->have_grad)
+            return gfail(g, MGN_E_STATE, "mgn_group_adam_update: no gradient is resident: mgn_group_step_datapoints has not succeeded yet");
+        return g->run([&](int k, mgn_handle* h) { return mgn_adam_update(h, grads ? grads : g->bufs[k].res.as<float>(), n_grads); });
+    } GROUP_CATCH(g)
+}
+
+// read: rank 0's moments and beta_t (every rank holds the same); write: the same values on every rank
+int mgn_group_adam_state(mgn_group* g, int32_t write, float* mt, float* vt, double beta_t[2]) {
+    GROUP_TRY(g) {
+        const size_t n = mgn_param_count(&g->cfg);
+        std::vector<double> bt((size_t)2 * g->P, 0.0);
+        return g->run([&](int k, mgn_handle* h) {
+            if (write || k == 0 || !mt || !vt || !beta_t) return mgn_adam_state(h, write, mt, vt, beta_t);
+            const mgn_group::Outs o = g->outs_of(k, mt, n, vt, n);
+            return mgn_adam_state(h, 0, o.p[0], o.p[1], &bt[(size_t)2 * k]);
+        });
+    } GROUP_CATCH(g)
 }
 
 }  // extern "C"

@@ -1532,6 +1532,44 @@ int train_run(mgn_handle* h, const TrainJob& J) {
 
 }  // namespace
 
+// The hooks of mgn_group_step_datapoints (engine_internal.h).  The checks are those of mgn_step_datapoint (share == 1) and of
+// mgn_step_datapoints at B > 1 (share > 1) below, in their order and with their statuses, less everything that launches or allocates.
+namespace mgn {
+int step_datapoints_check(mgn_engine* h, const char* who, const int32_t* datapoints, int32_t B, int32_t share, const int32_t* mask, int64_t nmask,
+                          int32_t mask_index_base, size_t n_grads) {
+    if (int rc = datapoint_need(h, who, true, true)) return rc;
+    const mgn_config& c = h->cfg;
+    if (share > 1 && c.nranks != 1) return fail(h, MGN_E_STATE, "%s with B > 1 drives one partition", who);
+    const int32_t T_ = h->train->traj.T;
+    for (int32_t b = 0; b < B; ++b)
+        if (datapoints[b] < 0 || datapoints[b] > T_ - 2)
+            return fail(h, MGN_E_ARG, "%s: datapoint %d (entry %d) outside [0, %d]", who, (int)datapoints[b], (int)b, (int)T_ - 2);
+    if (nmask < 1) return fail(h, MGN_E_ARG, "%s: empty mask", who);
+    if (mask_index_base != 0 && mask_index_base != 1) return fail(h, MGN_E_ARG, "%s: mask_index_base must be 0 or 1", who);
+    const int64_t n_nodes = c.nranks > 1 ? h->g.N : h->g.n_own;          // (a partition takes the mask of the whole mesh)
+    for (int64_t i = 0; i < nmask; ++i) {
+        const int64_t n = (int64_t)mask[i] - mask_index_base;
+        if (n < 0 || n >= n_nodes) return fail(h, MGN_E_ARG, "%s: mask entry %lld out of range", who, (long long)i);
+    }
+    if (share > 1) {
+        const int64_t N = h->g.n_own, E = h->g.set[0].e_local;
+        if ((int64_t)share * N > INT32_MAX || (int64_t)share * E > INT32_MAX)
+            return fail(h, MGN_E_ARG, "%s: %d copies of %lld nodes and %lld edges overflow int32 ids", who, (int)share, (long long)N, (long long)E);
+        if (h->nsets != 1) return fail(h, MGN_E_UNSUPPORTED, "%s with a share of more than one datapoint takes one edge set (the companion replicates one)", who);
+        if (c.ln_dims == MGN_LN_ALL)
+            return fail(h, MGN_E_UNSUPPORTED, "%s with a share of more than one datapoint and ln_dims = MGN_LN_ALL: whole-array statistics would span the batch, a different model", who);
+    }
+    if (int rc = need(h, true, true, false, true)) return rc;
+    if (c.nranks != 1 && h->nsets != 1) return fail(h, MGN_E_UNSUPPORTED, "%s on a partitioned mesh takes one edge set", who);
+    for (int q = 1; q < h->nsets; ++q)
+        if (h->g.set[q].E > 0 && !h->es[q].have_ef)
+            return fail(h, MGN_E_STATE, "edge set %d has edges but no features: call mgn_set_edge_features after mgn_set_edge_set", q);
+    if (n_grads != h->params.size()) return fail(h, MGN_E_ARG, "%s: grads has %zu floats, model has %zu", who, n_grads, h->params.size());
+    return MGN_OK;
+}
+int datapoint_accumulate(mgn_engine* h, int32_t t) { return datapoint_norms(h, t, true, h->stream); }
+}  // namespace mgn
+
 extern "C" int mgn_step(mgn_handle* h, const float* nf, const float* ef, const float* target, const int32_t* mask, int64_t nmask,
                         int32_t mask_index_base, float* grads, size_t n_grads, float* loss) try {
     if (!h) return MGN_E_ARG;

@@ -251,6 +251,16 @@ hipError_t launch_rank_sum(const float* all, int nranks, int64_t n, float* out, 
 #pragma GCC visibility push(hidden)   // (new host functions stay out of the library's dynamic symbols)
 int64_t rank_sum_f64_stride(int64_t nhead, int64_t n);
 hipError_t launch_rank_sum_f64(const double* all, int nranks, int64_t nhead, int64_t n, double* head, float* out, hipStream_t s);
+// The fold of a replica group (mgn_group_step_datapoints): all [P][replica_fold_stride(n)] floats, replica k's gradient of its share of
+// the minibatch (n floats, the row padded to a multiple of four so that every row starts on 16 bytes; the padding is never read).
+//   out[i] = (float) s_P,   s_0 = +0.0,   s_{k+1} = active k ? s_k + w[k] * (double) all[k][i] : s_k      (k ascending)
+// with every product and every sum rounded once in double and none contracted, so a float64 replay of "multiply, then add" gives the
+// same bits.  w (by value, P <= REPLICA_FOLD_MAX) holds B_k / B; bit k of `active` says that replica k had a share: neither the row
+// nor the weight of an idle replica is read.  No atomics; every replica runs it on the same gathered bytes.
+constexpr int REPLICA_FOLD_MAX = 64;
+struct ReplicaFoldW { double w[REPLICA_FOLD_MAX]; };
+int64_t replica_fold_stride(int64_t n);
+hipError_t launch_replica_fold(const float* all, int P, int64_t n, const ReplicaFoldW& w, uint64_t active, float* out, hipStream_t s);
 #pragma GCC visibility pop
 
 // solver-based training (mgn_solver_grad), one step k of the reverse sweep of a fixed-step Euler solve, per element of the [N][O] state:

@@ -2656,6 +2656,37 @@ __global__ __launch_bounds__(256) void k_rank_sum_f64(const double* __restrict__
     }
 }
 
+// The fold of a replica group (train.h: launch_replica_fold).  Memory-bound, 4 (P + 1) n bytes: each thread takes 16 bytes of every
+// active replica's row at a time in a grid-stride loop, the up to three floats behind the last whole quad go one by one (k_adam's
+// shape).  The product and the sum are plain operators under `fp contract(off)`: two roundings per term, as the float64 replay does.
+DEVINL void fold_elem(double& s, double w, float g) {
+#pragma clang fp contract(off)
+    const double t = w * (double)g;
+    s = s + t;
+}
+__global__ void __launch_bounds__(256) k_replica_fold(const float* __restrict__ all, int P, long long stride, long long n, unsigned long long active,
+                                                      ReplicaFoldW w, float* __restrict__ out) {
+    const long long nq = n >> 2, step = (long long)gridDim.x * blockDim.x;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long q = tid; q < nq; q += step) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int k = 0; k < P; ++k) {
+            if (!((active >> k) & 1ull)) continue;
+            const double wk = w.w[k];
+            const f32x4 v = reinterpret_cast<const f32x4*>(all + (long long)k * stride)[q];
+            fold_elem(s0, wk, v[0]); fold_elem(s1, wk, v[1]); fold_elem(s2, wk, v[2]); fold_elem(s3, wk, v[3]);
+        }
+        reinterpret_cast<f32x4*>(out)[q] = f32x4{(float)s0, (float)s1, (float)s2, (float)s3};
+    }
+    const long long i = 4 * nq + tid;                 // the tail: thread tid of block 0 takes element tid of it
+    if (i < n && tid < 4) {
+        double s = 0.0;
+        for (int k = 0; k < P; ++k)
+            if ((active >> k) & 1ull) fold_elem(s, w.w[k], all[(long long)k * stride + i]);
+        out[i] = (float)s;
+    }
+}
+
 hipError_t launch_halo_pack(int L, const float* src, const int32_t* idx, float* dst, int64_t rows, hipStream_t s) {
     const int64_t tot = rows * (L / 4);
     if (tot <= 0) return hipSuccess;
@@ -2694,6 +2725,22 @@ hipError_t launch_rank_sum_f64(const double* all, int nranks, int64_t nhead, int
     if (nranks < 1 || nhead < 0 || n < 0) return hipErrorInvalidValue;
     if (nhead + n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rank_sum_f64, dim3(grad_blocks(nhead + n)), dim3(256), 0, s, all, nranks, rank_sum_f64_stride(nhead, n), nhead, n, head, out);
+    return hipGetLastError();
+}
+
+int64_t replica_fold_stride(int64_t n) { return (n + 3) / 4 * 4; }
+
+hipError_t launch_replica_fold(const float* all, int P, int64_t n, const ReplicaFoldW& w, uint64_t active, float* out, hipStream_t s) {
+    if (P < 1 || P > REPLICA_FOLD_MAX || n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    if ((reinterpret_cast<uintptr_t>(all) | reinterpret_cast<uintptr_t>(out)) & 15) return hipErrorInvalidValue;   // (16-byte accesses)
+    const int64_t nq = n >> 2;
+    int64_t blocks = (nq + 255) / 256;
+    const int64_t cap = (int64_t)8 * device_cus();    // 8 blocks of 256 per CU, grid-stride above
+    if (blocks < 1) blocks = 1;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(k_replica_fold, dim3((unsigned)blocks), dim3(256), 0, s, all, P, (long long)replica_fold_stride(n), (long long)n,
+                       (unsigned long long)active, w, out);
     return hipGetLastError();
 }
 

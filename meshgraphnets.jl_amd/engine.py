@@ -1000,6 +1000,8 @@ class _RankView(Engine):
         self.lib = group.lib
         self.cfg = MgnConfig.from_buffer_copy(group.cfg)
         self.cfg.rank, self.cfg.nranks, self.cfg.device = k, group.nranks, group.devices[k]
+        if getattr(group, "replicas", False):        # (a replica is a whole one-partition handle)
+            self.cfg.rank, self.cfg.nranks = 0, 1
         self.h = C.c_void_p(self.lib.mgn_group_rank_handle(group.g, k))
         if not self.h.value:
             raise MgnError(_capi.MGN_E_ARG, f"no rank {k} in this group")
@@ -1017,15 +1019,19 @@ class GroupEngine:
     in-process "local" communicator.  The mirrored calls have Engine's names and take the GLOBAL arrays; results are the complete ones
     (rank 0's).  `with GroupEngine(...) as g:` or close()."""
 
-    def __init__(self, Fn, Fe, O, L=128, hidden_layers=2, mps=15, devices=(0,), dtype="f32", Fe2=None, ln_mode=0, ln_dims=0):
+    def __init__(self, Fn, Fe, O, L=128, hidden_layers=2, mps=15, devices=(0,), dtype="f32", Fe2=None, ln_mode=0, ln_dims=0, replicas=False):
+        """replicas=True: a replica group (mgn_group_create_replicas) -- every rank holds the WHOLE mesh, step_datapoints splits its
+        minibatch over them, every other call runs on all of them alike."""
         self.lib = _capi.load()
         self.devices = [int(d) for d in devices]
         self.nranks = len(self.devices)
+        self.replicas = bool(replicas)
         self.cfg = MgnConfig(Fn, Fe, O, L, hidden_layers, mps, {"f32": 0, "bf16": 1}[dtype], 0, 1, -1,
                              2 if Fe2 else 1, Fe2 or 0, ln_mode, {0: 0, 1: 1, "rows": 0, "all": 1}[ln_dims])
         self.g = C.c_void_p()
         dev = np.ascontiguousarray(self.devices, np.int32)
-        rc = self.lib.mgn_group_create(C.byref(self.cfg), self.nranks, i32(dev) if dev.size else None, C.byref(self.g))
+        create = self.lib.mgn_group_create_replicas if self.replicas else self.lib.mgn_group_create
+        rc = create(C.byref(self.cfg), self.nranks, i32(dev) if dev.size else None, C.byref(self.g))
         if rc != 0:
             raise MgnError(rc, self.lib.mgn_group_last_error(None).decode())
         self.N = self.E = 0
@@ -1202,8 +1208,10 @@ class GroupEngine:
     def __getattr__(self, name):
         # step_datapoint is looked up on the instance, not on the class: tests/test_step_datapoint_host.py, written when the datapoint
         # family drove one partition only, asserts that the class GroupEngine has no such attribute.  Every group has the method.
-        if name == "step_datapoint":
-            return self._step_datapoint
+        # The same holds for step_datapoints and the Adam / set_params_dev mirrors (tests/test_step_datapoints_host.py,
+        # tests/test_params_dev_host.py): instance attributes, the methods below under a leading underscore.
+        if name in ("step_datapoint", "step_datapoints", "set_params_dev", "adam_init", "adam_update", "adam_state", "set_adam_state"):
+            return object.__getattribute__(self, "_" + name)
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def _step_datapoint(self, t, mask, mask_index_base=0, accumulate=False, out=None):
@@ -1217,6 +1225,68 @@ class GroupEngine:
         self._chk(self.lib.mgn_group_step_datapoint(self.g, int(t), int(bool(accumulate)), i32(mask), mask.size, mask_index_base, p_gs,
                                                     self.param_count, C.byref(loss)))
         return gs, loss.value
+
+    # -- a minibatch over the group and Adam in place (mgn_group_step_datapoints, mgn_group_adam_*, mgn_group_*_params_dev) --
+    def _step_datapoints(self, ts, mask, mask_index_base=0, accumulate=False, out=None, want_grads=True):
+        """Engine.step_datapoints for the group: (gs or None, loss, losses).  A replica group splits ts over its replicas in contiguous
+        chunks (replica k: len(ts) // P + (k < len(ts) % P) entries) and folds their gradients in a fixed order: the same bits on every
+        replica; a partition group takes one datapoint.  want_grads=False leaves the gradient on the devices, where adam_update()
+        finds it: nothing of parameter size crosses PCIe.  `out`: a host array the gradient is written into."""
+        ts = np.ascontiguousarray(ts, dtype=np.int32).ravel()
+        mask = np.ascontiguousarray(mask, dtype=np.int32).ravel()
+        gs = None
+        if want_grads:
+            gs = np.zeros(self.param_count, np.float32) if out is None else out
+            self._host_arrays(out=gs)
+            if gs.dtype != np.float32 or not gs.flags.c_contiguous:
+                raise TypeError("out: a contiguous float32 array")
+        n_grads = self.param_count if gs is None else gs.size
+        loss = C.c_float()
+        losses = np.zeros(max(ts.size, 1), np.float32)
+        self._chk(self.lib.mgn_group_step_datapoints(self.g, i32(ts), ts.size, int(bool(accumulate)), i32(mask), mask.size, mask_index_base,
+                                                     f32(gs), n_grads, C.byref(loss), f32(losses)))
+        return gs, loss.value, losses[:ts.size]
+
+    def _set_params_dev(self, packed):
+        """New parameters into every rank's resident device vector, from a host array."""
+        packed = _c32(packed).ravel()
+        self._chk(self.lib.mgn_group_set_params_dev(self.g, f32(packed), packed.size))
+
+    def get_params_dev(self, rank=0, out=None):
+        """Rank `rank`'s resident parameter vector, on the host: all ranks hold the same bits."""
+        if out is None:
+            out = np.empty(self.param_count, np.float32)
+        self._chk(self.lib.mgn_group_get_params_dev(self.g, int(rank), f32(out), out.size))
+        return out
+
+    def _adam_init(self, eta=1e-3, beta=(0.9, 0.999), epsilon=1e-8):
+        """Engine.adam_init on every rank."""
+        d = _capi.MgnAdamDesc(float(eta), float(beta[0]), float(beta[1]), float(epsilon))
+        self._chk(self.lib.mgn_group_adam_init(self.g, C.byref(d)))
+
+    def _adam_update(self, grads=None):
+        """Optimisers.update on every rank's resident parameters.  grads=None: each rank reads the gradient the last step_datapoints
+        left on its own device (no copy, no host work); a host array: every rank reads it."""
+        if grads is None:
+            self._chk(self.lib.mgn_group_adam_update(self.g, None, self.param_count))
+            return
+        grads = _c32(grads).ravel()
+        self._chk(self.lib.mgn_group_adam_update(self.g, f32(grads), grads.size))
+
+    def _adam_state(self):
+        """Engine.adam_state: rank 0's (all ranks hold the same)."""
+        mt, vt = np.empty(self.param_count, np.float32), np.empty(self.param_count, np.float32)
+        bt = np.zeros(2, np.float64)
+        self._chk(self.lib.mgn_group_adam_state(self.g, 0, f32(mt), f32(vt), bt.ctypes.data_as(C.POINTER(C.c_double))))
+        return {"mt": mt, "vt": vt, "beta_t": bt}
+
+    def _set_adam_state(self, d):
+        """Engine.set_adam_state on every rank."""
+        mt, vt = _c32(d["mt"]).ravel(), _c32(d["vt"]).ravel()
+        bt = np.ascontiguousarray(d["beta_t"], dtype=np.float64).ravel()
+        if mt.shape != (self.param_count,) or vt.shape != (self.param_count,) or bt.shape != (2,):
+            raise ValueError(f"DimensionMismatch: expected mt, vt of ({self.param_count},) and beta_t of (2,)")
+        self._chk(self.lib.mgn_group_adam_state(self.g, 1, f32(mt), f32(vt), bt.ctypes.data_as(C.POINTER(C.c_double))))
 
     # -- solver-based training and the validation rollout on the partitioned mesh (mgn_group_solver_grad*, mgn_group_*_vjp,
     #    mgn_group_rollout_eval): Engine's methods, bodies included, run on the group's handle and the group's symbols --
