@@ -171,7 +171,7 @@ struct mgn_engine {
     DevBuf gwork, gout, gpos, gtype;   // device-side graph prologue (csrc/graph_dev.hip): scratch, outputs, positions, node types
     DevBuf d_stamps;  // diagnostic builds only
     DevBuf ode;       // native rollout: state, stages, frames, saves, Elat0
-    std::vector<std::unique_ptr<DevBuf>> tsit5_store;   // mgn_solver_grad_tsit5: chunks of stored stage inputs, grown as steps are accepted, kept across calls
+    std::vector<std::unique_ptr<DevBuf>> stage_store;   // mgn_solver_grad*: chunks of stored stage inputs, grown as steps are accepted, kept across calls
     const float* srcA_override = nullptr;  // rollout: encoder reads the node state from here instead of d_nfA
     const float* elat_src_override = nullptr;   // right-hand sides on small meshes: step 0's edge kernel reads the trajectory's encoded edge latents from here (EdgeArgs::ElatSrc) instead of a restore copy into Elat
     float* out_override = nullptr;         // rollout: decoder writes dx/dt here instead of d_out
@@ -243,11 +243,19 @@ int lnall_forward(mgn_engine* h, const float* nf, const float* ef, float* out);
 int lnall_processor_steps(mgn_engine* h, float* v, float* e, int32_t nsteps);
 int lnall_rhs_prepare(mgn_engine* h);                                              // binds the arena (may allocate / copy: outside of any capture)
 int lnall_rhs_dev(mgn_engine* h, const float* srcA, float* out, bool reuse_edges);  // the right-hand side on resident inputs; launches only
-// mgn_solver_grad: the training-side checks and arena (train_prepare), and the reverse sweep over the states the forward stored (mgn_train.cpp).
-// Device arrays in the engine's order unless noted; the user's pointers are read with hipMemcpyDefault.
+// Solver-based training (mgn_solver_grad*, mgn_shooting_grad): the training-side checks and arena (train_prepare), and the reverse sweep
+// over the stage inputs the forward loop stored (mgn_train.cpp).  Device arrays in the engine's order unless noted; the user's pointers
+// are read with hipMemcpyDefault.  The method is data: its `stages` active stages s (those whose right-hand side is evaluated on a stage
+// input of the step: all of them, less the FSAL stage; Euler: 1, Tsit5: 6), b[0 .. s) and A[j][i], 0-based
 struct SolverSweep {
-    int64_t K;                           // Euler steps
-    const float* states;                 // [K + 1][N][O]: the array the RHS of step k saw (P_k x_k), then x_K
+    int64_t K;                           // accepted steps
+    const float* const* steps;           // [K] (host): step n's stored stage inputs z_{n,1 .. s}, [s][N][O] each
+    const double* h;                     // [K] (host): the step sizes
+    const float* xend;                   // [N][O]: x_K (continuity term)
+    float* ybar;                         // scratch [s - 1][N][O]: ybar_2 .. ybar_s of the step being swept
+    int32_t stages;                      // s, 1 .. 6
+    const double* b;                     // [s]
+    const double (*A)[7];                // [s][7]
     const float* saves;                  // [n_saves][N][O]: the solution at the save points
     const int64_t* save_step;            // [n_saves] (host): the step whose state each save is, non-decreasing
     int32_t n_saves;
@@ -256,10 +264,15 @@ struct SolverSweep {
     const uint8_t* inflow;               // [N] or null
     const float* cont_target;            // [N][O] or null (continuity term on x_K)
     float cont_weight;
-    float dt;
     const float* onehot; const float* ef_raw; const float* val_mask;   // the caller's, in the caller's order
-    float* a; double* gacc; double* part;   // scratch: [N][O], [n_params], [n_saves + 1][2][solver_adjoint_blocks]
+    float* a; double* gacc; double* part;   // a = dL/dx (lam) [N][O]; scratch [n_params], [n_saves + 1][2][solver_adjoint_blocks]
     float* grads; float* loss;              // results (grads: host or device)
+    // dense saves (MGN_TSIT5_DENSE_SAVES, Tsit5 only; theta null: every save is a state).  Save s with theta[s] >= 0 was interpolated inside
+    // accepted step save_step[s] at that theta (save_step stays non-decreasing); its loss terms reach lam_n, kbar_{n,1 .. 6} and kbar_{n+1,1}
+    // through k_tsit5_dense_adjoint, not through the adjoint launch of a state.
+    const double* theta = nullptr;       // [n_saves] (host); < 0: the save is state save_step[s]
+    const float* zend = nullptr;         // [N][O]: z_{K,1}, the input k_{K-1,7} was evaluated on (the extra VJP of a last step with such saves)
+    float* dense = nullptr;              // scratch [7][N][O]: the step's sum of seeds, then W_1 .. W_6
     // mgn_shooting_grad (unset otherwise): the state holds windows of win_rows rows; the continuity weight per window (cw_win, device) replaces
     // cont_weight, the loss terms are added into lacc ([2][lacc_ld] doubles, launch_shoot_adjoint), every VJP adds to gacc (the caller zeroed
     // it), and nothing is finalised: the caller does that once for all passes
@@ -267,26 +280,7 @@ struct SolverSweep {
     double* lacc = nullptr; int32_t lacc_ld = 0; double lscale = 0.0;
 };
 int solver_prepare(mgn_engine* h, size_t n_grads);
-int solver_sweep(mgn_engine* h, const SolverSweep& S);
-// mgn_solver_grad_tsit5 and mgn_solver_grad_erk: S as for Euler with K = the accepted steps, save_step counting them, states / dt unused,
-// a = dL/dx (lam).  The method is data: its `stages` active stages s (those whose right-hand side is evaluated on a stage input of the
-// step: all of them, less the FSAL stage; Tsit5: 6), b[0 .. s) and A[j][i], 0-based
-struct Tsit5Sweep {
-    const float* const* steps;           // [K] (host): step n's stored stage inputs z_{n,1 .. s}, [s][N][O] each
-    const double* h;                     // [K] (host): the step sizes
-    const float* xend;                   // [N][O]: x_K (continuity term)
-    float* ybar;                         // scratch [5][N][O]: ybar_2 .. ybar_6 of the step being swept
-    // dense saves (MGN_TSIT5_DENSE_SAVES; theta null: every save is a state).  Save s with theta[s] >= 0 was interpolated inside accepted
-    // step S.save_step[s] at that theta (save_step stays non-decreasing); its loss terms reach lam_n, kbar_{n,1 .. 6} and kbar_{n+1,1}
-    // through k_tsit5_dense_adjoint, not through the adjoint launch of a state.
-    const double* theta = nullptr;       // [n_saves] (host); < 0: the save is state save_step[s]
-    const float* zend = nullptr;         // [N][O]: z_{K,1}, the input k_{K-1,7} was evaluated on (the extra VJP of a last step with such saves)
-    float* dense = nullptr;              // scratch [7][N][O]: the step's sum of seeds, then W_1 .. W_6
-    int32_t stages = 0;                  // s, 1 .. 6
-    const double* b = nullptr;           // [s]
-    const double (*A)[7] = nullptr;      // [s][7]
-};
-int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5);
+int erk_sweep(mgn_engine* h, const SolverSweep& S);
 
 // mgn_api.cpp, for the solve drivers of mgn_solve.cpp.  Hidden: they were file-local before the drivers had a file of their own, and
 // with default visibility these mgn:: functions would join the library's dynamic symbols
@@ -328,7 +322,7 @@ int ode_vjp_run(mgn_engine* h, const float* x, const float* node_type_onehot, co
                 float* dxdt, float* xbar, float* grads, size_t n_grads, bool partitions);
 int forward_vjp_run(mgn_engine* h, const float* nf, const float* ef, const float* ybar, float* out, float* nfbar, float* grads, size_t n_grads,
                     bool partitions);
-int solver_grad_run(mgn_engine* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
+int solver_grad_run(mgn_engine* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, int32_t solver, const float* gt, const float* loss_scale,
                     const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions);
 // (tab: mgn_rollout_eval_erk's tableau, checked here before anything else, and its step mode; null: the solver d->solver names)
 int rollout_eval_run(mgn_engine* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, bool partitions, const double* tab = nullptr, int32_t adaptive = 0);

@@ -491,7 +491,7 @@ int group_solver_grad(mgn_group* g, const char* who, mgn_rollout_desc* d, mgn_so
                 if (o->step_t) os[k].step_t = rec[k].data();
                 if (o->step_h) os[k].step_h = rec[k].data() + cap;
             }
-            return mgn::solver_grad_run(h, &ds[k], o ? &os[k] : nullptr, tsit5, gt, loss_scale, cont_target, cont_weight, outs.p[1], n_grads,
+            return mgn::solver_grad_run(h, &ds[k], o ? &os[k] : nullptr, tsit5 ? MGN_SOLVER_TSIT5 : MGN_SOLVER_EULER, gt, loss_scale, cont_target, cont_weight, outs.p[1], n_grads,
                                         k == 0 || !loss ? loss : &losses[k], true);
         });
     });

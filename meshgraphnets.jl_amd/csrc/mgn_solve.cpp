@@ -35,6 +35,8 @@ struct Erk {
     bool fsal = false, embedded = false;
     double beta1 = 0.7, beta2 = 0.4;
     double A[7][7] = {}, b[7] = {}, c[7] = {}, bt[7] = {};
+    // the stages whose right-hand side is evaluated on a stage input of the step, which the training form keeps: all, less the FSAL stage
+    int active() const { return s - (fsal ? 1 : 0); }
 };
 
 enum { ERK_A = 6, ERK_B = 55, ERK_C = 62, ERK_BT = 69 };     // offsets into the flat tableau
@@ -73,16 +75,6 @@ void erk_fill_tsit5(double* tab) {
     for (int i = 0; i < 7; ++i) rows[i] = TS_A[i];
     for (int j = 0; j < 6; ++j) b[j] = TS_A[6][j];
     erk_fill(tab, 7, 5, true, rows, b, TS_C, TS_BT, 0.0, 0.0);
-}
-
-// the tableau MGN_SOLVER_TSIT5 and the Tsit5 training loops drive
-const Erk& erk_tsit5() {
-    static const Erk e = [] {
-        double tab[MGN_ERK_TABLEAU_DOUBLES];
-        erk_fill_tsit5(tab);
-        return erk_unpack(tab);
-    }();
-    return e;
 }
 
 }  // namespace
@@ -186,13 +178,23 @@ extern "C" int mgn_tsit5_interp_weights(double theta, double b[7]) {
 
 namespace {
 
+// a named method (mgn_erk_named), unpacked
+Erk erk_of(int32_t name) {
+    double tab[MGN_ERK_TABLEAU_DOUBLES];
+    (void)mgn_erk_named(name, tab);
+    return erk_unpack(tab);
+}
+// the tableaux the solvers of mgn_rollout_desc.solver drive: MGN_SOLVER_EULER in training, MGN_SOLVER_TSIT5 everywhere
+const Erk& erk_euler() { static const Erk e = erk_of(MGN_ERK_EULER); return e; }
+const Erk& erk_tsit5() { static const Erk e = erk_of(MGN_ERK_TSIT5); return e; }
+
 // mgn_rollout's PI controller (beta1, beta2 the tableau's: 7/50 and 2/25 for Tsit5; gamma = 0.9, qmin = 0.2, qmax = 10): the accept /
 // reject decision for a trial of size hstep with error estimate EEst, and the next dt (a step cut by a stop does not shrink dt)
-struct Tsit5Control {
+struct StepControl {
     static constexpr double gamma = 0.9, qmin = 0.2, qmax = 10.0;
     double beta1, beta2;
     double qold = 1e-4;
-    explicit Tsit5Control(const Erk& e) : beta1(e.beta1), beta2(e.beta2) {}
+    explicit StepControl(const Erk& e) : beta1(e.beta1), beta2(e.beta2) {}
     bool decide(double EEst, double hstep, bool hit_stop, double& dt) {
         const double q11 = std::pow(EEst > 1e-30 ? EEst : 1e-30, beta1);
         if (EEst <= 1.0) {
@@ -230,15 +232,17 @@ struct Arena {
     size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
 };
 
-// the state and stage arrays of a solve, nb bytes each, as offsets into the call's arena.  one_k: fixed-step Euler in the training form, which
-// takes k[0] only and no unew (Rollout::bind points k[1 .. 6] at k[0]); zc: Tsit5's training-form copies za / zs / z7 exist
-struct SolveWs { size_t u, un, ut, k[7], za, zs, z7; bool one_k, zc; };
-SolveWs carve_solve(Arena& a, size_t nb, bool one_k, bool zc) {
+// the state and stage arrays of a solve, nb bytes each, as offsets into the call's arena, sized by the method: s stage arrays k, the stage
+// input utmp (and its copy zs) where there is a stage 2, z7 for an FSAL stage.  fixed: the solve is Rollout::erk_fixed's, which advances a
+// method without FSAL in place and takes no unew; zc: the training-form copies za / zs / z7 exist.  An array the method does not have is
+// null after Rollout::bind
+struct SolveWs { size_t u, un, ut, k[7], za, zs, z7; int s; bool has_un, has_z7, zc; };
+SolveWs carve_solve(Arena& a, size_t nb, int s, bool fsal, bool fixed, bool zc) {
     SolveWs w{};
-    w.one_k = one_k; w.zc = zc;
-    w.u = a.take(nb); w.un = a.take(one_k ? 0 : nb); w.ut = a.take(nb);
-    for (int j = 0; j < 7; ++j) w.k[j] = a.take(one_k && j > 0 ? 0 : nb);
-    w.za = a.take(zc ? nb : 0); w.zs = a.take(zc ? nb : 0); w.z7 = a.take(zc ? nb : 0);
+    w.s = s; w.has_un = fsal || !fixed; w.has_z7 = zc && fsal; w.zc = zc;
+    w.u = a.take(nb); w.un = a.take(w.has_un ? nb : 0); w.ut = a.take(s > 1 ? nb : 0);
+    for (int j = 0; j < 7; ++j) w.k[j] = a.take(j < s ? nb : 0);
+    w.za = a.take(zc ? nb : 0); w.zs = a.take(zc && s > 1 ? nb : 0); w.z7 = a.take(w.has_z7 ? nb : 0);
     return w;
 }
 
@@ -258,9 +262,10 @@ struct Rollout {
         : h(h_), d(d_), tg(g), n((int64_t)rows * h_->cfg.O), n_global((int64_t)rows_global * h_->cfg.O), nrows(rows) { train = train_; }
     // the solve workspace (carve_solve) at base
     void bind(char* base, const SolveWs& w) {
-        u = (float*)(base + w.u); unew = w.one_k ? nullptr : (float*)(base + w.un); utmp = (float*)(base + w.ut);
-        for (int j = 0; j < 7; ++j) k[j] = (float*)(base + w.k[w.one_k ? 0 : j]);
-        if (w.zc) { za = (float*)(base + w.za); zs = (float*)(base + w.zs); z7 = (float*)(base + w.z7); }
+        auto at = [&](size_t off, bool have) { return have ? (float*)(base + off) : nullptr; };
+        u = at(w.u, true); unew = at(w.un, w.has_un); utmp = at(w.ut, w.s > 1);
+        for (int j = 0; j < 7; ++j) k[j] = at(w.k[j], j < w.s);
+        za = at(w.za, w.zc); zs = at(w.zs, w.zc && w.s > 1); z7 = at(w.z7, w.has_z7);
     }
     double tt(double v) const { return tg.tt(v); }
 
@@ -402,7 +407,7 @@ struct Rollout {
     }
     // does pending save time ts sit on a step's end tn?  (at most tn, and within the tolerance the stops are hit with)
     static bool hits(double ts, double tn) { return ts <= tn && std::fabs(ts - tn) <= 1e-9 * std::fabs(tn) + 1e-12; }
-    // dense saves: the pending saves strictly inside the accepted trial of step nstep from t to tn with size hstep, before tsit5_advance
+    // dense saves: the pending saves strictly inside the accepted trial of step nstep from t to tn with size hstep, before erk_advance
     // (u = x_n, k[0 .. 6] = k_{n,1 .. 7}): saves[saved] <- x_n + hstep sum_i b_i(theta) k_{n,i}, theta = (ts - t) / hstep formed in double
     // from the time-type values (at most 1: tn is rounded), the weights rounded to float once.  The interpolant is formed once, in the save's
     // slot or -- mgn_rollout_eval without d->out -- in utmp (the stage-6 input, free once k6 exists), and reduced from there as save()
@@ -439,11 +444,11 @@ struct Rollout {
     }
 
     // Training form (solver-based training, ode_func_train): the right-hand side sees a COPY of its input with the inflow rows written --
-    // utmp for Euler; za for Tsit5 stage 1 (z_{n,1}), zs for stages 2 .. 6, z7 for stage 7 (z_{n+1,1}) -- and the state is never
+    // za for stage 1 (z_{n,1}), zs for stages 2 .. s', z7 for the FSAL stage (Tsit5's stage 7, z_{n+1,1}) -- and the state is never
     // overwritten.  mgn_rollout (train = false), or no inflow mask: the input itself (mgn_rollout overwrites it in place).
     bool train = false;
     float *za = nullptr, *zs = nullptr, *z7 = nullptr;
-    float* kept = nullptr;     // training form: the current Tsit5 trial's six stage inputs [6][n] (z_{n,1}, stages 2 .. 6), or null
+    float* kept = nullptr;     // training form: the current trial's stage inputs [s'][n] (z_{n,1}, stages 2 .. s'), or null
 
     // the array the right-hand side of input y sees (z: its training-form copy)
     float* rhs_input(float* y, float* z) const { return (train && mask) ? z : y; }
@@ -451,24 +456,6 @@ struct Rollout {
         float* x = rhs_input(y, z);
         if (x != y) HIPCHK(h, hipMemcpyAsync(x, y, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         return rhs(x, t, kout);
-    }
-
-    // ---- fixed-step Euler, training form: x_{k+1} = x_k + dt f(P_k x_k), P_k x_k -> store[k] and x_K -> store[K]; saves from the plan ----
-    int euler_train(int64_t K, const std::vector<int64_t>& plan, float* store) {
-        double t = tg.t0;
-        if (int rc = saves_after(plan, 0)) return rc;
-        for (int64_t i = 0; i < K; ++i) {
-            float* xin = rhs_input(u, utmp);
-            if (int rc = eval(u, utmp, t, k[0])) return rc;
-            HIPCHK(h, hipMemcpyAsync(store + (size_t)i * n, xin, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-            LinComb lc{1, {1.f}, {k[0]}};
-            HIPCHK(h, launch_lincomb(u, u, lc, (float)tg.dt, n, h->stream));
-            t = tg.next(i, K, t);
-            ++d->n_accept;
-            if (int rc = saves_after(plan, i + 1)) return rc;
-        }
-        HIPCHK(h, hipMemcpyAsync(store + (size_t)K * n, u, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-        return MGN_OK;
     }
 
     // ---- fixed-step Euler as mgn_rollout runs it: the inflow rows written into the state itself, a save on every save point reached ----
@@ -498,7 +485,7 @@ struct Rollout {
     const Erk* tb = &erk_tsit5();
     bool have_k1 = false;      // k[0] = f(u): kept over the retrials of a step; FSAL keeps it over accepted steps too
     // k1 = f(u) at t (FSAL afterwards)
-    int tsit5_first(double t) {
+    int erk_first(double t) {
         have_k1 = true;
         return eval(u, za, t, k[0]);
     }
@@ -510,7 +497,7 @@ struct Rollout {
         return lc;
     }
     // Hairer-Wanner starting step from (u, k1)
-    int tsit5_h0(double t, double* dt) {
+    int erk_h0(double t, double* dt) {
         double d0, d1, d2;
         LinComb l1{1, {1.f}, {k[0]}};
         // d0 = ||u||, d1 = ||f0|| in the scaled norm: errnorm(dt = 1) of u and k1 themselves
@@ -530,10 +517,12 @@ struct Rollout {
     // one trial step from (u, k1) over hstep: stages 2 .. s at tt(t + tt(c_i hstep)) on utmp; the FSAL stage (stage s of an FSAL tableau:
     // Tsit5's k7) is f(unew), unew = u + hstep sum_j b_j k_j, at t7; without FSAL unew is formed after the last stage and not evaluated.
     // EEst (null: none, the fixed-step mode) the scaled error norm of the embedded pair -- one small D2H.
+    // in_place (erk_fixed, without FSAL): the new state is formed in u itself -- no trial is rejected there, the stage inputs live in utmp,
+    // and the right-hand side keeps one input array from step to step (one captured graph per stage, not two)
     // fused_input (the fixed-step loops of mgn_rollout and mgn_rollout_erk): the stage sum and the in-place inflow rows of its stage time
     // in one launch (launch_tsit5_stage_input: launch_lincomb's bits, then launch_overwrite's rows) where the other loops issue two
-    bool fused_input = false;
-    int tsit5_trial(double t, double hstep, double t7, double* EEst) {
+    bool fused_input = false, in_place = false;
+    int erk_trial(double t, double hstep, double t7, double* EEst) {
         const Erk& e = *tb;
         const int last = e.s - 1, active = e.s - (e.fsal ? 1 : 0);      // active: the stages whose inputs the training form keeps
         for (int sidx = 1; sidx < e.s; ++sidx) {     // stages 2..s
@@ -558,13 +547,14 @@ struct Rollout {
             if (sidx < active && kept)
                 HIPCHK(h, hipMemcpyAsync(kept + (size_t)sidx * n, rhs_input(dst, z), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
         }
-        if (!e.fsal) HIPCHK(h, launch_lincomb(unew, u, stage_sum(e.b, e.s), (float)hstep, n, h->stream));
+        if (!e.fsal) HIPCHK(h, launch_lincomb(in_place ? u : unew, u, stage_sum(e.b, e.s), (float)hstep, n, h->stream));
         if (!EEst) return MGN_OK;
         return norm(u, unew, stage_sum(e.bt, e.s), (float)hstep, EEst);
     }
-    // the accepted trial becomes the state: unew -> u; FSAL: the last stage -> k1 (Tsit5: k7), z_{n+1,1} -> za; otherwise k1 is due again
-    void tsit5_advance() {
-        std::swap(u, unew);
+    // the accepted trial becomes the state: unew -> u (in_place: it is there); FSAL: the last stage -> k1 (Tsit5: k7), z_{n+1,1} -> za;
+    // otherwise k1 is due again
+    void erk_advance() {
+        if (!in_place) std::swap(u, unew);
         if (tb->fsal) {
             std::swap(k[0], k[tb->s - 1]);
             std::swap(za, z7);
@@ -573,7 +563,7 @@ struct Rollout {
         }
     }
 
-    // training form: slot(n, &p) gives accepted step n's storage for its six stage inputs
+    // training form: slot(n, &p) gives accepted step n's storage for its s' stage inputs
     using Slot = std::function<int(int64_t, float**)>;
     std::vector<double> step_t, step_h;    // training form: every accepted step's t and h
     // before a trial of step n: its storage, and z_{n,1} (what k1's right-hand side saw) into it
@@ -586,19 +576,20 @@ struct Rollout {
     // fixed steps of the tableau: K steps of dt on the fixed grid, the FSAL stage at t_{n+1}; saves from the plan.  slot: the training
     // form (mgn_solver_grad_tsit5, mgn_solver_grad_erk, mgn_shooting_grad), every step's stage inputs and record kept; none: the
     // evaluation form of mgn_rollout_erk, nothing stored
-    int tsit5_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot* slot) {
+    int erk_fixed(int64_t K, const std::vector<int64_t>& plan, const Slot* slot) {
         double t = tg.t0;
+        in_place = !tb->fsal;
         if (int rc = saves_after(plan, 0)) return rc;
         if (tb->fsal)
-            if (int rc = tsit5_first(t)) return rc;
+            if (int rc = erk_first(t)) return rc;
         for (int64_t i = 0; i < K; ++i) {
             const double tn = tg.next(i, K, t);
             if (!have_k1)
-                if (int rc = tsit5_first(t)) return rc;
+                if (int rc = erk_first(t)) return rc;
             if (slot)
                 if (int rc = begin_trial(*slot, i)) return rc;
-            if (int rc = tsit5_trial(t, tg.dt, tn, nullptr)) return rc;
-            tsit5_advance();
+            if (int rc = erk_trial(t, tg.dt, tn, nullptr)) return rc;
+            erk_advance();
             if (slot) { step_t.push_back(t); step_h.push_back(tg.dt); }
             t = tn;
             ++d->n_accept;
@@ -616,7 +607,7 @@ struct Rollout {
     int tsit5_fixed_dense(const Slot* slot) {
         double t = tg.t0;
         if (int rc = save(0)) return rc;
-        if (int rc = tsit5_first(t)) return rc;
+        if (int rc = erk_first(t)) return rc;
         int64_t nacc = 0;
         while (t < tg.t1 - 1e-5 * tg.sdt) {
             double hstep = tg.dt, tn = tt(t + tg.dt);
@@ -624,9 +615,9 @@ struct Rollout {
             else if (tn > tg.t1) { hstep = tt(tg.t1 - t); tn = tg.t1; }
             if (slot)
                 if (int rc = begin_trial(*slot, nacc)) return rc;
-            if (int rc = tsit5_trial(t, hstep, tn, nullptr)) return rc;
+            if (int rc = erk_trial(t, hstep, tn, nullptr)) return rc;
             if (int rc = saves_inside(nacc, t, hstep, tn)) return rc;
-            tsit5_advance();
+            erk_advance();
             if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
             t = tn;
             ++nacc;
@@ -639,20 +630,20 @@ struct Rollout {
         return MGN_OK;
     }
 
-    // adaptive Tsit5 from t0 to t1: mgn_rollout's PI controller (Tsit5Control), tstops = saves, a save on every stop it hits, missing saves
+    // adaptive Tsit5 from t0 to t1: mgn_rollout's PI controller (StepControl), tstops = saves, a save on every stop it hits, missing saves
     // (t1 short of the last stop) padded with the final state.  mgn_rollout (no slot): stage 7 at c7 h, and the iteration guard stops
     // silently.  Training form (slot): every trial's stage inputs kept in slot(n), stage 7 is z_{n+1,1} and sees t_{n+1}, the accepted
     // steps recorded, and the guard fails the call.  dense (training form only): no stop but t1, the saves as tsit5_fixed_dense takes them.
-    int tsit5_adaptive(const char* who, const Slot* slot) {
+    int erk_adaptive(const char* who, const Slot* slot) {
         const int ns = d->n_saves;
         double t = tg.t0;
         if (int rc = save(0)) return rc;
         double dt = tg.dt;
         if (tb->fsal || dt <= 0)
-            if (int rc = tsit5_first(t)) return rc;     // k1 (FSAL afterwards; otherwise once per state that starts a step, below)
+            if (int rc = erk_first(t)) return rc;     // k1 (FSAL afterwards; otherwise once per state that starts a step, below)
         if (dt <= 0)   // Hairer-Wanner starting step
-            if (int rc = tsit5_h0(t, &dt)) return rc;
-        Tsit5Control ctl(*tb);
+            if (int rc = erk_h0(t, &dt)) return rc;
+        StepControl ctl(*tb);
         int64_t guard = 0, nacc = 0;
         // float32 descriptors: t1 and n*saves_dt may differ in the last ulp; an interval shorter than 1e-5 save periods is not worth a step
         while (t < tg.t1 - 1e-5 * tg.sdt) {
@@ -669,16 +660,16 @@ struct Rollout {
             // (a stage that lands on the stop itself sees the stop's time: c7 = 1)
             const double t7 = (slot || hit_stop) ? tn : tt(t + tt(tb->c[tb->s - 1] * hstep));
             if (!have_k1)
-                if (int rc = tsit5_first(t)) return rc;
+                if (int rc = erk_first(t)) return rc;
             if (slot)
                 if (int rc = begin_trial(*slot, nacc)) return rc;
             double EEst;
-            if (int rc = tsit5_trial(t, hstep, t7, &EEst)) return rc;
+            if (int rc = erk_trial(t, hstep, t7, &EEst)) return rc;
             if (!(EEst == EEst)) return fail(h, MGN_E_STATE, "%s: NaN in the error estimate at t = %g", who, t);
             if (ctl.decide(EEst, hstep, hit_stop, dt)) {
                 if (dense)
                     if (int rc = saves_inside(nacc, t, hstep, tn)) return rc;
-                tsit5_advance();
+                erk_advance();
                 if (slot) { step_t.push_back(t); step_h.push_back(hstep); }
                 t = tn;
                 ++nacc;
@@ -830,7 +821,7 @@ int to_engine_order(mgn_handle* h, const float* src, int64_t count, float* dst, 
 // folded once in ascending rank order (rank_fold_f64) and divided by the whole mesh's counts; mse_time's rows go through
 // gather_rows_global.  Without d->out no save is kept, gathered or downloaded on any rank.
 // tab (mgn_rollout_erk and its kin; null: the solver d->solver names): the method is this tableau, already checked, d->solver is not read,
-// and adaptive chooses between the fixed grid (Rollout::tsit5_fixed without a slot) and the controller's loop (Rollout::tsit5_adaptive)
+// and adaptive chooses between the fixed grid (Rollout::erk_fixed without a slot) and the controller's loop (Rollout::erk_adaptive)
 int fixed_grid(mgn_handle* h, const char* who, const TimeGrid& T, int n_saves, int64_t* K, std::vector<int64_t>& save_step);
 int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, const char* who, const double* tab = nullptr, int32_t adaptive = 0) {
     const bool lnall = h && h->cfg.ln_dims == MGN_LN_ALL;
@@ -907,7 +898,7 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
         }
     }
     Arena a;
-    const SolveWs ws = carve_solve(a, nb, false, false);      // (Euler too keeps all seven k and unew)
+    const SolveWs ws = carve_solve(a, nb, 7, true, false, false);      // (every solver takes Tsit5's arrays: Euler too keeps all seven k and unew)
     const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)nloc), o_part = a.take(errnorm_partials() * sizeof(double));
     R.elat0_off = a.take(eb);
     const size_t o_eacc = a.take(e ? (size_t)R.n * 8 : 0), o_epart = a.take((size_t)d->n_saves * eblk * c.O * 8),
@@ -941,10 +932,10 @@ int rollout_solve(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_desc* e, 
         erk = erk_unpack(tab);
         R.tb = &erk;
         R.fused_input = !adaptive;
-        if (int rc = adaptive ? R.tsit5_adaptive(who, nullptr) : R.tsit5_fixed(erk_K, erk_plan, nullptr)) return rc;
+        if (int rc = adaptive ? R.erk_adaptive(who, nullptr) : R.erk_fixed(erk_K, erk_plan, nullptr)) return rc;
     } else {
         R.fused_input = d->solver == MGN_SOLVER_TSIT5_FIXED;
-        if (int rc = d->solver == MGN_SOLVER_EULER ? R.euler_rollout() : d->solver == MGN_SOLVER_TSIT5 ? R.tsit5_adaptive(who, nullptr) : R.tsit5_fixed_dense(nullptr))
+        if (int rc = d->solver == MGN_SOLVER_EULER ? R.euler_rollout() : d->solver == MGN_SOLVER_TSIT5 ? R.erk_adaptive(who, nullptr) : R.tsit5_fixed_dense(nullptr))
             return rc;
     }
     if (part) {     // every rank returns the complete solution (mgn_rollout_eval without d->out: none is kept)
@@ -1051,7 +1042,7 @@ extern "C" int mgn_rollout_eval(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_
 // ---- solver-based training (SolverTraining / MultipleShooting): loss and gradient of one solved window ------------------------------
 // Forward: mgn_rollout's time loop on the resident right-hand side (the same launches, the same hipGraph replay), in the training form of
 // the inflow overwrite (ode_func_train writes the inflow rows into a copy, reference src/solve.jl:101-117), storing the arrays the RHS saw.
-// Backward: solver_sweep / tsit5_sweep (mgn_train.cpp).  One edge set, fp32; the state in the engine's order throughout.  One partition
+// Backward: erk_sweep (mgn_train.cpp).  One edge set, fp32; the state in the engine's order throughout.  One partition
 // on a rank handle; through the group (partitions = true) the state is the rows a rank owns, every VJP of the sweep runs the partitioned
 // TrainPass, and the sweep's finish folds the ranks' loss sums and double gradient accumulators once (Sweep::finish, rank_fold_f64).
 namespace {
@@ -1092,48 +1083,37 @@ int solver_targets(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const fl
     return MGN_OK;
 }
 
-// the fields of a reverse sweep that every caller fills from its solve R (Euler: K steps over the stored states; Tsit5: K accepted steps).
+// the reverse sweep of solve R: its accepted steps over their stored stage inputs (steps[n]: step n's s' arrays), its tableau and its saves.
 // R.save_step is the plan the solve was given once all its saves are taken (saves_after pushes the plan's own entries; the shooting pass
-// checks R.saved), and R.tg.dt is the call's dt for every window (a group's grid copies it)
-SolverSweep sweep_setup(const Rollout& R, bool euler, int64_t K, const float* states, const float* gt, const float* loss_scale, const uint8_t* inflow,
-                        const float* cont_target, float* a, double* gacc) {
+// checks R.saved).  ybar: scratch [s' - 1][n]
+SolverSweep sweep_setup(const Rollout& R, const std::vector<float*>& steps, float* ybar, const float* gt, const float* loss_scale,
+                        const uint8_t* inflow, const float* cont_target, float* a, double* gacc) {
     SolverSweep S{};
-    S.K = K; S.states = euler ? states : nullptr; S.saves = R.saves; S.save_step = R.save_step.data(); S.n_saves = R.d->n_saves;
-    S.gt = gt; S.loss_scale = loss_scale; S.inflow = inflow; S.cont_target = cont_target; S.dt = euler ? (float)R.tg.dt : 0.f;
+    S.K = (int64_t)R.step_h.size(); S.steps = steps.data(); S.h = R.step_h.data(); S.xend = R.u; S.ybar = ybar;
+    S.stages = R.tb->active(); S.b = R.tb->b; S.A = R.tb->A;
+    S.saves = R.saves; S.save_step = R.save_step.data(); S.n_saves = R.d->n_saves;
+    S.gt = gt; S.loss_scale = loss_scale; S.inflow = inflow; S.cont_target = cont_target;
     S.a = a; S.gacc = gacc;
     return S;
 }
-// the sweep on engine e: Euler's, or Tsit5's over the stored stage inputs of R's accepted steps (ybar: scratch [5][n])
-// (dense: the scratch of a solve with dense saves, whose plan is R.save_step / R.save_theta; null otherwise)
-int run_sweep(mgn_engine* e, const SolverSweep& S, const Rollout& R, bool euler, const std::vector<float*>& steps, float* ybar, float* dense = nullptr) {
-    if (euler) return solver_sweep(e, S);
-    Tsit5Sweep T5{steps.data(), R.step_h.data(), R.u, ybar};
-    T5.stages = R.tb->s - (R.tb->fsal ? 1 : 0); T5.b = R.tb->b; T5.A = R.tb->A;
-    if (dense) {
-        T5.theta = R.save_theta.data();
-        T5.zend = R.rhs_input(R.u, R.za);      // z_{K,1}: what stage 7 of the last accepted trial was evaluated on
-        T5.dense = dense;
-    }
-    return tsit5_sweep(e, S, T5);
-}
 
-// mgn_solver_grad (o null: fixed-step Euler) and mgn_solver_grad_tsit5 (o: fixed steps, or adaptive), after their own checks: the time grid,
-// the forward loop keeping what the sweep needs (Euler: every step's RHS input; Tsit5: every accepted step's six stage inputs, in chunks on
-// the handle), the targets, solver_sweep / tsit5_sweep, the predicted saves.  tb (mgn_solver_grad_erk; null: Tsit5's): the tableau the
-// forward loop and the sweep drive, its s' = s - fsal active stages' inputs stored per step
-int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const char* who, const float* gt, const float* loss_scale,
-                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions, const Erk* tb = nullptr) {
-    const bool euler = !o, adaptive = o && (o->adaptive & MGN_TSIT5_ADAPTIVE), dense = o && (o->adaptive & MGN_TSIT5_DENSE_SAVES);
+// mgn_solver_grad (o null: it has no options of its caller's), mgn_solver_grad_tsit5 and mgn_solver_grad_erk after their own checks, for
+// tableau tb in the step mode o->adaptive names: the time grid, the forward loop keeping every accepted step's s' = s - fsal stage inputs
+// in chunks on the handle, the targets, erk_sweep, the predicted saves
+int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const Erk& tb, const char* who, const float* gt, const float* loss_scale,
+                const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
+    mgn_solver_grad_opts own{};
+    const bool bounded = o != nullptr;      // the ceiling of 100000 accepted steps (maxiters) is the entry points' that take options
+    if (!o) o = &own;
+    const bool adaptive = o->adaptive & MGN_TSIT5_ADAPTIVE, dense = o->adaptive & MGN_TSIT5_DENSE_SAVES;
     const TimeGrid T(d);
     if (d->n_saves < 1 || !(T.sdt > 0.0) || !(T.t1 >= T.t0)) return fail(h, MGN_E_ARG, "%s: bad time grid", who);
-    if (!adaptive && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, euler ? "%s: Euler needs dt > 0" : "%s: fixed steps need dt > 0", who);
+    if (!adaptive && !(T.dt > 0.0)) return fail(h, MGN_E_ARG, bounded ? "%s: fixed steps need dt > 0" : "%s: Euler needs dt > 0", who);
     if (adaptive && !(T.dt >= 0.0)) return fail(h, MGN_E_ARG, "%s: dt must be >= 0 (0: the Hairer-Wanner start)", who);
     if (adaptive && !(d->abstol > 0.f && d->reltol > 0.f)) return fail(h, MGN_E_ARG, "%s: tolerances must be > 0", who);
     if (int rc = solver_inflow_checks(h, d, who, cont_weight)) return rc;
-    if (o) {
-        o->n_steps = 0;
-        o->stored_bytes = 0;
-    }
+    o->n_steps = 0;
+    o->stored_bytes = 0;
     int64_t K = 0;                       // fixed steps: the step count; adaptive: the accepted steps, after the solve
     std::vector<int64_t> plan;
     if (!adaptive && !dense) {
@@ -1151,53 +1131,49 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     const int O = c.O;
     invalidate_static(h);
     Rollout R(h, d, T, true, N, h->g.N);
-    if (tb) R.tb = tb;
+    R.tb = &tb;
     const size_t nb = (size_t)R.n * 4;
     const size_t P = h->params.size();
     const int ablk = solver_adjoint_blocks(N, O);
-    if (euler && (size_t)(K + 1) > (SIZE_MAX / 2) / (nb > 0 ? nb : 1))
-        return fail(h, MGN_E_OOM, "%s: %lld stored states of %zu bytes overflow the address space", who, (long long)(K + 1), nb);
     const size_t fb = d->inflow_data ? (size_t)d->n_frames * nb : 0, sb = (size_t)d->n_saves * nb;
     const size_t eb = tile_floats(h->es[0].ntiles_e, c.L) * 4;
     Arena a;
-    const SolveWs ws = carve_solve(a, nb, euler, !euler && d->inflow_mask != nullptr);
-    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)N), o_pe = a.take(euler ? 0 : errnorm_partials() * sizeof(double));
+    const SolveWs ws = carve_solve(a, nb, tb.s, tb.fsal, !adaptive && !dense, d->inflow_mask != nullptr);
+    const size_t o_fr = a.take(fb), o_sv = a.take(sb), o_mask = a.take((size_t)N), o_pe = a.take(adaptive ? errnorm_partials() * sizeof(double) : 0);
     R.elat0_off = a.take(eb);
     const size_t o_gt = a.take(sb), o_ct = a.take(cont_target ? nb : 0), o_ls = a.take((size_t)O * 4), o_a = a.take(nb),
-                 o_tmp = a.take(part ? (size_t)h->g.N * O * 4 : nb), o_yb = a.take(euler ? 0 : 5 * nb), o_gacc = a.take(P * sizeof(double)), o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
-    const size_t o_st = a.take(euler ? (size_t)(K + 1) * nb : 0);
-    const size_t o_dn = a.take(dense ? 7 * nb : 0);      // dense saves: the sweep's sums of a step's interpolated saves (Tsit5Sweep::dense)
-    if (int rc = euler ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the %lld stored states of the solve and the call's buffers", who,
-                                        (double)a.off * 1e-9, (long long)(K + 1))
-                 : dense ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers (%.3f GB of them the sums of the interpolated saves)", who,
-                                          (double)a.off * 1e-9, (double)(7 * nb) * 1e-9)
-                         : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
+                 o_tmp = a.take(part ? (size_t)h->g.N * O * 4 : nb), o_yb = a.take((size_t)(tb.active() - 1) * nb), o_gacc = a.take(P * sizeof(double)),
+                 o_part = a.take((size_t)(d->n_saves + 1) * 2 * ablk * sizeof(double));
+    const size_t o_dn = a.take(dense ? 7 * nb : 0);      // dense saves: the sweep's sums of a step's interpolated saves (SolverSweep::dense)
+    if (int rc = dense ? ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers (%.3f GB of them the sums of the interpolated saves)", who,
+                                        (double)a.off * 1e-9, (double)(7 * nb) * 1e-9)
+                       : ensure_or_fail(h, h->ode, a.off, "%s: %.3f GB for the call's buffers", who, (double)a.off * 1e-9))
         return rc;
     char* base = h->ode.as<char>();
     R.bind(base, ws);
     R.frames = d->inflow_data ? (float*)(base + o_fr) : nullptr;
     R.saves = (float*)(base + o_sv);
     R.mask = d->inflow_mask ? (uint8_t*)(base + o_mask) : nullptr;
-    R.partial = euler ? nullptr : (double*)(base + o_pe);
+    R.partial = adaptive ? (double*)(base + o_pe) : nullptr;
     if (int rc = upload_engine_order(h, d, R.u, R.frames, R.mask)) return rc;
     if (int rc = upload_statics(h, d, d->x0, base + R.elat0_off, eb)) return rc;
 
-    // Tsit5 or a tableau: the stored stage inputs, step n's s' [N][O] arrays (Tsit5: six) at steps[n], carved out of chunks kept on the
-    // handle and grown geometrically (never reallocated: a stored step does not move)
-    const size_t stepb = (size_t)(R.tb->s - (R.tb->fsal ? 1 : 0)) * nb;
+    // the stored stage inputs, step n's s' [N][O] arrays (Euler: one, Tsit5: six) at steps[n], carved out of chunks kept on the handle and
+    // grown geometrically (never reallocated: a stored step does not move)
+    const size_t stepb = (size_t)tb.active() * nb;
     const size_t denseb = dense ? 7 * nb : 0;      // counted with the stored stage inputs (max_store_bytes, stored_bytes)
     const int64_t max_steps = 100000;
     std::vector<float*> steps;
     size_t chunk = 0, used_in_chunk = 0;
     const Rollout::Slot slot = [&](int64_t n, float** out) -> int {
         while ((int64_t)steps.size() <= n) {
-            if ((int64_t)steps.size() >= max_steps)
+            if (bounded && (int64_t)steps.size() >= max_steps)
                 return fail(h, MGN_E_STATE, "%s: more than %lld accepted steps (maxiters)", who, (long long)max_steps);
             if (o->max_store_bytes && (size_t)(steps.size() + 1) * stepb + denseb > o->max_store_bytes)
                 return fail(h, MGN_E_OOM, "%s: step %lld needs %zu bytes of stored stage inputs%s, beyond max_store_bytes = %zu", who,
                             (long long)steps.size(), (size_t)(steps.size() + 1) * stepb + denseb, dense ? " and sums of the interpolated saves" : "",
                             o->max_store_bytes);
-            DevBuf* cb = chunk < h->tsit5_store.size() ? h->tsit5_store[chunk].get() : nullptr;
+            DevBuf* cb = chunk < h->stage_store.size() ? h->stage_store[chunk].get() : nullptr;
             if (cb && used_in_chunk + stepb <= cb->bytes) {
                 steps.push_back(reinterpret_cast<float*>(cb->as<char>() + used_in_chunk));
                 used_in_chunk += stepb;
@@ -1210,8 +1186,8 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
             if (o->max_store_bytes) want = std::min(want, (o->max_store_bytes - denseb) / stepb - steps.size());
             if (want > (SIZE_MAX / 2) / stepb) return fail(h, MGN_E_OOM, "%s: %zu stored steps overflow the address space", who, want);
             if (!cb) {
-                h->tsit5_store.push_back(std::make_unique<DevBuf>());
-                cb = h->tsit5_store.back().get();
+                h->stage_store.push_back(std::make_unique<DevBuf>());
+                cb = h->stage_store.back().get();
             }
             if (int rc = ensure_or_fail(h, *cb, want * stepb, "%s: step %lld: %.3f GB more for the stored stage inputs (%.3f GB stored)", who,
                                         (long long)steps.size(), (double)(want * stepb) * 1e-9, (double)(steps.size() * stepb) * 1e-9))
@@ -1223,19 +1199,15 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     };
 
     d->n_accept = d->n_reject = 0;
-    float* states = (float*)(base + o_st);
     R.dense = dense;
-    if (int rc = euler ? R.euler_train(K, plan, states) : adaptive ? R.tsit5_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(&slot) : R.tsit5_fixed(K, plan, &slot))
-        return rc;
+    if (int rc = adaptive ? R.erk_adaptive(who, &slot) : dense ? R.tsit5_fixed_dense(&slot) : R.erk_fixed(K, plan, &slot)) return rc;
     d->n_rhs = R.n_rhs;
-    if (!euler) {
-        K = (int64_t)R.step_h.size();
-        o->n_steps = (int32_t)K;
-        o->stored_bytes = (size_t)K * stepb + denseb;
-        for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
-            if (o->step_t) o->step_t[i] = R.step_t[i];
-            if (o->step_h) o->step_h[i] = R.step_h[i];
-        }
+    K = (int64_t)R.step_h.size();
+    o->n_steps = (int32_t)K;
+    o->stored_bytes = (size_t)K * stepb + denseb;
+    for (int64_t i = 0; i < K && i < o->step_cap; ++i) {
+        if (o->step_t) o->step_t[i] = R.step_t[i];
+        if (o->step_h) o->step_h[i] = R.step_h[i];
     }
 
     float* gtl = (float*)(base + o_gt);
@@ -1243,11 +1215,16 @@ int solver_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, con
     float* lsd = loss_scale ? (float*)(base + o_ls) : nullptr;
     if (int rc = solver_targets(h, d, gt, cont_target, loss_scale, gtl, ctl, lsd, (float*)(base + o_tmp))) return rc;
 
-    SolverSweep S = sweep_setup(R, euler, K, states, gtl, lsd, R.mask, ctl, (float*)(base + o_a), (double*)(base + o_gacc));
+    SolverSweep S = sweep_setup(R, steps, (float*)(base + o_yb), gtl, lsd, R.mask, ctl, (float*)(base + o_a), (double*)(base + o_gacc));
     S.cont_weight = ctl ? cont_weight : 0.f;
     S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
     S.part = (double*)(base + o_part); S.grads = grads; S.loss = loss;
-    if (int rc = run_sweep(h, S, R, euler, steps, (float*)(base + o_yb), dense ? (float*)(base + o_dn) : nullptr)) return rc;
+    if (dense) {      // the plan of the interpolated saves is R.save_step / R.save_theta
+        S.theta = R.save_theta.data();
+        S.zend = R.rhs_input(R.u, R.za);      // z_{K,1}: what stage 7 of the last accepted trial was evaluated on
+        S.dense = (float*)(base + o_dn);
+    }
+    if (int rc = erk_sweep(h, S)) return rc;
     if (d->out && part) {      // the predicted saves, complete on every rank (every rank was given d->out, or none)
         for (int i = 0; i < d->n_saves; ++i)
             if (int rc = gather_rows_global(h, R.saves + (size_t)i * R.n, O, d->out + (size_t)i * h->g.N * O)) return rc;
@@ -1267,9 +1244,11 @@ int solver_checks(mgn_handle* h, mgn_rollout_desc* d, const char* who, const flo
 
 }  // namespace
 
-// mgn_solver_grad (tsit5 false; o unused) and mgn_solver_grad_tsit5 behind their symbols, and behind mgn_group_solver_grad* (partitions)
-int mgn::solver_grad_run(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, bool tsit5, const float* gt, const float* loss_scale,
+// mgn_solver_grad (solver MGN_SOLVER_EULER; o unused) and mgn_solver_grad_tsit5 (MGN_SOLVER_TSIT5) behind their symbols, and behind
+// mgn_group_solver_grad* (partitions)
+int mgn::solver_grad_run(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, int32_t solver, const float* gt, const float* loss_scale,
                          const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss, bool partitions) {
+    const bool tsit5 = solver == MGN_SOLVER_TSIT5;
     const char* who = tsit5 ? "mgn_solver_grad_tsit5" : "mgn_solver_grad";
     // the step mode first: a host-only handle answers it too
     if (tsit5 && o && (o->adaptive & ~(MGN_TSIT5_ADAPTIVE | MGN_TSIT5_DENSE_SAVES)))
@@ -1278,22 +1257,22 @@ int mgn::solver_grad_run(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opt
     if (!tsit5) {
         if (d->solver == 1) return fail(h, MGN_E_UNSUPPORTED, "mgn_solver_grad: the discrete adjoint is built for fixed-step Euler (solver 0); Tsit5 is mgn_solver_grad_tsit5");
         if (d->solver != 0) return fail(h, MGN_E_ARG, "mgn_solver_grad: solver must be 0 (Euler)");
-        return solver_grad(h, d, nullptr, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, partitions);
+        return solver_grad(h, d, nullptr, erk_euler(), who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, partitions);
     }
     if (!o) return fail(h, MGN_E_ARG, "%s: null argument", who);
     if (d->solver != 1) return fail(h, MGN_E_ARG, "%s: solver must be 1 (Tsit5)", who);
     if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
-    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, partitions);
+    return solver_grad(h, d, o, erk_tsit5(), who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, partitions);
 }
 
 extern "C" int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt, const float* loss_scale, const float* cont_target, float cont_weight,
                     float* grads, size_t n_grads, float* loss) try {
     if (!h) return MGN_E_ARG;
-    return solver_grad_run(h, d, nullptr, false, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
+    return solver_grad_run(h, d, nullptr, MGN_SOLVER_EULER, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
 } MGN_CATCH(h)
 
 // mgn_solver_grad_tsit5's loss and gradient for any explicit Runge-Kutta tableau with at most six active stages, fixed steps only: the
-// grid and saves of mgn_rollout_erk(adaptive = 0) in the training form, the s' stage inputs of every step kept in h->tsit5_store, then
+// grid and saves of mgn_rollout_erk(adaptive = 0) in the training form, the s' stage inputs of every step kept in h->stage_store, then
 // the same table-driven sweep.  d->solver is not read.
 extern "C" int mgn_solver_grad_erk(mgn_handle* h, mgn_rollout_desc* d, const double* tab, mgn_solver_grad_opts* o, const float* gt,
                                    const float* loss_scale, const float* cont_target, float cont_weight, float* grads, size_t n_grads,
@@ -1306,8 +1285,7 @@ extern "C" int mgn_solver_grad_erk(mgn_handle* h, mgn_rollout_desc* d, const dou
     if (o->adaptive != 0)
         return fail(h, MGN_E_UNSUPPORTED, "%s: adaptive = %d: fixed steps only (adaptive training is mgn_solver_grad_tsit5's, with Tsit5)", who, o->adaptive);
     const Erk erk = erk_unpack(tab);
-    if (erk.s - (erk.fsal ? 1 : 0) > 6)
-        return fail(h, MGN_E_UNSUPPORTED, "%s: %d active stages; the sweep holds six", who, erk.s - (erk.fsal ? 1 : 0));
+    if (erk.active() > 6) return fail(h, MGN_E_UNSUPPORTED, "%s: %d active stages; the sweep holds six", who, erk.active());
     if (int rc = solver_checks(h, d, who, gt, grads, loss, false)) return rc;
     if (o->step_cap < 0 || (o->step_cap > 0 && !o->step_t && !o->step_h)) return fail(h, MGN_E_ARG, "%s: step_cap needs step_t or step_h", who);
     const TimeGrid T(d);
@@ -1316,15 +1294,15 @@ extern "C" int mgn_solver_grad_erk(mgn_handle* h, mgn_rollout_desc* d, const dou
         if (!(m >= 1.0) || std::fabs(per - m) > 1e-6 * m)
             return fail(h, MGN_E_ARG, "%s: saves_dt / dt = %.9g is not an integer >= 1: a general tableau has no dense output", who, per);
     }
-    return solver_grad(h, d, o, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false, &erk);
+    return solver_grad(h, d, o, erk, who, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
 } MGN_CATCH(h)
 
-// Tsit5: mgn_rollout's adaptive loop (Rollout::tsit5_adaptive, Tsit5Control) or fixed steps on the Euler grid (Rollout::tsit5_fixed), in
-// the training form (za / zs / z7), keeping the six stage inputs of every accepted step in h->tsit5_store; then tsit5_sweep.
+// Tsit5: mgn_rollout's adaptive loop (Rollout::erk_adaptive, StepControl) or fixed steps on the fixed grid (Rollout::erk_fixed), in
+// the training form (za / zs / z7), keeping the six stage inputs of every accepted step in h->stage_store; then erk_sweep.
 extern "C" int mgn_solver_grad_tsit5(mgn_handle* h, mgn_rollout_desc* d, mgn_solver_grad_opts* o, const float* gt, const float* loss_scale,
                           const float* cont_target, float cont_weight, float* grads, size_t n_grads, float* loss) try {
     if (!h) return MGN_E_ARG;
-    return solver_grad_run(h, d, o, true, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
+    return solver_grad_run(h, d, o, MGN_SOLVER_TSIT5, gt, loss_scale, cont_target, cont_weight, grads, n_grads, loss, false);
 } MGN_CATCH(h)
 
 // ---- MultipleShooting as one batch (mgn_shooting_grad) ----------------------------------------------------------------------------------
@@ -1467,7 +1445,8 @@ struct ShootCtx {
     mgn_handle* h; mgn_rollout_desc* d; mgn_shooting_desc* s;
     float cont_weight; size_t n_grads;
     TimeGrid DG;                             // (its time type, dt and saves_dt; every window has its own t0 and t1)
-    bool euler, inflow;
+    const Erk& tb;                           // d->solver's tableau (the windows take fixed steps)
+    bool inflow;
     int32_t N; int O, W1, Fe; int64_t E, nN;
     mgn_rollout_desc dw;                     // a pass's descriptor: d with its group's n_saves
     std::vector<ShootGroup> groups;
@@ -1485,9 +1464,27 @@ struct ShootCtx {
     std::vector<float> hs, zero_x0;          // the statics of companion passes in the engine's order; the encoder's unused state slot of a one-window pass
     std::vector<std::unique_ptr<Rollout>> keep_alive;
     ShootCtx(mgn_handle* h_, mgn_rollout_desc* d_, mgn_shooting_desc* s_, float cw, size_t ng)
-        : h(h_), d(d_), s(s_), cont_weight(cw), n_grads(ng), DG(d_), euler(d_->solver == 0), inflow(d_->inflow_mask != nullptr), N(h_->g.N), O(h_->cfg.O),
+        : h(h_), d(d_), s(s_), cont_weight(cw), n_grads(ng), DG(d_), tb(d_->solver == MGN_SOLVER_EULER ? erk_euler() : erk_tsit5()), inflow(d_->inflow_mask != nullptr), N(h_->g.N), O(h_->cfg.O),
           W1(h_->cfg.Fn - O), Fe(h_->cfg.Fe), E(h_->g.set[0].e_local), nN((int64_t)N * O), dw(*d_) {}
 };
+
+// The times of the right-hand side evaluations of K fixed steps, in the order Rollout::erk_first / erk_trial make them.  FSAL: k1 once up
+// front, and the last stage (z_{n+1,1}) sees t_{n+1}; otherwise stage 1 at t every step.  Stages 2 .. s at tt(t + tt(c_i dt))
+template <typename F>
+int erk_eval_times(const Erk& e, const TimeGrid& T, int64_t K, F&& push) {
+    double t = T.t0;
+    if (e.fsal)
+        if (int rc = push(t)) return rc;
+    for (int64_t i = 0; i < K; ++i) {
+        const double tn = T.next(i, K, t);
+        if (!e.fsal)
+            if (int rc = push(t)) return rc;
+        for (int sidx = 1; sidx < e.s; ++sidx)
+            if (int rc = push(e.fsal && sidx == e.s - 1 ? tn : T.tt(t + T.tt(e.c[sidx] * T.dt)))) return rc;
+        t = tn;
+    }
+    return MGN_OK;
+}
 
 // ---- plans on the host: every window walks the single-window grid; identical plans form a group; then the passes and their tables
 int shoot_plans(ShootCtx& X) {
@@ -1511,20 +1508,7 @@ int shoot_plans(ShootCtx& X) {
                 fr.push_back((int32_t)f);
                 return MGN_OK;
             };
-            double t = T.t0;
-            if (!X.euler)
-                if (int rc = push(t)) return rc;                 // k1
-            for (int64_t i = 0; i < K; ++i) {
-                const double tn = T.next(i, K, t);
-                if (X.euler) {
-                    if (int rc = push(t)) return rc;
-                } else {
-                    for (int sidx = 1; sidx < 6; ++sidx)
-                        if (int rc = push(T.tt(t + T.tt(TS_C[sidx] * T.dt)))) return rc;
-                    if (int rc = push(tn)) return rc;            // stage 7 = z_{n+1,1} sees t_{n+1}
-                }
-                t = tn;
-            }
+            if (int rc = erk_eval_times(X.tb, T, K, push)) return rc;
         }
         int32_t gi = -1;
         for (size_t q = 0; q < X.groups.size() && gi < 0; ++q)
@@ -1652,11 +1636,13 @@ int shoot_pass(ShootCtx& X, const ShootPass& ps) {
     const size_t nb = (size_t)R.n * 4;
     const size_t eb = tile_floats(e->es[0].ntiles_e, h->cfg.L) * 4;
     Arena ea;
-    const SolveWs ws = carve_solve(ea, nb, X.euler, !X.euler && X.inflow);
+    const int sp = X.tb.active();
+    R.tb = &X.tb;
+    const SolveWs ws = carve_solve(ea, nb, X.tb.s, X.tb.fsal, true, X.inflow);
     const size_t o_sv = ea.take((size_t)ns * nb), o_el = ea.take(eb), o_tg = ea.take((size_t)ns * nb), o_ct = ea.take(nb), o_a = ea.take(nb),
-                 o_yb = ea.take(X.euler ? 0 : 5 * nb), o_mr = ea.take(X.inflow && B > 1 ? (size_t)B * X.N : 0);
+                 o_yb = ea.take((size_t)(sp - 1) * nb), o_mr = ea.take(X.inflow && B > 1 ? (size_t)B * X.N : 0);
     if ((size_t)(K + 1) > (SIZE_MAX / 8) / (nb > 0 ? nb : 1)) return fail(h, MGN_E_OOM, "%s: %lld stored steps overflow the address space", shoot_who, (long long)K);
-    const size_t o_st = ea.take((size_t)(X.euler ? K + 1 : 6 * K) * nb);
+    const size_t o_st = ea.take((size_t)sp * K * nb);
     if (int rc = ensure_or_fail(h, e->ode, ea.off, "%s: %.3f GB for a pass of %d windows (stored states and buffers)", shoot_who, (double)ea.off * 1e-9, B))
         return rc;
     char* base = e->ode.as<char>();
@@ -1681,11 +1667,11 @@ int shoot_pass(ShootCtx& X, const ShootPass& ps) {
     const int32_t* ix = X.itd + ps.idx_off;
     HIPCHK(h, launch_shoot_gather(R.u, X.gtl, R.n, X.nN, 0, ix, nullptr, 0, h->stream));     // x0 = gt[first[w]]
 
-    // forward: the single-window loops, save points from the group's plan; Tsit5 keeps step i's stage inputs contiguously at steps[i]
+    // forward: the single-window loop, save points from the group's plan; step i's stage inputs contiguously at steps[i]
     std::vector<float*> steps;
-    for (int64_t i = 0; !X.euler && i < K; ++i) steps.push_back(store + (size_t)i * 6 * R.n);
+    for (int64_t i = 0; i < K; ++i) steps.push_back(store + (size_t)i * sp * R.n);
     const Rollout::Slot slot = [&](int64_t i, float** out) { *out = steps[i]; return MGN_OK; };
-    if (int rc = X.euler ? R.euler_train(K, G.save_step, store) : R.tsit5_fixed(K, G.save_step, &slot)) return efail(rc);
+    if (int rc = R.erk_fixed(K, G.save_step, &slot)) return efail(rc);
     if (R.saved != ns) return fail(h, MGN_E_STATE, "%s: %d of %d saves taken", shoot_who, R.saved, ns);
     d->n_accept += (int32_t)(K * B);
     d->n_rhs += R.n_rhs * B;
@@ -1698,14 +1684,14 @@ int shoot_pass(ShootCtx& X, const ShootPass& ps) {
     HIPCHK(h, launch_shoot_gather(tg, X.gtl, (int64_t)ns * R.n, X.nN, 0, ix + B, nullptr, 0, h->stream));
     if (has_ct) HIPCHK(h, launch_shoot_gather(ctt, X.gtl, R.n, X.nN, 0, ix + B + (size_t)ns * B, nullptr, 0, h->stream));
 
-    SolverSweep S = sweep_setup(R, X.euler, K, store, tg, X.lsd, mrep, has_ct ? ctt : nullptr, (float*)(base + o_a), X.gacc);
+    SolverSweep S = sweep_setup(R, steps, (float*)(base + o_yb), tg, X.lsd, mrep, has_ct ? ctt : nullptr, (float*)(base + o_a), X.gacc);
     if (e == h) {
         S.onehot = d->node_type_onehot; S.ef_raw = d->ef_raw; S.val_mask = d->val_mask;
     } else {
         S.onehot = X.W1 > 0 ? e->d_nfB.as<float>() : nullptr; S.ef_raw = e->es[0].d_ef.as<float>(); S.val_mask = d->val_mask ? e->d_mask.as<float>() : nullptr;
     }
     S.cw_win = X.cwd + ps.cw_off; S.win_rows = X.N; S.lacc = X.lacc; S.lacc_ld = X.ld; S.lscale = 1.0 / ((double)ns * (double)X.nN);
-    if (int rc = run_sweep(e, S, R, X.euler, steps, (float*)(base + o_yb))) return efail(rc);
+    if (int rc = erk_sweep(e, S)) return efail(rc);
     if (d->out) {       // the predicted saves in window order
         float* oall = (float*)(X.sbase + X.o_out);
         for (int sv = 0; sv < ns; ++sv)

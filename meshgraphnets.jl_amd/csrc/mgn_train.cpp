@@ -1896,13 +1896,12 @@ int solver_prepare_partitions(mgn_engine* h, const char* who, size_t n_grads) { 
 
 namespace {
 
-// What the Euler and the Tsit5 sweeps share: the statics staged once per call, the adjoint launches of a state (k_solver_adjoint: every
-// loss term of state k, xbar folded in, the seed of the step before written), one VJP of the right-hand side through train_run, and the
-// results at the end.
+// The pieces of the reverse sweep: the statics staged once per call, the adjoint launches of a state (k_solver_adjoint: every loss term of
+// state k, xbar folded in, the seed of the step before written), one VJP of the right-hand side through train_run, and the results at the
+// end.
 struct Sweep {
     mgn_engine* h;
     const SolverSweep& S;
-    const float* xend;                         // x_K (continuity term)
     int64_t N = 0, n = 0, n_loss = 0;
     bool part = false;                         // a partition: N owned rows; the loss and the gradient fold over the ranks in finish()
     int O = 0, nb = 0;
@@ -1911,15 +1910,14 @@ struct Sweep {
     float gscale = 0.f;
     int64_t sidx = 0;                          // saves are visited last to first; save_step is non-decreasing
     int slot = 0;
-    const double* theta = nullptr;             // Tsit5 with dense saves: theta[s] >= 0 marks a save interpolated inside a step (skipped here)
 
     // is the last save not yet visited state k's?
     bool save_at(int64_t k) {
-        while (theta && sidx >= 0 && theta[sidx] >= 0.0) --sidx;
+        while (S.theta && sidx >= 0 && S.theta[sidx] >= 0.0) --sidx;      // (a save interpolated inside a step: not a state's)
         return sidx >= 0 && S.save_step[sidx] == k;
     }
 
-    Sweep(mgn_engine* h_, const SolverSweep& S_, const float* xend_) : h(h_), S(S_), xend(xend_) {}
+    Sweep(mgn_engine* h_, const SolverSweep& S_) : h(h_), S(S_) {}
 
     int begin() {
         const mgn_config& c = h->cfg;
@@ -1953,7 +1951,7 @@ struct Sweep {
                 p.xs = S.saves + (size_t)sidx * n; p.gt = S.gt + (size_t)sidx * n; p.ls = S.loss_scale; p.vm = vm; p.gscale = gscale;
                 --sidx;
             }
-            if (first && k == S.K && S.cont_target) { p.xend = xend; p.ct = S.cont_target; p.cw = S.cont_weight; }
+            if (first && k == S.K && S.cont_target) { p.xend = S.xend; p.ct = S.cont_target; p.cw = S.cont_weight; }
             const bool more = save_at(k);
             p.lam = (!more && k > 0) ? io + n : nullptr;
             p.dt = seed; p.N = N; p.O = O;
@@ -2018,46 +2016,33 @@ struct Sweep {
 
 }  // namespace
 
-// Reverse sweep of mgn_solver_grad: k = K-1 .. 0 through train_run's VJP path, seeded and chained by k_solver_adjoint (train.hip).
-int solver_sweep(mgn_engine* h, const SolverSweep& S) {
-    Sweep W(h, S, S.states + (size_t)S.K * h->g.n_own * h->cfg.O);
-    if (int rc = W.begin()) return rc;
-    if (int rc = W.adjoint(S.K, false, S.dt)) return rc;
-    for (int64_t k = S.K - 1; k >= 0; --k) {
-        if (int rc = W.vjp(S.states + (size_t)k * W.n, k == S.K - 1)) return rc;
-        if (int rc = W.adjoint(k, true, S.dt)) return rc;
-    }
-    return W.finish();
-}
-
-// Reverse sweep of mgn_solver_grad_tsit5 and mgn_solver_grad_erk, driven by the tableau (T5.stages active stages s, T5.b, T5.A; Tsit5:
-// s = 6, b = A[7]): steps n = K-1 .. 0, stages i = s .. 1, one VJP per stage on its stored input z_{n,i}.  The seed of stage s is written
+// The reverse sweep of solver-based training (mgn_solver_grad*, mgn_shooting_grad), driven by the tableau (S.stages active stages s, S.b,
+// S.A; Euler: s = 1; Tsit5: s = 6, b = A[7]): steps n = K-1 .. 0, stages i = s .. 1, one VJP per stage on its stored input z_{n,i}.  The seed of stage s is written
 // by the adjoint launch of state n + 1 (h_n b_s lam); k_erk_stage_seed masks zbar_{i+1} into ybar_{i+1} and writes
 // kbar_i = h_n (b_i lam + sum_{j>i} A[j][i] ybar_j) for i = s-1 .. 1, and before stage 1's VJP adds sum_{j>=2} ybar_j to lam; the adjoint
-// launch of state n folds in ybar_1 and the loss terms of x_n.  One stage: no seed launch at all (Euler's sweep).  No host
+// launch of state n folds in ybar_1 and the loss terms of x_n.  One stage (Euler): no seed launch at all.  No host
 // synchronisation until the end.
 //
-// Dense saves (T5.theta): the saves interpolated inside step n, xhat_s = x_n + h_n sum_i b_i(theta_s) k_{n,i}, seed lam_n with sum ghat_s,
+// Dense saves (S.theta): the saves interpolated inside step n, xhat_s = x_n + h_n sum_i b_i(theta_s) k_{n,i}, seed lam_n with sum ghat_s,
 // kbar_{n,i} with h_n W_i (W_i = sum_s b_i(theta_s) ghat_s, i = 1 .. 6) and, k_{n,7} being the evaluation at z_{n+1,1} (FSAL),
 // kbar_{n+1,1} with h_n W_7.  ghat_s needs forward values only, so one k_tsit5_dense_adjoint launch per TSIT5_DENSE_MAX saves of step n
 // runs right before the VJP at z_{n+1,1} -- stage 1 of step n + 1, whose seed launch has just consumed that step's own sums, or for the
 // last step one extra VJP at z_{K,1} before the sweep starts, its masked output folded into lam_K by the adjoint launch of state K.
-int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
-    const int sp = T5.stages;
-    if (sp < 1 || sp > 6 || !T5.b || !T5.A) return fail(h, MGN_E_STATE, "tsit5_sweep: %d stages", sp);
-    if (T5.theta && sp != 6) return fail(h, MGN_E_STATE, "tsit5_sweep: interpolated saves are Tsit5's dense output");
-    Sweep W(h, S, T5.xend);
+int erk_sweep(mgn_engine* h, const SolverSweep& S) {
+    const int sp = S.stages;
+    if (sp < 1 || sp > 6 || !S.b || !S.A) return fail(h, MGN_E_STATE, "erk_sweep: %d stages", sp);
+    if (S.theta && sp != 6) return fail(h, MGN_E_STATE, "erk_sweep: interpolated saves are Tsit5's dense output");
+    Sweep W(h, S);
     if (int rc = W.begin()) return rc;
-    W.theta = T5.theta;
     // the interpolated saves of every step, ascending
-    std::vector<std::vector<int32_t>> inner(T5.theta ? (size_t)S.K : 0);
-    for (int32_t s = 0; T5.theta && s < S.n_saves; ++s)
-        if (T5.theta[s] >= 0.0) {
-            if (S.save_step[s] < 0 || S.save_step[s] >= S.K || !T5.dense || !T5.zend || S.lacc) return fail(h, MGN_E_STATE, "tsit5_sweep: bad dense-save plan");
+    std::vector<std::vector<int32_t>> inner(S.theta ? (size_t)S.K : 0);
+    for (int32_t s = 0; S.theta && s < S.n_saves; ++s)
+        if (S.theta[s] >= 0.0) {
+            if (S.save_step[s] < 0 || S.save_step[s] >= S.K || !S.dense || !S.zend || S.lacc) return fail(h, MGN_E_STATE, "erk_sweep: bad dense-save plan");
             inner[(size_t)S.save_step[s]].push_back(s);
         }
     auto has_inner = [&](int64_t k) { return k >= 0 && k < (int64_t)inner.size() && !inner[(size_t)k].empty(); };
-    // the launches of step m's interpolated saves: T5.dense <- its sums, the VJP's lambda slot (+)= h_m W_7
+    // the launches of step m's interpolated saves: S.dense <- its sums, the VJP's lambda slot (+)= h_m W_7
     auto dense = [&](int64_t m, bool kbar_add) -> int {
         const std::vector<int32_t>& sv = inner[(size_t)m];
         for (size_t j0 = 0; j0 < sv.size(); j0 += TSIT5_DENSE_MAX) {
@@ -2066,24 +2051,24 @@ int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
             for (int j = 0; j < p.ns; ++j) {
                 const int32_t s = sv[j0 + j];
                 double b[7];
-                if (mgn_tsit5_interp_weights(T5.theta[s], b) != MGN_OK) return fail(h, MGN_E_STATE, "tsit5_sweep: theta = %g of save %d", T5.theta[s], s);
+                if (mgn_tsit5_interp_weights(S.theta[s], b) != MGN_OK) return fail(h, MGN_E_STATE, "erk_sweep: theta = %g of save %d", S.theta[s], s);
                 for (int i = 0; i < 7; ++i) p.b[j][i] = (float)b[i];
                 p.xs[j] = S.saves + (size_t)s * W.n; p.gt[j] = S.gt + (size_t)s * W.n;
                 p.part[j] = S.part + (size_t)W.slot++ * 2 * W.nb;
             }
             p.ls = S.loss_scale; p.vm = W.vm; p.gscale = W.gscale;
-            p.w = T5.dense; p.kbar = W.io + W.n; p.h = (float)T5.h[m];
+            p.w = S.dense; p.kbar = W.io + W.n; p.h = (float)S.h[m];
             p.accumulate = j0 > 0; p.kbar_add = kbar_add || j0 > 0;
             p.N = W.N; p.O = W.O; p.nblk = W.nb;
             HIPCHK(h, launch_tsit5_dense_adjoint(p, h->stream));
         }
         return MGN_OK;
     };
-    auto seed6 = [&](int64_t k) { return k > 0 ? (float)(T5.h[k - 1] * T5.b[sp - 1]) : 0.f; };      // the last stage's seed: h b_s lam
+    auto seed6 = [&](int64_t k) { return k > 0 ? (float)(S.h[k - 1] * S.b[sp - 1]) : 0.f; };      // the last stage's seed: h b_s lam
     bool first = true;                          // no VJP has run yet (the first one assigns the gradient accumulator)
     if (has_inner(S.K - 1)) {
         if (int rc = dense(S.K - 1, false)) return rc;
-        if (int rc = W.vjp(T5.zend, true)) return rc;
+        if (int rc = W.vjp(S.zend, true)) return rc;
         first = false;
     }
     if (int rc = W.adjoint(S.K, !first, seed6(S.K))) return rc;
@@ -2094,21 +2079,21 @@ int tsit5_sweep(mgn_engine* h, const SolverSweep& S, const Tsit5Sweep& T5) {
                 ErkSeedArgs p{};
                 p.xbar = i < sp ? W.io : nullptr;
                 p.inflow = S.inflow;
-                p.ybar = T5.ybar;
+                p.ybar = S.ybar;
                 p.a = S.a;
                 p.kbar = W.io + W.n;
-                p.cb = (float)(T5.h[k] * T5.b[i - 1]);
-                for (int j = i + 1; j <= sp; ++j) p.ca[j - 1] = (float)(T5.h[k] * T5.A[j - 1][i - 1]);
+                p.cb = (float)(S.h[k] * S.b[i - 1]);
+                for (int j = i + 1; j <= sp; ++j) p.ca[j - 1] = (float)(S.h[k] * S.A[j - 1][i - 1]);
                 p.i = i;
                 p.s = sp;
                 p.N = W.N;
                 p.O = W.O;
-                if (di) { p.w = T5.dense + (size_t)i * W.n; p.g = i == 1 ? T5.dense : nullptr; p.hw = (float)T5.h[k]; }
+                if (di) { p.w = S.dense + (size_t)i * W.n; p.g = i == 1 ? S.dense : nullptr; p.hw = (float)S.h[k]; }
                 HIPCHK(h, launch_erk_stage_seed(p, h->stream));
             }
             if (i == 1 && has_inner(k - 1))
                 if (int rc = dense(k - 1, true)) return rc;
-            if (int rc = W.vjp(T5.steps[k] + (size_t)(i - 1) * W.n, first)) return rc;
+            if (int rc = W.vjp(S.steps[k] + (size_t)(i - 1) * W.n, first)) return rc;
             first = false;
         }
         if (int rc = W.adjoint(k, true, seed6(k))) return rc;

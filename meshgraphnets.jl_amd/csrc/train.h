@@ -263,8 +263,9 @@ int64_t replica_fold_stride(int64_t n);
 hipError_t launch_replica_fold(const float* all, int P, int64_t n, const ReplicaFoldW& w, uint64_t active, float* out, hipStream_t s);
 #pragma GCC visibility pop
 
-// solver-based training (mgn_solver_grad), one step k of the reverse sweep of a fixed-step Euler solve, per element of the [N][O] state:
+// solver-based training (mgn_solver_grad*, mgn_shooting_grad), state k of the reverse sweep (erk_sweep), per element of the [N][O] state:
 //   a <- a + (xbar ? (inflow[n] ? 0 : xbar) : 0) + (gt ? -gscale ls[o]^2 (gt - xs) vm[n] : 0) + (ct ? cw sign(xend - ct) : 0);  lam <- dt a
+// (dt: the seed factor of the last stage of the step before, h_{k-1} b_s; Euler: its dt)
 // part (may be null): [2][solver_adjoint_blocks] doubles -- per block the sum of (ls (gt - xs))^2 vm, then of |xend - ct|
 struct SolverAdjArgs {
     float* a; float* lam; const float* xbar; const uint8_t* inflow;
@@ -275,7 +276,7 @@ struct SolverAdjArgs {
 };
 int solver_adjoint_blocks(int64_t N, int O);
 hipError_t launch_solver_adjoint(const SolverAdjArgs& p, hipStream_t s);
-// solver-based training with an explicit Runge-Kutta tableau of s <= 6 active stages (mgn_solver_grad_tsit5: s = 6; mgn_solver_grad_erk),
+// solver-based training with an explicit Runge-Kutta tableau of s <= 6 active stages (mgn_solver_grad: s = 1, no launch; mgn_solver_grad_tsit5: s = 6; mgn_solver_grad_erk),
 // stage i (1 .. s - 1) of the reverse pass of one step, per element of the [N][O] state, before the VJP of stage i:
 //   ybar_{i+1} <- inflow[n] ? 0 : xbar  (the VJP of stage i + 1 just finished);   kbar <- cb lam + sum_{i<j<=s} ca[j - 1] ybar_j
 //   (cb = h b[i], ca[j - 1] = h A[j][i]);   i = 1: lam <- lam + sum_{j=2..s} ybar_j as well.   ybar: [5][N][O], ybar_j at j - 2.

@@ -388,6 +388,22 @@ def test_launch_state_under_eight_threads(tmp_path):
     assert out.returncode == 0 and "launch_state OK" in out.stdout, out.stdout + out.stderr
 
 
+def test_solve_planning_on_the_host(tmp_path):
+    """mgn_solve.cpp's host-only planning -- fixed_grid, the frame plan of mgn_shooting_grad for the Euler and Tsit5 tableaux against the
+    loops it was first written with, carve_solve's offsets for one and seven stages: tests/c_abi/solve_plan.cpp, a stand-alone program
+    that needs neither the library nor a GPU."""
+    import shutil
+    import subprocess
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"       # (as build.py finds it; only its headers are used)
+    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")
+    src = os.path.join(ROOT, "tests", "c_abi", "solve_plan.cpp")
+    exe = str(tmp_path / "solve_plan")
+    subprocess.check_call(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", rocm_include, "-I", os.path.join(ROOT, "include"),
+                           "-ffunction-sections", "-fdata-sections", src, "-Wl,--gc-sections", "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "solve_plan OK" in out.stdout, out.stdout + out.stderr
+
+
 def test_integration_doc_names_every_symbol(lib_built):
     """INTEGRATION.md maps every entry point of include/mgn_hip.h to the reference interface it replaces: no symbol may be
     missing from it (a slash list such as `mgn_fwd_upload/encode/decode` counts)."""

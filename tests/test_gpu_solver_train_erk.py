@@ -1,6 +1,6 @@
 """mgn_solver_grad_erk (Engine.solver_grad_erk): the loss and discrete-adjoint gradient of one fixed-step solve with an explicit
 Runge-Kutta tableau on the device, against mgn_solver_grad_tsit5 bit for bit for the Tsit5 tableau (the same loop and the same
-table-driven sweep, handed the same coefficients), against tests/erk_ref.py's erk_adjoint composed from mgn_ode_step / mgn_ode_vjp on
+table-driven sweep, handed the same coefficients) and against mgn_solver_grad bit for bit for the Euler tableau, against tests/erk_ref.py's erk_adjoint composed from mgn_ode_step / mgn_ode_vjp on
 the same engine and from the float64 oracle, and against Engine.rollout's solution.  Fixtures: test_gpu_solver_train.problem (the
 150-point cylinder, L = 64, mps = 2, K = 4 steps of 0.01), and 151 points where N * O is no multiple of four (the stage-seed kernel's
 scalar form).  Tolerances: those of tests/test_gpu_solver_train_tsit5.py's fixed-step cases.  Run on the MI355X with `-m gpu`.
@@ -62,6 +62,26 @@ def test_tsit5_tableau_returns_the_bits_of_solver_grad_tsit5(n_points, factor):
     for key in ("n_accept", "n_reject", "n_rhs", "n_steps", "stored_bytes"):
         assert st[key] == st_r[key], key
     assert np.abs(gs).max() > 0 and np.isfinite(gs).all()
+
+
+@pytest.mark.parametrize("factor,inflow,full", [(1, False, False), (2, False, False), (1, True, False), (2, True, False), (2, True, True)])
+def test_euler_tableau_returns_the_bits_of_solver_grad(factor, inflow, full):
+    """two save intervals of 2 / factor steps each (K = 2 and 4); full: loss_scale, val_mask and the continuity term as well.  The two
+    entry points differ in their checks and in what they ask of the handle, not in a bit of what they return"""
+    P = prob()
+    eng, gt = P["eng"], P["gt"][:3]
+    t1, dt = float(F32(2 * SDT)), SDT / factor
+    kw = dict(want_pred=True)
+    if inflow:
+        kw["inflow_mask"], kw["inflow_data"] = inflow_of(P)
+    if full:
+        ct = (gt[-1] + 0.3 * np.random.default_rng(5).standard_normal(gt[-1].shape)).astype(F32)
+        kw.update(val_mask=P["vm"], loss_scale=P["ns"], cont_target=ct, cont_weight=0.01)
+    gs_r, loss_r, pred_r = eng.solver_grad(gt[0], P["onehot"], P["ef_raw"], gt, 0.0, t1, dt, SDT, 3, **kw)
+    gs, loss, st = eng.solver_grad_erk(erk_tableau("Euler"), gt[0], P["onehot"], P["ef_raw"], gt, 0.0, t1, SDT, 3, dt, **kw)
+    assert np.float32(loss).tobytes() == np.float32(loss_r).tobytes() and same_bits(gs, gs_r) and same_bits(st["pred"], pred_r)
+    assert (st["n_accept"], st["n_reject"], st["n_rhs"], st["n_steps"]) == (2 * factor, 0, 2 * factor, 2 * factor)
+    assert np.abs(gs).max() > 0 and np.isfinite(gs).all() and loss > 0
 
 
 # ---- C.2: the other methods against the host composition and the float64 oracle -------------------------------------------------------
