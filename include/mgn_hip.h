@@ -72,6 +72,15 @@ typedef struct mgn_config {
                            /* mgn_rollout, mgn_processor_steps_dev (the resident latents pass through the same driver as rows), and in     */
                            /* both directions behind mgn_step, mgn_forward_vjp, mgn_ode_vjp: fp32, one partition, one edge set.  The staged */
                            /* per-step calls of the fused kernels (mgn_proc_*, mgn_fwd_*) answer MGN_E_UNSUPPORTED                          */
+    /* Widths.  Fn, Fe, Fe2, O >= 1.  The inference entry points on ln_dims = MGN_LN_ROWS (mgn_forward, mgn_ode_step, mgn_set_static,   */
+    /* mgn_rollout*, mgn_rollout_eval*, the staged mgn_fwd_* calls) serve ANY width: the first layers read their inputs feature by     */
+    /* feature, the decoder writes its O columns one by one.  Everything that computes on the training kernels needs                   */
+    /* Fn, Fe, Fe2, O <= L -- they pad every input to L columns and hold the decoder's output in rows of L: the training entry points  */
+    /* (mgn_step, mgn_step_datapoint(s) and the mgn_train_* / mgn_datapoint_export calls around them, mgn_ode_vjp, mgn_forward_vjp,     */
+    /* mgn_solver_grad, mgn_solver_grad_tsit5, mgn_solver_grad_erk, mgn_shooting_grad, their mgn_group_* forms) answer                 */
+    /* MGN_E_UNSUPPORTED naming the width and L, before the device check (a MGN_DEVICE_NONE handle answers it too), any allocation,   */
+    /* launch or collective; the handle stays usable.  ln_dims = MGN_LN_ALL runs ALL of its compute on those kernels, inference        */
+    /* included: mgn_create answers MGN_E_ARG for such a configuration with a width above L.                                          */
 } mgn_config;
 
 typedef enum { MGN_LN_VAR_EPS = 0, MGN_LN_STD_EPS = 1 } mgn_ln_mode;
@@ -435,7 +444,8 @@ int mgn_rollout_eval_erk(mgn_handle* h, mgn_rollout_desc* d, mgn_rollout_eval_de
  * gt [n_saves][N][O].  grads [n_grads = mgn_param_count] receives the EXACT gradient of that loss of the computed Euler solution (the
  * discrete adjoint, what ReverseDiffAdjoint / ZygoteAdjoint give -- not InterpolatingAdjoint's continuous approximation); d->out, if not
  * NULL, the predicted saves; d->n_accept, d->n_rhs are filled.  gt, cont_target and grads may be host or device pointers (hipMemcpyDefault);
- * the others follow mgn_rollout.  fp32, one partition, one edge set, hidden_layers 1 .. 4, both ln_mode and ln_dims values.  Memory: the
+ * the others follow mgn_rollout.  fp32, one partition, one edge set, hidden_layers 1 .. 4, both ln_mode and ln_dims values,
+ * Fn, Fe, O <= L (MGN_E_UNSUPPORTED above: mgn_config, "Widths"; the same for mgn_solver_grad_tsit5, _erk and mgn_shooting_grad).  Memory: the
  * (K + 1) N O floats of the states before every step (4.8 GB for 1 M nodes over 600 steps); MGN_E_OOM when they do not fit.
  * Bitwise repeatable (reductions in a fixed order).                                                                                  */
 int mgn_solver_grad(mgn_handle* h, mgn_rollout_desc* d, const float* gt /* [n_saves][N][O] */, const float* loss_scale /* [O] or NULL */,
@@ -551,6 +561,10 @@ int mgn_shooting_grad(mgn_handle* h, mgn_rollout_desc* d, mgn_shooting_desc* s, 
  *   Optimisers.update(opt_state, ps, gs) keeps working on the Julia side;  *loss: the scalar.
  * fp32; both ln_mode values and both ln_dims values; hidden_layers 1 .. 4; with two edge sets the second set's
  * features are the ones installed by mgn_set_edge_features (as in mgn_forward).
+ * Restrictions on the widths: Fn, Fe, Fe2, O <= L for this and every other training entry point (mgn_step_datapoint, mgn_step_datapoints
+ * and the resident trajectory's calls, mgn_ode_vjp, mgn_forward_vjp, mgn_solver_grad*, mgn_shooting_grad, the mgn_group_* forms): a wider
+ * configuration is answered with MGN_E_UNSUPPORTED, the message naming the width and L, before the device check and before any
+ * allocation, launch or collective (mgn_config, "Widths").  Inference on MGN_LN_ROWS has no such bound.
  * Partitioned mesh (nranks > 1, after mgn_comm_init; one edge set): every rank calls with the GLOBAL nf [N][Fn], ef [E][Fe],
  * target [N][O] and the mask of the whole mesh (global node ids) and returns the COMPLETE gradient and the loss of the whole mesh,
  * the same bits on every rank.  Each rank computes on the rows it owns plus its halo rows and takes the mask entries it owns (the

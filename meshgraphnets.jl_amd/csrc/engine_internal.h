@@ -227,6 +227,9 @@ namespace mgn {
 
 int fail(mgn_engine* h, int code, const char* fmt, ...);
 int need(mgn_engine* h, bool params, bool graph, bool packed = true, bool lnall_ok = false);   // packed = false: the caller reads h->params only (training, get_params)
+// Fn, Fe, Fe2, O <= L on the training kernels: the first width above L, or null; and the MGN_E_UNSUPPORTED of the training entry points
+const char* width_over_L(const mgn_config& c, int* w);
+int width_refuse(mgn_engine* h, const char* who);
 int pack_inference_weights(mgn_engine* h);
 // L x L chunk of W (row-major [K][ldw], rows kbase.., all L output columns) -> MFMA fragment order
 void pack_chunk(float* dst, const float* W, int ldw, int kbase, int L);

@@ -42,6 +42,24 @@ int fail(mgn_engine* h, int code, const char* fmt, ...) {
     return code;
 }
 
+// The width rule of everything that computes on the training kernels (mgn_train.cpp, train.hip): they pad every input to L columns
+// (k_affine_pad), describe an encoder's first layer as one block of at most L rows and index the decoder's output in rows of L, so
+// Fn, Fe, Fe2 (with two edge sets) and O are at most L there.  The name of the first width above L (its value in *w), or null.
+const char* width_over_L(const mgn_config& c, int* w) {
+    const struct { const char* name; int v; } ws[] = {{"Fn", c.Fn}, {"Fe", c.Fe}, {"Fe2", c.n_edge_sets == 2 ? c.Fe2 : 0}, {"O", c.O}};
+    for (const auto& x : ws)
+        if (x.v > c.L) { *w = x.v; return x.name; }
+    return nullptr;
+}
+// ... as the refusal of a training entry point: before the device check (a host-only handle answers it too), any allocation, launch or
+// collective -- every rank of a group holds the same widths, so all of them stop here
+int width_refuse(mgn_engine* h, const char* who) {
+    int w = 0;
+    if (const char* name = width_over_L(h->cfg, &w))
+        return fail(h, MGN_E_UNSUPPORTED, "%s: %s = %d exceeds L = %d: the training kernels take Fn, Fe, Fe2, O <= L (inference with ln_dims = MGN_LN_ROWS serves any width)", who, name, w, h->cfg.L);
+    return MGN_OK;
+}
+
 }  // namespace mgn
 
 namespace {
@@ -62,6 +80,13 @@ bool cfg_ok(const mgn_config* c, std::string& why) {
     if (c->ln_dims == MGN_LN_ALL && (c->dtype != MGN_F32 || c->nranks != 1 || c->n_edge_sets > 1)) {
         why = "ln_dims = MGN_LN_ALL (whole-array LayerNorm) runs in fp32 on one partition with one edge set";
         return false;
+    }
+    if (c->ln_dims == MGN_LN_ALL) {                        // (every compute path of that mode runs on the training kernels: lnall_*)
+        int w = 0;
+        if (const char* name = mgn::width_over_L(*c, &w)) {
+            why = std::string("ln_dims = MGN_LN_ALL computes on the training kernels, which take Fn, Fe, Fe2, O <= L: ") + name + " = " + std::to_string(w) + ", L = " + std::to_string(c->L);
+            return false;
+        }
     }
     return true;
 }

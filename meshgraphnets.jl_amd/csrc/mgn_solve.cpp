@@ -770,6 +770,7 @@ int upload_statics(mgn_handle* h, const mgn_rollout_desc* d, const float* x0, ch
 
 // the handle's state that solver-based training needs: a device handle, one partition, fp32, one edge set, parameters and a graph
 int solver_state_checks(mgn_handle* h, const char* who, bool partitions = false) {
+    if (int rc = width_refuse(h, who)) return rc;
     if (h->host_only) return fail(h, MGN_E_HIP, "host-only handle (MGN_DEVICE_NONE): no compute path; create the handle on a HIP device");
     const mgn_config& c = h->cfg;
     if (c.nranks != 1 && !partitions) return fail(h, MGN_E_STATE, "%s drives one partition", who);

@@ -190,6 +190,10 @@ namespace {
 // launches: no host pass over the parameters, no upload of them unless the host copy is the newer one (mgn_set_params: dev_params), no
 // synchronisation.  Both doors for parameters end in the same buffer and the same kernels: the same bits.
 int pack_describe(mgn_engine* h) {
+    // an encoder's first layer is ONE block of at most L rows below (nin = m.in / L is the processor MLPs' 2 L and 3 L), the decoder's
+    // last layer at most L columns: no caller comes here with a wider configuration (train_prepare and mgn_create's MGN_LN_ALL
+    // check refuse it first); should one ever, it is turned away before a job is described
+    if (int rc = width_refuse(h, "the training weight layout")) return rc;
     TrainState& T = *h->train;
     const mgn_config& c = h->cfg;
     const int L = c.L;
@@ -568,6 +572,7 @@ struct TrainJob {
 
 // partitions: the entry point runs on a partitioned mesh (mgn_step); every check comes before the first collective
 int train_prepare(mgn_handle* h, const char* who, size_t n_grads, bool partitions = false) {
+    if (int rc = width_refuse(h, who)) return rc;
     if (int rc = need(h, true, true, false, true)) return rc;    // (the training kernels pack their own weights from h->params)
     const mgn_config& c = h->cfg;
     if (c.nranks != 1 && !partitions) return fail(h, MGN_E_STATE, "%s drives one partition", who);
@@ -799,6 +804,7 @@ int datapoints_stage(mgn_engine* h, mgn_engine* c, const int32_t* ts, int32_t B,
 }
 // what every entry point of the datapoint family asks of the handle before it looks at its arguments
 int datapoint_need(mgn_handle* h, const char* who, bool graph, bool trajectory) {
+    if (int rc = width_refuse(h, who)) return rc;
     if (int rc = need(h, false, graph)) return rc;
     if (h->cfg.nranks != 1 && h->nsets != 1) return fail(h, MGN_E_UNSUPPORTED, "%s on a partitioned mesh takes one edge set", who);
     if (h->cfg.nranks != 1 && !h->comm)

@@ -21,6 +21,7 @@ import mgn_oracle as orc
 from mgn_amd import reference_api as ra
 from mgn_amd import synth
 from mgn_amd._capi import f32, i32
+from train_checks import affine_ulps
 from util import rel_max, renumbered, scatter_labels, set_renumber, small_mesh
 
 pytestmark = pytest.mark.gpu
@@ -124,13 +125,6 @@ def prob():
 
 def same_bits(a, b):
     return np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
-
-
-def affine_ulps(y, ref, x, scale, shift):
-    """|y - ref| in ulps of the affine map's working magnitude (module docstring); returns the worst."""
-    x, scale, shift = np.asarray(x, F32), np.asarray(scale, F32), np.asarray(shift, F32)
-    mag = np.maximum(np.maximum(np.abs(x * scale), np.abs(shift)), np.maximum(np.abs(ref), np.abs(y)))
-    return float((np.abs(y.astype(np.float64) - ref.astype(np.float64)) / np.spacing(mag.astype(F32)).astype(np.float64)).max())
 
 
 def ulps(a, b):

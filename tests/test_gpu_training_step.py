@@ -8,28 +8,10 @@ import torch   # before the engine's first HIP call (device-array test), or torc
 import mgn_oracle as orc
 import mgn_amd
 from mgn_amd import synth
+from train_checks import TOL_GRAD, TOL_LOSS, check_grads   # noqa: F401  (other test files take them from here)
 from util import cfg_dict, engine_for, make_params, rel_max, small_mesh
 
 pytestmark = pytest.mark.gpu
-
-TOL_LOSS = 1e-5      # relative
-TOL_GRAD = 2e-4      # max|d| / max|ref| per parameter tensor (fp32 reductions over up to ~12k rows, 15 steps deep)
-
-
-def check_grads(gs, ref, cfg, tol=TOL_GRAD):
-    off, worst = 0, ("", 0.0)
-    for bname, tensors in orc.model_layout(cfg["Fn"], cfg["Fe"], cfg["O"], cfg["L"], 2, cfg["mps"]):
-        for tname, shape in tensors:
-            n = int(np.prod(shape))
-            a, b = gs[off:off + n], ref[off:off + n]
-            scale = max(np.abs(b).max(), 1e-3 * np.abs(ref).max())
-            err = float(np.abs(a - b).max() / scale)
-            if err > worst[1]:
-                worst = (f"{bname}.{tname}", err)
-            off += n
-    assert off == ref.size
-    assert worst[1] <= tol, worst
-    return worst
 
 
 def problem(cfg, pos, s, r, seed=0, frac=0.6):
